@@ -457,6 +457,33 @@ def sharded_full_path(ribbit_amd, dist, torch, sc, seq: bytes, bases: int, rank:
                     "merges and dispatch order on rank 0, refinement sharded by dispatched seed over the ranks"}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, runs) -> dict:
+    """--dump-outputs: the run records the timed path handed its caller in its last step (start, end, mlen, term of each,
+    in the order received) as DIR/runs_<field>.npy, float64 (exact for int32).  Above DUMP_MAX_BYTES a fixed, seeded sample
+    of the records is written instead, with its indices in DIR/runs_sample_index.npy.  -> {name: shape}"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    runs = np.array(runs, copy=True)
+    names = runs.dtype.names
+    n = len(runs)
+    per_run = 8 * len(names)
+    arrays = {}
+    budget = DUMP_MAX_BYTES - 4096                       # (the .npy headers)
+    if n * per_run > budget:
+        keep = budget // (per_run + 8)
+        idx = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        runs = runs[idx]
+        arrays["runs_sample_index"] = idx.astype(np.float64)
+    for f in names:
+        arrays[f"runs_{f}"] = runs[f].astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main():
     global M_HI
     ap = argparse.ArgumentParser()
@@ -489,7 +516,11 @@ def main():
     ap.add_argument("--stage-kernels", action="store_true",
                     help="after the timed region, run the substitution and anchored scan kernels once on the workload record "
                          "(so that a profiler pass over this command sees all three scan kernels at the same size)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the run records of the last timed step to DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.max_motif != M_HI:
         M_HI = args.max_motif
         args.chr1_bases = 0          # the chromosome leg and its digest are for -M 100
@@ -748,6 +779,9 @@ def main():
             device_gather = False
     dt, runs, kernel_ms, pack_ms, gpu_ms, counts, used_transport = timed_region(transports[0])
     nruns, nevents = counts
+    if args.dump_outputs and rank == 0:
+        # before anything else runs on the handles: on one GPU `runs` is a view of the library's result buffer
+        dump_outputs(args.dump_outputs, runs if world == 1 else np.concatenate(runs))
     headline_ng = T["ng"] is not None
     other = {}
 

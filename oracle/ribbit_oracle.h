@@ -105,8 +105,12 @@ int64_t rbo_refine_jobs(rbo_ctx *c, const rbo_refine_params_t *prm, const rbo_jo
 
 /* Rows f1/f4: the BED text processSequence writes for this record (fasta_utils.cpp:187-242 ->
  * processSeedMotifWise / processSeed).  Alignments are computed by the REFERENCE's own SSW
- * (oracle/_ref/libssw_ref.so); everything around them is restated.  seq = the record's bases. */
+ * (oracle/_ref/libssw_ref.so) when it was built, else by rbo_set_ssw_align's function; everything around them is restated.  seq = the record's bases. */
 const char *rbo_refine_bed(rbo_ctx *c, const rbo_refine_params_t *prm, const char *seq, const char *seq_id, int64_t *len);
+/* 1 when oracle/_ref/libssw_ref.so loads.  Without it rbo_refine_bed aligns with the function set here: ribbit_ssw_align
+ * (include/ribbit_hip.h), the product's host SSW, which tests/test_ssw.py pins to the reference library's stored outputs. */
+int rbo_have_ref_ssw(void);
+void rbo_set_ssw_align(void *ribbit_ssw_align_fn);
 
 #ifdef __cplusplus
 }

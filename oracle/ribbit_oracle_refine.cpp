@@ -328,8 +328,10 @@ int64_t rbo_refine_jobs(rbo_ctx *c, const rbo_refine_params_t *prm, const rbo_jo
 
 /* ===================================================================================================
  * Rows f1 / f4: alignment, CIGAR processing and BED rows.  The alignment itself is NOT restated here:
- * the oracle calls the reference's own vendored SSW, compiled from /root/reference into
- * oracle/_ref/libssw_ref.so (entry point ref_ssw_align, oracle/ssw_ref_shim.cpp).
+ * the oracle calls the reference's own vendored SSW, compiled from the reference sources into
+ * oracle/_ref/libssw_ref.so (entry point ref_ssw_align, oracle/ssw_ref_shim.cpp) where they were present at
+ * build time.  Without that library the caller hands in ribbit_ssw_align (rbo_set_ssw_align), the product's host
+ * SSW, whose every field and CIGAR tests/test_ssw.py pins to the reference library's stored outputs.
  * =================================================================================================== */
 namespace {
 
@@ -338,6 +340,9 @@ struct ref_ssw_result {
     int32_t flag, cigar_len;
 };
 typedef int (*ref_ssw_fn)(const char *, const char *, int, int, ref_ssw_result *, char *, int);
+/* ribbit_ssw_align's signature (include/ribbit_hip.h); RibbitAlignment has ref_ssw_result's layout */
+typedef int (*product_ssw_fn)(const char *, int32_t, const char *, int32_t, int32_t, ref_ssw_result *, char *, size_t);
+product_ssw_fn g_product_ssw = nullptr;
 
 ref_ssw_fn load_ref_ssw() {
     static ref_ssw_fn fn = nullptr;
@@ -360,10 +365,14 @@ ref_ssw_fn load_ref_ssw() {
 std::string align_cigar(const std::string &query, const std::string &ref, int ref_len, std::string &stale) {
     if (query.empty()) return stale;
     ref_ssw_fn fn = load_ref_ssw();
-    if (!fn) { std::fprintf(stderr, "oracle: oracle/_ref/libssw_ref.so is missing\n"); std::abort(); }
+    if (!fn && !g_product_ssw) {
+        std::fprintf(stderr, "oracle: oracle/_ref/libssw_ref.so is missing and no alignment function was set (rbo_set_ssw_align)\n");
+        std::abort();
+    }
     ref_ssw_result r;
     std::vector<char> buf(16 * (query.size() + ref.size()) + 64);
-    fn(query.c_str(), ref.c_str(), ref_len, 15, &r, buf.data(), (int)buf.size());
+    if (fn) fn(query.c_str(), ref.c_str(), ref_len, 15, &r, buf.data(), (int)buf.size());
+    else g_product_ssw(query.data(), (int32_t)query.size(), ref.c_str(), ref_len, 15, &r, buf.data(), buf.size());
     stale = buf.data();
     return stale;
 }
@@ -583,5 +592,9 @@ const char *rbo_refine_bed(rbo_ctx *c, const rbo_refine_params_t *prm, const cha
     *len = (int64_t)text.size();
     return text.c_str();
 }
+
+int rbo_have_ref_ssw(void) { return load_ref_ssw() != nullptr; }
+
+void rbo_set_ssw_align(void *fn) { g_product_ssw = (product_ssw_fn)fn; }
 
 }  // extern "C"

@@ -70,8 +70,26 @@ def lib():
         L.rbo_refine_bed.argtypes = [C.c_void_p, C.POINTER(RefineParams), C.c_char_p, C.c_char_p, C.POINTER(C.c_int64)]
         L.rbo_range_count.restype = C.c_int
         L.rbo_range_count.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        L.rbo_have_ref_ssw.restype = C.c_int
+        L.rbo_have_ref_ssw.argtypes = []
+        L.rbo_set_ssw_align.restype = None
+        L.rbo_set_ssw_align.argtypes = [C.c_void_p]
         _lib = L
     return _lib
+
+
+_ssw_ready = False
+
+
+def _ensure_ssw(L):
+    """rbo_refine_bed aligns with the reference library (oracle/_ref/libssw_ref.so) where it was built; elsewhere with the
+    product's host ribbit_ssw_align, whose outputs tests/test_ssw.py pins to the reference library's stored ones"""
+    global _ssw_ready
+    if not _ssw_ready:
+        if not L.rbo_have_ref_ssw():
+            import ribbit_amd
+            L.rbo_set_ssw_align(C.cast(ribbit_amd.load_library().ribbit_ssw_align, C.c_void_p))
+        _ssw_ready = True
 
 
 def _copy(ptr, n, dt):
@@ -176,7 +194,7 @@ class Oracle:
         return arr, (C.string_at(pool.value, size) if size else b"")
 
     def refine_bed(self, seq_id: str = "seq", params=None) -> str:
-        """BED text of this record (needs run_dispatch()); alignments by the reference's own SSW (oracle/_ref)"""
+        """BED text of this record (needs run_dispatch()); alignments by the reference's own SSW (oracle/_ref) if built (_ensure_ssw)"""
         rp = params
         if rp is None:
             rp = RefineParams()
@@ -189,6 +207,7 @@ class Oracle:
         if rp is None:
             rp = RefineParams()
             self._L.rbo_refine_params_default(C.byref(rp), self.m_lo, self.m_hi)
+        _ensure_ssw(self._L)
         n = C.c_int64()
         p = self._L.rbo_refine_bed(self._h, C.byref(rp), self.seq, seq_id.encode(), C.byref(n))
         return C.string_at(p, n.value)

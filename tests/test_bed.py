@@ -1,7 +1,6 @@
 """Rows f1/f4 on CPU: the product's BED rows (own refinement scans, own SSW, own CIGAR processing:
 ribbit_host_refine_bed) against the oracle's (restated refinement around the REFERENCE's own SSW from
-oracle/_ref) on the oracle's dispatch lists.  Text-identical, purity column included."""
-import os
+oracle/_ref where it was built, oracle_lib._ensure_ssw) on the oracle's dispatch lists.  Text-identical, purity column included."""
 
 import pytest
 
@@ -9,9 +8,6 @@ import ribbit_amd
 from cases import edge_cases, large_motif_cases, simulated_cases
 from oracle_lib import Oracle
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-pytestmark = pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libssw_ref.so")),
-                                reason="oracle/_ref/libssw_ref.so not built")
 ALL = edge_cases() + simulated_cases() + large_motif_cases()
 
 

@@ -1,6 +1,5 @@
 """CPU fuzz: the oracle's call logs replayed through the product's independently written merges, refinement and
 BED writer on seeded adversarial records (tests/fuzz.py).  Any disagreement prints the seed."""
-import os
 
 import numpy as np
 import pytest
@@ -9,8 +8,6 @@ import ribbit_amd
 from fuzz import fuzz_case
 from oracle_lib import LIST_ANCHORED, LIST_PERFECT, LIST_SUBST, Oracle
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HAVE_REF_SSW = os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libssw_ref.so"))
 
 
 def _seeds(block):
@@ -38,7 +35,7 @@ def test_merges_and_bed_rows_agree_with_the_oracle_on_fuzzed_records(block):
             assert np.array_equal(r["anchored"].view("<i4"), o.seeds(LIST_ANCHORED).view("<i4")), tag
             assert np.array_equal(r["dispatch"].view("<i4"), o.dispatch().view("<i4")), tag
             assert r["guard_hits"] == o.guard_hits(), tag
-            if HAVE_REF_SSW and len(seq):
+            if len(seq):
                 got = ribbit_amd.host_refine_bed(m_lo, m_hi, seq, xa, stride, o.dispatch(), "fz")
                 assert got.split("\n") == o.refine_bed("fz").split("\n"), tag
 
@@ -47,8 +44,6 @@ def test_refinement_with_random_length_and_unit_tables_agrees_with_the_oracle():
     """MINIMUM_LENGTH / PERFECT_UNITS other than the defaults (what -l / --min-units / --perfect-units set)."""
     import ctypes as C
     from oracle_lib import RefineParams as OracleRefineParams, lib as oracle_lib_handle
-    if not HAVE_REF_SSW:
-        pytest.skip("oracle/_ref/libssw_ref.so not built")
     for seed in range(12000, 12040):
         seq, m_lo, m_hi = fuzz_case(seed)
         if len(seq) < 40:
