@@ -507,6 +507,18 @@ int ribbit_hip_debug_pair_events(RibbitHandle *h, const uint64_t *events, size_t
  * makes a scan overflow its regions, after which it is sized for the fullest region and run again. */
 int ribbit_hip_debug_set_event_capacity(RibbitHandle *h, size_t events);
 
+/* Test hook: how the scan kernels split the motif range over the blocks of a tile (gridDim.y).  kernel selects the
+ * perfect scan, the substitution stage's window scan, the anchored stage's planes kernel, its window scan of the composed
+ * planes, or all four; motifs_per_block = 0 restores the automatic split (chosen from the record length), n > 0 gives every
+ * block n motifs (clamped to the number of motifs), a negative value is RIBBIT_E_ARG.  The output of every stage is the same
+ * under every split. */
+enum { RIBBIT_SCAN_PERFECT = 0, RIBBIT_SCAN_SUBST = 1, RIBBIT_SCAN_ANCHORED = 2, RIBBIT_SCAN_XA_WINDOW = 3, RIBBIT_SCAN_KERNELS = 4,
+       RIBBIT_SCAN_ALL = 4 };
+int ribbit_hip_debug_set_scan_split(RibbitHandle *h, int32_t kernel, int32_t motifs_per_block);
+/* Test hook: the split one kernel (not RIBBIT_SCAN_ALL) last ran with on the loaded record: gridDim.y and the motifs per block;
+ * both 0 when it has not run since the record was loaded. */
+int ribbit_hip_debug_last_scan_split(RibbitHandle *h, int32_t kernel, int32_t *grid_y, int32_t *motifs_per_block);
+
 /* Test hook: the window stages' merges run as independent position ranges on host threads (RIBBIT_THREADS, default
  * min(cores, 16)) wherever the call sequence can be cut; this sets the smallest number of calls per range (default 4096). */
 void ribbit_debug_set_merge_min_range(size_t calls);

@@ -51,7 +51,7 @@ ABI_SYMBOLS = [
     "ribbit_hip_xa_words",
     "ribbit_host_perfect_runs_from_events", "ribbit_runs_free", "ribbit_hip_perfect_runs_partial",
     "ribbit_hip_scan_perfect_chunk", "ribbit_hip_host_register", "ribbit_hip_host_unregister",
-    "ribbit_hip_set_host_threads", "ribbit_hip_ssw_passes", "ribbit_hip_ssw_align_jobs", "ribbit_hip_set_timing", "ribbit_hip_debug_set_event_capacity", "ribbit_hip_debug_pair_events", "ribbit_hip_scan_perfect_begin", "ribbit_hip_scan_perfect_end", "ribbit_hip_scan_perfect_wait", "ribbit_hip_scan_perfect_end_device",
+    "ribbit_hip_set_host_threads", "ribbit_hip_ssw_passes", "ribbit_hip_ssw_align_jobs", "ribbit_hip_set_timing", "ribbit_hip_debug_set_event_capacity", "ribbit_hip_debug_set_scan_split", "ribbit_hip_debug_last_scan_split", "ribbit_hip_debug_pair_events", "ribbit_hip_scan_perfect_begin", "ribbit_hip_scan_perfect_end", "ribbit_hip_scan_perfect_wait", "ribbit_hip_scan_perfect_end_device",
     "ribbit_hip_stage_calls_chunk", "ribbit_hip_xa_words_strided", "ribbit_host_merge_chunks",
 ]
 
@@ -98,6 +98,8 @@ class ChunkPart(C.Structure):
 
 
 STAGE_PERFECT, STAGE_SUBST, STAGE_ANCHORED = 0, 1, 2
+# scan kernels of Scanner.debug_set_scan_split (RIBBIT_SCAN_* of include/ribbit_hip.h)
+SCAN_PERFECT, SCAN_SUBST, SCAN_ANCHORED, SCAN_XA_WINDOW, SCAN_ALL = 0, 1, 2, 3, 4
 
 
 def library_path() -> str:
@@ -228,6 +230,8 @@ def load_library():
     L.ribbit_hip_set_host_threads.argtypes = [vp, i32]
     L.ribbit_hip_set_timing.argtypes = [vp, i32]
     L.ribbit_hip_debug_set_event_capacity.argtypes = [vp, C.c_size_t]
+    L.ribbit_hip_debug_set_scan_split.argtypes = [vp, i32, i32]
+    L.ribbit_hip_debug_last_scan_split.argtypes = [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.ribbit_hip_debug_pair_events.argtypes = [vp, vp, C.c_size_t, i64, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]
     L.ribbit_hip_ssw_passes.argtypes = [vp, vp, C.c_size_t, C.c_char_p, C.c_size_t, i32, vp]
     L.ribbit_hip_ssw_align_jobs.argtypes = [vp, vp, C.c_size_t, C.c_char_p, C.c_size_t, i32, vp, vp, C.c_size_t, vp, vp]
@@ -662,6 +666,16 @@ class Scanner:
 
     def debug_set_event_capacity(self, events: int) -> None:
         self._check(self._L.ribbit_hip_debug_set_event_capacity(self._h, events))
+
+    def debug_set_scan_split(self, kernel: int, motifs_per_block: int) -> None:
+        """motifs per block of a scan kernel (SCAN_PERFECT .. SCAN_XA_WINDOW, or SCAN_ALL); 0 = automatic"""
+        self._check(self._L.ribbit_hip_debug_set_scan_split(self._h, kernel, motifs_per_block))
+
+    def debug_last_scan_split(self, kernel: int) -> tuple:
+        """-> (gridDim.y, motifs per block) of the kernel's last launch on the loaded record; (0, 0) if it has not run"""
+        gy, mpb = C.c_int32(), C.c_int32()
+        self._check(self._L.ribbit_hip_debug_last_scan_split(self._h, kernel, C.byref(gy), C.byref(mpb)))
+        return gy.value, mpb.value
 
     def set_timing(self, enabled: bool) -> None:
         self._check(self._L.ribbit_hip_set_timing(self._h, int(enabled)))

@@ -127,6 +127,7 @@ int pack_loaded_ascii(RibbitHandle *h, const uint8_t *dev_ascii, int64_t length)
     h->host_planes_valid = false;
     h->eval_valid = false;
     h->xa_on_device = false;
+    for (rb::ScanSplit &sp : h->last_split) sp = rb::ScanSplit{};
     if (h->xa_copy_pending) { (void)hipEventSynchronize(h->ev_xa); h->xa_copy_pending = false; }
     h->stage_done = STAGE_NONE;
     h->length = length;
@@ -359,6 +360,20 @@ int64_t ribbit_hip_guard_hits(const RibbitHandle *h) { return h ? h->lists.guard
 int ribbit_hip_debug_set_event_capacity(RibbitHandle *h, size_t events) {
     if (!h) return fail(RIBBIT_E_ARG, "null argument");
     h->debug_first_cap = events;
+    return RIBBIT_OK;
+}
+
+int ribbit_hip_debug_set_scan_split(RibbitHandle *h, int32_t kernel, int32_t motifs_per_block) {
+    if (!h || kernel < 0 || kernel > RIBBIT_SCAN_ALL || motifs_per_block < 0) return fail(RIBBIT_E_ARG, "bad argument");
+    for (int k = 0; k < RIBBIT_SCAN_KERNELS; ++k)
+        if (kernel == RIBBIT_SCAN_ALL || kernel == k) h->debug_split[k] = motifs_per_block;
+    return RIBBIT_OK;
+}
+
+int ribbit_hip_debug_last_scan_split(RibbitHandle *h, int32_t kernel, int32_t *grid_y, int32_t *motifs_per_block) {
+    if (!h || !grid_y || !motifs_per_block || kernel < 0 || kernel >= RIBBIT_SCAN_KERNELS) return fail(RIBBIT_E_ARG, "bad argument");
+    *grid_y = h->last_split[kernel].grid_y;
+    *motifs_per_block = h->last_split[kernel].motifs_per_block;
     return RIBBIT_OK;
 }
 

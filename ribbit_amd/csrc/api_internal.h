@@ -170,6 +170,8 @@ struct RibbitHandle {
     rb::PairLaunch pair{};                // the perfect scan in flight (perfect_begin .. perfect_finish)
     bool pair_pending = false;
     size_t debug_first_cap = 0;           // ribbit_hip_debug_set_event_capacity: first guess of the event capacity (tests of the overflow path)
+    int32_t debug_split[RIBBIT_SCAN_KERNELS] = {};   // ribbit_hip_debug_set_scan_split: motifs per block of each scan kernel (0 = automatic)
+    rb::ScanSplit last_split[RIBBIT_SCAN_KERNELS];   // the split each scan kernel last ran with on the loaded record
     bool counters_clean = false;          // d_counters zeroed by the pack kernel and not used since
     bool copy_pending = false;            // result copies enqueued but not yet waited for (ribbit_hip_scan_perfect_end with wait = 0)
     DevBuf<RibbitRun> d_halves;

@@ -31,9 +31,10 @@ int collect_events(RibbitHandle *h, int which) {
         pp.m_lo = h->params.min_motif;
         pp.m_hi = h->params.max_motif;
         pp.ev_cap = (uint32_t)cap;
+        pp.motifs_per_block = h->debug_split[RIBBIT_SCAN_PERFECT];
         HIP_TRY(hipEventRecord(h->ev[2], h->stream));
         if (which != 0) return fail(RIBBIT_E_INTERNAL, "collect_events: the window stages' events stay on the device (window_stage.hip)");
-        rb::launch_scan_perfect(pl, pp, h->d_events.p, h->d_counters.p, h->stream);
+        h->last_split[RIBBIT_SCAN_PERFECT] = rb::launch_scan_perfect(pl, pp, h->d_events.p, h->d_counters.p, h->stream);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(h->ev[3], h->stream));
         rb::launch_compact_events(h->d_events.p, pp.ev_cap, h->d_counters.p, h->d_dense.p, h->stream);
@@ -129,9 +130,10 @@ int perfect_enqueue(RibbitHandle *h, size_t cap) {
     pp.m_lo = h->params.min_motif;
     pp.m_hi = h->params.max_motif;
     pp.ev_cap = (uint32_t)cap;
+    pp.motifs_per_block = h->debug_split[RIBBIT_SCAN_PERFECT];
     pr.region_cap = pp.ev_cap / (uint32_t)rb::EV_SHARDS;
     if (h->timing) HIP_TRY(hipEventRecord(h->ev[2], h->stream));
-    rb::launch_scan_perfect(h->planes(), pp, h->d_events.p, h->d_counters.p, h->stream);
+    h->last_split[RIBBIT_SCAN_PERFECT] = rb::launch_scan_perfect(h->planes(), pp, h->d_events.p, h->d_counters.p, h->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(h->ev[3], h->stream));
     // Everything after the scan (nine small, latency-bound launches, later the result copy) runs on the handle's

@@ -727,7 +727,8 @@ int ribbit_hip_adopt_dispatch(RibbitHandle *h, const RibbitSeed *seeds, size_t n
         pp.m_lo = h->params.min_motif;
         pp.m_hi = h->params.max_motif;
         pp.ev_cap = 0;
-        rb::launch_scan_anchored(h->planes(), pp, h->d_xa.p, h->xa_stride, h->stream);
+        pp.motifs_per_block = h->debug_split[RIBBIT_SCAN_ANCHORED];
+        h->last_split[RIBBIT_SCAN_ANCHORED] = rb::launch_scan_anchored(h->planes(), pp, h->d_xa.p, h->xa_stride, h->stream);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(h->stream));
         h->xa_on_device = true;

@@ -79,15 +79,19 @@ int scan_and_pair_streaks(RibbitHandle *h, int which, uint32_t *n_streaks, int (
         // (two-kernel anchored stage: the planes kernel runs on the first attempt only, so the stage's start mark stays where it
         // was put then -- timer 7 is "both kernels", also when the window scan had to run again with more room)
         if (attempt == 0 || which == 1) HIP_TRY(hipEventRecord(h->ev_stage[which - 1][0], h->stream));
-        if (which == 1) rb::launch_scan_window(pl, pp, 1, h->d_events.p, h->d_counters.p, h->stream);
-        else {
+        if (which == 1) {
+            pp.motifs_per_block = h->debug_split[RIBBIT_SCAN_SUBST];
+            h->last_split[RIBBIT_SCAN_SUBST] = rb::launch_scan_window(pl, pp, 1, h->d_events.p, h->d_counters.p, h->stream);
+        } else {
             if (attempt == 0) {          // the planes do not depend on the event capacity: once
-                rb::launch_scan_anchored(pl, pp, h->d_xa.p, h->xa_stride, h->stream);
+                pp.motifs_per_block = h->debug_split[RIBBIT_SCAN_ANCHORED];
+                h->last_split[RIBBIT_SCAN_ANCHORED] = rb::launch_scan_anchored(pl, pp, h->d_xa.p, h->xa_stride, h->stream);
                 HIP_TRY(hipGetLastError());
                 HIP_TRY(hipEventRecord(h->ev_planes, h->stream));
             }
-            rb::launch_scan_xa_window(pl, pp, h->d_xa.p, h->xa_stride, h->d_events.p, h->d_counters.p, filter ? h->d_tj.p : nullptr,
-                                      filter ? h->d_dropmap.p : nullptr, h->stream);
+            pp.motifs_per_block = h->debug_split[RIBBIT_SCAN_XA_WINDOW];
+            h->last_split[RIBBIT_SCAN_XA_WINDOW] = rb::launch_scan_xa_window(pl, pp, h->d_xa.p, h->xa_stride, h->d_events.p, h->d_counters.p,
+                                                                            filter ? h->d_tj.p : nullptr, filter ? h->d_dropmap.p : nullptr, h->stream);
         }
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(h->ev[3], h->stream));

@@ -17,23 +17,30 @@ void launch_pack(const uint8_t *dev_ascii, int64_t length, uint32_t *hi, uint32_
 struct PerfectLaunch {
     int m_lo, m_hi;        // motif (== shift) range scanned
     uint32_t ev_cap;       // capacity of the event buffer, in events
+    int motifs_per_block = 0;   // split of the motif range over gridDim.y: 0 = the launcher's own choice, n > 0 = n motifs per
+                                // block (clamped to the range; ribbit_hip_debug_set_scan_split)
+};
+// The motif split a scan launcher used: gridDim.y blocks of motifs_per_block motifs each (the last may hold fewer); {0, 0}
+// when it launched nothing.
+struct ScanSplit {
+    int grid_y = 0, motifs_per_block = 0;
 };
 // parse_perfect_shiftxor.cpp:173-223 hot loop -> run START / END events.
 // Events land in EV_SHARDS regions of ev_cap/EV_SHARDS events; counters[] (EV_COUNTER_WORDS words,
 // zeroed by the caller) holds one count per region.  A count above the region size = overflow.
-void launch_scan_perfect(const DevicePlanes &pl, const PerfectLaunch &pp, uint64_t *events, uint32_t *counters,
-                         hipStream_t stream);
+ScanSplit launch_scan_perfect(const DevicePlanes &pl, const PerfectLaunch &pp, uint64_t *events, uint32_t *counters,
+                              hipStream_t stream);
 
 // Window scan (parse_substitute_shiftxor.cpp:430-532 with allowed_mismatches = 1, i.e. threshold 7;
 // parse_anchored_shiftxor.cpp:580-679 with 2, threshold 6) -> pass-streak START / END events at
 // window-start positions.  Same event buffer conventions as launch_scan_perfect.
-void launch_scan_window(const DevicePlanes &pl, const PerfectLaunch &pp, int allowed_mismatches, uint64_t *events,
-                        uint32_t *counters, hipStream_t stream);
+ScanSplit launch_scan_window(const DevicePlanes &pl, const PerfectLaunch &pp, int allowed_mismatches, uint64_t *events,
+                             uint32_t *counters, hipStream_t stream);
 
 // generateAnchoredShiftXORs (parse_anchored_shiftxor.cpp:20-56) + the composition of fasta_utils.cpp:143-161: xa receives the
 // composed planes XA_m, motif-major, xa_stride words per motif.  Tiles are anchored_tile_words(anchored_halo_lanes(pp.m_hi))
 // wide.  Requires pp.m_hi <= ANCHORED_MAX_MOTIF.  launch_scan_xa_window scans the planes.
-void launch_scan_anchored(const DevicePlanes &pl, const PerfectLaunch &pp, uint32_t *xa, int64_t xa_stride, hipStream_t stream);
+ScanSplit launch_scan_anchored(const DevicePlanes &pl, const PerfectLaunch &pp, uint32_t *xa, int64_t xa_stride, hipStream_t stream);
 // Group filter of the window scan below.  tj_table (may be null: no filter): per motif of the launch, the number of positions a
 // group of pass-streaks must span for its call to be able to pass the stage's length filter (<= GROUP_FILTER_MAX; 0: keep every
 // group); groups that cannot, and are not kept for another reason (see the kernel), emit no events and leave their end bit in
@@ -41,8 +48,8 @@ void launch_scan_anchored(const DevicePlanes &pl, const PerfectLaunch &pp, uint3
 constexpr int GROUP_FILTER_MAX = 16;
 // The window scan of processShiftXORsAnchored on composed planes already in HBM (xa, xa_stride words per motif, readable up to
 // word ntiles * TILE_WORDS + 2 of every plane): same events and filter as the fused kernel, tiles of TILE_WORDS words.
-void launch_scan_xa_window(const DevicePlanes &pl, const PerfectLaunch &pp, const uint32_t *xa, int64_t xa_stride, uint64_t *events,
-                           uint32_t *counters, const int32_t *tj_table, uint32_t *dropmap, hipStream_t stream);
+ScanSplit launch_scan_xa_window(const DevicePlanes &pl, const PerfectLaunch &pp, const uint32_t *xa, int64_t xa_stride, uint64_t *events,
+                                uint32_t *counters, const int32_t *tj_table, uint32_t *dropmap, hipStream_t stream);
 
 // Gathers the used part of every region into `dense` (same capacity) in shard order and writes
 // counters[EV_SUMMARY] = total events, counters[EV_SUMMARY+1] = 1 if any region overflowed.

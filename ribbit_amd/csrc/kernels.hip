@@ -648,18 +648,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RB_PERFECT_
     sink_flush(sink, stage, staged, lane);
 }
 
-void launch_scan_perfect(const DevicePlanes &pl, const PerfectLaunch &pp, uint64_t *events, uint32_t *counters,
-                         hipStream_t stream) {
+// The split of a scan's motif range over gridDim.y.  Automatic: want_y blocks per tile, clamped to [1, max_y]; pp.motifs_per_block
+// > 0 overrides it (test hook; every value is safe: no kernel synchronises its block after a wave has run out of motifs).
+static ScanSplit scan_split(const PerfectLaunch &pp, int nm, int64_t want_y, int max_y) {
+    int motifs_per_block;
+    if (pp.motifs_per_block > 0) {
+        motifs_per_block = std::min(pp.motifs_per_block, nm);
+    } else {
+        const int gy = (int)(want_y < 1 ? 1 : (want_y > max_y ? max_y : want_y));
+        motifs_per_block = (nm + gy - 1) / gy;
+    }
+    ScanSplit sp;
+    sp.motifs_per_block = motifs_per_block;
+    sp.grid_y = (nm + motifs_per_block - 1) / motifs_per_block;
+    return sp;
+}
+
+ScanSplit launch_scan_perfect(const DevicePlanes &pl, const PerfectLaunch &pp, uint64_t *events, uint32_t *counters,
+                              hipStream_t stream) {
     const int nm = pp.m_hi - pp.m_lo + 1;
-    if (nm <= 0 || pl.ntiles <= 0) return;
-    // fill the chip: >= ~2048 blocks when the record is short, by splitting the motif range
-    int64_t want_y = (2048 + pl.ntiles - 1) / pl.ntiles;
-    int max_y = (nm + 3) / 4;              // at least one motif per wave
-    int gy = (int)(want_y < 1 ? 1 : (want_y > max_y ? max_y : want_y));
-    int motifs_per_block = (nm + gy - 1) / gy;
-    gy = (nm + motifs_per_block - 1) / motifs_per_block;
-    dim3 grid((unsigned)pl.ntiles, (unsigned)gy);
-    hipLaunchKernelGGL(scan_perfect_kernel, grid, dim3(256), 0, stream, pl, pp, motifs_per_block, events, counters);
+    if (nm <= 0 || pl.ntiles <= 0) return {};
+    // fill the chip: >= ~2048 blocks when the record is short, by splitting the motif range (at least one motif per wave)
+    const ScanSplit sp = scan_split(pp, nm, (2048 + pl.ntiles - 1) / pl.ntiles, (nm + 3) / 4);
+    dim3 grid((unsigned)pl.ntiles, (unsigned)sp.grid_y);
+    hipLaunchKernelGGL(scan_perfect_kernel, grid, dim3(256), 0, stream, pl, pp, sp.motifs_per_block, events, counters);
+    return sp;
 }
 
 // --------------------------------------------------------------------------- window scan
@@ -797,20 +810,17 @@ __global__ __launch_bounds__(256) void scan_window_kernel(DevicePlanes pl, Perfe
     sink_flush(sink, stage, staged, lane);
 }
 
-void launch_scan_window(const DevicePlanes &pl, const PerfectLaunch &pp, int allowed_mismatches, uint64_t *events,
-                        uint32_t *counters, hipStream_t stream) {
+ScanSplit launch_scan_window(const DevicePlanes &pl, const PerfectLaunch &pp, int allowed_mismatches, uint64_t *events,
+                             uint32_t *counters, hipStream_t stream) {
     const int nm = pp.m_hi - pp.m_lo + 1;
-    if (nm <= 0 || pl.ntiles <= 0) return;
-    int64_t want_y = (2048 + pl.ntiles - 1) / pl.ntiles;
-    int max_y = (nm + 3) / 4;
-    int gy = (int)(want_y < 1 ? 1 : (want_y > max_y ? max_y : want_y));
-    int motifs_per_block = (nm + gy - 1) / gy;
-    gy = (nm + motifs_per_block - 1) / motifs_per_block;
-    dim3 grid((unsigned)pl.ntiles, (unsigned)gy);
+    if (nm <= 0 || pl.ntiles <= 0) return {};
+    const ScanSplit sp = scan_split(pp, nm, (2048 + pl.ntiles - 1) / pl.ntiles, (nm + 3) / 4);
+    dim3 grid((unsigned)pl.ntiles, (unsigned)sp.grid_y);
     if (allowed_mismatches == 1)
-        hipLaunchKernelGGL(scan_window_kernel<1>, grid, dim3(256), 0, stream, pl, pp, motifs_per_block, events, counters);
+        hipLaunchKernelGGL(scan_window_kernel<1>, grid, dim3(256), 0, stream, pl, pp, sp.motifs_per_block, events, counters);
     else
-        hipLaunchKernelGGL(scan_window_kernel<2>, grid, dim3(256), 0, stream, pl, pp, motifs_per_block, events, counters);
+        hipLaunchKernelGGL(scan_window_kernel<2>, grid, dim3(256), 0, stream, pl, pp, sp.motifs_per_block, events, counters);
+    return sp;
 }
 
 // ------------------------------------------------------------------------- anchored scan
@@ -1053,20 +1063,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
     }
 }
 
-void launch_scan_anchored(const DevicePlanes &pl, const PerfectLaunch &pp, uint32_t *xa, int64_t xa_stride, hipStream_t stream) {
+ScanSplit launch_scan_anchored(const DevicePlanes &pl, const PerfectLaunch &pp, uint32_t *xa, int64_t xa_stride, hipStream_t stream) {
     const int nm = pp.m_hi - pp.m_lo + 1;
     const int64_t nwords = pl.length / 32 + 1;
     const int hl = anchored_halo_lanes(pp.m_hi);
     const int64_t ntiles = (nwords + anchored_tile_words(hl) - 1) / anchored_tile_words(hl);
-    if (nm <= 0 || ntiles <= 0 || pp.m_hi > ANCHORED_MAX_MOTIF) return;
+    if (nm <= 0 || ntiles <= 0 || pp.m_hi > ANCHORED_MAX_MOTIF) return {};
     // each wave recomputes 4 extra shifts around its motif group, so keep the groups large
-    int64_t want_y = (1024 + ntiles - 1) / ntiles;
-    int max_y = (nm + 31) / 32;
-    int gy = (int)(want_y < 1 ? 1 : (want_y > max_y ? max_y : want_y));
-    int motifs_per_block = (nm + gy - 1) / gy;
-    gy = (nm + motifs_per_block - 1) / motifs_per_block;
-    dim3 grid((unsigned)ntiles, (unsigned)gy);
-    hipLaunchKernelGGL(scan_anchored_kernel, grid, dim3(256), 0, stream, pl, pp, motifs_per_block, hl, xa, xa_stride);
+    const ScanSplit sp = scan_split(pp, nm, (1024 + ntiles - 1) / ntiles, (nm + 31) / 32);
+    dim3 grid((unsigned)ntiles, (unsigned)sp.grid_y);
+    hipLaunchKernelGGL(scan_anchored_kernel, grid, dim3(256), 0, stream, pl, pp, sp.motifs_per_block, hl, xa, xa_stride);
+    return sp;
 }
 
 // ------------------------------------------------------------- window scan of composed planes
@@ -1190,17 +1197,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     }
 }
 
-void launch_scan_xa_window(const DevicePlanes &pl, const PerfectLaunch &pp, const uint32_t *xa, int64_t xa_stride, uint64_t *events,
-                           uint32_t *counters, const int32_t *tj_table, uint32_t *dropmap, hipStream_t stream) {
+ScanSplit launch_scan_xa_window(const DevicePlanes &pl, const PerfectLaunch &pp, const uint32_t *xa, int64_t xa_stride, uint64_t *events,
+                                uint32_t *counters, const int32_t *tj_table, uint32_t *dropmap, hipStream_t stream) {
     const int nm = pp.m_hi - pp.m_lo + 1;
-    if (nm <= 0 || pl.ntiles <= 0) return;
-    int64_t want_y = (2048 + pl.ntiles - 1) / pl.ntiles;
-    int max_y = (nm + 3) / 4;
-    int gy = (int)(want_y < 1 ? 1 : (want_y > max_y ? max_y : want_y));
-    int motifs_per_block = (nm + gy - 1) / gy;
-    gy = (nm + motifs_per_block - 1) / motifs_per_block;
-    hipLaunchKernelGGL(scan_xa_window_kernel, dim3((unsigned)pl.ntiles, (unsigned)gy), dim3(256), 0, stream, pl, pp, motifs_per_block, xa, xa_stride,
+    if (nm <= 0 || pl.ntiles <= 0) return {};
+    const ScanSplit sp = scan_split(pp, nm, (2048 + pl.ntiles - 1) / pl.ntiles, (nm + 3) / 4);
+    hipLaunchKernelGGL(scan_xa_window_kernel, dim3((unsigned)pl.ntiles, (unsigned)sp.grid_y), dim3(256), 0, stream, pl, pp, sp.motifs_per_block, xa, xa_stride,
                        events, counters, tj_table, dropmap);
+    return sp;
 }
 
 // ------------------------------------------------------------------------ event compaction

@@ -103,3 +103,71 @@ def structured_cases():
         ("n_every_1000", bytes(n_every), 2, 40),
         ("mostly_n", mostly_n, 2, 30),
     ]
+
+
+SPLIT_RANGES = [(2, 100), (2, 14), (30, 200), (100, 500), (500, 990)]
+
+
+def scan_split_record(m_lo: int, m_hi: int, length: int, seed: int) -> bytes:
+    """A record of `length` bases for the motif-split tests (test_scan_split_gpu.py): perfect and degenerate tandem repeats whose
+    periods sit on and around multiples of 32 and at both ends of [m_lo, m_hi] (runs, and anchors for the composed planes), N
+    blocks, a 20-kb homopolymer across the first scan-tile edge (all-ones lanes), a degenerate repeat across the second, one still
+    open at the end of the record, and a stretch of short microsatellites (periods 2-16, one every 150-400 bases) dense enough
+    that a wave's candidate queue fills several times over its motifs."""
+    rs = np.random.RandomState(seed)
+    s = seed * 100
+    parts = [_rand(1500, s)]
+    # dense small-motif stretch (the perfect kernel's candidate queue)
+    for i in range(24):
+        p = int(rs.randint(2, 17))
+        parts.append(_rand(int(rs.randint(150, 400)), s + 1 + i))
+        parts.append(_rand(p, s + 50 + i) * (int(rs.randint(60, 120)) // p + 1))
+    parts.append(_rand(max(0, 16384 - sum(map(len, parts)) - 5000), s + 99))
+    parts.append(b"A" * 20000)                                     # crosses 16384 (and every anchored tile edge below it)
+    periods = [31, 32, 33, 63, 64, 65, 95, 96, 97, 127, 128, 129, m_lo, m_lo + 1, (m_lo + m_hi) // 2, m_hi - 1, m_hi]
+    for i, p in enumerate(periods):
+        p = max(p, 2)
+        unit = _rand(p, s + 200 + i)
+        copies = max(3, 240 // p)
+        parts.append(_rand(int(rs.randint(80, 400)), s + 300 + i))
+        parts.append(unit * copies if i % 2 == 0 else _mutate(unit, copies, 0.05, s + 400 + i))
+        if i % 5 == 4:
+            parts.append(b"N" * int(rs.randint(20, 800)))
+    head = b"".join(parts)
+    # a degenerate repeat of period m_hi - 1 across the second scan tile edge (32768), unless the record is too short for it
+    edge_unit = _rand(max(m_hi - 1, 2), s + 500)
+    across = _mutate(edge_unit, max(4, 3000 // len(edge_unit)), 0.04, s + 501)
+    tail_unit = _rand(max((m_lo + m_hi) // 2, 2), s + 502)
+    tail = _mutate(tail_unit, max(4, 1500 // len(tail_unit)), 0.03, s + 503)
+    fill = length - len(head) - len(across) - len(tail)
+    assert fill > 0, "record too short for its parts"
+    pre = max(0, min(fill, 32768 - len(head) - len(across) // 2))
+    seq = head + _rand(pre, s + 504) + across + _rand(fill - pre, s + 505) + tail
+    assert len(seq) == length
+    return seq
+
+
+def anchored_tile_bases(m_hi: int) -> int:
+    """bases per tile of the anchored kernel at max_motif m_hi (device_planes.h: anchored_halo_lanes, anchored_tile_words)"""
+    hl = (2 * (m_hi + 2) + 32 + 255) // 256
+    return (64 - 2 * hl) * 256
+
+
+HALO_STEP_M_HI = [110, 111, 238, 239, 366, 367, 494, 495, 622, 623, 750, 751, 878, 879, 990]
+
+
+def halo_step_record(m_hi: int, length: int) -> bytes:
+    """length bases of random sequence with a degenerate repeat of period m_hi - 3 across every anchored tile edge below the
+    end and a perfect one of period m_hi - 1 still open at the end of the record."""
+    T = anchored_tile_bases(m_hi)
+    unit_edge = _rand(m_hi - 3, m_hi)
+    unit_end = _rand(m_hi - 1, m_hi + 1)
+    tail = unit_end * 3
+    seq = bytearray(_rand(length, length * 7 + m_hi))
+    for k, edge in enumerate(range(T, length - len(tail), T)):
+        rep = _mutate(unit_edge, 4, 0.03, m_hi * 10 + k)
+        a = max(0, edge - len(rep) // 2)
+        b = min(a + len(rep), length - len(tail))
+        seq[a:b] = rep[: b - a]
+    seq[length - len(tail):] = tail
+    return bytes(seq)

@@ -10,7 +10,7 @@ import pytest
 import pyref
 import ribbit_amd
 from cases import edge_cases, simulated_cases
-from oracle_lib import LIST_PERFECT, Oracle
+from oracle_lib import LIST_ANCHORED, LIST_PERFECT, LIST_SUBST, Oracle
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -191,18 +191,32 @@ def test_event_buffer_overflow_is_retried_with_a_larger_buffer():
             assert np.array_equal(a.view("<i4"), b.view("<i4"))
 
 
-@pytest.mark.parametrize("length", [16383, 16384, 16385, 32767, 32768, 32769, 15871, 15872, 15873, 8 * 16384])
+# motif range of a length (default 2..20): 13824 is the anchored tile at 5 halo lanes (max_motif 495..622), 12288 at 8 (879..990)
+TILE_EDGE_RANGE = {13823: (460, 500), 13824: (460, 500), 13825: (460, 500), 12287: (950, 990), 12288: (950, 990), 12289: (950, 990)}
+
+
+@pytest.mark.parametrize("length", [16383, 16384, 16385, 32767, 32768, 32769, 15871, 15872, 15873, 8 * 16384,
+                                    13823, 13824, 13825, 12287, 12288, 12289])
 def test_record_lengths_at_tile_boundaries_with_a_run_open_at_the_end(length):
     """The end-of-sequence event sits at position L: exactly on, just before and just after a tile boundary of the
-    perfect / window kernels (16384 bases) and of the anchored kernel (15872), with a repeat still running there."""
+    perfect / window kernels (16384 bases) and of the anchored kernel (15872 at one halo lane, 13824 at five, 12288 at
+    eight), with a repeat still running there."""
+    m_lo, m_hi = TILE_EDGE_RANGE.get(length, (2, 20))
     rs = np.random.RandomState(length)
-    body = bytes(np.frombuffer(b"ACGT", dtype=np.uint8)[rs.randint(0, 4, size=length - 90)])
-    seq = body + (b"CAT" * 30)
+    # the repeat at the end: CAT for the small motifs, three copies of a unit of period m_hi - 20 for the large ones
+    tail = b"CAT" * 30 if m_hi <= 20 else bytes(np.frombuffer(b"ACGT", dtype=np.uint8)[rs.randint(0, 4, size=m_hi - 20)]) * 3
+    body = bytes(np.frombuffer(b"ACGT", dtype=np.uint8)[rs.randint(0, 4, size=length - len(tail))])
+    seq = body + tail
     assert len(seq) == length
-    with ribbit_amd.Scanner(2, 20) as sc, Oracle(seq, 2, 20) as o:
+    with ribbit_amd.Scanner(m_lo, m_hi) as sc, Oracle(seq, m_lo, m_hi) as o:
         sc.load_record(seq)
         o.run_all()
         assert np.array_equal(sc.perfect_calls().view("<i4"), o.calls(LIST_PERFECT).view("<i4"))
         perfect, subst, anchored = sc.processShiftXORsAnchored()
         assert np.array_equal(perfect.view("<i4"), o.seeds(LIST_PERFECT).view("<i4"))
+        assert np.array_equal(subst.view("<i4"), o.seeds(LIST_SUBST).view("<i4"))
+        assert np.array_equal(anchored.view("<i4"), o.seeds(LIST_ANCHORED).view("<i4"))
         assert np.array_equal(sc.dispatch_seeds().view("<i4"), o.dispatch().view("<i4"))
+        assert sc.guard_hits() == o.guard_hits()
+        assert np.array_equal(sc.subst_calls().view("<i4"), o.calls(LIST_SUBST).view("<i4"))
+        assert np.array_equal(sc.anchored_calls().view("<i4"), o.calls(LIST_ANCHORED).view("<i4"))
