@@ -308,6 +308,27 @@ int ribbit_host_refine_bed(const RibbitScanParams *params, const RibbitRefinePar
 void ribbit_text_free(char *text);
 
 /*
+ * ---- repeat-masked FASTA ----------------------------------------------------------------------------------------------
+ * The mask of a record is the union of its BED rows' half-open [start, end) (columns 2 and 3), clipped to [0, L); rows with
+ * start >= end add nothing.  RIBBIT_MASK_SOFT lowercases masked bytes in A-Z (c | 0x20) and leaves every other byte as it
+ * is; RIBBIT_MASK_HARD writes every masked byte as 'N'.  The body is the record's bytes in lines of line_width bytes, each
+ * ending in '\n' (the last one may be short; none for an empty record); line_width 0: the whole body on one line.
+ */
+#define RIBBIT_MASK_SOFT 0
+#define RIBBIT_MASK_HARD 1
+/* Masked, line-wrapped body of the loaded record (header not included); *text is handle-owned, valid until the
+ * handle's next mask call, load or close.  intervals: n pairs (start, end), half-open, any order, clipped to [0, L). */
+int ribbit_hip_mask_record(RibbitHandle *h, const int32_t *intervals, size_t n, int32_t mode, int32_t line_width,
+                           const char **text, size_t *len);
+/* Host-only twin (no GPU): same output for a host sequence; *text malloc'ed, release with ribbit_text_free(). */
+int ribbit_host_mask_record(const char *sequence, int64_t length, const int32_t *intervals, size_t n, int32_t mode,
+                            int32_t line_width, char **text, size_t *len);
+/* (start, end) of every row of BED text as ribbit_hip_refine_bed writes it (host only); *pairs malloc'ed, 2 * *n ints,
+ * release with ribbit_intervals_free().  A line that is not such a row: RIBBIT_E_ARG. */
+int ribbit_bed_intervals(const char *text, size_t len, int32_t **pairs, size_t *n);
+void ribbit_intervals_free(int32_t *pairs);
+
+/*
  * ---- streaming FASTA ingest ---------------------------------------------------------------------------------------
  * Replaces the reader loop of ribbit.cpp:269-280 (getline + `sequence += line` into one pageable std::string per
  * record).  The file is read in 16-MB blocks; line bodies are copied once, straight into a page-locked buffer

@@ -15,7 +15,8 @@ import numpy as np
 
 __all__ = ["RibbitHipError", "ScanParams", "Scanner", "library_path", "load_library", "host_replay_calls", "pack_planes", "pack_bit_planes",
            "RUN_DT", "CALL_DT", "SEED_DT", "JOB_DT", "ENDS_DT", "RANK", "TERM", "RefineParams", "host_refine_jobs", "host_refine_bed", "host_merge_chunks", "host_perfect_runs_from_events", "pair_halves", "ssw_align", "ssw_align_periodic", "merge_chunk_runs", "join_run_halves",
-           "RUN_NOT_OWNED", "RUN_HALF_START", "RUN_HALF_END"]
+           "RUN_NOT_OWNED", "RUN_HALF_START", "RUN_HALF_END",
+           "MASK_MODES", "host_mask_record", "bed_intervals"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -53,7 +54,10 @@ ABI_SYMBOLS = [
     "ribbit_hip_scan_perfect_chunk", "ribbit_hip_host_register", "ribbit_hip_host_unregister",
     "ribbit_hip_set_host_threads", "ribbit_hip_ssw_passes", "ribbit_hip_ssw_align_jobs", "ribbit_hip_set_timing", "ribbit_hip_debug_set_event_capacity", "ribbit_hip_debug_set_scan_split", "ribbit_hip_debug_last_scan_split", "ribbit_hip_debug_pair_events", "ribbit_hip_scan_perfect_begin", "ribbit_hip_scan_perfect_end", "ribbit_hip_scan_perfect_wait", "ribbit_hip_scan_perfect_end_device",
     "ribbit_hip_stage_calls_chunk", "ribbit_hip_xa_words_strided", "ribbit_host_merge_chunks",
+    "ribbit_hip_mask_record", "ribbit_host_mask_record", "ribbit_bed_intervals", "ribbit_intervals_free",
 ]
+
+MASK_MODES = {"soft": 0, "hard": 1}     # RIBBIT_MASK_SOFT / RIBBIT_MASK_HARD
 
 
 class RibbitHipError(RuntimeError):
@@ -252,6 +256,11 @@ def load_library():
     L.ribbit_hip_debug_stream_read.argtypes = [vp, i64, C.POINTER(i64)]
     L.ribbit_hip_last_event_count.restype = i64
     L.ribbit_hip_last_event_count.argtypes = [vp]
+    L.ribbit_hip_mask_record.argtypes = [vp, vp, C.c_size_t, i32, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_host_mask_record.argtypes = [C.c_char_p, i64, vp, C.c_size_t, i32, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_bed_intervals.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_intervals_free.restype = None
+    L.ribbit_intervals_free.argtypes = [vp]
     _lib = L
     return L
 
@@ -500,6 +509,43 @@ def host_refine_bed(min_motif: int, max_motif: int, sequence: bytes, xa, xa_stri
         return C.string_at(text.value, n.value).decode()
     finally:
         L.ribbit_text_free(text)
+
+
+def _mask_args(intervals, mode: str, line_width: int):
+    if mode not in MASK_MODES:
+        raise ValueError(f"mask mode must be one of {sorted(MASK_MODES)}, got {mode!r}")
+    iv = np.ascontiguousarray(np.asarray(intervals, dtype=np.int32).reshape(-1, 2))
+    return iv, MASK_MODES[mode], int(line_width)
+
+
+def host_mask_record(sequence: bytes, intervals, mode: str = "soft", line_width: int = 60) -> bytes:
+    """ribbit_host_mask_record: the masked, line-wrapped FASTA body of `sequence` (no header) under the union of the
+    half-open (start, end) rows of `intervals`.  No GPU needed."""
+    L = load_library()
+    iv, m, w = _mask_args(intervals, mode, line_width)
+    seq = bytes(sequence)
+    text, n = C.c_void_p(), C.c_size_t()
+    rc = L.ribbit_host_mask_record(seq, len(seq), iv.ctypes.data if len(iv) else None, len(iv), m, w, C.byref(text), C.byref(n))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_host_mask_record error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return C.string_at(text.value, n.value)
+    finally:
+        L.ribbit_text_free(text)
+
+
+def bed_intervals(text) -> np.ndarray:
+    """ribbit_bed_intervals: (start, end) of every row of BED text as refine_bed writes it, an (n, 2) int32 array."""
+    L = load_library()
+    raw = text.encode() if isinstance(text, str) else bytes(text)
+    pairs, n = C.c_void_p(), C.c_size_t()
+    rc = L.ribbit_bed_intervals(raw, len(raw), C.byref(pairs), C.byref(n))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_bed_intervals error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return _copy(pairs.value, 2 * n.value, np.dtype("<i4")).reshape(-1, 2)
+    finally:
+        L.ribbit_intervals_free(pairs)
 
 
 def host_perfect_runs_from_events(min_motif: int, max_motif: int, event_parts, count_parts):
@@ -797,6 +843,13 @@ class Scanner:
         if not n.value:
             return np.zeros(0, dtype=np.uint8)
         return np.ctypeslib.as_array(C.cast(text.value, C.POINTER(C.c_uint8)), shape=(n.value,))
+
+    def mask_record(self, intervals, mode: str = "soft", line_width: int = 60) -> bytes:
+        """The loaded record's masked, line-wrapped FASTA body on the GPU (ribbit_hip_mask_record); see host_mask_record"""
+        iv, m, w = _mask_args(intervals, mode, line_width)
+        text, n = C.c_void_p(), C.c_size_t()
+        self._check(self._L.ribbit_hip_mask_record(self._h, iv.ctypes.data if len(iv) else None, len(iv), m, w, C.byref(text), C.byref(n)))
+        return C.string_at(text.value, n.value) if n.value else b""
 
     def adopt_dispatch(self, seeds) -> None:
         """ribbit_hip_adopt_dispatch: this handle (same record loaded) refines a slice of another handle's dispatch list"""

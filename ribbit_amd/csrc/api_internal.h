@@ -8,6 +8,7 @@
 //   api_merge.cpp       the anchored stage's merge on the device: what parallel_merge.h's AnchoredDevicePass does on a handle
 //   api_align.cpp       the scans of the dispatched seeds, alignment jobs, batched striped passes and path searches
 //   api_refine_bed.cpp  refinement to BED text: the GPU alignment pipeline, the recursion's levels, the host-only form
+//   api_mask.cpp        the repeat-masked FASTA body of a record (mask.hip), its host twin, BED rows back to intervals
 // Not part of the ABI; nothing outside ribbit_amd/csrc includes it.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -262,6 +263,12 @@ struct RibbitHandle {
     int stage_done = STAGE_NONE;          // how far the seed lists have been advanced
     rb::SeedLists lists;
     bool refine_met_empty_query = false;  // the last ribbit_hip_refine_bed on this handle met an alignment with an empty query (ribbit_hip_refine_met_empty_query)
+    // the masked body of the loaded record (api_mask.cpp): coverage bitmap, intervals, the text on the device and on its way up
+    DevBuf<uint32_t> d_mask_bits;
+    DevBuf<int32_t> d_mask_iv;
+    DevBuf<uint8_t> d_mask_text;
+    PinnedBuf<int32_t> h_mask_iv;
+    PinnedBuf<char> h_mask_text;
     RibbitHandle *aux = nullptr;          // helper handle of ribbit_hip_refine_bed: streams and buffers of the long alignment batch
     std::vector<RibbitHandle *> feed_aux; // ... and of its further feeders (each takes every n-th slice of the short alignments)
 

@@ -1,0 +1,209 @@
+// api_mask.cpp -- the repeat-masked FASTA body of a record (mask.hip); see api_internal.h for the map of the files behind
+// include/ribbit_hip.h.  The GPU form reads the bases where the load left them (dev_ascii_src) and runs on the handle's
+// stream; the host twin and the BED row parser need no GPU.
+#include "api_internal.h"
+
+#include <exception>
+
+namespace {
+
+// width of a line as the format kernel takes it: 1 .. length (0 and anything longer: the whole body on one line)
+int64_t effective_width(int64_t length, int32_t line_width) {
+    return line_width == 0 || line_width > length ? length : line_width;
+}
+
+int64_t body_length(int64_t length, int64_t width) {
+    return length == 0 ? 0 : length + (length + width - 1) / width;
+}
+
+int check_mask_args(const int32_t *intervals, size_t n, int32_t mode, int32_t line_width, const void *text, const size_t *len) {
+    if (mode != RIBBIT_MASK_SOFT && mode != RIBBIT_MASK_HARD) return fail(RIBBIT_E_ARG, "mask mode %d is neither RIBBIT_MASK_SOFT nor RIBBIT_MASK_HARD", (int)mode);
+    if (line_width < 0) return fail(RIBBIT_E_ARG, "line width %d is negative", (int)line_width);
+    if ((!intervals && n > 0) || !text || !len) return fail(RIBBIT_E_ARG, "null argument");
+    if (n > ((size_t)1 << 40)) return fail(RIBBIT_E_ARG, "%zu intervals", n);
+    return RIBBIT_OK;
+}
+
+// one decimal field of a BED row; false unless it is [-]digits within int32
+bool parse_int32(const char *p, const char *end, int32_t *out) {
+    bool neg = false;
+    if (p < end && *p == '-') { neg = true; ++p; }
+    if (p == end) return false;
+    int64_t v = 0;
+    for (; p < end; ++p) {
+        if (*p < '0' || *p > '9') return false;
+        v = v * 10 + (*p - '0');
+        if (v > ((int64_t)1 << 31)) return false;
+    }
+    v = neg ? -v : v;
+    if (v < INT32_MIN || v > INT32_MAX) return false;
+    *out = (int32_t)v;
+    return true;
+}
+
+int mask_record_impl(RibbitHandle *h, const int32_t *intervals, size_t n, int32_t mode, int32_t line_width, const char **text, size_t *len) {
+    if (!h) return fail(RIBBIT_E_ARG, "null handle");
+    int rc;
+    if ((rc = check_mask_args(intervals, n, mode, line_width, text, len))) return rc;
+    if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
+    static const char kEmpty[1] = {0};
+    const int64_t length = h->length;
+    if (length == 0) { *text = kEmpty; *len = 0; return RIBBIT_OK; }
+    if ((rc = bind_device(h))) return rc;
+    const int64_t width = effective_width(length, line_width);
+    const int64_t out_len = body_length(length, width);
+    const int64_t nwords = length / 32 + 1;
+    if ((rc = h->d_mask_bits.ensure((size_t)nwords))) return rc;
+    if ((rc = h->d_mask_text.ensure((size_t)((out_len + 15) & ~(int64_t)15), true))) return rc;
+    if ((rc = h->h_mask_text.ensure((size_t)out_len, true))) return rc;
+    HIP_TRY(hipMemsetAsync(h->d_mask_bits.p, 0, (size_t)nwords * sizeof(uint32_t), h->stream));
+    if (n) {
+        if ((rc = h->h_mask_iv.ensure(2 * n, true))) return rc;
+        if ((rc = h->d_mask_iv.ensure(2 * n, true))) return rc;
+        // (the staging buffer may still be the source of the last call's copy: that call ended in a synchronise)
+        std::memcpy(h->h_mask_iv.p, intervals, 2 * n * sizeof(int32_t));
+        HIP_TRY(hipMemcpyAsync(h->d_mask_iv.p, h->h_mask_iv.p, 2 * n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+        rb::launch_mask_coverage(h->d_mask_iv.p, (int64_t)n, length, h->d_mask_bits.p, h->stream);
+        HIP_TRY(hipGetLastError());
+    }
+    rb::launch_mask_format(h->dev_ascii_src, length, h->d_mask_bits.p, nwords, mode == RIBBIT_MASK_HARD, width, out_len, h->d_mask_text.p, h->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h->h_mask_text.p, h->d_mask_text.p, (size_t)out_len, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    *text = h->h_mask_text.p;
+    *len = (size_t)out_len;
+    return RIBBIT_OK;
+}
+
+int host_mask_record_impl(const char *sequence, int64_t length, const int32_t *intervals, size_t n, int32_t mode, int32_t line_width,
+                          char **text, size_t *len) {
+    int rc;
+    if ((rc = check_mask_args(intervals, n, mode, line_width, text, len))) return rc;
+    if (length < 0 || (!sequence && length > 0)) return fail(RIBBIT_E_ARG, "bad sequence");
+    const int64_t width = std::max<int64_t>(1, effective_width(length, line_width));
+    const int64_t out_len = body_length(length, width);
+    // the clipped intervals sorted by start: the mask is walked as their union without a per-base array
+    std::vector<std::pair<int64_t, int64_t>> iv;
+    iv.reserve(n);
+    for (size_t i = 0; i < n; ++i) {
+        const int64_t s = std::max<int64_t>(intervals[2 * i], 0), e = std::min<int64_t>(intervals[2 * i + 1], length);
+        if (s < e) iv.emplace_back(s, e);
+    }
+    std::sort(iv.begin(), iv.end());
+    char *out = static_cast<char *>(std::malloc((size_t)out_len + 1));
+    if (!out) return fail(RIBBIT_E_NOMEM, "out of host memory");
+    int64_t o = 0, masked_to = 0;      // [.., masked_to): the union of the intervals that start at or before i
+    size_t next = 0;
+    for (int64_t i = 0; i < length; ++i) {
+        for (; next < iv.size() && iv[next].first <= i; ++next) masked_to = std::max(masked_to, iv[next].second);
+        const unsigned char c = (unsigned char)sequence[i];
+        out[o++] = i >= masked_to ? (char)c : mode == RIBBIT_MASK_HARD ? 'N' : (c >= 'A' && c <= 'Z') ? (char)(c | 0x20) : (char)c;
+        if ((i + 1) % width == 0 || i + 1 == length) out[o++] = '\n';
+    }
+    *text = out;
+    *len = (size_t)o;
+    return RIBBIT_OK;
+}
+
+// the rows of the whole lines in [p, end) appended to out; nullptr, or the first line that is not a row
+const char *parse_rows(const char *p, const char *end, std::vector<int32_t> &out) {
+    const char *tab[10];      // the last ten tabs of the line, in a ring
+    while (p < end) {
+        const char *eol = static_cast<const char *>(std::memchr(p, '\n', (size_t)(end - p)));
+        if (!eol) eol = end;
+        // 11 tab-separated columns; read from the right, so that a record name with a tab in it still parses
+        size_t nt = 0;
+        for (const char *q = p; (q = static_cast<const char *>(std::memchr(q, '\t', (size_t)(eol - q)))) != nullptr; ++q) tab[nt++ % 10] = q;
+        int32_t s = 0, e = 0;
+        if (nt < 10 || !parse_int32(tab[nt % 10] + 1, tab[(nt + 1) % 10], &s) || !parse_int32(tab[(nt + 1) % 10] + 1, tab[(nt + 2) % 10], &e))
+            return p;
+        out.push_back(s);
+        out.push_back(e);
+        p = eol + 1;
+    }
+    return nullptr;
+}
+
+int bed_intervals_impl(const char *text, size_t len, int32_t **pairs, size_t *n) {
+    if (!pairs || !n || (!text && len > 0)) return fail(RIBBIT_E_ARG, "null argument");
+    // a chromosome's BED is 150-200 MB of text: parsed in pieces of whole lines, one thread per piece of at least 4 MB
+    const unsigned hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+    const size_t parts = std::max<size_t>(1, std::min<size_t>(hw, len >> 22));
+    std::vector<const char *> cut(parts + 1, text + len);
+    cut[0] = text;
+    for (size_t k = 1; k < parts; ++k) {
+        const char *at = std::max(cut[k - 1], text + len * k / parts);
+        const char *nl = at > text ? static_cast<const char *>(std::memchr(at - 1, '\n', (size_t)(text + len - (at - 1)))) : at - 1;
+        cut[k] = nl ? nl + 1 : text + len;
+    }
+    std::vector<std::vector<int32_t>> rows(parts);
+    std::vector<const char *> bad(parts, nullptr);
+    std::vector<char> oom(parts, 0);
+    auto run = [&](size_t k) {
+        try { bad[k] = parse_rows(cut[k], cut[k + 1], rows[k]); } catch (const std::bad_alloc &) { oom[k] = 1; }
+    };
+    std::vector<std::thread> pool;
+    try {
+        for (size_t k = 1; k < parts; ++k) pool.emplace_back(run, k);
+    } catch (...) {            // a thread that could not start: its piece and the ones after it run here
+        for (size_t k = pool.size() + 1; k < parts; ++k) run(k);
+    }
+    run(0);
+    for (std::thread &t : pool) t.join();
+    size_t total = 0;
+    for (size_t k = 0; k < parts; ++k) {
+        if (oom[k]) return fail(RIBBIT_E_NOMEM, "out of host memory reading BED rows");
+        if (bad[k]) return fail(RIBBIT_E_ARG, "BED text at byte %zu is not a row of 11 tab-separated columns with integer start and end", (size_t)(bad[k] - text));
+        total += rows[k].size();
+    }
+    int32_t *mem = static_cast<int32_t *>(std::malloc(std::max<size_t>(total, 1) * sizeof(int32_t)));
+    if (!mem) return fail(RIBBIT_E_NOMEM, "out of host memory");
+    size_t at = 0;
+    for (const std::vector<int32_t> &r : rows) {
+        if (!r.empty()) std::memcpy(mem + at, r.data(), r.size() * sizeof(int32_t));
+        at += r.size();
+    }
+    *pairs = mem;
+    *n = total / 2;
+    return RIBBIT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ribbit_hip_mask_record(RibbitHandle *h, const int32_t *intervals, size_t n, int32_t mode, int32_t line_width,
+                           const char **text, size_t *len) {
+    try {
+        return mask_record_impl(h, intervals, n, mode, line_width, text, len);
+    } catch (const std::bad_alloc &) {          // nothing may unwind through the C boundary
+        return fail(RIBBIT_E_NOMEM, "out of host memory in the mask");
+    } catch (const std::exception &e) {
+        return fail(RIBBIT_E_INTERNAL, "mask: %s", e.what());
+    }
+}
+
+int ribbit_host_mask_record(const char *sequence, int64_t length, const int32_t *intervals, size_t n, int32_t mode,
+                            int32_t line_width, char **text, size_t *len) {
+    try {
+        return host_mask_record_impl(sequence, length, intervals, n, mode, line_width, text, len);
+    } catch (const std::bad_alloc &) {
+        return fail(RIBBIT_E_NOMEM, "out of host memory in the mask");
+    } catch (const std::exception &e) {
+        return fail(RIBBIT_E_INTERNAL, "mask: %s", e.what());
+    }
+}
+
+int ribbit_bed_intervals(const char *text, size_t len, int32_t **pairs, size_t *n) {
+    try {
+        return bed_intervals_impl(text, len, pairs, n);
+    } catch (const std::bad_alloc &) {
+        return fail(RIBBIT_E_NOMEM, "out of host memory reading BED rows");
+    } catch (const std::exception &e) {
+        return fail(RIBBIT_E_INTERNAL, "BED rows: %s", e.what());
+    }
+}
+
+void ribbit_intervals_free(int32_t *pairs) { std::free(pairs); }
+
+}  // extern "C"

@@ -248,6 +248,13 @@ struct AnchoredMergeArgs {
 void launch_anchored_merge(const AnchoredMergeArgs &a, uint32_t n_calls, uint32_t resident_waves /* <= AM_RESIDENT_WAVES */, hipStream_t stream);
 void launch_seed_types(const RibbitSeed *seeds, uint32_t n, int32_t *types, hipStream_t stream);      // types[i] = seeds[i].type
 
+// mask.hip: the repeat mask of the loaded record (api_mask.cpp).  bits: length / 32 + 1 words, zeroed by the caller;
+// intervals: n (start, end) pairs, clipped to [0, length) on the device.  format: width in 1 .. length (the caller maps
+// 0 and anything longer to length), out: out_len = length + ceil(length / width) bytes, rounded up to 16.
+void launch_mask_coverage(const int32_t *intervals, int64_t n, int64_t length, uint32_t *bits, hipStream_t stream);
+void launch_mask_format(const uint8_t *ascii, int64_t length, const uint32_t *bits, int64_t nwords, int hard, int64_t width,
+                        int64_t out_len, uint8_t *out, hipStream_t stream);
+
 // profiling aid: reads nwords dwords of src with one coalesced dword per lane (known byte count)
 void launch_calib_stream_read(const uint32_t *src, int64_t nwords, uint32_t *sink, hipStream_t stream);
 

@@ -3,7 +3,7 @@
 // between reading a record and writing its BED rows goes through the C ABI of libribbit_hip.so.
 //
 //   ribbit-hip -i in.fa [-o out.bed] [-m 2] [-M 100] [-p 0.85] [-l N|file] [--min-units N|file] [--perfect-units N|file]
-//              [--devices 0,1,...] [--jobs N]
+//              [--devices 0,1,...] [--jobs N] [--masked-fasta FILE [--mask soft|hard] [--mask-width N]]
 //
 // Records are independent (ribbit.cpp:269-280 handles them one after the other); here up to --jobs of them are in
 // flight at once PER GPU, each on its own handle / HIP streams, so that the upload and GPU scans of one record overlap
@@ -11,6 +11,9 @@
 // records are dealt over several GPUs, one handle set per device (partitioning by record: no halo, no
 // exchange).  Output order is the input order.  The file is read by ribbit_fasta_* (block reads, line bodies copied once into page-locked buffers that
 // the GPU uploads from asynchronously and refinement reads in place) instead of getline + string +=.
+//
+// --masked-fasta writes every record again with its BED rows masked (soft: lowercase, hard: N), on the GPU that refined it
+// (ribbit_hip_mask_record), in input order beside the BED.
 //
 // Reproduced quirks: -p is accepted and ignored (Q1); without -o the BED rows go to
 // stderr (Q2); --help exits with status 1 (Q3); the record name ends at the first space and the last
@@ -29,6 +32,7 @@
 #include <cstring>
 #include <ctime>
 #include <fstream>
+#include <functional>
 #include <iostream>
 #include <map>
 #include <string>
@@ -47,6 +51,10 @@ struct Options {
     std::vector<int> devices;                     // --devices / RIBBIT_DEVICES: GPUs the records are dealt over (empty: `device` alone)
     int jobs = 0;                                 // records in flight PER DEVICE; 0 = automatic
     std::string timing;                           // --timing FILE: a JSON record of the run (the reference has cerr progress lines only)
+    std::string masked_fasta;                     // --masked-fasta FILE: the records again, their BED rows masked (empty: off)
+    int mask_mode = RIBBIT_MASK_SOFT;             // --mask soft|hard
+    int mask_width = 60;                          // --mask-width N: bases per line, 0 = one line per record
+    bool has_mask_mode = false, has_mask_width = false;
 };
 
 const char *kHelp =
@@ -68,7 +76,13 @@ const char *kHelp =
     "                                FASTA are dealt over these GPUs, the longest of the look-ahead first; BED rows\n"
     "                                keep the input order\n"
     "  --timing arg                  (ribbit-hip) write a JSON record of the run to this file: records, bases, wall time and\n"
-    "                                the wall time per stage summed over the records\n";
+    "                                the wall time per stage summed over the records\n"
+    "  --masked-fasta arg            (ribbit-hip) also write the records to this FASTA file with the bases of their BED rows\n"
+    "                                masked; a header keeps the record name only (the description after the first space\n"
+    "                                is not kept)\n"
+    "  --mask arg                    (ribbit-hip) soft: masked letters A-Z become lowercase; hard: masked bases become N.\n"
+    "                                Default: soft\n"
+    "  --mask-width arg              (ribbit-hip) bases per line of the masked FASTA, 0 for one line per record. Default: 60\n";
 
 [[noreturn]] void die(const std::string &msg) {        // argument errors: main thread, before any worker exists
     std::cerr << "ribbit-hip: " << msg << "\n";
@@ -92,11 +106,14 @@ bool parse_device_list(const std::string &value, std::vector<int> &out) {
     return !out.empty();
 }
 
+bool is_number(const std::string &s) { return !s.empty() && std::all_of(s.begin(), s.end(), [](unsigned char c) { return std::isdigit(c); }); }
+
 // returns 0 for --help (the caller exits 1, as the reference does), 1 on success
 int parse_arguments(int argc, char **argv, Options &o) {
     static const std::map<std::string, std::string> longs = {
         {"help", "h"}, {"input-file", "i"}, {"output-file", "o"}, {"min-motif-length", "m"}, {"max-motif-length", "M"},
-        {"purity", "p"}, {"min-length", "l"}, {"min-units", "U"}, {"perfect-units", "P"}, {"device", "D"}, {"jobs", "J"}, {"devices", "G"}, {"timing", "T"}};
+        {"purity", "p"}, {"min-length", "l"}, {"min-units", "U"}, {"perfect-units", "P"}, {"device", "D"}, {"jobs", "J"}, {"devices", "G"}, {"timing", "T"},
+        {"masked-fasta", "X"}, {"mask", "K"}, {"mask-width", "W"}};
     bool help = false;
     for (int a = 1; a < argc; ++a) {
         std::string arg = argv[a], key, value;
@@ -131,14 +148,29 @@ int parse_arguments(int argc, char **argv, Options &o) {
         else if (key == "D") o.device = std::atoi(value.c_str());
         else if (key == "J") o.jobs = std::atoi(value.c_str());
         else if (key == "T") o.timing = value;
+        else if (key == "X") {
+            if (value.empty()) die("--masked-fasta wants a file name");
+            o.masked_fasta = value;
+        }
+        else if (key == "K") {
+            if (value == "soft") o.mask_mode = RIBBIT_MASK_SOFT;
+            else if (value == "hard") o.mask_mode = RIBBIT_MASK_HARD;
+            else die("--mask wants soft or hard, got '" + value + "'");
+            o.has_mask_mode = true;
+        }
+        else if (key == "W") {
+            if (!is_number(value) || value.size() > 9) die("--mask-width wants a whole number of bases (0 or more), got '" + value + "'");
+            o.mask_width = std::atoi(value.c_str());
+            o.has_mask_width = true;
+        }
         else if (key == "G") { if (!parse_device_list(value, o.devices)) die("--devices wants a comma separated list of GPU ordinals, got '" + value + "'"); }
     }
     if (help) { std::cerr << kHelp << "\n"; return 0; }                       // ribbit.cpp:114-117
+    if (o.masked_fasta.empty() && (o.has_mask_mode || o.has_mask_width))
+        die(std::string(o.has_mask_mode ? "--mask" : "--mask-width") + " needs --masked-fasta");
     if (o.fasta.empty()) { std::cerr << "ERROR: Please specify an input fasta file!\n"; return 0; }   // :122-126
     return 1;
 }
-
-bool is_number(const std::string &s) { return !s.empty() && std::all_of(s.begin(), s.end(), [](unsigned char c) { return std::isdigit(c); }); }
 
 // parseDualtypeArgs, ribbit.cpp:25-64: one integer for every motif size in range, or a two-column TSV
 void dual_type(const std::string &value, std::map<int, int> &table, int m_lo, int m_hi) {
@@ -192,7 +224,7 @@ size_t count_failed(const RibbitSeed *s, size_t n) {
 }
 
 // RIBBIT_PROFILE=1: wall time per stage, summed over the records, printed at exit
-double g_stage_ms[6] = {0, 0, 0, 0, 0, 0};
+double g_stage_ms[7] = {0, 0, 0, 0, 0, 0, 0};     // load, perfect, substitutions, anchored, dispatch, refine+BED, mask
 std::mutex g_stage_mu;
 struct StageClock {
     int slot;
@@ -205,7 +237,21 @@ struct StageClock {
     }
 };
 
-// processSequence (fasta_utils.cpp:59-250) through the C ABI, with the reference's progress lines
+// --masked-fasta: how to mask, and where the record's header and masked body go (null: masking is off for this record)
+struct MaskJob {
+    int mode, width;
+    std::function<void(const char *, size_t)> write;
+};
+
+// the (start, end) pairs of a BED text, appended to iv
+void append_intervals(const char *text, size_t len, std::vector<int32_t> &iv) {
+    int32_t *pairs = nullptr;
+    size_t n = 0;
+    if (ribbit_bed_intervals(text, len, &pairs, &n) != RIBBIT_OK) throw PathError{std::string("reading the BED rows back failed: ") + ribbit_hip_last_error()};
+    iv.insert(iv.end(), pairs, pairs + 2 * n);
+    ribbit_intervals_free(pairs);
+}
+
 // Refinement of ONE record over several GPUs (ribbit_hip_adopt_dispatch): the dispatched seeds in as many slices as there are
 // handles, equal numbers of seeds each (a seed's cost varies by orders of magnitude, but over millions of seeds the slices even
 // out); every helper loads the record on its own GPU, makes the composed planes there and refines its slice on its GPU's share of
@@ -213,7 +259,7 @@ struct StageClock {
 // previous seed's CIGAR, which may be another slice's) makes the record be refined again in one piece, on `h`.
 struct Helper { RibbitHandle *h; int host_threads; };
 bool refine_over_devices(RibbitHandle *h, const std::vector<Helper> &helpers, const RibbitRefineParams &prm, const std::string &name, const char *bases,
-                         int64_t length, const RibbitSeed *d, size_t nd, std::ostream &out, std::ostream &log) {
+                         int64_t length, const RibbitSeed *d, size_t nd, std::ostream &out, std::ostream &log, std::vector<int32_t> *mask_iv) {
     const size_t parts = helpers.size() + 1;
     const std::vector<RibbitSeed> all(d, d + nd);          // (`d` is `h`'s own list, which adopting a slice replaces)
     std::vector<std::string> text(parts), error(parts);
@@ -250,15 +296,20 @@ bool refine_over_devices(RibbitHandle *h, const std::vector<Helper> &helpers, co
         check(ribbit_hip_adopt_dispatch(h, all.data(), nd));
         check(ribbit_hip_refine_bed(h, &prm, name.c_str(), &t, &len));
         out.write(t, (std::streamsize)len);
+        if (mask_iv) append_intervals(t, len, *mask_iv);
         log << "[devices] an alignment with an empty query at the head of a slice: the record was refined again in one piece\n";
         return false;
     }
     for (size_t k = 0; k < parts; ++k) out.write(text[k].data(), (std::streamsize)text[k].size());
+    if (mask_iv)      // (the rows of all slices: the mask of a record is the union of all of its rows)
+        for (size_t k = 0; k < parts; ++k) append_intervals(text[k].data(), text[k].size(), *mask_iv);
     return true;
 }
 
+// processSequence (fasta_utils.cpp:59-250) through the C ABI, with the reference's progress lines; then, with --masked-fasta,
+// the record masked by its rows on `h`, the handle that loaded it
 void process_sequence(RibbitHandle *h, const RibbitRefineParams &prm, const std::string &name, const char *bases, int64_t length,
-                      std::ostream &out, std::ostream &log, const std::vector<Helper> *helpers = nullptr) {
+                      std::ostream &out, std::ostream &log, const MaskJob *mask, const std::vector<Helper> *helpers = nullptr) {
     const time_t t0 = time(0);
     auto secs = [&]() { return difftime(time(0), t0); };
     { StageClock c(0); check(ribbit_hip_load_record_pinned(h, bases, length)); }
@@ -279,9 +330,10 @@ void process_sequence(RibbitHandle *h, const RibbitRefineParams &prm, const std:
     { StageClock c(4); check(ribbit_hip_dispatch_seeds(h, &d, &nd)); }
     // one record over several GPUs: only worth it from a few hundred thousand seeds on (RIBBIT_SHARD_MIN_SEEDS: a test hook)
     static const size_t shard_min = std::getenv("RIBBIT_SHARD_MIN_SEEDS") ? (size_t)std::atoll(std::getenv("RIBBIT_SHARD_MIN_SEEDS")) : 400000;
+    std::vector<int32_t> mask_iv;
     if (helpers && !helpers->empty() && nd >= shard_min && nd >= 2 * (helpers->size() + 1)) {
         StageClock c(5);
-        const bool sharded = refine_over_devices(h, *helpers, prm, name, bases, length, d, nd, out, log);
+        const bool sharded = refine_over_devices(h, *helpers, prm, name, bases, length, d, nd, out, log, mask ? &mask_iv : nullptr);
         if (std::getenv("RIBBIT_PROFILE"))
             log << "[devices] refinement of " << name << ": " << nd << " dispatched seeds " << (sharded ? "in " : "NOT in ") << helpers->size() + 1 << " slices over as many handles\n";
     } else {
@@ -289,6 +341,15 @@ void process_sequence(RibbitHandle *h, const RibbitRefineParams &prm, const std:
         size_t len;
         { StageClock c(5); check(ribbit_hip_refine_bed(h, &prm, name.c_str(), &text, &len)); }
         out.write(text, (std::streamsize)len);
+        if (mask) { StageClock c(6); append_intervals(text, len, mask_iv); }
+    }
+    if (mask) {
+        const char *body = nullptr;
+        size_t body_len = 0;
+        { StageClock c(6); check(ribbit_hip_mask_record(h, mask_iv.data(), mask_iv.size() / 2, mask->mode, mask->width, &body, &body_len)); }
+        const std::string header = ">" + name + "\n";
+        mask->write(header.data(), header.size());
+        mask->write(body, body_len);
     }
     log << "Total number of seeds that are processed for alignment: " << nd << "\t Time elapsed: " << secs() << "secs\n";
 }
@@ -302,6 +363,12 @@ int main(int argc, char **argv) {
     std::ofstream file;
     if (!opt.out.empty()) file.open(opt.out);
     std::ostream &out = opt.out.empty() ? std::cerr : file;                   // ribbit.cpp:199-205
+    std::ofstream masked_file;
+    if (!opt.masked_fasta.empty()) {
+        masked_file.open(opt.masked_fasta, std::ios::binary);
+        if (!masked_file) die("--masked-fasta: cannot open '" + opt.masked_fasta + "' for writing");
+    }
+    const bool masking = !opt.masked_fasta.empty();
 
     const auto t_run0 = std::chrono::steady_clock::now();
     RibbitRefineParams prm;
@@ -338,7 +405,7 @@ int main(int argc, char **argv) {
     jobs = std::min(jobs, 64);
     const int workers = jobs * ndev;
     struct Record { size_t index; std::string name; const char *bases; int64_t length; };
-    struct Result { std::string bed, log; };
+    struct Result { std::string bed, log, masked; };
     std::mutex mu;
     std::condition_variable cv;
     std::deque<Record> queue;
@@ -361,6 +428,7 @@ int main(int argc, char **argv) {
         for (auto it = done.find(next_out); it != done.end(); it = done.find(next_out)) {
             std::cerr << it->second.log;
             out.write(it->second.bed.data(), (std::streamsize)it->second.bed.size());
+            masked_file.write(it->second.masked.data(), (std::streamsize)it->second.masked.size());
             done.erase(it);
             ++next_out;
         }
@@ -397,6 +465,8 @@ int main(int argc, char **argv) {
             }
             cv.notify_all();
             std::ostringstream bed, log;
+            std::string masked;
+            const MaskJob mask{opt.mask_mode, opt.mask_width, [&masked](const char *p, size_t n) { masked.append(p, n); }};
             bool ok = true;
             std::string why;
             {
@@ -406,7 +476,7 @@ int main(int argc, char **argv) {
                     try {
                         check(ribbit_hip_set_host_threads(wh, (int)std::max(1u, dev_cores * (unsigned)weight / (unsigned)jobs)));
                         log << "Processing sequence " << rec.name << "\n";
-                        process_sequence(wh, prm, rec.name, rec.bases, rec.length, bed, log);
+                        process_sequence(wh, prm, rec.name, rec.bases, rec.length, bed, log, masking ? &mask : nullptr);
                     } catch (const PathError &e) { ok = false; why = e.what; }
                 }
             }
@@ -414,7 +484,7 @@ int main(int argc, char **argv) {
             {
                 std::lock_guard<std::mutex> lk(mu);
                 if (!ok && !failed) { failed = true; failure = why; }
-                done[rec.index] = Result{bed.str(), log.str()};
+                done[rec.index] = Result{bed.str(), log.str(), std::move(masked)};
                 tokens[(size_t)dev] += weight;
                 if (!failed) flush_ready();
             }
@@ -475,7 +545,10 @@ int main(int argc, char **argv) {
             for (int d = 1; d < ndev && (size_t)d < handles.size(); ++d) helpers.push_back(Helper{handles[(size_t)d], (int)dev_cores});
             check(ribbit_hip_set_host_threads(h, helpers.empty() ? 0 : (int)dev_cores));
             static const char kNoBases[1] = {0};
-            process_sequence(h, prm, last_name, last_bases ? last_bases : kNoBases, last_length, out, std::cerr, &helpers);
+            // (every record the reader hands out is masked but the nameless empty one of a file without records, Q4)
+            const MaskJob mask{opt.mask_mode, opt.mask_width, [&masked_file](const char *p, size_t n) { masked_file.write(p, (std::streamsize)n); }};
+            const bool mask_last = masking && !(last_name.empty() && last_length == 0);
+            process_sequence(h, prm, last_name, last_bases ? last_bases : kNoBases, last_length, out, std::cerr, mask_last ? &mask : nullptr, &helpers);
         } catch (const PathError &e) { failed = true; failure = e.what; }
     }
     if (failed) { std::cerr << "ribbit-hip: " << failure << "\n"; status = 1; }
@@ -500,10 +573,13 @@ int main(int argc, char **argv) {
         tf << "{\"records\": " << n_records + 1 << ", \"bases\": " << total_bases << ", \"wall_s\": " << wall_s << ", \"status\": " << status
            << ", \"min_motif\": " << opt.min_motif << ", \"max_motif\": " << opt.max_motif << ", \"devices\": " << ndev << ", \"jobs_per_device\": " << jobs
            << ", \"stage_ms_summed_over_records\": {\"load\": " << g_stage_ms[0] << ", \"perfect\": " << g_stage_ms[1] << ", \"substitutions\": " << g_stage_ms[2]
-           << ", \"anchored\": " << g_stage_ms[3] << ", \"dispatch\": " << g_stage_ms[4] << ", \"refine_and_bed\": " << g_stage_ms[5] << "}}\n";
+           << ", \"anchored\": " << g_stage_ms[3] << ", \"dispatch\": " << g_stage_ms[4] << ", \"refine_and_bed\": " << g_stage_ms[5];
+        if (masking) tf << ", \"mask\": " << g_stage_ms[6];
+        tf << "}}\n";
     }
     if (std::getenv("RIBBIT_PROFILE"))
         std::cerr << "[stages, ms over all records] load " << g_stage_ms[0] << "  perfect " << g_stage_ms[1] << "  substitutions "
-                  << g_stage_ms[2] << "  anchored " << g_stage_ms[3] << "  dispatch " << g_stage_ms[4] << "  refine+BED " << g_stage_ms[5] << "\n";
+                  << g_stage_ms[2] << "  anchored " << g_stage_ms[3] << "  dispatch " << g_stage_ms[4] << "  refine+BED " << g_stage_ms[5]
+                  << (masking ? "  mask " + std::to_string(g_stage_ms[6]) : std::string()) << "\n";
     return status;
 }
