@@ -10,46 +10,21 @@ import numpy as np
 import pytest
 import torch.multiprocessing as mp
 
-import pyevents
 import ribbit_amd
-from cases import edge_cases, simulated_cases
+from cases import edge_cases, large_motif_cases, simulated_cases
+from chunk_contract import ANCHORED_SPAN, SUBST_SPAN, _chunk_calls, _chunk_runs, oracle_runs
 from oracle_lib import LIST_ANCHORED, LIST_PERFECT, LIST_SUBST, Oracle
-from ribbit_amd import CALL_DT, RUN_DT, sharded
+from ribbit_amd import sharded
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CASES = [c for c in edge_cases() if len(c[1]) >= 64] + simulated_cases()[:3]
-SUBST_SPAN = lambda m: m // 3 if m > 30 else 10                                       # parse_substitute_shiftxor.cpp:423
-ANCHORED_SPAN = lambda m: int(0.9 * m) if m >= 10 else (m if m > 6 else 10)           # parse_anchored_shiftxor.cpp:572-573
-
-
-def _chunk_calls(calls, length, own_lo, own_hi, last, span):
-    """what ribbit_hip_stage_calls_chunk keeps of a stage's full call list for the chunk owning scan positions
-    [own_lo, own_hi): the calls that pass the length filter, each with the largest end of the chunk's earlier calls;
-    the largest end of any of its calls; the end-of-sequence calls (pos == length) if it is the last chunk"""
-    loop = calls[(calls["pos"] < length) & (calls["pos"] >= own_lo) & (calls["pos"] < own_hi)]
-    ends = loop["end"].astype(np.int64)
-    seen = np.concatenate(([-1], np.maximum.accumulate(ends)[:-1])) if len(loop) else np.zeros(0, np.int64)
-    keep = (loop["end"] - loop["start"]) >= np.array([span(int(m)) for m in loop["mlen"]], dtype=np.int64) if len(loop) else np.zeros(0, bool)
-    flush = calls[calls["pos"] >= length] if last else np.zeros(0, CALL_DT)
-    return loop[keep].copy(), seen[keep].astype("<i4"), int(ends.max()) if len(loop) else -1, flush.copy()
-
-
-def _chunk_runs(runs, own_lo, own_hi):
-    """ribbit_hip_scan_perfect_chunk's records for the chunk: complete runs it owns, halves of the runs its edges cut"""
-    s, e = runs["start"], runs["end"]
-    s_own, e_own = (s >= own_lo) & (s < own_hi), (e >= own_lo) & (e < own_hi)
-    whole = runs[s_own & (e < own_hi)].copy()
-    hs = runs[s_own & (e >= own_hi)].copy(); hs["end"] = -1; hs["term"] = ribbit_amd.RUN_HALF_START
-    he = runs[e_own & (s < own_lo)].copy(); he["start"] = -1; he["term"] = ribbit_amd.RUN_HALF_END + he["term"]
-    return whole, np.concatenate((hs, he))
+CASES = [c for c in edge_cases() if len(c[1]) >= 64] + simulated_cases()[:3] + large_motif_cases()
 
 
 def _oracle_parts(seq, m_lo, m_hi, nparts):
     """(parts as ranks would produce them, oracle lists)"""
     L = len(seq)
     with Oracle(seq, m_lo, m_hi) as o:
-        ev0, cnt0 = pyevents.perfect_events(o, m_lo, m_hi)
-        runs = ribbit_amd.host_perfect_runs_from_events(m_lo, m_hi, [ev0], [cnt0])
+        runs = oracle_runs(o, m_lo, m_hi)
         o.run_perfect(); o.run_subst(); o.run_anchor_planes()
         xa_full, stride = ribbit_amd.pack_bit_planes([o.plane(m) for m in range(m_lo, m_hi + 1)], L)
         o.run_anchored(); o.run_dispatch()
