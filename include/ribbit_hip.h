@@ -329,6 +329,26 @@ int ribbit_bed_intervals(const char *text, size_t len, int32_t **pairs, size_t *
 void ribbit_intervals_free(int32_t *pairs);
 
 /*
+ * ---- repeat sequences with their flanks (FASTA) ------------------------------------------------------------------------
+ * One entry per (start, end) pair, in the order given, also for empty or out-of-range pairs.  With L the record's length
+ * and F the flank (0 .. INT32_MAX), in 64-bit arithmetic:
+ *   s' = min(max(s, 0), L)    e' = min(max(e, s'), L)    lo = max(s' - F, 0)    hi = min(e' + F, L)
+ *   entry = ">" name ":" s' "-" e' " flank=" (s' - lo) "," (hi - e') "\n" bases[lo, hi) "\n"
+ * Numbers are plain decimals; the body is the record's bytes as they are, on one line.  name is the record name as the
+ * BED writes it (it may be empty).  No pairs: no text.
+ */
+/* Entries of rows [0, k) of intervals for the loaded record, k >= 1 when n >= 1: the largest k whose text fits the
+ * handle's text budget (default 64 MiB), or k = 1 when the first entry alone is larger.  *text is handle-owned, valid
+ * until the handle's next repeat-sequence call, load or close; *rows_done = k.  Call again with intervals + 2k, n - k. */
+int ribbit_hip_repeat_sequences(RibbitHandle *h, const char *name, const int32_t *intervals, size_t n, int32_t flank,
+                                const char **text, size_t *len, size_t *rows_done);
+/* Host-only twin (no GPU): the whole text at once; *text malloc'ed, release with ribbit_text_free(). */
+int ribbit_host_repeat_sequences(const char *name, const char *sequence, int64_t length, const int32_t *intervals,
+                                 size_t n, int32_t flank, char **text, size_t *len);
+/* Test hook: the text budget of ribbit_hip_repeat_sequences in bytes (0: the default). */
+int ribbit_hip_debug_set_repeat_text_budget(RibbitHandle *h, size_t bytes);
+
+/*
  * ---- streaming FASTA ingest ---------------------------------------------------------------------------------------
  * Replaces the reader loop of ribbit.cpp:269-280 (getline + `sequence += line` into one pageable std::string per
  * record).  The file is read in 16-MB blocks; line bodies are copied once, straight into a page-locked buffer

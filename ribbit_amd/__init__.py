@@ -16,7 +16,7 @@ import numpy as np
 __all__ = ["RibbitHipError", "ScanParams", "Scanner", "library_path", "load_library", "host_replay_calls", "pack_planes", "pack_bit_planes",
            "RUN_DT", "CALL_DT", "SEED_DT", "JOB_DT", "ENDS_DT", "RANK", "TERM", "RefineParams", "host_refine_jobs", "host_refine_bed", "host_merge_chunks", "host_perfect_runs_from_events", "pair_halves", "ssw_align", "ssw_align_periodic", "merge_chunk_runs", "join_run_halves",
            "RUN_NOT_OWNED", "RUN_HALF_START", "RUN_HALF_END",
-           "MASK_MODES", "host_mask_record", "bed_intervals"]
+           "MASK_MODES", "host_mask_record", "bed_intervals", "host_repeat_sequences"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -55,6 +55,7 @@ ABI_SYMBOLS = [
     "ribbit_hip_set_host_threads", "ribbit_hip_ssw_passes", "ribbit_hip_ssw_align_jobs", "ribbit_hip_set_timing", "ribbit_hip_debug_set_event_capacity", "ribbit_hip_debug_set_scan_split", "ribbit_hip_debug_last_scan_split", "ribbit_hip_debug_pair_events", "ribbit_hip_scan_perfect_begin", "ribbit_hip_scan_perfect_end", "ribbit_hip_scan_perfect_wait", "ribbit_hip_scan_perfect_end_device",
     "ribbit_hip_stage_calls_chunk", "ribbit_hip_xa_words_strided", "ribbit_host_merge_chunks",
     "ribbit_hip_mask_record", "ribbit_host_mask_record", "ribbit_bed_intervals", "ribbit_intervals_free",
+    "ribbit_hip_repeat_sequences", "ribbit_host_repeat_sequences", "ribbit_hip_debug_set_repeat_text_budget",
 ]
 
 MASK_MODES = {"soft": 0, "hard": 1}     # RIBBIT_MASK_SOFT / RIBBIT_MASK_HARD
@@ -258,6 +259,9 @@ def load_library():
     L.ribbit_hip_last_event_count.argtypes = [vp]
     L.ribbit_hip_mask_record.argtypes = [vp, vp, C.c_size_t, i32, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.ribbit_host_mask_record.argtypes = [C.c_char_p, i64, vp, C.c_size_t, i32, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_hip_repeat_sequences.argtypes = [vp, C.c_char_p, vp, C.c_size_t, i32, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.ribbit_host_repeat_sequences.argtypes = [C.c_char_p, C.c_char_p, i64, vp, C.c_size_t, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_hip_debug_set_repeat_text_budget.argtypes = [vp, C.c_size_t]
     L.ribbit_bed_intervals.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.ribbit_intervals_free.restype = None
     L.ribbit_intervals_free.argtypes = [vp]
@@ -528,6 +532,33 @@ def host_mask_record(sequence: bytes, intervals, mode: str = "soft", line_width:
     rc = L.ribbit_host_mask_record(seq, len(seq), iv.ctypes.data if len(iv) else None, len(iv), m, w, C.byref(text), C.byref(n))
     if rc != 0:
         raise RibbitHipError(f"ribbit_host_mask_record error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return C.string_at(text.value, n.value)
+    finally:
+        L.ribbit_text_free(text)
+
+
+def _repeat_args(name, intervals, flank: int):
+    raw = name.encode() if isinstance(name, str) else bytes(name)
+    if b"\0" in raw:
+        raise ValueError("a record name cannot hold a NUL byte")
+    flank = int(flank)
+    if flank > 0x7FFFFFFF:
+        raise ValueError(f"flank {flank} is larger than INT32_MAX")
+    iv = np.ascontiguousarray(np.asarray(intervals, dtype=np.int32).reshape(-1, 2))
+    return raw, iv, max(flank, -(1 << 31))
+
+
+def host_repeat_sequences(name, sequence: bytes, intervals, flank: int = 100) -> bytes:
+    """ribbit_host_repeat_sequences: one FASTA entry per (start, end) row, in order: ">name:s-e flank=left,right" and the
+    row's bases with `flank` bases on either side, clipped to the record (include/ribbit_hip.h).  No GPU needed."""
+    L = load_library()
+    raw, iv, f = _repeat_args(name, intervals, flank)
+    seq = bytes(sequence)
+    text, n = C.c_void_p(), C.c_size_t()
+    rc = L.ribbit_host_repeat_sequences(raw, seq, len(seq), iv.ctypes.data if len(iv) else None, len(iv), f, C.byref(text), C.byref(n))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_host_repeat_sequences error {rc}: {L.ribbit_hip_last_error().decode()}")
     try:
         return C.string_at(text.value, n.value)
     finally:
@@ -850,6 +881,29 @@ class Scanner:
         text, n = C.c_void_p(), C.c_size_t()
         self._check(self._L.ribbit_hip_mask_record(self._h, iv.ctypes.data if len(iv) else None, len(iv), m, w, C.byref(text), C.byref(n)))
         return C.string_at(text.value, n.value) if n.value else b""
+
+    def repeat_sequences(self, name, intervals, flank: int = 100) -> bytes:
+        """The loaded record's repeat sequences with their flanks on the GPU (ribbit_hip_repeat_sequences), every batch of the
+        handle's text budget joined; see host_repeat_sequences"""
+        return b"".join(text for text, _ in self.repeat_sequence_batches(name, intervals, flank))
+
+    def repeat_sequence_batches(self, name, intervals, flank: int = 100):
+        """-> [(text, rows)] of the calls repeat_sequences makes, in order"""
+        raw, iv, f = _repeat_args(name, intervals, flank)
+        out, done = [], 0
+        while True:
+            text, n, k = C.c_void_p(), C.c_size_t(), C.c_size_t()
+            ptr = iv[done:].ctypes.data if done < len(iv) else None
+            self._check(self._L.ribbit_hip_repeat_sequences(self._h, raw, ptr, len(iv) - done, f, C.byref(text), C.byref(n), C.byref(k)))
+            if done < len(iv):          # (no rows at all: the one call still checks the handle's state)
+                out.append((C.string_at(text.value, n.value), k.value))
+                done += k.value
+            if done == len(iv):
+                return out
+
+    def debug_set_repeat_text_budget(self, nbytes: int) -> None:
+        """the text budget of one ribbit_hip_repeat_sequences call in bytes (0: the default, 64 MiB)"""
+        self._check(self._L.ribbit_hip_debug_set_repeat_text_budget(self._h, int(nbytes)))
 
     def adopt_dispatch(self, seeds) -> None:
         """ribbit_hip_adopt_dispatch: this handle (same record loaded) refines a slice of another handle's dispatch list"""

@@ -280,6 +280,8 @@ int ribbit_hip_close(RibbitHandle *h) {
     h->h_xa.release();
     h->mg.release(); h->h_seed_stage.release(); h->h_longest_stage.release();
     h->d_mask_bits.release(); h->d_mask_iv.release(); h->d_mask_text.release(); h->h_mask_iv.release(); h->h_mask_text.release();
+    h->d_rep_iv.release(); h->d_rep_off.release(); h->d_rep_span_row.release(); h->d_rep_scratch.release(); h->d_rep_pick.release();
+    h->d_rep_text.release(); h->h_rep_iv.release(); h->h_rep_pick.release(); h->h_rep_text.release();
     std::free(h->bed_raw); h->bed_raw = nullptr;
     if (h->ev_xa) (void)hipEventDestroy(h->ev_xa);
     if (h->ev_ssw) (void)hipEventDestroy(h->ev_ssw);

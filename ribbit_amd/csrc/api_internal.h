@@ -9,6 +9,7 @@
 //   api_align.cpp       the scans of the dispatched seeds, alignment jobs, batched striped passes and path searches
 //   api_refine_bed.cpp  refinement to BED text: the GPU alignment pipeline, the recursion's levels, the host-only form
 //   api_mask.cpp        the repeat-masked FASTA body of a record (mask.hip), its host twin, BED rows back to intervals
+//   api_repeats.cpp     every row's bases with their flanks as FASTA entries (repeats.hip), in batches of a text budget; its host twin
 // Not part of the ABI; nothing outside ribbit_amd/csrc includes it.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -269,6 +270,18 @@ struct RibbitHandle {
     DevBuf<uint8_t> d_mask_text;
     PinnedBuf<int32_t> h_mask_iv;
     PinnedBuf<char> h_mask_text;
+    // the repeat sequences of the loaded record (api_repeats.cpp): the rows with the name behind them, their entry offsets, the
+    // first row of every output span, the scan's scratch, k and the byte count on their way up, the text of one batch
+    DevBuf<int32_t> d_rep_iv;
+    DevBuf<int64_t> d_rep_off;
+    DevBuf<int32_t> d_rep_span_row;
+    DevBuf<uint8_t> d_rep_scratch;
+    DevBuf<int64_t> d_rep_pick;
+    DevBuf<uint8_t> d_rep_text;
+    PinnedBuf<int32_t> h_rep_iv;
+    PinnedBuf<int64_t> h_rep_pick;
+    PinnedBuf<char> h_rep_text;
+    size_t rep_budget = 0;                // text budget of one batch in bytes (0: REPEAT_TEXT_BUDGET)
     RibbitHandle *aux = nullptr;          // helper handle of ribbit_hip_refine_bed: streams and buffers of the long alignment batch
     std::vector<RibbitHandle *> feed_aux; // ... and of its further feeders (each takes every n-th slice of the short alignments)
 

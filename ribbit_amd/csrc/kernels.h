@@ -255,6 +255,19 @@ void launch_mask_coverage(const int32_t *intervals, int64_t n, int64_t length, u
 void launch_mask_format(const uint8_t *ascii, int64_t length, const uint32_t *bits, int64_t nwords, int hard, int64_t width,
                         int64_t out_len, uint8_t *out, hipStream_t stream);
 
+// repeats.hip: the repeat sequences of the loaded record with their flanks (api_repeats.cpp).  The format kernel writes
+// REPEAT_SPAN output bytes per workgroup; span_row holds the first row of every span.
+constexpr int64_t REPEAT_SPAN = 4096;
+size_t repeat_scan_scratch_bytes(int64_t m);
+// off: m + 1 entry offsets of the m rows of iv (off[0] = 0, off[i + 1] - off[i] = length of entry i); then pick[0] = k, the
+// largest k in 1 .. m with off[k] <= budget (1 when there is none), and pick[1] = off[k].  m >= 1.
+hipError_t launch_repeat_offsets(const int32_t *iv, int64_t m, int64_t length, int32_t flank, int32_t name_len, int64_t budget,
+                                 int64_t *off, int64_t *pick, void *scratch, size_t scratch_bytes, hipStream_t stream);
+// the entries of rows [0, k): total = off[k] bytes into out (rounded up to 16; bytes past total are 0); span_row:
+// ceil(total / REPEAT_SPAN) + 1 ints.  ascii: the record's bases (any alignment), name: name_len bytes on the device.
+void launch_repeat_format(const uint8_t *ascii, int64_t length, const int32_t *iv, const int64_t *off, int64_t k, int64_t total,
+                          int32_t flank, const char *name, int32_t name_len, int32_t *span_row, uint8_t *out, hipStream_t stream);
+
 // profiling aid: reads nwords dwords of src with one coalesced dword per lane (known byte count)
 void launch_calib_stream_read(const uint32_t *src, int64_t nwords, uint32_t *sink, hipStream_t stream);
 

@@ -4,6 +4,7 @@
 //
 //   ribbit-hip -i in.fa [-o out.bed] [-m 2] [-M 100] [-p 0.85] [-l N|file] [--min-units N|file] [--perfect-units N|file]
 //              [--devices 0,1,...] [--jobs N] [--masked-fasta FILE [--mask soft|hard] [--mask-width N]]
+//              [--repeat-fasta FILE [--flank N]]
 //
 // Records are independent (ribbit.cpp:269-280 handles them one after the other); here up to --jobs of them are in
 // flight at once PER GPU, each on its own handle / HIP streams, so that the upload and GPU scans of one record overlap
@@ -13,7 +14,8 @@
 // the GPU uploads from asynchronously and refinement reads in place) instead of getline + string +=.
 //
 // --masked-fasta writes every record again with its BED rows masked (soft: lowercase, hard: N), on the GPU that refined it
-// (ribbit_hip_mask_record), in input order beside the BED.
+// (ribbit_hip_mask_record), in input order beside the BED.  --repeat-fasta writes every BED row's bases with N flanking bases on
+// either side (ribbit_hip_repeat_sequences), the same way.  Both read the BED rows back once.
 //
 // Reproduced quirks: -p is accepted and ignored (Q1); without -o the BED rows go to
 // stderr (Q2); --help exits with status 1 (Q3); the record name ends at the first space and the last
@@ -55,6 +57,9 @@ struct Options {
     int mask_mode = RIBBIT_MASK_SOFT;             // --mask soft|hard
     int mask_width = 60;                          // --mask-width N: bases per line, 0 = one line per record
     bool has_mask_mode = false, has_mask_width = false;
+    std::string repeat_fasta;                     // --repeat-fasta FILE: every BED row's bases with their flanks (empty: off)
+    int flank = 100;                              // --flank N: bases on either side of a row
+    bool has_flank = false;
 };
 
 const char *kHelp =
@@ -82,7 +87,12 @@ const char *kHelp =
     "                                is not kept)\n"
     "  --mask arg                    (ribbit-hip) soft: masked letters A-Z become lowercase; hard: masked bases become N.\n"
     "                                Default: soft\n"
-    "  --mask-width arg              (ribbit-hip) bases per line of the masked FASTA, 0 for one line per record. Default: 60\n";
+    "  --mask-width arg              (ribbit-hip) bases per line of the masked FASTA, 0 for one line per record. Default: 60\n"
+    "  --repeat-fasta arg            (ribbit-hip) also write every BED row's bases with their flanks to this FASTA file, one\n"
+    "                                entry per row in BED order, headed '>name:start-end flank=left,right' (start and end\n"
+    "                                clipped to the record; left, right: the flank bases taken on either side)\n"
+    "  --flank arg                   (ribbit-hip) bases of the record taken on either side of a row for --repeat-fasta.\n"
+    "                                Default: 100\n";
 
 [[noreturn]] void die(const std::string &msg) {        // argument errors: main thread, before any worker exists
     std::cerr << "ribbit-hip: " << msg << "\n";
@@ -113,7 +123,7 @@ int parse_arguments(int argc, char **argv, Options &o) {
     static const std::map<std::string, std::string> longs = {
         {"help", "h"}, {"input-file", "i"}, {"output-file", "o"}, {"min-motif-length", "m"}, {"max-motif-length", "M"},
         {"purity", "p"}, {"min-length", "l"}, {"min-units", "U"}, {"perfect-units", "P"}, {"device", "D"}, {"jobs", "J"}, {"devices", "G"}, {"timing", "T"},
-        {"masked-fasta", "X"}, {"mask", "K"}, {"mask-width", "W"}};
+        {"masked-fasta", "X"}, {"mask", "K"}, {"mask-width", "W"}, {"repeat-fasta", "Y"}, {"flank", "F"}};
     bool help = false;
     for (int a = 1; a < argc; ++a) {
         std::string arg = argv[a], key, value;
@@ -163,11 +173,21 @@ int parse_arguments(int argc, char **argv, Options &o) {
             o.mask_width = std::atoi(value.c_str());
             o.has_mask_width = true;
         }
+        else if (key == "Y") {
+            if (value.empty()) die("--repeat-fasta wants a file name");
+            o.repeat_fasta = value;
+        }
+        else if (key == "F") {
+            if (!is_number(value) || value.size() > 9) die("--flank wants a whole number of bases (0 or more, at most 9 digits), got '" + value + "'");
+            o.flank = std::atoi(value.c_str());
+            o.has_flank = true;
+        }
         else if (key == "G") { if (!parse_device_list(value, o.devices)) die("--devices wants a comma separated list of GPU ordinals, got '" + value + "'"); }
     }
     if (help) { std::cerr << kHelp << "\n"; return 0; }                       // ribbit.cpp:114-117
     if (o.masked_fasta.empty() && (o.has_mask_mode || o.has_mask_width))
         die(std::string(o.has_mask_mode ? "--mask" : "--mask-width") + " needs --masked-fasta");
+    if (o.repeat_fasta.empty() && o.has_flank) die("--flank needs --repeat-fasta");
     if (o.fasta.empty()) { std::cerr << "ERROR: Please specify an input fasta file!\n"; return 0; }   // :122-126
     return 1;
 }
@@ -224,7 +244,7 @@ size_t count_failed(const RibbitSeed *s, size_t n) {
 }
 
 // RIBBIT_PROFILE=1: wall time per stage, summed over the records, printed at exit
-double g_stage_ms[7] = {0, 0, 0, 0, 0, 0, 0};     // load, perfect, substitutions, anchored, dispatch, refine+BED, mask
+double g_stage_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // load, perfect, substitutions, anchored, dispatch, refine+BED, mask, repeats
 std::mutex g_stage_mu;
 struct StageClock {
     int slot;
@@ -240,6 +260,12 @@ struct StageClock {
 // --masked-fasta: how to mask, and where the record's header and masked body go (null: masking is off for this record)
 struct MaskJob {
     int mode, width;
+    std::function<void(const char *, size_t)> write;
+};
+
+// --repeat-fasta: the flank, and where the record's entries go (null: off for this record)
+struct RepeatJob {
+    int flank;
     std::function<void(const char *, size_t)> write;
 };
 
@@ -307,9 +333,10 @@ bool refine_over_devices(RibbitHandle *h, const std::vector<Helper> &helpers, co
 }
 
 // processSequence (fasta_utils.cpp:59-250) through the C ABI, with the reference's progress lines; then, with --masked-fasta,
-// the record masked by its rows on `h`, the handle that loaded it
+// the record masked by its rows, and with --repeat-fasta the rows' entries, both on `h`, the handle that loaded it
 void process_sequence(RibbitHandle *h, const RibbitRefineParams &prm, const std::string &name, const char *bases, int64_t length,
-                      std::ostream &out, std::ostream &log, const MaskJob *mask, const std::vector<Helper> *helpers = nullptr) {
+                      std::ostream &out, std::ostream &log, const MaskJob *mask, const RepeatJob *repeats,
+                      const std::vector<Helper> *helpers = nullptr) {
     const time_t t0 = time(0);
     auto secs = [&]() { return difftime(time(0), t0); };
     { StageClock c(0); check(ribbit_hip_load_record_pinned(h, bases, length)); }
@@ -330,10 +357,11 @@ void process_sequence(RibbitHandle *h, const RibbitRefineParams &prm, const std:
     { StageClock c(4); check(ribbit_hip_dispatch_seeds(h, &d, &nd)); }
     // one record over several GPUs: only worth it from a few hundred thousand seeds on (RIBBIT_SHARD_MIN_SEEDS: a test hook)
     static const size_t shard_min = std::getenv("RIBBIT_SHARD_MIN_SEEDS") ? (size_t)std::atoll(std::getenv("RIBBIT_SHARD_MIN_SEEDS")) : 400000;
-    std::vector<int32_t> mask_iv;
+    std::vector<int32_t> mask_iv;        // the record's rows in BED order, read back once for both outputs
+    const bool rows = mask || repeats;
     if (helpers && !helpers->empty() && nd >= shard_min && nd >= 2 * (helpers->size() + 1)) {
         StageClock c(5);
-        const bool sharded = refine_over_devices(h, *helpers, prm, name, bases, length, d, nd, out, log, mask ? &mask_iv : nullptr);
+        const bool sharded = refine_over_devices(h, *helpers, prm, name, bases, length, d, nd, out, log, rows ? &mask_iv : nullptr);
         if (std::getenv("RIBBIT_PROFILE"))
             log << "[devices] refinement of " << name << ": " << nd << " dispatched seeds " << (sharded ? "in " : "NOT in ") << helpers->size() + 1 << " slices over as many handles\n";
     } else {
@@ -341,7 +369,7 @@ void process_sequence(RibbitHandle *h, const RibbitRefineParams &prm, const std:
         size_t len;
         { StageClock c(5); check(ribbit_hip_refine_bed(h, &prm, name.c_str(), &text, &len)); }
         out.write(text, (std::streamsize)len);
-        if (mask) { StageClock c(6); append_intervals(text, len, mask_iv); }
+        if (rows) { StageClock c(mask ? 6 : 7); append_intervals(text, len, mask_iv); }
     }
     if (mask) {
         const char *body = nullptr;
@@ -350,6 +378,15 @@ void process_sequence(RibbitHandle *h, const RibbitRefineParams &prm, const std:
         const std::string header = ">" + name + "\n";
         mask->write(header.data(), header.size());
         mask->write(body, body_len);
+    }
+    if (repeats) {      // in batches of the handle's text budget, each written before the next call reuses the text
+        const size_t n = mask_iv.size() / 2;
+        for (size_t done = 0, k = 0; done < n; done += k) {
+            const char *text = nullptr;
+            size_t len = 0;
+            { StageClock c(7); check(ribbit_hip_repeat_sequences(h, name.c_str(), mask_iv.data() + 2 * done, n - done, repeats->flank, &text, &len, &k)); }
+            repeats->write(text, len);
+        }
     }
     log << "Total number of seeds that are processed for alignment: " << nd << "\t Time elapsed: " << secs() << "secs\n";
 }
@@ -369,6 +406,12 @@ int main(int argc, char **argv) {
         if (!masked_file) die("--masked-fasta: cannot open '" + opt.masked_fasta + "' for writing");
     }
     const bool masking = !opt.masked_fasta.empty();
+    std::ofstream repeat_file;
+    if (!opt.repeat_fasta.empty()) {
+        repeat_file.open(opt.repeat_fasta, std::ios::binary);
+        if (!repeat_file) die("--repeat-fasta: cannot open '" + opt.repeat_fasta + "' for writing");
+    }
+    const bool repeating = !opt.repeat_fasta.empty();
 
     const auto t_run0 = std::chrono::steady_clock::now();
     RibbitRefineParams prm;
@@ -405,7 +448,7 @@ int main(int argc, char **argv) {
     jobs = std::min(jobs, 64);
     const int workers = jobs * ndev;
     struct Record { size_t index; std::string name; const char *bases; int64_t length; };
-    struct Result { std::string bed, log, masked; };
+    struct Result { std::string bed, log, masked, repeats; };
     std::mutex mu;
     std::condition_variable cv;
     std::deque<Record> queue;
@@ -429,6 +472,7 @@ int main(int argc, char **argv) {
             std::cerr << it->second.log;
             out.write(it->second.bed.data(), (std::streamsize)it->second.bed.size());
             masked_file.write(it->second.masked.data(), (std::streamsize)it->second.masked.size());
+            repeat_file.write(it->second.repeats.data(), (std::streamsize)it->second.repeats.size());
             done.erase(it);
             ++next_out;
         }
@@ -467,6 +511,8 @@ int main(int argc, char **argv) {
             std::ostringstream bed, log;
             std::string masked;
             const MaskJob mask{opt.mask_mode, opt.mask_width, [&masked](const char *p, size_t n) { masked.append(p, n); }};
+            std::string repeat_text;         // (kept in memory until the record's turn to be written, as the masked text is)
+            const RepeatJob repeats{opt.flank, [&repeat_text](const char *p, size_t n) { repeat_text.append(p, n); }};
             bool ok = true;
             std::string why;
             {
@@ -476,7 +522,7 @@ int main(int argc, char **argv) {
                     try {
                         check(ribbit_hip_set_host_threads(wh, (int)std::max(1u, dev_cores * (unsigned)weight / (unsigned)jobs)));
                         log << "Processing sequence " << rec.name << "\n";
-                        process_sequence(wh, prm, rec.name, rec.bases, rec.length, bed, log, masking ? &mask : nullptr);
+                        process_sequence(wh, prm, rec.name, rec.bases, rec.length, bed, log, masking ? &mask : nullptr, repeating ? &repeats : nullptr);
                     } catch (const PathError &e) { ok = false; why = e.what; }
                 }
             }
@@ -484,7 +530,7 @@ int main(int argc, char **argv) {
             {
                 std::lock_guard<std::mutex> lk(mu);
                 if (!ok && !failed) { failed = true; failure = why; }
-                done[rec.index] = Result{bed.str(), log.str(), std::move(masked)};
+                done[rec.index] = Result{bed.str(), log.str(), std::move(masked), std::move(repeat_text)};
                 tokens[(size_t)dev] += weight;
                 if (!failed) flush_ready();
             }
@@ -547,8 +593,10 @@ int main(int argc, char **argv) {
             static const char kNoBases[1] = {0};
             // (every record the reader hands out is masked but the nameless empty one of a file without records, Q4)
             const MaskJob mask{opt.mask_mode, opt.mask_width, [&masked_file](const char *p, size_t n) { masked_file.write(p, (std::streamsize)n); }};
-            const bool mask_last = masking && !(last_name.empty() && last_length == 0);
-            process_sequence(h, prm, last_name, last_bases ? last_bases : kNoBases, last_length, out, std::cerr, mask_last ? &mask : nullptr, &helpers);
+            const RepeatJob repeats{opt.flank, [&repeat_file](const char *p, size_t n) { repeat_file.write(p, (std::streamsize)n); }};
+            const bool real_last = !(last_name.empty() && last_length == 0);
+            process_sequence(h, prm, last_name, last_bases ? last_bases : kNoBases, last_length, out, std::cerr, masking && real_last ? &mask : nullptr,
+                             repeating && real_last ? &repeats : nullptr, &helpers);
         } catch (const PathError &e) { failed = true; failure = e.what; }
     }
     if (failed) { std::cerr << "ribbit-hip: " << failure << "\n"; status = 1; }
@@ -575,11 +623,13 @@ int main(int argc, char **argv) {
            << ", \"stage_ms_summed_over_records\": {\"load\": " << g_stage_ms[0] << ", \"perfect\": " << g_stage_ms[1] << ", \"substitutions\": " << g_stage_ms[2]
            << ", \"anchored\": " << g_stage_ms[3] << ", \"dispatch\": " << g_stage_ms[4] << ", \"refine_and_bed\": " << g_stage_ms[5];
         if (masking) tf << ", \"mask\": " << g_stage_ms[6];
+        if (repeating) tf << ", \"repeats\": " << g_stage_ms[7];
         tf << "}}\n";
     }
     if (std::getenv("RIBBIT_PROFILE"))
         std::cerr << "[stages, ms over all records] load " << g_stage_ms[0] << "  perfect " << g_stage_ms[1] << "  substitutions "
                   << g_stage_ms[2] << "  anchored " << g_stage_ms[3] << "  dispatch " << g_stage_ms[4] << "  refine+BED " << g_stage_ms[5]
-                  << (masking ? "  mask " + std::to_string(g_stage_ms[6]) : std::string()) << "\n";
+                  << (masking ? "  mask " + std::to_string(g_stage_ms[6]) : std::string())
+                  << (repeating ? "  repeats " + std::to_string(g_stage_ms[7]) : std::string()) << "\n";
     return status;
 }
