@@ -11,6 +11,7 @@
  * Conventions
  *   - every call returns 0 on success or a negative RIBBIT_E_* code; ribbit_hip_last_error()
  *     returns a human-readable message for the last failure on the calling thread;
+ *   - no entry point lets a C++ exception out; out of host memory is reported as RIBBIT_E_NOMEM;
  *   - a handle is bound to one GPU and one HIP stream and is single-thread-affine;
  *   - there is NO CPU fallback: if no gfx950 device is usable every call fails loudly;
  *   - host arrays returned through `T **out` are owned by the handle and stay valid until the

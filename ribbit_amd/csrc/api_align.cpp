@@ -6,7 +6,7 @@ namespace rbapi {
 
 // longestContinuousMatches of every dispatched seed, one GPU launch (a13)
 int build_longest_runs(RibbitHandle *h) {
-    if (h->longest_valid) return RIBBIT_OK;
+    if (h->rec.longest_valid) return RIBBIT_OK;
     int rc = advance_to_anchored(h);
     if (rc) return rc;
     if ((rc = bind_device(h))) return rc;
@@ -36,7 +36,7 @@ int build_longest_runs(RibbitHandle *h) {
         HIP_TRY(hipStreamSynchronize(h->stream));
         on_threads([&](size_t lo, size_t hi) { std::memcpy(h->longest_runs.data() + lo, h->h_longest_stage.p + lo, (hi - lo) * sizeof(int32_t)); });
     }
-    h->longest_valid = true;
+    h->rec.longest_valid = true;
     return RIBBIT_OK;
 }
 
@@ -75,7 +75,7 @@ int best_rows_of(RibbitHandle *h, const RibbitRefineParams &prm, const rb::SeedV
         if ((rc = h->d_sym.ensure((size_t)h->length + 16))) return rc;
         if ((rc = h->d_seeds_small.ensure(jobs.size()))) return rc;      // (d_seeds holds the dispatch list: the small-motif scan beside this one reads it)
         if ((rc = h->d_best.ensure(jobs.size()))) return rc;
-        if (!h->sym_valid) { rb::launch_sym(h->dev_ascii_src, h->length, h->d_sym.p, h->stream); HIP_TRY(hipGetLastError()); h->sym_valid = true; }
+        if (!h->rec.sym_valid) { rb::launch_sym(h->dev_ascii_src, h->length, h->d_sym.p, h->stream); HIP_TRY(hipGetLastError()); h->rec.sym_valid = true; }
         HIP_TRY(hipMemcpyAsync(h->d_seeds_small.p, jobs.data(), jobs.size() * sizeof(RibbitSeed), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(hipMemsetAsync(h->d_best.p, 0, jobs.size() * sizeof(unsigned long long), h->stream));
         // 64-row slices of every seed: {job, first row}
@@ -101,7 +101,7 @@ int best_rows_of(RibbitHandle *h, const RibbitRefineParams &prm, const rb::SeedV
 }
 
 int build_best_rows(RibbitHandle *h, const RibbitRefineParams &prm) {
-    if (h->best_rows_valid) return RIBBIT_OK;
+    if (h->rec.best_rows_valid) return RIBBIT_OK;
     int rc = build_longest_runs(h);
     if (rc) return rc;
     {
@@ -119,7 +119,7 @@ int build_best_rows(RibbitHandle *h, const RibbitRefineParams &prm) {
         for (std::thread &th : pool) th.join();
     }
     if ((rc = best_rows_of(h, prm, h->dispatch, h->longest_runs.data(), h->best_rows.data()))) return rc;
-    h->best_rows_valid = true;
+    h->rec.best_rows_valid = true;
     return RIBBIT_OK;
 }
 
@@ -128,7 +128,7 @@ int build_best_rows(RibbitHandle *h, const RibbitRefineParams &prm) {
 // `stream`: where its copies and its kernel go (default: the handle's).  With another stream it may run beside build_best_rows on
 // another thread, PROVIDED the longest runs and the symbols are there already (scan_seeds_side_by_side sees to that).
 int build_small_motifs(RibbitHandle *h, const RibbitRefineParams &prm, hipStream_t stream) {
-    if (h->small_valid) return RIBBIT_OK;
+    if (h->rec.small_valid) return RIBBIT_OK;
     if (!stream) stream = h->stream;
     int rc = build_longest_runs(h);
     if (rc) return rc;
@@ -158,7 +158,7 @@ int build_small_motifs(RibbitHandle *h, const RibbitRefineParams &prm, hipStream
         if ((rc = h->d_sym.ensure((size_t)h->length + 16)) || (rc = h->d_small_head.ensure(4 * n)) ||
             (rc = h->d_small_records.ensure(4 * cap)) || (rc = h->d_small_count.ensure(4)))
             return rc;
-        if (!h->sym_valid) { rb::launch_sym(h->dev_ascii_src, h->length, h->d_sym.p, stream); HIP_TRY(hipGetLastError()); h->sym_valid = true; }
+        if (!h->rec.sym_valid) { rb::launch_sym(h->dev_ascii_src, h->length, h->d_sym.p, stream); HIP_TRY(hipGetLastError()); h->rec.sym_valid = true; }
         HIP_TRY(hipMemsetAsync(h->d_small_count.p, 0, 4 * sizeof(uint32_t), stream));
         HIP_TRY(hipMemsetAsync(h->d_small_head.p, 0xff, 4 * n * sizeof(int32_t), stream));      // flags -1: no device result
         rb::launch_small_motifs(h->d_sym.p, h->length, h->d_seeds.p, (int64_t)n, lim, h->d_small_records.p, (uint32_t)cap, h->d_small_count.p,
@@ -178,7 +178,7 @@ int build_small_motifs(RibbitHandle *h, const RibbitRefineParams &prm, hipStream
     }
     static const bool profile = std::getenv("RIBBIT_PROFILE") != nullptr;
     if (profile) std::fprintf(stderr, "[small motifs] %zu dispatched seeds looked at on the GPU, %zu records, %.1f ms incl. transfers\n", n, h->n_small_records, now_ms() - t0);
-    h->small_valid = true;
+    h->rec.small_valid = true;
     return RIBBIT_OK;
 }
 
@@ -189,13 +189,13 @@ int build_small_motifs(RibbitHandle *h, const RibbitRefineParams &prm, hipStream
 int scan_seeds_side_by_side(RibbitHandle *h, const RibbitRefineParams &prm) {
     int rc = build_longest_runs(h);
     if (rc) return rc;
-    if (h->best_rows_valid || h->small_valid || h->dispatch.size() < 200000) {      // (a small record: not worth a thread)
+    if (h->rec.best_rows_valid || h->rec.small_valid || h->dispatch.size() < 200000) {      // (a small record: not worth a thread)
         if ((rc = build_best_rows(h, prm))) return rc;
         return build_small_motifs(h, prm);
     }
     if ((rc = bind_device(h))) return rc;
     if ((rc = h->d_sym.ensure((size_t)h->length + 16))) return rc;
-    if (!h->sym_valid) { rb::launch_sym(h->dev_ascii_src, h->length, h->d_sym.p, h->stream); HIP_TRY(hipGetLastError()); h->sym_valid = true; }
+    if (!h->rec.sym_valid) { rb::launch_sym(h->dev_ascii_src, h->length, h->d_sym.p, h->stream); HIP_TRY(hipGetLastError()); h->rec.sym_valid = true; }
     HIP_TRY(hipStreamSynchronize(h->stream));
     int small_rc = RIBBIT_OK;
     std::string small_error;
@@ -456,7 +456,7 @@ void ribbit_refine_params_default(RibbitRefineParams *p, int32_t min_motif, int3
     if (p) fill_refine_defaults(p, min_motif, max_motif);
 }
 
-int ribbit_hip_seed_longest_runs(RibbitHandle *h, const int32_t **out, size_t *n) {
+int ribbit_hip_seed_longest_runs(RibbitHandle *h, const int32_t **out, size_t *n) { return guarded("the longest runs", [&]() -> int {
     if (!h || !out || !n) return fail(RIBBIT_E_ARG, "null argument");
     if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
     int rc = build_longest_runs(h);
@@ -464,10 +464,10 @@ int ribbit_hip_seed_longest_runs(RibbitHandle *h, const int32_t **out, size_t *n
     *out = h->longest_runs.data();
     *n = h->longest_runs.size();
     return RIBBIT_OK;
-}
+}); }
 
 int ribbit_hip_ssw_passes(RibbitHandle *h, const RibbitAlignJob *jobs, size_t n, const char *motif_pool, size_t pool_len,
-                          int32_t mask_len, RibbitSswEnds *out) {
+                          int32_t mask_len, RibbitSswEnds *out) { return guarded("the alignments", [&]() -> int {
     if (!h || (n && (!jobs || !out || !motif_pool))) return fail(RIBBIT_E_ARG, "null argument");
     if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
     for (size_t j = 0; j < n; ++j)
@@ -479,10 +479,10 @@ int ribbit_hip_ssw_passes(RibbitHandle *h, const RibbitAlignJob *jobs, size_t n,
     static_assert(sizeof(RibbitSswEnds) == sizeof(rb::SswEnds), "ends record layout");
     if (n) std::memcpy(out, ends.data(), n * sizeof(RibbitSswEnds));
     return RIBBIT_OK;
-}
+}); }
 
 int ribbit_hip_ssw_align_jobs(RibbitHandle *h, const RibbitAlignJob *jobs, size_t n, const char *motif_pool, size_t pool_len, int32_t mask_len,
-                              RibbitAlignment *out, char *cigars, size_t cap, int64_t *cigar_off, int32_t *on_gpu) {
+                              RibbitAlignment *out, char *cigars, size_t cap, int64_t *cigar_off, int32_t *on_gpu) { return guarded("the alignments", [&]() -> int {
     if (!h || (n && (!jobs || !out || !motif_pool || !cigars || !cigar_off))) return fail(RIBBIT_E_ARG, "null argument");
     if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
     for (size_t j = 0; j < n; ++j)
@@ -526,14 +526,14 @@ int ribbit_hip_ssw_align_jobs(RibbitHandle *h, const RibbitAlignJob *jobs, size_
         at += r.cigar.size() + 1;
     }
     return RIBBIT_OK;
-}
+}); }
 
 int ribbit_hip_refine_jobs(RibbitHandle *h, const RibbitRefineParams *prm, const RibbitAlignJob **jobs, size_t *n,
-                           const char **motif_pool) {
+                           const char **motif_pool) { return guarded("the alignment jobs", [&]() -> int {
     if (!h || !prm || !jobs || !n || !motif_pool) return fail(RIBBIT_E_ARG, "null argument");
     if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
-    h->best_rows_valid = false;            // depends on prm's thresholds
-    h->small_valid = false;
+    h->rec.best_rows_valid = false;            // depends on prm's thresholds
+    h->rec.small_valid = false;
     int rc = build_best_rows(h, *prm);
     if (rc) return rc;
     if ((rc = build_small_motifs(h, *prm))) return rc;
@@ -543,12 +543,12 @@ int ribbit_hip_refine_jobs(RibbitHandle *h, const RibbitRefineParams *prm, const
     *n = h->jobs.size();
     *motif_pool = h->motif_pool.c_str();
     return RIBBIT_OK;
-}
+}); }
 
 int ribbit_host_refine_jobs(const RibbitScanParams *params, const RibbitRefineParams *prm, int64_t length,
                             const uint32_t *hi, const uint32_t *lo, const uint32_t *brk, size_t nwords,
                             const uint32_t *xa, size_t xa_stride, const RibbitSeed *dispatch, size_t n_dispatch,
-                            RibbitAlignJob **jobs, size_t *n_jobs, char **motif_pool, size_t *pool_len) {
+                            RibbitAlignJob **jobs, size_t *n_jobs, char **motif_pool, size_t *pool_len) { return guarded("the alignment jobs", [&]() -> int {
     if (!params || !prm || !jobs || !n_jobs || !motif_pool || !pool_len || (n_dispatch && !dispatch)) return fail(RIBBIT_E_ARG, "null argument");
     if (length > 0 && (!hi || !lo || !brk)) return fail(RIBBIT_E_ARG, "null plane");
     if (nwords < (size_t)(length / 32 + 1) || (xa && xa_stride < (size_t)(length / 32 + 1))) return fail(RIBBIT_E_ARG, "planes too short");
@@ -606,10 +606,10 @@ int ribbit_host_refine_jobs(const RibbitScanParams *params, const RibbitRefinePa
     if (!out.empty()) std::memcpy(*jobs, out.data(), out.size() * sizeof(RibbitAlignJob));
     std::memcpy(*motif_pool, pool.c_str(), pool.size() + 1);
     return RIBBIT_OK;
-}
+}); }
 
 int ribbit_host_longest_runs(const RibbitScanParams *params, int64_t length, const uint32_t *hi, const uint32_t *lo,
-                             const uint32_t *brk, size_t nwords, const RibbitSeed *seeds, size_t n, int32_t *out) {
+                             const uint32_t *brk, size_t nwords, const RibbitSeed *seeds, size_t n, int32_t *out) { return guarded("the longest runs", [&]() -> int {
     if (!params || (n && (!seeds || !out)) || (length > 0 && (!hi || !lo || !brk))) return fail(RIBBIT_E_ARG, "null argument");
     if (nwords < (size_t)(length / 32 + 1) + (size_t)(params->max_motif + 2) / 32 + 2)
         return fail(RIBBIT_E_ARG, "planes too short (zero padding past the record)");
@@ -626,7 +626,7 @@ int ribbit_host_longest_runs(const RibbitScanParams *params, int64_t length, con
         out[i] = rb::longest_run_host(hp, seeds[i].mlen, seeds[i].start, seeds[i].end);
     }
     return RIBBIT_OK;
-}
+}); }
 
 void ribbit_refine_jobs_free(RibbitAlignJob *jobs, char *motif_pool) {
     std::free(jobs);
@@ -634,7 +634,7 @@ void ribbit_refine_jobs_free(RibbitAlignJob *jobs, char *motif_pool) {
 }
 
 int ribbit_ssw_align(const char *query, int32_t query_len, const char *ref, int32_t ref_len, int32_t mask_len,
-                     RibbitAlignment *out, char *cigar, size_t cap) {
+                     RibbitAlignment *out, char *cigar, size_t cap) { return guarded("the alignment", [&]() -> int {
     if (!query || !ref || !out || (cap && !cigar) || query_len < 0 || ref_len < 0) return fail(RIBBIT_E_ARG, "bad argument");
     rb::SswResult r;
     rb::ssw_align(query, query_len, ref, ref_len, mask_len, r);
@@ -649,10 +649,10 @@ int ribbit_ssw_align(const char *query, int32_t query_len, const char *ref, int3
         cigar[cap - 1] = 0;
     }
     return RIBBIT_OK;
-}
+}); }
 
 int ribbit_debug_ssw_align_periodic(const char *query, int32_t query_len, const char *motif, int32_t atom, int32_t ref_len, int32_t mask_len,
-                                    RibbitAlignment *out, char *cigar, size_t cap) {
+                                    RibbitAlignment *out, char *cigar, size_t cap) { return guarded("the alignment", [&]() -> int {
     if (!query || !motif || !out || (cap && !cigar) || query_len < 0 || ref_len < 0 || atom <= 0) return fail(RIBBIT_E_ARG, "bad argument");
     rb::SswResult r;
     rb::ssw_align_periodic(query, query_len, motif, atom, ref_len, mask_len, r);
@@ -667,13 +667,13 @@ int ribbit_debug_ssw_align_periodic(const char *query, int32_t query_len, const 
         cigar[cap - 1] = 0;
     }
     return RIBBIT_OK;
-}
+}); }
 
 int ribbit_hip_small_motifs(RibbitHandle *h, const RibbitRefineParams *prm, const int32_t **head, size_t *n_seeds,
-                            const uint32_t **records, size_t *n_records) {
+                            const uint32_t **records, size_t *n_records) { return guarded("the small-motif scan", [&]() -> int {
     if (!h || !prm || !head || !n_seeds || !records || !n_records) return fail(RIBBIT_E_ARG, "null argument");
     if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
-    h->small_valid = false;                // depends on prm's thresholds
+    h->rec.small_valid = false;                // depends on prm's thresholds
     const int rc = build_small_motifs(h, *prm);
     if (rc) return rc;
     *head = h->small_head.p;
@@ -681,7 +681,7 @@ int ribbit_hip_small_motifs(RibbitHandle *h, const RibbitRefineParams *prm, cons
     *records = h->small_records.p;
     *n_records = h->n_small_records;
     return RIBBIT_OK;
-}
+}); }
 
 void ribbit_debug_alignment_counters(int64_t out[3]) {
     long a = 0, b = 0, c = 0;

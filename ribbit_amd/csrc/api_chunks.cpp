@@ -4,7 +4,7 @@
 
 extern "C" {
 
-int ribbit_hip_xa_words(RibbitHandle *h, int64_t word_lo, int64_t word_hi, uint32_t *out) {
+int ribbit_hip_xa_words(RibbitHandle *h, int64_t word_lo, int64_t word_hi, uint32_t *out) { return guarded("the composed planes", [&]() -> int {
     if (!h || !out) return fail(RIBBIT_E_ARG, "null argument");
     if (!h->loaded || !h->d_xa.p || h->xa_stride == 0) return fail(RIBBIT_E_STATE, "the anchored kernel has not run on this record");
     if (word_lo < 0 || word_hi < word_lo || word_hi > h->xa_stride) return fail(RIBBIT_E_ARG, "word range outside the planes");
@@ -17,9 +17,9 @@ int ribbit_hip_xa_words(RibbitHandle *h, int64_t word_lo, int64_t word_hi, uint3
                              w * sizeof(uint32_t), nm, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return RIBBIT_OK;
-}
+}); }
 
-int ribbit_hip_xa_words_strided(RibbitHandle *h, int64_t word_lo, int64_t word_hi, uint32_t *out, int64_t out_stride) {
+int ribbit_hip_xa_words_strided(RibbitHandle *h, int64_t word_lo, int64_t word_hi, uint32_t *out, int64_t out_stride) { return guarded("the composed planes", [&]() -> int {
     if (!h || !out) return fail(RIBBIT_E_ARG, "null argument");
     if (!h->loaded || !h->d_xa.p || h->xa_stride == 0) return fail(RIBBIT_E_STATE, "the anchored kernel has not run on this record");
     if (word_lo < 0 || word_hi < word_lo || word_hi > h->xa_stride || out_stride < word_hi - word_lo) return fail(RIBBIT_E_ARG, "word range outside the planes");
@@ -32,11 +32,11 @@ int ribbit_hip_xa_words_strided(RibbitHandle *h, int64_t word_lo, int64_t word_h
                              w * sizeof(uint32_t), nm, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return RIBBIT_OK;
-}
+}); }
 
 // One window stage of one chunk of a longer record, on the device end to end (include/ribbit_hip.h).
 int ribbit_hip_stage_calls_chunk(RibbitHandle *h, int stage, int64_t own_lo, int64_t own_hi, int64_t pos_offset, int64_t record_length,
-                                 RibbitChunkCalls *out) {
+                                 RibbitChunkCalls *out) { return guarded("the chunk's window stage", [&]() -> int {
     if (!h || !out) return fail(RIBBIT_E_ARG, "null argument");
     if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
     if (stage != RIBBIT_STAGE_SUBST && stage != RIBBIT_STAGE_ANCHORED) return fail(RIBBIT_E_ARG, "stage must be RIBBIT_STAGE_SUBST or RIBBIT_STAGE_ANCHORED");
@@ -74,7 +74,7 @@ int ribbit_hip_stage_calls_chunk(RibbitHandle *h, int stage, int64_t own_lo, int
     const int which = stage == RIBBIT_STAGE_SUBST ? 1 : 2;
     if (which == 2 && (rc = prepare_anchored(h))) return rc;
     if ((rc = window_stage_device(h, which, false, which == 1 ? rb::subst_seedlen_cutoff : rb::anchored_seedlen_cutoff, &dc, &cw))) return rc;
-    if (which == 2) h->xa_on_device = true;
+    if (which == 2) h->rec.xa_on_device = true;
     out->calls = dc.calls; out->n = dc.n;
     out->pend = dc.pend;
     out->tail_pend = dc.tail_pend;
@@ -84,7 +84,7 @@ int ribbit_hip_stage_calls_chunk(RibbitHandle *h, int stage, int64_t own_lo, int
     out->dev_pend = dc.pend ? h->d_pend.p : nullptr;
     out->streaks = h->last_streaks;
     return RIBBIT_OK;
-}
+}); }
 
 // The merging rank's half of the chunk-sharded path: the three seed-list merges and the dispatch merge over what the
 // chunks kept (include/ribbit_hip.h).
@@ -104,7 +104,8 @@ int ribbit_host_merge_chunks(const RibbitScanParams *params, int64_t length,
         if (pt.subst.inexact || pt.anchored.inexact) return fail(RIBBIT_E_ARG, "chunk %zu is marked inexact (left halo too short): scan it again with a longer halo", p);
     }
     std::memset(out, 0, sizeof *out);
-    try {
+    // (the checks above only read: what follows is what allocates, and `out` is now safe to free)
+    const int ret = guarded("the merge of the chunks", [&]() -> int {
         rb::HostPlanes hp;
         hp.resize(length, nwords);
         std::memcpy(hp.hi.data(), hi, nwords * sizeof(uint32_t));
@@ -245,11 +246,10 @@ int ribbit_host_merge_chunks(const RibbitScanParams *params, int64_t length,
             return fail(RIBBIT_E_NOMEM, "out of host memory");
         }
         out->guard_hits = sl.guard_hits;
-    } catch (const std::bad_alloc &) {
-        ribbit_seed_lists_free(out);
-        return fail(RIBBIT_E_NOMEM, "out of host memory in the merge of the chunks");
-    }
-    return RIBBIT_OK;
+        return RIBBIT_OK;
+    });
+    if (ret) ribbit_seed_lists_free(out);
+    return ret;
 }
 
 }  // extern "C"

@@ -119,17 +119,8 @@ int pack_loaded_ascii(RibbitHandle *h, const uint8_t *dev_ascii, int64_t length)
     if (h->copy_pending) { const int rcw = perfect_wait(h); if (rcw) return rcw; }
     h->loaded = false;
     h->dev_ascii_src = dev_ascii;
-    h->runs_valid = h->calls_valid = h->subst_calls_valid = h->anchored_calls_valid = false;
-    h->longest_valid = false;
-    h->best_rows_valid = false;
-    h->small_valid = false;
-    h->sym_valid = false;
-    h->host_planes_valid = false;
-    h->eval_valid = false;
-    h->xa_on_device = false;
-    for (rb::ScanSplit &sp : h->last_split) sp = rb::ScanSplit{};
+    h->rec = RibbitHandle::RecordState{};
     if (h->xa_copy_pending) { (void)hipEventSynchronize(h->ev_xa); h->xa_copy_pending = false; }
-    h->stage_done = STAGE_NONE;
     h->length = length;
     const int64_t nwords = length / 32 + 1;   // word holding position L is included
     h->ntiles = (nwords + rb::TILE_WORDS - 1) / rb::TILE_WORDS;
@@ -162,7 +153,7 @@ int pack_loaded_ascii(RibbitHandle *h, const uint8_t *dev_ascii, int64_t length)
 
 // D2H of the packed planes (3 bits per base), once per record, for the host-side sparse reads
 int ensure_host_planes(RibbitHandle *h) {
-    if (h->host_planes_valid) return RIBBIT_OK;
+    if (h->rec.host_planes_valid) return RIBBIT_OK;
     int rc;
     if ((rc = bind_device(h))) return rc;
     const size_t n = (size_t)(h->ntiles * rb::TILE_WORDS + h->tail_words);
@@ -172,11 +163,21 @@ int ensure_host_planes(RibbitHandle *h) {
     HIP_TRY(hipMemcpyAsync(h->host.brk.data(), h->d_brk.p + rb::LEAD_WORDS, n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->host.index_breaks();
-    h->host_planes_valid = true;
+    h->rec.host_planes_valid = true;
     return RIBBIT_OK;
 }
 
 }  // namespace rbapi
+
+// What is still enqueued is waited for, then the members release what they own (api_internal.h: buffers, then events, then streams).
+RibbitHandle::~RibbitHandle() {
+    delete aux;
+    for (RibbitHandle *fa : feed_aux) delete fa;
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (copy_stream) (void)hipStreamSynchronize(copy_stream);
+    device_free_pending();
+}
 
 extern "C" {
 
@@ -202,13 +203,13 @@ int ribbit_hip_device_count(void) {
     return ok;
 }
 
-int ribbit_hip_device_pci_bus_id(int device, char *out, size_t cap) {
+int ribbit_hip_device_pci_bus_id(int device, char *out, size_t cap) { return guarded("the PCI bus id", [&]() -> int {
     if (!out || cap < 16) return fail(RIBBIT_E_ARG, "bad argument");
     HIP_TRY(hipDeviceGetPCIBusId(out, (int)cap, device));
     return RIBBIT_OK;
-}
+}); }
 
-int ribbit_hip_open(const RibbitScanParams *params, int device, RibbitHandle **out) {
+int ribbit_hip_open(const RibbitScanParams *params, int device, RibbitHandle **out) { return guarded("opening a handle", [&]() -> int {
     if (!params || !out) return fail(RIBBIT_E_ARG, "null argument");
     *out = nullptr;
     if (params->min_motif < 1 || params->max_motif < params->min_motif || params->max_motif > 990)
@@ -229,71 +230,31 @@ int ribbit_hip_open(const RibbitScanParams *params, int device, RibbitHandle **o
     h->min_shift = (params->min_motif > 2) ? params->min_motif - 2 : 1;   // ribbit.cpp:241
     h->max_shift = params->max_motif + 2;                                   // ribbit.cpp:242
     hipError_t err = hipSetDevice(device);
-    if (err == hipSuccess) err = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-    if (err == hipSuccess) err = hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking);
-    if (err == hipSuccess) err = hipEventCreateWithFlags(&h->ev_ready, hipEventDisableTiming);
-    if (err == hipSuccess) err = hipEventCreateWithFlags(&h->ev_xa, hipEventDisableTiming);
-    if (err == hipSuccess) err = hipEventCreateWithFlags(&h->ev_ssw, hipEventDisableTiming);
+    if (err == hipSuccess) err = h->own_stream.create();
+    if (err == hipSuccess) err = h->copy_stream.create();
+    if (err == hipSuccess) err = h->ev_ready.create(hipEventDisableTiming);
+    if (err == hipSuccess) err = h->ev_xa.create(hipEventDisableTiming);
+    if (err == hipSuccess) err = h->ev_ssw.create(hipEventDisableTiming);
     // The upload stream is created by the first upload that uses it.  Measured (bench.py, three handles on one shared
     // compute stream, same box, alternating runs): with an unused upload stream per handle a step takes 0.267 ms, without
     // 0.245 ms (round 1: 0.243), while the scan kernel's own time is unchanged.  Presumably the extra streams change which
     // hardware queue the handles' post streams share, so that the pairing chain no longer overlaps the next scan; that
     // part is inferred, not observed.
-    if (err == hipSuccess) err = hipEventCreateWithFlags(&h->ev_up, hipEventDisableTiming);
-    if (err == hipSuccess) err = hipEventCreateWithFlags(&h->ev_busy, hipEventDisableTiming);
-    for (int i = 0; i < 4 && err == hipSuccess; ++i) err = hipEventCreate(&h->ev_stage[i / 2][i % 2]);
-    if (err == hipSuccess) err = hipEventCreate(&h->ev_planes);
-    for (int i = 0; i < 6 && err == hipSuccess; ++i) err = hipEventCreate(&h->ev[i]);
+    if (err == hipSuccess) err = h->ev_up.create(hipEventDisableTiming);
+    if (err == hipSuccess) err = h->ev_busy.create(hipEventDisableTiming);
+    for (int i = 0; i < 4 && err == hipSuccess; ++i) err = h->ev_stage[i / 2][i % 2].create();
+    if (err == hipSuccess) err = h->ev_planes.create();
+    for (int i = 0; i < 6 && err == hipSuccess; ++i) err = h->ev[i].create();
     if (err != hipSuccess) {
-        delete h;
+        delete h;      // (with what it had created)
         return fail(RIBBIT_E_DEVICE, "device setup failed: %s", hipGetErrorString(err));
     }
     h->stream = h->own_stream;
     *out = h;
     return RIBBIT_OK;
-}
+}); }
 
 int ribbit_hip_close(RibbitHandle *h) {
-    if (!h) return RIBBIT_OK;
-    if (h->aux) { (void)ribbit_hip_close(h->aux); h->aux = nullptr; }
-    for (RibbitHandle *fa : h->feed_aux) (void)ribbit_hip_close(fa);
-    h->feed_aux.clear();
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
-    device_free_pending();
-    h->d_ascii.release(); h->d_hi.release(); h->d_lo.release(); h->d_brk.release();
-    h->d_events.release(); h->d_dense.release(); h->d_counters.release(); h->d_query.release(); h->d_xa.release(); h->d_seeds.release(); h->d_seeds_small.release(); h->d_longest.release(); h->d_sym.release(); h->d_best.release(); h->d_slices.release();
-    h->d_ssw_jobs.release(); h->d_ssw_order.release(); h->d_ssw_out.release(); h->d_ssw_pool.release();
-    h->d_path_items.release(); h->d_path_result.release(); h->d_path_cell_off.release(); h->d_path_ops_off.release(); h->d_path_cells.release();
-    h->d_path_scratch.release(); h->d_path_ops.release(); h->d_path_count.release(); h->h_path_ops.release();
-    h->d_small_head.release(); h->d_small_records.release(); h->d_small_count.release(); h->small_head.release(); h->small_records.release();
-    h->h_events.release(); h->h_counters.release(); h->h_query.release();
-    h->d_pair_table.release(); h->d_run_base.release(); h->d_pair_partial.release(); h->d_pair_status.release();
-    h->d_tj.release(); h->d_dropmap.release();
-    h->h_pub.release(); h->h_runs.release(); h->h_halves.release(); h->d_halves.release();
-    h->d_eval.release(); h->d_first_rev.release(); h->d_word_tmp.release(); h->d_last_word.release(); h->d_bitmap.release();
-    h->d_edge_tmp.release(); h->d_edge_end1.release(); h->d_ws_counters.release(); h->d_group.release(); h->d_sort_keys.release();
-    h->d_sort_vals.release(); h->d_edge_keys.release(); h->d_edge_vals.release(); h->d_edge_keys2.release(); h->d_edge_vals2.release();
-    h->d_min_span.release(); h->d_pend.release(); h->d_flush.release(); h->d_scratch.release();
-    for (int k = 0; k < 2; ++k) { h->h_calls_[k].release(); h->h_flush_[k].release(); h->h_pend_[k].release(); h->h_ws_[k].release(); }
-    h->h_xa.release();
-    h->mg.release(); h->h_seed_stage.release(); h->h_longest_stage.release();
-    h->d_mask_bits.release(); h->d_mask_iv.release(); h->d_mask_text.release(); h->h_mask_iv.release(); h->h_mask_text.release();
-    h->d_rep_iv.release(); h->d_rep_off.release(); h->d_rep_span_row.release(); h->d_rep_scratch.release(); h->d_rep_pick.release();
-    h->d_rep_text.release(); h->h_rep_iv.release(); h->h_rep_pick.release(); h->h_rep_text.release();
-    std::free(h->bed_raw); h->bed_raw = nullptr;
-    if (h->ev_xa) (void)hipEventDestroy(h->ev_xa);
-    if (h->ev_ssw) (void)hipEventDestroy(h->ev_ssw);
-    if (h->ev_up) (void)hipEventDestroy(h->ev_up);
-    if (h->ev_busy) (void)hipEventDestroy(h->ev_busy);
-    for (int i = 0; i < 4; ++i) if (h->ev_stage[i / 2][i % 2]) (void)hipEventDestroy(h->ev_stage[i / 2][i % 2]);
-    if (h->ev_planes) (void)hipEventDestroy(h->ev_planes);
-    if (h->up_stream) { (void)hipStreamSynchronize(h->up_stream); (void)hipStreamDestroy(h->up_stream); }
-    for (int i = 0; i < 6; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-    if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-    if (h->ev_ready) (void)hipEventDestroy(h->ev_ready);
     delete h;
     return RIBBIT_OK;
 }
@@ -306,6 +267,12 @@ int ribbit_hip_set_stream(RibbitHandle *h, void *hip_stream) {
 
 // H2D of the bases on the upload stream (so that it overlaps kernels of other handles on a shared compute stream),
 // then the pack kernel on the compute stream
+static int check_record_args(const RibbitHandle *h, const void *bases, int64_t length) {
+    if (!h || (!bases && length > 0)) return fail(RIBBIT_E_ARG, "null argument");
+    if (length < 0 || length >= ((int64_t)1 << 31) - 64) return fail(RIBBIT_E_ARG, "record length %lld not supported (positions are int32, fasta_utils.cpp:78)", (long long)length);
+    return RIBBIT_OK;
+}
+
 static int upload_and_pack(RibbitHandle *h, const char *ascii, int64_t length) {
     int rc;
     if ((rc = bind_device(h))) return rc;
@@ -313,7 +280,7 @@ static int upload_and_pack(RibbitHandle *h, const char *ascii, int64_t length) {
     if (length) {
         // the previous record's kernels may still read d_ascii
         HIP_TRY(hipEventRecord(h->ev_busy, h->stream));
-        if (!h->up_stream) HIP_TRY(hipStreamCreateWithFlags(&h->up_stream, hipStreamNonBlocking));
+        if (!h->up_stream) HIP_TRY(h->up_stream.create());
         HIP_TRY(hipStreamWaitEvent(h->up_stream, h->ev_busy, 0));
         HIP_TRY(hipMemcpyAsync(h->d_ascii.p, ascii, (size_t)length, hipMemcpyHostToDevice, h->up_stream));
         HIP_TRY(hipEventRecord(h->ev_up, h->up_stream));
@@ -322,36 +289,33 @@ static int upload_and_pack(RibbitHandle *h, const char *ascii, int64_t length) {
     return pack_loaded_ascii(h, h->d_ascii.p, length);
 }
 
-int ribbit_hip_load_record(RibbitHandle *h, const char *ascii, int64_t length) {
-    if (!h || (!ascii && length > 0)) return fail(RIBBIT_E_ARG, "null argument");
-    if (length < 0 || length >= ((int64_t)1 << 31) - 64) return fail(RIBBIT_E_ARG, "record length %lld not supported (positions are int32, fasta_utils.cpp:78)", (long long)length);
+int ribbit_hip_load_record(RibbitHandle *h, const char *ascii, int64_t length) { return guarded("loading a record", [&]() -> int {
+    if (const int bad = check_record_args(h, ascii, length)) return bad;
     h->host_ascii_valid = false;      // not duplicated: refinement fetches the bases back from the device if it runs
     h->host_bases = nullptr;
     return upload_and_pack(h, ascii, length);
-}
+}); }
 
-int ribbit_hip_load_record_pinned(RibbitHandle *h, const char *pinned_ascii, int64_t length) {
-    if (!h || (!pinned_ascii && length > 0)) return fail(RIBBIT_E_ARG, "null argument");
-    if (length < 0 || length >= ((int64_t)1 << 31) - 64) return fail(RIBBIT_E_ARG, "record length %lld not supported", (long long)length);
+int ribbit_hip_load_record_pinned(RibbitHandle *h, const char *pinned_ascii, int64_t length) { return guarded("loading a record", [&]() -> int {
+    if (const int bad = check_record_args(h, pinned_ascii, length)) return bad;
     h->host_ascii_valid = false;
     h->host_bases = pinned_ascii;     // stays the caller's; read again by refinement
     return upload_and_pack(h, pinned_ascii, length);
-}
+}); }
 
-int ribbit_hip_load_record_device(RibbitHandle *h, const void *dev_ascii, int64_t length) {
-    if (!h || (!dev_ascii && length > 0)) return fail(RIBBIT_E_ARG, "null argument");
-    if (length < 0 || length >= ((int64_t)1 << 31) - 64) return fail(RIBBIT_E_ARG, "record length %lld not supported", (long long)length);
+int ribbit_hip_load_record_device(RibbitHandle *h, const void *dev_ascii, int64_t length) { return guarded("loading a record", [&]() -> int {
+    if (const int bad = check_record_args(h, dev_ascii, length)) return bad;
     int rc;
     if ((rc = bind_device(h))) return rc;
     h->host_ascii_valid = false;
     h->host_bases = nullptr;
     return pack_loaded_ascii(h, (const uint8_t *)dev_ascii, length);
-}
+}); }
 
-int ribbit_hip_host_alloc(size_t bytes, void **out) {
+int ribbit_hip_host_alloc(size_t bytes, void **out) { return guarded("the page-locked allocation", [&]() -> int {
     if (!out || !bytes) return fail(RIBBIT_E_ARG, "bad argument");
     return pinned_alloc(bytes, out);
-}
+}); }
 
 int ribbit_hip_host_free(void *p) {
     pinned_free(p);
@@ -375,8 +339,8 @@ int ribbit_hip_debug_set_scan_split(RibbitHandle *h, int32_t kernel, int32_t mot
 
 int ribbit_hip_debug_last_scan_split(RibbitHandle *h, int32_t kernel, int32_t *grid_y, int32_t *motifs_per_block) {
     if (!h || !grid_y || !motifs_per_block || kernel < 0 || kernel >= RIBBIT_SCAN_KERNELS) return fail(RIBBIT_E_ARG, "bad argument");
-    *grid_y = h->last_split[kernel].grid_y;
-    *motifs_per_block = h->last_split[kernel].motifs_per_block;
+    *grid_y = h->rec.last_split[kernel].grid_y;
+    *motifs_per_block = h->rec.last_split[kernel].motifs_per_block;
     return RIBBIT_OK;
 }
 
@@ -393,17 +357,17 @@ int ribbit_hip_set_host_threads(RibbitHandle *h, int32_t threads) {
     return RIBBIT_OK;
 }
 
-int ribbit_hip_host_register(void *p, size_t bytes) {
+int ribbit_hip_host_register(void *p, size_t bytes) { return guarded("registering host memory", [&]() -> int {
     if (!p || !bytes) return fail(RIBBIT_E_ARG, "null argument");
     HIP_TRY(hipHostRegister(p, bytes, hipHostRegisterDefault));
     return RIBBIT_OK;
-}
+}); }
 
-int ribbit_hip_host_unregister(void *p) {
+int ribbit_hip_host_unregister(void *p) { return guarded("unregistering host memory", [&]() -> int {
     if (!p) return fail(RIBBIT_E_ARG, "null argument");
     HIP_TRY(hipHostUnregister(p));
     return RIBBIT_OK;
-}
+}); }
 
 static int query_plane(RibbitHandle *h, int32_t shift, int64_t start, int64_t end, bool want_words, uint32_t *count_out) {
     if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
@@ -427,9 +391,9 @@ static int query_plane(RibbitHandle *h, int32_t shift, int64_t start, int64_t en
     return RIBBIT_OK;
 }
 
-int ribbit_hip_plane_bits(RibbitHandle *h, int32_t shift, int64_t start, int64_t end, uint8_t *out) {
+int ribbit_hip_plane_bits(RibbitHandle *h, int32_t shift, int64_t start, int64_t end, uint8_t *out) { return guarded("the plane query", [&]() -> int {
     if (!h || (!out && end > start)) return fail(RIBBIT_E_ARG, "null argument");
-    if (h->loaded && h->xa_on_device && shift >= h->params.min_motif && shift <= h->params.max_motif) {
+    if (h->loaded && h->rec.xa_on_device && shift >= h->params.min_motif && shift <= h->params.max_motif) {
         // composed plane (fasta_utils.cpp:159): written by the anchored kernel, resident in HBM
         if (start < 0 || end > h->length || start > end) return fail(RIBBIT_E_ARG, "range [%lld,%lld) outside the record", (long long)start, (long long)end);
         if (end == start) return RIBBIT_OK;
@@ -448,20 +412,20 @@ int ribbit_hip_plane_bits(RibbitHandle *h, int32_t shift, int64_t start, int64_t
     const int64_t w0 = start / 32;
     for (int64_t p = start; p < end; ++p) out[p - start] = (h->h_query.p[p / 32 - w0] >> (p & 31)) & 1u;
     return RIBBIT_OK;
-}
+}); }
 
-int ribbit_hip_range_popcount(RibbitHandle *h, int32_t shift, int64_t start, int64_t end, int32_t *count) {
+int ribbit_hip_range_popcount(RibbitHandle *h, int32_t shift, int64_t start, int64_t end, int32_t *count) { return guarded("the plane query", [&]() -> int {
     if (!h || !count) return fail(RIBBIT_E_ARG, "null argument");
     uint32_t c = 0;
     int rc = query_plane(h, shift, start, end, false, &c);
     if (rc) return rc;
     *count = (int32_t)c;
     return RIBBIT_OK;
-}
+}); }
 
 int64_t ribbit_hip_plane_words(const RibbitHandle *h) { return h && h->loaded ? h->length / 32 + 1 : 0; }
 
-int ribbit_hip_packed_plane(RibbitHandle *h, int which, uint32_t *out_words) {
+int ribbit_hip_packed_plane(RibbitHandle *h, int which, uint32_t *out_words) { return guarded("the plane query", [&]() -> int {
     if (!h || !out_words) return fail(RIBBIT_E_ARG, "null argument");
     if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
     if (which < 0 || which > 2) return fail(RIBBIT_E_ARG, "which must be 0, 1 or 2");
@@ -472,9 +436,9 @@ int ribbit_hip_packed_plane(RibbitHandle *h, int which, uint32_t *out_words) {
     HIP_TRY(hipMemcpyAsync(out_words, src, n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return RIBBIT_OK;
-}
+}); }
 
-int ribbit_hip_last_timing_ms(const RibbitHandle *h, int what, double *ms) {
+int ribbit_hip_last_timing_ms(const RibbitHandle *h, int what, double *ms) { return guarded("the timing query", [&]() -> int {
     if (!h || !ms) return fail(RIBBIT_E_ARG, "null argument");
     if (what == 3) { *ms = h->host_ms; return RIBBIT_OK; }
     if (what == 4) { *ms = h->merge_ms; return RIBBIT_OK; }
@@ -503,9 +467,9 @@ int ribbit_hip_last_timing_ms(const RibbitHandle *h, int what, double *ms) {
     HIP_TRY(hipEventElapsedTime(&f, h->ev[2 * what], h->ev[2 * what + 1]));
     *ms = f;
     return RIBBIT_OK;
-}
+}); }
 
-int ribbit_hip_debug_stream_read(RibbitHandle *h, int64_t nbytes, int64_t *bytes_read) {
+int ribbit_hip_debug_stream_read(RibbitHandle *h, int64_t nbytes, int64_t *bytes_read) { return guarded("the stream read", [&]() -> int {
     if (!h || !bytes_read) return fail(RIBBIT_E_ARG, "null argument");
     if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
     int rc;
@@ -520,7 +484,7 @@ int ribbit_hip_debug_stream_read(RibbitHandle *h, int64_t nbytes, int64_t *bytes
     HIP_TRY(hipStreamSynchronize(h->stream));
     *bytes_read = n * 4;
     return RIBBIT_OK;
-}
+}); }
 
 int64_t ribbit_hip_last_event_count(const RibbitHandle *h) { return h ? h->last_event_count : 0; }
 

@@ -23,6 +23,8 @@
 #include <condition_variable>
 #include <cstring>
 #include <deque>
+#include <exception>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -44,6 +46,25 @@ namespace rbapi {
 
 extern thread_local std::string g_last_error;
 int fail(int code, const char *fmt, ...);
+// No entry point lets a C++ exception out (the callers are C, ctypes and the command-line tool: an exception that leaves
+// extern "C" ends the process).  Every extern "C" function of the api_*.cpp files that returns a status is
+//     int ribbit_x(...) { return guarded("x", [&]() -> int {
+//         ... the body, indented as a function's ...
+//     }); }
+// `what` names the operation in the message.  Not guarded, because all they do is check arguments and read or write plain
+// fields of the handle or of globals: ribbit_hip_abi_version, ribbit_hip_device_count (a count, not a status), ribbit_hip_set_stream,
+// ribbit_hip_set_timing, ribbit_hip_set_host_threads, ribbit_hip_debug_set_event_capacity, ribbit_hip_debug_set_scan_split,
+// ribbit_hip_debug_last_scan_split, ribbit_hip_debug_set_repeat_text_budget, ribbit_hip_refine_met_empty_query,
+// ribbit_hip_guard_hits, ribbit_hip_last_event_count, ribbit_hip_plane_words, ribbit_hip_last_error, ribbit_hip_host_free and the
+// other *_free functions, ribbit_*_params_default, the ribbit_debug_* counter readers and setters; and ribbit_hip_close, which is
+// `delete` (a destructor does not throw).  Threads the library starts keep an exception inside themselves where they are made.
+template <typename F>
+int guarded(const char *what, F &&body) {
+    try { return body(); }
+    catch (const std::bad_alloc &) { return fail(RIBBIT_E_NOMEM, "out of host memory in %s", what); }
+    catch (const std::exception &e) { return fail(RIBBIT_E_INTERNAL, "%s: %s", what, e.what()); }
+    catch (...) { return RIBBIT_E_INTERNAL; }
+}
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
         hipError_t e_ = (expr);                                                                    \
@@ -79,7 +100,10 @@ struct DevBuf {
         cap = n;
         return RIBBIT_OK;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
 };
 
 // Page-locked host memory (api_core.cpp).  From PINNED_HUGE_FROM bytes on: anonymous memory advised into 2-MB pages, touched on
@@ -104,8 +128,33 @@ struct PinnedBuf {
         cap = n;
         return RIBBIT_OK;
     }
-    void release() { if (p) pinned_free(p); p = nullptr; cap = 0; }
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() { pinned_free(p); }
 };
+
+// A stream / an event of a handle: created by the handle (OwnedStream::create, OwnedEvent::create), destroyed with it -- a stream
+// after what is still enqueued on it.  Both read as the plain HIP type.
+struct OwnedStream {
+    hipStream_t s = nullptr;
+    OwnedStream() = default;
+    OwnedStream(const OwnedStream &) = delete;
+    OwnedStream &operator=(const OwnedStream &) = delete;
+    ~OwnedStream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+    hipError_t create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+    operator hipStream_t() const { return s; }
+};
+struct OwnedEvent {
+    hipEvent_t e = nullptr;
+    OwnedEvent() = default;
+    OwnedEvent(const OwnedEvent &) = delete;
+    OwnedEvent &operator=(const OwnedEvent &) = delete;
+    ~OwnedEvent() { if (e) (void)hipEventDestroy(e); }
+    hipError_t create(unsigned flags = hipEventDefault) { return hipEventCreateWithFlags(&e, flags); }
+    operator hipEvent_t() const { return e; }
+};
+struct FreeDeleter { void operator()(void *p) const { std::free(p); } };
 
 inline double now_ms() {
     using namespace std::chrono;
@@ -119,21 +168,46 @@ enum Stage { STAGE_NONE = 0, STAGE_PERFECT = 1, STAGE_SUBST = 2, STAGE_ANCHORED 
 using namespace rbapi;
 
 struct RibbitHandle {
+    // ORDER MATTERS HERE, and only here: members are destroyed last to first, and the handle gives up its buffers first, then its
+    // events, then its streams.  So the streams are declared first, the events second, and everything that owns memory (DevBuf,
+    // PinnedBuf, bed_raw) after them.  ~RibbitHandle (api_core.cpp) runs before any member goes: it drains the streams.
+    OwnedStream own_stream;
+    OwnedStream copy_stream;             // post stream of the perfect scan: pairing kernels and result copies, so that they overlap
+                                         // the next record's kernels when several handles share `stream`
+    OwnedStream up_stream;               // uploads: the next record's bases travel while this record's kernels run (created by the first upload)
+    OwnedEvent ev_ready;                 // pairing done, counters and status on the host
+    OwnedEvent ev[6];                    // 0/1 pack, 2/3 scan kernel, 4/5 whole GPU side of the last scan
+    OwnedEvent ev_xa;                    // the copy of the composed planes has landed
+    OwnedEvent ev_ssw;                   // orders the longest alignment class (on the copy stream) against the compute stream
+    OwnedEvent ev_up, ev_busy;
+    OwnedEvent ev_stage[2][2];           // scan kernel of the substitution [0] / anchored [1] stage
+    OwnedEvent ev_planes;                // between the two kernels of the anchored stage (planes | window scan)
+
+    RibbitHandle() = default;
+    RibbitHandle(const RibbitHandle &) = delete;
+    RibbitHandle &operator=(const RibbitHandle &) = delete;
+    ~RibbitHandle();
+
     RibbitScanParams params{};
     int device = 0;
     int min_shift = 1, max_shift = 102;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    hipStream_t copy_stream = nullptr;   // post stream of the perfect scan: pairing kernels and result copies, so that they overlap
-                                         // the next record's kernels when several handles share `stream`
-    hipEvent_t ev_ready = nullptr;       // pairing done, counters and status on the host
-    hipEvent_t ev[6] = {};        // 0/1 pack, 2/3 scan kernel, 4/5 whole GPU side of the last scan
+    hipStream_t stream = nullptr;        // own_stream, or the caller's (ribbit_hip_set_stream): not owned
+    // everything here is forgotten when a record is loaded; a cached result's flag belongs here
+    struct RecordState {
+        bool runs_valid = false, calls_valid = false, subst_calls_valid = false, anchored_calls_valid = false;
+        bool longest_valid = false, best_rows_valid = false, small_valid = false;
+        bool sym_valid = false;               // d_sym holds the loaded record
+        bool host_planes_valid = false;
+        bool eval_valid = false;              // d_eval / d_first_rev belong to the loaded record
+        bool xa_on_device = false;            // the anchored kernel has written the composed planes of the loaded record
+        int stage_done = STAGE_NONE;          // how far the seed lists have been advanced
+        rb::ScanSplit last_split[RIBBIT_SCAN_KERNELS];   // the split each scan kernel last ran with on the loaded record
+    } rec;
     bool have_timing[3] = {false, false, false};
     bool timing = true;           // record the HIP events behind ribbit_hip_last_timing_ms (each costs a barrier packet on the stream)
     double host_ms = 0.0;         // post-processing of the last scan after its pairing (device state machine, sort, read-back), wall clock
     double merge_ms = 0.0;        // sequential host merge of the last window stage, wall clock
     double subst_merge_ms = 0.0;  // ... of the substitution stage when ribbit_hip_seeds_anchored ran both
-    bool xa_on_device = false;    // the anchored kernel has written the composed planes of the loaded record
     unsigned host_threads = 0;    // worker threads of the host stages (0 = RIBBIT_THREADS or min(cores, 16))
 
     bool loaded = false;
@@ -153,7 +227,6 @@ struct RibbitHandle {
     // host copy of the packed planes: answers the sparse, latency-bound range reads of the
     // sequential merges (retainNestedSeed & co) without a GPU round trip per query
     rb::HostPlanes host;
-    bool host_planes_valid = false;
 
     // ordered view of the last event collection
     int64_t last_event_count = 0;
@@ -161,7 +234,6 @@ struct RibbitHandle {
     std::vector<uint64_t> chunk_table;   // (offset, count) per (motif, tile)
     size_t table_ntile = 0;
 
-    bool runs_valid = false, calls_valid = false;
     std::vector<RibbitRun> runs;          // chunk-local pairing (multi-GPU path)
     // device-side pairing of the perfect scan: scratch + the pinned run list it lands in
     DevBuf<uint64_t> d_pair_table;
@@ -173,14 +245,12 @@ struct RibbitHandle {
     bool pair_pending = false;
     size_t debug_first_cap = 0;           // ribbit_hip_debug_set_event_capacity: first guess of the event capacity (tests of the overflow path)
     int32_t debug_split[RIBBIT_SCAN_KERNELS] = {};   // ribbit_hip_debug_set_scan_split: motifs per block of each scan kernel (0 = automatic)
-    rb::ScanSplit last_split[RIBBIT_SCAN_KERNELS];   // the split each scan kernel last ran with on the loaded record
     bool counters_clean = false;          // d_counters zeroed by the pack kernel and not used since
     bool copy_pending = false;            // result copies enqueued but not yet waited for (ribbit_hip_scan_perfect_end with wait = 0)
     DevBuf<RibbitRun> d_halves;
     size_t n_runs = 0, n_halves = 0;
     // window stages on the device (window_stage.hip): scratch of the streak -> call pipeline and its pinned results
     DevBuf<uint32_t> d_eval, d_first_rev, d_word_tmp, d_last_word, d_bitmap, d_edge_tmp, d_edge_end1, d_ws_counters;
-    bool eval_valid = false;              // d_eval / d_first_rev belong to the loaded record
     DevBuf<uint64_t> d_group, d_sort_keys, d_sort_vals, d_edge_keys, d_edge_vals, d_edge_keys2, d_edge_vals2;
     DevBuf<int32_t> d_min_span, d_pend, d_tj;
     DevBuf<uint32_t> d_dropmap;           // group filter of the anchored scan: ends of the groups it dropped
@@ -200,23 +270,13 @@ struct RibbitHandle {
         PinnedBuf<RibbitSeed> h_own;
         PinnedBuf<uint32_t> h_range_out, h_log, h_head_log, h_counts, h_sync;      // h_sync: read and written by the lanes while the kernel runs
         uint32_t *h_sync_dev = nullptr;
-        void release() {
-            d_perfect.release(); d_subst.release(); d_own.release(); d_type0.release(); d_cuts.release(); d_first.release(); d_range_out.release();
-            d_log.release(); d_head_log.release(); d_counts.release(); d_scratch.release();
-            h_own.release(); h_range_out.release(); h_log.release(); h_head_log.release(); h_counts.release(); h_sync.release(); h_sync_dev = nullptr;
-        }
     } mg;
-    hipEvent_t ev_xa = nullptr;        // the copy of the composed planes has landed
-    hipEvent_t ev_ssw = nullptr;       // orders the longest alignment class (on the copy stream) against the compute stream
     bool xa_copy_pending = false;
     int64_t last_streaks = 0, last_calls = 0, last_edge_calls = 0;
     rb::CallVec perfect_calls;
-    bool subst_calls_valid = false;
     rb::CallVec subst_calls;
-    bool anchored_calls_valid = false;
     rb::CallVec anchored_calls;
     rb::SeedVec dispatch;
-    bool longest_valid = false;
     std::vector<int32_t> longest_runs;
     DevBuf<RibbitSeed> d_seeds;
     DevBuf<RibbitSeed> d_seeds_small;     // the consensus-row scan's jobs (the small-motif scan beside it reads d_seeds: the dispatch list as build_longest_runs left it)
@@ -224,13 +284,11 @@ struct RibbitHandle {
     PinnedBuf<int32_t> h_longest_stage;   // ... and the longest runs on their way down
     DevBuf<int32_t> d_longest;
     DevBuf<uint8_t> d_sym;
-    bool sym_valid = false;                                 // d_sym holds the loaded record
     DevBuf<uint32_t> d_small_records, d_small_count;        // possibleMotifs of the dispatched seeds (small_motifs.hip)
     DevBuf<int32_t> d_small_head;
     PinnedBuf<int32_t> small_head;                          // 4 per dispatched seed; flags (4 i + 3) != 0: no device result
     PinnedBuf<uint32_t> small_records;
     size_t n_small_records = 0;
-    bool small_valid = false;
     DevBuf<unsigned long long> d_best;
     DevBuf<int32_t> d_slices;
     DevBuf<int32_t> d_ssw_jobs, d_ssw_order, d_ssw_out;   // batched striped passes (ssw_kernels.hip)
@@ -242,7 +300,6 @@ struct RibbitHandle {
     PinnedBuf<uint32_t> h_path_ops;
     std::vector<rb::SswPath> ssw_paths;                    // per job of h->jobs: the path the GPU found (ops == null: none)
     std::vector<rb::SswEnds> ssw_ends;                     // per job of h->jobs; flag -1 = not computed on the GPU          // {job, first row} per 64-row slice of the long-motif seeds
-    bool best_rows_valid = false;
     std::vector<int32_t> best_rows;       // per dispatch seed: mostFrequentLongerMotif's window start, or -1
     std::vector<RibbitAlignJob> jobs;
     std::string motif_pool;
@@ -250,18 +307,13 @@ struct RibbitHandle {
     std::string host_ascii;   // the record's bases on the host when they had to be fetched back (refinement slices them for the aligner)
     bool host_ascii_valid = false;
     const char *host_bases = nullptr;     // where refinement reads the bases: the caller's page-locked buffer (load_record_pinned) or host_ascii
-    hipStream_t up_stream = nullptr;      // uploads: the next record's bases travel while this record's kernels run
-    hipEvent_t ev_up = nullptr, ev_busy = nullptr;
-    hipEvent_t ev_stage[2][2] = {};       // scan kernel of the substitution [0] / anchored [1] stage
-    hipEvent_t ev_planes = nullptr;       // between the two kernels of the anchored stage (planes | window scan)
     bool planes_timing_valid = false;     // ev_stage[1][0] .. ev_planes .. ev_stage[1][1] bracket the two kernels of one run
     bool have_stage_timing[2] = {false, false};
     const uint8_t *dev_ascii_src = nullptr;
     std::string bed;
-    char *bed_raw = nullptr;              // the text of the last refinement when its pieces were joined (join_pieces: storage the copying threads touch first)
+    std::unique_ptr<char[], FreeDeleter> bed_raw;   // the text of the last refinement when its pieces were joined (join_pieces: storage the copying threads touch first)
     size_t bed_raw_len = 0, bed_raw_cap = 0;
     bool bed_in_raw = false;              // the last ribbit_hip_refine_bed returned bed_raw, not bed
-    int stage_done = STAGE_NONE;          // how far the seed lists have been advanced
     rb::SeedLists lists;
     bool refine_met_empty_query = false;  // the last ribbit_hip_refine_bed on this handle met an alignment with an empty query (ribbit_hip_refine_met_empty_query)
     // the masked body of the loaded record (api_mask.cpp): coverage bitmap, intervals, the text on the device and on its way up

@@ -3,8 +3,6 @@
 // stream; the host twin and the BED row parser need no GPU.
 #include "api_internal.h"
 
-#include <exception>
-
 namespace {
 
 // width of a line as the format kernel takes it: 1 .. length (0 and anything longer: the whole body on one line)
@@ -174,34 +172,16 @@ extern "C" {
 
 int ribbit_hip_mask_record(RibbitHandle *h, const int32_t *intervals, size_t n, int32_t mode, int32_t line_width,
                            const char **text, size_t *len) {
-    try {
-        return mask_record_impl(h, intervals, n, mode, line_width, text, len);
-    } catch (const std::bad_alloc &) {          // nothing may unwind through the C boundary
-        return fail(RIBBIT_E_NOMEM, "out of host memory in the mask");
-    } catch (const std::exception &e) {
-        return fail(RIBBIT_E_INTERNAL, "mask: %s", e.what());
-    }
+    return guarded("the mask", [&]() -> int { return mask_record_impl(h, intervals, n, mode, line_width, text, len); });
 }
 
 int ribbit_host_mask_record(const char *sequence, int64_t length, const int32_t *intervals, size_t n, int32_t mode,
                             int32_t line_width, char **text, size_t *len) {
-    try {
-        return host_mask_record_impl(sequence, length, intervals, n, mode, line_width, text, len);
-    } catch (const std::bad_alloc &) {
-        return fail(RIBBIT_E_NOMEM, "out of host memory in the mask");
-    } catch (const std::exception &e) {
-        return fail(RIBBIT_E_INTERNAL, "mask: %s", e.what());
-    }
+    return guarded("the mask", [&]() -> int { return host_mask_record_impl(sequence, length, intervals, n, mode, line_width, text, len); });
 }
 
 int ribbit_bed_intervals(const char *text, size_t len, int32_t **pairs, size_t *n) {
-    try {
-        return bed_intervals_impl(text, len, pairs, n);
-    } catch (const std::bad_alloc &) {
-        return fail(RIBBIT_E_NOMEM, "out of host memory reading BED rows");
-    } catch (const std::exception &e) {
-        return fail(RIBBIT_E_INTERNAL, "BED rows: %s", e.what());
-    }
+    return guarded("reading BED rows", [&]() -> int { return bed_intervals_impl(text, len, pairs, n); });
 }
 
 void ribbit_intervals_free(int32_t *pairs) { std::free(pairs); }

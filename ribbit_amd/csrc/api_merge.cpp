@@ -22,7 +22,7 @@ bool run_device_pass(RibbitHandle *h, RibbitCall *d_calls, const int32_t *d_pend
     const size_t nr = cut_pos.size(), nP = lists.perfect.size(), nS = lists.subst.size(), n = kc.n;
     if (nr < 2 || first.size() != nr + 1 || start_cursor.size() != nr || first[nr] != n || order.size() != nr) return false;
     if (nP >= (1u << 30) || nS >= (1u << 30) || n + nr >= (1ull << 30) || nr >= (1u << 28)) return false;      // (the packing of candidates and log entries)
-    if (!h->xa_on_device || !h->d_xa.p) return false;
+    if (!h->rec.xa_on_device || !h->d_xa.p) return false;
     if (bind_device(h)) return false;
     const uint32_t head_cap = 1u << 16;
     const size_t log_cap = nP + nS + n / 4 + 65536;

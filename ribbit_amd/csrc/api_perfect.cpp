@@ -34,7 +34,7 @@ int collect_events(RibbitHandle *h, int which) {
         pp.motifs_per_block = h->debug_split[RIBBIT_SCAN_PERFECT];
         HIP_TRY(hipEventRecord(h->ev[2], h->stream));
         if (which != 0) return fail(RIBBIT_E_INTERNAL, "collect_events: the window stages' events stay on the device (window_stage.hip)");
-        h->last_split[RIBBIT_SCAN_PERFECT] = rb::launch_scan_perfect(pl, pp, h->d_events.p, h->d_counters.p, h->stream);
+        h->rec.last_split[RIBBIT_SCAN_PERFECT] = rb::launch_scan_perfect(pl, pp, h->d_events.p, h->d_counters.p, h->stream);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(h->ev[3], h->stream));
         rb::launch_compact_events(h->d_events.p, pp.ev_cap, h->d_counters.p, h->d_dense.p, h->stream);
@@ -133,7 +133,7 @@ int perfect_enqueue(RibbitHandle *h, size_t cap) {
     pp.motifs_per_block = h->debug_split[RIBBIT_SCAN_PERFECT];
     pr.region_cap = pp.ev_cap / (uint32_t)rb::EV_SHARDS;
     if (h->timing) HIP_TRY(hipEventRecord(h->ev[2], h->stream));
-    h->last_split[RIBBIT_SCAN_PERFECT] = rb::launch_scan_perfect(h->planes(), pp, h->d_events.p, h->d_counters.p, h->stream);
+    h->rec.last_split[RIBBIT_SCAN_PERFECT] = rb::launch_scan_perfect(h->planes(), pp, h->d_events.p, h->d_counters.p, h->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(h->ev[3], h->stream));
     // Everything after the scan (nine small, latency-bound launches, later the result copy) runs on the handle's
@@ -151,7 +151,7 @@ int perfect_enqueue(RibbitHandle *h, size_t cap) {
 int perfect_begin(RibbitHandle *h, int64_t own_lo, int64_t own_hi, int64_t pos_offset) {
     if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
     if (h->copy_pending) { int rcw = perfect_wait(h); if (rcw) return rcw; }
-    h->runs_valid = h->calls_valid = false;
+    h->rec.runs_valid = h->rec.calls_valid = false;
     h->pair_pending = false;
     int rc;
     if ((rc = h->d_counters.ensure(rb::EV_COUNTER_WORDS))) return rc;
@@ -243,7 +243,7 @@ int perfect_finish(RibbitHandle *h, RibbitRun *dst, size_t dst_cap, RibbitRun *h
     if (h->timing) HIP_TRY(hipEventRecord(h->ev[5], h->copy_stream));
     h->have_timing[1] = h->have_timing[2] = h->timing;
     h->host_ms = 0.0;
-    h->runs_valid = whole;
+    h->rec.runs_valid = whole;
     h->copy_pending = true;
     return wait ? perfect_wait(h) : RIBBIT_OK;
 }
@@ -252,7 +252,7 @@ int run_perfect_scan_range(RibbitHandle *h, int64_t own_lo, int64_t own_hi, int6
                            RibbitRun *half_dst, size_t half_dst_cap) {
     if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
     const bool whole = own_lo == 0 && own_hi == INT64_MAX && pos_offset == 0 && !dst;
-    if (whole && h->runs_valid) return RIBBIT_OK;
+    if (whole && h->rec.runs_valid) return RIBBIT_OK;
     int rc = perfect_begin(h, own_lo, own_hi, pos_offset);
     if (rc) return rc;
     return perfect_finish(h, dst, dst_cap, half_dst, half_dst_cap);
@@ -261,23 +261,23 @@ int run_perfect_scan_range(RibbitHandle *h, int64_t own_lo, int64_t own_hi, int6
 int run_perfect_scan(RibbitHandle *h) { return run_perfect_scan_range(h, 0, INT64_MAX, 0, nullptr, 0); }
 
 int build_perfect_calls(RibbitHandle *h) {
-    if (h->calls_valid) return RIBBIT_OK;
+    if (h->rec.calls_valid) return RIBBIT_OK;
     int rc = run_perfect_scan(h);
     if (rc) return rc;
     rb::perfect_calls_from_runs(h->h_runs.p, h->n_runs, h->length, h->min_shift, h->perfect_calls);
-    h->calls_valid = true;
+    h->rec.calls_valid = true;
     return RIBBIT_OK;
 }
 
 int advance_to_perfect(RibbitHandle *h) {
-    if (h->stage_done >= STAGE_PERFECT) return RIBBIT_OK;
+    if (h->rec.stage_done >= STAGE_PERFECT) return RIBBIT_OK;
     const double t0 = now_ms();
     int rc = build_perfect_calls(h);
     if (rc) return rc;
     const double t1 = now_ms();
     h->lists.perfect.clear();
     for (const RibbitCall &c : h->perfect_calls) rb::perfect_add(h->lists, c.start, c.end, c.mlen);
-    h->stage_done = STAGE_PERFECT;
+    h->rec.stage_done = STAGE_PERFECT;
     static const bool profile = std::getenv("RIBBIT_PROFILE") != nullptr;
     if (profile) std::fprintf(stderr, "[perfect stage] scan, pairing, runs and planes to the host, calls %.1f ms; merge of %zu calls into %zu seeds on one thread %.1f ms\n",
                               t1 - t0, h->perfect_calls.size(), h->lists.perfect.size(), now_ms() - t1);
@@ -288,18 +288,18 @@ int advance_to_perfect(RibbitHandle *h) {
 
 extern "C" {
 
-int ribbit_hip_scan_perfect_runs(RibbitHandle *h, const RibbitRun **out, size_t *n) {
+int ribbit_hip_scan_perfect_runs(RibbitHandle *h, const RibbitRun **out, size_t *n) { return guarded("the perfect stage", [&]() -> int {
     if (!h || !out || !n) return fail(RIBBIT_E_ARG, "null argument");
-    h->runs_valid = false;   // an explicit scan call always relaunches the kernel
-    h->calls_valid = false;
+    h->rec.runs_valid = false;   // an explicit scan call always relaunches the kernel
+    h->rec.calls_valid = false;
     int rc = run_perfect_scan(h);
     if (rc) return rc;
     *out = h->h_runs.p;
     *n = h->n_runs;
     return RIBBIT_OK;
-}
+}); }
 
-int ribbit_hip_perfect_calls(RibbitHandle *h, const RibbitCall **out, size_t *n) {
+int ribbit_hip_perfect_calls(RibbitHandle *h, const RibbitCall **out, size_t *n) { return guarded("the perfect stage", [&]() -> int {
     if (!h || !out || !n) return fail(RIBBIT_E_ARG, "null argument");
     if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
     int rc = build_perfect_calls(h);
@@ -307,26 +307,26 @@ int ribbit_hip_perfect_calls(RibbitHandle *h, const RibbitCall **out, size_t *n)
     *out = h->perfect_calls.data();
     *n = h->perfect_calls.size();
     return RIBBIT_OK;
-}
+}); }
 
-int ribbit_hip_seeds_perfect(RibbitHandle *h, const RibbitSeed **out, size_t *n) {
+int ribbit_hip_seeds_perfect(RibbitHandle *h, const RibbitSeed **out, size_t *n) { return guarded("the perfect stage", [&]() -> int {
     if (!h || !out || !n) return fail(RIBBIT_E_ARG, "null argument");
     if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
-    if (h->stage_done > STAGE_PERFECT) return fail(RIBBIT_E_STATE, "a later stage already re-typed the perfect list; reload the record");
+    if (h->rec.stage_done > STAGE_PERFECT) return fail(RIBBIT_E_STATE, "a later stage already re-typed the perfect list; reload the record");
     int rc = advance_to_perfect(h);
     if (rc) return rc;
     *out = h->lists.perfect.data();
     *n = h->lists.perfect.size();
     return RIBBIT_OK;
-}
+}); }
 
 int ribbit_hip_perfect_runs_partial(RibbitHandle *h, int64_t own_lo, int64_t own_hi, int64_t pos_offset,
-                                    const RibbitRun **runs, size_t *n_runs, const uint64_t **halves, size_t *n_halves) {
+                                    const RibbitRun **runs, size_t *n_runs, const uint64_t **halves, size_t *n_halves) { return guarded("the perfect stage", [&]() -> int {
     if (!h || !runs || !n_runs || !halves || !n_halves) return fail(RIBBIT_E_ARG, "null argument");
     if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
     int rc = collect_events(h, 0);
     if (rc) return rc;
-    h->runs_valid = h->calls_valid = false;
+    h->rec.runs_valid = h->rec.calls_valid = false;
     const double t0 = now_ms();
     std::string why;
     if (!rb::pair_perfect_runs_partial(event_source(h), own_lo, own_hi, pos_offset, h->runs, h->export_events, &why))
@@ -337,11 +337,11 @@ int ribbit_hip_perfect_runs_partial(RibbitHandle *h, int64_t own_lo, int64_t own
     *halves = h->export_events.data();
     *n_halves = h->export_events.size();
     return RIBBIT_OK;
-}
+}); }
 
 int ribbit_hip_scan_perfect_chunk(RibbitHandle *h, int64_t own_lo, int64_t own_hi, int64_t pos_offset, RibbitRun *dst, size_t dst_cap,
                                   RibbitRun *half_dst, size_t half_dst_cap, const RibbitRun **out, size_t *n,
-                                  const RibbitRun **halves, size_t *n_halves) {
+                                  const RibbitRun **halves, size_t *n_halves) { return guarded("the perfect stage", [&]() -> int {
     if (!h || !out || !n || !halves || !n_halves) return fail(RIBBIT_E_ARG, "null argument");
     if (own_lo < 0 || own_hi < own_lo) return fail(RIBBIT_E_ARG, "bad own range");
     int rc = run_perfect_scan_range(h, own_lo, own_hi, pos_offset, dst, dst_cap, half_dst, half_dst_cap);
@@ -351,19 +351,19 @@ int ribbit_hip_scan_perfect_chunk(RibbitHandle *h, int64_t own_lo, int64_t own_h
     *halves = half_dst ? half_dst : h->h_halves.p;
     *n_halves = h->n_halves;
     return RIBBIT_OK;
-}
+}); }
 
-int ribbit_hip_scan_perfect_begin(RibbitHandle *h, int64_t own_lo, int64_t own_hi, int64_t pos_offset) {
+int ribbit_hip_scan_perfect_begin(RibbitHandle *h, int64_t own_lo, int64_t own_hi, int64_t pos_offset) { return guarded("the perfect stage", [&]() -> int {
     if (!h) return fail(RIBBIT_E_ARG, "null argument");
     if (own_lo < 0 || own_hi < own_lo) return fail(RIBBIT_E_ARG, "bad own range");
     return perfect_begin(h, own_lo, own_hi, pos_offset);
-}
+}); }
 
-int ribbit_hip_scan_perfect_end_device(RibbitHandle *h, const void **dev_runs, size_t *n, const void **dev_halves, size_t *n_halves) {
+int ribbit_hip_scan_perfect_end_device(RibbitHandle *h, const void **dev_runs, size_t *n, const void **dev_halves, size_t *n_halves) { return guarded("the perfect stage", [&]() -> int {
     if (!h || !dev_runs || !n || !dev_halves || !n_halves) return fail(RIBBIT_E_ARG, "null argument");
     int rc = perfect_collect(h);
     if (rc) return rc;
-    h->runs_valid = false;
+    h->rec.runs_valid = false;
     h->have_timing[1] = h->timing;
     h->have_timing[2] = false;
     *dev_runs = h->d_dense.p;
@@ -371,15 +371,15 @@ int ribbit_hip_scan_perfect_end_device(RibbitHandle *h, const void **dev_runs, s
     *dev_halves = h->d_halves.p;
     *n_halves = h->n_halves;
     return RIBBIT_OK;
-}
+}); }
 
-int ribbit_hip_scan_perfect_wait(RibbitHandle *h) {
+int ribbit_hip_scan_perfect_wait(RibbitHandle *h) { return guarded("the perfect stage", [&]() -> int {
     if (!h) return fail(RIBBIT_E_ARG, "null argument");
     return perfect_wait(h);
-}
+}); }
 
 int ribbit_hip_scan_perfect_end(RibbitHandle *h, RibbitRun *dst, size_t dst_cap, RibbitRun *half_dst, size_t half_dst_cap,
-                                int wait, const RibbitRun **out, size_t *n, const RibbitRun **halves, size_t *n_halves) {
+                                int wait, const RibbitRun **out, size_t *n, const RibbitRun **halves, size_t *n_halves) { return guarded("the perfect stage", [&]() -> int {
     if (!h || !out || !n) return fail(RIBBIT_E_ARG, "null argument");
     int rc = perfect_finish(h, dst, dst_cap, half_dst, half_dst_cap, wait != 0);
     if (rc) return rc;
@@ -388,10 +388,10 @@ int ribbit_hip_scan_perfect_end(RibbitHandle *h, RibbitRun *dst, size_t dst_cap,
     if (halves) *halves = half_dst ? half_dst : h->h_halves.p;
     if (n_halves) *n_halves = h->n_halves;
     return RIBBIT_OK;
-}
+}); }
 
 int ribbit_hip_debug_pair_events(RibbitHandle *h, const uint64_t *events, size_t n, int64_t length, RibbitRun *runs, size_t runs_cap,
-                                 size_t *n_runs, uint32_t *flags) {
+                                 size_t *n_runs, uint32_t *flags) { return guarded("the pairing of the events", [&]() -> int {
     if (!h || (n && !events) || !n_runs || !flags || (runs_cap && !runs)) return fail(RIBBIT_E_ARG, "null argument");
     if (length < 0 || n > ((size_t)1 << 24)) return fail(RIBBIT_E_ARG, "bad size");
     int rc;
@@ -413,29 +413,20 @@ int ribbit_hip_debug_pair_events(RibbitHandle *h, const uint64_t *events, size_t
         return rc;
     std::vector<uint32_t> counters(rb::EV_COUNTER_WORDS, 0), status(rb::PAIR_STATUS_WORDS, 0);
     counters[0] = (uint32_t)n;
-    int ret = RIBBIT_OK;
-    do {
-        if (n && hipMemcpy(d_ev.p, events, n * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess) { ret = fail(RIBBIT_E_DEVICE, "copy failed"); break; }
-        if (hipMemcpy(d_cnt.p, counters.data(), counters.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) { ret = fail(RIBBIT_E_DEVICE, "copy failed"); break; }
-        if (rb::launch_pair_runs(d_ev.p, d_cnt.p, pr, d_table.p, d_base.p, d_part.p, d_runs.p, (uint32_t)(cap / 2), d_half.p, 2 * pr.nm, d_status.p, h->stream) != hipSuccess) {
-            ret = fail(RIBBIT_E_DEVICE, "pairing kernels could not be launched");
-            break;
-        }
-        if (hipStreamSynchronize(h->stream) != hipSuccess || hipMemcpy(status.data(), d_status.p, status.size() * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) {
-            ret = fail(RIBBIT_E_DEVICE, "pairing kernels failed");
-            break;
-        }
-        *flags = status[rb::PAIR_FLAGS];
-        *n_runs = status[rb::PAIR_TOTAL];
-        const size_t take = std::min(*n_runs, runs_cap);
-        if (take && hipMemcpy(runs, d_runs.p, take * sizeof(RibbitRun), hipMemcpyDeviceToHost) != hipSuccess) ret = fail(RIBBIT_E_DEVICE, "copy failed");
-    } while (false);
-    d_ev.release(); d_table.release(); d_runs.release(); d_cnt.release(); d_base.release(); d_part.release(); d_status.release(); d_half.release();
-    return ret;
-}
+    if (n) HIP_TRY(hipMemcpy(d_ev.p, events, n * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_cnt.p, counters.data(), counters.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(rb::launch_pair_runs(d_ev.p, d_cnt.p, pr, d_table.p, d_base.p, d_part.p, d_runs.p, (uint32_t)(cap / 2), d_half.p, 2 * pr.nm, d_status.p, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(status.data(), d_status.p, status.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    *flags = status[rb::PAIR_FLAGS];
+    *n_runs = status[rb::PAIR_TOTAL];
+    const size_t take = std::min(*n_runs, runs_cap);
+    if (take) HIP_TRY(hipMemcpy(runs, d_runs.p, take * sizeof(RibbitRun), hipMemcpyDeviceToHost));
+    return RIBBIT_OK;
+}); }
 
 int ribbit_host_perfect_runs_from_events(const RibbitScanParams *params, size_t nparts, const uint64_t *events,
-                                         const uint64_t *counts, RibbitRun **runs, size_t *n) {
+                                         const uint64_t *counts, RibbitRun **runs, size_t *n) { return guarded("the pairing of the events", [&]() -> int {
     if (!params || !counts || !runs || !n) return fail(RIBBIT_E_ARG, "null argument");
     const size_t nm = (size_t)(params->max_motif - params->min_motif + 1);
     std::vector<rb::Seg> segs(nm * nparts, rb::Seg{0, 0});
@@ -452,7 +443,7 @@ int ribbit_host_perfect_runs_from_events(const RibbitScanParams *params, size_t 
     if (!*runs) return fail(RIBBIT_E_NOMEM, "out of host memory");
     if (!out.empty()) std::memcpy(*runs, out.data(), out.size() * sizeof(RibbitRun));
     return RIBBIT_OK;
-}
+}); }
 
 void ribbit_runs_free(RibbitRun *runs) { std::free(runs); }
 

@@ -7,18 +7,14 @@ extern "C" {
 static int refine_bed_impl(RibbitHandle *h, const RibbitRefineParams *prm, const char *sequence_id, const char **text, size_t *len);
 
 int ribbit_hip_refine_bed(RibbitHandle *h, const RibbitRefineParams *prm, const char *sequence_id,
-                          const char **text, size_t *len) {
-    try {
-        // (the helper threads' calls report an empty query through their order_dependent flags, which end in a call on THIS thread)
-        rb::refine_met_empty_query(true);
-        const int rc = refine_bed_impl(h, prm, sequence_id, text, len);
-        device_free_pending();       // (buffers the alignment batches outgrew: released now that their streams are idle)
-        if (h) h->refine_met_empty_query = rb::refine_met_empty_query(true);
-        return rc;
-    } catch (const std::bad_alloc &) {           // nothing may unwind through the C boundary
-        return fail(RIBBIT_E_NOMEM, "out of host memory in refinement");
-    }
-}
+                          const char **text, size_t *len) { return guarded("refinement", [&]() -> int {
+    // (the helper threads' calls report an empty query through their order_dependent flags, which end in a call on THIS thread)
+    rb::refine_met_empty_query(true);
+    const int rc = refine_bed_impl(h, prm, sequence_id, text, len);
+    device_free_pending();       // (buffers the alignment batches outgrew: released now that their streams are idle)
+    if (h) h->refine_met_empty_query = rb::refine_met_empty_query(true);
+    return rc;
+}); }
 
 // Nodes of long-motif seeds' recursion trees that were put off for the GPU (refine.h: DeferredNode): their usable length from
 // this many bases on (RIBBIT_DEFER_MIN; 0 = nothing is put off, every node is done where it is met, as until round 4).
@@ -127,9 +123,8 @@ static void join_pieces(RibbitHandle *h, std::vector<rb::BedPiece> &pieces, unsi
     // handle's first record; here the threads that copy the pieces are also the first to touch the pages they copy into.
     const size_t total = at[pieces.size()];
     if (total + 1 > h->bed_raw_cap) {
-        std::free(h->bed_raw);
         h->bed_raw_cap = total + total / 8 + 1;
-        h->bed_raw = static_cast<char *>(std::malloc(h->bed_raw_cap));
+        h->bed_raw.reset(static_cast<char *>(std::malloc(h->bed_raw_cap)));
         if (!h->bed_raw) { h->bed_raw_cap = 0; throw std::bad_alloc(); }
     }
     h->bed_raw[total] = '\0';
@@ -141,7 +136,7 @@ static void join_pieces(RibbitHandle *h, std::vector<rb::BedPiece> &pieces, unsi
     auto place = [&]() {
         for (size_t k; (k = next_piece.fetch_add(64)) < pieces.size();)
             for (size_t q = k; q < std::min(pieces.size(), k + 64); ++q)
-                if (!pieces[q].text.empty()) std::memcpy(h->bed_raw + at[q], pieces[q].text.data(), pieces[q].text.size());
+                if (!pieces[q].text.empty()) std::memcpy(h->bed_raw.get() + at[q], pieces[q].text.data(), pieces[q].text.size());
     };
     std::vector<std::thread> pool;
     for (unsigned t = 1; t < nt; ++t) pool.emplace_back(place);
@@ -154,8 +149,8 @@ static std::atomic<int64_t> g_level_counts[3];      // levels run, nodes put off
 static int refine_bed_impl(RibbitHandle *h, const RibbitRefineParams *prm, const char *sequence_id, const char **text, size_t *len) {
     if (!h || !prm || !sequence_id || !text || !len) return fail(RIBBIT_E_ARG, "null argument");
     if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
-    h->best_rows_valid = false;
-    h->small_valid = false;
+    h->rec.best_rows_valid = false;
+    h->rec.small_valid = false;
     h->bed_in_raw = false;
     // cumulative over every handle of the process (ribbit-hip runs up to 64 workers through here at once): microseconds in atomics
     const double t_begin = now_ms();
@@ -628,7 +623,7 @@ static int refine_bed_impl(RibbitHandle *h, const RibbitRefineParams *prm, const
     if (profile) std::fprintf(stderr, "[refine_bed] cumulative: GPU scans of the seeds %.1f ms, alignment set-up + GPU striped passes %.1f ms, host refinement + BED %.1f ms; nodes put off for GPU batches: %lld in %lld levels (%lld alignments)\n",
                               t_rows_us.load() / 1000.0, t_jobs_us.load() / 1000.0, t_text_us.load() / 1000.0,
                               (long long)g_level_counts[1].load(), (long long)g_level_counts[0].load(), (long long)g_level_counts[2].load());
-    *text = h->bed_in_raw ? h->bed_raw : h->bed.c_str();
+    *text = h->bed_in_raw ? h->bed_raw.get() : h->bed.c_str();
     *len = h->bed_in_raw ? h->bed_raw_len : h->bed.size();
     return RIBBIT_OK;
 }
@@ -636,7 +631,7 @@ static int refine_bed_impl(RibbitHandle *h, const RibbitRefineParams *prm, const
 int ribbit_host_refine_bed(const RibbitScanParams *params, const RibbitRefineParams *prm, const char *sequence, int64_t length,
                            const uint32_t *hi, const uint32_t *lo, const uint32_t *brk, size_t nwords,
                            const uint32_t *xa, size_t xa_stride, const RibbitSeed *dispatch, size_t n_dispatch,
-                           const char *sequence_id, char **text, size_t *len) {
+                           const char *sequence_id, char **text, size_t *len) { return guarded("refinement", [&]() -> int {
     if (!params || !prm || !text || !len || !sequence_id || (n_dispatch && !dispatch)) return fail(RIBBIT_E_ARG, "null argument");
     if (length > 0 && (!sequence || !hi || !lo || !brk)) return fail(RIBBIT_E_ARG, "null plane");
     if (nwords < (size_t)(length / 32 + 1) || (xa && xa_stride < (size_t)(length / 32 + 1))) return fail(RIBBIT_E_ARG, "planes too short");
@@ -705,7 +700,7 @@ int ribbit_host_refine_bed(const RibbitScanParams *params, const RibbitRefinePar
     if (!*text) return fail(RIBBIT_E_NOMEM, "out of host memory");
     std::memcpy(*text, bed.c_str(), bed.size() + 1);
     return RIBBIT_OK;
-}
+}); }
 
 void ribbit_text_free(char *text) { std::free(text); }
 
@@ -713,7 +708,7 @@ void ribbit_debug_level_counters(int64_t out[3]) {
     for (int k = 0; k < 3; ++k) out[k] = g_level_counts[k].load();
 }
 
-int ribbit_hip_adopt_dispatch(RibbitHandle *h, const RibbitSeed *seeds, size_t n) {
+int ribbit_hip_adopt_dispatch(RibbitHandle *h, const RibbitSeed *seeds, size_t n) { return guarded("adopting the dispatch list", [&]() -> int {
     if (!h || (n && !seeds)) return fail(RIBBIT_E_ARG, "null argument");
     if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
     if (h->pair_pending || h->copy_pending) return fail(RIBBIT_E_STATE, "a perfect scan is in flight on this handle");
@@ -721,21 +716,21 @@ int ribbit_hip_adopt_dispatch(RibbitHandle *h, const RibbitSeed *seeds, size_t n
     if ((rc = bind_device(h))) return rc;
     if ((rc = ensure_host_planes(h))) return rc;
     // the composed planes on THIS device (the scans of the seeds read them there): the planes kernel alone, no window scan
-    if (!h->xa_on_device) {
+    if (!h->rec.xa_on_device) {
         if ((rc = prepare_anchored(h))) return rc;
         rb::PerfectLaunch pp;
         pp.m_lo = h->params.min_motif;
         pp.m_hi = h->params.max_motif;
         pp.ev_cap = 0;
         pp.motifs_per_block = h->debug_split[RIBBIT_SCAN_ANCHORED];
-        h->last_split[RIBBIT_SCAN_ANCHORED] = rb::launch_scan_anchored(h->planes(), pp, h->d_xa.p, h->xa_stride, h->stream);
+        h->rec.last_split[RIBBIT_SCAN_ANCHORED] = rb::launch_scan_anchored(h->planes(), pp, h->d_xa.p, h->xa_stride, h->stream);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(h->stream));
-        h->xa_on_device = true;
+        h->rec.xa_on_device = true;
     }
     // No host copy of the composed planes is made: refinement reads them on the host only for the flank nodes' longest runs, and
     // HostPlanes recomputes the slice a query covers from the packed planes when it has no copy (0.6 us a query).
-    if (h->stage_done < STAGE_ANCHORED) {
+    if (h->rec.stage_done < STAGE_ANCHORED) {
         if (h->xa_copy_pending) { HIP_TRY(hipEventSynchronize(h->ev_xa)); h->xa_copy_pending = false; }
         h->host.xa.clear(); h->host.xa_view = nullptr; h->host.xa_stride = 0;
         h->host.xa_m_lo = h->params.min_motif; h->host.xa_m_hi = h->params.max_motif;      // plane m IS the composed plane (fasta_utils.cpp:159), recomputed on request
@@ -743,10 +738,10 @@ int ribbit_hip_adopt_dispatch(RibbitHandle *h, const RibbitSeed *seeds, size_t n
     // `seeds` may point into this handle's own dispatch list (a slice of it)
     rb::SeedVec taken(seeds, seeds + n);
     h->dispatch.swap(taken);
-    h->longest_valid = false; h->best_rows_valid = false; h->small_valid = false;
-    h->stage_done = STAGE_ANCHORED;
+    h->rec.longest_valid = false; h->rec.best_rows_valid = false; h->rec.small_valid = false;
+    h->rec.stage_done = STAGE_ANCHORED;
     return RIBBIT_OK;
-}
+}); }
 
 int ribbit_hip_refine_met_empty_query(const RibbitHandle *h) { return h && h->refine_met_empty_query ? 1 : 0; }
 

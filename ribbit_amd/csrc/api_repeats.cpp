@@ -4,7 +4,6 @@
 #include "api_internal.h"
 
 #include <charconv>
-#include <exception>
 
 namespace {
 
@@ -114,24 +113,12 @@ extern "C" {
 
 int ribbit_hip_repeat_sequences(RibbitHandle *h, const char *name, const int32_t *intervals, size_t n, int32_t flank,
                                 const char **text, size_t *len, size_t *rows_done) {
-    try {
-        return repeat_sequences_impl(h, name, intervals, n, flank, text, len, rows_done);
-    } catch (const std::bad_alloc &) {          // nothing may unwind through the C boundary
-        return fail(RIBBIT_E_NOMEM, "out of host memory in the repeat sequences");
-    } catch (const std::exception &e) {
-        return fail(RIBBIT_E_INTERNAL, "repeat sequences: %s", e.what());
-    }
+    return guarded("the repeat sequences", [&]() -> int { return repeat_sequences_impl(h, name, intervals, n, flank, text, len, rows_done); });
 }
 
 int ribbit_host_repeat_sequences(const char *name, const char *sequence, int64_t length, const int32_t *intervals,
                                  size_t n, int32_t flank, char **text, size_t *len) {
-    try {
-        return host_repeat_sequences_impl(name, sequence, length, intervals, n, flank, text, len);
-    } catch (const std::bad_alloc &) {
-        return fail(RIBBIT_E_NOMEM, "out of host memory in the repeat sequences");
-    } catch (const std::exception &e) {
-        return fail(RIBBIT_E_INTERNAL, "repeat sequences: %s", e.what());
-    }
+    return guarded("the repeat sequences", [&]() -> int { return host_repeat_sequences_impl(name, sequence, length, intervals, n, flank, text, len); });
 }
 
 int ribbit_hip_debug_set_repeat_text_budget(RibbitHandle *h, size_t bytes) {

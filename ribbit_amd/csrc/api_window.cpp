@@ -81,16 +81,16 @@ int scan_and_pair_streaks(RibbitHandle *h, int which, uint32_t *n_streaks, int (
         if (attempt == 0 || which == 1) HIP_TRY(hipEventRecord(h->ev_stage[which - 1][0], h->stream));
         if (which == 1) {
             pp.motifs_per_block = h->debug_split[RIBBIT_SCAN_SUBST];
-            h->last_split[RIBBIT_SCAN_SUBST] = rb::launch_scan_window(pl, pp, 1, h->d_events.p, h->d_counters.p, h->stream);
+            h->rec.last_split[RIBBIT_SCAN_SUBST] = rb::launch_scan_window(pl, pp, 1, h->d_events.p, h->d_counters.p, h->stream);
         } else {
             if (attempt == 0) {          // the planes do not depend on the event capacity: once
                 pp.motifs_per_block = h->debug_split[RIBBIT_SCAN_ANCHORED];
-                h->last_split[RIBBIT_SCAN_ANCHORED] = rb::launch_scan_anchored(pl, pp, h->d_xa.p, h->xa_stride, h->stream);
+                h->rec.last_split[RIBBIT_SCAN_ANCHORED] = rb::launch_scan_anchored(pl, pp, h->d_xa.p, h->xa_stride, h->stream);
                 HIP_TRY(hipGetLastError());
                 HIP_TRY(hipEventRecord(h->ev_planes, h->stream));
             }
             pp.motifs_per_block = h->debug_split[RIBBIT_SCAN_XA_WINDOW];
-            h->last_split[RIBBIT_SCAN_XA_WINDOW] = rb::launch_scan_xa_window(pl, pp, h->d_xa.p, h->xa_stride, h->d_events.p, h->d_counters.p,
+            h->rec.last_split[RIBBIT_SCAN_XA_WINDOW] = rb::launch_scan_xa_window(pl, pp, h->d_xa.p, h->xa_stride, h->d_events.p, h->d_counters.p,
                                                                             filter ? h->d_tj.p : nullptr, filter ? h->d_dropmap.p : nullptr, h->stream);
         }
         HIP_TRY(hipGetLastError());
@@ -147,12 +147,12 @@ int window_stage_device(RibbitHandle *h, int which, bool full, int (*min_span)(i
     size_t scratch = rb::window_stage_scratch_bytes(n, n_words, n, std::max<size_t>(n / 16, (size_t)1 << 16), key_bits);
     if ((rc = h->d_scratch.ensure(scratch))) return rc;
     if ((rc = h->d_word_tmp.ensure(n_words + 1))) return rc;
-    if (!h->eval_valid) {
+    if (!h->rec.eval_valid) {
         if ((rc = h->d_eval.ensure(n_words + 1))) return rc;
         if ((rc = h->d_first_rev.ensure(n_words + 1))) return rc;
         HIP_TRY(rb::launch_eval_planes(h->d_brk.p + rb::LEAD_WORDS, n_words, h->d_eval.p, h->d_first_rev.p, h->d_word_tmp.p, h->d_scratch.p, h->d_scratch.cap, h->stream));
         HIP_TRY(hipGetLastError());
-        h->eval_valid = true;
+        h->rec.eval_valid = true;
     }
     if ((rc = h->d_group.ensure(std::max<size_t>(n, 1)))) return rc;
     const RibbitRun *runs = reinterpret_cast<const RibbitRun *>(h->d_dense.p);
@@ -275,13 +275,13 @@ void full_calls_from_device(const DeviceCalls &dc, rb::CallVec &calls) {
 // window scan (1 mismatch) + per-motif state machine, both on the device -> the addSeed call list of
 // processShiftXORswithSubstitutions (parse_substitute_shiftxor.cpp:430-574)
 int build_subst_calls(RibbitHandle *h) {
-    if (h->subst_calls_valid) return RIBBIT_OK;
+    if (h->rec.subst_calls_valid) return RIBBIT_OK;
     if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
     DeviceCalls dc;
     int rc = window_stage_device(h, 1, true, nullptr, &dc);
     if (rc) return rc;
     full_calls_from_device(dc, h->subst_calls);
-    h->subst_calls_valid = true;
+    h->rec.subst_calls_valid = true;
     return RIBBIT_OK;
 }
 
@@ -296,7 +296,7 @@ void subst_merge(RibbitHandle *h, const DeviceCalls *dc) {
     if (dc) rb::merge_subst_stage(h->lists, *dc, threads, &st);
     else rb::merge_subst_stage_full(h->lists, h->subst_calls.data(), h->subst_calls.size(), threads, &st);
     h->merge_ms = now_ms() - t0;
-    h->stage_done = STAGE_SUBST;
+    h->rec.stage_done = STAGE_SUBST;
     static const bool profile = std::getenv("RIBBIT_PROFILE") != nullptr;
     if (profile)
         std::fprintf(stderr, "[subst merge] %zu seeds: %u ranges on %u threads%s, preparation %.1f ms, merges %.1f ms\n", h->lists.subst.size(), st.ranges,
@@ -304,12 +304,12 @@ void subst_merge(RibbitHandle *h, const DeviceCalls *dc) {
 }
 
 int advance_to_subst(RibbitHandle *h) {
-    if (h->stage_done >= STAGE_SUBST) return RIBBIT_OK;
+    if (h->rec.stage_done >= STAGE_SUBST) return RIBBIT_OK;
     int rc = advance_to_perfect(h);
     if (rc) return rc;
     if ((rc = ensure_host_planes(h))) return rc;
     DeviceCalls dc;
-    const bool full = h->subst_calls_valid;      // the full call list has been asked for (ribbit_hip_subst_calls): replay that
+    const bool full = h->rec.subst_calls_valid;      // the full call list has been asked for (ribbit_hip_subst_calls): replay that
     if (!full && (rc = window_stage_device(h, 1, false, rb::subst_seedlen_cutoff, &dc))) return rc;
     subst_merge(h, full ? nullptr : &dc);
     return RIBBIT_OK;
@@ -361,14 +361,14 @@ int xa_wait_host(RibbitHandle *h) {
 // fused anchored kernel (anchor planes + composition + 6-of-8 window scan) + state machine, on the device ->
 // the addSeed call list of processShiftXORsAnchored (parse_anchored_shiftxor.cpp:580-723)
 int build_anchored_calls(RibbitHandle *h) {
-    if (h->anchored_calls_valid) return RIBBIT_OK;
+    if (h->rec.anchored_calls_valid) return RIBBIT_OK;
     int rc = prepare_anchored(h);
     if (rc) return rc;
     DeviceCalls dc;
     if ((rc = window_stage_device(h, 2, true, nullptr, &dc))) return rc;
     full_calls_from_device(dc, h->anchored_calls);
-    h->xa_on_device = true;
-    h->anchored_calls_valid = true;
+    h->rec.xa_on_device = true;
+    h->rec.anchored_calls_valid = true;
     return RIBBIT_OK;
 }
 
@@ -383,21 +383,21 @@ void print_anchored_merge_profile(size_t seeds, const rb::MergeStats &st, double
 }
 
 int advance_to_anchored(RibbitHandle *h) {
-    if (h->stage_done >= STAGE_ANCHORED) return RIBBIT_OK;
+    if (h->rec.stage_done >= STAGE_ANCHORED) return RIBBIT_OK;
     int rc = advance_to_perfect(h);
     if (rc) return rc;
     if ((rc = ensure_host_planes(h))) return rc;
     DeviceCalls dcs, dca;
-    const bool subst_todo = h->stage_done < STAGE_SUBST;
-    const bool subst_full = h->subst_calls_valid;
+    const bool subst_todo = h->rec.stage_done < STAGE_SUBST;
+    const bool subst_full = h->rec.subst_calls_valid;
     // the full call lists only when they have been asked for (ribbit_hip_*_calls); otherwise the compact form:
     // nine anchored calls in ten fail the length filter and never leave the device
     if (subst_todo && !subst_full && (rc = window_stage_device(h, 1, false, rb::subst_seedlen_cutoff, &dcs))) return rc;
-    const bool full = h->anchored_calls_valid;
+    const bool full = h->rec.anchored_calls_valid;
     if (!full) {
         if ((rc = prepare_anchored(h))) return rc;
         if ((rc = window_stage_device(h, 2, false, rb::anchored_seedlen_cutoff, &dca))) return rc;
-        h->xa_on_device = true;
+        h->rec.xa_on_device = true;
     }
     if ((rc = bind_device(h))) return rc;
     const double tx0 = now_ms();
@@ -434,7 +434,7 @@ int advance_to_anchored(RibbitHandle *h) {
     static const bool profile = std::getenv("RIBBIT_PROFILE") != nullptr;
     if (profile) print_anchored_merge_profile(h->lists.anchored.size(), st, now_ms() - t1, dispatch_ranges);
     h->subst_merge_ms = subst_todo ? merge_s : 0.0;
-    h->stage_done = STAGE_ANCHORED;
+    h->rec.stage_done = STAGE_ANCHORED;
     return RIBBIT_OK;
 }
 
@@ -442,20 +442,20 @@ int advance_to_anchored(RibbitHandle *h) {
 
 extern "C" {
 
-int ribbit_hip_subst_calls(RibbitHandle *h, const RibbitCall **out, size_t *n) {
+int ribbit_hip_subst_calls(RibbitHandle *h, const RibbitCall **out, size_t *n) { return guarded("the substitution stage", [&]() -> int {
     if (!h || !out || !n) return fail(RIBBIT_E_ARG, "null argument");
     int rc = build_subst_calls(h);
     if (rc) return rc;
     *out = h->subst_calls.data();
     *n = h->subst_calls.size();
     return RIBBIT_OK;
-}
+}); }
 
 int ribbit_hip_seeds_substitutions(RibbitHandle *h, const RibbitSeed **perfect, size_t *n_perfect,
-                                   const RibbitSeed **subst, size_t *n_subst) {
+                                   const RibbitSeed **subst, size_t *n_subst) { return guarded("the substitution stage", [&]() -> int {
     if (!h || !perfect || !n_perfect || !subst || !n_subst) return fail(RIBBIT_E_ARG, "null argument");
     if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
-    if (h->stage_done > STAGE_SUBST) return fail(RIBBIT_E_STATE, "a later stage already re-typed the lists; reload the record");
+    if (h->rec.stage_done > STAGE_SUBST) return fail(RIBBIT_E_STATE, "a later stage already re-typed the lists; reload the record");
     int rc = advance_to_subst(h);
     if (rc) return rc;
     *perfect = h->lists.perfect.data();
@@ -463,20 +463,20 @@ int ribbit_hip_seeds_substitutions(RibbitHandle *h, const RibbitSeed **perfect, 
     *subst = h->lists.subst.data();
     *n_subst = h->lists.subst.size();
     return RIBBIT_OK;
-}
+}); }
 
-int ribbit_hip_anchored_calls(RibbitHandle *h, const RibbitCall **out, size_t *n) {
+int ribbit_hip_anchored_calls(RibbitHandle *h, const RibbitCall **out, size_t *n) { return guarded("the anchored stage", [&]() -> int {
     if (!h || !out || !n) return fail(RIBBIT_E_ARG, "null argument");
     int rc = build_anchored_calls(h);
     if (rc) return rc;
     *out = h->anchored_calls.data();
     *n = h->anchored_calls.size();
     return RIBBIT_OK;
-}
+}); }
 
 int ribbit_hip_seeds_anchored(RibbitHandle *h, const RibbitSeed **perfect, size_t *n_perfect,
                               const RibbitSeed **subst, size_t *n_subst,
-                              const RibbitSeed **anchored, size_t *n_anchored) {
+                              const RibbitSeed **anchored, size_t *n_anchored) { return guarded("the anchored stage", [&]() -> int {
     if (!h || !perfect || !n_perfect || !subst || !n_subst || !anchored || !n_anchored) return fail(RIBBIT_E_ARG, "null argument");
     if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
     int rc = advance_to_anchored(h);
@@ -485,9 +485,9 @@ int ribbit_hip_seeds_anchored(RibbitHandle *h, const RibbitSeed **perfect, size_
     *subst = h->lists.subst.data();       *n_subst = h->lists.subst.size();
     *anchored = h->lists.anchored.data(); *n_anchored = h->lists.anchored.size();
     return RIBBIT_OK;
-}
+}); }
 
-int ribbit_hip_dispatch_seeds(RibbitHandle *h, const RibbitSeed **out, size_t *n) {
+int ribbit_hip_dispatch_seeds(RibbitHandle *h, const RibbitSeed **out, size_t *n) { return guarded("the anchored stage", [&]() -> int {
     if (!h || !out || !n) return fail(RIBBIT_E_ARG, "null argument");
     if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
     int rc = advance_to_anchored(h);
@@ -495,7 +495,7 @@ int ribbit_hip_dispatch_seeds(RibbitHandle *h, const RibbitSeed **out, size_t *n
     *out = h->dispatch.data();
     *n = h->dispatch.size();
     return RIBBIT_OK;
-}
+}); }
 
 void ribbit_debug_set_merge_min_range(size_t calls) { rb::set_merge_min_range(calls); }
 
@@ -518,7 +518,7 @@ int ribbit_host_replay_calls(const RibbitScanParams *params, int64_t length,
                              const RibbitCall *perfect_calls, size_t n_perfect_calls,
                              const RibbitCall *subst_calls, size_t n_subst_calls,
                              const RibbitCall *anchored_calls, size_t n_anchored_calls,
-                             RibbitSeedLists *out) {
+                             RibbitSeedLists *out) { return guarded("the replay of the calls", [&]() -> int {
     if (!params || !out || (length > 0 && (!hi || !lo || !brk))) return fail(RIBBIT_E_ARG, "null argument");
     if ((n_perfect_calls && !perfect_calls) || (n_subst_calls && !subst_calls) || (n_anchored_calls && !anchored_calls))
         return fail(RIBBIT_E_ARG, "null call list");
@@ -589,7 +589,7 @@ int ribbit_host_replay_calls(const RibbitScanParams *params, int64_t length,
     }
     out->guard_hits = sl.guard_hits;
     return RIBBIT_OK;
-}
+}); }
 
 void ribbit_seed_lists_free(RibbitSeedLists *lists) {
     if (!lists) return;
