@@ -350,6 +350,48 @@ int ribbit_host_repeat_sequences(const char *name, const char *sequence, int64_t
 int ribbit_hip_debug_set_repeat_text_budget(RibbitHandle *h, size_t bytes);
 
 /*
+ * ---- merged, sorted loci and a density track -----------------------------------------------------------------------
+ * The BED has one row per refined seed, in dispatch order: rows overlap and are not sorted.  With L the record's length,
+ * every row (s, e) is clipped as the mask clips it, s' = max(s, 0), e' = min(e, L); a row with s' >= e' is empty: it
+ * belongs to no locus and counts nowhere.  A position is covered when a non-empty row holds it; a run is a maximal
+ * stretch of covered positions (rows that overlap or abut form one run).
+ *   Loci:    consecutive runs are one locus while next.start - previous.end <= gap (gap 0: a locus is a run; this is
+ *            `bedtools merge -d gap` of the sorted rows).  Loci come by ascending start.  Every non-empty row lies in
+ *            exactly one locus.
+ *   Density: window k = [k W, min((k + 1) W, L)) for k = 0 .. ceil(L / W) - 1; its value is the number of covered
+ *            positions in it (a count of bases, not a fraction).  L = 0: no windows.
+ */
+typedef struct {
+    int32_t start, end;    /* half-open */
+    int32_t rows;          /* non-empty rows inside the locus */
+    int32_t covered;       /* covered positions inside it (end - start when gap is 0) */
+    int32_t best_row;      /* index into the rows given of the row with the largest e' - s'; among equals the lowest */
+} RibbitLocus;
+/* Loci of the loaded record under n rows (at most INT32_MAX), on the GPU.  *loci is handle-owned page-locked memory, valid
+ * until the handle's next loci call, load or close.  L = 0 or no non-empty row: *n_loci = 0. */
+int ribbit_hip_record_loci(RibbitHandle *h, const int32_t *intervals, size_t n, int32_t gap, const RibbitLocus **loci,
+                           size_t *n_loci);
+/* Covered bases per window of the loaded record, on the GPU; *covered is handle-owned page-locked memory, valid until the
+ * handle's next density call, load or close.  When one record gets its mask, loci and density from the same rows, the
+ * coverage bitmap behind all three is built once. */
+int ribbit_hip_record_density(RibbitHandle *h, const int32_t *intervals, size_t n, int32_t window, const int32_t **covered,
+                              size_t *n_windows);
+/* Host-only twins (no GPU) for a record of `length` bases (0 <= length < 2^31): *loci malloc'ed, release with
+ * ribbit_loci_free(); *covered malloc'ed, release with ribbit_intervals_free(). */
+int ribbit_host_record_loci(int64_t length, const int32_t *intervals, size_t n, int32_t gap, RibbitLocus **loci, size_t *n_loci);
+int ribbit_host_record_density(int64_t length, const int32_t *intervals, size_t n, int32_t window, int32_t **covered,
+                               size_t *n_windows);
+void ribbit_loci_free(RibbitLocus *loci);
+/* The loci of one record as text (host only), one line per locus, 15 tab-separated columns:
+ *   name, start, end, rows, covered, then the last ten columns of row best_row of bed_text, byte for byte (its start, end,
+ *   motif, `atomicity | m`, length, units, purity, strand, seed type, CIGAR).
+ * bed_text: the record's BED rows as ribbit_hip_refine_bed writes them, row i on line i (the rows the loci were made from);
+ * a row's columns are found from the right, so a name with a tab in it works.  A best_row that is no line of bed_text, or
+ * a line that is not a row: RIBBIT_E_ARG.  *text malloc'ed, release with ribbit_text_free(). */
+int ribbit_bed_loci_text(const char *name, const char *bed_text, size_t bed_len, const RibbitLocus *loci, size_t n_loci,
+                         char **text, size_t *len);
+
+/*
  * ---- streaming FASTA ingest ---------------------------------------------------------------------------------------
  * Replaces the reader loop of ribbit.cpp:269-280 (getline + `sequence += line` into one pageable std::string per
  * record).  The file is read in 16-MB blocks; line bodies are copied once, straight into a page-locked buffer

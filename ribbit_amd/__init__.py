@@ -16,7 +16,8 @@ import numpy as np
 __all__ = ["RibbitHipError", "ScanParams", "Scanner", "library_path", "load_library", "host_replay_calls", "pack_planes", "pack_bit_planes",
            "RUN_DT", "CALL_DT", "SEED_DT", "JOB_DT", "ENDS_DT", "RANK", "TERM", "RefineParams", "host_refine_jobs", "host_refine_bed", "host_merge_chunks", "host_perfect_runs_from_events", "pair_halves", "ssw_align", "ssw_align_periodic", "merge_chunk_runs", "join_run_halves",
            "RUN_NOT_OWNED", "RUN_HALF_START", "RUN_HALF_END",
-           "MASK_MODES", "host_mask_record", "bed_intervals", "host_repeat_sequences"]
+           "MASK_MODES", "host_mask_record", "bed_intervals", "host_repeat_sequences",
+           "LOCUS_DT", "host_record_loci", "host_record_density", "bed_loci_text"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -30,6 +31,7 @@ ENDS_DT = np.dtype([(n, "<i4") for n in ("score", "ref_end", "query_end", "score
 RUN_DT = np.dtype([("start", "<i4"), ("end", "<i4"), ("mlen", "<i4"), ("term", "<i4")])
 CALL_DT = np.dtype([("pos", "<i4"), ("mlen", "<i4"), ("start", "<i4"), ("end", "<i4")])
 SEED_DT = np.dtype([("start", "<i4"), ("end", "<i4"), ("mlen", "<i4"), ("type", "<i4")])
+LOCUS_DT = np.dtype([(n, "<i4") for n in ("start", "end", "rows", "covered", "best_row")])      # RibbitLocus
 
 # every symbol include/ribbit_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -56,6 +58,8 @@ ABI_SYMBOLS = [
     "ribbit_hip_stage_calls_chunk", "ribbit_hip_xa_words_strided", "ribbit_host_merge_chunks",
     "ribbit_hip_mask_record", "ribbit_host_mask_record", "ribbit_bed_intervals", "ribbit_intervals_free",
     "ribbit_hip_repeat_sequences", "ribbit_host_repeat_sequences", "ribbit_hip_debug_set_repeat_text_budget",
+    "ribbit_hip_record_loci", "ribbit_hip_record_density", "ribbit_host_record_loci", "ribbit_host_record_density", "ribbit_loci_free",
+    "ribbit_bed_loci_text",
 ]
 
 MASK_MODES = {"soft": 0, "hard": 1}     # RIBBIT_MASK_SOFT / RIBBIT_MASK_HARD
@@ -265,6 +269,13 @@ def load_library():
     L.ribbit_bed_intervals.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.ribbit_intervals_free.restype = None
     L.ribbit_intervals_free.argtypes = [vp]
+    L.ribbit_hip_record_loci.argtypes = [vp, vp, C.c_size_t, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_hip_record_density.argtypes = [vp, vp, C.c_size_t, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_host_record_loci.argtypes = [i64, vp, C.c_size_t, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_host_record_density.argtypes = [i64, vp, C.c_size_t, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_loci_free.restype = None
+    L.ribbit_loci_free.argtypes = [vp]
+    L.ribbit_bed_loci_text.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
     _lib = L
     return L
 
@@ -577,6 +588,61 @@ def bed_intervals(text) -> np.ndarray:
         return _copy(pairs.value, 2 * n.value, np.dtype("<i4")).reshape(-1, 2)
     finally:
         L.ribbit_intervals_free(pairs)
+
+
+def _rows_arg(intervals, value: int, what: str):
+    value = int(value)
+    if not -(1 << 31) <= value < (1 << 31):
+        raise ValueError(f"{what} {value} is not an int32")
+    return np.ascontiguousarray(np.asarray(intervals, dtype=np.int32).reshape(-1, 2)), value
+
+
+def host_record_loci(length: int, intervals, gap: int = 0) -> np.ndarray:
+    """ribbit_host_record_loci: the rows of a record of `length` bases merged into loci (runs of covered positions, joined
+    while they lie at most `gap` apart), by ascending start: a LOCUS_DT array (include/ribbit_hip.h).  No GPU needed."""
+    L = load_library()
+    iv, gap = _rows_arg(intervals, gap, "gap")
+    loci, n = C.c_void_p(), C.c_size_t()
+    rc = L.ribbit_host_record_loci(int(length), iv.ctypes.data if len(iv) else None, len(iv), gap, C.byref(loci), C.byref(n))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_host_record_loci error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return _copy(loci.value, n.value, LOCUS_DT)
+    finally:
+        L.ribbit_loci_free(loci)
+
+
+def host_record_density(length: int, intervals, window: int) -> np.ndarray:
+    """ribbit_host_record_density: covered bases per window of `window` bases (the last one may be short), int32.  No GPU needed."""
+    L = load_library()
+    iv, window = _rows_arg(intervals, window, "window")
+    cov, n = C.c_void_p(), C.c_size_t()
+    rc = L.ribbit_host_record_density(int(length), iv.ctypes.data if len(iv) else None, len(iv), window, C.byref(cov), C.byref(n))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_host_record_density error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return _copy(cov.value, n.value, np.dtype("<i4"))
+    finally:
+        L.ribbit_intervals_free(cov)
+
+
+def bed_loci_text(name, bed, loci) -> bytes:
+    """ribbit_bed_loci_text: one line per locus of one record: name, start, end, rows, covered and the last ten columns of the
+    locus's best row of `bed` (the record's BED text, row i on line i)."""
+    L = load_library()
+    raw = name.encode() if isinstance(name, str) else bytes(name)
+    if b"\0" in raw:
+        raise ValueError("a record name cannot hold a NUL byte")
+    text_in = bed.encode() if isinstance(bed, str) else bytes(bed)
+    lo = np.ascontiguousarray(np.asarray(loci, dtype=LOCUS_DT).reshape(-1))
+    text, n = C.c_void_p(), C.c_size_t()
+    rc = L.ribbit_bed_loci_text(raw, text_in, len(text_in), lo.ctypes.data if len(lo) else None, len(lo), C.byref(text), C.byref(n))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_bed_loci_text error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return C.string_at(text.value, n.value)
+    finally:
+        L.ribbit_text_free(text)
 
 
 def host_perfect_runs_from_events(min_motif: int, max_motif: int, event_parts, count_parts):
@@ -900,6 +966,20 @@ class Scanner:
                 done += k.value
             if done == len(iv):
                 return out
+
+    def record_loci(self, intervals, gap: int = 0) -> np.ndarray:
+        """The loaded record's rows merged into loci on the GPU (ribbit_hip_record_loci); see host_record_loci"""
+        iv, gap = _rows_arg(intervals, gap, "gap")
+        loci, n = C.c_void_p(), C.c_size_t()
+        self._check(self._L.ribbit_hip_record_loci(self._h, iv.ctypes.data if len(iv) else None, len(iv), gap, C.byref(loci), C.byref(n)))
+        return _copy(loci.value, n.value, LOCUS_DT)
+
+    def record_density(self, intervals, window: int) -> np.ndarray:
+        """The loaded record's covered bases per window on the GPU (ribbit_hip_record_density); see host_record_density"""
+        iv, window = _rows_arg(intervals, window, "window")
+        cov, n = C.c_void_p(), C.c_size_t()
+        self._check(self._L.ribbit_hip_record_density(self._h, iv.ctypes.data if len(iv) else None, len(iv), window, C.byref(cov), C.byref(n)))
+        return _copy(cov.value, n.value, np.dtype("<i4"))
 
     def debug_set_repeat_text_budget(self, nbytes: int) -> None:
         """the text budget of one ribbit_hip_repeat_sequences call in bytes (0: the default, 64 MiB)"""

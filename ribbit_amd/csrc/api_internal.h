@@ -10,6 +10,7 @@
 //   api_refine_bed.cpp  refinement to BED text: the GPU alignment pipeline, the recursion's levels, the host-only form
 //   api_mask.cpp        the repeat-masked FASTA body of a record (mask.hip), its host twin, BED rows back to intervals
 //   api_repeats.cpp     every row's bases with their flanks as FASTA entries (repeats.hip), in batches of a text budget; its host twin
+//   api_loci.cpp        merged, sorted loci and the per-window density of a record (loci.hip), their host twins, the loci as text
 // Not part of the ABI; nothing outside ribbit_amd/csrc includes it.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -201,6 +202,8 @@ struct RibbitHandle {
         bool eval_valid = false;              // d_eval / d_first_rev belong to the loaded record
         bool xa_on_device = false;            // the anchored kernel has written the composed planes of the loaded record
         int stage_done = STAGE_NONE;          // how far the seed lists have been advanced
+        bool coverage_valid = false;          // d_mask_bits is the coverage of the coverage_n rows in h_mask_iv / d_mask_iv (build_coverage)
+        size_t coverage_n = 0;
         rb::ScanSplit last_split[RIBBIT_SCAN_KERNELS];   // the split each scan kernel last ran with on the loaded record
     } rec;
     bool have_timing[3] = {false, false, false};
@@ -334,6 +337,17 @@ struct RibbitHandle {
     PinnedBuf<int64_t> h_rep_pick;
     PinnedBuf<char> h_rep_text;
     size_t rep_budget = 0;                // text budget of one batch in bytes (0: REPEAT_TEXT_BUDGET)
+    // the loci and the density track of the loaded record (api_loci.cpp), both from d_mask_bits: the lanes' run ranks, the runs
+    // (starts | ends) with the loci's starts and covered prefixes behind them, the join's prefixes with the rows' keys behind
+    // them, the loci and their number on the device and on their way up; the windows' counts
+    DevBuf<uint64_t> d_loci_off, d_loci_u64;
+    DevBuf<int32_t> d_loci_i32;
+    DevBuf<RibbitLocus> d_loci;
+    DevBuf<uint8_t> d_loci_scratch;
+    PinnedBuf<uint64_t> h_loci_count;
+    PinnedBuf<RibbitLocus> h_loci;
+    DevBuf<int32_t> d_density;
+    PinnedBuf<int32_t> h_density;
     RibbitHandle *aux = nullptr;          // helper handle of ribbit_hip_refine_bed: streams and buffers of the long alignment batch
     std::vector<RibbitHandle *> feed_aux; // ... and of its further feeders (each takes every n-th slice of the short alignments)
 
@@ -408,5 +422,8 @@ int ssw_class(const RibbitAlignJob &jb);
 int run_ssw_passes(RibbitHandle *h, const RibbitAlignJob *jobs, size_t n, const char *pool, size_t pool_len, int mask_len,
                           std::vector<rb::SswEnds> &ends, unsigned classes = 0x1fu, bool pool_resident = false);
 int run_ssw_paths(RibbitHandle *h, const RibbitAlignJob *jobs, size_t n, const std::vector<rb::SswEnds> &ends, std::vector<rb::SswPath> &paths);
+// api_mask.cpp: the coverage bitmap of the loaded record (length > 0) under n rows in d_mask_bits, rb::coverage_words(length) words,
+// and the rows in d_mask_iv, enqueued on the handle's stream; nothing is enqueued when the bitmap already is the one of these rows
+int build_coverage(RibbitHandle *h, const int32_t *intervals, size_t n);
 
 }  // namespace rbapi

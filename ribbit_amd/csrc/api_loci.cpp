@@ -1,0 +1,287 @@
+// api_loci.cpp -- merged, sorted loci and the per-window density of a record (loci.hip); see api_internal.h for the map of the
+// files behind include/ribbit_hip.h.  The GPU forms read the coverage bitmap the mask builds (build_coverage, api_mask.cpp) and run
+// on the handle's stream; the host twins sort the clipped rows and sweep them, without a per-base array, so that they state the
+// contract a second time instead of repeating the kernels; the loci's text needs no GPU either.
+#include "api_internal.h"
+
+#include <charconv>
+
+namespace {
+
+constexpr size_t MAX_ROWS = (size_t)INT32_MAX;      // (best_row is an int32)
+
+int check_rows(const int32_t *intervals, size_t n) {
+    if (!intervals && n > 0) return fail(RIBBIT_E_ARG, "null argument");
+    if (n > MAX_ROWS) return fail(RIBBIT_E_ARG, "%zu intervals", n);
+    return RIBBIT_OK;
+}
+
+int check_length(int64_t length) {
+    if (length < 0 || length > (int64_t)INT32_MAX) return fail(RIBBIT_E_ARG, "a record of %lld bases", (long long)length);
+    return RIBBIT_OK;
+}
+
+int64_t window_count(int64_t length, int64_t window) { return (length + window - 1) / window; }
+
+int record_loci_impl(RibbitHandle *h, const int32_t *intervals, size_t n, int32_t gap, const RibbitLocus **loci, size_t *n_loci) {
+    if (!h) return fail(RIBBIT_E_ARG, "null handle");
+    if (!loci || !n_loci) return fail(RIBBIT_E_ARG, "null argument");
+    if (gap < 0) return fail(RIBBIT_E_ARG, "gap %d is negative", (int)gap);
+    int rc;
+    if ((rc = check_rows(intervals, n))) return rc;
+    if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
+    static const RibbitLocus kNone{};
+    *loci = &kNone;
+    *n_loci = 0;
+    const int64_t length = h->length;
+    if (length == 0 || n == 0) return RIBBIT_OK;
+    if ((rc = bind_device(h))) return rc;
+    if ((rc = build_coverage(h, intervals, n))) return rc;
+    const int64_t lanes = rb::loci_lanes(length);
+    if ((rc = h->d_loci_off.ensure((size_t)lanes + 1))) return rc;
+    if ((rc = h->d_loci_scratch.ensure(rb::loci_scan_scratch_bytes(lanes), true))) return rc;
+    if ((rc = h->h_loci_count.ensure(2))) return rc;
+    HIP_TRY(rb::launch_run_ranks(h->d_mask_bits.p, length, h->d_loci_off.p, h->d_loci_scratch.p, h->d_loci_scratch.cap, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->h_loci_count.p, h->d_loci_off.p + lanes, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const uint64_t ranks = h->h_loci_count.p[0];
+    const size_t runs = (size_t)(ranks >> 32);
+    if (runs != (size_t)(uint32_t)ranks || runs > n) return fail(RIBBIT_E_INTERNAL, "%zu run starts, %zu run ends, %zu rows", runs, (size_t)(uint32_t)ranks, n);
+    if (runs == 0) return RIBBIT_OK;      // every row is empty
+    // d_loci_i32: run starts | run ends | locus starts | covered prefixes; d_loci_u64: the join's prefixes | the rows' keys | the count
+    if ((rc = h->d_loci_i32.ensure(4 * runs, true))) return rc;
+    if ((rc = h->d_loci_u64.ensure(2 * runs + 1, true))) return rc;
+    if ((rc = h->d_loci.ensure(runs, true))) return rc;
+    if ((rc = h->d_loci_scratch.ensure(rb::loci_scan_scratch_bytes((int64_t)runs), true))) return rc;
+    int32_t *run_start = h->d_loci_i32.p, *run_end = run_start + runs, *locus_start = run_end + runs, *post = locus_start + runs;
+    uint64_t *join = h->d_loci_u64.p, *key = join + runs, *count = key + runs;
+    rb::launch_run_bounds(h->d_mask_bits.p, length, h->d_loci_off.p, run_start, run_end, h->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(key, 0, (runs + 1) * sizeof(uint64_t), h->stream));
+    HIP_TRY(hipMemsetAsync(h->d_loci.p, 0, runs * sizeof(RibbitLocus), h->stream));
+    HIP_TRY(rb::launch_loci(run_start, run_end, (int64_t)runs, gap, h->d_mask_iv.p, (int64_t)n, length, join, locus_start, post,
+                            reinterpret_cast<unsigned long long *>(key), h->d_loci.p, reinterpret_cast<uint32_t *>(count), h->d_loci_scratch.p,
+                            h->d_loci_scratch.cap, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->h_loci_count.p + 1, count, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const size_t found = (size_t)(uint32_t)h->h_loci_count.p[1];
+    if (found < 1 || found > runs) return fail(RIBBIT_E_INTERNAL, "%zu loci of %zu runs", found, runs);
+    if ((rc = h->h_loci.ensure(found, true))) return rc;
+    HIP_TRY(hipMemcpyAsync(h->h_loci.p, h->d_loci.p, found * sizeof(RibbitLocus), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    *loci = h->h_loci.p;
+    *n_loci = found;
+    return RIBBIT_OK;
+}
+
+int record_density_impl(RibbitHandle *h, const int32_t *intervals, size_t n, int32_t window, const int32_t **covered, size_t *n_windows) {
+    if (!h) return fail(RIBBIT_E_ARG, "null handle");
+    if (!covered || !n_windows) return fail(RIBBIT_E_ARG, "null argument");
+    if (window < 1) return fail(RIBBIT_E_ARG, "window %d is below 1", (int)window);
+    int rc;
+    if ((rc = check_rows(intervals, n))) return rc;
+    if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
+    static const int32_t kNone[1] = {0};
+    *covered = kNone;
+    *n_windows = 0;
+    const int64_t length = h->length;
+    if (length == 0) return RIBBIT_OK;
+    if ((rc = bind_device(h))) return rc;
+    const size_t windows = (size_t)window_count(length, window);
+    if ((rc = h->d_density.ensure(windows, true))) return rc;
+    if ((rc = h->h_density.ensure(windows, true))) return rc;
+    if ((rc = build_coverage(h, intervals, n))) return rc;
+    rb::launch_density(h->d_mask_bits.p, length, window, (int64_t)windows, h->d_density.p, h->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h->h_density.p, h->d_density.p, windows * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    *covered = h->h_density.p;
+    *n_windows = windows;
+    return RIBBIT_OK;
+}
+
+// ---- host twins: the clipped, non-empty rows sorted by start, then one sweep
+struct Row { int64_t s, e; size_t index; };
+
+std::vector<Row> sorted_rows(int64_t length, const int32_t *intervals, size_t n) {
+    std::vector<Row> rows;
+    rows.reserve(n);
+    for (size_t i = 0; i < n; ++i) {
+        const int64_t s = std::max<int64_t>(intervals[2 * i], 0), e = std::min<int64_t>(intervals[2 * i + 1], length);
+        if (s < e) rows.push_back(Row{s, e, i});
+    }
+    std::sort(rows.begin(), rows.end(), [](const Row &a, const Row &b) { return a.s != b.s ? a.s < b.s : a.index < b.index; });
+    return rows;
+}
+
+int host_record_loci_impl(int64_t length, const int32_t *intervals, size_t n, int32_t gap, RibbitLocus **loci, size_t *n_loci) {
+    if (!loci || !n_loci) return fail(RIBBIT_E_ARG, "null argument");
+    if (gap < 0) return fail(RIBBIT_E_ARG, "gap %d is negative", (int)gap);
+    int rc;
+    if ((rc = check_rows(intervals, n)) || (rc = check_length(length))) return rc;
+    const std::vector<Row> rows = sorted_rows(length, intervals, n);
+    std::vector<RibbitLocus> out;
+    int64_t run_from = 0, run_to = -1, best = 0;      // the open run, and the length of the open locus's best row
+    for (const Row &r : rows) {
+        if (out.empty() || r.s > run_to) {            // a new run (a row that abuts the open run continues it)
+            if (!out.empty()) out.back().covered += (int32_t)(run_to - run_from);
+            if (out.empty() || r.s - run_to > gap) {
+                out.push_back(RibbitLocus{(int32_t)r.s, 0, 0, 0, 0});
+                best = 0;
+            }
+            run_from = r.s;
+            run_to = r.e;
+        } else {
+            run_to = std::max(run_to, r.e);
+        }
+        RibbitLocus &l = out.back();
+        l.end = (int32_t)run_to;
+        ++l.rows;
+        if (r.e - r.s > best || (r.e - r.s == best && (int64_t)r.index < l.best_row)) {
+            best = r.e - r.s;
+            l.best_row = (int32_t)r.index;
+        }
+    }
+    if (!out.empty()) out.back().covered += (int32_t)(run_to - run_from);
+    RibbitLocus *mem = static_cast<RibbitLocus *>(std::malloc(std::max<size_t>(out.size(), 1) * sizeof(RibbitLocus)));
+    if (!mem) return fail(RIBBIT_E_NOMEM, "out of host memory");
+    if (!out.empty()) std::memcpy(mem, out.data(), out.size() * sizeof(RibbitLocus));
+    *loci = mem;
+    *n_loci = out.size();
+    return RIBBIT_OK;
+}
+
+int host_record_density_impl(int64_t length, const int32_t *intervals, size_t n, int32_t window, int32_t **covered, size_t *n_windows) {
+    if (!covered || !n_windows) return fail(RIBBIT_E_ARG, "null argument");
+    if (window < 1) return fail(RIBBIT_E_ARG, "window %d is below 1", (int)window);
+    int rc;
+    if ((rc = check_rows(intervals, n)) || (rc = check_length(length))) return rc;
+    const std::vector<Row> rows = sorted_rows(length, intervals, n);
+    const int64_t windows = window_count(length, window);
+    int32_t *mem = static_cast<int32_t *>(std::calloc((size_t)std::max<int64_t>(windows, 1), sizeof(int32_t)));
+    if (!mem) return fail(RIBBIT_E_NOMEM, "out of host memory for %lld windows", (long long)windows);
+    // every stretch [from, to) that the sweep newly covers goes to the windows it meets
+    int64_t covered_to = 0;
+    for (const Row &r : rows) {
+        int64_t from = std::max(r.s, covered_to);
+        const int64_t to = r.e;
+        while (from < to) {
+            const int64_t k = from / window, stop = std::min(to, (k + 1) * (int64_t)window);
+            mem[k] += (int32_t)(stop - from);
+            from = stop;
+        }
+        covered_to = std::max(covered_to, to);
+    }
+    *covered = mem;
+    *n_windows = (size_t)windows;
+    return RIBBIT_OK;
+}
+
+// ---- the loci as text
+// fn(k) for k in [0, parts) on as many threads; a thread that cannot start leaves its part and the ones after it to the caller
+template <typename F>
+void in_parts(size_t parts, F &&fn) {
+    std::vector<std::thread> pool;
+    try {
+        for (size_t k = 1; k < parts; ++k) pool.emplace_back(fn, k);
+    } catch (...) {
+        for (size_t k = pool.size() + 1; k < parts; ++k) fn(k);
+    }
+    fn(0);
+    for (std::thread &t : pool) t.join();
+}
+
+int bed_loci_text_impl(const char *name, const char *bed, size_t bed_len, const RibbitLocus *loci, size_t n_loci, char **text, size_t *len) {
+    if (!name || !text || !len || (!bed && bed_len > 0) || (!loci && n_loci > 0)) return fail(RIBBIT_E_ARG, "null argument");
+    // a chromosome's BED is 150-200 MB of text: its line starts are found in pieces, one thread per piece of at least 4 MB, and
+    // the loci's lines are written in as many pieces
+    const unsigned hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+    const size_t parts = n_loci ? std::max<size_t>(1, std::min<size_t>(hw, bed_len >> 22)) : 1;
+    std::vector<std::vector<size_t>> starts(parts);      // per piece: the offsets just behind its newlines
+    std::vector<char> oom(parts, 0);
+    if (n_loci)
+        in_parts(parts, [&](size_t k) {
+            try {
+                const char *p = bed + bed_len * k / parts, *end = bed + bed_len * (k + 1) / parts;
+                while (p < end && (p = static_cast<const char *>(std::memchr(p, '\n', (size_t)(end - p)))) != nullptr) starts[k].push_back((size_t)(++p - bed));
+            } catch (const std::bad_alloc &) { oom[k] = 1; }
+        });
+    std::vector<size_t> line{0};       // line i is [line[i], line[i + 1]); a last line without its newline counts
+    for (size_t k = 0; k < parts; ++k) {
+        if (oom[k]) return fail(RIBBIT_E_NOMEM, "out of host memory reading BED rows");
+        line.insert(line.end(), starts[k].begin(), starts[k].end());
+    }
+    if (line.back() != bed_len) line.push_back(bed_len);
+    const size_t n_lines = line.size() - 1, name_len = std::strlen(name);
+    const size_t out_parts = std::max<size_t>(1, std::min<size_t>(parts, n_loci >> 12));
+    std::vector<std::string> piece(out_parts);
+    std::vector<size_t> bad(out_parts, (size_t)-1);
+    in_parts(out_parts, [&](size_t k) {
+        try {
+            char num[16];
+            std::string &out = piece[k];
+            for (size_t i = n_loci * k / out_parts; i < n_loci * (k + 1) / out_parts; ++i) {
+                const RibbitLocus &l = loci[i];
+                if (l.best_row < 0 || (size_t)l.best_row >= n_lines) { bad[k] = i; return; }
+                const char *p = bed + line[(size_t)l.best_row], *eol = bed + line[(size_t)l.best_row + 1];
+                if (eol > p && eol[-1] == '\n') --eol;
+                const char *from = eol;        // the tenth tab from the right: the row's last ten columns lie behind it
+                int tabs = 0;
+                while (from > p && tabs < 10) tabs += *--from == '\t';
+                if (tabs < 10) { bad[k] = i; return; }
+                out.append(name, name_len);
+                for (const int32_t v : {l.start, l.end, l.rows, l.covered}) {
+                    out += '\t';
+                    out.append(num, (size_t)(std::to_chars(num, num + sizeof num, v).ptr - num));
+                }
+                out.append(from, (size_t)(eol - from));
+                out += '\n';
+            }
+        } catch (const std::bad_alloc &) { bad[k] = (size_t)-2; }
+    });
+    size_t total = 0;
+    for (size_t k = 0; k < out_parts; ++k) {
+        if (bad[k] == (size_t)-2) return fail(RIBBIT_E_NOMEM, "out of host memory writing loci");
+        if (bad[k] != (size_t)-1) return fail(RIBBIT_E_ARG, "locus %zu: its best row %d is not a row of 11 tab-separated columns of the BED text (%zu lines)", bad[k], (int)loci[bad[k]].best_row, n_lines);
+        total += piece[k].size();
+    }
+    char *mem = static_cast<char *>(std::malloc(total + 1));
+    if (!mem) return fail(RIBBIT_E_NOMEM, "out of host memory");
+    size_t at = 0;
+    for (const std::string &s : piece) {
+        std::memcpy(mem + at, s.data(), s.size());
+        at += s.size();
+    }
+    mem[total] = 0;
+    *text = mem;
+    *len = total;
+    return RIBBIT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ribbit_hip_record_loci(RibbitHandle *h, const int32_t *intervals, size_t n, int32_t gap, const RibbitLocus **loci, size_t *n_loci) {
+    return guarded("the loci", [&]() -> int { return record_loci_impl(h, intervals, n, gap, loci, n_loci); });
+}
+
+int ribbit_hip_record_density(RibbitHandle *h, const int32_t *intervals, size_t n, int32_t window, const int32_t **covered, size_t *n_windows) {
+    return guarded("the density", [&]() -> int { return record_density_impl(h, intervals, n, window, covered, n_windows); });
+}
+
+int ribbit_host_record_loci(int64_t length, const int32_t *intervals, size_t n, int32_t gap, RibbitLocus **loci, size_t *n_loci) {
+    return guarded("the loci", [&]() -> int { return host_record_loci_impl(length, intervals, n, gap, loci, n_loci); });
+}
+
+int ribbit_host_record_density(int64_t length, const int32_t *intervals, size_t n, int32_t window, int32_t **covered, size_t *n_windows) {
+    return guarded("the density", [&]() -> int { return host_record_density_impl(length, intervals, n, window, covered, n_windows); });
+}
+
+int ribbit_bed_loci_text(const char *name, const char *bed_text, size_t bed_len, const RibbitLocus *loci, size_t n_loci, char **text, size_t *len) {
+    return guarded("the loci's text", [&]() -> int { return bed_loci_text_impl(name, bed_text, bed_len, loci, n_loci, text, len); });
+}
+
+void ribbit_loci_free(RibbitLocus *loci) { std::free(loci); }
+
+}  // extern "C"

@@ -51,19 +51,9 @@ int mask_record_impl(RibbitHandle *h, const int32_t *intervals, size_t n, int32_
     const int64_t width = effective_width(length, line_width);
     const int64_t out_len = body_length(length, width);
     const int64_t nwords = length / 32 + 1;
-    if ((rc = h->d_mask_bits.ensure((size_t)nwords))) return rc;
     if ((rc = h->d_mask_text.ensure((size_t)((out_len + 15) & ~(int64_t)15), true))) return rc;
     if ((rc = h->h_mask_text.ensure((size_t)out_len, true))) return rc;
-    HIP_TRY(hipMemsetAsync(h->d_mask_bits.p, 0, (size_t)nwords * sizeof(uint32_t), h->stream));
-    if (n) {
-        if ((rc = h->h_mask_iv.ensure(2 * n, true))) return rc;
-        if ((rc = h->d_mask_iv.ensure(2 * n, true))) return rc;
-        // (the staging buffer may still be the source of the last call's copy: that call ended in a synchronise)
-        std::memcpy(h->h_mask_iv.p, intervals, 2 * n * sizeof(int32_t));
-        HIP_TRY(hipMemcpyAsync(h->d_mask_iv.p, h->h_mask_iv.p, 2 * n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-        rb::launch_mask_coverage(h->d_mask_iv.p, (int64_t)n, length, h->d_mask_bits.p, h->stream);
-        HIP_TRY(hipGetLastError());
-    }
+    if ((rc = build_coverage(h, intervals, n))) return rc;
     rb::launch_mask_format(h->dev_ascii_src, length, h->d_mask_bits.p, nwords, mode == RIBBIT_MASK_HARD, width, out_len, h->d_mask_text.p, h->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(h->h_mask_text.p, h->d_mask_text.p, (size_t)out_len, hipMemcpyDeviceToHost, h->stream));
@@ -72,6 +62,34 @@ int mask_record_impl(RibbitHandle *h, const int32_t *intervals, size_t n, int32_
     *len = (size_t)out_len;
     return RIBBIT_OK;
 }
+
+}  // namespace
+
+// The staged copy of the last rows stays in h_mask_iv: a call with the same rows (the command-line tool hands one record's rows to
+// the mask, the loci and the density) finds the bitmap as it needs it, at the price of one comparison.
+int rbapi::build_coverage(RibbitHandle *h, const int32_t *intervals, size_t n) {
+    if (h->rec.coverage_valid && h->rec.coverage_n == n && (n == 0 || std::memcmp(h->h_mask_iv.p, intervals, 2 * n * sizeof(int32_t)) == 0))
+        return RIBBIT_OK;
+    h->rec.coverage_valid = false;
+    int rc;
+    const size_t words = (size_t)rb::coverage_words(h->length);
+    if ((rc = h->d_mask_bits.ensure(words))) return rc;
+    HIP_TRY(hipMemsetAsync(h->d_mask_bits.p, 0, words * sizeof(uint32_t), h->stream));
+    if (n) {
+        if ((rc = h->h_mask_iv.ensure(2 * n, true))) return rc;
+        if ((rc = h->d_mask_iv.ensure(2 * n, true))) return rc;
+        // (the staging buffer may still be the source of the last call's copy: that call ended in a synchronise)
+        std::memcpy(h->h_mask_iv.p, intervals, 2 * n * sizeof(int32_t));
+        HIP_TRY(hipMemcpyAsync(h->d_mask_iv.p, h->h_mask_iv.p, 2 * n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+        rb::launch_mask_coverage(h->d_mask_iv.p, (int64_t)n, h->length, h->d_mask_bits.p, h->stream);
+        HIP_TRY(hipGetLastError());
+    }
+    h->rec.coverage_valid = true;
+    h->rec.coverage_n = n;
+    return RIBBIT_OK;
+}
+
+namespace {
 
 int host_mask_record_impl(const char *sequence, int64_t length, const int32_t *intervals, size_t n, int32_t mode, int32_t line_width,
                           char **text, size_t *len) {

@@ -268,6 +268,27 @@ hipError_t launch_repeat_offsets(const int32_t *iv, int64_t m, int64_t length, i
 void launch_repeat_format(const uint8_t *ascii, int64_t length, const int32_t *iv, const int64_t *off, int64_t k, int64_t total,
                           int32_t flank, const char *name, int32_t name_len, int32_t *span_row, uint8_t *out, hipStream_t stream);
 
+// loci.hip: merged loci and the density track of the loaded record from the mask's coverage bitmap (api_loci.cpp).
+// bits: coverage_words(length) words, zeroed and then filled by launch_mask_coverage: padded so that a lane of the run
+// kernels reads its LOCI_LANE_WORDS words and the word behind them without a bound check (the padding stays zero).
+constexpr int64_t LOCI_LANE_WORDS = 8;
+inline int64_t coverage_words(int64_t length) { return ((length / 32 + 1) + LOCI_LANE_WORDS - 1) / LOCI_LANE_WORDS * LOCI_LANE_WORDS + LOCI_LANE_WORDS; }
+inline int64_t loci_lanes(int64_t length) { return ((length / 32 + 1) + LOCI_LANE_WORDS - 1) / LOCI_LANE_WORDS; }
+size_t loci_scan_scratch_bytes(int64_t items);
+// off: loci_lanes(length) + 1 packed ranks, off[t] = (run starts before lane t's words) << 32 | (run ends before them);
+// off[lanes] holds the number of runs in both halves
+hipError_t launch_run_ranks(const uint32_t *bits, int64_t length, uint64_t *off, void *scratch, size_t scratch_bytes, hipStream_t stream);
+// run_start / run_end: the n_runs runs in ascending order, half-open
+void launch_run_bounds(const uint32_t *bits, int64_t length, const uint64_t *off, int32_t *run_start, int32_t *run_end, hipStream_t stream);
+// The gap join and the rows of every locus.  join: n_runs packed prefixes (locus id + 1) << 32 | covered positions so far;
+// locus_start / post: n_runs ints (the loci's starts for the rows' search; covered positions up to each locus's end);
+// key: n_runs zeroed words, loci: n_runs zeroed records; count[0] = number of loci.  intervals: the n rows on the device.
+hipError_t launch_loci(const int32_t *run_start, const int32_t *run_end, int64_t n_runs, int32_t gap, const int32_t *intervals, int64_t n,
+                       int64_t length, uint64_t *join, int32_t *locus_start, int32_t *post, unsigned long long *key, RibbitLocus *loci,
+                       uint32_t *count, void *scratch, size_t scratch_bytes, hipStream_t stream);
+// covered[k] = covered positions of [k window, min((k + 1) window, length)), k < n_windows = ceil(length / window)
+void launch_density(const uint32_t *bits, int64_t length, int64_t window, int64_t n_windows, int32_t *covered, hipStream_t stream);
+
 // profiling aid: reads nwords dwords of src with one coalesced dword per lane (known byte count)
 void launch_calib_stream_read(const uint32_t *src, int64_t nwords, uint32_t *sink, hipStream_t stream);
 

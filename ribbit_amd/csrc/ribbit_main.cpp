@@ -4,7 +4,7 @@
 //
 //   ribbit-hip -i in.fa [-o out.bed] [-m 2] [-M 100] [-p 0.85] [-l N|file] [--min-units N|file] [--perfect-units N|file]
 //              [--devices 0,1,...] [--jobs N] [--masked-fasta FILE [--mask soft|hard] [--mask-width N]]
-//              [--repeat-fasta FILE [--flank N]]
+//              [--repeat-fasta FILE [--flank N]] [--loci-bed FILE [--loci-gap D]] [--density-bedgraph FILE [--density-window W]]
 //
 // Records are independent (ribbit.cpp:269-280 handles them one after the other); here up to --jobs of them are in
 // flight at once PER GPU, each on its own handle / HIP streams, so that the upload and GPU scans of one record overlap
@@ -15,13 +15,16 @@
 //
 // --masked-fasta writes every record again with its BED rows masked (soft: lowercase, hard: N), on the GPU that refined it
 // (ribbit_hip_mask_record), in input order beside the BED.  --repeat-fasta writes every BED row's bases with N flanking bases on
-// either side (ribbit_hip_repeat_sequences), the same way.  Both read the BED rows back once.
+// either side (ribbit_hip_repeat_sequences), the same way.  --loci-bed writes the rows of every record merged into sorted loci
+// (ribbit_hip_record_loci, ribbit_bed_loci_text) and --density-bedgraph the covered bases per window (ribbit_hip_record_density),
+// the same way again.  The BED rows are read back once per record, however many of the four are asked for.
 //
 // Reproduced quirks: -p is accepted and ignored (Q1); without -o the BED rows go to
 // stderr (Q2); --help exits with status 1 (Q3); the record name ends at the first space and the last
 // record is processed even when the file is empty (Q4).
 #include <algorithm>
 #include <cctype>
+#include <charconv>
 #include <chrono>
 #include <condition_variable>
 #include <deque>
@@ -60,6 +63,12 @@ struct Options {
     std::string repeat_fasta;                     // --repeat-fasta FILE: every BED row's bases with their flanks (empty: off)
     int flank = 100;                              // --flank N: bases on either side of a row
     bool has_flank = false;
+    std::string loci_bed;                         // --loci-bed FILE: the rows merged into sorted loci (empty: off)
+    int loci_gap = 0;                             // --loci-gap D: runs at most D bases apart are one locus
+    bool has_loci_gap = false;
+    std::string density_bedgraph;                 // --density-bedgraph FILE: covered bases per window (empty: off)
+    int density_window = 10000;                   // --density-window W
+    bool has_density_window = false;
 };
 
 const char *kHelp =
@@ -92,7 +101,16 @@ const char *kHelp =
     "                                entry per row in BED order, headed '>name:start-end flank=left,right' (start and end\n"
     "                                clipped to the record; left, right: the flank bases taken on either side)\n"
     "  --flank arg                   (ribbit-hip) bases of the record taken on either side of a row for --repeat-fasta.\n"
-    "                                Default: 100\n";
+    "                                Default: 100\n"
+    "  --loci-bed arg                (ribbit-hip) also write the BED rows of every record merged into loci to this file, sorted\n"
+    "                                by start: rows that overlap or abut are one locus. 15 columns: name, start, end, rows\n"
+    "                                merged, bases covered, then the last ten columns of the locus's longest row\n"
+    "  --loci-gap arg                (ribbit-hip) for --loci-bed: stretches of rows at most this many bases apart are one\n"
+    "                                locus, as bedtools merge -d. Default: 0\n"
+    "  --density-bedgraph arg        (ribbit-hip) also write a bedGraph to this file: one line per window of every record,\n"
+    "                                empty windows too: name, start, end, and the NUMBER OF BASES of the window that BED\n"
+    "                                rows cover (an exact integer count, not a fraction: divide by end - start for one)\n"
+    "  --density-window arg          (ribbit-hip) bases per window of --density-bedgraph, 1 or more. Default: 10000\n";
 
 [[noreturn]] void die(const std::string &msg) {        // argument errors: main thread, before any worker exists
     std::cerr << "ribbit-hip: " << msg << "\n";
@@ -123,7 +141,8 @@ int parse_arguments(int argc, char **argv, Options &o) {
     static const std::map<std::string, std::string> longs = {
         {"help", "h"}, {"input-file", "i"}, {"output-file", "o"}, {"min-motif-length", "m"}, {"max-motif-length", "M"},
         {"purity", "p"}, {"min-length", "l"}, {"min-units", "U"}, {"perfect-units", "P"}, {"device", "D"}, {"jobs", "J"}, {"devices", "G"}, {"timing", "T"},
-        {"masked-fasta", "X"}, {"mask", "K"}, {"mask-width", "W"}, {"repeat-fasta", "Y"}, {"flank", "F"}};
+        {"masked-fasta", "X"}, {"mask", "K"}, {"mask-width", "W"}, {"repeat-fasta", "Y"}, {"flank", "F"},
+        {"loci-bed", "LB"}, {"loci-gap", "LG"}, {"density-bedgraph", "DB"}, {"density-window", "DW"}};
     bool help = false;
     for (int a = 1; a < argc; ++a) {
         std::string arg = argv[a], key, value;
@@ -182,12 +201,34 @@ int parse_arguments(int argc, char **argv, Options &o) {
             o.flank = std::atoi(value.c_str());
             o.has_flank = true;
         }
+        else if (key == "LB") {
+            if (value.empty()) die("--loci-bed wants a file name");
+            o.loci_bed = value;
+        }
+        else if (key == "LG") {
+            if (!is_number(value) || value.size() > 10 || std::atoll(value.c_str()) > 2147483647LL)
+                die("--loci-gap wants a whole number of bases (0 .. 2147483647), got '" + value + "'");
+            o.loci_gap = (int)std::atoll(value.c_str());
+            o.has_loci_gap = true;
+        }
+        else if (key == "DB") {
+            if (value.empty()) die("--density-bedgraph wants a file name");
+            o.density_bedgraph = value;
+        }
+        else if (key == "DW") {
+            if (!is_number(value) || value.size() > 10 || std::atoll(value.c_str()) < 1 || std::atoll(value.c_str()) > 2147483647LL)
+                die("--density-window wants a whole number of bases (1 .. 2147483647), got '" + value + "'");
+            o.density_window = (int)std::atoll(value.c_str());
+            o.has_density_window = true;
+        }
         else if (key == "G") { if (!parse_device_list(value, o.devices)) die("--devices wants a comma separated list of GPU ordinals, got '" + value + "'"); }
     }
     if (help) { std::cerr << kHelp << "\n"; return 0; }                       // ribbit.cpp:114-117
     if (o.masked_fasta.empty() && (o.has_mask_mode || o.has_mask_width))
         die(std::string(o.has_mask_mode ? "--mask" : "--mask-width") + " needs --masked-fasta");
     if (o.repeat_fasta.empty() && o.has_flank) die("--flank needs --repeat-fasta");
+    if (o.loci_bed.empty() && o.has_loci_gap) die("--loci-gap needs --loci-bed");
+    if (o.density_bedgraph.empty() && o.has_density_window) die("--density-window needs --density-bedgraph");
     if (o.fasta.empty()) { std::cerr << "ERROR: Please specify an input fasta file!\n"; return 0; }   // :122-126
     return 1;
 }
@@ -244,7 +285,7 @@ size_t count_failed(const RibbitSeed *s, size_t n) {
 }
 
 // RIBBIT_PROFILE=1: wall time per stage, summed over the records, printed at exit
-double g_stage_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // load, perfect, substitutions, anchored, dispatch, refine+BED, mask, repeats
+double g_stage_ms[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};     // load, perfect, substitutions, anchored, dispatch, refine+BED, mask, repeats, loci, density
 std::mutex g_stage_mu;
 struct StageClock {
     int slot;
@@ -269,6 +310,28 @@ struct RepeatJob {
     std::function<void(const char *, size_t)> write;
 };
 
+// --loci-bed: the gap, and where the record's lines go (null: off for this record)
+struct LociJob {
+    int gap;
+    std::function<void(const char *, size_t)> write;
+};
+
+// --density-bedgraph: the window, and where the record's lines go (null: off for this record)
+struct DensityJob {
+    int window;
+    std::function<void(const char *, size_t)> write;
+};
+
+// what a record's rows are wanted for; the stage clock that pays for reading them back is the first one's
+struct RowJobs {
+    const MaskJob *mask = nullptr;
+    const RepeatJob *repeats = nullptr;
+    const LociJob *loci = nullptr;
+    const DensityJob *density = nullptr;
+    bool any() const { return mask || repeats || loci || density; }
+    int first_slot() const { return mask ? 6 : repeats ? 7 : loci ? 8 : 9; }
+};
+
 // the (start, end) pairs of a BED text, appended to iv
 void append_intervals(const char *text, size_t len, std::vector<int32_t> &iv) {
     int32_t *pairs = nullptr;
@@ -285,7 +348,8 @@ void append_intervals(const char *text, size_t len, std::vector<int32_t> &iv) {
 // previous seed's CIGAR, which may be another slice's) makes the record be refined again in one piece, on `h`.
 struct Helper { RibbitHandle *h; int host_threads; };
 bool refine_over_devices(RibbitHandle *h, const std::vector<Helper> &helpers, const RibbitRefineParams &prm, const std::string &name, const char *bases,
-                         int64_t length, const RibbitSeed *d, size_t nd, std::ostream &out, std::ostream &log, std::vector<int32_t> *mask_iv) {
+                         int64_t length, const RibbitSeed *d, size_t nd, std::ostream &out, std::ostream &log, std::vector<int32_t> *mask_iv,
+                         std::string *bed_copy) {
     const size_t parts = helpers.size() + 1;
     const std::vector<RibbitSeed> all(d, d + nd);          // (`d` is `h`'s own list, which adopting a slice replaces)
     std::vector<std::string> text(parts), error(parts);
@@ -323,20 +387,25 @@ bool refine_over_devices(RibbitHandle *h, const std::vector<Helper> &helpers, co
         check(ribbit_hip_refine_bed(h, &prm, name.c_str(), &t, &len));
         out.write(t, (std::streamsize)len);
         if (mask_iv) append_intervals(t, len, *mask_iv);
+        if (bed_copy) bed_copy->assign(t, len);
         log << "[devices] an alignment with an empty query at the head of a slice: the record was refined again in one piece\n";
         return false;
     }
     for (size_t k = 0; k < parts; ++k) out.write(text[k].data(), (std::streamsize)text[k].size());
     if (mask_iv)      // (the rows of all slices: the mask of a record is the union of all of its rows)
         for (size_t k = 0; k < parts; ++k) append_intervals(text[k].data(), text[k].size(), *mask_iv);
+    if (bed_copy)     // (the loci's lines quote the rows: the slices' texts as one, row i on line i)
+        for (size_t k = 0; k < parts; ++k) bed_copy->append(text[k]);
     return true;
 }
 
 // processSequence (fasta_utils.cpp:59-250) through the C ABI, with the reference's progress lines; then, with --masked-fasta,
-// the record masked by its rows, and with --repeat-fasta the rows' entries, both on `h`, the handle that loaded it
+// the record masked by its rows, with --repeat-fasta the rows' entries, with --loci-bed the rows merged into loci and with
+// --density-bedgraph the covered bases per window, all on `h`, the handle that loaded it
 void process_sequence(RibbitHandle *h, const RibbitRefineParams &prm, const std::string &name, const char *bases, int64_t length,
-                      std::ostream &out, std::ostream &log, const MaskJob *mask, const RepeatJob *repeats,
-                      const std::vector<Helper> *helpers = nullptr) {
+                      std::ostream &out, std::ostream &log, const RowJobs &jobs, const std::vector<Helper> *helpers = nullptr) {
+    const MaskJob *mask = jobs.mask;
+    const RepeatJob *repeats = jobs.repeats;
     const time_t t0 = time(0);
     auto secs = [&]() { return difftime(time(0), t0); };
     { StageClock c(0); check(ribbit_hip_load_record_pinned(h, bases, length)); }
@@ -357,11 +426,17 @@ void process_sequence(RibbitHandle *h, const RibbitRefineParams &prm, const std:
     { StageClock c(4); check(ribbit_hip_dispatch_seeds(h, &d, &nd)); }
     // one record over several GPUs: only worth it from a few hundred thousand seeds on (RIBBIT_SHARD_MIN_SEEDS: a test hook)
     static const size_t shard_min = std::getenv("RIBBIT_SHARD_MIN_SEEDS") ? (size_t)std::atoll(std::getenv("RIBBIT_SHARD_MIN_SEEDS")) : 400000;
-    std::vector<int32_t> mask_iv;        // the record's rows in BED order, read back once for both outputs
-    const bool rows = mask || repeats;
+    std::vector<int32_t> mask_iv;        // the record's rows in BED order, read back once for all outputs
+    const bool rows = jobs.any();
+    std::string bed_copy;                // the record's BED text when it came in slices and the loci quote it
+    const char *bed_text = nullptr;      // the record's BED text, for the loci's lines
+    size_t bed_len = 0;
     if (helpers && !helpers->empty() && nd >= shard_min && nd >= 2 * (helpers->size() + 1)) {
         StageClock c(5);
-        const bool sharded = refine_over_devices(h, *helpers, prm, name, bases, length, d, nd, out, log, rows ? &mask_iv : nullptr);
+        const bool sharded = refine_over_devices(h, *helpers, prm, name, bases, length, d, nd, out, log, rows ? &mask_iv : nullptr,
+                                                 jobs.loci ? &bed_copy : nullptr);
+        bed_text = bed_copy.data();
+        bed_len = bed_copy.size();
         if (std::getenv("RIBBIT_PROFILE"))
             log << "[devices] refinement of " << name << ": " << nd << " dispatched seeds " << (sharded ? "in " : "NOT in ") << helpers->size() + 1 << " slices over as many handles\n";
     } else {
@@ -369,7 +444,9 @@ void process_sequence(RibbitHandle *h, const RibbitRefineParams &prm, const std:
         size_t len;
         { StageClock c(5); check(ribbit_hip_refine_bed(h, &prm, name.c_str(), &text, &len)); }
         out.write(text, (std::streamsize)len);
-        if (rows) { StageClock c(mask ? 6 : 7); append_intervals(text, len, mask_iv); }
+        if (rows) { StageClock c(jobs.first_slot()); append_intervals(text, len, mask_iv); }
+        bed_text = text;                 // (handle-owned: valid until the handle's next refinement)
+        bed_len = len;
     }
     if (mask) {
         const char *body = nullptr;
@@ -387,6 +464,36 @@ void process_sequence(RibbitHandle *h, const RibbitRefineParams &prm, const std:
             { StageClock c(7); check(ribbit_hip_repeat_sequences(h, name.c_str(), mask_iv.data() + 2 * done, n - done, repeats->flank, &text, &len, &k)); }
             repeats->write(text, len);
         }
+    }
+    if (jobs.loci) {
+        const RibbitLocus *loci = nullptr;
+        size_t n_loci = 0;
+        char *text = nullptr;
+        size_t len = 0;
+        StageClock c(8);
+        check(ribbit_hip_record_loci(h, mask_iv.data(), mask_iv.size() / 2, jobs.loci->gap, &loci, &n_loci));
+        check(ribbit_bed_loci_text(name.c_str(), bed_text, bed_len, loci, n_loci, &text, &len));
+        jobs.loci->write(text, len);
+        ribbit_text_free(text);
+    }
+    if (jobs.density) {
+        const int32_t *covered = nullptr;
+        size_t n_windows = 0;
+        StageClock c(9);
+        check(ribbit_hip_record_density(h, mask_iv.data(), mask_iv.size() / 2, jobs.density->window, &covered, &n_windows));
+        std::string lines;
+        char num[24];
+        auto put = [&](int64_t v, char sep) { lines.append(num, (size_t)(std::to_chars(num, num + sizeof num, v).ptr - num)); lines += sep; };
+        for (size_t k = 0; k < n_windows; ++k) {
+            const int64_t from = (int64_t)k * jobs.density->window;
+            lines += name;
+            lines += '\t';
+            put(from, '\t');
+            put(std::min<int64_t>(from + jobs.density->window, length), '\t');
+            put(covered[k], '\n');
+            if (lines.size() > ((size_t)1 << 20)) { jobs.density->write(lines.data(), lines.size()); lines.clear(); }
+        }
+        jobs.density->write(lines.data(), lines.size());
     }
     log << "Total number of seeds that are processed for alignment: " << nd << "\t Time elapsed: " << secs() << "secs\n";
 }
@@ -412,6 +519,16 @@ int main(int argc, char **argv) {
         if (!repeat_file) die("--repeat-fasta: cannot open '" + opt.repeat_fasta + "' for writing");
     }
     const bool repeating = !opt.repeat_fasta.empty();
+    std::ofstream loci_file, density_file;
+    if (!opt.loci_bed.empty()) {
+        loci_file.open(opt.loci_bed, std::ios::binary);
+        if (!loci_file) die("--loci-bed: cannot open '" + opt.loci_bed + "' for writing");
+    }
+    if (!opt.density_bedgraph.empty()) {
+        density_file.open(opt.density_bedgraph, std::ios::binary);
+        if (!density_file) die("--density-bedgraph: cannot open '" + opt.density_bedgraph + "' for writing");
+    }
+    const bool merging = !opt.loci_bed.empty(), counting = !opt.density_bedgraph.empty();
 
     const auto t_run0 = std::chrono::steady_clock::now();
     RibbitRefineParams prm;
@@ -448,7 +565,7 @@ int main(int argc, char **argv) {
     jobs = std::min(jobs, 64);
     const int workers = jobs * ndev;
     struct Record { size_t index; std::string name; const char *bases; int64_t length; };
-    struct Result { std::string bed, log, masked, repeats; };
+    struct Result { std::string bed, log, masked, repeats, loci, density; };
     std::mutex mu;
     std::condition_variable cv;
     std::deque<Record> queue;
@@ -473,6 +590,8 @@ int main(int argc, char **argv) {
             out.write(it->second.bed.data(), (std::streamsize)it->second.bed.size());
             masked_file.write(it->second.masked.data(), (std::streamsize)it->second.masked.size());
             repeat_file.write(it->second.repeats.data(), (std::streamsize)it->second.repeats.size());
+            loci_file.write(it->second.loci.data(), (std::streamsize)it->second.loci.size());
+            density_file.write(it->second.density.data(), (std::streamsize)it->second.density.size());
             done.erase(it);
             ++next_out;
         }
@@ -513,6 +632,10 @@ int main(int argc, char **argv) {
             const MaskJob mask{opt.mask_mode, opt.mask_width, [&masked](const char *p, size_t n) { masked.append(p, n); }};
             std::string repeat_text;         // (kept in memory until the record's turn to be written, as the masked text is)
             const RepeatJob repeats{opt.flank, [&repeat_text](const char *p, size_t n) { repeat_text.append(p, n); }};
+            std::string loci_text, density_text;
+            const LociJob loci{opt.loci_gap, [&loci_text](const char *p, size_t n) { loci_text.append(p, n); }};
+            const DensityJob density{opt.density_window, [&density_text](const char *p, size_t n) { density_text.append(p, n); }};
+            const RowJobs row_jobs{masking ? &mask : nullptr, repeating ? &repeats : nullptr, merging ? &loci : nullptr, counting ? &density : nullptr};
             bool ok = true;
             std::string why;
             {
@@ -522,7 +645,7 @@ int main(int argc, char **argv) {
                     try {
                         check(ribbit_hip_set_host_threads(wh, (int)std::max(1u, dev_cores * (unsigned)weight / (unsigned)jobs)));
                         log << "Processing sequence " << rec.name << "\n";
-                        process_sequence(wh, prm, rec.name, rec.bases, rec.length, bed, log, masking ? &mask : nullptr, repeating ? &repeats : nullptr);
+                        process_sequence(wh, prm, rec.name, rec.bases, rec.length, bed, log, row_jobs);
                     } catch (const PathError &e) { ok = false; why = e.what; }
                 }
             }
@@ -530,7 +653,7 @@ int main(int argc, char **argv) {
             {
                 std::lock_guard<std::mutex> lk(mu);
                 if (!ok && !failed) { failed = true; failure = why; }
-                done[rec.index] = Result{bed.str(), log.str(), std::move(masked), std::move(repeat_text)};
+                done[rec.index] = Result{bed.str(), log.str(), std::move(masked), std::move(repeat_text), std::move(loci_text), std::move(density_text)};
                 tokens[(size_t)dev] += weight;
                 if (!failed) flush_ready();
             }
@@ -594,9 +717,12 @@ int main(int argc, char **argv) {
             // (every record the reader hands out is masked but the nameless empty one of a file without records, Q4)
             const MaskJob mask{opt.mask_mode, opt.mask_width, [&masked_file](const char *p, size_t n) { masked_file.write(p, (std::streamsize)n); }};
             const RepeatJob repeats{opt.flank, [&repeat_file](const char *p, size_t n) { repeat_file.write(p, (std::streamsize)n); }};
+            const LociJob loci{opt.loci_gap, [&loci_file](const char *p, size_t n) { loci_file.write(p, (std::streamsize)n); }};
+            const DensityJob density{opt.density_window, [&density_file](const char *p, size_t n) { density_file.write(p, (std::streamsize)n); }};
             const bool real_last = !(last_name.empty() && last_length == 0);
-            process_sequence(h, prm, last_name, last_bases ? last_bases : kNoBases, last_length, out, std::cerr, masking && real_last ? &mask : nullptr,
-                             repeating && real_last ? &repeats : nullptr, &helpers);
+            const RowJobs row_jobs{masking && real_last ? &mask : nullptr, repeating && real_last ? &repeats : nullptr,
+                                   merging && real_last ? &loci : nullptr, counting && real_last ? &density : nullptr};
+            process_sequence(h, prm, last_name, last_bases ? last_bases : kNoBases, last_length, out, std::cerr, row_jobs, &helpers);
         } catch (const PathError &e) { failed = true; failure = e.what; }
     }
     if (failed) { std::cerr << "ribbit-hip: " << failure << "\n"; status = 1; }
@@ -624,12 +750,16 @@ int main(int argc, char **argv) {
            << ", \"anchored\": " << g_stage_ms[3] << ", \"dispatch\": " << g_stage_ms[4] << ", \"refine_and_bed\": " << g_stage_ms[5];
         if (masking) tf << ", \"mask\": " << g_stage_ms[6];
         if (repeating) tf << ", \"repeats\": " << g_stage_ms[7];
+        if (merging) tf << ", \"loci\": " << g_stage_ms[8];
+        if (counting) tf << ", \"density\": " << g_stage_ms[9];
         tf << "}}\n";
     }
     if (std::getenv("RIBBIT_PROFILE"))
         std::cerr << "[stages, ms over all records] load " << g_stage_ms[0] << "  perfect " << g_stage_ms[1] << "  substitutions "
                   << g_stage_ms[2] << "  anchored " << g_stage_ms[3] << "  dispatch " << g_stage_ms[4] << "  refine+BED " << g_stage_ms[5]
                   << (masking ? "  mask " + std::to_string(g_stage_ms[6]) : std::string())
-                  << (repeating ? "  repeats " + std::to_string(g_stage_ms[7]) : std::string()) << "\n";
+                  << (repeating ? "  repeats " + std::to_string(g_stage_ms[7]) : std::string())
+                  << (merging ? "  loci " + std::to_string(g_stage_ms[8]) : std::string())
+                  << (counting ? "  density " + std::to_string(g_stage_ms[9]) : std::string()) << "\n";
     return status;
 }
