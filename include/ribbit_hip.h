@@ -622,6 +622,12 @@ void ribbit_debug_last_device_merge(int32_t out[5]);
 /* Test hook: in how many independent ranges the calling thread's last dispatch merge (fasta_utils.cpp:187-224) ran; 1 = the
  * sequential merge (no cuts, or a list did not split cleanly at them). */
 int32_t ribbit_debug_last_dispatch_ranges(void);
+/* Test hook: faults in the teams of host threads the library runs its host stages on (process-wide; -1 turns a mode off).  From
+ * the call on, in every team of two parts or more: with refuse_starts_from >= 0 the team's thread start number refuse_starts_from
+ * (0 = its first) and every later one fail as a start the system refuses does -- the parts left over run on the calling thread and
+ * the result is the same; with throw_in_part >= 0 that part throws std::bad_alloc before its work -- the entry point returns
+ * RIBBIT_E_NOMEM with every thread joined.  Returns the number of faults injected since the previous call. */
+int64_t ribbit_host_debug_thread_faults(int32_t refuse_starts_from, int32_t throw_in_part);
 
 /* possibleMotifs (parse_smallmotif_seed.cpp:76-188) of every dispatched seed with m <= 10 that reaches it, computed
  * by one GPU launch (small_motifs.hip) -- what ribbit_hip_refine_jobs / ribbit_hip_refine_bed use for those seeds.

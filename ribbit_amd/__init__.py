@@ -44,7 +44,7 @@ ABI_SYMBOLS = [
     "ribbit_hip_last_timing_ms", "ribbit_hip_last_event_count",
     "ribbit_hip_subst_calls", "ribbit_hip_seeds_substitutions",
     "ribbit_host_replay_calls", "ribbit_seed_lists_free", "ribbit_host_longest_runs", "ribbit_debug_set_merge_min_range", "ribbit_debug_last_merge",
-    "ribbit_hip_small_motifs", "ribbit_debug_small_motif_counters", "ribbit_debug_last_dispatch_ranges", "ribbit_debug_last_device_merge", "ribbit_debug_alignment_counters", "ribbit_debug_level_counters",
+    "ribbit_hip_small_motifs", "ribbit_debug_small_motif_counters", "ribbit_debug_last_dispatch_ranges", "ribbit_host_debug_thread_faults", "ribbit_debug_last_device_merge", "ribbit_debug_alignment_counters", "ribbit_debug_level_counters",
     "ribbit_hip_adopt_dispatch", "ribbit_hip_refine_met_empty_query", "ribbit_hip_device_pci_bus_id",
     "ribbit_hip_anchored_calls", "ribbit_hip_seeds_anchored", "ribbit_hip_dispatch_seeds", "ribbit_hip_guard_hits",
     "ribbit_hip_debug_stream_read",
@@ -197,6 +197,8 @@ def load_library():
     L.ribbit_debug_last_device_merge.argtypes = [C.POINTER(C.c_int32 * 5)]
     L.ribbit_debug_last_dispatch_ranges.restype = C.c_int32
     L.ribbit_debug_last_dispatch_ranges.argtypes = []
+    L.ribbit_host_debug_thread_faults.restype = i64
+    L.ribbit_host_debug_thread_faults.argtypes = [C.c_int32, C.c_int32]
     L.ribbit_debug_alignment_counters.restype = None
     L.ribbit_debug_alignment_counters.argtypes = [C.POINTER(C.c_int64 * 3)]
     L.ribbit_hip_device_pci_bus_id.argtypes = [C.c_int, C.c_char_p, C.c_size_t]

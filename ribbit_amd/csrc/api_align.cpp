@@ -18,23 +18,14 @@ int build_longest_runs(RibbitHandle *h) {
         // Through page-locked memory, copied on the host threads: the list is a quarter of a gigabyte for a chromosome, and a copy
         // straight from (or to) a vector's pageable storage runs at a tenth of the link's speed on one thread.
         if ((rc = h->h_seed_stage.ensure(n)) || (rc = h->h_longest_stage.ensure(n))) return rc;
-        unsigned nt = h->host_threads ? h->host_threads : std::min(std::thread::hardware_concurrency(), 16u);
-        if (!h->host_threads)
-            if (const char *env = std::getenv("RIBBIT_THREADS")) nt = (unsigned)std::max(1, std::atoi(env));
-        nt = (unsigned)std::max<size_t>(1, std::min<size_t>(nt, n / 262144 + 1));
-        auto on_threads = [&](auto fn) {
-            std::vector<std::thread> pool;
-            for (unsigned t = 1; t < nt; ++t) pool.emplace_back(fn, n * t / nt, n * (t + 1) / nt);
-            fn((size_t)0, n / nt);
-            for (std::thread &th : pool) th.join();
-        };
-        on_threads([&](size_t lo, size_t hi) { std::memcpy(h->h_seed_stage.p + lo, h->dispatch.data() + lo, (hi - lo) * sizeof(RibbitSeed)); });
+        const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(rb::host_thread_count(h->host_threads), n / 262144 + 1));
+        rb::over_pieces(n, nt, [&](size_t lo, size_t hi, unsigned) { std::memcpy(h->h_seed_stage.p + lo, h->dispatch.data() + lo, (hi - lo) * sizeof(RibbitSeed)); });
         HIP_TRY(hipMemcpyAsync(h->d_seeds.p, h->h_seed_stage.p, n * sizeof(RibbitSeed), hipMemcpyHostToDevice, h->stream));
         rb::launch_seed_longest_runs(h->d_xa.p, h->xa_stride, h->params.min_motif, h->d_seeds.p, (int64_t)n, h->d_longest.p, h->stream);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(h->h_longest_stage.p, h->d_longest.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
-        on_threads([&](size_t lo, size_t hi) { std::memcpy(h->longest_runs.data() + lo, h->h_longest_stage.p + lo, (hi - lo) * sizeof(int32_t)); });
+        rb::over_pieces(n, nt, [&](size_t lo, size_t hi, unsigned) { std::memcpy(h->longest_runs.data() + lo, h->h_longest_stage.p + lo, (hi - lo) * sizeof(int32_t)); });
     }
     h->rec.longest_valid = true;
     return RIBBIT_OK;
@@ -51,23 +42,15 @@ int best_rows_of(RibbitHandle *h, const RibbitRefineParams &prm, const rb::SeedV
     {
         // the usable length of every long-motif seed (a walk over its bases up to the first N) on the host threads: 0.8 M seeds of
         // a hundred bases per 64 Mbp were 80 ms on one
-        unsigned nt = h->host_threads ? h->host_threads : std::min(std::thread::hardware_concurrency(), 16u);
-        if (!h->host_threads)
-            if (const char *env = std::getenv("RIBBIT_THREADS")) nt = (unsigned)std::max(1, std::atoi(env));
-        nt = (unsigned)std::max<size_t>(1, std::min<size_t>(nt, n / 65536 + 1));
+        const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(rb::host_thread_count(h->host_threads), n / 65536 + 1));
         std::vector<rb::SeedVec> part(nt);
-        auto work = [&](unsigned t) {
-            const size_t lo = n * t / nt, hi = n * (t + 1) / nt;
+        rb::over_pieces(n, nt, [&](size_t lo, size_t hi, unsigned t) {
             for (size_t i = lo; i < hi; ++i) {
                 const RibbitSeed &s = seeds[i];
                 if (best[i] >= 0 || s.mlen <= 10 || s.end - s.start < 0.9 * s.mlen || longest[i] < prm.continuous_ones_threshold) continue;
                 part[t].push_back(RibbitSeed{s.start, rb::usable_length_host(h->host, s.start, s.end, s.mlen), s.mlen, (int32_t)i});
             }
-        };
-        std::vector<std::thread> pool;
-        for (unsigned t = 1; t < nt; ++t) pool.emplace_back(work, t);
-        work(0);
-        for (std::thread &th : pool) th.join();
+        });
         for (const rb::SeedVec &p : part) jobs.insert(jobs.end(), p.begin(), p.end());
     }
     if (!jobs.empty()) {
@@ -108,15 +91,8 @@ int build_best_rows(RibbitHandle *h, const RibbitRefineParams &prm) {
         // (-1 everywhere, on the host threads: seventy megabytes for a chromosome were 10-15 ms of every refinement on one)
         const size_t n = h->dispatch.size();
         h->best_rows.resize(n);
-        unsigned nt = h->host_threads ? h->host_threads : std::min(std::thread::hardware_concurrency(), 16u);
-        if (!h->host_threads)
-            if (const char *env = std::getenv("RIBBIT_THREADS")) nt = (unsigned)std::max(1, std::atoi(env));
-        nt = (unsigned)std::max<size_t>(1, std::min<size_t>(nt, n / 1048576 + 1));
-        auto fill = [&](size_t lo, size_t hi) { std::fill(h->best_rows.begin() + (std::ptrdiff_t)lo, h->best_rows.begin() + (std::ptrdiff_t)hi, -1); };
-        std::vector<std::thread> pool;
-        for (unsigned t = 1; t < nt; ++t) pool.emplace_back(fill, n * t / nt, n * (t + 1) / nt);
-        fill(0, n / nt);
-        for (std::thread &th : pool) th.join();
+        const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(rb::host_thread_count(h->host_threads), n / 1048576 + 1));
+        rb::over_pieces(n, nt, [&](size_t lo, size_t hi, unsigned) { std::fill(h->best_rows.begin() + (std::ptrdiff_t)lo, h->best_rows.begin() + (std::ptrdiff_t)hi, -1); });
     }
     if ((rc = best_rows_of(h, prm, h->dispatch, h->longest_runs.data(), h->best_rows.data()))) return rc;
     h->rec.best_rows_valid = true;
@@ -176,8 +152,7 @@ int build_small_motifs(RibbitHandle *h, const RibbitRefineParams &prm, hipStream
         }
         h->n_small_records = used;
     }
-    static const bool profile = std::getenv("RIBBIT_PROFILE") != nullptr;
-    if (profile) std::fprintf(stderr, "[small motifs] %zu dispatched seeds looked at on the GPU, %zu records, %.1f ms incl. transfers\n", n, h->n_small_records, now_ms() - t0);
+    if (rb::profile_on()) std::fprintf(stderr, "[small motifs] %zu dispatched seeds looked at on the GPU, %zu records, %.1f ms incl. transfers\n", n, h->n_small_records, now_ms() - t0);
     h->rec.small_valid = true;
     return RIBBIT_OK;
 }
@@ -203,9 +178,10 @@ int scan_seeds_side_by_side(RibbitHandle *h, const RibbitRefineParams &prm) {
         try { small_rc = build_small_motifs(h, prm, h->copy_stream); if (small_rc) small_error = g_last_error; }
         catch (const std::bad_alloc &) { small_rc = RIBBIT_E_NOMEM; small_error = "out of host memory in the small-motif scan"; }
     });
-    try { rc = build_best_rows(h, prm); }
-    catch (...) { side.join(); throw; }
-    side.join();
+    {
+        rb::JoinOnExit join_side({}, side);
+        rc = build_best_rows(h, prm);
+    }
     if (rc) return rc;
     if (small_rc) { g_last_error = small_error; return small_rc; }
     return RIBBIT_OK;
@@ -584,9 +560,7 @@ int ribbit_host_refine_jobs(const RibbitScanParams *params, const RibbitRefinePa
         std::vector<std::vector<RibbitAlignJob>> slice_jobs(n_slices);
         std::vector<std::string> slice_pool(n_slices);
         std::mutex mu;
-        unsigned nt = std::min(std::thread::hardware_concurrency(), 16u);
-        if (const char *env = std::getenv("RIBBIT_THREADS")) nt = (unsigned)std::max(1, std::atoi(env));
-        rb::build_align_jobs_slices(hp, *prm, seeds, longest.data(), nullptr, nt, nullptr, bounds,
+        rb::build_align_jobs_slices(hp, *prm, seeds, longest.data(), nullptr, rb::host_thread_count(0), nullptr, bounds,
                                     [&](size_t c, std::vector<RibbitAlignJob> &&j, std::string &&p) {
                                         std::lock_guard<std::mutex> lk(mu);
                                         slice_jobs[c] = std::move(j);
@@ -620,11 +594,14 @@ int ribbit_host_longest_runs(const RibbitScanParams *params, int64_t length, con
     std::memcpy(hp.brk.data(), brk, nwords * sizeof(uint32_t));
     hp.xa_m_lo = params->min_motif;
     hp.xa_m_hi = params->max_motif;
-    for (size_t i = 0; i < n; ++i) {
+    for (size_t i = 0; i < n; ++i)
         if (seeds[i].start < 0 || seeds[i].end > length || seeds[i].start > seeds[i].end || seeds[i].mlen < 1 || seeds[i].mlen > params->max_motif + 2)
             return fail(RIBBIT_E_ARG, "seed %zu outside the record or the shift range", i);
-        out[i] = rb::longest_run_host(hp, seeds[i].mlen, seeds[i].start, seeds[i].end);
-    }
+    // (on the host threads, a piece per 1024 seeds: every seed recomputes its slice of a composed plane)
+    const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(rb::host_thread_count(0), n / 1024 + 1));
+    rb::over_pieces(n, nt, [&](size_t lo, size_t hi, unsigned) {
+        for (size_t i = lo; i < hi; ++i) out[i] = rb::longest_run_host(hp, seeds[i].mlen, seeds[i].start, seeds[i].end);
+    });
     return RIBBIT_OK;
 }); }
 

@@ -117,7 +117,7 @@ int ribbit_host_merge_chunks(const RibbitScanParams *params, int64_t length,
         sl.max_motif = params->max_motif;
         sl.min_shift = (params->min_motif > 2) ? params->min_motif - 2 : 1;
         sl.range_count = [&hp](int shift, int start, int end) { return hp.range_count(shift, start, end); };
-        const unsigned threads = rb::merge_threads(0);
+        const unsigned threads = rb::host_thread_count(0);
 
         // ---- perfect stage: the chunks' complete runs, and the runs a chunk edge cut, paired across chunks
         {

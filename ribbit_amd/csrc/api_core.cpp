@@ -34,17 +34,11 @@ int pinned_alloc(size_t bytes, void **out) {
         if (p != MAP_FAILED) {
             (void)madvise(p, len, MADV_HUGEPAGE);
             // fault the pages in on several threads (one touch per 4 KB covers both page sizes): registration alone would do it on one
-            const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(std::min(std::thread::hardware_concurrency(), 16u), len >> 26));
-            auto touch = [p, len, nt](unsigned t) {
+            const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(std::min(rb::host_thread_count(0), 16u), len >> 26));
+            rb::on_threads(nt, [p, len, nt](unsigned t) {
                 volatile char *c = static_cast<volatile char *>(p);
                 for (size_t i = len / nt * t, e = t + 1 == nt ? len : len / nt * (t + 1); i < e; i += 4096) c[i] = 0;
-            };
-            std::vector<std::thread> pool;
-            unsigned started = 1;          // part 0 is this thread's
-            try { for (; started < nt; ++started) pool.emplace_back(touch, started); } catch (...) {}
-            touch(0);
-            for (unsigned t = started; t < nt; ++t) touch(t);      // (parts whose thread could not start)
-            for (std::thread &th : pool) th.join();
+            });
             if (hipHostRegister(p, len, hipHostRegisterDefault) == hipSuccess) {
                 std::lock_guard<std::mutex> lk(g_mapped_mu);
                 g_mapped.emplace_back(p, len);
@@ -194,6 +188,8 @@ void ribbit_scan_params_default(RibbitScanParams *p, int32_t min_motif, int32_t 
 const char *ribbit_hip_last_error(void) { return g_last_error.c_str(); }
 
 int ribbit_hip_abi_version(void) { return RIBBIT_ABI_VERSION; }
+
+int64_t ribbit_host_debug_thread_faults(int32_t refuse_starts_from, int32_t throw_in_part) { return rb::set_thread_faults(refuse_starts_from, throw_in_part); }
 
 int ribbit_hip_device_count(void) {
     int n = 0;

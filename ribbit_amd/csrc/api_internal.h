@@ -11,6 +11,11 @@
 //   api_mask.cpp        the repeat-masked FASTA body of a record (mask.hip), its host twin, BED rows back to intervals
 //   api_repeats.cpp     every row's bases with their flanks as FASTA entries (repeats.hip), in batches of a text budget; its host twin
 //   api_loci.cpp        merged, sorted loci and the per-window density of a record (loci.hip), their host twins, the loci as text
+// Host threads: every team of them, here and in refine.cpp, parallel_merge.cpp and host_planes.cpp, is started by rb::on_threads /
+// rb::over_pieces of host_threads.h (part 0 on the caller, a thread that cannot start leaves its part to the caller, all joined, the
+// first exception of any part rethrown on the caller: it then meets guarded() below); the thread count rule (the handle's, else
+// RIBBIT_THREADS, else min(cores, 16)) is rb::host_thread_count, the RIBBIT_PROFILE switch rb::profile_on, and the threads that
+// outlive one loop (feeders, tabler, side, ...) are joined by an rb::JoinOnExit.
 // Not part of the ABI; nothing outside ribbit_amd/csrc includes it.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -35,6 +40,7 @@
 #include "device_planes.h"
 #include "event_stream.h"
 #include "host_planes.h"
+#include "host_threads.h"
 #include "kernels.h"
 #include "parallel_merge.h"
 #include "refine.h"
@@ -56,9 +62,10 @@ int fail(int code, const char *fmt, ...);
 // fields of the handle or of globals: ribbit_hip_abi_version, ribbit_hip_device_count (a count, not a status), ribbit_hip_set_stream,
 // ribbit_hip_set_timing, ribbit_hip_set_host_threads, ribbit_hip_debug_set_event_capacity, ribbit_hip_debug_set_scan_split,
 // ribbit_hip_debug_last_scan_split, ribbit_hip_debug_set_repeat_text_budget, ribbit_hip_refine_met_empty_query,
-// ribbit_hip_guard_hits, ribbit_hip_last_event_count, ribbit_hip_plane_words, ribbit_hip_last_error, ribbit_hip_host_free and the
+// ribbit_hip_guard_hits, ribbit_host_debug_thread_faults, ribbit_hip_last_event_count, ribbit_hip_plane_words, ribbit_hip_last_error, ribbit_hip_host_free and the
 // other *_free functions, ribbit_*_params_default, the ribbit_debug_* counter readers and setters; and ribbit_hip_close, which is
-// `delete` (a destructor does not throw).  Threads the library starts keep an exception inside themselves where they are made.
+// `delete` (a destructor does not throw).  A team of threads hands an exception of any part to its caller (host_threads.h); the
+// threads that outlive one loop keep theirs inside themselves where they are made.
 template <typename F>
 int guarded(const char *what, F &&body) {
     try { return body(); }
@@ -211,7 +218,7 @@ struct RibbitHandle {
     double host_ms = 0.0;         // post-processing of the last scan after its pairing (device state machine, sort, read-back), wall clock
     double merge_ms = 0.0;        // sequential host merge of the last window stage, wall clock
     double subst_merge_ms = 0.0;  // ... of the substitution stage when ribbit_hip_seeds_anchored ran both
-    unsigned host_threads = 0;    // worker threads of the host stages (0 = RIBBIT_THREADS or min(cores, 16))
+    unsigned host_threads = 0;    // worker threads of the host stages (0 = RIBBIT_THREADS or min(cores, 16): rb::host_thread_count)
 
     bool loaded = false;
     int64_t length = 0;

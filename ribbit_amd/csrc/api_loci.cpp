@@ -178,29 +178,15 @@ int host_record_density_impl(int64_t length, const int32_t *intervals, size_t n,
 }
 
 // ---- the loci as text
-// fn(k) for k in [0, parts) on as many threads; a thread that cannot start leaves its part and the ones after it to the caller
-template <typename F>
-void in_parts(size_t parts, F &&fn) {
-    std::vector<std::thread> pool;
-    try {
-        for (size_t k = 1; k < parts; ++k) pool.emplace_back(fn, k);
-    } catch (...) {
-        for (size_t k = pool.size() + 1; k < parts; ++k) fn(k);
-    }
-    fn(0);
-    for (std::thread &t : pool) t.join();
-}
-
 int bed_loci_text_impl(const char *name, const char *bed, size_t bed_len, const RibbitLocus *loci, size_t n_loci, char **text, size_t *len) {
     if (!name || !text || !len || (!bed && bed_len > 0) || (!loci && n_loci > 0)) return fail(RIBBIT_E_ARG, "null argument");
     // a chromosome's BED is 150-200 MB of text: its line starts are found in pieces, one thread per piece of at least 4 MB, and
     // the loci's lines are written in as many pieces
-    const unsigned hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    const size_t parts = n_loci ? std::max<size_t>(1, std::min<size_t>(hw, bed_len >> 22)) : 1;
+    const size_t parts = n_loci ? std::max<size_t>(1, std::min<size_t>(std::min(rb::host_thread_count(0), 16u), bed_len >> 22)) : 1;
     std::vector<std::vector<size_t>> starts(parts);      // per piece: the offsets just behind its newlines
     std::vector<char> oom(parts, 0);
     if (n_loci)
-        in_parts(parts, [&](size_t k) {
+        rb::on_threads((unsigned)parts, [&](unsigned k) {
             try {
                 const char *p = bed + bed_len * k / parts, *end = bed + bed_len * (k + 1) / parts;
                 while (p < end && (p = static_cast<const char *>(std::memchr(p, '\n', (size_t)(end - p)))) != nullptr) starts[k].push_back((size_t)(++p - bed));
@@ -216,7 +202,7 @@ int bed_loci_text_impl(const char *name, const char *bed, size_t bed_len, const 
     const size_t out_parts = std::max<size_t>(1, std::min<size_t>(parts, n_loci >> 12));
     std::vector<std::string> piece(out_parts);
     std::vector<size_t> bad(out_parts, (size_t)-1);
-    in_parts(out_parts, [&](size_t k) {
+    rb::on_threads((unsigned)out_parts, [&](unsigned k) {
         try {
             char num[16];
             std::string &out = piece[k];

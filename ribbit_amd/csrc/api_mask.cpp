@@ -143,8 +143,7 @@ const char *parse_rows(const char *p, const char *end, std::vector<int32_t> &out
 int bed_intervals_impl(const char *text, size_t len, int32_t **pairs, size_t *n) {
     if (!pairs || !n || (!text && len > 0)) return fail(RIBBIT_E_ARG, "null argument");
     // a chromosome's BED is 150-200 MB of text: parsed in pieces of whole lines, one thread per piece of at least 4 MB
-    const unsigned hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    const size_t parts = std::max<size_t>(1, std::min<size_t>(hw, len >> 22));
+    const size_t parts = std::max<size_t>(1, std::min<size_t>(std::min(rb::host_thread_count(0), 16u), len >> 22));
     std::vector<const char *> cut(parts + 1, text + len);
     cut[0] = text;
     for (size_t k = 1; k < parts; ++k) {
@@ -155,17 +154,9 @@ int bed_intervals_impl(const char *text, size_t len, int32_t **pairs, size_t *n)
     std::vector<std::vector<int32_t>> rows(parts);
     std::vector<const char *> bad(parts, nullptr);
     std::vector<char> oom(parts, 0);
-    auto run = [&](size_t k) {
+    rb::on_threads((unsigned)parts, [&](unsigned k) {
         try { bad[k] = parse_rows(cut[k], cut[k + 1], rows[k]); } catch (const std::bad_alloc &) { oom[k] = 1; }
-    };
-    std::vector<std::thread> pool;
-    try {
-        for (size_t k = 1; k < parts; ++k) pool.emplace_back(run, k);
-    } catch (...) {            // a thread that could not start: its piece and the ones after it run here
-        for (size_t k = pool.size() + 1; k < parts; ++k) run(k);
-    }
-    run(0);
-    for (std::thread &t : pool) t.join();
+    });
     size_t total = 0;
     for (size_t k = 0; k < parts; ++k) {
         if (oom[k]) return fail(RIBBIT_E_NOMEM, "out of host memory reading BED rows");

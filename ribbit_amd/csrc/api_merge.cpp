@@ -16,7 +16,7 @@ bool run_device_pass(RibbitHandle *h, RibbitCall *d_calls, const int32_t *d_pend
                      const std::vector<uint32_t> &order, size_t device_limit, const std::function<void(uint32_t *, const uint32_t *)> &meanwhile,
                      std::vector<rb::AnchoredDevicePass::RangeResult> &ranges, std::vector<rb::AnchoredDevicePass::LogEntry> &undo,
                      std::vector<rb::AnchoredDevicePass::LogEntry> &reads, std::vector<rb::AnchoredDevicePass::HeadEntry> &heads) {
-    static const bool profile = std::getenv("RIBBIT_PROFILE") != nullptr;
+    const bool profile = rb::profile_on();
     const double t0 = now_ms();
     RibbitHandle::MergeBufs &mg = h->mg;
     const size_t nr = cut_pos.size(), nP = lists.perfect.size(), nS = lists.subst.size(), n = kc.n;

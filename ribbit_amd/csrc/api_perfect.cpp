@@ -278,7 +278,7 @@ int advance_to_perfect(RibbitHandle *h) {
     h->lists.perfect.clear();
     for (const RibbitCall &c : h->perfect_calls) rb::perfect_add(h->lists, c.start, c.end, c.mlen);
     h->rec.stage_done = STAGE_PERFECT;
-    static const bool profile = std::getenv("RIBBIT_PROFILE") != nullptr;
+    const bool profile = rb::profile_on();
     if (profile) std::fprintf(stderr, "[perfect stage] scan, pairing, runs and planes to the host, calls %.1f ms; merge of %zu calls into %zu seeds on one thread %.1f ms\n",
                               t1 - t0, h->perfect_calls.size(), h->lists.perfect.size(), now_ms() - t1);
     return RIBBIT_OK;

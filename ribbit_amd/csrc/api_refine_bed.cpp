@@ -49,7 +49,7 @@ constexpr size_t LEVEL_OWN_BATCH = 400;
 
 static int refine_levels(RibbitHandle *h, const RibbitRefineParams &prm, const std::string &sequence_id, std::vector<rb::DeferredNode> &nodes,
                          std::vector<rb::BedPiece> &pieces, unsigned threads, bool *order_dependent, int64_t counts[3]) {
-    static const bool profile = std::getenv("RIBBIT_PROFILE") != nullptr;
+    const bool profile = rb::profile_on();
     const char *own_env = std::getenv("RIBBIT_LEVEL_MIN");          // (test hook, read per record: levels from this many nodes on get a batch of their own)
     const size_t own_batch = own_env ? (size_t)std::max(1, std::atoi(own_env)) : LEVEL_OWN_BATCH;
     static const bool level_lines = profile && std::getenv("RIBBIT_PROFILE_LEVELS") != nullptr;
@@ -138,10 +138,7 @@ static void join_pieces(RibbitHandle *h, std::vector<rb::BedPiece> &pieces, unsi
             for (size_t q = k; q < std::min(pieces.size(), k + 64); ++q)
                 if (!pieces[q].text.empty()) std::memcpy(h->bed_raw.get() + at[q], pieces[q].text.data(), pieces[q].text.size());
     };
-    std::vector<std::thread> pool;
-    for (unsigned t = 1; t < nt; ++t) pool.emplace_back(place);
-    place();
-    for (std::thread &th : pool) th.join();
+    rb::on_threads(nt, [&](unsigned) { place(); });
 }
 
 static std::atomic<int64_t> g_level_counts[3];      // levels run, nodes put off, their alignments (process-wide, cumulative)
@@ -156,7 +153,7 @@ static int refine_bed_impl(RibbitHandle *h, const RibbitRefineParams *prm, const
     const double t_begin = now_ms();
     static std::atomic<int64_t> t_rows_us{0}, t_text_us{0}, t_jobs_us{0};
     auto add_ms = [](std::atomic<int64_t> &acc, double ms) { acc.fetch_add((int64_t)(ms * 1000.0), std::memory_order_relaxed); };
-    static const bool profile = std::getenv("RIBBIT_PROFILE") != nullptr;
+    const bool profile = rb::profile_on();
     double t0 = now_ms();
     int rc = scan_seeds_side_by_side(h, *prm);
     if (rc) return rc;
@@ -182,9 +179,7 @@ static int refine_bed_impl(RibbitHandle *h, const RibbitRefineParams *prm, const
     constexpr size_t GPU_SSW_MIN_SEEDS = 400000;
     static const char *const gpu_ssw_env = std::getenv("RIBBIT_GPU_SSW");
     const bool gpu_ssw = gpu_ssw_env ? std::atoi(gpu_ssw_env) != 0 : h->dispatch.size() >= GPU_SSW_MIN_SEEDS;
-    unsigned threads = h->host_threads ? h->host_threads : std::min(std::thread::hardware_concurrency(), 16u);
-    if (!h->host_threads)
-        if (const char *env = std::getenv("RIBBIT_THREADS")) threads = (unsigned)std::max(1, std::atoi(env));
+    const unsigned threads = rb::host_thread_count(h->host_threads);
     bool done = false;
     if (gpu_ssw && !h->dispatch.empty()) {
         // The pipeline (DESIGN.md 7 has the measurements behind every step):
@@ -209,17 +204,12 @@ static int refine_bed_impl(RibbitHandle *h, const RibbitRefineParams *prm, const
         {   // (on the threads, pieces joined in order: seventeen million seeds on one thread were a quarter of this step)
             const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(threads, n_seeds / 262144 + 1));
             std::vector<std::vector<uint32_t>> part(nt);
-            auto scan = [&](unsigned t) {
-                const size_t lo = n_seeds * t / nt, hi = n_seeds * (t + 1) / nt;
+            rb::over_pieces(n_seeds, nt, [&](size_t lo, size_t hi, unsigned t) {
                 for (size_t i = lo; i < hi; ++i) {
                     const RibbitSeed &sd = h->dispatch[i];
                     if ((int64_t)sd.end - sd.start + sd.mlen > 500 || sd.mlen > 400) part[t].push_back((uint32_t)i);
                 }
-            };
-            std::vector<std::thread> pool;
-            for (unsigned t = 1; t < nt; ++t) pool.emplace_back(scan, t);
-            scan(0);
-            for (std::thread &th : pool) th.join();
+            });
             for (const std::vector<uint32_t> &pt : part) cand.insert(cand.end(), pt.begin(), pt.end());
         }
         std::vector<RibbitAlignJob> cand_jobs;
@@ -279,10 +269,8 @@ static int refine_bed_impl(RibbitHandle *h, const RibbitRefineParams *prm, const
         const size_t level_batch = level_env ? (size_t)std::max(1, std::atoi(level_env)) : LEVEL_OWN_BATCH;
         if ((rc = bind_device(h))) return rc;       // before any helper thread exists: nothing to join on this way out
         std::thread long_thread, later_thread;
-        struct JoinGuard {
-            std::atomic<bool> &stop; std::condition_variable &cv; std::thread &a, &b;
-            ~JoinGuard() { stop = true; cv.notify_all(); if (a.joinable()) a.join(); if (b.joinable()) b.join(); }
-        } join_guard{stop, cv, later_thread, long_thread};
+        const auto stop_all = [&stop, &cv]() { stop = true; cv.notify_all(); };
+        rb::JoinOnExit join_guard(stop_all, later_thread, long_thread);
         static const bool fail_later_slices = std::getenv("RIBBIT_DEBUG_FAIL_BATCHES") != nullptr;      // test hook: see below
         if (!long_jobs.empty()) {
             if (!h->aux && (rc = ribbit_hip_open(&h->params, h->device, &h->aux))) return rc;
@@ -413,7 +401,7 @@ static int refine_bed_impl(RibbitHandle *h, const RibbitRefineParams *prm, const
             sl.t_feed = now_ms() - tf0;
         };
         std::thread tabler;
-        struct TablerGuard { std::atomic<bool> &stop; std::condition_variable &cv; std::thread &t; ~TablerGuard() { stop = true; cv.notify_all(); if (t.joinable()) t.join(); } } tabler_guard{stop, cv, tabler};
+        rb::JoinOnExit tabler_guard(stop_all, tabler);
         tabler = std::thread([&]() {
             for (size_t c = 0; c < n_slices; ++c) {
                 { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&]() { return slices[c].built || stop.load(); }); if (!slices[c].built) return; }
@@ -449,15 +437,11 @@ static int refine_bed_impl(RibbitHandle *h, const RibbitRefineParams *prm, const
                 if (slices[c].rc) break;
             }
         };
-        std::vector<std::thread> feeders;
-        struct FeederGuard {
-            std::atomic<bool> &stop; std::condition_variable &cv; std::vector<std::thread> &all;
-            ~FeederGuard() { stop = true; cv.notify_all(); for (std::thread &t : all) if (t.joinable()) t.join(); }
-        } feeder_guard{stop, cv, feeders};
-        feeders.reserve(n_feeders);
+        std::thread feeders[FEEDERS];
+        rb::JoinOnExit feeder_guard(stop_all, feeders);
         for (size_t k = 0; k < n_feeders; ++k) {
             RibbitHandle *fh = k == 0 ? h : h->feed_aux[k - 1];
-            feeders.emplace_back([&feeder_loop, k, fh]() { feeder_loop(k, fh); });
+            feeders[k] = std::thread([&feeder_loop, k, fh]() { feeder_loop(k, fh); });
         }
         {
             // all slices in one parallel region (refine.cpp): a slice is handed over by the thread that finished its last chunk
@@ -500,7 +484,7 @@ static int refine_bed_impl(RibbitHandle *h, const RibbitRefineParams *prm, const
         }
         stop = true;
         cv.notify_all();
-        for (std::thread &t : feeders) t.join();
+        for (size_t k = 0; k < n_feeders; ++k) feeders[k].join();
         const double tw = now_ms();
         if (long_thread.joinable()) long_thread.join();
         if (later_thread.joinable()) later_thread.join();

@@ -136,7 +136,7 @@ int window_stage_device(RibbitHandle *h, int which, bool full, int (*min_span)(i
     PinnedBuf<RibbitCall> &h_calls = h->h_calls_[which - 1], &h_flush = h->h_flush_[which - 1];
     PinnedBuf<int32_t> &h_pend = h->h_pend_[which - 1];
     PinnedBuf<uint32_t> &h_ws = h->h_ws_[which - 1];
-    static const bool profile = std::getenv("RIBBIT_PROFILE") != nullptr;
+    const bool profile = rb::profile_on();
     const double t_scan = now_ms();
     if ((rc = scan_and_pair_streaks(h, which, &n, full ? nullptr : min_span))) return rc;
     const double t0 = now_ms();
@@ -291,13 +291,13 @@ void subst_merge(RibbitHandle *h, const DeviceCalls *dc) {
     h->lists.range_count = [hp](int shift, int start, int end) { return hp->range_count(shift, start, end); };
     h->lists.subst.clear();
     const double t0 = now_ms();
-    const unsigned threads = rb::merge_threads(h->host_threads);
+    const unsigned threads = rb::host_thread_count(h->host_threads);
     rb::MergeStats st;
     if (dc) rb::merge_subst_stage(h->lists, *dc, threads, &st);
     else rb::merge_subst_stage_full(h->lists, h->subst_calls.data(), h->subst_calls.size(), threads, &st);
     h->merge_ms = now_ms() - t0;
     h->rec.stage_done = STAGE_SUBST;
-    static const bool profile = std::getenv("RIBBIT_PROFILE") != nullptr;
+    const bool profile = rb::profile_on();
     if (profile)
         std::fprintf(stderr, "[subst merge] %zu seeds: %u ranges on %u threads%s, preparation %.1f ms, merges %.1f ms\n", h->lists.subst.size(), st.ranges,
                      st.threads, st.redone_in_order ? " (REDONE IN ORDER)" : "", st.prepare_ms, st.merge_ms);
@@ -407,7 +407,7 @@ int advance_to_anchored(RibbitHandle *h) {
     const double merge_s = h->merge_ms;
     const double tx2 = now_ms();
     if ((rc = xa_wait_host(h))) return rc;
-    static const bool profile_xa = std::getenv("RIBBIT_PROFILE") != nullptr;
+    const bool profile_xa = rb::profile_on();
     if (profile_xa)
         std::fprintf(stderr, "[composed planes] %.2f GB to the host for the merges' range reads: page-locked room and enqueue %.1f ms, waited %.1f ms for the copy after the substitution merge\n",
                      (double)(h->params.max_motif - h->params.min_motif + 1) * (double)h->xa_stride * 4e-9, tx1 - tx0, now_ms() - tx2);
@@ -419,7 +419,7 @@ int advance_to_anchored(RibbitHandle *h) {
     if (hp->xa_stored()) { h->lists.plane_words = hp->xa_words(); h->lists.plane_stride = hp->xa_stride; h->lists.plane_lo = hp->xa_m_lo; h->lists.plane_hi = hp->xa_m_hi; }
     // (lists.anchored is not cleared here: every path of the stage sets it, and the join reuses what it holds, parallel_merge.cpp)
     const double t0 = now_ms();
-    const unsigned threads = rb::merge_threads(h->host_threads);
+    const unsigned threads = rb::host_thread_count(h->host_threads);
     rb::MergeStats st;
     if (full) rb::merge_anchored_stage_full(h->lists, h->anchored_calls.data(), h->anchored_calls.size(), threads, &st);
     else {
@@ -431,7 +431,7 @@ int advance_to_anchored(RibbitHandle *h) {
     const double t1 = now_ms();
     const unsigned dispatch_ranges = rb::dispatch_order_ranges(h->lists, st.cut_pos, threads, h->dispatch);
     h->merge_ms = now_ms() - t0;
-    static const bool profile = std::getenv("RIBBIT_PROFILE") != nullptr;
+    const bool profile = rb::profile_on();
     if (profile) print_anchored_merge_profile(h->lists.anchored.size(), st, now_ms() - t1, dispatch_ranges);
     h->subst_merge_ms = subst_todo ? merge_s : 0.0;
     h->rec.stage_done = STAGE_ANCHORED;
@@ -538,7 +538,7 @@ int ribbit_host_replay_calls(const RibbitScanParams *params, int64_t length,
     sl.min_shift = (params->min_motif > 2) ? params->min_motif - 2 : 1;
     sl.range_count = [&hp](int shift, int start, int end) { return hp.range_count(shift, start, end); };
     for (size_t i = 0; i < n_perfect_calls; ++i) rb::perfect_add(sl, perfect_calls[i].start, perfect_calls[i].end, perfect_calls[i].mlen);
-    rb::merge_subst_stage_full(sl, subst_calls, n_subst_calls, rb::merge_threads(0));
+    rb::merge_subst_stage_full(sl, subst_calls, n_subst_calls, rb::host_thread_count(0));
     // the anchored stage runs when there are anchored calls or composed planes are given; anchored_calls non-null with
     // n == 0 also asks for it (a record whose anchored scan made no call still gets its dispatch list)
     const bool anchored_stage = n_anchored_calls || xa || anchored_calls;
@@ -571,10 +571,10 @@ int ribbit_host_replay_calls(const RibbitScanParams *params, int64_t length,
                 return false;
             };
         }
-        rb::merge_anchored_stage_full(sl, anchored_calls, n_anchored_calls, rb::merge_threads(0), &st, fine ? &no_device : nullptr);
+        rb::merge_anchored_stage_full(sl, anchored_calls, n_anchored_calls, rb::host_thread_count(0), &st, fine ? &no_device : nullptr);
         const double td = now_ms();
-        const unsigned dispatch_ranges = rb::dispatch_order_ranges(sl, st.cut_pos, rb::merge_threads(0), dispatch);
-        if (std::getenv("RIBBIT_PROFILE")) print_anchored_merge_profile(sl.anchored.size(), st, now_ms() - td, dispatch_ranges);
+        const unsigned dispatch_ranges = rb::dispatch_order_ranges(sl, st.cut_pos, rb::host_thread_count(0), dispatch);
+        if (rb::profile_on()) print_anchored_merge_profile(sl.anchored.size(), st, now_ms() - td, dispatch_ranges);
     }
     auto give = [](const rb::SeedVec &v, RibbitSeed **p, size_t *n) {
         *n = v.size();

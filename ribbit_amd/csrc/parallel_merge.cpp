@@ -1,6 +1,8 @@
 // parallel_merge.cpp -- see parallel_merge.h.
 #include "parallel_merge.h"
 
+#include "host_threads.h"
+
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -118,14 +120,7 @@ size_t piece_grain() { return std::max<size_t>(1, std::min<size_t>(65536, g_min_
 unsigned pieces_for(size_t n, unsigned threads) { return (unsigned)std::max<size_t>(1, std::min<size_t>(threads, n / piece_grain() + 1)); }
 
 template <class Fn>
-void parallel_pieces(size_t n, unsigned threads, Fn fn) {
-    threads = pieces_for(n, threads);
-    if (threads == 1) { fn((size_t)0, n, 0u); return; }
-    std::vector<std::thread> pool;
-    for (unsigned t = 1; t < threads; ++t) pool.emplace_back(fn, n * t / threads, n * (t + 1) / threads, t);
-    fn((size_t)0, n / threads, 0u);
-    for (std::thread &th : pool) th.join();
-}
+void parallel_pieces(size_t n, unsigned threads, Fn fn) { over_pieces(n, pieces_for(n, threads), fn); }
 
 // Running extrema over the kept calls, built by two-pass scans on the host threads:
 //   end_before[i]  = largest end of the calls before i (-1 if none): what a cut before call i has on its left;
@@ -216,18 +211,16 @@ std::vector<size_t> cut_ranges(const KeptCalls &kc, std::initializer_list<const 
     return first;
 }
 
+// (not host_thread_count: the callers of the merges have applied that rule and pass its answer.  This caps what they pass at 256
+// ranges in flight; a zero would mean every core of the machine, without the cap of 16 and without RIBBIT_THREADS.)
 unsigned resolve_threads(unsigned threads) { return std::max(1u, std::min(threads ? threads : std::thread::hardware_concurrency(), 256u)); }
 
 template <class Work>
 void run_ranges(size_t n_ranges, unsigned threads, Work work) {
     std::atomic<size_t> next{0};
     const bool reverse = std::getenv("RIBBIT_MERGE_REVERSE_RANGES") != nullptr;     // debugging aid
-    auto loop = [&]() { for (size_t k; (k = next.fetch_add(1)) < n_ranges;) work(reverse ? n_ranges - 1 - k : k); };
-    std::vector<std::thread> pool;
     const unsigned nt = std::getenv("RIBBIT_MERGE_SERIAL_RANGES") ? 1u : (unsigned)std::min<size_t>(threads, n_ranges);   // debugging aid: ranges one after the other
-    for (unsigned t = 1; t < nt; ++t) pool.emplace_back(loop);
-    loop();
-    for (std::thread &t : pool) t.join();
+    on_threads(nt, [&](unsigned) { for (size_t k; (k = next.fetch_add(1)) < n_ranges;) work(reverse ? n_ranges - 1 - k : k); });
 }
 
 // the ranges' lists, joined in range order (each without its sentinel).  `out` is NOT cleared first: resize() then only
@@ -286,12 +279,6 @@ void anchored_in_order(SeedLists &lists, const KeptCalls &kc) {
 
 void set_merge_min_range(size_t calls) { g_min_range = std::max<size_t>(calls, 1); }
 MergeStats last_merge_stats(int stage) { return tl_last_stats[stage ? 1 : 0]; }
-
-unsigned merge_threads(unsigned asked) {
-    if (asked) return asked;
-    if (const char *env = std::getenv("RIBBIT_THREADS")) return (unsigned)std::max(1, std::atoi(env));
-    return std::max(1u, std::min(std::thread::hardware_concurrency(), 16u));
-}
 
 namespace {
 // full call list -> the kept calls with cumulative bounds (the largest end of ANY earlier call), the flush apart
@@ -516,7 +503,7 @@ void merge_anchored_stage(SeedLists &lists, const KeptCalls &kc, unsigned thread
         bool other_failed = false;
         {
             std::thread other([&]() { try { ms = running_max(lists.subst); } catch (...) { other_failed = true; } });
-            struct Join { std::thread &t; ~Join() { if (t.joinable()) t.join(); } } join{other};      // (also on the way out of an exception)
+            JoinOnExit join({}, other);      // (also on the way out of an exception)
             mp = running_max(lists.perfect);
         }
         if (other_failed) throw std::bad_alloc();
@@ -608,7 +595,7 @@ void merge_anchored_stage(SeedLists &lists, const KeptCalls &kc, unsigned thread
         try { lists.anchored.clear(); lists.anchored.resize(kc.n + kc.n_flush + 1); }
         catch (...) { lists.anchored.clear(); }      // out of memory here: the join's own resize reports it on the calling thread
     });
-    struct JoinPresize { std::thread &t; ~JoinPresize() { if (t.joinable()) t.join(); } } presize_guard{presize};
+    JoinOnExit presize_guard({}, presize);
     st.before_passes_ms = now_ms() - t1;
     while (done < nr && !fallback) {
         if (++passes > 16) { fallback = true; break; }
@@ -834,7 +821,7 @@ unsigned dispatch_order_ranges(const SeedLists &sl, const std::vector<int> &all_
     std::vector<SeedVec> part(nr);
     std::atomic<bool> out_of_place{false};
     std::atomic<size_t> next{0};
-    auto loop = [&]() {
+    on_threads((unsigned)std::min<size_t>(threads, nr), [&](unsigned) {
         for (size_t k; (k = next.fetch_add(1)) < nr && !out_of_place;) {
             const int64_t lo = k > 0 ? (int64_t)cut_pos[k] : -1, hi = k + 1 < nr ? (int64_t)cut_pos[k + 1] : INT64_MAX;
             for (int x = 0; x < 3 && !out_of_place; ++x) {
@@ -848,30 +835,16 @@ unsigned dispatch_order_ranges(const SeedLists &sl, const std::vector<int> &all_
             dispatch_order_slices(sl.perfect.data() + split[0][k], split[0][k + 1] - split[0][k], sl.subst.data() + split[1][k], split[1][k + 1] - split[1][k],
                                   sl.anchored.data() + split[2][k], split[2][k + 1] - split[2][k], part[k]);
         }
-    };
-    {
-        std::vector<std::thread> pool;
-        const unsigned nt = (unsigned)std::min<size_t>(threads, nr);
-        for (unsigned t = 1; t < nt; ++t) pool.emplace_back(loop);
-        loop();
-        for (std::thread &t : pool) t.join();
-    }
+    });
     if (out_of_place) { dispatch_order(sl, out); return 1; }
     std::vector<size_t> at(nr + 1, 0);
     for (size_t k = 0; k < nr; ++k) at[k + 1] = at[k] + part[k].size();
     out.resize(at[nr]);
     next = 0;
-    auto copy = [&]() {
+    on_threads((unsigned)std::max<size_t>(1, std::min<size_t>(threads, at[nr] / 65536 + 1)), [&](unsigned) {
         for (size_t k; (k = next.fetch_add(1)) < nr;)
             if (!part[k].empty()) std::memcpy(out.data() + at[k], part[k].data(), part[k].size() * sizeof(RibbitSeed));
-    };
-    {
-        std::vector<std::thread> pool;
-        const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(threads, at[nr] / 65536 + 1));
-        for (unsigned t = 1; t < nt; ++t) pool.emplace_back(copy);
-        copy();
-        for (std::thread &t : pool) t.join();
-    }
+    });
     tl_last_dispatch_ranges = (unsigned)nr;
     return (unsigned)nr;
 }

@@ -124,9 +124,6 @@ void replay_subst_calls(SeedLists &lists, const RibbitCall *calls, size_t n);
 void merge_subst_stage_full(SeedLists &lists, const RibbitCall *calls, size_t n, unsigned threads, MergeStats *stats = nullptr);
 void merge_anchored_stage_full(SeedLists &lists, const RibbitCall *calls, size_t n, unsigned threads, MergeStats *stats = nullptr, const AnchoredDevicePass *device = nullptr);
 
-// threads the merges may use: `asked` if non-zero, else environment RIBBIT_THREADS, else min(cores, 16)
-unsigned merge_threads(unsigned asked);
-
 // test hook: smallest number of calls per range (default 4096); small values cut wherever a cut is valid
 void set_merge_min_range(size_t calls);
 // test hook: what the last merge of a stage (0 substitution, 1 anchored) on the calling thread did

@@ -1,5 +1,6 @@
 #include "refine.h"
 
+#include "host_threads.h"
 #include "ssw_exact.h"
 
 #include <algorithm>
@@ -404,13 +405,10 @@ void build_align_jobs(const HostPlanes &hp, const RibbitRefineParams &prm, const
     std::vector<std::vector<RibbitAlignJob>> part_jobs(nchunks);
     std::vector<std::string> part_pool(nchunks);
     std::atomic<size_t> next{0};
-    std::vector<std::thread> pool;
-    for (unsigned t = 0; t < threads; ++t)
-        pool.emplace_back([&]() {
-            for (size_t c; (c = next.fetch_add(1)) < nchunks;)
-                build_align_jobs_range(b, prm, dispatch, longest_runs, best_rows, seed_lo + c * chunk, seed_lo + std::min(n, (c + 1) * chunk), part_jobs[c], part_pool[c], small);
-        });
-    for (std::thread &th : pool) th.join();
+    on_threads(threads, [&](unsigned) {
+        for (size_t c; (c = next.fetch_add(1)) < nchunks;)
+            build_align_jobs_range(b, prm, dispatch, longest_runs, best_rows, seed_lo + c * chunk, seed_lo + std::min(n, (c + 1) * chunk), part_jobs[c], part_pool[c], small);
+    });
     // the chunks' jobs and motif strings into place, on the threads again (one thread did this for a fifth of the set-up's time)
     const auto tj0 = std::chrono::steady_clock::now();
     tl_build_par_ms += std::chrono::duration<double, std::milli>(tj0 - tp0).count();
@@ -419,18 +417,14 @@ void build_align_jobs(const HostPlanes &hp, const RibbitRefineParams &prm, const
     jobs.resize(job_at[nchunks]);
     motif_pool.resize(pool_at[nchunks]);
     next = 0;
-    auto place = [&]() {
+    on_threads(threads, [&](unsigned) {
         for (size_t c; (c = next.fetch_add(1)) < nchunks;) {
             RibbitAlignJob *out = jobs.data() + job_at[c];
             const int32_t base = (int32_t)pool_at[c];
             for (size_t k = 0; k < part_jobs[c].size(); ++k) { out[k] = part_jobs[c][k]; out[k].motif_offset += base; }
             if (!part_pool[c].empty()) std::memcpy(&motif_pool[pool_at[c]], part_pool[c].data(), part_pool[c].size());
         }
-    };
-    pool.clear();
-    for (unsigned t = 1; t < threads; ++t) pool.emplace_back(place);
-    place();
-    for (std::thread &th : pool) th.join();
+    });
     tl_build_join_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tj0).count();
 }
 
@@ -483,7 +477,7 @@ void build_align_jobs_slices(const HostPlanes &hp, const RibbitRefineParams &prm
     for (size_t c = 0; c < sl.size(); ++c)
         if (sl[c].nchunks == 0) finish(c);            // an empty slice is done at once
     std::atomic<size_t> next{0};
-    auto work = [&]() {
+    auto work = [&](unsigned) {
         size_t c = 0;
         for (size_t id; (id = next.fetch_add(1)) < total;) {
             while (c + 1 < sl.size() && id >= sl[c].first_chunk + sl[c].nchunks) ++c;      // ids only grow for one thread
@@ -493,11 +487,7 @@ void build_align_jobs_slices(const HostPlanes &hp, const RibbitRefineParams &prm
             if (s.left.fetch_sub(1) == 1) finish(c);
         }
     };
-    const unsigned threads = (unsigned)std::max<size_t>(1, std::min<size_t>(host_threads ? host_threads : 1, total));
-    std::vector<std::thread> pool;
-    for (unsigned t = 1; t < threads; ++t) pool.emplace_back(work);
-    work();
-    for (std::thread &th : pool) th.join();
+    on_threads((unsigned)std::max<size_t>(1, std::min<size_t>(host_threads ? host_threads : 1, total)), work);
 }
 
 double build_align_jobs_join_ms(bool reset) { const double v = tl_build_join_ms; if (reset) tl_build_join_ms = 0.0; return v; }
@@ -515,15 +505,11 @@ void build_align_jobs_of(const HostPlanes &hp, const RibbitRefineParams &prm, co
     std::vector<std::vector<RibbitAlignJob>> part_jobs(nchunks);
     std::vector<std::string> part_pool(nchunks);
     std::atomic<size_t> next{0};
-    auto work = [&]() {
+    on_threads(threads, [&](unsigned) {
         for (size_t c; (c = next.fetch_add(1)) < nchunks;)
             for (size_t k = c * chunk; k < std::min(n, (c + 1) * chunk); ++k)
                 build_align_jobs_range(b, prm, dispatch, longest_runs, best_rows, which[k], (size_t)which[k] + 1, part_jobs[c], part_pool[c], small);
-    };
-    std::vector<std::thread> pool;
-    for (unsigned t = 1; t < threads; ++t) pool.emplace_back(work);
-    work();
-    for (std::thread &th : pool) th.join();
+    });
     for (size_t c = 0; c < nchunks; ++c) {
         const int32_t base = (int32_t)motif_pool.size();
         for (RibbitAlignJob &j : part_jobs[c]) { j.motif_offset += base; jobs.push_back(j); }
@@ -543,7 +529,6 @@ std::atomic<long> g_n_align{0}, g_n_known{0}, g_n_paths{0}, g_n_small_device{0},
 std::atomic<long> g_n_flank{0};
 std::atomic<long long> g_t_flank{0}, g_t_whole_first{0};      // profile: flank-recursion alignments; whole first-level alignments on the host
 std::atomic<long long> g_t_digest{0}, g_t_units{0}, g_t_row{0}, g_t_query{0}, g_t_atom{0}, g_t_small_all{0}, g_t_long_all{0}, g_t_range{0};
-const bool g_profile = std::getenv("RIBBIT_PROFILE") != nullptr;
 struct LocalCounters {
     long n_align = 0, n_known = 0, n_paths = 0, n_small_device = 0, n_small_host = 0, n_flank = 0;
     long long t_align = 0, t_small = 0, t_long = 0, t_flank = 0, t_whole_first = 0, t_digest = 0, t_units = 0, t_row = 0, t_query = 0, t_atom = 0,
@@ -561,7 +546,7 @@ void flush_counters() {
 struct Stopwatch {
     long long *acc;
     std::chrono::steady_clock::time_point t0;
-    explicit Stopwatch(long long *a) : acc(g_profile ? a : nullptr) { if (acc) t0 = std::chrono::steady_clock::now(); }
+    explicit Stopwatch(long long *a) : acc(profile_on() ? a : nullptr) { if (acc) t0 = std::chrono::steady_clock::now(); }
     ~Stopwatch() { if (acc) *acc += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(); }
 };
 
@@ -926,17 +911,14 @@ void refine_to_bed(const HostPlanes &hp, const char *sequence, const RibbitRefin
     // reference's shared Alignment object untouched and so sees the previous seed's CIGAR.  Chunks of seeds
     // therefore run on host threads with their own writers, concatenated in seed order; if any chunk met an
     // empty query the record is redone sequentially.
-    unsigned threads = host_threads ? host_threads : std::min(std::thread::hardware_concurrency(), 16u);   // one GPU's share of the host by default
-    if (!host_threads)
-        if (const char *env = std::getenv("RIBBIT_THREADS")) threads = (unsigned)std::max(1, std::atoi(env));
-    threads = std::max(1u, std::min(threads, 256u));
+    unsigned threads = std::min(host_thread_count(host_threads), 256u);
     if (only) {
         // the seeds an earlier call left out, each a piece of its own (they are few and individually expensive)
         // (a seed is one piece, or several around the nodes it put off; a thread collects its own and adds them at the end)
         std::atomic<size_t> next{0};
         std::atomic<bool> empty_seen{false};
         std::mutex out_lock;
-        auto work = [&]() {
+        auto work = [&](unsigned) {
             std::vector<BedPiece> mine;
             for (size_t k; (k = next.fetch_add(1)) < n_seeds;) {
                 const size_t i = (*only)[k];
@@ -957,10 +939,7 @@ void refine_to_bed(const HostPlanes &hp, const char *sequence, const RibbitRefin
             flush_counters();
         };
         threads = (unsigned)std::max<size_t>(1, std::min<size_t>(threads, n_seeds));
-        std::vector<std::thread> pool;
-        for (unsigned t = 1; t < threads; ++t) pool.emplace_back(work);
-        work();
-        for (std::thread &th : pool) th.join();
+        on_threads(threads, work);
         if (empty_seen) tl_met_empty_query = true;
         if (empty_seen && order_dependent) *order_dependent = true;
         return;
@@ -976,19 +955,16 @@ void refine_to_bed(const HostPlanes &hp, const char *sequence, const RibbitRefin
         std::vector<std::vector<BedPiece>> part_pieces(pieces ? nchunks : 0);
         std::atomic<size_t> next{0};
         std::atomic<bool> empty_seen{false};
-        std::vector<std::thread> pool;
-        for (unsigned t = 0; t < threads; ++t)
-            pool.emplace_back([&]() {
-                for (size_t c; (c = next.fetch_add(1)) < nchunks;) {
-                    Stopwatch swr(&tl.t_range);
-                    Writer w(b, hp, sequence, prm, sequence_id);
-                    run_range(seed_lo + c * chunk, seed_lo + std::min(n_seeds, (c + 1) * chunk), w, pieces ? &part_pieces[c] : nullptr);
-                    if (w.saw_empty_query) empty_seen = true;
-                    if (!pieces) parts[c] = w.os.str();
-                }
-                flush_counters();
-            });
-        for (std::thread &th : pool) th.join();
+        on_threads(threads, [&](unsigned) {
+            for (size_t c; (c = next.fetch_add(1)) < nchunks;) {
+                Stopwatch swr(&tl.t_range);
+                Writer w(b, hp, sequence, prm, sequence_id);
+                run_range(seed_lo + c * chunk, seed_lo + std::min(n_seeds, (c + 1) * chunk), w, pieces ? &part_pieces[c] : nullptr);
+                if (w.saw_empty_query) empty_seen = true;
+                if (!pieces) parts[c] = w.os.str();
+            }
+            flush_counters();
+        });
         if (empty_seen) tl_met_empty_query = true;
         if (empty_seen && order_dependent) { *order_dependent = true; return; }
         if (empty_seen) sequential = true;
@@ -1008,7 +984,7 @@ void refine_to_bed(const HostPlanes &hp, const char *sequence, const RibbitRefin
     if (wall_lines)
         std::fprintf(stderr, "[refine] call over %zu seeds on %u threads: %.1f ms wall\n", n_seeds, threads,
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count());
-    if (g_profile)
+    if (profile_on())
         std::fprintf(stderr, "[refine] seeds %zu  threads %u  alignments %ld (%ld with GPU passes, %ld with GPU paths)  small-motif seeds %ld from the GPU / %ld on the host  (summed over threads, cumulative) align %.2fs (of it %.2fs in %ld flank-recursion alignments, %.2fs in first-level alignments done whole on the host)  small-motif discovery %.2fs  long-motif consensus %.2fs  CIGAR digestion %.2fs  motif units %.2fs  row text %.2fs  reference strings %.2fs  long atomicity %.2fs | whole small seeds %.2fs  whole long seeds %.2fs  whole chunks %.2fs\n",
                      n_seeds, threads, g_n_align.load(), g_n_known.load(), g_n_paths.load(), g_n_small_device.load(), g_n_small_host.load(), g_t_align.load() * 1e-9, g_t_flank.load() * 1e-9, g_n_flank.load(), g_t_whole_first.load() * 1e-9, g_t_small.load() * 1e-9, g_t_long.load() * 1e-9,
                      g_t_digest.load() * 1e-9, g_t_units.load() * 1e-9, g_t_row.load() * 1e-9, g_t_query.load() * 1e-9, g_t_atom.load() * 1e-9,

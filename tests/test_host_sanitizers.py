@@ -65,6 +65,7 @@ lib = ribbit_amd.load_library()
 # seed 38 at 300 kb: the record whose one list-head write (Q8) changes its entry -- logged by a worker, decided after the pass
 cases = [fuzz_case(s) for s in range(9000, 9010)] + [(simulate_sequence(300_000, 38, 2, 30)[0], 2, 30),
                                                       (simulate_sequence(200_000, 17, 2, 60, n_block_rate=0.3)[0], 2, 60)]
+faults = 0
 for min_range in (1, 16):
     lib.ribbit_debug_set_merge_min_range(min_range)
     for seq, m_lo, m_hi in cases:
@@ -93,6 +94,24 @@ for min_range in (1, 16):
                 os.environ["RIBBIT_HOST_DEFER"] = "1"; os.environ["RIBBIT_DEFER_MIN"] = "30"
                 assert ribbit_amd.host_refine_bed(m_lo, m_hi, seq, xa, stride, o.dispatch(), "fz") == o.refine_bed("fz")
                 del os.environ["RIBBIT_HOST_DEFER"], os.environ["RIBBIT_DEFER_MIN"]
+                # the teams' helper with its faults injected (host_threads.h): a thread that does not start leaves its part to the
+                # caller; a part that throws hands its exception to the caller behind the joins
+                lib.ribbit_host_debug_thread_faults(1, -1)
+                assert ribbit_amd.host_refine_bed(m_lo, m_hi, seq, xa, stride, o.dispatch(), "fz") == o.refine_bed("fz")
+                faults += lib.ribbit_host_debug_thread_faults(-1, 1)
+                for call in (lambda: ribbit_amd.host_replay_calls(m_lo, m_hi, seq, pc, sc, o.calls(LIST_ANCHORED), xa, stride),
+                             lambda: ribbit_amd.host_refine_bed(m_lo, m_hi, seq, xa, stride, o.dispatch(), "fz")):
+                    try:
+                        call()
+                        raised = False
+                    except ribbit_amd.RibbitHipError as e:
+                        assert "out of host memory" in str(e)
+                        raised = True
+                    fired = lib.ribbit_host_debug_thread_faults(-1, 1)          # (of this call; the mode stays)
+                    assert raised == (fired > 0), (raised, fired)             # a team formed and its part threw: the call says so
+                    faults += fired
+                lib.ribbit_host_debug_thread_faults(-1, -1)
+assert faults > 0
 print("host-tsan-run-ok")
 """
 
