@@ -11,6 +11,8 @@
 //   api_mask.cpp        the repeat-masked FASTA body of a record (mask.hip), its host twin, BED rows back to intervals
 //   api_repeats.cpp     every row's bases with their flanks as FASTA entries (repeats.hip), in batches of a text budget; its host twin
 //   api_loci.cpp        merged, sorted loci and the per-window density of a record (loci.hip), their host twins, the loci as text
+// The last three are the row outputs: their buffers are the handle's RowBufs `rows`, and what their host sides share is below
+// (hand_out, clipped_sorted_rows, bed_text_parts).
 // Host threads: every team of them, here and in refine.cpp, parallel_merge.cpp and host_planes.cpp, is started by rb::on_threads /
 // rb::over_pieces of host_threads.h (part 0 on the caller, a thread that cannot start leaves its part to the caller, all joined, the
 // first exception of any part rethrown on the caller: it then meets guarded() below); the thread count rule (the handle's, else
@@ -171,6 +173,36 @@ inline double now_ms() {
 
 enum Stage { STAGE_NONE = 0, STAGE_PERFECT = 1, STAGE_SUBST = 2, STAGE_ANCHORED = 3 };
 
+// ---- shared by the host sides of the row outputs (api_mask.cpp, api_repeats.cpp, api_loci.cpp)
+
+// n elements as malloc memory the caller frees (never a null pointer, whatever n): a copy of src, or for the caller to fill
+// when src is null; terminate: a zero element behind them
+template <typename T>
+int hand_out(const T *src, size_t n, bool terminate, T **out) {
+    T *mem = static_cast<T *>(std::malloc((std::max<size_t>(n, 1) + (terminate ? 1 : 0)) * sizeof(T)));
+    if (!mem) return fail(RIBBIT_E_NOMEM, "out of host memory");
+    if (src && n) std::memcpy(mem, src, n * sizeof(T));
+    if (terminate) mem[n] = T();
+    *out = mem;
+    return RIBBIT_OK;
+}
+
+// the rows clipped to [0, length), the empty ones dropped, sorted by start (among equals by index): what the host twins sweep
+struct ClippedRow { int64_t s, e; size_t index; };
+inline std::vector<ClippedRow> clipped_sorted_rows(int64_t length, const int32_t *intervals, size_t n) {
+    std::vector<ClippedRow> rows;
+    rows.reserve(n);
+    for (size_t i = 0; i < n; ++i) {
+        const int64_t s = std::max<int64_t>(intervals[2 * i], 0), e = std::min<int64_t>(intervals[2 * i + 1], length);
+        if (s < e) rows.push_back(ClippedRow{s, e, i});
+    }
+    std::sort(rows.begin(), rows.end(), [](const ClippedRow &a, const ClippedRow &b) { return a.s != b.s ? a.s < b.s : a.index < b.index; });
+    return rows;
+}
+
+// a chromosome's BED is 150-200 MB of text: it is walked in pieces, one thread per piece of at least 4 MB
+inline size_t bed_text_parts(size_t len) { return std::max<size_t>(1, std::min<size_t>(std::min(rb::host_thread_count(0), 16u), len >> 22)); }
+
 }  // namespace rbapi
 
 using namespace rbapi;
@@ -209,7 +241,7 @@ struct RibbitHandle {
         bool eval_valid = false;              // d_eval / d_first_rev belong to the loaded record
         bool xa_on_device = false;            // the anchored kernel has written the composed planes of the loaded record
         int stage_done = STAGE_NONE;          // how far the seed lists have been advanced
-        bool coverage_valid = false;          // d_mask_bits is the coverage of the coverage_n rows in h_mask_iv / d_mask_iv (build_coverage)
+        bool coverage_valid = false;          // rows.d_mask_bits is the coverage of the coverage_n rows in rows.h_mask_iv / d_mask_iv (build_coverage)
         size_t coverage_n = 0;
         rb::ScanSplit last_split[RIBBIT_SCAN_KERNELS];   // the split each scan kernel last ran with on the loaded record
     } rec;
@@ -326,35 +358,38 @@ struct RibbitHandle {
     bool bed_in_raw = false;              // the last ribbit_hip_refine_bed returned bed_raw, not bed
     rb::SeedLists lists;
     bool refine_met_empty_query = false;  // the last ribbit_hip_refine_bed on this handle met an alignment with an empty query (ribbit_hip_refine_met_empty_query)
-    // the masked body of the loaded record (api_mask.cpp): coverage bitmap, intervals, the text on the device and on its way up
-    DevBuf<uint32_t> d_mask_bits;
-    DevBuf<int32_t> d_mask_iv;
-    DevBuf<uint8_t> d_mask_text;
-    PinnedBuf<int32_t> h_mask_iv;
-    PinnedBuf<char> h_mask_text;
-    // the repeat sequences of the loaded record (api_repeats.cpp): the rows with the name behind them, their entry offsets, the
-    // first row of every output span, the scan's scratch, k and the byte count on their way up, the text of one batch
-    DevBuf<int32_t> d_rep_iv;
-    DevBuf<int64_t> d_rep_off;
-    DevBuf<int32_t> d_rep_span_row;
-    DevBuf<uint8_t> d_rep_scratch;
-    DevBuf<int64_t> d_rep_pick;
-    DevBuf<uint8_t> d_rep_text;
-    PinnedBuf<int32_t> h_rep_iv;
-    PinnedBuf<int64_t> h_rep_pick;
-    PinnedBuf<char> h_rep_text;
-    size_t rep_budget = 0;                // text budget of one batch in bytes (0: REPEAT_TEXT_BUDGET)
-    // the loci and the density track of the loaded record (api_loci.cpp), both from d_mask_bits: the lanes' run ranks, the runs
-    // (starts | ends) with the loci's starts and covered prefixes behind them, the join's prefixes with the rows' keys behind
-    // them, the loci and their number on the device and on their way up; the windows' counts
-    DevBuf<uint64_t> d_loci_off, d_loci_u64;
-    DevBuf<int32_t> d_loci_i32;
-    DevBuf<RibbitLocus> d_loci;
-    DevBuf<uint8_t> d_loci_scratch;
-    PinnedBuf<uint64_t> h_loci_count;
-    PinnedBuf<RibbitLocus> h_loci;
-    DevBuf<int32_t> d_density;
-    PinnedBuf<int32_t> h_density;
+    // the row outputs of the loaded record (api_mask.cpp, api_repeats.cpp, api_loci.cpp)
+    struct RowBufs {
+        // the masked body of the loaded record (api_mask.cpp): coverage bitmap, intervals, the text on the device and on its way up
+        DevBuf<uint32_t> d_mask_bits;
+        DevBuf<int32_t> d_mask_iv;
+        DevBuf<uint8_t> d_mask_text;
+        PinnedBuf<int32_t> h_mask_iv;
+        PinnedBuf<char> h_mask_text;
+        // the repeat sequences of the loaded record (api_repeats.cpp): the rows with the name behind them, their entry offsets, the
+        // first row of every output span, the scan's scratch, k and the byte count on their way up, the text of one batch
+        DevBuf<int32_t> d_rep_iv;
+        DevBuf<int64_t> d_rep_off;
+        DevBuf<int32_t> d_rep_span_row;
+        DevBuf<uint8_t> d_rep_scratch;
+        DevBuf<int64_t> d_rep_pick;
+        DevBuf<uint8_t> d_rep_text;
+        PinnedBuf<int32_t> h_rep_iv;
+        PinnedBuf<int64_t> h_rep_pick;
+        PinnedBuf<char> h_rep_text;
+        // the loci and the density track of the loaded record (api_loci.cpp), both from d_mask_bits: the lanes' run ranks, the runs
+        // (starts | ends) with the loci's starts and covered prefixes behind them, the join's prefixes with the rows' keys behind
+        // them, the loci and their number on the device and on their way up; the windows' counts
+        DevBuf<uint64_t> d_loci_off, d_loci_u64;
+        DevBuf<int32_t> d_loci_i32;
+        DevBuf<RibbitLocus> d_loci;
+        DevBuf<uint8_t> d_loci_scratch;
+        PinnedBuf<uint64_t> h_loci_count;
+        PinnedBuf<RibbitLocus> h_loci;
+        DevBuf<int32_t> d_density;
+        PinnedBuf<int32_t> h_density;
+        size_t rep_budget = 0;            // text budget of one batch of repeat sequences in bytes (0: REPEAT_TEXT_BUDGET)
+    } rows;
     RibbitHandle *aux = nullptr;          // helper handle of ribbit_hip_refine_bed: streams and buffers of the long alignment batch
     std::vector<RibbitHandle *> feed_aux; // ... and of its further feeders (each takes every n-th slice of the short alignments)
 
@@ -429,8 +464,8 @@ int ssw_class(const RibbitAlignJob &jb);
 int run_ssw_passes(RibbitHandle *h, const RibbitAlignJob *jobs, size_t n, const char *pool, size_t pool_len, int mask_len,
                           std::vector<rb::SswEnds> &ends, unsigned classes = 0x1fu, bool pool_resident = false);
 int run_ssw_paths(RibbitHandle *h, const RibbitAlignJob *jobs, size_t n, const std::vector<rb::SswEnds> &ends, std::vector<rb::SswPath> &paths);
-// api_mask.cpp: the coverage bitmap of the loaded record (length > 0) under n rows in d_mask_bits, rb::coverage_words(length) words,
-// and the rows in d_mask_iv, enqueued on the handle's stream; nothing is enqueued when the bitmap already is the one of these rows
+// api_mask.cpp: the coverage bitmap of the loaded record (length > 0) under n rows in rows.d_mask_bits, rb::coverage_words(length)
+// words, and the rows in rows.d_mask_iv, enqueued on the handle's stream; nothing is enqueued when the bitmap already is the one of these rows
 int build_coverage(RibbitHandle *h, const int32_t *intervals, size_t n);
 
 }  // namespace rbapi

@@ -38,38 +38,38 @@ int record_loci_impl(RibbitHandle *h, const int32_t *intervals, size_t n, int32_
     if ((rc = bind_device(h))) return rc;
     if ((rc = build_coverage(h, intervals, n))) return rc;
     const int64_t lanes = rb::loci_lanes(length);
-    if ((rc = h->d_loci_off.ensure((size_t)lanes + 1))) return rc;
-    if ((rc = h->d_loci_scratch.ensure(rb::loci_scan_scratch_bytes(lanes), true))) return rc;
-    if ((rc = h->h_loci_count.ensure(2))) return rc;
-    HIP_TRY(rb::launch_run_ranks(h->d_mask_bits.p, length, h->d_loci_off.p, h->d_loci_scratch.p, h->d_loci_scratch.cap, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->h_loci_count.p, h->d_loci_off.p + lanes, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    if ((rc = h->rows.d_loci_off.ensure((size_t)lanes + 1))) return rc;
+    if ((rc = h->rows.d_loci_scratch.ensure(rb::loci_scan_scratch_bytes(lanes), true))) return rc;
+    if ((rc = h->rows.h_loci_count.ensure(2))) return rc;
+    HIP_TRY(rb::launch_run_ranks(h->rows.d_mask_bits.p, length, h->rows.d_loci_off.p, h->rows.d_loci_scratch.p, h->rows.d_loci_scratch.cap, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->rows.h_loci_count.p, h->rows.d_loci_off.p + lanes, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    const uint64_t ranks = h->h_loci_count.p[0];
+    const uint64_t ranks = h->rows.h_loci_count.p[0];
     const size_t runs = (size_t)(ranks >> 32);
     if (runs != (size_t)(uint32_t)ranks || runs > n) return fail(RIBBIT_E_INTERNAL, "%zu run starts, %zu run ends, %zu rows", runs, (size_t)(uint32_t)ranks, n);
     if (runs == 0) return RIBBIT_OK;      // every row is empty
     // d_loci_i32: run starts | run ends | locus starts | covered prefixes; d_loci_u64: the join's prefixes | the rows' keys | the count
-    if ((rc = h->d_loci_i32.ensure(4 * runs, true))) return rc;
-    if ((rc = h->d_loci_u64.ensure(2 * runs + 1, true))) return rc;
-    if ((rc = h->d_loci.ensure(runs, true))) return rc;
-    if ((rc = h->d_loci_scratch.ensure(rb::loci_scan_scratch_bytes((int64_t)runs), true))) return rc;
-    int32_t *run_start = h->d_loci_i32.p, *run_end = run_start + runs, *locus_start = run_end + runs, *post = locus_start + runs;
-    uint64_t *join = h->d_loci_u64.p, *key = join + runs, *count = key + runs;
-    rb::launch_run_bounds(h->d_mask_bits.p, length, h->d_loci_off.p, run_start, run_end, h->stream);
+    if ((rc = h->rows.d_loci_i32.ensure(4 * runs, true))) return rc;
+    if ((rc = h->rows.d_loci_u64.ensure(2 * runs + 1, true))) return rc;
+    if ((rc = h->rows.d_loci.ensure(runs, true))) return rc;
+    if ((rc = h->rows.d_loci_scratch.ensure(rb::loci_scan_scratch_bytes((int64_t)runs), true))) return rc;
+    int32_t *run_start = h->rows.d_loci_i32.p, *run_end = run_start + runs, *locus_start = run_end + runs, *post = locus_start + runs;
+    uint64_t *join = h->rows.d_loci_u64.p, *key = join + runs, *count = key + runs;
+    rb::launch_run_bounds(h->rows.d_mask_bits.p, length, h->rows.d_loci_off.p, run_start, run_end, h->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemsetAsync(key, 0, (runs + 1) * sizeof(uint64_t), h->stream));
-    HIP_TRY(hipMemsetAsync(h->d_loci.p, 0, runs * sizeof(RibbitLocus), h->stream));
-    HIP_TRY(rb::launch_loci(run_start, run_end, (int64_t)runs, gap, h->d_mask_iv.p, (int64_t)n, length, join, locus_start, post,
-                            reinterpret_cast<unsigned long long *>(key), h->d_loci.p, reinterpret_cast<uint32_t *>(count), h->d_loci_scratch.p,
-                            h->d_loci_scratch.cap, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->h_loci_count.p + 1, count, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemsetAsync(h->rows.d_loci.p, 0, runs * sizeof(RibbitLocus), h->stream));
+    HIP_TRY(rb::launch_loci(run_start, run_end, (int64_t)runs, gap, h->rows.d_mask_iv.p, (int64_t)n, length, join, locus_start, post,
+                            reinterpret_cast<unsigned long long *>(key), h->rows.d_loci.p, reinterpret_cast<uint32_t *>(count), h->rows.d_loci_scratch.p,
+                            h->rows.d_loci_scratch.cap, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->rows.h_loci_count.p + 1, count, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    const size_t found = (size_t)(uint32_t)h->h_loci_count.p[1];
+    const size_t found = (size_t)(uint32_t)h->rows.h_loci_count.p[1];
     if (found < 1 || found > runs) return fail(RIBBIT_E_INTERNAL, "%zu loci of %zu runs", found, runs);
-    if ((rc = h->h_loci.ensure(found, true))) return rc;
-    HIP_TRY(hipMemcpyAsync(h->h_loci.p, h->d_loci.p, found * sizeof(RibbitLocus), hipMemcpyDeviceToHost, h->stream));
+    if ((rc = h->rows.h_loci.ensure(found, true))) return rc;
+    HIP_TRY(hipMemcpyAsync(h->rows.h_loci.p, h->rows.d_loci.p, found * sizeof(RibbitLocus), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    *loci = h->h_loci.p;
+    *loci = h->rows.h_loci.p;
     *n_loci = found;
     return RIBBIT_OK;
 }
@@ -88,41 +88,28 @@ int record_density_impl(RibbitHandle *h, const int32_t *intervals, size_t n, int
     if (length == 0) return RIBBIT_OK;
     if ((rc = bind_device(h))) return rc;
     const size_t windows = (size_t)window_count(length, window);
-    if ((rc = h->d_density.ensure(windows, true))) return rc;
-    if ((rc = h->h_density.ensure(windows, true))) return rc;
+    if ((rc = h->rows.d_density.ensure(windows, true))) return rc;
+    if ((rc = h->rows.h_density.ensure(windows, true))) return rc;
     if ((rc = build_coverage(h, intervals, n))) return rc;
-    rb::launch_density(h->d_mask_bits.p, length, window, (int64_t)windows, h->d_density.p, h->stream);
+    rb::launch_density(h->rows.d_mask_bits.p, length, window, (int64_t)windows, h->rows.d_density.p, h->stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h->h_density.p, h->d_density.p, windows * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->rows.h_density.p, h->rows.d_density.p, windows * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    *covered = h->h_density.p;
+    *covered = h->rows.h_density.p;
     *n_windows = windows;
     return RIBBIT_OK;
 }
 
-// ---- host twins: the clipped, non-empty rows sorted by start, then one sweep
-struct Row { int64_t s, e; size_t index; };
-
-std::vector<Row> sorted_rows(int64_t length, const int32_t *intervals, size_t n) {
-    std::vector<Row> rows;
-    rows.reserve(n);
-    for (size_t i = 0; i < n; ++i) {
-        const int64_t s = std::max<int64_t>(intervals[2 * i], 0), e = std::min<int64_t>(intervals[2 * i + 1], length);
-        if (s < e) rows.push_back(Row{s, e, i});
-    }
-    std::sort(rows.begin(), rows.end(), [](const Row &a, const Row &b) { return a.s != b.s ? a.s < b.s : a.index < b.index; });
-    return rows;
-}
-
+// ---- host twins: the clipped, non-empty rows sorted by start (clipped_sorted_rows), then one sweep
 int host_record_loci_impl(int64_t length, const int32_t *intervals, size_t n, int32_t gap, RibbitLocus **loci, size_t *n_loci) {
     if (!loci || !n_loci) return fail(RIBBIT_E_ARG, "null argument");
     if (gap < 0) return fail(RIBBIT_E_ARG, "gap %d is negative", (int)gap);
     int rc;
     if ((rc = check_rows(intervals, n)) || (rc = check_length(length))) return rc;
-    const std::vector<Row> rows = sorted_rows(length, intervals, n);
+    const std::vector<ClippedRow> rows = clipped_sorted_rows(length, intervals, n);
     std::vector<RibbitLocus> out;
     int64_t run_from = 0, run_to = -1, best = 0;      // the open run, and the length of the open locus's best row
-    for (const Row &r : rows) {
+    for (const ClippedRow &r : rows) {
         if (out.empty() || r.s > run_to) {            // a new run (a row that abuts the open run continues it)
             if (!out.empty()) out.back().covered += (int32_t)(run_to - run_from);
             if (out.empty() || r.s - run_to > gap) {
@@ -143,10 +130,7 @@ int host_record_loci_impl(int64_t length, const int32_t *intervals, size_t n, in
         }
     }
     if (!out.empty()) out.back().covered += (int32_t)(run_to - run_from);
-    RibbitLocus *mem = static_cast<RibbitLocus *>(std::malloc(std::max<size_t>(out.size(), 1) * sizeof(RibbitLocus)));
-    if (!mem) return fail(RIBBIT_E_NOMEM, "out of host memory");
-    if (!out.empty()) std::memcpy(mem, out.data(), out.size() * sizeof(RibbitLocus));
-    *loci = mem;
+    if ((rc = hand_out(out.data(), out.size(), false, loci))) return rc;
     *n_loci = out.size();
     return RIBBIT_OK;
 }
@@ -156,13 +140,13 @@ int host_record_density_impl(int64_t length, const int32_t *intervals, size_t n,
     if (window < 1) return fail(RIBBIT_E_ARG, "window %d is below 1", (int)window);
     int rc;
     if ((rc = check_rows(intervals, n)) || (rc = check_length(length))) return rc;
-    const std::vector<Row> rows = sorted_rows(length, intervals, n);
+    const std::vector<ClippedRow> rows = clipped_sorted_rows(length, intervals, n);
     const int64_t windows = window_count(length, window);
     int32_t *mem = static_cast<int32_t *>(std::calloc((size_t)std::max<int64_t>(windows, 1), sizeof(int32_t)));
     if (!mem) return fail(RIBBIT_E_NOMEM, "out of host memory for %lld windows", (long long)windows);
     // every stretch [from, to) that the sweep newly covers goes to the windows it meets
     int64_t covered_to = 0;
-    for (const Row &r : rows) {
+    for (const ClippedRow &r : rows) {
         int64_t from = std::max(r.s, covered_to);
         const int64_t to = r.e;
         while (from < to) {
@@ -180,9 +164,8 @@ int host_record_density_impl(int64_t length, const int32_t *intervals, size_t n,
 // ---- the loci as text
 int bed_loci_text_impl(const char *name, const char *bed, size_t bed_len, const RibbitLocus *loci, size_t n_loci, char **text, size_t *len) {
     if (!name || !text || !len || (!bed && bed_len > 0) || (!loci && n_loci > 0)) return fail(RIBBIT_E_ARG, "null argument");
-    // a chromosome's BED is 150-200 MB of text: its line starts are found in pieces, one thread per piece of at least 4 MB, and
-    // the loci's lines are written in as many pieces
-    const size_t parts = n_loci ? std::max<size_t>(1, std::min<size_t>(std::min(rb::host_thread_count(0), 16u), bed_len >> 22)) : 1;
+    // the BED text's line starts are found in pieces, and the loci's lines are written in as many pieces
+    const size_t parts = n_loci ? bed_text_parts(bed_len) : 1;
     std::vector<std::vector<size_t>> starts(parts);      // per piece: the offsets just behind its newlines
     std::vector<char> oom(parts, 0);
     if (n_loci)
@@ -231,15 +214,13 @@ int bed_loci_text_impl(const char *name, const char *bed, size_t bed_len, const 
         if (bad[k] != (size_t)-1) return fail(RIBBIT_E_ARG, "locus %zu: its best row %d is not a row of 11 tab-separated columns of the BED text (%zu lines)", bad[k], (int)loci[bad[k]].best_row, n_lines);
         total += piece[k].size();
     }
-    char *mem = static_cast<char *>(std::malloc(total + 1));
-    if (!mem) return fail(RIBBIT_E_NOMEM, "out of host memory");
+    int rc;
+    if ((rc = hand_out<char>(nullptr, total, true, text))) return rc;
     size_t at = 0;
     for (const std::string &s : piece) {
-        std::memcpy(mem + at, s.data(), s.size());
+        std::memcpy(*text + at, s.data(), s.size());
         at += s.size();
     }
-    mem[total] = 0;
-    *text = mem;
     *len = total;
     return RIBBIT_OK;
 }

@@ -51,37 +51,37 @@ int mask_record_impl(RibbitHandle *h, const int32_t *intervals, size_t n, int32_
     const int64_t width = effective_width(length, line_width);
     const int64_t out_len = body_length(length, width);
     const int64_t nwords = length / 32 + 1;
-    if ((rc = h->d_mask_text.ensure((size_t)((out_len + 15) & ~(int64_t)15), true))) return rc;
-    if ((rc = h->h_mask_text.ensure((size_t)out_len, true))) return rc;
+    if ((rc = h->rows.d_mask_text.ensure((size_t)((out_len + 15) & ~(int64_t)15), true))) return rc;
+    if ((rc = h->rows.h_mask_text.ensure((size_t)out_len, true))) return rc;
     if ((rc = build_coverage(h, intervals, n))) return rc;
-    rb::launch_mask_format(h->dev_ascii_src, length, h->d_mask_bits.p, nwords, mode == RIBBIT_MASK_HARD, width, out_len, h->d_mask_text.p, h->stream);
+    rb::launch_mask_format(h->dev_ascii_src, length, h->rows.d_mask_bits.p, nwords, mode == RIBBIT_MASK_HARD, width, out_len, h->rows.d_mask_text.p, h->stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h->h_mask_text.p, h->d_mask_text.p, (size_t)out_len, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->rows.h_mask_text.p, h->rows.d_mask_text.p, (size_t)out_len, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    *text = h->h_mask_text.p;
+    *text = h->rows.h_mask_text.p;
     *len = (size_t)out_len;
     return RIBBIT_OK;
 }
 
 }  // namespace
 
-// The staged copy of the last rows stays in h_mask_iv: a call with the same rows (the command-line tool hands one record's rows to
+// The staged copy of the last rows stays in rows.h_mask_iv: a call with the same rows (the command-line tool hands one record's rows to
 // the mask, the loci and the density) finds the bitmap as it needs it, at the price of one comparison.
 int rbapi::build_coverage(RibbitHandle *h, const int32_t *intervals, size_t n) {
-    if (h->rec.coverage_valid && h->rec.coverage_n == n && (n == 0 || std::memcmp(h->h_mask_iv.p, intervals, 2 * n * sizeof(int32_t)) == 0))
+    if (h->rec.coverage_valid && h->rec.coverage_n == n && (n == 0 || std::memcmp(h->rows.h_mask_iv.p, intervals, 2 * n * sizeof(int32_t)) == 0))
         return RIBBIT_OK;
     h->rec.coverage_valid = false;
     int rc;
     const size_t words = (size_t)rb::coverage_words(h->length);
-    if ((rc = h->d_mask_bits.ensure(words))) return rc;
-    HIP_TRY(hipMemsetAsync(h->d_mask_bits.p, 0, words * sizeof(uint32_t), h->stream));
+    if ((rc = h->rows.d_mask_bits.ensure(words))) return rc;
+    HIP_TRY(hipMemsetAsync(h->rows.d_mask_bits.p, 0, words * sizeof(uint32_t), h->stream));
     if (n) {
-        if ((rc = h->h_mask_iv.ensure(2 * n, true))) return rc;
-        if ((rc = h->d_mask_iv.ensure(2 * n, true))) return rc;
+        if ((rc = h->rows.h_mask_iv.ensure(2 * n, true))) return rc;
+        if ((rc = h->rows.d_mask_iv.ensure(2 * n, true))) return rc;
         // (the staging buffer may still be the source of the last call's copy: that call ended in a synchronise)
-        std::memcpy(h->h_mask_iv.p, intervals, 2 * n * sizeof(int32_t));
-        HIP_TRY(hipMemcpyAsync(h->d_mask_iv.p, h->h_mask_iv.p, 2 * n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-        rb::launch_mask_coverage(h->d_mask_iv.p, (int64_t)n, h->length, h->d_mask_bits.p, h->stream);
+        std::memcpy(h->rows.h_mask_iv.p, intervals, 2 * n * sizeof(int32_t));
+        HIP_TRY(hipMemcpyAsync(h->rows.d_mask_iv.p, h->rows.h_mask_iv.p, 2 * n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+        rb::launch_mask_coverage(h->rows.d_mask_iv.p, (int64_t)n, h->length, h->rows.d_mask_bits.p, h->stream);
         HIP_TRY(hipGetLastError());
     }
     h->rec.coverage_valid = true;
@@ -99,19 +99,14 @@ int host_mask_record_impl(const char *sequence, int64_t length, const int32_t *i
     const int64_t width = std::max<int64_t>(1, effective_width(length, line_width));
     const int64_t out_len = body_length(length, width);
     // the clipped intervals sorted by start: the mask is walked as their union without a per-base array
-    std::vector<std::pair<int64_t, int64_t>> iv;
-    iv.reserve(n);
-    for (size_t i = 0; i < n; ++i) {
-        const int64_t s = std::max<int64_t>(intervals[2 * i], 0), e = std::min<int64_t>(intervals[2 * i + 1], length);
-        if (s < e) iv.emplace_back(s, e);
-    }
-    std::sort(iv.begin(), iv.end());
+    const std::vector<ClippedRow> iv = clipped_sorted_rows(length, intervals, n);
+    // (written where it is handed out: no second copy of a whole chromosome)
     char *out = static_cast<char *>(std::malloc((size_t)out_len + 1));
     if (!out) return fail(RIBBIT_E_NOMEM, "out of host memory");
     int64_t o = 0, masked_to = 0;      // [.., masked_to): the union of the intervals that start at or before i
     size_t next = 0;
     for (int64_t i = 0; i < length; ++i) {
-        for (; next < iv.size() && iv[next].first <= i; ++next) masked_to = std::max(masked_to, iv[next].second);
+        for (; next < iv.size() && iv[next].s <= i; ++next) masked_to = std::max(masked_to, iv[next].e);
         const unsigned char c = (unsigned char)sequence[i];
         out[o++] = i >= masked_to ? (char)c : mode == RIBBIT_MASK_HARD ? 'N' : (c >= 'A' && c <= 'Z') ? (char)(c | 0x20) : (char)c;
         if ((i + 1) % width == 0 || i + 1 == length) out[o++] = '\n';
@@ -142,8 +137,7 @@ const char *parse_rows(const char *p, const char *end, std::vector<int32_t> &out
 
 int bed_intervals_impl(const char *text, size_t len, int32_t **pairs, size_t *n) {
     if (!pairs || !n || (!text && len > 0)) return fail(RIBBIT_E_ARG, "null argument");
-    // a chromosome's BED is 150-200 MB of text: parsed in pieces of whole lines, one thread per piece of at least 4 MB
-    const size_t parts = std::max<size_t>(1, std::min<size_t>(std::min(rb::host_thread_count(0), 16u), len >> 22));
+    const size_t parts = bed_text_parts(len);      // (pieces of whole lines)
     std::vector<const char *> cut(parts + 1, text + len);
     cut[0] = text;
     for (size_t k = 1; k < parts; ++k) {
@@ -163,14 +157,13 @@ int bed_intervals_impl(const char *text, size_t len, int32_t **pairs, size_t *n)
         if (bad[k]) return fail(RIBBIT_E_ARG, "BED text at byte %zu is not a row of 11 tab-separated columns with integer start and end", (size_t)(bad[k] - text));
         total += rows[k].size();
     }
-    int32_t *mem = static_cast<int32_t *>(std::malloc(std::max<size_t>(total, 1) * sizeof(int32_t)));
-    if (!mem) return fail(RIBBIT_E_NOMEM, "out of host memory");
+    int rc;
+    if ((rc = hand_out<int32_t>(nullptr, total, false, pairs))) return rc;
     size_t at = 0;
     for (const std::vector<int32_t> &r : rows) {
-        if (!r.empty()) std::memcpy(mem + at, r.data(), r.size() * sizeof(int32_t));
+        if (!r.empty()) std::memcpy(*pairs + at, r.data(), r.size() * sizeof(int32_t));
         at += r.size();
     }
-    *pairs = mem;
     *n = total / 2;
     return RIBBIT_OK;
 }

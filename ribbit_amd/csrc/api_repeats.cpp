@@ -30,42 +30,42 @@ int repeat_sequences_impl(RibbitHandle *h, const char *name, const int32_t *inte
     if ((rc = bind_device(h))) return rc;
     const int64_t length = h->length;
     const size_t name_len = std::strlen(name);
-    const size_t budget = std::min(h->rep_budget ? h->rep_budget : REPEAT_TEXT_BUDGET, (size_t)1 << 50);
+    const size_t budget = std::min(h->rows.rep_budget ? h->rows.rep_budget : REPEAT_TEXT_BUDGET, (size_t)1 << 50);
     // Every entry is at least 17 + name_len + min(F, L) bytes (its body holds a flank or reaches both ends of the record), so
     // no more rows than m can fit the budget: only those go up and through the scan, however many rows are left.
     const size_t min_entry = 17 + name_len + (size_t)std::min<int64_t>(flank, length);
     const size_t m = std::min(n, budget / min_entry + 1);
     const size_t name_words = (name_len + 4) / 4;        // the name follows the rows in the same buffer
-    if ((rc = h->h_rep_iv.ensure(2 * m + name_words, true))) return rc;
-    if ((rc = h->d_rep_iv.ensure(2 * m + name_words, true))) return rc;
-    if ((rc = h->d_rep_off.ensure(m + 1, true))) return rc;
+    if ((rc = h->rows.h_rep_iv.ensure(2 * m + name_words, true))) return rc;
+    if ((rc = h->rows.d_rep_iv.ensure(2 * m + name_words, true))) return rc;
+    if ((rc = h->rows.d_rep_off.ensure(m + 1, true))) return rc;
     const size_t scratch = rb::repeat_scan_scratch_bytes((int64_t)m);
-    if ((rc = h->d_rep_scratch.ensure(scratch, true))) return rc;
-    if ((rc = h->d_rep_pick.ensure(2))) return rc;
-    if ((rc = h->h_rep_pick.ensure(2))) return rc;
+    if ((rc = h->rows.d_rep_scratch.ensure(scratch, true))) return rc;
+    if ((rc = h->rows.d_rep_pick.ensure(2))) return rc;
+    if ((rc = h->rows.h_rep_pick.ensure(2))) return rc;
     // (the staging buffers may still be the source or target of the last call's copies: that call ended in a synchronise)
-    std::memcpy(h->h_rep_iv.p, intervals, 2 * m * sizeof(int32_t));
-    std::memcpy(h->h_rep_iv.p + 2 * m, name, name_len + 1);
-    HIP_TRY(hipMemcpyAsync(h->d_rep_iv.p, h->h_rep_iv.p, (2 * m + name_words) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(rb::launch_repeat_offsets(h->d_rep_iv.p, (int64_t)m, length, flank, (int32_t)name_len, (int64_t)budget, h->d_rep_off.p,
-                                      h->d_rep_pick.p, h->d_rep_scratch.p, h->d_rep_scratch.cap, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->h_rep_pick.p, h->d_rep_pick.p, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    std::memcpy(h->rows.h_rep_iv.p, intervals, 2 * m * sizeof(int32_t));
+    std::memcpy(h->rows.h_rep_iv.p + 2 * m, name, name_len + 1);
+    HIP_TRY(hipMemcpyAsync(h->rows.d_rep_iv.p, h->rows.h_rep_iv.p, (2 * m + name_words) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(rb::launch_repeat_offsets(h->rows.d_rep_iv.p, (int64_t)m, length, flank, (int32_t)name_len, (int64_t)budget, h->rows.d_rep_off.p,
+                                      h->rows.d_rep_pick.p, h->rows.d_rep_scratch.p, h->rows.d_rep_scratch.cap, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->rows.h_rep_pick.p, h->rows.d_rep_pick.p, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    const int64_t k = h->h_rep_pick.p[0], total = h->h_rep_pick.p[1];
+    const int64_t k = h->rows.h_rep_pick.p[0], total = h->rows.h_rep_pick.p[1];
     if (k < 1 || (size_t)k > m || total <= 0) return fail(RIBBIT_E_INTERNAL, "repeat batch of %lld rows, %lld bytes", (long long)k, (long long)total);
     // the text buffers: at least twice the last size when they grow, never more than the budget unless one entry is larger
     const size_t padded = (size_t)((total + 15) & ~(int64_t)15);
     const size_t want = std::max(padded, std::min(2 * padded, (budget + 15) & ~(size_t)15));
-    if (padded > h->d_rep_text.cap && (rc = h->d_rep_text.ensure(want))) return rc;
-    if ((size_t)total > h->h_rep_text.cap && (rc = h->h_rep_text.ensure(want))) return rc;
-    if ((rc = h->d_rep_span_row.ensure((size_t)((total + rb::REPEAT_SPAN - 1) / rb::REPEAT_SPAN) + 1, true))) return rc;
-    rb::launch_repeat_format(h->dev_ascii_src, length, h->d_rep_iv.p, h->d_rep_off.p, k, total, flank,
-                             reinterpret_cast<const char *>(h->d_rep_iv.p + 2 * m), (int32_t)name_len, h->d_rep_span_row.p, h->d_rep_text.p,
+    if (padded > h->rows.d_rep_text.cap && (rc = h->rows.d_rep_text.ensure(want))) return rc;
+    if ((size_t)total > h->rows.h_rep_text.cap && (rc = h->rows.h_rep_text.ensure(want))) return rc;
+    if ((rc = h->rows.d_rep_span_row.ensure((size_t)((total + rb::REPEAT_SPAN - 1) / rb::REPEAT_SPAN) + 1, true))) return rc;
+    rb::launch_repeat_format(h->dev_ascii_src, length, h->rows.d_rep_iv.p, h->rows.d_rep_off.p, k, total, flank,
+                             reinterpret_cast<const char *>(h->rows.d_rep_iv.p + 2 * m), (int32_t)name_len, h->rows.d_rep_span_row.p, h->rows.d_rep_text.p,
                              h->stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h->h_rep_text.p, h->d_rep_text.p, (size_t)total, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->rows.h_rep_text.p, h->rows.d_rep_text.p, (size_t)total, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    *text = h->h_rep_text.p;
+    *text = h->rows.h_rep_text.p;
     *len = (size_t)total;
     *rows_done = (size_t)k;
     return RIBBIT_OK;
@@ -98,11 +98,7 @@ int host_repeat_sequences_impl(const char *name, const char *sequence, int64_t l
         out.append(sequence + lo, (size_t)(hi - lo));
         out += '\n';
     }
-    char *mem = static_cast<char *>(std::malloc(out.size() + 1));
-    if (!mem) return fail(RIBBIT_E_NOMEM, "out of host memory");
-    std::memcpy(mem, out.data(), out.size());
-    mem[out.size()] = 0;
-    *text = mem;
+    if ((rc = hand_out(out.data(), out.size(), true, text))) return rc;
     *len = out.size();
     return RIBBIT_OK;
 }
@@ -123,7 +119,7 @@ int ribbit_host_repeat_sequences(const char *name, const char *sequence, int64_t
 
 int ribbit_hip_debug_set_repeat_text_budget(RibbitHandle *h, size_t bytes) {
     if (!h) return fail(RIBBIT_E_ARG, "null handle");
-    h->rep_budget = bytes;
+    h->rows.rep_budget = bytes;
     return RIBBIT_OK;
 }
 

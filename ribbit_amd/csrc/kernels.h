@@ -3,6 +3,8 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "device_planes.h"
 #include "ribbit_hip.h"
 
@@ -247,6 +249,11 @@ struct AnchoredMergeArgs {
 };
 void launch_anchored_merge(const AnchoredMergeArgs &a, uint32_t n_calls, uint32_t resident_waves /* <= AM_RESIDENT_WAVES */, hipStream_t stream);
 void launch_seed_types(const RibbitSeed *seeds, uint32_t n, int32_t *types, hipStream_t stream);      // types[i] = seeds[i].type
+
+// blocks for `items` items, `per_block` of them to a block: at least one, at most `cap` (a striding kernel takes the rest)
+inline unsigned grid_for(int64_t items, int per_block, int64_t cap) {
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block, cap));
+}
 
 // mask.hip: the repeat mask of the loaded record (api_mask.cpp).  bits: length / 32 + 1 words, zeroed by the caller;
 // intervals: n (start, end) pairs, clipped to [0, length) on the device.  format: width in 1 .. length (the caller maps

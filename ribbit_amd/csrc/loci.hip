@@ -26,6 +26,7 @@ namespace rb {
 namespace {
 
 constexpr int LOCI_THREADS = 256;
+constexpr int64_t LOCI_MAX_BLOCKS = 256 * 32;      // blocks of a launch at most; the kernels stride
 // windows of at least this many bases are summed by a whole wavefront (64 words: one word per lane and pass)
 constexpr int64_t DENSITY_WAVE_FROM = 64 * 32;
 
@@ -167,10 +168,6 @@ __global__ void __launch_bounds__(LOCI_THREADS) density_wave_kernel(const uint32
     }
 }
 
-unsigned grid_for(int64_t items) {
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + LOCI_THREADS - 1) / LOCI_THREADS, 256 * 32));
-}
-
 auto run_counts(const uint32_t *bits) {
     return rocprim::make_transform_iterator(rocprim::make_counting_iterator<int64_t>(0), RunCounts{bits});
 }
@@ -201,7 +198,7 @@ hipError_t launch_run_ranks(const uint32_t *bits, int64_t length, uint64_t *off,
 
 void launch_run_bounds(const uint32_t *bits, int64_t length, const uint64_t *off, int32_t *run_start, int32_t *run_end, hipStream_t stream) {
     const int64_t lanes = loci_lanes(length);
-    hipLaunchKernelGGL(run_bounds_kernel, dim3(grid_for(lanes)), dim3(LOCI_THREADS), 0, stream, bits, lanes, off, run_start, run_end);
+    hipLaunchKernelGGL(run_bounds_kernel, dim3(grid_for(lanes, LOCI_THREADS, LOCI_MAX_BLOCKS)), dim3(LOCI_THREADS), 0, stream, bits, lanes, off, run_start, run_end);
 }
 
 hipError_t launch_loci(const int32_t *run_start, const int32_t *run_end, int64_t n_runs, int32_t gap, const int32_t *intervals, int64_t n,
@@ -210,19 +207,19 @@ hipError_t launch_loci(const int32_t *run_start, const int32_t *run_end, int64_t
     if (n_runs <= 0) return hipSuccess;
     hipError_t e = scan_packed(scratch, scratch_bytes, join_in(run_start, run_end, gap), join, n_runs, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(locus_bounds_kernel, dim3(grid_for(n_runs)), dim3(LOCI_THREADS), 0, stream, run_start, run_end, n_runs, join, locus_start,
+    hipLaunchKernelGGL(locus_bounds_kernel, dim3(grid_for(n_runs, LOCI_THREADS, LOCI_MAX_BLOCKS)), dim3(LOCI_THREADS), 0, stream, run_start, run_end, n_runs, join, locus_start,
                        post, loci, count);
-    hipLaunchKernelGGL(locus_rows_kernel, dim3(grid_for(n)), dim3(LOCI_THREADS), 0, stream, intervals, n, length, join, n_runs, locus_start, loci, key);
-    hipLaunchKernelGGL(locus_finish_kernel, dim3(grid_for(n_runs)), dim3(LOCI_THREADS), 0, stream, join, n_runs, post, key, loci);
+    hipLaunchKernelGGL(locus_rows_kernel, dim3(grid_for(n, LOCI_THREADS, LOCI_MAX_BLOCKS)), dim3(LOCI_THREADS), 0, stream, intervals, n, length, join, n_runs, locus_start, loci, key);
+    hipLaunchKernelGGL(locus_finish_kernel, dim3(grid_for(n_runs, LOCI_THREADS, LOCI_MAX_BLOCKS)), dim3(LOCI_THREADS), 0, stream, join, n_runs, post, key, loci);
     return hipGetLastError();
 }
 
 void launch_density(const uint32_t *bits, int64_t length, int64_t window, int64_t n_windows, int32_t *covered, hipStream_t stream) {
     if (n_windows <= 0) return;
     if (window < DENSITY_WAVE_FROM)
-        hipLaunchKernelGGL(density_lane_kernel, dim3(grid_for(n_windows)), dim3(LOCI_THREADS), 0, stream, bits, length, window, n_windows, covered);
+        hipLaunchKernelGGL(density_lane_kernel, dim3(grid_for(n_windows, LOCI_THREADS, LOCI_MAX_BLOCKS)), dim3(LOCI_THREADS), 0, stream, bits, length, window, n_windows, covered);
     else
-        hipLaunchKernelGGL(density_wave_kernel, dim3(grid_for(n_windows * 64)), dim3(LOCI_THREADS), 0, stream, bits, length, window, n_windows, covered);
+        hipLaunchKernelGGL(density_wave_kernel, dim3(grid_for(n_windows * 64, LOCI_THREADS, LOCI_MAX_BLOCKS)), dim3(LOCI_THREADS), 0, stream, bits, length, window, n_windows, covered);
 }
 
 }  // namespace rb

@@ -11,6 +11,7 @@ namespace rb {
 namespace {
 
 constexpr int MASK_THREADS = 256;
+constexpr int64_t MASK_MAX_BLOCKS = 256 * 32;      // blocks of a launch at most; the kernels stride
 // interior words a lane sets on its own; longer intervals are set by the whole wave, 64 words per store instruction
 constexpr int32_t MASK_LANE_WORDS = 8;
 
@@ -127,22 +128,18 @@ __global__ void __launch_bounds__(MASK_THREADS) mask_format_kernel(const uint8_t
     }
 }
 
-unsigned grid_for(int64_t items) {
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + MASK_THREADS - 1) / MASK_THREADS, 256 * 32));
-}
-
 }  // namespace
 
 void launch_mask_coverage(const int32_t *intervals, int64_t n, int64_t length, uint32_t *bits, hipStream_t stream) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(mask_coverage_kernel, dim3(grid_for(n)), dim3(MASK_THREADS), 0, stream, intervals, n, length, bits);
+    hipLaunchKernelGGL(mask_coverage_kernel, dim3(grid_for(n, MASK_THREADS, MASK_MAX_BLOCKS)), dim3(MASK_THREADS), 0, stream, intervals, n, length, bits);
 }
 
 void launch_mask_format(const uint8_t *ascii, int64_t length, const uint32_t *bits, int64_t nwords, int hard, int64_t width,
                         int64_t out_len, uint8_t *out, hipStream_t stream) {
     if (out_len <= 0) return;
     const uint64_t recip = ~(uint64_t)0 / ((uint64_t)width + 1);
-    hipLaunchKernelGGL(mask_format_kernel, dim3(grid_for((out_len + 15) >> 4)), dim3(MASK_THREADS), 0, stream, ascii, length, bits, nwords,
+    hipLaunchKernelGGL(mask_format_kernel, dim3(grid_for((out_len + 15) >> 4, MASK_THREADS, MASK_MAX_BLOCKS)), dim3(MASK_THREADS), 0, stream, ascii, length, bits, nwords,
                        hard, width, recip, out_len, (uint4 *)out);
 }
 

@@ -229,10 +229,10 @@ void launch_repeat_format(const uint8_t *ascii, int64_t length, const int32_t *i
                           int32_t flank, const char *name, int32_t name_len, int32_t *span_row, uint8_t *out, hipStream_t stream) {
     if (total <= 0) return;
     const int64_t spans = (total + REPEAT_SPAN - 1) / REPEAT_SPAN;
-    hipLaunchKernelGGL(repeat_span_kernel, dim3((unsigned)((spans + REP_THREADS) / REP_THREADS)), dim3(REP_THREADS), 0, stream, off, k, total,
-                       spans, span_row);
-    hipLaunchKernelGGL(repeat_format_kernel, dim3((unsigned)std::min<int64_t>(spans, 256 * 64)), dim3(REP_THREADS), 0, stream, ascii, length, iv,
-                       off, total, flank, name, name_len, span_row, (uint4 *)out);
+    // (one lane per span and one more, none of them striding: no cap; one workgroup per span, striding from 256 * 64 spans on)
+    hipLaunchKernelGGL(repeat_span_kernel, dim3(grid_for(spans + 1, REP_THREADS, INT32_MAX)), dim3(REP_THREADS), 0, stream, off, k, total, spans, span_row);
+    hipLaunchKernelGGL(repeat_format_kernel, dim3(grid_for(spans, 1, 256 * 64)), dim3(REP_THREADS), 0, stream, ascii, length, iv, off, total, flank,
+                       name, name_len, span_row, (uint4 *)out);
 }
 
 }  // namespace rb

@@ -19,10 +19,17 @@
 // (ribbit_hip_record_loci, ribbit_bed_loci_text) and --density-bedgraph the covered bases per window (ribbit_hip_record_density),
 // the same way again.  The BED rows are read back once per record, however many of the four are asked for.
 //
+// These four are the ROW OUTPUTS, and each is described once, by its entry of kOutputs below: its file option, its stage (enum
+// Stage, with the stage's names beside it), its qualifier options with their ranges and wording (defaults: Settings), and the function that
+// makes one record's text from the record's rows.  Parsing, the "needs" checks, opening the files, the sinks of the pipelined
+// records and of the last one, --timing and the RIBBIT_PROFILE line are loops over that table.  A fifth row output is: a stage in
+// the enum and its names, the qualifiers' fields in Settings, a produce function, an entry of kOutputs, and its lines of kHelp.
+//
 // Reproduced quirks: -p is accepted and ignored (Q1); without -o the BED rows go to
 // stderr (Q2); --help exits with status 1 (Q3); the record name ends at the first space and the last
 // record is processed even when the file is empty (Q4).
 #include <algorithm>
+#include <array>
 #include <cctype>
 #include <charconv>
 #include <chrono>
@@ -47,6 +54,165 @@
 
 namespace {
 
+[[noreturn]] void die(const std::string &msg) {        // argument errors: main thread, before any worker exists
+    std::cerr << "ribbit-hip: " << msg << "\n";
+    std::exit(1);
+}
+
+// a failure of the GPU path inside the record pipeline: carried to main(), which lets the workers drain, closes the
+// handles and returns 1 (exiting from a worker would run static destructors under live threads)
+struct PathError { std::string what; };
+
+void check(int rc) {
+    if (rc != RIBBIT_OK) throw PathError{std::string("GPU path failed: ") + ribbit_hip_last_error()};
+}
+
+// The stages of a record: the six every record goes through, then one per row output, in the order of kOutputs.
+enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, N_STAGES };
+constexpr int N_FIXED_STAGES = MASK;
+// a stage's key in --timing's stage_ms_summed_over_records and its label in the RIBBIT_PROFILE line
+const struct { const char *key, *label; } kStageNames[N_STAGES] = {
+    {"load", "load"}, {"perfect", "perfect"}, {"substitutions", "substitutions"}, {"anchored", "anchored"}, {"dispatch", "dispatch"},
+    {"refine_and_bed", "refine+BED"}, {"mask", "mask"}, {"repeats", "repeats"}, {"loci", "loci"}, {"density", "density"}};
+
+// wall time per stage, summed over the records (--timing, RIBBIT_PROFILE=1)
+double g_stage_ms[N_STAGES] = {};
+std::mutex g_stage_mu;
+struct StageClock {
+    Stage stage;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    explicit StageClock(Stage s) : stage(s) {}
+    ~StageClock() {
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        std::lock_guard<std::mutex> lk(g_stage_mu);
+        g_stage_ms[stage] += ms;
+    }
+};
+
+// ---- the row outputs: what is written from a record's BED rows beside the BED itself
+// where an output's text for one record goes: the record's string of the pipeline, or the file itself for the last record
+using Sink = std::function<void(const char *, size_t)>;
+
+// what the outputs of one record share: the record and its rows in BED order, read back once for all of them
+struct RecordRows {
+    const std::string &name;
+    int64_t length;
+    std::vector<int32_t> iv;             // (start, end) per row
+    const char *bed_text;                // the record's BED text, row i on line i (handle-owned: valid until the handle's next refinement) ...
+    size_t bed_len;
+    std::string bed_copy;                // ... or this copy of it, when it came in slices and an output quotes it
+    size_t n() const { return iv.size() / 2; }
+};
+
+// the qualifiers' values and their defaults
+struct Settings {
+    int mask_mode = RIBBIT_MASK_SOFT;    // --mask soft|hard
+    int mask_width = 60;                 // --mask-width N: bases per line, 0 = one line per record
+    int flank = 100;                     // --flank N: bases on either side of a row
+    int loci_gap = 0;                    // --loci-gap D: runs at most D bases apart are one locus
+    int density_window = 10000;          // --density-window W
+};
+
+// --name VALUE: a whole number of bases in [lo, hi] of at most max_digits digits (`range`: how the message puts that), or soft|hard
+struct Qualifier {
+    const char *name;
+    enum Kind { BASES, SOFT_HARD } kind;
+    int64_t lo, hi;
+    size_t max_digits;
+    const char *range;
+    int Settings::*field;
+};
+constexpr size_t MAX_QUALIFIERS = 2;
+
+void produce_masked(RibbitHandle *h, const RecordRows &r, const Settings &s, const Sink &write) {      // the header and the masked body
+    const char *body = nullptr;
+    size_t body_len = 0;
+    { StageClock c(MASK); check(ribbit_hip_mask_record(h, r.iv.data(), r.n(), s.mask_mode, s.mask_width, &body, &body_len)); }
+    const std::string header = ">" + r.name + "\n";
+    write(header.data(), header.size());
+    write(body, body_len);
+}
+
+void produce_repeats(RibbitHandle *h, const RecordRows &r, const Settings &s, const Sink &write) {
+    // in batches of the handle's text budget, each written before the next call reuses the text
+    for (size_t done = 0, k = 0; done < r.n(); done += k) {
+        const char *text = nullptr;
+        size_t len = 0;
+        { StageClock c(REPEATS); check(ribbit_hip_repeat_sequences(h, r.name.c_str(), r.iv.data() + 2 * done, r.n() - done, s.flank, &text, &len, &k)); }
+        write(text, len);
+    }
+}
+
+void produce_loci(RibbitHandle *h, const RecordRows &r, const Settings &s, const Sink &write) {
+    const RibbitLocus *loci = nullptr;
+    size_t n_loci = 0;
+    char *text = nullptr;
+    size_t len = 0;
+    StageClock c(LOCI);
+    check(ribbit_hip_record_loci(h, r.iv.data(), r.n(), s.loci_gap, &loci, &n_loci));
+    check(ribbit_bed_loci_text(r.name.c_str(), r.bed_text, r.bed_len, loci, n_loci, &text, &len));
+    write(text, len);
+    ribbit_text_free(text);
+}
+
+void produce_density(RibbitHandle *h, const RecordRows &r, const Settings &s, const Sink &write) {
+    const int32_t *covered = nullptr;
+    size_t n_windows = 0;
+    StageClock c(DENSITY);
+    check(ribbit_hip_record_density(h, r.iv.data(), r.n(), s.density_window, &covered, &n_windows));
+    std::string lines;
+    char num[24];
+    auto put = [&](int64_t v, char sep) { lines.append(num, (size_t)(std::to_chars(num, num + sizeof num, v).ptr - num)); lines += sep; };
+    for (size_t k = 0; k < n_windows; ++k) {
+        const int64_t from = (int64_t)k * s.density_window;
+        lines += r.name;
+        lines += '\t';
+        put(from, '\t');
+        put(std::min<int64_t>(from + s.density_window, r.length), '\t');
+        put(covered[k], '\n');
+        if (lines.size() > ((size_t)1 << 20)) { write(lines.data(), lines.size()); lines.clear(); }
+    }
+    write(lines.data(), lines.size());
+}
+
+// One entry per row output.  The order is the order of everything that is done for all of them: the "needs" checks, opening the
+// files (binary), producing a record's texts, the keys of --timing.
+struct Output {
+    const char *option;                      // --option FILE
+    Stage stage;
+    bool quotes_bed;                         // its lines quote the rows' lines: it needs RecordRows::bed_text
+    void (*produce)(RibbitHandle *, const RecordRows &, const Settings &, const Sink &);      // one record's text for this output
+    Qualifier qualifiers[MAX_QUALIFIERS];    // (name null: none)
+};
+constexpr size_t N_OUTPUTS = 4;
+const Output kOutputs[N_OUTPUTS] = {
+    {"masked-fasta", MASK, false, produce_masked,
+     {{"mask", Qualifier::SOFT_HARD, 0, 0, 0, nullptr, &Settings::mask_mode},
+      {"mask-width", Qualifier::BASES, 0, 999999999, 9, "0 or more", &Settings::mask_width}}},
+    {"repeat-fasta", REPEATS, false, produce_repeats,
+     {{"flank", Qualifier::BASES, 0, 999999999, 9, "0 or more, at most 9 digits", &Settings::flank}, {}}},
+    {"loci-bed", LOCI, true, produce_loci,
+     {{"loci-gap", Qualifier::BASES, 0, 2147483647, 10, "0 .. 2147483647", &Settings::loci_gap}, {}}},
+    {"density-bedgraph", DENSITY, false, produce_density,
+     {{"density-window", Qualifier::BASES, 1, 2147483647, 10, "1 .. 2147483647", &Settings::density_window}, {}}}};
+
+// which outputs are on for one record, and where each one's text goes (an empty sink: off)
+struct RowJobs {
+    std::array<Sink, N_OUTPUTS> sink;
+    template <typename Make>
+    RowJobs(const std::array<bool, N_OUTPUTS> &on, Make make) {
+        for (size_t k = 0; k < N_OUTPUTS; ++k)
+            if (on[k]) sink[k] = make(k);
+    }
+    // the first one that is on (the stage clock that pays for reading the rows back is its); quoting: ... and quotes the BED text
+    const Output *first(bool quoting = false) const {
+        for (size_t k = 0; k < N_OUTPUTS; ++k)
+            if (sink[k] && (kOutputs[k].quotes_bed || !quoting)) return &kOutputs[k];
+        return nullptr;
+    }
+    bool any() const { return first() != nullptr; }
+};
+
 struct Options {
     std::string fasta, out;
     int min_motif = 2, max_motif = 100;          // global_variables.cpp:21-22
@@ -56,19 +222,9 @@ struct Options {
     std::vector<int> devices;                     // --devices / RIBBIT_DEVICES: GPUs the records are dealt over (empty: `device` alone)
     int jobs = 0;                                 // records in flight PER DEVICE; 0 = automatic
     std::string timing;                           // --timing FILE: a JSON record of the run (the reference has cerr progress lines only)
-    std::string masked_fasta;                     // --masked-fasta FILE: the records again, their BED rows masked (empty: off)
-    int mask_mode = RIBBIT_MASK_SOFT;             // --mask soft|hard
-    int mask_width = 60;                          // --mask-width N: bases per line, 0 = one line per record
-    bool has_mask_mode = false, has_mask_width = false;
-    std::string repeat_fasta;                     // --repeat-fasta FILE: every BED row's bases with their flanks (empty: off)
-    int flank = 100;                              // --flank N: bases on either side of a row
-    bool has_flank = false;
-    std::string loci_bed;                         // --loci-bed FILE: the rows merged into sorted loci (empty: off)
-    int loci_gap = 0;                             // --loci-gap D: runs at most D bases apart are one locus
-    bool has_loci_gap = false;
-    std::string density_bedgraph;                 // --density-bedgraph FILE: covered bases per window (empty: off)
-    int density_window = 10000;                   // --density-window W
-    bool has_density_window = false;
+    std::array<std::string, N_OUTPUTS> row_path;                  // the row outputs' files, as kOutputs orders them (empty: off)
+    std::array<std::array<bool, MAX_QUALIFIERS>, N_OUTPUTS> qualifier_given{};
+    Settings settings;
 };
 
 const char *kHelp =
@@ -112,15 +268,6 @@ const char *kHelp =
     "                                rows cover (an exact integer count, not a fraction: divide by end - start for one)\n"
     "  --density-window arg          (ribbit-hip) bases per window of --density-bedgraph, 1 or more. Default: 10000\n";
 
-[[noreturn]] void die(const std::string &msg) {        // argument errors: main thread, before any worker exists
-    std::cerr << "ribbit-hip: " << msg << "\n";
-    std::exit(1);
-}
-
-// a failure of the GPU path inside the record pipeline: carried to main(), which lets the workers drain, closes the
-// handles and returns 1 (exiting from a worker would run static destructors under live threads)
-struct PathError { std::string what; };
-
 bool parse_device_list(const std::string &value, std::vector<int> &out) {
     out.clear();
     size_t at = 0;
@@ -140,19 +287,23 @@ bool is_number(const std::string &s) { return !s.empty() && std::all_of(s.begin(
 int parse_arguments(int argc, char **argv, Options &o) {
     static const std::map<std::string, std::string> longs = {
         {"help", "h"}, {"input-file", "i"}, {"output-file", "o"}, {"min-motif-length", "m"}, {"max-motif-length", "M"},
-        {"purity", "p"}, {"min-length", "l"}, {"min-units", "U"}, {"perfect-units", "P"}, {"device", "D"}, {"jobs", "J"}, {"devices", "G"}, {"timing", "T"},
-        {"masked-fasta", "X"}, {"mask", "K"}, {"mask-width", "W"}, {"repeat-fasta", "Y"}, {"flank", "F"},
-        {"loci-bed", "LB"}, {"loci-gap", "LG"}, {"density-bedgraph", "DB"}, {"density-window", "DW"}};
+        {"purity", "p"}, {"min-length", "l"}, {"min-units", "U"}, {"perfect-units", "P"}, {"device", "D"}, {"jobs", "J"}, {"devices", "G"}, {"timing", "T"}};
     bool help = false;
     for (int a = 1; a < argc; ++a) {
         std::string arg = argv[a], key, value;
         bool has_value = false;
+        size_t output = N_OUTPUTS, qualifier = MAX_QUALIFIERS;      // a row output's option: --option FILE, or qualifier `qualifier` of it
         if (arg.rfind("--", 0) == 0) {
             const size_t eq = arg.find('=');
             const std::string name = arg.substr(2, eq == std::string::npos ? std::string::npos : eq - 2);
             auto it = longs.find(name);
-            if (it == longs.end()) die("unrecognised option '" + arg + "'");
-            key = it->second;
+            for (size_t k = 0; k < N_OUTPUTS; ++k) {
+                if (name == kOutputs[k].option) output = k;
+                for (size_t q = 0; q < MAX_QUALIFIERS; ++q)
+                    if (kOutputs[k].qualifiers[q].name && name == kOutputs[k].qualifiers[q].name) { output = k; qualifier = q; }
+            }
+            if (it == longs.end() && output == N_OUTPUTS) die("unrecognised option '" + arg + "'");
+            if (it != longs.end()) key = it->second;
             if (eq != std::string::npos) { value = arg.substr(eq + 1); has_value = true; }
         } else if (arg.size() >= 2 && arg[0] == '-') {
             key = arg.substr(1, 1);
@@ -166,7 +317,22 @@ int parse_arguments(int argc, char **argv, Options &o) {
             if (a + 1 >= argc) die("the required argument for option '" + arg + "' is missing");
             value = argv[++a];
         }
-        if (key == "i") o.fasta = value;
+        if (output < N_OUTPUTS && qualifier == MAX_QUALIFIERS) {
+            if (value.empty()) die(std::string("--") + kOutputs[output].option + " wants a file name");
+            o.row_path[output] = value;
+        } else if (output < N_OUTPUTS) {
+            const Qualifier &q = kOutputs[output].qualifiers[qualifier];
+            if (q.kind == Qualifier::SOFT_HARD) {
+                if (value != "soft" && value != "hard") die(std::string("--") + q.name + " wants soft or hard, got '" + value + "'");
+                o.settings.*q.field = value == "soft" ? RIBBIT_MASK_SOFT : RIBBIT_MASK_HARD;
+            } else {
+                if (!is_number(value) || value.size() > q.max_digits || std::atoll(value.c_str()) < q.lo || std::atoll(value.c_str()) > q.hi)
+                    die(std::string("--") + q.name + " wants a whole number of bases (" + q.range + "), got '" + value + "'");
+                o.settings.*q.field = (int)std::atoll(value.c_str());
+            }
+            o.qualifier_given[output][qualifier] = true;
+        }
+        else if (key == "i") o.fasta = value;
         else if (key == "o") o.out = value;
         else if (key == "m") o.min_motif = std::atoi(value.c_str());
         else if (key == "M") o.max_motif = std::atoi(value.c_str());
@@ -177,58 +343,12 @@ int parse_arguments(int argc, char **argv, Options &o) {
         else if (key == "D") o.device = std::atoi(value.c_str());
         else if (key == "J") o.jobs = std::atoi(value.c_str());
         else if (key == "T") o.timing = value;
-        else if (key == "X") {
-            if (value.empty()) die("--masked-fasta wants a file name");
-            o.masked_fasta = value;
-        }
-        else if (key == "K") {
-            if (value == "soft") o.mask_mode = RIBBIT_MASK_SOFT;
-            else if (value == "hard") o.mask_mode = RIBBIT_MASK_HARD;
-            else die("--mask wants soft or hard, got '" + value + "'");
-            o.has_mask_mode = true;
-        }
-        else if (key == "W") {
-            if (!is_number(value) || value.size() > 9) die("--mask-width wants a whole number of bases (0 or more), got '" + value + "'");
-            o.mask_width = std::atoi(value.c_str());
-            o.has_mask_width = true;
-        }
-        else if (key == "Y") {
-            if (value.empty()) die("--repeat-fasta wants a file name");
-            o.repeat_fasta = value;
-        }
-        else if (key == "F") {
-            if (!is_number(value) || value.size() > 9) die("--flank wants a whole number of bases (0 or more, at most 9 digits), got '" + value + "'");
-            o.flank = std::atoi(value.c_str());
-            o.has_flank = true;
-        }
-        else if (key == "LB") {
-            if (value.empty()) die("--loci-bed wants a file name");
-            o.loci_bed = value;
-        }
-        else if (key == "LG") {
-            if (!is_number(value) || value.size() > 10 || std::atoll(value.c_str()) > 2147483647LL)
-                die("--loci-gap wants a whole number of bases (0 .. 2147483647), got '" + value + "'");
-            o.loci_gap = (int)std::atoll(value.c_str());
-            o.has_loci_gap = true;
-        }
-        else if (key == "DB") {
-            if (value.empty()) die("--density-bedgraph wants a file name");
-            o.density_bedgraph = value;
-        }
-        else if (key == "DW") {
-            if (!is_number(value) || value.size() > 10 || std::atoll(value.c_str()) < 1 || std::atoll(value.c_str()) > 2147483647LL)
-                die("--density-window wants a whole number of bases (1 .. 2147483647), got '" + value + "'");
-            o.density_window = (int)std::atoll(value.c_str());
-            o.has_density_window = true;
-        }
         else if (key == "G") { if (!parse_device_list(value, o.devices)) die("--devices wants a comma separated list of GPU ordinals, got '" + value + "'"); }
     }
     if (help) { std::cerr << kHelp << "\n"; return 0; }                       // ribbit.cpp:114-117
-    if (o.masked_fasta.empty() && (o.has_mask_mode || o.has_mask_width))
-        die(std::string(o.has_mask_mode ? "--mask" : "--mask-width") + " needs --masked-fasta");
-    if (o.repeat_fasta.empty() && o.has_flank) die("--flank needs --repeat-fasta");
-    if (o.loci_bed.empty() && o.has_loci_gap) die("--loci-gap needs --loci-bed");
-    if (o.density_bedgraph.empty() && o.has_density_window) die("--density-window needs --density-bedgraph");
+    for (size_t k = 0; k < N_OUTPUTS; ++k)
+        for (size_t q = 0; q < MAX_QUALIFIERS && o.row_path[k].empty(); ++q)
+            if (o.qualifier_given[k][q]) die(std::string("--") + kOutputs[k].qualifiers[q].name + " needs --" + kOutputs[k].option);
     if (o.fasta.empty()) { std::cerr << "ERROR: Please specify an input fasta file!\n"; return 0; }   // :122-126
     return 1;
 }
@@ -274,63 +394,11 @@ void build_refine_params(const Options &o, RibbitRefineParams &prm) {
     for (auto &kv : perfect_units) if (kv.first >= 0 && kv.first < RIBBIT_TABLE) prm.perfect_units[kv.first] = kv.second;
 }
 
-void check(int rc) {
-    if (rc != RIBBIT_OK) throw PathError{std::string("GPU path failed: ") + ribbit_hip_last_error()};
-}
-
 size_t count_failed(const RibbitSeed *s, size_t n) {
     size_t c = 0;
     for (size_t i = 0; i < n; ++i) c += s[i].type == RIBBIT_RANK_N;
     return c;
 }
-
-// RIBBIT_PROFILE=1: wall time per stage, summed over the records, printed at exit
-double g_stage_ms[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};     // load, perfect, substitutions, anchored, dispatch, refine+BED, mask, repeats, loci, density
-std::mutex g_stage_mu;
-struct StageClock {
-    int slot;
-    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    explicit StageClock(int s) : slot(s) {}
-    ~StageClock() {
-        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        std::lock_guard<std::mutex> lk(g_stage_mu);
-        g_stage_ms[slot] += ms;
-    }
-};
-
-// --masked-fasta: how to mask, and where the record's header and masked body go (null: masking is off for this record)
-struct MaskJob {
-    int mode, width;
-    std::function<void(const char *, size_t)> write;
-};
-
-// --repeat-fasta: the flank, and where the record's entries go (null: off for this record)
-struct RepeatJob {
-    int flank;
-    std::function<void(const char *, size_t)> write;
-};
-
-// --loci-bed: the gap, and where the record's lines go (null: off for this record)
-struct LociJob {
-    int gap;
-    std::function<void(const char *, size_t)> write;
-};
-
-// --density-bedgraph: the window, and where the record's lines go (null: off for this record)
-struct DensityJob {
-    int window;
-    std::function<void(const char *, size_t)> write;
-};
-
-// what a record's rows are wanted for; the stage clock that pays for reading them back is the first one's
-struct RowJobs {
-    const MaskJob *mask = nullptr;
-    const RepeatJob *repeats = nullptr;
-    const LociJob *loci = nullptr;
-    const DensityJob *density = nullptr;
-    bool any() const { return mask || repeats || loci || density; }
-    int first_slot() const { return mask ? 6 : repeats ? 7 : loci ? 8 : 9; }
-};
 
 // the (start, end) pairs of a BED text, appended to iv
 void append_intervals(const char *text, size_t len, std::vector<int32_t> &iv) {
@@ -399,102 +467,51 @@ bool refine_over_devices(RibbitHandle *h, const std::vector<Helper> &helpers, co
     return true;
 }
 
-// processSequence (fasta_utils.cpp:59-250) through the C ABI, with the reference's progress lines; then, with --masked-fasta,
-// the record masked by its rows, with --repeat-fasta the rows' entries, with --loci-bed the rows merged into loci and with
-// --density-bedgraph the covered bases per window, all on `h`, the handle that loaded it
+// processSequence (fasta_utils.cpp:59-250) through the C ABI, with the reference's progress lines; then the record's text for
+// every row output that `jobs` has a sink for, in the order of kOutputs, all on `h`, the handle that loaded it
 void process_sequence(RibbitHandle *h, const RibbitRefineParams &prm, const std::string &name, const char *bases, int64_t length,
-                      std::ostream &out, std::ostream &log, const RowJobs &jobs, const std::vector<Helper> *helpers = nullptr) {
-    const MaskJob *mask = jobs.mask;
-    const RepeatJob *repeats = jobs.repeats;
+                      std::ostream &out, std::ostream &log, const Settings &settings, const RowJobs &jobs, const std::vector<Helper> *helpers = nullptr) {
     const time_t t0 = time(0);
     auto secs = [&]() { return difftime(time(0), t0); };
-    { StageClock c(0); check(ribbit_hip_load_record_pinned(h, bases, length)); }
+    { StageClock c(LOAD); check(ribbit_hip_load_record_pinned(h, bases, length)); }
     log << "Generated shift XORs!\t Time elapsed:" << secs() << "secs\n";
     const RibbitSeed *p, *s, *a;
     size_t np, ns, na;
-    { StageClock c(1); check(ribbit_hip_seeds_perfect(h, &p, &np)); }
+    { StageClock c(PERFECT); check(ribbit_hip_seeds_perfect(h, &p, &np)); }
     log << "Total number of perfect seeds: " << np << "\t Time elapsed: " << secs() << "secs\n";
-    { StageClock c(2); check(ribbit_hip_seeds_substitutions(h, &p, &np, &s, &ns)); }
+    { StageClock c(SUBSTITUTIONS); check(ribbit_hip_seeds_substitutions(h, &p, &np, &s, &ns)); }
     log << "Total number of seeds considering substitutions: " << np + ns - count_failed(p, np) - count_failed(s, ns)
               << "\t Time elapsed: " << secs() << "secs\n";
-    { StageClock c(3); check(ribbit_hip_seeds_anchored(h, &p, &np, &s, &ns, &a, &na)); }
+    { StageClock c(ANCHORED); check(ribbit_hip_seeds_anchored(h, &p, &np, &s, &ns, &a, &na)); }
     log << "Generated anchored shift XORs!\t Time elapsed: " << secs() << "secs\n";
     log << "Total number of seeds considering indels: "
               << np + ns + na - count_failed(p, np) - count_failed(s, ns) - count_failed(a, na) << "\t Time elapsed: " << secs() << "secs\n";
     const RibbitSeed *d;
     size_t nd;
-    { StageClock c(4); check(ribbit_hip_dispatch_seeds(h, &d, &nd)); }
+    { StageClock c(DISPATCH); check(ribbit_hip_dispatch_seeds(h, &d, &nd)); }
     // one record over several GPUs: only worth it from a few hundred thousand seeds on (RIBBIT_SHARD_MIN_SEEDS: a test hook)
     static const size_t shard_min = std::getenv("RIBBIT_SHARD_MIN_SEEDS") ? (size_t)std::atoll(std::getenv("RIBBIT_SHARD_MIN_SEEDS")) : 400000;
-    std::vector<int32_t> mask_iv;        // the record's rows in BED order, read back once for all outputs
-    const bool rows = jobs.any();
-    std::string bed_copy;                // the record's BED text when it came in slices and the loci quote it
-    const char *bed_text = nullptr;      // the record's BED text, for the loci's lines
-    size_t bed_len = 0;
+    RecordRows rows{name, length, {}, nullptr, 0, {}};
+    const bool want_rows = jobs.any();
     if (helpers && !helpers->empty() && nd >= shard_min && nd >= 2 * (helpers->size() + 1)) {
-        StageClock c(5);
-        const bool sharded = refine_over_devices(h, *helpers, prm, name, bases, length, d, nd, out, log, rows ? &mask_iv : nullptr,
-                                                 jobs.loci ? &bed_copy : nullptr);
-        bed_text = bed_copy.data();
-        bed_len = bed_copy.size();
+        StageClock c(REFINE_BED);
+        const bool sharded = refine_over_devices(h, *helpers, prm, name, bases, length, d, nd, out, log, want_rows ? &rows.iv : nullptr,
+                                                 jobs.first(true) ? &rows.bed_copy : nullptr);
+        rows.bed_text = rows.bed_copy.data();
+        rows.bed_len = rows.bed_copy.size();
         if (std::getenv("RIBBIT_PROFILE"))
             log << "[devices] refinement of " << name << ": " << nd << " dispatched seeds " << (sharded ? "in " : "NOT in ") << helpers->size() + 1 << " slices over as many handles\n";
     } else {
         const char *text;
         size_t len;
-        { StageClock c(5); check(ribbit_hip_refine_bed(h, &prm, name.c_str(), &text, &len)); }
+        { StageClock c(REFINE_BED); check(ribbit_hip_refine_bed(h, &prm, name.c_str(), &text, &len)); }
         out.write(text, (std::streamsize)len);
-        if (rows) { StageClock c(jobs.first_slot()); append_intervals(text, len, mask_iv); }
-        bed_text = text;                 // (handle-owned: valid until the handle's next refinement)
-        bed_len = len;
+        if (want_rows) { StageClock c(jobs.first()->stage); append_intervals(text, len, rows.iv); }
+        rows.bed_text = text;
+        rows.bed_len = len;
     }
-    if (mask) {
-        const char *body = nullptr;
-        size_t body_len = 0;
-        { StageClock c(6); check(ribbit_hip_mask_record(h, mask_iv.data(), mask_iv.size() / 2, mask->mode, mask->width, &body, &body_len)); }
-        const std::string header = ">" + name + "\n";
-        mask->write(header.data(), header.size());
-        mask->write(body, body_len);
-    }
-    if (repeats) {      // in batches of the handle's text budget, each written before the next call reuses the text
-        const size_t n = mask_iv.size() / 2;
-        for (size_t done = 0, k = 0; done < n; done += k) {
-            const char *text = nullptr;
-            size_t len = 0;
-            { StageClock c(7); check(ribbit_hip_repeat_sequences(h, name.c_str(), mask_iv.data() + 2 * done, n - done, repeats->flank, &text, &len, &k)); }
-            repeats->write(text, len);
-        }
-    }
-    if (jobs.loci) {
-        const RibbitLocus *loci = nullptr;
-        size_t n_loci = 0;
-        char *text = nullptr;
-        size_t len = 0;
-        StageClock c(8);
-        check(ribbit_hip_record_loci(h, mask_iv.data(), mask_iv.size() / 2, jobs.loci->gap, &loci, &n_loci));
-        check(ribbit_bed_loci_text(name.c_str(), bed_text, bed_len, loci, n_loci, &text, &len));
-        jobs.loci->write(text, len);
-        ribbit_text_free(text);
-    }
-    if (jobs.density) {
-        const int32_t *covered = nullptr;
-        size_t n_windows = 0;
-        StageClock c(9);
-        check(ribbit_hip_record_density(h, mask_iv.data(), mask_iv.size() / 2, jobs.density->window, &covered, &n_windows));
-        std::string lines;
-        char num[24];
-        auto put = [&](int64_t v, char sep) { lines.append(num, (size_t)(std::to_chars(num, num + sizeof num, v).ptr - num)); lines += sep; };
-        for (size_t k = 0; k < n_windows; ++k) {
-            const int64_t from = (int64_t)k * jobs.density->window;
-            lines += name;
-            lines += '\t';
-            put(from, '\t');
-            put(std::min<int64_t>(from + jobs.density->window, length), '\t');
-            put(covered[k], '\n');
-            if (lines.size() > ((size_t)1 << 20)) { jobs.density->write(lines.data(), lines.size()); lines.clear(); }
-        }
-        jobs.density->write(lines.data(), lines.size());
-    }
+    for (size_t k = 0; k < N_OUTPUTS; ++k)
+        if (jobs.sink[k]) kOutputs[k].produce(h, rows, settings, jobs.sink[k]);
     log << "Total number of seeds that are processed for alignment: " << nd << "\t Time elapsed: " << secs() << "secs\n";
 }
 
@@ -507,28 +524,14 @@ int main(int argc, char **argv) {
     std::ofstream file;
     if (!opt.out.empty()) file.open(opt.out);
     std::ostream &out = opt.out.empty() ? std::cerr : file;                   // ribbit.cpp:199-205
-    std::ofstream masked_file;
-    if (!opt.masked_fasta.empty()) {
-        masked_file.open(opt.masked_fasta, std::ios::binary);
-        if (!masked_file) die("--masked-fasta: cannot open '" + opt.masked_fasta + "' for writing");
+    std::array<std::ofstream, N_OUTPUTS> row_file;
+    std::array<bool, N_OUTPUTS> row_on;
+    for (size_t k = 0; k < N_OUTPUTS; ++k) {
+        row_on[k] = !opt.row_path[k].empty();
+        if (!row_on[k]) continue;
+        row_file[k].open(opt.row_path[k], std::ios::binary);
+        if (!row_file[k]) die(std::string("--") + kOutputs[k].option + ": cannot open '" + opt.row_path[k] + "' for writing");
     }
-    const bool masking = !opt.masked_fasta.empty();
-    std::ofstream repeat_file;
-    if (!opt.repeat_fasta.empty()) {
-        repeat_file.open(opt.repeat_fasta, std::ios::binary);
-        if (!repeat_file) die("--repeat-fasta: cannot open '" + opt.repeat_fasta + "' for writing");
-    }
-    const bool repeating = !opt.repeat_fasta.empty();
-    std::ofstream loci_file, density_file;
-    if (!opt.loci_bed.empty()) {
-        loci_file.open(opt.loci_bed, std::ios::binary);
-        if (!loci_file) die("--loci-bed: cannot open '" + opt.loci_bed + "' for writing");
-    }
-    if (!opt.density_bedgraph.empty()) {
-        density_file.open(opt.density_bedgraph, std::ios::binary);
-        if (!density_file) die("--density-bedgraph: cannot open '" + opt.density_bedgraph + "' for writing");
-    }
-    const bool merging = !opt.loci_bed.empty(), counting = !opt.density_bedgraph.empty();
 
     const auto t_run0 = std::chrono::steady_clock::now();
     RibbitRefineParams prm;
@@ -565,7 +568,7 @@ int main(int argc, char **argv) {
     jobs = std::min(jobs, 64);
     const int workers = jobs * ndev;
     struct Record { size_t index; std::string name; const char *bases; int64_t length; };
-    struct Result { std::string bed, log, masked, repeats, loci, density; };
+    struct Result { std::string bed, log; std::array<std::string, N_OUTPUTS> rows; };
     std::mutex mu;
     std::condition_variable cv;
     std::deque<Record> queue;
@@ -588,10 +591,7 @@ int main(int argc, char **argv) {
         for (auto it = done.find(next_out); it != done.end(); it = done.find(next_out)) {
             std::cerr << it->second.log;
             out.write(it->second.bed.data(), (std::streamsize)it->second.bed.size());
-            masked_file.write(it->second.masked.data(), (std::streamsize)it->second.masked.size());
-            repeat_file.write(it->second.repeats.data(), (std::streamsize)it->second.repeats.size());
-            loci_file.write(it->second.loci.data(), (std::streamsize)it->second.loci.size());
-            density_file.write(it->second.density.data(), (std::streamsize)it->second.density.size());
+            for (size_t k = 0; k < N_OUTPUTS; ++k) row_file[k].write(it->second.rows[k].data(), (std::streamsize)it->second.rows[k].size());
             done.erase(it);
             ++next_out;
         }
@@ -628,14 +628,8 @@ int main(int argc, char **argv) {
             }
             cv.notify_all();
             std::ostringstream bed, log;
-            std::string masked;
-            const MaskJob mask{opt.mask_mode, opt.mask_width, [&masked](const char *p, size_t n) { masked.append(p, n); }};
-            std::string repeat_text;         // (kept in memory until the record's turn to be written, as the masked text is)
-            const RepeatJob repeats{opt.flank, [&repeat_text](const char *p, size_t n) { repeat_text.append(p, n); }};
-            std::string loci_text, density_text;
-            const LociJob loci{opt.loci_gap, [&loci_text](const char *p, size_t n) { loci_text.append(p, n); }};
-            const DensityJob density{opt.density_window, [&density_text](const char *p, size_t n) { density_text.append(p, n); }};
-            const RowJobs row_jobs{masking ? &mask : nullptr, repeating ? &repeats : nullptr, merging ? &loci : nullptr, counting ? &density : nullptr};
+            std::array<std::string, N_OUTPUTS> texts;      // (kept in memory until the record's turn to be written)
+            const RowJobs row_jobs(row_on, [&texts](size_t k) { return [&texts, k](const char *p, size_t n) { texts[k].append(p, n); }; });
             bool ok = true;
             std::string why;
             {
@@ -645,7 +639,7 @@ int main(int argc, char **argv) {
                     try {
                         check(ribbit_hip_set_host_threads(wh, (int)std::max(1u, dev_cores * (unsigned)weight / (unsigned)jobs)));
                         log << "Processing sequence " << rec.name << "\n";
-                        process_sequence(wh, prm, rec.name, rec.bases, rec.length, bed, log, row_jobs);
+                        process_sequence(wh, prm, rec.name, rec.bases, rec.length, bed, log, opt.settings, row_jobs);
                     } catch (const PathError &e) { ok = false; why = e.what; }
                 }
             }
@@ -653,7 +647,7 @@ int main(int argc, char **argv) {
             {
                 std::lock_guard<std::mutex> lk(mu);
                 if (!ok && !failed) { failed = true; failure = why; }
-                done[rec.index] = Result{bed.str(), log.str(), std::move(masked), std::move(repeat_text), std::move(loci_text), std::move(density_text)};
+                done[rec.index] = Result{bed.str(), log.str(), std::move(texts)};
                 tokens[(size_t)dev] += weight;
                 if (!failed) flush_ready();
             }
@@ -714,15 +708,11 @@ int main(int argc, char **argv) {
             for (int d = 1; d < ndev && (size_t)d < handles.size(); ++d) helpers.push_back(Helper{handles[(size_t)d], (int)dev_cores});
             check(ribbit_hip_set_host_threads(h, helpers.empty() ? 0 : (int)dev_cores));
             static const char kNoBases[1] = {0};
-            // (every record the reader hands out is masked but the nameless empty one of a file without records, Q4)
-            const MaskJob mask{opt.mask_mode, opt.mask_width, [&masked_file](const char *p, size_t n) { masked_file.write(p, (std::streamsize)n); }};
-            const RepeatJob repeats{opt.flank, [&repeat_file](const char *p, size_t n) { repeat_file.write(p, (std::streamsize)n); }};
-            const LociJob loci{opt.loci_gap, [&loci_file](const char *p, size_t n) { loci_file.write(p, (std::streamsize)n); }};
-            const DensityJob density{opt.density_window, [&density_file](const char *p, size_t n) { density_file.write(p, (std::streamsize)n); }};
+            // (every record the reader hands out has its row outputs but the nameless empty one of a file without records, Q4)
             const bool real_last = !(last_name.empty() && last_length == 0);
-            const RowJobs row_jobs{masking && real_last ? &mask : nullptr, repeating && real_last ? &repeats : nullptr,
-                                   merging && real_last ? &loci : nullptr, counting && real_last ? &density : nullptr};
-            process_sequence(h, prm, last_name, last_bases ? last_bases : kNoBases, last_length, out, std::cerr, row_jobs, &helpers);
+            const RowJobs row_jobs(real_last ? row_on : std::array<bool, N_OUTPUTS>{},
+                                   [&row_file](size_t k) { return [&row_file, k](const char *p, size_t n) { row_file[k].write(p, (std::streamsize)n); }; });
+            process_sequence(h, prm, last_name, last_bases ? last_bases : kNoBases, last_length, out, std::cerr, opt.settings, row_jobs, &helpers);
         } catch (const PathError &e) { failed = true; failure = e.what; }
     }
     if (failed) { std::cerr << "ribbit-hip: " << failure << "\n"; status = 1; }
@@ -746,20 +736,18 @@ int main(int argc, char **argv) {
         for (int d = 0; d < ndev; ++d) total_bases += dev_bases[(size_t)d];
         tf << "{\"records\": " << n_records + 1 << ", \"bases\": " << total_bases << ", \"wall_s\": " << wall_s << ", \"status\": " << status
            << ", \"min_motif\": " << opt.min_motif << ", \"max_motif\": " << opt.max_motif << ", \"devices\": " << ndev << ", \"jobs_per_device\": " << jobs
-           << ", \"stage_ms_summed_over_records\": {\"load\": " << g_stage_ms[0] << ", \"perfect\": " << g_stage_ms[1] << ", \"substitutions\": " << g_stage_ms[2]
-           << ", \"anchored\": " << g_stage_ms[3] << ", \"dispatch\": " << g_stage_ms[4] << ", \"refine_and_bed\": " << g_stage_ms[5];
-        if (masking) tf << ", \"mask\": " << g_stage_ms[6];
-        if (repeating) tf << ", \"repeats\": " << g_stage_ms[7];
-        if (merging) tf << ", \"loci\": " << g_stage_ms[8];
-        if (counting) tf << ", \"density\": " << g_stage_ms[9];
+           << ", \"stage_ms_summed_over_records\": {";
+        for (int s = 0; s < N_FIXED_STAGES; ++s) tf << (s ? ", \"" : "\"") << kStageNames[s].key << "\": " << g_stage_ms[s];
+        for (size_t k = 0; k < N_OUTPUTS; ++k)
+            if (row_on[k]) tf << ", \"" << kStageNames[kOutputs[k].stage].key << "\": " << g_stage_ms[kOutputs[k].stage];
         tf << "}}\n";
     }
-    if (std::getenv("RIBBIT_PROFILE"))
-        std::cerr << "[stages, ms over all records] load " << g_stage_ms[0] << "  perfect " << g_stage_ms[1] << "  substitutions "
-                  << g_stage_ms[2] << "  anchored " << g_stage_ms[3] << "  dispatch " << g_stage_ms[4] << "  refine+BED " << g_stage_ms[5]
-                  << (masking ? "  mask " + std::to_string(g_stage_ms[6]) : std::string())
-                  << (repeating ? "  repeats " + std::to_string(g_stage_ms[7]) : std::string())
-                  << (merging ? "  loci " + std::to_string(g_stage_ms[8]) : std::string())
-                  << (counting ? "  density " + std::to_string(g_stage_ms[9]) : std::string()) << "\n";
+    if (std::getenv("RIBBIT_PROFILE")) {
+        std::cerr << "[stages, ms over all records]";
+        for (int s = 0; s < N_FIXED_STAGES; ++s) std::cerr << (s ? "  " : " ") << kStageNames[s].label << " " << g_stage_ms[s];
+        for (size_t k = 0; k < N_OUTPUTS; ++k)
+            if (row_on[k]) std::cerr << "  " << kStageNames[kOutputs[k].stage].label << " " << std::to_string(g_stage_ms[kOutputs[k].stage]);
+        std::cerr << "\n";
+    }
     return status;
 }

@@ -1,9 +1,8 @@
 """Merged loci and the density track on the GPU (loci.hip through ribbit_hip_record_loci / ribbit_hip_record_density):
 Scanner.record_loci and Scanner.record_density against the host twins and the numpy statement of the contract
 (tests/loci_contract.py), and ribbit-hip --loci-bed / --density-bedgraph end to end."""
-import json
-import os
-import subprocess
+import functools
+import types
 
 import numpy as np
 import pytest
@@ -11,12 +10,12 @@ import pytest
 import loci_contract
 import ribbit_amd
 import segments
+from cli_rows import records, rows_by_record, run as _run, stages as _stages, write_nine_records
 from mask_contract import masked_body
+from repeat_contract import repeat_entries
 from ribbit_amd.simulate import simulate_sequence, write_fasta
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "ribbit_amd", "ribbit-hip")
 I32_MIN, I32_MAX = -(1 << 31), (1 << 31) - 1
 GAPS = (0, 1, 5, 1000, I32_MAX)
 
@@ -139,56 +138,36 @@ def test_before_load_is_a_state_error():
             sc.record_density([(0, 1)], 0)
 
 
-def _rows_by_record(bed: str):
-    out = {}
-    for line in bed.splitlines(keepends=True):
-        out.setdefault(line.split("\t")[0], []).append(line)
-    return {k: "".join(v) for k, v in out.items()}
-
-
 def _expected(fa, bed, gap, window):
     """the loci file and the bedGraph: the contract applied to the BED per record, in input order"""
-    by_name = _rows_by_record(bed)
+    by_name = rows_by_record(bed)
     loci_text, density_text = "", ""
-    for name, bases, _ in ribbit_amd.read_fasta(str(fa)):
-        if not (name or bases):
-            continue
+    for name, bases in records(fa):
         rows = ribbit_amd.bed_intervals(by_name.get(name, ""))
         loci_text += loci_contract.loci_lines(name, by_name.get(name, ""), loci_contract.record_loci(len(bases), rows, gap))
         density_text += loci_contract.density_lines(name, len(bases), window, loci_contract.record_density(len(bases), rows, window))
     return loci_text, density_text
 
 
-def _run(args, env=None, timeout=600):
-    r = subprocess.run([BIN] + [str(a) for a in args], capture_output=True, text=True, timeout=timeout, env=dict(os.environ, **(env or {})))
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r
-
-
-def _stages(path):
-    return json.loads(path.read_text())["stage_ms_summed_over_records"]
-
-
-def test_cli_loci_bed_and_density_bedgraph(tmp_path):
-    recs = []
-    for k in range(6):
-        s, _ = simulate_sequence(20_000 + 9_000 * k, 300 + k, 2, 30, n_block_rate=0.3, lower_rate=0.2)
-        recs.append((f"rec{k} description dropped", s))
-    fa = tmp_path / "in.fa"
-    write_fasta(str(fa), recs[:3] + [("vanishes", b"")] + recs[3:] + [("empty_last", b"")], width=70)
-    lead, _ = simulate_sequence(15_000, 77, 2, 30, lower_rate=0.3)
-    with open(fa, "rb") as f:
-        body = f.read()
-    with open(fa, "wb") as f:            # a nameless body before the first header
-        f.write(b"".join(lead[i:i + 50] + b"\n" for i in range(0, len(lead), 50)) + body)
-
+@pytest.fixture(scope="module")
+def nine(tmp_path_factory):
+    """the nine-record FASTA and a run without loci and density, once: its BED, masked FASTA and repeat FASTA, and the loci file and
+    the bedGraph that the contract makes of that BED"""
+    d = tmp_path_factory.mktemp("nine")
+    fa = d / "in.fa"
+    write_nine_records(fa, 300, 77)
     common = ["-i", fa, "-m", 2, "-M", 30]
-    bed0, masked0, repeats0 = tmp_path / "plain.bed", tmp_path / "plain_masked.fa", tmp_path / "plain_repeats.fa"
-    _run(common + ["-o", bed0, "--masked-fasta", masked0, "--repeat-fasta", repeats0, "--timing", tmp_path / "t0.json"])
+    bed0, masked0, repeats0 = d / "plain.bed", d / "plain_masked.fa", d / "plain_repeats.fa"
+    _run(common + ["-o", bed0, "--masked-fasta", masked0, "--repeat-fasta", repeats0, "--timing", d / "t0.json"])
     want_bed = bed0.read_text()
-    assert "loci" not in _stages(tmp_path / "t0.json") and "density" not in _stages(tmp_path / "t0.json")
+    assert "loci" not in _stages(d / "t0.json") and "density" not in _stages(d / "t0.json")
     assert len(want_bed.splitlines()) > 100
+    return types.SimpleNamespace(fa=fa, common=common, want_bed=want_bed, masked0=masked0, repeats0=repeats0,
+                                 expected=functools.lru_cache(None)(lambda gap, window: _expected(fa, want_bed, gap, window)))
 
+
+def test_cli_loci_bed_and_density_bedgraph(nine, tmp_path):
+    fa, common, want_bed, masked0, repeats0 = nine.fa, nine.common, nine.want_bed, nine.masked0, nine.repeats0
     runs = [(0, 10_000, []),
             (0, 10_000, ["--devices", "0,0", "--jobs", "2"]),
             (25, 1000, ["--loci-gap", "25", "--density-window", "1000"]),
@@ -197,7 +176,7 @@ def test_cli_loci_bed_and_density_bedgraph(tmp_path):
         bed, loci, graph, timing = tmp_path / f"r{k}.bed", tmp_path / f"r{k}.loci.bed", tmp_path / f"r{k}.bedgraph", tmp_path / f"t{k + 1}.json"
         _run(common + ["-o", bed, "--loci-bed", loci, "--density-bedgraph", graph, "--timing", timing] + extra)
         assert bed.read_text() == want_bed
-        want_loci, want_graph = _expected(fa, want_bed, gap, window)
+        want_loci, want_graph = nine.expected(gap, window)
         assert loci.read_text() == want_loci, (gap, extra)
         assert graph.read_text() == want_graph, (window, extra)
         assert 0 < len(want_loci.splitlines()) < len(want_bed.splitlines())
@@ -207,7 +186,25 @@ def test_cli_loci_bed_and_density_bedgraph(tmp_path):
     # one of the two alone: only its key
     _run(common + ["-o", tmp_path / "only.bed", "--density-bedgraph", tmp_path / "only.bedgraph", "--timing", tmp_path / "t9.json"])
     assert "density" in _stages(tmp_path / "t9.json") and "loci" not in _stages(tmp_path / "t9.json")
-    assert (tmp_path / "only.bedgraph").read_text() == _expected(fa, want_bed, 0, 10_000)[1]
+    assert (tmp_path / "only.bedgraph").read_text() == nine.expected(0, 10_000)[1]
+
+
+def test_cli_all_four_outputs_side_by_side(nine, tmp_path):
+    """the four row outputs in one run, the records dealt over two handle sets with two in flight on each: every file as when it is
+    written alone, and --timing names the six stages of every record and then the four outputs' in their order"""
+    bed, masked, repeats, loci, graph = (tmp_path / n for n in ("out.bed", "masked.fa", "repeats.fa", "loci.bed", "out.bedgraph"))
+    _run(nine.common + ["-o", bed, "--density-bedgraph", graph, "--loci-bed", loci, "--repeat-fasta", repeats, "--masked-fasta", masked,
+                        "--timing", tmp_path / "t.json", "--devices", "0,0", "--jobs", "2"])
+    assert bed.read_text() == nine.want_bed
+    by_name = rows_by_record(nine.want_bed)
+    rows = [(n, b, ribbit_amd.bed_intervals(by_name.get(n, ""))) for n, b in records(nine.fa)]
+    assert masked.read_bytes() == nine.masked0.read_bytes() == b"".join(b">" + n.encode() + b"\n" + masked_body(b, iv, "soft", 60) for n, b, iv in rows)
+    assert repeats.read_bytes() == nine.repeats0.read_bytes() == b"".join(repeat_entries(n, b, iv, 100) for n, b, iv in rows)
+    want_loci, want_graph = nine.expected(0, 10_000)
+    assert loci.read_text() == want_loci
+    assert graph.read_text() == want_graph
+    assert list(_stages(tmp_path / "t.json")) == ["load", "perfect", "substitutions", "anchored", "dispatch", "refine_and_bed",
+                                                  "mask", "repeats", "loci", "density"]
 
 
 def test_cli_record_refined_in_slices(tmp_path):

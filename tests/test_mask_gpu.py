@@ -1,20 +1,15 @@
 """The masked FASTA on the GPU (mask.hip through ribbit_hip_mask_record): Scanner.mask_record against the host twin and
 the numpy statement of the contract (tests/mask_contract.py), and ribbit-hip --masked-fasta end to end."""
-import json
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import ribbit_amd
 import segments
 from mask_contract import masked_body
+from cli_rows import records, rows_by_record, run as _run, stages as _stages, write_nine_records
 from ribbit_amd.simulate import simulate_sequence, write_fasta
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "ribbit_amd", "ribbit-hip")
 MODES = ("soft", "hard")
 
 
@@ -31,7 +26,7 @@ def _same(sc, seq, iv, mode, width):
 def test_edge_cases_match_host_twin_and_contract():
     with ribbit_amd.Scanner(2, 30) as sc:
         for length, width in [(0, 60), (0, 0), (7, 60), (120, 60), (180, 60), (37, 1), (1, 1), (95, 0), (64, 64), (65, 64), (100, 3),
-                              (300, 16), (300, 15), (300, 17)]:
+                              (300, 16), (300, 15), (300, 17)] + [(n, w) for n in (15, 16, 17, 31, 32, 33, 48) for w in (60, 5)]:
             seq = _seq(length, length * 7 + width)
             sc.load_record(seq)
             sets = [[], [(0, length)], [(3, 9), (5, 20)], [(-5, 4), (length - 2, length + 50)], [(50, 10), (20, 20)],
@@ -104,44 +99,19 @@ def test_mask_before_load_is_a_state_error():
             sc.mask_record([(0, 1)])
 
 
-def _rows_by_record(bed: str):
-    out = {}
-    for line in bed.splitlines(keepends=True):
-        out.setdefault(line.split("\t")[0], []).append(line)
-    return {k: "".join(v) for k, v in out.items()}
-
-
 def _expected(fa, bed, mode, width):
-    by_name = _rows_by_record(bed)
-    recs = [(n, b) for n, b, last in ribbit_amd.read_fasta(str(fa)) if n or b]
-    return b"".join(b">" + n.encode() + b"\n" + masked_body(b, ribbit_amd.bed_intervals(by_name.get(n, "")), mode, width) for n, b in recs)
-
-
-def _run(args, env=None, timeout=600):
-    r = subprocess.run([BIN] + [str(a) for a in args], capture_output=True, text=True, timeout=timeout, env=dict(os.environ, **(env or {})))
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r
+    by_name = rows_by_record(bed)
+    return b"".join(b">" + n.encode() + b"\n" + masked_body(b, ribbit_amd.bed_intervals(by_name.get(n, "")), mode, width) for n, b in records(fa))
 
 
 def test_cli_masked_fasta(tmp_path):
-    recs = []
-    for k in range(6):
-        s, _ = simulate_sequence(20_000 + 9_000 * k, 300 + k, 2, 30, n_block_rate=0.3, lower_rate=0.2)
-        recs.append((f"rec{k} description dropped", s))
     fa = tmp_path / "in.fa"
-    write_fasta(str(fa), recs[:3] + [("vanishes", b"")] + recs[3:] + [("empty_last", b"")], width=70)
-    lead, _ = simulate_sequence(15_000, 77, 2, 30, lower_rate=0.3)
-    with open(fa, "rb") as f:
-        body = f.read()
-    with open(fa, "wb") as f:            # a nameless body before the first header
-        f.write(b"".join(lead[i:i + 50] + b"\n" for i in range(0, len(lead), 50)) + body)
-    names = [n for n, _, _ in ribbit_amd.read_fasta(str(fa))]
-    assert names[0] == "" and names[-1] == "empty_last" and "vanishes" not in names
+    write_nine_records(fa, 300, 77)
 
     bed0 = tmp_path / "plain.bed"
     _run(["-i", fa, "-o", bed0, "-m", 2, "-M", 30, "--timing", tmp_path / "t0.json"])
     want_bed = bed0.read_text()
-    assert "mask" not in json.loads((tmp_path / "t0.json").read_text())["stage_ms_summed_over_records"]
+    assert "mask" not in _stages(tmp_path / "t0.json")
     runs = [("soft", 60, []), ("hard", 0, ["--mask", "hard", "--mask-width", "0"]),
             ("soft", 7, ["--mask", "soft", "--mask-width", "7", "--devices", "0,0", "--jobs", "2"])]
     for k, (mode, width, extra) in enumerate(runs):
@@ -149,7 +119,7 @@ def test_cli_masked_fasta(tmp_path):
         _run(["-i", fa, "-o", bed, "-m", 2, "-M", 30, "--masked-fasta", out, "--timing", tmp_path / f"t{k}.json"] + extra)
         assert bed.read_text() == want_bed
         assert out.read_bytes() == _expected(fa, want_bed, mode, width), (mode, width, extra)
-        assert "mask" in json.loads((tmp_path / f"t{k}.json").read_text())["stage_ms_summed_over_records"]
+        assert "mask" in _stages(tmp_path / f"t{k}.json")
 
 
 def test_cli_masked_fasta_refined_in_slices(tmp_path):

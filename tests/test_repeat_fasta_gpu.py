@@ -1,10 +1,6 @@
 """The repeat FASTA on the GPU (repeats.hip through ribbit_hip_repeat_sequences): Scanner.repeat_sequences against the host
 twin and the numpy statement of the contract (tests/repeat_contract.py), in batches of forced text budgets, and ribbit-hip
 --repeat-fasta end to end."""
-import json
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
@@ -12,12 +8,11 @@ import ribbit_amd
 import segments
 from mask_contract import masked_body
 from repeat_contract import repeat_entries
+from cli_rows import records as _records, rows_by_record as _rows_by_record, run as _run, stages as _stages, write_nine_records
 from ribbit_amd.simulate import simulate_sequence, write_fasta
 from test_repeat_fasta import I32_MAX, edge_rows
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "ribbit_amd", "ribbit-hip")
 
 
 def _seq(n, seed):
@@ -33,7 +28,7 @@ def _same(sc, name, seq, iv, flank):
 
 def test_edge_cases_match_host_twin_and_contract():
     with ribbit_amd.Scanner(2, 30) as sc:
-        for length in (0, 1, 15, 16, 17, 300):
+        for length in (0, 1, 15, 16, 17, 31, 32, 33, 47, 48, 300):
             seq = _seq(length, length + 3)
             sc.load_record(seq)
             for flank in (0, 1, 100, length, length + 1, I32_MAX):
@@ -122,17 +117,6 @@ def test_repeat_sequences_before_load_is_a_state_error():
             sc.repeat_sequences("c", [(0, 1)], -1)
 
 
-def _rows_by_record(bed: str):
-    out = {}
-    for line in bed.splitlines(keepends=True):
-        out.setdefault(line.split("\t")[0], []).append(line)
-    return {k: "".join(v) for k, v in out.items()}
-
-
-def _records(fa):
-    return [(n, b) for n, b, last in ribbit_amd.read_fasta(str(fa)) if n or b]
-
-
 def _expected_repeats(fa, bed, flank):
     by_name = _rows_by_record(bed)
     return b"".join(repeat_entries(n, b, ribbit_amd.bed_intervals(by_name.get(n, "")), flank) for n, b in _records(fa))
@@ -144,30 +128,9 @@ def _expected_masked(fa, bed):
                     for n, b in _records(fa))
 
 
-def _run(args, env=None, timeout=600):
-    r = subprocess.run([BIN] + [str(a) for a in args], capture_output=True, text=True, timeout=timeout, env=dict(os.environ, **(env or {})))
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r
-
-
-def _stages(path):
-    return json.loads(path.read_text())["stage_ms_summed_over_records"]
-
-
 def test_cli_repeat_fasta(tmp_path):
-    recs = []
-    for k in range(6):
-        s, _ = simulate_sequence(20_000 + 9_000 * k, 400 + k, 2, 30, n_block_rate=0.3, lower_rate=0.2)
-        recs.append((f"rec{k} description dropped", s))
     fa = tmp_path / "in.fa"
-    write_fasta(str(fa), recs[:3] + [("vanishes", b"")] + recs[3:] + [("empty_last", b"")], width=70)
-    lead, _ = simulate_sequence(15_000, 78, 2, 30, lower_rate=0.3)
-    with open(fa, "rb") as f:
-        body = f.read()
-    with open(fa, "wb") as f:            # a nameless body before the first header
-        f.write(b"".join(lead[i:i + 50] + b"\n" for i in range(0, len(lead), 50)) + body)
-    names = [n for n, _, _ in ribbit_amd.read_fasta(str(fa))]
-    assert names[0] == "" and names[-1] == "empty_last"
+    write_nine_records(fa, 400, 78)
 
     bed0 = tmp_path / "plain.bed"
     _run(["-i", fa, "-o", bed0, "-m", 2, "-M", 30, "--timing", tmp_path / "t0.json"])
