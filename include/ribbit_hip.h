@@ -677,12 +677,15 @@ int ribbit_host_perfect_runs_from_events(const RibbitScanParams *params, size_t 
                                          const uint64_t *counts, RibbitRun **runs, size_t *n);
 void ribbit_runs_free(RibbitRun *runs);
 
-/* Timing of the last call, milliseconds.  what: 0 pack kernel, 1 last scan kernel, 2 GPU side of
+/* Timing of the last call, milliseconds.  what: PACK the pack kernel, SCAN the last scan kernel, GPU the GPU side of
  * the last scan (kernel + pairing + state machine + sort + read-back), all by HIP events on the launch stream;
- * 3 everything after the pairing of the last window stage (device state machine, sort, read-back; wall clock);
- * 4 the host merge of the last window stage (wall clock); 5 that of the substitution stage when
- * ribbit_hip_seeds_anchored ran both stages; 6 / 7 the scan kernel of the substitution / anchored stage (HIP events; the
- * anchored stage runs as two kernels, 7 is both); 8 / 9 its planes kernel (anchors + composition) / its window-scan kernel. */
+ * HOST everything after the pairing of the last window stage (device state machine, sort, read-back; wall clock);
+ * MERGE the host merge of the last window stage (wall clock); SUBST_MERGE that of the substitution stage when
+ * ribbit_hip_seeds_anchored ran both stages; SUBST_SCAN / ANCHORED_SCAN the scan kernel of the substitution / anchored stage
+ * (HIP events; the anchored stage runs as two kernels, ANCHORED_SCAN is both); ANCHORED_PLANES / ANCHORED_WINDOW its planes
+ * kernel (anchors + composition) / its window-scan kernel. */
+enum { RIBBIT_TIME_PACK = 0, RIBBIT_TIME_SCAN = 1, RIBBIT_TIME_GPU = 2, RIBBIT_TIME_HOST = 3, RIBBIT_TIME_MERGE = 4, RIBBIT_TIME_SUBST_MERGE = 5,
+       RIBBIT_TIME_SUBST_SCAN = 6, RIBBIT_TIME_ANCHORED_SCAN = 7, RIBBIT_TIME_ANCHORED_PLANES = 8, RIBBIT_TIME_ANCHORED_WINDOW = 9 };
 int ribbit_hip_last_timing_ms(const RibbitHandle *h, int what, double *ms);
 /* Profiling aid (no effect on results): streams `nbytes` of the loaded record's ASCII buffer /
  * planes through calib_stream_read_kernel so that a PMC pass contains a launch with a known byte

@@ -71,10 +71,10 @@ int ribbit_hip_stage_calls_chunk(RibbitHandle *h, int stage, int64_t own_lo, int
         if (q0 < 0 || q0 + 7 >= own_lo) inexact = true;
     }
     DeviceCalls dc;
-    const int which = stage == RIBBIT_STAGE_SUBST ? 1 : 2;
-    if (which == 2 && (rc = prepare_anchored(h))) return rc;
-    if ((rc = window_stage_device(h, which, false, which == 1 ? rb::subst_seedlen_cutoff : rb::anchored_seedlen_cutoff, &dc, &cw))) return rc;
-    if (which == 2) h->rec.xa_on_device = true;
+    const bool anchored = stage == RIBBIT_STAGE_ANCHORED;
+    if (anchored && (rc = prepare_anchored(h))) return rc;
+    if ((rc = window_stage_device(h, stage, false, anchored ? rb::anchored_seedlen_cutoff : rb::subst_seedlen_cutoff, &dc, &cw))) return rc;
+    if (anchored) h->rec.xa_on_device = true;
     out->calls = dc.calls; out->n = dc.n;
     out->pend = dc.pend;
     out->tail_pend = dc.tail_pend;
@@ -92,10 +92,8 @@ int ribbit_host_merge_chunks(const RibbitScanParams *params, int64_t length,
                              const uint32_t *hi, const uint32_t *lo, const uint32_t *brk, size_t nwords,
                              const uint32_t *xa, size_t xa_stride, const RibbitChunkPart *parts, size_t nparts,
                              RibbitSeedLists *out) {
-    if (!params || !out || (nparts && !parts) || (length > 0 && (!hi || !lo || !brk))) return fail(RIBBIT_E_ARG, "null argument");
-    const size_t need = (size_t)(length / 32 + 1) + (size_t)(params->max_motif + 2) / 32 + 2;
-    if (nwords < need) return fail(RIBBIT_E_ARG, "planes too short: %zu words, need %zu (zero padding past the record)", nwords, need);
-    if (xa && xa_stride < (size_t)(length / 32 + 1)) return fail(RIBBIT_E_ARG, "composed planes (xa) too short");
+    if (!out || (nparts && !parts)) return fail(RIBBIT_E_ARG, "null argument");
+    if (const int bad = check_caller_planes(params, length, hi, lo, brk, nwords, xa, xa_stride)) return bad;
     for (size_t p = 0; p < nparts; ++p) {
         const RibbitChunkPart &pt = parts[p];
         if ((pt.n_runs && !pt.runs) || (pt.n_halves && !pt.halves) || (pt.subst.n && !pt.subst.calls) || (pt.anchored.n && !pt.anchored.calls) ||
@@ -107,16 +105,8 @@ int ribbit_host_merge_chunks(const RibbitScanParams *params, int64_t length,
     // (the checks above only read: what follows is what allocates, and `out` is now safe to free)
     const int ret = guarded("the merge of the chunks", [&]() -> int {
         rb::HostPlanes hp;
-        hp.resize(length, nwords);
-        std::memcpy(hp.hi.data(), hi, nwords * sizeof(uint32_t));
-        std::memcpy(hp.lo.data(), lo, nwords * sizeof(uint32_t));
-        std::memcpy(hp.brk.data(), brk, nwords * sizeof(uint32_t));
         rb::SeedLists sl;
-        sl.length = length;
-        sl.min_motif = params->min_motif;
-        sl.max_motif = params->max_motif;
-        sl.min_shift = (params->min_motif > 2) ? params->min_motif - 2 : 1;
-        sl.range_count = [&hp](int shift, int start, int end) { return hp.range_count(shift, start, end); };
+        lists_over_caller_planes(params, length, hi, lo, brk, nwords, hp, sl);
         const unsigned threads = rb::host_thread_count(0);
 
         // ---- perfect stage: the chunks' complete runs, and the runs a chunk edge cut, paired across chunks
@@ -222,10 +212,7 @@ int ribbit_host_merge_chunks(const RibbitScanParams *params, int64_t length,
         hp.xa_stride = xa ? (int64_t)xa_stride : 0;
         hp.xa_m_lo = params->min_motif;
         hp.xa_m_hi = params->max_motif;
-        sl.range_count = [&hp](int shift, int start, int end) {
-            return hp.has_xa(shift) ? hp.range_count_xa(shift, start, end) : hp.range_count(shift, start, end);
-        };
-        if (hp.xa_stored()) { sl.plane_words = hp.xa_words(); sl.plane_stride = hp.xa_stride; sl.plane_lo = hp.xa_m_lo; sl.plane_hi = hp.xa_m_hi; }
+        use_composed_planes(sl, &hp);
         rb::SeedVec dispatch;
         {
             Joined j;
@@ -234,19 +221,7 @@ int ribbit_host_merge_chunks(const RibbitScanParams *params, int64_t length,
             rb::merge_anchored_stage(sl, j.kc, threads, &st);
             rb::dispatch_order_ranges(sl, st.cut_pos, threads, dispatch);
         }
-        auto give = [](const rb::SeedVec &v, RibbitSeed **p, size_t *n) {
-            *n = v.size();
-            *p = (RibbitSeed *)std::malloc(std::max<size_t>(v.size(), 1) * sizeof(RibbitSeed));
-            if (*p && !v.empty()) std::memcpy(*p, v.data(), v.size() * sizeof(RibbitSeed));
-            return *p != nullptr;
-        };
-        if (!give(sl.perfect, &out->perfect, &out->n_perfect) || !give(sl.subst, &out->subst, &out->n_subst) ||
-            !give(sl.anchored, &out->anchored, &out->n_anchored) || !give(dispatch, &out->dispatch, &out->n_dispatch)) {
-            ribbit_seed_lists_free(out);
-            return fail(RIBBIT_E_NOMEM, "out of host memory");
-        }
-        out->guard_hits = sl.guard_hits;
-        return RIBBIT_OK;
+        return give_seed_lists(sl, dispatch, out);
     });
     if (ret) ribbit_seed_lists_free(out);
     return ret;

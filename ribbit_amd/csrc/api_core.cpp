@@ -124,13 +124,13 @@ int pack_loaded_ascii(RibbitHandle *h, const uint8_t *dev_ascii, int64_t length)
     if ((rc = h->d_hi.ensure((size_t)h->total_words))) return rc;
     if ((rc = h->d_lo.ensure((size_t)h->total_words))) return rc;
     if ((rc = h->d_brk.ensure((size_t)h->total_words))) return rc;
-    if (h->timing) HIP_TRY(hipEventRecord(h->ev[0], h->stream));
-    if ((rc = h->d_counters.ensure(rb::EV_COUNTER_WORDS))) return rc;
-    rb::launch_pack(dev_ascii, length, h->d_hi.p, h->d_lo.p, h->d_brk.p, h->total_words, h->d_counters.p, rb::EV_COUNTER_WORDS, h->stream);
+    if (h->timing) HIP_TRY(hipEventRecord(h->timers.begin[RIBBIT_TIME_PACK], h->stream));
+    if ((rc = h->pb.d_counters.ensure(rb::EV_COUNTER_WORDS))) return rc;
+    rb::launch_pack(dev_ascii, length, h->d_hi.p, h->d_lo.p, h->d_brk.p, h->total_words, h->pb.d_counters.p, rb::EV_COUNTER_WORDS, h->stream);
     h->counters_clean = true;      // until a scan kernel runs
     HIP_TRY(hipGetLastError());
-    if (h->timing) HIP_TRY(hipEventRecord(h->ev[1], h->stream));
-    h->have_timing[0] = h->timing;
+    if (h->timing) HIP_TRY(hipEventRecord(h->timers.end[RIBBIT_TIME_PACK], h->stream));
+    h->timers.have[RIBBIT_TIME_PACK] = h->timing;
     // the previous record's seed lists are emptied, not freed: giving half a gigabyte back to the system took 98 ms after a
     // chromosome (munmap walks every page), and the next record's merges then faulted the same pages in again
     h->lists.perfect.clear(); h->lists.subst.clear(); h->lists.anchored.clear();
@@ -238,9 +238,11 @@ int ribbit_hip_open(const RibbitScanParams *params, int device, RibbitHandle **o
     // part is inferred, not observed.
     if (err == hipSuccess) err = h->ev_up.create(hipEventDisableTiming);
     if (err == hipSuccess) err = h->ev_busy.create(hipEventDisableTiming);
-    for (int i = 0; i < 4 && err == hipSuccess; ++i) err = h->ev_stage[i / 2][i % 2].create();
-    if (err == hipSuccess) err = h->ev_planes.create();
-    for (int i = 0; i < 6 && err == hipSuccess; ++i) err = h->ev[i].create();
+    for (OwnedEvent *e : {&h->win[RIBBIT_STAGE_SUBST].ev_begin, &h->win[RIBBIT_STAGE_SUBST].ev_end, &h->win[RIBBIT_STAGE_ANCHORED].ev_begin,
+                          &h->win[RIBBIT_STAGE_ANCHORED].ev_end, &h->ev_planes})
+        if (err == hipSuccess) err = e->create();
+    for (int t = 0; t < 3 && err == hipSuccess; ++t)
+        if ((err = h->timers.begin[t].create()) == hipSuccess) err = h->timers.end[t].create();
     if (err != hipSuccess) {
         delete h;      // (with what it had created)
         return fail(RIBBIT_E_DEVICE, "device setup failed: %s", hipGetErrorString(err));
@@ -343,7 +345,7 @@ int ribbit_hip_debug_last_scan_split(RibbitHandle *h, int32_t kernel, int32_t *g
 int ribbit_hip_set_timing(RibbitHandle *h, int32_t enabled) {
     if (!h) return fail(RIBBIT_E_ARG, "null argument");
     h->timing = enabled != 0;
-    if (!h->timing) h->have_timing[0] = h->have_timing[1] = h->have_timing[2] = false;
+    if (!h->timing) h->timers.have[RIBBIT_TIME_PACK] = h->timers.have[RIBBIT_TIME_SCAN] = h->timers.have[RIBBIT_TIME_GPU] = false;
     return RIBBIT_OK;
 }
 
@@ -436,31 +438,29 @@ int ribbit_hip_packed_plane(RibbitHandle *h, int which, uint32_t *out_words) { r
 
 int ribbit_hip_last_timing_ms(const RibbitHandle *h, int what, double *ms) { return guarded("the timing query", [&]() -> int {
     if (!h || !ms) return fail(RIBBIT_E_ARG, "null argument");
-    if (what == 3) { *ms = h->host_ms; return RIBBIT_OK; }
-    if (what == 4) { *ms = h->merge_ms; return RIBBIT_OK; }
-    if (what == 5) { *ms = h->subst_merge_ms; return RIBBIT_OK; }
-    if (what == 6 || what == 7) {
-        if (!h->have_stage_timing[what - 6]) return fail(RIBBIT_E_STATE, "that stage's kernel has not run on this handle");
-        float f = 0.f;
-        HIP_TRY(hipEventSynchronize(h->ev_stage[what - 6][1]));
-        HIP_TRY(hipEventElapsedTime(&f, h->ev_stage[what - 6][0], h->ev_stage[what - 6][1]));
-        *ms = f;
-        return RIBBIT_OK;
+    if (what == RIBBIT_TIME_HOST) { *ms = h->host_ms; return RIBBIT_OK; }
+    if (what == RIBBIT_TIME_MERGE) { *ms = h->merge_ms; return RIBBIT_OK; }
+    if (what == RIBBIT_TIME_SUBST_MERGE) { *ms = h->subst_merge_ms; return RIBBIT_OK; }
+    // the interval [from, to] of HIP events, read once `last` (the latest of the interval's stage) has happened
+    hipEvent_t from, to, last;
+    const RibbitHandle::WindowStage &anchored = h->win[RIBBIT_STAGE_ANCHORED];
+    if (what == RIBBIT_TIME_SUBST_SCAN || what == RIBBIT_TIME_ANCHORED_SCAN) {
+        const RibbitHandle::WindowStage &st = what == RIBBIT_TIME_SUBST_SCAN ? h->win[RIBBIT_STAGE_SUBST] : anchored;
+        if (!st.have_timing) return fail(RIBBIT_E_STATE, "that stage's kernel has not run on this handle");
+        from = st.ev_begin; to = last = st.ev_end;
+    } else if (what == RIBBIT_TIME_ANCHORED_PLANES || what == RIBBIT_TIME_ANCHORED_WINDOW) {      // the anchored stage's two kernels
+        if (!anchored.have_timing || !h->planes_timing_valid) return fail(RIBBIT_E_STATE, "the anchored stage has not run as two kernels on this handle");
+        from = what == RIBBIT_TIME_ANCHORED_PLANES ? anchored.ev_begin : h->ev_planes;
+        to = what == RIBBIT_TIME_ANCHORED_PLANES ? h->ev_planes : anchored.ev_end;
+        last = anchored.ev_end;
+    } else {
+        if (what < 0 || what > RIBBIT_TIME_ANCHORED_WINDOW) return fail(RIBBIT_E_ARG, "what must be 0..9");
+        if (!h->timers.have[what]) return fail(RIBBIT_E_STATE, "no timing recorded yet");
+        from = h->timers.begin[what]; to = last = h->timers.end[what];
     }
-    if (what == 8 || what == 9) {      // the anchored stage's two kernels: 8 planes (anchors + composition), 9 window scan of the planes
-        if (!h->have_stage_timing[1] || !h->planes_timing_valid) return fail(RIBBIT_E_STATE, "the anchored stage has not run as two kernels on this handle");
-        float f = 0.f;
-        HIP_TRY(hipEventSynchronize(h->ev_stage[1][1]));
-        if (what == 8) HIP_TRY(hipEventElapsedTime(&f, h->ev_stage[1][0], h->ev_planes));
-        else HIP_TRY(hipEventElapsedTime(&f, h->ev_planes, h->ev_stage[1][1]));
-        *ms = f;
-        return RIBBIT_OK;
-    }
-    if (what < 0 || what > 9) return fail(RIBBIT_E_ARG, "what must be 0..9");
-    if (!h->have_timing[what]) return fail(RIBBIT_E_STATE, "no timing recorded yet");
     float f = 0.f;
-    HIP_TRY(hipEventSynchronize(h->ev[2 * what + 1]));
-    HIP_TRY(hipEventElapsedTime(&f, h->ev[2 * what], h->ev[2 * what + 1]));
+    HIP_TRY(hipEventSynchronize(last));
+    HIP_TRY(hipEventElapsedTime(&f, from, to));
     *ms = f;
     return RIBBIT_OK;
 }); }
@@ -470,12 +470,12 @@ int ribbit_hip_debug_stream_read(RibbitHandle *h, int64_t nbytes, int64_t *bytes
     if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
     int rc;
     if ((rc = bind_device(h))) return rc;
-    if ((rc = h->d_counters.ensure(rb::EV_COUNTER_WORDS))) return rc;
+    if ((rc = h->pb.d_counters.ensure(rb::EV_COUNTER_WORDS))) return rc;
     // the event buffer is the largest resident allocation; fall back to the hi plane
     const uint32_t *src = h->d_events.p ? (const uint32_t *)h->d_events.p : h->d_hi.p;
     const int64_t avail = h->d_events.p ? (int64_t)h->d_events.cap * 8 : h->total_words * 4;
     const int64_t n = std::max<int64_t>(0, std::min(nbytes, avail)) / 4;
-    rb::launch_calib_stream_read(src, n, h->d_counters.p + rb::EV_SUMMARY + 8, h->stream);
+    rb::launch_calib_stream_read(src, n, h->pb.d_counters.p + rb::EV_SUMMARY + 8, h->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(h->stream));
     *bytes_read = n * 4;

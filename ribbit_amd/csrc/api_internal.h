@@ -2,6 +2,7 @@
 // the handle, its device / page-locked buffers, error reporting, and the internal steps that more than one of those files
 // takes.  Until round 4 all of this was one 3,200-line api.cpp; it is now
 //   api_core.cpp        handles, streams, loading a record (pack), timers, plane queries
+//   api_events.cpp      the event pass every scan takes: region sizes, pairing on the device, what it publishes, growth on overflow
 //   api_perfect.cpp     the perfect stage: scan, device-side pairing, runs, calls, seeds; its chunk form
 //   api_window.cpp      the substitution and anchored stages: scans, streak pairing, window state machines, merges, dispatch order
 //   api_chunks.cpp      one chunk of a longer record (window stages) and the merging rank's half
@@ -171,7 +172,18 @@ inline double now_ms() {
     return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
 
-enum Stage { STAGE_NONE = 0, STAGE_PERFECT = 1, STAGE_SUBST = 2, STAGE_ANCHORED = 3 };
+enum Stage { STAGE_NONE = 0, STAGE_PERFECT = 1, STAGE_SUBST = 2, STAGE_ANCHORED = 3 };      // how far the seed lists have come (rec.stage_done)
+
+// What the device-side pairing of one scan's events works in (api_events.cpp: pair_prepare sizes it, enqueue_pairing uses it):
+// the handle's, and ribbit_hip_debug_pair_events' own.
+struct PairBufs {
+    DevBuf<uint32_t> d_counters;           // the scan's region counters (also zeroed by the pack kernel)
+    DevBuf<uint64_t> d_pair_table;
+    DevBuf<uint32_t> d_run_base, d_pair_partial, d_pair_status;
+    DevBuf<RibbitRun> d_halves;
+    PinnedBuf<uint32_t> h_pub;             // region counters + pairing status, written by the GPU (pair_publish_kernel)
+    uint32_t *h_pub_dev = nullptr;         // the same memory as the device sees it
+};
 
 // ---- shared by the host sides of the row outputs (api_mask.cpp, api_repeats.cpp, api_loci.cpp)
 
@@ -210,17 +222,19 @@ using namespace rbapi;
 struct RibbitHandle {
     // ORDER MATTERS HERE, and only here: members are destroyed last to first, and the handle gives up its buffers first, then its
     // events, then its streams.  So the streams are declared first, the events second, and everything that owns memory (DevBuf,
-    // PinnedBuf, bed_raw) after them.  ~RibbitHandle (api_core.cpp) runs before any member goes: it drains the streams.
+    // PinnedBuf, bed_raw; `win`, with the events of its stages) after them.  ~RibbitHandle (api_core.cpp) runs before any member goes: it drains the streams.
     OwnedStream own_stream;
     OwnedStream copy_stream;             // post stream of the perfect scan: pairing kernels and result copies, so that they overlap
                                          // the next record's kernels when several handles share `stream`
     OwnedStream up_stream;               // uploads: the next record's bases travel while this record's kernels run (created by the first upload)
     OwnedEvent ev_ready;                 // pairing done, counters and status on the host
-    OwnedEvent ev[6];                    // 0/1 pack, 2/3 scan kernel, 4/5 whole GPU side of the last scan
+    struct Timers {                      // timers RIBBIT_TIME_PACK, RIBBIT_TIME_SCAN (the last scan's kernel) and RIBBIT_TIME_GPU (its whole GPU side),
+        OwnedEvent begin[3], end[3];     // indexed by those ids; have: both events of the interval have been recorded
+        bool have[3] = {false, false, false};
+    } timers;
     OwnedEvent ev_xa;                    // the copy of the composed planes has landed
     OwnedEvent ev_ssw;                   // orders the longest alignment class (on the copy stream) against the compute stream
     OwnedEvent ev_up, ev_busy;
-    OwnedEvent ev_stage[2][2];           // scan kernel of the substitution [0] / anchored [1] stage
     OwnedEvent ev_planes;                // between the two kernels of the anchored stage (planes | window scan)
 
     RibbitHandle() = default;
@@ -245,7 +259,6 @@ struct RibbitHandle {
         size_t coverage_n = 0;
         rb::ScanSplit last_split[RIBBIT_SCAN_KERNELS];   // the split each scan kernel last ran with on the loaded record
     } rec;
-    bool have_timing[3] = {false, false, false};
     bool timing = true;           // record the HIP events behind ribbit_hip_last_timing_ms (each costs a barrier packet on the stream)
     double host_ms = 0.0;         // post-processing of the last scan after its pairing (device state machine, sort, read-back), wall clock
     double merge_ms = 0.0;        // sequential host merge of the last window stage, wall clock
@@ -258,7 +271,6 @@ struct RibbitHandle {
     DevBuf<uint8_t> d_ascii;
     DevBuf<uint32_t> d_hi, d_lo, d_brk;
     DevBuf<uint64_t> d_events, d_dense;
-    DevBuf<uint32_t> d_counters;
     DevBuf<uint32_t> d_query;
     DevBuf<uint32_t> d_xa;             // composed planes XA_m, motif-major
     int64_t xa_stride = 0;
@@ -272,24 +284,19 @@ struct RibbitHandle {
 
     // ordered view of the last event collection
     int64_t last_event_count = 0;
-    uint32_t produced = 0;
     std::vector<uint64_t> chunk_table;   // (offset, count) per (motif, tile)
     size_t table_ntile = 0;
 
     std::vector<RibbitRun> runs;          // chunk-local pairing (multi-GPU path)
     // device-side pairing of the perfect scan: scratch + the pinned run list it lands in
-    DevBuf<uint64_t> d_pair_table;
-    DevBuf<uint32_t> d_run_base, d_pair_partial, d_pair_status;
-    PinnedBuf<uint32_t> h_pub;             // region counters + pairing status, written by the GPU (pair_publish_kernel)
-    uint32_t *h_pub_dev = nullptr;         // the same memory as the device sees it
+    PairBufs pb;
     PinnedBuf<RibbitRun> h_runs, h_halves;
     rb::PairLaunch pair{};                // the perfect scan in flight (perfect_begin .. perfect_finish)
     bool pair_pending = false;
     size_t debug_first_cap = 0;           // ribbit_hip_debug_set_event_capacity: first guess of the event capacity (tests of the overflow path)
     int32_t debug_split[RIBBIT_SCAN_KERNELS] = {};   // ribbit_hip_debug_set_scan_split: motifs per block of each scan kernel (0 = automatic)
-    bool counters_clean = false;          // d_counters zeroed by the pack kernel and not used since
+    bool counters_clean = false;          // pb.d_counters zeroed by the pack kernel and not used since
     bool copy_pending = false;            // result copies enqueued but not yet waited for (ribbit_hip_scan_perfect_end with wait = 0)
-    DevBuf<RibbitRun> d_halves;
     size_t n_runs = 0, n_halves = 0;
     // window stages on the device (window_stage.hip): scratch of the streak -> call pipeline and its pinned results
     DevBuf<uint32_t> d_eval, d_first_rev, d_word_tmp, d_last_word, d_bitmap, d_edge_tmp, d_edge_end1, d_ws_counters;
@@ -299,10 +306,15 @@ struct RibbitHandle {
     bool dropmap_valid = false;           // the last anchored scan ran with the filter
     DevBuf<RibbitCall> d_flush;
     DevBuf<uint8_t> d_scratch;
-    // results of the substitution [0] and anchored [1] stage, page-locked: both stages' kernels run before either merge
-    PinnedBuf<RibbitCall> h_calls_[2], h_flush_[2];
-    PinnedBuf<int32_t> h_pend_[2];
-    PinnedBuf<uint32_t> h_ws_[2];
+    // per window stage, indexed by RIBBIT_STAGE_SUBST / RIBBIT_STAGE_ANCHORED (entry RIBBIT_STAGE_PERFECT stays empty): its results,
+    // page-locked (both stages' kernels run before either merge), and the events around its scan kernel(s)
+    struct WindowStage {
+        PinnedBuf<RibbitCall> h_calls, h_flush;
+        PinnedBuf<int32_t> h_pend;
+        PinnedBuf<uint32_t> h_ws;
+        OwnedEvent ev_begin, ev_end;
+        bool have_timing = false;
+    } win[3];
     PinnedBuf<uint32_t> h_xa;          // host copy of the composed planes (rb::HostPlanes::xa_view points here)
     // the anchored stage's merge as device work (api_merge.cpp, anchored_merge.hip): the lists, the ranges and what they leave
     struct MergeBufs {
@@ -349,8 +361,7 @@ struct RibbitHandle {
     std::string host_ascii;   // the record's bases on the host when they had to be fetched back (refinement slices them for the aligner)
     bool host_ascii_valid = false;
     const char *host_bases = nullptr;     // where refinement reads the bases: the caller's page-locked buffer (load_record_pinned) or host_ascii
-    bool planes_timing_valid = false;     // ev_stage[1][0] .. ev_planes .. ev_stage[1][1] bracket the two kernels of one run
-    bool have_stage_timing[2] = {false, false};
+    bool planes_timing_valid = false;     // the anchored stage's ev_begin .. ev_planes .. ev_end bracket the two kernels of one run
     const uint8_t *dev_ascii_src = nullptr;
     std::string bed;
     std::unique_ptr<char[], FreeDeleter> bed_raw;   // the text of the last refinement when its pieces were joined (join_pieces: storage the copying threads touch first)
@@ -426,7 +437,19 @@ int bind_device(const RibbitHandle *h);
 int is_gfx950(int device);
 int pack_loaded_ascii(RibbitHandle *h, const uint8_t *dev_ascii, int64_t length);
 int ensure_host_planes(RibbitHandle *h);
-int collect_events(RibbitHandle *h, int which);
+// api_events.cpp: the steps of the event pass, in the order a scan takes them
+inline size_t dropmap_words(int64_t length) { return (size_t)(length / 32 + 1) + 1024; }      // of the anchored scan's group filter
+int pair_prepare(RibbitHandle *h, PairBufs &pb, int64_t length, int64_t own_lo, int64_t own_hi, int64_t pos_offset, rb::PairLaunch &pr);
+size_t first_event_cap(const RibbitHandle *h, size_t per_base_x4);
+int grow_event_cap(int attempt, uint32_t worst, size_t *cap);
+int event_room(RibbitHandle *h, size_t *cap, rb::PairLaunch *pr);
+int zero_counters(RibbitHandle *h, bool even_if_clean = false);
+rb::PerfectLaunch scan_launch_args(const RibbitHandle *h, size_t cap, int kernel);
+int enqueue_pairing(PairBufs &pb, const rb::PairLaunch &pr, const uint64_t *d_events, uint64_t *d_dense, size_t cap, hipStream_t stream);
+struct Published { uint32_t worst = 0; uint64_t produced = 0; };
+Published read_published(const PairBufs &pb);
+int pairing_verdict(const PairBufs &pb, uint64_t produced, const char *noun, size_t *n, size_t *n_halves);
+int collect_perfect_events(RibbitHandle *h);
 rb::EventSource event_source(const RibbitHandle *h);
 int perfect_wait(RibbitHandle *h);
 int perfect_enqueue(RibbitHandle *h, size_t cap);
@@ -438,8 +461,8 @@ int run_perfect_scan_range(RibbitHandle *h, int64_t own_lo, int64_t own_hi, int6
 int run_perfect_scan(RibbitHandle *h);
 int build_perfect_calls(RibbitHandle *h);
 int advance_to_perfect(RibbitHandle *h);
-int scan_and_pair_streaks(RibbitHandle *h, int which, uint32_t *n_streaks, int (*filter_min_span)(int) = nullptr);
-int window_stage_device(RibbitHandle *h, int which, bool full, int (*min_span)(int), DeviceCalls *out, ChunkWindow *cw = nullptr);
+int scan_and_pair_streaks(RibbitHandle *h, int stage /* RIBBIT_STAGE_SUBST | RIBBIT_STAGE_ANCHORED */, uint32_t *n_streaks, int (*filter_min_span)(int) = nullptr);
+int window_stage_device(RibbitHandle *h, int stage, bool full, int (*min_span)(int), DeviceCalls *out, ChunkWindow *cw = nullptr);
 void full_calls_from_device(const DeviceCalls &dc, rb::CallVec &calls);
 int build_subst_calls(RibbitHandle *h);
 void subst_merge(RibbitHandle *h, const DeviceCalls *dc);
@@ -454,6 +477,11 @@ int xa_wait_host(RibbitHandle *h);
 int build_anchored_calls(RibbitHandle *h);
 void print_anchored_merge_profile(size_t seeds, const rb::MergeStats &st, double dispatch_ms, unsigned dispatch_ranges);
 int advance_to_anchored(RibbitHandle *h);
+// set-up and hand-over of the host-only entry points (ribbit_host_replay_calls, ribbit_host_merge_chunks), api_window.cpp
+int check_caller_planes(const RibbitScanParams *params, int64_t length, const uint32_t *hi, const uint32_t *lo, const uint32_t *brk, size_t nwords, const uint32_t *xa, size_t xa_stride);
+void lists_over_caller_planes(const RibbitScanParams *params, int64_t length, const uint32_t *hi, const uint32_t *lo, const uint32_t *brk, size_t nwords, rb::HostPlanes &hp, rb::SeedLists &sl);
+void use_composed_planes(rb::SeedLists &sl, const rb::HostPlanes *hp);
+int give_seed_lists(const rb::SeedLists &sl, const rb::SeedVec &dispatch, RibbitSeedLists *out);
 int build_longest_runs(RibbitHandle *h);
 int best_rows_of(RibbitHandle *h, const RibbitRefineParams &prm, const rb::SeedVec &seeds, const int32_t *longest, int32_t *best);
 int build_best_rows(RibbitHandle *h, const RibbitRefineParams &prm);

@@ -6,50 +6,32 @@ namespace rbapi {
 
 // ---- window stages on the device ---------------------------------------------------------------------
 // scan kernel -> pass-streak START / END events (left in their regions) -> pairing kernels -> one 16-byte record per
-// streak, motif-major by start, in d_dense.  which: 1 window scan (1 mismatch), 2 fused anchored scan.
+// streak, motif-major by start, in d_dense: the event pass of api_events.cpp around the window scan (1 mismatch) of
+// RIBBIT_STAGE_SUBST or the two kernels of RIBBIT_STAGE_ANCHORED.
 // filter (anchored scan only): groups of pass-streaks whose call cannot pass min_span leave no events (kernels.hip, "group
 // filter"); their ends are left in h->d_dropmap for window_stage_device.
-int scan_and_pair_streaks(RibbitHandle *h, int which, uint32_t *n_streaks, int (*filter_min_span)(int)) {
+int scan_and_pair_streaks(RibbitHandle *h, int stage, uint32_t *n_streaks, int (*filter_min_span)(int)) {
     int rc;
     if ((rc = bind_device(h))) return rc;
     if (h->copy_pending && (rc = perfect_wait(h))) return rc;      // d_dense / d_events are shared with the perfect stage
-    if ((rc = h->d_counters.ensure(rb::EV_COUNTER_WORDS))) return rc;
-    if ((rc = h->d_pair_status.ensure(rb::PAIR_STATUS_WORDS))) return rc;
-    if (!h->h_pub.p) {
-        if ((rc = h->h_pub.ensure(rb::EV_SHARDS + rb::PAIR_STATUS_WORDS))) return rc;
-        HIP_TRY(hipHostGetDevicePointer((void **)&h->h_pub_dev, h->h_pub.p, 0));
-    }
-    rb::PairLaunch pr{};
-    pr.m_lo = (uint32_t)h->params.min_motif;
-    pr.nm = (uint32_t)(h->params.max_motif - h->params.min_motif + 1);
     // the anchored stage runs as two kernels: the planes (anchors + composition), then the window scan of the planes (kernels.hip).
     // (The fused form of rounds 1-2 -- 256 VGPRs, two waves per SIMD, 3.3 against 2.3 ms per 100 Mbp -- is gone from the product
     // since round 4; DESIGN.md 4 has its measurements.)
-    pr.tile_bases = (uint32_t)rb::TILE_BASES;
-    pr.ntile = (uint32_t)(h->length / pr.tile_bases + 1);
-    pr.own_lo = 0; pr.own_hi = INT64_MAX; pr.pos_offset = 0;
-    const size_t entries = (size_t)pr.nm * pr.ntile;
-    if (entries > 0xfffffff0u) return fail(RIBBIT_E_ARG, "record too long for %u motif sizes", pr.nm);
-    if ((rc = h->d_pair_table.ensure(entries))) return rc;
-    if ((rc = h->d_run_base.ensure(entries))) return rc;
-    if ((rc = h->d_pair_partial.ensure(entries / 1024 + 2))) return rc;
-    if ((rc = h->d_halves.ensure(2 * (size_t)pr.nm))) return rc;
-    const bool filter = which == 2 && filter_min_span != nullptr && std::getenv("RIBBIT_NO_GROUP_FILTER") == nullptr;
+    const bool subst = stage == RIBBIT_STAGE_SUBST;
+    RibbitHandle::WindowStage &st = h->win[stage];
+    rb::PairLaunch pr{};
+    if ((rc = pair_prepare(h, h->pb, h->length, 0, INT64_MAX, 0, pr))) return rc;
+    const bool filter = !subst && filter_min_span != nullptr && std::getenv("RIBBIT_NO_GROUP_FILTER") == nullptr;
     // typical event densities on repeat-rich sequence: 0.25 per base (1-mismatch windows); anchored windows 3.7 at 99 motif
     // sizes without the group filter (growing with the motif sizes), and 1.3 (99 sizes) .. 1.6 (499) with it: the filter drops
     // nearly everything the large motifs add.  A too small first guess costs a second launch of the window scan; a too large
     // one costs memory -- until round 4 the filtered scan was sized like the unfiltered one, which at -M 500 meant 2 x 34 GB for
     // 3.3 GB of events, and on a box whose memory had just been used two seconds of the driver clearing it.
     // (1-mismatch windows at 499 motif sizes: 0.49 per base, and the profile of round 4 showed the scan launched twice)
-    const size_t nm_all = (size_t)(h->params.max_motif - h->params.min_motif + 1);
-    const size_t per_base_x4 = which == 1 ? std::max<size_t>(2, nm_all / 100) : filter ? 10 : std::max<size_t>(16, nm_all / 6);
-    size_t cap = std::max<size_t>((size_t)1 << 20, (size_t)h->length * per_base_x4 / 4);
-    cap = std::max(cap, h->d_events.cap);
-    if (h->debug_first_cap) cap = h->debug_first_cap;
+    size_t cap = first_event_cap(h, subst ? std::max<size_t>(2, pr.nm / 100) : filter ? 10 : std::max<size_t>(16, pr.nm / 6));
     const rb::DevicePlanes pl = h->planes();
-    uint64_t produced = 0;
+    Published pub;
     bool first_attempt_fit = false;
-    const size_t drop_words = (size_t)(h->length / 32 + 1) + 1024;
     h->dropmap_valid = false;
     if (filter) {
         // positions a group must span for its call to be able to pass: the call's length is the group's span + 7
@@ -58,87 +40,63 @@ int scan_and_pair_streaks(RibbitHandle *h, int which, uint32_t *n_streaks, int (
             const int t = std::min(filter_min_span((int)(pr.m_lo + mi)), rb::GROUP_FILTER_MAX + 7) - 7;
             tj[mi] = t > 1 ? t : 0;
         }
-        if ((rc = h->d_tj.ensure(pr.nm)) || (rc = h->d_dropmap.ensure(drop_words))) return rc;
+        if ((rc = h->d_tj.ensure(pr.nm)) || (rc = h->d_dropmap.ensure(dropmap_words(h->length)))) return rc;
         HIP_TRY(hipMemcpyAsync(h->d_tj.p, tj.data(), pr.nm * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));       // tj is a local
     }
     for (int attempt = 0;; ++attempt) {
-        cap = std::min<size_t>((cap + rb::EV_SHARDS - 1) / rb::EV_SHARDS * rb::EV_SHARDS, 0xffffff00u);
-        if ((rc = h->d_events.ensure(cap))) return rc;
-        if ((rc = h->d_dense.ensure(cap))) return rc;          // cap / 2 streak records of 16 bytes
-        if (filter) HIP_TRY(hipMemsetAsync(h->d_dropmap.p, 0, drop_words * sizeof(uint32_t), h->stream));
-        HIP_TRY(hipEventRecord(h->ev[4], h->stream));
-        if (!h->counters_clean) HIP_TRY(hipMemsetAsync(h->d_counters.p, 0, rb::EV_COUNTER_WORDS * sizeof(uint32_t), h->stream));
-        h->counters_clean = false;
-        rb::PerfectLaunch pp;
-        pp.m_lo = h->params.min_motif;
-        pp.m_hi = h->params.max_motif;
-        pp.ev_cap = (uint32_t)cap;
-        pr.region_cap = pp.ev_cap / (uint32_t)rb::EV_SHARDS;
-        HIP_TRY(hipEventRecord(h->ev[2], h->stream));
+        if ((rc = event_room(h, &cap, &pr))) return rc;
+        if (filter) HIP_TRY(hipMemsetAsync(h->d_dropmap.p, 0, dropmap_words(h->length) * sizeof(uint32_t), h->stream));
+        HIP_TRY(hipEventRecord(h->timers.begin[RIBBIT_TIME_GPU], h->stream));
+        if ((rc = zero_counters(h))) return rc;
+        HIP_TRY(hipEventRecord(h->timers.begin[RIBBIT_TIME_SCAN], h->stream));
         // (two-kernel anchored stage: the planes kernel runs on the first attempt only, so the stage's start mark stays where it
-        // was put then -- timer 7 is "both kernels", also when the window scan had to run again with more room)
-        if (attempt == 0 || which == 1) HIP_TRY(hipEventRecord(h->ev_stage[which - 1][0], h->stream));
-        if (which == 1) {
-            pp.motifs_per_block = h->debug_split[RIBBIT_SCAN_SUBST];
-            h->rec.last_split[RIBBIT_SCAN_SUBST] = rb::launch_scan_window(pl, pp, 1, h->d_events.p, h->d_counters.p, h->stream);
+        // was put then -- timer RIBBIT_TIME_ANCHORED_SCAN is "both kernels", also when the window scan had to run again with more room)
+        if (attempt == 0 || subst) HIP_TRY(hipEventRecord(st.ev_begin, h->stream));
+        if (subst) {
+            h->rec.last_split[RIBBIT_SCAN_SUBST] = rb::launch_scan_window(pl, scan_launch_args(h, cap, RIBBIT_SCAN_SUBST), 1, h->d_events.p, h->pb.d_counters.p, h->stream);
         } else {
             if (attempt == 0) {          // the planes do not depend on the event capacity: once
-                pp.motifs_per_block = h->debug_split[RIBBIT_SCAN_ANCHORED];
-                h->rec.last_split[RIBBIT_SCAN_ANCHORED] = rb::launch_scan_anchored(pl, pp, h->d_xa.p, h->xa_stride, h->stream);
+                h->rec.last_split[RIBBIT_SCAN_ANCHORED] = rb::launch_scan_anchored(pl, scan_launch_args(h, cap, RIBBIT_SCAN_ANCHORED), h->d_xa.p, h->xa_stride, h->stream);
                 HIP_TRY(hipGetLastError());
                 HIP_TRY(hipEventRecord(h->ev_planes, h->stream));
             }
-            pp.motifs_per_block = h->debug_split[RIBBIT_SCAN_XA_WINDOW];
-            h->rec.last_split[RIBBIT_SCAN_XA_WINDOW] = rb::launch_scan_xa_window(pl, pp, h->d_xa.p, h->xa_stride, h->d_events.p, h->d_counters.p,
-                                                                            filter ? h->d_tj.p : nullptr, filter ? h->d_dropmap.p : nullptr, h->stream);
+            h->rec.last_split[RIBBIT_SCAN_XA_WINDOW] = rb::launch_scan_xa_window(pl, scan_launch_args(h, cap, RIBBIT_SCAN_XA_WINDOW), h->d_xa.p, h->xa_stride, h->d_events.p,
+                                                                            h->pb.d_counters.p, filter ? h->d_tj.p : nullptr, filter ? h->d_dropmap.p : nullptr, h->stream);
         }
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(h->ev[3], h->stream));
-        HIP_TRY(hipEventRecord(h->ev_stage[which - 1][1], h->stream));
-        h->have_stage_timing[which - 1] = true;
-        HIP_TRY(rb::launch_pair_runs(h->d_events.p, h->d_counters.p, pr, h->d_pair_table.p, h->d_run_base.p, h->d_pair_partial.p,
-                                     h->d_dense.p, (uint32_t)(cap / 2), h->d_halves.p, (uint32_t)(2 * (size_t)pr.nm), h->d_pair_status.p, h->stream));
-        rb::launch_pair_publish(h->d_counters.p, h->d_pair_status.p, h->h_pub_dev, h->stream);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(h->timers.end[RIBBIT_TIME_SCAN], h->stream));
+        HIP_TRY(hipEventRecord(st.ev_end, h->stream));
+        st.have_timing = true;
+        if ((rc = enqueue_pairing(h->pb, pr, h->d_events.p, h->d_dense.p, cap, h->stream))) return rc;
         HIP_TRY(hipStreamSynchronize(h->stream));
-        uint32_t worst = 0;
-        produced = 0;
-        for (int t = 0; t < rb::EV_SHARDS; ++t) { worst = std::max(worst, h->h_pub.p[t]); produced += h->h_pub.p[t]; }
-        if (worst <= pr.region_cap) { first_attempt_fit = attempt == 0; break; }
-        if (attempt == 2 || (size_t)worst * rb::EV_SHARDS > 0xffffff00u)
-            return fail(RIBBIT_E_OVERFLOW, "event buffer overflow: fullest region needs %u events", worst);
-        cap = ((size_t)worst + 1024) * rb::EV_SHARDS;
+        pub = read_published(h->pb);
+        if (pub.worst <= pr.region_cap) { first_attempt_fit = attempt == 0; break; }
+        if ((rc = grow_event_cap(attempt, pub.worst, &cap))) return rc;
     }
-    h->have_timing[1] = true;
-    h->last_event_count = (int64_t)produced;
-    const uint32_t flags = h->h_pub.p[rb::EV_SHARDS + rb::PAIR_FLAGS];
-    if (flags)
-        return fail(RIBBIT_E_INTERNAL, "streak pairing failed (flags 0x%x):%s%s%s%s%s", flags,
-                    flags & rb::PAIR_BAD_EVENT ? " malformed event;" : "", flags & rb::PAIR_DUP_CHUNK ? " duplicate event chunk;" : "",
-                    flags & rb::PAIR_NOT_ALTERNATING ? " streak starts and ends do not alternate;" : "",
-                    flags & rb::PAIR_UNTERMINATED ? " unterminated streak;" : "", flags & rb::PAIR_NO_ROOM ? " streak buffer too small;" : "");
-    const uint32_t n = h->h_pub.p[rb::EV_SHARDS + rb::PAIR_TOTAL];
-    if ((uint64_t)n * 2 != produced) return fail(RIBBIT_E_INTERNAL, "%llu events but %u streaks", (unsigned long long)produced, n);
-    if (h->h_pub.p[rb::EV_SHARDS + rb::PAIR_HALVES]) return fail(RIBBIT_E_INTERNAL, "streak cut by the own range of a whole record");
-    *n_streaks = n;
-    h->last_streaks = n;
+    h->timers.have[RIBBIT_TIME_SCAN] = true;
+    h->last_event_count = (int64_t)pub.produced;
+    size_t n = 0, n_cut = 0;
+    if ((rc = pairing_verdict(h->pb, pub.produced, "streak", &n, &n_cut))) return rc;
+    if (n_cut) return fail(RIBBIT_E_INTERNAL, "streak cut by the own range of a whole record");
+    *n_streaks = (uint32_t)n;
+    h->last_streaks = (int64_t)n;
     h->dropmap_valid = filter;
-    if (which == 2) h->planes_timing_valid = first_attempt_fit;
+    if (!subst) h->planes_timing_valid = first_attempt_fit;
     return RIBBIT_OK;
 }
 
 // The whole window stage on the device (window_stage.hip).  full: every call, unfiltered (the call-list entry points
 // and the parity tests); otherwise only the calls that pass min_span, with their cursor bounds.  cw: chunk mode.
-int window_stage_device(RibbitHandle *h, int which, bool full, int (*min_span)(int), DeviceCalls *out, ChunkWindow *cw) {
+int window_stage_device(RibbitHandle *h, int stage, bool full, int (*min_span)(int), DeviceCalls *out, ChunkWindow *cw) {
     int rc;
     uint32_t n = 0;
-    PinnedBuf<RibbitCall> &h_calls = h->h_calls_[which - 1], &h_flush = h->h_flush_[which - 1];
-    PinnedBuf<int32_t> &h_pend = h->h_pend_[which - 1];
-    PinnedBuf<uint32_t> &h_ws = h->h_ws_[which - 1];
+    PinnedBuf<RibbitCall> &h_calls = h->win[stage].h_calls, &h_flush = h->win[stage].h_flush;
+    PinnedBuf<int32_t> &h_pend = h->win[stage].h_pend;
+    PinnedBuf<uint32_t> &h_ws = h->win[stage].h_ws;
     const bool profile = rb::profile_on();
     const double t_scan = now_ms();
-    if ((rc = scan_and_pair_streaks(h, which, &n, full ? nullptr : min_span))) return rc;
+    if ((rc = scan_and_pair_streaks(h, stage, &n, full ? nullptr : min_span))) return rc;
     const double t0 = now_ms();
     const uint32_t nm = (uint32_t)(h->params.max_motif - h->params.min_motif + 1);
     const uint32_t n_words = (uint32_t)(h->length / 32 + 1);
@@ -190,7 +148,7 @@ int window_stage_device(RibbitHandle *h, int which, bool full, int (*min_span)(i
         rb::launch_window_calls(w, h->stream);
         HIP_TRY(hipGetLastError());
         if (h->dropmap_valid && !full) {
-            rb::launch_merge_dropmap(h->d_dropmap.p, (uint32_t)((size_t)(h->length / 32 + 1) + 1024), n_words, w.own_lo, w.own_hi, h->d_bitmap.p,
+            rb::launch_merge_dropmap(h->d_dropmap.p, (uint32_t)dropmap_words(h->length), n_words, w.own_lo, w.own_hi, h->d_bitmap.p,
                                      h->d_ws_counters.p, h->stream);
             HIP_TRY(hipGetLastError());
         }
@@ -238,9 +196,9 @@ int window_stage_device(RibbitHandle *h, int which, bool full, int (*min_span)(i
         HIP_TRY(hipMemcpyAsync(h_pend.p, h->d_pend.p, (size_t)n_main * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipMemcpyAsync(h_ws.p, h->d_ws_counters.p, rb::WS_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     }
-    HIP_TRY(hipEventRecord(h->ev[5], h->stream));
+    HIP_TRY(hipEventRecord(h->timers.end[RIBBIT_TIME_GPU], h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    h->have_timing[2] = true;
+    h->timers.have[RIBBIT_TIME_GPU] = true;
     wflags = h_ws.p[rb::WS_FLAGS];
     if (wflags) return fail(RIBBIT_E_INTERNAL, "cursor bounds of the edge calls failed (flags 0x%x)", wflags);
     // end-of-sequence calls: at most one per motif, already in motif order; close the gaps
@@ -262,7 +220,7 @@ int window_stage_device(RibbitHandle *h, int which, bool full, int (*min_span)(i
     h->host_ms = now_ms() - t0;
     if (profile)
         std::fprintf(stderr, "[window stage %d%s] scan + pairing %.1f ms (%u streaks), group scan + calls kernel %.1f ms, sort + bounds + read-back %.1f ms: "
-                     "%u calls, %u edge calls, %zu flush calls\n", which, full ? " full" : "", t0 - t_scan, n, t_calls - t0, now_ms() - t_calls, n_main, n_edge, nf);
+                     "%u calls, %u edge calls, %zu flush calls\n", stage, full ? " full" : "", t0 - t_scan, n, t_calls - t0, now_ms() - t_calls, n_main, n_edge, nf);
     return RIBBIT_OK;
 }
 
@@ -278,7 +236,7 @@ int build_subst_calls(RibbitHandle *h) {
     if (h->rec.subst_calls_valid) return RIBBIT_OK;
     if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
     DeviceCalls dc;
-    int rc = window_stage_device(h, 1, true, nullptr, &dc);
+    int rc = window_stage_device(h, RIBBIT_STAGE_SUBST, true, nullptr, &dc);
     if (rc) return rc;
     full_calls_from_device(dc, h->subst_calls);
     h->rec.subst_calls_valid = true;
@@ -310,7 +268,7 @@ int advance_to_subst(RibbitHandle *h) {
     if ((rc = ensure_host_planes(h))) return rc;
     DeviceCalls dc;
     const bool full = h->rec.subst_calls_valid;      // the full call list has been asked for (ribbit_hip_subst_calls): replay that
-    if (!full && (rc = window_stage_device(h, 1, false, rb::subst_seedlen_cutoff, &dc))) return rc;
+    if (!full && (rc = window_stage_device(h, RIBBIT_STAGE_SUBST, false, rb::subst_seedlen_cutoff, &dc))) return rc;
     subst_merge(h, full ? nullptr : &dc);
     return RIBBIT_OK;
 }
@@ -365,7 +323,7 @@ int build_anchored_calls(RibbitHandle *h) {
     int rc = prepare_anchored(h);
     if (rc) return rc;
     DeviceCalls dc;
-    if ((rc = window_stage_device(h, 2, true, nullptr, &dc))) return rc;
+    if ((rc = window_stage_device(h, RIBBIT_STAGE_ANCHORED, true, nullptr, &dc))) return rc;
     full_calls_from_device(dc, h->anchored_calls);
     h->rec.xa_on_device = true;
     h->rec.anchored_calls_valid = true;
@@ -382,6 +340,54 @@ void print_anchored_merge_profile(size_t seeds, const rb::MergeStats &st, double
                  st.ranges_redone, st.prepare_ms, st.prep_parts[0], st.prep_parts[1] - st.prep_parts[0], st.prep_parts[2] - st.prep_parts[1], st.merge_ms, st.pass_ms, st.ranges_run, st.device_ms, st.device_ranges, st.device_host_share, st.device_meanwhile_ms, st.device_apply_ms, st.device_bailed, st.range_ms_sum, st.range_ms_sum / std::max(1u, st.threads), st.range_ms_max, st.walk_ms, st.concat_ms, st.before_passes_ms, st.flush_ms, dispatch_ms, dispatch_ranges);
 }
 
+// from here on "plane m" means the composed plane XA_m (fasta_utils.cpp:159) wherever hp has it: the merges' range reads, and
+// the planes they may read word by word when hp stores them
+void use_composed_planes(rb::SeedLists &sl, const rb::HostPlanes *hp) {
+    sl.range_count = [hp](int shift, int start, int end) {
+        return hp->has_xa(shift) ? hp->range_count_xa(shift, start, end) : hp->range_count(shift, start, end);
+    };
+    if (hp->xa_stored()) { sl.plane_words = hp->xa_words(); sl.plane_stride = hp->xa_stride; sl.plane_lo = hp->xa_m_lo; sl.plane_hi = hp->xa_m_hi; }
+}
+
+// ---- what the host-only entry points (ribbit_host_replay_calls, ribbit_host_merge_chunks) share: the caller's planes checked,
+// copied into hp with the record's constants in sl, and at the end the lists handed out as malloc memory
+int check_caller_planes(const RibbitScanParams *params, int64_t length, const uint32_t *hi, const uint32_t *lo, const uint32_t *brk, size_t nwords, const uint32_t *xa, size_t xa_stride) {
+    if (!params || (length > 0 && (!hi || !lo || !brk))) return fail(RIBBIT_E_ARG, "null argument");
+    const size_t need = (size_t)(length / 32 + 1) + (size_t)(params->max_motif + 2) / 32 + 2;
+    if (nwords < need) return fail(RIBBIT_E_ARG, "planes too short: %zu words, need %zu (zero padding past the record)", nwords, need);
+    if (xa && xa_stride < (size_t)(length / 32 + 1)) return fail(RIBBIT_E_ARG, "composed planes (xa) too short");
+    return RIBBIT_OK;
+}
+
+void lists_over_caller_planes(const RibbitScanParams *params, int64_t length, const uint32_t *hi, const uint32_t *lo, const uint32_t *brk, size_t nwords, rb::HostPlanes &hp, rb::SeedLists &sl) {
+    hp.resize(length, nwords);
+    std::memcpy(hp.hi.data(), hi, nwords * sizeof(uint32_t));
+    std::memcpy(hp.lo.data(), lo, nwords * sizeof(uint32_t));
+    std::memcpy(hp.brk.data(), brk, nwords * sizeof(uint32_t));
+    sl.length = length;
+    sl.min_motif = params->min_motif;
+    sl.max_motif = params->max_motif;
+    sl.min_shift = (params->min_motif > 2) ? params->min_motif - 2 : 1;
+    const rb::HostPlanes *p = &hp;
+    sl.range_count = [p](int shift, int start, int end) { return p->range_count(shift, start, end); };
+}
+
+int give_seed_lists(const rb::SeedLists &sl, const rb::SeedVec &dispatch, RibbitSeedLists *out) {
+    auto give = [](const rb::SeedVec &v, RibbitSeed **p, size_t *n) {
+        *n = v.size();
+        *p = (RibbitSeed *)std::malloc(std::max<size_t>(v.size(), 1) * sizeof(RibbitSeed));
+        if (*p && !v.empty()) std::memcpy(*p, v.data(), v.size() * sizeof(RibbitSeed));
+        return *p != nullptr;
+    };
+    if (!give(sl.perfect, &out->perfect, &out->n_perfect) || !give(sl.subst, &out->subst, &out->n_subst) ||
+        !give(sl.anchored, &out->anchored, &out->n_anchored) || !give(dispatch, &out->dispatch, &out->n_dispatch)) {
+        ribbit_seed_lists_free(out);
+        return fail(RIBBIT_E_NOMEM, "out of host memory");
+    }
+    out->guard_hits = sl.guard_hits;
+    return RIBBIT_OK;
+}
+
 int advance_to_anchored(RibbitHandle *h) {
     if (h->rec.stage_done >= STAGE_ANCHORED) return RIBBIT_OK;
     int rc = advance_to_perfect(h);
@@ -392,11 +398,11 @@ int advance_to_anchored(RibbitHandle *h) {
     const bool subst_full = h->rec.subst_calls_valid;
     // the full call lists only when they have been asked for (ribbit_hip_*_calls); otherwise the compact form:
     // nine anchored calls in ten fail the length filter and never leave the device
-    if (subst_todo && !subst_full && (rc = window_stage_device(h, 1, false, rb::subst_seedlen_cutoff, &dcs))) return rc;
+    if (subst_todo && !subst_full && (rc = window_stage_device(h, RIBBIT_STAGE_SUBST, false, rb::subst_seedlen_cutoff, &dcs))) return rc;
     const bool full = h->rec.anchored_calls_valid;
     if (!full) {
         if ((rc = prepare_anchored(h))) return rc;
-        if ((rc = window_stage_device(h, 2, false, rb::anchored_seedlen_cutoff, &dca))) return rc;
+        if ((rc = window_stage_device(h, RIBBIT_STAGE_ANCHORED, false, rb::anchored_seedlen_cutoff, &dca))) return rc;
         h->rec.xa_on_device = true;
     }
     if ((rc = bind_device(h))) return rc;
@@ -411,12 +417,7 @@ int advance_to_anchored(RibbitHandle *h) {
     if (profile_xa)
         std::fprintf(stderr, "[composed planes] %.2f GB to the host for the merges' range reads: page-locked room and enqueue %.1f ms, waited %.1f ms for the copy after the substitution merge\n",
                      (double)(h->params.max_motif - h->params.min_motif + 1) * (double)h->xa_stride * 4e-9, tx1 - tx0, now_ms() - tx2);
-    // from here on "plane m" means the composed plane XA_m (fasta_utils.cpp:159)
-    const rb::HostPlanes *hp = &h->host;
-    h->lists.range_count = [hp](int shift, int start, int end) {
-        return hp->has_xa(shift) ? hp->range_count_xa(shift, start, end) : hp->range_count(shift, start, end);
-    };
-    if (hp->xa_stored()) { h->lists.plane_words = hp->xa_words(); h->lists.plane_stride = hp->xa_stride; h->lists.plane_lo = hp->xa_m_lo; h->lists.plane_hi = hp->xa_m_hi; }
+    use_composed_planes(h->lists, &h->host);
     // (lists.anchored is not cleared here: every path of the stage sets it, and the join reuses what it holds, parallel_merge.cpp)
     const double t0 = now_ms();
     const unsigned threads = rb::host_thread_count(h->host_threads);
@@ -522,21 +523,11 @@ int ribbit_host_replay_calls(const RibbitScanParams *params, int64_t length,
     if (!params || !out || (length > 0 && (!hi || !lo || !brk))) return fail(RIBBIT_E_ARG, "null argument");
     if ((n_perfect_calls && !perfect_calls) || (n_subst_calls && !subst_calls) || (n_anchored_calls && !anchored_calls))
         return fail(RIBBIT_E_ARG, "null call list");
-    const size_t need = (size_t)(length / 32 + 1) + (size_t)(params->max_motif + 2) / 32 + 2;
-    if (nwords < need) return fail(RIBBIT_E_ARG, "planes too short: %zu words, need %zu (zero padding past the record)", nwords, need);
-    if (xa && xa_stride < (size_t)(length / 32 + 1)) return fail(RIBBIT_E_ARG, "composed planes (xa) too short");
+    if (const int bad = check_caller_planes(params, length, hi, lo, brk, nwords, xa, xa_stride)) return bad;
     std::memset(out, 0, sizeof *out);
     rb::HostPlanes hp;
-    hp.resize(length, nwords);
-    std::memcpy(hp.hi.data(), hi, nwords * sizeof(uint32_t));
-    std::memcpy(hp.lo.data(), lo, nwords * sizeof(uint32_t));
-    std::memcpy(hp.brk.data(), brk, nwords * sizeof(uint32_t));
     rb::SeedLists sl;
-    sl.length = length;
-    sl.min_motif = params->min_motif;
-    sl.max_motif = params->max_motif;
-    sl.min_shift = (params->min_motif > 2) ? params->min_motif - 2 : 1;
-    sl.range_count = [&hp](int shift, int start, int end) { return hp.range_count(shift, start, end); };
+    lists_over_caller_planes(params, length, hi, lo, brk, nwords, hp, sl);
     for (size_t i = 0; i < n_perfect_calls; ++i) rb::perfect_add(sl, perfect_calls[i].start, perfect_calls[i].end, perfect_calls[i].mlen);
     rb::merge_subst_stage_full(sl, subst_calls, n_subst_calls, rb::host_thread_count(0));
     // the anchored stage runs when there are anchored calls or composed planes are given; anchored_calls non-null with
@@ -548,10 +539,7 @@ int ribbit_host_replay_calls(const RibbitScanParams *params, int64_t length,
         hp.xa_stride = xa ? (int64_t)xa_stride : 0;
         hp.xa_m_lo = params->min_motif;
         hp.xa_m_hi = params->max_motif;
-        sl.range_count = [&hp](int shift, int start, int end) {
-            return hp.has_xa(shift) ? hp.range_count_xa(shift, start, end) : hp.range_count(shift, start, end);
-        };
-        if (hp.xa_stored()) { sl.plane_words = hp.xa_words(); sl.plane_stride = hp.xa_stride; sl.plane_lo = hp.xa_m_lo; sl.plane_hi = hp.xa_m_hi; }
+        use_composed_planes(sl, &hp);
     }
     rb::SeedVec dispatch;
     if (anchored_stage) {
@@ -576,19 +564,7 @@ int ribbit_host_replay_calls(const RibbitScanParams *params, int64_t length,
         const unsigned dispatch_ranges = rb::dispatch_order_ranges(sl, st.cut_pos, rb::host_thread_count(0), dispatch);
         if (rb::profile_on()) print_anchored_merge_profile(sl.anchored.size(), st, now_ms() - td, dispatch_ranges);
     }
-    auto give = [](const rb::SeedVec &v, RibbitSeed **p, size_t *n) {
-        *n = v.size();
-        *p = (RibbitSeed *)std::malloc(std::max<size_t>(v.size(), 1) * sizeof(RibbitSeed));
-        if (*p && !v.empty()) std::memcpy(*p, v.data(), v.size() * sizeof(RibbitSeed));
-        return *p != nullptr;
-    };
-    if (!give(sl.perfect, &out->perfect, &out->n_perfect) || !give(sl.subst, &out->subst, &out->n_subst) ||
-        !give(sl.anchored, &out->anchored, &out->n_anchored) || !give(dispatch, &out->dispatch, &out->n_dispatch)) {
-        ribbit_seed_lists_free(out);
-        return fail(RIBBIT_E_NOMEM, "out of host memory");
-    }
-    out->guard_hits = sl.guard_hits;
-    return RIBBIT_OK;
+    return give_seed_lists(sl, dispatch, out);
 }); }
 
 void ribbit_seed_lists_free(RibbitSeedLists *lists) {
