@@ -392,6 +392,41 @@ int ribbit_bed_loci_text(const char *name, const char *bed_text, size_t bed_len,
                          char **text, size_t *len);
 
 /*
+ * ---- the rows against a second set of intervals -------------------------------------------------------------------
+ * OTHER is a second set of (start, end) intervals on the same record: a truth set, another caller's BED, an annotation.
+ * With L the record's length, every interval (s, e), row or OTHER, is clipped as the mask clips it, s' = max(s, 0),
+ * e' = min(e, L), in 64-bit; one with s' >= e' is empty.  U_rows and U_other are the sets of positions held by a non-empty
+ * row and by a non-empty OTHER interval.
+ *   Per row i:  others[i] = the number of non-empty OTHER intervals j with s'_j < e'_i and e'_j > s'_i (duplicates each
+ *               count; an abutting interval does not overlap); bases[i] = |[s'_i, e'_i) & U_other|.  An empty row: 0, 0.
+ *   Totals:     rows / other = the number of non-empty rows / OTHER intervals; rows_hit = the non-empty rows with
+ *               bases > 0; other_hit = the non-empty OTHER intervals that hold a position of U_rows; rows_bases = |U_rows|,
+ *               other_bases = |U_other|, both_bases = |U_rows & U_other|.
+ * All of them are counts: recall is other_hit / other, precision rows_hit / rows, the base-level Jaccard index
+ * both_bases / (rows_bases + other_bases - both_bases).
+ */
+typedef struct {
+    int64_t rows_bases, other_bases, both_bases;
+    int32_t rows, rows_hit, other, other_hit;
+} RibbitOverlapTotals;
+/* The loaded record's n rows against n_other intervals (each at most INT32_MAX), on the GPU.  *per_row: (others, bases) of
+ * row i at [2 i] and [2 i + 1], 2 n ints of handle-owned page-locked memory, valid until the handle's next overlap call,
+ * load or close.  L = 0, n = 0 and n_other = 0 are no errors.  The coverage bitmap of the rows is the one the mask, the
+ * loci and the density use: it is built once for all of them.  A second call with the same rows and the same OTHER on the
+ * same loaded record returns what the first one found and gives the GPU nothing to do. */
+int ribbit_hip_record_overlap(RibbitHandle *h, const int32_t *rows, size_t n, const int32_t *other, size_t n_other,
+                              const int32_t **per_row, RibbitOverlapTotals *totals);
+/* Host-only twin (no GPU) for a record of `length` bases (0 <= length < 2^31): *per_row malloc'ed, release with
+ * ribbit_intervals_free(). */
+int ribbit_host_record_overlap(int64_t length, const int32_t *rows, size_t n, const int32_t *other, size_t n_other,
+                               int32_t **per_row, RibbitOverlapTotals *totals);
+/* The record's BED rows with the two per-row values appended (host only): line i of bed_text, byte for byte, then a tab,
+ * others[i], a tab, bases[i] and a newline: 13 columns.  bed_text: the rows as ribbit_hip_refine_bed writes them, row i on
+ * line i (a last line without its newline counts); per_row: 2 n ints as above.  A bed_text that does not have n lines:
+ * RIBBIT_E_ARG.  *text malloc'ed, release with ribbit_text_free(). */
+int ribbit_bed_overlap_text(const char *bed_text, size_t bed_len, const int32_t *per_row, size_t n, char **text, size_t *len);
+
+/*
  * ---- streaming FASTA ingest ---------------------------------------------------------------------------------------
  * Replaces the reader loop of ribbit.cpp:269-280 (getline + `sequence += line` into one pageable std::string per
  * record).  The file is read in 16-MB blocks; line bodies are copied once, straight into a page-locked buffer

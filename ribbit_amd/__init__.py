@@ -17,7 +17,8 @@ __all__ = ["RibbitHipError", "ScanParams", "Scanner", "library_path", "load_libr
            "RUN_DT", "CALL_DT", "SEED_DT", "JOB_DT", "ENDS_DT", "RANK", "TERM", "RefineParams", "host_refine_jobs", "host_refine_bed", "host_merge_chunks", "host_perfect_runs_from_events", "pair_halves", "ssw_align", "ssw_align_periodic", "merge_chunk_runs", "join_run_halves",
            "RUN_NOT_OWNED", "RUN_HALF_START", "RUN_HALF_END",
            "MASK_MODES", "host_mask_record", "bed_intervals", "host_repeat_sequences",
-           "LOCUS_DT", "host_record_loci", "host_record_density", "bed_loci_text"]
+           "LOCUS_DT", "host_record_loci", "host_record_density", "bed_loci_text",
+           "OverlapTotals", "OVERLAP_TOTALS", "host_record_overlap", "bed_overlap_text"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -60,6 +61,7 @@ ABI_SYMBOLS = [
     "ribbit_hip_repeat_sequences", "ribbit_host_repeat_sequences", "ribbit_hip_debug_set_repeat_text_budget",
     "ribbit_hip_record_loci", "ribbit_hip_record_density", "ribbit_host_record_loci", "ribbit_host_record_density", "ribbit_loci_free",
     "ribbit_bed_loci_text",
+    "ribbit_hip_record_overlap", "ribbit_host_record_overlap", "ribbit_bed_overlap_text",
 ]
 
 MASK_MODES = {"soft": 0, "hard": 1}     # RIBBIT_MASK_SOFT / RIBBIT_MASK_HARD
@@ -73,6 +75,19 @@ class ScanParams(C.Structure):
     """RibbitScanParams (ribbit.cpp:191,240-243; fasta_utils.cpp:165)."""
     _fields_ = [("min_motif", C.c_int32), ("max_motif", C.c_int32), ("window_length", C.c_int32),
                 ("subst_threshold", C.c_int32), ("anchor_threshold", C.c_int32), ("anchor_length", C.c_int32)]
+
+
+class OverlapTotals(C.Structure):
+    """RibbitOverlapTotals: what record_overlap counts over all rows and all OTHER intervals (include/ribbit_hip.h)."""
+    _fields_ = [("rows_bases", C.c_int64), ("other_bases", C.c_int64), ("both_bases", C.c_int64),
+                ("rows", C.c_int32), ("rows_hit", C.c_int32), ("other", C.c_int32), ("other_hit", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name in OVERLAP_TOTALS}
+
+
+# the totals in the order of ribbit-hip --overlap-summary's columns (behind name and length)
+OVERLAP_TOTALS = ("rows", "rows_hit", "other", "other_hit", "rows_bases", "other_bases", "both_bases")
 
 
 class RefineParams(C.Structure):
@@ -278,6 +293,9 @@ def load_library():
     L.ribbit_loci_free.restype = None
     L.ribbit_loci_free.argtypes = [vp]
     L.ribbit_bed_loci_text.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_hip_record_overlap.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(OverlapTotals)]
+    L.ribbit_host_record_overlap.argtypes = [i64, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(OverlapTotals)]
+    L.ribbit_bed_overlap_text.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
     _lib = L
     return L
 
@@ -647,6 +665,43 @@ def bed_loci_text(name, bed, loci) -> bytes:
         L.ribbit_text_free(text)
 
 
+def _pairs(intervals) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(intervals, dtype=np.int32).reshape(-1, 2))
+
+
+def host_record_overlap(length: int, rows, other):
+    """ribbit_host_record_overlap: the rows of a record of `length` bases against the intervals `other` -> ((n, 2) int32 array:
+    per row the number of OTHER intervals it overlaps and the number of its bases that OTHER covers; the totals as a dict with
+    the keys OVERLAP_TOTALS).  The contract is in include/ribbit_hip.h.  No GPU needed."""
+    L = load_library()
+    iv, ot = _pairs(rows), _pairs(other)
+    per_row, totals = C.c_void_p(), OverlapTotals()
+    rc = L.ribbit_host_record_overlap(int(length), iv.ctypes.data if len(iv) else None, len(iv), ot.ctypes.data if len(ot) else None, len(ot),
+                                      C.byref(per_row), C.byref(totals))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_host_record_overlap error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return _copy(per_row.value, 2 * len(iv), np.dtype("<i4")).reshape(-1, 2), totals.as_dict()
+    finally:
+        L.ribbit_intervals_free(per_row)
+
+
+def bed_overlap_text(bed, per_row) -> bytes:
+    """ribbit_bed_overlap_text: the lines of `bed` (one record's BED text, row i on line i), each with row i's two values of
+    `per_row` appended as two more columns."""
+    L = load_library()
+    text_in = bed.encode() if isinstance(bed, str) else bytes(bed)
+    pr = _pairs(per_row)
+    text, n = C.c_void_p(), C.c_size_t()
+    rc = L.ribbit_bed_overlap_text(text_in, len(text_in), pr.ctypes.data if len(pr) else None, len(pr), C.byref(text), C.byref(n))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_bed_overlap_text error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return C.string_at(text.value, n.value)
+    finally:
+        L.ribbit_text_free(text)
+
+
 def host_perfect_runs_from_events(min_motif: int, max_motif: int, event_parts, count_parts):
     """ribbit_host_perfect_runs_from_events: per-rank (events, per-motif counts) -> paired runs. No GPU needed."""
     L = load_library()
@@ -975,6 +1030,14 @@ class Scanner:
         loci, n = C.c_void_p(), C.c_size_t()
         self._check(self._L.ribbit_hip_record_loci(self._h, iv.ctypes.data if len(iv) else None, len(iv), gap, C.byref(loci), C.byref(n)))
         return _copy(loci.value, n.value, LOCUS_DT)
+
+    def record_overlap(self, rows, other):
+        """The loaded record's rows against the intervals `other` on the GPU (ribbit_hip_record_overlap); see host_record_overlap"""
+        iv, ot = _pairs(rows), _pairs(other)
+        per_row, totals = C.c_void_p(), OverlapTotals()
+        self._check(self._L.ribbit_hip_record_overlap(self._h, iv.ctypes.data if len(iv) else None, len(iv), ot.ctypes.data if len(ot) else None, len(ot),
+                                                      C.byref(per_row), C.byref(totals)))
+        return _copy(per_row.value, 2 * len(iv), np.dtype("<i4")).reshape(-1, 2), totals.as_dict()
 
     def record_density(self, intervals, window: int) -> np.ndarray:
         """The loaded record's covered bases per window on the GPU (ribbit_hip_record_density); see host_record_density"""

@@ -12,8 +12,9 @@
 //   api_mask.cpp        the repeat-masked FASTA body of a record (mask.hip), its host twin, BED rows back to intervals
 //   api_repeats.cpp     every row's bases with their flanks as FASTA entries (repeats.hip), in batches of a text budget; its host twin
 //   api_loci.cpp        merged, sorted loci and the per-window density of a record (loci.hip), their host twins, the loci as text
-// The last three are the row outputs: their buffers are the handle's RowBufs `rows`, and what their host sides share is below
-// (hand_out, clipped_sorted_rows, bed_text_parts).
+//   api_overlap.cpp     the rows of a record against a second set of intervals (overlap.hip), its host twin, the rows' text with the two columns
+// The last four are the row outputs: their buffers are the handle's RowBufs `rows`, and what their host sides share is below
+// (hand_out, clipped_sorted_rows, bed_text_parts, bed_line_starts).
 // Host threads: every team of them, here and in refine.cpp, parallel_merge.cpp and host_planes.cpp, is started by rb::on_threads /
 // rb::over_pieces of host_threads.h (part 0 on the caller, a thread that cannot start leaves its part to the caller, all joined, the
 // first exception of any part rethrown on the caller: it then meets guarded() below); the thread count rule (the handle's, else
@@ -185,7 +186,7 @@ struct PairBufs {
     uint32_t *h_pub_dev = nullptr;         // the same memory as the device sees it
 };
 
-// ---- shared by the host sides of the row outputs (api_mask.cpp, api_repeats.cpp, api_loci.cpp)
+// ---- shared by the host sides of the row outputs (api_mask.cpp, api_repeats.cpp, api_loci.cpp, api_overlap.cpp)
 
 // n elements as malloc memory the caller frees (never a null pointer, whatever n): a copy of src, or for the caller to fill
 // when src is null; terminate: a zero element behind them
@@ -214,6 +215,26 @@ inline std::vector<ClippedRow> clipped_sorted_rows(int64_t length, const int32_t
 
 // a chromosome's BED is 150-200 MB of text: it is walked in pieces, one thread per piece of at least 4 MB
 inline size_t bed_text_parts(size_t len) { return std::max<size_t>(1, std::min<size_t>(std::min(rb::host_thread_count(0), 16u), len >> 22)); }
+
+// where the lines of a BED text start: line i is [line[i], line[i + 1]), its newline included; a last line without its newline
+// counts.  The newlines are found in `parts` pieces, one thread per piece.
+inline int bed_line_starts(const char *bed, size_t bed_len, size_t parts, std::vector<size_t> &line) {
+    std::vector<std::vector<size_t>> starts(parts);      // per piece: the offsets just behind its newlines
+    std::vector<char> oom(parts, 0);
+    rb::on_threads((unsigned)parts, [&](unsigned k) {
+        try {
+            const char *p = bed + bed_len * k / parts, *end = bed + bed_len * (k + 1) / parts;
+            while (p < end && (p = static_cast<const char *>(std::memchr(p, '\n', (size_t)(end - p)))) != nullptr) starts[k].push_back((size_t)(++p - bed));
+        } catch (const std::bad_alloc &) { oom[k] = 1; }
+    });
+    line.assign(1, 0);
+    for (size_t k = 0; k < parts; ++k) {
+        if (oom[k]) return fail(RIBBIT_E_NOMEM, "out of host memory reading BED rows");
+        line.insert(line.end(), starts[k].begin(), starts[k].end());
+    }
+    if (line.back() != bed_len) line.push_back(bed_len);
+    return RIBBIT_OK;
+}
 
 }  // namespace rbapi
 
@@ -257,6 +278,8 @@ struct RibbitHandle {
         int stage_done = STAGE_NONE;          // how far the seed lists have been advanced
         bool coverage_valid = false;          // rows.d_mask_bits is the coverage of the coverage_n rows in rows.h_mask_iv / d_mask_iv (build_coverage)
         size_t coverage_n = 0;
+        bool overlap_valid = false;           // rows.h_overlap is the overlap of those rows with the overlap_n intervals in rows.h_overlap_iv (api_overlap.cpp)
+        size_t overlap_n = 0;
         rb::ScanSplit last_split[RIBBIT_SCAN_KERNELS];   // the split each scan kernel last ran with on the loaded record
     } rec;
     bool timing = true;           // record the HIP events behind ribbit_hip_last_timing_ms (each costs a barrier packet on the stream)
@@ -369,7 +392,7 @@ struct RibbitHandle {
     bool bed_in_raw = false;              // the last ribbit_hip_refine_bed returned bed_raw, not bed
     rb::SeedLists lists;
     bool refine_met_empty_query = false;  // the last ribbit_hip_refine_bed on this handle met an alignment with an empty query (ribbit_hip_refine_met_empty_query)
-    // the row outputs of the loaded record (api_mask.cpp, api_repeats.cpp, api_loci.cpp)
+    // the row outputs of the loaded record (api_mask.cpp, api_repeats.cpp, api_loci.cpp, api_overlap.cpp)
     struct RowBufs {
         // the masked body of the loaded record (api_mask.cpp): coverage bitmap, intervals, the text on the device and on its way up
         DevBuf<uint32_t> d_mask_bits;
@@ -399,6 +422,16 @@ struct RibbitHandle {
         PinnedBuf<RibbitLocus> h_loci;
         DevBuf<int32_t> d_density;
         PinnedBuf<int32_t> h_density;
+        // the rows against a second set of intervals (api_overlap.cpp): those intervals, their coverage bitmap (the rows' is
+        // d_mask_bits), the blocks' counts with their ranks behind them, the intervals' starts | ends | sorted starts | sorted ends,
+        // the scan's and the sorts' scratch, and the result on the device and on its way up: the totals, then (others, bases) per row
+        DevBuf<int32_t> d_overlap_iv;
+        PinnedBuf<int32_t> h_overlap_iv;
+        DevBuf<uint32_t> d_overlap_bits, d_overlap_keys;
+        DevBuf<uint64_t> d_overlap_ranks;
+        DevBuf<uint8_t> d_overlap_scratch;
+        DevBuf<int32_t> d_overlap;
+        PinnedBuf<int32_t> h_overlap;
         size_t rep_budget = 0;            // text budget of one batch of repeat sequences in bytes (0: REPEAT_TEXT_BUDGET)
     } rows;
     RibbitHandle *aux = nullptr;          // helper handle of ribbit_hip_refine_bed: streams and buffers of the long alignment batch
@@ -493,7 +526,9 @@ int run_ssw_passes(RibbitHandle *h, const RibbitAlignJob *jobs, size_t n, const 
                           std::vector<rb::SswEnds> &ends, unsigned classes = 0x1fu, bool pool_resident = false);
 int run_ssw_paths(RibbitHandle *h, const RibbitAlignJob *jobs, size_t n, const std::vector<rb::SswEnds> &ends, std::vector<rb::SswPath> &paths);
 // api_mask.cpp: the coverage bitmap of the loaded record (length > 0) under n rows in rows.d_mask_bits, rb::coverage_words(length)
-// words, and the rows in rows.d_mask_iv, enqueued on the handle's stream; nothing is enqueued when the bitmap already is the one of these rows
+// words, and the rows in rows.d_mask_iv, enqueued on the handle's stream; nothing is enqueued when the bitmap already is the one of these
+// rows (coverage_is)
+bool coverage_is(const RibbitHandle *h, const int32_t *intervals, size_t n);
 int build_coverage(RibbitHandle *h, const int32_t *intervals, size_t n);
 
 }  // namespace rbapi

@@ -166,20 +166,9 @@ int bed_loci_text_impl(const char *name, const char *bed, size_t bed_len, const 
     if (!name || !text || !len || (!bed && bed_len > 0) || (!loci && n_loci > 0)) return fail(RIBBIT_E_ARG, "null argument");
     // the BED text's line starts are found in pieces, and the loci's lines are written in as many pieces
     const size_t parts = n_loci ? bed_text_parts(bed_len) : 1;
-    std::vector<std::vector<size_t>> starts(parts);      // per piece: the offsets just behind its newlines
-    std::vector<char> oom(parts, 0);
-    if (n_loci)
-        rb::on_threads((unsigned)parts, [&](unsigned k) {
-            try {
-                const char *p = bed + bed_len * k / parts, *end = bed + bed_len * (k + 1) / parts;
-                while (p < end && (p = static_cast<const char *>(std::memchr(p, '\n', (size_t)(end - p)))) != nullptr) starts[k].push_back((size_t)(++p - bed));
-            } catch (const std::bad_alloc &) { oom[k] = 1; }
-        });
     std::vector<size_t> line{0};       // line i is [line[i], line[i + 1]); a last line without its newline counts
-    for (size_t k = 0; k < parts; ++k) {
-        if (oom[k]) return fail(RIBBIT_E_NOMEM, "out of host memory reading BED rows");
-        line.insert(line.end(), starts[k].begin(), starts[k].end());
-    }
+    int rc;
+    if (n_loci && (rc = bed_line_starts(bed, bed_len, parts, line))) return rc;
     if (line.back() != bed_len) line.push_back(bed_len);
     const size_t n_lines = line.size() - 1, name_len = std::strlen(name);
     const size_t out_parts = std::max<size_t>(1, std::min<size_t>(parts, n_loci >> 12));
@@ -214,7 +203,6 @@ int bed_loci_text_impl(const char *name, const char *bed, size_t bed_len, const 
         if (bad[k] != (size_t)-1) return fail(RIBBIT_E_ARG, "locus %zu: its best row %d is not a row of 11 tab-separated columns of the BED text (%zu lines)", bad[k], (int)loci[bad[k]].best_row, n_lines);
         total += piece[k].size();
     }
-    int rc;
     if ((rc = hand_out<char>(nullptr, total, true, text))) return rc;
     size_t at = 0;
     for (const std::string &s : piece) {

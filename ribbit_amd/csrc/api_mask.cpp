@@ -67,10 +67,14 @@ int mask_record_impl(RibbitHandle *h, const int32_t *intervals, size_t n, int32_
 
 // The staged copy of the last rows stays in rows.h_mask_iv: a call with the same rows (the command-line tool hands one record's rows to
 // the mask, the loci and the density) finds the bitmap as it needs it, at the price of one comparison.
+bool rbapi::coverage_is(const RibbitHandle *h, const int32_t *intervals, size_t n) {
+    return h->rec.coverage_valid && h->rec.coverage_n == n && (n == 0 || std::memcmp(h->rows.h_mask_iv.p, intervals, 2 * n * sizeof(int32_t)) == 0);
+}
+
 int rbapi::build_coverage(RibbitHandle *h, const int32_t *intervals, size_t n) {
-    if (h->rec.coverage_valid && h->rec.coverage_n == n && (n == 0 || std::memcmp(h->rows.h_mask_iv.p, intervals, 2 * n * sizeof(int32_t)) == 0))
-        return RIBBIT_OK;
+    if (coverage_is(h, intervals, n)) return RIBBIT_OK;
     h->rec.coverage_valid = false;
+    h->rec.overlap_valid = false;      // (what api_overlap.cpp keeps belongs to the rows of the bitmap)
     int rc;
     const size_t words = (size_t)rb::coverage_words(h->length);
     if ((rc = h->rows.d_mask_bits.ensure(words))) return rc;

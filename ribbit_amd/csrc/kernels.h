@@ -296,6 +296,15 @@ hipError_t launch_loci(const int32_t *run_start, const int32_t *run_end, int64_t
 // covered[k] = covered positions of [k window, min((k + 1) window, length)), k < n_windows = ceil(length / window)
 void launch_density(const uint32_t *bits, int64_t length, int64_t window, int64_t n_windows, int32_t *covered, hipStream_t stream);
 
+// overlap.hip: the rows of the loaded record (length > 0) against a second set of intervals (api_overlap.cpp).  a_bits: the
+// coverage bitmap of the n rows, b_bits: that of the n_other intervals of `other`, both as loci.hip takes them.  ranks:
+// 2 loci_lanes(length) words, keys: 4 n_other words, scratch: overlap_scratch_bytes(length, n_other).  totals is zeroed and
+// filled; per_row: (others, bases) of every row, 2 n ints.
+size_t overlap_scratch_bytes(int64_t length, int64_t n_other);
+hipError_t launch_overlap(const uint32_t *a_bits, const uint32_t *b_bits, int64_t length, const int32_t *rows, int64_t n, const int32_t *other, int64_t n_other,
+                          uint64_t *ranks, uint32_t *keys, RibbitOverlapTotals *totals, int32_t *per_row, void *scratch, size_t scratch_bytes,
+                          hipStream_t stream);
+
 // profiling aid: reads nwords dwords of src with one coalesced dword per lane (known byte count)
 void launch_calib_stream_read(const uint32_t *src, int64_t nwords, uint32_t *sink, hipStream_t stream);
 

@@ -5,6 +5,7 @@
 //   ribbit-hip -i in.fa [-o out.bed] [-m 2] [-M 100] [-p 0.85] [-l N|file] [--min-units N|file] [--perfect-units N|file]
 //              [--devices 0,1,...] [--jobs N] [--masked-fasta FILE [--mask soft|hard] [--mask-width N]]
 //              [--repeat-fasta FILE [--flank N]] [--loci-bed FILE [--loci-gap D]] [--density-bedgraph FILE [--density-window W]]
+//              [--overlap-with OTHER.bed [--overlap-bed FILE] [--overlap-summary FILE]]
 //
 // Records are independent (ribbit.cpp:269-280 handles them one after the other); here up to --jobs of them are in
 // flight at once PER GPU, each on its own handle / HIP streams, so that the upload and GPU scans of one record overlap
@@ -17,12 +18,15 @@
 // (ribbit_hip_mask_record), in input order beside the BED.  --repeat-fasta writes every BED row's bases with N flanking bases on
 // either side (ribbit_hip_repeat_sequences), the same way.  --loci-bed writes the rows of every record merged into sorted loci
 // (ribbit_hip_record_loci, ribbit_bed_loci_text) and --density-bedgraph the covered bases per window (ribbit_hip_record_density),
-// the same way again.  The BED rows are read back once per record, however many of the four are asked for.
+// the same way again.  --overlap-with reads a second BED file, grouped by record name before the first record is scanned, and
+// --overlap-bed / --overlap-summary set every record's rows against its intervals of that file (ribbit_hip_record_overlap): the
+// rows again with two columns more (ribbit_bed_overlap_text), and one line of counts per record.  The BED rows are read back once
+// per record, however many of the six are asked for.
 //
-// These four are the ROW OUTPUTS, and each is described once, by its entry of kOutputs below: its file option, its stage (enum
+// These six are the ROW OUTPUTS, and each is described once, by its entry of kOutputs below: its file option, its stage (enum
 // Stage, with the stage's names beside it), its qualifier options with their ranges and wording (defaults: Settings), and the function that
 // makes one record's text from the record's rows.  Parsing, the "needs" checks, opening the files, the sinks of the pipelined
-// records and of the last one, --timing and the RIBBIT_PROFILE line are loops over that table.  A fifth row output is: a stage in
+// records and of the last one, --timing and the RIBBIT_PROFILE line are loops over that table.  A seventh row output is: a stage in
 // the enum and its names, the qualifiers' fields in Settings, a produce function, an entry of kOutputs, and its lines of kHelp.
 //
 // Reproduced quirks: -p is accepted and ignored (Q1); without -o the BED rows go to
@@ -68,12 +72,12 @@ void check(int rc) {
 }
 
 // The stages of a record: the six every record goes through, then one per row output, in the order of kOutputs.
-enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, N_STAGES };
+enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, OVERLAP, N_STAGES };
 constexpr int N_FIXED_STAGES = MASK;
 // a stage's key in --timing's stage_ms_summed_over_records and its label in the RIBBIT_PROFILE line
 const struct { const char *key, *label; } kStageNames[N_STAGES] = {
     {"load", "load"}, {"perfect", "perfect"}, {"substitutions", "substitutions"}, {"anchored", "anchored"}, {"dispatch", "dispatch"},
-    {"refine_and_bed", "refine+BED"}, {"mask", "mask"}, {"repeats", "repeats"}, {"loci", "loci"}, {"density", "density"}};
+    {"refine_and_bed", "refine+BED"}, {"mask", "mask"}, {"repeats", "repeats"}, {"loci", "loci"}, {"density", "density"}, {"overlap", "overlap"}};
 
 // wall time per stage, summed over the records (--timing, RIBBIT_PROFILE=1)
 double g_stage_ms[N_STAGES] = {};
@@ -101,7 +105,18 @@ struct RecordRows {
     const char *bed_text;                // the record's BED text, row i on line i (handle-owned: valid until the handle's next refinement) ...
     size_t bed_len;
     std::string bed_copy;                // ... or this copy of it, when it came in slices and an output quotes it
+    const std::vector<int32_t> *other;   // the record's intervals of --overlap-with, (start, end) each in file order (null: none)
     size_t n() const { return iv.size() / 2; }
+};
+
+// --overlap-with: the intervals of a second BED file by record name, and which names have been a record of the input
+struct OtherBed {
+    struct Group { std::vector<int32_t> iv; bool is_record = false; };
+    std::map<std::string, Group> by_name;
+    const std::vector<int32_t> *of(const std::string &name) const {
+        const auto it = by_name.find(name);
+        return it == by_name.end() ? nullptr : &it->second.iv;
+    }
 };
 
 // the qualifiers' values and their defaults
@@ -111,6 +126,7 @@ struct Settings {
     int flank = 100;                     // --flank N: bases on either side of a row
     int loci_gap = 0;                    // --loci-gap D: runs at most D bases apart are one locus
     int density_window = 10000;          // --density-window W
+    const OtherBed *other = nullptr;         // --overlap-with FILE, read and grouped by name
 };
 
 // --name VALUE: a whole number of bases in [lo, hi] of at most max_digits digits (`range`: how the message puts that), or soft|hard
@@ -175,6 +191,40 @@ void produce_density(RibbitHandle *h, const RecordRows &r, const Settings &s, co
     write(lines.data(), lines.size());
 }
 
+// both overlap outputs of a record: the second call finds what the first left on the handle and gives the GPU nothing to do
+const int32_t *overlap_of(RibbitHandle *h, const RecordRows &r, RibbitOverlapTotals *totals) {
+    static const std::vector<int32_t> kNone;
+    const std::vector<int32_t> &other = r.other ? *r.other : kNone;
+    const int32_t *per_row = nullptr;
+    check(ribbit_hip_record_overlap(h, r.iv.data(), r.n(), other.data(), other.size() / 2, &per_row, totals));
+    return per_row;
+}
+
+void produce_overlap_bed(RibbitHandle *h, const RecordRows &r, const Settings &, const Sink &write) {
+    RibbitOverlapTotals totals;
+    char *text = nullptr;
+    size_t len = 0;
+    StageClock c(OVERLAP);
+    const int32_t *per_row = overlap_of(h, r, &totals);
+    check(ribbit_bed_overlap_text(r.bed_text, r.bed_len, per_row, r.n(), &text, &len));
+    write(text, len);
+    ribbit_text_free(text);
+}
+
+void produce_overlap_summary(RibbitHandle *h, const RecordRows &r, const Settings &, const Sink &write) {
+    RibbitOverlapTotals t;
+    StageClock c(OVERLAP);
+    overlap_of(h, r, &t);
+    std::string line = r.name;
+    char num[24];
+    for (const int64_t v : {r.length, (int64_t)t.rows, (int64_t)t.rows_hit, (int64_t)t.other, (int64_t)t.other_hit, t.rows_bases, t.other_bases, t.both_bases}) {
+        line += '\t';
+        line.append(num, (size_t)(std::to_chars(num, num + sizeof num, v).ptr - num));
+    }
+    line += '\n';
+    write(line.data(), line.size());
+}
+
 // One entry per row output.  The order is the order of everything that is done for all of them: the "needs" checks, opening the
 // files (binary), producing a record's texts, the keys of --timing.
 struct Output {
@@ -183,18 +233,29 @@ struct Output {
     bool quotes_bed;                         // its lines quote the rows' lines: it needs RecordRows::bed_text
     void (*produce)(RibbitHandle *, const RecordRows &, const Settings &, const Sink &);      // one record's text for this output
     Qualifier qualifiers[MAX_QUALIFIERS];    // (name null: none)
+    bool needs_other;                        // it compares the rows with the intervals of --overlap-with
 };
-constexpr size_t N_OUTPUTS = 4;
+constexpr size_t N_OUTPUTS = 6;
 const Output kOutputs[N_OUTPUTS] = {
     {"masked-fasta", MASK, false, produce_masked,
      {{"mask", Qualifier::SOFT_HARD, 0, 0, 0, nullptr, &Settings::mask_mode},
-      {"mask-width", Qualifier::BASES, 0, 999999999, 9, "0 or more", &Settings::mask_width}}},
+      {"mask-width", Qualifier::BASES, 0, 999999999, 9, "0 or more", &Settings::mask_width}}, false},
     {"repeat-fasta", REPEATS, false, produce_repeats,
-     {{"flank", Qualifier::BASES, 0, 999999999, 9, "0 or more, at most 9 digits", &Settings::flank}, {}}},
+     {{"flank", Qualifier::BASES, 0, 999999999, 9, "0 or more, at most 9 digits", &Settings::flank}, {}}, false},
     {"loci-bed", LOCI, true, produce_loci,
-     {{"loci-gap", Qualifier::BASES, 0, 2147483647, 10, "0 .. 2147483647", &Settings::loci_gap}, {}}},
+     {{"loci-gap", Qualifier::BASES, 0, 2147483647, 10, "0 .. 2147483647", &Settings::loci_gap}, {}}, false},
     {"density-bedgraph", DENSITY, false, produce_density,
-     {{"density-window", Qualifier::BASES, 1, 2147483647, 10, "1 .. 2147483647", &Settings::density_window}, {}}}};
+     {{"density-window", Qualifier::BASES, 1, 2147483647, 10, "1 .. 2147483647", &Settings::density_window}, {}}, false},
+    {"overlap-bed", OVERLAP, true, produce_overlap_bed, {{}, {}}, true},
+    {"overlap-summary", OVERLAP, false, produce_overlap_summary, {{}, {}}, true}};
+
+// the row outputs that are on, by stage: an output whose stage an earlier one has already named is left out (--timing, RIBBIT_PROFILE)
+std::vector<Stage> stages_on(const std::array<bool, N_OUTPUTS> &on) {
+    std::vector<Stage> stages;
+    for (size_t k = 0; k < N_OUTPUTS; ++k)
+        if (on[k] && std::find(stages.begin(), stages.end(), kOutputs[k].stage) == stages.end()) stages.push_back(kOutputs[k].stage);
+    return stages;
+}
 
 // which outputs are on for one record, and where each one's text goes (an empty sink: off)
 struct RowJobs {
@@ -222,6 +283,7 @@ struct Options {
     std::vector<int> devices;                     // --devices / RIBBIT_DEVICES: GPUs the records are dealt over (empty: `device` alone)
     int jobs = 0;                                 // records in flight PER DEVICE; 0 = automatic
     std::string timing;                           // --timing FILE: a JSON record of the run (the reference has cerr progress lines only)
+    std::string other_path;                       // --overlap-with FILE: the intervals the overlap outputs compare the rows with
     std::array<std::string, N_OUTPUTS> row_path;                  // the row outputs' files, as kOutputs orders them (empty: off)
     std::array<std::array<bool, MAX_QUALIFIERS>, N_OUTPUTS> qualifier_given{};
     Settings settings;
@@ -266,7 +328,17 @@ const char *kHelp =
     "  --density-bedgraph arg        (ribbit-hip) also write a bedGraph to this file: one line per window of every record,\n"
     "                                empty windows too: name, start, end, and the NUMBER OF BASES of the window that BED\n"
     "                                rows cover (an exact integer count, not a fraction: divide by end - start for one)\n"
-    "  --density-window arg          (ribbit-hip) bases per window of --density-bedgraph, 1 or more. Default: 10000\n";
+    "  --density-window arg          (ribbit-hip) bases per window of --density-bedgraph, 1 or more. Default: 10000\n"
+    "  --overlap-with arg            (ribbit-hip) a second BED file (name, start, end, further columns ignored; a truth set,\n"
+    "                                another caller's rows, an annotation) that --overlap-bed and --overlap-summary compare\n"
+    "                                the BED rows of every record with; a name is matched against the record names\n"
+    "  --overlap-bed arg             (ribbit-hip) also write every BED row to this file with two columns appended: the number\n"
+    "                                of intervals of --overlap-with that the row overlaps, and the number of the row's bases\n"
+    "                                that those intervals cover\n"
+    "  --overlap-summary arg         (ribbit-hip) also write one line per record to this file: name, length, rows, rows_hit,\n"
+    "                                other, other_hit, rows_bases, other_bases, both_bases (exact counts, not fractions: recall\n"
+    "                                is other_hit / other, precision rows_hit / rows, the base-level Jaccard index\n"
+    "                                both_bases / (rows_bases + other_bases - both_bases))\n";
 
 bool parse_device_list(const std::string &value, std::vector<int> &out) {
     out.clear();
@@ -287,7 +359,8 @@ bool is_number(const std::string &s) { return !s.empty() && std::all_of(s.begin(
 int parse_arguments(int argc, char **argv, Options &o) {
     static const std::map<std::string, std::string> longs = {
         {"help", "h"}, {"input-file", "i"}, {"output-file", "o"}, {"min-motif-length", "m"}, {"max-motif-length", "M"},
-        {"purity", "p"}, {"min-length", "l"}, {"min-units", "U"}, {"perfect-units", "P"}, {"device", "D"}, {"jobs", "J"}, {"devices", "G"}, {"timing", "T"}};
+        {"purity", "p"}, {"min-length", "l"}, {"min-units", "U"}, {"perfect-units", "P"}, {"device", "D"}, {"jobs", "J"}, {"devices", "G"}, {"timing", "T"},
+        {"overlap-with", "W"}};
     bool help = false;
     for (int a = 1; a < argc; ++a) {
         std::string arg = argv[a], key, value;
@@ -343,14 +416,48 @@ int parse_arguments(int argc, char **argv, Options &o) {
         else if (key == "D") o.device = std::atoi(value.c_str());
         else if (key == "J") o.jobs = std::atoi(value.c_str());
         else if (key == "T") o.timing = value;
+        else if (key == "W") { if (value.empty()) die("--overlap-with wants a file name"); o.other_path = value; }
         else if (key == "G") { if (!parse_device_list(value, o.devices)) die("--devices wants a comma separated list of GPU ordinals, got '" + value + "'"); }
     }
     if (help) { std::cerr << kHelp << "\n"; return 0; }                       // ribbit.cpp:114-117
     for (size_t k = 0; k < N_OUTPUTS; ++k)
         for (size_t q = 0; q < MAX_QUALIFIERS && o.row_path[k].empty(); ++q)
             if (o.qualifier_given[k][q]) die(std::string("--") + kOutputs[k].qualifiers[q].name + " needs --" + kOutputs[k].option);
+    bool needs_other = false;
+    for (size_t k = 0; k < N_OUTPUTS; ++k) needs_other = needs_other || (kOutputs[k].needs_other && !o.row_path[k].empty());
+    if (!o.other_path.empty() && !needs_other) die("--overlap-with needs --overlap-bed or --overlap-summary");
+    for (size_t k = 0; k < N_OUTPUTS; ++k)
+        if (kOutputs[k].needs_other && !o.row_path[k].empty() && o.other_path.empty()) die(std::string("--") + kOutputs[k].option + " needs --overlap-with");
     if (o.fasta.empty()) { std::cerr << "ERROR: Please specify an input fasta file!\n"; return 0; }   // :122-126
     return 1;
+}
+
+// one decimal field of a BED line; false unless it is [-]digits within int32
+bool parse_int32(const char *p, const char *end, int32_t *out) {
+    int64_t v = 0;
+    const auto r = std::from_chars(p, end, v);
+    if (p == end || r.ec != std::errc() || r.ptr != end || v < INT32_MIN || v > INT32_MAX) return false;
+    *out = (int32_t)v;
+    return true;
+}
+
+// --overlap-with FILE: name, start, end and whatever follows, tab separated; empty lines and lines that start with '#', "track" or
+// "browser" are skipped.  A name may come anywhere in the file; its intervals keep the file's order.
+void read_other_bed(const std::string &path, OtherBed &other) {
+    std::ifstream in(path, std::ios::binary);
+    if (!in) die("--overlap-with: cannot open '" + path + "' for reading");
+    std::string line;
+    for (size_t k = 1; std::getline(in, line); ++k) {
+        if (line.empty() || line[0] == '#' || line.rfind("track", 0) == 0 || line.rfind("browser", 0) == 0) continue;
+        const size_t t1 = line.find('\t'), t2 = t1 == std::string::npos ? t1 : line.find('\t', t1 + 1);
+        const size_t t3 = t2 == std::string::npos ? t2 : std::min(line.find('\t', t2 + 1), line.size());
+        int32_t s = 0, e = 0;
+        if (t2 == std::string::npos || !parse_int32(line.data() + t1 + 1, line.data() + t2, &s) || !parse_int32(line.data() + t2 + 1, line.data() + t3, &e))
+            die("--overlap-with: line " + std::to_string(k) + " of '" + path + "' is not a BED line (name, start, end)");
+        std::vector<int32_t> &iv = other.by_name[line.substr(0, t1)].iv;
+        iv.push_back(s);
+        iv.push_back(e);
+    }
 }
 
 // parseDualtypeArgs, ribbit.cpp:25-64: one integer for every motif size in range, or a two-column TSV
@@ -491,7 +598,7 @@ void process_sequence(RibbitHandle *h, const RibbitRefineParams &prm, const std:
     { StageClock c(DISPATCH); check(ribbit_hip_dispatch_seeds(h, &d, &nd)); }
     // one record over several GPUs: only worth it from a few hundred thousand seeds on (RIBBIT_SHARD_MIN_SEEDS: a test hook)
     static const size_t shard_min = std::getenv("RIBBIT_SHARD_MIN_SEEDS") ? (size_t)std::atoll(std::getenv("RIBBIT_SHARD_MIN_SEEDS")) : 400000;
-    RecordRows rows{name, length, {}, nullptr, 0, {}};
+    RecordRows rows{name, length, {}, nullptr, 0, {}, settings.other ? settings.other->of(name) : nullptr};
     const bool want_rows = jobs.any();
     if (helpers && !helpers->empty() && nd >= shard_min && nd >= 2 * (helpers->size() + 1)) {
         StageClock c(REFINE_BED);
@@ -521,6 +628,11 @@ int main(int argc, char **argv) {
     Options opt;
     if (!parse_arguments(argc, argv, opt)) return 1;                          // ribbit.cpp:193-195
 
+    OtherBed other;                 // (read before any file is made and any GPU is touched)
+    if (!opt.other_path.empty()) {
+        read_other_bed(opt.other_path, other);
+        opt.settings.other = &other;
+    }
     std::ofstream file;
     if (!opt.out.empty()) file.open(opt.out);
     std::ostream &out = opt.out.empty() ? std::cerr : file;                   // ribbit.cpp:199-205
@@ -680,6 +792,7 @@ int main(int argc, char **argv) {
         const int got = reader ? ribbit_fasta_next(reader, &name, &bases, &length, &is_last) : 0;
         if (got < 0) { std::lock_guard<std::mutex> lk(mu); failed = true; failure = ribbit_fasta_last_error(); break; }
         if (got == 0) break;
+        if (const auto it = other.by_name.find(name); it != other.by_name.end()) it->second.is_record = true;
         if (is_last) { last_name = name; last_bases = bases; last_length = length; break; }
         std::unique_lock<std::mutex> lk(mu);
         cv.wait(lk, [&] { return queue.size() < (size_t)(2 * workers) || failed; });       // bounded look-ahead
@@ -738,16 +851,18 @@ int main(int argc, char **argv) {
            << ", \"min_motif\": " << opt.min_motif << ", \"max_motif\": " << opt.max_motif << ", \"devices\": " << ndev << ", \"jobs_per_device\": " << jobs
            << ", \"stage_ms_summed_over_records\": {";
         for (int s = 0; s < N_FIXED_STAGES; ++s) tf << (s ? ", \"" : "\"") << kStageNames[s].key << "\": " << g_stage_ms[s];
-        for (size_t k = 0; k < N_OUTPUTS; ++k)
-            if (row_on[k]) tf << ", \"" << kStageNames[kOutputs[k].stage].key << "\": " << g_stage_ms[kOutputs[k].stage];
+        for (const Stage s : stages_on(row_on)) tf << ", \"" << kStageNames[s].key << "\": " << g_stage_ms[s];
         tf << "}}\n";
     }
     if (std::getenv("RIBBIT_PROFILE")) {
         std::cerr << "[stages, ms over all records]";
         for (int s = 0; s < N_FIXED_STAGES; ++s) std::cerr << (s ? "  " : " ") << kStageNames[s].label << " " << g_stage_ms[s];
-        for (size_t k = 0; k < N_OUTPUTS; ++k)
-            if (row_on[k]) std::cerr << "  " << kStageNames[kOutputs[k].stage].label << " " << std::to_string(g_stage_ms[kOutputs[k].stage]);
+        for (const Stage s : stages_on(row_on)) std::cerr << "  " << kStageNames[s].label << " " << std::to_string(g_stage_ms[s]);
         std::cerr << "\n";
     }
+    size_t ignored = 0, ignored_names = 0;
+    for (const auto &group : other.by_name)
+        if (!group.second.is_record) { ignored += group.second.iv.size() / 2; ++ignored_names; }
+    if (ignored) std::cerr << "ribbit-hip: --overlap-with: " << ignored << " intervals of " << ignored_names << " names that are no record of the input were ignored\n";
     return status;
 }

@@ -157,6 +157,11 @@ def simulate_sequence(total_len: int, seed: int, m_lo: int = 2, m_hi: int = 100,
     return seq, truth
 
 
+def truth_bed_text(name: str, truth) -> str:
+    """The truth list of simulate_sequence as BED lines: name, start, end, motif size, motif (what ribbit-hip --overlap-with reads)."""
+    return "".join(f"{name}\t{start}\t{end}\t{m}\t{motif}\n" for start, end, m, motif in truth)
+
+
 def random_sequence(total_len: int, seed: int, n_fraction: float = 0.001,
                     n_run_lo: int = 1000, n_run_hi: int = 10000) -> bytes:
     """Uniform ACGT control with a fraction of the bases inside N runs."""
