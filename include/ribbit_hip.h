@@ -427,6 +427,36 @@ int ribbit_host_record_overlap(int64_t length, const int32_t *rows, size_t n, co
 int ribbit_bed_overlap_text(const char *bed_text, size_t bed_len, const int32_t *per_row, size_t n, char **text, size_t *len);
 
 /*
+ * ---- the best non-overlapping rows --------------------------------------------------------------------------------
+ * A non-redundant call set: a subset of the record's own rows in which no two overlap, chosen so that it covers as many
+ * bases as any such subset can, by ascending position.  With L the record's length:
+ *   Clipping:    every row i = (s, e) is clipped as the mask clips it, s' = max(s, 0), e' = min(e, L), in 64-bit; a row
+ *                with s' >= e' is empty and is never selected.
+ *   Order:       the non-empty rows ordered by (e', s', i) ascending, at positions k = 1 .. r; w_k = e'_k - s'_k.
+ *   Predecessor: p(k) = the number of ordered rows with e' <= s'_k (all of them come before k; an abutting row counts:
+ *                abutting rows do not overlap).
+ *   Forward:     dp[0] = 0, dp[k] = max(dp[k - 1], w_k + dp[p(k)]).
+ *   Backward:    k = r; while k > 0: if w_k + dp[p(k)] > dp[k - 1] (strictly), row k is selected and k = p(k);
+ *                otherwise k = k - 1.
+ *   Result:      the indices (into the rows given) of the selected rows by ascending s', which is also ascending e';
+ *                bases = dp[r], the bases the selection covers.
+ * No other set of pairwise non-overlapping rows covers more bases; the rule fixes one optimal set exactly (among
+ * identical rows the lowest index is the one selected); dp never exceeds L < 2^31.
+ */
+/* The selection for the loaded record's n rows (at most INT32_MAX), on the GPU.  *rows: *n_best indices of handle-owned
+ * page-locked memory, valid until the handle's next best call, load or close.  L = 0, n = 0 and rows that are all empty
+ * are no errors: *n_best = 0, *bases = 0. */
+int ribbit_hip_record_best(RibbitHandle *h, const int32_t *intervals, size_t n, const int32_t **rows, size_t *n_best,
+                           int64_t *bases);
+/* Host-only twin (no GPU) for a record of `length` bases (0 <= length < 2^31): one sort, one forward and one backward
+ * sweep.  *rows malloc'ed, release with ribbit_intervals_free(). */
+int ribbit_host_record_best(int64_t length, const int32_t *intervals, size_t n, int32_t **rows, size_t *n_best, int64_t *bases);
+/* Lines rows[0], rows[1], ... of bed_text (host only), byte for byte, each with its newline: the record's BED rows as
+ * ribbit_hip_refine_bed writes them, row i on line i (a last line without its newline counts, and is written with one, as ribbit_bed_overlap_text writes it).
+ * An index that is no line of bed_text: RIBBIT_E_ARG.  *text malloc'ed, release with ribbit_text_free(). */
+int ribbit_bed_rows_text(const char *bed_text, size_t bed_len, const int32_t *rows, size_t n_rows, char **text, size_t *len);
+
+/*
  * ---- streaming FASTA ingest ---------------------------------------------------------------------------------------
  * Replaces the reader loop of ribbit.cpp:269-280 (getline + `sequence += line` into one pageable std::string per
  * record).  The file is read in 16-MB blocks; line bodies are copied once, straight into a page-locked buffer

@@ -18,7 +18,8 @@ __all__ = ["RibbitHipError", "ScanParams", "Scanner", "library_path", "load_libr
            "RUN_NOT_OWNED", "RUN_HALF_START", "RUN_HALF_END",
            "MASK_MODES", "host_mask_record", "bed_intervals", "host_repeat_sequences",
            "LOCUS_DT", "host_record_loci", "host_record_density", "bed_loci_text",
-           "OverlapTotals", "OVERLAP_TOTALS", "host_record_overlap", "bed_overlap_text"]
+           "OverlapTotals", "OVERLAP_TOTALS", "host_record_overlap", "bed_overlap_text",
+           "host_record_best", "bed_rows_text"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -62,6 +63,7 @@ ABI_SYMBOLS = [
     "ribbit_hip_record_loci", "ribbit_hip_record_density", "ribbit_host_record_loci", "ribbit_host_record_density", "ribbit_loci_free",
     "ribbit_bed_loci_text",
     "ribbit_hip_record_overlap", "ribbit_host_record_overlap", "ribbit_bed_overlap_text",
+    "ribbit_hip_record_best", "ribbit_host_record_best", "ribbit_bed_rows_text",
 ]
 
 MASK_MODES = {"soft": 0, "hard": 1}     # RIBBIT_MASK_SOFT / RIBBIT_MASK_HARD
@@ -296,6 +298,9 @@ def load_library():
     L.ribbit_hip_record_overlap.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(OverlapTotals)]
     L.ribbit_host_record_overlap.argtypes = [i64, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(OverlapTotals)]
     L.ribbit_bed_overlap_text.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_hip_record_best.argtypes = [vp, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(i64)]
+    L.ribbit_host_record_best.argtypes = [i64, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(i64)]
+    L.ribbit_bed_rows_text.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
     _lib = L
     return L
 
@@ -702,6 +707,36 @@ def bed_overlap_text(bed, per_row) -> bytes:
         L.ribbit_text_free(text)
 
 
+def host_record_best(length: int, intervals):
+    """ribbit_host_record_best: the rows of a record of `length` bases of which no two overlap and which cover the most bases ->
+    (their indices by ascending start, int32; the bases they cover).  The contract is in include/ribbit_hip.h.  No GPU needed."""
+    L = load_library()
+    iv = _pairs(intervals)
+    rows, n, bases = C.c_void_p(), C.c_size_t(), C.c_int64()
+    rc = L.ribbit_host_record_best(int(length), iv.ctypes.data if len(iv) else None, len(iv), C.byref(rows), C.byref(n), C.byref(bases))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_host_record_best error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return _copy(rows.value, n.value, np.dtype("<i4")), int(bases.value)
+    finally:
+        L.ribbit_intervals_free(rows)
+
+
+def bed_rows_text(bed, rows) -> bytes:
+    """ribbit_bed_rows_text: lines rows[0], rows[1], ... of `bed` (one record's BED text, row i on line i), byte for byte."""
+    L = load_library()
+    text_in = bed.encode() if isinstance(bed, str) else bytes(bed)
+    idx = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
+    text, n = C.c_void_p(), C.c_size_t()
+    rc = L.ribbit_bed_rows_text(text_in, len(text_in), idx.ctypes.data if len(idx) else None, len(idx), C.byref(text), C.byref(n))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_bed_rows_text error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return C.string_at(text.value, n.value)
+    finally:
+        L.ribbit_text_free(text)
+
+
 def host_perfect_runs_from_events(min_motif: int, max_motif: int, event_parts, count_parts):
     """ribbit_host_perfect_runs_from_events: per-rank (events, per-motif counts) -> paired runs. No GPU needed."""
     L = load_library()
@@ -1038,6 +1073,13 @@ class Scanner:
         self._check(self._L.ribbit_hip_record_overlap(self._h, iv.ctypes.data if len(iv) else None, len(iv), ot.ctypes.data if len(ot) else None, len(ot),
                                                       C.byref(per_row), C.byref(totals)))
         return _copy(per_row.value, 2 * len(iv), np.dtype("<i4")).reshape(-1, 2), totals.as_dict()
+
+    def record_best(self, intervals):
+        """The loaded record's best non-overlapping rows on the GPU (ribbit_hip_record_best); see host_record_best"""
+        iv = _pairs(intervals)
+        rows, n, bases = C.c_void_p(), C.c_size_t(), C.c_int64()
+        self._check(self._L.ribbit_hip_record_best(self._h, iv.ctypes.data if len(iv) else None, len(iv), C.byref(rows), C.byref(n), C.byref(bases)))
+        return _copy(rows.value, n.value, np.dtype("<i4")), int(bases.value)
 
     def record_density(self, intervals, window: int) -> np.ndarray:
         """The loaded record's covered bases per window on the GPU (ribbit_hip_record_density); see host_record_density"""

@@ -305,6 +305,20 @@ hipError_t launch_overlap(const uint32_t *a_bits, const uint32_t *b_bits, int64_
                           uint64_t *ranks, uint32_t *keys, RibbitOverlapTotals *totals, int32_t *per_row, void *scratch, size_t scratch_bytes,
                           hipStream_t stream);
 
+// best.hip: the best non-overlapping rows of the loaded record (api_best.cpp).  rows: the n >= 1 rows on the device.  keys: 2 n
+// words (the rows' keys | the keys sorted; the first half then holds w << 32 | p per sorted position), work: 3 n ints (the row
+// indices | the indices in sorted order | the reversed suffix minimum of s'; the first third then holds dp), flags: 2 n bytes
+// (segment heads | take flags), scratch: best_scratch_bytes(n, length).  totals is zeroed and filled; selected: the chosen
+// rows' indices by ascending start, totals->selected of them (n ints of room).
+struct BestTotals {
+    unsigned long long selected;      // rows chosen
+    unsigned long long bases;         // bases they cover
+    uint32_t rows, spare;             // non-empty rows
+};
+size_t best_scratch_bytes(int64_t n, int64_t length);
+hipError_t launch_best(const int32_t *rows, int64_t n, int64_t length, uint64_t *keys, int32_t *work, uint8_t *flags, BestTotals *totals,
+                       int32_t *selected, void *scratch, size_t scratch_bytes, hipStream_t stream);
+
 // profiling aid: reads nwords dwords of src with one coalesced dword per lane (known byte count)
 void launch_calib_stream_read(const uint32_t *src, int64_t nwords, uint32_t *sink, hipStream_t stream);
 

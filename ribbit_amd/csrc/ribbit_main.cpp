@@ -5,7 +5,7 @@
 //   ribbit-hip -i in.fa [-o out.bed] [-m 2] [-M 100] [-p 0.85] [-l N|file] [--min-units N|file] [--perfect-units N|file]
 //              [--devices 0,1,...] [--jobs N] [--masked-fasta FILE [--mask soft|hard] [--mask-width N]]
 //              [--repeat-fasta FILE [--flank N]] [--loci-bed FILE [--loci-gap D]] [--density-bedgraph FILE [--density-window W]]
-//              [--overlap-with OTHER.bed [--overlap-bed FILE] [--overlap-summary FILE]]
+//              [--overlap-with OTHER.bed [--overlap-bed FILE] [--overlap-summary FILE]] [--best-bed FILE]
 //
 // Records are independent (ribbit.cpp:269-280 handles them one after the other); here up to --jobs of them are in
 // flight at once PER GPU, each on its own handle / HIP streams, so that the upload and GPU scans of one record overlap
@@ -20,13 +20,14 @@
 // (ribbit_hip_record_loci, ribbit_bed_loci_text) and --density-bedgraph the covered bases per window (ribbit_hip_record_density),
 // the same way again.  --overlap-with reads a second BED file, grouped by record name before the first record is scanned, and
 // --overlap-bed / --overlap-summary set every record's rows against its intervals of that file (ribbit_hip_record_overlap): the
-// rows again with two columns more (ribbit_bed_overlap_text), and one line of counts per record.  The BED rows are read back once
-// per record, however many of the six are asked for.
+// rows again with two columns more (ribbit_bed_overlap_text), and one line of counts per record.  --best-bed writes the rows of
+// every record that ribbit_hip_record_best selects, a subset in which no two overlap and which covers the most bases, by ascending
+// start (ribbit_bed_rows_text).  The BED rows are read back once per record, however many of the seven are asked for.
 //
-// These six are the ROW OUTPUTS, and each is described once, by its entry of kOutputs below: its file option, its stage (enum
+// These seven are the ROW OUTPUTS, and each is described once, by its entry of kOutputs below: its file option, its stage (enum
 // Stage, with the stage's names beside it), its qualifier options with their ranges and wording (defaults: Settings), and the function that
 // makes one record's text from the record's rows.  Parsing, the "needs" checks, opening the files, the sinks of the pipelined
-// records and of the last one, --timing and the RIBBIT_PROFILE line are loops over that table.  A seventh row output is: a stage in
+// records and of the last one, --timing and the RIBBIT_PROFILE line are loops over that table.  An eighth row output is: a stage in
 // the enum and its names, the qualifiers' fields in Settings, a produce function, an entry of kOutputs, and its lines of kHelp.
 //
 // Reproduced quirks: -p is accepted and ignored (Q1); without -o the BED rows go to
@@ -72,12 +73,13 @@ void check(int rc) {
 }
 
 // The stages of a record: the six every record goes through, then one per row output, in the order of kOutputs.
-enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, OVERLAP, N_STAGES };
+enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, OVERLAP, BEST, N_STAGES };
 constexpr int N_FIXED_STAGES = MASK;
 // a stage's key in --timing's stage_ms_summed_over_records and its label in the RIBBIT_PROFILE line
 const struct { const char *key, *label; } kStageNames[N_STAGES] = {
     {"load", "load"}, {"perfect", "perfect"}, {"substitutions", "substitutions"}, {"anchored", "anchored"}, {"dispatch", "dispatch"},
-    {"refine_and_bed", "refine+BED"}, {"mask", "mask"}, {"repeats", "repeats"}, {"loci", "loci"}, {"density", "density"}, {"overlap", "overlap"}};
+    {"refine_and_bed", "refine+BED"}, {"mask", "mask"}, {"repeats", "repeats"}, {"loci", "loci"}, {"density", "density"}, {"overlap", "overlap"},
+    {"best", "best"}};
 
 // wall time per stage, summed over the records (--timing, RIBBIT_PROFILE=1)
 double g_stage_ms[N_STAGES] = {};
@@ -225,6 +227,19 @@ void produce_overlap_summary(RibbitHandle *h, const RecordRows &r, const Setting
     write(line.data(), line.size());
 }
 
+void produce_best(RibbitHandle *h, const RecordRows &r, const Settings &, const Sink &write) {
+    const int32_t *chosen = nullptr;
+    size_t n_chosen = 0;
+    int64_t bases = 0;
+    char *text = nullptr;
+    size_t len = 0;
+    StageClock c(BEST);
+    check(ribbit_hip_record_best(h, r.iv.data(), r.n(), &chosen, &n_chosen, &bases));
+    check(ribbit_bed_rows_text(r.bed_text, r.bed_len, chosen, n_chosen, &text, &len));
+    write(text, len);
+    ribbit_text_free(text);
+}
+
 // One entry per row output.  The order is the order of everything that is done for all of them: the "needs" checks, opening the
 // files (binary), producing a record's texts, the keys of --timing.
 struct Output {
@@ -235,7 +250,7 @@ struct Output {
     Qualifier qualifiers[MAX_QUALIFIERS];    // (name null: none)
     bool needs_other;                        // it compares the rows with the intervals of --overlap-with
 };
-constexpr size_t N_OUTPUTS = 6;
+constexpr size_t N_OUTPUTS = 7;
 const Output kOutputs[N_OUTPUTS] = {
     {"masked-fasta", MASK, false, produce_masked,
      {{"mask", Qualifier::SOFT_HARD, 0, 0, 0, nullptr, &Settings::mask_mode},
@@ -247,7 +262,8 @@ const Output kOutputs[N_OUTPUTS] = {
     {"density-bedgraph", DENSITY, false, produce_density,
      {{"density-window", Qualifier::BASES, 1, 2147483647, 10, "1 .. 2147483647", &Settings::density_window}, {}}, false},
     {"overlap-bed", OVERLAP, true, produce_overlap_bed, {{}, {}}, true},
-    {"overlap-summary", OVERLAP, false, produce_overlap_summary, {{}, {}}, true}};
+    {"overlap-summary", OVERLAP, false, produce_overlap_summary, {{}, {}}, true},
+    {"best-bed", BEST, true, produce_best, {{}, {}}, false}};
 
 // the row outputs that are on, by stage: an output whose stage an earlier one has already named is left out (--timing, RIBBIT_PROFILE)
 std::vector<Stage> stages_on(const std::array<bool, N_OUTPUTS> &on) {
@@ -338,7 +354,10 @@ const char *kHelp =
     "  --overlap-summary arg         (ribbit-hip) also write one line per record to this file: name, length, rows, rows_hit,\n"
     "                                other, other_hit, rows_bases, other_bases, both_bases (exact counts, not fractions: recall\n"
     "                                is other_hit / other, precision rows_hit / rows, the base-level Jaccard index\n"
-    "                                both_bases / (rows_bases + other_bases - both_bases))\n";
+    "                                both_bases / (rows_bases + other_bases - both_bases))\n"
+    "  --best-bed arg                (ribbit-hip) also write a non-redundant call set to this file: the BED rows of every record\n"
+    "                                of which no two overlap and which together cover the most bases, each row as it is in\n"
+    "                                the BED, sorted by start\n";
 
 bool parse_device_list(const std::string &value, std::vector<int> &out) {
     out.clear();
