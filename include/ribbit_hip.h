@@ -457,6 +457,63 @@ int ribbit_host_record_best(int64_t length, const int32_t *intervals, size_t n, 
 int ribbit_bed_rows_text(const char *bed_text, size_t bed_len, const int32_t *rows, size_t n_rows, char **text, size_t *len);
 
 /*
+ * ---- the rows by canonical motif class ----------------------------------------------------------------------------
+ * A census of what repeats: CA, AC, TG and GT are one class, and so are GATA, ATAG, TATC and their other rotations.
+ *   Motif of a row:  column 4 of the BED row, found from the right (the eighth column from the end, as ribbit_bed_loci_text
+ *                    finds columns: a name with a tab in it works).  A non-empty string over A, C, G, T of at most 1023
+ *                    bytes (refinement writes nothing else, and -M ends at 990); anything else is RIBBIT_E_ARG.
+ *   Class of a motif u of length k: of the 2k strings that are the k cyclic rotations of u and the k cyclic rotations of
+ *                    its reverse complement (A<->T, C<->G, reversed) the least in byte order A < C < G < T.  It has length
+ *                    k: there is no reduction to a primitive root (ACAC stays a 4-mer class; column 5 tells its atomicity).
+ *   Strand:          '+' if the class is a rotation of u itself, '-' otherwise.  A motif whose reverse complement is one of
+ *                    its own rotations (AT, ACGT) is '+'.
+ *   Order of classes: ascending by length, then by byte order.
+ *   Group of a class, within one record of length L: with s' = max(s, 0), e' = min(e, L) (the mask's clipping, in 64-bit)
+ *                    and a row's width max(0, e' - s'):
+ *                    rows        = the number of the record's rows whose motif has that class; every row counts, an empty
+ *                                  one too;
+ *                    bases       = the sum of those rows' widths, int64.  NOT a union: rows of one class overlap;
+ *                    longest_row = the index of the row of the largest width, among equals the lowest index (empty rows
+ *                                  have width 0 and tie with each other);
+ *                    first_row   = the lowest row index of the group; the class's text is read from that row.
+ * For motifs of at most 10 bases on the '+' strand alone, the least rotation is what the reference's calculateRepeatClass
+ * returns (its 2-bit codes order as the letters do).
+ */
+typedef struct { int64_t bases; int32_t length, rows, first_row, longest_row; } RibbitMotifClass;
+/* The motifs of a BED text (host only), concatenated: motif i is pool[offsets[i] .. offsets[i + 1]); offsets has n + 1
+ * entries.  A line that is not a row, or a motif that is not as above: RIBBIT_E_ARG.  *pool malloc'ed, release with
+ * ribbit_text_free(); *offsets malloc'ed, release with ribbit_intervals_free(). */
+int ribbit_bed_motifs(const char *bed_text, size_t bed_len, char **pool, int32_t **offsets, size_t *n);
+/* The classes of the loaded record's n rows (at most INT32_MAX), on the GPU.  intervals: (start, end) per row; motifs and
+ * offsets as ribbit_bed_motifs hands them out (offsets[0] = 0, a pool below 2^31 bytes).  *classes: the class of row i at offsets[i], as
+ * long as its motif; *strands: one byte per row, '+' or '-'; *groups: *n_groups groups in class order.  All three are
+ * handle-owned page-locked memory, valid until the handle's next classes call, load or close.  n == 0: no groups.  L == 0
+ * is no error: every row is a row of 0 bases.  Offsets that do not ascend, an empty motif or one of more than 1023 bytes,
+ * a byte outside ACGT, a pool of 2^31 bytes or more, n > INT32_MAX: RIBBIT_E_ARG.  Before a load: RIBBIT_E_STATE. */
+int ribbit_hip_record_classes(RibbitHandle *h, const int32_t *intervals, size_t n, const char *motifs, const int32_t *offsets,
+                              const char **classes, const char **strands, const RibbitMotifClass **groups, size_t *n_groups);
+/* Host-only twin (no GPU) for a record of `length` bases (0 <= length < 2^31): a least rotation per row, one sort of the
+ * rows by (length, class, index), one sweep.  *classes and *strands malloc'ed, release with ribbit_text_free(); *groups
+ * malloc'ed, release with ribbit_motif_classes_free(). */
+int ribbit_host_record_classes(int64_t length, const int32_t *intervals, size_t n, const char *motifs, const int32_t *offsets,
+                               char **classes, char **strands, RibbitMotifClass **groups, size_t *n_groups);
+void ribbit_motif_classes_free(RibbitMotifClass *groups);
+/* The record's BED rows with class and strand appended (host only): line i of bed_text, byte for byte, then a tab, the
+ * class of row i, a tab, its strand and a newline: 13 columns.  bed_text: the rows as ribbit_hip_refine_bed writes them,
+ * row i on line i (a last line without its newline counts, and is written with one, as ribbit_bed_overlap_text writes it).
+ * A bed_text that does not have n lines, offsets that do not ascend: RIBBIT_E_ARG.  *text malloc'ed, release with
+ * ribbit_text_free(). */
+int ribbit_bed_class_text(const char *bed_text, size_t bed_len, const char *classes, const int32_t *offsets, const char *strands,
+                          size_t n, char **text, size_t *len);
+/* One line per group of one record (host only), in class order, seven tab-separated columns: name, class, length, rows,
+ * bases, then start and end of longest_row as the BED has them, which are taken from `intervals` (the n rows the groups were
+ * made from, unclipped: what ribbit_bed_intervals reads from the record's BED text).  The class's text is read at
+ * offsets[first_row].  A first_row or longest_row that is no row, a length that is not the row's: RIBBIT_E_ARG.  *text
+ * malloc'ed, release with ribbit_text_free(). */
+int ribbit_class_summary_text(const char *name, const int32_t *intervals, size_t n, const char *classes, const int32_t *offsets,
+                              const RibbitMotifClass *groups, size_t n_groups, char **text, size_t *len);
+
+/*
  * ---- streaming FASTA ingest ---------------------------------------------------------------------------------------
  * Replaces the reader loop of ribbit.cpp:269-280 (getline + `sequence += line` into one pageable std::string per
  * record).  The file is read in 16-MB blocks; line bodies are copied once, straight into a page-locked buffer

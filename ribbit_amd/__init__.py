@@ -19,7 +19,8 @@ __all__ = ["RibbitHipError", "ScanParams", "Scanner", "library_path", "load_libr
            "MASK_MODES", "host_mask_record", "bed_intervals", "host_repeat_sequences",
            "LOCUS_DT", "host_record_loci", "host_record_density", "bed_loci_text",
            "OverlapTotals", "OVERLAP_TOTALS", "host_record_overlap", "bed_overlap_text",
-           "host_record_best", "bed_rows_text"]
+           "host_record_best", "bed_rows_text",
+           "MOTIF_CLASS_DT", "bed_motifs", "host_record_classes", "bed_class_text", "class_summary_text"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -34,6 +35,7 @@ RUN_DT = np.dtype([("start", "<i4"), ("end", "<i4"), ("mlen", "<i4"), ("term", "
 CALL_DT = np.dtype([("pos", "<i4"), ("mlen", "<i4"), ("start", "<i4"), ("end", "<i4")])
 SEED_DT = np.dtype([("start", "<i4"), ("end", "<i4"), ("mlen", "<i4"), ("type", "<i4")])
 LOCUS_DT = np.dtype([(n, "<i4") for n in ("start", "end", "rows", "covered", "best_row")])      # RibbitLocus
+MOTIF_CLASS_DT = np.dtype([("bases", "<i8")] + [(n, "<i4") for n in ("length", "rows", "first_row", "longest_row")])      # RibbitMotifClass
 
 # every symbol include/ribbit_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -64,6 +66,8 @@ ABI_SYMBOLS = [
     "ribbit_bed_loci_text",
     "ribbit_hip_record_overlap", "ribbit_host_record_overlap", "ribbit_bed_overlap_text",
     "ribbit_hip_record_best", "ribbit_host_record_best", "ribbit_bed_rows_text",
+    "ribbit_bed_motifs", "ribbit_hip_record_classes", "ribbit_host_record_classes", "ribbit_motif_classes_free", "ribbit_bed_class_text",
+    "ribbit_class_summary_text",
 ]
 
 MASK_MODES = {"soft": 0, "hard": 1}     # RIBBIT_MASK_SOFT / RIBBIT_MASK_HARD
@@ -301,6 +305,13 @@ def load_library():
     L.ribbit_hip_record_best.argtypes = [vp, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(i64)]
     L.ribbit_host_record_best.argtypes = [i64, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(i64)]
     L.ribbit_bed_rows_text.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_bed_motifs.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_hip_record_classes.argtypes = [vp, vp, C.c_size_t, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_host_record_classes.argtypes = [i64, vp, C.c_size_t, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_motif_classes_free.argtypes = [vp]
+    L.ribbit_motif_classes_free.restype = None
+    L.ribbit_bed_class_text.argtypes = [C.c_char_p, C.c_size_t, vp, vp, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_class_summary_text.argtypes = [C.c_char_p, vp, C.c_size_t, vp, vp, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
     _lib = L
     return L
 
@@ -737,6 +748,101 @@ def bed_rows_text(bed, rows) -> bytes:
         L.ribbit_text_free(text)
 
 
+def bed_motifs(text):
+    """ribbit_bed_motifs: column 4 of every row of BED text as refine_bed writes it -> (the motifs concatenated, bytes; their
+    n + 1 offsets, int32)."""
+    L = load_library()
+    raw = text.encode() if isinstance(text, str) else bytes(text)
+    pool, offsets, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
+    rc = L.ribbit_bed_motifs(raw, len(raw), C.byref(pool), C.byref(offsets), C.byref(n))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_bed_motifs error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        off = _copy(offsets.value, n.value + 1, np.dtype("<i4"))
+        return C.string_at(pool.value, int(off[-1])), off
+    finally:
+        L.ribbit_text_free(pool)
+        L.ribbit_intervals_free(offsets)
+
+
+def _class_args(intervals, motifs, offsets):
+    """the rows, the motif pool and its offsets as the C ABI takes them; `motifs` may also be a list of strings (offsets None)"""
+    iv = _pairs(intervals)
+    if offsets is None:
+        parts = [m.encode() if isinstance(m, str) else bytes(m) for m in motifs]
+        offsets = np.concatenate([[0], np.cumsum([len(m) for m in parts], dtype=np.int64)])
+        motifs = b"".join(parts)
+    pool = motifs.encode() if isinstance(motifs, str) else bytes(motifs)
+    off = np.asarray(offsets)
+    if off.ndim != 1 or len(off) != len(iv) + 1:
+        raise ValueError(f"{len(iv)} rows want {len(iv) + 1} offsets")
+    if len(off) and (off.min() < -(1 << 31) or off.max() >= (1 << 31)):
+        raise ValueError("an offset is not an int32")
+    return iv, pool, np.ascontiguousarray(off, dtype=np.int32)
+
+
+def host_record_classes(length: int, intervals, motifs, offsets=None):
+    """ribbit_host_record_classes: the rows of a record of `length` bases by canonical motif class -> (the rows' classes
+    concatenated at the motifs' offsets, bytes; a strand byte per row, bytes; the groups in class order, a MOTIF_CLASS_DT array).
+    motifs, offsets: as bed_motifs returns them, or a list of strings and None.  The contract is in include/ribbit_hip.h.  No
+    GPU needed."""
+    L = load_library()
+    iv, pool, off = _class_args(intervals, motifs, offsets)
+    classes, strands, groups, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t()
+    rc = L.ribbit_host_record_classes(int(length), iv.ctypes.data if len(iv) else None, len(iv), pool, off.ctypes.data, C.byref(classes), C.byref(strands),
+                                      C.byref(groups), C.byref(n))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_host_record_classes error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return C.string_at(classes.value, int(off[-1])), C.string_at(strands.value, len(iv)), _copy(groups.value, n.value, MOTIF_CLASS_DT)
+    finally:
+        L.ribbit_text_free(classes)
+        L.ribbit_text_free(strands)
+        L.ribbit_motif_classes_free(groups)
+
+
+def bed_class_text(bed, classes, offsets, strands) -> bytes:
+    """ribbit_bed_class_text: the lines of `bed` (one record's BED text, row i on line i), each with row i's class and strand
+    appended as two more columns."""
+    L = load_library()
+    text_in = bed.encode() if isinstance(bed, str) else bytes(bed)
+    cls, st = bytes(classes), bytes(strands)
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int32).reshape(-1))
+    if len(off) != len(st) + 1 or len(cls) < int(off[-1]):
+        raise ValueError(f"{len(st)} rows want {len(st) + 1} offsets into the classes")
+    text, n = C.c_void_p(), C.c_size_t()
+    rc = L.ribbit_bed_class_text(text_in, len(text_in), cls, off.ctypes.data, st, len(st), C.byref(text), C.byref(n))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_bed_class_text error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return C.string_at(text.value, n.value)
+    finally:
+        L.ribbit_text_free(text)
+
+
+def class_summary_text(name, intervals, classes, offsets, groups) -> bytes:
+    """ribbit_class_summary_text: one line per group of one record: name, class, length, rows, bases, start and end of the
+    group's longest row as `intervals` (the rows the groups were made from) has them."""
+    L = load_library()
+    raw = name.encode() if isinstance(name, str) else bytes(name)
+    if b"\0" in raw:
+        raise ValueError("a record name cannot hold a NUL byte")
+    iv, cls = _pairs(intervals), bytes(classes)
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int32).reshape(-1))
+    if len(off) != len(iv) + 1 or len(cls) < int(off[-1]):
+        raise ValueError(f"{len(iv)} rows want {len(iv) + 1} offsets into the classes")
+    gr = np.ascontiguousarray(np.asarray(groups, dtype=MOTIF_CLASS_DT).reshape(-1))
+    text, n = C.c_void_p(), C.c_size_t()
+    rc = L.ribbit_class_summary_text(raw, iv.ctypes.data if len(iv) else None, len(iv), cls, off.ctypes.data, gr.ctypes.data if len(gr) else None, len(gr),
+                                     C.byref(text), C.byref(n))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_class_summary_text error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return C.string_at(text.value, n.value)
+    finally:
+        L.ribbit_text_free(text)
+
+
 def host_perfect_runs_from_events(min_motif: int, max_motif: int, event_parts, count_parts):
     """ribbit_host_perfect_runs_from_events: per-rank (events, per-motif counts) -> paired runs. No GPU needed."""
     L = load_library()
@@ -1080,6 +1186,14 @@ class Scanner:
         rows, n, bases = C.c_void_p(), C.c_size_t(), C.c_int64()
         self._check(self._L.ribbit_hip_record_best(self._h, iv.ctypes.data if len(iv) else None, len(iv), C.byref(rows), C.byref(n), C.byref(bases)))
         return _copy(rows.value, n.value, np.dtype("<i4")), int(bases.value)
+
+    def record_classes(self, intervals, motifs, offsets=None):
+        """The loaded record's rows by canonical motif class on the GPU (ribbit_hip_record_classes); see host_record_classes"""
+        iv, pool, off = _class_args(intervals, motifs, offsets)
+        classes, strands, groups, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t()
+        self._check(self._L.ribbit_hip_record_classes(self._h, iv.ctypes.data if len(iv) else None, len(iv), pool, off.ctypes.data, C.byref(classes),
+                                                      C.byref(strands), C.byref(groups), C.byref(n)))
+        return C.string_at(classes.value, int(off[-1])), C.string_at(strands.value, len(iv)), _copy(groups.value, n.value, MOTIF_CLASS_DT)
 
     def record_density(self, intervals, window: int) -> np.ndarray:
         """The loaded record's covered bases per window on the GPU (ribbit_hip_record_density); see host_record_density"""

@@ -319,6 +319,25 @@ size_t best_scratch_bytes(int64_t n, int64_t length);
 hipError_t launch_best(const int32_t *rows, int64_t n, int64_t length, uint64_t *keys, int32_t *work, uint8_t *flags, BestTotals *totals,
                        int32_t *selected, void *scratch, size_t scratch_bytes, hipStream_t stream);
 
+// classes.hip: the loaded record's rows grouped by canonical motif class (api_classes.cpp).  rows: the n >= 1 rows on the device;
+// offsets: n + 1 ascending offsets into pool, every motif 1 .. 1023 bytes over ACGT (the host has checked); pool: 8-byte aligned,
+// with 16 readable bytes behind the last motif.  work: classes_work_words(n) 64-bit words (the rows' sort items | the items sorted
+// | the groups' aggregates | head flags | group ids | the long rows' list), scratch: classes_scratch_bytes(n).  header is zeroed
+// and filled; groups: header->groups of them in class order (n of room); strands: n bytes; classes: the class of row i at
+// offsets[i], as many bytes as the pool.
+struct ClassItem {
+    uint64_t key;                     // 10 bits of length, then the first 27 bases of the class, 2 bits each
+    uint32_t row, off;                // the row and where its class lies in the pool
+};
+struct ClassHeader {
+    unsigned long long groups;        // classes found
+    unsigned long long long_rows;     // rows whose motif has more than 32 bases
+};
+size_t classes_work_words(int64_t n);
+size_t classes_scratch_bytes(int64_t n);
+hipError_t launch_classes(const int32_t *rows, const int32_t *offsets, const uint8_t *pool, int64_t n, int64_t length, uint64_t *work, ClassHeader *header,
+                          RibbitMotifClass *groups, uint8_t *strands, uint8_t *classes, void *scratch, size_t scratch_bytes, hipStream_t stream);
+
 // profiling aid: reads nwords dwords of src with one coalesced dword per lane (known byte count)
 void launch_calib_stream_read(const uint32_t *src, int64_t nwords, uint32_t *sink, hipStream_t stream);
 

@@ -6,6 +6,7 @@
 //              [--devices 0,1,...] [--jobs N] [--masked-fasta FILE [--mask soft|hard] [--mask-width N]]
 //              [--repeat-fasta FILE [--flank N]] [--loci-bed FILE [--loci-gap D]] [--density-bedgraph FILE [--density-window W]]
 //              [--overlap-with OTHER.bed [--overlap-bed FILE] [--overlap-summary FILE]] [--best-bed FILE]
+//              [--class-bed FILE] [--motif-summary FILE]
 //
 // Records are independent (ribbit.cpp:269-280 handles them one after the other); here up to --jobs of them are in
 // flight at once PER GPU, each on its own handle / HIP streams, so that the upload and GPU scans of one record overlap
@@ -22,12 +23,15 @@
 // --overlap-bed / --overlap-summary set every record's rows against its intervals of that file (ribbit_hip_record_overlap): the
 // rows again with two columns more (ribbit_bed_overlap_text), and one line of counts per record.  --best-bed writes the rows of
 // every record that ribbit_hip_record_best selects, a subset in which no two overlap and which covers the most bases, by ascending
-// start (ribbit_bed_rows_text).  The BED rows are read back once per record, however many of the seven are asked for.
+// start (ribbit_bed_rows_text).  --class-bed and --motif-summary group every record's rows by the canonical class of their motif
+// (ribbit_bed_motifs, ribbit_hip_record_classes): the rows again with class and strand behind them (ribbit_bed_class_text), and
+// one line per class and record (ribbit_class_summary_text).  The BED rows are read back once per record, however many of the
+// nine are asked for.
 //
-// These seven are the ROW OUTPUTS, and each is described once, by its entry of kOutputs below: its file option, its stage (enum
+// These nine are the ROW OUTPUTS, and each is described once, by its entry of kOutputs below: its file option, its stage (enum
 // Stage, with the stage's names beside it), its qualifier options with their ranges and wording (defaults: Settings), and the function that
 // makes one record's text from the record's rows.  Parsing, the "needs" checks, opening the files, the sinks of the pipelined
-// records and of the last one, --timing and the RIBBIT_PROFILE line are loops over that table.  An eighth row output is: a stage in
+// records and of the last one, --timing and the RIBBIT_PROFILE line are loops over that table.  A tenth row output is: a stage in
 // the enum and its names, the qualifiers' fields in Settings, a produce function, an entry of kOutputs, and its lines of kHelp.
 //
 // Reproduced quirks: -p is accepted and ignored (Q1); without -o the BED rows go to
@@ -73,13 +77,13 @@ void check(int rc) {
 }
 
 // The stages of a record: the six every record goes through, then one per row output, in the order of kOutputs.
-enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, OVERLAP, BEST, N_STAGES };
+enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, OVERLAP, BEST, CLASSES, N_STAGES };
 constexpr int N_FIXED_STAGES = MASK;
 // a stage's key in --timing's stage_ms_summed_over_records and its label in the RIBBIT_PROFILE line
 const struct { const char *key, *label; } kStageNames[N_STAGES] = {
     {"load", "load"}, {"perfect", "perfect"}, {"substitutions", "substitutions"}, {"anchored", "anchored"}, {"dispatch", "dispatch"},
     {"refine_and_bed", "refine+BED"}, {"mask", "mask"}, {"repeats", "repeats"}, {"loci", "loci"}, {"density", "density"}, {"overlap", "overlap"},
-    {"best", "best"}};
+    {"best", "best"}, {"classes", "classes"}};
 
 // wall time per stage, summed over the records (--timing, RIBBIT_PROFILE=1)
 double g_stage_ms[N_STAGES] = {};
@@ -108,6 +112,21 @@ struct RecordRows {
     size_t bed_len;
     std::string bed_copy;                // ... or this copy of it, when it came in slices and an output quotes it
     const std::vector<int32_t> *other;   // the record's intervals of --overlap-with, (start, end) each in file order (null: none)
+    // the record's rows by motif class, computed by the first of the two outputs that asks (classes_of): the motifs of the BED text
+    // (owned here) and the handle's result, which stays valid while the record's outputs are produced
+    struct Classes {
+        bool have = false;
+        char *motifs = nullptr;
+        int32_t *offsets = nullptr;
+        const char *classes = nullptr, *strands = nullptr;
+        const RibbitMotifClass *groups = nullptr;
+        size_t n_groups = 0;
+        Classes() = default;
+        Classes(const Classes &) = delete;
+        Classes &operator=(const Classes &) = delete;
+        ~Classes() { ribbit_text_free(motifs); ribbit_intervals_free(offsets); }
+    };
+    mutable Classes by_class;
     size_t n() const { return iv.size() / 2; }
 };
 
@@ -240,6 +259,38 @@ void produce_best(RibbitHandle *h, const RecordRows &r, const Settings &, const 
     ribbit_text_free(text);
 }
 
+// both class outputs of a record: the second call finds what the first left in the record's rows
+const RecordRows::Classes &classes_of(RibbitHandle *h, const RecordRows &r) {
+    RecordRows::Classes &c = r.by_class;
+    if (c.have) return c;
+    size_t n = 0;
+    check(ribbit_bed_motifs(r.bed_text, r.bed_len, &c.motifs, &c.offsets, &n));
+    if (n != r.n()) throw PathError{"the BED text has " + std::to_string(n) + " motifs for " + std::to_string(r.n()) + " rows"};
+    check(ribbit_hip_record_classes(h, r.iv.data(), n, c.motifs, c.offsets, &c.classes, &c.strands, &c.groups, &c.n_groups));
+    c.have = true;
+    return c;
+}
+
+void produce_class_bed(RibbitHandle *h, const RecordRows &r, const Settings &, const Sink &write) {
+    char *text = nullptr;
+    size_t len = 0;
+    StageClock c(CLASSES);
+    const RecordRows::Classes &k = classes_of(h, r);
+    check(ribbit_bed_class_text(r.bed_text, r.bed_len, k.classes, k.offsets, k.strands, r.n(), &text, &len));
+    write(text, len);
+    ribbit_text_free(text);
+}
+
+void produce_motif_summary(RibbitHandle *h, const RecordRows &r, const Settings &, const Sink &write) {
+    char *text = nullptr;
+    size_t len = 0;
+    StageClock c(CLASSES);
+    const RecordRows::Classes &k = classes_of(h, r);
+    check(ribbit_class_summary_text(r.name.c_str(), r.iv.data(), r.n(), k.classes, k.offsets, k.groups, k.n_groups, &text, &len));
+    write(text, len);
+    ribbit_text_free(text);
+}
+
 // One entry per row output.  The order is the order of everything that is done for all of them: the "needs" checks, opening the
 // files (binary), producing a record's texts, the keys of --timing.
 struct Output {
@@ -250,7 +301,7 @@ struct Output {
     Qualifier qualifiers[MAX_QUALIFIERS];    // (name null: none)
     bool needs_other;                        // it compares the rows with the intervals of --overlap-with
 };
-constexpr size_t N_OUTPUTS = 7;
+constexpr size_t N_OUTPUTS = 9;
 const Output kOutputs[N_OUTPUTS] = {
     {"masked-fasta", MASK, false, produce_masked,
      {{"mask", Qualifier::SOFT_HARD, 0, 0, 0, nullptr, &Settings::mask_mode},
@@ -263,7 +314,9 @@ const Output kOutputs[N_OUTPUTS] = {
      {{"density-window", Qualifier::BASES, 1, 2147483647, 10, "1 .. 2147483647", &Settings::density_window}, {}}, false},
     {"overlap-bed", OVERLAP, true, produce_overlap_bed, {{}, {}}, true},
     {"overlap-summary", OVERLAP, false, produce_overlap_summary, {{}, {}}, true},
-    {"best-bed", BEST, true, produce_best, {{}, {}}, false}};
+    {"best-bed", BEST, true, produce_best, {{}, {}}, false},
+    {"class-bed", CLASSES, true, produce_class_bed, {{}, {}}, false},
+    {"motif-summary", CLASSES, true, produce_motif_summary, {{}, {}}, false}};
 
 // the row outputs that are on, by stage: an output whose stage an earlier one has already named is left out (--timing, RIBBIT_PROFILE)
 std::vector<Stage> stages_on(const std::array<bool, N_OUTPUTS> &on) {
@@ -357,7 +410,14 @@ const char *kHelp =
     "                                both_bases / (rows_bases + other_bases - both_bases))\n"
     "  --best-bed arg                (ribbit-hip) also write a non-redundant call set to this file: the BED rows of every record\n"
     "                                of which no two overlap and which together cover the most bases, each row as it is in\n"
-    "                                the BED, sorted by start\n";
+    "                                the BED, sorted by start\n"
+    "  --class-bed arg               (ribbit-hip) also write every BED row to this file with two columns appended: the canonical\n"
+    "                                class of its motif (the least of the motif's rotations and of the rotations of its\n"
+    "                                reverse complement, so AC, CA, GT and TG are all AC) and '+' if a rotation of the motif\n"
+    "                                itself is that class, '-' if only the reverse complement's is\n"
+    "  --motif-summary arg           (ribbit-hip) also write a census of what repeats to this file, one line per record and motif\n"
+    "                                class, by class length, then alphabetically: name, class, length, rows, bases (the sum of\n"
+    "                                the rows' lengths, not their union), start and end of the class's longest row\n";
 
 bool parse_device_list(const std::string &value, std::vector<int> &out) {
     out.clear();
@@ -617,7 +677,7 @@ void process_sequence(RibbitHandle *h, const RibbitRefineParams &prm, const std:
     { StageClock c(DISPATCH); check(ribbit_hip_dispatch_seeds(h, &d, &nd)); }
     // one record over several GPUs: only worth it from a few hundred thousand seeds on (RIBBIT_SHARD_MIN_SEEDS: a test hook)
     static const size_t shard_min = std::getenv("RIBBIT_SHARD_MIN_SEEDS") ? (size_t)std::atoll(std::getenv("RIBBIT_SHARD_MIN_SEEDS")) : 400000;
-    RecordRows rows{name, length, {}, nullptr, 0, {}, settings.other ? settings.other->of(name) : nullptr};
+    RecordRows rows{name, length, {}, nullptr, 0, {}, settings.other ? settings.other->of(name) : nullptr, {}};
     const bool want_rows = jobs.any();
     if (helpers && !helpers->empty() && nd >= shard_min && nd >= 2 * (helpers->size() + 1)) {
         StageClock c(REFINE_BED);
