@@ -514,6 +514,64 @@ int ribbit_class_summary_text(const char *name, const int32_t *intervals, size_t
                               const RibbitMotifClass *groups, size_t n_groups, char **text, size_t *len);
 
 /*
+ * ---- the rows chained into compound loci --------------------------------------------------------------------------
+ * What a locus is made of: one pure stretch (CA)20, the same motif broken by a few bases (CA)12n3(CA)9, or different motifs
+ * side by side (CA)12(GA)8 -- the perfect, interrupted and compound repeats of MISA and Krait.  With L the record's length,
+ * every row i = (s, e) carries a caller-given int32 label; any value is a label, INT32_MIN and INT32_MAX included (what
+ * ribbit_class_labels makes of the rows' motif classes is one choice).
+ *   Clipping:  as everywhere, s' = max(s, 0), e' = min(e, L), in 64-bit; a row with s' >= e' is empty: it is in no chain and
+ *              counts nowhere.
+ *   Order:     the non-empty rows by (s', e', i) ascending, at positions k = 1 .. r.
+ *   Reach:     reach_k = max(e'_1 .. e'_k).
+ *   Chains:    row 1 starts a chain; row k > 1 starts a new chain iff s'_k - reach_{k-1} > gap, computed in 64-bit, and
+ *              otherwise continues the chain of row k - 1.  Chains come by ascending start.  At the same gap, the start, end
+ *              and rows of the chains equal those of the loci of ribbit_hip_record_loci.
+ *   Per chain: start    = s' of its first member;
+ *              end      = reach of its last member;
+ *              rows     = the number of members;
+ *              bases    = the sum of the members' widths e' - s', int64.  NOT a union;
+ *              classes  = the number of distinct labels among the members;
+ *              switches = the number of members, not the first, whose label differs from the previous member's;
+ *              overlaps = the number of members, not the first, with s'_k < reach_{k-1}: 0 whenever no two of the rows given
+ *                         overlap, and then bases equals the locus's covered;
+ *              first    = the position of its first member in members.
+ *   members:   the r row indices (into the rows given) in the order above; chain c owns members[first .. first + rows).
+ *   Kind:      derived by ribbit_compound_text, not stored: p (perfect) when rows == 1, i (interrupted) when rows > 1 and
+ *              classes == 1, c (compound) when classes > 1; a * is appended when overlaps > 0.
+ * pad is always 0: it keeps sizeof at 40 without hidden tail padding.
+ */
+typedef struct { int64_t bases; int32_t start, end, rows, classes, switches, overlaps, first, pad; } RibbitCompound;
+/* The chains of the loaded record's n rows (at most INT32_MAX) with their labels (n ints), on the GPU.  *compounds:
+ * *n_compounds chains; *members: *n_members row indices.  Both are handle-owned page-locked memory, valid until the handle's
+ * next compounds call, load or close.  L = 0, n = 0 and rows that are all empty are no errors: no chains, no members.
+ * gap < 0, n > INT32_MAX: RIBBIT_E_ARG.  Before a load: RIBBIT_E_STATE. */
+int ribbit_hip_record_compounds(RibbitHandle *h, const int32_t *intervals, const int32_t *labels, size_t n, int32_t gap,
+                                const RibbitCompound **compounds, size_t *n_compounds, const int32_t **members, size_t *n_members);
+/* Host-only twin (no GPU) for a record of `length` bases (0 <= length < 2^31): one sort, one sweep.  *compounds malloc'ed,
+ * release with ribbit_compounds_free(); *members malloc'ed, release with ribbit_intervals_free(). */
+int ribbit_host_record_compounds(int64_t length, const int32_t *intervals, const int32_t *labels, size_t n, int32_t gap,
+                                 RibbitCompound **compounds, size_t *n_compounds, int32_t **members, size_t *n_members);
+void ribbit_compounds_free(RibbitCompound *compounds);
+/* The rows' motif classes as labels (host only): labels[i] = the index, in class order, of the group whose class is row i's.
+ * classes, offsets, groups: what ribbit_hip_record_classes and its host twin hand out for the n rows.  A group whose
+ * first_row is no row or whose length is not that row's, a row whose class is no group: RIBBIT_E_ARG.  *labels malloc'ed,
+ * release with ribbit_intervals_free(). */
+int ribbit_class_labels(const char *classes, const int32_t *offsets, size_t n, const RibbitMotifClass *groups, size_t n_groups,
+                        int32_t **labels);
+/* The chains of one record as text (host only), one line per chain, eight tab-separated columns:
+ *   name, start, end, kind, rows, classes, bases, structure.
+ * The structure is built from the chain's members in order: each is written "(MOTIF)UNITS", MOTIF and UNITS being the
+ * eighth and the fifth column from the end of the member's line of bed_text, byte for byte (columns are found from the
+ * right, as ribbit_bed_loci_text finds them); between two consecutive members, with d = s'_k - reach_{k-1} (the clipping of
+ * `length` applied to `intervals`, the n rows the chains were made from): d > 0 writes "n" and d, as in (CA)12n5(GA)8;
+ * d == 0 writes nothing; d < 0 writes "o" and -d.  bed_text: row i on line i.  A member that is no row or no line of
+ * bed_text or is empty, a first / rows outside members, a line that is not a row: RIBBIT_E_ARG.  *text malloc'ed, release
+ * with ribbit_text_free(). */
+int ribbit_compound_text(const char *name, const char *bed_text, size_t bed_len, int64_t length, const int32_t *intervals,
+                         size_t n, const RibbitCompound *compounds, size_t n_compounds, const int32_t *members,
+                         size_t n_members, char **text, size_t *len);
+
+/*
  * ---- streaming FASTA ingest ---------------------------------------------------------------------------------------
  * Replaces the reader loop of ribbit.cpp:269-280 (getline + `sequence += line` into one pageable std::string per
  * record).  The file is read in 16-MB blocks; line bodies are copied once, straight into a page-locked buffer

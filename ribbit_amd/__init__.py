@@ -20,7 +20,8 @@ __all__ = ["RibbitHipError", "ScanParams", "Scanner", "library_path", "load_libr
            "LOCUS_DT", "host_record_loci", "host_record_density", "bed_loci_text",
            "OverlapTotals", "OVERLAP_TOTALS", "host_record_overlap", "bed_overlap_text",
            "host_record_best", "bed_rows_text",
-           "MOTIF_CLASS_DT", "bed_motifs", "host_record_classes", "bed_class_text", "class_summary_text"]
+           "MOTIF_CLASS_DT", "bed_motifs", "host_record_classes", "bed_class_text", "class_summary_text",
+           "COMPOUND_DT", "host_record_compounds", "class_labels", "compound_text"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -36,6 +37,7 @@ CALL_DT = np.dtype([("pos", "<i4"), ("mlen", "<i4"), ("start", "<i4"), ("end", "
 SEED_DT = np.dtype([("start", "<i4"), ("end", "<i4"), ("mlen", "<i4"), ("type", "<i4")])
 LOCUS_DT = np.dtype([(n, "<i4") for n in ("start", "end", "rows", "covered", "best_row")])      # RibbitLocus
 MOTIF_CLASS_DT = np.dtype([("bases", "<i8")] + [(n, "<i4") for n in ("length", "rows", "first_row", "longest_row")])      # RibbitMotifClass
+COMPOUND_DT = np.dtype([("bases", "<i8")] + [(n, "<i4") for n in ("start", "end", "rows", "classes", "switches", "overlaps", "first", "pad")])      # RibbitCompound
 
 # every symbol include/ribbit_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -68,6 +70,7 @@ ABI_SYMBOLS = [
     "ribbit_hip_record_best", "ribbit_host_record_best", "ribbit_bed_rows_text",
     "ribbit_bed_motifs", "ribbit_hip_record_classes", "ribbit_host_record_classes", "ribbit_motif_classes_free", "ribbit_bed_class_text",
     "ribbit_class_summary_text",
+    "ribbit_hip_record_compounds", "ribbit_host_record_compounds", "ribbit_compounds_free", "ribbit_class_labels", "ribbit_compound_text",
 ]
 
 MASK_MODES = {"soft": 0, "hard": 1}     # RIBBIT_MASK_SOFT / RIBBIT_MASK_HARD
@@ -312,6 +315,12 @@ def load_library():
     L.ribbit_motif_classes_free.restype = None
     L.ribbit_bed_class_text.argtypes = [C.c_char_p, C.c_size_t, vp, vp, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.ribbit_class_summary_text.argtypes = [C.c_char_p, vp, C.c_size_t, vp, vp, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_hip_record_compounds.argtypes = [vp, vp, vp, C.c_size_t, i32, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_host_record_compounds.argtypes = [i64, vp, vp, C.c_size_t, i32, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_compounds_free.argtypes = [vp]
+    L.ribbit_compounds_free.restype = None
+    L.ribbit_class_labels.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp)]
+    L.ribbit_compound_text.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, i64, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
     _lib = L
     return L
 
@@ -843,6 +852,77 @@ def class_summary_text(name, intervals, classes, offsets, groups) -> bytes:
         L.ribbit_text_free(text)
 
 
+def _compound_args(intervals, labels, gap):
+    """the rows, their labels and the gap as the C ABI takes them"""
+    iv, gap = _rows_arg(intervals, gap, "gap")
+    lab = np.asarray(labels)
+    if lab.ndim != 1 or len(lab) != len(iv):
+        raise ValueError(f"{len(iv)} rows want {len(iv)} labels")
+    if len(lab) and (lab.min() < -(1 << 31) or lab.max() >= (1 << 31)):
+        raise ValueError("a label is not an int32")
+    return iv, np.ascontiguousarray(lab, dtype=np.int32), gap
+
+
+def host_record_compounds(length: int, intervals, labels, gap: int = 100):
+    """ribbit_host_record_compounds: the rows of a record of `length` bases, each with an int32 label, chained while a row starts
+    at most `gap` bases behind everything before it -> (the chains by ascending start, a COMPOUND_DT array; the non-empty rows'
+    indices in (start, end, index) order, int32: chain c owns members[first : first + rows]).  The contract is in
+    include/ribbit_hip.h.  No GPU needed."""
+    L = load_library()
+    iv, lab, gap = _compound_args(intervals, labels, gap)
+    chains, n, members, m = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t()
+    rc = L.ribbit_host_record_compounds(int(length), iv.ctypes.data if len(iv) else None, lab.ctypes.data if len(iv) else None, len(iv), gap,
+                                        C.byref(chains), C.byref(n), C.byref(members), C.byref(m))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_host_record_compounds error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return _copy(chains.value, n.value, COMPOUND_DT), _copy(members.value, m.value, np.dtype("<i4"))
+    finally:
+        L.ribbit_compounds_free(chains)
+        L.ribbit_intervals_free(members)
+
+
+def class_labels(classes, offsets, groups) -> np.ndarray:
+    """ribbit_class_labels: per row the index, in class order, of the group whose class is the row's, int32.  classes, offsets,
+    groups: what record_classes / host_record_classes return for the rows (offsets: the motifs')."""
+    L = load_library()
+    cls = bytes(classes)
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int32).reshape(-1))
+    if len(off) < 1 or len(cls) < int(off[-1]):
+        raise ValueError("n rows want n + 1 offsets into the classes")
+    gr = np.ascontiguousarray(np.asarray(groups, dtype=MOTIF_CLASS_DT).reshape(-1))
+    labels = C.c_void_p()
+    rc = L.ribbit_class_labels(cls, off.ctypes.data, len(off) - 1, gr.ctypes.data if len(gr) else None, len(gr), C.byref(labels))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_class_labels error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return _copy(labels.value, len(off) - 1, np.dtype("<i4"))
+    finally:
+        L.ribbit_intervals_free(labels)
+
+
+def compound_text(name, bed, length: int, intervals, compounds, members) -> bytes:
+    """ribbit_compound_text: one line per chain of one record: name, start, end, kind (p, i or c, with * when members overlap),
+    rows, classes, bases and the structure, e.g. (CA)12n5(GA)8, read from the members' lines of `bed` (row i on line i)."""
+    L = load_library()
+    raw = name.encode() if isinstance(name, str) else bytes(name)
+    if b"\0" in raw:
+        raise ValueError("a record name cannot hold a NUL byte")
+    text_in = bed.encode() if isinstance(bed, str) else bytes(bed)
+    iv = _pairs(intervals)
+    ch = np.ascontiguousarray(np.asarray(compounds, dtype=COMPOUND_DT).reshape(-1))
+    mem = np.ascontiguousarray(np.asarray(members, dtype=np.int32).reshape(-1))
+    text, n = C.c_void_p(), C.c_size_t()
+    rc = L.ribbit_compound_text(raw, text_in, len(text_in), int(length), iv.ctypes.data if len(iv) else None, len(iv), ch.ctypes.data if len(ch) else None,
+                                len(ch), mem.ctypes.data if len(mem) else None, len(mem), C.byref(text), C.byref(n))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_compound_text error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return C.string_at(text.value, n.value)
+    finally:
+        L.ribbit_text_free(text)
+
+
 def host_perfect_runs_from_events(min_motif: int, max_motif: int, event_parts, count_parts):
     """ribbit_host_perfect_runs_from_events: per-rank (events, per-motif counts) -> paired runs. No GPU needed."""
     L = load_library()
@@ -1194,6 +1274,14 @@ class Scanner:
         self._check(self._L.ribbit_hip_record_classes(self._h, iv.ctypes.data if len(iv) else None, len(iv), pool, off.ctypes.data, C.byref(classes),
                                                       C.byref(strands), C.byref(groups), C.byref(n)))
         return C.string_at(classes.value, int(off[-1])), C.string_at(strands.value, len(iv)), _copy(groups.value, n.value, MOTIF_CLASS_DT)
+
+    def record_compounds(self, intervals, labels, gap: int = 100):
+        """The loaded record's rows chained into compound loci on the GPU (ribbit_hip_record_compounds); see host_record_compounds"""
+        iv, lab, gap = _compound_args(intervals, labels, gap)
+        chains, n, members, m = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t()
+        self._check(self._L.ribbit_hip_record_compounds(self._h, iv.ctypes.data if len(iv) else None, lab.ctypes.data if len(iv) else None, len(iv), gap,
+                                                        C.byref(chains), C.byref(n), C.byref(members), C.byref(m)))
+        return _copy(chains.value, n.value, COMPOUND_DT), _copy(members.value, m.value, np.dtype("<i4"))
 
     def record_density(self, intervals, window: int) -> np.ndarray:
         """The loaded record's covered bases per window on the GPU (ribbit_hip_record_density); see host_record_density"""

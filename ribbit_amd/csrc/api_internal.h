@@ -15,7 +15,8 @@
 //   api_overlap.cpp     the rows of a record against a second set of intervals (overlap.hip), its host twin, the rows' text with the two columns
 //   api_best.cpp        the best non-overlapping rows of a record (best.hip), its host twin, the chosen rows' text
 //   api_classes.cpp     the rows of a record grouped by canonical motif class (classes.hip), its host twin, the motifs of a BED text, both texts
-// The last six are the row outputs: their buffers are the handle's RowBufs `rows`, and what their host sides share is below
+//   api_compound.cpp    the rows of a record chained into compound loci (compound.hip), its host twin, the classes as labels, the chains' text
+// The last seven are the row outputs: their buffers are the handle's RowBufs `rows`, and what their host sides share is below
 // (hand_out, clipped_sorted_rows, bed_text_parts, bed_line_starts).
 // Host threads: every team of them, here and in refine.cpp, parallel_merge.cpp and host_planes.cpp, is started by rb::on_threads /
 // rb::over_pieces of host_threads.h (part 0 on the caller, a thread that cannot start leaves its part to the caller, all joined, the
@@ -188,7 +189,7 @@ struct PairBufs {
     uint32_t *h_pub_dev = nullptr;         // the same memory as the device sees it
 };
 
-// ---- shared by the host sides of the row outputs (api_mask.cpp, api_repeats.cpp, api_loci.cpp, api_overlap.cpp, api_best.cpp, api_classes.cpp)
+// ---- shared by the host sides of the row outputs (api_mask.cpp, api_repeats.cpp, api_loci.cpp, api_overlap.cpp, api_best.cpp, api_classes.cpp, api_compound.cpp)
 
 // n elements as malloc memory the caller frees (never a null pointer, whatever n): a copy of src, or for the caller to fill
 // when src is null; terminate: a zero element behind them
@@ -394,7 +395,7 @@ struct RibbitHandle {
     bool bed_in_raw = false;              // the last ribbit_hip_refine_bed returned bed_raw, not bed
     rb::SeedLists lists;
     bool refine_met_empty_query = false;  // the last ribbit_hip_refine_bed on this handle met an alignment with an empty query (ribbit_hip_refine_met_empty_query)
-    // the row outputs of the loaded record (api_mask.cpp, api_repeats.cpp, api_loci.cpp, api_overlap.cpp, api_best.cpp, api_classes.cpp)
+    // the row outputs of the loaded record (api_mask.cpp, api_repeats.cpp, api_loci.cpp, api_overlap.cpp, api_best.cpp, api_classes.cpp, api_compound.cpp)
     struct RowBufs {
         // the masked body of the loaded record (api_mask.cpp): coverage bitmap, intervals, the text on the device and on its way up
         DevBuf<uint32_t> d_mask_bits;
@@ -451,6 +452,17 @@ struct RibbitHandle {
         DevBuf<uint64_t> d_class_work;
         DevBuf<uint8_t> d_class;
         PinnedBuf<uint8_t> h_class;
+        // the rows chained into compound loci (api_compound.cpp): the rows | their labels on their way down and on the device, the
+        // keys | the keys sorted | the (chain, label) keys sorted, the indices or chain ids | reach | the chains' first positions, the
+        // prefix sums, the flag bytes, the sorts' and the scans' scratch, and the result on the device and on its way up: the
+        // counts, then the chains, then the members
+        PinnedBuf<int32_t> h_cmp_in;
+        DevBuf<int32_t> d_cmp_in, d_cmp_work;
+        DevBuf<uint64_t> d_cmp_keys;
+        DevBuf<rb::CompoundSums> d_cmp_sums;
+        DevBuf<uint8_t> d_cmp_flags, d_cmp_scratch;
+        DevBuf<uint8_t> d_cmp;
+        PinnedBuf<uint8_t> h_cmp;
         size_t rep_budget = 0;           // text budget of one batch of repeat sequences in bytes (0: REPEAT_TEXT_BUDGET)
     } rows;
     RibbitHandle *aux = nullptr;          // helper handle of ribbit_hip_refine_bed: streams and buffers of the long alignment batch

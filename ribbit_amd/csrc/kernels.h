@@ -338,6 +338,25 @@ size_t classes_scratch_bytes(int64_t n);
 hipError_t launch_classes(const int32_t *rows, const int32_t *offsets, const uint8_t *pool, int64_t n, int64_t length, uint64_t *work, ClassHeader *header,
                           RibbitMotifClass *groups, uint8_t *strands, uint8_t *classes, void *scratch, size_t scratch_bytes, hipStream_t stream);
 
+// compound.hip: the loaded record's rows chained into compound loci (api_compound.cpp).  rows, labels: the n >= 1 rows and their
+// labels on the device.  keys: 3 n words (the rows' keys, then the (chain, label) keys | the keys sorted | the (chain, label) keys
+// sorted), work: 3 n + 1 ints (the row indices, then the chain ids | reach | where every chain starts, and r behind the last),
+// sums: n prefix records, flags: n bytes (head, switch and overlap bits), scratch: compound_scratch_bytes(n, length).  totals is
+// zeroed and filled; members: the non-empty rows' indices in (s', e', index) order, totals->rows of them (n ints of room);
+// compounds: totals->chains of them by ascending start (n of room).
+struct CompoundTotals {
+    uint32_t rows, chains;            // non-empty rows, chains
+    uint32_t spare[2];
+};
+struct CompoundSums {                 // what the positions up to one add up to
+    unsigned long long bases;
+    uint32_t switches, overlaps, classes, spare;
+};
+size_t compound_scratch_bytes(int64_t n, int64_t length);
+hipError_t launch_compounds(const int32_t *rows, const int32_t *labels, int64_t n, int64_t length, int32_t gap, uint64_t *keys, int32_t *work,
+                            CompoundSums *sums, uint8_t *flags, CompoundTotals *totals, int32_t *members, RibbitCompound *compounds, void *scratch,
+                            size_t scratch_bytes, hipStream_t stream);
+
 // profiling aid: reads nwords dwords of src with one coalesced dword per lane (known byte count)
 void launch_calib_stream_read(const uint32_t *src, int64_t nwords, uint32_t *sink, hipStream_t stream);
 

@@ -6,7 +6,7 @@
 //              [--devices 0,1,...] [--jobs N] [--masked-fasta FILE [--mask soft|hard] [--mask-width N]]
 //              [--repeat-fasta FILE [--flank N]] [--loci-bed FILE [--loci-gap D]] [--density-bedgraph FILE [--density-window W]]
 //              [--overlap-with OTHER.bed [--overlap-bed FILE] [--overlap-summary FILE]] [--best-bed FILE]
-//              [--class-bed FILE] [--motif-summary FILE]
+//              [--class-bed FILE] [--motif-summary FILE] [--compound-bed FILE [--compound-gap D]]
 //
 // Records are independent (ribbit.cpp:269-280 handles them one after the other); here up to --jobs of them are in
 // flight at once PER GPU, each on its own handle / HIP streams, so that the upload and GPU scans of one record overlap
@@ -25,13 +25,16 @@
 // every record that ribbit_hip_record_best selects, a subset in which no two overlap and which covers the most bases, by ascending
 // start (ribbit_bed_rows_text).  --class-bed and --motif-summary group every record's rows by the canonical class of their motif
 // (ribbit_bed_motifs, ribbit_hip_record_classes): the rows again with class and strand behind them (ribbit_bed_class_text), and
-// one line per class and record (ribbit_class_summary_text).  The BED rows are read back once per record, however many of the
-// nine are asked for.
+// one line per class and record (ribbit_class_summary_text).  --compound-bed chains the rows of --best-bed's selection that lie at most
+// --compound-gap bases apart (ribbit_hip_record_compounds) and writes one line per chain with its kind -- perfect, interrupted,
+// compound -- and its structure, e.g. (CA)12n5(GA)8 (ribbit_class_labels, ribbit_compound_text); the selection and the classes are
+// computed once per record, whichever outputs ask for them.  The BED rows are read back once per record, however many of the
+// ten are asked for.
 //
-// These nine are the ROW OUTPUTS, and each is described once, by its entry of kOutputs below: its file option, its stage (enum
+// These ten are the ROW OUTPUTS, and each is described once, by its entry of kOutputs below: its file option, its stage (enum
 // Stage, with the stage's names beside it), its qualifier options with their ranges and wording (defaults: Settings), and the function that
 // makes one record's text from the record's rows.  Parsing, the "needs" checks, opening the files, the sinks of the pipelined
-// records and of the last one, --timing and the RIBBIT_PROFILE line are loops over that table.  A tenth row output is: a stage in
+// records and of the last one, --timing and the RIBBIT_PROFILE line are loops over that table.  An eleventh row output is: a stage in
 // the enum and its names, the qualifiers' fields in Settings, a produce function, an entry of kOutputs, and its lines of kHelp.
 //
 // Reproduced quirks: -p is accepted and ignored (Q1); without -o the BED rows go to
@@ -77,13 +80,13 @@ void check(int rc) {
 }
 
 // The stages of a record: the six every record goes through, then one per row output, in the order of kOutputs.
-enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, OVERLAP, BEST, CLASSES, N_STAGES };
+enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, OVERLAP, BEST, CLASSES, COMPOUND, N_STAGES };
 constexpr int N_FIXED_STAGES = MASK;
 // a stage's key in --timing's stage_ms_summed_over_records and its label in the RIBBIT_PROFILE line
 const struct { const char *key, *label; } kStageNames[N_STAGES] = {
     {"load", "load"}, {"perfect", "perfect"}, {"substitutions", "substitutions"}, {"anchored", "anchored"}, {"dispatch", "dispatch"},
     {"refine_and_bed", "refine+BED"}, {"mask", "mask"}, {"repeats", "repeats"}, {"loci", "loci"}, {"density", "density"}, {"overlap", "overlap"},
-    {"best", "best"}, {"classes", "classes"}};
+    {"best", "best"}, {"classes", "classes"}, {"compound", "compound"}};
 
 // wall time per stage, summed over the records (--timing, RIBBIT_PROFILE=1)
 double g_stage_ms[N_STAGES] = {};
@@ -127,6 +130,14 @@ struct RecordRows {
         ~Classes() { ribbit_text_free(motifs); ribbit_intervals_free(offsets); }
     };
     mutable Classes by_class;
+    // the record's best non-overlapping rows, computed by the first of the two outputs that asks (best_of): the handle's result,
+    // which stays valid while the record's outputs are produced
+    struct Best {
+        bool have = false;
+        const int32_t *chosen = nullptr;
+        size_t n = 0;
+    };
+    mutable Best best;
     size_t n() const { return iv.size() / 2; }
 };
 
@@ -147,6 +158,7 @@ struct Settings {
     int flank = 100;                     // --flank N: bases on either side of a row
     int loci_gap = 0;                    // --loci-gap D: runs at most D bases apart are one locus
     int density_window = 10000;          // --density-window W
+    int compound_gap = 100;              // --compound-gap D: rows at most D bases behind what came before them are one chain (MISA's default)
     const OtherBed *other = nullptr;         // --overlap-with FILE, read and grouped by name
 };
 
@@ -246,15 +258,22 @@ void produce_overlap_summary(RibbitHandle *h, const RecordRows &r, const Setting
     write(line.data(), line.size());
 }
 
-void produce_best(RibbitHandle *h, const RecordRows &r, const Settings &, const Sink &write) {
-    const int32_t *chosen = nullptr;
-    size_t n_chosen = 0;
+// the selection of a record, for --best-bed and --compound-bed: the second call finds what the first left in the record's rows
+const RecordRows::Best &best_of(RibbitHandle *h, const RecordRows &r) {
+    RecordRows::Best &b = r.best;
+    if (b.have) return b;
     int64_t bases = 0;
+    check(ribbit_hip_record_best(h, r.iv.data(), r.n(), &b.chosen, &b.n, &bases));
+    b.have = true;
+    return b;
+}
+
+void produce_best(RibbitHandle *h, const RecordRows &r, const Settings &, const Sink &write) {
     char *text = nullptr;
     size_t len = 0;
     StageClock c(BEST);
-    check(ribbit_hip_record_best(h, r.iv.data(), r.n(), &chosen, &n_chosen, &bases));
-    check(ribbit_bed_rows_text(r.bed_text, r.bed_len, chosen, n_chosen, &text, &len));
+    const RecordRows::Best &b = best_of(h, r);
+    check(ribbit_bed_rows_text(r.bed_text, r.bed_len, b.chosen, b.n, &text, &len));
     write(text, len);
     ribbit_text_free(text);
 }
@@ -291,6 +310,34 @@ void produce_motif_summary(RibbitHandle *h, const RecordRows &r, const Settings 
     ribbit_text_free(text);
 }
 
+// the selected rows with the labels of their motif classes, chained; the chains' lines quote the selected rows' lines
+void produce_compound(RibbitHandle *h, const RecordRows &r, const Settings &s, const Sink &write) {
+    StageClock c(COMPOUND);
+    const RecordRows::Best &b = best_of(h, r);
+    const RecordRows::Classes &k = classes_of(h, r);
+    int32_t *labels = nullptr;
+    check(ribbit_class_labels(k.classes, k.offsets, r.n(), k.groups, k.n_groups, &labels));
+    std::vector<int32_t> iv(2 * b.n), label(b.n);
+    for (size_t j = 0; j < b.n; ++j) {
+        const size_t row = (size_t)b.chosen[j];
+        iv[2 * j] = r.iv[2 * row];
+        iv[2 * j + 1] = r.iv[2 * row + 1];
+        label[j] = labels[row];
+    }
+    ribbit_intervals_free(labels);
+    char *lines = nullptr, *text = nullptr;
+    size_t lines_len = 0, len = 0, n_chains = 0, n_members = 0;
+    const RibbitCompound *chains = nullptr;
+    const int32_t *members = nullptr;
+    check(ribbit_bed_rows_text(r.bed_text, r.bed_len, b.chosen, b.n, &lines, &lines_len));
+    int rc = ribbit_hip_record_compounds(h, iv.data(), label.data(), b.n, s.compound_gap, &chains, &n_chains, &members, &n_members);
+    if (rc == RIBBIT_OK) rc = ribbit_compound_text(r.name.c_str(), lines, lines_len, r.length, iv.data(), b.n, chains, n_chains, members, n_members, &text, &len);
+    ribbit_text_free(lines);
+    check(rc);
+    write(text, len);
+    ribbit_text_free(text);
+}
+
 // One entry per row output.  The order is the order of everything that is done for all of them: the "needs" checks, opening the
 // files (binary), producing a record's texts, the keys of --timing.
 struct Output {
@@ -301,7 +348,7 @@ struct Output {
     Qualifier qualifiers[MAX_QUALIFIERS];    // (name null: none)
     bool needs_other;                        // it compares the rows with the intervals of --overlap-with
 };
-constexpr size_t N_OUTPUTS = 9;
+constexpr size_t N_OUTPUTS = 10;
 const Output kOutputs[N_OUTPUTS] = {
     {"masked-fasta", MASK, false, produce_masked,
      {{"mask", Qualifier::SOFT_HARD, 0, 0, 0, nullptr, &Settings::mask_mode},
@@ -316,7 +363,9 @@ const Output kOutputs[N_OUTPUTS] = {
     {"overlap-summary", OVERLAP, false, produce_overlap_summary, {{}, {}}, true},
     {"best-bed", BEST, true, produce_best, {{}, {}}, false},
     {"class-bed", CLASSES, true, produce_class_bed, {{}, {}}, false},
-    {"motif-summary", CLASSES, true, produce_motif_summary, {{}, {}}, false}};
+    {"motif-summary", CLASSES, true, produce_motif_summary, {{}, {}}, false},
+    {"compound-bed", COMPOUND, true, produce_compound,
+     {{"compound-gap", Qualifier::BASES, 0, 2147483647, 10, "0 .. 2147483647", &Settings::compound_gap}, {}}, false}};
 
 // the row outputs that are on, by stage: an output whose stage an earlier one has already named is left out (--timing, RIBBIT_PROFILE)
 std::vector<Stage> stages_on(const std::array<bool, N_OUTPUTS> &on) {
@@ -417,7 +466,15 @@ const char *kHelp =
     "                                itself is that class, '-' if only the reverse complement's is\n"
     "  --motif-summary arg           (ribbit-hip) also write a census of what repeats to this file, one line per record and motif\n"
     "                                class, by class length, then alphabetically: name, class, length, rows, bases (the sum of\n"
-    "                                the rows' lengths, not their union), start and end of the class's longest row\n";
+    "                                the rows' lengths, not their union), start and end of the class's longest row\n"
+    "  --compound-bed arg            (ribbit-hip) also write what every locus is made of to this file: the rows of --best-bed's\n"
+    "                                selection chained while they lie at most --compound-gap bases apart, one line per chain:\n"
+    "                                name, start, end, kind (p perfect: one row; i interrupted: several rows of one motif\n"
+    "                                class; c compound: more than one class), rows, classes, bases (the sum of the rows'\n"
+    "                                lengths) and the structure, e.g. (CA)12n5(GA)8: motif and units of every row, n5 for 5\n"
+    "                                bases between two rows\n"
+    "  --compound-gap arg            (ribbit-hip) for --compound-bed: a row at most this many bases behind the rows before it\n"
+    "                                continues their chain, 0 .. 2147483647. Default: 100\n";
 
 bool parse_device_list(const std::string &value, std::vector<int> &out) {
     out.clear();
@@ -677,7 +734,7 @@ void process_sequence(RibbitHandle *h, const RibbitRefineParams &prm, const std:
     { StageClock c(DISPATCH); check(ribbit_hip_dispatch_seeds(h, &d, &nd)); }
     // one record over several GPUs: only worth it from a few hundred thousand seeds on (RIBBIT_SHARD_MIN_SEEDS: a test hook)
     static const size_t shard_min = std::getenv("RIBBIT_SHARD_MIN_SEEDS") ? (size_t)std::atoll(std::getenv("RIBBIT_SHARD_MIN_SEEDS")) : 400000;
-    RecordRows rows{name, length, {}, nullptr, 0, {}, settings.other ? settings.other->of(name) : nullptr, {}};
+    RecordRows rows{name, length, {}, nullptr, 0, {}, settings.other ? settings.other->of(name) : nullptr, {}, {}};
     const bool want_rows = jobs.any();
     if (helpers && !helpers->empty() && nd >= shard_min && nd >= 2 * (helpers->size() + 1)) {
         StageClock c(REFINE_BED);
