@@ -572,6 +572,79 @@ int ribbit_compound_text(const char *name, const char *bed_text, size_t bed_len,
                          size_t n_members, char **text, size_t *len);
 
 /*
+ * ---- every row's CIGAR decoded: interruptions and the pure stretch ----------------------------------------------------
+ * Where the imperfections of an imperfect repeat are (the CAA inside a CAG tract), and how long its longest uninterrupted
+ * stretch is.  Per row i: (s, e) from columns 2 and 3, k >= 1 the length of the column-4 motif, and the row's CIGAR, column 11,
+ * which may be empty.  With L the record's length:
+ *   Grammar:      a CIGAR is a sequence of ops; an op is one to ten decimal digits with a value in 1 .. 2^31 - 1 followed by one
+ *                 byte of = M X I D (M is a match, as in the reference).  Anything else is RIBBIT_E_ARG, and the error text
+ *                 names the byte's offset in the CIGARs given: the offending byte itself; the op letter when its digits are
+ *                 missing, more than ten or out of range; the row's end when digits are its last bytes.  An empty CIGAR has
+ *                 no ops and is valid.  A row whose op lengths (D included) sum to more than INT32_MAX, or for which
+ *                 s + query does not fit int32: RIBBIT_E_ARG.  The first offending row decides, its grammar before its sums.
+ *   Offsets:      q_0 = 0; q_{j+1} = q_j + len_j when op_j is not D, otherwise q_j.  query = q after the last op.  The row
+ *                 is CONSISTENT iff s + query == e, computed in 64-bit.
+ *   Stretch:      a maximal run of consecutive match ops j .. j' (3=2M is one stretch); it spans [s + q_j, s + q_{j'+1}).
+ *                 pure_start, pure_end: the longest stretch, the leftmost among equals; (s, s) for a row without a match op.
+ *   Interruption: a maximal run of consecutive non-match ops j .. j'.  start = s + q_j, end = s + q_{j'+1} (a run of D alone has
+ *                 start == end); x, ins, del: the sums of its lengths by kind; cigar_at, cigar_len: its bytes in the CIGARs
+ *                 given, from the first digit of op j through the letter of op j'.
+ *   Observed:     with a = min(max(start, 0), L) and b = min(max(end, a), L), the interruption's observed bases are the
+ *                 record's bytes [a, b) as loaded (case kept, N kept), concatenated in interruption order behind n_sites + 1
+ *                 int32 offsets.  More than INT32_MAX observed bytes: RIBBIT_E_ARG (a pool below 2^31 bytes has fewer than
+ *                 2^30 interruptions).
+ *   Per row:      first = the number of interruptions of the rows before it; count, x, ins, del: the totals over the row's
+ *                 interruptions; then query, pure_start, pure_end.
+ *   Order:        interruptions come by row, then in CIGAR order.
+ */
+typedef struct { int32_t row, start, end, x, ins, del, cigar_at, cigar_len; } RibbitInterruption;   /* 32 bytes */
+typedef struct { int32_t first, count, x, ins, del, query, pure_start, pure_end; } RibbitRowPurity; /* 32 bytes */
+/* The CIGARs of a BED text (host only), concatenated: CIGAR i is pool[offsets[i] .. offsets[i + 1]); offsets has n + 1
+ * entries.  Column 11 is the last one (columns are found from the right: a name with a tab in it works); a last line
+ * without its newline counts; the CIGARs' grammar is not looked at.  A line that is not a row of 11 tab-separated columns,
+ * 2^31 bytes of CIGARs or more: RIBBIT_E_ARG.  *pool malloc'ed, release with ribbit_text_free(); *offsets malloc'ed, release
+ * with ribbit_intervals_free(). */
+int ribbit_bed_cigars(const char *bed_text, size_t bed_len, char **pool, int32_t **offsets, size_t *n);
+/* The decode for the loaded record's n rows (at most INT32_MAX), on the GPU.  intervals: (start, end) per row;
+ * motif_lengths: k per row; cigars and offsets as ribbit_bed_cigars hands them out (offsets[0] = 0, ascending, a pool below
+ * 2^31 bytes).  *rows: n records; *sites: *n_sites interruptions; *observed: the observed bases behind *observed_offsets
+ * (*n_sites + 1 of them).  All four are handle-owned page-locked memory, valid until the handle's next interruptions call,
+ * load or close.  n == 0 and L == 0 are no errors; L == 0: every observed string is empty.  Offsets that do not start at 0
+ * or do not ascend, a k below 1, the grammar and the sums above: RIBBIT_E_ARG.  Before a load: RIBBIT_E_STATE. */
+int ribbit_hip_record_interruptions(RibbitHandle *h, const int32_t *intervals, const int32_t *motif_lengths, size_t n,
+                                    const char *cigars, const int32_t *offsets, const RibbitRowPurity **rows,
+                                    const RibbitInterruption **sites, size_t *n_sites, const char **observed,
+                                    const int32_t **observed_offsets);
+/* Host-only twin (no GPU) for a record of `length` bases (0 <= length < 2^31) at `sequence`: a plain loop over the rows and
+ * their ops.  *rows malloc'ed, release with ribbit_row_purity_free(); *sites with ribbit_interruptions_free(); *observed
+ * with ribbit_text_free(); *observed_offsets with ribbit_intervals_free(). */
+int ribbit_host_record_interruptions(const char *sequence, int64_t length, const int32_t *intervals, const int32_t *motif_lengths,
+                                     size_t n, const char *cigars, const int32_t *offsets, RibbitRowPurity **rows,
+                                     RibbitInterruption **sites, size_t *n_sites, char **observed, int32_t **observed_offsets);
+void ribbit_row_purity_free(RibbitRowPurity *rows);
+void ribbit_interruptions_free(RibbitInterruption *sites);
+/* One line per interruption of every CONSISTENT row of one record (host only), in order, nine tab-separated columns:
+ *   name, start, end, the interruption's ops byte for byte from the CIGAR (1X, 2I1X), the observed bases or "." when there
+ *   are none, the row's start and end as the BED has them (from `intervals`), the row's motif byte for byte, and
+ *   unit = (start - s) / k, the 0-based repeat unit the site falls in, k being the motif's length.
+ * bed_text: row i on line i, the motif its eighth column from the end; cigars: the pool the sites' cigar_at point into,
+ * NUL-terminated as ribbit_bed_cigars hands it out.  The interruptions of inconsistent rows are left out;
+ * *rows_left_out = the number of inconsistent rows.  A bed_text that does not have n lines or has a line that is not a
+ * row, a first / count outside sites, a site whose row is not the row that owns it, a cigar_at / cigar_len outside the
+ * pool, observed_offsets that do not start at 0 or do not ascend: RIBBIT_E_ARG.  *text malloc'ed, release with
+ * ribbit_text_free(). */
+int ribbit_interruption_text(const char *name, const char *bed_text, size_t bed_len, const int32_t *intervals, size_t n,
+                             const RibbitRowPurity *rows, const RibbitInterruption *sites, size_t n_sites, const char *cigars,
+                             const char *observed, const int32_t *observed_offsets, char **text, size_t *len,
+                             size_t *rows_left_out);
+/* The record's BED rows with the decode appended (host only): line i of bed_text, byte for byte, then seven more columns, 18
+ * in all: count, x, ins, del, pure_start, pure_end and pure_units = (pure_end - pure_start) / k; for an inconsistent row
+ * the last three are ".".  bed_text: row i on line i (a last line without its newline counts, and is written with one).  A
+ * bed_text that does not have n lines, a k below 1: RIBBIT_E_ARG.  *text malloc'ed, release with ribbit_text_free(). */
+int ribbit_bed_purity_text(const char *bed_text, size_t bed_len, const int32_t *intervals, const int32_t *motif_lengths,
+                           const RibbitRowPurity *rows, size_t n, char **text, size_t *len);
+
+/*
  * ---- streaming FASTA ingest ---------------------------------------------------------------------------------------
  * Replaces the reader loop of ribbit.cpp:269-280 (getline + `sequence += line` into one pageable std::string per
  * record).  The file is read in 16-MB blocks; line bodies are copied once, straight into a page-locked buffer

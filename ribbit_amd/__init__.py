@@ -21,7 +21,8 @@ __all__ = ["RibbitHipError", "ScanParams", "Scanner", "library_path", "load_libr
            "OverlapTotals", "OVERLAP_TOTALS", "host_record_overlap", "bed_overlap_text",
            "host_record_best", "bed_rows_text",
            "MOTIF_CLASS_DT", "bed_motifs", "host_record_classes", "bed_class_text", "class_summary_text",
-           "COMPOUND_DT", "host_record_compounds", "class_labels", "compound_text"]
+           "COMPOUND_DT", "host_record_compounds", "class_labels", "compound_text",
+           "INTERRUPTION_DT", "ROW_PURITY_DT", "bed_cigars", "host_record_interruptions", "interruption_text", "bed_purity_text"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -38,6 +39,8 @@ SEED_DT = np.dtype([("start", "<i4"), ("end", "<i4"), ("mlen", "<i4"), ("type", 
 LOCUS_DT = np.dtype([(n, "<i4") for n in ("start", "end", "rows", "covered", "best_row")])      # RibbitLocus
 MOTIF_CLASS_DT = np.dtype([("bases", "<i8")] + [(n, "<i4") for n in ("length", "rows", "first_row", "longest_row")])      # RibbitMotifClass
 COMPOUND_DT = np.dtype([("bases", "<i8")] + [(n, "<i4") for n in ("start", "end", "rows", "classes", "switches", "overlaps", "first", "pad")])      # RibbitCompound
+INTERRUPTION_DT = np.dtype([(n, "<i4") for n in ("row", "start", "end", "x", "ins", "del", "cigar_at", "cigar_len")])      # RibbitInterruption
+ROW_PURITY_DT = np.dtype([(n, "<i4") for n in ("first", "count", "x", "ins", "del", "query", "pure_start", "pure_end")])      # RibbitRowPurity
 
 # every symbol include/ribbit_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -71,6 +74,8 @@ ABI_SYMBOLS = [
     "ribbit_bed_motifs", "ribbit_hip_record_classes", "ribbit_host_record_classes", "ribbit_motif_classes_free", "ribbit_bed_class_text",
     "ribbit_class_summary_text",
     "ribbit_hip_record_compounds", "ribbit_host_record_compounds", "ribbit_compounds_free", "ribbit_class_labels", "ribbit_compound_text",
+    "ribbit_bed_cigars", "ribbit_hip_record_interruptions", "ribbit_host_record_interruptions", "ribbit_row_purity_free", "ribbit_interruptions_free",
+    "ribbit_interruption_text", "ribbit_bed_purity_text",
 ]
 
 MASK_MODES = {"soft": 0, "hard": 1}     # RIBBIT_MASK_SOFT / RIBBIT_MASK_HARD
@@ -321,6 +326,17 @@ def load_library():
     L.ribbit_compounds_free.restype = None
     L.ribbit_class_labels.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp)]
     L.ribbit_compound_text.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, i64, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_bed_cigars.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_hip_record_interruptions.argtypes = [vp, vp, vp, C.c_size_t, C.c_char_p, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(vp)]
+    L.ribbit_host_record_interruptions.argtypes = [C.c_char_p, i64, vp, vp, C.c_size_t, C.c_char_p, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp),
+                                                   C.POINTER(vp)]
+    L.ribbit_row_purity_free.argtypes = [vp]
+    L.ribbit_row_purity_free.restype = None
+    L.ribbit_interruptions_free.argtypes = [vp]
+    L.ribbit_interruptions_free.restype = None
+    L.ribbit_interruption_text.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, vp, C.c_size_t, vp, vp, C.c_size_t, C.c_char_p, C.c_char_p, vp, C.POINTER(vp),
+                                           C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.ribbit_bed_purity_text.argtypes = [C.c_char_p, C.c_size_t, vp, vp, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
     _lib = L
     return L
 
@@ -923,6 +939,121 @@ def compound_text(name, bed, length: int, intervals, compounds, members) -> byte
         L.ribbit_text_free(text)
 
 
+def bed_cigars(text):
+    """ribbit_bed_cigars: column 11 of every row of BED text as refine_bed writes it -> (the CIGARs concatenated, bytes; their
+    n + 1 offsets, int32)."""
+    L = load_library()
+    raw = text.encode() if isinstance(text, str) else bytes(text)
+    pool, offsets, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
+    rc = L.ribbit_bed_cigars(raw, len(raw), C.byref(pool), C.byref(offsets), C.byref(n))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_bed_cigars error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        off = _copy(offsets.value, n.value + 1, np.dtype("<i4"))
+        return C.string_at(pool.value, int(off[-1])), off
+    finally:
+        L.ribbit_text_free(pool)
+        L.ribbit_intervals_free(offsets)
+
+
+def _interruption_args(intervals, motif_lengths, cigars, offsets):
+    """the rows, their motif lengths, the CIGAR pool and its offsets as the C ABI takes them; `cigars` may also be a list of
+    strings (offsets None)"""
+    iv = _pairs(intervals)
+    if offsets is None:
+        parts = [c.encode() if isinstance(c, str) else bytes(c) for c in cigars]
+        offsets = np.concatenate([[0], np.cumsum([len(c) for c in parts], dtype=np.int64)])
+        cigars = b"".join(parts)
+    pool = cigars.encode() if isinstance(cigars, str) else bytes(cigars)
+    off, k = np.asarray(offsets), np.asarray(motif_lengths)
+    if off.ndim != 1 or len(off) != len(iv) + 1:
+        raise ValueError(f"{len(iv)} rows want {len(iv) + 1} offsets")
+    if k.ndim != 1 or len(k) != len(iv):
+        raise ValueError(f"{len(iv)} rows want {len(iv)} motif lengths")
+    for a in (off, k):
+        if len(a) and (a.min() < -(1 << 31) or a.max() >= (1 << 31)):
+            raise ValueError("an offset or a motif length is not an int32")
+    return iv, np.ascontiguousarray(k, dtype=np.int32), pool, np.ascontiguousarray(off, dtype=np.int32)
+
+
+def _interruption_result(rows, n, sites, m, observed, offsets):
+    off = _copy(offsets, m + 1, np.dtype("<i4")) if m else np.zeros(1, np.int32)
+    return _copy(rows, n, ROW_PURITY_DT), _copy(sites, m, INTERRUPTION_DT), C.string_at(observed, int(off[-1])) if m else b"", off
+
+
+def host_record_interruptions(sequence: bytes, intervals, motif_lengths, cigars, offsets=None):
+    """ribbit_host_record_interruptions: every row's CIGAR decoded -> (a ROW_PURITY_DT record per row; the interruptions by row,
+    then in CIGAR order, an INTERRUPTION_DT array; their observed bases concatenated, bytes; the n_sites + 1 offsets of those,
+    int32).  cigars, offsets: as bed_cigars returns them, or a list of strings and None.  The contract is in
+    include/ribbit_hip.h.  No GPU needed."""
+    L = load_library()
+    iv, k, pool, off = _interruption_args(intervals, motif_lengths, cigars, offsets)
+    seq = bytes(sequence)
+    rows, sites, m, observed, offsets_out = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_void_p()
+    rc = L.ribbit_host_record_interruptions(seq, len(seq), iv.ctypes.data if len(iv) else None, k.ctypes.data if len(iv) else None, len(iv), pool, off.ctypes.data,
+                                            C.byref(rows), C.byref(sites), C.byref(m), C.byref(observed), C.byref(offsets_out))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_host_record_interruptions error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return _interruption_result(rows.value, len(iv), sites.value, m.value, observed.value, offsets_out.value)
+    finally:
+        L.ribbit_row_purity_free(rows)
+        L.ribbit_interruptions_free(sites)
+        L.ribbit_text_free(observed)
+        L.ribbit_intervals_free(offsets_out)
+
+
+def interruption_text(name, bed, intervals, rows, sites, cigars, observed, observed_offsets):
+    """ribbit_interruption_text: one line per interruption of every consistent row of one record -> (the text: name, start, end,
+    the interruption's ops, the observed bases or '.', the row's start and end, its motif and the 0-based repeat unit the site
+    falls in; the number of inconsistent rows, whose interruptions are left out).  cigars: the pool the sites point into."""
+    L = load_library()
+    raw = name.encode() if isinstance(name, str) else bytes(name)
+    pool = cigars.encode() if isinstance(cigars, str) else bytes(cigars)
+    if b"\0" in raw or b"\0" in pool:
+        raise ValueError("a record name or a CIGAR pool cannot hold a NUL byte")
+    text_in = bed.encode() if isinstance(bed, str) else bytes(bed)
+    iv = _pairs(intervals)
+    per_row = np.ascontiguousarray(np.asarray(rows, dtype=ROW_PURITY_DT).reshape(-1))
+    st = np.ascontiguousarray(np.asarray(sites, dtype=INTERRUPTION_DT).reshape(-1))
+    off = np.ascontiguousarray(np.asarray(observed_offsets, dtype=np.int32).reshape(-1))
+    if len(per_row) != len(iv) or len(off) != len(st) + 1:
+        raise ValueError(f"{len(iv)} rows want {len(iv)} records, {len(st)} interruptions {len(st) + 1} offsets")
+    obs = bytes(observed)
+    if len(off) and len(obs) < int(off.max()):
+        raise ValueError("the offsets reach behind the observed bases")
+    text, n, left = C.c_void_p(), C.c_size_t(), C.c_size_t()
+    rc = L.ribbit_interruption_text(raw, text_in, len(text_in), iv.ctypes.data if len(iv) else None, len(iv), per_row.ctypes.data if len(iv) else None,
+                                    st.ctypes.data if len(st) else None, len(st), pool, obs, off.ctypes.data, C.byref(text), C.byref(n), C.byref(left))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_interruption_text error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return C.string_at(text.value, n.value), left.value
+    finally:
+        L.ribbit_text_free(text)
+
+
+def bed_purity_text(bed, intervals, motif_lengths, rows) -> bytes:
+    """ribbit_bed_purity_text: the lines of `bed` (one record's BED text, row i on line i), each with seven more columns: count,
+    x, ins, del, pure_start, pure_end and pure_units (the last three '.' for a row whose CIGAR does not span it)."""
+    L = load_library()
+    text_in = bed.encode() if isinstance(bed, str) else bytes(bed)
+    iv = _pairs(intervals)
+    k = np.ascontiguousarray(np.asarray(motif_lengths, dtype=np.int32).reshape(-1))
+    per_row = np.ascontiguousarray(np.asarray(rows, dtype=ROW_PURITY_DT).reshape(-1))
+    if len(k) != len(iv) or len(per_row) != len(iv):
+        raise ValueError(f"{len(iv)} rows want {len(iv)} motif lengths and records")
+    text, n = C.c_void_p(), C.c_size_t()
+    rc = L.ribbit_bed_purity_text(text_in, len(text_in), iv.ctypes.data if len(iv) else None, k.ctypes.data if len(iv) else None,
+                                  per_row.ctypes.data if len(iv) else None, len(iv), C.byref(text), C.byref(n))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_bed_purity_text error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return C.string_at(text.value, n.value)
+    finally:
+        L.ribbit_text_free(text)
+
+
 def host_perfect_runs_from_events(min_motif: int, max_motif: int, event_parts, count_parts):
     """ribbit_host_perfect_runs_from_events: per-rank (events, per-motif counts) -> paired runs. No GPU needed."""
     L = load_library()
@@ -1282,6 +1413,14 @@ class Scanner:
         self._check(self._L.ribbit_hip_record_compounds(self._h, iv.ctypes.data if len(iv) else None, lab.ctypes.data if len(iv) else None, len(iv), gap,
                                                         C.byref(chains), C.byref(n), C.byref(members), C.byref(m)))
         return _copy(chains.value, n.value, COMPOUND_DT), _copy(members.value, m.value, np.dtype("<i4"))
+
+    def record_interruptions(self, intervals, motif_lengths, cigars, offsets=None):
+        """The loaded record's rows' CIGARs decoded on the GPU (ribbit_hip_record_interruptions); see host_record_interruptions"""
+        iv, k, pool, off = _interruption_args(intervals, motif_lengths, cigars, offsets)
+        rows, sites, m, observed, offsets_out = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_void_p()
+        self._check(self._L.ribbit_hip_record_interruptions(self._h, iv.ctypes.data if len(iv) else None, k.ctypes.data if len(iv) else None, len(iv), pool,
+                                                            off.ctypes.data, C.byref(rows), C.byref(sites), C.byref(m), C.byref(observed), C.byref(offsets_out)))
+        return _interruption_result(rows.value, len(iv), sites.value, m.value, observed.value, offsets_out.value)
 
     def record_density(self, intervals, window: int) -> np.ndarray:
         """The loaded record's covered bases per window on the GPU (ribbit_hip_record_density); see host_record_density"""

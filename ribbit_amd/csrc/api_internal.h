@@ -16,7 +16,8 @@
 //   api_best.cpp        the best non-overlapping rows of a record (best.hip), its host twin, the chosen rows' text
 //   api_classes.cpp     the rows of a record grouped by canonical motif class (classes.hip), its host twin, the motifs of a BED text, both texts
 //   api_compound.cpp    the rows of a record chained into compound loci (compound.hip), its host twin, the classes as labels, the chains' text
-// The last seven are the row outputs: their buffers are the handle's RowBufs `rows`, and what their host sides share is below
+//   api_interruptions.cpp  every row's CIGAR decoded into interruptions and the pure stretch (interruptions.hip), its host twin, the CIGARs of a BED text, both texts
+// The last eight are the row outputs: their buffers are the handle's RowBufs `rows`, and what their host sides share is below
 // (hand_out, clipped_sorted_rows, bed_text_parts, bed_line_starts).
 // Host threads: every team of them, here and in refine.cpp, parallel_merge.cpp and host_planes.cpp, is started by rb::on_threads /
 // rb::over_pieces of host_threads.h (part 0 on the caller, a thread that cannot start leaves its part to the caller, all joined, the
@@ -189,7 +190,8 @@ struct PairBufs {
     uint32_t *h_pub_dev = nullptr;         // the same memory as the device sees it
 };
 
-// ---- shared by the host sides of the row outputs (api_mask.cpp, api_repeats.cpp, api_loci.cpp, api_overlap.cpp, api_best.cpp, api_classes.cpp, api_compound.cpp)
+// ---- shared by the host sides of the row outputs (api_mask.cpp, api_repeats.cpp, api_loci.cpp, api_overlap.cpp, api_best.cpp, api_classes.cpp, api_compound.cpp,
+// api_interruptions.cpp)
 
 // n elements as malloc memory the caller frees (never a null pointer, whatever n): a copy of src, or for the caller to fill
 // when src is null; terminate: a zero element behind them
@@ -395,7 +397,8 @@ struct RibbitHandle {
     bool bed_in_raw = false;              // the last ribbit_hip_refine_bed returned bed_raw, not bed
     rb::SeedLists lists;
     bool refine_met_empty_query = false;  // the last ribbit_hip_refine_bed on this handle met an alignment with an empty query (ribbit_hip_refine_met_empty_query)
-    // the row outputs of the loaded record (api_mask.cpp, api_repeats.cpp, api_loci.cpp, api_overlap.cpp, api_best.cpp, api_classes.cpp, api_compound.cpp)
+    // the row outputs of the loaded record (api_mask.cpp, api_repeats.cpp, api_loci.cpp, api_overlap.cpp, api_best.cpp, api_classes.cpp, api_compound.cpp,
+    // api_interruptions.cpp)
     struct RowBufs {
         // the masked body of the loaded record (api_mask.cpp): coverage bitmap, intervals, the text on the device and on its way up
         DevBuf<uint32_t> d_mask_bits;
@@ -463,6 +466,13 @@ struct RibbitHandle {
         DevBuf<uint8_t> d_cmp_flags, d_cmp_scratch;
         DevBuf<uint8_t> d_cmp;
         PinnedBuf<uint8_t> h_cmp;
+        // the rows' CIGARs decoded (api_interruptions.cpp): the rows | the offsets | the CIGARs on their way down and on the device,
+        // everything that is per op, per run, per interruption or per row (rb::InterruptionLayout), the scans' scratch, the counts on
+        // their way up, the observed bases on the device, and the result on its way up: the rows, the interruptions, the offsets,
+        // the observed bases
+        PinnedBuf<uint8_t> h_int_in, h_int_totals;
+        DevBuf<uint8_t> d_int_in, d_int_work, d_int_scratch, d_int_text;
+        PinnedBuf<uint8_t> h_int;
         size_t rep_budget = 0;           // text budget of one batch of repeat sequences in bytes (0: REPEAT_TEXT_BUDGET)
     } rows;
     RibbitHandle *aux = nullptr;          // helper handle of ribbit_hip_refine_bed: streams and buffers of the long alignment batch

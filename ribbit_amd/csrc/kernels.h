@@ -357,6 +357,40 @@ hipError_t launch_compounds(const int32_t *rows, const int32_t *labels, int64_t 
                             CompoundSums *sums, uint8_t *flags, CompoundTotals *totals, int32_t *members, RibbitCompound *compounds, void *scratch,
                             size_t scratch_bytes, hipStream_t stream);
 
+// interruptions.hip: every row's CIGAR decoded into interruptions and the pure stretch (api_interruptions.cpp).  rows, offsets:
+// the n >= 1 rows and their n + 1 ascending offsets into pool on the device; pool: 16-byte aligned, zero-filled from its last
+// byte to the next multiple of 16 and 16 bytes further.  The ops of a pool of P bytes are at most interruptions_op_cap(P), which
+// sizes everything that is per op, per run or per interruption; work: interruptions_layout(n, P).bytes, carved as the layout
+// says; scratch: interruptions_scratch_bytes(P).  launch_interruptions fills totals, the rows' records and the sites (with their
+// clipped widths and where their observed bases start); the caller reads totals, refuses what it reports (bad_at, bad_row,
+// observed) and, when there are observed bytes, calls launch_interruption_gather for them.
+struct InterruptionTotals {
+    uint32_t ops, runs, sites;        // ops, runs of ops of one kind (match / not), interruptions
+    uint32_t bad_at;                  // the lowest offending byte offset of the pool (the grammar), 0xffffffff: none
+    uint32_t bad_row;                 // the lowest row whose sums do not fit, 0xffffffff: none
+    uint32_t spare;
+    unsigned long long observed;      // observed bytes of all interruptions
+};
+struct InterruptionSums {             // what the ops up to one add up to
+    unsigned long long match, x, ins, del;
+    uint32_t runs, sites, row, spare; // run heads and interruption heads so far; the last row head's row + 1
+};
+struct InterruptionBest {             // a run's stretch key (length << 32 | ~start, 0: no stretch) and whether it is its row's first
+    unsigned long long key;
+    uint32_t head, spare;
+};
+struct InterruptionLayout {           // byte offsets into work, each a multiple of 16
+    size_t counts, ops, op_row, first_op, sums, run_head, best, width, source, offsets64, spans, rows, sites, offsets32, totals, bytes;
+};
+constexpr int64_t INTERRUPTION_SPAN = 4096;      // observed bytes one workgroup gathers, 16 per lane
+inline size_t interruptions_op_cap(size_t pool_bytes) { return pool_bytes / 2 + 1; }
+InterruptionLayout interruptions_layout(int64_t n, size_t pool_bytes);
+size_t interruptions_scratch_bytes(size_t pool_bytes);
+hipError_t launch_interruptions(const int32_t *rows, const int32_t *offsets, const uint8_t *pool, int64_t n, size_t pool_bytes, int64_t length, uint8_t *work,
+                                const InterruptionLayout &at, void *scratch, size_t scratch_bytes, hipStream_t stream);
+hipError_t launch_interruption_gather(const uint8_t *ascii, uint8_t *work, const InterruptionLayout &at, uint32_t sites, int64_t observed, uint8_t *out,
+                                      hipStream_t stream);
+
 // profiling aid: reads nwords dwords of src with one coalesced dword per lane (known byte count)
 void launch_calib_stream_read(const uint32_t *src, int64_t nwords, uint32_t *sink, hipStream_t stream);
 

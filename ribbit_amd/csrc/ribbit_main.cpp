@@ -7,6 +7,7 @@
 //              [--repeat-fasta FILE [--flank N]] [--loci-bed FILE [--loci-gap D]] [--density-bedgraph FILE [--density-window W]]
 //              [--overlap-with OTHER.bed [--overlap-bed FILE] [--overlap-summary FILE]] [--best-bed FILE]
 //              [--class-bed FILE] [--motif-summary FILE] [--compound-bed FILE [--compound-gap D]]
+//              [--interruption-bed FILE] [--purity-bed FILE]
 //
 // Records are independent (ribbit.cpp:269-280 handles them one after the other); here up to --jobs of them are in
 // flight at once PER GPU, each on its own handle / HIP streams, so that the upload and GPU scans of one record overlap
@@ -28,13 +29,16 @@
 // one line per class and record (ribbit_class_summary_text).  --compound-bed chains the rows of --best-bed's selection that lie at most
 // --compound-gap bases apart (ribbit_hip_record_compounds) and writes one line per chain with its kind -- perfect, interrupted,
 // compound -- and its structure, e.g. (CA)12n5(GA)8 (ribbit_class_labels, ribbit_compound_text); the selection and the classes are
-// computed once per record, whichever outputs ask for them.  The BED rows are read back once per record, however many of the
-// ten are asked for.
+// computed once per record, whichever outputs ask for them.  --interruption-bed and --purity-bed decode every row's CIGAR, column 11
+// (ribbit_bed_cigars, ribbit_hip_record_interruptions): one line per run of substitutions and indels inside a row, with the bases
+// the record has there (ribbit_interruption_text), and the rows again with their interruption counts and their longest
+// uninterrupted stretch (ribbit_bed_purity_text); the column-4 motifs are parsed once per record for these and the class outputs.
+// The BED rows are read back once per record, however many of the twelve are asked for.
 //
-// These ten are the ROW OUTPUTS, and each is described once, by its entry of kOutputs below: its file option, its stage (enum
+// These twelve are the ROW OUTPUTS, and each is described once, by its entry of kOutputs below: its file option, its stage (enum
 // Stage, with the stage's names beside it), its qualifier options with their ranges and wording (defaults: Settings), and the function that
 // makes one record's text from the record's rows.  Parsing, the "needs" checks, opening the files, the sinks of the pipelined
-// records and of the last one, --timing and the RIBBIT_PROFILE line are loops over that table.  An eleventh row output is: a stage in
+// records and of the last one, --timing and the RIBBIT_PROFILE line are loops over that table.  A thirteenth row output is: a stage in
 // the enum and its names, the qualifiers' fields in Settings, a produce function, an entry of kOutputs, and its lines of kHelp.
 //
 // Reproduced quirks: -p is accepted and ignored (Q1); without -o the BED rows go to
@@ -42,6 +46,7 @@
 // record is processed even when the file is empty (Q4).
 #include <algorithm>
 #include <array>
+#include <atomic>
 #include <cctype>
 #include <charconv>
 #include <chrono>
@@ -80,13 +85,13 @@ void check(int rc) {
 }
 
 // The stages of a record: the six every record goes through, then one per row output, in the order of kOutputs.
-enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, OVERLAP, BEST, CLASSES, COMPOUND, N_STAGES };
+enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, OVERLAP, BEST, CLASSES, COMPOUND, INTERRUPTIONS, N_STAGES };
 constexpr int N_FIXED_STAGES = MASK;
 // a stage's key in --timing's stage_ms_summed_over_records and its label in the RIBBIT_PROFILE line
 const struct { const char *key, *label; } kStageNames[N_STAGES] = {
     {"load", "load"}, {"perfect", "perfect"}, {"substitutions", "substitutions"}, {"anchored", "anchored"}, {"dispatch", "dispatch"},
     {"refine_and_bed", "refine+BED"}, {"mask", "mask"}, {"repeats", "repeats"}, {"loci", "loci"}, {"density", "density"}, {"overlap", "overlap"},
-    {"best", "best"}, {"classes", "classes"}, {"compound", "compound"}};
+    {"best", "best"}, {"classes", "classes"}, {"compound", "compound"}, {"interruptions", "interruptions"}};
 
 // wall time per stage, summed over the records (--timing, RIBBIT_PROFILE=1)
 double g_stage_ms[N_STAGES] = {};
@@ -115,19 +120,27 @@ struct RecordRows {
     size_t bed_len;
     std::string bed_copy;                // ... or this copy of it, when it came in slices and an output quotes it
     const std::vector<int32_t> *other;   // the record's intervals of --overlap-with, (start, end) each in file order (null: none)
-    // the record's rows by motif class, computed by the first of the two outputs that asks (classes_of): the motifs of the BED text
-    // (owned here) and the handle's result, which stays valid while the record's outputs are produced
+    // the column-4 motifs of the BED text (owned here), parsed by the first output that asks (motifs_of): the class outputs and the
+    // interruption outputs
+    struct Motifs {
+        bool have = false;
+        char *pool = nullptr;
+        int32_t *offsets = nullptr;
+        Motifs() = default;
+        Motifs(const Motifs &) = delete;
+        Motifs &operator=(const Motifs &) = delete;
+        ~Motifs() { ribbit_text_free(pool); ribbit_intervals_free(offsets); }
+    };
+    mutable Motifs motifs;
+    // the record's rows by motif class, computed by the first of the outputs that asks (classes_of): the handle's result, which
+    // stays valid while the record's outputs are produced
     struct Classes {
         bool have = false;
-        char *motifs = nullptr;
-        int32_t *offsets = nullptr;
+        const char *motifs = nullptr;        // (RecordRows::motifs')
+        const int32_t *offsets = nullptr;
         const char *classes = nullptr, *strands = nullptr;
         const RibbitMotifClass *groups = nullptr;
         size_t n_groups = 0;
-        Classes() = default;
-        Classes(const Classes &) = delete;
-        Classes &operator=(const Classes &) = delete;
-        ~Classes() { ribbit_text_free(motifs); ribbit_intervals_free(offsets); }
     };
     mutable Classes by_class;
     // the record's best non-overlapping rows, computed by the first of the two outputs that asks (best_of): the handle's result,
@@ -138,6 +151,24 @@ struct RecordRows {
         size_t n = 0;
     };
     mutable Best best;
+    // the record's CIGARs decoded, computed by the first of the two outputs that asks (interruptions_of): the CIGARs of the BED text
+    // and the motifs' lengths (owned here) and the handle's result, which stays valid while the record's outputs are produced
+    struct Interruptions {
+        bool have = false;
+        char *cigars = nullptr;
+        int32_t *offsets = nullptr;
+        std::vector<int32_t> motif_lengths;
+        const RibbitRowPurity *rows = nullptr;
+        const RibbitInterruption *sites = nullptr;
+        size_t n_sites = 0;
+        const char *observed = nullptr;
+        const int32_t *observed_offsets = nullptr;
+        Interruptions() = default;
+        Interruptions(const Interruptions &) = delete;
+        Interruptions &operator=(const Interruptions &) = delete;
+        ~Interruptions() { ribbit_text_free(cigars); ribbit_intervals_free(offsets); }
+    };
+    mutable Interruptions decoded;
     size_t n() const { return iv.size() / 2; }
 };
 
@@ -278,14 +309,25 @@ void produce_best(RibbitHandle *h, const RecordRows &r, const Settings &, const 
     ribbit_text_free(text);
 }
 
+// the column-4 motifs of a record's rows: the second call finds what the first left in the record's rows
+const RecordRows::Motifs &motifs_of(const RecordRows &r) {
+    RecordRows::Motifs &m = r.motifs;
+    if (m.have) return m;
+    size_t n = 0;
+    check(ribbit_bed_motifs(r.bed_text, r.bed_len, &m.pool, &m.offsets, &n));
+    if (n != r.n()) throw PathError{"the BED text has " + std::to_string(n) + " motifs for " + std::to_string(r.n()) + " rows"};
+    m.have = true;
+    return m;
+}
+
 // both class outputs of a record: the second call finds what the first left in the record's rows
 const RecordRows::Classes &classes_of(RibbitHandle *h, const RecordRows &r) {
     RecordRows::Classes &c = r.by_class;
     if (c.have) return c;
-    size_t n = 0;
-    check(ribbit_bed_motifs(r.bed_text, r.bed_len, &c.motifs, &c.offsets, &n));
-    if (n != r.n()) throw PathError{"the BED text has " + std::to_string(n) + " motifs for " + std::to_string(r.n()) + " rows"};
-    check(ribbit_hip_record_classes(h, r.iv.data(), n, c.motifs, c.offsets, &c.classes, &c.strands, &c.groups, &c.n_groups));
+    const RecordRows::Motifs &m = motifs_of(r);
+    c.motifs = m.pool;
+    c.offsets = m.offsets;
+    check(ribbit_hip_record_classes(h, r.iv.data(), r.n(), c.motifs, c.offsets, &c.classes, &c.strands, &c.groups, &c.n_groups));
     c.have = true;
     return c;
 }
@@ -338,6 +380,47 @@ void produce_compound(RibbitHandle *h, const RecordRows &r, const Settings &s, c
     ribbit_text_free(text);
 }
 
+// both interruption outputs of a record: the second call finds what the first left in the record's rows
+const RecordRows::Interruptions &interruptions_of(RibbitHandle *h, const RecordRows &r) {
+    RecordRows::Interruptions &d = r.decoded;
+    if (d.have) return d;
+    const RecordRows::Motifs &m = motifs_of(r);
+    d.motif_lengths.resize(r.n());
+    for (size_t i = 0; i < r.n(); ++i) d.motif_lengths[i] = m.offsets[i + 1] - m.offsets[i];
+    size_t n = 0;
+    check(ribbit_bed_cigars(r.bed_text, r.bed_len, &d.cigars, &d.offsets, &n));
+    if (n != r.n()) throw PathError{"the BED text has " + std::to_string(n) + " CIGARs for " + std::to_string(r.n()) + " rows"};
+    check(ribbit_hip_record_interruptions(h, r.iv.data(), d.motif_lengths.data(), n, d.cigars, d.offsets, &d.rows, &d.sites, &d.n_sites, &d.observed,
+                                          &d.observed_offsets));
+    d.have = true;
+    return d;
+}
+
+// rows whose CIGAR does not span them, over all records: their interruptions are not in --interruption-bed
+std::atomic<size_t> g_rows_left_out{0};
+
+void produce_interruption_bed(RibbitHandle *h, const RecordRows &r, const Settings &, const Sink &write) {
+    char *text = nullptr;
+    size_t len = 0, left_out = 0;
+    StageClock c(INTERRUPTIONS);
+    const RecordRows::Interruptions &d = interruptions_of(h, r);
+    check(ribbit_interruption_text(r.name.c_str(), r.bed_text, r.bed_len, r.iv.data(), r.n(), d.rows, d.sites, d.n_sites, d.cigars, d.observed, d.observed_offsets,
+                                   &text, &len, &left_out));
+    g_rows_left_out += left_out;
+    write(text, len);
+    ribbit_text_free(text);
+}
+
+void produce_purity_bed(RibbitHandle *h, const RecordRows &r, const Settings &, const Sink &write) {
+    char *text = nullptr;
+    size_t len = 0;
+    StageClock c(INTERRUPTIONS);
+    const RecordRows::Interruptions &d = interruptions_of(h, r);
+    check(ribbit_bed_purity_text(r.bed_text, r.bed_len, r.iv.data(), d.motif_lengths.data(), d.rows, r.n(), &text, &len));
+    write(text, len);
+    ribbit_text_free(text);
+}
+
 // One entry per row output.  The order is the order of everything that is done for all of them: the "needs" checks, opening the
 // files (binary), producing a record's texts, the keys of --timing.
 struct Output {
@@ -348,7 +431,7 @@ struct Output {
     Qualifier qualifiers[MAX_QUALIFIERS];    // (name null: none)
     bool needs_other;                        // it compares the rows with the intervals of --overlap-with
 };
-constexpr size_t N_OUTPUTS = 10;
+constexpr size_t N_OUTPUTS = 12;
 const Output kOutputs[N_OUTPUTS] = {
     {"masked-fasta", MASK, false, produce_masked,
      {{"mask", Qualifier::SOFT_HARD, 0, 0, 0, nullptr, &Settings::mask_mode},
@@ -365,7 +448,9 @@ const Output kOutputs[N_OUTPUTS] = {
     {"class-bed", CLASSES, true, produce_class_bed, {{}, {}}, false},
     {"motif-summary", CLASSES, true, produce_motif_summary, {{}, {}}, false},
     {"compound-bed", COMPOUND, true, produce_compound,
-     {{"compound-gap", Qualifier::BASES, 0, 2147483647, 10, "0 .. 2147483647", &Settings::compound_gap}, {}}, false}};
+     {{"compound-gap", Qualifier::BASES, 0, 2147483647, 10, "0 .. 2147483647", &Settings::compound_gap}, {}}, false},
+    {"interruption-bed", INTERRUPTIONS, true, produce_interruption_bed, {{}, {}}, false},
+    {"purity-bed", INTERRUPTIONS, true, produce_purity_bed, {{}, {}}, false}};
 
 // the row outputs that are on, by stage: an output whose stage an earlier one has already named is left out (--timing, RIBBIT_PROFILE)
 std::vector<Stage> stages_on(const std::array<bool, N_OUTPUTS> &on) {
@@ -474,7 +559,16 @@ const char *kHelp =
     "                                lengths) and the structure, e.g. (CA)12n5(GA)8: motif and units of every row, n5 for 5\n"
     "                                bases between two rows\n"
     "  --compound-gap arg            (ribbit-hip) for --compound-bed: a row at most this many bases behind the rows before it\n"
-    "                                continues their chain, 0 .. 2147483647. Default: 100\n";
+    "                                continues their chain, 0 .. 2147483647. Default: 100\n"
+    "  --interruption-bed arg        (ribbit-hip) also write where the imperfections are to this file, decoded from the CIGAR of\n"
+    "                                every BED row: one line per run of substitutions and indels inside a row: name, start,\n"
+    "                                end, the run's CIGAR ops (1X, 2I1X, 1D), the bases the record has there ('.' for a\n"
+    "                                deletion alone), the row's start, end and motif, and the 0-based repeat unit the run\n"
+    "                                falls in. Rows whose CIGAR does not span them are left out and counted on stderr\n"
+    "  --purity-bed arg              (ribbit-hip) also write every BED row to this file with seven columns appended: the number\n"
+    "                                of such runs, their substituted, inserted and deleted bases, then start, end and whole\n"
+    "                                motif units of the row's longest uninterrupted stretch (the leftmost of equals; '.'\n"
+    "                                three times for a row whose CIGAR does not span it)\n";
 
 bool parse_device_list(const std::string &value, std::vector<int> &out) {
     out.clear();
@@ -734,7 +828,7 @@ void process_sequence(RibbitHandle *h, const RibbitRefineParams &prm, const std:
     { StageClock c(DISPATCH); check(ribbit_hip_dispatch_seeds(h, &d, &nd)); }
     // one record over several GPUs: only worth it from a few hundred thousand seeds on (RIBBIT_SHARD_MIN_SEEDS: a test hook)
     static const size_t shard_min = std::getenv("RIBBIT_SHARD_MIN_SEEDS") ? (size_t)std::atoll(std::getenv("RIBBIT_SHARD_MIN_SEEDS")) : 400000;
-    RecordRows rows{name, length, {}, nullptr, 0, {}, settings.other ? settings.other->of(name) : nullptr, {}, {}};
+    RecordRows rows{name, length, {}, nullptr, 0, {}, settings.other ? settings.other->of(name) : nullptr, {}, {}, {}, {}};
     const bool want_rows = jobs.any();
     if (helpers && !helpers->empty() && nd >= shard_min && nd >= 2 * (helpers->size() + 1)) {
         StageClock c(REFINE_BED);
@@ -999,6 +1093,8 @@ int main(int argc, char **argv) {
     size_t ignored = 0, ignored_names = 0;
     for (const auto &group : other.by_name)
         if (!group.second.is_record) { ignored += group.second.iv.size() / 2; ++ignored_names; }
+    if (const size_t left_out = g_rows_left_out.load())
+        std::cerr << "ribbit-hip: --interruption-bed: " << left_out << " rows whose CIGAR does not span the row were left out\n";
     if (ignored) std::cerr << "ribbit-hip: --overlap-with: " << ignored << " intervals of " << ignored_names << " names that are no record of the input were ignored\n";
     return status;
 }
