@@ -1,8 +1,8 @@
 // api_best.cpp -- the best non-overlapping rows of a record (best.hip); see api_internal.h for the map of the files behind
-// include/ribbit_hip.h.  The GPU form stages the rows itself (it reads no coverage bitmap), runs on the handle's stream and keeps
-// nothing between calls; the host twin is written from the contract, one sort and two sweeps over the whole order without the
+// include/ribbit_hip.h.  The GPU form stages the rows through stage_down (it reads no coverage bitmap), runs on the handle's stream
+// and keeps nothing between calls; the host twin is written from the contract, one sort and two sweeps over the whole order without the
 // kernels' segments; the chosen rows' text needs no GPU either.
-#include "api_internal.h"
+#include "bed_text.h"
 
 namespace {
 
@@ -29,19 +29,17 @@ int record_best_impl(RibbitHandle *h, const int32_t *intervals, size_t n, const 
     if (length == 0 || n == 0) return RIBBIT_OK;
     if ((rc = bind_device(h))) return rc;
     RibbitHandle::RowBufs &buf = h->rows;
-    if ((rc = buf.h_best_iv.ensure(2 * n, true))) return rc;
-    if ((rc = buf.d_best_iv.ensure(2 * n, true))) return rc;
     if ((rc = buf.d_best_keys.ensure(2 * n, true))) return rc;
     if ((rc = buf.d_best_work.ensure(3 * n, true))) return rc;
     if ((rc = buf.d_best_flags.ensure(2 * n, true))) return rc;
-    if ((rc = buf.d_best_scratch.ensure(rb::best_scratch_bytes((int64_t)n, length), true))) return rc;
+    if ((rc = buf.d_scratch.ensure(rb::best_scratch_bytes((int64_t)n, length), true))) return rc;
     if ((rc = buf.d_best.ensure(TOTALS_INTS + n, true))) return rc;
     if ((rc = buf.h_best.ensure(TOTALS_INTS + n, true))) return rc;
-    // (the staging buffer may still be the source of the last call's copy: that call ended in a synchronise)
-    std::memcpy(buf.h_best_iv.p, intervals, 2 * n * sizeof(int32_t));
-    HIP_TRY(hipMemcpyAsync(buf.d_best_iv.p, buf.h_best_iv.p, 2 * n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(rb::launch_best(buf.d_best_iv.p, (int64_t)n, length, buf.d_best_keys.p, buf.d_best_work.p, buf.d_best_flags.p,
-                            reinterpret_cast<rb::BestTotals *>(buf.d_best.p), buf.d_best.p + TOTALS_INTS, buf.d_best_scratch.p, buf.d_best_scratch.cap, h->stream));
+    const StageSegment down{intervals, 2 * n * sizeof(int32_t)};
+    const uint8_t *d_rows = nullptr;
+    if ((rc = stage_down(h, &down, 1, &d_rows))) return rc;
+    HIP_TRY(rb::launch_best(reinterpret_cast<const int32_t *>(d_rows), (int64_t)n, length, buf.d_best_keys.p, buf.d_best_work.p, buf.d_best_flags.p,
+                            reinterpret_cast<rb::BestTotals *>(buf.d_best.p), buf.d_best.p + TOTALS_INTS, buf.d_scratch.p, buf.d_scratch.cap, h->stream));
     HIP_TRY(hipMemcpyAsync(buf.h_best.p, buf.d_best.p, (TOTALS_INTS + n) * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     rb::BestTotals totals;
@@ -60,14 +58,9 @@ int host_record_best_impl(int64_t length, const int32_t *intervals, size_t n, in
     int rc;
     if ((rc = check_best_args(intervals, n, rows, n_best, bases))) return rc;
     if (length < 0 || length > (int64_t)INT32_MAX) return fail(RIBBIT_E_ARG, "a record of %lld bases", (long long)length);
-    struct Row { int64_t s, e; int32_t index; };
-    std::vector<Row> order;
-    order.reserve(n);
-    for (size_t i = 0; i < n; ++i) {
-        const int64_t s = std::max<int64_t>(intervals[2 * i], 0), e = std::min<int64_t>(intervals[2 * i + 1], length);
-        if (s < e) order.push_back(Row{s, e, (int32_t)i});
-    }
-    std::sort(order.begin(), order.end(), [](const Row &a, const Row &b) { return a.e != b.e ? a.e < b.e : a.s != b.s ? a.s < b.s : a.index < b.index; });
+    using Row = ClippedRow;
+    const std::vector<Row> order =
+        clipped_sorted_rows(length, intervals, n, [](const Row &a, const Row &b) { return a.e != b.e ? a.e < b.e : a.s != b.s ? a.s < b.s : a.index < b.index; });
     const size_t r = order.size();
     // forward: row k (1-based) is order[k - 1]; p(k): the rows that end at or before its start
     std::vector<int64_t> dp(r + 1, 0);
@@ -82,7 +75,7 @@ int host_record_best_impl(int64_t length, const int32_t *intervals, size_t n, in
     for (size_t k = r; k > 0;) {
         const Row &row = order[k - 1];
         if (row.e - row.s + dp[p[k]] > dp[k - 1]) {
-            chosen.push_back(row.index);
+            chosen.push_back((int32_t)row.index);
             k = p[k];
         } else {
             --k;
@@ -100,45 +93,25 @@ int bed_rows_text_impl(const char *bed, size_t bed_len, const int32_t *rows, siz
     if (!text || !len || (!bed && bed_len > 0) || (!rows && n_rows > 0)) return fail(RIBBIT_E_ARG, "null argument");
     // the BED text's line starts are found in pieces, and the chosen lines are copied in as many pieces
     const size_t parts = n_rows ? bed_text_parts(bed_len) : 1;
-    std::vector<size_t> line{0};
+    BedLines lines;
     int rc;
-    if (n_rows && (rc = bed_line_starts(bed, bed_len, parts, line))) return rc;
-    const size_t n_lines = line.size() - 1;
+    if (n_rows && (rc = lines.find(bed, bed_len, parts))) return rc;
+    const size_t n_lines = lines.count();
     const size_t out_parts = std::max<size_t>(1, std::min<size_t>(parts, n_rows >> 12));
-    std::vector<std::string> piece(out_parts);
-    std::vector<size_t> bad(out_parts, (size_t)-1);
-    rb::on_threads((unsigned)out_parts, [&](unsigned k) {
-        try {
-            std::string &out = piece[k];
-            const size_t from = n_rows * k / out_parts, to = n_rows * (k + 1) / out_parts;
-            size_t room = 0;
-            for (size_t i = from; i < to; ++i) {
-                if (rows[i] < 0 || (size_t)rows[i] >= n_lines) { bad[k] = i; return; }
-                room += line[(size_t)rows[i] + 1] - line[(size_t)rows[i]] + 1;
-            }
-            out.reserve(room);
-            for (size_t i = from; i < to; ++i) {
-                const char *p = bed + line[(size_t)rows[i]], *eol = bed + line[(size_t)rows[i] + 1];
-                if (eol > p && eol[-1] == '\n') --eol;
-                out.append(p, (size_t)(eol - p));
-                out += '\n';
-            }
-        } catch (const std::bad_alloc &) { bad[k] = (size_t)-2; }
-    });
-    size_t total = 0;
-    for (size_t k = 0; k < out_parts; ++k) {
-        if (bad[k] == (size_t)-2) return fail(RIBBIT_E_NOMEM, "out of host memory writing the chosen rows");
-        if (bad[k] != (size_t)-1) return fail(RIBBIT_E_ARG, "entry %zu: row %d is no line of the BED text (%zu lines)", bad[k], (int)rows[bad[k]], n_lines);
-        total += piece[k].size();
-    }
-    if ((rc = hand_out<char>(nullptr, total, true, text))) return rc;
-    size_t at = 0;
-    for (const std::string &s : piece) {
-        std::memcpy(*text + at, s.data(), s.size());
-        at += s.size();
-    }
-    *len = total;
-    return RIBBIT_OK;
+    return write_pieces(out_parts, "the chosen rows", text, len, [&](size_t k, std::string &out) {
+        const size_t from = n_rows * k / out_parts, to = n_rows * (k + 1) / out_parts;
+        size_t room = 0;
+        for (size_t i = from; i < to; ++i) {
+            if (rows[i] < 0 || (size_t)rows[i] >= n_lines) return PieceRefusal{1, i};
+            room += lines[(size_t)rows[i]].size() + 2;
+        }
+        out.reserve(room);
+        for (size_t i = from; i < to; ++i) {
+            put_field(out, lines[(size_t)rows[i]]);
+            out += '\n';
+        }
+        return PieceRefusal{};
+    }, [&](const PieceRefusal &b) { return fail(RIBBIT_E_ARG, "entry %zu: row %d is no line of the BED text (%zu lines)", b.a, (int)rows[b.a], n_lines); });
 }
 
 }  // namespace

@@ -1,16 +1,13 @@
 // api_classes.cpp -- the rows of a record grouped by canonical motif class (classes.hip); see api_internal.h for the map of the files
-// behind include/ribbit_hip.h.  The GPU form stages the rows, the offsets and the motifs in one page-locked buffer of its own (it
-// reads no coverage bitmap), runs on the handle's stream and keeps nothing between calls; the host twin is written from the
+// behind include/ribbit_hip.h.  The GPU form stages the rows, the offsets and the motifs through stage_down (it reads no coverage
+// bitmap), runs on the handle's stream and keeps nothing between calls; the host twin is written from the
 // contract: a least rotation of every motif and of its reverse complement on the host thread team, one sort, one sweep.  The
 // motifs of a BED text and the two outputs' texts need no GPU.
-#include "api_internal.h"
-
-#include <charconv>
+#include "bed_text.h"
 
 namespace {
 
-constexpr size_t MAX_ROWS = (size_t)INT32_MAX;      // (the indices are int32)
-constexpr size_t MAX_POOL = (size_t)INT32_MAX;      // (and so are the offsets)
+constexpr size_t MAX_ROWS = BED_MAX_ROWS;
 constexpr int32_t MAX_MOTIF = 1023;
 
 inline bool is_base(char c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T'; }
@@ -51,7 +48,6 @@ int check_class_args(const int32_t *intervals, size_t n, const char *motifs, con
 
 constexpr size_t HEADER_BYTES = 16;
 static_assert(sizeof(rb::ClassHeader) == HEADER_BYTES && sizeof(RibbitMotifClass) == 24, "the groups follow the header in one buffer");
-inline size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 int record_classes_impl(RibbitHandle *h, const int32_t *intervals, size_t n, const char *motifs, const int32_t *offsets, const char **classes,
                         const char **strands, const RibbitMotifClass **groups, size_t *n_groups) {
@@ -69,26 +65,19 @@ int record_classes_impl(RibbitHandle *h, const int32_t *intervals, size_t n, con
     // down: the rows | the offsets | the motifs, each on a 16-byte boundary (the motifs are read in aligned 8-byte words, up to one
     // word past their end); up: the header | n groups of room | the strands | the classes
     const size_t pool = (size_t)offsets[n];
-    const size_t in_off = round16(2 * n * sizeof(int32_t)), in_pool = in_off + round16((n + 1) * sizeof(int32_t)), in_bytes = in_pool + round16(pool) + 16;
     const size_t out_strands = HEADER_BYTES + n * sizeof(RibbitMotifClass), out_classes = out_strands + round16(n), out_bytes = out_classes + pool;
     RibbitHandle::RowBufs &buf = h->rows;
-    if ((rc = buf.h_class_in.ensure(in_bytes, true))) return rc;
-    if ((rc = buf.d_class_in.ensure(in_bytes, true))) return rc;
     if ((rc = buf.d_class_work.ensure(rb::classes_work_words((int64_t)n), true))) return rc;
-    if ((rc = buf.d_class_scratch.ensure(rb::classes_scratch_bytes((int64_t)n), true))) return rc;
+    if ((rc = buf.d_scratch.ensure(rb::classes_scratch_bytes((int64_t)n), true))) return rc;
     if ((rc = buf.d_class.ensure(out_bytes, true))) return rc;
     if ((rc = buf.h_class.ensure(out_bytes, true))) return rc;
-    // (the staging buffer may still be the source of the last call's copy: that call ended in a synchronise)
-    uint8_t *in = buf.h_class_in.p;
-    std::memcpy(in, intervals, 2 * n * sizeof(int32_t));
-    std::memcpy(in + in_off, offsets, (n + 1) * sizeof(int32_t));
-    std::memcpy(in + in_pool, motifs, pool);
-    std::memset(in + in_pool + pool, 0, in_bytes - in_pool - pool);
-    HIP_TRY(hipMemcpyAsync(buf.d_class_in.p, in, in_bytes, hipMemcpyHostToDevice, h->stream));
-    uint8_t *d_in = buf.d_class_in.p, *d_out = buf.d_class.p;
-    HIP_TRY(rb::launch_classes(reinterpret_cast<const int32_t *>(d_in), reinterpret_cast<const int32_t *>(d_in + in_off), d_in + in_pool, (int64_t)n, h->length,
+    const StageSegment down[3] = {{intervals, 2 * n * sizeof(int32_t)}, {offsets, (n + 1) * sizeof(int32_t)}, {motifs, pool}};
+    const uint8_t *d_in[3];
+    if ((rc = stage_down(h, down, 3, d_in))) return rc;
+    uint8_t *d_out = buf.d_class.p;
+    HIP_TRY(rb::launch_classes(reinterpret_cast<const int32_t *>(d_in[0]), reinterpret_cast<const int32_t *>(d_in[1]), d_in[2], (int64_t)n, h->length,
                                buf.d_class_work.p, reinterpret_cast<rb::ClassHeader *>(d_out), reinterpret_cast<RibbitMotifClass *>(d_out + HEADER_BYTES),
-                               d_out + out_strands, d_out + out_classes, buf.d_class_scratch.p, buf.d_class_scratch.cap, h->stream));
+                               d_out + out_strands, d_out + out_classes, buf.d_scratch.p, buf.d_scratch.cap, h->stream));
     HIP_TRY(hipMemcpyAsync(buf.h_class.p, d_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     rb::ClassHeader header;
@@ -122,14 +111,8 @@ int host_record_classes_impl(int64_t length, const int32_t *intervals, size_t n,
     if ((rc = check_class_args(intervals, n, motifs, offsets, classes, strands, groups, n_groups, 0))) return rc;
     if (length < 0 || length > (int64_t)INT32_MAX) return fail(RIBBIT_E_ARG, "a record of %lld bases", (long long)length);
     const size_t pool = n ? (size_t)offsets[n] : 0;
-    std::unique_ptr<char[], FreeDeleter> cls, str;
-    {
-        char *a = nullptr, *b = nullptr;
-        if ((rc = hand_out<char>(nullptr, pool, true, &a))) return rc;
-        cls.reset(a);
-        if ((rc = hand_out<char>(nullptr, n, true, &b))) return rc;
-        str.reset(b);
-    }
+    Handed<char> cls, str;
+    if ((rc = hand_out<char>(nullptr, pool, true, cls)) || (rc = hand_out<char>(nullptr, n, true, str))) return rc;
     rb::over_pieces(n, row_threads(n), [&](size_t from, size_t to, unsigned) {
         char rc_text[MAX_MOTIF];
         for (size_t i = from; i < to; ++i) {
@@ -177,120 +160,39 @@ int host_record_classes_impl(int64_t length, const int32_t *intervals, size_t n,
 }
 
 // ---- the motifs of a BED text
-// the motifs of the whole lines in [p, end) appended to pool, their lengths to lens; nullptr, or the first line that is not a row
-// with a motif
-const char *parse_motifs(const char *p, const char *end, std::string &pool, std::vector<int32_t> &lens) {
-    const char *tab[10];      // the last ten tabs of the line, in a ring (as api_mask.cpp reads the rows)
-    while (p < end) {
-        const char *eol = static_cast<const char *>(std::memchr(p, '\n', (size_t)(end - p)));
-        if (!eol) eol = end;
-        size_t nt = 0;
-        for (const char *q = p; (q = static_cast<const char *>(std::memchr(q, '\t', (size_t)(eol - q)))) != nullptr; ++q) tab[nt++ % 10] = q;
-        if (nt < 10) return p;
-        const char *from = tab[(nt + 2) % 10] + 1, *to = tab[(nt + 3) % 10];      // the eighth column from the end
-        if (to <= from || to - from > MAX_MOTIF || !std::all_of(from, to, is_base)) return p;
-        pool.append(from, (size_t)(to - from));
-        lens.push_back((int32_t)(to - from));
-        p = eol + 1;
-    }
-    return nullptr;
-}
-
 int bed_motifs_impl(const char *text, size_t len, char **pool, int32_t **offsets, size_t *n) {
     if (!pool || !offsets || !n || (!text && len > 0)) return fail(RIBBIT_E_ARG, "null argument");
-    const size_t parts = bed_text_parts(len);      // (pieces of whole lines, as ribbit_bed_intervals cuts them)
-    std::vector<const char *> cut(parts + 1, text + len);
-    cut[0] = text;
-    for (size_t k = 1; k < parts; ++k) {
-        const char *at = std::max(cut[k - 1], text + len * k / parts);
-        const char *nl = at > text ? static_cast<const char *>(std::memchr(at - 1, '\n', (size_t)(text + len - (at - 1)))) : at - 1;
-        cut[k] = nl ? nl + 1 : text + len;
-    }
-    std::vector<std::string> piece(parts);
-    std::vector<std::vector<int32_t>> lens(parts);
-    std::vector<const char *> bad(parts, nullptr);
-    std::vector<char> oom(parts, 0);
-    rb::on_threads((unsigned)parts, [&](unsigned k) {
-        try { bad[k] = parse_motifs(cut[k], cut[k + 1], piece[k], lens[k]); } catch (const std::bad_alloc &) { oom[k] = 1; }
-    });
-    size_t bytes = 0, rows = 0;
-    for (size_t k = 0; k < parts; ++k) {
-        if (oom[k]) return fail(RIBBIT_E_NOMEM, "out of host memory reading the motifs");
-        if (bad[k])
-            return fail(RIBBIT_E_ARG, "BED text at byte %zu is not a row of 11 tab-separated columns whose motif is 1 .. %d bytes over ACGT", (size_t)(bad[k] - text), (int)MAX_MOTIF);
-        bytes += piece[k].size();
-        rows += lens[k].size();
-    }
-    if (bytes > MAX_POOL || rows > MAX_ROWS) return fail(RIBBIT_E_ARG, "%zu rows with %zu bytes of motifs", rows, bytes);
-    std::unique_ptr<char[], FreeDeleter> out;
-    {
-        char *a = nullptr;
-        int rc;
-        if ((rc = hand_out<char>(nullptr, bytes, true, &a))) return rc;
-        out.reset(a);
-        if ((rc = hand_out<int32_t>(nullptr, rows + 1, false, offsets))) return rc;
-    }
-    size_t at = 0, row = 0;
-    for (size_t k = 0; k < parts; ++k) {
-        std::memcpy(out.get() + at, piece[k].data(), piece[k].size());
-        for (const int32_t l : lens[k]) {
-            (*offsets)[row++] = (int32_t)at;
-            at += (size_t)l;
-        }
-    }
-    (*offsets)[rows] = (int32_t)at;
-    *pool = out.release();
-    *n = rows;
-    return RIBBIT_OK;
+    return bed_gather(text, len, "motifs", [](const BedRow &row) {
+        const BedField m = row.motif;
+        return m.to > m.from && m.to - m.from <= MAX_MOTIF && std::all_of(m.from, m.to, is_base) ? m : BedField{};
+    }, [](size_t at) {
+        return fail(RIBBIT_E_ARG, "BED text at byte %zu is not a row of 11 tab-separated columns whose motif is 1 .. %d bytes over ACGT", at, (int)MAX_MOTIF);
+    }, pool, offsets, n);
 }
 
 // ---- the two outputs as text
-int copy_pieces(const std::vector<std::string> &piece, char **text, size_t *len) {
-    size_t total = 0;
-    for (const std::string &s : piece) total += s.size();
-    int rc;
-    if ((rc = hand_out<char>(nullptr, total, true, text))) return rc;
-    size_t at = 0;
-    for (const std::string &s : piece) {
-        std::memcpy(*text + at, s.data(), s.size());
-        at += s.size();
-    }
-    *len = total;
-    return RIBBIT_OK;
-}
-
 int bed_class_text_impl(const char *bed, size_t bed_len, const char *classes, const int32_t *offsets, const char *strands, size_t n, char **text, size_t *len) {
     if (!text || !len || (!bed && bed_len > 0) || ((!classes || !offsets || !strands) && n > 0)) return fail(RIBBIT_E_ARG, "null argument");
     const size_t parts = bed_text_parts(bed_len);
-    std::vector<size_t> line;
+    BedLines lines;
     int rc;
-    if ((rc = bed_line_starts(bed, bed_len, parts, line))) return rc;
-    if (line.size() - 1 != n) return fail(RIBBIT_E_ARG, "the BED text has %zu lines, not the %zu of the rows", line.size() - 1, n);
+    if ((rc = lines.find(bed, bed_len, parts))) return rc;
+    if (lines.count() != n) return fail(RIBBIT_E_ARG, "the BED text has %zu lines, not the %zu of the rows", lines.count(), n);
     for (size_t i = 0; i < n; ++i)
         if (offsets[i] < 0 || offsets[i + 1] < offsets[i]) return fail(RIBBIT_E_ARG, "row %zu: the classes' offsets do not ascend", i);
     // piece k writes lines [n k / parts, n (k + 1) / parts): every line grows by two tabs, its class and its strand
-    std::vector<std::string> piece(parts);
-    std::vector<char> oom(parts, 0);
-    rb::on_threads((unsigned)parts, [&](unsigned k) {
-        try {
-            std::string &out = piece[k];
-            const size_t from = n * k / parts, to = n * (k + 1) / parts;
-            out.reserve(line[to] - line[from] + (size_t)(offsets[to] - offsets[from]) + 4 * (to - from));
-            for (size_t i = from; i < to; ++i) {
-                const char *p = bed + line[i], *eol = bed + line[i + 1];
-                if (eol > p && eol[-1] == '\n') --eol;
-                out.append(p, (size_t)(eol - p));
-                out += '\t';
-                out.append(classes + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
-                out += '\t';
-                out += strands[i];
-                out += '\n';
-            }
-        } catch (const std::bad_alloc &) { oom[k] = 1; }
+    return write_pieces(parts, "the rows' classes", text, len, [&](size_t k, std::string &out) {
+        const size_t from = n * k / parts, to = n * (k + 1) / parts;
+        out.reserve(lines.start[to] - lines.start[from] + (size_t)(offsets[to] - offsets[from]) + 4 * (to - from));
+        for (size_t i = from; i < to; ++i) {
+            put_field(out, lines[i]);
+            out += '\t';
+            out.append(classes + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
+            out += '\t';
+            out += strands[i];
+            out += '\n';
+        }
     });
-    for (size_t k = 0; k < parts; ++k)
-        if (oom[k]) return fail(RIBBIT_E_NOMEM, "out of host memory writing the rows' classes");
-    return copy_pieces(piece, text, len);
 }
 
 int class_summary_text_impl(const char *name, const int32_t *intervals, size_t n, const char *classes, const int32_t *offsets, const RibbitMotifClass *groups,
@@ -299,7 +201,6 @@ int class_summary_text_impl(const char *name, const int32_t *intervals, size_t n
     const size_t name_len = std::strlen(name);
     std::vector<std::string> piece(1);
     std::string &out = piece[0];
-    char num[24];
     for (size_t g = 0; g < n_groups; ++g) {
         const RibbitMotifClass &c = groups[g];
         if (c.first_row < 0 || (size_t)c.first_row >= n || c.longest_row < 0 || (size_t)c.longest_row >= n)
@@ -311,11 +212,11 @@ int class_summary_text_impl(const char *name, const int32_t *intervals, size_t n
         out.append(classes + from, (size_t)k);
         for (const int64_t v : {(int64_t)c.length, (int64_t)c.rows, c.bases, (int64_t)intervals[2 * (size_t)c.longest_row], (int64_t)intervals[2 * (size_t)c.longest_row + 1]}) {
             out += '\t';
-            out.append(num, (size_t)(std::to_chars(num, num + sizeof num, v).ptr - num));
+            put_number(out, v);
         }
         out += '\n';
     }
-    return copy_pieces(piece, text, len);
+    return join_text(piece, text, len);
 }
 
 }  // namespace

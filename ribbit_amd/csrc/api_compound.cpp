@@ -1,10 +1,8 @@
 // api_compound.cpp -- the rows of a record chained into compound loci (compound.hip); see api_internal.h for the map of the files
-// behind include/ribbit_hip.h.  The GPU form stages the rows and their labels itself (it reads no coverage bitmap), runs on the
+// behind include/ribbit_hip.h.  The GPU form stages the rows and their labels through stage_down (it reads no coverage bitmap), runs on the
 // handle's stream and keeps nothing between calls; the host twin is written from the contract, one sort and one sweep; the
 // labels of the rows' motif classes and the chains' text need no GPU either.
-#include "api_internal.h"
-
-#include <charconv>
+#include "bed_text.h"
 
 namespace {
 
@@ -36,23 +34,21 @@ int record_compounds_impl(RibbitHandle *h, const int32_t *intervals, const int32
     if ((rc = bind_device(h))) return rc;
     const size_t out_members = TOTALS_BYTES + n * sizeof(RibbitCompound), out_bytes = out_members + n * sizeof(int32_t);
     RibbitHandle::RowBufs &buf = h->rows;
-    if ((rc = buf.h_cmp_in.ensure(3 * n, true))) return rc;
-    if ((rc = buf.d_cmp_in.ensure(3 * n, true))) return rc;
     if ((rc = buf.d_cmp_keys.ensure(3 * n, true))) return rc;
     if ((rc = buf.d_cmp_work.ensure(3 * n + 1, true))) return rc;
     if ((rc = buf.d_cmp_sums.ensure(n, true))) return rc;
     if ((rc = buf.d_cmp_flags.ensure(n, true))) return rc;
-    if ((rc = buf.d_cmp_scratch.ensure(rb::compound_scratch_bytes((int64_t)n, length), true))) return rc;
+    if ((rc = buf.d_scratch.ensure(rb::compound_scratch_bytes((int64_t)n, length), true))) return rc;
     if ((rc = buf.d_cmp.ensure(out_bytes, true))) return rc;
     if ((rc = buf.h_cmp.ensure(out_bytes, true))) return rc;
-    // (the staging buffer may still be the source of the last call's copy: that call ended in a synchronise)
-    std::memcpy(buf.h_cmp_in.p, intervals, 2 * n * sizeof(int32_t));
-    std::memcpy(buf.h_cmp_in.p + 2 * n, labels, n * sizeof(int32_t));
-    HIP_TRY(hipMemcpyAsync(buf.d_cmp_in.p, buf.h_cmp_in.p, 3 * n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    const StageSegment down[2] = {{intervals, 2 * n * sizeof(int32_t)}, {labels, n * sizeof(int32_t)}};
+    const uint8_t *d_in[2];
+    if ((rc = stage_down(h, down, 2, d_in))) return rc;
     uint8_t *d_out = buf.d_cmp.p, *up = buf.h_cmp.p;
-    HIP_TRY(rb::launch_compounds(buf.d_cmp_in.p, buf.d_cmp_in.p + 2 * n, (int64_t)n, length, gap, buf.d_cmp_keys.p, buf.d_cmp_work.p, buf.d_cmp_sums.p,
-                                 buf.d_cmp_flags.p, reinterpret_cast<rb::CompoundTotals *>(d_out), reinterpret_cast<int32_t *>(d_out + out_members),
-                                 reinterpret_cast<RibbitCompound *>(d_out + TOTALS_BYTES), buf.d_cmp_scratch.p, buf.d_cmp_scratch.cap, h->stream));
+    HIP_TRY(rb::launch_compounds(reinterpret_cast<const int32_t *>(d_in[0]), reinterpret_cast<const int32_t *>(d_in[1]), (int64_t)n, length, gap, buf.d_cmp_keys.p,
+                                 buf.d_cmp_work.p, buf.d_cmp_sums.p, buf.d_cmp_flags.p, reinterpret_cast<rb::CompoundTotals *>(d_out),
+                                 reinterpret_cast<int32_t *>(d_out + out_members), reinterpret_cast<RibbitCompound *>(d_out + TOTALS_BYTES), buf.d_scratch.p,
+                                 buf.d_scratch.cap, h->stream));
     // the two counts come up first; then the chains and the members there are, not the room they have
     HIP_TRY(hipMemcpyAsync(up, d_out, TOTALS_BYTES, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -80,14 +76,9 @@ int host_record_compounds_impl(int64_t length, const int32_t *intervals, const i
     int rc;
     if ((rc = check_compound_args(intervals, labels, n, gap, compounds, n_compounds, members, n_members))) return rc;
     if (length < 0 || length > (int64_t)INT32_MAX) return fail(RIBBIT_E_ARG, "a record of %lld bases", (long long)length);
-    struct Row { int64_t s, e; int32_t index; };
-    std::vector<Row> order;
-    order.reserve(n);
-    for (size_t i = 0; i < n; ++i) {
-        const int64_t s = std::max<int64_t>(intervals[2 * i], 0), e = std::min<int64_t>(intervals[2 * i + 1], length);
-        if (s < e) order.push_back(Row{s, e, (int32_t)i});
-    }
-    std::sort(order.begin(), order.end(), [](const Row &a, const Row &b) { return a.s != b.s ? a.s < b.s : a.e != b.e ? a.e < b.e : a.index < b.index; });
+    using Row = ClippedRow;
+    const std::vector<Row> order =
+        clipped_sorted_rows(length, intervals, n, [](const Row &a, const Row &b) { return a.s != b.s ? a.s < b.s : a.e != b.e ? a.e < b.e : a.index < b.index; });
     std::vector<RibbitCompound> chains;
     std::vector<int32_t> in_order(order.size()), seen;      // seen: the open chain's labels
     auto close_chain = [&]() {
@@ -99,7 +90,7 @@ int host_record_compounds_impl(int64_t length, const int32_t *intervals, const i
     int64_t reach = 0;
     for (size_t k = 0; k < order.size(); ++k) {
         const Row &row = order[k];
-        in_order[k] = row.index;
+        in_order[k] = (int32_t)row.index;
         if (k == 0 || row.s - reach > (int64_t)gap) {
             close_chain();
             chains.push_back(RibbitCompound{0, (int32_t)row.s, 0, 0, 0, 0, 0, (int32_t)k, 0});
@@ -117,13 +108,8 @@ int host_record_compounds_impl(int64_t length, const int32_t *intervals, const i
         seen.push_back(labels[row.index]);
     }
     close_chain();
-    std::unique_ptr<RibbitCompound, FreeDeleter> out;
-    {
-        RibbitCompound *a = nullptr;
-        if ((rc = hand_out(chains.data(), chains.size(), false, &a))) return rc;
-        out.reset(a);
-    }
-    if ((rc = hand_out(in_order.data(), in_order.size(), false, members))) return rc;
+    Handed<RibbitCompound> out;
+    if ((rc = hand_out(chains.data(), chains.size(), false, out)) || (rc = hand_out(in_order.data(), in_order.size(), false, members))) return rc;
     *compounds = out.release();
     *n_compounds = chains.size();
     *n_members = in_order.size();
@@ -146,13 +132,9 @@ int class_labels_impl(const char *classes, const int32_t *offsets, size_t n, con
     auto order = [&](int32_t k, const char *text, const RibbitMotifClass &c) {      // < 0, 0, > 0: the class (k, text) against the group's
         return k != c.length ? (k < c.length ? -1 : 1) : std::memcmp(text, classes + offsets[c.first_row], (size_t)k);
     };
-    std::unique_ptr<int32_t, FreeDeleter> out;
-    {
-        int32_t *a = nullptr;
-        int rc;
-        if ((rc = hand_out<int32_t>(nullptr, n, false, &a))) return rc;
-        out.reset(a);
-    }
+    Handed<int32_t> out;
+    int rc;
+    if ((rc = hand_out<int32_t>(nullptr, n, false, out))) return rc;
     for (size_t i = 0; i < n; ++i) {
         const int32_t k = offsets[i + 1] - offsets[i];
         const char *text = classes + offsets[i];
@@ -162,7 +144,7 @@ int class_labels_impl(const char *classes, const int32_t *offsets, size_t n, con
             if (order(k, text, groups[mid]) > 0) lo = mid + 1; else hi = mid;
         }
         if (lo == n_groups || order(k, text, groups[lo]) != 0) return fail(RIBBIT_E_ARG, "row %zu: its class is the class of no group", i);
-        out.get()[i] = (int32_t)lo;
+        out[i] = (int32_t)lo;
     }
     *labels = out.release();
     return RIBBIT_OK;
@@ -176,93 +158,67 @@ int compound_text_impl(const char *name, const char *bed, size_t bed_len, int64_
     if (length < 0 || length > (int64_t)INT32_MAX) return fail(RIBBIT_E_ARG, "a record of %lld bases", (long long)length);
     // the BED text's line starts are found in pieces, and the chains' lines are written in as many pieces
     const size_t parts = n_compounds ? bed_text_parts(bed_len) : 1;
-    std::vector<size_t> line{0};       // line i is [line[i], line[i + 1]); a last line without its newline counts
+    BedLines lines;
     int rc;
-    if (n_compounds && (rc = bed_line_starts(bed, bed_len, parts, line))) return rc;
-    const size_t n_lines = line.size() - 1, name_len = std::strlen(name);
+    if (n_compounds && (rc = lines.find(bed, bed_len, parts))) return rc;
+    const size_t n_lines = lines.count(), name_len = std::strlen(name);
     const size_t out_parts = std::max<size_t>(1, std::min<size_t>(parts, n_compounds >> 12));
-    std::vector<std::string> piece(out_parts);
-    enum : int { FINE = 0, NOMEM, RANGE, MEMBER, EMPTY, LINE };
-    struct Bad { int why = FINE; size_t chain = 0, at = 0; };
-    std::vector<Bad> bad(out_parts);
-    rb::on_threads((unsigned)out_parts, [&](unsigned t) {
-        try {
-            char num[24];
-            std::string &out = piece[t];
-            auto put = [&](int64_t v) { out.append(num, (size_t)(std::to_chars(num, num + sizeof num, v).ptr - num)); };
-            std::string structure;
-            for (size_t c = n_compounds * t / out_parts; c < n_compounds * (t + 1) / out_parts; ++c) {
-                const RibbitCompound &k = compounds[c];
-                if (k.first < 0 || k.rows < 1 || (size_t)k.first + (size_t)k.rows > n_members) { bad[t] = Bad{RANGE, c, 0}; return; }
-                structure.clear();
-                int64_t reach = 0;
-                for (size_t j = (size_t)k.first; j < (size_t)k.first + (size_t)k.rows; ++j) {
-                    const int32_t row = members[j];
-                    if (row < 0 || (size_t)row >= n || (size_t)row >= n_lines) { bad[t] = Bad{MEMBER, c, j}; return; }
-                    const int64_t s = std::max<int64_t>(intervals[2 * (size_t)row], 0), e = std::min<int64_t>(intervals[2 * (size_t)row + 1], length);
-                    if (s >= e) { bad[t] = Bad{EMPTY, c, j}; return; }
-                    const char *p = bed + line[(size_t)row], *eol = bed + line[(size_t)row + 1];
-                    if (eol > p && eol[-1] == '\n') --eol;
-                    const char *tab[10];      // the last ten tabs of the line from the right: column j from the end lies between tab[j - 1] and tab[j - 2]
-                    int tabs = 0;
-                    for (const char *q = eol; q > p && tabs < 10;)
-                        if (*--q == '\t') tab[tabs++] = q;
-                    if (tabs < 10) { bad[t] = Bad{LINE, c, j}; return; }
-                    if (j > (size_t)k.first) {
-                        const int64_t d = s - reach;
-                        if (d) {
-                            char sep[24];
-                            structure += d > 0 ? 'n' : 'o';
-                            structure.append(sep, (size_t)(std::to_chars(sep, sep + sizeof sep, d > 0 ? d : -d).ptr - sep));
-                        }
+    enum : int { FINE = 0, RANGE, MEMBER, EMPTY, LINE };      // a refusal's why; a: the chain, b: its member's position
+    return write_pieces(out_parts, "the chains", text, len, [&](size_t t, std::string &out) {
+        std::string structure;
+        for (size_t c = n_compounds * t / out_parts; c < n_compounds * (t + 1) / out_parts; ++c) {
+            const RibbitCompound &k = compounds[c];
+            if (k.first < 0 || k.rows < 1 || (size_t)k.first + (size_t)k.rows > n_members) return PieceRefusal{RANGE, c, 0};
+            structure.clear();
+            int64_t reach = 0;
+            for (size_t j = (size_t)k.first; j < (size_t)k.first + (size_t)k.rows; ++j) {
+                const int32_t row = members[j];
+                if (row < 0 || (size_t)row >= n || (size_t)row >= n_lines) return PieceRefusal{MEMBER, c, j};
+                const int64_t s = std::max<int64_t>(intervals[2 * (size_t)row], 0), e = std::min<int64_t>(intervals[2 * (size_t)row + 1], length);
+                if (s >= e) return PieceRefusal{EMPTY, c, j};
+                const BedField line = lines[(size_t)row];
+                const BedRow fields = bed_row(line.from, line.to);
+                if (!fields.ok) return PieceRefusal{LINE, c, j};
+                if (j > (size_t)k.first) {
+                    const int64_t d = s - reach;
+                    if (d) {
+                        structure += d > 0 ? 'n' : 'o';
+                        put_number(structure, d > 0 ? d : -d);
                     }
-                    structure += '(';
-                    structure.append(tab[7] + 1, (size_t)(tab[6] - tab[7] - 1));      // the motif: the eighth column from the end
-                    structure += ')';
-                    structure.append(tab[4] + 1, (size_t)(tab[3] - tab[4] - 1));      // the units: the fifth
-                    reach = j == (size_t)k.first ? e : std::max(reach, e);
                 }
-                out.append(name, name_len);
-                out += '\t';
-                put(k.start);
-                out += '\t';
-                put(k.end);
-                out += '\t';
-                out += k.rows == 1 ? 'p' : k.classes > 1 ? 'c' : 'i';
-                if (k.overlaps > 0) out += '*';
-                for (const int64_t v : {(int64_t)k.rows, (int64_t)k.classes, k.bases}) {
-                    out += '\t';
-                    put(v);
-                }
-                out += '\t';
-                out += structure;
-                out += '\n';
+                structure += '(';
+                put_field(structure, fields.motif);
+                structure += ')';
+                put_field(structure, fields.units);
+                reach = j == (size_t)k.first ? e : std::max(reach, e);
             }
-        } catch (const std::bad_alloc &) { bad[t].why = NOMEM; }
-    });
-    size_t total = 0;
-    for (size_t t = 0; t < out_parts; ++t) {
-        const Bad &b = bad[t];
-        switch (b.why) {
-            case FINE: break;
-            case NOMEM: return fail(RIBBIT_E_NOMEM, "out of host memory writing the chains");
-            case RANGE:
-                return fail(RIBBIT_E_ARG, "chain %zu: members %d .. %lld of %zu", b.chain, (int)compounds[b.chain].first,
-                            (long long)compounds[b.chain].first + compounds[b.chain].rows, n_members);
-            case MEMBER: return fail(RIBBIT_E_ARG, "chain %zu: member %d is no row of %zu with a line of the BED text (%zu lines)", b.chain, (int)members[b.at], n, n_lines);
-            case EMPTY: return fail(RIBBIT_E_ARG, "chain %zu: member %d is an empty row", b.chain, (int)members[b.at]);
-            default: return fail(RIBBIT_E_ARG, "chain %zu: line %d of the BED text is not a row of 11 tab-separated columns", b.chain, (int)members[b.at]);
+            out.append(name, name_len);
+            out += '\t';
+            put_number(out, k.start);
+            out += '\t';
+            put_number(out, k.end);
+            out += '\t';
+            out += k.rows == 1 ? 'p' : k.classes > 1 ? 'c' : 'i';
+            if (k.overlaps > 0) out += '*';
+            for (const int64_t v : {(int64_t)k.rows, (int64_t)k.classes, k.bases}) {
+                out += '\t';
+                put_number(out, v);
+            }
+            out += '\t';
+            out += structure;
+            out += '\n';
         }
-        total += piece[t].size();
-    }
-    if ((rc = hand_out<char>(nullptr, total, true, text))) return rc;
-    size_t at = 0;
-    for (const std::string &s : piece) {
-        std::memcpy(*text + at, s.data(), s.size());
-        at += s.size();
-    }
-    *len = total;
-    return RIBBIT_OK;
+        return PieceRefusal{};
+    }, [&](const PieceRefusal &b) {
+        switch (b.why) {
+            case RANGE:
+                return fail(RIBBIT_E_ARG, "chain %zu: members %d .. %lld of %zu", b.a, (int)compounds[b.a].first, (long long)compounds[b.a].first + compounds[b.a].rows,
+                            n_members);
+            case MEMBER: return fail(RIBBIT_E_ARG, "chain %zu: member %d is no row of %zu with a line of the BED text (%zu lines)", b.a, (int)members[b.b], n, n_lines);
+            case EMPTY: return fail(RIBBIT_E_ARG, "chain %zu: member %d is an empty row", b.a, (int)members[b.b]);
+            default: return fail(RIBBIT_E_ARG, "chain %zu: line %d of the BED text is not a row of 11 tab-separated columns", b.a, (int)members[b.b]);
+        }
+    });
 }
 
 }  // namespace

@@ -17,8 +17,10 @@
 //   api_classes.cpp     the rows of a record grouped by canonical motif class (classes.hip), its host twin, the motifs of a BED text, both texts
 //   api_compound.cpp    the rows of a record chained into compound loci (compound.hip), its host twin, the classes as labels, the chains' text
 //   api_interruptions.cpp  every row's CIGAR decoded into interruptions and the pure stretch (interruptions.hip), its host twin, the CIGARs of a BED text, both texts
-// The last eight are the row outputs: their buffers are the handle's RowBufs `rows`, and what their host sides share is below
-// (hand_out, clipped_sorted_rows, bed_text_parts, bed_line_starts).
+// The last eight are the row outputs: their buffers are the handle's RowBufs `rows`, the last four stage their inputs through
+// stage_down, what their host sides share is below (hand_out, clipped_sorted_rows), and the BED text they read and write (the row
+// format, the reader in pieces, the writer in pieces) is
+//   bed_text.h          a row's named fields, bed_read / bed_gather, BedLines, write_pieces / join_text, put_number
 // Host threads: every team of them, here and in refine.cpp, parallel_merge.cpp and host_planes.cpp, is started by rb::on_threads /
 // rb::over_pieces of host_threads.h (part 0 on the caller, a thread that cannot start leaves its part to the caller, all joined, the
 // first exception of any part rethrown on the caller: it then meets guarded() below); the thread count rule (the handle's, else
@@ -204,41 +206,33 @@ int hand_out(const T *src, size_t n, bool terminate, T **out) {
     *out = mem;
     return RIBBIT_OK;
 }
+// ... owned here until it is released to the caller (an entry point that hands out several and fails half way frees the first)
+template <typename T>
+using Handed = std::unique_ptr<T[], FreeDeleter>;
+template <typename T>
+int hand_out(const T *src, size_t n, bool terminate, Handed<T> &out) {
+    T *mem = nullptr;
+    const int rc = hand_out(src, n, terminate, &mem);
+    out.reset(mem);
+    return rc;
+}
 
-// the rows clipped to [0, length), the empty ones dropped, sorted by start (among equals by index): what the host twins sweep
+// the rows clipped to [0, length), the empty ones dropped, sorted by `less`: what the host twins sweep
 struct ClippedRow { int64_t s, e; size_t index; };
-inline std::vector<ClippedRow> clipped_sorted_rows(int64_t length, const int32_t *intervals, size_t n) {
+template <typename Less>
+std::vector<ClippedRow> clipped_sorted_rows(int64_t length, const int32_t *intervals, size_t n, Less less) {
     std::vector<ClippedRow> rows;
     rows.reserve(n);
     for (size_t i = 0; i < n; ++i) {
         const int64_t s = std::max<int64_t>(intervals[2 * i], 0), e = std::min<int64_t>(intervals[2 * i + 1], length);
         if (s < e) rows.push_back(ClippedRow{s, e, i});
     }
-    std::sort(rows.begin(), rows.end(), [](const ClippedRow &a, const ClippedRow &b) { return a.s != b.s ? a.s < b.s : a.index < b.index; });
+    std::sort(rows.begin(), rows.end(), less);
     return rows;
 }
-
-// a chromosome's BED is 150-200 MB of text: it is walked in pieces, one thread per piece of at least 4 MB
-inline size_t bed_text_parts(size_t len) { return std::max<size_t>(1, std::min<size_t>(std::min(rb::host_thread_count(0), 16u), len >> 22)); }
-
-// where the lines of a BED text start: line i is [line[i], line[i + 1]), its newline included; a last line without its newline
-// counts.  The newlines are found in `parts` pieces, one thread per piece.
-inline int bed_line_starts(const char *bed, size_t bed_len, size_t parts, std::vector<size_t> &line) {
-    std::vector<std::vector<size_t>> starts(parts);      // per piece: the offsets just behind its newlines
-    std::vector<char> oom(parts, 0);
-    rb::on_threads((unsigned)parts, [&](unsigned k) {
-        try {
-            const char *p = bed + bed_len * k / parts, *end = bed + bed_len * (k + 1) / parts;
-            while (p < end && (p = static_cast<const char *>(std::memchr(p, '\n', (size_t)(end - p)))) != nullptr) starts[k].push_back((size_t)(++p - bed));
-        } catch (const std::bad_alloc &) { oom[k] = 1; }
-    });
-    line.assign(1, 0);
-    for (size_t k = 0; k < parts; ++k) {
-        if (oom[k]) return fail(RIBBIT_E_NOMEM, "out of host memory reading BED rows");
-        line.insert(line.end(), starts[k].begin(), starts[k].end());
-    }
-    if (line.back() != bed_len) line.push_back(bed_len);
-    return RIBBIT_OK;
+// ... by start (among equals by index)
+inline std::vector<ClippedRow> clipped_sorted_rows(int64_t length, const int32_t *intervals, size_t n) {
+    return clipped_sorted_rows(length, intervals, n, [](const ClippedRow &a, const ClippedRow &b) { return a.s != b.s ? a.s < b.s : a.index < b.index; });
 }
 
 }  // namespace rbapi
@@ -400,6 +394,11 @@ struct RibbitHandle {
     // the row outputs of the loaded record (api_mask.cpp, api_repeats.cpp, api_loci.cpp, api_overlap.cpp, api_best.cpp, api_classes.cpp, api_compound.cpp,
     // api_interruptions.cpp)
     struct RowBufs {
+        // shared by all of them, because every row output ends in a synchronise of the handle's stream and keeps none of the three
+        // between calls: the inputs on their way down and on the device (stage_down lays them out), and the temporary storage of the
+        // rocPRIM scans, sorts, selects and reductions, which only work enqueued on the handle's stream within one call touches
+        PinnedBuf<uint8_t> h_in;
+        DevBuf<uint8_t> d_in, d_scratch;
         // the masked body of the loaded record (api_mask.cpp): coverage bitmap, intervals, the text on the device and on its way up
         DevBuf<uint32_t> d_mask_bits;
         DevBuf<int32_t> d_mask_iv;
@@ -407,11 +406,10 @@ struct RibbitHandle {
         PinnedBuf<int32_t> h_mask_iv;
         PinnedBuf<char> h_mask_text;
         // the repeat sequences of the loaded record (api_repeats.cpp): the rows with the name behind them, their entry offsets, the
-        // first row of every output span, the scan's scratch, k and the byte count on their way up, the text of one batch
+        // first row of every output span, k and the byte count on their way up, the text of one batch
         DevBuf<int32_t> d_rep_iv;
         DevBuf<int64_t> d_rep_off;
         DevBuf<int32_t> d_rep_span_row;
-        DevBuf<uint8_t> d_rep_scratch;
         DevBuf<int64_t> d_rep_pick;
         DevBuf<uint8_t> d_rep_text;
         PinnedBuf<int32_t> h_rep_iv;
@@ -423,55 +421,46 @@ struct RibbitHandle {
         DevBuf<uint64_t> d_loci_off, d_loci_u64;
         DevBuf<int32_t> d_loci_i32;
         DevBuf<RibbitLocus> d_loci;
-        DevBuf<uint8_t> d_loci_scratch;
         PinnedBuf<uint64_t> h_loci_count;
         PinnedBuf<RibbitLocus> h_loci;
         DevBuf<int32_t> d_density;
         PinnedBuf<int32_t> h_density;
         // the rows against a second set of intervals (api_overlap.cpp): those intervals, their coverage bitmap (the rows' is
         // d_mask_bits), the blocks' counts with their ranks behind them, the intervals' starts | ends | sorted starts | sorted ends,
-        // the scan's and the sorts' scratch, and the result on the device and on its way up: the totals, then (others, bases) per row
+        // and the result on the device and on its way up: the totals, then (others, bases) per row
         DevBuf<int32_t> d_overlap_iv;
         PinnedBuf<int32_t> h_overlap_iv;
         DevBuf<uint32_t> d_overlap_bits, d_overlap_keys;
         DevBuf<uint64_t> d_overlap_ranks;
-        DevBuf<uint8_t> d_overlap_scratch;
         DevBuf<int32_t> d_overlap;
         PinnedBuf<int32_t> h_overlap;
-        // the best non-overlapping rows (api_best.cpp): the rows on their way down and on the device, their keys | the keys
-        // sorted, the row indices | the indices in sorted order | the suffix minimum, the segment heads | the take flags, the sort's,
-        // the scan's and the select's scratch, and the result on the device and on its way up: the totals, then the chosen indices
-        PinnedBuf<int32_t> h_best_iv;
-        DevBuf<int32_t> d_best_iv, d_best_work;
+        // the best non-overlapping rows (api_best.cpp): the rows' keys | the keys sorted, the row indices | the indices in sorted
+        // order | the suffix minimum, the segment heads | the take flags, and the result on the device and on its way up: the
+        // totals, then the chosen indices
+        DevBuf<int32_t> d_best_work;
         DevBuf<uint64_t> d_best_keys;
-        DevBuf<uint8_t> d_best_flags, d_best_scratch;
+        DevBuf<uint8_t> d_best_flags;
         DevBuf<int32_t> d_best;
         PinnedBuf<int32_t> h_best;
-        // the rows by motif class (api_classes.cpp): the rows | the offsets | the motifs on their way down and on the device, the sort
-        // items | the items sorted | the groups' aggregates | head flags | group ids | the long rows' list, the sort's, the scan's and
-        // the reduction's scratch, and the result on the device and on its way up: the header, the groups, the strands, the classes
-        PinnedBuf<uint8_t> h_class_in;
-        DevBuf<uint8_t> d_class_in, d_class_scratch;
+        // the rows by motif class (api_classes.cpp): the sort items | the items sorted | the groups' aggregates | head flags | group
+        // ids | the long rows' list, and the result on the device and on its way up: the header, the groups, the strands, the classes
         DevBuf<uint64_t> d_class_work;
         DevBuf<uint8_t> d_class;
         PinnedBuf<uint8_t> h_class;
-        // the rows chained into compound loci (api_compound.cpp): the rows | their labels on their way down and on the device, the
-        // keys | the keys sorted | the (chain, label) keys sorted, the indices or chain ids | reach | the chains' first positions, the
-        // prefix sums, the flag bytes, the sorts' and the scans' scratch, and the result on the device and on its way up: the
-        // counts, then the chains, then the members
-        PinnedBuf<int32_t> h_cmp_in;
-        DevBuf<int32_t> d_cmp_in, d_cmp_work;
+        // the rows chained into compound loci (api_compound.cpp): the keys | the keys sorted | the (chain, label) keys sorted, the
+        // indices or chain ids | reach | the chains' first positions, the prefix sums, the flag bytes, and the result on the device
+        // and on its way up: the counts, then the chains, then the members
+        DevBuf<int32_t> d_cmp_work;
         DevBuf<uint64_t> d_cmp_keys;
         DevBuf<rb::CompoundSums> d_cmp_sums;
-        DevBuf<uint8_t> d_cmp_flags, d_cmp_scratch;
+        DevBuf<uint8_t> d_cmp_flags;
         DevBuf<uint8_t> d_cmp;
         PinnedBuf<uint8_t> h_cmp;
-        // the rows' CIGARs decoded (api_interruptions.cpp): the rows | the offsets | the CIGARs on their way down and on the device,
-        // everything that is per op, per run, per interruption or per row (rb::InterruptionLayout), the scans' scratch, the counts on
-        // their way up, the observed bases on the device, and the result on its way up: the rows, the interruptions, the offsets,
-        // the observed bases
-        PinnedBuf<uint8_t> h_int_in, h_int_totals;
-        DevBuf<uint8_t> d_int_in, d_int_work, d_int_scratch, d_int_text;
+        // the rows' CIGARs decoded (api_interruptions.cpp): everything that is per op, per run, per interruption or per row
+        // (rb::InterruptionLayout), the counts on their way up, the observed bases on the device, and the result on its way up: the
+        // rows, the interruptions, the offsets, the observed bases
+        PinnedBuf<uint8_t> h_int_totals;
+        DevBuf<uint8_t> d_int_work, d_int_text;
         PinnedBuf<uint8_t> h_int;
         size_t rep_budget = 0;           // text budget of one batch of repeat sequences in bytes (0: REPEAT_TEXT_BUDGET)
     } rows;
@@ -571,5 +560,12 @@ int run_ssw_paths(RibbitHandle *h, const RibbitAlignJob *jobs, size_t n, const s
 // rows (coverage_is)
 bool coverage_is(const RibbitHandle *h, const int32_t *intervals, size_t n);
 int build_coverage(RibbitHandle *h, const int32_t *intervals, size_t n);
+// api_mask.cpp: a row output's inputs on their way down.  The n_segs segments are copied into rows.h_in one behind the other, each
+// on a 16-byte boundary, the tail zero-filled to 16 bytes past the last segment (the kernels read pools in aligned words, up to one
+// word past their end); one copy to rows.d_in is enqueued on the handle's stream; at[i]: where segment i lies on the device.
+// The caller ends in a synchronise of that stream, so the next call finds both buffers free.
+inline size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
+struct StageSegment { const void *p; size_t bytes; };
+int stage_down(RibbitHandle *h, const StageSegment *segs, size_t n_segs, const uint8_t **at);
 
 }  // namespace rbapi

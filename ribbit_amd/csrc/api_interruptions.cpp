@@ -1,20 +1,16 @@
 // api_interruptions.cpp -- every row's CIGAR decoded into interruptions and the pure stretch (interruptions.hip); see
 // api_internal.h for the map of the files behind include/ribbit_hip.h.  The GPU form stages the rows, the offsets and the CIGARs
-// in one page-locked buffer of its own, reads the bases where the load left them (dev_ascii_src), runs on the handle's stream and
+// through stage_down, reads the bases where the load left them (dev_ascii_src), runs on the handle's stream and
 // keeps nothing between calls; it synchronises twice: once for the counts (which size the observed text and carry what the
 // grammar check found), once for the results.  The host twin is the contract as a plain loop over the rows and their ops, and
 // words every refusal: when the GPU reports an offending byte or row, the twin's walk over the same CIGARs writes the message.
 // The CIGARs of a BED text and the two outputs' texts need no GPU.
-#include "api_internal.h"
-
-#include <charconv>
+#include "bed_text.h"
 
 namespace {
 
-constexpr size_t MAX_ROWS = (size_t)INT32_MAX;      // (the indices are int32)
-constexpr size_t MAX_POOL = (size_t)INT32_MAX;      // (and so are the offsets)
+constexpr size_t MAX_ROWS = BED_MAX_ROWS;
 
-inline size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
 inline bool is_match(char c) { return c == '=' || c == 'M'; }
 inline bool is_op(char c) { return is_match(c) || c == 'X' || c == 'I' || c == 'D'; }
 
@@ -95,24 +91,17 @@ int record_interruptions_impl(RibbitHandle *h, const int32_t *intervals, const i
     if ((rc = bind_device(h))) return rc;
     // down: the rows | the offsets | the CIGARs, each on a 16-byte boundary, the CIGARs zero-filled to one 16 bytes behind theirs
     const size_t pool = (size_t)offsets[n];
-    const size_t in_off = round16(2 * n * sizeof(int32_t)), in_pool = in_off + round16((n + 1) * sizeof(int32_t)), in_bytes = in_pool + round16(pool) + 16;
     const rb::InterruptionLayout at = rb::interruptions_layout((int64_t)n, pool);
     RibbitHandle::RowBufs &buf = h->rows;
-    if ((rc = buf.h_int_in.ensure(in_bytes, true))) return rc;
-    if ((rc = buf.d_int_in.ensure(in_bytes, true))) return rc;
     if ((rc = buf.d_int_work.ensure(at.bytes, true))) return rc;
-    if ((rc = buf.d_int_scratch.ensure(rb::interruptions_scratch_bytes(pool), true))) return rc;
+    if ((rc = buf.d_scratch.ensure(rb::interruptions_scratch_bytes(pool), true))) return rc;
     if ((rc = buf.h_int_totals.ensure(sizeof(rb::InterruptionTotals)))) return rc;
-    // (the staging buffer may still be the source of the last call's copy: that call ended in a synchronise)
-    uint8_t *in = buf.h_int_in.p;
-    std::memcpy(in, intervals, 2 * n * sizeof(int32_t));
-    std::memcpy(in + in_off, offsets, (n + 1) * sizeof(int32_t));
-    if (pool) std::memcpy(in + in_pool, cigars, pool);
-    std::memset(in + in_pool + pool, 0, in_bytes - in_pool - pool);
-    HIP_TRY(hipMemcpyAsync(buf.d_int_in.p, in, in_bytes, hipMemcpyHostToDevice, h->stream));
-    uint8_t *d_in = buf.d_int_in.p, *work = buf.d_int_work.p;
-    HIP_TRY(rb::launch_interruptions(reinterpret_cast<const int32_t *>(d_in), reinterpret_cast<const int32_t *>(d_in + in_off), d_in + in_pool, (int64_t)n, pool,
-                                     h->length, work, at, buf.d_int_scratch.p, buf.d_int_scratch.cap, h->stream));
+    const StageSegment down[3] = {{intervals, 2 * n * sizeof(int32_t)}, {offsets, (n + 1) * sizeof(int32_t)}, {cigars, pool}};
+    const uint8_t *d_in[3];
+    if ((rc = stage_down(h, down, 3, d_in))) return rc;
+    uint8_t *work = buf.d_int_work.p;
+    HIP_TRY(rb::launch_interruptions(reinterpret_cast<const int32_t *>(d_in[0]), reinterpret_cast<const int32_t *>(d_in[1]), d_in[2], (int64_t)n, pool, h->length,
+                                     work, at, buf.d_scratch.p, buf.d_scratch.cap, h->stream));
     HIP_TRY(hipMemcpyAsync(buf.h_int_totals.p, work + at.totals, sizeof(rb::InterruptionTotals), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     rb::InterruptionTotals totals;
@@ -209,21 +198,12 @@ int host_record_interruptions_impl(const char *sequence, int64_t length, const i
             text_at.push_back((int32_t)text.size());
         }
     }
-    std::unique_ptr<RibbitRowPurity, FreeDeleter> out_rows;
-    std::unique_ptr<RibbitInterruption, FreeDeleter> out_sites;
-    std::unique_ptr<char, FreeDeleter> out_text;
-    {
-        RibbitRowPurity *a = nullptr;
-        RibbitInterruption *b = nullptr;
-        char *c = nullptr;
-        if ((rc = hand_out(per_row.data(), n, false, &a))) return rc;
-        out_rows.reset(a);
-        if ((rc = hand_out(found.data(), found.size(), false, &b))) return rc;
-        out_sites.reset(b);
-        if ((rc = hand_out(text.data(), text.size(), true, &c))) return rc;
-        out_text.reset(c);
-    }
-    if ((rc = hand_out(text_at.data(), text_at.size(), false, observed_offsets))) return rc;
+    Handed<RibbitRowPurity> out_rows;
+    Handed<RibbitInterruption> out_sites;
+    Handed<char> out_text;
+    if ((rc = hand_out(per_row.data(), n, false, out_rows)) || (rc = hand_out(found.data(), found.size(), false, out_sites)) ||
+        (rc = hand_out(text.data(), text.size(), true, out_text)) || (rc = hand_out(text_at.data(), text_at.size(), false, observed_offsets)))
+        return rc;
     *rows = out_rows.release();
     *sites = out_sites.release();
     *n_sites = found.size();
@@ -231,85 +211,14 @@ int host_record_interruptions_impl(const char *sequence, int64_t length, const i
     return RIBBIT_OK;
 }
 
-// ---- the CIGARs of a BED text
-// the last columns of the whole lines in [p, end) appended to pool, their lengths to lens; nullptr, or the first line that is not a row
-const char *parse_cigars(const char *p, const char *end, std::string &pool, std::vector<int32_t> &lens) {
-    while (p < end) {
-        const char *eol = static_cast<const char *>(std::memchr(p, '\n', (size_t)(end - p)));
-        if (!eol) eol = end;
-        size_t tabs = 0;
-        const char *last = nullptr;
-        for (const char *q = p; (q = static_cast<const char *>(std::memchr(q, '\t', (size_t)(eol - q)))) != nullptr; ++q) { ++tabs; last = q; }
-        if (tabs < 10) return p;
-        pool.append(last + 1, (size_t)(eol - last - 1));
-        lens.push_back((int32_t)(eol - last - 1));
-        p = eol + 1;
-    }
-    return nullptr;
-}
-
+// ---- the CIGARs of a BED text: every row's last column
 int bed_cigars_impl(const char *text, size_t len, char **pool, int32_t **offsets, size_t *n) {
     if (!pool || !offsets || !n || (!text && len > 0)) return fail(RIBBIT_E_ARG, "null argument");
-    const size_t parts = bed_text_parts(len);      // (pieces of whole lines, as ribbit_bed_motifs cuts them)
-    std::vector<const char *> cut(parts + 1, text + len);
-    cut[0] = text;
-    for (size_t k = 1; k < parts; ++k) {
-        const char *at = std::max(cut[k - 1], text + len * k / parts);
-        const char *nl = at > text ? static_cast<const char *>(std::memchr(at - 1, '\n', (size_t)(text + len - (at - 1)))) : at - 1;
-        cut[k] = nl ? nl + 1 : text + len;
-    }
-    std::vector<std::string> piece(parts);
-    std::vector<std::vector<int32_t>> lens(parts);
-    std::vector<const char *> bad(parts, nullptr);
-    std::vector<char> oom(parts, 0);
-    rb::on_threads((unsigned)parts, [&](unsigned k) {
-        try { bad[k] = parse_cigars(cut[k], cut[k + 1], piece[k], lens[k]); } catch (const std::bad_alloc &) { oom[k] = 1; }
-    });
-    size_t bytes = 0, rows = 0;
-    for (size_t k = 0; k < parts; ++k) {
-        if (oom[k]) return fail(RIBBIT_E_NOMEM, "out of host memory reading the CIGARs");
-        if (bad[k]) return fail(RIBBIT_E_ARG, "BED text at byte %zu is not a row of 11 tab-separated columns", (size_t)(bad[k] - text));
-        bytes += piece[k].size();
-        rows += lens[k].size();
-    }
-    if (bytes > MAX_POOL || rows > MAX_ROWS) return fail(RIBBIT_E_ARG, "%zu rows with %zu bytes of CIGARs", rows, bytes);
-    std::unique_ptr<char[], FreeDeleter> out;
-    {
-        char *a = nullptr;
-        int rc;
-        if ((rc = hand_out<char>(nullptr, bytes, true, &a))) return rc;
-        out.reset(a);
-        if ((rc = hand_out<int32_t>(nullptr, rows + 1, false, offsets))) return rc;
-    }
-    size_t at = 0, row = 0;
-    for (size_t k = 0; k < parts; ++k) {
-        std::memcpy(out.get() + at, piece[k].data(), piece[k].size());
-        for (const int32_t l : lens[k]) {
-            (*offsets)[row++] = (int32_t)at;
-            at += (size_t)l;
-        }
-    }
-    (*offsets)[rows] = (int32_t)at;
-    *pool = out.release();
-    *n = rows;
-    return RIBBIT_OK;
+    return bed_gather(text, len, "CIGARs", [](const BedRow &row) { return row.cigar; },
+                      [](size_t at) { return fail(RIBBIT_E_ARG, "BED text at byte %zu is not a row of 11 tab-separated columns", at); }, pool, offsets, n);
 }
 
 // ---- the two outputs as text
-int join_pieces(const std::vector<std::string> &piece, char **text, size_t *len) {
-    size_t total = 0;
-    for (const std::string &s : piece) total += s.size();
-    int rc;
-    if ((rc = hand_out<char>(nullptr, total, true, text))) return rc;
-    size_t at = 0;
-    for (const std::string &s : piece) {
-        std::memcpy(*text + at, s.data(), s.size());
-        at += s.size();
-    }
-    *len = total;
-    return RIBBIT_OK;
-}
-
 inline bool consistent(const int32_t *intervals, const RibbitRowPurity *rows, size_t i) {
     return (int64_t)intervals[2 * i] + (int64_t)rows[i].query == (int64_t)intervals[2 * i + 1];
 }
@@ -321,129 +230,101 @@ int interruption_text_impl(const char *name, const char *bed, size_t bed_len, co
         return fail(RIBBIT_E_ARG, "null argument");
     if (n > MAX_ROWS || n_sites > MAX_ROWS) return fail(RIBBIT_E_ARG, "%zu rows with %zu interruptions", n, n_sites);
     const size_t parts = bed_text_parts(bed_len);
-    std::vector<size_t> line;
+    BedLines lines;
     int rc;
-    if ((rc = bed_line_starts(bed, bed_len, parts, line))) return rc;
-    if (line.size() - 1 != n) return fail(RIBBIT_E_ARG, "the BED text has %zu lines, not the %zu of the rows", line.size() - 1, n);
+    if ((rc = lines.find(bed, bed_len, parts))) return rc;
+    if (lines.count() != n) return fail(RIBBIT_E_ARG, "the BED text has %zu lines, not the %zu of the rows", lines.count(), n);
     if (n_sites && observed_offsets[0] != 0) return fail(RIBBIT_E_ARG, "the observed bases' offsets start at %d, not at 0", (int)observed_offsets[0]);
     for (size_t j = 0; j < n_sites; ++j)
         if (observed_offsets[j + 1] < observed_offsets[j]) return fail(RIBBIT_E_ARG, "interruption %zu: the observed bases' offsets do not ascend", j);
     if (n_sites && observed_offsets[n_sites] > 0 && !observed) return fail(RIBBIT_E_ARG, "null argument");
     const size_t pool_len = cigars ? std::strlen(cigars) : 0, name_len = std::strlen(name);
-    enum : int { FINE = 0, NOMEM, RANGE, OWNER, CIGAR, LINE };
-    struct Bad { int why = FINE; size_t row = 0, site = 0; };
-    std::vector<Bad> bad(parts);
-    std::vector<std::string> piece(parts);
+    enum : int { FINE = 0, RANGE, OWNER, CIGAR, LINE };      // a refusal's why; a: the row, b: the interruption
     std::vector<size_t> left_out(parts, 0);
-    rb::on_threads((unsigned)parts, [&](unsigned t) {
-        try {
-            char num[24];
-            std::string &out = piece[t];
-            auto put = [&](int64_t v) { out.append(num, (size_t)(std::to_chars(num, num + sizeof num, v).ptr - num)); };
-            for (size_t i = n * t / parts; i < n * (t + 1) / parts; ++i) {
-                const RibbitRowPurity &r = rows[i];
-                if (r.first < 0 || r.count < 0 || (size_t)r.first + (size_t)r.count > n_sites) { bad[t] = Bad{RANGE, i, 0}; return; }
-                if (!consistent(intervals, rows, i)) { ++left_out[t]; continue; }
-                if (r.count == 0) continue;
-                const char *p = bed + line[i], *eol = bed + line[i + 1];
-                if (eol > p && eol[-1] == '\n') --eol;
-                const char *tab[10];      // the last ten tabs of the line from the right: column j from the end lies between tab[j - 1] and tab[j - 2]
-                int tabs = 0;
-                for (const char *q = eol; q > p && tabs < 10;)
-                    if (*--q == '\t') tab[tabs++] = q;
-                if (tabs < 10 || tab[6] - tab[7] - 1 < 1) { bad[t] = Bad{LINE, i, 0}; return; }
-                const char *motif = tab[7] + 1;
-                const size_t k = (size_t)(tab[6] - tab[7] - 1);
-                const int64_t s = intervals[2 * i];
-                for (size_t j = (size_t)r.first; j < (size_t)r.first + (size_t)r.count; ++j) {
-                    const RibbitInterruption &site = sites[j];
-                    if (site.row < 0 || (size_t)site.row != i) { bad[t] = Bad{OWNER, i, j}; return; }
-                    if (site.cigar_at < 0 || site.cigar_len < 0 || (size_t)site.cigar_at + (size_t)site.cigar_len > pool_len) { bad[t] = Bad{CIGAR, i, j}; return; }
-                    out.append(name, name_len);
-                    out += '\t';
-                    put(site.start);
-                    out += '\t';
-                    put(site.end);
-                    out += '\t';
-                    out.append(cigars + site.cigar_at, (size_t)site.cigar_len);
-                    out += '\t';
-                    const int32_t from = observed_offsets[j], to = observed_offsets[j + 1];
-                    if (to > from) out.append(observed + from, (size_t)(to - from)); else out += '.';
-                    out += '\t';
-                    put(s);
-                    out += '\t';
-                    put(intervals[2 * i + 1]);
-                    out += '\t';
-                    out.append(motif, k);
-                    out += '\t';
-                    put(((int64_t)site.start - s) / (int64_t)k);
-                    out += '\n';
-                }
+    rc = write_pieces(parts, "the interruptions", text, len, [&](size_t t, std::string &out) {
+        for (size_t i = n * t / parts; i < n * (t + 1) / parts; ++i) {
+            const RibbitRowPurity &r = rows[i];
+            if (r.first < 0 || r.count < 0 || (size_t)r.first + (size_t)r.count > n_sites) return PieceRefusal{RANGE, i, 0};
+            if (!consistent(intervals, rows, i)) { ++left_out[t]; continue; }
+            if (r.count == 0) continue;
+            const BedField line = lines[i];
+            const BedField motif = bed_row(line.from, line.to).motif;      // (not a row: no motif)
+            if (motif.to <= motif.from) return PieceRefusal{LINE, i, 0};
+            const int64_t s = intervals[2 * i], k = (int64_t)motif.size();
+            for (size_t j = (size_t)r.first; j < (size_t)r.first + (size_t)r.count; ++j) {
+                const RibbitInterruption &site = sites[j];
+                if (site.row < 0 || (size_t)site.row != i) return PieceRefusal{OWNER, i, j};
+                if (site.cigar_at < 0 || site.cigar_len < 0 || (size_t)site.cigar_at + (size_t)site.cigar_len > pool_len) return PieceRefusal{CIGAR, i, j};
+                out.append(name, name_len);
+                out += '\t';
+                put_number(out, site.start);
+                out += '\t';
+                put_number(out, site.end);
+                out += '\t';
+                out.append(cigars + site.cigar_at, (size_t)site.cigar_len);
+                out += '\t';
+                const int32_t from = observed_offsets[j], to = observed_offsets[j + 1];
+                if (to > from) out.append(observed + from, (size_t)(to - from)); else out += '.';
+                out += '\t';
+                put_number(out, s);
+                out += '\t';
+                put_number(out, intervals[2 * i + 1]);
+                out += '\t';
+                put_field(out, motif);
+                out += '\t';
+                put_number(out, ((int64_t)site.start - s) / k);
+                out += '\n';
             }
-        } catch (const std::bad_alloc &) { bad[t].why = NOMEM; }
-    });
-    size_t left = 0;
-    for (size_t t = 0; t < parts; ++t) {
-        const Bad &b = bad[t];
-        switch (b.why) {
-            case FINE: break;
-            case NOMEM: return fail(RIBBIT_E_NOMEM, "out of host memory writing the interruptions");
-            case RANGE: return fail(RIBBIT_E_ARG, "row %zu: interruptions %d .. %lld of %zu", b.row, (int)rows[b.row].first, (long long)rows[b.row].first + rows[b.row].count, n_sites);
-            case OWNER: return fail(RIBBIT_E_ARG, "row %zu: interruption %zu is row %d's", b.row, b.site, (int)sites[b.site].row);
-            case CIGAR:
-                return fail(RIBBIT_E_ARG, "interruption %zu: CIGAR bytes %d .. %lld of a pool of %zu", b.site, (int)sites[b.site].cigar_at,
-                            (long long)sites[b.site].cigar_at + sites[b.site].cigar_len, pool_len);
-            default: return fail(RIBBIT_E_ARG, "line %zu of the BED text is not a row of 11 tab-separated columns with a motif", b.row);
         }
-        left += left_out[t];
-    }
-    *rows_left_out = left;
-    return join_pieces(piece, text, len);
+        return PieceRefusal{};
+    }, [&](const PieceRefusal &b) {
+        switch (b.why) {
+            case RANGE: return fail(RIBBIT_E_ARG, "row %zu: interruptions %d .. %lld of %zu", b.a, (int)rows[b.a].first, (long long)rows[b.a].first + rows[b.a].count, n_sites);
+            case OWNER: return fail(RIBBIT_E_ARG, "row %zu: interruption %zu is row %d's", b.a, b.b, (int)sites[b.b].row);
+            case CIGAR:
+                return fail(RIBBIT_E_ARG, "interruption %zu: CIGAR bytes %d .. %lld of a pool of %zu", b.b, (int)sites[b.b].cigar_at,
+                            (long long)sites[b.b].cigar_at + sites[b.b].cigar_len, pool_len);
+            default: return fail(RIBBIT_E_ARG, "line %zu of the BED text is not a row of 11 tab-separated columns with a motif", b.a);
+        }
+    });
+    if (rc) return rc;
+    *rows_left_out = 0;
+    for (const size_t l : left_out) *rows_left_out += l;
+    return RIBBIT_OK;
 }
 
 int bed_purity_text_impl(const char *bed, size_t bed_len, const int32_t *intervals, const int32_t *motif_lengths, const RibbitRowPurity *rows, size_t n, char **text,
                          size_t *len) {
     if (!text || !len || (!bed && bed_len > 0) || ((!intervals || !motif_lengths || !rows) && n > 0)) return fail(RIBBIT_E_ARG, "null argument");
     const size_t parts = bed_text_parts(bed_len);
-    std::vector<size_t> line;
+    BedLines lines;
     int rc;
-    if ((rc = bed_line_starts(bed, bed_len, parts, line))) return rc;
-    if (line.size() - 1 != n) return fail(RIBBIT_E_ARG, "the BED text has %zu lines, not the %zu of the rows", line.size() - 1, n);
+    if ((rc = lines.find(bed, bed_len, parts))) return rc;
+    if (lines.count() != n) return fail(RIBBIT_E_ARG, "the BED text has %zu lines, not the %zu of the rows", lines.count(), n);
     for (size_t i = 0; i < n; ++i)
         if (motif_lengths[i] < 1) return fail(RIBBIT_E_ARG, "row %zu: a motif of %d bases", i, (int)motif_lengths[i]);
     // piece k writes lines [n k / parts, n (k + 1) / parts): every line grows by seven columns
-    std::vector<std::string> piece(parts);
-    std::vector<char> oom(parts, 0);
-    rb::on_threads((unsigned)parts, [&](unsigned k) {
-        try {
-            char num[24];
-            std::string &out = piece[k];
-            const size_t from = n * k / parts, to = n * (k + 1) / parts;
-            out.reserve(line[to] - line[from] + 40 * (to - from));
-            for (size_t i = from; i < to; ++i) {
-                const char *p = bed + line[i], *eol = bed + line[i + 1];
-                if (eol > p && eol[-1] == '\n') --eol;
-                out.append(p, (size_t)(eol - p));
-                const RibbitRowPurity &r = rows[i];
-                for (const int64_t v : {(int64_t)r.count, (int64_t)r.x, (int64_t)r.ins, (int64_t)r.del}) {
-                    out += '\t';
-                    out.append(num, (size_t)(std::to_chars(num, num + sizeof num, v).ptr - num));
-                }
-                if (consistent(intervals, rows, i)) {
-                    for (const int64_t v : {(int64_t)r.pure_start, (int64_t)r.pure_end, ((int64_t)r.pure_end - (int64_t)r.pure_start) / (int64_t)motif_lengths[i]}) {
-                        out += '\t';
-                        out.append(num, (size_t)(std::to_chars(num, num + sizeof num, v).ptr - num));
-                    }
-                } else {
-                    out += "\t.\t.\t.";
-                }
-                out += '\n';
+    return write_pieces(parts, "the rows' purity", text, len, [&](size_t k, std::string &out) {
+        const size_t from = n * k / parts, to = n * (k + 1) / parts;
+        out.reserve(lines.start[to] - lines.start[from] + 40 * (to - from));
+        for (size_t i = from; i < to; ++i) {
+            put_field(out, lines[i]);
+            const RibbitRowPurity &r = rows[i];
+            for (const int64_t v : {(int64_t)r.count, (int64_t)r.x, (int64_t)r.ins, (int64_t)r.del}) {
+                out += '\t';
+                put_number(out, v);
             }
-        } catch (const std::bad_alloc &) { oom[k] = 1; }
+            if (consistent(intervals, rows, i)) {
+                for (const int64_t v : {(int64_t)r.pure_start, (int64_t)r.pure_end, ((int64_t)r.pure_end - (int64_t)r.pure_start) / (int64_t)motif_lengths[i]}) {
+                    out += '\t';
+                    put_number(out, v);
+                }
+            } else {
+                out += "\t.\t.\t.";
+            }
+            out += '\n';
+        }
     });
-    for (size_t k = 0; k < parts; ++k)
-        if (oom[k]) return fail(RIBBIT_E_NOMEM, "out of host memory writing the rows' purity");
-    return join_pieces(piece, text, len);
 }
 
 }  // namespace

@@ -2,9 +2,7 @@
 // files behind include/ribbit_hip.h.  The GPU forms read the coverage bitmap the mask builds (build_coverage, api_mask.cpp) and run
 // on the handle's stream; the host twins sort the clipped rows and sweep them, without a per-base array, so that they state the
 // contract a second time instead of repeating the kernels; the loci's text needs no GPU either.
-#include "api_internal.h"
-
-#include <charconv>
+#include "bed_text.h"
 
 namespace {
 
@@ -39,9 +37,9 @@ int record_loci_impl(RibbitHandle *h, const int32_t *intervals, size_t n, int32_
     if ((rc = build_coverage(h, intervals, n))) return rc;
     const int64_t lanes = rb::loci_lanes(length);
     if ((rc = h->rows.d_loci_off.ensure((size_t)lanes + 1))) return rc;
-    if ((rc = h->rows.d_loci_scratch.ensure(rb::loci_scan_scratch_bytes(lanes), true))) return rc;
+    if ((rc = h->rows.d_scratch.ensure(rb::loci_scan_scratch_bytes(lanes), true))) return rc;
     if ((rc = h->rows.h_loci_count.ensure(2))) return rc;
-    HIP_TRY(rb::launch_run_ranks(h->rows.d_mask_bits.p, length, h->rows.d_loci_off.p, h->rows.d_loci_scratch.p, h->rows.d_loci_scratch.cap, h->stream));
+    HIP_TRY(rb::launch_run_ranks(h->rows.d_mask_bits.p, length, h->rows.d_loci_off.p, h->rows.d_scratch.p, h->rows.d_scratch.cap, h->stream));
     HIP_TRY(hipMemcpyAsync(h->rows.h_loci_count.p, h->rows.d_loci_off.p + lanes, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     const uint64_t ranks = h->rows.h_loci_count.p[0];
@@ -52,7 +50,7 @@ int record_loci_impl(RibbitHandle *h, const int32_t *intervals, size_t n, int32_
     if ((rc = h->rows.d_loci_i32.ensure(4 * runs, true))) return rc;
     if ((rc = h->rows.d_loci_u64.ensure(2 * runs + 1, true))) return rc;
     if ((rc = h->rows.d_loci.ensure(runs, true))) return rc;
-    if ((rc = h->rows.d_loci_scratch.ensure(rb::loci_scan_scratch_bytes((int64_t)runs), true))) return rc;
+    if ((rc = h->rows.d_scratch.ensure(rb::loci_scan_scratch_bytes((int64_t)runs), true))) return rc;
     int32_t *run_start = h->rows.d_loci_i32.p, *run_end = run_start + runs, *locus_start = run_end + runs, *post = locus_start + runs;
     uint64_t *join = h->rows.d_loci_u64.p, *key = join + runs, *count = key + runs;
     rb::launch_run_bounds(h->rows.d_mask_bits.p, length, h->rows.d_loci_off.p, run_start, run_end, h->stream);
@@ -60,8 +58,8 @@ int record_loci_impl(RibbitHandle *h, const int32_t *intervals, size_t n, int32_
     HIP_TRY(hipMemsetAsync(key, 0, (runs + 1) * sizeof(uint64_t), h->stream));
     HIP_TRY(hipMemsetAsync(h->rows.d_loci.p, 0, runs * sizeof(RibbitLocus), h->stream));
     HIP_TRY(rb::launch_loci(run_start, run_end, (int64_t)runs, gap, h->rows.d_mask_iv.p, (int64_t)n, length, join, locus_start, post,
-                            reinterpret_cast<unsigned long long *>(key), h->rows.d_loci.p, reinterpret_cast<uint32_t *>(count), h->rows.d_loci_scratch.p,
-                            h->rows.d_loci_scratch.cap, h->stream));
+                            reinterpret_cast<unsigned long long *>(key), h->rows.d_loci.p, reinterpret_cast<uint32_t *>(count), h->rows.d_scratch.p,
+                            h->rows.d_scratch.cap, h->stream));
     HIP_TRY(hipMemcpyAsync(h->rows.h_loci_count.p + 1, count, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     const size_t found = (size_t)(uint32_t)h->rows.h_loci_count.p[1];
@@ -166,51 +164,30 @@ int bed_loci_text_impl(const char *name, const char *bed, size_t bed_len, const 
     if (!name || !text || !len || (!bed && bed_len > 0) || (!loci && n_loci > 0)) return fail(RIBBIT_E_ARG, "null argument");
     // the BED text's line starts are found in pieces, and the loci's lines are written in as many pieces
     const size_t parts = n_loci ? bed_text_parts(bed_len) : 1;
-    std::vector<size_t> line{0};       // line i is [line[i], line[i + 1]); a last line without its newline counts
+    BedLines lines;
     int rc;
-    if (n_loci && (rc = bed_line_starts(bed, bed_len, parts, line))) return rc;
-    if (line.back() != bed_len) line.push_back(bed_len);
-    const size_t n_lines = line.size() - 1, name_len = std::strlen(name);
+    if (n_loci && (rc = lines.find(bed, bed_len, parts))) return rc;
+    const size_t n_lines = lines.count(), name_len = std::strlen(name);
     const size_t out_parts = std::max<size_t>(1, std::min<size_t>(parts, n_loci >> 12));
-    std::vector<std::string> piece(out_parts);
-    std::vector<size_t> bad(out_parts, (size_t)-1);
-    rb::on_threads((unsigned)out_parts, [&](unsigned k) {
-        try {
-            char num[16];
-            std::string &out = piece[k];
-            for (size_t i = n_loci * k / out_parts; i < n_loci * (k + 1) / out_parts; ++i) {
-                const RibbitLocus &l = loci[i];
-                if (l.best_row < 0 || (size_t)l.best_row >= n_lines) { bad[k] = i; return; }
-                const char *p = bed + line[(size_t)l.best_row], *eol = bed + line[(size_t)l.best_row + 1];
-                if (eol > p && eol[-1] == '\n') --eol;
-                const char *from = eol;        // the tenth tab from the right: the row's last ten columns lie behind it
-                int tabs = 0;
-                while (from > p && tabs < 10) tabs += *--from == '\t';
-                if (tabs < 10) { bad[k] = i; return; }
-                out.append(name, name_len);
-                for (const int32_t v : {l.start, l.end, l.rows, l.covered}) {
-                    out += '\t';
-                    out.append(num, (size_t)(std::to_chars(num, num + sizeof num, v).ptr - num));
-                }
-                out.append(from, (size_t)(eol - from));
-                out += '\n';
+    return write_pieces(out_parts, "loci", text, len, [&](size_t k, std::string &out) {
+        for (size_t i = n_loci * k / out_parts; i < n_loci * (k + 1) / out_parts; ++i) {
+            const RibbitLocus &l = loci[i];
+            if (l.best_row < 0 || (size_t)l.best_row >= n_lines) return PieceRefusal{1, i};
+            const BedField line = lines[(size_t)l.best_row];
+            const BedRow row = bed_row(line.from, line.to);
+            if (!row.ok) return PieceRefusal{1, i};
+            out.append(name, name_len);
+            for (const int32_t v : {l.start, l.end, l.rows, l.covered}) {
+                out += '\t';
+                put_number(out, v);
             }
-        } catch (const std::bad_alloc &) { bad[k] = (size_t)-2; }
+            put_field(out, BedField{row.tail, line.to});      // the row's last ten columns, with the tab before them
+            out += '\n';
+        }
+        return PieceRefusal{};
+    }, [&](const PieceRefusal &b) {
+        return fail(RIBBIT_E_ARG, "locus %zu: its best row %d is not a row of 11 tab-separated columns of the BED text (%zu lines)", b.a, (int)loci[b.a].best_row, n_lines);
     });
-    size_t total = 0;
-    for (size_t k = 0; k < out_parts; ++k) {
-        if (bad[k] == (size_t)-2) return fail(RIBBIT_E_NOMEM, "out of host memory writing loci");
-        if (bad[k] != (size_t)-1) return fail(RIBBIT_E_ARG, "locus %zu: its best row %d is not a row of 11 tab-separated columns of the BED text (%zu lines)", bad[k], (int)loci[bad[k]].best_row, n_lines);
-        total += piece[k].size();
-    }
-    if ((rc = hand_out<char>(nullptr, total, true, text))) return rc;
-    size_t at = 0;
-    for (const std::string &s : piece) {
-        std::memcpy(*text + at, s.data(), s.size());
-        at += s.size();
-    }
-    *len = total;
-    return RIBBIT_OK;
 }
 
 }  // namespace

@@ -1,7 +1,8 @@
 // api_mask.cpp -- the repeat-masked FASTA body of a record (mask.hip); see api_internal.h for the map of the files behind
 // include/ribbit_hip.h.  The GPU form reads the bases where the load left them (dev_ascii_src) and runs on the handle's
-// stream; the host twin and the BED row parser need no GPU.
-#include "api_internal.h"
+// stream; the host twin and the BED row parser need no GPU.  stage_down, the way down of the other row outputs' inputs, is
+// here beside build_coverage.
+#include "bed_text.h"
 
 namespace {
 
@@ -93,6 +94,26 @@ int rbapi::build_coverage(RibbitHandle *h, const int32_t *intervals, size_t n) {
     return RIBBIT_OK;
 }
 
+int rbapi::stage_down(RibbitHandle *h, const StageSegment *segs, size_t n_segs, const uint8_t **at) {
+    size_t bytes = 0, filled = 0;
+    for (size_t i = 0; i < n_segs; ++i) bytes += round16(segs[i].bytes);
+    bytes += 16;
+    int rc;
+    if ((rc = h->rows.h_in.ensure(bytes, true)) || (rc = h->rows.d_in.ensure(bytes, true))) return rc;
+    // (the staging buffer may still be the source of the last call's copy: that call ended in a synchronise)
+    uint8_t *in = h->rows.h_in.p;
+    size_t to = 0;
+    for (size_t i = 0; i < n_segs; ++i) {
+        at[i] = h->rows.d_in.p + to;
+        if (segs[i].bytes) std::memcpy(in + to, segs[i].p, segs[i].bytes);
+        filled = to + segs[i].bytes;
+        to += round16(segs[i].bytes);
+    }
+    std::memset(in + filled, 0, bytes - filled);
+    HIP_TRY(hipMemcpyAsync(h->rows.d_in.p, in, bytes, hipMemcpyHostToDevice, h->stream));
+    return RIBBIT_OK;
+}
+
 namespace {
 
 int host_mask_record_impl(const char *sequence, int64_t length, const int32_t *intervals, size_t n, int32_t mode, int32_t line_width,
@@ -120,47 +141,20 @@ int host_mask_record_impl(const char *sequence, int64_t length, const int32_t *i
     return RIBBIT_OK;
 }
 
-// the rows of the whole lines in [p, end) appended to out; nullptr, or the first line that is not a row
-const char *parse_rows(const char *p, const char *end, std::vector<int32_t> &out) {
-    const char *tab[10];      // the last ten tabs of the line, in a ring
-    while (p < end) {
-        const char *eol = static_cast<const char *>(std::memchr(p, '\n', (size_t)(end - p)));
-        if (!eol) eol = end;
-        // 11 tab-separated columns; read from the right, so that a record name with a tab in it still parses
-        size_t nt = 0;
-        for (const char *q = p; (q = static_cast<const char *>(std::memchr(q, '\t', (size_t)(eol - q)))) != nullptr; ++q) tab[nt++ % 10] = q;
-        int32_t s = 0, e = 0;
-        if (nt < 10 || !parse_int32(tab[nt % 10] + 1, tab[(nt + 1) % 10], &s) || !parse_int32(tab[(nt + 1) % 10] + 1, tab[(nt + 2) % 10], &e))
-            return p;
-        out.push_back(s);
-        out.push_back(e);
-        p = eol + 1;
-    }
-    return nullptr;
-}
-
 int bed_intervals_impl(const char *text, size_t len, int32_t **pairs, size_t *n) {
     if (!pairs || !n || (!text && len > 0)) return fail(RIBBIT_E_ARG, "null argument");
-    const size_t parts = bed_text_parts(len);      // (pieces of whole lines)
-    std::vector<const char *> cut(parts + 1, text + len);
-    cut[0] = text;
-    for (size_t k = 1; k < parts; ++k) {
-        const char *at = std::max(cut[k - 1], text + len * k / parts);
-        const char *nl = at > text ? static_cast<const char *>(std::memchr(at - 1, '\n', (size_t)(text + len - (at - 1)))) : at - 1;
-        cut[k] = nl ? nl + 1 : text + len;
-    }
-    std::vector<std::vector<int32_t>> rows(parts);
-    std::vector<const char *> bad(parts, nullptr);
-    std::vector<char> oom(parts, 0);
-    rb::on_threads((unsigned)parts, [&](unsigned k) {
-        try { bad[k] = parse_rows(cut[k], cut[k + 1], rows[k]); } catch (const std::bad_alloc &) { oom[k] = 1; }
+    std::vector<std::vector<int32_t>> rows;      // per piece: start, end of its lines
+    const BedRead read = bed_read(text, len, rows, [](std::vector<int32_t> &out, const BedRow &row, const char *, const char *) {
+        int32_t s = 0, e = 0;
+        if (!row.ok || !parse_int32(row.start.from, row.start.to, &s) || !parse_int32(row.end.from, row.end.to, &e)) return false;
+        out.push_back(s);
+        out.push_back(e);
+        return true;
     });
+    if (read.oom) return fail(RIBBIT_E_NOMEM, "out of host memory reading BED rows");
+    if (read.bad) return fail(RIBBIT_E_ARG, "BED text at byte %zu is not a row of 11 tab-separated columns with integer start and end", (size_t)(read.bad - text));
     size_t total = 0;
-    for (size_t k = 0; k < parts; ++k) {
-        if (oom[k]) return fail(RIBBIT_E_NOMEM, "out of host memory reading BED rows");
-        if (bad[k]) return fail(RIBBIT_E_ARG, "BED text at byte %zu is not a row of 11 tab-separated columns with integer start and end", (size_t)(bad[k] - text));
-        total += rows[k].size();
-    }
+    for (const std::vector<int32_t> &r : rows) total += r.size();
     int rc;
     if ((rc = hand_out<int32_t>(nullptr, total, false, pairs))) return rc;
     size_t at = 0;

@@ -3,9 +3,7 @@
 // api_mask.cpp), makes a second one of OTHER with the same kernel and runs on the handle's stream; the host twin sorts the clipped
 // intervals and sweeps them, without a per-base array, so that it states the contract a second time instead of repeating the
 // kernels; the rows' text with the two columns needs no GPU either.
-#include "api_internal.h"
-
-#include <charconv>
+#include "bed_text.h"
 
 namespace {
 
@@ -46,7 +44,7 @@ int record_overlap_impl(RibbitHandle *h, const int32_t *rows, size_t n, const in
         const size_t words = (size_t)rb::coverage_words(length), lanes = (size_t)rb::loci_lanes(length);
         if ((rc = buf.d_overlap_bits.ensure(words))) return rc;
         if ((rc = buf.d_overlap_ranks.ensure(2 * lanes))) return rc;
-        if ((rc = buf.d_overlap_scratch.ensure(rb::overlap_scratch_bytes(length, (int64_t)n_other), true))) return rc;
+        if ((rc = buf.d_scratch.ensure(rb::overlap_scratch_bytes(length, (int64_t)n_other), true))) return rc;
         if ((rc = buf.d_overlap.ensure(TOTALS_INTS + 2 * n, true))) return rc;
         HIP_TRY(hipMemsetAsync(buf.d_overlap_bits.p, 0, words * sizeof(uint32_t), h->stream));
         if (n_other) {
@@ -61,7 +59,7 @@ int record_overlap_impl(RibbitHandle *h, const int32_t *rows, size_t n, const in
         }
         HIP_TRY(rb::launch_overlap(buf.d_mask_bits.p, buf.d_overlap_bits.p, length, buf.d_mask_iv.p, (int64_t)n, buf.d_overlap_iv.p, (int64_t)n_other,
                                    buf.d_overlap_ranks.p, buf.d_overlap_keys.p, reinterpret_cast<RibbitOverlapTotals *>(buf.d_overlap.p),
-                                   buf.d_overlap.p + TOTALS_INTS, buf.d_overlap_scratch.p, buf.d_overlap_scratch.cap, h->stream));
+                                   buf.d_overlap.p + TOTALS_INTS, buf.d_scratch.p, buf.d_scratch.cap, h->stream));
         HIP_TRY(hipMemcpyAsync(buf.h_overlap.p, buf.d_overlap.p, (TOTALS_INTS + 2 * n) * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
         h->rec.overlap_n = n_other;
@@ -142,44 +140,23 @@ int host_record_overlap_impl(int64_t length, const int32_t *rows, size_t n, cons
 int bed_overlap_text_impl(const char *bed, size_t bed_len, const int32_t *per_row, size_t n, char **text, size_t *len) {
     if (!text || !len || (!bed && bed_len > 0) || (!per_row && n > 0)) return fail(RIBBIT_E_ARG, "null argument");
     const size_t parts = bed_text_parts(bed_len);
-    std::vector<size_t> line;
+    BedLines lines;
     int rc;
-    if ((rc = bed_line_starts(bed, bed_len, parts, line))) return rc;
-    if (line.size() - 1 != n) return fail(RIBBIT_E_ARG, "the BED text has %zu lines, not the %zu of the rows", line.size() - 1, n);
+    if ((rc = lines.find(bed, bed_len, parts))) return rc;
+    if (lines.count() != n) return fail(RIBBIT_E_ARG, "the BED text has %zu lines, not the %zu of the rows", lines.count(), n);
     // piece k writes lines [n k / parts, n (k + 1) / parts) where they belong: every line grows by two tabs and two numbers
-    std::vector<std::string> piece(parts);
-    std::vector<char> oom(parts, 0);
-    rb::on_threads((unsigned)parts, [&](unsigned k) {
-        try {
-            char num[16];
-            std::string &out = piece[k];
-            const size_t from = n * k / parts, to = n * (k + 1) / parts;
-            out.reserve(line[to] - line[from] + 24 * (to - from));
-            for (size_t i = from; i < to; ++i) {
-                const char *p = bed + line[i], *eol = bed + line[i + 1];
-                if (eol > p && eol[-1] == '\n') --eol;
-                out.append(p, (size_t)(eol - p));
-                for (const int32_t v : {per_row[2 * i], per_row[2 * i + 1]}) {
-                    out += '\t';
-                    out.append(num, (size_t)(std::to_chars(num, num + sizeof num, v).ptr - num));
-                }
-                out += '\n';
+    return write_pieces(parts, "the rows' overlap", text, len, [&](size_t k, std::string &out) {
+        const size_t from = n * k / parts, to = n * (k + 1) / parts;
+        out.reserve(lines.start[to] - lines.start[from] + 24 * (to - from));
+        for (size_t i = from; i < to; ++i) {
+            put_field(out, lines[i]);
+            for (const int32_t v : {per_row[2 * i], per_row[2 * i + 1]}) {
+                out += '\t';
+                put_number(out, v);
             }
-        } catch (const std::bad_alloc &) { oom[k] = 1; }
+            out += '\n';
+        }
     });
-    size_t total = 0;
-    for (size_t k = 0; k < parts; ++k) {
-        if (oom[k]) return fail(RIBBIT_E_NOMEM, "out of host memory writing the rows' overlap");
-        total += piece[k].size();
-    }
-    if ((rc = hand_out<char>(nullptr, total, true, text))) return rc;
-    size_t at = 0;
-    for (const std::string &s : piece) {
-        std::memcpy(*text + at, s.data(), s.size());
-        at += s.size();
-    }
-    *len = total;
-    return RIBBIT_OK;
 }
 
 }  // namespace

@@ -1,9 +1,7 @@
 // api_repeats.cpp -- every row's bases with their flanks as FASTA entries (repeats.hip); see api_internal.h for the map of the
 // files behind include/ribbit_hip.h.  The GPU form reads the bases where the load left them (dev_ascii_src), runs on the handle's
 // stream and hands the text back in batches of at most the handle's text budget; the host twin writes the whole text at once.
-#include "api_internal.h"
-
-#include <charconv>
+#include "bed_text.h"
 
 namespace {
 
@@ -40,7 +38,7 @@ int repeat_sequences_impl(RibbitHandle *h, const char *name, const int32_t *inte
     if ((rc = h->rows.d_rep_iv.ensure(2 * m + name_words, true))) return rc;
     if ((rc = h->rows.d_rep_off.ensure(m + 1, true))) return rc;
     const size_t scratch = rb::repeat_scan_scratch_bytes((int64_t)m);
-    if ((rc = h->rows.d_rep_scratch.ensure(scratch, true))) return rc;
+    if ((rc = h->rows.d_scratch.ensure(scratch, true))) return rc;
     if ((rc = h->rows.d_rep_pick.ensure(2))) return rc;
     if ((rc = h->rows.h_rep_pick.ensure(2))) return rc;
     // (the staging buffers may still be the source or target of the last call's copies: that call ended in a synchronise)
@@ -48,7 +46,7 @@ int repeat_sequences_impl(RibbitHandle *h, const char *name, const int32_t *inte
     std::memcpy(h->rows.h_rep_iv.p + 2 * m, name, name_len + 1);
     HIP_TRY(hipMemcpyAsync(h->rows.d_rep_iv.p, h->rows.h_rep_iv.p, (2 * m + name_words) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(rb::launch_repeat_offsets(h->rows.d_rep_iv.p, (int64_t)m, length, flank, (int32_t)name_len, (int64_t)budget, h->rows.d_rep_off.p,
-                                      h->rows.d_rep_pick.p, h->rows.d_rep_scratch.p, h->rows.d_rep_scratch.cap, h->stream));
+                                      h->rows.d_rep_pick.p, h->rows.d_scratch.p, h->rows.d_scratch.cap, h->stream));
     HIP_TRY(hipMemcpyAsync(h->rows.h_rep_pick.p, h->rows.d_rep_pick.p, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     const int64_t k = h->rows.h_rep_pick.p[0], total = h->rows.h_rep_pick.p[1];
@@ -78,8 +76,7 @@ int host_repeat_sequences_impl(const char *name, const char *sequence, int64_t l
     if ((rc = check_repeat_args(name, intervals, n, flank, text, len))) return rc;
     if (length < 0 || (!sequence && length > 0)) return fail(RIBBIT_E_ARG, "bad sequence");
     std::string out;
-    char num[24];
-    auto put = [&](int64_t v) { out.append(num, (size_t)(std::to_chars(num, num + sizeof num, v).ptr - num)); };
+    auto put = [&](int64_t v) { put_number(out, v); };
     for (size_t i = 0; i < n; ++i) {
         const int64_t s = std::min(std::max<int64_t>(intervals[2 * i], 0), length);
         const int64_t e = std::min(std::max<int64_t>(intervals[2 * i + 1], s), length);

@@ -1,0 +1,120 @@
+"""The row outputs interleaved on one handle.  Best, classes, compounds and interruptions stage their inputs through one pair of
+buffers, and every row output takes its scans' and sorts' temporary storage from one device buffer (RowBufs in
+ribbit_amd/csrc/api_internal.h), so a buffer grows inside another feature than the one that allocated it; the results stay in
+buffers of their own, "valid until the handle's next same call, load or close" (include/ribbit_hip.h).  Every answer here is
+compared with the host twin's."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import interruptions_contract as ic
+import ribbit_amd
+from classes_contract import random_motif
+
+pytestmark = pytest.mark.gpu
+
+
+def _seq(n, seed=0):
+    return np.frombuffer(b"ACGTNacgt", np.uint8)[np.random.RandomState(seed).randint(0, 9, n)].tobytes()
+
+
+def _rows(n, length, seed):
+    """n rows of a record of `length` bases with everything a row output takes: intervals, motifs, labels, motif lengths, CIGARs"""
+    rs = np.random.RandomState(seed)
+    cigars = [ic.random_cigar(rs, int(k)) for k in rs.randint(0, 4, n)]
+    starts = rs.randint(-20, length + 20, n)
+    iv = np.stack([starts, starts + [ic.query_of(c) + (0 if rs.randint(5) else 1) for c in cigars]], 1).astype(np.int32)
+    motifs = [random_motif(rs, int(k)) for k in rs.randint(1, 9, n)]
+    return dict(iv=iv, motifs=motifs, labels=rs.randint(-2, 3, n), ks=np.array([len(m) for m in motifs]), cigars=cigars)
+
+
+def _plain(result):
+    return tuple(x if isinstance(x, (bytes, int, dict)) else x.tobytes() for x in (result if isinstance(result, tuple) else (result,)))
+
+
+# name -> (the call on the handle, its host twin); each takes the record's bases and one _rows
+CALLS = {
+    "best": (lambda sc, seq, r: sc.record_best(r["iv"]), lambda seq, r: ribbit_amd.host_record_best(len(seq), r["iv"])),
+    "classes": (lambda sc, seq, r: sc.record_classes(r["iv"], r["motifs"]), lambda seq, r: ribbit_amd.host_record_classes(len(seq), r["iv"], r["motifs"])),
+    "compounds": (lambda sc, seq, r: sc.record_compounds(r["iv"], r["labels"], 40), lambda seq, r: ribbit_amd.host_record_compounds(len(seq), r["iv"], r["labels"], 40)),
+    "interruptions": (lambda sc, seq, r: sc.record_interruptions(r["iv"], r["ks"], r["cigars"]),
+                      lambda seq, r: ribbit_amd.host_record_interruptions(seq, r["iv"], r["ks"], r["cigars"])),
+    "loci": (lambda sc, seq, r: sc.record_loci(r["iv"], 25), lambda seq, r: ribbit_amd.host_record_loci(len(seq), r["iv"], 25)),
+    "overlap": (lambda sc, seq, r: sc.record_overlap(r["iv"], r["iv"][::3] + 7), lambda seq, r: ribbit_amd.host_record_overlap(len(seq), r["iv"], r["iv"][::3] + 7)),
+    "repeats": (lambda sc, seq, r: sc.repeat_sequences("chr", r["iv"], 30), lambda seq, r: ribbit_amd.host_repeat_sequences("chr", seq, r["iv"], 30)),
+}
+
+
+def _same(sc, seq, name, rows):
+    on_handle, twin = CALLS[name]
+    got, want = _plain(on_handle(sc, seq, rows)), _plain(twin(seq, rows))
+    assert got == want, (name, len(rows["iv"]), len(seq))
+    return got
+
+
+def test_row_outputs_interleaved_on_one_handle():
+    """the shared staging and temporary storage are allocated by best at 70 rows, grow inside classes at 3 000, serve the other
+    outputs at 300 and best again at 3 000; then the first call again, a shorter record, and the round in reverse"""
+    few, mid, many = _rows(70, 3000, 1), _rows(300, 3000, 2), _rows(3000, 3000, 3)
+    steps = [("best", few), ("classes", many)] + [(name, mid) for name in ("compounds", "interruptions", "loci", "overlap", "repeats")] + [("best", many)]
+    with ribbit_amd.Scanner(2, 30) as sc:
+        seq = _seq(3000)
+        sc.load_record(seq)
+        answers = [_same(sc, seq, name, rows) for name, rows in steps]
+        assert _same(sc, seq, *steps[0]) == answers[0]
+        short = _seq(900, 1)
+        sc.load_record(short)
+        for name, rows in reversed(steps):
+            _same(sc, short, name, rows)
+        sc.load_record(seq)
+        assert [_same(sc, seq, name, rows) for name, rows in steps] == answers
+
+
+def test_a_result_outlives_the_other_row_outputs():
+    """what ribbit_hip_record_best returned is still there, byte for byte, after classes, compounds and interruptions on the same
+    handle; what ribbit_hip_record_classes returned, after best"""
+    L = ribbit_amd.load_library()
+    seq = _seq(3000)
+    r = _rows(3000, 3000, 4)
+    iv = r["iv"]
+    pool, off = "".join(r["motifs"]).encode(), np.concatenate([[0], np.cumsum(r["ks"])]).astype(np.int32)
+    params = ribbit_amd.ScanParams()
+    L.ribbit_scan_params_default(C.byref(params), 2, 30)
+    h = C.c_void_p()
+    assert L.ribbit_hip_open(C.byref(params), 0, C.byref(h)) == 0
+    try:
+        assert L.ribbit_hip_load_record(h, seq, len(seq)) == 0
+        best, n_best, bases = C.c_void_p(), C.c_size_t(), C.c_int64()
+        assert L.ribbit_hip_record_best(h, iv.ctypes.data, len(iv), C.byref(best), C.byref(n_best), C.byref(bases)) == 0
+        assert n_best.value > 10
+        kept = C.string_at(best.value, 4 * n_best.value)
+        want, _ = ribbit_amd.host_record_best(len(seq), iv)
+        assert kept == want.tobytes()
+
+        classes, strands, groups, n_groups = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t()
+        assert L.ribbit_hip_record_classes(h, iv.ctypes.data, len(iv), pool, off.ctypes.data, C.byref(classes), C.byref(strands), C.byref(groups), C.byref(n_groups)) == 0
+        labels = np.ascontiguousarray(r["labels"], dtype=np.int32)
+        chains, n_chains, members, n_members = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t()
+        assert L.ribbit_hip_record_compounds(h, iv.ctypes.data, labels.ctypes.data, len(iv), 40, C.byref(chains), C.byref(n_chains), C.byref(members), C.byref(n_members)) == 0
+        ks, cigars = r["ks"].astype(np.int32), b"".join(r["cigars"])
+        cigar_off = np.concatenate([[0], np.cumsum([len(c) for c in r["cigars"]])]).astype(np.int32)
+        rows, sites, n_sites, observed, observed_off = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_void_p()
+        assert L.ribbit_hip_record_interruptions(h, iv.ctypes.data, ks.ctypes.data, len(iv), cigars, cigar_off.ctypes.data, C.byref(rows), C.byref(sites),
+                                                 C.byref(n_sites), C.byref(observed), C.byref(observed_off)) == 0
+        assert n_chains.value > 0 and n_sites.value > 0
+        assert C.string_at(best.value, 4 * n_best.value) == kept
+
+        def classes_now():
+            return (C.string_at(classes.value, int(off[-1])), C.string_at(strands.value, len(iv)),
+                    C.string_at(groups.value, n_groups.value * ribbit_amd.MOTIF_CLASS_DT.itemsize))
+
+        kept_classes = classes_now()
+        host = ribbit_amd.host_record_classes(len(seq), iv, pool, off)
+        assert kept_classes == (host[0], host[1], host[2].tobytes())
+        fewer = np.ascontiguousarray(iv[::-1][:2000])
+        assert L.ribbit_hip_record_best(h, fewer.ctypes.data, len(fewer), C.byref(best), C.byref(n_best), C.byref(bases)) == 0
+        assert classes_now() == kept_classes
+        assert C.string_at(best.value, 4 * n_best.value) == ribbit_amd.host_record_best(len(seq), fewer)[0].tobytes()
+    finally:
+        L.ribbit_hip_close(h)
