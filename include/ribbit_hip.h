@@ -645,6 +645,62 @@ int ribbit_bed_purity_text(const char *bed_text, size_t bed_len, const int32_t *
                            const RibbitRowPurity *rows, size_t n, char **text, size_t *len);
 
 /*
+ * ---- the nearest feature of a second set of intervals ---------------------------------------------------------------
+ * Which interval of a second set a row lies in or touches, and which ones are its neighbours to either side: what bedtools
+ * closest answers.  The contract is symmetric in QUERIES and TARGETS, two sets of (start, end) intervals on one record: the
+ * command-line tool asks with the rows as queries and the other file's intervals as targets, and the other way round.
+ * With L the record's length, every interval (s, e), query or target, is clipped as the mask clips it, s' = max(s, 0),
+ * e' = min(e, L), in 64-bit; one with s' >= e' is empty.  Empty targets are never named.  j is a target's index as given.
+ *   Order A:  the non-empty targets by (s', e', j) ascending.      Order B:  by (e', s', j) ascending.
+ * For a non-empty query, (s, e) being its clipped ends:
+ *   inside:  C = { j : s'_j <= s and e'_j >= e }.  If C is not empty, kind = RIBBIT_NEAREST_INSIDE and hit is the member of C
+ *            with the greatest e', among those the first in order A: the container that reaches furthest; among equals
+ *            the one that starts first; then the lowest j.
+ *   over:    otherwise O = { j : s'_j < e and e'_j > s } (an abutting interval does not overlap, as in the overlap above).
+ *            If O is not empty, kind = RIBBIT_NEAREST_OVER and hit is the first member of O in order A.
+ *   apart:   otherwise kind = RIBBIT_NEAREST_APART and hit = -1.
+ *   left:    the last in order B of { j : e'_j <= s }, left_dist = s - e'_j (0 when it abuts); none: -1, -1.
+ *   right:   the first in order A of { j : s'_j >= e }, right_dist = s'_j - e; none: -1, -1.
+ * left and right are reported whatever kind is: a row inside a gene still names its neighbours.
+ * An empty query: kind = 0 and -1 in the five other fields.
+ */
+typedef struct { int32_t kind, hit, left, left_dist, right, right_dist; } RibbitNearest;   /* 24 bytes */
+#define RIBBIT_NEAREST_APART 0
+#define RIBBIT_NEAREST_OVER 1
+#define RIBBIT_NEAREST_INSIDE 2
+/* The loaded record's n queries against n_targets targets (each at most INT32_MAX), on the GPU.  *out: n records of
+ * handle-owned page-locked memory, valid until the handle's next nearest call, load or close.  L = 0, n = 0 and
+ * n_targets = 0 are no errors.  Before a load: RIBBIT_E_STATE. */
+int ribbit_hip_record_nearest(RibbitHandle *h, const int32_t *queries, size_t n, const int32_t *targets, size_t n_targets,
+                              const RibbitNearest **out);
+/* Host-only twin (no GPU) for a record of `length` bases (0 <= length < 2^31): two sorts and the same searches.  *out
+ * malloc'ed, release with ribbit_nearest_free(). */
+int ribbit_host_record_nearest(int64_t length, const int32_t *queries, size_t n, const int32_t *targets, size_t n_targets,
+                               RibbitNearest **out);
+void ribbit_nearest_free(RibbitNearest *nearest);
+/* The record's BED rows with what is nearest to each appended (host only): line i of bed_text, byte for byte, then eight
+ * more columns, 19 in all:
+ *   "in", "over" or "."; the hit's label, start and end; the left neighbour's label and left_dist; the right neighbour's
+ *   label and right_dist.
+ * targets: the n_targets (start, end) pairs the rows were set against, written as given, unclipped; the label of target j is
+ * labels[label_offsets[j] .. label_offsets[j + 1]), labels NUL-terminated, n_targets + 1 offsets.  A field with nothing to
+ * say (no hit, no neighbour) is ".".  bed_text: row i on line i (a last line without its newline counts, and is written
+ * with one).  A bed_text that does not have n lines, a hit, left or right outside [-1, n_targets), a kind outside 0 .. 2,
+ * label offsets that are negative, do not ascend or leave the pool: RIBBIT_E_ARG.  *text malloc'ed, release with
+ * ribbit_text_free(). */
+int ribbit_bed_nearest_text(const char *bed_text, size_t bed_len, const RibbitNearest *nearest, size_t n, const int32_t *targets,
+                            const char *labels, const int32_t *label_offsets, size_t n_targets, char **text, size_t *len);
+/* The other direction (host only): one line per interval of the second set, in the order given, 12 columns:
+ *   name; the interval's start, end and label as given; then the eight columns above with the record's rows as the targets:
+ *   a row's label is its motif, motifs[motif_offsets[i] .. motif_offsets[i + 1]) as ribbit_bed_motifs hands them out, its
+ *   start and end are rows[2 i] and rows[2 i + 1].
+ * nearest: n_targets records, interval j as the query against the n_rows rows.  The refusals are those above, with the
+ * rows in the targets' place.  *text malloc'ed, release with ribbit_text_free(). */
+int ribbit_nearest_other_text(const char *name, const int32_t *targets, const char *labels, const int32_t *label_offsets,
+                              size_t n_targets, const RibbitNearest *nearest, const int32_t *rows, const char *motifs,
+                              const int32_t *motif_offsets, size_t n_rows, char **text, size_t *len);
+
+/*
  * ---- streaming FASTA ingest ---------------------------------------------------------------------------------------
  * Replaces the reader loop of ribbit.cpp:269-280 (getline + `sequence += line` into one pageable std::string per
  * record).  The file is read in 16-MB blocks; line bodies are copied once, straight into a page-locked buffer

@@ -22,7 +22,8 @@ __all__ = ["RibbitHipError", "ScanParams", "Scanner", "library_path", "load_libr
            "host_record_best", "bed_rows_text",
            "MOTIF_CLASS_DT", "bed_motifs", "host_record_classes", "bed_class_text", "class_summary_text",
            "COMPOUND_DT", "host_record_compounds", "class_labels", "compound_text",
-           "INTERRUPTION_DT", "ROW_PURITY_DT", "bed_cigars", "host_record_interruptions", "interruption_text", "bed_purity_text"]
+           "INTERRUPTION_DT", "ROW_PURITY_DT", "bed_cigars", "host_record_interruptions", "interruption_text", "bed_purity_text",
+           "Nearest", "NEAREST_DT", "host_record_nearest", "bed_nearest_text", "nearest_other_text"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -41,6 +42,7 @@ MOTIF_CLASS_DT = np.dtype([("bases", "<i8")] + [(n, "<i4") for n in ("length", "
 COMPOUND_DT = np.dtype([("bases", "<i8")] + [(n, "<i4") for n in ("start", "end", "rows", "classes", "switches", "overlaps", "first", "pad")])      # RibbitCompound
 INTERRUPTION_DT = np.dtype([(n, "<i4") for n in ("row", "start", "end", "x", "ins", "del", "cigar_at", "cigar_len")])      # RibbitInterruption
 ROW_PURITY_DT = np.dtype([(n, "<i4") for n in ("first", "count", "x", "ins", "del", "query", "pure_start", "pure_end")])      # RibbitRowPurity
+NEAREST_DT = np.dtype([(n, "<i4") for n in ("kind", "hit", "left", "left_dist", "right", "right_dist")])      # RibbitNearest
 
 # every symbol include/ribbit_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -76,6 +78,7 @@ ABI_SYMBOLS = [
     "ribbit_hip_record_compounds", "ribbit_host_record_compounds", "ribbit_compounds_free", "ribbit_class_labels", "ribbit_compound_text",
     "ribbit_bed_cigars", "ribbit_hip_record_interruptions", "ribbit_host_record_interruptions", "ribbit_row_purity_free", "ribbit_interruptions_free",
     "ribbit_interruption_text", "ribbit_bed_purity_text",
+    "ribbit_hip_record_nearest", "ribbit_host_record_nearest", "ribbit_nearest_free", "ribbit_bed_nearest_text", "ribbit_nearest_other_text",
 ]
 
 MASK_MODES = {"soft": 0, "hard": 1}     # RIBBIT_MASK_SOFT / RIBBIT_MASK_HARD
@@ -102,6 +105,12 @@ class OverlapTotals(C.Structure):
 
 # the totals in the order of ribbit-hip --overlap-summary's columns (behind name and length)
 OVERLAP_TOTALS = ("rows", "rows_hit", "other", "other_hit", "rows_bases", "other_bases", "both_bases")
+
+
+class Nearest(C.Structure):
+    """RibbitNearest: what record_nearest finds for one query (include/ribbit_hip.h; kind 0: apart, 1: over, 2: inside); NEAREST_DT is
+    the same record for numpy."""
+    _fields_ = [(n, C.c_int32) for n in ("kind", "hit", "left", "left_dist", "right", "right_dist")]
 
 
 class RefineParams(C.Structure):
@@ -337,6 +346,12 @@ def load_library():
     L.ribbit_interruption_text.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, vp, C.c_size_t, vp, vp, C.c_size_t, C.c_char_p, C.c_char_p, vp, C.POINTER(vp),
                                            C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.ribbit_bed_purity_text.argtypes = [C.c_char_p, C.c_size_t, vp, vp, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_hip_record_nearest.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp)]
+    L.ribbit_host_record_nearest.argtypes = [i64, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp)]
+    L.ribbit_nearest_free.argtypes = [vp]
+    L.ribbit_nearest_free.restype = None
+    L.ribbit_bed_nearest_text.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_size_t, vp, C.c_char_p, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_nearest_other_text.argtypes = [C.c_char_p, vp, C.c_char_p, vp, C.c_size_t, vp, vp, C.c_char_p, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
     _lib = L
     return L
 
@@ -737,6 +752,68 @@ def bed_overlap_text(bed, per_row) -> bytes:
     rc = L.ribbit_bed_overlap_text(text_in, len(text_in), pr.ctypes.data if len(pr) else None, len(pr), C.byref(text), C.byref(n))
     if rc != 0:
         raise RibbitHipError(f"ribbit_bed_overlap_text error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return C.string_at(text.value, n.value)
+    finally:
+        L.ribbit_text_free(text)
+
+
+def host_record_nearest(length: int, queries, targets) -> np.ndarray:
+    """ribbit_host_record_nearest: for every query interval on a record of `length` bases, the target it lies in or overlaps and its
+    neighbours to either side -> a NEAREST_DT array, one record per query.  The contract is in include/ribbit_hip.h.  No GPU needed."""
+    L = load_library()
+    q, t = _pairs(queries), _pairs(targets)
+    out = C.c_void_p()
+    rc = L.ribbit_host_record_nearest(int(length), q.ctypes.data if len(q) else None, len(q), t.ctypes.data if len(t) else None, len(t), C.byref(out))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_host_record_nearest error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return _copy(out.value, len(q), NEAREST_DT)
+    finally:
+        L.ribbit_nearest_free(out)
+
+
+def _nearest_arg(nearest) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(nearest, dtype=NEAREST_DT).reshape(-1))
+
+
+def bed_nearest_text(bed, nearest, targets, labels, label_offsets=None) -> bytes:
+    """ribbit_bed_nearest_text: the lines of `bed` (one record's BED text, row i on line i), each with eight more columns: what
+    `nearest` (record_nearest with the rows as queries) names among `targets`.  labels, label_offsets: a pool and its offsets, or
+    a list of strings and None."""
+    L = load_library()
+    text_in = bed.encode() if isinstance(bed, str) else bytes(bed)
+    near = _nearest_arg(nearest)
+    iv, pool, off = _class_args(targets, labels, label_offsets)
+    text, n = C.c_void_p(), C.c_size_t()
+    rc = L.ribbit_bed_nearest_text(text_in, len(text_in), near.ctypes.data if len(near) else None, len(near), iv.ctypes.data if len(iv) else None, pool,
+                                   off.ctypes.data, len(iv), C.byref(text), C.byref(n))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_bed_nearest_text error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return C.string_at(text.value, n.value)
+    finally:
+        L.ribbit_text_free(text)
+
+
+def nearest_other_text(name, targets, labels, nearest, rows, motifs, label_offsets=None, motif_offsets=None) -> bytes:
+    """ribbit_nearest_other_text: one line per interval of `targets` (a second BED's intervals on one record, with their labels): name,
+    start, end, label and the eight columns of what `nearest` (record_nearest with the intervals as queries) names among the
+    record's `rows`, a row's label being its motif.  Pools with offsets, or lists of strings and None."""
+    L = load_library()
+    raw = name.encode() if isinstance(name, str) else bytes(name)
+    if b"\0" in raw:
+        raise ValueError("a record name cannot hold a NUL byte")
+    iv, pool, off = _class_args(targets, labels, label_offsets)
+    rw, motif_pool, motif_off = _class_args(rows, motifs, motif_offsets)
+    near = _nearest_arg(nearest)
+    if len(near) != len(iv):
+        raise ValueError(f"{len(iv)} intervals want {len(iv)} nearest records, not {len(near)}")
+    text, n = C.c_void_p(), C.c_size_t()
+    rc = L.ribbit_nearest_other_text(raw, iv.ctypes.data if len(iv) else None, pool, off.ctypes.data, len(iv), near.ctypes.data if len(near) else None,
+                                     rw.ctypes.data if len(rw) else None, motif_pool, motif_off.ctypes.data, len(rw), C.byref(text), C.byref(n))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_nearest_other_text error {rc}: {L.ribbit_hip_last_error().decode()}")
     try:
         return C.string_at(text.value, n.value)
     finally:
@@ -1390,6 +1467,13 @@ class Scanner:
         self._check(self._L.ribbit_hip_record_overlap(self._h, iv.ctypes.data if len(iv) else None, len(iv), ot.ctypes.data if len(ot) else None, len(ot),
                                                       C.byref(per_row), C.byref(totals)))
         return _copy(per_row.value, 2 * len(iv), np.dtype("<i4")).reshape(-1, 2), totals.as_dict()
+
+    def record_nearest(self, queries, targets) -> np.ndarray:
+        """The loaded record's queries against `targets` on the GPU (ribbit_hip_record_nearest); see host_record_nearest"""
+        q, t = _pairs(queries), _pairs(targets)
+        out = C.c_void_p()
+        self._check(self._L.ribbit_hip_record_nearest(self._h, q.ctypes.data if len(q) else None, len(q), t.ctypes.data if len(t) else None, len(t), C.byref(out)))
+        return _copy(out.value, len(q), NEAREST_DT)
 
     def record_best(self, intervals):
         """The loaded record's best non-overlapping rows on the GPU (ribbit_hip_record_best); see host_record_best"""

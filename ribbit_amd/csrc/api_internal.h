@@ -17,7 +17,8 @@
 //   api_classes.cpp     the rows of a record grouped by canonical motif class (classes.hip), its host twin, the motifs of a BED text, both texts
 //   api_compound.cpp    the rows of a record chained into compound loci (compound.hip), its host twin, the classes as labels, the chains' text
 //   api_interruptions.cpp  every row's CIGAR decoded into interruptions and the pure stretch (interruptions.hip), its host twin, the CIGARs of a BED text, both texts
-// The last eight are the row outputs: their buffers are the handle's RowBufs `rows`, the last four stage their inputs through
+//   api_nearest.cpp     the nearest interval of a second set for every row, and the other way round (nearest.hip), its host twin, both texts
+// The last nine are the row outputs: their buffers are the handle's RowBufs `rows`, the last five stage their inputs through
 // stage_down, what their host sides share is below (hand_out, clipped_sorted_rows), and the BED text they read and write (the row
 // format, the reader in pieces, the writer in pieces) is
 //   bed_text.h          a row's named fields, bed_read / bed_gather, BedLines, write_pieces / join_text, put_number
@@ -193,7 +194,7 @@ struct PairBufs {
 };
 
 // ---- shared by the host sides of the row outputs (api_mask.cpp, api_repeats.cpp, api_loci.cpp, api_overlap.cpp, api_best.cpp, api_classes.cpp, api_compound.cpp,
-// api_interruptions.cpp)
+// api_interruptions.cpp, api_nearest.cpp)
 
 // n elements as malloc memory the caller frees (never a null pointer, whatever n): a copy of src, or for the caller to fill
 // when src is null; terminate: a zero element behind them
@@ -392,7 +393,7 @@ struct RibbitHandle {
     rb::SeedLists lists;
     bool refine_met_empty_query = false;  // the last ribbit_hip_refine_bed on this handle met an alignment with an empty query (ribbit_hip_refine_met_empty_query)
     // the row outputs of the loaded record (api_mask.cpp, api_repeats.cpp, api_loci.cpp, api_overlap.cpp, api_best.cpp, api_classes.cpp, api_compound.cpp,
-    // api_interruptions.cpp)
+    // api_interruptions.cpp, api_nearest.cpp)
     struct RowBufs {
         // shared by all of them, because every row output ends in a synchronise of the handle's stream and keeps none of the three
         // between calls: the inputs on their way down and on the device (stage_down lays them out), and the temporary storage of the
@@ -462,6 +463,12 @@ struct RibbitHandle {
         PinnedBuf<uint8_t> h_int_totals;
         DevBuf<uint8_t> d_int_work, d_int_text;
         PinnedBuf<uint8_t> h_int;
+        // the nearest targets of the queries (api_nearest.cpp): the targets' keys in both orders, unsorted (then the scan's input and
+        // the scanned maxima) | sorted, their indices in both orders, and the result on the device and on its way up
+        DevBuf<uint64_t> d_near_keys;
+        DevBuf<int32_t> d_near_order;
+        DevBuf<RibbitNearest> d_near;
+        PinnedBuf<RibbitNearest> h_near;
         size_t rep_budget = 0;           // text budget of one batch of repeat sequences in bytes (0: REPEAT_TEXT_BUDGET)
     } rows;
     RibbitHandle *aux = nullptr;          // helper handle of ribbit_hip_refine_bed: streams and buffers of the long alignment batch

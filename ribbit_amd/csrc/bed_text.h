@@ -1,5 +1,5 @@
 // bed_text.h -- the refined BED text as the row outputs read and write it (api_mask.cpp, api_loci.cpp, api_overlap.cpp, api_best.cpp,
-// api_classes.cpp, api_compound.cpp, api_interruptions.cpp, api_repeats.cpp): the row format, the reader that walks a text in
+// api_classes.cpp, api_compound.cpp, api_interruptions.cpp, api_nearest.cpp, api_repeats.cpp): the row format, the reader that walks a text in
 // pieces of whole lines on the host thread team, and the writer that builds a text in pieces and joins them.  No GPU.  What makes a
 // field acceptable, and the words of every refusal, stay with the callers.
 // Not part of the ABI; nothing outside ribbit_amd/csrc includes it.

@@ -391,6 +391,14 @@ hipError_t launch_interruptions(const int32_t *rows, const int32_t *offsets, con
 hipError_t launch_interruption_gather(const uint8_t *ascii, uint8_t *work, const InterruptionLayout &at, uint32_t sites, int64_t observed, uint8_t *out,
                                       hipStream_t stream);
 
+// nearest.hip: n >= 1 queries of the loaded record against n_targets >= 0 targets (api_nearest.cpp), both on the device.  keys:
+// 4 n_targets words (the A keys, then the scan's input | the B keys, then the scanned maxima | the A keys sorted | the B keys
+// sorted), order: 2 n_targets ints (the targets' indices in order A | in order B), scratch: nearest_scratch_bytes(n_targets).
+// out: one record per query.
+size_t nearest_scratch_bytes(int64_t n_targets);
+hipError_t launch_nearest(const int32_t *queries, int64_t n, const int32_t *targets, int64_t n_targets, int64_t length, uint64_t *keys, int32_t *order,
+                          RibbitNearest *out, void *scratch, size_t scratch_bytes, hipStream_t stream);
+
 // profiling aid: reads nwords dwords of src with one coalesced dword per lane (known byte count)
 void launch_calib_stream_read(const uint32_t *src, int64_t nwords, uint32_t *sink, hipStream_t stream);
 

@@ -8,6 +8,7 @@
 //              [--overlap-with OTHER.bed [--overlap-bed FILE] [--overlap-summary FILE]] [--best-bed FILE]
 //              [--class-bed FILE] [--motif-summary FILE] [--compound-bed FILE [--compound-gap D]]
 //              [--interruption-bed FILE] [--purity-bed FILE]
+//              [--overlap-with OTHER.bed [--nearest-bed FILE] [--nearest-other-bed FILE]]
 //
 // Records are independent (ribbit.cpp:269-280 handles them one after the other); here up to --jobs of them are in
 // flight at once PER GPU, each on its own handle / HIP streams, so that the upload and GPU scans of one record overlap
@@ -33,12 +34,16 @@
 // (ribbit_bed_cigars, ribbit_hip_record_interruptions): one line per run of substitutions and indels inside a row, with the bases
 // the record has there (ribbit_interruption_text), and the rows again with their interruption counts and their longest
 // uninterrupted stretch (ribbit_bed_purity_text); the column-4 motifs are parsed once per record for these and the class outputs.
-// The BED rows are read back once per record, however many of the twelve are asked for.
+// --nearest-bed and --nearest-other-bed name, for --overlap-with's file, which interval a row lies in or overlaps and which ones are
+// its neighbours to either side, with their distances (ribbit_hip_record_nearest, once per direction): the rows again with eight
+// columns more, the intervals by their column-4 labels (ribbit_bed_nearest_text), and one line per interval of the file with the
+// rows in the intervals' place, named by their motifs (ribbit_nearest_other_text).
+// The BED rows are read back once per record, however many of the fourteen are asked for.
 //
-// These twelve are the ROW OUTPUTS, and each is described once, by its entry of kOutputs below: its file option, its stage (enum
+// These fourteen are the ROW OUTPUTS, and each is described once, by its entry of kOutputs below: its file option, its stage (enum
 // Stage, with the stage's names beside it), its qualifier options with their ranges and wording (defaults: Settings), and the function that
 // makes one record's text from the record's rows.  Parsing, the "needs" checks, opening the files, the sinks of the pipelined
-// records and of the last one, --timing and the RIBBIT_PROFILE line are loops over that table.  A thirteenth row output is: a stage in
+// records and of the last one, --timing and the RIBBIT_PROFILE line are loops over that table.  A fifteenth row output is: a stage in
 // the enum and its names, the qualifiers' fields in Settings, a produce function, an entry of kOutputs, and its lines of kHelp.
 //
 // Reproduced quirks: -p is accepted and ignored (Q1); without -o the BED rows go to
@@ -85,13 +90,13 @@ void check(int rc) {
 }
 
 // The stages of a record: the six every record goes through, then one per row output, in the order of kOutputs.
-enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, OVERLAP, BEST, CLASSES, COMPOUND, INTERRUPTIONS, N_STAGES };
+enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, OVERLAP, BEST, CLASSES, COMPOUND, INTERRUPTIONS, NEAREST, N_STAGES };
 constexpr int N_FIXED_STAGES = MASK;
 // a stage's key in --timing's stage_ms_summed_over_records and its label in the RIBBIT_PROFILE line
 const struct { const char *key, *label; } kStageNames[N_STAGES] = {
     {"load", "load"}, {"perfect", "perfect"}, {"substitutions", "substitutions"}, {"anchored", "anchored"}, {"dispatch", "dispatch"},
     {"refine_and_bed", "refine+BED"}, {"mask", "mask"}, {"repeats", "repeats"}, {"loci", "loci"}, {"density", "density"}, {"overlap", "overlap"},
-    {"best", "best"}, {"classes", "classes"}, {"compound", "compound"}, {"interruptions", "interruptions"}};
+    {"best", "best"}, {"classes", "classes"}, {"compound", "compound"}, {"interruptions", "interruptions"}, {"nearest", "nearest"}};
 
 // wall time per stage, summed over the records (--timing, RIBBIT_PROFILE=1)
 double g_stage_ms[N_STAGES] = {};
@@ -111,6 +116,23 @@ struct StageClock {
 // where an output's text for one record goes: the record's string of the pipeline, or the file itself for the last record
 using Sink = std::function<void(const char *, size_t)>;
 
+// --overlap-with: the intervals of a second BED file by record name, each with its column-4 label, and which names have been a
+// record of the input
+struct OtherBed {
+    struct Group {
+        std::vector<int32_t> iv;                 // (start, end) per interval, in file order
+        std::string labels;                      // the intervals' labels one behind the other ...
+        std::vector<int32_t> label_at{0};        // ... label j at [label_at[j], label_at[j + 1])
+        bool is_record = false;
+        size_t n() const { return iv.size() / 2; }
+    };
+    std::map<std::string, Group> by_name;
+    const Group *of(const std::string &name) const {
+        const auto it = by_name.find(name);
+        return it == by_name.end() ? nullptr : &it->second;
+    }
+};
+
 // what the outputs of one record share: the record and its rows in BED order, read back once for all of them
 struct RecordRows {
     const std::string &name;
@@ -119,9 +141,9 @@ struct RecordRows {
     const char *bed_text;                // the record's BED text, row i on line i (handle-owned: valid until the handle's next refinement) ...
     size_t bed_len;
     std::string bed_copy;                // ... or this copy of it, when it came in slices and an output quotes it
-    const std::vector<int32_t> *other;   // the record's intervals of --overlap-with, (start, end) each in file order (null: none)
-    // the column-4 motifs of the BED text (owned here), parsed by the first output that asks (motifs_of): the class outputs and the
-    // interruption outputs
+    const OtherBed::Group *other;        // the record's intervals of --overlap-with with their labels (null: none)
+    // the column-4 motifs of the BED text (owned here), parsed by the first output that asks (motifs_of): the class outputs, the
+    // interruption outputs and --nearest-other-bed
     struct Motifs {
         bool have = false;
         char *pool = nullptr;
@@ -170,16 +192,6 @@ struct RecordRows {
     };
     mutable Interruptions decoded;
     size_t n() const { return iv.size() / 2; }
-};
-
-// --overlap-with: the intervals of a second BED file by record name, and which names have been a record of the input
-struct OtherBed {
-    struct Group { std::vector<int32_t> iv; bool is_record = false; };
-    std::map<std::string, Group> by_name;
-    const std::vector<int32_t> *of(const std::string &name) const {
-        const auto it = by_name.find(name);
-        return it == by_name.end() ? nullptr : &it->second.iv;
-    }
 };
 
 // the qualifiers' values and their defaults
@@ -258,7 +270,7 @@ void produce_density(RibbitHandle *h, const RecordRows &r, const Settings &s, co
 // both overlap outputs of a record: the second call finds what the first left on the handle and gives the GPU nothing to do
 const int32_t *overlap_of(RibbitHandle *h, const RecordRows &r, RibbitOverlapTotals *totals) {
     static const std::vector<int32_t> kNone;
-    const std::vector<int32_t> &other = r.other ? *r.other : kNone;
+    const std::vector<int32_t> &other = r.other ? r.other->iv : kNone;
     const int32_t *per_row = nullptr;
     check(ribbit_hip_record_overlap(h, r.iv.data(), r.n(), other.data(), other.size() / 2, &per_row, totals));
     return per_row;
@@ -421,17 +433,52 @@ void produce_purity_bed(RibbitHandle *h, const RecordRows &r, const Settings &, 
     ribbit_text_free(text);
 }
 
+// the record's intervals of --overlap-with, or a group without any
+const OtherBed::Group &other_of(const RecordRows &r) {
+    static const OtherBed::Group kNone;
+    return r.other ? *r.other : kNone;
+}
+
+// the rows as queries against the file's intervals: every row again, with what is nearest to it
+void produce_nearest_bed(RibbitHandle *h, const RecordRows &r, const Settings &, const Sink &write) {
+    const OtherBed::Group &other = other_of(r);
+    const RibbitNearest *nearest = nullptr;
+    char *text = nullptr;
+    size_t len = 0;
+    StageClock c(NEAREST);
+    check(ribbit_hip_record_nearest(h, r.iv.data(), r.n(), other.iv.data(), other.n(), &nearest));
+    check(ribbit_bed_nearest_text(r.bed_text, r.bed_len, nearest, r.n(), other.iv.data(), other.labels.c_str(), other.label_at.data(), other.n(), &text, &len));
+    write(text, len);
+    ribbit_text_free(text);
+}
+
+// the file's intervals as queries against the rows: one line per interval of this record, none for a record without any
+void produce_nearest_other(RibbitHandle *h, const RecordRows &r, const Settings &, const Sink &write) {
+    const OtherBed::Group &other = other_of(r);
+    if (other.n() == 0) return;
+    const RibbitNearest *nearest = nullptr;
+    char *text = nullptr;
+    size_t len = 0;
+    StageClock c(NEAREST);
+    const RecordRows::Motifs &m = motifs_of(r);
+    check(ribbit_hip_record_nearest(h, other.iv.data(), other.n(), r.iv.data(), r.n(), &nearest));
+    check(ribbit_nearest_other_text(r.name.c_str(), other.iv.data(), other.labels.c_str(), other.label_at.data(), other.n(), nearest, r.iv.data(), m.pool, m.offsets,
+                                    r.n(), &text, &len));
+    write(text, len);
+    ribbit_text_free(text);
+}
+
 // One entry per row output.  The order is the order of everything that is done for all of them: the "needs" checks, opening the
 // files (binary), producing a record's texts, the keys of --timing.
 struct Output {
     const char *option;                      // --option FILE
     Stage stage;
-    bool quotes_bed;                         // its lines quote the rows' lines: it needs RecordRows::bed_text
+    bool quotes_bed;                         // its lines quote the rows' lines or their motifs: it needs RecordRows::bed_text
     void (*produce)(RibbitHandle *, const RecordRows &, const Settings &, const Sink &);      // one record's text for this output
     Qualifier qualifiers[MAX_QUALIFIERS];    // (name null: none)
     bool needs_other;                        // it compares the rows with the intervals of --overlap-with
 };
-constexpr size_t N_OUTPUTS = 12;
+constexpr size_t N_OUTPUTS = 14;
 const Output kOutputs[N_OUTPUTS] = {
     {"masked-fasta", MASK, false, produce_masked,
      {{"mask", Qualifier::SOFT_HARD, 0, 0, 0, nullptr, &Settings::mask_mode},
@@ -450,7 +497,9 @@ const Output kOutputs[N_OUTPUTS] = {
     {"compound-bed", COMPOUND, true, produce_compound,
      {{"compound-gap", Qualifier::BASES, 0, 2147483647, 10, "0 .. 2147483647", &Settings::compound_gap}, {}}, false},
     {"interruption-bed", INTERRUPTIONS, true, produce_interruption_bed, {{}, {}}, false},
-    {"purity-bed", INTERRUPTIONS, true, produce_purity_bed, {{}, {}}, false}};
+    {"purity-bed", INTERRUPTIONS, true, produce_purity_bed, {{}, {}}, false},
+    {"nearest-bed", NEAREST, true, produce_nearest_bed, {{}, {}}, true},
+    {"nearest-other-bed", NEAREST, true, produce_nearest_other, {{}, {}}, true}};
 
 // the row outputs that are on, by stage: an output whose stage an earlier one has already named is left out (--timing, RIBBIT_PROFILE)
 std::vector<Stage> stages_on(const std::array<bool, N_OUTPUTS> &on) {
@@ -486,7 +535,7 @@ struct Options {
     std::vector<int> devices;                     // --devices / RIBBIT_DEVICES: GPUs the records are dealt over (empty: `device` alone)
     int jobs = 0;                                 // records in flight PER DEVICE; 0 = automatic
     std::string timing;                           // --timing FILE: a JSON record of the run (the reference has cerr progress lines only)
-    std::string other_path;                       // --overlap-with FILE: the intervals the overlap outputs compare the rows with
+    std::string other_path;                       // --overlap-with FILE: the intervals the overlap and nearest outputs compare the rows with
     std::array<std::string, N_OUTPUTS> row_path;                  // the row outputs' files, as kOutputs orders them (empty: off)
     std::array<std::array<bool, MAX_QUALIFIERS>, N_OUTPUTS> qualifier_given{};
     Settings settings;
@@ -532,9 +581,11 @@ const char *kHelp =
     "                                empty windows too: name, start, end, and the NUMBER OF BASES of the window that BED\n"
     "                                rows cover (an exact integer count, not a fraction: divide by end - start for one)\n"
     "  --density-window arg          (ribbit-hip) bases per window of --density-bedgraph, 1 or more. Default: 10000\n"
-    "  --overlap-with arg            (ribbit-hip) a second BED file (name, start, end, further columns ignored; a truth set,\n"
-    "                                another caller's rows, an annotation) that --overlap-bed and --overlap-summary compare\n"
-    "                                the BED rows of every record with; a name is matched against the record names\n"
+    "  --overlap-with arg            (ribbit-hip) a second BED file (name, start, end; a truth set, another caller's rows, an\n"
+    "                                annotation) that --overlap-bed, --overlap-summary, --nearest-bed and --nearest-other-bed\n"
+    "                                compare the BED rows of every record with; a name is matched against the record names;\n"
+    "                                column 4, if there is one, is the interval's label in the nearest outputs ('.' without\n"
+    "                                one); further columns are ignored\n"
     "  --overlap-bed arg             (ribbit-hip) also write every BED row to this file with two columns appended: the number\n"
     "                                of intervals of --overlap-with that the row overlaps, and the number of the row's bases\n"
     "                                that those intervals cover\n"
@@ -568,7 +619,18 @@ const char *kHelp =
     "  --purity-bed arg              (ribbit-hip) also write every BED row to this file with seven columns appended: the number\n"
     "                                of such runs, their substituted, inserted and deleted bases, then start, end and whole\n"
     "                                motif units of the row's longest uninterrupted stretch (the leftmost of equals; '.'\n"
-    "                                three times for a row whose CIGAR does not span it)\n";
+    "                                three times for a row whose CIGAR does not span it)\n"
+    "  --nearest-bed arg             (ribbit-hip) also write every BED row to this file with eight columns appended, as bedtools\n"
+    "                                closest would: 'in' if one interval of --overlap-with holds the whole row, 'over' if one\n"
+    "                                overlaps it, '.' if none does; that interval's label, start and end (of several\n"
+    "                                containers the one that reaches furthest, else the first overlapping one by start); then\n"
+    "                                label and distance in bases of the nearest interval that ends at or before the row's\n"
+    "                                start, and of the nearest that starts at or behind its end (0: they abut; '.': none)\n"
+    "  --nearest-other-bed arg       (ribbit-hip) also write the other direction to this file, one line per interval of\n"
+    "                                --overlap-with that belongs to a record, in the file's order: name, start, end, label,\n"
+    "                                then the same eight columns with the record's BED rows in the intervals' place, a row's\n"
+    "                                label being its motif: a truth locus that no row meets but that has one 3 bases away\n"
+    "                                is a boundary disagreement, not a miss\n";
 
 bool parse_device_list(const std::string &value, std::vector<int> &out) {
     out.clear();
@@ -671,8 +733,9 @@ bool parse_int32(const char *p, const char *end, int32_t *out) {
     return true;
 }
 
-// --overlap-with FILE: name, start, end and whatever follows, tab separated; empty lines and lines that start with '#', "track" or
-// "browser" are skipped.  A name may come anywhere in the file; its intervals keep the file's order.
+// --overlap-with FILE: name, start, end, a label if there is a fourth column, and whatever follows, tab separated; empty lines and
+// lines that start with '#', "track" or "browser" are skipped.  A name may come anywhere in the file; its intervals keep the file's
+// order.
 void read_other_bed(const std::string &path, OtherBed &other) {
     std::ifstream in(path, std::ios::binary);
     if (!in) die("--overlap-with: cannot open '" + path + "' for reading");
@@ -684,9 +747,14 @@ void read_other_bed(const std::string &path, OtherBed &other) {
         int32_t s = 0, e = 0;
         if (t2 == std::string::npos || !parse_int32(line.data() + t1 + 1, line.data() + t2, &s) || !parse_int32(line.data() + t2 + 1, line.data() + t3, &e))
             die("--overlap-with: line " + std::to_string(k) + " of '" + path + "' is not a BED line (name, start, end)");
-        std::vector<int32_t> &iv = other.by_name[line.substr(0, t1)].iv;
-        iv.push_back(s);
-        iv.push_back(e);
+        OtherBed::Group &group = other.by_name[line.substr(0, t1)];
+        group.iv.push_back(s);
+        group.iv.push_back(e);
+        // the label: the bytes between the third tab and the next one or the line's end; "." for none
+        const size_t from = std::min(t3 + 1, line.size()), to = std::min(line.find('\t', from), line.size());
+        if (to > from) group.labels.append(line, from, to - from); else group.labels += '.';
+        if (group.labels.size() > (size_t)INT32_MAX) die("--overlap-with: the labels of '" + line.substr(0, t1) + "' in '" + path + "' are 2^31 bytes or more");
+        group.label_at.push_back((int32_t)group.labels.size());
     }
 }
 
@@ -1092,7 +1160,7 @@ int main(int argc, char **argv) {
     }
     size_t ignored = 0, ignored_names = 0;
     for (const auto &group : other.by_name)
-        if (!group.second.is_record) { ignored += group.second.iv.size() / 2; ++ignored_names; }
+        if (!group.second.is_record) { ignored += group.second.n(); ++ignored_names; }
     if (const size_t left_out = g_rows_left_out.load())
         std::cerr << "ribbit-hip: --interruption-bed: " << left_out << " rows whose CIGAR does not span the row were left out\n";
     if (ignored) std::cerr << "ribbit-hip: --overlap-with: " << ignored << " intervals of " << ignored_names << " names that are no record of the input were ignored\n";
