@@ -701,6 +701,61 @@ int ribbit_nearest_other_text(const char *name, const int32_t *targets, const ch
                               const int32_t *motif_offsets, size_t n_rows, char **text, size_t *len);
 
 /*
+ * ---- base composition of the rows, their flanks and the windows ------------------------------------------------------
+ * What the bases are: A/C/G/T beside every repeat, as TRF prints them; for primer design the GC content of either flank,
+ * whether it holds an N and whether it runs into another repeat; and the composition per window beside the density track.
+ * A byte b of the record is of one of five kinds, by the rule the record is packed with: A, C, G or T if b | 0x20 is 'a',
+ * 'c', 'g' or 't', and `other` for everything else (N, the IUPAC letters, any other byte).  Upper and lower case count alike.
+ *   Per row:    for a row (s, e) and a flank F (0 .. INT32_MAX), the arithmetic of the repeat sequences above, in 64-bit:
+ *                 s' = min(max(s, 0), L)    e' = min(max(e, s'), L)    lo = max(s' - F, 0)    hi = min(e' + F, L)
+ *               One record per row, in the order given, also for empty and out-of-range rows.  A position is covered when a
+ *               non-empty row of the same call holds it, rows clipped as the mask clips them: left_covered > 0 means the left
+ *               flank runs into another repeat (or into a row that overlaps this one).
+ *   Per window: the windows of the density track, window k = [k W, min((k + 1) W, L)) for k = 0 .. ceil(L / W) - 1, W in
+ *               1 .. INT32_MAX.  L = 0: no windows.
+ * Every value is a count of bases.  GC fraction, skew and entropy are one formula away and left to the reader, so that the
+ * GPU, the host twin and this statement can be compared exactly.  Lower-case (soft-masked) input is not counted apart.
+ */
+typedef struct {
+    int32_t a, c, g, t, other;                              /* of [s', e'): they sum to e' - s' */
+    int32_t left,  left_gc,  left_other,  left_covered;     /* of [lo, s'): its length, its C + G, its `other`, its covered positions */
+    int32_t right, right_gc, right_other, right_covered;    /* of [e', hi) likewise */
+} RibbitRowComposition;                                     /* 52 bytes */
+typedef struct { int32_t a, c, g, t, other; } RibbitBaseCounts;   /* 20 bytes; they sum to the window's length */
+/* The loaded record's n rows (at most INT32_MAX) with `flank` bases on either side, on the GPU, from the bit planes the scans
+ * read: *rows is n records of handle-owned page-locked memory, valid until the handle's next composition call, load or
+ * close.  n = 0 and L = 0 are no errors; flank < 0: RIBBIT_E_ARG; before a load: RIBBIT_E_STATE.  The coverage bitmap of
+ * the rows is the one the mask, the loci, the density and the overlap use; the record's prefix counts are built by the first
+ * of these two calls after a load and kept until the next load. */
+int ribbit_hip_record_composition(RibbitHandle *h, const int32_t *intervals, size_t n, int32_t flank,
+                                  const RibbitRowComposition **rows);
+/* The loaded record's base counts per window, on the GPU; *windows is handle-owned page-locked memory, valid until the
+ * handle's next base-window call, load or close.  window < 1: RIBBIT_E_ARG; before a load: RIBBIT_E_STATE. */
+int ribbit_hip_record_base_windows(RibbitHandle *h, int32_t window, const RibbitBaseCounts **windows, size_t *n_windows);
+/* Host-only twins (no GPU), counting the bytes of `sequence` (0 <= length < 2^31): *rows and *windows malloc'ed, release
+ * with ribbit_composition_free(). */
+int ribbit_host_record_composition(const char *sequence, int64_t length, const int32_t *intervals, size_t n, int32_t flank,
+                                   RibbitRowComposition **rows);
+int ribbit_host_record_base_windows(const char *sequence, int64_t length, int32_t window, RibbitBaseCounts **windows,
+                                    size_t *n_windows);
+void ribbit_composition_free(void *rows_or_windows);
+/* Test hook: how often a handle of this process has built a record's prefix counts on the GPU (once per loaded record
+ * that gets either output, however many calls follow). */
+int64_t ribbit_debug_composition_prefix_builds(void);
+/* The record's BED rows with their composition appended (host only): line i of bed_text, byte for byte, then the 13 values
+ * of rows[i] in the struct's order, each behind a tab, and a newline: 24 columns.  bed_text: row i on line i (a last line
+ * without its newline counts).  A bed_text that does not have n lines: RIBBIT_E_ARG.  *text malloc'ed, release with
+ * ribbit_text_free(). */
+int ribbit_bed_composition_text(const char *bed_text, size_t bed_len, const RibbitRowComposition *rows, size_t n, char **text,
+                                size_t *len);
+/* The windows of one record as text (host only), one line per window, empty ones too, 8 tab-separated columns: name, start,
+ * end, A, C, G, T, other.  With equal windows the lines pair one to one with the density track's.  length outside
+ * 0 .. INT32_MAX, window < 1 or an n_windows that is not ceil(length / window): RIBBIT_E_ARG.  *text malloc'ed, release with
+ * ribbit_text_free(). */
+int ribbit_base_windows_text(const char *name, int64_t length, int32_t window, const RibbitBaseCounts *windows, size_t n_windows,
+                             char **text, size_t *len);
+
+/*
  * ---- streaming FASTA ingest ---------------------------------------------------------------------------------------
  * Replaces the reader loop of ribbit.cpp:269-280 (getline + `sequence += line` into one pageable std::string per
  * record).  The file is read in 16-MB blocks; line bodies are copied once, straight into a page-locked buffer

@@ -23,7 +23,8 @@ __all__ = ["RibbitHipError", "ScanParams", "Scanner", "library_path", "load_libr
            "MOTIF_CLASS_DT", "bed_motifs", "host_record_classes", "bed_class_text", "class_summary_text",
            "COMPOUND_DT", "host_record_compounds", "class_labels", "compound_text",
            "INTERRUPTION_DT", "ROW_PURITY_DT", "bed_cigars", "host_record_interruptions", "interruption_text", "bed_purity_text",
-           "Nearest", "NEAREST_DT", "host_record_nearest", "bed_nearest_text", "nearest_other_text"]
+           "Nearest", "NEAREST_DT", "host_record_nearest", "bed_nearest_text", "nearest_other_text",
+           "COMPOSITION_DT", "BASE_COUNTS_DT", "host_record_composition", "host_record_base_windows", "bed_composition_text", "base_windows_text"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -43,6 +44,10 @@ COMPOUND_DT = np.dtype([("bases", "<i8")] + [(n, "<i4") for n in ("start", "end"
 INTERRUPTION_DT = np.dtype([(n, "<i4") for n in ("row", "start", "end", "x", "ins", "del", "cigar_at", "cigar_len")])      # RibbitInterruption
 ROW_PURITY_DT = np.dtype([(n, "<i4") for n in ("first", "count", "x", "ins", "del", "query", "pure_start", "pure_end")])      # RibbitRowPurity
 NEAREST_DT = np.dtype([(n, "<i4") for n in ("kind", "hit", "left", "left_dist", "right", "right_dist")])      # RibbitNearest
+
+COMPOSITION_DT = np.dtype([(n, "<i4") for n in ("a", "c", "g", "t", "other", "left", "left_gc", "left_other", "left_covered",
+                                                 "right", "right_gc", "right_other", "right_covered")])      # RibbitRowComposition
+BASE_COUNTS_DT = np.dtype([(n, "<i4") for n in ("a", "c", "g", "t", "other")])      # RibbitBaseCounts
 
 # every symbol include/ribbit_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -79,6 +84,8 @@ ABI_SYMBOLS = [
     "ribbit_bed_cigars", "ribbit_hip_record_interruptions", "ribbit_host_record_interruptions", "ribbit_row_purity_free", "ribbit_interruptions_free",
     "ribbit_interruption_text", "ribbit_bed_purity_text",
     "ribbit_hip_record_nearest", "ribbit_host_record_nearest", "ribbit_nearest_free", "ribbit_bed_nearest_text", "ribbit_nearest_other_text",
+    "ribbit_hip_record_composition", "ribbit_hip_record_base_windows", "ribbit_host_record_composition", "ribbit_host_record_base_windows",
+    "ribbit_composition_free", "ribbit_debug_composition_prefix_builds", "ribbit_bed_composition_text", "ribbit_base_windows_text",
 ]
 
 MASK_MODES = {"soft": 0, "hard": 1}     # RIBBIT_MASK_SOFT / RIBBIT_MASK_HARD
@@ -352,6 +359,16 @@ def load_library():
     L.ribbit_nearest_free.restype = None
     L.ribbit_bed_nearest_text.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_size_t, vp, C.c_char_p, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.ribbit_nearest_other_text.argtypes = [C.c_char_p, vp, C.c_char_p, vp, C.c_size_t, vp, vp, C.c_char_p, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_hip_record_composition.argtypes = [vp, vp, C.c_size_t, i32, C.POINTER(vp)]
+    L.ribbit_hip_record_base_windows.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_host_record_composition.argtypes = [C.c_char_p, i64, vp, C.c_size_t, i32, C.POINTER(vp)]
+    L.ribbit_host_record_base_windows.argtypes = [C.c_char_p, i64, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_composition_free.argtypes = [vp]
+    L.ribbit_composition_free.restype = None
+    L.ribbit_debug_composition_prefix_builds.argtypes = []
+    L.ribbit_debug_composition_prefix_builds.restype = i64
+    L.ribbit_bed_composition_text.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_base_windows_text.argtypes = [C.c_char_p, i64, i32, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
     _lib = L
     return L
 
@@ -814,6 +831,74 @@ def nearest_other_text(name, targets, labels, nearest, rows, motifs, label_offse
                                      rw.ctypes.data if len(rw) else None, motif_pool, motif_off.ctypes.data, len(rw), C.byref(text), C.byref(n))
     if rc != 0:
         raise RibbitHipError(f"ribbit_nearest_other_text error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return C.string_at(text.value, n.value)
+    finally:
+        L.ribbit_text_free(text)
+
+
+def host_record_composition(sequence: bytes, intervals, flank: int = 100) -> np.ndarray:
+    """ribbit_host_record_composition: the A, C, G, T and other bases of every (start, end) row of `sequence`, and of the `flank` bases on
+    either side of it the length, the C + G, the other bases and the positions that rows cover -> a COMPOSITION_DT array, one record
+    per row.  The contract is in include/ribbit_hip.h.  No GPU needed."""
+    L = load_library()
+    iv, flank = _rows_arg(intervals, flank, "flank")
+    seq = bytes(sequence)
+    out = C.c_void_p()
+    rc = L.ribbit_host_record_composition(seq, len(seq), iv.ctypes.data if len(iv) else None, len(iv), flank, C.byref(out))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_host_record_composition error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return _copy(out.value, len(iv), COMPOSITION_DT)
+    finally:
+        L.ribbit_composition_free(out)
+
+
+def host_record_base_windows(sequence: bytes, window: int) -> np.ndarray:
+    """ribbit_host_record_base_windows: the A, C, G, T and other bases of every window of `window` bases of `sequence` (the last one may
+    be short) -> a BASE_COUNTS_DT array.  No GPU needed."""
+    L = load_library()
+    _, window = _rows_arg((), window, "window")
+    seq = bytes(sequence)
+    out, n = C.c_void_p(), C.c_size_t()
+    rc = L.ribbit_host_record_base_windows(seq, len(seq), window, C.byref(out), C.byref(n))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_host_record_base_windows error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return _copy(out.value, n.value, BASE_COUNTS_DT)
+    finally:
+        L.ribbit_composition_free(out)
+
+
+def bed_composition_text(bed, rows) -> bytes:
+    """ribbit_bed_composition_text: the lines of `bed` (one record's BED text, row i on line i), each with the 13 values of row i of
+    `rows` (record_composition) appended as 13 more columns."""
+    L = load_library()
+    text_in = bed.encode() if isinstance(bed, str) else bytes(bed)
+    rw = np.ascontiguousarray(np.asarray(rows, dtype=COMPOSITION_DT).reshape(-1))
+    text, n = C.c_void_p(), C.c_size_t()
+    rc = L.ribbit_bed_composition_text(text_in, len(text_in), rw.ctypes.data if len(rw) else None, len(rw), C.byref(text), C.byref(n))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_bed_composition_text error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return C.string_at(text.value, n.value)
+    finally:
+        L.ribbit_text_free(text)
+
+
+def base_windows_text(name, length: int, window: int, windows) -> bytes:
+    """ribbit_base_windows_text: one line per window of a record of `length` bases: name, start, end and the five counts of
+    `windows` (record_base_windows)."""
+    L = load_library()
+    raw = name.encode() if isinstance(name, str) else bytes(name)
+    if b"\0" in raw:
+        raise ValueError("a record name cannot hold a NUL byte")
+    _, window = _rows_arg((), window, "window")
+    w = np.ascontiguousarray(np.asarray(windows, dtype=BASE_COUNTS_DT).reshape(-1))
+    text, n = C.c_void_p(), C.c_size_t()
+    rc = L.ribbit_base_windows_text(raw, int(length), window, w.ctypes.data if len(w) else None, len(w), C.byref(text), C.byref(n))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_base_windows_text error {rc}: {L.ribbit_hip_last_error().decode()}")
     try:
         return C.string_at(text.value, n.value)
     finally:
@@ -1474,6 +1559,20 @@ class Scanner:
         out = C.c_void_p()
         self._check(self._L.ribbit_hip_record_nearest(self._h, q.ctypes.data if len(q) else None, len(q), t.ctypes.data if len(t) else None, len(t), C.byref(out)))
         return _copy(out.value, len(q), NEAREST_DT)
+
+    def record_composition(self, intervals, flank: int = 100) -> np.ndarray:
+        """The loaded record's rows' and flanks' base counts on the GPU (ribbit_hip_record_composition); see host_record_composition"""
+        iv, flank = _rows_arg(intervals, flank, "flank")
+        out = C.c_void_p()
+        self._check(self._L.ribbit_hip_record_composition(self._h, iv.ctypes.data if len(iv) else None, len(iv), flank, C.byref(out)))
+        return _copy(out.value, len(iv), COMPOSITION_DT)
+
+    def record_base_windows(self, window: int) -> np.ndarray:
+        """The loaded record's base counts per window on the GPU (ribbit_hip_record_base_windows); see host_record_base_windows"""
+        _, window = _rows_arg((), window, "window")
+        out, n = C.c_void_p(), C.c_size_t()
+        self._check(self._L.ribbit_hip_record_base_windows(self._h, window, C.byref(out), C.byref(n)))
+        return _copy(out.value, n.value, BASE_COUNTS_DT)
 
     def record_best(self, intervals):
         """The loaded record's best non-overlapping rows on the GPU (ribbit_hip_record_best); see host_record_best"""

@@ -18,7 +18,8 @@
 //   api_compound.cpp    the rows of a record chained into compound loci (compound.hip), its host twin, the classes as labels, the chains' text
 //   api_interruptions.cpp  every row's CIGAR decoded into interruptions and the pure stretch (interruptions.hip), its host twin, the CIGARs of a BED text, both texts
 //   api_nearest.cpp     the nearest interval of a second set for every row, and the other way round (nearest.hip), its host twin, both texts
-// The last nine are the row outputs: their buffers are the handle's RowBufs `rows`, the last five stage their inputs through
+//   api_composition.cpp the base counts of every row, its flanks and every window from the bit planes (composition.hip), their host twins, both texts
+// The last ten are the row outputs: their buffers are the handle's RowBufs `rows`, the last five stage their inputs through
 // stage_down, what their host sides share is below (hand_out, clipped_sorted_rows), and the BED text they read and write (the row
 // format, the reader in pieces, the writer in pieces) is
 //   bed_text.h          a row's named fields, bed_read / bed_gather, BedLines, write_pieces / join_text, put_number
@@ -194,7 +195,7 @@ struct PairBufs {
 };
 
 // ---- shared by the host sides of the row outputs (api_mask.cpp, api_repeats.cpp, api_loci.cpp, api_overlap.cpp, api_best.cpp, api_classes.cpp, api_compound.cpp,
-// api_interruptions.cpp, api_nearest.cpp)
+// api_interruptions.cpp, api_nearest.cpp, api_composition.cpp)
 
 // n elements as malloc memory the caller frees (never a null pointer, whatever n): a copy of src, or for the caller to fill
 // when src is null; terminate: a zero element behind them
@@ -235,6 +236,31 @@ std::vector<ClippedRow> clipped_sorted_rows(int64_t length, const int32_t *inter
 inline std::vector<ClippedRow> clipped_sorted_rows(int64_t length, const int32_t *intervals, size_t n) {
     return clipped_sorted_rows(length, intervals, n, [](const ClippedRow &a, const ClippedRow &b) { return a.s != b.s ? a.s < b.s : a.index < b.index; });
 }
+
+// ... merged into their runs of covered positions: what the host twins of the overlap and of the composition count coverage with
+struct CoveredRuns {
+    std::vector<int64_t> start, end, before;      // ascending, disjoint, not abutting; before[k]: covered positions before run k
+    int64_t covered = 0;
+    explicit CoveredRuns(const std::vector<ClippedRow> &sorted) {
+        for (const ClippedRow &r : sorted) {
+            if (start.empty() || r.s > end.back()) {
+                start.push_back(r.s);
+                end.push_back(r.e);
+            } else {
+                end.back() = std::max(end.back(), r.e);
+            }
+        }
+        for (size_t k = 0; k < start.size(); ++k) {
+            before.push_back(covered);
+            covered += end[k] - start[k];
+        }
+    }
+    int64_t covered_before(int64_t p) const {
+        const size_t k = (size_t)(std::upper_bound(start.begin(), start.end(), p) - start.begin());      // runs that start at or before p
+        return k == 0 ? 0 : before[k - 1] + std::min(p, end[k - 1]) - start[k - 1];
+    }
+    int64_t covered_in(const ClippedRow &r) const { return covered_before(r.e) - covered_before(r.s); }
+};
 
 }  // namespace rbapi
 
@@ -278,6 +304,7 @@ struct RibbitHandle {
         int stage_done = STAGE_NONE;          // how far the seed lists have been advanced
         bool coverage_valid = false;          // rows.d_mask_bits is the coverage of the coverage_n rows in rows.h_mask_iv / d_mask_iv (build_coverage)
         size_t coverage_n = 0;
+        bool base_prefix_valid = false;       // rows.d_comp_sums holds the base prefix of the loaded record (api_composition.cpp)
         bool overlap_valid = false;           // rows.h_overlap is the overlap of those rows with the overlap_n intervals in rows.h_overlap_iv (api_overlap.cpp)
         size_t overlap_n = 0;
         rb::ScanSplit last_split[RIBBIT_SCAN_KERNELS];   // the split each scan kernel last ran with on the loaded record
@@ -393,7 +420,7 @@ struct RibbitHandle {
     rb::SeedLists lists;
     bool refine_met_empty_query = false;  // the last ribbit_hip_refine_bed on this handle met an alignment with an empty query (ribbit_hip_refine_met_empty_query)
     // the row outputs of the loaded record (api_mask.cpp, api_repeats.cpp, api_loci.cpp, api_overlap.cpp, api_best.cpp, api_classes.cpp, api_compound.cpp,
-    // api_interruptions.cpp, api_nearest.cpp)
+    // api_interruptions.cpp, api_nearest.cpp, api_composition.cpp)
     struct RowBufs {
         // shared by all of them, because every row output ends in a synchronise of the handle's stream and keeps none of the three
         // between calls: the inputs on their way down and on the device (stage_down lays them out), and the temporary storage of the
@@ -469,6 +496,15 @@ struct RibbitHandle {
         DevBuf<int32_t> d_near_order;
         DevBuf<RibbitNearest> d_near;
         PinnedBuf<RibbitNearest> h_near;
+        // the base composition (api_composition.cpp): the blocks' base counts | their prefix, which belongs to the record
+        // (rec.base_prefix_valid), the blocks' covered positions | their ranks, which belong to one call's rows, and the two results
+        // on the device and on their way up
+        DevBuf<rb::BaseSums> d_comp_sums;
+        DevBuf<uint32_t> d_comp_cover;
+        DevBuf<RibbitRowComposition> d_comp_rows;
+        PinnedBuf<RibbitRowComposition> h_comp_rows;
+        DevBuf<RibbitBaseCounts> d_comp_windows;
+        PinnedBuf<RibbitBaseCounts> h_comp_windows;
         size_t rep_budget = 0;           // text budget of one batch of repeat sequences in bytes (0: REPEAT_TEXT_BUDGET)
     } rows;
     RibbitHandle *aux = nullptr;          // helper handle of ribbit_hip_refine_bed: streams and buffers of the long alignment batch

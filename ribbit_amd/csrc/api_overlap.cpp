@@ -72,38 +72,14 @@ int record_overlap_impl(RibbitHandle *h, const int32_t *rows, size_t n, const in
     return RIBBIT_OK;
 }
 
-// ---- host twin: both sets clipped and sorted by start (clipped_sorted_rows), each merged into its runs of covered positions
-struct Runs {
-    std::vector<int64_t> start, end, before;      // ascending, disjoint, not abutting; before[k]: covered positions before run k
-    int64_t covered = 0;
-    explicit Runs(const std::vector<ClippedRow> &sorted) {
-        for (const ClippedRow &r : sorted) {
-            if (start.empty() || r.s > end.back()) {
-                start.push_back(r.s);
-                end.push_back(r.e);
-            } else {
-                end.back() = std::max(end.back(), r.e);
-            }
-        }
-        for (size_t k = 0; k < start.size(); ++k) {
-            before.push_back(covered);
-            covered += end[k] - start[k];
-        }
-    }
-    int64_t covered_before(int64_t p) const {
-        const size_t k = (size_t)(std::upper_bound(start.begin(), start.end(), p) - start.begin());      // runs that start at or before p
-        return k == 0 ? 0 : before[k - 1] + std::min(p, end[k - 1]) - start[k - 1];
-    }
-    int64_t covered_in(const ClippedRow &r) const { return covered_before(r.e) - covered_before(r.s); }
-};
-
+// ---- host twin: both sets clipped and sorted by start (clipped_sorted_rows), each merged into its runs of covered positions (CoveredRuns)
 int host_record_overlap_impl(int64_t length, const int32_t *rows, size_t n, const int32_t *other, size_t n_other, int32_t **per_row,
                              RibbitOverlapTotals *totals) {
     int rc;
     if ((rc = check_sets(rows, n, other, n_other, per_row, totals))) return rc;
     if (length < 0 || length > (int64_t)INT32_MAX) return fail(RIBBIT_E_ARG, "a record of %lld bases", (long long)length);
     const std::vector<ClippedRow> a = clipped_sorted_rows(length, rows, n), b = clipped_sorted_rows(length, other, n_other);
-    const Runs runs_a(a), runs_b(b);
+    const CoveredRuns runs_a(a), runs_b(b);
     int32_t *out = static_cast<int32_t *>(std::calloc(std::max<size_t>(2 * n, 1), sizeof(int32_t)));
     if (!out) return fail(RIBBIT_E_NOMEM, "out of host memory for %zu rows", n);
     RibbitOverlapTotals t{};

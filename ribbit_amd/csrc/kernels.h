@@ -399,6 +399,22 @@ size_t nearest_scratch_bytes(int64_t n_targets);
 hipError_t launch_nearest(const int32_t *queries, int64_t n, const int32_t *targets, int64_t n_targets, int64_t length, uint64_t *keys, int32_t *order,
                           RibbitNearest *out, void *scratch, size_t scratch_bytes, hipStream_t stream);
 
+// composition.hip: base counts of the loaded record (length > 0) from its bit planes (api_composition.cpp).  A block is
+// COMP_BLOCK bases, the WORDS_PER_LANE words a lane of the scan tile owns; loci_lanes(length) blocks, the lanes of loci.hip and overlap.hip, hold the positions
+// 0 .. length.  sums / prefix: one BaseSums per block (the blocks' counts | C, G, T and other of the positions before the block);
+// scratch: composition_scratch_bytes(length).  The prefix belongs to the record.  bits: the coverage bitmap of the n >= 1 rows as
+// loci.hip takes it; cover_sums / cover_rank: one word per block (the blocks' covered positions | those before the block), made
+// by every rows launch.  out: one record per row / per window, n_windows = ceil(length / window) >= 1.
+constexpr int COMP_BLOCK_WORDS = 8;
+constexpr int COMP_BLOCK = COMP_BLOCK_WORDS * 32;
+struct alignas(16) BaseSums { uint32_t c, g, t, other; };
+size_t composition_scratch_bytes(int64_t length);
+hipError_t launch_composition_prefix(const DevicePlanes &pl, BaseSums *sums, BaseSums *prefix, void *scratch, size_t scratch_bytes, hipStream_t stream);
+hipError_t launch_composition_rows(const DevicePlanes &pl, const BaseSums *prefix, const uint32_t *bits, uint32_t *cover_sums, uint32_t *cover_rank,
+                                   const int32_t *rows, int64_t n, int32_t flank, RibbitRowComposition *out, void *scratch, size_t scratch_bytes,
+                                   hipStream_t stream);
+hipError_t launch_composition_windows(const DevicePlanes &pl, const BaseSums *prefix, int64_t window, int64_t n_windows, RibbitBaseCounts *out, hipStream_t stream);
+
 // profiling aid: reads nwords dwords of src with one coalesced dword per lane (known byte count)
 void launch_calib_stream_read(const uint32_t *src, int64_t nwords, uint32_t *sink, hipStream_t stream);
 

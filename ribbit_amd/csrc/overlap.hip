@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
+#include "bit_blocks.h"
 #include "kernels.h"
 
 namespace rb {
@@ -29,14 +30,6 @@ constexpr int OVL_THREADS = 256;
 // blocks of a launch at most; the kernels stride.  Four blocks per CU: a stride of the block counts covers 2^26 positions, and
 // a record or a row set beyond one stride is still small enough to test
 constexpr int64_t OVL_MAX_BLOCKS = 1024;
-static_assert(LOCI_LANE_WORDS == 8, "a lane loads its words as two dwordx4");
-
-__device__ inline void load_block(const uint32_t *__restrict__ bits, int64_t t, uint32_t (&w)[LOCI_LANE_WORDS]) {
-    const uint4 a = *(const uint4 *)(bits + LOCI_LANE_WORDS * t), b = *(const uint4 *)(bits + LOCI_LANE_WORDS * t + 4);
-    w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
-    w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
-}
-
 __device__ inline unsigned long long wave_sum(unsigned long long v) {
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
@@ -81,10 +74,8 @@ __global__ void __launch_bounds__(OVL_THREADS) overlap_counts_kernel(const uint3
 // covered positions of the bitmap before p, 0 <= p <= length; HIGH: the bitmap's prefixes are the high halves of `rank`
 template <bool HIGH>
 __device__ inline uint32_t rank_at(const uint32_t *__restrict__ bits, const uint64_t *__restrict__ rank, int64_t p) {
-    const int64_t w = p >> 5, t = w / LOCI_LANE_WORDS;
-    uint32_t r = HIGH ? (uint32_t)(rank[t] >> 32) : (uint32_t)rank[t];
-    for (int64_t j = t * LOCI_LANE_WORDS; j < w; ++j) r += (uint32_t)__popc(bits[j]);
-    return r + (uint32_t)__popc(bits[w] & ((1u << (p & 31)) - 1u));
+    const uint64_t r = rank[block_of(p)];
+    return (HIGH ? (uint32_t)(r >> 32) : (uint32_t)r) + ones_before_in_block(bits, p);
 }
 
 // One lane per interval, intervals in grid-stride waves (every lane of a wave takes the same number of turns: the ballots see

@@ -9,6 +9,7 @@
 //              [--class-bed FILE] [--motif-summary FILE] [--compound-bed FILE [--compound-gap D]]
 //              [--interruption-bed FILE] [--purity-bed FILE]
 //              [--overlap-with OTHER.bed [--nearest-bed FILE] [--nearest-other-bed FILE]]
+//              [--composition-bed FILE [--composition-flank F]] [--composition-track FILE [--composition-window W]]
 //
 // Records are independent (ribbit.cpp:269-280 handles them one after the other); here up to --jobs of them are in
 // flight at once PER GPU, each on its own handle / HIP streams, so that the upload and GPU scans of one record overlap
@@ -37,13 +38,17 @@
 // --nearest-bed and --nearest-other-bed name, for --overlap-with's file, which interval a row lies in or overlaps and which ones are
 // its neighbours to either side, with their distances (ribbit_hip_record_nearest, once per direction): the rows again with eight
 // columns more, the intervals by their column-4 labels (ribbit_bed_nearest_text), and one line per interval of the file with the
-// rows in the intervals' place, named by their motifs (ribbit_nearest_other_text).
-// The BED rows are read back once per record, however many of the fourteen are asked for.
+// rows in the intervals' place, named by their motifs (ribbit_nearest_other_text).  --composition-bed writes every row again with
+// its A, C, G, T and other bases and, for --composition-flank bases on either side, the flank's length, C + G, other bases and the
+// positions other rows cover (ribbit_hip_record_composition, ribbit_bed_composition_text); --composition-track writes the five
+// counts per window, line for line beside --density-bedgraph's (ribbit_hip_record_base_windows, ribbit_base_windows_text); both
+// read the bit planes the scans read, whose prefix counts are built once per record.
+// The BED rows are read back once per record, however many of the sixteen are asked for.
 //
-// These fourteen are the ROW OUTPUTS, and each is described once, by its entry of kOutputs below: its file option, its stage (enum
+// These sixteen are the ROW OUTPUTS, and each is described once, by its entry of kOutputs below: its file option, its stage (enum
 // Stage, with the stage's names beside it), its qualifier options with their ranges and wording (defaults: Settings), and the function that
 // makes one record's text from the record's rows.  Parsing, the "needs" checks, opening the files, the sinks of the pipelined
-// records and of the last one, --timing and the RIBBIT_PROFILE line are loops over that table.  A fifteenth row output is: a stage in
+// records and of the last one, --timing and the RIBBIT_PROFILE line are loops over that table.  A seventeenth row output is: a stage in
 // the enum and its names, the qualifiers' fields in Settings, a produce function, an entry of kOutputs, and its lines of kHelp.
 //
 // Reproduced quirks: -p is accepted and ignored (Q1); without -o the BED rows go to
@@ -90,13 +95,13 @@ void check(int rc) {
 }
 
 // The stages of a record: the six every record goes through, then one per row output, in the order of kOutputs.
-enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, OVERLAP, BEST, CLASSES, COMPOUND, INTERRUPTIONS, NEAREST, N_STAGES };
+enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, OVERLAP, BEST, CLASSES, COMPOUND, INTERRUPTIONS, NEAREST, COMPOSITION, N_STAGES };
 constexpr int N_FIXED_STAGES = MASK;
 // a stage's key in --timing's stage_ms_summed_over_records and its label in the RIBBIT_PROFILE line
 const struct { const char *key, *label; } kStageNames[N_STAGES] = {
     {"load", "load"}, {"perfect", "perfect"}, {"substitutions", "substitutions"}, {"anchored", "anchored"}, {"dispatch", "dispatch"},
     {"refine_and_bed", "refine+BED"}, {"mask", "mask"}, {"repeats", "repeats"}, {"loci", "loci"}, {"density", "density"}, {"overlap", "overlap"},
-    {"best", "best"}, {"classes", "classes"}, {"compound", "compound"}, {"interruptions", "interruptions"}, {"nearest", "nearest"}};
+    {"best", "best"}, {"classes", "classes"}, {"compound", "compound"}, {"interruptions", "interruptions"}, {"nearest", "nearest"}, {"composition", "composition"}};
 
 // wall time per stage, summed over the records (--timing, RIBBIT_PROFILE=1)
 double g_stage_ms[N_STAGES] = {};
@@ -202,6 +207,8 @@ struct Settings {
     int loci_gap = 0;                    // --loci-gap D: runs at most D bases apart are one locus
     int density_window = 10000;          // --density-window W
     int compound_gap = 100;              // --compound-gap D: rows at most D bases behind what came before them are one chain (MISA's default)
+    int composition_flank = 100;         // --composition-flank F: bases on either side of a row
+    int composition_window = 10000;      // --composition-window W
     const OtherBed *other = nullptr;         // --overlap-with FILE, read and grouped by name
 };
 
@@ -468,6 +475,30 @@ void produce_nearest_other(RibbitHandle *h, const RecordRows &r, const Settings 
     ribbit_text_free(text);
 }
 
+// every row again, with what its bases and its flanks' bases are
+void produce_composition_bed(RibbitHandle *h, const RecordRows &r, const Settings &s, const Sink &write) {
+    const RibbitRowComposition *rows = nullptr;
+    char *text = nullptr;
+    size_t len = 0;
+    StageClock c(COMPOSITION);
+    check(ribbit_hip_record_composition(h, r.iv.data(), r.n(), s.composition_flank, &rows));
+    check(ribbit_bed_composition_text(r.bed_text, r.bed_len, rows, r.n(), &text, &len));
+    write(text, len);
+    ribbit_text_free(text);
+}
+
+// one line per window of the record, as --density-bedgraph has them
+void produce_composition_track(RibbitHandle *h, const RecordRows &r, const Settings &s, const Sink &write) {
+    const RibbitBaseCounts *windows = nullptr;
+    char *text = nullptr;
+    size_t n_windows = 0, len = 0;
+    StageClock c(COMPOSITION);
+    check(ribbit_hip_record_base_windows(h, s.composition_window, &windows, &n_windows));
+    check(ribbit_base_windows_text(r.name.c_str(), r.length, s.composition_window, windows, n_windows, &text, &len));
+    write(text, len);
+    ribbit_text_free(text);
+}
+
 // One entry per row output.  The order is the order of everything that is done for all of them: the "needs" checks, opening the
 // files (binary), producing a record's texts, the keys of --timing.
 struct Output {
@@ -478,7 +509,7 @@ struct Output {
     Qualifier qualifiers[MAX_QUALIFIERS];    // (name null: none)
     bool needs_other;                        // it compares the rows with the intervals of --overlap-with
 };
-constexpr size_t N_OUTPUTS = 14;
+constexpr size_t N_OUTPUTS = 16;
 const Output kOutputs[N_OUTPUTS] = {
     {"masked-fasta", MASK, false, produce_masked,
      {{"mask", Qualifier::SOFT_HARD, 0, 0, 0, nullptr, &Settings::mask_mode},
@@ -499,7 +530,11 @@ const Output kOutputs[N_OUTPUTS] = {
     {"interruption-bed", INTERRUPTIONS, true, produce_interruption_bed, {{}, {}}, false},
     {"purity-bed", INTERRUPTIONS, true, produce_purity_bed, {{}, {}}, false},
     {"nearest-bed", NEAREST, true, produce_nearest_bed, {{}, {}}, true},
-    {"nearest-other-bed", NEAREST, true, produce_nearest_other, {{}, {}}, true}};
+    {"nearest-other-bed", NEAREST, true, produce_nearest_other, {{}, {}}, true},
+    {"composition-bed", COMPOSITION, true, produce_composition_bed,
+     {{"composition-flank", Qualifier::BASES, 0, 999999999, 9, "0 or more, at most 9 digits", &Settings::composition_flank}, {}}, false},
+    {"composition-track", COMPOSITION, false, produce_composition_track,
+     {{"composition-window", Qualifier::BASES, 1, 2147483647, 10, "1 .. 2147483647", &Settings::composition_window}, {}}, false}};
 
 // the row outputs that are on, by stage: an output whose stage an earlier one has already named is left out (--timing, RIBBIT_PROFILE)
 std::vector<Stage> stages_on(const std::array<bool, N_OUTPUTS> &on) {
@@ -630,7 +665,18 @@ const char *kHelp =
     "                                --overlap-with that belongs to a record, in the file's order: name, start, end, label,\n"
     "                                then the same eight columns with the record's BED rows in the intervals' place, a row's\n"
     "                                label being its motif: a truth locus that no row meets but that has one 3 bases away\n"
-    "                                is a boundary disagreement, not a miss\n";
+    "                                is a boundary disagreement, not a miss\n"
+    "  --composition-bed arg         (ribbit-hip) also write every BED row to this file with 13 columns appended: the row's A, C,\n"
+    "                                G, T and other bases (N, IUPAC letters; case is ignored), then for the flank to its left\n"
+    "                                its length, its C + G, its other bases and its bases that BED rows cover (more than 0:\n"
+    "                                the flank runs into another repeat), then the same four for the flank to its right.\n"
+    "                                Exact counts, not fractions: GC content is (C + G) / length\n"
+    "  --composition-flank arg       (ribbit-hip) bases of the record taken on either side of a row for --composition-bed, as\n"
+    "                                --flank takes them for --repeat-fasta. Default: 100\n"
+    "  --composition-track arg       (ribbit-hip) also write one line per window of every record to this file, empty windows\n"
+    "                                too: name, start, end, A, C, G, T, other (exact counts of the window's bases; with equal\n"
+    "                                windows the lines pair with those of --density-bedgraph)\n"
+    "  --composition-window arg      (ribbit-hip) bases per window of --composition-track, 1 or more. Default: 10000\n";
 
 bool parse_device_list(const std::string &value, std::vector<int> &out) {
     out.clear();
