@@ -7,7 +7,7 @@
 namespace {
 
 constexpr size_t MAX_ROWS = (size_t)INT32_MAX;      // (the indices are int32)
-constexpr size_t TOTALS_INTS = sizeof(rb::BestTotals) / sizeof(int32_t);      // the result: the totals, then the chosen rows' indices
+constexpr size_t TOTALS_INTS = sizeof(rb::BestTotals) / sizeof(int32_t);      // the result on its way up: the totals, then the chosen rows' indices
 static_assert(sizeof(rb::BestTotals) == 24, "the indices follow the totals in one buffer of ints");
 
 int check_best_args(const int32_t *intervals, size_t n, const void *rows, const size_t *n_best, const int64_t *bases) {
@@ -29,18 +29,16 @@ int record_best_impl(RibbitHandle *h, const int32_t *intervals, size_t n, const 
     if (length == 0 || n == 0) return RIBBIT_OK;
     if ((rc = bind_device(h))) return rc;
     RibbitHandle::RowBufs &buf = h->rows;
-    if ((rc = buf.d_best_keys.ensure(2 * n, true))) return rc;
-    if ((rc = buf.d_best_work.ensure(3 * n, true))) return rc;
-    if ((rc = buf.d_best_flags.ensure(2 * n, true))) return rc;
-    if ((rc = buf.d_scratch.ensure(rb::best_scratch_bytes((int64_t)n, length), true))) return rc;
-    if ((rc = buf.d_best.ensure(TOTALS_INTS + n, true))) return rc;
+    const rb::BestLayout at = rb::best_layout((int64_t)n, length);
+    if ((rc = buf.d_work.ensure(at.bytes, true))) return rc;
     if ((rc = buf.h_best.ensure(TOTALS_INTS + n, true))) return rc;
     const StageSegment down{intervals, 2 * n * sizeof(int32_t)};
     const uint8_t *d_rows = nullptr;
     if ((rc = stage_down(h, &down, 1, &d_rows))) return rc;
-    HIP_TRY(rb::launch_best(reinterpret_cast<const int32_t *>(d_rows), (int64_t)n, length, buf.d_best_keys.p, buf.d_best_work.p, buf.d_best_flags.p,
-                            reinterpret_cast<rb::BestTotals *>(buf.d_best.p), buf.d_best.p + TOTALS_INTS, buf.d_scratch.p, buf.d_scratch.cap, h->stream));
-    HIP_TRY(hipMemcpyAsync(buf.h_best.p, buf.d_best.p, (TOTALS_INTS + n) * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    uint8_t *work = buf.d_work.p;
+    HIP_TRY(rb::launch_best(reinterpret_cast<const int32_t *>(d_rows), (int64_t)n, length, work, buf.d_work.cap, at, h->stream));
+    HIP_TRY(hipMemcpyAsync(buf.h_best.p, work + at.totals, sizeof(rb::BestTotals), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(buf.h_best.p + TOTALS_INTS, work + at.selected, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     rb::BestTotals totals;
     std::memcpy(&totals, buf.h_best.p, sizeof totals);

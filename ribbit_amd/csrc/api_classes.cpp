@@ -67,18 +67,19 @@ int record_classes_impl(RibbitHandle *h, const int32_t *intervals, size_t n, con
     const size_t pool = (size_t)offsets[n];
     const size_t out_strands = HEADER_BYTES + n * sizeof(RibbitMotifClass), out_classes = out_strands + round16(n), out_bytes = out_classes + pool;
     RibbitHandle::RowBufs &buf = h->rows;
-    if ((rc = buf.d_class_work.ensure(rb::classes_work_words((int64_t)n), true))) return rc;
-    if ((rc = buf.d_scratch.ensure(rb::classes_scratch_bytes((int64_t)n), true))) return rc;
-    if ((rc = buf.d_class.ensure(out_bytes, true))) return rc;
+    const rb::ClassesLayout at = rb::classes_layout((int64_t)n, pool);
+    if ((rc = buf.d_work.ensure(at.bytes, true))) return rc;
     if ((rc = buf.h_class.ensure(out_bytes, true))) return rc;
     const StageSegment down[3] = {{intervals, 2 * n * sizeof(int32_t)}, {offsets, (n + 1) * sizeof(int32_t)}, {motifs, pool}};
     const uint8_t *d_in[3];
     if ((rc = stage_down(h, down, 3, d_in))) return rc;
-    uint8_t *d_out = buf.d_class.p;
-    HIP_TRY(rb::launch_classes(reinterpret_cast<const int32_t *>(d_in[0]), reinterpret_cast<const int32_t *>(d_in[1]), d_in[2], (int64_t)n, h->length,
-                               buf.d_class_work.p, reinterpret_cast<rb::ClassHeader *>(d_out), reinterpret_cast<RibbitMotifClass *>(d_out + HEADER_BYTES),
-                               d_out + out_strands, d_out + out_classes, buf.d_scratch.p, buf.d_scratch.cap, h->stream));
-    HIP_TRY(hipMemcpyAsync(buf.h_class.p, d_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
+    uint8_t *work = buf.d_work.p, *to = buf.h_class.p;
+    HIP_TRY(rb::launch_classes(reinterpret_cast<const int32_t *>(d_in[0]), reinterpret_cast<const int32_t *>(d_in[1]), d_in[2], (int64_t)n, h->length, work,
+                               buf.d_work.cap, at, h->stream));
+    HIP_TRY(hipMemcpyAsync(to, work + at.header, HEADER_BYTES, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(to + HEADER_BYTES, work + at.groups, n * sizeof(RibbitMotifClass), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(to + out_strands, work + at.strands, n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(to + out_classes, work + at.classes, pool, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     rb::ClassHeader header;
     std::memcpy(&header, buf.h_class.p, sizeof header);

@@ -33,15 +33,15 @@ int check_window(int32_t window, const void *windows, const size_t *n_windows) {
 int64_t window_count(int64_t length, int64_t window) { return (length + window - 1) / window; }
 
 // the prefix counts of the loaded record (length > 0) in rows.d_comp_sums behind the blocks' counts, enqueued on the handle's
-// stream unless they are there already; the caller has sized rows.d_scratch (composition_scratch_bytes).  They count as there
+// stream unless they are there already; the caller has sized rows.d_work by `at`, whose scratch region the scan takes.  They count as there
 // (prefix_landed) only once the caller's synchronise has come back clean: a call that fails on its way leaves them to be built again.
-int ensure_base_prefix(RibbitHandle *h) {
+int ensure_base_prefix(RibbitHandle *h, const rb::CompositionLayout &at) {
     if (h->rec.base_prefix_valid) return RIBBIT_OK;
     RibbitHandle::RowBufs &buf = h->rows;
     const size_t blocks = (size_t)rb::loci_lanes(h->length);
     int rc;
     if ((rc = buf.d_comp_sums.ensure(2 * blocks))) return rc;
-    HIP_TRY(rb::launch_composition_prefix(h->planes(), buf.d_comp_sums.p, buf.d_comp_sums.p + blocks, buf.d_scratch.p, buf.d_scratch.cap, h->stream));
+    HIP_TRY(rb::launch_composition_prefix(h->planes(), buf.d_comp_sums.p, buf.d_work.p, buf.d_work.cap, at, h->stream));
     ++g_prefix_builds;
     return RIBBIT_OK;
 }
@@ -63,15 +63,13 @@ int record_composition_impl(RibbitHandle *h, const int32_t *intervals, size_t n,
         return RIBBIT_OK;
     }
     if ((rc = bind_device(h))) return rc;
-    const size_t blocks = (size_t)rb::loci_lanes(length);
-    if ((rc = buf.d_comp_rows.ensure(n, true))) return rc;
-    if ((rc = buf.d_comp_cover.ensure(2 * blocks))) return rc;
-    if ((rc = buf.d_scratch.ensure(rb::composition_scratch_bytes(length), true))) return rc;
-    if ((rc = ensure_base_prefix(h))) return rc;
+    const rb::CompositionLayout at = rb::composition_rows_layout((int64_t)n, length);
+    if ((rc = buf.d_work.ensure(at.bytes, true))) return rc;
+    if ((rc = ensure_base_prefix(h, at))) return rc;
     if ((rc = build_coverage(h, intervals, n))) return rc;
-    HIP_TRY(rb::launch_composition_rows(h->planes(), buf.d_comp_sums.p + blocks, buf.d_mask_bits.p, buf.d_comp_cover.p, buf.d_comp_cover.p + blocks,
-                                        buf.d_mask_iv.p, (int64_t)n, flank, buf.d_comp_rows.p, buf.d_scratch.p, buf.d_scratch.cap, h->stream));
-    HIP_TRY(hipMemcpyAsync(buf.h_comp_rows.p, buf.d_comp_rows.p, n * sizeof(RibbitRowComposition), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(rb::launch_composition_rows(h->planes(), buf.d_comp_sums.p, buf.d_mask_bits.p, buf.d_mask_iv.p, (int64_t)n, flank, buf.d_work.p, buf.d_work.cap, at,
+                                        h->stream));
+    HIP_TRY(hipMemcpyAsync(buf.h_comp_rows.p, buf.d_work.p + at.out, n * sizeof(RibbitRowComposition), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     prefix_landed(h);
     for (size_t i = 0; i < n; ++i) {
@@ -95,13 +93,13 @@ int record_base_windows_impl(RibbitHandle *h, int32_t window, const RibbitBaseCo
     if (length == 0) return RIBBIT_OK;
     if ((rc = bind_device(h))) return rc;
     RibbitHandle::RowBufs &buf = h->rows;
-    const size_t count = (size_t)window_count(length, window), blocks = (size_t)rb::loci_lanes(length);
-    if ((rc = buf.d_comp_windows.ensure(count, true))) return rc;
+    const size_t count = (size_t)window_count(length, window);
+    const rb::CompositionLayout at = rb::composition_windows_layout((int64_t)count, length);
+    if ((rc = buf.d_work.ensure(at.bytes, true))) return rc;
     if ((rc = buf.h_comp_windows.ensure(count, true))) return rc;
-    if ((rc = buf.d_scratch.ensure(rb::composition_scratch_bytes(length), true))) return rc;
-    if ((rc = ensure_base_prefix(h))) return rc;
-    HIP_TRY(rb::launch_composition_windows(h->planes(), buf.d_comp_sums.p + blocks, window, (int64_t)count, buf.d_comp_windows.p, h->stream));
-    HIP_TRY(hipMemcpyAsync(buf.h_comp_windows.p, buf.d_comp_windows.p, count * sizeof(RibbitBaseCounts), hipMemcpyDeviceToHost, h->stream));
+    if ((rc = ensure_base_prefix(h, at))) return rc;
+    HIP_TRY(rb::launch_composition_windows(h->planes(), buf.d_comp_sums.p, window, (int64_t)count, buf.d_work.p, buf.d_work.cap, at, h->stream));
+    HIP_TRY(hipMemcpyAsync(buf.h_comp_windows.p, buf.d_work.p + at.out, count * sizeof(RibbitBaseCounts), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     prefix_landed(h);
     *windows = buf.h_comp_windows.p;

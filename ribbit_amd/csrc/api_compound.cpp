@@ -7,7 +7,7 @@
 namespace {
 
 constexpr size_t MAX_ROWS = (size_t)INT32_MAX;      // (the indices are int32)
-constexpr size_t TOTALS_BYTES = sizeof(rb::CompoundTotals);      // the result: the totals, then n chains of room, then the members
+constexpr size_t TOTALS_BYTES = sizeof(rb::CompoundTotals);      // the result on its way up: the totals, then n chains of room, then the members
 static_assert(TOTALS_BYTES == 16 && sizeof(RibbitCompound) == 40 && sizeof(rb::CompoundSums) == 24, "the chains follow the totals in one buffer, 8-byte aligned");
 
 int check_compound_args(const int32_t *intervals, const int32_t *labels, size_t n, int32_t gap, const void *compounds, const size_t *n_compounds,
@@ -34,31 +34,25 @@ int record_compounds_impl(RibbitHandle *h, const int32_t *intervals, const int32
     if ((rc = bind_device(h))) return rc;
     const size_t out_members = TOTALS_BYTES + n * sizeof(RibbitCompound), out_bytes = out_members + n * sizeof(int32_t);
     RibbitHandle::RowBufs &buf = h->rows;
-    if ((rc = buf.d_cmp_keys.ensure(3 * n, true))) return rc;
-    if ((rc = buf.d_cmp_work.ensure(3 * n + 1, true))) return rc;
-    if ((rc = buf.d_cmp_sums.ensure(n, true))) return rc;
-    if ((rc = buf.d_cmp_flags.ensure(n, true))) return rc;
-    if ((rc = buf.d_scratch.ensure(rb::compound_scratch_bytes((int64_t)n, length), true))) return rc;
-    if ((rc = buf.d_cmp.ensure(out_bytes, true))) return rc;
+    const rb::CompoundLayout at = rb::compound_layout((int64_t)n, length);
+    if ((rc = buf.d_work.ensure(at.bytes, true))) return rc;
     if ((rc = buf.h_cmp.ensure(out_bytes, true))) return rc;
     const StageSegment down[2] = {{intervals, 2 * n * sizeof(int32_t)}, {labels, n * sizeof(int32_t)}};
     const uint8_t *d_in[2];
     if ((rc = stage_down(h, down, 2, d_in))) return rc;
-    uint8_t *d_out = buf.d_cmp.p, *up = buf.h_cmp.p;
-    HIP_TRY(rb::launch_compounds(reinterpret_cast<const int32_t *>(d_in[0]), reinterpret_cast<const int32_t *>(d_in[1]), (int64_t)n, length, gap, buf.d_cmp_keys.p,
-                                 buf.d_cmp_work.p, buf.d_cmp_sums.p, buf.d_cmp_flags.p, reinterpret_cast<rb::CompoundTotals *>(d_out),
-                                 reinterpret_cast<int32_t *>(d_out + out_members), reinterpret_cast<RibbitCompound *>(d_out + TOTALS_BYTES), buf.d_scratch.p,
-                                 buf.d_scratch.cap, h->stream));
+    uint8_t *work = buf.d_work.p, *up = buf.h_cmp.p;
+    HIP_TRY(rb::launch_compounds(reinterpret_cast<const int32_t *>(d_in[0]), reinterpret_cast<const int32_t *>(d_in[1]), (int64_t)n, length, gap, work,
+                                 buf.d_work.cap, at, h->stream));
     // the two counts come up first; then the chains and the members there are, not the room they have
-    HIP_TRY(hipMemcpyAsync(up, d_out, TOTALS_BYTES, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(up, work + at.totals, TOTALS_BYTES, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     rb::CompoundTotals totals;
     std::memcpy(&totals, up, sizeof totals);
     if (totals.rows > n || totals.chains > totals.rows || (totals.chains == 0) != (totals.rows == 0))
         return fail(RIBBIT_E_INTERNAL, "the chains' counts contradict each other (%u chains of %u rows of %zu)", totals.chains, totals.rows, n);
     if (totals.rows == 0) return RIBBIT_OK;      // every row is empty
-    HIP_TRY(hipMemcpyAsync(up + TOTALS_BYTES, d_out + TOTALS_BYTES, totals.chains * sizeof(RibbitCompound), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(up + out_members, d_out + out_members, totals.rows * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(up + TOTALS_BYTES, work + at.compounds, totals.chains * sizeof(RibbitCompound), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(up + out_members, work + at.members, totals.rows * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     const RibbitCompound *found = reinterpret_cast<const RibbitCompound *>(up + TOTALS_BYTES);
     if (found[0].first != 0 || (size_t)found[totals.chains - 1].first + (size_t)found[totals.chains - 1].rows != totals.rows)

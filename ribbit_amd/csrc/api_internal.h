@@ -19,9 +19,10 @@
 //   api_interruptions.cpp  every row's CIGAR decoded into interruptions and the pure stretch (interruptions.hip), its host twin, the CIGARs of a BED text, both texts
 //   api_nearest.cpp     the nearest interval of a second set for every row, and the other way round (nearest.hip), its host twin, both texts
 //   api_composition.cpp the base counts of every row, its flanks and every window from the bit planes (composition.hip), their host twins, both texts
-// The last ten are the row outputs: their buffers are the handle's RowBufs `rows`, the last five stage their inputs through
-// stage_down, what their host sides share is below (hand_out, clipped_sorted_rows), and the BED text they read and write (the row
-// format, the reader in pieces, the writer in pieces) is
+// The last ten are the row outputs: their buffers are the handle's RowBufs `rows`, where all device work of a call is carved from
+// one buffer by the layout its .hip file states (kernels.h); the last five stage their inputs through stage_down, what their host
+// sides share is below (hand_out, clipped_sorted_rows), what their kernels share is row_kernels.h, and the BED text they read and
+// write (the row format, the reader in pieces, the writer in pieces) is
 //   bed_text.h          a row's named fields, bed_read / bed_gather, BedLines, write_pieces / join_text, put_number
 // Host threads: every team of them, here and in refine.cpp, parallel_merge.cpp and host_planes.cpp, is started by rb::on_threads /
 // rb::over_pieces of host_threads.h (part 0 on the caller, a thread that cannot start leaves its part to the caller, all joined, the
@@ -423,18 +424,22 @@ struct RibbitHandle {
     // api_interruptions.cpp, api_nearest.cpp, api_composition.cpp)
     struct RowBufs {
         // shared by all of them, because every row output ends in a synchronise of the handle's stream and keeps none of the three
-        // between calls: the inputs on their way down and on the device (stage_down lays them out), and the temporary storage of the
-        // rocPRIM scans, sorts, selects and reductions, which only work enqueued on the handle's stream within one call touches
+        // between calls: the inputs on their way down and on the device (stage_down lays them out), and the one device work buffer.
+        // A call sizes d_work once, before it enqueues anything, by the layout its .hip file states (rb::BestLayout and the others,
+        // kernels.h): every intermediate array, the result on the device and the temporary storage of the rocPRIM scans, sorts,
+        // selects and reductions are regions of it.  The masked text and the density are all of it; the loci and the repeats take
+        // only that temporary storage from it.  What is named below is pinned (a result stays valid until the handle's next same
+        // call, load or close), or a cache that a later call reads, or a device buffer that is sized by a count the host reads in
+        // the middle of a call, when d_work, if it grew, would move what the first half wrote.
         PinnedBuf<uint8_t> h_in;
-        DevBuf<uint8_t> d_in, d_scratch;
-        // the masked body of the loaded record (api_mask.cpp): coverage bitmap, intervals, the text on the device and on its way up
+        DevBuf<uint8_t> d_in, d_work;
+        // the masked body of the loaded record (api_mask.cpp): coverage bitmap and intervals (rec.coverage_valid), the text on its way up
         DevBuf<uint32_t> d_mask_bits;
         DevBuf<int32_t> d_mask_iv;
-        DevBuf<uint8_t> d_mask_text;
         PinnedBuf<int32_t> h_mask_iv;
         PinnedBuf<char> h_mask_text;
         // the repeat sequences of the loaded record (api_repeats.cpp): the rows with the name behind them, their entry offsets, the
-        // first row of every output span, k and the byte count on their way up, the text of one batch
+        // first row of every output span, k and the byte count on their way up, the text of one batch (sized by k)
         DevBuf<int32_t> d_rep_iv;
         DevBuf<int64_t> d_rep_off;
         DevBuf<int32_t> d_rep_span_row;
@@ -443,68 +448,34 @@ struct RibbitHandle {
         PinnedBuf<int32_t> h_rep_iv;
         PinnedBuf<int64_t> h_rep_pick;
         PinnedBuf<char> h_rep_text;
-        // the loci and the density track of the loaded record (api_loci.cpp), both from d_mask_bits: the lanes' run ranks, the runs
-        // (starts | ends) with the loci's starts and covered prefixes behind them, the join's prefixes with the rows' keys behind
-        // them, the loci and their number on the device and on their way up; the windows' counts
+        // the loci of the loaded record (api_loci.cpp), from d_mask_bits: the lanes' run ranks, the runs (starts | ends) with the
+        // loci's starts and covered prefixes behind them, the join's prefixes with the rows' keys behind them, the loci (all sized
+        // by the number of runs) and their number on their way up; the density's windows on their way up
         DevBuf<uint64_t> d_loci_off, d_loci_u64;
         DevBuf<int32_t> d_loci_i32;
         DevBuf<RibbitLocus> d_loci;
         PinnedBuf<uint64_t> h_loci_count;
         PinnedBuf<RibbitLocus> h_loci;
-        DevBuf<int32_t> d_density;
         PinnedBuf<int32_t> h_density;
-        // the rows against a second set of intervals (api_overlap.cpp): those intervals, their coverage bitmap (the rows' is
-        // d_mask_bits), the blocks' counts with their ranks behind them, the intervals' starts | ends | sorted starts | sorted ends,
-        // and the result on the device and on its way up: the totals, then (others, bases) per row
-        DevBuf<int32_t> d_overlap_iv;
+        // the rows against a second set of intervals (api_overlap.cpp): those intervals as the last call staged them and its result,
+        // the totals, then (others, bases) per row (rec.overlap_valid)
         PinnedBuf<int32_t> h_overlap_iv;
-        DevBuf<uint32_t> d_overlap_bits, d_overlap_keys;
-        DevBuf<uint64_t> d_overlap_ranks;
-        DevBuf<int32_t> d_overlap;
         PinnedBuf<int32_t> h_overlap;
-        // the best non-overlapping rows (api_best.cpp): the rows' keys | the keys sorted, the row indices | the indices in sorted
-        // order | the suffix minimum, the segment heads | the take flags, and the result on the device and on its way up: the
-        // totals, then the chosen indices
-        DevBuf<int32_t> d_best_work;
-        DevBuf<uint64_t> d_best_keys;
-        DevBuf<uint8_t> d_best_flags;
-        DevBuf<int32_t> d_best;
+        // the results on their way up: the best rows (the totals, then the chosen indices), the motif classes (the header, the
+        // groups, the strands, the classes), the compound loci (the counts, the chains, the members), the CIGARs decoded (the counts;
+        // the rows, the interruptions, the offsets, the observed bases, which are gathered on the device into d_int_text, sized by
+        // the counts), the nearest targets, the base composition of the rows and of the windows
         PinnedBuf<int32_t> h_best;
-        // the rows by motif class (api_classes.cpp): the sort items | the items sorted | the groups' aggregates | head flags | group
-        // ids | the long rows' list, and the result on the device and on its way up: the header, the groups, the strands, the classes
-        DevBuf<uint64_t> d_class_work;
-        DevBuf<uint8_t> d_class;
         PinnedBuf<uint8_t> h_class;
-        // the rows chained into compound loci (api_compound.cpp): the keys | the keys sorted | the (chain, label) keys sorted, the
-        // indices or chain ids | reach | the chains' first positions, the prefix sums, the flag bytes, and the result on the device
-        // and on its way up: the counts, then the chains, then the members
-        DevBuf<int32_t> d_cmp_work;
-        DevBuf<uint64_t> d_cmp_keys;
-        DevBuf<rb::CompoundSums> d_cmp_sums;
-        DevBuf<uint8_t> d_cmp_flags;
-        DevBuf<uint8_t> d_cmp;
         PinnedBuf<uint8_t> h_cmp;
-        // the rows' CIGARs decoded (api_interruptions.cpp): everything that is per op, per run, per interruption or per row
-        // (rb::InterruptionLayout), the counts on their way up, the observed bases on the device, and the result on its way up: the
-        // rows, the interruptions, the offsets, the observed bases
         PinnedBuf<uint8_t> h_int_totals;
-        DevBuf<uint8_t> d_int_work, d_int_text;
+        DevBuf<uint8_t> d_int_text;
         PinnedBuf<uint8_t> h_int;
-        // the nearest targets of the queries (api_nearest.cpp): the targets' keys in both orders, unsorted (then the scan's input and
-        // the scanned maxima) | sorted, their indices in both orders, and the result on the device and on its way up
-        DevBuf<uint64_t> d_near_keys;
-        DevBuf<int32_t> d_near_order;
-        DevBuf<RibbitNearest> d_near;
         PinnedBuf<RibbitNearest> h_near;
-        // the base composition (api_composition.cpp): the blocks' base counts | their prefix, which belongs to the record
-        // (rec.base_prefix_valid), the blocks' covered positions | their ranks, which belong to one call's rows, and the two results
-        // on the device and on their way up
-        DevBuf<rb::BaseSums> d_comp_sums;
-        DevBuf<uint32_t> d_comp_cover;
-        DevBuf<RibbitRowComposition> d_comp_rows;
         PinnedBuf<RibbitRowComposition> h_comp_rows;
-        DevBuf<RibbitBaseCounts> d_comp_windows;
         PinnedBuf<RibbitBaseCounts> h_comp_windows;
+        // the blocks' base counts | their prefix, which belongs to the record (rec.base_prefix_valid, api_composition.cpp)
+        DevBuf<rb::BaseSums> d_comp_sums;
         size_t rep_budget = 0;           // text budget of one batch of repeat sequences in bytes (0: REPEAT_TEXT_BUDGET)
     } rows;
     RibbitHandle *aux = nullptr;          // helper handle of ribbit_hip_refine_bed: streams and buffers of the long alignment batch

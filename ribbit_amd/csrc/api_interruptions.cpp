@@ -93,15 +93,14 @@ int record_interruptions_impl(RibbitHandle *h, const int32_t *intervals, const i
     const size_t pool = (size_t)offsets[n];
     const rb::InterruptionLayout at = rb::interruptions_layout((int64_t)n, pool);
     RibbitHandle::RowBufs &buf = h->rows;
-    if ((rc = buf.d_int_work.ensure(at.bytes, true))) return rc;
-    if ((rc = buf.d_scratch.ensure(rb::interruptions_scratch_bytes(pool), true))) return rc;
+    if ((rc = buf.d_work.ensure(at.bytes, true))) return rc;
     if ((rc = buf.h_int_totals.ensure(sizeof(rb::InterruptionTotals)))) return rc;
     const StageSegment down[3] = {{intervals, 2 * n * sizeof(int32_t)}, {offsets, (n + 1) * sizeof(int32_t)}, {cigars, pool}};
     const uint8_t *d_in[3];
     if ((rc = stage_down(h, down, 3, d_in))) return rc;
-    uint8_t *work = buf.d_int_work.p;
+    uint8_t *work = buf.d_work.p;
     HIP_TRY(rb::launch_interruptions(reinterpret_cast<const int32_t *>(d_in[0]), reinterpret_cast<const int32_t *>(d_in[1]), d_in[2], (int64_t)n, pool, h->length,
-                                     work, at, buf.d_scratch.p, buf.d_scratch.cap, h->stream));
+                                     work, buf.d_work.cap, at, h->stream));
     HIP_TRY(hipMemcpyAsync(buf.h_int_totals.p, work + at.totals, sizeof(rb::InterruptionTotals), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     rb::InterruptionTotals totals;

@@ -37,9 +37,9 @@ int record_loci_impl(RibbitHandle *h, const int32_t *intervals, size_t n, int32_
     if ((rc = build_coverage(h, intervals, n))) return rc;
     const int64_t lanes = rb::loci_lanes(length);
     if ((rc = h->rows.d_loci_off.ensure((size_t)lanes + 1))) return rc;
-    if ((rc = h->rows.d_scratch.ensure(rb::loci_scan_scratch_bytes(lanes), true))) return rc;
+    if ((rc = h->rows.d_work.ensure(rb::loci_scan_scratch_bytes(lanes), true))) return rc;
     if ((rc = h->rows.h_loci_count.ensure(2))) return rc;
-    HIP_TRY(rb::launch_run_ranks(h->rows.d_mask_bits.p, length, h->rows.d_loci_off.p, h->rows.d_scratch.p, h->rows.d_scratch.cap, h->stream));
+    HIP_TRY(rb::launch_run_ranks(h->rows.d_mask_bits.p, length, h->rows.d_loci_off.p, h->rows.d_work.p, h->rows.d_work.cap, h->stream));
     HIP_TRY(hipMemcpyAsync(h->rows.h_loci_count.p, h->rows.d_loci_off.p + lanes, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     const uint64_t ranks = h->rows.h_loci_count.p[0];
@@ -50,7 +50,7 @@ int record_loci_impl(RibbitHandle *h, const int32_t *intervals, size_t n, int32_
     if ((rc = h->rows.d_loci_i32.ensure(4 * runs, true))) return rc;
     if ((rc = h->rows.d_loci_u64.ensure(2 * runs + 1, true))) return rc;
     if ((rc = h->rows.d_loci.ensure(runs, true))) return rc;
-    if ((rc = h->rows.d_scratch.ensure(rb::loci_scan_scratch_bytes((int64_t)runs), true))) return rc;
+    if ((rc = h->rows.d_work.ensure(rb::loci_scan_scratch_bytes((int64_t)runs), true))) return rc;
     int32_t *run_start = h->rows.d_loci_i32.p, *run_end = run_start + runs, *locus_start = run_end + runs, *post = locus_start + runs;
     uint64_t *join = h->rows.d_loci_u64.p, *key = join + runs, *count = key + runs;
     rb::launch_run_bounds(h->rows.d_mask_bits.p, length, h->rows.d_loci_off.p, run_start, run_end, h->stream);
@@ -58,8 +58,8 @@ int record_loci_impl(RibbitHandle *h, const int32_t *intervals, size_t n, int32_
     HIP_TRY(hipMemsetAsync(key, 0, (runs + 1) * sizeof(uint64_t), h->stream));
     HIP_TRY(hipMemsetAsync(h->rows.d_loci.p, 0, runs * sizeof(RibbitLocus), h->stream));
     HIP_TRY(rb::launch_loci(run_start, run_end, (int64_t)runs, gap, h->rows.d_mask_iv.p, (int64_t)n, length, join, locus_start, post,
-                            reinterpret_cast<unsigned long long *>(key), h->rows.d_loci.p, reinterpret_cast<uint32_t *>(count), h->rows.d_scratch.p,
-                            h->rows.d_scratch.cap, h->stream));
+                            reinterpret_cast<unsigned long long *>(key), h->rows.d_loci.p, reinterpret_cast<uint32_t *>(count), h->rows.d_work.p,
+                            h->rows.d_work.cap, h->stream));
     HIP_TRY(hipMemcpyAsync(h->rows.h_loci_count.p + 1, count, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     const size_t found = (size_t)(uint32_t)h->rows.h_loci_count.p[1];
@@ -86,12 +86,12 @@ int record_density_impl(RibbitHandle *h, const int32_t *intervals, size_t n, int
     if (length == 0) return RIBBIT_OK;
     if ((rc = bind_device(h))) return rc;
     const size_t windows = (size_t)window_count(length, window);
-    if ((rc = h->rows.d_density.ensure(windows, true))) return rc;
+    if ((rc = h->rows.d_work.ensure(windows * sizeof(int32_t), true))) return rc;
     if ((rc = h->rows.h_density.ensure(windows, true))) return rc;
     if ((rc = build_coverage(h, intervals, n))) return rc;
-    rb::launch_density(h->rows.d_mask_bits.p, length, window, (int64_t)windows, h->rows.d_density.p, h->stream);
+    rb::launch_density(h->rows.d_mask_bits.p, length, window, (int64_t)windows, reinterpret_cast<int32_t *>(h->rows.d_work.p), h->stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h->rows.h_density.p, h->rows.d_density.p, windows * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->rows.h_density.p, h->rows.d_work.p, windows * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     *covered = h->rows.h_density.p;
     *n_windows = windows;

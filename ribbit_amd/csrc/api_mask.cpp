@@ -52,12 +52,12 @@ int mask_record_impl(RibbitHandle *h, const int32_t *intervals, size_t n, int32_
     const int64_t width = effective_width(length, line_width);
     const int64_t out_len = body_length(length, width);
     const int64_t nwords = length / 32 + 1;
-    if ((rc = h->rows.d_mask_text.ensure((size_t)((out_len + 15) & ~(int64_t)15), true))) return rc;
+    if ((rc = h->rows.d_work.ensure((size_t)((out_len + 15) & ~(int64_t)15), true))) return rc;
     if ((rc = h->rows.h_mask_text.ensure((size_t)out_len, true))) return rc;
     if ((rc = build_coverage(h, intervals, n))) return rc;
-    rb::launch_mask_format(h->dev_ascii_src, length, h->rows.d_mask_bits.p, nwords, mode == RIBBIT_MASK_HARD, width, out_len, h->rows.d_mask_text.p, h->stream);
+    rb::launch_mask_format(h->dev_ascii_src, length, h->rows.d_mask_bits.p, nwords, mode == RIBBIT_MASK_HARD, width, out_len, h->rows.d_work.p, h->stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h->rows.h_mask_text.p, h->rows.d_mask_text.p, (size_t)out_len, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->rows.h_mask_text.p, h->rows.d_work.p, (size_t)out_len, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     *text = h->rows.h_mask_text.p;
     *len = (size_t)out_len;

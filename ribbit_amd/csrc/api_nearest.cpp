@@ -32,19 +32,15 @@ int record_nearest_impl(RibbitHandle *h, const int32_t *queries, size_t n, const
         return RIBBIT_OK;
     }
     if ((rc = bind_device(h))) return rc;
-    if ((rc = buf.d_near.ensure(n, true))) return rc;
-    if (n_targets) {
-        if ((rc = buf.d_near_keys.ensure(4 * n_targets, true))) return rc;
-        if ((rc = buf.d_near_order.ensure(2 * n_targets, true))) return rc;
-    }
-    if ((rc = buf.d_scratch.ensure(rb::nearest_scratch_bytes((int64_t)n_targets), true))) return rc;
+    const rb::NearestLayout at = rb::nearest_layout((int64_t)n, (int64_t)n_targets);
+    if ((rc = buf.d_work.ensure(at.bytes, true))) return rc;
     // down: the queries | the targets
     const StageSegment down[2] = {{queries, 2 * n * sizeof(int32_t)}, {targets, 2 * n_targets * sizeof(int32_t)}};
     const uint8_t *d_in[2];
     if ((rc = stage_down(h, down, 2, d_in))) return rc;
     HIP_TRY(rb::launch_nearest(reinterpret_cast<const int32_t *>(d_in[0]), (int64_t)n, reinterpret_cast<const int32_t *>(d_in[1]), (int64_t)n_targets, h->length,
-                               buf.d_near_keys.p, buf.d_near_order.p, buf.d_near.p, buf.d_scratch.p, buf.d_scratch.cap, h->stream));
-    HIP_TRY(hipMemcpyAsync(buf.h_near.p, buf.d_near.p, n * sizeof(RibbitNearest), hipMemcpyDeviceToHost, h->stream));
+                               buf.d_work.p, buf.d_work.cap, at, h->stream));
+    HIP_TRY(hipMemcpyAsync(buf.h_near.p, buf.d_work.p + at.out, n * sizeof(RibbitNearest), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     for (size_t i = 0; i < n; ++i) {
         const RibbitNearest &r = buf.h_near.p[i];

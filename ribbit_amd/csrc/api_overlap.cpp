@@ -8,7 +8,7 @@
 namespace {
 
 constexpr size_t MAX_INTERVALS = (size_t)INT32_MAX;      // (the counts are int32)
-constexpr size_t TOTALS_INTS = sizeof(RibbitOverlapTotals) / sizeof(int32_t);      // the result: the totals, then (others, bases) per row
+constexpr size_t TOTALS_INTS = sizeof(RibbitOverlapTotals) / sizeof(int32_t);      // the result on its way up: the totals, then (others, bases) per row
 static_assert(sizeof(RibbitOverlapTotals) == 40 && TOTALS_INTS % 2 == 0, "the per-row values follow the totals in one buffer of ints");
 
 int check_sets(const int32_t *rows, size_t n, const int32_t *other, size_t n_other, const void *per_row, const RibbitOverlapTotals *totals) {
@@ -41,26 +41,17 @@ int record_overlap_impl(RibbitHandle *h, const int32_t *rows, size_t n, const in
         h->rec.overlap_valid = false;
         if ((rc = bind_device(h))) return rc;
         if ((rc = build_coverage(h, rows, n))) return rc;
-        const size_t words = (size_t)rb::coverage_words(length), lanes = (size_t)rb::loci_lanes(length);
-        if ((rc = buf.d_overlap_bits.ensure(words))) return rc;
-        if ((rc = buf.d_overlap_ranks.ensure(2 * lanes))) return rc;
-        if ((rc = buf.d_scratch.ensure(rb::overlap_scratch_bytes(length, (int64_t)n_other), true))) return rc;
-        if ((rc = buf.d_overlap.ensure(TOTALS_INTS + 2 * n, true))) return rc;
-        HIP_TRY(hipMemsetAsync(buf.d_overlap_bits.p, 0, words * sizeof(uint32_t), h->stream));
+        const rb::OverlapLayout at = rb::overlap_layout((int64_t)n, (int64_t)n_other, length);
+        if ((rc = buf.d_work.ensure(at.bytes, true))) return rc;
+        uint8_t *work = buf.d_work.p;
         if (n_other) {
             if ((rc = buf.h_overlap_iv.ensure(2 * n_other, true))) return rc;
-            if ((rc = buf.d_overlap_iv.ensure(2 * n_other, true))) return rc;
-            if ((rc = buf.d_overlap_keys.ensure(4 * n_other, true))) return rc;
             // (the staging buffer may still be the source of the last call's copy: that call ended in a synchronise)
             std::memcpy(buf.h_overlap_iv.p, other, 2 * n_other * sizeof(int32_t));
-            HIP_TRY(hipMemcpyAsync(buf.d_overlap_iv.p, buf.h_overlap_iv.p, 2 * n_other * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-            rb::launch_mask_coverage(buf.d_overlap_iv.p, (int64_t)n_other, length, buf.d_overlap_bits.p, h->stream);
-            HIP_TRY(hipGetLastError());
         }
-        HIP_TRY(rb::launch_overlap(buf.d_mask_bits.p, buf.d_overlap_bits.p, length, buf.d_mask_iv.p, (int64_t)n, buf.d_overlap_iv.p, (int64_t)n_other,
-                                   buf.d_overlap_ranks.p, buf.d_overlap_keys.p, reinterpret_cast<RibbitOverlapTotals *>(buf.d_overlap.p),
-                                   buf.d_overlap.p + TOTALS_INTS, buf.d_scratch.p, buf.d_scratch.cap, h->stream));
-        HIP_TRY(hipMemcpyAsync(buf.h_overlap.p, buf.d_overlap.p, (TOTALS_INTS + 2 * n) * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(rb::launch_overlap(buf.d_mask_bits.p, length, buf.d_mask_iv.p, (int64_t)n, buf.h_overlap_iv.p, (int64_t)n_other, work, buf.d_work.cap, at, h->stream));
+        HIP_TRY(hipMemcpyAsync(buf.h_overlap.p, work + at.totals, sizeof(RibbitOverlapTotals), hipMemcpyDeviceToHost, h->stream));
+        if (n) HIP_TRY(hipMemcpyAsync(buf.h_overlap.p + TOTALS_INTS, work + at.per_row, 2 * n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
         h->rec.overlap_n = n_other;
         h->rec.overlap_valid = true;

@@ -38,7 +38,7 @@ int repeat_sequences_impl(RibbitHandle *h, const char *name, const int32_t *inte
     if ((rc = h->rows.d_rep_iv.ensure(2 * m + name_words, true))) return rc;
     if ((rc = h->rows.d_rep_off.ensure(m + 1, true))) return rc;
     const size_t scratch = rb::repeat_scan_scratch_bytes((int64_t)m);
-    if ((rc = h->rows.d_scratch.ensure(scratch, true))) return rc;
+    if ((rc = h->rows.d_work.ensure(scratch, true))) return rc;
     if ((rc = h->rows.d_rep_pick.ensure(2))) return rc;
     if ((rc = h->rows.h_rep_pick.ensure(2))) return rc;
     // (the staging buffers may still be the source or target of the last call's copies: that call ended in a synchronise)
@@ -46,7 +46,7 @@ int repeat_sequences_impl(RibbitHandle *h, const char *name, const int32_t *inte
     std::memcpy(h->rows.h_rep_iv.p + 2 * m, name, name_len + 1);
     HIP_TRY(hipMemcpyAsync(h->rows.d_rep_iv.p, h->rows.h_rep_iv.p, (2 * m + name_words) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(rb::launch_repeat_offsets(h->rows.d_rep_iv.p, (int64_t)m, length, flank, (int32_t)name_len, (int64_t)budget, h->rows.d_rep_off.p,
-                                      h->rows.d_rep_pick.p, h->rows.d_scratch.p, h->rows.d_scratch.cap, h->stream));
+                                      h->rows.d_rep_pick.p, h->rows.d_work.p, h->rows.d_work.cap, h->stream));
     HIP_TRY(hipMemcpyAsync(h->rows.h_rep_pick.p, h->rows.d_rep_pick.p, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     const int64_t k = h->rows.h_rep_pick.p[0], total = h->rows.h_rep_pick.p[1];

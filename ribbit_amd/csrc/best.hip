@@ -23,28 +23,26 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
-#include "kernels.h"
+#include "row_kernels.h"
 
 namespace rb {
 
 namespace {
 
-constexpr int BEST_THREADS = 256;
-constexpr int64_t BEST_MAX_BLOCKS = 1024;      // blocks of a launch at most (four per CU); the kernels stride
 constexpr uint64_t EMPTY_KEY = ~(uint64_t)0;
 enum : uint8_t { INSIDE = 0, HEAD = 1, EMPTY = 2 };      // a sorted position: inside a segment, its first row, an empty row (the tail)
 
 // One lane per row, rows in grid-stride waves (every lane of a wave takes the same number of turns: the ballot sees whole waves).
-__global__ void __launch_bounds__(BEST_THREADS) best_keys_kernel(const int32_t *__restrict__ iv, int64_t n, int64_t length, uint64_t *__restrict__ keys,
+__global__ void __launch_bounds__(ROW_THREADS) best_keys_kernel(const int32_t *__restrict__ iv, int64_t n, int64_t length, uint64_t *__restrict__ keys,
                                                                  int32_t *__restrict__ index, uint32_t *__restrict__ count) {
     const int lane = threadIdx.x & 63;
-    const int64_t waves = (int64_t)gridDim.x * (BEST_THREADS / 64);
+    const int64_t waves = (int64_t)gridDim.x * (ROW_THREADS / 64);
     uint32_t some = 0;
-    for (int64_t base = ((int64_t)blockIdx.x * (BEST_THREADS / 64) + (threadIdx.x >> 6)) * 64; base < n; base += waves * 64) {
+    for (int64_t base = ((int64_t)blockIdx.x * (ROW_THREADS / 64) + (threadIdx.x >> 6)) * 64; base < n; base += waves * 64) {
         const int64_t i = base + lane;
         bool has = false;
         if (i < n) {
-            const int64_t s = max((int64_t)iv[2 * i], (int64_t)0), e = min((int64_t)iv[2 * i + 1], length);
+            const auto [s, e] = clip_row(iv, i, length);
             has = s < e;
             keys[i] = has ? (uint64_t)e << 32 | (uint64_t)s : EMPTY_KEY;
             index[i] = (int32_t)i;
@@ -61,9 +59,9 @@ struct StartsFromTheEnd {
     __host__ __device__ uint32_t operator()(int64_t j) const { return (uint32_t)sorted[n - 1 - j]; }
 };
 
-__global__ void __launch_bounds__(BEST_THREADS) best_prepare_kernel(const uint64_t *__restrict__ sorted, int64_t n, const uint32_t *__restrict__ rev,
+__global__ void __launch_bounds__(ROW_THREADS) best_prepare_kernel(const uint64_t *__restrict__ sorted, int64_t n, const uint32_t *__restrict__ rev,
                                                                     uint64_t *__restrict__ pw, uint8_t *__restrict__ head, uint8_t *__restrict__ take) {
-    for (int64_t k = (int64_t)blockIdx.x * BEST_THREADS + threadIdx.x; k < n; k += (int64_t)gridDim.x * BEST_THREADS) {
+    for (int64_t k = (int64_t)blockIdx.x * ROW_THREADS + threadIdx.x; k < n; k += (int64_t)gridDim.x * ROW_THREADS) {
         const uint64_t key = sorted[k];
         take[k] = 0;
         if (key == EMPTY_KEY) { head[k] = EMPTY; continue; }
@@ -78,21 +76,15 @@ __global__ void __launch_bounds__(BEST_THREADS) best_prepare_kernel(const uint64
     }
 }
 
-__device__ inline unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
-    return v;      // (lane 0's)
-}
-
 // Sorted positions in grid-stride waves, as the keys.  With f the head's position, the count c of rows before a row stands for
 // dp(c) = 0 when c == f (the segment's base) and dp[c - 1] otherwise, c - 1 being a position of the segment that the lane has
 // written.  Back: the row at j is taken exactly when dp(j + 1) > dp(j), which is the contract's w + dp(p) > dp(j).
-__global__ void __launch_bounds__(BEST_THREADS) best_dp_kernel(const uint64_t *__restrict__ pw, const uint8_t *__restrict__ head, int64_t n, int32_t *dp,
+__global__ void __launch_bounds__(ROW_THREADS) best_dp_kernel(const uint64_t *__restrict__ pw, const uint8_t *__restrict__ head, int64_t n, int32_t *dp,
                                                                uint8_t *__restrict__ take, unsigned long long *__restrict__ bases) {
     const int lane = threadIdx.x & 63;
-    const int64_t waves = (int64_t)gridDim.x * (BEST_THREADS / 64);
+    const int64_t waves = (int64_t)gridDim.x * (ROW_THREADS / 64);
     unsigned long long sum = 0;
-    for (int64_t base = ((int64_t)blockIdx.x * (BEST_THREADS / 64) + (threadIdx.x >> 6)) * 64; base < n; base += waves * 64) {
+    for (int64_t base = ((int64_t)blockIdx.x * (ROW_THREADS / 64) + (threadIdx.x >> 6)) * 64; base < n; base += waves * 64) {
         const int64_t f = base + lane;
         if (f < n && head[f] == HEAD) {
             int64_t j = f;
@@ -128,16 +120,10 @@ __global__ void __launch_bounds__(BEST_THREADS) best_dp_kernel(const uint64_t *_
     if (lane == 0 && sum) atomicAdd(bases, sum);
 }
 
-// the bits a key can have: the positions 0 .. length in its high half
-unsigned key_bits(int64_t length) {
-    unsigned bits = 1;
-    while (bits < 32 && (length >> bits)) ++bits;
-    return 32 + bits;
-}
-
+// over the bits a key can have: the positions 0 .. length in its high half
 hipError_t sort_rows(void *scratch, size_t &bytes, const uint64_t *keys, uint64_t *sorted, const int32_t *index, int32_t *order, int64_t n, int64_t length,
                      hipStream_t stream) {
-    return rocprim::radix_sort_pairs(scratch, bytes, keys, sorted, index, order, (size_t)n, 0u, key_bits(length), stream);
+    return rocprim::radix_sort_pairs(scratch, bytes, keys, sorted, index, order, (size_t)n, 0u, 32 + bits_for(length), stream);
 }
 
 hipError_t scan_starts(void *scratch, size_t &bytes, const uint64_t *sorted, uint32_t *rev, int64_t n, hipStream_t stream) {
@@ -152,23 +138,36 @@ hipError_t select_taken(void *scratch, size_t &bytes, const int32_t *order, cons
 
 }  // namespace
 
-size_t best_scratch_bytes(int64_t n, int64_t length) {
+BestLayout best_layout(int64_t n, int64_t length) {
+    const size_t rows = (size_t)n;
     size_t a = 0, b = 0, c = 0;
     (void)sort_rows(nullptr, a, nullptr, nullptr, nullptr, nullptr, n, length, 0);
     (void)scan_starts(nullptr, b, nullptr, nullptr, n, 0);
     (void)select_taken(nullptr, c, nullptr, nullptr, nullptr, nullptr, n, 0);
-    return std::max(a, std::max(b, c)) + 256;
+    BestLayout at{};
+    WorkCarver w;
+    at.keys = w.take(2 * rows * sizeof(uint64_t));
+    at.work = w.take(3 * rows * sizeof(int32_t));
+    at.flags = w.take(2 * rows);
+    at.totals = w.take(sizeof(BestTotals));
+    at.selected = w.take(rows * sizeof(int32_t));
+    w.close(at, std::max(a, std::max(b, c)));
+    return at;
 }
 
-hipError_t launch_best(const int32_t *rows, int64_t n, int64_t length, uint64_t *keys, int32_t *work, uint8_t *flags, BestTotals *totals,
-                       int32_t *selected, void *scratch, size_t scratch_bytes, hipStream_t stream) {
-    uint64_t *sorted = keys + n;
-    int32_t *index = work, *order = work + n;
-    uint32_t *rev = reinterpret_cast<uint32_t *>(work + 2 * n);
+hipError_t launch_best(const int32_t *rows, int64_t n, int64_t length, uint8_t *work, size_t work_bytes, const BestLayout &at, hipStream_t stream) {
+    if (work_bytes < at.bytes) return hipErrorInvalidValue;
+    uint64_t *keys = region<uint64_t>(work, at.keys), *sorted = keys + n;
+    int32_t *index = region<int32_t>(work, at.work), *order = index + n;
+    uint32_t *rev = reinterpret_cast<uint32_t *>(index + 2 * n);
     uint64_t *pw = keys;                            // (the unsorted keys and indices are done with after the sort)
-    int32_t *dp = work;
-    uint8_t *head = flags, *take = flags + n;
-    const dim3 grid(grid_for(n, BEST_THREADS, BEST_MAX_BLOCKS)), block(BEST_THREADS);
+    int32_t *dp = index;
+    uint8_t *head = region<uint8_t>(work, at.flags), *take = head + n;
+    BestTotals *totals = region<BestTotals>(work, at.totals);
+    int32_t *selected = region<int32_t>(work, at.selected);
+    void *scratch = work + at.scratch;
+    const size_t scratch_bytes = at.scratch_bytes;
+    const dim3 grid(grid_for(n, ROW_THREADS, ROW_MAX_BLOCKS)), block(ROW_THREADS);
     hipError_t e = hipMemsetAsync(totals, 0, sizeof(BestTotals), stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(best_keys_kernel, grid, block, 0, stream, rows, n, length, keys, index, &totals->rows);

@@ -24,14 +24,12 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
-#include "kernels.h"
+#include "row_kernels.h"
 
 namespace rb {
 
 namespace {
 
-constexpr int CLASS_THREADS = 256;
-constexpr int64_t CLASS_MAX_BLOCKS = 1024;      // blocks of a launch at most; the kernels stride
 constexpr int SHORT_MAX = 32;                   // bases one 64-bit register holds
 constexpr int KEY_BASES = 27;                   // bases the key holds behind its 10 bits of length
 constexpr int MOTIF_MAX = 1023;
@@ -41,7 +39,7 @@ struct ClassAgg {                               // what a group's rows reduce to
     uint64_t longest;                           // width << 32 | ~index
     int32_t rows, first;
 };
-static_assert(sizeof(ClassItem) == 16 && sizeof(ClassAgg) == 24, "the work buffer's layout");
+static_assert(sizeof(ClassItem) == 16 && sizeof(ClassAgg) == 24, "as ClassesLayout says");
 
 // the 2-bit codes of 8 ASCII bases (A 0, C 1, G 2, T 3), the first (lowest) byte in the highest two of 16 bits
 __device__ inline uint64_t pack8(uint64_t v) {
@@ -59,13 +57,13 @@ __device__ inline uint64_t class_key(int k, uint64_t head) { return (uint64_t)k 
 
 // Rows in grid-stride waves (every lane of a wave takes the same number of turns: the ballot sees whole waves).  pool is 8-byte
 // aligned and has 16 readable bytes behind its last motif.
-__global__ void __launch_bounds__(CLASS_THREADS) classes_short_kernel(const int32_t *__restrict__ off, const uint8_t *__restrict__ pool, int64_t n,
+__global__ void __launch_bounds__(ROW_THREADS) classes_short_kernel(const int32_t *__restrict__ off, const uint8_t *__restrict__ pool, int64_t n,
                                                                       ClassItem *__restrict__ items, uint8_t *__restrict__ classes,
                                                                       uint8_t *__restrict__ strands, int32_t *__restrict__ long_rows,
                                                                       unsigned long long *__restrict__ n_long) {
     const int lane = threadIdx.x & 63;
-    const int64_t waves = (int64_t)gridDim.x * (CLASS_THREADS / 64);
-    for (int64_t base = ((int64_t)blockIdx.x * (CLASS_THREADS / 64) + (threadIdx.x >> 6)) * 64; base < n; base += waves * 64) {
+    const int64_t waves = (int64_t)gridDim.x * (ROW_THREADS / 64);
+    for (int64_t base = ((int64_t)blockIdx.x * (ROW_THREADS / 64) + (threadIdx.x >> 6)) * 64; base < n; base += waves * 64) {
         const int64_t i = base + lane;
         bool is_long = false;
         if (i < n) {
@@ -178,9 +176,9 @@ struct ClassLess {
     }
 };
 
-__global__ void __launch_bounds__(CLASS_THREADS) classes_heads_kernel(const ClassItem *__restrict__ sorted, const uint8_t *__restrict__ classes, int64_t n,
+__global__ void __launch_bounds__(ROW_THREADS) classes_heads_kernel(const ClassItem *__restrict__ sorted, const uint8_t *__restrict__ classes, int64_t n,
                                                                       uint32_t *__restrict__ head) {
-    for (int64_t j = (int64_t)blockIdx.x * CLASS_THREADS + threadIdx.x; j < n; j += (int64_t)gridDim.x * CLASS_THREADS) {
+    for (int64_t j = (int64_t)blockIdx.x * ROW_THREADS + threadIdx.x; j < n; j += (int64_t)gridDim.x * ROW_THREADS) {
         bool first = j == 0;
         if (!first) {
             const ClassItem a = sorted[j - 1], b = sorted[j];
@@ -197,7 +195,7 @@ struct RowOfGroup {
     int64_t length;
     __host__ __device__ ClassAgg operator()(int64_t j) const {
         const uint32_t row = sorted[j].row;
-        const int64_t s = max((int64_t)iv[2 * (int64_t)row], (int64_t)0), e = min((int64_t)iv[2 * (int64_t)row + 1], length);
+        const auto [s, e] = clip_row(iv, (int64_t)row, length);
         const int64_t width = max(e - s, (int64_t)0);
         return ClassAgg{width, (uint64_t)width << 32 | (uint64_t)(uint32_t)~row, 1, (int32_t)row};
     }
@@ -209,11 +207,11 @@ struct JoinRows {
     }
 };
 
-__global__ void __launch_bounds__(CLASS_THREADS) classes_groups_kernel(const ClassAgg *__restrict__ agg, const int32_t *__restrict__ off,
+__global__ void __launch_bounds__(ROW_THREADS) classes_groups_kernel(const ClassAgg *__restrict__ agg, const int32_t *__restrict__ off,
                                                                        const unsigned long long *__restrict__ n_groups, int64_t n,
                                                                        RibbitMotifClass *__restrict__ groups) {
     const int64_t count = min((int64_t)*n_groups, n);
-    for (int64_t g = (int64_t)blockIdx.x * CLASS_THREADS + threadIdx.x; g < count; g += (int64_t)gridDim.x * CLASS_THREADS) {
+    for (int64_t g = (int64_t)blockIdx.x * ROW_THREADS + threadIdx.x; g < count; g += (int64_t)gridDim.x * ROW_THREADS) {
         const ClassAgg a = agg[g];
         groups[g] = RibbitMotifClass{a.bases, off[a.first + 1] - off[a.first], a.rows, a.first, (int32_t)~(uint32_t)a.longest};
     }
@@ -235,28 +233,44 @@ hipError_t reduce_groups(void *scratch, size_t &bytes, const uint32_t *gid, cons
 
 }  // namespace
 
-size_t classes_work_words(int64_t n) { return (size_t)(7 * n) + (size_t)(3 * n + 1) / 2; }
-
-size_t classes_scratch_bytes(int64_t n) {
+ClassesLayout classes_layout(int64_t n, size_t pool_bytes) {
+    const size_t rows = (size_t)n;
     size_t a = 0, b = 0, c = 0;
     (void)sort_items(nullptr, a, nullptr, nullptr, nullptr, n, 0);
     (void)scan_heads(nullptr, b, nullptr, nullptr, n, 0);
     (void)reduce_groups(nullptr, c, nullptr, nullptr, nullptr, 0, nullptr, nullptr, n, 0);
-    return std::max(a, std::max(b, c)) + 256;
+    ClassesLayout at{};
+    WorkCarver w;
+    at.items = w.take(2 * rows * sizeof(ClassItem));
+    at.agg = w.take(rows * sizeof(ClassAgg));
+    at.heads = w.take(2 * rows * sizeof(uint32_t));
+    at.long_rows = w.take(rows * sizeof(int32_t));
+    at.header = w.take(sizeof(ClassHeader));
+    at.groups = w.take(rows * sizeof(RibbitMotifClass));
+    at.strands = w.take(rows);
+    at.classes = w.take(pool_bytes);
+    w.close(at, std::max(a, std::max(b, c)));
+    return at;
 }
 
-hipError_t launch_classes(const int32_t *rows, const int32_t *offsets, const uint8_t *pool, int64_t n, int64_t length, uint64_t *work, ClassHeader *header,
-                          RibbitMotifClass *groups, uint8_t *strands, uint8_t *classes, void *scratch, size_t scratch_bytes, hipStream_t stream) {
-    ClassItem *items = reinterpret_cast<ClassItem *>(work), *sorted = items + n;
-    ClassAgg *agg = reinterpret_cast<ClassAgg *>(work + 4 * n);
-    uint32_t *head = reinterpret_cast<uint32_t *>(work + 7 * n), *gid = head + n;
-    int32_t *long_rows = reinterpret_cast<int32_t *>(gid + n);
-    const dim3 grid(grid_for(n, CLASS_THREADS, CLASS_MAX_BLOCKS)), block(CLASS_THREADS);
+hipError_t launch_classes(const int32_t *rows, const int32_t *offsets, const uint8_t *pool, int64_t n, int64_t length, uint8_t *work, size_t work_bytes,
+                          const ClassesLayout &at, hipStream_t stream) {
+    if (work_bytes < at.bytes) return hipErrorInvalidValue;
+    ClassItem *items = region<ClassItem>(work, at.items), *sorted = items + n;
+    ClassAgg *agg = region<ClassAgg>(work, at.agg);
+    uint32_t *head = region<uint32_t>(work, at.heads), *gid = head + n;
+    int32_t *long_rows = region<int32_t>(work, at.long_rows);
+    ClassHeader *header = region<ClassHeader>(work, at.header);
+    RibbitMotifClass *groups = region<RibbitMotifClass>(work, at.groups);
+    uint8_t *strands = region<uint8_t>(work, at.strands), *classes = region<uint8_t>(work, at.classes);
+    void *scratch = work + at.scratch;
+    const size_t scratch_bytes = at.scratch_bytes;
+    const dim3 grid(grid_for(n, ROW_THREADS, ROW_MAX_BLOCKS)), block(ROW_THREADS);
     hipError_t e = hipMemsetAsync(header, 0, sizeof(ClassHeader), stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(classes_short_kernel, grid, block, 0, stream, offsets, pool, n, items, classes, strands, long_rows, &header->long_rows);
     // (how many rows are long stays on the device: at most one block per row, and a block that finds the list empty ends at once)
-    hipLaunchKernelGGL(classes_long_kernel, dim3(grid_for(n, 1, CLASS_MAX_BLOCKS)), dim3(64), 0, stream, offsets, pool, items, classes, strands, long_rows,
+    hipLaunchKernelGGL(classes_long_kernel, dim3(grid_for(n, 1, ROW_MAX_BLOCKS)), dim3(64), 0, stream, offsets, pool, items, classes, strands, long_rows,
                        &header->long_rows);
     size_t bytes = scratch_bytes;
     if ((e = sort_items(scratch, bytes, items, sorted, classes, n, stream)) != hipSuccess) return e;

@@ -16,21 +16,19 @@
 //                 most 7) + the popc of the position's word below it; the 13 values are differences
 //   windows:      one lane per window: the prefixes at both of its ends, five differences
 // brk is 1 for every position >= L: no prefix is taken beyond L, and the one at L counts only the bits below it.  p = L lies in
-// a word of every plane and of the bitmap (L / 32 + 1 words hold positions).  The kernels stride beyond COMP_MAX_BLOCKS blocks.
+// a word of every plane and of the bitmap (L / 32 + 1 words hold positions).  The kernels stride beyond ROW_MAX_BLOCKS blocks.
 #include <cstring>
 
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
 #include "bit_blocks.h"
-#include "kernels.h"
+#include "row_kernels.h"
 
 namespace rb {
 
 namespace {
 
-constexpr int COMP_THREADS = 256;
-constexpr int64_t COMP_MAX_BLOCKS = 1024;      // blocks of a launch at most, as the other row outputs: the kernels stride
 static_assert(COMP_BLOCK_WORDS == 8 && COMP_BLOCK_WORDS == WORDS_PER_LANE && COMP_BLOCK_WORDS == LOCI_LANE_WORDS,
               "a lane loads its words as two dwordx4, and a block is a lane's words of the scan tile and of the coverage bitmap");
 static_assert(TILE_WORDS % COMP_BLOCK_WORDS == 0 && LEAD_WORDS % 4 == 0, "the blocks tile the planes, 16-byte aligned");
@@ -48,9 +46,9 @@ __device__ inline void add_word(BaseSums &s, uint32_t hi, uint32_t lo, uint32_t 
     s.other += (uint32_t)__popc(brk);
 }
 
-__global__ void __launch_bounds__(COMP_THREADS) composition_counts_kernel(const uint32_t *__restrict__ hi, const uint32_t *__restrict__ lo,
+__global__ void __launch_bounds__(ROW_THREADS) composition_counts_kernel(const uint32_t *__restrict__ hi, const uint32_t *__restrict__ lo,
                                                                           const uint32_t *__restrict__ brk, int64_t blocks, BaseSums *__restrict__ sums) {
-    for (int64_t t = (int64_t)blockIdx.x * COMP_THREADS + threadIdx.x; t < blocks; t += (int64_t)gridDim.x * COMP_THREADS) {
+    for (int64_t t = (int64_t)blockIdx.x * ROW_THREADS + threadIdx.x; t < blocks; t += (int64_t)gridDim.x * ROW_THREADS) {
         uint32_t h[COMP_BLOCK_WORDS], l[COMP_BLOCK_WORDS], b[COMP_BLOCK_WORDS];
         load_block(hi, t, h);
         load_block(lo, t, l);
@@ -62,8 +60,8 @@ __global__ void __launch_bounds__(COMP_THREADS) composition_counts_kernel(const 
     }
 }
 
-__global__ void __launch_bounds__(COMP_THREADS) composition_cover_counts_kernel(const uint32_t *__restrict__ bits, int64_t blocks, uint32_t *__restrict__ sums) {
-    for (int64_t t = (int64_t)blockIdx.x * COMP_THREADS + threadIdx.x; t < blocks; t += (int64_t)gridDim.x * COMP_THREADS) {
+__global__ void __launch_bounds__(ROW_THREADS) composition_cover_counts_kernel(const uint32_t *__restrict__ bits, int64_t blocks, uint32_t *__restrict__ sums) {
+    for (int64_t t = (int64_t)blockIdx.x * ROW_THREADS + threadIdx.x; t < blocks; t += (int64_t)gridDim.x * ROW_THREADS) {
         uint32_t w[COMP_BLOCK_WORDS];
         load_block(bits, t, w);
         uint32_t s = 0;
@@ -88,11 +86,11 @@ __device__ inline uint32_t covered_before(const uint32_t *__restrict__ bits, con
     return rank[block_of(p)] + ones_before_in_block(bits, p);
 }
 
-__global__ void __launch_bounds__(COMP_THREADS) composition_rows_kernel(const int32_t *__restrict__ rows, int64_t n, int32_t flank, DevicePlanes pl,
+__global__ void __launch_bounds__(ROW_THREADS) composition_rows_kernel(const int32_t *__restrict__ rows, int64_t n, int32_t flank, DevicePlanes pl,
                                                                         const BaseSums *__restrict__ prefix, const uint32_t *__restrict__ bits,
                                                                         const uint32_t *__restrict__ rank, RibbitRowComposition *__restrict__ out) {
     const int64_t length = pl.length;
-    for (int64_t i = (int64_t)blockIdx.x * COMP_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * COMP_THREADS) {
+    for (int64_t i = (int64_t)blockIdx.x * ROW_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * ROW_THREADS) {
         const int64_t s = min(max((int64_t)rows[2 * i], (int64_t)0), length), e = min(max((int64_t)rows[2 * i + 1], s), length);
         const int64_t lo = max(s - (int64_t)flank, (int64_t)0), hi = min(e + (int64_t)flank, length);
         const BaseSums at_lo = bases_before(pl, prefix, lo), at_s = bases_before(pl, prefix, s), at_e = bases_before(pl, prefix, e),
@@ -117,9 +115,9 @@ __global__ void __launch_bounds__(COMP_THREADS) composition_rows_kernel(const in
     }
 }
 
-__global__ void __launch_bounds__(COMP_THREADS) composition_windows_kernel(DevicePlanes pl, const BaseSums *__restrict__ prefix, int64_t window, int64_t n_windows,
+__global__ void __launch_bounds__(ROW_THREADS) composition_windows_kernel(DevicePlanes pl, const BaseSums *__restrict__ prefix, int64_t window, int64_t n_windows,
                                                                            RibbitBaseCounts *__restrict__ out) {
-    for (int64_t k = (int64_t)blockIdx.x * COMP_THREADS + threadIdx.x; k < n_windows; k += (int64_t)gridDim.x * COMP_THREADS) {
+    for (int64_t k = (int64_t)blockIdx.x * ROW_THREADS + threadIdx.x; k < n_windows; k += (int64_t)gridDim.x * ROW_THREADS) {
         const int64_t from = k * window, to = min(from + window, pl.length);      // (k < ceil(length / window): from < length)
         const BaseSums a = bases_before(pl, prefix, from), b = bases_before(pl, prefix, to);
         RibbitBaseCounts r;
@@ -140,40 +138,66 @@ hipError_t scan_cover(void *scratch, size_t &bytes, const uint32_t *sums, uint32
     return rocprim::exclusive_scan(scratch, bytes, sums, rank, (uint32_t)0, (size_t)blocks, rocprim::plus<uint32_t>(), stream);
 }
 
-}  // namespace
-
-size_t composition_scratch_bytes(int64_t length) {
+// cover_blocks: the blocks of the rows' coverage (0: the windows have none); out_bytes: the result.  Either call may have to make
+// the record's prefix first, so the scratch serves that scan too.
+CompositionLayout composition_layout(size_t cover_blocks, size_t out_bytes, int64_t length) {
     size_t a = 0, b = 0;
     (void)scan_sums(nullptr, a, nullptr, nullptr, loci_lanes(length), 0);
-    (void)scan_cover(nullptr, b, nullptr, nullptr, loci_lanes(length), 0);
-    return std::max(a, b) + 256;
+    if (cover_blocks) (void)scan_cover(nullptr, b, nullptr, nullptr, loci_lanes(length), 0);
+    CompositionLayout at{};
+    WorkCarver w;
+    at.cover = w.take(2 * cover_blocks * sizeof(uint32_t));
+    at.out = w.take(out_bytes);
+    w.close(at, std::max(a, b));
+    return at;
 }
 
-hipError_t launch_composition_prefix(const DevicePlanes &pl, BaseSums *sums, BaseSums *prefix, void *scratch, size_t scratch_bytes, hipStream_t stream) {
+}  // namespace
+
+CompositionLayout composition_rows_layout(int64_t n, int64_t length) {
+    return composition_layout((size_t)loci_lanes(length), (size_t)n * sizeof(RibbitRowComposition), length);
+}
+
+CompositionLayout composition_windows_layout(int64_t n_windows, int64_t length) {
+    return composition_layout(0, (size_t)n_windows * sizeof(RibbitBaseCounts), length);
+}
+
+hipError_t launch_composition_prefix(const DevicePlanes &pl, BaseSums *sums, uint8_t *work, size_t work_bytes, const CompositionLayout &at, hipStream_t stream) {
+    if (work_bytes < at.bytes) return hipErrorInvalidValue;
     const int64_t blocks = loci_lanes(pl.length);
-    hipLaunchKernelGGL(composition_counts_kernel, dim3(grid_for(blocks, COMP_THREADS, COMP_MAX_BLOCKS)), dim3(COMP_THREADS), 0, stream, pl.hi, pl.lo, pl.brk, blocks,
+    BaseSums *prefix = sums + blocks;
+    void *scratch = work + at.scratch;
+    hipLaunchKernelGGL(composition_counts_kernel, dim3(grid_for(blocks, ROW_THREADS, ROW_MAX_BLOCKS)), dim3(ROW_THREADS), 0, stream, pl.hi, pl.lo, pl.brk, blocks,
                        sums);
-    size_t bytes = scratch_bytes;
+    size_t bytes = at.scratch_bytes;
     const hipError_t e = scan_sums(scratch, bytes, sums, prefix, blocks, stream);
     return e != hipSuccess ? e : hipGetLastError();
 }
 
-hipError_t launch_composition_rows(const DevicePlanes &pl, const BaseSums *prefix, const uint32_t *bits, uint32_t *cover_sums, uint32_t *cover_rank,
-                                   const int32_t *rows, int64_t n, int32_t flank, RibbitRowComposition *out, void *scratch, size_t scratch_bytes,
-                                   hipStream_t stream) {
+hipError_t launch_composition_rows(const DevicePlanes &pl, const BaseSums *sums, const uint32_t *bits, const int32_t *rows, int64_t n, int32_t flank, uint8_t *work,
+                                   size_t work_bytes, const CompositionLayout &at, hipStream_t stream) {
+    if (work_bytes < at.bytes) return hipErrorInvalidValue;
     const int64_t blocks = loci_lanes(pl.length);
-    hipLaunchKernelGGL(composition_cover_counts_kernel, dim3(grid_for(blocks, COMP_THREADS, COMP_MAX_BLOCKS)), dim3(COMP_THREADS), 0, stream, bits, blocks,
+    const BaseSums *prefix = sums + blocks;
+    uint32_t *cover_sums = region<uint32_t>(work, at.cover), *cover_rank = cover_sums + blocks;
+    RibbitRowComposition *out = region<RibbitRowComposition>(work, at.out);
+    void *scratch = work + at.scratch;
+    hipLaunchKernelGGL(composition_cover_counts_kernel, dim3(grid_for(blocks, ROW_THREADS, ROW_MAX_BLOCKS)), dim3(ROW_THREADS), 0, stream, bits, blocks,
                        cover_sums);
-    size_t bytes = scratch_bytes;
+    size_t bytes = at.scratch_bytes;
     const hipError_t e = scan_cover(scratch, bytes, cover_sums, cover_rank, blocks, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(composition_rows_kernel, dim3(grid_for(n, COMP_THREADS, COMP_MAX_BLOCKS)), dim3(COMP_THREADS), 0, stream, rows, n, flank, pl, prefix, bits,
+    hipLaunchKernelGGL(composition_rows_kernel, dim3(grid_for(n, ROW_THREADS, ROW_MAX_BLOCKS)), dim3(ROW_THREADS), 0, stream, rows, n, flank, pl, prefix, bits,
                        cover_rank, out);
     return hipGetLastError();
 }
 
-hipError_t launch_composition_windows(const DevicePlanes &pl, const BaseSums *prefix, int64_t window, int64_t n_windows, RibbitBaseCounts *out, hipStream_t stream) {
-    hipLaunchKernelGGL(composition_windows_kernel, dim3(grid_for(n_windows, COMP_THREADS, COMP_MAX_BLOCKS)), dim3(COMP_THREADS), 0, stream, pl, prefix, window,
+hipError_t launch_composition_windows(const DevicePlanes &pl, const BaseSums *sums, int64_t window, int64_t n_windows, uint8_t *work, size_t work_bytes,
+                                      const CompositionLayout &at, hipStream_t stream) {
+    if (work_bytes < at.bytes) return hipErrorInvalidValue;
+    const BaseSums *prefix = sums + loci_lanes(pl.length);
+    RibbitBaseCounts *out = region<RibbitBaseCounts>(work, at.out);
+    hipLaunchKernelGGL(composition_windows_kernel, dim3(grid_for(n_windows, ROW_THREADS, ROW_MAX_BLOCKS)), dim3(ROW_THREADS), 0, stream, pl, prefix, window,
                        n_windows, out);
     return hipGetLastError();
 }

@@ -24,21 +24,19 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
-#include "kernels.h"
+#include "row_kernels.h"
 
 namespace rb {
 
 namespace {
 
-constexpr int COMPOUND_THREADS = 256;
-constexpr int64_t COMPOUND_MAX_BLOCKS = 1024;      // blocks of a launch at most (four per CU); the kernels stride
 constexpr uint64_t EMPTY_KEY = ~(uint64_t)0;
 enum : uint8_t { HEAD = 1, SWITCH = 2, OVERLAP = 4 };
 
-__global__ void __launch_bounds__(COMPOUND_THREADS) compound_keys_kernel(const int32_t *__restrict__ iv, int64_t n, int64_t length, uint64_t *__restrict__ keys,
+__global__ void __launch_bounds__(ROW_THREADS) compound_keys_kernel(const int32_t *__restrict__ iv, int64_t n, int64_t length, uint64_t *__restrict__ keys,
                                                                          int32_t *__restrict__ index) {
-    for (int64_t i = (int64_t)blockIdx.x * COMPOUND_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * COMPOUND_THREADS) {
-        const int64_t s = max((int64_t)iv[2 * i], (int64_t)0), e = min((int64_t)iv[2 * i + 1], length);
+    for (int64_t i = (int64_t)blockIdx.x * ROW_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * ROW_THREADS) {
+        const auto [s, e] = clip_row(iv, i, length);
         keys[i] = s < e ? (uint64_t)s << 32 | (uint64_t)e : EMPTY_KEY;
         index[i] = (int32_t)i;
     }
@@ -53,10 +51,10 @@ struct EndsInOrder {
     }
 };
 
-__global__ void __launch_bounds__(COMPOUND_THREADS) compound_flags_kernel(const uint64_t *__restrict__ sorted, const int32_t *__restrict__ order,
+__global__ void __launch_bounds__(ROW_THREADS) compound_flags_kernel(const uint64_t *__restrict__ sorted, const int32_t *__restrict__ order,
                                                                           const uint32_t *__restrict__ reach, const int32_t *__restrict__ labels, int64_t n,
                                                                           int32_t gap, uint8_t *__restrict__ flags) {
-    for (int64_t k = (int64_t)blockIdx.x * COMPOUND_THREADS + threadIdx.x; k < n; k += (int64_t)gridDim.x * COMPOUND_THREADS) {
+    for (int64_t k = (int64_t)blockIdx.x * ROW_THREADS + threadIdx.x; k < n; k += (int64_t)gridDim.x * ROW_THREADS) {
         const uint64_t key = sorted[k];
         uint8_t f = 0;
         if (key != EMPTY_KEY) {
@@ -77,11 +75,11 @@ struct HeadBits {
     __host__ __device__ uint32_t operator()(int64_t k) const { return flags[k] & HEAD; }
 };
 
-__global__ void __launch_bounds__(COMPOUND_THREADS) compound_keys2_kernel(const uint64_t *__restrict__ sorted, const int32_t *__restrict__ order,
+__global__ void __launch_bounds__(ROW_THREADS) compound_keys2_kernel(const uint64_t *__restrict__ sorted, const int32_t *__restrict__ order,
                                                                           const uint32_t *__restrict__ chain, const uint8_t *__restrict__ flags,
                                                                           const int32_t *__restrict__ labels, int64_t n, uint64_t *__restrict__ keys2,
                                                                           int32_t *__restrict__ first, CompoundTotals *__restrict__ totals) {
-    for (int64_t k = (int64_t)blockIdx.x * COMPOUND_THREADS + threadIdx.x; k < n; k += (int64_t)gridDim.x * COMPOUND_THREADS) {
+    for (int64_t k = (int64_t)blockIdx.x * ROW_THREADS + threadIdx.x; k < n; k += (int64_t)gridDim.x * ROW_THREADS) {
         if (sorted[k] == EMPTY_KEY) { keys2[k] = EMPTY_KEY; continue; }
         const uint32_t c = chain[k];                     // 1 .. n
         keys2[k] = (uint64_t)c << 32 | (uint64_t)((uint32_t)labels[order[k]] ^ 0x80000000u);
@@ -114,12 +112,12 @@ struct AddSums {
     }
 };
 
-__global__ void __launch_bounds__(COMPOUND_THREADS) compound_finish_kernel(const uint64_t *__restrict__ sorted, const uint32_t *__restrict__ reach,
+__global__ void __launch_bounds__(ROW_THREADS) compound_finish_kernel(const uint64_t *__restrict__ sorted, const uint32_t *__restrict__ reach,
                                                                            const int32_t *__restrict__ first, const CompoundSums *__restrict__ sums,
                                                                            const CompoundTotals *__restrict__ totals, int64_t n,
                                                                            RibbitCompound *__restrict__ compounds) {
     const int64_t count = min((int64_t)totals->chains, n);
-    for (int64_t c = (int64_t)blockIdx.x * COMPOUND_THREADS + threadIdx.x; c < count; c += (int64_t)gridDim.x * COMPOUND_THREADS) {
+    for (int64_t c = (int64_t)blockIdx.x * ROW_THREADS + threadIdx.x; c < count; c += (int64_t)gridDim.x * ROW_THREADS) {
         const int64_t f = first[c], l = first[c + 1];      // the chain's positions are [f, l)
         if (f < 0 || l <= f || l > n) { compounds[c] = RibbitCompound{0, 0, 0, 0, 0, 0, 0, -1, 0}; continue; }      // (never: the host refuses it)
         const CompoundSums to = sums[l - 1];
@@ -128,13 +126,6 @@ __global__ void __launch_bounds__(COMPOUND_THREADS) compound_finish_kernel(const
                                       (int32_t)(to.classes - from.classes), (int32_t)(to.switches - from.switches), (int32_t)(to.overlaps - from.overlaps),
                                       (int32_t)f, 0};
     }
-}
-
-// the least b >= 1 with v < 2^b, at most 32
-unsigned bits_for(int64_t v) {
-    unsigned bits = 1;
-    while (bits < 32 && (v >> bits)) ++bits;
-    return bits;
 }
 
 // the bits a key can have: the starts 0 .. length - 1 in its high half, below the all-ones of an empty row
@@ -167,24 +158,42 @@ hipError_t scan_sums(void *scratch, size_t &bytes, const uint64_t *sorted, const
 
 }  // namespace
 
-size_t compound_scratch_bytes(int64_t n, int64_t length) {
+CompoundLayout compound_layout(int64_t n, int64_t length) {
+    const size_t rows = (size_t)n;
     size_t a = 0, b = 0, c = 0, d = 0, e = 0;
     (void)sort_rows(nullptr, a, nullptr, nullptr, nullptr, nullptr, n, length, 0);
     (void)scan_reach(nullptr, b, nullptr, nullptr, n, 0);
     (void)scan_heads(nullptr, c, nullptr, nullptr, n, 0);
     (void)sort_labels(nullptr, d, nullptr, nullptr, n, 0);
     (void)scan_sums(nullptr, e, nullptr, nullptr, nullptr, nullptr, n, 0);
-    return std::max(std::max(a, b), std::max(c, std::max(d, e))) + 256;
+    CompoundLayout at{};
+    WorkCarver w;
+    at.keys = w.take(3 * rows * sizeof(uint64_t));
+    at.work = w.take((3 * rows + 1) * sizeof(int32_t));
+    at.sums = w.take(rows * sizeof(CompoundSums));
+    at.flags = w.take(rows);
+    at.totals = w.take(sizeof(CompoundTotals));
+    at.compounds = w.take(rows * sizeof(RibbitCompound));
+    at.members = w.take(rows * sizeof(int32_t));
+    w.close(at, std::max(std::max(a, b), std::max(c, std::max(d, e))));
+    return at;
 }
 
-hipError_t launch_compounds(const int32_t *rows, const int32_t *labels, int64_t n, int64_t length, int32_t gap, uint64_t *keys, int32_t *work,
-                            CompoundSums *sums, uint8_t *flags, CompoundTotals *totals, int32_t *members, RibbitCompound *compounds, void *scratch,
-                            size_t scratch_bytes, hipStream_t stream) {
-    uint64_t *sorted = keys + n, *sorted2 = keys + 2 * n;
+hipError_t launch_compounds(const int32_t *rows, const int32_t *labels, int64_t n, int64_t length, int32_t gap, uint8_t *work, size_t work_bytes,
+                            const CompoundLayout &at, hipStream_t stream) {
+    if (work_bytes < at.bytes) return hipErrorInvalidValue;
+    uint64_t *keys = region<uint64_t>(work, at.keys), *sorted = keys + n, *sorted2 = keys + 2 * n;
     uint64_t *keys2 = keys;                         // (the unsorted keys and indices are done with after the first sort)
-    int32_t *index = work, *first = work + 2 * n;
-    uint32_t *chain = reinterpret_cast<uint32_t *>(work), *reach = reinterpret_cast<uint32_t *>(work + n);
-    const dim3 grid(grid_for(n, COMPOUND_THREADS, COMPOUND_MAX_BLOCKS)), block(COMPOUND_THREADS);
+    int32_t *index = region<int32_t>(work, at.work), *first = index + 2 * n;
+    uint32_t *chain = reinterpret_cast<uint32_t *>(index), *reach = chain + n;
+    CompoundSums *sums = region<CompoundSums>(work, at.sums);
+    uint8_t *flags = region<uint8_t>(work, at.flags);
+    CompoundTotals *totals = region<CompoundTotals>(work, at.totals);
+    RibbitCompound *compounds = region<RibbitCompound>(work, at.compounds);
+    int32_t *members = region<int32_t>(work, at.members);
+    void *scratch = work + at.scratch;
+    const size_t scratch_bytes = at.scratch_bytes;
+    const dim3 grid(grid_for(n, ROW_THREADS, ROW_MAX_BLOCKS)), block(ROW_THREADS);
     hipError_t e = hipMemsetAsync(totals, 0, sizeof(CompoundTotals), stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(compound_keys_kernel, grid, block, 0, stream, rows, n, length, keys, index);

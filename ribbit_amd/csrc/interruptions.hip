@@ -38,18 +38,16 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
-#include "kernels.h"
+#include "row_kernels.h"
 
 namespace rb {
 
 namespace {
 
-constexpr int INT_THREADS = 256;
-constexpr int64_t INT_MAX_BLOCKS = 1024;      // blocks of a launch at most (four per CU); the kernels stride
 constexpr uint32_t NONE = 0xffffffffu;
 constexpr uint32_t MAX_LEN = 0x7fffffffu;
 enum : uint32_t { MATCH = 0, SUBST = 1, INS = 2, DEL = 3, DIGIT = 4, OTHER = 5 };
-static_assert(sizeof(InterruptionTotals) == 32 && sizeof(InterruptionSums) == 48 && sizeof(InterruptionBest) == 16, "carved on 16-byte boundaries");
+static_assert(sizeof(InterruptionTotals) == 32 && sizeof(InterruptionSums) == 48 && sizeof(InterruptionBest) == 16, "as InterruptionLayout says");
 static_assert(sizeof(RibbitInterruption) == 32 && sizeof(RibbitRowPurity) == 32, "as include/ribbit_hip.h says");
 
 __device__ __forceinline__ uint32_t kind_of_byte(uint32_t c) {
@@ -95,24 +93,24 @@ __device__ __forceinline__ uint32_t walk_chunk(const uint4 *__restrict__ pool, i
     return found;
 }
 
-__global__ void __launch_bounds__(INT_THREADS) int_count_kernel(const uint4 *__restrict__ pool, int64_t chunks, int64_t pool_bytes, uint32_t *__restrict__ counts,
+__global__ void __launch_bounds__(ROW_THREADS) int_count_kernel(const uint4 *__restrict__ pool, int64_t chunks, int64_t pool_bytes, uint32_t *__restrict__ counts,
                                                                 InterruptionTotals *__restrict__ totals) {
-    for (int64_t c = (int64_t)blockIdx.x * INT_THREADS + threadIdx.x; c <= chunks; c += (int64_t)gridDim.x * INT_THREADS)
+    for (int64_t c = (int64_t)blockIdx.x * ROW_THREADS + threadIdx.x; c <= chunks; c += (int64_t)gridDim.x * ROW_THREADS)
         counts[c] = c < chunks ? walk_chunk<false>(pool, c, pool_bytes, nullptr, 0, 0, &totals->bad_at) : 0u;
 }
 
-__global__ void __launch_bounds__(INT_THREADS) int_emit_kernel(const uint4 *__restrict__ pool, int64_t chunks, int64_t pool_bytes, const uint32_t *__restrict__ prefix,
+__global__ void __launch_bounds__(ROW_THREADS) int_emit_kernel(const uint4 *__restrict__ pool, int64_t chunks, int64_t pool_bytes, const uint32_t *__restrict__ prefix,
                                                                uint64_t *__restrict__ ops, uint32_t cap) {
-    for (int64_t c = (int64_t)blockIdx.x * INT_THREADS + threadIdx.x; c < chunks; c += (int64_t)gridDim.x * INT_THREADS)
+    for (int64_t c = (int64_t)blockIdx.x * ROW_THREADS + threadIdx.x; c < chunks; c += (int64_t)gridDim.x * ROW_THREADS)
         (void)walk_chunk<true>(pool, c, pool_bytes, ops, prefix[c], cap, nullptr);
 }
 
 // first_op[i] = the ops before byte offsets[i], i = 0 .. n; a non-empty row's first op gets the row's head mark
-__global__ void __launch_bounds__(INT_THREADS) int_row_heads_kernel(const uint8_t *__restrict__ pool, const int32_t *__restrict__ offsets, int64_t n, int64_t pool_bytes,
+__global__ void __launch_bounds__(ROW_THREADS) int_row_heads_kernel(const uint8_t *__restrict__ pool, const int32_t *__restrict__ offsets, int64_t n, int64_t pool_bytes,
                                                                     const uint32_t *__restrict__ prefix, uint32_t *__restrict__ first_op, uint32_t *__restrict__ op_row,
                                                                     uint32_t cap, InterruptionTotals *__restrict__ totals) {
     const uint32_t ops = min(prefix[(pool_bytes + 15) / 16], cap);
-    for (int64_t i = (int64_t)blockIdx.x * INT_THREADS + threadIdx.x; i <= n; i += (int64_t)gridDim.x * INT_THREADS) {
+    for (int64_t i = (int64_t)blockIdx.x * ROW_THREADS + threadIdx.x; i <= n; i += (int64_t)gridDim.x * ROW_THREADS) {
         const int64_t at = min(max((int64_t)offsets[i], (int64_t)0), pool_bytes);      // (the host has checked: 0 .. pool_bytes, ascending)
         const uint4 chunk = reinterpret_cast<const uint4 *>(pool)[at >> 4];              // (a zero chunk follows the pool's last)
         const uint32_t w[4] = {chunk.x, chunk.y, chunk.z, chunk.w};
@@ -163,11 +161,11 @@ __device__ __forceinline__ InterruptionSums sums_before(const InterruptionSums *
 }
 __device__ __forceinline__ unsigned long long query_of(const InterruptionSums &s) { return s.match + s.x + s.ins; }
 
-__global__ void __launch_bounds__(INT_THREADS) int_run_heads_kernel(const uint64_t *__restrict__ ops, const uint32_t *__restrict__ op_row,
+__global__ void __launch_bounds__(ROW_THREADS) int_run_heads_kernel(const uint64_t *__restrict__ ops, const uint32_t *__restrict__ op_row,
                                                                     const InterruptionSums *__restrict__ sums, uint32_t *__restrict__ run_head,
                                                                     InterruptionTotals *__restrict__ totals) {
     const int64_t count = totals->ops;
-    for (int64_t j = (int64_t)blockIdx.x * INT_THREADS + threadIdx.x; j < count; j += (int64_t)gridDim.x * INT_THREADS) {
+    for (int64_t j = (int64_t)blockIdx.x * ROW_THREADS + threadIdx.x; j < count; j += (int64_t)gridDim.x * ROW_THREADS) {
         bool run, site;
         heads_of_op(ops, op_row, j, &run, &site);
         const InterruptionSums s = sums[j];
@@ -182,14 +180,14 @@ __global__ void __launch_bounds__(INT_THREADS) int_run_heads_kernel(const uint64
 
 __device__ __forceinline__ int32_t clamp_int32(long long v) { return (int32_t)min(max(v, (long long)INT32_MIN), (long long)INT32_MAX); }
 
-__global__ void __launch_bounds__(INT_THREADS) int_runs_kernel(const int32_t *__restrict__ iv, const int32_t *__restrict__ offsets, int64_t n, int64_t length,
+__global__ void __launch_bounds__(ROW_THREADS) int_runs_kernel(const int32_t *__restrict__ iv, const int32_t *__restrict__ offsets, int64_t n, int64_t length,
                                                                const uint64_t *__restrict__ ops, const uint32_t *__restrict__ op_row,
                                                                const uint32_t *__restrict__ first_op, const InterruptionSums *__restrict__ sums,
                                                                const uint32_t *__restrict__ run_head, const InterruptionTotals *__restrict__ totals,
                                                                InterruptionBest *__restrict__ best, RibbitInterruption *__restrict__ sites,
                                                                uint32_t *__restrict__ width, int32_t *__restrict__ source) {
     const int64_t count = totals->runs, n_ops = totals->ops;
-    for (int64_t r = (int64_t)blockIdx.x * INT_THREADS + threadIdx.x; r < count; r += (int64_t)gridDim.x * INT_THREADS) {
+    for (int64_t r = (int64_t)blockIdx.x * ROW_THREADS + threadIdx.x; r < count; r += (int64_t)gridDim.x * ROW_THREADS) {
         // (on a pool whose grammar is bad the indices below are still indices: the host refuses the result)
         const int64_t head = min((int64_t)run_head[r], n_ops - 1), next = min(max((int64_t)run_head[r + 1], head + 1), n_ops);
         const InterruptionSums from = sums_before(sums, head), to = sums[next - 1];
@@ -235,19 +233,19 @@ struct WidthOfSite {
     __host__ __device__ unsigned long long operator()(int64_t id) const { return id < (int64_t)totals->sites ? width[id] : 0ull; }
 };
 
-__global__ void __launch_bounds__(INT_THREADS) int_offsets_kernel(const unsigned long long *__restrict__ offsets64, int32_t *__restrict__ offsets32,
+__global__ void __launch_bounds__(ROW_THREADS) int_offsets_kernel(const unsigned long long *__restrict__ offsets64, int32_t *__restrict__ offsets32,
                                                                   InterruptionTotals *__restrict__ totals) {
     const int64_t count = totals->sites;
-    for (int64_t id = (int64_t)blockIdx.x * INT_THREADS + threadIdx.x; id <= count; id += (int64_t)gridDim.x * INT_THREADS) {
+    for (int64_t id = (int64_t)blockIdx.x * ROW_THREADS + threadIdx.x; id <= count; id += (int64_t)gridDim.x * ROW_THREADS) {
         offsets32[id] = (int32_t)min(offsets64[id], (unsigned long long)INT32_MAX);      // (more than INT32_MAX: the host refuses the total)
         if (id == count) totals->observed = offsets64[id];
     }
 }
 
-__global__ void __launch_bounds__(INT_THREADS) int_finish_kernel(const int32_t *__restrict__ iv, int64_t n, const uint32_t *__restrict__ first_op,
+__global__ void __launch_bounds__(ROW_THREADS) int_finish_kernel(const int32_t *__restrict__ iv, int64_t n, const uint32_t *__restrict__ first_op,
                                                                  const InterruptionSums *__restrict__ sums, const InterruptionBest *__restrict__ best,
                                                                  RibbitRowPurity *__restrict__ rows, InterruptionTotals *__restrict__ totals) {
-    for (int64_t i = (int64_t)blockIdx.x * INT_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * INT_THREADS) {
+    for (int64_t i = (int64_t)blockIdx.x * ROW_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * ROW_THREADS) {
         const int64_t f = first_op[i], l = max((int64_t)first_op[i + 1], f);
         const InterruptionSums base = sums_before(sums, f), to = sums_before(sums, l);
         const long long s = iv[2 * i];
@@ -277,16 +275,16 @@ __device__ __forceinline__ int32_t site_of_byte(const int32_t *__restrict__ offs
 }
 
 // span_site[b] = the interruption that holds observed byte b * SPAN (the last byte for b = spans)
-__global__ void __launch_bounds__(INT_THREADS) int_spans_kernel(const int32_t *__restrict__ offsets, int32_t sites, int64_t total, int64_t spans,
+__global__ void __launch_bounds__(ROW_THREADS) int_spans_kernel(const int32_t *__restrict__ offsets, int32_t sites, int64_t total, int64_t spans,
                                                                 int32_t *__restrict__ span_site) {
-    const int64_t b = (int64_t)blockIdx.x * INT_THREADS + threadIdx.x;
+    const int64_t b = (int64_t)blockIdx.x * ROW_THREADS + threadIdx.x;
     if (b > spans) return;
     span_site[b] = site_of_byte(offsets, 0, sites - 1, (int32_t)min(b * INTERRUPTION_SPAN, total - 1));
 }
 
-__global__ void __launch_bounds__(INT_THREADS) int_gather_kernel(const uint8_t *__restrict__ ascii, const int32_t *__restrict__ offsets, const int32_t *__restrict__ source,
+__global__ void __launch_bounds__(ROW_THREADS) int_gather_kernel(const uint8_t *__restrict__ ascii, const int32_t *__restrict__ offsets, const int32_t *__restrict__ source,
                                                                  const int32_t *__restrict__ span_site, int32_t sites, int64_t total, uint4 *__restrict__ out) {
-    static_assert(INTERRUPTION_SPAN == 16 * INT_THREADS, "a workgroup gathers one span, 16 bytes per lane");
+    static_assert(INTERRUPTION_SPAN == 16 * ROW_THREADS, "a workgroup gathers one span, 16 bytes per lane");
     const int64_t spans = (total + INTERRUPTION_SPAN - 1) / INTERRUPTION_SPAN;
     for (int64_t b = blockIdx.x; b < spans; b += gridDim.x) {
         const int64_t o = b * INTERRUPTION_SPAN + 16 * (int64_t)threadIdx.x;
@@ -327,61 +325,56 @@ hipError_t scan_widths(void *scratch, size_t &bytes, const uint32_t *width, cons
                                    0ull, cap, rocprim::plus<unsigned long long>(), stream);
 }
 
-inline size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 }  // namespace
 
 InterruptionLayout interruptions_layout(int64_t n, size_t pool_bytes) {
-    const size_t cap = interruptions_op_cap(pool_bytes), chunks = (pool_bytes + 15) / 16;
-    InterruptionLayout at{};
-    size_t end = 0;
-    auto take = [&](size_t bytes) { const size_t from = end; end += round16(bytes); return from; };
-    at.counts = take((chunks + 1) * sizeof(uint32_t));
-    at.ops = take(cap * sizeof(uint64_t));
-    at.op_row = take(cap * sizeof(uint32_t));
-    at.first_op = take(((size_t)n + 1) * sizeof(uint32_t));
-    at.sums = take(cap * sizeof(InterruptionSums));
-    at.run_head = take((cap + 1) * sizeof(uint32_t));
-    at.best = take(2 * cap * sizeof(InterruptionBest));      // the runs' keys | the keys scanned
-    at.width = take((cap + 1) * sizeof(uint32_t));
-    at.source = take(cap * sizeof(int32_t));
-    at.offsets64 = take((cap + 1) * sizeof(unsigned long long));
-    at.spans = take(((size_t)INT32_MAX / INTERRUPTION_SPAN + 3) * sizeof(int32_t));      // (the observed bytes are at most INT32_MAX)
-    at.rows = take((size_t)n * sizeof(RibbitRowPurity));
-    at.sites = take(cap * sizeof(RibbitInterruption));
-    at.offsets32 = take((cap + 1) * sizeof(int32_t));
-    at.totals = take(sizeof(InterruptionTotals));
-    at.bytes = end;
-    return at;
-}
-
-size_t interruptions_scratch_bytes(size_t pool_bytes) {
     const size_t cap = interruptions_op_cap(pool_bytes), chunks = (pool_bytes + 15) / 16;
     size_t a = 0, b = 0, c = 0, d = 0;
     (void)scan_counts(nullptr, a, nullptr, chunks + 1, 0);
     (void)scan_sums(nullptr, b, nullptr, nullptr, nullptr, nullptr, cap, 0);
     (void)scan_best(nullptr, c, nullptr, nullptr, nullptr, cap, 0);
     (void)scan_widths(nullptr, d, nullptr, nullptr, nullptr, cap + 1, 0);
-    return std::max(std::max(a, b), std::max(c, d)) + 256;
+    InterruptionLayout at{};
+    WorkCarver w;
+    at.counts = w.take((chunks + 1) * sizeof(uint32_t));
+    at.ops = w.take(cap * sizeof(uint64_t));
+    at.op_row = w.take(cap * sizeof(uint32_t));
+    at.first_op = w.take(((size_t)n + 1) * sizeof(uint32_t));
+    at.sums = w.take(cap * sizeof(InterruptionSums));
+    at.run_head = w.take((cap + 1) * sizeof(uint32_t));
+    at.best = w.take(2 * cap * sizeof(InterruptionBest));
+    at.width = w.take((cap + 1) * sizeof(uint32_t));
+    at.source = w.take(cap * sizeof(int32_t));
+    at.offsets64 = w.take((cap + 1) * sizeof(unsigned long long));
+    at.spans = w.take(((size_t)INT32_MAX / INTERRUPTION_SPAN + 3) * sizeof(int32_t));      // (the observed bytes are at most INT32_MAX)
+    at.rows = w.take((size_t)n * sizeof(RibbitRowPurity));
+    at.sites = w.take(cap * sizeof(RibbitInterruption));
+    at.offsets32 = w.take((cap + 1) * sizeof(int32_t));
+    at.totals = w.take(sizeof(InterruptionTotals));
+    w.close(at, std::max(std::max(a, b), std::max(c, d)));
+    return at;
 }
 
 hipError_t launch_interruptions(const int32_t *rows, const int32_t *offsets, const uint8_t *pool, int64_t n, size_t pool_bytes, int64_t length, uint8_t *work,
-                                const InterruptionLayout &at, void *scratch, size_t scratch_bytes, hipStream_t stream) {
+                                size_t work_bytes, const InterruptionLayout &at, hipStream_t stream) {
+    if (work_bytes < at.bytes) return hipErrorInvalidValue;
+    void *scratch = work + at.scratch;
+    const size_t scratch_bytes = at.scratch_bytes;
     const size_t cap = interruptions_op_cap(pool_bytes);
     const int64_t chunks = (int64_t)((pool_bytes + 15) / 16);
-    uint32_t *counts = reinterpret_cast<uint32_t *>(work + at.counts), *op_row = reinterpret_cast<uint32_t *>(work + at.op_row);
-    uint32_t *first_op = reinterpret_cast<uint32_t *>(work + at.first_op), *run_head = reinterpret_cast<uint32_t *>(work + at.run_head);
-    uint32_t *width = reinterpret_cast<uint32_t *>(work + at.width);
-    uint64_t *ops = reinterpret_cast<uint64_t *>(work + at.ops);
-    InterruptionSums *sums = reinterpret_cast<InterruptionSums *>(work + at.sums);
-    InterruptionBest *best_in = reinterpret_cast<InterruptionBest *>(work + at.best), *best = best_in + cap;
-    int32_t *source = reinterpret_cast<int32_t *>(work + at.source), *offsets32 = reinterpret_cast<int32_t *>(work + at.offsets32);
-    unsigned long long *offsets64 = reinterpret_cast<unsigned long long *>(work + at.offsets64);
-    RibbitRowPurity *out_rows = reinterpret_cast<RibbitRowPurity *>(work + at.rows);
-    RibbitInterruption *sites = reinterpret_cast<RibbitInterruption *>(work + at.sites);
-    InterruptionTotals *totals = reinterpret_cast<InterruptionTotals *>(work + at.totals);
-    const dim3 block(INT_THREADS), by_chunk(grid_for(chunks + 1, INT_THREADS, INT_MAX_BLOCKS)), by_row(grid_for(n + 1, INT_THREADS, INT_MAX_BLOCKS)),
-        by_op(grid_for((int64_t)cap + 1, INT_THREADS, INT_MAX_BLOCKS));
+    uint32_t *counts = region<uint32_t>(work, at.counts), *op_row = region<uint32_t>(work, at.op_row);
+    uint32_t *first_op = region<uint32_t>(work, at.first_op), *run_head = region<uint32_t>(work, at.run_head);
+    uint32_t *width = region<uint32_t>(work, at.width);
+    uint64_t *ops = region<uint64_t>(work, at.ops);
+    InterruptionSums *sums = region<InterruptionSums>(work, at.sums);
+    InterruptionBest *best_in = region<InterruptionBest>(work, at.best), *best = best_in + cap;
+    int32_t *source = region<int32_t>(work, at.source), *offsets32 = region<int32_t>(work, at.offsets32);
+    unsigned long long *offsets64 = region<unsigned long long>(work, at.offsets64);
+    RibbitRowPurity *out_rows = region<RibbitRowPurity>(work, at.rows);
+    RibbitInterruption *sites = region<RibbitInterruption>(work, at.sites);
+    InterruptionTotals *totals = region<InterruptionTotals>(work, at.totals);
+    const dim3 block(ROW_THREADS), by_chunk(grid_for(chunks + 1, ROW_THREADS, ROW_MAX_BLOCKS)), by_row(grid_for(n + 1, ROW_THREADS, ROW_MAX_BLOCKS)),
+        by_op(grid_for((int64_t)cap + 1, ROW_THREADS, ROW_MAX_BLOCKS));
     hipError_t e;
     // the totals start as: no ops, nothing bad (bad_at and bad_row lie side by side)
     if ((e = hipMemsetAsync(totals, 0, sizeof(InterruptionTotals), stream)) != hipSuccess) return e;
@@ -408,11 +401,11 @@ hipError_t launch_interruptions(const int32_t *rows, const int32_t *offsets, con
 hipError_t launch_interruption_gather(const uint8_t *ascii, uint8_t *work, const InterruptionLayout &at, uint32_t sites, int64_t observed, uint8_t *out,
                                       hipStream_t stream) {
     const int64_t spans = (observed + INTERRUPTION_SPAN - 1) / INTERRUPTION_SPAN;
-    const int32_t *offsets32 = reinterpret_cast<const int32_t *>(work + at.offsets32), *source = reinterpret_cast<const int32_t *>(work + at.source);
-    int32_t *span_site = reinterpret_cast<int32_t *>(work + at.spans);
-    hipLaunchKernelGGL(int_spans_kernel, dim3(grid_for(spans + 1, INT_THREADS, INT32_MAX)), dim3(INT_THREADS), 0, stream, offsets32, (int32_t)sites, observed, spans,
+    const int32_t *offsets32 = region<const int32_t>(work, at.offsets32), *source = region<const int32_t>(work, at.source);
+    int32_t *span_site = region<int32_t>(work, at.spans);
+    hipLaunchKernelGGL(int_spans_kernel, dim3(grid_for(spans + 1, ROW_THREADS, INT32_MAX)), dim3(ROW_THREADS), 0, stream, offsets32, (int32_t)sites, observed, spans,
                        span_site);
-    hipLaunchKernelGGL(int_gather_kernel, dim3(grid_for(spans, 1, 256 * 64)), dim3(INT_THREADS), 0, stream, ascii, offsets32, source, span_site, (int32_t)sites,
+    hipLaunchKernelGGL(int_gather_kernel, dim3(grid_for(spans, 1, 256 * 64)), dim3(ROW_THREADS), 0, stream, ascii, offsets32, source, span_site, (int32_t)sites,
                        observed, reinterpret_cast<uint4 *>(out));
     return hipGetLastError();
 }

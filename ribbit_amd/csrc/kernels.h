@@ -296,35 +296,60 @@ hipError_t launch_loci(const int32_t *run_start, const int32_t *run_end, int64_t
 // covered[k] = covered positions of [k window, min((k + 1) window, length)), k < n_windows = ceil(length / window)
 void launch_density(const uint32_t *bits, int64_t length, int64_t window, int64_t n_windows, int32_t *covered, hipStream_t stream);
 
-// overlap.hip: the rows of the loaded record (length > 0) against a second set of intervals (api_overlap.cpp).  a_bits: the
-// coverage bitmap of the n rows, b_bits: that of the n_other intervals of `other`, both as loci.hip takes them.  ranks:
-// 2 loci_lanes(length) words, keys: 4 n_other words, scratch: overlap_scratch_bytes(length, n_other).  totals is zeroed and
-// filled; per_row: (others, bases) of every row, 2 n ints.
-size_t overlap_scratch_bytes(int64_t length, int64_t n_other);
-hipError_t launch_overlap(const uint32_t *a_bits, const uint32_t *b_bits, int64_t length, const int32_t *rows, int64_t n, const int32_t *other, int64_t n_other,
-                          uint64_t *ranks, uint32_t *keys, RibbitOverlapTotals *totals, int32_t *per_row, void *scratch, size_t scratch_bytes,
-                          hipStream_t stream);
+// ---- the row outputs that carve one device work buffer (overlap.hip, best.hip, classes.hip, compound.hip, interruptions.hip,
+// nearest.hip, composition.hip).  Each states its regions once, as a layout of byte offsets made by one function beside its kernels:
+// every intermediate array, the result on the device, and one region for the temporary storage of its rocPRIM calls (the most any
+// of them asks for these sizes: the function asks them, so it needs the device).  The api file sizes the handle's work buffer by
+// `bytes`; launch_* takes that buffer with its size and the layout, derives its pointers from the layout and refuses a buffer
+// smaller than `bytes` (hipErrorInvalidValue) before it enqueues anything.
+// take(bytes): the offset of the next region.  Regions start on multiples of 256 bytes, hipMalloc's own granularity.
+// Every layout ends in the region of rocPRIM's temporary storage: close(at, most) takes it last and sets the buffer's size.
+struct WorkLayout {
+    size_t scratch, scratch_bytes, bytes;      // rocPRIM's temporary storage, as much as the primitives' queries ask for (no slack); the whole buffer
+};
+struct WorkCarver {
+    size_t end = 0;
+    size_t take(size_t bytes) { const size_t from = end; end += (bytes + 255) & ~(size_t)255; return from; }
+    void close(WorkLayout &at, size_t scratch_bytes) { at.scratch_bytes = scratch_bytes; at.scratch = take(scratch_bytes); at.bytes = end; }
+};
+template <typename T>
+T *region(uint8_t *work, size_t offset) { return reinterpret_cast<T *>(work + offset); }
 
-// best.hip: the best non-overlapping rows of the loaded record (api_best.cpp).  rows: the n >= 1 rows on the device.  keys: 2 n
-// words (the rows' keys | the keys sorted; the first half then holds w << 32 | p per sorted position), work: 3 n ints (the row
-// indices | the indices in sorted order | the reversed suffix minimum of s'; the first third then holds dp), flags: 2 n bytes
-// (segment heads | take flags), scratch: best_scratch_bytes(n, length).  totals is zeroed and filled; selected: the chosen
-// rows' indices by ascending start, totals->selected of them (n ints of room).
+// overlap.hip: the rows of the loaded record (length > 0) against a second set of intervals (api_overlap.cpp).  a_bits: the
+// coverage bitmap of the n rows as loci.hip takes it; other: the n_other intervals in page-locked host memory, copied down and made
+// into their own bitmap by the launch.  totals is zeroed and filled.
+struct OverlapLayout : WorkLayout {
+    size_t other;        // the second set's intervals, 2 n_other ints
+    size_t b_bits;       // their coverage bitmap, coverage_words(length) words
+    size_t ranks;        // the blocks' counts | their ranks, loci_lanes(length) words of 64 bits each
+    size_t keys;         // the intervals' starts | ends | sorted starts | sorted ends, n_other words each
+    size_t totals;       // the result: RibbitOverlapTotals ...
+    size_t per_row;      // ... and (others, bases) of every row, 2 n ints
+};
+OverlapLayout overlap_layout(int64_t n, int64_t n_other, int64_t length);
+hipError_t launch_overlap(const uint32_t *a_bits, int64_t length, const int32_t *rows, int64_t n, const int32_t *other, int64_t n_other, uint8_t *work,
+                          size_t work_bytes, const OverlapLayout &at, hipStream_t stream);
+
+// best.hip: the best non-overlapping rows of the loaded record (api_best.cpp).  rows: the n >= 1 rows on the device.  totals is
+// zeroed and filled.
 struct BestTotals {
     unsigned long long selected;      // rows chosen
     unsigned long long bases;         // bases they cover
     uint32_t rows, spare;             // non-empty rows
 };
-size_t best_scratch_bytes(int64_t n, int64_t length);
-hipError_t launch_best(const int32_t *rows, int64_t n, int64_t length, uint64_t *keys, int32_t *work, uint8_t *flags, BestTotals *totals,
-                       int32_t *selected, void *scratch, size_t scratch_bytes, hipStream_t stream);
+struct BestLayout : WorkLayout {
+    size_t keys;         // the rows' keys | the keys sorted, n words of 64 bits each; the first half then holds w << 32 | p per sorted position
+    size_t work;         // the row indices | the indices in sorted order | the reversed suffix minimum of s', n ints each; the first third then holds dp
+    size_t flags;        // segment heads | take flags, n bytes each
+    size_t totals;       // the result: BestTotals ...
+    size_t selected;     // ... and the chosen rows' indices by ascending start, totals.selected of them (n ints of room)
+};
+BestLayout best_layout(int64_t n, int64_t length);
+hipError_t launch_best(const int32_t *rows, int64_t n, int64_t length, uint8_t *work, size_t work_bytes, const BestLayout &at, hipStream_t stream);
 
 // classes.hip: the loaded record's rows grouped by canonical motif class (api_classes.cpp).  rows: the n >= 1 rows on the device;
 // offsets: n + 1 ascending offsets into pool, every motif 1 .. 1023 bytes over ACGT (the host has checked); pool: 8-byte aligned,
-// with 16 readable bytes behind the last motif.  work: classes_work_words(n) 64-bit words (the rows' sort items | the items sorted
-// | the groups' aggregates | head flags | group ids | the long rows' list), scratch: classes_scratch_bytes(n).  header is zeroed
-// and filled; groups: header->groups of them in class order (n of room); strands: n bytes; classes: the class of row i at
-// offsets[i], as many bytes as the pool.
+// with 16 readable bytes behind the last motif.  header is zeroed and filled.
 struct ClassItem {
     uint64_t key;                     // 10 bits of length, then the first 27 bases of the class, 2 bits each
     uint32_t row, off;                // the row and where its class lies in the pool
@@ -333,17 +358,22 @@ struct ClassHeader {
     unsigned long long groups;        // classes found
     unsigned long long long_rows;     // rows whose motif has more than 32 bases
 };
-size_t classes_work_words(int64_t n);
-size_t classes_scratch_bytes(int64_t n);
-hipError_t launch_classes(const int32_t *rows, const int32_t *offsets, const uint8_t *pool, int64_t n, int64_t length, uint64_t *work, ClassHeader *header,
-                          RibbitMotifClass *groups, uint8_t *strands, uint8_t *classes, void *scratch, size_t scratch_bytes, hipStream_t stream);
+struct ClassesLayout : WorkLayout {
+    size_t items;        // the rows' sort items | the items sorted, n ClassItem each
+    size_t agg;          // the groups' aggregates, n of 24 bytes
+    size_t heads;        // head flags | group ids, n words each
+    size_t long_rows;    // the long rows' list, n ints
+    size_t header;       // the result: ClassHeader ...
+    size_t groups;       // ... header.groups RibbitMotifClass in class order (n of room) ...
+    size_t strands;      // ... n strand bytes ...
+    size_t classes;      // ... and the class of row i at offsets[i], as many bytes as the pool
+};
+ClassesLayout classes_layout(int64_t n, size_t pool_bytes);
+hipError_t launch_classes(const int32_t *rows, const int32_t *offsets, const uint8_t *pool, int64_t n, int64_t length, uint8_t *work, size_t work_bytes,
+                          const ClassesLayout &at, hipStream_t stream);
 
 // compound.hip: the loaded record's rows chained into compound loci (api_compound.cpp).  rows, labels: the n >= 1 rows and their
-// labels on the device.  keys: 3 n words (the rows' keys, then the (chain, label) keys | the keys sorted | the (chain, label) keys
-// sorted), work: 3 n + 1 ints (the row indices, then the chain ids | reach | where every chain starts, and r behind the last),
-// sums: n prefix records, flags: n bytes (head, switch and overlap bits), scratch: compound_scratch_bytes(n, length).  totals is
-// zeroed and filled; members: the non-empty rows' indices in (s', e', index) order, totals->rows of them (n ints of room);
-// compounds: totals->chains of them by ascending start (n of room).
+// labels on the device.  totals is zeroed and filled.
 struct CompoundTotals {
     uint32_t rows, chains;            // non-empty rows, chains
     uint32_t spare[2];
@@ -352,18 +382,25 @@ struct CompoundSums {                 // what the positions up to one add up to
     unsigned long long bases;
     uint32_t switches, overlaps, classes, spare;
 };
-size_t compound_scratch_bytes(int64_t n, int64_t length);
-hipError_t launch_compounds(const int32_t *rows, const int32_t *labels, int64_t n, int64_t length, int32_t gap, uint64_t *keys, int32_t *work,
-                            CompoundSums *sums, uint8_t *flags, CompoundTotals *totals, int32_t *members, RibbitCompound *compounds, void *scratch,
-                            size_t scratch_bytes, hipStream_t stream);
+struct CompoundLayout : WorkLayout {
+    size_t keys;         // the rows' keys, then the (chain, label) keys | the keys sorted | the (chain, label) keys sorted, n words of 64 bits each
+    size_t work;         // the row indices, then the chain ids | reach | where every chain starts, n ints each, and r behind the last
+    size_t sums;         // n CompoundSums, the prefixes
+    size_t flags;        // head, switch and overlap bits, n bytes
+    size_t totals;       // the result: CompoundTotals ...
+    size_t compounds;    // ... totals.chains RibbitCompound by ascending start (n of room) ...
+    size_t members;      // ... and the non-empty rows' indices in (s', e', index) order, totals.rows of them (n ints of room)
+};
+CompoundLayout compound_layout(int64_t n, int64_t length);
+hipError_t launch_compounds(const int32_t *rows, const int32_t *labels, int64_t n, int64_t length, int32_t gap, uint8_t *work, size_t work_bytes,
+                            const CompoundLayout &at, hipStream_t stream);
 
 // interruptions.hip: every row's CIGAR decoded into interruptions and the pure stretch (api_interruptions.cpp).  rows, offsets:
 // the n >= 1 rows and their n + 1 ascending offsets into pool on the device; pool: 16-byte aligned, zero-filled from its last
 // byte to the next multiple of 16 and 16 bytes further.  The ops of a pool of P bytes are at most interruptions_op_cap(P), which
-// sizes everything that is per op, per run or per interruption; work: interruptions_layout(n, P).bytes, carved as the layout
-// says; scratch: interruptions_scratch_bytes(P).  launch_interruptions fills totals, the rows' records and the sites (with their
-// clipped widths and where their observed bases start); the caller reads totals, refuses what it reports (bad_at, bad_row,
-// observed) and, when there are observed bytes, calls launch_interruption_gather for them.
+// sizes everything that is per op, per run or per interruption.  launch_interruptions fills totals, the rows' records and the
+// sites (with their clipped widths and where their observed bases start); the caller reads totals, refuses what it reports
+// (bad_at, bad_row, observed) and, when there are observed bytes, calls launch_interruption_gather for them.
 struct InterruptionTotals {
     uint32_t ops, runs, sites;        // ops, runs of ops of one kind (match / not), interruptions
     uint32_t bad_at;                  // the lowest offending byte offset of the pool (the grammar), 0xffffffff: none
@@ -379,41 +416,60 @@ struct InterruptionBest {             // a run's stretch key (length << 32 | ~st
     unsigned long long key;
     uint32_t head, spare;
 };
-struct InterruptionLayout {           // byte offsets into work, each a multiple of 16
-    size_t counts, ops, op_row, first_op, sums, run_head, best, width, source, offsets64, spans, rows, sites, offsets32, totals, bytes;
+struct InterruptionLayout : WorkLayout {
+    size_t counts;       // the lanes' op counts, then their prefix: one word per 16 pool bytes and one more
+    size_t ops;          // the ops, 64 bits each (cap)
+    size_t op_row;       // a row's first op: the row + 1 (cap words)
+    size_t first_op;     // the ops before every row, n + 1 words
+    size_t sums;         // InterruptionSums up to every op (cap)
+    size_t run_head;     // every run's first op, cap + 1 words
+    size_t best;         // the runs' keys | the keys scanned, cap InterruptionBest each
+    size_t width;        // the interruptions' clipped widths, cap + 1 words
+    size_t source;       // where their observed bases start in the record, cap ints
+    size_t offsets64;    // the widths' prefix, cap + 1 words of 64 bits
+    size_t spans;        // the interruption that holds every 4096th observed byte
+    size_t rows;         // the result: n RibbitRowPurity ...
+    size_t sites;        // ... totals.sites RibbitInterruption (cap of room) ...
+    size_t offsets32;    // ... where each one's observed bases start, and their total behind the last ...
+    size_t totals;       // ... and InterruptionTotals
 };
 constexpr int64_t INTERRUPTION_SPAN = 4096;      // observed bytes one workgroup gathers, 16 per lane
 inline size_t interruptions_op_cap(size_t pool_bytes) { return pool_bytes / 2 + 1; }
 InterruptionLayout interruptions_layout(int64_t n, size_t pool_bytes);
-size_t interruptions_scratch_bytes(size_t pool_bytes);
 hipError_t launch_interruptions(const int32_t *rows, const int32_t *offsets, const uint8_t *pool, int64_t n, size_t pool_bytes, int64_t length, uint8_t *work,
-                                const InterruptionLayout &at, void *scratch, size_t scratch_bytes, hipStream_t stream);
+                                size_t work_bytes, const InterruptionLayout &at, hipStream_t stream);
 hipError_t launch_interruption_gather(const uint8_t *ascii, uint8_t *work, const InterruptionLayout &at, uint32_t sites, int64_t observed, uint8_t *out,
                                       hipStream_t stream);
 
-// nearest.hip: n >= 1 queries of the loaded record against n_targets >= 0 targets (api_nearest.cpp), both on the device.  keys:
-// 4 n_targets words (the A keys, then the scan's input | the B keys, then the scanned maxima | the A keys sorted | the B keys
-// sorted), order: 2 n_targets ints (the targets' indices in order A | in order B), scratch: nearest_scratch_bytes(n_targets).
-// out: one record per query.
-size_t nearest_scratch_bytes(int64_t n_targets);
-hipError_t launch_nearest(const int32_t *queries, int64_t n, const int32_t *targets, int64_t n_targets, int64_t length, uint64_t *keys, int32_t *order,
-                          RibbitNearest *out, void *scratch, size_t scratch_bytes, hipStream_t stream);
+// nearest.hip: n >= 1 queries of the loaded record against n_targets >= 0 targets (api_nearest.cpp), both on the device.
+struct NearestLayout : WorkLayout {
+    size_t keys;         // the A keys, then the scan's input | the B keys, then the scanned maxima | the A keys sorted | the B keys sorted, n_targets words of 64 bits each
+    size_t order;        // the targets' indices in order A | in order B, n_targets ints each
+    size_t out;          // the result: one RibbitNearest per query
+};
+NearestLayout nearest_layout(int64_t n, int64_t n_targets);
+hipError_t launch_nearest(const int32_t *queries, int64_t n, const int32_t *targets, int64_t n_targets, int64_t length, uint8_t *work, size_t work_bytes,
+                          const NearestLayout &at, hipStream_t stream);
 
 // composition.hip: base counts of the loaded record (length > 0) from its bit planes (api_composition.cpp).  A block is
 // COMP_BLOCK bases, the WORDS_PER_LANE words a lane of the scan tile owns; loci_lanes(length) blocks, the lanes of loci.hip and overlap.hip, hold the positions
-// 0 .. length.  sums / prefix: one BaseSums per block (the blocks' counts | C, G, T and other of the positions before the block);
-// scratch: composition_scratch_bytes(length).  The prefix belongs to the record.  bits: the coverage bitmap of the n >= 1 rows as
-// loci.hip takes it; cover_sums / cover_rank: one word per block (the blocks' covered positions | those before the block), made
-// by every rows launch.  out: one record per row / per window, n_windows = ceil(length / window) >= 1.
+// 0 .. length.  sums: two BaseSums per block (the blocks' counts | C, G, T and other of the positions before the block), which belong
+// to the record and are no part of the work buffer; launch_composition_prefix makes them with the scratch region of either layout.
+// bits: the coverage bitmap of the n >= 1 rows as loci.hip takes it.  n_windows = ceil(length / window) >= 1.
 constexpr int COMP_BLOCK_WORDS = 8;
 constexpr int COMP_BLOCK = COMP_BLOCK_WORDS * 32;
 struct alignas(16) BaseSums { uint32_t c, g, t, other; };
-size_t composition_scratch_bytes(int64_t length);
-hipError_t launch_composition_prefix(const DevicePlanes &pl, BaseSums *sums, BaseSums *prefix, void *scratch, size_t scratch_bytes, hipStream_t stream);
-hipError_t launch_composition_rows(const DevicePlanes &pl, const BaseSums *prefix, const uint32_t *bits, uint32_t *cover_sums, uint32_t *cover_rank,
-                                   const int32_t *rows, int64_t n, int32_t flank, RibbitRowComposition *out, void *scratch, size_t scratch_bytes,
-                                   hipStream_t stream);
-hipError_t launch_composition_windows(const DevicePlanes &pl, const BaseSums *prefix, int64_t window, int64_t n_windows, RibbitBaseCounts *out, hipStream_t stream);
+struct CompositionLayout : WorkLayout {
+    size_t cover;        // rows: the blocks' covered positions | those before the block, one word per block each
+    size_t out;          // the result: one RibbitRowComposition per row, or one RibbitBaseCounts per window
+};
+CompositionLayout composition_rows_layout(int64_t n, int64_t length);
+CompositionLayout composition_windows_layout(int64_t n_windows, int64_t length);
+hipError_t launch_composition_prefix(const DevicePlanes &pl, BaseSums *sums, uint8_t *work, size_t work_bytes, const CompositionLayout &at, hipStream_t stream);
+hipError_t launch_composition_rows(const DevicePlanes &pl, const BaseSums *sums, const uint32_t *bits, const int32_t *rows, int64_t n, int32_t flank, uint8_t *work,
+                                   size_t work_bytes, const CompositionLayout &at, hipStream_t stream);
+hipError_t launch_composition_windows(const DevicePlanes &pl, const BaseSums *sums, int64_t window, int64_t n_windows, uint8_t *work, size_t work_bytes,
+                                      const CompositionLayout &at, hipStream_t stream);
 
 // profiling aid: reads nwords dwords of src with one coalesced dword per lane (known byte count)
 void launch_calib_stream_read(const uint32_t *src, int64_t nwords, uint32_t *sink, hipStream_t stream);

@@ -14,34 +14,32 @@
 //             inside iff pa > 0 and M[pa - 1] >= e: the hit is the position the scan names there; otherwise over iff po < pe
 //             (M[po] > s >= M[po - 1] makes e'_po = M[po], and po < pe makes s'_po < e); left is position pb - 1 of order B,
 //             right position pe of order A unless that is an empty target's.  Nothing walks the overlapping targets.
-// The key kernel and the query kernel take one item per lane and stride beyond NEAR_MAX_BLOCKS blocks.
+// The key kernel and the query kernel take one item per lane and stride beyond ROW_MAX_BLOCKS blocks.
 #include <cstring>
 
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
-#include "kernels.h"
+#include "row_kernels.h"
 
 namespace rb {
 
 namespace {
 
-constexpr int NEAR_THREADS = 256;
-constexpr int64_t NEAR_MAX_BLOCKS = 1024;      // blocks of a launch at most, as the other row outputs: the kernels stride
 constexpr uint64_t NEAR_EMPTY = ~(uint64_t)0;
 
-__global__ void __launch_bounds__(NEAR_THREADS) nearest_keys_kernel(const int32_t *__restrict__ targets, int64_t m, int64_t length, uint64_t *__restrict__ a,
+__global__ void __launch_bounds__(ROW_THREADS) nearest_keys_kernel(const int32_t *__restrict__ targets, int64_t m, int64_t length, uint64_t *__restrict__ a,
                                                                     uint64_t *__restrict__ b) {
-    for (int64_t j = (int64_t)blockIdx.x * NEAR_THREADS + threadIdx.x; j < m; j += (int64_t)gridDim.x * NEAR_THREADS) {
-        const int64_t s = max((int64_t)targets[2 * j], (int64_t)0), e = min((int64_t)targets[2 * j + 1], length);
+    for (int64_t j = (int64_t)blockIdx.x * ROW_THREADS + threadIdx.x; j < m; j += (int64_t)gridDim.x * ROW_THREADS) {
+        const auto [s, e] = clip_row(targets, j, length);
         const bool has = s < e;
         a[j] = has ? (uint64_t)s << 32 | (uint64_t)e : NEAR_EMPTY;
         b[j] = has ? (uint64_t)e << 32 | (uint64_t)s : NEAR_EMPTY;
     }
 }
 
-__global__ void __launch_bounds__(NEAR_THREADS) nearest_scan_input_kernel(const uint64_t *__restrict__ a_sorted, int64_t m, uint64_t *__restrict__ reach) {
-    for (int64_t k = (int64_t)blockIdx.x * NEAR_THREADS + threadIdx.x; k < m; k += (int64_t)gridDim.x * NEAR_THREADS) {
+__global__ void __launch_bounds__(ROW_THREADS) nearest_scan_input_kernel(const uint64_t *__restrict__ a_sorted, int64_t m, uint64_t *__restrict__ reach) {
+    for (int64_t k = (int64_t)blockIdx.x * ROW_THREADS + threadIdx.x; k < m; k += (int64_t)gridDim.x * ROW_THREADS) {
         const uint64_t key = a_sorted[k];
         reach[k] = key == NEAR_EMPTY ? 0 : key << 32 | (uint32_t)~(uint32_t)k;
     }
@@ -57,12 +55,12 @@ __device__ inline int64_t high_below(const uint64_t *__restrict__ keys, int64_t 
     return lo;
 }
 
-__global__ void __launch_bounds__(NEAR_THREADS) nearest_queries_kernel(const int32_t *__restrict__ queries, int64_t n, int64_t length,
+__global__ void __launch_bounds__(ROW_THREADS) nearest_queries_kernel(const int32_t *__restrict__ queries, int64_t n, int64_t length,
                                                                        const uint64_t *__restrict__ a_sorted, const uint64_t *__restrict__ b_sorted,
                                                                        const uint64_t *__restrict__ reach, const int32_t *__restrict__ order_a,
                                                                        const int32_t *__restrict__ order_b, int64_t m, RibbitNearest *__restrict__ out) {
-    for (int64_t i = (int64_t)blockIdx.x * NEAR_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * NEAR_THREADS) {
-        const int64_t s = max((int64_t)queries[2 * i], (int64_t)0), e = min((int64_t)queries[2 * i + 1], length);
+    for (int64_t i = (int64_t)blockIdx.x * ROW_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * ROW_THREADS) {
+        const auto [s, e] = clip_row(queries, i, length);
         RibbitNearest r{RIBBIT_NEAREST_APART, -1, -1, -1, -1, -1};
         if (s < e) {
             // (s + 1 <= length < 2^31: an empty target's high half, 2^32 - 1, is never below a limit)
@@ -110,35 +108,45 @@ hipError_t scan_reach(void *scratch, size_t &bytes, const uint64_t *in, uint64_t
 
 }  // namespace
 
-size_t nearest_scratch_bytes(int64_t n_targets) {
+NearestLayout nearest_layout(int64_t n, int64_t n_targets) {
     size_t a = 0, b = 0;
     if (n_targets > 0) {
         (void)sort_by_key(nullptr, a, nullptr, nullptr, nullptr, n_targets, 0);
         (void)scan_reach(nullptr, b, nullptr, nullptr, n_targets, 0);
     }
-    return std::max(a, b) + 256;
+    NearestLayout at{};
+    WorkCarver w;
+    at.keys = w.take(4 * (size_t)n_targets * sizeof(uint64_t));
+    at.order = w.take(2 * (size_t)n_targets * sizeof(int32_t));
+    at.out = w.take((size_t)n * sizeof(RibbitNearest));
+    w.close(at, std::max(a, b));
+    return at;
 }
 
-hipError_t launch_nearest(const int32_t *queries, int64_t n, const int32_t *targets, int64_t n_targets, int64_t length, uint64_t *keys, int32_t *order,
-                          RibbitNearest *out, void *scratch, size_t scratch_bytes, hipStream_t stream) {
+hipError_t launch_nearest(const int32_t *queries, int64_t n, const int32_t *targets, int64_t n_targets, int64_t length, uint8_t *work, size_t work_bytes,
+                          const NearestLayout &at, hipStream_t stream) {
+    if (work_bytes < at.bytes) return hipErrorInvalidValue;
     const int64_t m = n_targets;
-    uint64_t *a = keys, *b = keys + m, *a_sorted = keys + 2 * m, *b_sorted = keys + 3 * m;
+    uint64_t *a = region<uint64_t>(work, at.keys), *b = a + m, *a_sorted = a + 2 * m, *b_sorted = a + 3 * m;
     uint64_t *reach_in = a, *reach = b;      // (the unsorted keys are done with once both sorts have run)
-    int32_t *order_a = order, *order_b = order + m;
+    int32_t *order_a = region<int32_t>(work, at.order), *order_b = order_a + m;
+    RibbitNearest *out = region<RibbitNearest>(work, at.out);
+    void *scratch = work + at.scratch;
+    const size_t scratch_bytes = at.scratch_bytes;
     hipError_t e;
     if (m > 0) {
-        const dim3 grid(grid_for(m, NEAR_THREADS, NEAR_MAX_BLOCKS));
-        hipLaunchKernelGGL(nearest_keys_kernel, grid, dim3(NEAR_THREADS), 0, stream, targets, m, length, a, b);
+        const dim3 grid(grid_for(m, ROW_THREADS, ROW_MAX_BLOCKS));
+        hipLaunchKernelGGL(nearest_keys_kernel, grid, dim3(ROW_THREADS), 0, stream, targets, m, length, a, b);
         size_t bytes = scratch_bytes;
         if ((e = sort_by_key(scratch, bytes, a, a_sorted, order_a, m, stream)) != hipSuccess) return e;
         bytes = scratch_bytes;
         if ((e = sort_by_key(scratch, bytes, b, b_sorted, order_b, m, stream)) != hipSuccess) return e;
-        hipLaunchKernelGGL(nearest_scan_input_kernel, grid, dim3(NEAR_THREADS), 0, stream, a_sorted, m, reach_in);
+        hipLaunchKernelGGL(nearest_scan_input_kernel, grid, dim3(ROW_THREADS), 0, stream, a_sorted, m, reach_in);
         bytes = scratch_bytes;
         if ((e = scan_reach(scratch, bytes, reach_in, reach, m, stream)) != hipSuccess) return e;
     }
     if (n > 0)
-        hipLaunchKernelGGL(nearest_queries_kernel, dim3(grid_for(n, NEAR_THREADS, NEAR_MAX_BLOCKS)), dim3(NEAR_THREADS), 0, stream, queries, n, length, a_sorted,
+        hipLaunchKernelGGL(nearest_queries_kernel, dim3(grid_for(n, ROW_THREADS, ROW_MAX_BLOCKS)), dim3(ROW_THREADS), 0, stream, queries, n, length, a_sorted,
                            b_sorted, reach, order_a, order_b, m, out);
     return hipGetLastError();
 }

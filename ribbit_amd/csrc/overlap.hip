@@ -20,27 +20,20 @@
 #include <rocprim/rocprim.hpp>
 
 #include "bit_blocks.h"
-#include "kernels.h"
+#include "row_kernels.h"
 
 namespace rb {
 
 namespace {
 
-constexpr int OVL_THREADS = 256;
-// blocks of a launch at most; the kernels stride.  Four blocks per CU: a stride of the block counts covers 2^26 positions, and
-// a record or a row set beyond one stride is still small enough to test
-constexpr int64_t OVL_MAX_BLOCKS = 1024;
-__device__ inline unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
-    return v;      // (lane 0's)
-}
+// (ROW_MAX_BLOCKS, four blocks per CU: a stride of the block counts covers 2^26 positions, and a record or a row set beyond one
+// stride is still small enough to test)
 
 // totals: rows_bases, other_bases, both_bases
-__global__ void __launch_bounds__(OVL_THREADS) overlap_counts_kernel(const uint32_t *__restrict__ a_bits, const uint32_t *__restrict__ b_bits, int64_t lanes,
+__global__ void __launch_bounds__(ROW_THREADS) overlap_counts_kernel(const uint32_t *__restrict__ a_bits, const uint32_t *__restrict__ b_bits, int64_t lanes,
                                                                      uint64_t *__restrict__ sums, unsigned long long *__restrict__ totals) {
     unsigned long long in_a = 0, in_b = 0, in_both = 0;
-    for (int64_t t = (int64_t)blockIdx.x * OVL_THREADS + threadIdx.x; t < lanes; t += (int64_t)gridDim.x * OVL_THREADS) {
+    for (int64_t t = (int64_t)blockIdx.x * ROW_THREADS + threadIdx.x; t < lanes; t += (int64_t)gridDim.x * ROW_THREADS) {
         uint32_t a[LOCI_LANE_WORDS], b[LOCI_LANE_WORDS];
         load_block(a_bits, t, a);
         load_block(b_bits, t, b);
@@ -80,17 +73,17 @@ __device__ inline uint32_t rank_at(const uint32_t *__restrict__ bits, const uint
 
 // One lane per interval, intervals in grid-stride waves (every lane of a wave takes the same number of turns: the ballots see
 // whole waves).  counts: the number of non-empty intervals, and of those that hold a position of the other bitmap.
-__global__ void __launch_bounds__(OVL_THREADS) overlap_other_kernel(const int32_t *__restrict__ iv, int64_t n, int64_t length, const uint32_t *__restrict__ a_bits,
+__global__ void __launch_bounds__(ROW_THREADS) overlap_other_kernel(const int32_t *__restrict__ iv, int64_t n, int64_t length, const uint32_t *__restrict__ a_bits,
                                                                     const uint64_t *__restrict__ rank, uint32_t *__restrict__ starts,
                                                                     uint32_t *__restrict__ ends, int32_t *__restrict__ counts) {
     const int lane = threadIdx.x & 63;
-    const int64_t waves = (int64_t)gridDim.x * (OVL_THREADS / 64);
+    const int64_t waves = (int64_t)gridDim.x * (ROW_THREADS / 64);
     int32_t some = 0, hit = 0;
-    for (int64_t base = ((int64_t)blockIdx.x * (OVL_THREADS / 64) + (threadIdx.x >> 6)) * 64; base < n; base += waves * 64) {
+    for (int64_t base = ((int64_t)blockIdx.x * (ROW_THREADS / 64) + (threadIdx.x >> 6)) * 64; base < n; base += waves * 64) {
         const int64_t i = base + lane;
         bool has = false, hits = false;
         if (i < n) {
-            const int64_t s = max((int64_t)iv[2 * i], (int64_t)0), e = min((int64_t)iv[2 * i + 1], length);
+            const auto [s, e] = clip_row(iv, i, length);
             has = s < e;
             starts[i] = (uint32_t)(has ? s : length);
             ends[i] = (uint32_t)(has ? e : length);
@@ -115,18 +108,18 @@ __device__ inline int32_t count_below(const uint32_t *__restrict__ keys, int64_t
 }
 
 // per_row: (others, bases) of every row; counts: the number of non-empty rows, and of those with bases > 0
-__global__ void __launch_bounds__(OVL_THREADS) overlap_rows_kernel(const int32_t *__restrict__ iv, int64_t n, int64_t length, const uint32_t *__restrict__ b_bits,
+__global__ void __launch_bounds__(ROW_THREADS) overlap_rows_kernel(const int32_t *__restrict__ iv, int64_t n, int64_t length, const uint32_t *__restrict__ b_bits,
                                                                    const uint64_t *__restrict__ rank, const uint32_t *__restrict__ starts,
                                                                    const uint32_t *__restrict__ ends, int64_t n_other, int32_t *__restrict__ per_row,
                                                                    int32_t *__restrict__ counts) {
     const int lane = threadIdx.x & 63;
-    const int64_t waves = (int64_t)gridDim.x * (OVL_THREADS / 64);
+    const int64_t waves = (int64_t)gridDim.x * (ROW_THREADS / 64);
     int32_t some = 0, hit = 0;
-    for (int64_t base = ((int64_t)blockIdx.x * (OVL_THREADS / 64) + (threadIdx.x >> 6)) * 64; base < n; base += waves * 64) {
+    for (int64_t base = ((int64_t)blockIdx.x * (ROW_THREADS / 64) + (threadIdx.x >> 6)) * 64; base < n; base += waves * 64) {
         const int64_t i = base + lane;
         bool has = false, hits = false;
         if (i < n) {
-            const int64_t s = max((int64_t)iv[2 * i], (int64_t)0), e = min((int64_t)iv[2 * i + 1], length);
+            const auto [s, e] = clip_row(iv, i, length);
             int32_t others = 0, bases = 0;
             has = s < e;
             if (has) {
@@ -151,40 +144,54 @@ hipError_t scan_ranks(void *scratch, size_t &bytes, const uint64_t *sums, uint64
     return rocprim::exclusive_scan(scratch, bytes, sums, rank, (uint64_t)0, (size_t)lanes, rocprim::plus<uint64_t>(), stream);
 }
 
-// the bits a key can have: the positions 0 .. length
-unsigned key_bits(int64_t length) {
-    unsigned bits = 1;
-    while (bits < 32 && (length >> bits)) ++bits;
-    return bits;
-}
-
+// over the bits a key can have: the positions 0 .. length
 hipError_t sort_keys(void *scratch, size_t &bytes, const uint32_t *in, uint32_t *out, int64_t m, int64_t length, hipStream_t stream) {
-    return rocprim::radix_sort_keys(scratch, bytes, in, out, (size_t)m, 0u, key_bits(length), stream);
+    return rocprim::radix_sort_keys(scratch, bytes, in, out, (size_t)m, 0u, bits_for(length), stream);
 }
 
 }  // namespace
 
-size_t overlap_scratch_bytes(int64_t length, int64_t n_other) {
+OverlapLayout overlap_layout(int64_t n, int64_t n_other, int64_t length) {
     size_t a = 0, b = 0;
     (void)scan_ranks(nullptr, a, nullptr, nullptr, loci_lanes(length), 0);
     if (n_other > 0) (void)sort_keys(nullptr, b, nullptr, nullptr, n_other, length, 0);
-    return std::max(a, b) + 256;
+    OverlapLayout at{};
+    WorkCarver w;
+    at.other = w.take(2 * (size_t)n_other * sizeof(int32_t));
+    at.b_bits = w.take((size_t)coverage_words(length) * sizeof(uint32_t));
+    at.ranks = w.take(2 * (size_t)loci_lanes(length) * sizeof(uint64_t));
+    at.keys = w.take(4 * (size_t)n_other * sizeof(uint32_t));
+    at.totals = w.take(sizeof(RibbitOverlapTotals));
+    at.per_row = w.take(2 * (size_t)n * sizeof(int32_t));
+    w.close(at, std::max(a, b));
+    return at;
 }
 
-hipError_t launch_overlap(const uint32_t *a_bits, const uint32_t *b_bits, int64_t length, const int32_t *rows, int64_t n, const int32_t *other, int64_t n_other,
-                          uint64_t *ranks, uint32_t *keys, RibbitOverlapTotals *totals, int32_t *per_row, void *scratch, size_t scratch_bytes,
-                          hipStream_t stream) {
+hipError_t launch_overlap(const uint32_t *a_bits, int64_t length, const int32_t *rows, int64_t n, const int32_t *other_host, int64_t n_other, uint8_t *work,
+                          size_t work_bytes, const OverlapLayout &at, hipStream_t stream) {
+    if (work_bytes < at.bytes) return hipErrorInvalidValue;
     const int64_t lanes = loci_lanes(length);
-    uint64_t *sums = ranks, *rank = ranks + lanes;
-    uint32_t *starts = keys, *ends = keys + n_other, *starts_sorted = ends + n_other, *ends_sorted = starts_sorted + n_other;
+    int32_t *other = region<int32_t>(work, at.other);
+    uint32_t *b_bits = region<uint32_t>(work, at.b_bits);
+    uint64_t *sums = region<uint64_t>(work, at.ranks), *rank = sums + lanes;
+    uint32_t *starts = region<uint32_t>(work, at.keys), *ends = starts + n_other, *starts_sorted = ends + n_other, *ends_sorted = starts_sorted + n_other;
+    RibbitOverlapTotals *totals = region<RibbitOverlapTotals>(work, at.totals);
+    int32_t *per_row = region<int32_t>(work, at.per_row);
+    void *scratch = work + at.scratch;
+    const size_t scratch_bytes = at.scratch_bytes;
     hipError_t e = hipMemsetAsync(totals, 0, sizeof(RibbitOverlapTotals), stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(overlap_counts_kernel, dim3(grid_for(lanes, OVL_THREADS, OVL_MAX_BLOCKS)), dim3(OVL_THREADS), 0, stream, a_bits, b_bits, lanes, sums,
+    if ((e = hipMemsetAsync(b_bits, 0, (size_t)coverage_words(length) * sizeof(uint32_t), stream)) != hipSuccess) return e;
+    if (n_other > 0) {
+        if ((e = hipMemcpyAsync(other, other_host, 2 * (size_t)n_other * sizeof(int32_t), hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
+        launch_mask_coverage(other, n_other, length, b_bits, stream);
+    }
+    hipLaunchKernelGGL(overlap_counts_kernel, dim3(grid_for(lanes, ROW_THREADS, ROW_MAX_BLOCKS)), dim3(ROW_THREADS), 0, stream, a_bits, b_bits, lanes, sums,
                        reinterpret_cast<unsigned long long *>(&totals->rows_bases));
     size_t bytes = scratch_bytes;
     if ((e = scan_ranks(scratch, bytes, sums, rank, lanes, stream)) != hipSuccess) return e;
     if (n_other > 0) {
-        hipLaunchKernelGGL(overlap_other_kernel, dim3(grid_for(n_other, OVL_THREADS, OVL_MAX_BLOCKS)), dim3(OVL_THREADS), 0, stream, other, n_other, length, a_bits,
+        hipLaunchKernelGGL(overlap_other_kernel, dim3(grid_for(n_other, ROW_THREADS, ROW_MAX_BLOCKS)), dim3(ROW_THREADS), 0, stream, other, n_other, length, a_bits,
                            rank, starts, ends, &totals->other);
         bytes = scratch_bytes;
         if ((e = sort_keys(scratch, bytes, starts, starts_sorted, n_other, length, stream)) != hipSuccess) return e;
@@ -192,7 +199,7 @@ hipError_t launch_overlap(const uint32_t *a_bits, const uint32_t *b_bits, int64_
         if ((e = sort_keys(scratch, bytes, ends, ends_sorted, n_other, length, stream)) != hipSuccess) return e;
     }
     if (n > 0)
-        hipLaunchKernelGGL(overlap_rows_kernel, dim3(grid_for(n, OVL_THREADS, OVL_MAX_BLOCKS)), dim3(OVL_THREADS), 0, stream, rows, n, length, b_bits, rank,
+        hipLaunchKernelGGL(overlap_rows_kernel, dim3(grid_for(n, ROW_THREADS, ROW_MAX_BLOCKS)), dim3(ROW_THREADS), 0, stream, rows, n, length, b_bits, rank,
                            starts_sorted, ends_sorted, n_other, per_row, &totals->rows);
     return hipGetLastError();
 }

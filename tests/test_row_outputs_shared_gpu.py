@@ -1,8 +1,8 @@
-"""The row outputs interleaved on one handle.  Best, classes, compounds and interruptions stage their inputs through one pair of
-buffers, and every row output takes its scans' and sorts' temporary storage from one device buffer (RowBufs in
-ribbit_amd/csrc/api_internal.h), so a buffer grows inside another feature than the one that allocated it; the results stay in
-buffers of their own, "valid until the handle's next same call, load or close" (include/ribbit_hip.h).  Every answer here is
-compared with the host twin's."""
+"""The row outputs interleaved on one handle.  Best, classes, compounds, interruptions and nearest stage their inputs through one
+pair of buffers, and every row output carves its intermediate arrays, its result on the device and its scans' and sorts'
+temporary storage from one device work buffer (RowBufs in ribbit_amd/csrc/api_internal.h, the layouts in kernels.h), so that
+buffer grows inside another feature than the one that sized it last; the results come up into pinned buffers of their own, "valid
+until the handle's next same call, load or close" (include/ribbit_hip.h).  Every answer here is compared with the host twin's."""
 import ctypes as C
 
 import numpy as np
@@ -43,6 +43,11 @@ CALLS = {
     "loci": (lambda sc, seq, r: sc.record_loci(r["iv"], 25), lambda seq, r: ribbit_amd.host_record_loci(len(seq), r["iv"], 25)),
     "overlap": (lambda sc, seq, r: sc.record_overlap(r["iv"], r["iv"][::3] + 7), lambda seq, r: ribbit_amd.host_record_overlap(len(seq), r["iv"], r["iv"][::3] + 7)),
     "repeats": (lambda sc, seq, r: sc.repeat_sequences("chr", r["iv"], 30), lambda seq, r: ribbit_amd.host_repeat_sequences("chr", seq, r["iv"], 30)),
+    "nearest": (lambda sc, seq, r: sc.record_nearest(r["iv"], r["iv"][::3] + 7), lambda seq, r: ribbit_amd.host_record_nearest(len(seq), r["iv"], r["iv"][::3] + 7)),
+    "composition": (lambda sc, seq, r: sc.record_composition(r["iv"], 30), lambda seq, r: ribbit_amd.host_record_composition(seq, r["iv"], 30)),
+    "base windows": (lambda sc, seq, r: sc.record_base_windows(100), lambda seq, r: ribbit_amd.host_record_base_windows(seq, 100)),
+    "density": (lambda sc, seq, r: sc.record_density(r["iv"], 100), lambda seq, r: ribbit_amd.host_record_density(len(seq), r["iv"], 100)),
+    "mask": (lambda sc, seq, r: sc.mask_record(r["iv"], "soft", 60), lambda seq, r: ribbit_amd.host_mask_record(seq, r["iv"], "soft", 60)),
 }
 
 
@@ -54,10 +59,14 @@ def _same(sc, seq, name, rows):
 
 
 def test_row_outputs_interleaved_on_one_handle():
-    """the shared staging and temporary storage are allocated by best at 70 rows, grow inside classes at 3 000, serve the other
-    outputs at 300 and best again at 3 000; then the first call again, a shorter record, and the round in reverse"""
+    """the shared staging and work buffer are allocated by best at 70 rows, grow inside classes at 3 000, serve the other
+    outputs at 300 and best again at 3 000.  Then every output at 1 row and at 65 (one lane past a wavefront: every region of the
+    work buffer ends off its alignment).  Then the first call again, a shorter record, and the round in reverse"""
     few, mid, many = _rows(70, 3000, 1), _rows(300, 3000, 2), _rows(3000, 3000, 3)
+    one, odd = _rows(1, 3000, 5), _rows(65, 3000, 6)
     steps = [("best", few), ("classes", many)] + [(name, mid) for name in ("compounds", "interruptions", "loci", "overlap", "repeats")] + [("best", many)]
+    steps += [(name, mid) for name in ("nearest", "composition", "base windows", "density", "mask")]
+    steps += [(name, rows) for rows in (one, odd) for name in CALLS]
     with ribbit_amd.Scanner(2, 30) as sc:
         seq = _seq(3000)
         sc.load_record(seq)
@@ -71,9 +80,23 @@ def test_row_outputs_interleaved_on_one_handle():
         assert [_same(sc, seq, name, rows) for name, rows in steps] == answers
 
 
+def test_the_work_buffer_regrows_inside_another_output_than_the_one_that_sized_it():
+    """on a fresh handle best at 70 rows allocates the work buffer (a few KB: a buffer only ever grows, so nothing larger may have
+    run before); nearest at 9 000 queries against 3 000 targets needs some 340 KB (96 KB of keys, 24 KB of orders, 216 KB of
+    result) and so replaces it in the middle of the handle's life; best at 70 rows then carves the larger buffer and answers as before"""
+    few, dense = _rows(70, 3000, 1), _rows(9000, 3000, 7)
+    with ribbit_amd.Scanner(2, 30) as sc:
+        seq = _seq(3000)
+        sc.load_record(seq)
+        first = _same(sc, seq, "best", few)
+        _same(sc, seq, "nearest", dense)
+        assert _same(sc, seq, "best", few) == first
+
+
 def test_a_result_outlives_the_other_row_outputs():
     """what ribbit_hip_record_best returned is still there, byte for byte, after classes, compounds and interruptions on the same
-    handle; what ribbit_hip_record_classes returned, after best"""
+    handle; what ribbit_hip_record_classes returned, after best; what ribbit_hip_record_nearest and ribbit_hip_record_composition
+    returned, whose results on the device are regions of the work buffer the others carve anew, after best, classes and compounds"""
     L = ribbit_amd.load_library()
     seq = _seq(3000)
     r = _rows(3000, 3000, 4)
@@ -85,6 +108,16 @@ def test_a_result_outlives_the_other_row_outputs():
     assert L.ribbit_hip_open(C.byref(params), 0, C.byref(h)) == 0
     try:
         assert L.ribbit_hip_load_record(h, seq, len(seq)) == 0
+        targets = np.ascontiguousarray(iv[::3] + 7)
+        near, comp = C.c_void_p(), C.c_void_p()
+        assert L.ribbit_hip_record_nearest(h, iv.ctypes.data, len(iv), targets.ctypes.data, len(targets), C.byref(near)) == 0
+        assert L.ribbit_hip_record_composition(h, iv.ctypes.data, len(iv), 30, C.byref(comp)) == 0
+
+        def rows_now():
+            return (C.string_at(near.value, len(iv) * ribbit_amd.NEAREST_DT.itemsize), C.string_at(comp.value, len(iv) * ribbit_amd.COMPOSITION_DT.itemsize))
+
+        kept_rows = rows_now()
+        assert kept_rows == (ribbit_amd.host_record_nearest(len(seq), iv, targets).tobytes(), ribbit_amd.host_record_composition(seq, iv, 30).tobytes())
         best, n_best, bases = C.c_void_p(), C.c_size_t(), C.c_int64()
         assert L.ribbit_hip_record_best(h, iv.ctypes.data, len(iv), C.byref(best), C.byref(n_best), C.byref(bases)) == 0
         assert n_best.value > 10
@@ -104,6 +137,7 @@ def test_a_result_outlives_the_other_row_outputs():
                                                  C.byref(n_sites), C.byref(observed), C.byref(observed_off)) == 0
         assert n_chains.value > 0 and n_sites.value > 0
         assert C.string_at(best.value, 4 * n_best.value) == kept
+        assert rows_now() == kept_rows
 
         def classes_now():
             return (C.string_at(classes.value, int(off[-1])), C.string_at(strands.value, len(iv)),
