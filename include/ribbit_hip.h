@@ -179,6 +179,12 @@ int ribbit_hip_dispatch_seeds(RibbitHandle *h, const RibbitSeed **out, size_t *n
  * the previous seed's CIGAR (the reference's shared Alignment object); inside a slice that is resolved exactly, across a slice's
  * first seed it cannot be, so if ribbit_hip_refine_met_empty_query is 1 for any slice the record is refined again in one piece.
  * After this call the handle's seed lists are not available (ribbit_hip_seeds_* run the stages again from the next load on).
+ * The scans of the seeds index the planes and the bases with what a seed says, so every seed of the list must satisfy
+ *     0 <= start <= end <= length   and   min_motif <= mlen <= min(max_motif, length)
+ * (length = the loaded record's; min_motif, max_motif = the handle's).  Every list ribbit_hip_dispatch_seeds returns does: a seed
+ * is made of positions of the record and of a motif length that has a run in it (end + mlen may lie beyond the record; the scans
+ * clamp that themselves).  Otherwise the call returns RIBBIT_E_ARG, ribbit_hip_last_error names the first offending index, and
+ * the handle keeps the list it had.
  */
 int ribbit_hip_adopt_dispatch(RibbitHandle *h, const RibbitSeed *seeds, size_t n);
 /* 1 if the last ribbit_hip_refine_bed on this handle met an alignment with an empty query */
@@ -233,6 +239,13 @@ int ribbit_hip_ssw_passes(RibbitHandle *h, const RibbitAlignJob *jobs, size_t n,
 /* longestContinuousMatches (parse_seed.cpp:26-44; calls at parse_seed.cpp:366, parse_smallmotif_seed.cpp:234)
  * for every dispatched seed at once, on the GPU: out[i] belongs to dispatch seed i. */
 int ribbit_hip_seed_longest_runs(RibbitHandle *h, const int32_t **out, size_t *n);
+
+/* mostFrequentLongerMotif's choice (parse_seed.cpp:153-256) for every dispatched seed at once, on the GPU: out[i] = the start of
+ * the window of dispatch seed i whose bases become its motif -- the first row with the highest count, 0 (of the RECORD,
+ * parse_seed.cpp:169) when no row counts anything -- or -1 for a seed that never gets there (m <= 10, shorter than 0.9 m, longest
+ * run below prm's threshold).  What ribbit_hip_refine_jobs / ribbit_hip_refine_bed use for those seeds; valid until the next call
+ * on the handle. */
+int ribbit_hip_seed_best_rows(RibbitHandle *h, const RibbitRefineParams *prm, const int32_t **out, size_t *n);
 
 /* Host-only twin (no GPU): the same scan over seeds[0..n) of a record given by its packed planes (LSB-first words as
  * ribbit_hip_packed_plane returns them, zero-padded by max_motif/32 + 4 words past word L/32).  The composed planes
@@ -1004,6 +1017,9 @@ int64_t ribbit_host_debug_thread_faults(int32_t refuse_starts_from, int32_t thro
  * otherwise only the one that passes, or none.  Valid until the next call on the handle. */
 int ribbit_hip_small_motifs(RibbitHandle *h, const RibbitRefineParams *prm, const int32_t **head, size_t *n_seeds,
                             const uint32_t **records, size_t *n_records);
+/* Test hook: the number of records the arena of ribbit_hip_small_motifs holds (0 = automatic: four per dispatched seed and 2^20
+ * more).  A seed whose records no longer fit gets flags 2 and is computed by the host twin; the results are the same. */
+int ribbit_hip_debug_set_small_record_capacity(RibbitHandle *h, size_t records);
 /* Test hook: cumulative, process-wide: small-motif seeds that refinement took from the GPU's table / computed on the host. */
 void ribbit_debug_small_motif_counters(int64_t out[2]);
 /* Test hook: cumulative, process-wide: alignments refinement made / of them with the striped passes from the GPU / with the

@@ -1072,3 +1072,21 @@ int rbo_run_dispatch(rbo_ctx *c) {
     }
     return (int)c->dispatch.n;
 }
+
+/* Test door: the dispatch list becomes the caller's (any seeds over this record, for rbo_refine_jobs / rbo_refine_bed; the
+ * planes stay as the stages left them, so rbo_run_anchor_planes must have run).  The refinement half indexes planes and bases
+ * with what a seed says, unchecked like the reference: a seed outside 0 <= start <= end <= L or with a motif length outside
+ * m_lo .. min(m_hi, L) (a seed without a scoring row takes its motif from bases 0 .. mlen-1, parse_seed.cpp:165,246) is
+ * refused: -1, and the list stays as it was. */
+int rbo_set_dispatch(rbo_ctx *c, const rbo_seed_t *seeds, int64_t n) {
+    if (!c || n < 0 || (n && !seeds)) return -1;
+    for (int64_t i = 0; i < n; i++) {
+        if (seeds[i].start < 0 || seeds[i].end < seeds[i].start || (int64_t)seeds[i].end > c->L) return -1;
+        if (seeds[i].mlen < c->m_lo || seeds[i].mlen > c->m_hi || (int64_t)seeds[i].mlen > c->L) return -1;
+    }
+    seedvec fresh = {NULL, 0, 0};       /* (seeds may point into the list that is replaced) */
+    for (int64_t i = 0; i < n; i++) sv_push(&fresh, seeds[i].start, seeds[i].end, seeds[i].mlen, seeds[i].type);
+    free(c->dispatch.a);
+    c->dispatch = fresh;
+    return 0;
+}

@@ -67,6 +67,11 @@ int rbo_run_anchored(rbo_ctx *c);
 /* 3-way merge + filters of fasta_utils.cpp:187-224: seeds in the order they reach refinement */
 int rbo_run_dispatch(rbo_ctx *c);
 
+/* test door: replace the dispatch list by any n seeds over this record (after the stages have run: the planes are read as they
+ * are).  -1, and the list unchanged, if a seed breaks 0 <= start <= end <= L or m_lo <= mlen <= min(m_hi, L): the
+ * refinement half indexes its planes and bases unchecked. */
+int rbo_set_dispatch(rbo_ctx *c, const rbo_seed_t *seeds, int64_t n);
+
 int64_t rbo_seeds(const rbo_ctx *c, int which, const rbo_seed_t **out);
 int64_t rbo_calls(const rbo_ctx *c, int which, const rbo_call_t **out);
 int64_t rbo_dispatch(const rbo_ctx *c, const rbo_seed_t **out);

@@ -60,7 +60,7 @@ ABI_SYMBOLS = [
     "ribbit_hip_last_timing_ms", "ribbit_hip_last_event_count",
     "ribbit_hip_subst_calls", "ribbit_hip_seeds_substitutions",
     "ribbit_host_replay_calls", "ribbit_seed_lists_free", "ribbit_host_longest_runs", "ribbit_debug_set_merge_min_range", "ribbit_debug_last_merge",
-    "ribbit_hip_small_motifs", "ribbit_debug_small_motif_counters", "ribbit_debug_last_dispatch_ranges", "ribbit_host_debug_thread_faults", "ribbit_debug_last_device_merge", "ribbit_debug_alignment_counters", "ribbit_debug_level_counters",
+    "ribbit_hip_small_motifs", "ribbit_hip_seed_best_rows", "ribbit_debug_small_motif_counters", "ribbit_debug_last_dispatch_ranges", "ribbit_host_debug_thread_faults", "ribbit_debug_last_device_merge", "ribbit_debug_alignment_counters", "ribbit_debug_level_counters",
     "ribbit_hip_adopt_dispatch", "ribbit_hip_refine_met_empty_query", "ribbit_hip_device_pci_bus_id",
     "ribbit_hip_anchored_calls", "ribbit_hip_seeds_anchored", "ribbit_hip_dispatch_seeds", "ribbit_hip_guard_hits",
     "ribbit_hip_debug_stream_read",
@@ -73,7 +73,7 @@ ABI_SYMBOLS = [
     "ribbit_hip_set_host_threads", "ribbit_hip_ssw_passes", "ribbit_hip_ssw_align_jobs", "ribbit_hip_set_timing", "ribbit_hip_debug_set_event_capacity", "ribbit_hip_debug_set_scan_split", "ribbit_hip_debug_last_scan_split", "ribbit_hip_debug_pair_events", "ribbit_hip_scan_perfect_begin", "ribbit_hip_scan_perfect_end", "ribbit_hip_scan_perfect_wait", "ribbit_hip_scan_perfect_end_device",
     "ribbit_hip_stage_calls_chunk", "ribbit_hip_xa_words_strided", "ribbit_host_merge_chunks",
     "ribbit_hip_mask_record", "ribbit_host_mask_record", "ribbit_bed_intervals", "ribbit_intervals_free",
-    "ribbit_hip_repeat_sequences", "ribbit_host_repeat_sequences", "ribbit_hip_debug_set_repeat_text_budget",
+    "ribbit_hip_repeat_sequences", "ribbit_host_repeat_sequences", "ribbit_hip_debug_set_repeat_text_budget", "ribbit_hip_debug_set_small_record_capacity",
     "ribbit_hip_record_loci", "ribbit_hip_record_density", "ribbit_host_record_loci", "ribbit_host_record_density", "ribbit_loci_free",
     "ribbit_bed_loci_text",
     "ribbit_hip_record_overlap", "ribbit_host_record_overlap", "ribbit_bed_overlap_text",
@@ -254,6 +254,7 @@ def load_library():
     L.ribbit_debug_small_motif_counters.restype = None
     L.ribbit_debug_small_motif_counters.argtypes = [C.POINTER(C.c_int64 * 2)]
     L.ribbit_hip_small_motifs.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.ribbit_hip_seed_best_rows.argtypes = [vp, vp, vp, vp]
     L.ribbit_debug_set_merge_min_range.restype = None
     L.ribbit_debug_set_merge_min_range.argtypes = [C.c_size_t]
     L.ribbit_host_longest_runs.argtypes = [C.POINTER(ScanParams), i64, vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp]
@@ -313,6 +314,7 @@ def load_library():
     L.ribbit_hip_repeat_sequences.argtypes = [vp, C.c_char_p, vp, C.c_size_t, i32, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.ribbit_host_repeat_sequences.argtypes = [C.c_char_p, C.c_char_p, i64, vp, C.c_size_t, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.ribbit_hip_debug_set_repeat_text_budget.argtypes = [vp, C.c_size_t]
+    L.ribbit_hip_debug_set_small_record_capacity.argtypes = [vp, C.c_size_t]
     L.ribbit_bed_intervals.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.ribbit_intervals_free.restype = None
     L.ribbit_intervals_free.argtypes = [vp]
@@ -1466,6 +1468,16 @@ class Scanner:
         self._check(self._L.ribbit_hip_seed_longest_runs(self._h, C.byref(p), C.byref(n)))
         return _copy(p.value, n.value, np.dtype("<i4"))
 
+    def seed_best_rows(self, refine_params=None):
+        """ribbit_hip_seed_best_rows: per dispatched seed the window start mostFrequentLongerMotif selects (GPU), -1 where it is not asked"""
+        rp = refine_params
+        if rp is None:
+            rp = RefineParams()
+            self._L.ribbit_refine_params_default(C.byref(rp), self.params.min_motif, self.params.max_motif)
+        p, n = C.c_void_p(), C.c_size_t()
+        self._check(self._L.ribbit_hip_seed_best_rows(self._h, C.byref(rp), C.byref(p), C.byref(n)))
+        return _copy(p.value, n.value, np.dtype("<i4"))
+
     def refine_jobs(self, refine_params=None):
         rp = refine_params
         if rp is None:
@@ -1615,6 +1627,10 @@ class Scanner:
     def debug_set_repeat_text_budget(self, nbytes: int) -> None:
         """the text budget of one ribbit_hip_repeat_sequences call in bytes (0: the default, 64 MiB)"""
         self._check(self._L.ribbit_hip_debug_set_repeat_text_budget(self._h, int(nbytes)))
+
+    def debug_set_small_record_capacity(self, records: int) -> None:
+        """records the arena of small_motifs holds (0 = automatic); seeds that find it full get flags 2 and go to the host twin"""
+        self._check(self._L.ribbit_hip_debug_set_small_record_capacity(self._h, int(records)))
 
     def adopt_dispatch(self, seeds) -> None:
         """ribbit_hip_adopt_dispatch: this handle (same record loaded) refines a slice of another handle's dispatch list"""

@@ -130,7 +130,8 @@ int build_small_motifs(RibbitHandle *h, const RibbitRefineParams &prm, hipStream
         // room for four records a seed (0.43 on average on the simulated 20-Mbp record: early reports, the one reported
         // survivor, and all classes only for the seeds with two or more) and a million more; a seed that finds the arena
         // full is left to the host
-        const size_t cap = std::min<size_t>(4 * n + (1u << 20), 0x7fffffffu);
+        // (ribbit_hip_debug_set_small_record_capacity: a smaller arena, for the tests of that path)
+        const size_t cap = std::min<size_t>(h->debug_small_record_cap ? h->debug_small_record_cap : 4 * n + (1u << 20), 0x7fffffffu);
         if ((rc = h->d_sym.ensure((size_t)h->length + 16)) || (rc = h->d_small_head.ensure(4 * n)) ||
             (rc = h->d_small_records.ensure(4 * cap)) || (rc = h->d_small_count.ensure(4)))
             return rc;
@@ -442,6 +443,17 @@ int ribbit_hip_seed_longest_runs(RibbitHandle *h, const int32_t **out, size_t *n
     return RIBBIT_OK;
 }); }
 
+int ribbit_hip_seed_best_rows(RibbitHandle *h, const RibbitRefineParams *prm, const int32_t **out, size_t *n) { return guarded("the consensus rows", [&]() -> int {
+    if (!h || !prm || !out || !n) return fail(RIBBIT_E_ARG, "null argument");
+    if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
+    h->rec.best_rows_valid = false;            // depends on prm's threshold
+    int rc = build_best_rows(h, *prm);
+    if (rc) return rc;
+    *out = h->best_rows.data();
+    *n = h->best_rows.size();
+    return RIBBIT_OK;
+}); }
+
 int ribbit_hip_ssw_passes(RibbitHandle *h, const RibbitAlignJob *jobs, size_t n, const char *motif_pool, size_t pool_len,
                           int32_t mask_len, RibbitSswEnds *out) { return guarded("the alignments", [&]() -> int {
     if (!h || (n && (!jobs || !out || !motif_pool))) return fail(RIBBIT_E_ARG, "null argument");
@@ -664,6 +676,13 @@ void ribbit_debug_alignment_counters(int64_t out[3]) {
     long a = 0, b = 0, c = 0;
     rb::alignment_counters(a, b, c);
     out[0] = a; out[1] = b; out[2] = c;
+}
+
+int ribbit_hip_debug_set_small_record_capacity(RibbitHandle *h, size_t records) {
+    if (!h) return fail(RIBBIT_E_ARG, "null handle");
+    h->debug_small_record_cap = records;
+    h->rec.small_valid = false;            // the table of the loaded record was made with the old capacity
+    return RIBBIT_OK;
 }
 
 void ribbit_debug_small_motif_counters(int64_t out[2]) {

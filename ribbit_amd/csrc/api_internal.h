@@ -74,7 +74,7 @@ int fail(int code, const char *fmt, ...);
 // `what` names the operation in the message.  Not guarded, because all they do is check arguments and read or write plain
 // fields of the handle or of globals: ribbit_hip_abi_version, ribbit_hip_device_count (a count, not a status), ribbit_hip_set_stream,
 // ribbit_hip_set_timing, ribbit_hip_set_host_threads, ribbit_hip_debug_set_event_capacity, ribbit_hip_debug_set_scan_split,
-// ribbit_hip_debug_last_scan_split, ribbit_hip_debug_set_repeat_text_budget, ribbit_hip_refine_met_empty_query,
+// ribbit_hip_debug_last_scan_split, ribbit_hip_debug_set_repeat_text_budget, ribbit_hip_debug_set_small_record_capacity, ribbit_hip_refine_met_empty_query,
 // ribbit_hip_guard_hits, ribbit_host_debug_thread_faults, ribbit_hip_last_event_count, ribbit_hip_plane_words, ribbit_hip_last_error, ribbit_hip_host_free and the
 // other *_free functions, ribbit_*_params_default, the ribbit_debug_* counter readers and setters; and ribbit_hip_close, which is
 // `delete` (a destructor does not throw).  A team of threads hands an exception of any part to its caller (host_threads.h); the
@@ -345,6 +345,7 @@ struct RibbitHandle {
     rb::PairLaunch pair{};                // the perfect scan in flight (perfect_begin .. perfect_finish)
     bool pair_pending = false;
     size_t debug_first_cap = 0;           // ribbit_hip_debug_set_event_capacity: first guess of the event capacity (tests of the overflow path)
+    size_t debug_small_record_cap = 0;    // ribbit_hip_debug_set_small_record_capacity: records of the small-motif arena (0 = 4 n + 2^20)
     int32_t debug_split[RIBBIT_SCAN_KERNELS] = {};   // ribbit_hip_debug_set_scan_split: motifs per block of each scan kernel (0 = automatic)
     bool counters_clean = false;          // pb.d_counters zeroed by the pack kernel and not used since
     bool copy_pending = false;            // result copies enqueued but not yet waited for (ribbit_hip_scan_perfect_end with wait = 0)

@@ -696,6 +696,19 @@ int ribbit_hip_adopt_dispatch(RibbitHandle *h, const RibbitSeed *seeds, size_t n
     if (!h || (n && !seeds)) return fail(RIBBIT_E_ARG, "null argument");
     if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
     if (h->pair_pending || h->copy_pending) return fail(RIBBIT_E_STATE, "a perfect scan is in flight on this handle");
+    // The scans of the seeds index with what a seed says, unchecked: seed_longest_run_kernel reads words start >> 5 .. (end - 1) >> 5
+    // of plane mlen - min_motif (the planes have length / 32 + 1 words and more, one per motif of the handle), small_motifs_kernel,
+    // long_motif_rows_kernel and first_n_cut read one symbol / one N bit per position from max(start, 0) to below min(end + mlen,
+    // length), and a long-motif seed without a scoring row takes its motif from positions 0 .. mlen - 1.  So, before anything on
+    // the handle changes (include/ribbit_hip.h states the rule):
+    for (size_t i = 0; i < n; ++i) {
+        const RibbitSeed &s = seeds[i];
+        if (s.start < 0 || s.end < s.start || (int64_t)s.end > h->length)
+            return fail(RIBBIT_E_ARG, "seed %zu of the adopted list: [%d, %d) is not a range of the record's %lld bases", i, (int)s.start, (int)s.end, (long long)h->length);
+        if (s.mlen < h->params.min_motif || s.mlen > h->params.max_motif || (int64_t)s.mlen > h->length)
+            return fail(RIBBIT_E_ARG, "seed %zu of the adopted list: motif length %d is outside the handle's %d..%d or beyond the record's %lld bases", i,
+                        (int)s.mlen, (int)h->params.min_motif, (int)h->params.max_motif, (long long)h->length);
+    }
     int rc;
     if ((rc = bind_device(h))) return rc;
     if ((rc = ensure_host_planes(h))) return rc;

@@ -62,6 +62,8 @@ def lib():
         L.rbo_calls.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         L.rbo_dispatch.restype = C.c_int64
         L.rbo_dispatch.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.rbo_set_dispatch.restype = C.c_int
+        L.rbo_set_dispatch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.rbo_refine_params_default.restype = None
         L.rbo_refine_params_default.argtypes = [C.POINTER(RefineParams), C.c_int, C.c_int]
         L.rbo_refine_jobs.restype = C.c_int64
@@ -180,6 +182,14 @@ class Oracle:
         p = C.c_void_p()
         n = self._L.rbo_dispatch(self._h, C.byref(p))
         return _copy(p.value, n, SEED_DT)
+
+    def set_dispatch(self, seeds):
+        """rbo_set_dispatch: the dispatch list becomes `seeds` (SEED_DT; after run_all()); ValueError, and the list unchanged, for
+        a seed the refinement half cannot index.  Returns self."""
+        d = np.ascontiguousarray(seeds, dtype=SEED_DT)
+        if self._L.rbo_set_dispatch(self._h, d.ctypes.data, len(d)) != 0:
+            raise ValueError("rbo_set_dispatch: a seed outside 0 <= start <= end <= length or m_lo <= mlen <= min(m_hi, length)")
+        return self
 
     def refine_jobs(self, params=None):
         """(jobs array, motif pool bytes); needs run_dispatch() first"""

@@ -5,6 +5,7 @@ import pytest
 
 import pyref
 import ribbit_amd
+import seed_scan_contract
 from cases import edge_cases, simulated_cases
 from oracle_lib import Oracle
 
@@ -49,6 +50,9 @@ def _seed_table_checks(sc, seq):
         assert n_cls >= 0 and first + n_early + n_cls <= len(rec)      # 0 or 1: at most one class will be reported at the seed's end
         finals = rec[first + n_early:first + n_early + n_cls]
         assert len(set(int(c) for c in finals[:, 0])) == n_cls  # one record per rotation class
+    # ... and their content is possibleMotifs as tests/seed_scan_contract.py states it: every flag, count and record
+    case = {"name": "dispatch", "seq": seq, "m_lo": int(sc.params.min_motif), "m_hi": int(sc.params.max_motif), "seeds": d}
+    seed_scan_contract.assert_table_matches(case, head, rec, sc.seed_longest_runs())
     before = ribbit_amd.small_motif_counters()
     sc.refine_bed("x")
     after = ribbit_amd.small_motif_counters()
