@@ -964,6 +964,32 @@ int ribbit_host_merge_chunks(const RibbitScanParams *params, int64_t length,
 int ribbit_hip_debug_pair_events(RibbitHandle *h, const uint64_t *events, size_t n, int64_t length, RibbitRun *runs, size_t runs_cap,
                                  size_t *n_runs, uint32_t *flags);
 
+/* Test hook: the same pairing on events placed where the caller says.  events holds 64 regions of region_cap words each, laid out
+ * as a scan leaves them (the chunk of one (motif, tile) contiguous inside one region, chunks in any order); counters holds the 64
+ * region counters as the scan would have left them (a value above region_cap means the region overflowed: the kernels read its
+ * first region_cap events).  The motif range is the handle's; no record needs to be loaded.  own_lo / own_hi / pos_offset as for
+ * ribbit_hip_scan_perfect_chunk.  The caller provides the four buffers of `out`; the call fills
+ *   runs       min(status[1], runs_cap, 32 * region_cap) slots, place holders included, ordered by (motif, start);
+ *   halves     min(status[2], halves_cap, 2 * motifs) half records, in no particular order;
+ *   status     PAIR_FLAGS, PAIR_TOTAL, PAIR_HALVES (device_planes.h);   published: the 64 counters the GPU published;
+ * and then, from the same events and counters, what the host-pairing form (ribbit_hip_perfect_runs_partial) works from:
+ *   dense      the regions concatenated in region order, each cut at region_cap: min(summary, dense_cap) events;
+ *   summary / overflow   the number of events kept, and whether any region overflowed;
+ *   table      entry (motif - min_motif) * ntile + tile = {index of the chunk's first event in dense + 1, index past its last},
+ *              low word first, 0 = no chunk; ntile = length / 16384 + 1; min(motifs * ntile, table_cap) entries;
+ *   table_status         bit 0 malformed event, bit 1 a (motif, tile) with two chunks. */
+typedef struct RibbitDebugPairing {
+    RibbitRun *runs; size_t runs_cap;
+    RibbitRun *halves; size_t halves_cap;
+    uint64_t *dense; size_t dense_cap;
+    uint64_t *table; size_t table_cap;
+    uint32_t status[3];
+    uint32_t published[64];
+    uint32_t summary, overflow, table_status;
+} RibbitDebugPairing;
+int ribbit_hip_debug_pair_events_sharded(RibbitHandle *h, const uint64_t *events, const uint32_t *counters, size_t region_cap,
+                                         int64_t length, int64_t own_lo, int64_t own_hi, int64_t pos_offset, RibbitDebugPairing *out);
+
 /* Test hook: the first guess of the event-buffer capacity of the scans (0 = automatic).  A guess that is too small
  * makes a scan overflow its regions, after which it is sized for the fullest region and run again. */
 int ribbit_hip_debug_set_event_capacity(RibbitHandle *h, size_t events);

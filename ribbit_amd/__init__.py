@@ -70,7 +70,7 @@ ABI_SYMBOLS = [
     "ribbit_hip_xa_words",
     "ribbit_host_perfect_runs_from_events", "ribbit_runs_free", "ribbit_hip_perfect_runs_partial",
     "ribbit_hip_scan_perfect_chunk", "ribbit_hip_host_register", "ribbit_hip_host_unregister",
-    "ribbit_hip_set_host_threads", "ribbit_hip_ssw_passes", "ribbit_hip_ssw_align_jobs", "ribbit_hip_set_timing", "ribbit_hip_debug_set_event_capacity", "ribbit_hip_debug_set_scan_split", "ribbit_hip_debug_last_scan_split", "ribbit_hip_debug_pair_events", "ribbit_hip_scan_perfect_begin", "ribbit_hip_scan_perfect_end", "ribbit_hip_scan_perfect_wait", "ribbit_hip_scan_perfect_end_device",
+    "ribbit_hip_set_host_threads", "ribbit_hip_ssw_passes", "ribbit_hip_ssw_align_jobs", "ribbit_hip_set_timing", "ribbit_hip_debug_set_event_capacity", "ribbit_hip_debug_set_scan_split", "ribbit_hip_debug_last_scan_split", "ribbit_hip_debug_pair_events", "ribbit_hip_debug_pair_events_sharded", "ribbit_hip_scan_perfect_begin", "ribbit_hip_scan_perfect_end", "ribbit_hip_scan_perfect_wait", "ribbit_hip_scan_perfect_end_device",
     "ribbit_hip_stage_calls_chunk", "ribbit_hip_xa_words_strided", "ribbit_host_merge_chunks",
     "ribbit_hip_mask_record", "ribbit_host_mask_record", "ribbit_bed_intervals", "ribbit_intervals_free",
     "ribbit_hip_repeat_sequences", "ribbit_host_repeat_sequences", "ribbit_hip_debug_set_repeat_text_budget", "ribbit_hip_debug_set_small_record_capacity",
@@ -118,6 +118,14 @@ class Nearest(C.Structure):
     """RibbitNearest: what record_nearest finds for one query (include/ribbit_hip.h; kind 0: apart, 1: over, 2: inside); NEAREST_DT is
     the same record for numpy."""
     _fields_ = [(n, C.c_int32) for n in ("kind", "hit", "left", "left_dist", "right", "right_dist")]
+
+
+class DebugPairing(C.Structure):
+    """RibbitDebugPairing: the caller's buffers and the words ribbit_hip_debug_pair_events_sharded fills (include/ribbit_hip.h)."""
+    _fields_ = [("runs", C.c_void_p), ("runs_cap", C.c_size_t), ("halves", C.c_void_p), ("halves_cap", C.c_size_t),
+                ("dense", C.c_void_p), ("dense_cap", C.c_size_t), ("table", C.c_void_p), ("table_cap", C.c_size_t),
+                ("status", C.c_uint32 * 3), ("published", C.c_uint32 * 64),
+                ("summary", C.c_uint32), ("overflow", C.c_uint32), ("table_status", C.c_uint32)]
 
 
 class RefineParams(C.Structure):
@@ -290,6 +298,7 @@ def load_library():
     L.ribbit_hip_debug_set_scan_split.argtypes = [vp, i32, i32]
     L.ribbit_hip_debug_last_scan_split.argtypes = [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.ribbit_hip_debug_pair_events.argtypes = [vp, vp, C.c_size_t, i64, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]
+    L.ribbit_hip_debug_pair_events_sharded.argtypes = [vp, vp, vp, C.c_size_t, i64, i64, i64, i64, C.POINTER(DebugPairing)]
     L.ribbit_hip_ssw_passes.argtypes = [vp, vp, C.c_size_t, C.c_char_p, C.c_size_t, i32, vp]
     L.ribbit_hip_ssw_align_jobs.argtypes = [vp, vp, C.c_size_t, C.c_char_p, C.c_size_t, i32, vp, vp, C.c_size_t, vp, vp]
     L.ribbit_hip_scan_perfect_begin.argtypes = [vp, i64, i64, i64]
@@ -1379,6 +1388,28 @@ class Scanner:
         n, flags = C.c_size_t(), C.c_uint32()
         self._check(self._L.ribbit_hip_debug_pair_events(self._h, ev.ctypes.data, len(ev), length, runs.ctypes.data, len(runs), C.byref(n), C.byref(flags)))
         return runs[:min(n.value, len(runs))], flags.value
+
+    def debug_pair_events_sharded(self, events: np.ndarray, counters: np.ndarray, region_cap: int, length: int,
+                                  own_lo: int = 0, own_hi: int = 2 ** 63 - 1, pos_offset: int = 0) -> dict:
+        """The device-side pairing, and the legacy compaction and chunk table, on events placed by the caller: `events` holds 64 regions
+        of region_cap words, `counters` the 64 region counters (they may exceed region_cap).  -> dict: runs (every slot, place holders
+        included), halves, flags, total, n_halves, published (64 counters), dense, summary, overflow, table ((motifs, ntile, 2) of
+        {first + 1, end}), table_status."""
+        ev = np.ascontiguousarray(events, dtype="<u8").reshape(-1)
+        cnt = np.ascontiguousarray(counters, dtype="<u4").reshape(-1)
+        assert region_cap >= 1 and len(ev) == 64 * region_cap and len(cnt) == 64
+        nm, ntile = self.params.max_motif - self.params.min_motif + 1, length // 16384 + 1
+        runs, halves = np.zeros(32 * region_cap, RUN_DT), np.zeros(2 * nm, RUN_DT)
+        dense, table = np.zeros(len(ev), "<u8"), np.zeros(nm * ntile, "<u8")
+        out = DebugPairing(runs.ctypes.data, len(runs), halves.ctypes.data, len(halves), dense.ctypes.data, len(dense), table.ctypes.data, len(table))
+        self._check(self._L.ribbit_hip_debug_pair_events_sharded(self._h, ev.ctypes.data, cnt.ctypes.data, region_cap, length, own_lo, own_hi,
+                                                                 pos_offset, C.byref(out)))
+        flags, total, n_halves = (int(x) for x in out.status)
+        return {"runs": runs[:min(total, len(runs))], "halves": halves[:min(n_halves, len(halves))], "flags": flags, "total": total,
+                "n_halves": n_halves, "published": np.array(out.published, dtype="<u4"), "dense": dense[:min(out.summary, len(dense))],
+                "summary": int(out.summary), "overflow": int(out.overflow),
+                "table": np.stack((table & np.uint64(0xFFFFFFFF), table >> np.uint64(32)), axis=-1).astype("<u4").reshape(nm, ntile, 2),
+                "table_status": int(out.table_status)}
 
     def debug_set_event_capacity(self, events: int) -> None:
         self._check(self._L.ribbit_hip_debug_set_event_capacity(self._h, events))

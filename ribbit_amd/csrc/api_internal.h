@@ -185,7 +185,7 @@ inline double now_ms() {
 enum Stage { STAGE_NONE = 0, STAGE_PERFECT = 1, STAGE_SUBST = 2, STAGE_ANCHORED = 3 };      // how far the seed lists have come (rec.stage_done)
 
 // What the device-side pairing of one scan's events works in (api_events.cpp: pair_prepare sizes it, enqueue_pairing uses it):
-// the handle's, and ribbit_hip_debug_pair_events' own.
+// the handle's, and the own ones of ribbit_hip_debug_pair_events and ribbit_hip_debug_pair_events_sharded.
 struct PairBufs {
     DevBuf<uint32_t> d_counters;           // the scan's region counters (also zeroed by the pack kernel)
     DevBuf<uint64_t> d_pair_table;

@@ -280,6 +280,50 @@ int ribbit_hip_debug_pair_events(RibbitHandle *h, const uint64_t *events, size_t
     return RIBBIT_OK;
 }); }
 
+int ribbit_hip_debug_pair_events_sharded(RibbitHandle *h, const uint64_t *events, const uint32_t *counters, size_t region_cap,
+                                         int64_t length, int64_t own_lo, int64_t own_hi, int64_t pos_offset, RibbitDebugPairing *out) {
+    return guarded("the pairing of the events", [&]() -> int {
+    if (!h || !events || !counters || !out) return fail(RIBBIT_E_ARG, "null argument");
+    if ((out->runs_cap && !out->runs) || (out->halves_cap && !out->halves) || (out->dense_cap && !out->dense) || (out->table_cap && !out->table))
+        return fail(RIBBIT_E_ARG, "null argument");
+    if (length < 0 || region_cap < 1 || region_cap * rb::EV_SHARDS > ((size_t)1 << 24)) return fail(RIBBIT_E_ARG, "bad size");
+    if (own_lo < 0 || own_hi < own_lo) return fail(RIBBIT_E_ARG, "bad own range");
+    int rc;
+    if ((rc = bind_device(h))) return rc;
+    rb::PairLaunch pr{};
+    PairBufs pb;
+    if ((rc = pair_prepare(h, pb, length, own_lo, own_hi, pos_offset, pr))) return rc;
+    pr.region_cap = (uint32_t)region_cap;
+    const size_t cap = region_cap * rb::EV_SHARDS, entries = (size_t)pr.nm * pr.ntile;
+    DevBuf<uint64_t> d_ev, d_dense;                                     // d_dense: the run records, then the dense stream (as the handle's)
+    if ((rc = d_ev.ensure(cap)) || (rc = d_dense.ensure(cap))) return rc;
+    std::vector<uint32_t> words(rb::EV_COUNTER_WORDS, 0);
+    for (int t = 0; t < rb::EV_SHARDS; ++t) words[(size_t)t * rb::EV_COUNTER_STRIDE] = counters[t];
+    HIP_TRY(hipMemcpy(d_ev.p, events, cap * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(pb.d_counters.p, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if ((rc = enqueue_pairing(pb, pr, d_ev.p, d_dense.p, cap, h->stream))) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    std::copy(pb.h_pub.p, pb.h_pub.p + rb::EV_SHARDS, out->published);
+    std::copy(pb.h_pub.p + rb::EV_SHARDS, pb.h_pub.p + rb::EV_SHARDS + 3, out->status);
+    const size_t n_runs = std::min({(size_t)out->status[rb::PAIR_TOTAL], out->runs_cap, cap / 2});
+    const size_t n_halves = std::min({(size_t)out->status[rb::PAIR_HALVES], out->halves_cap, 2 * (size_t)pr.nm});
+    if (n_runs) HIP_TRY(hipMemcpy(out->runs, d_dense.p, n_runs * sizeof(RibbitRun), hipMemcpyDeviceToHost));
+    if (n_halves) HIP_TRY(hipMemcpy(out->halves, pb.d_halves.p, n_halves * sizeof(RibbitRun), hipMemcpyDeviceToHost));
+    // the legacy pair, as collect_perfect_events runs it
+    rb::launch_compact_events(d_ev.p, (uint32_t)cap, pb.d_counters.p, d_dense.p, h->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(rb::launch_chunk_table(d_dense.p, pb.d_counters.p, pr.m_lo, pr.nm, pr.ntile, pr.tile_bases, pb.d_pair_table.p, pb.d_pair_status.p, h->stream));
+    HIP_TRY(hipMemcpyAsync(words.data(), pb.d_counters.p, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(&out->table_status, pb.d_pair_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    out->summary = words[rb::EV_SUMMARY];
+    out->overflow = words[rb::EV_SUMMARY + 1];
+    const size_t n_dense = std::min({(size_t)out->summary, out->dense_cap, cap}), n_table = std::min(entries, out->table_cap);
+    if (n_dense) HIP_TRY(hipMemcpy(out->dense, d_dense.p, n_dense * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (n_table) HIP_TRY(hipMemcpy(out->table, pb.d_pair_table.p, n_table * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return RIBBIT_OK;
+}); }
+
 int ribbit_host_perfect_runs_from_events(const RibbitScanParams *params, size_t nparts, const uint64_t *events,
                                          const uint64_t *counts, RibbitRun **runs, size_t *n) { return guarded("the pairing of the events", [&]() -> int {
     if (!params || !counts || !runs || !n) return fail(RIBBIT_E_ARG, "null argument");
