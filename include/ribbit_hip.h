@@ -769,6 +769,79 @@ int ribbit_base_windows_text(const char *name, int64_t length, int32_t window, c
                              char **text, size_t *len);
 
 /*
+ * ---- PCR primers in the flanks of chosen rows --------------------------------------------------------------------------
+ * For every target (s, e), usually a row of the best selection, a forward primer in the flank to its left and a reverse primer
+ * in the flank to its right, each chosen on its own: the candidate oligos of either flank are all of its substrings of
+ * min_length .. max_length bases, a candidate is admissible or not, and the admissible one with the least penalty is taken.
+ * Everything is integer arithmetic, so that the GPU, the host twin and this statement can be compared exactly.  The pair is
+ * not optimised together and nothing is checked for dimers, hairpins or priming elsewhere in the genome.
+ *   Windows:    the arithmetic of the composition above, in 64-bit, with the flank F = params->flank:
+ *                 s' = min(max(s, 0), L)    e' = min(max(e, s'), L)    lo = max(s' - F, 0)    hi = min(e' + F, L)
+ *               A left candidate is [p, p + k) with lo <= p and p + k <= s', a right candidate [q, q + k) with e' <= q and
+ *               q + k <= hi; min_length <= k <= max_length.  The left primer is the candidate's bases, the right primer their
+ *               reverse complement.  All rules below are the same on either strand and are stated on the forward strand; the
+ *               3' position of a left candidate is p + k - 1, that of a right candidate is q.
+ *   Blocked:    a position is blocked when its byte is of kind `other` (any byte but ACGTacgt) or when a non-empty row of
+ *               `intervals`, clipped as the mask clips them, holds it: all rows of the record, not only the targets.
+ *   Admissible: (1) no position of the candidate is blocked; (2) with g its C and G bases, 100 g >= gc_min_percent k and
+ *               100 g <= gc_max_percent k; (3) no max_run + 1 equal consecutive bases inside it; (4) if gc_clamp is set, the
+ *               base at its 3' position is C or G; (5) tm_min <= Tm <= tm_max.
+ *   Tm:         SantaLucia's unified nearest-neighbour parameters (1998) in fixed point, dH in 100 cal/mol and dS in
+ *               0.1 cal/(K mol), per step of two adjacent bases read 5' to 3' on the forward strand:
+ *                 AA TT  -79 -222    AT  -72 -204    TA  -72 -213    CA TG  -85 -227    GT AC  -84 -224
+ *                 CT AG  -78 -210    GA TC  -82 -222    CG -106 -272    GC  -98 -244    GG CC  -80 -199
+ *               and per terminal base (the first and the last) 23, 41 for A or T and 1, -28 for C or G.  With H and S the
+ *               sums over the k - 1 steps and both terminals,
+ *                 S' = S - 11 (k - 1) - 362        Tm = (10000 H) / S' - 2732      in tenths of a degree Celsius
+ *               -11 per step is the salt correction at 50 mM Na+ (0.368 ln 0.05 = -1.10), -362 is R ln(50 nM / 4) = -36.2.
+ *               H and S' are negative for every k >= 2, and the division truncates their positive quotient.
+ *   Choice:     penalty = |Tm - tm_opt| + 10 |k - opt_length|.  Of the admissible candidates of a side, the one with the
+ *               least (penalty, distance, k) in that order, the distance to the target being s' - (p + k) on the left and
+ *               q - e' on the right.  No two candidates of a side share that triple.
+ */
+#define RIBBIT_PRIMER_MAX_FLANK 1000
+#define RIBBIT_PRIMER_MAX_LENGTH 32
+typedef struct {
+    int32_t flank;                            /* 200;  0 .. RIBBIT_PRIMER_MAX_FLANK */
+    int32_t min_length, max_length;           /* 18, 25;  2 <= min_length <= max_length <= RIBBIT_PRIMER_MAX_LENGTH */
+    int32_t opt_length;                       /* 20;  min_length .. max_length */
+    int32_t tm_min, tm_opt, tm_max;           /* 570, 600, 630, tenths of a degree;  0 <= tm_min <= tm_opt <= tm_max <= 2000 */
+    int32_t gc_min_percent, gc_max_percent;   /* 40, 60;  0 <= gc_min_percent <= gc_max_percent <= 100 */
+    int32_t max_run;                          /* 4;  1 or more */
+    int32_t gc_clamp;                         /* 1;  0 or 1 */
+} RibbitPrimerParams;
+void ribbit_primer_params_default(RibbitPrimerParams *params);
+typedef struct {
+    int32_t start, length;                    /* the candidate [start, start + length) on the forward strand; start -1 and */
+    int32_t tm, penalty;                      /* every other field 0 when the side has no admissible candidate */
+    int32_t bases_lo, bases_hi;               /* its forward-strand bases, A 0, C 1, G 2, T 3: base j at bits 2 j of the 64 bits hi : lo */
+} RibbitPrimer;
+typedef struct {
+    RibbitPrimer left, right;
+    int32_t left_candidates, right_candidates;   /* the admissible candidates of either side */
+} RibbitRowPrimers;                           /* 56 bytes */
+/* The loaded record's n_targets targets (at most INT32_MAX) against the coverage of its n rows `intervals`, on the GPU, from
+ * the bit planes the scans read: *rows is one record per target, in the order given, of handle-owned page-locked memory, valid
+ * until the handle's next primer call, load or close.  The coverage bitmap of the rows is the one the mask, the loci, the
+ * density, the overlap and the composition use.  n_targets = 0, n = 0 and L = 0 are no errors.  A parameter outside its range
+ * above: RIBBIT_E_ARG, and the error text names the field; before a load: RIBBIT_E_STATE. */
+int ribbit_hip_record_primers(RibbitHandle *h, const int32_t *intervals, size_t n, const int32_t *targets, size_t n_targets,
+                              const RibbitPrimerParams *params, const RibbitRowPrimers **rows);
+/* Host-only twin (no GPU), from the bytes of `sequence` (0 <= length < 2^31), every candidate computed on its own: *rows
+ * malloc'ed, release with ribbit_primers_free(). */
+int ribbit_host_record_primers(const char *sequence, int64_t length, const int32_t *intervals, size_t n, const int32_t *targets,
+                               size_t n_targets, const RibbitPrimerParams *params, RibbitRowPrimers **rows);
+void ribbit_primers_free(RibbitRowPrimers *rows);
+/* The targets' BED rows with their primers appended (host only): line i of bed_text, byte for byte, then 11 columns, each
+ * behind a tab, and a newline: 22 columns.  The 11 are: the left primer's start, end, sequence 5' to 3' and Tm (tenths as
+ * d.d); the right primer's start, end, sequence 5' to 3' (the reverse complement of its forward-strand bases) and Tm; the
+ * product's size, right end - left start; the admissible candidates on the left and on the right.  A side without a primer
+ * (start < 0) has "." in its four columns, and the product is "." unless both sides have one.  bed_text: row i on line i (a last
+ * line without its newline counts).  A bed_text that does not have n lines, a primer of fewer than 1 or more than
+ * RIBBIT_PRIMER_MAX_LENGTH bases: RIBBIT_E_ARG.  *text malloc'ed, release with ribbit_text_free(). */
+int ribbit_bed_primers_text(const char *bed_text, size_t bed_len, const RibbitRowPrimers *rows, size_t n, char **text, size_t *len);
+
+/*
  * ---- streaming FASTA ingest ---------------------------------------------------------------------------------------
  * Replaces the reader loop of ribbit.cpp:269-280 (getline + `sequence += line` into one pageable std::string per
  * record).  The file is read in 16-MB blocks; line bodies are copied once, straight into a page-locked buffer

@@ -24,7 +24,8 @@ __all__ = ["RibbitHipError", "ScanParams", "Scanner", "library_path", "load_libr
            "COMPOUND_DT", "host_record_compounds", "class_labels", "compound_text",
            "INTERRUPTION_DT", "ROW_PURITY_DT", "bed_cigars", "host_record_interruptions", "interruption_text", "bed_purity_text",
            "Nearest", "NEAREST_DT", "host_record_nearest", "bed_nearest_text", "nearest_other_text",
-           "COMPOSITION_DT", "BASE_COUNTS_DT", "host_record_composition", "host_record_base_windows", "bed_composition_text", "base_windows_text"]
+           "COMPOSITION_DT", "BASE_COUNTS_DT", "host_record_composition", "host_record_base_windows", "bed_composition_text", "base_windows_text",
+           "PRIMERS_DT", "PrimerParams", "primer_params", "host_record_primers", "bed_primers_text"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -48,6 +49,8 @@ NEAREST_DT = np.dtype([(n, "<i4") for n in ("kind", "hit", "left", "left_dist", 
 COMPOSITION_DT = np.dtype([(n, "<i4") for n in ("a", "c", "g", "t", "other", "left", "left_gc", "left_other", "left_covered",
                                                  "right", "right_gc", "right_other", "right_covered")])      # RibbitRowComposition
 BASE_COUNTS_DT = np.dtype([(n, "<i4") for n in ("a", "c", "g", "t", "other")])      # RibbitBaseCounts
+PRIMERS_DT = np.dtype([(f"{side}_{n}", "<i4") for side in ("left", "right") for n in ("start", "length", "tm", "penalty", "bases_lo", "bases_hi")]
+                      + [("left_candidates", "<i4"), ("right_candidates", "<i4")])      # RibbitRowPrimers
 
 # every symbol include/ribbit_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -86,6 +89,7 @@ ABI_SYMBOLS = [
     "ribbit_hip_record_nearest", "ribbit_host_record_nearest", "ribbit_nearest_free", "ribbit_bed_nearest_text", "ribbit_nearest_other_text",
     "ribbit_hip_record_composition", "ribbit_hip_record_base_windows", "ribbit_host_record_composition", "ribbit_host_record_base_windows",
     "ribbit_composition_free", "ribbit_debug_composition_prefix_builds", "ribbit_bed_composition_text", "ribbit_base_windows_text",
+    "ribbit_primer_params_default", "ribbit_hip_record_primers", "ribbit_host_record_primers", "ribbit_primers_free", "ribbit_bed_primers_text",
 ]
 
 MASK_MODES = {"soft": 0, "hard": 1}     # RIBBIT_MASK_SOFT / RIBBIT_MASK_HARD
@@ -118,6 +122,13 @@ class Nearest(C.Structure):
     """RibbitNearest: what record_nearest finds for one query (include/ribbit_hip.h; kind 0: apart, 1: over, 2: inside); NEAREST_DT is
     the same record for numpy."""
     _fields_ = [(n, C.c_int32) for n in ("kind", "hit", "left", "left_dist", "right", "right_dist")]
+
+
+class PrimerParams(C.Structure):
+    """RibbitPrimerParams: what record_primers takes for a primer (include/ribbit_hip.h; Tm in tenths of a degree); primer_params()
+    fills one."""
+    _fields_ = [(n, C.c_int32) for n in ("flank", "min_length", "max_length", "opt_length", "tm_min", "tm_opt", "tm_max", "gc_min_percent", "gc_max_percent",
+                                         "max_run", "gc_clamp")]
 
 
 class DebugPairing(C.Structure):
@@ -380,6 +391,13 @@ def load_library():
     L.ribbit_debug_composition_prefix_builds.restype = i64
     L.ribbit_bed_composition_text.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.ribbit_base_windows_text.argtypes = [C.c_char_p, i64, i32, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_primer_params_default.argtypes = [C.POINTER(PrimerParams)]
+    L.ribbit_primer_params_default.restype = None
+    L.ribbit_hip_record_primers.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(PrimerParams), C.POINTER(vp)]
+    L.ribbit_host_record_primers.argtypes = [C.c_char_p, i64, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(PrimerParams), C.POINTER(vp)]
+    L.ribbit_primers_free.argtypes = [vp]
+    L.ribbit_primers_free.restype = None
+    L.ribbit_bed_primers_text.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
     _lib = L
     return L
 
@@ -910,6 +928,64 @@ def base_windows_text(name, length: int, window: int, windows) -> bytes:
     rc = L.ribbit_base_windows_text(raw, int(length), window, w.ctypes.data if len(w) else None, len(w), C.byref(text), C.byref(n))
     if rc != 0:
         raise RibbitHipError(f"ribbit_base_windows_text error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return C.string_at(text.value, n.value)
+    finally:
+        L.ribbit_text_free(text)
+
+
+def primer_params(**fields) -> PrimerParams:
+    """ribbit_primer_params_default with the given fields replaced, e.g. primer_params(flank=100, gc_clamp=0); the ranges are
+    checked by the calls that take it (include/ribbit_hip.h)"""
+    p = PrimerParams()
+    load_library().ribbit_primer_params_default(C.byref(p))
+    names = {n for n, _ in PrimerParams._fields_}
+    for name, value in fields.items():
+        if name not in names:
+            raise TypeError(f"RibbitPrimerParams has no field {name!r}")
+        if not -2**31 <= int(value) < 2**31:
+            raise ValueError(f"{name} {value} does not fit int32")
+        setattr(p, name, int(value))
+    return p
+
+
+def _primer_args(intervals, targets, params):
+    iv, tg = _pairs(intervals), _pairs(targets)
+    if params is None:
+        params = primer_params()
+    if not isinstance(params, PrimerParams):
+        raise TypeError("params: a PrimerParams (primer_params())")
+    return iv, tg, params
+
+
+def host_record_primers(sequence: bytes, intervals, targets, params: PrimerParams | None = None) -> np.ndarray:
+    """ribbit_host_record_primers: for every (start, end) target a forward primer in the flank to its left and a reverse primer in
+    the flank to its right, clear of every base that the rows `intervals` cover or that is not A, C, G or T -> a PRIMERS_DT array,
+    one record per target.  The contract is in include/ribbit_hip.h.  No GPU needed."""
+    L = load_library()
+    iv, tg, params = _primer_args(intervals, targets, params)
+    seq = bytes(sequence)
+    out = C.c_void_p()
+    rc = L.ribbit_host_record_primers(seq, len(seq), iv.ctypes.data if len(iv) else None, len(iv), tg.ctypes.data if len(tg) else None, len(tg),
+                                      C.byref(params), C.byref(out))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_host_record_primers error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return _copy(out.value, len(tg), PRIMERS_DT)
+    finally:
+        L.ribbit_primers_free(out)
+
+
+def bed_primers_text(bed, rows) -> bytes:
+    """ribbit_bed_primers_text: the lines of `bed` (the targets' BED rows, target i on line i), each with the primers of row i of
+    `rows` (record_primers) appended as 11 more columns."""
+    L = load_library()
+    text_in = bed.encode() if isinstance(bed, str) else bytes(bed)
+    rw = np.ascontiguousarray(np.asarray(rows, dtype=PRIMERS_DT).reshape(-1))
+    text, n = C.c_void_p(), C.c_size_t()
+    rc = L.ribbit_bed_primers_text(text_in, len(text_in), rw.ctypes.data if len(rw) else None, len(rw), C.byref(text), C.byref(n))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_bed_primers_text error {rc}: {L.ribbit_hip_last_error().decode()}")
     try:
         return C.string_at(text.value, n.value)
     finally:
@@ -1616,6 +1692,15 @@ class Scanner:
         out, n = C.c_void_p(), C.c_size_t()
         self._check(self._L.ribbit_hip_record_base_windows(self._h, window, C.byref(out), C.byref(n)))
         return _copy(out.value, n.value, BASE_COUNTS_DT)
+
+    def record_primers(self, intervals, targets, params: PrimerParams | None = None) -> np.ndarray:
+        """A forward and a reverse primer in the flanks of every target of the loaded record on the GPU, clear of the rows
+        `intervals` (ribbit_hip_record_primers); see host_record_primers"""
+        iv, tg, params = _primer_args(intervals, targets, params)
+        out = C.c_void_p()
+        self._check(self._L.ribbit_hip_record_primers(self._h, iv.ctypes.data if len(iv) else None, len(iv), tg.ctypes.data if len(tg) else None, len(tg),
+                                                      C.byref(params), C.byref(out)))
+        return _copy(out.value, len(tg), PRIMERS_DT)
 
     def record_best(self, intervals):
         """The loaded record's best non-overlapping rows on the GPU (ribbit_hip_record_best); see host_record_best"""

@@ -19,8 +19,9 @@
 //   api_interruptions.cpp  every row's CIGAR decoded into interruptions and the pure stretch (interruptions.hip), its host twin, the CIGARs of a BED text, both texts
 //   api_nearest.cpp     the nearest interval of a second set for every row, and the other way round (nearest.hip), its host twin, both texts
 //   api_composition.cpp the base counts of every row, its flanks and every window from the bit planes (composition.hip), their host twins, both texts
-// The last ten are the row outputs: their buffers are the handle's RowBufs `rows`, where all device work of a call is carved from
-// one buffer by the layout its .hip file states (kernels.h); the last five stage their inputs through stage_down, what their host
+//   api_primers.cpp     a forward and a reverse primer in the flanks of every target, from the bit planes and the rows' coverage (primers.hip), its host twin, the text
+// The last eleven are the row outputs: their buffers are the handle's RowBufs `rows`, where all device work of a call is carved from
+// one buffer by the layout its .hip file states (kernels.h); best, classes, compound, interruptions, nearest and primers stage their inputs through stage_down, what their host
 // sides share is below (hand_out, clipped_sorted_rows), what their kernels share is row_kernels.h, and the BED text they read and
 // write (the row format, the reader in pieces, the writer in pieces) is
 //   bed_text.h          a row's named fields, bed_read / bed_gather, BedLines, write_pieces / join_text, put_number
@@ -475,6 +476,7 @@ struct RibbitHandle {
         PinnedBuf<RibbitNearest> h_near;
         PinnedBuf<RibbitRowComposition> h_comp_rows;
         PinnedBuf<RibbitBaseCounts> h_comp_windows;
+        PinnedBuf<RibbitRowPrimers> h_primers;          // the targets' primers on their way up (api_primers.cpp)
         // the blocks' base counts | their prefix, which belongs to the record (rec.base_prefix_valid, api_composition.cpp)
         DevBuf<rb::BaseSums> d_comp_sums;
         size_t rep_budget = 0;           // text budget of one batch of repeat sequences in bytes (0: REPEAT_TEXT_BUDGET)

@@ -1,0 +1,269 @@
+// api_primers.cpp -- a forward and a reverse primer in the flanks of every target of a record (primers.hip); see api_internal.h
+// for the map of the files behind include/ribbit_hip.h.  The GPU form reads the bit planes the load packed and the coverage bitmap
+// the mask builds of the record's rows (build_coverage, api_mask.cpp), stages the targets through stage_down and runs on the handle's
+// stream; it keeps nothing between calls and leaves what the other row outputs keep (the bitmap's rows, the base prefix) as it
+// finds it.  The host twin works from the bytes of the sequence and computes every candidate on its own, base by base, without a
+// prefix, so that it states the contract a second time instead of repeating the kernel; the text needs no GPU.
+#include "bed_text.h"
+
+#include <tuple>
+
+namespace {
+
+constexpr size_t MAX_TARGETS = (size_t)INT32_MAX;
+static_assert(sizeof(RibbitRowPrimers) == 56 && sizeof(RibbitPrimer) == 24 && sizeof(RibbitPrimerParams) == 44, "14, 6 and 11 ints");
+constexpr RibbitPrimer NO_PRIMER{-1, 0, 0, 0, 0, 0};
+
+int check_params(const RibbitPrimerParams *p) {
+    if (!p) return fail(RIBBIT_E_ARG, "null argument");
+    if (p->flank < 0 || p->flank > RIBBIT_PRIMER_MAX_FLANK) return fail(RIBBIT_E_ARG, "flank %d is outside 0 .. %d", (int)p->flank, RIBBIT_PRIMER_MAX_FLANK);
+    if (p->max_length > RIBBIT_PRIMER_MAX_LENGTH) return fail(RIBBIT_E_ARG, "max_length %d is above %d", (int)p->max_length, RIBBIT_PRIMER_MAX_LENGTH);
+    if (p->min_length < 2 || p->min_length > p->max_length) return fail(RIBBIT_E_ARG, "min_length %d is outside 2 .. max_length %d", (int)p->min_length, (int)p->max_length);
+    if (p->opt_length < p->min_length || p->opt_length > p->max_length)
+        return fail(RIBBIT_E_ARG, "opt_length %d is outside min_length %d .. max_length %d", (int)p->opt_length, (int)p->min_length, (int)p->max_length);
+    if (p->tm_max > 2000) return fail(RIBBIT_E_ARG, "tm_max %d is above 2000", (int)p->tm_max);
+    if (p->tm_opt > p->tm_max) return fail(RIBBIT_E_ARG, "tm_opt %d is above tm_max %d", (int)p->tm_opt, (int)p->tm_max);
+    if (p->tm_min < 0 || p->tm_min > p->tm_opt) return fail(RIBBIT_E_ARG, "tm_min %d is outside 0 .. tm_opt %d", (int)p->tm_min, (int)p->tm_opt);
+    if (p->gc_max_percent > 100) return fail(RIBBIT_E_ARG, "gc_max_percent %d is above 100", (int)p->gc_max_percent);
+    if (p->gc_min_percent < 0 || p->gc_min_percent > p->gc_max_percent)
+        return fail(RIBBIT_E_ARG, "gc_min_percent %d is outside 0 .. gc_max_percent %d", (int)p->gc_min_percent, (int)p->gc_max_percent);
+    if (p->max_run < 1) return fail(RIBBIT_E_ARG, "max_run %d is below 1", (int)p->max_run);
+    if (p->gc_clamp != 0 && p->gc_clamp != 1) return fail(RIBBIT_E_ARG, "gc_clamp %d is neither 0 nor 1", (int)p->gc_clamp);
+    return RIBBIT_OK;
+}
+
+int check_args(const int32_t *intervals, size_t n, const int32_t *targets, size_t n_targets, const RibbitPrimerParams *params, const void *rows) {
+    if ((!intervals && n > 0) || (!targets && n_targets > 0) || !rows) return fail(RIBBIT_E_ARG, "null argument");
+    if (n > MAX_TARGETS) return fail(RIBBIT_E_ARG, "%zu intervals", n);
+    if (n_targets > MAX_TARGETS) return fail(RIBBIT_E_ARG, "%zu targets", n_targets);
+    return check_params(params);
+}
+
+// a target's two windows: the left candidates lie in [lo, s), the right ones in [e, hi)
+struct Flanks { int64_t lo, s, e, hi; };
+Flanks flanks_of(const int32_t *targets, size_t i, int32_t flank, int64_t length) {
+    const int64_t s = std::min(std::max<int64_t>(targets[2 * i], 0), length), e = std::min(std::max<int64_t>(targets[2 * i + 1], s), length);
+    return Flanks{std::max<int64_t>(s - flank, 0), s, e, std::min<int64_t>(e + flank, length)};
+}
+
+void no_primers(RibbitRowPrimers *rows, size_t n) {
+    for (size_t i = 0; i < n; ++i) rows[i] = RibbitRowPrimers{NO_PRIMER, NO_PRIMER, 0, 0};
+}
+
+int record_primers_impl(RibbitHandle *h, const int32_t *intervals, size_t n, const int32_t *targets, size_t n_targets, const RibbitPrimerParams *params,
+                        const RibbitRowPrimers **rows) {
+    if (!h) return fail(RIBBIT_E_ARG, "null handle");
+    int rc;
+    if ((rc = check_args(intervals, n, targets, n_targets, params, rows))) return rc;
+    if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
+    RibbitHandle::RowBufs &buf = h->rows;
+    if ((rc = buf.h_primers.ensure(std::max<size_t>(n_targets, 1), true))) return rc;
+    *rows = buf.h_primers.p;
+    if (n_targets == 0) return RIBBIT_OK;
+    const int64_t length = h->length;
+    if (length == 0) {      // (every flank is empty)
+        no_primers(buf.h_primers.p, n_targets);
+        return RIBBIT_OK;
+    }
+    if ((rc = bind_device(h))) return rc;
+    const rb::PrimerLayout at = rb::primers_layout((int64_t)n_targets);
+    if ((rc = buf.d_work.ensure(at.bytes, true))) return rc;
+    const StageSegment down{targets, 2 * n_targets * sizeof(int32_t)};
+    const uint8_t *d_targets = nullptr;
+    if ((rc = stage_down(h, &down, 1, &d_targets))) return rc;
+    if ((rc = build_coverage(h, intervals, n))) return rc;
+    HIP_TRY(rb::launch_primers(h->planes(), buf.d_mask_bits.p, reinterpret_cast<const int32_t *>(d_targets), (int64_t)n_targets, *params, buf.d_work.p,
+                               buf.d_work.cap, at, h->stream));
+    HIP_TRY(hipMemcpyAsync(buf.h_primers.p, buf.d_work.p + at.out, n_targets * sizeof(RibbitRowPrimers), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < n_targets; ++i) {
+        const RibbitRowPrimers &r = buf.h_primers.p[i];
+        const Flanks f = flanks_of(targets, i, params->flank, length);
+        const auto inside = [&](const RibbitPrimer &p, int64_t from, int64_t to) {
+            return p.start == -1 ? p.length == 0 : p.length >= params->min_length && p.length <= params->max_length && p.start >= from && (int64_t)p.start + p.length <= to;
+        };
+        if (!inside(r.left, f.lo, f.s) || !inside(r.right, f.e, f.hi) || r.left_candidates < (r.left.start >= 0) || r.right_candidates < (r.right.start >= 0))
+            return fail(RIBBIT_E_INTERNAL, "target %zu: a primer the GPU found lies outside its flank", i);
+    }
+    return RIBBIT_OK;
+}
+
+// ---- host twin: the bytes themselves, every candidate from scratch
+int code_of(unsigned char b) {      // A 0, C 1, G 2, T 3 in either case, -1 for every other byte
+    switch (b | 0x20) {
+        case 'a': return 0;
+        case 'c': return 1;
+        case 'g': return 2;
+        case 't': return 3;
+        default: return -1;
+    }
+}
+
+// SantaLucia 1998 as the contract tabulates it: dH in 100 cal/mol, dS in 0.1 cal/(K mol), by the step's two letters
+struct Step { char a, b; int32_t h, s; };
+constexpr Step kSteps[16] = {{'A', 'A', -79, -222}, {'T', 'T', -79, -222}, {'A', 'T', -72, -204}, {'T', 'A', -72, -213}, {'C', 'A', -85, -227}, {'T', 'G', -85, -227},
+                             {'G', 'T', -84, -224}, {'A', 'C', -84, -224}, {'C', 'T', -78, -210}, {'A', 'G', -78, -210}, {'G', 'A', -82, -222}, {'T', 'C', -82, -222},
+                             {'C', 'G', -106, -272}, {'G', 'C', -98, -244}, {'G', 'G', -80, -199}, {'C', 'C', -80, -199}};
+const Step &step_of(int a, int b) {
+    for (const Step &st : kSteps)
+        if (st.a == "ACGT"[a] && st.b == "ACGT"[b]) return st;
+    return kSteps[0];      // (not reached: the sixteen pairs are all there)
+}
+
+struct Candidate { bool ok; int32_t tm; };
+// [p, p + k) of the sequence, whose 3' base is the one at `three`
+Candidate candidate(const unsigned char *seq, const std::vector<uint8_t> &covered, int64_t p, int32_t k, int64_t three, const RibbitPrimerParams &prm) {
+    int32_t gc = 0, run = 0, h = 0, s = 0;
+    for (int64_t q = p; q < p + k; ++q) {
+        const int c = code_of(seq[q]);
+        if (c < 0 || covered[(size_t)q]) return {false, 0};
+        gc += c == 1 || c == 2;
+        run = q > p && c == code_of(seq[q - 1]) ? run + 1 : 1;
+        if (run > prm.max_run) return {false, 0};
+        if (q > p) {
+            const Step &st = step_of(code_of(seq[q - 1]), c);
+            h += st.h;
+            s += st.s;
+        }
+        if (q == p || q == p + k - 1) {
+            h += c == 1 || c == 2 ? 1 : 23;
+            s += c == 1 || c == 2 ? -28 : 41;
+        }
+    }
+    if (100 * gc < prm.gc_min_percent * k || 100 * gc > prm.gc_max_percent * k) return {false, 0};
+    const int c3 = code_of(seq[three]);
+    if (prm.gc_clamp && c3 != 1 && c3 != 2) return {false, 0};
+    s += -11 * (k - 1) - 362;
+    const int32_t tm = (int32_t)((10000 * (int64_t)h) / s) - 2732;      // (both negative: the quotient is positive, and / truncates)
+    return {tm >= prm.tm_min && tm <= prm.tm_max, tm};
+}
+
+// the best admissible candidate of the window [from, to) and their number
+int32_t side(const unsigned char *seq, const std::vector<uint8_t> &covered, int64_t from, int64_t to, bool right, const RibbitPrimerParams &prm, RibbitPrimer &best) {
+    best = NO_PRIMER;
+    int32_t found = 0;
+    int64_t best_distance = 0;
+    for (int64_t p = from; p < to; ++p)
+        for (int32_t k = prm.min_length; k <= prm.max_length && p + k <= to; ++k) {
+            const Candidate c = candidate(seq, covered, p, k, right ? p : p + k - 1, prm);
+            if (!c.ok) continue;
+            ++found;
+            const int32_t penalty = std::abs(c.tm - prm.tm_opt) + 10 * std::abs(k - prm.opt_length);
+            const int64_t distance = right ? p - from : to - (p + k);
+            if (best.start >= 0 && std::make_tuple(best.penalty, best_distance, best.length) <= std::make_tuple(penalty, distance, k)) continue;
+            uint64_t bases = 0;
+            for (int32_t j = 0; j < k; ++j) bases |= (uint64_t)code_of(seq[p + j]) << (2 * j);
+            best = RibbitPrimer{(int32_t)p, k, c.tm, penalty, (int32_t)(uint32_t)bases, (int32_t)(uint32_t)(bases >> 32)};
+            best_distance = distance;
+        }
+    return found;
+}
+
+int host_record_primers_impl(const char *sequence, int64_t length, const int32_t *intervals, size_t n, const int32_t *targets, size_t n_targets,
+                             const RibbitPrimerParams *params, RibbitRowPrimers **rows) {
+    int rc;
+    if ((rc = check_args(intervals, n, targets, n_targets, params, rows))) return rc;
+    if (length < 0 || length > (int64_t)INT32_MAX) return fail(RIBBIT_E_ARG, "a record of %lld bases", (long long)length);
+    if (!sequence && length > 0) return fail(RIBBIT_E_ARG, "bad sequence");
+    const unsigned char *seq = reinterpret_cast<const unsigned char *>(sequence);
+    std::vector<uint8_t> covered((size_t)length, 0);
+    const CoveredRuns runs(clipped_sorted_rows(length, intervals, n));
+    for (size_t k = 0; k < runs.start.size(); ++k) std::fill(covered.begin() + runs.start[k], covered.begin() + runs.end[k], 1);
+    Handed<RibbitRowPrimers> out;
+    if ((rc = hand_out<RibbitRowPrimers>(nullptr, n_targets, false, out))) return rc;
+    const RibbitPrimerParams prm = *params;
+    const unsigned threads = (unsigned)std::max<size_t>(1, std::min<size_t>(rb::host_thread_count(0), n_targets / 16));
+    rb::over_pieces(n_targets, threads, [&](size_t lo, size_t hi, unsigned) {
+        for (size_t i = lo; i < hi; ++i) {
+            const Flanks f = flanks_of(targets, i, prm.flank, length);
+            RibbitRowPrimers &r = out[i];
+            r.left_candidates = side(seq, covered, f.lo, f.s, false, prm, r.left);
+            r.right_candidates = side(seq, covered, f.e, f.hi, true, prm, r.right);
+        }
+    });
+    *rows = out.release();
+    return RIBBIT_OK;
+}
+
+// ---- the text
+enum : int { BAD_LENGTH = 1 };
+
+void put_tenths(std::string &out, int32_t v) {
+    if (v < 0) out += '-';
+    const int64_t a = v < 0 ? -(int64_t)v : v;
+    put_number(out, a / 10);
+    out += '.';
+    out += (char)('0' + a % 10);
+}
+
+// start, end, sequence 5' to 3' and Tm of one side, or four dots
+void put_primer(std::string &out, const RibbitPrimer &p, bool reverse) {
+    if (p.start < 0) { out += "\t.\t.\t.\t."; return; }
+    const uint64_t bases = (uint64_t)(uint32_t)p.bases_hi << 32 | (uint32_t)p.bases_lo;
+    out += '\t';
+    put_number(out, p.start);
+    out += '\t';
+    put_number(out, (int64_t)p.start + p.length);
+    out += '\t';
+    for (int32_t j = 0; j < p.length; ++j) out += reverse ? "TGCA"[(bases >> (2 * (p.length - 1 - j))) & 3] : "ACGT"[(bases >> (2 * j)) & 3];
+    out += '\t';
+    put_tenths(out, p.tm);
+}
+
+int bed_primers_text_impl(const char *bed, size_t bed_len, const RibbitRowPrimers *rows, size_t n, char **text, size_t *len) {
+    if (!text || !len || (!bed && bed_len > 0) || (!rows && n > 0)) return fail(RIBBIT_E_ARG, "null argument");
+    const size_t parts = bed_text_parts(bed_len);
+    BedLines lines;
+    int rc;
+    if ((rc = lines.find(bed, bed_len, parts))) return rc;
+    if (lines.count() != n) return fail(RIBBIT_E_ARG, "the BED text has %zu lines, not the %zu of the rows", lines.count(), n);
+    return write_pieces(
+        parts, "the rows' primers", text, len,
+        [&](size_t k, std::string &out) {
+            const size_t from = n * k / parts, to = n * (k + 1) / parts;
+            out.reserve(lines.start[to] - lines.start[from] + 128 * (to - from));
+            for (size_t i = from; i < to; ++i) {
+                const RibbitRowPrimers &r = rows[i];
+                for (const RibbitPrimer *p : {&r.left, &r.right})
+                    if (p->start >= 0 && (p->length < 1 || p->length > RIBBIT_PRIMER_MAX_LENGTH)) return PieceRefusal{BAD_LENGTH, i, (size_t)(uint32_t)p->length};
+                put_field(out, lines[i]);
+                put_primer(out, r.left, false);
+                put_primer(out, r.right, true);
+                out += '\t';
+                if (r.left.start >= 0 && r.right.start >= 0) put_number(out, (int64_t)r.right.start + r.right.length - r.left.start); else out += '.';
+                out += '\t';
+                put_number(out, r.left_candidates);
+                out += '\t';
+                put_number(out, r.right_candidates);
+                out += '\n';
+            }
+            return PieceRefusal{};
+        },
+        [](const PieceRefusal &bad) { return fail(RIBBIT_E_ARG, "row %zu: a primer of %d bases, not 1 .. %d", bad.a, (int)(int32_t)(uint32_t)bad.b, RIBBIT_PRIMER_MAX_LENGTH); });
+}
+
+}  // namespace
+
+extern "C" {
+
+void ribbit_primer_params_default(RibbitPrimerParams *params) {
+    if (params) *params = RibbitPrimerParams{200, 18, 25, 20, 570, 600, 630, 40, 60, 4, 1};
+}
+
+int ribbit_hip_record_primers(RibbitHandle *h, const int32_t *intervals, size_t n, const int32_t *targets, size_t n_targets, const RibbitPrimerParams *params,
+                              const RibbitRowPrimers **rows) {
+    return guarded("the primers", [&]() -> int { return record_primers_impl(h, intervals, n, targets, n_targets, params, rows); });
+}
+
+int ribbit_host_record_primers(const char *sequence, int64_t length, const int32_t *intervals, size_t n, const int32_t *targets, size_t n_targets,
+                               const RibbitPrimerParams *params, RibbitRowPrimers **rows) {
+    return guarded("the primers", [&]() -> int { return host_record_primers_impl(sequence, length, intervals, n, targets, n_targets, params, rows); });
+}
+
+void ribbit_primers_free(RibbitRowPrimers *rows) { std::free(rows); }
+
+int ribbit_bed_primers_text(const char *bed_text, size_t bed_len, const RibbitRowPrimers *rows, size_t n, char **text, size_t *len) {
+    return guarded("the rows' primers as text", [&]() -> int { return bed_primers_text_impl(bed_text, bed_len, rows, n, text, len); });
+}
+
+}  // extern "C"

@@ -297,7 +297,7 @@ hipError_t launch_loci(const int32_t *run_start, const int32_t *run_end, int64_t
 void launch_density(const uint32_t *bits, int64_t length, int64_t window, int64_t n_windows, int32_t *covered, hipStream_t stream);
 
 // ---- the row outputs that carve one device work buffer (overlap.hip, best.hip, classes.hip, compound.hip, interruptions.hip,
-// nearest.hip, composition.hip).  Each states its regions once, as a layout of byte offsets made by one function beside its kernels:
+// nearest.hip, composition.hip, primers.hip).  Each states its regions once, as a layout of byte offsets made by one function beside its kernels:
 // every intermediate array, the result on the device, and one region for the temporary storage of its rocPRIM calls (the most any
 // of them asks for these sizes: the function asks them, so it needs the device).  The api file sizes the handle's work buffer by
 // `bytes`; launch_* takes that buffer with its size and the layout, derives its pointers from the layout and refuses a buffer
@@ -470,6 +470,17 @@ hipError_t launch_composition_rows(const DevicePlanes &pl, const BaseSums *sums,
                                    size_t work_bytes, const CompositionLayout &at, hipStream_t stream);
 hipError_t launch_composition_windows(const DevicePlanes &pl, const BaseSums *sums, int64_t window, int64_t n_windows, uint8_t *work, size_t work_bytes,
                                       const CompositionLayout &at, hipStream_t stream);
+
+// primers.hip: a forward primer in the left flank and a reverse primer in the right flank of n_targets >= 1 targets of the loaded
+// record (length > 0), from its bit planes (api_primers.cpp; include/ribbit_hip.h has the contract).  bits: the coverage bitmap of
+// the record's rows as loci.hip takes it; targets: the (start, end) pairs on the device; prm: checked by the caller.  One wavefront
+// per target and side; it has no rocPRIM call, so its scratch region is empty.
+struct PrimerLayout : WorkLayout {
+    size_t out;          // the result: one RibbitRowPrimers per target
+};
+PrimerLayout primers_layout(int64_t n_targets);
+hipError_t launch_primers(const DevicePlanes &pl, const uint32_t *bits, const int32_t *targets, int64_t n_targets, const RibbitPrimerParams &prm, uint8_t *work,
+                          size_t work_bytes, const PrimerLayout &at, hipStream_t stream);
 
 // profiling aid: reads nwords dwords of src with one coalesced dword per lane (known byte count)
 void launch_calib_stream_read(const uint32_t *src, int64_t nwords, uint32_t *sink, hipStream_t stream);
