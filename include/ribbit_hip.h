@@ -842,6 +842,86 @@ void ribbit_primers_free(RibbitRowPrimers *rows);
 int ribbit_bed_primers_text(const char *bed_text, size_t bed_len, const RibbitRowPrimers *rows, size_t n, char **text, size_t *len);
 
 /*
+ * ---- PCR primer pairs, chosen together and checked for dimers and hairpins ---------------------------------------------
+ * The same windows, blocked positions, five admissibility rules, Tm and penalty as above, with the same RibbitPrimerParams;
+ * on top of them an ungapped model of an oligo that binds to itself or to its partner, and the choice of the two primers of a
+ * target as one pair.  Everything is integer arithmetic on the oligos' letters.  Gapped or thermodynamic (dG) dimer models,
+ * priming elsewhere in the genome and bounds on the product's size are not part of it.
+ *   Oligos:     an oligo is read 5' to 3'.  The left primer is its candidate's forward-strand bases, the right primer the reverse
+ *               complement of its candidate's forward-strand bases (the text ribbit_bed_primers_text prints).  Bases x and y are
+ *               bonded when y is the complement of x: with the codes A 0, C 1, G 2, T 3, when x ^ y == 3.
+ *   Duplex:     of two oligos a (ka bases) and b (kb bases).  A placement is a constant c in 0 .. ka + kb - 2; it pairs a[i] with
+ *               b[c - i] for every i for which both exist (antiparallel, ungapped).  any(a, b) is the longest run of consecutive
+ *               i whose pairs are all bonded, over all placements; end(a, b) is the longest such run that contains the pair of
+ *               a's 3' base (i = ka - 1) or the pair of b's 3' base (c - i = kb - 1), over all placements.  Both are symmetric
+ *               in a and b.
+ *   Hairpin:    of one oligo a: the placements of a with itself, restricted to the pairs (i, j = c - i) with i < j and
+ *               j - i - 1 >= RIBBIT_PRIMER_HAIRPIN_LOOP; hairpin(a) is the longest run of consecutive i whose pairs are bonded,
+ *               over all c.
+ *   Values:     (any, end) and hairpin of a few oligos, computed from a plain statement of the above:
+ *                 ACGT self (4,4)    AAAAAAAA / TTTTTTTT (8,8)    AAAAAAAA self (0,0)    GGGGCCCC self (8,8), hairpin 2
+ *                 CCCCCCCCCCCCCCCCCCAT self (2,2)    CAGTCGATCGGATCCATGCA self (6,4), hairpin 3
+ *                 ACGTTGCAACGTACGTAGCT self (12,4), hairpin 4; with CAGTCGATCGGATCCATGCA, either order, (4,4)
+ *                 GATTACAGATTACAGGC / TTTGCCTGTAATC (10,10)    GCGCGCGCGCGCGCGCGCGC self (20,20), hairpin 8
+ *                 hairpins: GGGGAAACCCC 4, GGGGAACCCC 3, GGGCTTTTGCCC 4, GGGCTTTGCCC 4, GGGCTTGCCC 3, CCCCCAAAGGGGG 5
+ *   Selection:  per target.  (1) A candidate passes when it is admissible by the five rules and, as an oligo o,
+ *               any(o, o) <= max_self_any, end(o, o) <= max_self_end and hairpin(o) <= max_hairpin.  (2) The shortlist of a
+ *               side is its first `shortlist` passing candidates in the order (penalty, distance, k) of the choice above; rank
+ *               0 is the best.  (3) A pair (l, r) of the two shortlists is admissible when |Tm_l - Tm_r| <= max_tm_difference,
+ *               any(l, r) <= max_pair_any and end(l, r) <= max_pair_end.  (4) The chosen pair is the admissible one with the
+ *               least (penalty_l + penalty_r + |Tm_l - Tm_r|, product, rank_l, rank_r), the product being the right
+ *               candidate's end - the left candidate's start.  (5) There is no fallback to a one-sided answer.
+ */
+#define RIBBIT_PRIMER_HAIRPIN_LOOP 3
+#define RIBBIT_PRIMER_PAIR_SHORTLIST 8
+typedef struct {
+    int32_t shortlist;                        /* 8;  1 .. RIBBIT_PRIMER_PAIR_SHORTLIST */
+    int32_t max_self_any, max_self_end;       /* 4, 3;  0 .. 32 each: at 32 a limit never refuses, an oligo has at most 32 bases */
+    int32_t max_hairpin;                      /* 3;  0 .. 32 */
+    int32_t max_pair_any, max_pair_end;       /* 4, 3;  0 .. 32 */
+    int32_t max_tm_difference;                /* 30, tenths of a degree;  0 .. 2000 */
+} RibbitPrimerPairParams;
+void ribbit_primer_pair_params_default(RibbitPrimerPairParams *params);
+typedef struct {
+    RibbitPrimer left, right;                 /* the chosen pair; without an admissible pair both starts are -1 and every */
+    int32_t pair_penalty, tm_difference;      /* field is 0 except the six counts below.  penalty_l + penalty_r + |Tm_l - Tm_r|; |Tm_l - Tm_r| */
+    int32_t product;                          /* right end - left start */
+    int32_t left_rank, right_rank;            /* their places in the shortlists */
+    int32_t left_self_any, left_self_end, left_hairpin;
+    int32_t right_self_any, right_self_end, right_hairpin;
+    int32_t pair_any, pair_end;
+    int32_t left_candidates, right_candidates;   /* admissible by the five rules: ribbit_hip_record_primers' counts */
+    int32_t left_passed, right_passed;        /* all passing candidates, not only the shortlisted ones */
+    int32_t pairs_tried;                      /* min(shortlist, left_passed) * min(shortlist, right_passed) */
+    int32_t pairs_admissible;
+    int32_t reserved;                         /* 0 */
+} RibbitRowPrimerPair;                        /* 32 ints, 128 bytes */
+/* The loaded record's n_targets targets (at most INT32_MAX) against the coverage of its n rows `intervals`, on the GPU
+ * (primer_pairs.hip): *rows is one record per target, in the order given, of handle-owned page-locked memory, valid until the
+ * handle's next primer pair call, load or close.  States and refusals are those of ribbit_hip_record_primers; a field of
+ * pair_params outside its range above: RIBBIT_E_ARG, and the error text names the field. */
+int ribbit_hip_record_primer_pairs(RibbitHandle *h, const int32_t *intervals, size_t n, const int32_t *targets, size_t n_targets,
+                                   const RibbitPrimerParams *params, const RibbitPrimerPairParams *pair_params,
+                                   const RibbitRowPrimerPair **rows);
+/* Host-only twin (no GPU), from the bytes of `sequence` (0 <= length < 2^31), letter by letter with loops over the placements:
+ * *rows malloc'ed, release with ribbit_primer_pairs_free(). */
+int ribbit_host_record_primer_pairs(const char *sequence, int64_t length, const int32_t *intervals, size_t n, const int32_t *targets,
+                                    size_t n_targets, const RibbitPrimerParams *params, const RibbitPrimerPairParams *pair_params,
+                                    RibbitRowPrimerPair **rows);
+void ribbit_primer_pairs_free(RibbitRowPrimerPair *rows);
+/* any(a, b) and end(a, b), and hairpin(a), of oligos given as text, 5' to 3' (host only): 1 .. 32 letters of ACGTacgt each,
+ * anything else is RIBBIT_E_ARG.  For checking a hand-made primer against the limits above. */
+int ribbit_host_oligo_duplex(const char *a, const char *b, int32_t *any, int32_t *end);
+int ribbit_host_oligo_hairpin(const char *a, int32_t *hairpin);
+/* The targets' BED rows with their primer pairs appended (host only): line i of bed_text, byte for byte, then 21 columns, each
+ * behind a tab, and a newline: 32 columns.  Columns 1 to 9 are the eight primer columns and the product as
+ * ribbit_bed_primers_text writes them; 10 is tm_difference (tenths as d.d); 11 and 12 are pair_any and pair_end; 13 to 18 the
+ * left side's, then the right side's, self any, self end and hairpin; 19 to 21 left_passed, right_passed and pairs_admissible.
+ * Without a pair the first 18 are ".".  bed_text and the refusals as for ribbit_bed_primers_text.  *text malloc'ed, release
+ * with ribbit_text_free(). */
+int ribbit_bed_primer_pairs_text(const char *bed_text, size_t bed_len, const RibbitRowPrimerPair *rows, size_t n, char **text, size_t *len);
+
+/*
  * ---- streaming FASTA ingest ---------------------------------------------------------------------------------------
  * Replaces the reader loop of ribbit.cpp:269-280 (getline + `sequence += line` into one pageable std::string per
  * record).  The file is read in 16-MB blocks; line bodies are copied once, straight into a page-locked buffer

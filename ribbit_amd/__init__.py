@@ -25,7 +25,8 @@ __all__ = ["RibbitHipError", "ScanParams", "Scanner", "library_path", "load_libr
            "INTERRUPTION_DT", "ROW_PURITY_DT", "bed_cigars", "host_record_interruptions", "interruption_text", "bed_purity_text",
            "Nearest", "NEAREST_DT", "host_record_nearest", "bed_nearest_text", "nearest_other_text",
            "COMPOSITION_DT", "BASE_COUNTS_DT", "host_record_composition", "host_record_base_windows", "bed_composition_text", "base_windows_text",
-           "PRIMERS_DT", "PrimerParams", "primer_params", "host_record_primers", "bed_primers_text"]
+           "PRIMERS_DT", "PrimerParams", "primer_params", "host_record_primers", "bed_primers_text",
+           "PRIMER_PAIRS_DT", "PrimerPairParams", "primer_pair_params", "host_record_primer_pairs", "bed_primer_pairs_text", "oligo_duplex", "oligo_hairpin"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -51,6 +52,10 @@ COMPOSITION_DT = np.dtype([(n, "<i4") for n in ("a", "c", "g", "t", "other", "le
 BASE_COUNTS_DT = np.dtype([(n, "<i4") for n in ("a", "c", "g", "t", "other")])      # RibbitBaseCounts
 PRIMERS_DT = np.dtype([(f"{side}_{n}", "<i4") for side in ("left", "right") for n in ("start", "length", "tm", "penalty", "bases_lo", "bases_hi")]
                       + [("left_candidates", "<i4"), ("right_candidates", "<i4")])      # RibbitRowPrimers
+PRIMER_PAIRS_DT = np.dtype([(f"{side}_{n}", "<i4") for side in ("left", "right") for n in ("start", "length", "tm", "penalty", "bases_lo", "bases_hi")]
+                           + [(n, "<i4") for n in ("pair_penalty", "tm_difference", "product", "left_rank", "right_rank", "left_self_any", "left_self_end", "left_hairpin",
+                                                   "right_self_any", "right_self_end", "right_hairpin", "pair_any", "pair_end", "left_candidates", "right_candidates",
+                                                   "left_passed", "right_passed", "pairs_tried", "pairs_admissible", "reserved")])      # RibbitRowPrimerPair
 
 # every symbol include/ribbit_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -90,6 +95,8 @@ ABI_SYMBOLS = [
     "ribbit_hip_record_composition", "ribbit_hip_record_base_windows", "ribbit_host_record_composition", "ribbit_host_record_base_windows",
     "ribbit_composition_free", "ribbit_debug_composition_prefix_builds", "ribbit_bed_composition_text", "ribbit_base_windows_text",
     "ribbit_primer_params_default", "ribbit_hip_record_primers", "ribbit_host_record_primers", "ribbit_primers_free", "ribbit_bed_primers_text",
+    "ribbit_primer_pair_params_default", "ribbit_hip_record_primer_pairs", "ribbit_host_record_primer_pairs", "ribbit_primer_pairs_free",
+    "ribbit_host_oligo_duplex", "ribbit_host_oligo_hairpin", "ribbit_bed_primer_pairs_text",
 ]
 
 MASK_MODES = {"soft": 0, "hard": 1}     # RIBBIT_MASK_SOFT / RIBBIT_MASK_HARD
@@ -129,6 +136,12 @@ class PrimerParams(C.Structure):
     fills one."""
     _fields_ = [(n, C.c_int32) for n in ("flank", "min_length", "max_length", "opt_length", "tm_min", "tm_opt", "tm_max", "gc_min_percent", "gc_max_percent",
                                          "max_run", "gc_clamp")]
+
+
+class PrimerPairParams(C.Structure):
+    """RibbitPrimerPairParams: the shortlist and the limits record_primer_pairs holds a pair to (include/ribbit_hip.h; the Tm
+    difference in tenths of a degree); primer_pair_params() fills one."""
+    _fields_ = [(n, C.c_int32) for n in ("shortlist", "max_self_any", "max_self_end", "max_hairpin", "max_pair_any", "max_pair_end", "max_tm_difference")]
 
 
 class DebugPairing(C.Structure):
@@ -398,6 +411,15 @@ def load_library():
     L.ribbit_primers_free.argtypes = [vp]
     L.ribbit_primers_free.restype = None
     L.ribbit_bed_primers_text.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_primer_pair_params_default.argtypes = [C.POINTER(PrimerPairParams)]
+    L.ribbit_primer_pair_params_default.restype = None
+    L.ribbit_hip_record_primer_pairs.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(PrimerParams), C.POINTER(PrimerPairParams), C.POINTER(vp)]
+    L.ribbit_host_record_primer_pairs.argtypes = [C.c_char_p, i64, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(PrimerParams), C.POINTER(PrimerPairParams), C.POINTER(vp)]
+    L.ribbit_primer_pairs_free.argtypes = [vp]
+    L.ribbit_primer_pairs_free.restype = None
+    L.ribbit_host_oligo_duplex.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(i32), C.POINTER(i32)]
+    L.ribbit_host_oligo_hairpin.argtypes = [C.c_char_p, C.POINTER(i32)]
+    L.ribbit_bed_primer_pairs_text.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
     _lib = L
     return L
 
@@ -990,6 +1012,90 @@ def bed_primers_text(bed, rows) -> bytes:
         return C.string_at(text.value, n.value)
     finally:
         L.ribbit_text_free(text)
+
+
+def primer_pair_params(**fields) -> PrimerPairParams:
+    """ribbit_primer_pair_params_default with the given fields replaced, e.g. primer_pair_params(shortlist=4, max_hairpin=2); the
+    ranges are checked by the calls that take it (include/ribbit_hip.h)"""
+    p = PrimerPairParams()
+    load_library().ribbit_primer_pair_params_default(C.byref(p))
+    names = {n for n, _ in PrimerPairParams._fields_}
+    for name, value in fields.items():
+        if name not in names:
+            raise TypeError(f"RibbitPrimerPairParams has no field {name!r}")
+        if not -2**31 <= int(value) < 2**31:
+            raise ValueError(f"{name} {value} does not fit int32")
+        setattr(p, name, int(value))
+    return p
+
+
+def _primer_pair_args(intervals, targets, params, pair_params):
+    iv, tg, params = _primer_args(intervals, targets, params)
+    if pair_params is None:
+        pair_params = primer_pair_params()
+    if not isinstance(pair_params, PrimerPairParams):
+        raise TypeError("pair_params: a PrimerPairParams (primer_pair_params())")
+    return iv, tg, params, pair_params
+
+
+def host_record_primer_pairs(sequence: bytes, intervals, targets, params: PrimerParams | None = None, pair_params: PrimerPairParams | None = None) -> np.ndarray:
+    """ribbit_host_record_primer_pairs: for every (start, end) target the forward and the reverse primer of host_record_primers'
+    candidates chosen as one pair: each oligo within the limits on self-dimers and hairpins, the two within the limits on
+    cross-dimers and on their Tm difference, the pair with the least penalty -> a PRIMER_PAIRS_DT array, one record per target.
+    The contract is in include/ribbit_hip.h.  No GPU needed."""
+    L = load_library()
+    iv, tg, params, pair_params = _primer_pair_args(intervals, targets, params, pair_params)
+    seq = bytes(sequence)
+    out = C.c_void_p()
+    rc = L.ribbit_host_record_primer_pairs(seq, len(seq), iv.ctypes.data if len(iv) else None, len(iv), tg.ctypes.data if len(tg) else None, len(tg),
+                                           C.byref(params), C.byref(pair_params), C.byref(out))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_host_record_primer_pairs error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return _copy(out.value, len(tg), PRIMER_PAIRS_DT)
+    finally:
+        L.ribbit_primer_pairs_free(out)
+
+
+def bed_primer_pairs_text(bed, rows) -> bytes:
+    """ribbit_bed_primer_pairs_text: the lines of `bed` (the targets' BED rows, target i on line i), each with the primer pair of
+    row i of `rows` (record_primer_pairs) appended as 21 more columns."""
+    L = load_library()
+    text_in = bed.encode() if isinstance(bed, str) else bytes(bed)
+    rw = np.ascontiguousarray(np.asarray(rows, dtype=PRIMER_PAIRS_DT).reshape(-1))
+    text, n = C.c_void_p(), C.c_size_t()
+    rc = L.ribbit_bed_primer_pairs_text(text_in, len(text_in), rw.ctypes.data if len(rw) else None, len(rw), C.byref(text), C.byref(n))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_bed_primer_pairs_text error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return C.string_at(text.value, n.value)
+    finally:
+        L.ribbit_text_free(text)
+
+
+def _oligo(text) -> bytes:
+    return text.encode() if isinstance(text, str) else bytes(text)
+
+
+def oligo_duplex(a, b) -> tuple:
+    """ribbit_host_oligo_duplex: (any, end) of two oligos of 1 .. 32 letters of ACGT, each read 5' to 3': the longest run of
+    bonded pairs over all ungapped antiparallel placements, and the longest that holds a 3' base (include/ribbit_hip.h)"""
+    L = load_library()
+    any_, end = C.c_int32(), C.c_int32()
+    rc = L.ribbit_host_oligo_duplex(_oligo(a), _oligo(b), C.byref(any_), C.byref(end))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_host_oligo_duplex error {rc}: {L.ribbit_hip_last_error().decode()}")
+    return any_.value, end.value
+
+
+def oligo_hairpin(a) -> int:
+    """ribbit_host_oligo_hairpin: the longest stem an oligo closes on itself around a loop of 3 bases or more"""
+    L = load_library()
+    out = C.c_int32()
+    rc = L.ribbit_host_oligo_hairpin(_oligo(a), C.byref(out))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_host_oligo_hairpin error {rc}: {L.ribbit_hip_last_error().decode()}")
+    return out.value
 
 
 def host_record_best(length: int, intervals):
@@ -1701,6 +1807,15 @@ class Scanner:
         self._check(self._L.ribbit_hip_record_primers(self._h, iv.ctypes.data if len(iv) else None, len(iv), tg.ctypes.data if len(tg) else None, len(tg),
                                                       C.byref(params), C.byref(out)))
         return _copy(out.value, len(tg), PRIMERS_DT)
+
+    def record_primer_pairs(self, intervals, targets, params: PrimerParams | None = None, pair_params: PrimerPairParams | None = None) -> np.ndarray:
+        """The two primers of every target of the loaded record chosen as a pair on the GPU, checked for dimers and hairpins
+        (ribbit_hip_record_primer_pairs); see host_record_primer_pairs"""
+        iv, tg, params, pair_params = _primer_pair_args(intervals, targets, params, pair_params)
+        out = C.c_void_p()
+        self._check(self._L.ribbit_hip_record_primer_pairs(self._h, iv.ctypes.data if len(iv) else None, len(iv), tg.ctypes.data if len(tg) else None, len(tg),
+                                                           C.byref(params), C.byref(pair_params), C.byref(out)))
+        return _copy(out.value, len(tg), PRIMER_PAIRS_DT)
 
     def record_best(self, intervals):
         """The loaded record's best non-overlapping rows on the GPU (ribbit_hip_record_best); see host_record_best"""

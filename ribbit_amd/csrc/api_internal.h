@@ -20,11 +20,13 @@
 //   api_nearest.cpp     the nearest interval of a second set for every row, and the other way round (nearest.hip), its host twin, both texts
 //   api_composition.cpp the base counts of every row, its flanks and every window from the bit planes (composition.hip), their host twins, both texts
 //   api_primers.cpp     a forward and a reverse primer in the flanks of every target, from the bit planes and the rows' coverage (primers.hip), its host twin, the text
-// The last eleven are the row outputs: their buffers are the handle's RowBufs `rows`, where all device work of a call is carved from
-// one buffer by the layout its .hip file states (kernels.h); best, classes, compound, interruptions, nearest and primers stage their inputs through stage_down, what their host
+//   api_primer_pairs.cpp  the two primers of every target chosen as a pair and checked for dimers and hairpins (primer_pairs.hip), its host twin, the oligo checks, the text
+// The last twelve are the row outputs: their buffers are the handle's RowBufs `rows`, where all device work of a call is carved from
+// one buffer by the layout its .hip file states (kernels.h); best, classes, compound, interruptions, nearest, primers and primer pairs stage their inputs through stage_down, what their host
 // sides share is below (hand_out, clipped_sorted_rows), what their kernels share is row_kernels.h, and the BED text they read and
 // write (the row format, the reader in pieces, the writer in pieces) is
 //   bed_text.h          a row's named fields, bed_read / bed_gather, BedLines, write_pieces / join_text, put_number
+//   primers_host.h      what the two primer outputs' host sides share: the parameter checks, a target's windows, one candidate from the bytes, a primer's columns
 // Host threads: every team of them, here and in refine.cpp, parallel_merge.cpp and host_planes.cpp, is started by rb::on_threads /
 // rb::over_pieces of host_threads.h (part 0 on the caller, a thread that cannot start leaves its part to the caller, all joined, the
 // first exception of any part rethrown on the caller: it then meets guarded() below); the thread count rule (the handle's, else
@@ -477,6 +479,7 @@ struct RibbitHandle {
         PinnedBuf<RibbitRowComposition> h_comp_rows;
         PinnedBuf<RibbitBaseCounts> h_comp_windows;
         PinnedBuf<RibbitRowPrimers> h_primers;          // the targets' primers on their way up (api_primers.cpp)
+        PinnedBuf<RibbitRowPrimerPair> h_primer_pairs;  // the targets' primer pairs on their way up (api_primer_pairs.cpp)
         // the blocks' base counts | their prefix, which belongs to the record (rec.base_prefix_valid, api_composition.cpp)
         DevBuf<rb::BaseSums> d_comp_sums;
         size_t rep_budget = 0;           // text budget of one batch of repeat sequences in bytes (0: REPEAT_TEXT_BUDGET)

@@ -482,6 +482,17 @@ PrimerLayout primers_layout(int64_t n_targets);
 hipError_t launch_primers(const DevicePlanes &pl, const uint32_t *bits, const int32_t *targets, int64_t n_targets, const RibbitPrimerParams &prm, uint8_t *work,
                           size_t work_bytes, const PrimerLayout &at, hipStream_t stream);
 
+// primer_pairs.hip: the two primers of n_targets >= 1 targets of the loaded record (length > 0) chosen as a pair, each checked for
+// self-dimers and hairpins and the pair for cross-dimers (api_primer_pairs.cpp; include/ribbit_hip.h has the contract).  bits,
+// targets, prm: as for primers.hip; pair: checked by the caller.  One wavefront per target; no rocPRIM call, so its scratch region
+// is empty.
+struct PrimerPairLayout : WorkLayout {
+    size_t out;          // the result: one RibbitRowPrimerPair per target
+};
+PrimerPairLayout primer_pairs_layout(int64_t n_targets);
+hipError_t launch_primer_pairs(const DevicePlanes &pl, const uint32_t *bits, const int32_t *targets, int64_t n_targets, const RibbitPrimerParams &prm,
+                               const RibbitPrimerPairParams &pair, uint8_t *work, size_t work_bytes, const PrimerPairLayout &at, hipStream_t stream);
+
 // profiling aid: reads nwords dwords of src with one coalesced dword per lane (known byte count)
 void launch_calib_stream_read(const uint32_t *src, int64_t nwords, uint32_t *sink, hipStream_t stream);
 

@@ -1,0 +1,120 @@
+// primers_host.h -- what the host sides of the two primer outputs share (api_primers.cpp, api_primer_pairs.cpp): the checks of
+// RibbitPrimerParams and of a call's arguments with their wording, a target's two windows, one candidate judged from the bytes of
+// the sequence letter by letter (the five rules and the Tm table as include/ribbit_hip.h states them), and the columns of a primer
+// as text.  No GPU, and nothing of the kernels' packed forms.
+// Not part of the ABI; nothing outside ribbit_amd/csrc includes it.
+#pragma once
+#include "bed_text.h"
+
+namespace rbapi {
+
+constexpr size_t MAX_TARGETS = (size_t)INT32_MAX;
+static_assert(sizeof(RibbitRowPrimers) == 56 && sizeof(RibbitPrimer) == 24 && sizeof(RibbitPrimerParams) == 44, "14, 6 and 11 ints");
+constexpr RibbitPrimer NO_PRIMER{-1, 0, 0, 0, 0, 0};
+
+inline int check_primer_params(const RibbitPrimerParams *p) {
+    if (!p) return fail(RIBBIT_E_ARG, "null argument");
+    if (p->flank < 0 || p->flank > RIBBIT_PRIMER_MAX_FLANK) return fail(RIBBIT_E_ARG, "flank %d is outside 0 .. %d", (int)p->flank, RIBBIT_PRIMER_MAX_FLANK);
+    if (p->max_length > RIBBIT_PRIMER_MAX_LENGTH) return fail(RIBBIT_E_ARG, "max_length %d is above %d", (int)p->max_length, RIBBIT_PRIMER_MAX_LENGTH);
+    if (p->min_length < 2 || p->min_length > p->max_length) return fail(RIBBIT_E_ARG, "min_length %d is outside 2 .. max_length %d", (int)p->min_length, (int)p->max_length);
+    if (p->opt_length < p->min_length || p->opt_length > p->max_length)
+        return fail(RIBBIT_E_ARG, "opt_length %d is outside min_length %d .. max_length %d", (int)p->opt_length, (int)p->min_length, (int)p->max_length);
+    if (p->tm_max > 2000) return fail(RIBBIT_E_ARG, "tm_max %d is above 2000", (int)p->tm_max);
+    if (p->tm_opt > p->tm_max) return fail(RIBBIT_E_ARG, "tm_opt %d is above tm_max %d", (int)p->tm_opt, (int)p->tm_max);
+    if (p->tm_min < 0 || p->tm_min > p->tm_opt) return fail(RIBBIT_E_ARG, "tm_min %d is outside 0 .. tm_opt %d", (int)p->tm_min, (int)p->tm_opt);
+    if (p->gc_max_percent > 100) return fail(RIBBIT_E_ARG, "gc_max_percent %d is above 100", (int)p->gc_max_percent);
+    if (p->gc_min_percent < 0 || p->gc_min_percent > p->gc_max_percent)
+        return fail(RIBBIT_E_ARG, "gc_min_percent %d is outside 0 .. gc_max_percent %d", (int)p->gc_min_percent, (int)p->gc_max_percent);
+    if (p->max_run < 1) return fail(RIBBIT_E_ARG, "max_run %d is below 1", (int)p->max_run);
+    if (p->gc_clamp != 0 && p->gc_clamp != 1) return fail(RIBBIT_E_ARG, "gc_clamp %d is neither 0 nor 1", (int)p->gc_clamp);
+    return RIBBIT_OK;
+}
+
+inline int check_primer_args(const int32_t *intervals, size_t n, const int32_t *targets, size_t n_targets, const RibbitPrimerParams *params, const void *rows) {
+    if ((!intervals && n > 0) || (!targets && n_targets > 0) || !rows) return fail(RIBBIT_E_ARG, "null argument");
+    if (n > MAX_TARGETS) return fail(RIBBIT_E_ARG, "%zu intervals", n);
+    if (n_targets > MAX_TARGETS) return fail(RIBBIT_E_ARG, "%zu targets", n_targets);
+    return check_primer_params(params);
+}
+
+// a target's two windows: the left candidates lie in [lo, s), the right ones in [e, hi)
+struct Flanks { int64_t lo, s, e, hi; };
+inline Flanks flanks_of(const int32_t *targets, size_t i, int32_t flank, int64_t length) {
+    const int64_t s = std::min(std::max<int64_t>(targets[2 * i], 0), length), e = std::min(std::max<int64_t>(targets[2 * i + 1], s), length);
+    return Flanks{std::max<int64_t>(s - flank, 0), s, e, std::min<int64_t>(e + flank, length)};
+}
+
+// ---- one candidate from the bytes themselves
+inline int code_of(unsigned char b) {      // A 0, C 1, G 2, T 3 in either case, -1 for every other byte
+    switch (b | 0x20) {
+        case 'a': return 0;
+        case 'c': return 1;
+        case 'g': return 2;
+        case 't': return 3;
+        default: return -1;
+    }
+}
+
+// SantaLucia 1998 as the contract tabulates it: dH in 100 cal/mol, dS in 0.1 cal/(K mol), by the step's two letters
+struct Step { char a, b; int32_t h, s; };
+constexpr Step kSteps[16] = {{'A', 'A', -79, -222}, {'T', 'T', -79, -222}, {'A', 'T', -72, -204}, {'T', 'A', -72, -213}, {'C', 'A', -85, -227}, {'T', 'G', -85, -227},
+                             {'G', 'T', -84, -224}, {'A', 'C', -84, -224}, {'C', 'T', -78, -210}, {'A', 'G', -78, -210}, {'G', 'A', -82, -222}, {'T', 'C', -82, -222},
+                             {'C', 'G', -106, -272}, {'G', 'C', -98, -244}, {'G', 'G', -80, -199}, {'C', 'C', -80, -199}};
+inline const Step &step_of(int a, int b) {
+    for (const Step &st : kSteps)
+        if (st.a == "ACGT"[a] && st.b == "ACGT"[b]) return st;
+    return kSteps[0];      // (not reached: the sixteen pairs are all there)
+}
+
+struct Candidate { bool ok; int32_t tm; };
+// [p, p + k) of the sequence, whose 3' base is the one at `three`
+inline Candidate candidate(const unsigned char *seq, const std::vector<uint8_t> &covered, int64_t p, int32_t k, int64_t three, const RibbitPrimerParams &prm) {
+    int32_t gc = 0, run = 0, h = 0, s = 0;
+    for (int64_t q = p; q < p + k; ++q) {
+        const int c = code_of(seq[q]);
+        if (c < 0 || covered[(size_t)q]) return {false, 0};
+        gc += c == 1 || c == 2;
+        run = q > p && c == code_of(seq[q - 1]) ? run + 1 : 1;
+        if (run > prm.max_run) return {false, 0};
+        if (q > p) {
+            const Step &st = step_of(code_of(seq[q - 1]), c);
+            h += st.h;
+            s += st.s;
+        }
+        if (q == p || q == p + k - 1) {
+            h += c == 1 || c == 2 ? 1 : 23;
+            s += c == 1 || c == 2 ? -28 : 41;
+        }
+    }
+    if (100 * gc < prm.gc_min_percent * k || 100 * gc > prm.gc_max_percent * k) return {false, 0};
+    const int c3 = code_of(seq[three]);
+    if (prm.gc_clamp && c3 != 1 && c3 != 2) return {false, 0};
+    s += -11 * (k - 1) - 362;
+    const int32_t tm = (int32_t)((10000 * (int64_t)h) / s) - 2732;      // (both negative: the quotient is positive, and / truncates)
+    return {tm >= prm.tm_min && tm <= prm.tm_max, tm};
+}
+
+// ---- the text
+inline void put_tenths(std::string &out, int32_t v) {
+    if (v < 0) out += '-';
+    const int64_t a = v < 0 ? -(int64_t)v : v;
+    put_number(out, a / 10);
+    out += '.';
+    out += (char)('0' + a % 10);
+}
+
+// start, end, sequence 5' to 3' and Tm of one side, or four dots
+inline void put_primer(std::string &out, const RibbitPrimer &p, bool reverse) {
+    if (p.start < 0) { out += "\t.\t.\t.\t."; return; }
+    const uint64_t bases = (uint64_t)(uint32_t)p.bases_hi << 32 | (uint32_t)p.bases_lo;
+    out += '\t';
+    put_number(out, p.start);
+    out += '\t';
+    put_number(out, (int64_t)p.start + p.length);
+    out += '\t';
+    for (int32_t j = 0; j < p.length; ++j) out += reverse ? "TGCA"[(bases >> (2 * (p.length - 1 - j))) & 3] : "ACGT"[(bases >> (2 * j)) & 3];
+    out += '\t';
+    put_tenths(out, p.tm);
+}
+
+}  // namespace rbapi

@@ -11,6 +11,7 @@
 //              [--overlap-with OTHER.bed [--nearest-bed FILE] [--nearest-other-bed FILE]]
 //              [--composition-bed FILE [--composition-flank F]] [--composition-track FILE [--composition-window W]]
 //              [--primer-bed FILE [--primer-flank F]]
+//              [--primer-pair-bed FILE [--primer-pair-flank F]]
 //
 // Records are independent (ribbit.cpp:269-280 handles them one after the other); here up to --jobs of them are in
 // flight at once PER GPU, each on its own handle / HIP streams, so that the upload and GPU scans of one record overlap
@@ -46,13 +47,15 @@
 // read the bit planes the scans read, whose prefix counts are built once per record.  --primer-bed writes the rows of --best-bed's
 // selection again, each with a forward primer in the --primer-flank bases to its left and a reverse primer in those to its right,
 // chosen clear of every base that any row of the record covers or that is no A, C, G or T (ribbit_hip_record_primers,
-// ribbit_bed_primers_text).
-// The BED rows are read back once per record, however many of the seventeen are asked for.
+// ribbit_bed_primers_text).  --primer-pair-bed writes the same rows with the two primers chosen together, from the best candidates of
+// either flank that are clear of self-dimers and hairpins: the pair that is clear of cross-dimers, melts alike and has the least
+// penalty, in --primer-pair-flank bases on either side (ribbit_hip_record_primer_pairs, ribbit_bed_primer_pairs_text).
+// The BED rows are read back once per record, however many of the eighteen are asked for.
 //
-// These seventeen are the ROW OUTPUTS, and each is described once, by its entry of kOutputs below: its file option, its stage (enum
+// These eighteen are the ROW OUTPUTS, and each is described once, by its entry of kOutputs below: its file option, its stage (enum
 // Stage, with the stage's names beside it), its qualifier options with their ranges and wording (defaults: Settings), and the function that
 // makes one record's text from the record's rows.  Parsing, the "needs" checks, opening the files, the sinks of the pipelined
-// records and of the last one, --timing and the RIBBIT_PROFILE line are loops over that table.  An eighteenth row output is: a stage in
+// records and of the last one, --timing and the RIBBIT_PROFILE line are loops over that table.  A nineteenth row output is: a stage in
 // the enum and its names, the qualifiers' fields in Settings, a produce function, an entry of kOutputs, and its lines of kHelp.
 //
 // Reproduced quirks: -p is accepted and ignored (Q1); without -o the BED rows go to
@@ -99,13 +102,14 @@ void check(int rc) {
 }
 
 // The stages of a record: the six every record goes through, then one per row output, in the order of kOutputs.
-enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, OVERLAP, BEST, CLASSES, COMPOUND, INTERRUPTIONS, NEAREST, COMPOSITION, PRIMERS, N_STAGES };
+enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, OVERLAP, BEST, CLASSES, COMPOUND, INTERRUPTIONS, NEAREST, COMPOSITION, PRIMERS, PRIMER_PAIRS, N_STAGES };
 constexpr int N_FIXED_STAGES = MASK;
 // a stage's key in --timing's stage_ms_summed_over_records and its label in the RIBBIT_PROFILE line
 const struct { const char *key, *label; } kStageNames[N_STAGES] = {
     {"load", "load"}, {"perfect", "perfect"}, {"substitutions", "substitutions"}, {"anchored", "anchored"}, {"dispatch", "dispatch"},
     {"refine_and_bed", "refine+BED"}, {"mask", "mask"}, {"repeats", "repeats"}, {"loci", "loci"}, {"density", "density"}, {"overlap", "overlap"},
-    {"best", "best"}, {"classes", "classes"}, {"compound", "compound"}, {"interruptions", "interruptions"}, {"nearest", "nearest"}, {"composition", "composition"}, {"primers", "primers"}};
+    {"best", "best"}, {"classes", "classes"}, {"compound", "compound"}, {"interruptions", "interruptions"}, {"nearest", "nearest"}, {"composition", "composition"}, {"primers", "primers"},
+    {"primer_pairs", "primer_pairs"}};
 
 // wall time per stage, summed over the records (--timing, RIBBIT_PROFILE=1)
 double g_stage_ms[N_STAGES] = {};
@@ -174,7 +178,7 @@ struct RecordRows {
         size_t n_groups = 0;
     };
     mutable Classes by_class;
-    // the record's best non-overlapping rows, computed by the first of the three outputs that asks (best_of): the handle's result,
+    // the record's best non-overlapping rows, computed by the first of the four outputs that asks (best_of): the handle's result,
     // which stays valid while the record's outputs are produced
     struct Best {
         bool have = false;
@@ -214,6 +218,7 @@ struct Settings {
     int composition_flank = 100;         // --composition-flank F: bases on either side of a row
     int composition_window = 10000;      // --composition-window W
     int primer_flank = 200;              // --primer-flank F: bases on either side of a row that a primer may lie in
+    int primer_pair_flank = 200;         // --primer-pair-flank F: the same for --primer-pair-bed
     const OtherBed *other = nullptr;         // --overlap-with FILE, read and grouped by name
 };
 
@@ -313,7 +318,7 @@ void produce_overlap_summary(RibbitHandle *h, const RecordRows &r, const Setting
     write(line.data(), line.size());
 }
 
-// the selection of a record, for --best-bed, --compound-bed and --primer-bed: a later call finds what the first left in the record's rows
+// the selection of a record, for --best-bed, --compound-bed, --primer-bed and --primer-pair-bed: a later call finds what the first left in the record's rows
 const RecordRows::Best &best_of(RibbitHandle *h, const RecordRows &r) {
     RecordRows::Best &b = r.best;
     if (b.have) return b;
@@ -504,16 +509,22 @@ void produce_composition_track(RibbitHandle *h, const RecordRows &r, const Setti
     ribbit_text_free(text);
 }
 
-// the selected rows again, each with a primer in either flank, clear of all rows of the record
-void produce_primers(RibbitHandle *h, const RecordRows &r, const Settings &s, const Sink &write) {
-    StageClock c(PRIMERS);
-    const RecordRows::Best &b = best_of(h, r);
+// the selected rows as targets: (start, end) of every chosen row
+std::vector<int32_t> targets_of(const RecordRows &r, const RecordRows::Best &b) {
     std::vector<int32_t> targets(2 * b.n);
     for (size_t j = 0; j < b.n; ++j) {
         const size_t row = (size_t)b.chosen[j];
         targets[2 * j] = r.iv[2 * row];
         targets[2 * j + 1] = r.iv[2 * row + 1];
     }
+    return targets;
+}
+
+// the selected rows again, each with a primer in either flank, clear of all rows of the record
+void produce_primers(RibbitHandle *h, const RecordRows &r, const Settings &s, const Sink &write) {
+    StageClock c(PRIMERS);
+    const RecordRows::Best &b = best_of(h, r);
+    const std::vector<int32_t> targets = targets_of(r, b);
     RibbitPrimerParams prm;
     ribbit_primer_params_default(&prm);
     prm.flank = s.primer_flank;
@@ -523,6 +534,28 @@ void produce_primers(RibbitHandle *h, const RecordRows &r, const Settings &s, co
     check(ribbit_bed_rows_text(r.bed_text, r.bed_len, b.chosen, b.n, &lines, &lines_len));
     int rc = ribbit_hip_record_primers(h, r.iv.data(), r.n(), targets.data(), b.n, &prm, &primers);
     if (rc == RIBBIT_OK) rc = ribbit_bed_primers_text(lines, lines_len, primers, b.n, &text, &len);
+    ribbit_text_free(lines);
+    check(rc);
+    write(text, len);
+    ribbit_text_free(text);
+}
+
+// the selected rows again, each with its two primers chosen as a pair and checked for dimers and hairpins
+void produce_primer_pairs(RibbitHandle *h, const RecordRows &r, const Settings &s, const Sink &write) {
+    StageClock c(PRIMER_PAIRS);
+    const RecordRows::Best &b = best_of(h, r);
+    const std::vector<int32_t> targets = targets_of(r, b);
+    RibbitPrimerParams prm;
+    ribbit_primer_params_default(&prm);
+    prm.flank = s.primer_pair_flank;
+    RibbitPrimerPairParams pair;
+    ribbit_primer_pair_params_default(&pair);
+    char *lines = nullptr, *text = nullptr;
+    size_t lines_len = 0, len = 0;
+    const RibbitRowPrimerPair *pairs = nullptr;
+    check(ribbit_bed_rows_text(r.bed_text, r.bed_len, b.chosen, b.n, &lines, &lines_len));
+    int rc = ribbit_hip_record_primer_pairs(h, r.iv.data(), r.n(), targets.data(), b.n, &prm, &pair, &pairs);
+    if (rc == RIBBIT_OK) rc = ribbit_bed_primer_pairs_text(lines, lines_len, pairs, b.n, &text, &len);
     ribbit_text_free(lines);
     check(rc);
     write(text, len);
@@ -539,7 +572,7 @@ struct Output {
     Qualifier qualifiers[MAX_QUALIFIERS];    // (name null: none)
     bool needs_other;                        // it compares the rows with the intervals of --overlap-with
 };
-constexpr size_t N_OUTPUTS = 17;
+constexpr size_t N_OUTPUTS = 18;
 const Output kOutputs[N_OUTPUTS] = {
     {"masked-fasta", MASK, false, produce_masked,
      {{"mask", Qualifier::SOFT_HARD, 0, 0, 0, nullptr, &Settings::mask_mode},
@@ -566,8 +599,10 @@ const Output kOutputs[N_OUTPUTS] = {
     {"composition-track", COMPOSITION, false, produce_composition_track,
      {{"composition-window", Qualifier::BASES, 1, 2147483647, 10, "1 .. 2147483647", &Settings::composition_window}, {}}, false},
     {"primer-bed", PRIMERS, true, produce_primers,
-     {{"primer-flank", Qualifier::BASES, 0, RIBBIT_PRIMER_MAX_FLANK, 4, "0 .. 1000", &Settings::primer_flank}, {}}, false}};
-static_assert(RIBBIT_PRIMER_MAX_FLANK == 1000, "the range as --primer-flank's message and help put it");
+     {{"primer-flank", Qualifier::BASES, 0, RIBBIT_PRIMER_MAX_FLANK, 4, "0 .. 1000", &Settings::primer_flank}, {}}, false},
+    {"primer-pair-bed", PRIMER_PAIRS, true, produce_primer_pairs,
+     {{"primer-pair-flank", Qualifier::BASES, 0, RIBBIT_PRIMER_MAX_FLANK, 4, "0 .. 1000", &Settings::primer_pair_flank}, {}}, false}};
+static_assert(RIBBIT_PRIMER_MAX_FLANK == 1000, "the range as --primer-flank's and --primer-pair-flank's messages and help put it");
 
 // the row outputs that are on, by stage: an output whose stage an earlier one has already named is left out (--timing, RIBBIT_PROFILE)
 std::vector<Stage> stages_on(const std::array<bool, N_OUTPUTS> &on) {
@@ -716,9 +751,21 @@ const char *kHelp =
     "                                its right, the product's size, and the admissible candidates of either flank ('.' where a\n"
     "                                flank has none). 18 .. 25 bases, Tm 57 .. 63 C (nearest neighbour, 50 mM Na+, 50 nM), 40 ..\n"
     "                                60 % GC, a 3' C or G, no base repeated 5 times, no N and no base that a BED row covers.\n"
-    "                                Each side is chosen on its own: check the pair for dimers, e.g. Primer3 check_primers\n"
+    "                                Each side is chosen on its own: check the pair for dimers, e.g. Primer3 check_primers;\n"
+    "                                --primer-pair-bed is the checked form\n"
     "  --primer-flank arg            (ribbit-hip) bases of the record on either side of a row that --primer-bed may place a\n"
-    "                                primer in, 0 .. 1000. Default: 200\n";
+    "                                primer in, 0 .. 1000. Default: 200\n"
+    "  --primer-pair-bed arg         (ribbit-hip) also write the rows of --best-bed's selection to this file with 21 columns\n"
+    "                                appended: the two primers of --primer-bed's rules chosen together. A candidate must not\n"
+    "                                bind to itself (ungapped: at most 4 bonded bases in a row, 3 at a 3' end) nor fold into a\n"
+    "                                hairpin (stem of at most 3 around a loop of 3 or more); of the 8 best of either flank the\n"
+    "                                pair is taken that does not bind to each other (the same limits), melts within 3 C of\n"
+    "                                each other and has the least penalty. Columns: the eight primer columns and the product,\n"
+    "                                Tm difference, pair any and end, self any, self end and hairpin of the left and of the\n"
+    "                                right primer, passing candidates left and right, admissible pairs ('.' in the first 18\n"
+    "                                where no pair is admissible)\n"
+    "  --primer-pair-flank arg       (ribbit-hip) bases of the record on either side of a row that --primer-pair-bed may place\n"
+    "                                a primer in, 0 .. 1000. Default: 200\n";
 
 bool parse_device_list(const std::string &value, std::vector<int> &out) {
     out.clear();
