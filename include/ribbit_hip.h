@@ -774,7 +774,8 @@ int ribbit_base_windows_text(const char *name, int64_t length, int32_t window, c
  * in the flank to its right, each chosen on its own: the candidate oligos of either flank are all of its substrings of
  * min_length .. max_length bases, a candidate is admissible or not, and the admissible one with the least penalty is taken.
  * Everything is integer arithmetic, so that the GPU, the host twin and this statement can be compared exactly.  The pair is
- * not optimised together and nothing is checked for dimers, hairpins or priming elsewhere in the genome.
+ * not optimised together and nothing is checked for dimers or hairpins (the primer pairs below) or for priming elsewhere (the
+ * in-silico PCR below them).
  *   Windows:    the arithmetic of the composition above, in 64-bit, with the flank F = params->flank:
  *                 s' = min(max(s, 0), L)    e' = min(max(e, s'), L)    lo = max(s' - F, 0)    hi = min(e' + F, L)
  *               A left candidate is [p, p + k) with lo <= p and p + k <= s', a right candidate [q, q + k) with e' <= q and
@@ -846,7 +847,8 @@ int ribbit_bed_primers_text(const char *bed_text, size_t bed_len, const RibbitRo
  * The same windows, blocked positions, five admissibility rules, Tm and penalty as above, with the same RibbitPrimerParams;
  * on top of them an ungapped model of an oligo that binds to itself or to its partner, and the choice of the two primers of a
  * target as one pair.  Everything is integer arithmetic on the oligos' letters.  Gapped or thermodynamic (dG) dimer models,
- * priming elsewhere in the genome and bounds on the product's size are not part of it.
+ * bounds on the product's size and priming in other records are not part of it; priming elsewhere in the record is the in-silico PCR
+ * below.
  *   Oligos:     an oligo is read 5' to 3'.  The left primer is its candidate's forward-strand bases, the right primer the reverse
  *               complement of its candidate's forward-strand bases (the text ribbit_bed_primers_text prints).  Bases x and y are
  *               bonded when y is the complement of x: with the codes A 0, C 1, G 2, T 3, when x ^ y == 3.
@@ -920,6 +922,92 @@ int ribbit_host_oligo_hairpin(const char *a, int32_t *hairpin);
  * Without a pair the first 18 are ".".  bed_text and the refusals as for ribbit_bed_primers_text.  *text malloc'ed, release
  * with ribbit_text_free(). */
 int ribbit_bed_primer_pairs_text(const char *bed_text, size_t bed_len, const RibbitRowPrimerPair *rows, size_t n, char **text, size_t *len);
+
+/*
+ * ---- in-silico PCR: where else in the record an oligo primes, and what a primer pair amplifies there ----------------------
+ * The check Primer-BLAST, UCSC isPCR, e-PCR and MFEprimer make before a pair is ordered, for the loaded record: every place
+ * on either strand where an oligo's 3' end matches exactly and the rest of it nearly, and every two such places of a pair's
+ * primers that face each other within a product size.  Everything is integer arithmetic on letters.  Other records of the
+ * input, gapped alignments and thermodynamic binding are not part of it.
+ *   Letters:    codes A 0, C 1, G 2, T 3, case ignored; any other byte is `other`, as the record is packed (the brk plane).
+ *   Oligo:      o has k bases, is read 5' to 3', 1 <= k <= 32; q = revcomp(o), q[j] = 3 - o[k - 1 - j].
+ *   Sites:      with s = seed and d = max_mismatches, on the record R[0, L): o has a FORWARD SITE at x when 0 <= x and
+ *               x + k <= L, no byte of R[x, x + k) is `other`, R[x + j] == o[j] for k - s <= j < k (the 3' end matches exactly)
+ *               and at most d of the j < k - s have R[x + j] != o[j].  o has a REVERSE SITE at x when the same window conditions
+ *               hold, R[x + j] == q[j] for j < s, and at most d of the j >= s mismatch q: the oligo's 3' base lies at x.  The
+ *               rows' coverage plays no part: a site inside a repeat counts.  A palindromic oligo may have both sites at one x;
+ *               both count.
+ *   Products:   of a pair.  a is the left primer, its RibbitPrimer's bases as they stand; b is the right primer, the reverse
+ *               complement of its RibbitPrimer's forward-strand bases (as ribbit_bed_primer_pairs_text prints it).  F is the
+ *               forward sites of a and those of b, V the reverse sites of a and those of b; each site carries its own oligo's
+ *               length, and a site of a and a site of b are counted separately even when a == b.  A product is a pair (f, v)
+ *               of F x V with f.x + f.k <= v.x (the windows do not overlap) and size = v.x + v.k - f.x <= max_product.
+ *               own is 1 when (a forward at left.start, b reverse at right.start) is one of the products, else 0;
+ *               shortest_other is the least size among the other products, 0 when there is none.  When any of the four lists
+ *               is longer than max_sites: products = -1, own = 0, shortest_other = 0; the four counts are always exact.
+ *               A pair is specific in this record when products - own == 0.
+ *   Values:     with L = GATTACAGATTACAGGCT, M = ACGTTGCATGCCATGACTGA, R = CCTGAAGTCTCGGATCAA, the pair a = L, b = revcomp(R)
+ *               and the defaults, as (left_forward, left_reverse, right_forward, right_reverse, products, own, shortest_other):
+ *                 L M R, own (0, 38)                      (1, 0, 0, 1,  1, 1, 0)    max_product 56: the same; 55: (1, 0, 0, 1, 0, 0, 0)
+ *                 L's last base T -> A (in the seed)      (0, 0, 0, 1,  0, 0, 0)
+ *                 L's first two bases GA -> CT            (1, 0, 0, 1,  1, 1, 0)    first three GAT -> CTA: (0, 0, 0, 1, 0, 0, 0)
+ *                 L's first base -> N                     (0, 0, 0, 1,  0, 0, 0)
+ *                 L without its first base, own (0, 37)   (0, 0, 0, 1,  0, 0, 0)    R without its last base: (1, 0, 0, 0, 0, 0, 0)
+ *                 L R, own (0, 18): abutting              (1, 0, 0, 1,  1, 1, 0)
+ *                 GATTACAGATTACAGGC CTGAAGTCTCGGATCAA with a = GATTACAGATTACAGGCC, own (0, 17): one base shared
+ *                                                         (1, 0, 0, 1,  0, 0, 0)
+ *                 L M revcomp(L) M R, own (0, 76)         (1, 1, 0, 1,  2, 1, 56): a left-left product
+ *                 L M L M R, own (0, 76)                  (2, 0, 0, 1,  2, 1, 56)   max_sites 1: (2, 0, 0, 1, -1, 0, 0)
+ *                 P = ACGTACGTACGTACGT, a = b = P: on P, own (0, 0)   (1, 1, 1, 1, 0, 0, 0)
+ *                                                  on P P, own (0, 16) (5, 5, 5, 5, 4, 1, 32)
+ */
+typedef struct {
+    int32_t seed;                             /* 15;  6 .. 16: the 3' bases that match exactly (isPCR's minPerfect) */
+    int32_t max_mismatches;                   /* 2;  0 .. 32 outside the seed (32 never refuses) */
+    int32_t max_product;                      /* 4000;  1 .. 2^31 - 1 (isPCR's maxSize) */
+    int32_t max_sites;                        /* 64;  1 .. 1024: the longest list of sites that is kept */
+} RibbitProductParams;
+void ribbit_product_params_default(RibbitProductParams *params);
+typedef struct {
+    int32_t left_forward, left_reverse, right_forward, right_reverse;   /* the sites of a and of b, exact */
+    int32_t products, own, shortest_other, reserved;                    /* reserved 0 */
+} RibbitRowProducts;                          /* 32 bytes; eight zeros for a target without a pair (left.start < 0) */
+typedef struct {
+    int32_t length, bases_lo, bases_hi;       /* 5' to 3', base j at bits 2 j of the 64 bits hi : lo; bits from 2 length on are ignored */
+} RibbitOligo;
+typedef struct {
+    int32_t forward, reverse;                 /* the sites on either strand, exact */
+    int32_t forward_at, reverse_at;           /* where the list starts in *positions, ascending window starts x; -1 when the list */
+} RibbitOligoSites;                           /* is longer than max_sites (it then takes no room).  16 bytes */
+/* The sites of n oligos (n * max_sites at most 2^29) on the loaded record, on the GPU (primer_products.hip): equal oligos are searched once,
+ * the record's bit planes are read once.  *sites is one record per oligo in the order given; *positions holds the kept lists one
+ * behind the other, oligo by oligo, the forward list before the reverse list, *n_positions values in all.  Both are handle-owned
+ * page-locked memory, valid until the handle's next call of either function below, load or close.  n = 0 and L = 0 are no
+ * errors.  A field of params outside its range above: RIBBIT_E_ARG, and the error text names the field; an oligo of fewer than
+ * `seed` or more than 32 bases: RIBBIT_E_ARG, and the text names its index; before a load: RIBBIT_E_STATE.  Counts and
+ * products add up over records, so a genome is answered by loading each record in turn. */
+int ribbit_hip_record_oligo_sites(RibbitHandle *h, const RibbitOligo *oligos, size_t n, const RibbitProductParams *params,
+                                  const RibbitOligoSites **sites, const int32_t **positions, size_t *n_positions);
+/* Host-only twin (no GPU), from the bytes of `sequence` (0 <= length < 2^31), letter by letter: *sites and *positions malloc'ed,
+ * release each with ribbit_products_free(). */
+int ribbit_host_record_oligo_sites(const char *sequence, int64_t length, const RibbitOligo *oligos, size_t n,
+                                   const RibbitProductParams *params, RibbitOligoSites **sites, int32_t **positions, size_t *n_positions);
+/* The products of n pairs (at most 2^24: ribbit_hip_record_primer_pairs' rows, or hand-made ones of which only the two primers'
+ * start, length and bases are read) on the loaded record, on the GPU: *rows is one record per pair in the order given, of
+ * handle-owned page-locked memory as above.  States and refusals as above; a primer of fewer than `seed` or more than 32 bases:
+ * RIBBIT_E_ARG, and the text names the pair's index. */
+int ribbit_hip_record_primer_products(RibbitHandle *h, const RibbitRowPrimerPair *pairs, size_t n, const RibbitProductParams *params,
+                                      const RibbitRowProducts **rows);
+/* Host-only twin: *rows malloc'ed, release with ribbit_products_free(). */
+int ribbit_host_record_primer_products(const char *sequence, int64_t length, const RibbitRowPrimerPair *pairs, size_t n,
+                                       const RibbitProductParams *params, RibbitRowProducts **rows);
+void ribbit_products_free(void *from_a_host_twin);
+/* The targets' BED rows with their primer pairs and products (host only): the 32 columns of ribbit_bed_primer_pairs_text, then
+ * six more, 38 in all: the four counts, products - own, shortest_other.  The last two are "." when products is -1, all six
+ * without a pair.  bed_text and the refusals as for ribbit_bed_primer_pairs_text.  *text malloc'ed, release with
+ * ribbit_text_free(). */
+int ribbit_bed_primer_products_text(const char *bed_text, size_t bed_len, const RibbitRowPrimerPair *pairs, const RibbitRowProducts *products,
+                                    size_t n, char **text, size_t *len);
 
 /*
  * ---- streaming FASTA ingest ---------------------------------------------------------------------------------------

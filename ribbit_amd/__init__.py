@@ -26,7 +26,9 @@ __all__ = ["RibbitHipError", "ScanParams", "Scanner", "library_path", "load_libr
            "Nearest", "NEAREST_DT", "host_record_nearest", "bed_nearest_text", "nearest_other_text",
            "COMPOSITION_DT", "BASE_COUNTS_DT", "host_record_composition", "host_record_base_windows", "bed_composition_text", "base_windows_text",
            "PRIMERS_DT", "PrimerParams", "primer_params", "host_record_primers", "bed_primers_text",
-           "PRIMER_PAIRS_DT", "PrimerPairParams", "primer_pair_params", "host_record_primer_pairs", "bed_primer_pairs_text", "oligo_duplex", "oligo_hairpin"]
+           "PRIMER_PAIRS_DT", "PrimerPairParams", "primer_pair_params", "host_record_primer_pairs", "bed_primer_pairs_text", "oligo_duplex", "oligo_hairpin",
+           "PRIMER_PRODUCTS_DT", "OLIGO_SITES_DT", "ProductParams", "product_params", "host_record_oligo_sites", "host_record_primer_products",
+           "bed_primer_products_text"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -56,6 +58,10 @@ PRIMER_PAIRS_DT = np.dtype([(f"{side}_{n}", "<i4") for side in ("left", "right")
                            + [(n, "<i4") for n in ("pair_penalty", "tm_difference", "product", "left_rank", "right_rank", "left_self_any", "left_self_end", "left_hairpin",
                                                    "right_self_any", "right_self_end", "right_hairpin", "pair_any", "pair_end", "left_candidates", "right_candidates",
                                                    "left_passed", "right_passed", "pairs_tried", "pairs_admissible", "reserved")])      # RibbitRowPrimerPair
+PRIMER_PRODUCTS_DT = np.dtype([(n, "<i4") for n in ("left_forward", "left_reverse", "right_forward", "right_reverse", "products", "own", "shortest_other",
+                                                     "reserved")])      # RibbitRowProducts
+OLIGO_SITES_DT = np.dtype([(n, "<i4") for n in ("forward", "reverse", "forward_at", "reverse_at")])      # RibbitOligoSites
+_OLIGO_DT = np.dtype([(n, "<i4") for n in ("length", "bases_lo", "bases_hi")])      # RibbitOligo
 
 # every symbol include/ribbit_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -97,6 +103,8 @@ ABI_SYMBOLS = [
     "ribbit_primer_params_default", "ribbit_hip_record_primers", "ribbit_host_record_primers", "ribbit_primers_free", "ribbit_bed_primers_text",
     "ribbit_primer_pair_params_default", "ribbit_hip_record_primer_pairs", "ribbit_host_record_primer_pairs", "ribbit_primer_pairs_free",
     "ribbit_host_oligo_duplex", "ribbit_host_oligo_hairpin", "ribbit_bed_primer_pairs_text",
+    "ribbit_product_params_default", "ribbit_hip_record_oligo_sites", "ribbit_host_record_oligo_sites", "ribbit_hip_record_primer_products",
+    "ribbit_host_record_primer_products", "ribbit_products_free", "ribbit_bed_primer_products_text",
 ]
 
 MASK_MODES = {"soft": 0, "hard": 1}     # RIBBIT_MASK_SOFT / RIBBIT_MASK_HARD
@@ -142,6 +150,12 @@ class PrimerPairParams(C.Structure):
     """RibbitPrimerPairParams: the shortlist and the limits record_primer_pairs holds a pair to (include/ribbit_hip.h; the Tm
     difference in tenths of a degree); primer_pair_params() fills one."""
     _fields_ = [(n, C.c_int32) for n in ("shortlist", "max_self_any", "max_self_end", "max_hairpin", "max_pair_any", "max_pair_end", "max_tm_difference")]
+
+
+class ProductParams(C.Structure):
+    """RibbitProductParams: the exact 3' seed, the mismatches outside it, the longest product and the longest list of sites
+    that record_oligo_sites and record_primer_products work with (include/ribbit_hip.h); product_params() fills one."""
+    _fields_ = [(n, C.c_int32) for n in ("seed", "max_mismatches", "max_product", "max_sites")]
 
 
 class DebugPairing(C.Structure):
@@ -420,6 +434,15 @@ def load_library():
     L.ribbit_host_oligo_duplex.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(i32), C.POINTER(i32)]
     L.ribbit_host_oligo_hairpin.argtypes = [C.c_char_p, C.POINTER(i32)]
     L.ribbit_bed_primer_pairs_text.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_product_params_default.argtypes = [C.POINTER(ProductParams)]
+    L.ribbit_product_params_default.restype = None
+    L.ribbit_hip_record_oligo_sites.argtypes = [vp, vp, C.c_size_t, C.POINTER(ProductParams), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_host_record_oligo_sites.argtypes = [C.c_char_p, i64, vp, C.c_size_t, C.POINTER(ProductParams), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.ribbit_hip_record_primer_products.argtypes = [vp, vp, C.c_size_t, C.POINTER(ProductParams), C.POINTER(vp)]
+    L.ribbit_host_record_primer_products.argtypes = [C.c_char_p, i64, vp, C.c_size_t, C.POINTER(ProductParams), C.POINTER(vp)]
+    L.ribbit_products_free.argtypes = [vp]
+    L.ribbit_products_free.restype = None
+    L.ribbit_bed_primer_products_text.argtypes = [C.c_char_p, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
     _lib = L
     return L
 
@@ -1075,6 +1098,105 @@ def bed_primer_pairs_text(bed, rows) -> bytes:
 
 def _oligo(text) -> bytes:
     return text.encode() if isinstance(text, str) else bytes(text)
+
+
+def product_params(**fields) -> ProductParams:
+    """ribbit_product_params_default with the given fields replaced, e.g. product_params(seed=12, max_sites=256); the ranges are
+    checked by the calls that take it (include/ribbit_hip.h)"""
+    p = ProductParams()
+    load_library().ribbit_product_params_default(C.byref(p))
+    names = {n for n, _ in ProductParams._fields_}
+    for name, value in fields.items():
+        if name not in names:
+            raise TypeError(f"RibbitProductParams has no field {name!r}")
+        if not -2**31 <= int(value) < 2**31:
+            raise ValueError(f"{name} {value} does not fit int32")
+        setattr(p, name, int(value))
+    return p
+
+
+def _product_params(params) -> ProductParams:
+    if params is None:
+        params = product_params()
+    if not isinstance(params, ProductParams):
+        raise TypeError("params: a ProductParams (product_params())")
+    return params
+
+
+def _oligos(oligos) -> np.ndarray:
+    """oligos as text, 5' to 3', letters of ACGT in either case -> RibbitOligo records (a text of no or of more than 32 letters keeps
+    its length, for the call to refuse)"""
+    out = np.zeros(len(oligos), dtype=_OLIGO_DT)
+    for i, text in enumerate(oligos):
+        letters = _oligo(text).upper()
+        if any(ch not in b"ACGT" for ch in letters):
+            raise ValueError(f"oligo {i}: {letters!r} has letters other than ACGT")
+        bases = sum(b"ACGT".index(ch) << (2 * j) for j, ch in enumerate(letters[:32]))
+        out[i] = (len(letters), np.uint32(bases & 0xffffffff).astype(np.int32), np.uint32(bases >> 32).astype(np.int32))
+    return out
+
+
+def _sites(sites_ptr, n, positions_ptr, n_positions):
+    """-> an OLIGO_SITES_DT array and the flat positions"""
+    return _copy(sites_ptr, n, OLIGO_SITES_DT), _copy(positions_ptr, n_positions, np.dtype("<i4"))
+
+
+def host_record_oligo_sites(sequence: bytes, oligos, params: ProductParams | None = None):
+    """ribbit_host_record_oligo_sites: where every oligo (text, 5' to 3') primes on either strand of the record: its last `seed`
+    bases match exactly, at most max_mismatches of the others differ -> (an OLIGO_SITES_DT array, one record per oligo, and the
+    int32 window starts of the kept lists one behind the other: list = positions[forward_at : forward_at + forward]; a list longer
+    than max_sites has forward_at -1).  The contract is in include/ribbit_hip.h.  No GPU needed."""
+    L = load_library()
+    og, params, seq = _oligos(oligos), _product_params(params), bytes(sequence)
+    sites, positions, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
+    rc = L.ribbit_host_record_oligo_sites(seq, len(seq), og.ctypes.data if len(og) else None, len(og), C.byref(params), C.byref(sites), C.byref(positions), C.byref(n))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_host_record_oligo_sites error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return _sites(sites.value, len(og), positions.value, n.value)
+    finally:
+        L.ribbit_products_free(sites)
+        L.ribbit_products_free(positions)
+
+
+def _pair_rows(pairs) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(pairs, dtype=PRIMER_PAIRS_DT).reshape(-1))
+
+
+def host_record_primer_products(sequence: bytes, pairs, params: ProductParams | None = None) -> np.ndarray:
+    """ribbit_host_record_primer_products: an in-silico PCR of every pair of `pairs` (a PRIMER_PAIRS_DT array: record_primer_pairs'
+    rows, or hand-made ones) on the record: the sites of both primers on both strands, the products between a forward and a reverse
+    site of either, whether the pair's own product is among them and the shortest of the others -> a PRIMER_PRODUCTS_DT array.  A
+    pair is specific in this record when products - own == 0.  The contract is in include/ribbit_hip.h.  No GPU needed."""
+    L = load_library()
+    rw, params, seq = _pair_rows(pairs), _product_params(params), bytes(sequence)
+    out = C.c_void_p()
+    rc = L.ribbit_host_record_primer_products(seq, len(seq), rw.ctypes.data if len(rw) else None, len(rw), C.byref(params), C.byref(out))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_host_record_primer_products error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return _copy(out.value, len(rw), PRIMER_PRODUCTS_DT)
+    finally:
+        L.ribbit_products_free(out)
+
+
+def bed_primer_products_text(bed, pairs, products) -> bytes:
+    """ribbit_bed_primer_products_text: the lines of bed_primer_pairs_text(bed, pairs), each with six more columns from row i of
+    `products` (record_primer_products): the four site counts, the products other than the pair's own and the shortest of them."""
+    L = load_library()
+    text_in = bed.encode() if isinstance(bed, str) else bytes(bed)
+    rw = _pair_rows(pairs)
+    pr = np.ascontiguousarray(np.asarray(products, dtype=PRIMER_PRODUCTS_DT).reshape(-1))
+    if len(pr) != len(rw):
+        raise ValueError(f"{len(rw)} pairs and {len(pr)} products")
+    text, n = C.c_void_p(), C.c_size_t()
+    rc = L.ribbit_bed_primer_products_text(text_in, len(text_in), rw.ctypes.data if len(rw) else None, pr.ctypes.data if len(pr) else None, len(rw), C.byref(text), C.byref(n))
+    if rc != 0:
+        raise RibbitHipError(f"ribbit_bed_primer_products_text error {rc}: {L.ribbit_hip_last_error().decode()}")
+    try:
+        return C.string_at(text.value, n.value)
+    finally:
+        L.ribbit_text_free(text)
 
 
 def oligo_duplex(a, b) -> tuple:
@@ -1816,6 +1938,24 @@ class Scanner:
         self._check(self._L.ribbit_hip_record_primer_pairs(self._h, iv.ctypes.data if len(iv) else None, len(iv), tg.ctypes.data if len(tg) else None, len(tg),
                                                            C.byref(params), C.byref(pair_params), C.byref(out)))
         return _copy(out.value, len(tg), PRIMER_PAIRS_DT)
+
+    def record_oligo_sites(self, oligos, params: ProductParams | None = None):
+        """Where every oligo (text, 5' to 3') primes on either strand of the loaded record, on the GPU: equal oligos are searched
+        once, the record's bit planes are read once (ribbit_hip_record_oligo_sites); see host_record_oligo_sites.  Counts add up
+        over records: for a genome, load each record in turn and sum."""
+        og, params = _oligos(oligos), _product_params(params)
+        sites, positions, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
+        self._check(self._L.ribbit_hip_record_oligo_sites(self._h, og.ctypes.data if len(og) else None, len(og), C.byref(params), C.byref(sites), C.byref(positions),
+                                                          C.byref(n)))
+        return _sites(sites.value, len(og), positions.value, n.value)
+
+    def record_primer_products(self, pairs, params: ProductParams | None = None) -> np.ndarray:
+        """An in-silico PCR of every primer pair on the loaded record, on the GPU (ribbit_hip_record_primer_products); see
+        host_record_primer_products"""
+        rw, params = _pair_rows(pairs), _product_params(params)
+        out = C.c_void_p()
+        self._check(self._L.ribbit_hip_record_primer_products(self._h, rw.ctypes.data if len(rw) else None, len(rw), C.byref(params), C.byref(out)))
+        return _copy(out.value, len(rw), PRIMER_PRODUCTS_DT)
 
     def record_best(self, intervals):
         """The loaded record's best non-overlapping rows on the GPU (ribbit_hip_record_best); see host_record_best"""

@@ -21,12 +21,13 @@
 //   api_composition.cpp the base counts of every row, its flanks and every window from the bit planes (composition.hip), their host twins, both texts
 //   api_primers.cpp     a forward and a reverse primer in the flanks of every target, from the bit planes and the rows' coverage (primers.hip), its host twin, the text
 //   api_primer_pairs.cpp  the two primers of every target chosen as a pair and checked for dimers and hairpins (primer_pairs.hip), its host twin, the oligo checks, the text
-// The last twelve are the row outputs: their buffers are the handle's RowBufs `rows`, where all device work of a call is carved from
+//   api_primer_products.cpp  the sites of oligos on either strand of the record and the products of primer pairs among them (primer_products.hip), their host twins, the text
+// The last thirteen are the row outputs: their buffers are the handle's RowBufs `rows`, where all device work of a call is carved from
 // one buffer by the layout its .hip file states (kernels.h); best, classes, compound, interruptions, nearest, primers and primer pairs stage their inputs through stage_down, what their host
 // sides share is below (hand_out, clipped_sorted_rows), what their kernels share is row_kernels.h, and the BED text they read and
 // write (the row format, the reader in pieces, the writer in pieces) is
 //   bed_text.h          a row's named fields, bed_read / bed_gather, BedLines, write_pieces / join_text, put_number
-//   primers_host.h      what the two primer outputs' host sides share: the parameter checks, a target's windows, one candidate from the bytes, a primer's columns
+//   primers_host.h      what the primer outputs' host sides share: the parameter checks, a target's windows, one candidate from the bytes, a primer's and a pair's columns
 // Host threads: every team of them, here and in refine.cpp, parallel_merge.cpp and host_planes.cpp, is started by rb::on_threads /
 // rb::over_pieces of host_threads.h (part 0 on the caller, a thread that cannot start leaves its part to the caller, all joined, the
 // first exception of any part rethrown on the caller: it then meets guarded() below); the thread count rule (the handle's, else
@@ -480,6 +481,13 @@ struct RibbitHandle {
         PinnedBuf<RibbitBaseCounts> h_comp_windows;
         PinnedBuf<RibbitRowPrimers> h_primers;          // the targets' primers on their way up (api_primers.cpp)
         PinnedBuf<RibbitRowPrimerPair> h_primer_pairs;  // the targets' primer pairs on their way up (api_primer_pairs.cpp)
+        // the oligos' sites and the pairs' products (api_primer_products.cpp): the patterns' lists, sized by the unique oligos the
+        // host reads in the middle of the call, and the kept lists one behind the other, sized by their sum; the header, the
+        // records (RibbitOligoSites or RibbitRowProducts) and the positions on their way up
+        DevBuf<int32_t> d_site_lists, d_site_flat;
+        PinnedBuf<uint32_t> h_product_header;
+        PinnedBuf<uint8_t> h_products;
+        PinnedBuf<int32_t> h_site_positions;
         // the blocks' base counts | their prefix, which belongs to the record (rec.base_prefix_valid, api_composition.cpp)
         DevBuf<rb::BaseSums> d_comp_sums;
         size_t rep_budget = 0;           // text budget of one batch of repeat sequences in bytes (0: REPEAT_TEXT_BUDGET)

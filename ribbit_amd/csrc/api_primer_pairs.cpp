@@ -263,29 +263,9 @@ int bed_primer_pairs_text_impl(const char *bed, size_t bed_len, const RibbitRowP
             out.reserve(lines.start[to] - lines.start[from] + 192 * (to - from));
             for (size_t i = from; i < to; ++i) {
                 const RibbitRowPrimerPair &r = rows[i];
-                const bool have = r.left.start >= 0 && r.right.start >= 0;
-                if (have)
-                    for (const RibbitPrimer *p : {&r.left, &r.right})
-                        if (p->length < 1 || p->length > RIBBIT_PRIMER_MAX_LENGTH) return PieceRefusal{BAD_LENGTH, i, (size_t)(uint32_t)p->length};
+                if (const RibbitPrimer *p = bad_primer(r)) return PieceRefusal{BAD_LENGTH, i, (size_t)(uint32_t)p->length};
                 put_field(out, lines[i]);
-                if (have) {
-                    put_primer(out, r.left, false);
-                    put_primer(out, r.right, true);
-                    out += '\t';
-                    put_number(out, r.product);
-                    out += '\t';
-                    put_tenths(out, r.tm_difference);
-                    for (const int32_t v : {r.pair_any, r.pair_end, r.left_self_any, r.left_self_end, r.left_hairpin, r.right_self_any, r.right_self_end, r.right_hairpin}) {
-                        out += '\t';
-                        put_number(out, v);
-                    }
-                } else {
-                    for (int c = 0; c < 18; ++c) out += "\t.";
-                }
-                for (const int32_t v : {r.left_passed, r.right_passed, r.pairs_admissible}) {
-                    out += '\t';
-                    put_number(out, v);
-                }
+                put_pair_columns(out, r);
                 out += '\n';
             }
             return PieceRefusal{};

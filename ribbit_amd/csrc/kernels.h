@@ -493,6 +493,49 @@ PrimerPairLayout primer_pairs_layout(int64_t n_targets);
 hipError_t launch_primer_pairs(const DevicePlanes &pl, const uint32_t *bits, const int32_t *targets, int64_t n_targets, const RibbitPrimerParams &prm,
                                const RibbitPrimerPairParams &pair, uint8_t *work, size_t work_bytes, const PrimerPairLayout &at, hipStream_t stream);
 
+// primer_products.hip: the sites of n_oligos >= 1 oligos on either strand of the loaded record (length > 0), from its bit planes, and
+// the products of n_pairs primer pairs among them (api_primer_products.cpp; include/ribbit_hip.h has the contract).  A call takes
+// the launches in this order, and the host reads `header` between them, because two sizes are counts the device finds:
+//   launch_product_uniques   the oligos sorted and made unique; header.uniques = U
+//   launch_product_scan      the 2 U patterns (an oligo's bases with the seed at the window's end, its reverse complement with the
+//                            seed at the window's start) sorted by seed key, one pass over the planes, every kept list sorted.
+//                            lists: 2 U max_sites ints, sized by the host from U before the pass and not by what the pass finds;
+//                            use_filter: look a position's key up in the hashed bitmap first (false: for measuring what it saves)
+//   launch_pair_products     one RibbitRowProducts per pair into `out`, or
+//   launch_oligo_sites       one RibbitOligoSites per oligo into `out`; header.positions = P, then
+//   launch_site_gather       the kept lists one behind the other into flat (P ints)
+struct ProductHeader { uint32_t uniques, positions, spare[2]; };
+struct ProductPattern { uint32_t hi, lo, id, k; };      // the k bases in plane form, window base j at bit j; id = 2 unique + strand
+struct ProductLayout : WorkLayout {
+    size_t items;        // the oligos' sort items | the items sorted, n_oligos of 16 bytes each
+    size_t heads;        // head flags | their inclusive sum, n_oligos words each
+    size_t unique_of;    // the unique oligo of every oligo, n_oligos words
+    size_t uniques;      // the unique oligos {bases, length}, n_oligos of 16 bytes
+    size_t keys;         // the patterns' seed keys | their ids | the keys sorted | the ids sorted, 2 n_oligos words each
+    size_t patterns;     // the patterns in key order, 2 n_oligos ProductPattern
+    size_t counts;       // the sites of every pattern, 2 n_oligos words
+    size_t filter;       // a bitmap of the seed keys' hashes in front of the bisection, product_filter_bits(n_oligos) bits
+    size_t lens;         // the oligos' kept list lengths | where each list starts in the flat positions, 2 n_oligos words each
+    size_t header;       // ProductHeader
+    size_t out;          // the result: n_pairs RibbitRowProducts or n_oligos RibbitOligoSites
+};
+// 16 bits per pattern rounded up to a power of two, 2^15 .. 2^30: of a random record one position in 16 to 32 passes
+inline int product_filter_log2(int64_t n_oligos) {
+    int bits = 15;
+    while (bits < 30 && ((int64_t)1 << bits) < 32 * n_oligos) ++bits;
+    return bits;
+}
+ProductLayout products_layout(int64_t n_oligos, int64_t n_pairs);
+hipError_t launch_product_uniques(const RibbitOligo *oligos, int64_t n_oligos, const RibbitProductParams &prm, uint8_t *work, size_t work_bytes, const ProductLayout &at,
+                                  hipStream_t stream);
+hipError_t launch_product_scan(const DevicePlanes &pl, int64_t n_oligos, int64_t uniques, const RibbitProductParams &prm, uint8_t *work, size_t work_bytes,
+                               const ProductLayout &at, int32_t *lists, bool use_filter, hipStream_t stream);
+// pairs: four ints per pair on the device, {a's oligo, b's oligo, left.start, right.start}; a's oligo -1: no pair
+hipError_t launch_pair_products(const int32_t *pairs, int64_t n_pairs, const RibbitProductParams &prm, uint8_t *work, size_t work_bytes, const ProductLayout &at,
+                                const int32_t *lists, hipStream_t stream);
+hipError_t launch_oligo_sites(int64_t n_oligos, const RibbitProductParams &prm, uint8_t *work, size_t work_bytes, const ProductLayout &at, hipStream_t stream);
+void launch_site_gather(int64_t n_oligos, const RibbitProductParams &prm, uint8_t *work, const ProductLayout &at, const int32_t *lists, int32_t *flat, hipStream_t stream);
+
 // profiling aid: reads nwords dwords of src with one coalesced dword per lane (known byte count)
 void launch_calib_stream_read(const uint32_t *src, int64_t nwords, uint32_t *sink, hipStream_t stream);
 

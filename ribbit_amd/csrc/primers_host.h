@@ -1,7 +1,7 @@
-// primers_host.h -- what the host sides of the two primer outputs share (api_primers.cpp, api_primer_pairs.cpp): the checks of
+// primers_host.h -- what the host sides of the primer outputs share (api_primers.cpp, api_primer_pairs.cpp, api_primer_products.cpp): the checks of
 // RibbitPrimerParams and of a call's arguments with their wording, a target's two windows, one candidate judged from the bytes of
 // the sequence letter by letter (the five rules and the Tm table as include/ribbit_hip.h states them), and the columns of a primer
-// as text.  No GPU, and nothing of the kernels' packed forms.
+// and of a pair as text.  No GPU, and nothing of the kernels' packed forms.
 // Not part of the ABI; nothing outside ribbit_amd/csrc includes it.
 #pragma once
 #include "bed_text.h"
@@ -115,6 +115,35 @@ inline void put_primer(std::string &out, const RibbitPrimer &p, bool reverse) {
     for (int32_t j = 0; j < p.length; ++j) out += reverse ? "TGCA"[(bases >> (2 * (p.length - 1 - j))) & 3] : "ACGT"[(bases >> (2 * j)) & 3];
     out += '\t';
     put_tenths(out, p.tm);
+}
+
+// the 21 columns of a row's primer pair, each behind a tab (ribbit_bed_primer_pairs_text, and ribbit_bed_primer_products_text
+// before its own six); bad_primer: the primer whose length the text refuses, or null
+inline const RibbitPrimer *bad_primer(const RibbitRowPrimerPair &r) {
+    if (r.left.start >= 0 && r.right.start >= 0)
+        for (const RibbitPrimer *p : {&r.left, &r.right})
+            if (p->length < 1 || p->length > RIBBIT_PRIMER_MAX_LENGTH) return p;
+    return nullptr;
+}
+inline void put_pair_columns(std::string &out, const RibbitRowPrimerPair &r) {
+    if (r.left.start >= 0 && r.right.start >= 0) {
+        put_primer(out, r.left, false);
+        put_primer(out, r.right, true);
+        out += '\t';
+        put_number(out, r.product);
+        out += '\t';
+        put_tenths(out, r.tm_difference);
+        for (const int32_t v : {r.pair_any, r.pair_end, r.left_self_any, r.left_self_end, r.left_hairpin, r.right_self_any, r.right_self_end, r.right_hairpin}) {
+            out += '\t';
+            put_number(out, v);
+        }
+    } else {
+        for (int c = 0; c < 18; ++c) out += "\t.";
+    }
+    for (const int32_t v : {r.left_passed, r.right_passed, r.pairs_admissible}) {
+        out += '\t';
+        put_number(out, v);
+    }
 }
 
 }  // namespace rbapi

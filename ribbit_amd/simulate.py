@@ -157,6 +157,19 @@ def simulate_sequence(total_len: int, seed: int, m_lo: int = 2, m_hi: int = 100,
     return seq, truth
 
 
+def with_random_background(seq: bytes, truth, seed: int) -> bytes:
+    """The same record with every A, C, G or T byte outside the truth loci replaced by a uniform random base (upper case).
+    simulate_sequence tiles one fixed unit between its loci, so every flank of a record recurs at every locus; this is the record
+    whose flanks are unique, as a genome's mostly are.  N blocks, lower-case loci and the loci themselves stay as they are."""
+    b = np.frombuffer(bytes(seq), dtype=np.uint8).copy()
+    background = np.isin(b, np.frombuffer(b"ACGTacgt", dtype=np.uint8))
+    for start, end, *_ in truth:
+        background[max(start, 0):max(end, 0)] = False
+    drawn = np.frombuffer(_ALPHABET, dtype=np.uint8)[np.random.RandomState(seed).randint(0, 4, size=len(b))]
+    b[background] = drawn[background]
+    return b.tobytes()
+
+
 def truth_bed_text(name: str, truth) -> str:
     """The truth list of simulate_sequence as BED lines: name, start, end, motif size, motif (what ribbit-hip --overlap-with reads)."""
     return "".join(f"{name}\t{start}\t{end}\t{m}\t{motif}\n" for start, end, m, motif in truth)
