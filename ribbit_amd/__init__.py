@@ -4,6 +4,11 @@ This module is only the Python face of the C ABI in include/ribbit_hip.h (ctypes
 types cross the boundary).  All compute happens in ribbit_amd/libribbit_hip.so (hand-written
 gfx950 kernels + C++ host logic).  There is no CPU fallback: importing works anywhere, but
 opening a scanner without the built library or without a gfx950 GPU raises.
+
+How the module is laid out: _signatures() is the one table of the C signatures (ABI_SYMBOLS is its keys, load_library() applies
+it); _ok, _ptr, _bytes, _name, _records, _call, _array and _text are what every wrapper is made of; every row output is
+marshalled once, in a _record_*(call, ...) function that its host_record_* twin and its Scanner.record_* method both call.
+An array's address does not keep the array alive: whatever _ptr() is given is bound to a local name of the calling frame.
 """
 from __future__ import annotations
 
@@ -62,50 +67,7 @@ PRIMER_PRODUCTS_DT = np.dtype([(n, "<i4") for n in ("left_forward", "left_revers
                                                      "reserved")])      # RibbitRowProducts
 OLIGO_SITES_DT = np.dtype([(n, "<i4") for n in ("forward", "reverse", "forward_at", "reverse_at")])      # RibbitOligoSites
 _OLIGO_DT = np.dtype([(n, "<i4") for n in ("length", "bases_lo", "bases_hi")])      # RibbitOligo
-
-# every symbol include/ribbit_hip.h declares (checked by tests/test_abi.py)
-ABI_SYMBOLS = [
-    "ribbit_scan_params_default", "ribbit_hip_last_error", "ribbit_hip_abi_version",
-    "ribbit_hip_device_count", "ribbit_hip_open", "ribbit_hip_close", "ribbit_hip_set_stream",
-    "ribbit_hip_load_record", "ribbit_hip_load_record_device", "ribbit_hip_load_record_pinned", "ribbit_hip_host_alloc", "ribbit_hip_host_free",
-    "ribbit_fasta_open", "ribbit_fasta_next", "ribbit_fasta_release", "ribbit_fasta_close", "ribbit_fasta_last_error", "ribbit_hip_scan_perfect_runs",
-    "ribbit_hip_perfect_calls", "ribbit_hip_seeds_perfect", "ribbit_hip_plane_bits",
-    "ribbit_hip_range_popcount", "ribbit_hip_plane_words", "ribbit_hip_packed_plane",
-    "ribbit_hip_last_timing_ms", "ribbit_hip_last_event_count",
-    "ribbit_hip_subst_calls", "ribbit_hip_seeds_substitutions",
-    "ribbit_host_replay_calls", "ribbit_seed_lists_free", "ribbit_host_longest_runs", "ribbit_debug_set_merge_min_range", "ribbit_debug_last_merge",
-    "ribbit_hip_small_motifs", "ribbit_hip_seed_best_rows", "ribbit_debug_small_motif_counters", "ribbit_debug_last_dispatch_ranges", "ribbit_host_debug_thread_faults", "ribbit_debug_last_device_merge", "ribbit_debug_alignment_counters", "ribbit_debug_level_counters",
-    "ribbit_hip_adopt_dispatch", "ribbit_hip_refine_met_empty_query", "ribbit_hip_device_pci_bus_id",
-    "ribbit_hip_anchored_calls", "ribbit_hip_seeds_anchored", "ribbit_hip_dispatch_seeds", "ribbit_hip_guard_hits",
-    "ribbit_hip_debug_stream_read",
-    "ribbit_refine_params_default", "ribbit_hip_seed_longest_runs", "ribbit_hip_refine_jobs",
-    "ribbit_host_refine_jobs", "ribbit_refine_jobs_free", "ribbit_ssw_align", "ribbit_debug_ssw_align_periodic",
-    "ribbit_hip_refine_bed", "ribbit_host_refine_bed", "ribbit_text_free",
-    "ribbit_hip_xa_words",
-    "ribbit_host_perfect_runs_from_events", "ribbit_runs_free", "ribbit_hip_perfect_runs_partial",
-    "ribbit_hip_scan_perfect_chunk", "ribbit_hip_host_register", "ribbit_hip_host_unregister",
-    "ribbit_hip_set_host_threads", "ribbit_hip_ssw_passes", "ribbit_hip_ssw_align_jobs", "ribbit_hip_set_timing", "ribbit_hip_debug_set_event_capacity", "ribbit_hip_debug_set_scan_split", "ribbit_hip_debug_last_scan_split", "ribbit_hip_debug_pair_events", "ribbit_hip_debug_pair_events_sharded", "ribbit_hip_scan_perfect_begin", "ribbit_hip_scan_perfect_end", "ribbit_hip_scan_perfect_wait", "ribbit_hip_scan_perfect_end_device",
-    "ribbit_hip_stage_calls_chunk", "ribbit_hip_xa_words_strided", "ribbit_host_merge_chunks",
-    "ribbit_hip_mask_record", "ribbit_host_mask_record", "ribbit_bed_intervals", "ribbit_intervals_free",
-    "ribbit_hip_repeat_sequences", "ribbit_host_repeat_sequences", "ribbit_hip_debug_set_repeat_text_budget", "ribbit_hip_debug_set_small_record_capacity",
-    "ribbit_hip_record_loci", "ribbit_hip_record_density", "ribbit_host_record_loci", "ribbit_host_record_density", "ribbit_loci_free",
-    "ribbit_bed_loci_text",
-    "ribbit_hip_record_overlap", "ribbit_host_record_overlap", "ribbit_bed_overlap_text",
-    "ribbit_hip_record_best", "ribbit_host_record_best", "ribbit_bed_rows_text",
-    "ribbit_bed_motifs", "ribbit_hip_record_classes", "ribbit_host_record_classes", "ribbit_motif_classes_free", "ribbit_bed_class_text",
-    "ribbit_class_summary_text",
-    "ribbit_hip_record_compounds", "ribbit_host_record_compounds", "ribbit_compounds_free", "ribbit_class_labels", "ribbit_compound_text",
-    "ribbit_bed_cigars", "ribbit_hip_record_interruptions", "ribbit_host_record_interruptions", "ribbit_row_purity_free", "ribbit_interruptions_free",
-    "ribbit_interruption_text", "ribbit_bed_purity_text",
-    "ribbit_hip_record_nearest", "ribbit_host_record_nearest", "ribbit_nearest_free", "ribbit_bed_nearest_text", "ribbit_nearest_other_text",
-    "ribbit_hip_record_composition", "ribbit_hip_record_base_windows", "ribbit_host_record_composition", "ribbit_host_record_base_windows",
-    "ribbit_composition_free", "ribbit_debug_composition_prefix_builds", "ribbit_bed_composition_text", "ribbit_base_windows_text",
-    "ribbit_primer_params_default", "ribbit_hip_record_primers", "ribbit_host_record_primers", "ribbit_primers_free", "ribbit_bed_primers_text",
-    "ribbit_primer_pair_params_default", "ribbit_hip_record_primer_pairs", "ribbit_host_record_primer_pairs", "ribbit_primer_pairs_free",
-    "ribbit_host_oligo_duplex", "ribbit_host_oligo_hairpin", "ribbit_bed_primer_pairs_text",
-    "ribbit_product_params_default", "ribbit_hip_record_oligo_sites", "ribbit_host_record_oligo_sites", "ribbit_hip_record_primer_products",
-    "ribbit_host_record_primer_products", "ribbit_products_free", "ribbit_bed_primer_products_text",
-]
+_I4 = np.dtype("<i4")
 
 MASK_MODES = {"soft": 0, "hard": 1}     # RIBBIT_MASK_SOFT / RIBBIT_MASK_HARD
 
@@ -202,6 +164,148 @@ STAGE_PERFECT, STAGE_SUBST, STAGE_ANCHORED = 0, 1, 2
 SCAN_PERFECT, SCAN_SUBST, SCAN_ANCHORED, SCAN_XA_WINDOW, SCAN_ALL = 0, 1, 2, 3, 4
 
 
+def _signatures() -> dict:
+    """{symbol: (restype, argtypes)} of every symbol include/ribbit_hip.h declares (tests/test_abi.py holds the keys to the header).
+    c_char_p takes bytes, c_void_p an integer address or a byref(): they are not interchangeable."""
+    P, vp, cp, sz, ci, i32, i64 = C.POINTER, C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_int32, C.c_int64
+    st = C.c_int                                     # a status: 0, or an error that ribbit_hip_last_error() explains
+    pvp, psz, pi32 = P(vp), P(sz), P(i32)
+    scan, refine = P(ScanParams), P(RefineParams)
+    planes = [i64, vp, vp, vp, sz, vp, sz]           # length, hi, lo, brk, their words, xa, its stride
+    t = {
+        "ribbit_scan_params_default": (None, [scan, i32, i32]),
+        "ribbit_hip_last_error": (cp, []),
+        "ribbit_hip_abi_version": (ci, []),
+        "ribbit_hip_device_count": (ci, []),
+        "ribbit_hip_open": (st, [scan, ci, pvp]),
+        "ribbit_hip_close": (st, [vp]),
+        "ribbit_hip_set_stream": (st, [vp, vp]),
+        "ribbit_hip_load_record": (st, [vp, cp, i64]),
+        "ribbit_hip_load_record_device": (st, [vp, vp, i64]),
+        "ribbit_hip_load_record_pinned": (st, [vp, vp, i64]),
+        "ribbit_hip_host_alloc": (st, [sz, pvp]),
+        "ribbit_hip_host_free": (st, [vp]),
+        "ribbit_fasta_open": (st, [cp, ci, pvp]),
+        "ribbit_fasta_next": (ci, [vp, P(cp), pvp, P(i64), P(ci)]),
+        "ribbit_fasta_release": (st, [vp, vp]),
+        "ribbit_fasta_close": (st, [vp]),
+        "ribbit_fasta_last_error": (cp, []),
+        "ribbit_hip_seeds_substitutions": (st, [vp, pvp, psz, pvp, psz]),
+        "ribbit_hip_seeds_anchored": (st, [vp] + [pvp, psz] * 3),
+        "ribbit_hip_guard_hits": (i64, [vp]),
+        "ribbit_host_replay_calls": (st, [scan] + planes + [vp, sz, vp, sz, vp, sz, P(SeedLists)]),
+        "ribbit_seed_lists_free": (None, [P(SeedLists)]),
+        "ribbit_debug_last_merge": (None, [ci, P(i32 * 5)]),
+        "ribbit_debug_last_device_merge": (None, [P(i32 * 5)]),
+        "ribbit_debug_last_dispatch_ranges": (i32, []),
+        "ribbit_host_debug_thread_faults": (i64, [i32, i32]),
+        "ribbit_debug_alignment_counters": (None, [P(i64 * 3)]),
+        "ribbit_debug_level_counters": (None, [P(i64 * 3)]),
+        "ribbit_debug_small_motif_counters": (None, [P(i64 * 2)]),
+        "ribbit_debug_set_merge_min_range": (None, [sz]),
+        "ribbit_hip_device_pci_bus_id": (st, [ci, cp, sz]),
+        "ribbit_hip_adopt_dispatch": (st, [vp, vp, sz]),
+        "ribbit_hip_refine_met_empty_query": (ci, [vp]),
+        "ribbit_hip_small_motifs": (st, [vp] * 6),
+        "ribbit_hip_seed_best_rows": (st, [vp] * 4),
+        "ribbit_host_longest_runs": (st, [scan] + planes[:5] + [vp, sz, vp]),
+        "ribbit_hip_plane_bits": (st, [vp, i32, i64, i64, vp]),
+        "ribbit_hip_range_popcount": (st, [vp, i32, i64, i64, pi32]),
+        "ribbit_hip_plane_words": (i64, [vp]),
+        "ribbit_hip_packed_plane": (st, [vp, ci, vp]),
+        "ribbit_hip_last_timing_ms": (st, [vp, ci, P(C.c_double)]),
+        "ribbit_hip_last_event_count": (i64, [vp]),
+        "ribbit_refine_params_default": (None, [refine, i32, i32]),
+        "ribbit_hip_refine_jobs": (st, [vp, refine, pvp, psz, pvp]),
+        "ribbit_host_refine_jobs": (st, [scan, refine] + planes + [vp, sz, pvp, psz, pvp, psz]),
+        "ribbit_refine_jobs_free": (None, [vp, vp]),
+        "ribbit_hip_refine_bed": (st, [vp, refine, cp, pvp, psz]),
+        "ribbit_host_refine_bed": (st, [scan, refine, cp] + planes + [vp, sz, cp, pvp, psz]),
+        "ribbit_hip_xa_words": (st, [vp, i64, i64, vp]),
+        "ribbit_hip_xa_words_strided": (st, [vp, i64, i64, vp, i64]),
+        "ribbit_hip_perfect_runs_partial": (st, [vp, i64, i64, i64, pvp, psz, pvp, psz]),
+        "ribbit_hip_scan_perfect_chunk": (st, [vp, i64, i64, i64, vp, sz, vp, sz, pvp, psz, pvp, psz]),
+        "ribbit_hip_scan_perfect_begin": (st, [vp, i64, i64, i64]),
+        "ribbit_hip_scan_perfect_end": (st, [vp, vp, sz, vp, sz, ci, pvp, psz, pvp, psz]),
+        "ribbit_hip_scan_perfect_wait": (st, [vp]),
+        "ribbit_hip_scan_perfect_end_device": (st, [vp, pvp, psz, pvp, psz]),
+        "ribbit_hip_stage_calls_chunk": (st, [vp, ci, i64, i64, i64, i64, P(ChunkCalls)]),
+        "ribbit_host_merge_chunks": (st, [scan] + planes + [P(ChunkPart), sz, P(SeedLists)]),
+        "ribbit_host_perfect_runs_from_events": (st, [scan, sz, vp, vp, pvp, psz]),
+        "ribbit_hip_host_register": (st, [vp, sz]),
+        "ribbit_hip_host_unregister": (st, [vp]),
+        "ribbit_hip_set_host_threads": (st, [vp, i32]),
+        "ribbit_hip_set_timing": (st, [vp, i32]),
+        "ribbit_hip_debug_set_scan_split": (st, [vp, i32, i32]),
+        "ribbit_hip_debug_last_scan_split": (st, [vp, i32, pi32, pi32]),
+        "ribbit_hip_debug_pair_events": (st, [vp, vp, sz, i64, vp, sz, psz, P(C.c_uint32)]),
+        "ribbit_hip_debug_pair_events_sharded": (st, [vp, vp, vp, sz, i64, i64, i64, i64, P(DebugPairing)]),
+        "ribbit_hip_debug_stream_read": (st, [vp, i64, P(i64)]),
+        "ribbit_hip_ssw_passes": (st, [vp, vp, sz, cp, sz, i32, vp]),
+        "ribbit_hip_ssw_align_jobs": (st, [vp, vp, sz, cp, sz, i32, vp, vp, sz, vp, vp]),
+        "ribbit_ssw_align": (st, [cp, i32, cp, i32, i32, P(Alignment), cp, sz]),
+        "ribbit_debug_ssw_align_periodic": (st, [cp, i32, cp, i32, i32, i32, P(Alignment), cp, sz]),
+        "ribbit_hip_repeat_sequences": (st, [vp, cp, vp, sz, i32, pvp, psz, psz]),
+        "ribbit_host_repeat_sequences": (st, [cp, cp, i64, vp, sz, i32, pvp, psz]),
+        "ribbit_bed_intervals": (st, [cp, sz, pvp, psz]),
+        "ribbit_bed_motifs": (st, [cp, sz, pvp, pvp, psz]),
+        "ribbit_bed_cigars": (st, [cp, sz, pvp, pvp, psz]),
+        "ribbit_class_labels": (st, [vp, vp, sz, vp, sz, pvp]),
+        "ribbit_debug_composition_prefix_builds": (i64, []),
+        "ribbit_primer_params_default": (None, [P(PrimerParams)]),
+        "ribbit_primer_pair_params_default": (None, [P(PrimerPairParams)]),
+        "ribbit_product_params_default": (None, [P(ProductParams)]),
+        "ribbit_host_oligo_duplex": (st, [cp, cp, pi32, pi32]),
+        "ribbit_host_oligo_hairpin": (st, [cp, pi32]),
+        # the text writers: malloc'ed text and its length come last (interruption_text: and the rows left out)
+        "ribbit_bed_loci_text": (st, [cp, cp, sz, vp, sz, pvp, psz]),
+        "ribbit_bed_class_text": (st, [cp, sz, vp, vp, vp, sz, pvp, psz]),
+        "ribbit_class_summary_text": (st, [cp, vp, sz, vp, vp, vp, sz, pvp, psz]),
+        "ribbit_compound_text": (st, [cp, cp, sz, i64, vp, sz, vp, sz, vp, sz, pvp, psz]),
+        "ribbit_interruption_text": (st, [cp, cp, sz, vp, sz, vp, vp, sz, cp, cp, vp, pvp, psz, psz]),
+        "ribbit_bed_purity_text": (st, [cp, sz, vp, vp, vp, sz, pvp, psz]),
+        "ribbit_bed_nearest_text": (st, [cp, sz, vp, sz, vp, cp, vp, sz, pvp, psz]),
+        "ribbit_nearest_other_text": (st, [cp, vp, cp, vp, sz, vp, vp, cp, vp, sz, pvp, psz]),
+        "ribbit_base_windows_text": (st, [cp, i64, i32, vp, sz, pvp, psz]),
+        "ribbit_bed_primer_products_text": (st, [cp, sz, vp, vp, sz, pvp, psz]),
+    }
+    for name in ("ribbit_hip_scan_perfect_runs", "ribbit_hip_perfect_calls", "ribbit_hip_seeds_perfect", "ribbit_hip_subst_calls",
+                 "ribbit_hip_anchored_calls", "ribbit_hip_dispatch_seeds", "ribbit_hip_seed_longest_runs"):
+        t[name] = (st, [vp, pvp, psz])                       # a list of the handle's and its length
+    for name in ("ribbit_hip_debug_set_event_capacity", "ribbit_hip_debug_set_repeat_text_budget", "ribbit_hip_debug_set_small_record_capacity"):
+        t[name] = (st, [vp, sz])
+    for name in ("ribbit_bed_overlap_text", "ribbit_bed_rows_text", "ribbit_bed_composition_text", "ribbit_bed_primers_text",
+                 "ribbit_bed_primer_pairs_text"):
+        t[name] = (st, [cp, sz, vp, sz, pvp, psz])           # BED text, an array with a record per row
+    for name in ("ribbit_text_free", "ribbit_runs_free", "ribbit_intervals_free", "ribbit_loci_free", "ribbit_motif_classes_free",
+                 "ribbit_compounds_free", "ribbit_row_purity_free", "ribbit_interruptions_free", "ribbit_nearest_free", "ribbit_composition_free",
+                 "ribbit_primers_free", "ribbit_primer_pairs_free", "ribbit_products_free"):
+        t[name] = (None, [vp])
+    # the row outputs: the device form takes the handle, the host form the record's length, or its bases and their number
+    length, bases = [i64], [cp, i64]
+    for name, lead, rest in (("mask_record", bases, [vp, sz, i32, i32, pvp, psz]),
+                             ("record_loci", length, [vp, sz, i32, pvp, psz]),
+                             ("record_density", length, [vp, sz, i32, pvp, psz]),
+                             ("record_overlap", length, [vp, sz, vp, sz, pvp, P(OverlapTotals)]),
+                             ("record_nearest", length, [vp, sz, vp, sz, pvp]),
+                             ("record_composition", bases, [vp, sz, i32, pvp]),
+                             ("record_base_windows", bases, [i32, pvp, psz]),
+                             ("record_primers", bases, [vp, sz, vp, sz, P(PrimerParams), pvp]),
+                             ("record_primer_pairs", bases, [vp, sz, vp, sz, P(PrimerParams), P(PrimerPairParams), pvp]),
+                             ("record_oligo_sites", bases, [vp, sz, P(ProductParams), pvp, pvp, psz]),
+                             ("record_primer_products", bases, [vp, sz, P(ProductParams), pvp]),
+                             ("record_best", length, [vp, sz, pvp, psz, P(i64)]),
+                             ("record_classes", length, [vp, sz, vp, vp, pvp, pvp, pvp, psz]),
+                             ("record_compounds", length, [vp, vp, sz, i32, pvp, psz, pvp, psz]),
+                             ("record_interruptions", bases, [vp, vp, sz, cp, vp, pvp, pvp, psz, pvp, pvp])):
+        t[f"ribbit_hip_{name}"], t[f"ribbit_host_{name}"] = (st, [vp] + rest), (st, lead + rest)
+    return t
+
+
+_ABI = _signatures()
+ABI_SYMBOLS = list(_ABI)
+
+
 def library_path() -> str:
     # RIBBIT_HIP_LIBRARY: another build of the same library (the sanitizer build of the CPU tests)
     return os.environ.get("RIBBIT_HIP_LIBRARY") or os.path.join(_HERE, "libribbit_hip.so")
@@ -251,200 +355,55 @@ def load_library():
     global loaded_before_torch
     loaded_before_torch = "torch" not in sys.modules and not _share_torchs_hip_runtime()      # see ribbit_amd.distributed.device_bytes
     L = C.CDLL(path)
-    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
-    L.ribbit_scan_params_default.restype = None
-    L.ribbit_scan_params_default.argtypes = [C.POINTER(ScanParams), i32, i32]
-    L.ribbit_hip_last_error.restype = C.c_char_p
-    L.ribbit_hip_last_error.argtypes = []
-    L.ribbit_hip_abi_version.restype = C.c_int
-    L.ribbit_hip_device_count.restype = C.c_int
-    L.ribbit_hip_open.argtypes = [C.POINTER(ScanParams), C.c_int, C.POINTER(vp)]
-    L.ribbit_hip_close.argtypes = [vp]
-    L.ribbit_hip_set_stream.argtypes = [vp, vp]
-    L.ribbit_hip_load_record.argtypes = [vp, C.c_char_p, i64]
-    L.ribbit_hip_load_record_device.argtypes = [vp, vp, i64]
-    L.ribbit_hip_load_record_pinned.argtypes = [vp, vp, i64]
-    L.ribbit_hip_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]
-    L.ribbit_hip_host_free.argtypes = [vp]
-    L.ribbit_fasta_open.argtypes = [C.c_char_p, C.c_int, C.POINTER(vp)]
-    L.ribbit_fasta_next.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_int)]
-    L.ribbit_fasta_release.argtypes = [vp, vp]
-    L.ribbit_fasta_close.argtypes = [vp]
-    L.ribbit_fasta_last_error.restype = C.c_char_p
-    for f in ("ribbit_hip_scan_perfect_runs", "ribbit_hip_perfect_calls", "ribbit_hip_seeds_perfect", "ribbit_hip_subst_calls",
-              "ribbit_hip_anchored_calls", "ribbit_hip_dispatch_seeds"):
-        getattr(L, f).argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_hip_seeds_substitutions.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_hip_seeds_anchored.argtypes = [vp] + [C.POINTER(vp), C.POINTER(C.c_size_t)] * 3
-    L.ribbit_hip_guard_hits.restype = i64
-    L.ribbit_hip_guard_hits.argtypes = [vp]
-    L.ribbit_host_replay_calls.argtypes = [C.POINTER(ScanParams), i64, vp, vp, vp, C.c_size_t, vp, C.c_size_t,
-                                           vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(SeedLists)]
-    L.ribbit_seed_lists_free.restype = None
-    L.ribbit_seed_lists_free.argtypes = [C.POINTER(SeedLists)]
-    L.ribbit_debug_last_merge.restype = None
-    L.ribbit_debug_last_merge.argtypes = [C.c_int, C.POINTER(C.c_int32 * 5)]
-    L.ribbit_debug_last_device_merge.restype = None
-    L.ribbit_debug_last_device_merge.argtypes = [C.POINTER(C.c_int32 * 5)]
-    L.ribbit_debug_last_dispatch_ranges.restype = C.c_int32
-    L.ribbit_debug_last_dispatch_ranges.argtypes = []
-    L.ribbit_host_debug_thread_faults.restype = i64
-    L.ribbit_host_debug_thread_faults.argtypes = [C.c_int32, C.c_int32]
-    L.ribbit_debug_alignment_counters.restype = None
-    L.ribbit_debug_alignment_counters.argtypes = [C.POINTER(C.c_int64 * 3)]
-    L.ribbit_hip_device_pci_bus_id.argtypes = [C.c_int, C.c_char_p, C.c_size_t]
-    L.ribbit_hip_adopt_dispatch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    L.ribbit_hip_refine_met_empty_query.argtypes = [C.c_void_p]
-    L.ribbit_debug_level_counters.restype = None
-    L.ribbit_debug_level_counters.argtypes = [C.POINTER(C.c_int64 * 3)]
-    L.ribbit_debug_small_motif_counters.restype = None
-    L.ribbit_debug_small_motif_counters.argtypes = [C.POINTER(C.c_int64 * 2)]
-    L.ribbit_hip_small_motifs.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.ribbit_hip_seed_best_rows.argtypes = [vp, vp, vp, vp]
-    L.ribbit_debug_set_merge_min_range.restype = None
-    L.ribbit_debug_set_merge_min_range.argtypes = [C.c_size_t]
-    L.ribbit_host_longest_runs.argtypes = [C.POINTER(ScanParams), i64, vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp]
-    L.ribbit_hip_plane_bits.argtypes = [vp, i32, i64, i64, vp]
-    L.ribbit_hip_range_popcount.argtypes = [vp, i32, i64, i64, C.POINTER(i32)]
-    L.ribbit_hip_plane_words.restype = i64
-    L.ribbit_hip_plane_words.argtypes = [vp]
-    L.ribbit_hip_packed_plane.argtypes = [vp, C.c_int, vp]
-    L.ribbit_hip_last_timing_ms.argtypes = [vp, C.c_int, C.POINTER(C.c_double)]
-    L.ribbit_refine_params_default.restype = None
-    L.ribbit_refine_params_default.argtypes = [C.POINTER(RefineParams), i32, i32]
-    L.ribbit_hip_seed_longest_runs.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_hip_refine_jobs.argtypes = [vp, C.POINTER(RefineParams), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp)]
-    L.ribbit_host_refine_jobs.argtypes = [C.POINTER(ScanParams), C.POINTER(RefineParams), i64, vp, vp, vp, C.c_size_t,
-                                          vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t),
-                                          C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_refine_jobs_free.restype = None
-    L.ribbit_refine_jobs_free.argtypes = [vp, vp]
-    L.ribbit_hip_refine_bed.argtypes = [vp, C.POINTER(RefineParams), C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_host_refine_bed.argtypes = [C.POINTER(ScanParams), C.POINTER(RefineParams), C.c_char_p, i64, vp, vp, vp, C.c_size_t,
-                                         vp, C.c_size_t, vp, C.c_size_t, C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_text_free.restype = None
-    L.ribbit_text_free.argtypes = [vp]
-    L.ribbit_hip_xa_words.argtypes = [vp, i64, i64, vp]
-    L.ribbit_hip_perfect_runs_partial.argtypes = [vp, i64, i64, i64, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_hip_scan_perfect_chunk.argtypes = [vp, i64, i64, i64, vp, C.c_size_t, vp, C.c_size_t,
-                                                C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_hip_host_register.argtypes = [vp, C.c_size_t]
-    L.ribbit_hip_host_unregister.argtypes = [vp]
-    L.ribbit_hip_set_host_threads.argtypes = [vp, i32]
-    L.ribbit_hip_set_timing.argtypes = [vp, i32]
-    L.ribbit_hip_debug_set_event_capacity.argtypes = [vp, C.c_size_t]
-    L.ribbit_hip_debug_set_scan_split.argtypes = [vp, i32, i32]
-    L.ribbit_hip_debug_last_scan_split.argtypes = [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    L.ribbit_hip_debug_pair_events.argtypes = [vp, vp, C.c_size_t, i64, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]
-    L.ribbit_hip_debug_pair_events_sharded.argtypes = [vp, vp, vp, C.c_size_t, i64, i64, i64, i64, C.POINTER(DebugPairing)]
-    L.ribbit_hip_ssw_passes.argtypes = [vp, vp, C.c_size_t, C.c_char_p, C.c_size_t, i32, vp]
-    L.ribbit_hip_ssw_align_jobs.argtypes = [vp, vp, C.c_size_t, C.c_char_p, C.c_size_t, i32, vp, vp, C.c_size_t, vp, vp]
-    L.ribbit_hip_scan_perfect_begin.argtypes = [vp, i64, i64, i64]
-    L.ribbit_hip_scan_perfect_end.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int,
-                                              C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_hip_scan_perfect_wait.argtypes = [vp]
-    L.ribbit_hip_scan_perfect_end_device.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_host_perfect_runs_from_events.argtypes = [C.POINTER(ScanParams), C.c_size_t, vp, vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_runs_free.restype = None
-    L.ribbit_runs_free.argtypes = [vp]
-    L.ribbit_ssw_align.argtypes = [C.c_char_p, i32, C.c_char_p, i32, i32, C.POINTER(Alignment), C.c_char_p, C.c_size_t]
-    L.ribbit_debug_ssw_align_periodic.argtypes = [C.c_char_p, i32, C.c_char_p, i32, i32, i32, C.POINTER(Alignment), C.c_char_p, C.c_size_t]
-    L.ribbit_hip_stage_calls_chunk.argtypes = [vp, C.c_int, i64, i64, i64, i64, C.POINTER(ChunkCalls)]
-    L.ribbit_hip_xa_words_strided.argtypes = [vp, i64, i64, vp, i64]
-    L.ribbit_host_merge_chunks.argtypes = [C.POINTER(ScanParams), i64, vp, vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(ChunkPart), C.c_size_t,
-                                           C.POINTER(SeedLists)]
-    L.ribbit_hip_debug_stream_read.argtypes = [vp, i64, C.POINTER(i64)]
-    L.ribbit_hip_last_event_count.restype = i64
-    L.ribbit_hip_last_event_count.argtypes = [vp]
-    L.ribbit_hip_mask_record.argtypes = [vp, vp, C.c_size_t, i32, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_host_mask_record.argtypes = [C.c_char_p, i64, vp, C.c_size_t, i32, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_hip_repeat_sequences.argtypes = [vp, C.c_char_p, vp, C.c_size_t, i32, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
-    L.ribbit_host_repeat_sequences.argtypes = [C.c_char_p, C.c_char_p, i64, vp, C.c_size_t, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_hip_debug_set_repeat_text_budget.argtypes = [vp, C.c_size_t]
-    L.ribbit_hip_debug_set_small_record_capacity.argtypes = [vp, C.c_size_t]
-    L.ribbit_bed_intervals.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_intervals_free.restype = None
-    L.ribbit_intervals_free.argtypes = [vp]
-    L.ribbit_hip_record_loci.argtypes = [vp, vp, C.c_size_t, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_hip_record_density.argtypes = [vp, vp, C.c_size_t, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_host_record_loci.argtypes = [i64, vp, C.c_size_t, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_host_record_density.argtypes = [i64, vp, C.c_size_t, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_loci_free.restype = None
-    L.ribbit_loci_free.argtypes = [vp]
-    L.ribbit_bed_loci_text.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_hip_record_overlap.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(OverlapTotals)]
-    L.ribbit_host_record_overlap.argtypes = [i64, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(OverlapTotals)]
-    L.ribbit_bed_overlap_text.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_hip_record_best.argtypes = [vp, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(i64)]
-    L.ribbit_host_record_best.argtypes = [i64, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(i64)]
-    L.ribbit_bed_rows_text.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_bed_motifs.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_hip_record_classes.argtypes = [vp, vp, C.c_size_t, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_host_record_classes.argtypes = [i64, vp, C.c_size_t, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_motif_classes_free.argtypes = [vp]
-    L.ribbit_motif_classes_free.restype = None
-    L.ribbit_bed_class_text.argtypes = [C.c_char_p, C.c_size_t, vp, vp, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_class_summary_text.argtypes = [C.c_char_p, vp, C.c_size_t, vp, vp, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_hip_record_compounds.argtypes = [vp, vp, vp, C.c_size_t, i32, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_host_record_compounds.argtypes = [i64, vp, vp, C.c_size_t, i32, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_compounds_free.argtypes = [vp]
-    L.ribbit_compounds_free.restype = None
-    L.ribbit_class_labels.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp)]
-    L.ribbit_compound_text.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, i64, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_bed_cigars.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_hip_record_interruptions.argtypes = [vp, vp, vp, C.c_size_t, C.c_char_p, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(vp)]
-    L.ribbit_host_record_interruptions.argtypes = [C.c_char_p, i64, vp, vp, C.c_size_t, C.c_char_p, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp),
-                                                   C.POINTER(vp)]
-    L.ribbit_row_purity_free.argtypes = [vp]
-    L.ribbit_row_purity_free.restype = None
-    L.ribbit_interruptions_free.argtypes = [vp]
-    L.ribbit_interruptions_free.restype = None
-    L.ribbit_interruption_text.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, vp, C.c_size_t, vp, vp, C.c_size_t, C.c_char_p, C.c_char_p, vp, C.POINTER(vp),
-                                           C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
-    L.ribbit_bed_purity_text.argtypes = [C.c_char_p, C.c_size_t, vp, vp, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_hip_record_nearest.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp)]
-    L.ribbit_host_record_nearest.argtypes = [i64, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp)]
-    L.ribbit_nearest_free.argtypes = [vp]
-    L.ribbit_nearest_free.restype = None
-    L.ribbit_bed_nearest_text.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_size_t, vp, C.c_char_p, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_nearest_other_text.argtypes = [C.c_char_p, vp, C.c_char_p, vp, C.c_size_t, vp, vp, C.c_char_p, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_hip_record_composition.argtypes = [vp, vp, C.c_size_t, i32, C.POINTER(vp)]
-    L.ribbit_hip_record_base_windows.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_host_record_composition.argtypes = [C.c_char_p, i64, vp, C.c_size_t, i32, C.POINTER(vp)]
-    L.ribbit_host_record_base_windows.argtypes = [C.c_char_p, i64, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_composition_free.argtypes = [vp]
-    L.ribbit_composition_free.restype = None
-    L.ribbit_debug_composition_prefix_builds.argtypes = []
-    L.ribbit_debug_composition_prefix_builds.restype = i64
-    L.ribbit_bed_composition_text.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_base_windows_text.argtypes = [C.c_char_p, i64, i32, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_primer_params_default.argtypes = [C.POINTER(PrimerParams)]
-    L.ribbit_primer_params_default.restype = None
-    L.ribbit_hip_record_primers.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(PrimerParams), C.POINTER(vp)]
-    L.ribbit_host_record_primers.argtypes = [C.c_char_p, i64, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(PrimerParams), C.POINTER(vp)]
-    L.ribbit_primers_free.argtypes = [vp]
-    L.ribbit_primers_free.restype = None
-    L.ribbit_bed_primers_text.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_primer_pair_params_default.argtypes = [C.POINTER(PrimerPairParams)]
-    L.ribbit_primer_pair_params_default.restype = None
-    L.ribbit_hip_record_primer_pairs.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(PrimerParams), C.POINTER(PrimerPairParams), C.POINTER(vp)]
-    L.ribbit_host_record_primer_pairs.argtypes = [C.c_char_p, i64, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(PrimerParams), C.POINTER(PrimerPairParams), C.POINTER(vp)]
-    L.ribbit_primer_pairs_free.argtypes = [vp]
-    L.ribbit_primer_pairs_free.restype = None
-    L.ribbit_host_oligo_duplex.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(i32), C.POINTER(i32)]
-    L.ribbit_host_oligo_hairpin.argtypes = [C.c_char_p, C.POINTER(i32)]
-    L.ribbit_bed_primer_pairs_text.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_product_params_default.argtypes = [C.POINTER(ProductParams)]
-    L.ribbit_product_params_default.restype = None
-    L.ribbit_hip_record_oligo_sites.argtypes = [vp, vp, C.c_size_t, C.POINTER(ProductParams), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_host_record_oligo_sites.argtypes = [C.c_char_p, i64, vp, C.c_size_t, C.POINTER(ProductParams), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.ribbit_hip_record_primer_products.argtypes = [vp, vp, C.c_size_t, C.POINTER(ProductParams), C.POINTER(vp)]
-    L.ribbit_host_record_primer_products.argtypes = [C.c_char_p, i64, vp, C.c_size_t, C.POINTER(ProductParams), C.POINTER(vp)]
-    L.ribbit_products_free.argtypes = [vp]
-    L.ribbit_products_free.restype = None
-    L.ribbit_bed_primer_products_text.argtypes = [C.c_char_p, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    for name, (restype, argtypes) in _ABI.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
+
+
+# what every wrapper below is made of ------------------------------------------------------------
+def _ok(label: str, rc: int) -> None:
+    """the status check: label is the symbol's name for a module-level function, ribbit_hip for a Scanner method"""
+    if rc != 0:
+        raise RibbitHipError(f"{label} error {rc}: {load_library().ribbit_hip_last_error().decode()}")
+
+
+def _ptr(a):
+    """the address of an array, or None when it is empty.  The address does not keep the array alive: `a` is a local name of
+    the caller's, bound until the C call has returned."""
+    return a.ctypes.data if len(a) else None
+
+
+def _bytes(text) -> bytes:
+    return text.encode() if isinstance(text, str) else bytes(text)
+
+
+def _name(name) -> bytes:
+    raw = _bytes(name)
+    if b"\0" in raw:
+        raise ValueError("a record name cannot hold a NUL byte")
+    return raw
+
+
+def _records(a, dt) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(a, dtype=dt).reshape(-1))
+
+
+def _pairs(intervals) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(intervals, dtype=np.int32).reshape(-1, 2))
+
+
+def _int32(value, what: str) -> int:
+    value = int(value)
+    if not -(1 << 31) <= value < (1 << 31):
+        raise ValueError(f"{what} {value} is not an int32")
+    return value
+
+
+def _all_int32(a, message: str) -> None:
+    if len(a) and (a.min() < -(1 << 31) or a.max() >= (1 << 31)):
+        raise ValueError(message)
 
 
 def _copy(ptr, n, dt):
@@ -461,6 +420,106 @@ def _view(ptr, n, dt):
     v = np.frombuffer((C.c_char * (n * dt.itemsize)).from_address(ptr), dtype=dt)
     v.flags.writeable = False
     return v
+
+
+def _host(symbol: str, *lead) -> tuple:
+    """a call of a module-level function: the entry point, its leading arguments, its name as the error label, and that the
+    results are malloc'ed and the caller's to free.  Scanner._dev makes the device form's: the handle leads, the label is
+    ribbit_hip, the results are the handle's."""
+    return symbol, lead, symbol, True
+
+
+def _host_bases(symbol: str, sequence) -> tuple:
+    seq = bytes(sequence)
+    return _host(symbol, seq, len(seq))
+
+
+def _call(call, *args) -> bool:
+    """make the call (a symbol's name, or what _host / Scanner._dev return) with args behind its leading arguments and check
+    its status -> whether the results are the caller's to free"""
+    symbol, lead, label, owned = _host(call) if isinstance(call, str) else call
+    _ok(label, getattr(load_library(), symbol)(*lead, *args))
+    return owned
+
+
+def _free(owned: bool, free: str, *pointers) -> None:
+    if owned:
+        for p in pointers:
+            getattr(load_library(), free)(p)
+
+
+def _array(call, *args, dt, free: str, count=None, tail=()) -> np.ndarray:
+    """a call whose result is one array of dt records: `count` of them, or as many as the call says behind the pointer; copied,
+    and freed where it is the caller's"""
+    out, n = C.c_void_p(), C.c_size_t()
+    owned = _call(call, *args, C.byref(out), *(() if count is not None else (C.byref(n),)), *tail)
+    try:
+        return _copy(out.value, n.value if count is None else count, dt)
+    finally:
+        _free(owned, free, out)
+
+
+def _text(call, *args, tail=()) -> bytes:
+    """a call whose result is text and its length: copied, and freed where it is the caller's"""
+    text, n = C.c_void_p(), C.c_size_t()
+    owned = _call(call, *args, C.byref(text), C.byref(n), *tail)
+    try:
+        return C.string_at(text.value, n.value) if n.value else b""
+    finally:
+        _free(owned, "ribbit_text_free", text)
+
+
+def _params(struct, default: str, c_name: str, fields: dict):
+    p = struct()
+    getattr(load_library(), default)(C.byref(p))
+    names = {n for n, _ in struct._fields_}
+    for name, value in fields.items():
+        if name not in names:
+            raise TypeError(f"{c_name} has no field {name!r}")
+        if not -2**31 <= int(value) < 2**31:
+            raise ValueError(f"{name} {value} does not fit int32")
+        setattr(p, name, int(value))
+    return p
+
+
+def _params_arg(params, builder, struct, what: str = "params"):
+    if params is None:
+        params = builder()
+    if not isinstance(params, struct):
+        raise TypeError(f"{what}: a {struct.__name__} ({builder.__name__}())")
+    return params
+
+
+def _scan_params(min_motif: int, max_motif: int) -> ScanParams:
+    params = ScanParams()
+    load_library().ribbit_scan_params_default(C.byref(params), min_motif, max_motif)
+    return params
+
+
+def _refine_params(refine_params, min_motif: int, max_motif: int) -> RefineParams:
+    if refine_params is None:
+        refine_params = RefineParams()
+        load_library().ribbit_refine_params_default(C.byref(refine_params), min_motif, max_motif)
+    return refine_params
+
+
+def _seed_lists(out: SeedLists) -> dict:
+    """a filled RibbitSeedLists -> dict of copies; the lists are freed"""
+    try:
+        return {"perfect": _copy(out.perfect, out.n_perfect, SEED_DT), "subst": _copy(out.subst, out.n_subst, SEED_DT),
+                "anchored": _copy(out.anchored, out.n_anchored, SEED_DT), "dispatch": _copy(out.dispatch, out.n_dispatch, SEED_DT),
+                "guard_hits": int(out.guard_hits)}
+    finally:
+        load_library().ribbit_seed_lists_free(C.byref(out))
+
+
+def _pool(texts, offsets):
+    """a pool of texts and its offsets as given, or made of a list of strings (offsets None)"""
+    if offsets is None:
+        parts = [_bytes(t) for t in texts]
+        offsets = np.concatenate([[0], np.cumsum([len(p) for p in parts], dtype=np.int64)])
+        texts = b"".join(parts)
+    return _bytes(texts), np.asarray(offsets)
 
 
 def pack_planes(sequence: bytes, max_motif: int):
@@ -498,36 +557,24 @@ def pack_bit_planes(planes_bits, length: int):
 def host_replay_calls(min_motif: int, max_motif: int, sequence: bytes, perfect_calls, subst_calls=None,
                       anchored_calls=None, xa=None, xa_stride: int = 0):
     """ribbit_host_replay_calls: call lists -> dict(perfect, subst, anchored, dispatch, guard_hits). No GPU needed."""
-    L = load_library()
-    params = ScanParams()
-    L.ribbit_scan_params_default(C.byref(params), min_motif, max_motif)
+    params = _scan_params(min_motif, max_motif)
     hi, lo, brk = pack_planes(sequence, max_motif)
     empty = np.zeros(0, CALL_DT)
     pc = np.ascontiguousarray(perfect_calls, dtype=CALL_DT)
     sc = np.ascontiguousarray(subst_calls if subst_calls is not None else empty, dtype=CALL_DT)
     ac = np.ascontiguousarray(anchored_calls if anchored_calls is not None else empty, dtype=CALL_DT)
     out = SeedLists()
-    rc = L.ribbit_host_replay_calls(C.byref(params), len(sequence), hi.ctypes.data, lo.ctypes.data, brk.ctypes.data, len(hi),
-                                    xa.ctypes.data if xa is not None else None, xa_stride,
-                                    pc.ctypes.data, len(pc), sc.ctypes.data, len(sc),
-                                    ac.ctypes.data if anchored_calls is not None else None, len(ac), C.byref(out))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_host_replay_calls error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return {"perfect": _copy(out.perfect, out.n_perfect, SEED_DT), "subst": _copy(out.subst, out.n_subst, SEED_DT),
-                "anchored": _copy(out.anchored, out.n_anchored, SEED_DT), "dispatch": _copy(out.dispatch, out.n_dispatch, SEED_DT),
-                "guard_hits": int(out.guard_hits)}
-    finally:
-        L.ribbit_seed_lists_free(C.byref(out))
+    _call("ribbit_host_replay_calls", C.byref(params), len(sequence), hi.ctypes.data, lo.ctypes.data, brk.ctypes.data, len(hi),
+          xa.ctypes.data if xa is not None else None, xa_stride, pc.ctypes.data, len(pc), sc.ctypes.data, len(sc),
+          ac.ctypes.data if anchored_calls is not None else None, len(ac), C.byref(out))
+    return _seed_lists(out)
 
 
 def host_merge_chunks(min_motif: int, max_motif: int, length: int, hi, lo, brk, xa, xa_stride: int, parts):
     """ribbit_host_merge_chunks: the merging rank's half of the chunk-sharded path.  parts (chunk order) = dicts with
     RUN_DT arrays `runs`, `halves` and, per window stage s in ("subst", "anchored"), `<s>_calls` (CALL_DT), `<s>_pend`
     (int32 per call, or None), `<s>_tail_pend` (int), `<s>_flush` (CALL_DT).  -> dict of the record's seed lists."""
-    L = load_library()
-    params = ScanParams()
-    L.ribbit_scan_params_default(C.byref(params), min_motif, max_motif)
+    params = _scan_params(min_motif, max_motif)
     hi, lo, brk = (np.ascontiguousarray(a, dtype="<u4") for a in (hi, lo, brk))
     keep = []                                        # arrays the C structs point into
 
@@ -554,41 +601,29 @@ def host_merge_chunks(min_motif: int, max_motif: int, length: int, hi, lo, brk, 
             cc.tail_pend = int(p[f"{stage}_tail_pend"])
             cc.inexact = int(p.get(f"{stage}_inexact", 0))
     out = SeedLists()
-    rc = L.ribbit_host_merge_chunks(C.byref(params), length, hi.ctypes.data, lo.ctypes.data, brk.ctypes.data, len(hi),
-                                    xa.ctypes.data if xa is not None else None, xa_stride, cparts, len(parts), C.byref(out))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_host_merge_chunks error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return {"perfect": _copy(out.perfect, out.n_perfect, SEED_DT), "subst": _copy(out.subst, out.n_subst, SEED_DT),
-                "anchored": _copy(out.anchored, out.n_anchored, SEED_DT), "dispatch": _copy(out.dispatch, out.n_dispatch, SEED_DT),
-                "guard_hits": int(out.guard_hits)}
-    finally:
-        L.ribbit_seed_lists_free(C.byref(out))
+    _call("ribbit_host_merge_chunks", C.byref(params), length, hi.ctypes.data, lo.ctypes.data, brk.ctypes.data, len(hi),
+          xa.ctypes.data if xa is not None else None, xa_stride, cparts, len(parts), C.byref(out))
+    return _seed_lists(out)
+
+
+def _alignment(symbol: str, cap: int, *args):
+    """-> (dict of alignment fields, cigar string) of a call that ends in an alignment, a text buffer and its capacity"""
+    out, buf = Alignment(), C.create_string_buffer(cap)
+    _call(symbol, *args, C.byref(out), buf, cap)
+    return {n: getattr(out, n) for n, _ in Alignment._fields_}, buf.value.decode()
 
 
 def ssw_align(query: bytes, ref: bytes, ref_len: int | None = None, mask_len: int = 15):
     """ribbit_ssw_align -> (dict of alignment fields, cigar string)"""
-    L = load_library()
-    out = Alignment()
-    cap = 16 * (len(query) + len(ref)) + 64
-    buf = C.create_string_buffer(cap)
-    rc = L.ribbit_ssw_align(query, len(query), ref, len(ref) if ref_len is None else ref_len, mask_len, C.byref(out), buf, cap)
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_ssw_align error {rc}: {L.ribbit_hip_last_error().decode()}")
-    return {n: getattr(out, n) for n, _ in Alignment._fields_}, buf.value.decode()
+    return _alignment("ribbit_ssw_align", 16 * (len(query) + len(ref)) + 64,
+                      query, len(query), ref, len(ref) if ref_len is None else ref_len, mask_len)
 
 
 def ssw_align_periodic(query: bytes, motif: bytes, ref_len: int, mask_len: int = 15):
     """ribbit_debug_ssw_align_periodic (test hook): the alignment against `motif` repeated past ref_len, finished the way
     refinement finishes an alignment whose path is known -> (dict of alignment fields, cigar string)"""
-    L = load_library()
-    out = Alignment()
-    cap = 16 * (len(query) + ref_len + len(motif)) + 64
-    buf = C.create_string_buffer(cap)
-    rc = L.ribbit_debug_ssw_align_periodic(query, len(query), motif, len(motif), ref_len, mask_len, C.byref(out), buf, cap)
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_debug_ssw_align_periodic error {rc}: {L.ribbit_hip_last_error().decode()}")
-    return {n: getattr(out, n) for n, _ in Alignment._fields_}, buf.value.decode()
+    return _alignment("ribbit_debug_ssw_align_periodic", 16 * (len(query) + ref_len + len(motif)) + 64,
+                      query, len(query), motif, len(motif), ref_len, mask_len)
 
 
 def _jobs_with_motifs(jobs, pool: bytes):
@@ -596,469 +631,211 @@ def _jobs_with_motifs(jobs, pool: bytes):
     return [(j, pool[int(j["motif_offset"]):int(j["motif_offset"]) + int(j["atomicity"])].decode()) for j in jobs]
 
 
+def _counters(symbol: str, ctype, n: int) -> tuple:
+    out = (ctype * n)()
+    getattr(load_library(), symbol)(C.byref(out))
+    return tuple(int(v) for v in out)
+
+
 def alignment_counters():
     """(alignments refinement made, of them with GPU passes, with GPU paths), cumulative"""
-    L = load_library()
-    out = (C.c_int64 * 3)()
-    L.ribbit_debug_alignment_counters(C.byref(out))
-    return int(out[0]), int(out[1]), int(out[2])
+    return _counters("ribbit_debug_alignment_counters", C.c_int64, 3)
 
 
 def level_counters():
     """(levels run, nodes put off, alignments of those nodes) of the level-by-level GPU refinement of long-motif seeds'
     recursion trees, cumulative"""
-    L = load_library()
-    out = (C.c_int64 * 3)()
-    L.ribbit_debug_level_counters(C.byref(out))
-    return int(out[0]), int(out[1]), int(out[2])
+    return _counters("ribbit_debug_level_counters", C.c_int64, 3)
 
 
 def last_device_merge():
     """(ranges the GPU merged, ranges it was given but left to the host threads, ranges the host threads merged while its kernel
     ran, ranges of the stage, ranges merged again by the validation walk) of the calling thread's last anchored-stage merge; the
     first three are zero when the merge ran on the host threads alone"""
-    L = load_library()
-    out = (C.c_int32 * 5)()
-    L.ribbit_debug_last_device_merge(C.byref(out))
-    return tuple(int(v) for v in out)
+    return _counters("ribbit_debug_last_device_merge", C.c_int32, 5)
 
 
 def small_motif_counters():
     """(seeds refinement took from the GPU's possibleMotifs table, seeds it computed on the host), cumulative"""
-    L = load_library()
-    out = (C.c_int64 * 2)()
-    L.ribbit_debug_small_motif_counters(C.byref(out))
-    return int(out[0]), int(out[1])
+    return _counters("ribbit_debug_small_motif_counters", C.c_int64, 2)
 
 
 def host_longest_runs(min_motif: int, max_motif: int, sequence: bytes, seeds):
     """ribbit_host_longest_runs: longestContinuousMatches of seeds on the composed planes, recomputed on the host. No GPU."""
-    L = load_library()
-    params = ScanParams()
-    L.ribbit_scan_params_default(C.byref(params), min_motif, max_motif)
+    params = _scan_params(min_motif, max_motif)
     hi, lo, brk = pack_planes(sequence, max_motif)
     s = np.ascontiguousarray(seeds, dtype=SEED_DT)
     out = np.zeros(len(s), dtype="<i4")
-    rc = L.ribbit_host_longest_runs(C.byref(params), len(sequence), hi.ctypes.data, lo.ctypes.data, brk.ctypes.data, len(hi),
-                                    s.ctypes.data, len(s), out.ctypes.data)
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_host_longest_runs error {rc}: {L.ribbit_hip_last_error().decode()}")
+    _call("ribbit_host_longest_runs", C.byref(params), len(sequence), hi.ctypes.data, lo.ctypes.data, brk.ctypes.data, len(hi),
+          s.ctypes.data, len(s), out.ctypes.data)
     return out
 
 
 def host_refine_jobs(min_motif: int, max_motif: int, sequence: bytes, xa, xa_stride: int, dispatch, refine_params=None):
     """ribbit_host_refine_jobs: dispatch seeds + planes -> (jobs array, motif pool bytes). No GPU needed."""
-    L = load_library()
-    params = ScanParams()
-    L.ribbit_scan_params_default(C.byref(params), min_motif, max_motif)
-    rp = refine_params
-    if rp is None:
-        rp = RefineParams()
-        L.ribbit_refine_params_default(C.byref(rp), min_motif, max_motif)
+    params, rp = _scan_params(min_motif, max_motif), _refine_params(refine_params, min_motif, max_motif)
     hi, lo, brk = pack_planes(sequence, max_motif)
     d = np.ascontiguousarray(dispatch, dtype=SEED_DT)
     jobs, nj, pool, npool = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_host_refine_jobs(C.byref(params), C.byref(rp), len(sequence), hi.ctypes.data, lo.ctypes.data, brk.ctypes.data,
-                                   len(hi), xa.ctypes.data if xa is not None else None, xa_stride, d.ctypes.data, len(d),
-                                   C.byref(jobs), C.byref(nj), C.byref(pool), C.byref(npool))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_host_refine_jobs error {rc}: {L.ribbit_hip_last_error().decode()}")
+    _call("ribbit_host_refine_jobs", C.byref(params), C.byref(rp), len(sequence), hi.ctypes.data, lo.ctypes.data, brk.ctypes.data,
+          len(hi), xa.ctypes.data if xa is not None else None, xa_stride, d.ctypes.data, len(d),
+          C.byref(jobs), C.byref(nj), C.byref(pool), C.byref(npool))
     try:
         return _copy(jobs.value, nj.value, JOB_DT), C.string_at(pool.value, npool.value)
     finally:
-        L.ribbit_refine_jobs_free(jobs, pool)
+        load_library().ribbit_refine_jobs_free(jobs, pool)
 
 
 def host_refine_bed(min_motif: int, max_motif: int, sequence: bytes, xa, xa_stride: int, dispatch, sequence_id: str = "seq",
                     refine_params=None) -> str:
     """ribbit_host_refine_bed: dispatch seeds + planes -> BED text.  No GPU needed."""
-    L = load_library()
-    params = ScanParams()
-    L.ribbit_scan_params_default(C.byref(params), min_motif, max_motif)
-    rp = refine_params
-    if rp is None:
-        rp = RefineParams()
-        L.ribbit_refine_params_default(C.byref(rp), min_motif, max_motif)
+    params, rp = _scan_params(min_motif, max_motif), _refine_params(refine_params, min_motif, max_motif)
     hi, lo, brk = pack_planes(sequence, max_motif)
     d = np.ascontiguousarray(dispatch, dtype=SEED_DT)
-    text, n = C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_host_refine_bed(C.byref(params), C.byref(rp), sequence, len(sequence), hi.ctypes.data, lo.ctypes.data,
-                                  brk.ctypes.data, len(hi), xa.ctypes.data if xa is not None else None, xa_stride, d.ctypes.data, len(d),
-                                  sequence_id.encode(), C.byref(text), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_host_refine_bed error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return C.string_at(text.value, n.value).decode()
-    finally:
-        L.ribbit_text_free(text)
+    return _text("ribbit_host_refine_bed", C.byref(params), C.byref(rp), sequence, len(sequence), hi.ctypes.data, lo.ctypes.data,
+                 brk.ctypes.data, len(hi), xa.ctypes.data if xa is not None else None, xa_stride, d.ctypes.data, len(d),
+                 sequence_id.encode()).decode()
 
 
-def _mask_args(intervals, mode: str, line_width: int):
+# the row outputs: each marshalled once, for its host twin and its Scanner method ------------------------------
+def _mask_record(call, intervals, mode: str, line_width: int) -> bytes:
     if mode not in MASK_MODES:
         raise ValueError(f"mask mode must be one of {sorted(MASK_MODES)}, got {mode!r}")
-    iv = np.ascontiguousarray(np.asarray(intervals, dtype=np.int32).reshape(-1, 2))
-    return iv, MASK_MODES[mode], int(line_width)
+    iv = _pairs(intervals)
+    return _text(call, _ptr(iv), len(iv), MASK_MODES[mode], int(line_width))
 
 
 def host_mask_record(sequence: bytes, intervals, mode: str = "soft", line_width: int = 60) -> bytes:
     """ribbit_host_mask_record: the masked, line-wrapped FASTA body of `sequence` (no header) under the union of the
     half-open (start, end) rows of `intervals`.  No GPU needed."""
-    L = load_library()
-    iv, m, w = _mask_args(intervals, mode, line_width)
-    seq = bytes(sequence)
-    text, n = C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_host_mask_record(seq, len(seq), iv.ctypes.data if len(iv) else None, len(iv), m, w, C.byref(text), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_host_mask_record error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return C.string_at(text.value, n.value)
-    finally:
-        L.ribbit_text_free(text)
+    return _mask_record(_host_bases("ribbit_host_mask_record", sequence), intervals, mode, line_width)
 
 
 def _repeat_args(name, intervals, flank: int):
-    raw = name.encode() if isinstance(name, str) else bytes(name)
-    if b"\0" in raw:
-        raise ValueError("a record name cannot hold a NUL byte")
+    raw = _name(name)
     flank = int(flank)
     if flank > 0x7FFFFFFF:
         raise ValueError(f"flank {flank} is larger than INT32_MAX")
-    iv = np.ascontiguousarray(np.asarray(intervals, dtype=np.int32).reshape(-1, 2))
-    return raw, iv, max(flank, -(1 << 31))
+    return raw, _pairs(intervals), max(flank, -(1 << 31))
 
 
 def host_repeat_sequences(name, sequence: bytes, intervals, flank: int = 100) -> bytes:
     """ribbit_host_repeat_sequences: one FASTA entry per (start, end) row, in order: ">name:s-e flank=left,right" and the
     row's bases with `flank` bases on either side, clipped to the record (include/ribbit_hip.h).  No GPU needed."""
-    L = load_library()
     raw, iv, f = _repeat_args(name, intervals, flank)
     seq = bytes(sequence)
-    text, n = C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_host_repeat_sequences(raw, seq, len(seq), iv.ctypes.data if len(iv) else None, len(iv), f, C.byref(text), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_host_repeat_sequences error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return C.string_at(text.value, n.value)
-    finally:
-        L.ribbit_text_free(text)
-
-
-def bed_intervals(text) -> np.ndarray:
-    """ribbit_bed_intervals: (start, end) of every row of BED text as refine_bed writes it, an (n, 2) int32 array."""
-    L = load_library()
-    raw = text.encode() if isinstance(text, str) else bytes(text)
-    pairs, n = C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_bed_intervals(raw, len(raw), C.byref(pairs), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_bed_intervals error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return _copy(pairs.value, 2 * n.value, np.dtype("<i4")).reshape(-1, 2)
-    finally:
-        L.ribbit_intervals_free(pairs)
+    return _text("ribbit_host_repeat_sequences", raw, seq, len(seq), _ptr(iv), len(iv), f)
 
 
 def _rows_arg(intervals, value: int, what: str):
-    value = int(value)
-    if not -(1 << 31) <= value < (1 << 31):
-        raise ValueError(f"{what} {value} is not an int32")
-    return np.ascontiguousarray(np.asarray(intervals, dtype=np.int32).reshape(-1, 2)), value
+    value = _int32(value, what)
+    return _pairs(intervals), value
+
+
+def _record_loci(call, intervals, gap: int) -> np.ndarray:
+    iv, gap = _rows_arg(intervals, gap, "gap")
+    return _array(call, _ptr(iv), len(iv), gap, dt=LOCUS_DT, free="ribbit_loci_free")
 
 
 def host_record_loci(length: int, intervals, gap: int = 0) -> np.ndarray:
     """ribbit_host_record_loci: the rows of a record of `length` bases merged into loci (runs of covered positions, joined
     while they lie at most `gap` apart), by ascending start: a LOCUS_DT array (include/ribbit_hip.h).  No GPU needed."""
-    L = load_library()
-    iv, gap = _rows_arg(intervals, gap, "gap")
-    loci, n = C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_host_record_loci(int(length), iv.ctypes.data if len(iv) else None, len(iv), gap, C.byref(loci), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_host_record_loci error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return _copy(loci.value, n.value, LOCUS_DT)
-    finally:
-        L.ribbit_loci_free(loci)
+    return _record_loci(_host("ribbit_host_record_loci", int(length)), intervals, gap)
+
+
+def _record_density(call, intervals, window: int) -> np.ndarray:
+    iv, window = _rows_arg(intervals, window, "window")
+    return _array(call, _ptr(iv), len(iv), window, dt=_I4, free="ribbit_intervals_free")
 
 
 def host_record_density(length: int, intervals, window: int) -> np.ndarray:
     """ribbit_host_record_density: covered bases per window of `window` bases (the last one may be short), int32.  No GPU needed."""
-    L = load_library()
-    iv, window = _rows_arg(intervals, window, "window")
-    cov, n = C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_host_record_density(int(length), iv.ctypes.data if len(iv) else None, len(iv), window, C.byref(cov), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_host_record_density error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return _copy(cov.value, n.value, np.dtype("<i4"))
-    finally:
-        L.ribbit_intervals_free(cov)
+    return _record_density(_host("ribbit_host_record_density", int(length)), intervals, window)
 
 
-def bed_loci_text(name, bed, loci) -> bytes:
-    """ribbit_bed_loci_text: one line per locus of one record: name, start, end, rows, covered and the last ten columns of the
-    locus's best row of `bed` (the record's BED text, row i on line i)."""
-    L = load_library()
-    raw = name.encode() if isinstance(name, str) else bytes(name)
-    if b"\0" in raw:
-        raise ValueError("a record name cannot hold a NUL byte")
-    text_in = bed.encode() if isinstance(bed, str) else bytes(bed)
-    lo = np.ascontiguousarray(np.asarray(loci, dtype=LOCUS_DT).reshape(-1))
-    text, n = C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_bed_loci_text(raw, text_in, len(text_in), lo.ctypes.data if len(lo) else None, len(lo), C.byref(text), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_bed_loci_text error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return C.string_at(text.value, n.value)
-    finally:
-        L.ribbit_text_free(text)
-
-
-def _pairs(intervals) -> np.ndarray:
-    return np.ascontiguousarray(np.asarray(intervals, dtype=np.int32).reshape(-1, 2))
+def _record_overlap(call, rows, other):
+    iv, ot, totals = _pairs(rows), _pairs(other), OverlapTotals()
+    per_row = _array(call, _ptr(iv), len(iv), _ptr(ot), len(ot), dt=_I4, free="ribbit_intervals_free", count=2 * len(iv), tail=(C.byref(totals),))
+    return per_row.reshape(-1, 2), totals.as_dict()
 
 
 def host_record_overlap(length: int, rows, other):
     """ribbit_host_record_overlap: the rows of a record of `length` bases against the intervals `other` -> ((n, 2) int32 array:
     per row the number of OTHER intervals it overlaps and the number of its bases that OTHER covers; the totals as a dict with
     the keys OVERLAP_TOTALS).  The contract is in include/ribbit_hip.h.  No GPU needed."""
-    L = load_library()
-    iv, ot = _pairs(rows), _pairs(other)
-    per_row, totals = C.c_void_p(), OverlapTotals()
-    rc = L.ribbit_host_record_overlap(int(length), iv.ctypes.data if len(iv) else None, len(iv), ot.ctypes.data if len(ot) else None, len(ot),
-                                      C.byref(per_row), C.byref(totals))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_host_record_overlap error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return _copy(per_row.value, 2 * len(iv), np.dtype("<i4")).reshape(-1, 2), totals.as_dict()
-    finally:
-        L.ribbit_intervals_free(per_row)
+    return _record_overlap(_host("ribbit_host_record_overlap", int(length)), rows, other)
 
 
-def bed_overlap_text(bed, per_row) -> bytes:
-    """ribbit_bed_overlap_text: the lines of `bed` (one record's BED text, row i on line i), each with row i's two values of
-    `per_row` appended as two more columns."""
-    L = load_library()
-    text_in = bed.encode() if isinstance(bed, str) else bytes(bed)
-    pr = _pairs(per_row)
-    text, n = C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_bed_overlap_text(text_in, len(text_in), pr.ctypes.data if len(pr) else None, len(pr), C.byref(text), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_bed_overlap_text error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return C.string_at(text.value, n.value)
-    finally:
-        L.ribbit_text_free(text)
+def _record_nearest(call, queries, targets) -> np.ndarray:
+    q, t = _pairs(queries), _pairs(targets)
+    return _array(call, _ptr(q), len(q), _ptr(t), len(t), dt=NEAREST_DT, free="ribbit_nearest_free", count=len(q))
 
 
 def host_record_nearest(length: int, queries, targets) -> np.ndarray:
     """ribbit_host_record_nearest: for every query interval on a record of `length` bases, the target it lies in or overlaps and its
     neighbours to either side -> a NEAREST_DT array, one record per query.  The contract is in include/ribbit_hip.h.  No GPU needed."""
-    L = load_library()
-    q, t = _pairs(queries), _pairs(targets)
-    out = C.c_void_p()
-    rc = L.ribbit_host_record_nearest(int(length), q.ctypes.data if len(q) else None, len(q), t.ctypes.data if len(t) else None, len(t), C.byref(out))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_host_record_nearest error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return _copy(out.value, len(q), NEAREST_DT)
-    finally:
-        L.ribbit_nearest_free(out)
+    return _record_nearest(_host("ribbit_host_record_nearest", int(length)), queries, targets)
 
 
-def _nearest_arg(nearest) -> np.ndarray:
-    return np.ascontiguousarray(np.asarray(nearest, dtype=NEAREST_DT).reshape(-1))
-
-
-def bed_nearest_text(bed, nearest, targets, labels, label_offsets=None) -> bytes:
-    """ribbit_bed_nearest_text: the lines of `bed` (one record's BED text, row i on line i), each with eight more columns: what
-    `nearest` (record_nearest with the rows as queries) names among `targets`.  labels, label_offsets: a pool and its offsets, or
-    a list of strings and None."""
-    L = load_library()
-    text_in = bed.encode() if isinstance(bed, str) else bytes(bed)
-    near = _nearest_arg(nearest)
-    iv, pool, off = _class_args(targets, labels, label_offsets)
-    text, n = C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_bed_nearest_text(text_in, len(text_in), near.ctypes.data if len(near) else None, len(near), iv.ctypes.data if len(iv) else None, pool,
-                                   off.ctypes.data, len(iv), C.byref(text), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_bed_nearest_text error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return C.string_at(text.value, n.value)
-    finally:
-        L.ribbit_text_free(text)
-
-
-def nearest_other_text(name, targets, labels, nearest, rows, motifs, label_offsets=None, motif_offsets=None) -> bytes:
-    """ribbit_nearest_other_text: one line per interval of `targets` (a second BED's intervals on one record, with their labels): name,
-    start, end, label and the eight columns of what `nearest` (record_nearest with the intervals as queries) names among the
-    record's `rows`, a row's label being its motif.  Pools with offsets, or lists of strings and None."""
-    L = load_library()
-    raw = name.encode() if isinstance(name, str) else bytes(name)
-    if b"\0" in raw:
-        raise ValueError("a record name cannot hold a NUL byte")
-    iv, pool, off = _class_args(targets, labels, label_offsets)
-    rw, motif_pool, motif_off = _class_args(rows, motifs, motif_offsets)
-    near = _nearest_arg(nearest)
-    if len(near) != len(iv):
-        raise ValueError(f"{len(iv)} intervals want {len(iv)} nearest records, not {len(near)}")
-    text, n = C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_nearest_other_text(raw, iv.ctypes.data if len(iv) else None, pool, off.ctypes.data, len(iv), near.ctypes.data if len(near) else None,
-                                     rw.ctypes.data if len(rw) else None, motif_pool, motif_off.ctypes.data, len(rw), C.byref(text), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_nearest_other_text error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return C.string_at(text.value, n.value)
-    finally:
-        L.ribbit_text_free(text)
+def _record_composition(call, intervals, flank: int) -> np.ndarray:
+    iv, flank = _rows_arg(intervals, flank, "flank")
+    return _array(call, _ptr(iv), len(iv), flank, dt=COMPOSITION_DT, free="ribbit_composition_free", count=len(iv))
 
 
 def host_record_composition(sequence: bytes, intervals, flank: int = 100) -> np.ndarray:
     """ribbit_host_record_composition: the A, C, G, T and other bases of every (start, end) row of `sequence`, and of the `flank` bases on
     either side of it the length, the C + G, the other bases and the positions that rows cover -> a COMPOSITION_DT array, one record
     per row.  The contract is in include/ribbit_hip.h.  No GPU needed."""
-    L = load_library()
-    iv, flank = _rows_arg(intervals, flank, "flank")
-    seq = bytes(sequence)
-    out = C.c_void_p()
-    rc = L.ribbit_host_record_composition(seq, len(seq), iv.ctypes.data if len(iv) else None, len(iv), flank, C.byref(out))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_host_record_composition error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return _copy(out.value, len(iv), COMPOSITION_DT)
-    finally:
-        L.ribbit_composition_free(out)
+    return _record_composition(_host_bases("ribbit_host_record_composition", sequence), intervals, flank)
+
+
+def _record_base_windows(call, window: int) -> np.ndarray:
+    return _array(call, _int32(window, "window"), dt=BASE_COUNTS_DT, free="ribbit_composition_free")
 
 
 def host_record_base_windows(sequence: bytes, window: int) -> np.ndarray:
     """ribbit_host_record_base_windows: the A, C, G, T and other bases of every window of `window` bases of `sequence` (the last one may
     be short) -> a BASE_COUNTS_DT array.  No GPU needed."""
-    L = load_library()
-    _, window = _rows_arg((), window, "window")
-    seq = bytes(sequence)
-    out, n = C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_host_record_base_windows(seq, len(seq), window, C.byref(out), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_host_record_base_windows error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return _copy(out.value, n.value, BASE_COUNTS_DT)
-    finally:
-        L.ribbit_composition_free(out)
-
-
-def bed_composition_text(bed, rows) -> bytes:
-    """ribbit_bed_composition_text: the lines of `bed` (one record's BED text, row i on line i), each with the 13 values of row i of
-    `rows` (record_composition) appended as 13 more columns."""
-    L = load_library()
-    text_in = bed.encode() if isinstance(bed, str) else bytes(bed)
-    rw = np.ascontiguousarray(np.asarray(rows, dtype=COMPOSITION_DT).reshape(-1))
-    text, n = C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_bed_composition_text(text_in, len(text_in), rw.ctypes.data if len(rw) else None, len(rw), C.byref(text), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_bed_composition_text error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return C.string_at(text.value, n.value)
-    finally:
-        L.ribbit_text_free(text)
-
-
-def base_windows_text(name, length: int, window: int, windows) -> bytes:
-    """ribbit_base_windows_text: one line per window of a record of `length` bases: name, start, end and the five counts of
-    `windows` (record_base_windows)."""
-    L = load_library()
-    raw = name.encode() if isinstance(name, str) else bytes(name)
-    if b"\0" in raw:
-        raise ValueError("a record name cannot hold a NUL byte")
-    _, window = _rows_arg((), window, "window")
-    w = np.ascontiguousarray(np.asarray(windows, dtype=BASE_COUNTS_DT).reshape(-1))
-    text, n = C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_base_windows_text(raw, int(length), window, w.ctypes.data if len(w) else None, len(w), C.byref(text), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_base_windows_text error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return C.string_at(text.value, n.value)
-    finally:
-        L.ribbit_text_free(text)
+    return _record_base_windows(_host_bases("ribbit_host_record_base_windows", sequence), window)
 
 
 def primer_params(**fields) -> PrimerParams:
     """ribbit_primer_params_default with the given fields replaced, e.g. primer_params(flank=100, gc_clamp=0); the ranges are
     checked by the calls that take it (include/ribbit_hip.h)"""
-    p = PrimerParams()
-    load_library().ribbit_primer_params_default(C.byref(p))
-    names = {n for n, _ in PrimerParams._fields_}
-    for name, value in fields.items():
-        if name not in names:
-            raise TypeError(f"RibbitPrimerParams has no field {name!r}")
-        if not -2**31 <= int(value) < 2**31:
-            raise ValueError(f"{name} {value} does not fit int32")
-        setattr(p, name, int(value))
-    return p
+    return _params(PrimerParams, "ribbit_primer_params_default", "RibbitPrimerParams", fields)
 
 
-def _primer_args(intervals, targets, params):
+def primer_pair_params(**fields) -> PrimerPairParams:
+    """ribbit_primer_pair_params_default with the given fields replaced, e.g. primer_pair_params(shortlist=4, max_hairpin=2); the
+    ranges are checked by the calls that take it (include/ribbit_hip.h)"""
+    return _params(PrimerPairParams, "ribbit_primer_pair_params_default", "RibbitPrimerPairParams", fields)
+
+
+def product_params(**fields) -> ProductParams:
+    """ribbit_product_params_default with the given fields replaced, e.g. product_params(seed=12, max_sites=256); the ranges are
+    checked by the calls that take it (include/ribbit_hip.h)"""
+    return _params(ProductParams, "ribbit_product_params_default", "RibbitProductParams", fields)
+
+
+def _record_primers(call, intervals, targets, params) -> np.ndarray:
     iv, tg = _pairs(intervals), _pairs(targets)
-    if params is None:
-        params = primer_params()
-    if not isinstance(params, PrimerParams):
-        raise TypeError("params: a PrimerParams (primer_params())")
-    return iv, tg, params
+    params = _params_arg(params, primer_params, PrimerParams)
+    return _array(call, _ptr(iv), len(iv), _ptr(tg), len(tg), C.byref(params), dt=PRIMERS_DT, free="ribbit_primers_free", count=len(tg))
 
 
 def host_record_primers(sequence: bytes, intervals, targets, params: PrimerParams | None = None) -> np.ndarray:
     """ribbit_host_record_primers: for every (start, end) target a forward primer in the flank to its left and a reverse primer in
     the flank to its right, clear of every base that the rows `intervals` cover or that is not A, C, G or T -> a PRIMERS_DT array,
     one record per target.  The contract is in include/ribbit_hip.h.  No GPU needed."""
-    L = load_library()
-    iv, tg, params = _primer_args(intervals, targets, params)
-    seq = bytes(sequence)
-    out = C.c_void_p()
-    rc = L.ribbit_host_record_primers(seq, len(seq), iv.ctypes.data if len(iv) else None, len(iv), tg.ctypes.data if len(tg) else None, len(tg),
-                                      C.byref(params), C.byref(out))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_host_record_primers error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return _copy(out.value, len(tg), PRIMERS_DT)
-    finally:
-        L.ribbit_primers_free(out)
+    return _record_primers(_host_bases("ribbit_host_record_primers", sequence), intervals, targets, params)
 
 
-def bed_primers_text(bed, rows) -> bytes:
-    """ribbit_bed_primers_text: the lines of `bed` (the targets' BED rows, target i on line i), each with the primers of row i of
-    `rows` (record_primers) appended as 11 more columns."""
-    L = load_library()
-    text_in = bed.encode() if isinstance(bed, str) else bytes(bed)
-    rw = np.ascontiguousarray(np.asarray(rows, dtype=PRIMERS_DT).reshape(-1))
-    text, n = C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_bed_primers_text(text_in, len(text_in), rw.ctypes.data if len(rw) else None, len(rw), C.byref(text), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_bed_primers_text error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return C.string_at(text.value, n.value)
-    finally:
-        L.ribbit_text_free(text)
-
-
-def primer_pair_params(**fields) -> PrimerPairParams:
-    """ribbit_primer_pair_params_default with the given fields replaced, e.g. primer_pair_params(shortlist=4, max_hairpin=2); the
-    ranges are checked by the calls that take it (include/ribbit_hip.h)"""
-    p = PrimerPairParams()
-    load_library().ribbit_primer_pair_params_default(C.byref(p))
-    names = {n for n, _ in PrimerPairParams._fields_}
-    for name, value in fields.items():
-        if name not in names:
-            raise TypeError(f"RibbitPrimerPairParams has no field {name!r}")
-        if not -2**31 <= int(value) < 2**31:
-            raise ValueError(f"{name} {value} does not fit int32")
-        setattr(p, name, int(value))
-    return p
-
-
-def _primer_pair_args(intervals, targets, params, pair_params):
-    iv, tg, params = _primer_args(intervals, targets, params)
-    if pair_params is None:
-        pair_params = primer_pair_params()
-    if not isinstance(pair_params, PrimerPairParams):
-        raise TypeError("pair_params: a PrimerPairParams (primer_pair_params())")
-    return iv, tg, params, pair_params
+def _record_primer_pairs(call, intervals, targets, params, pair_params) -> np.ndarray:
+    iv, tg = _pairs(intervals), _pairs(targets)
+    params = _params_arg(params, primer_params, PrimerParams)
+    pair_params = _params_arg(pair_params, primer_pair_params, PrimerPairParams, "pair_params")
+    return _array(call, _ptr(iv), len(iv), _ptr(tg), len(tg), C.byref(params), C.byref(pair_params), dt=PRIMER_PAIRS_DT, free="ribbit_primer_pairs_free",
+                  count=len(tg))
 
 
 def host_record_primer_pairs(sequence: bytes, intervals, targets, params: PrimerParams | None = None, pair_params: PrimerPairParams | None = None) -> np.ndarray:
@@ -1066,61 +843,7 @@ def host_record_primer_pairs(sequence: bytes, intervals, targets, params: Primer
     candidates chosen as one pair: each oligo within the limits on self-dimers and hairpins, the two within the limits on
     cross-dimers and on their Tm difference, the pair with the least penalty -> a PRIMER_PAIRS_DT array, one record per target.
     The contract is in include/ribbit_hip.h.  No GPU needed."""
-    L = load_library()
-    iv, tg, params, pair_params = _primer_pair_args(intervals, targets, params, pair_params)
-    seq = bytes(sequence)
-    out = C.c_void_p()
-    rc = L.ribbit_host_record_primer_pairs(seq, len(seq), iv.ctypes.data if len(iv) else None, len(iv), tg.ctypes.data if len(tg) else None, len(tg),
-                                           C.byref(params), C.byref(pair_params), C.byref(out))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_host_record_primer_pairs error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return _copy(out.value, len(tg), PRIMER_PAIRS_DT)
-    finally:
-        L.ribbit_primer_pairs_free(out)
-
-
-def bed_primer_pairs_text(bed, rows) -> bytes:
-    """ribbit_bed_primer_pairs_text: the lines of `bed` (the targets' BED rows, target i on line i), each with the primer pair of
-    row i of `rows` (record_primer_pairs) appended as 21 more columns."""
-    L = load_library()
-    text_in = bed.encode() if isinstance(bed, str) else bytes(bed)
-    rw = np.ascontiguousarray(np.asarray(rows, dtype=PRIMER_PAIRS_DT).reshape(-1))
-    text, n = C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_bed_primer_pairs_text(text_in, len(text_in), rw.ctypes.data if len(rw) else None, len(rw), C.byref(text), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_bed_primer_pairs_text error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return C.string_at(text.value, n.value)
-    finally:
-        L.ribbit_text_free(text)
-
-
-def _oligo(text) -> bytes:
-    return text.encode() if isinstance(text, str) else bytes(text)
-
-
-def product_params(**fields) -> ProductParams:
-    """ribbit_product_params_default with the given fields replaced, e.g. product_params(seed=12, max_sites=256); the ranges are
-    checked by the calls that take it (include/ribbit_hip.h)"""
-    p = ProductParams()
-    load_library().ribbit_product_params_default(C.byref(p))
-    names = {n for n, _ in ProductParams._fields_}
-    for name, value in fields.items():
-        if name not in names:
-            raise TypeError(f"RibbitProductParams has no field {name!r}")
-        if not -2**31 <= int(value) < 2**31:
-            raise ValueError(f"{name} {value} does not fit int32")
-        setattr(p, name, int(value))
-    return p
-
-
-def _product_params(params) -> ProductParams:
-    if params is None:
-        params = product_params()
-    if not isinstance(params, ProductParams):
-        raise TypeError("params: a ProductParams (product_params())")
-    return params
+    return _record_primer_pairs(_host_bases("ribbit_host_record_primer_pairs", sequence), intervals, targets, params, pair_params)
 
 
 def _oligos(oligos) -> np.ndarray:
@@ -1128,7 +851,7 @@ def _oligos(oligos) -> np.ndarray:
     its length, for the call to refuse)"""
     out = np.zeros(len(oligos), dtype=_OLIGO_DT)
     for i, text in enumerate(oligos):
-        letters = _oligo(text).upper()
+        letters = _bytes(text).upper()
         if any(ch not in b"ACGT" for ch in letters):
             raise ValueError(f"oligo {i}: {letters!r} has letters other than ACGT")
         bases = sum(b"ACGT".index(ch) << (2 * j) for j, ch in enumerate(letters[:32]))
@@ -1136,9 +859,15 @@ def _oligos(oligos) -> np.ndarray:
     return out
 
 
-def _sites(sites_ptr, n, positions_ptr, n_positions):
+def _record_oligo_sites(call, oligos, params):
     """-> an OLIGO_SITES_DT array and the flat positions"""
-    return _copy(sites_ptr, n, OLIGO_SITES_DT), _copy(positions_ptr, n_positions, np.dtype("<i4"))
+    og, params = _oligos(oligos), _params_arg(params, product_params, ProductParams)
+    sites, positions, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
+    owned = _call(call, _ptr(og), len(og), C.byref(params), C.byref(sites), C.byref(positions), C.byref(n))
+    try:
+        return _copy(sites.value, len(og), OLIGO_SITES_DT), _copy(positions.value, n.value, _I4)
+    finally:
+        _free(owned, "ribbit_products_free", sites, positions)
 
 
 def host_record_oligo_sites(sequence: bytes, oligos, params: ProductParams | None = None):
@@ -1146,21 +875,12 @@ def host_record_oligo_sites(sequence: bytes, oligos, params: ProductParams | Non
     bases match exactly, at most max_mismatches of the others differ -> (an OLIGO_SITES_DT array, one record per oligo, and the
     int32 window starts of the kept lists one behind the other: list = positions[forward_at : forward_at + forward]; a list longer
     than max_sites has forward_at -1).  The contract is in include/ribbit_hip.h.  No GPU needed."""
-    L = load_library()
-    og, params, seq = _oligos(oligos), _product_params(params), bytes(sequence)
-    sites, positions, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_host_record_oligo_sites(seq, len(seq), og.ctypes.data if len(og) else None, len(og), C.byref(params), C.byref(sites), C.byref(positions), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_host_record_oligo_sites error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return _sites(sites.value, len(og), positions.value, n.value)
-    finally:
-        L.ribbit_products_free(sites)
-        L.ribbit_products_free(positions)
+    return _record_oligo_sites(_host_bases("ribbit_host_record_oligo_sites", sequence), oligos, params)
 
 
-def _pair_rows(pairs) -> np.ndarray:
-    return np.ascontiguousarray(np.asarray(pairs, dtype=PRIMER_PAIRS_DT).reshape(-1))
+def _record_primer_products(call, pairs, params) -> np.ndarray:
+    rw, params = _records(pairs, PRIMER_PAIRS_DT), _params_arg(params, product_params, ProductParams)
+    return _array(call, _ptr(rw), len(rw), C.byref(params), dt=PRIMER_PRODUCTS_DT, free="ribbit_products_free", count=len(rw))
 
 
 def host_record_primer_products(sequence: bytes, pairs, params: ProductParams | None = None) -> np.ndarray:
@@ -1168,119 +888,40 @@ def host_record_primer_products(sequence: bytes, pairs, params: ProductParams | 
     rows, or hand-made ones) on the record: the sites of both primers on both strands, the products between a forward and a reverse
     site of either, whether the pair's own product is among them and the shortest of the others -> a PRIMER_PRODUCTS_DT array.  A
     pair is specific in this record when products - own == 0.  The contract is in include/ribbit_hip.h.  No GPU needed."""
-    L = load_library()
-    rw, params, seq = _pair_rows(pairs), _product_params(params), bytes(sequence)
-    out = C.c_void_p()
-    rc = L.ribbit_host_record_primer_products(seq, len(seq), rw.ctypes.data if len(rw) else None, len(rw), C.byref(params), C.byref(out))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_host_record_primer_products error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return _copy(out.value, len(rw), PRIMER_PRODUCTS_DT)
-    finally:
-        L.ribbit_products_free(out)
+    return _record_primer_products(_host_bases("ribbit_host_record_primer_products", sequence), pairs, params)
 
 
-def bed_primer_products_text(bed, pairs, products) -> bytes:
-    """ribbit_bed_primer_products_text: the lines of bed_primer_pairs_text(bed, pairs), each with six more columns from row i of
-    `products` (record_primer_products): the four site counts, the products other than the pair's own and the shortest of them."""
-    L = load_library()
-    text_in = bed.encode() if isinstance(bed, str) else bytes(bed)
-    rw = _pair_rows(pairs)
-    pr = np.ascontiguousarray(np.asarray(products, dtype=PRIMER_PRODUCTS_DT).reshape(-1))
-    if len(pr) != len(rw):
-        raise ValueError(f"{len(rw)} pairs and {len(pr)} products")
-    text, n = C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_bed_primer_products_text(text_in, len(text_in), rw.ctypes.data if len(rw) else None, pr.ctypes.data if len(pr) else None, len(rw), C.byref(text), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_bed_primer_products_text error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return C.string_at(text.value, n.value)
-    finally:
-        L.ribbit_text_free(text)
-
-
-def oligo_duplex(a, b) -> tuple:
-    """ribbit_host_oligo_duplex: (any, end) of two oligos of 1 .. 32 letters of ACGT, each read 5' to 3': the longest run of
-    bonded pairs over all ungapped antiparallel placements, and the longest that holds a 3' base (include/ribbit_hip.h)"""
-    L = load_library()
-    any_, end = C.c_int32(), C.c_int32()
-    rc = L.ribbit_host_oligo_duplex(_oligo(a), _oligo(b), C.byref(any_), C.byref(end))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_host_oligo_duplex error {rc}: {L.ribbit_hip_last_error().decode()}")
-    return any_.value, end.value
-
-
-def oligo_hairpin(a) -> int:
-    """ribbit_host_oligo_hairpin: the longest stem an oligo closes on itself around a loop of 3 bases or more"""
-    L = load_library()
-    out = C.c_int32()
-    rc = L.ribbit_host_oligo_hairpin(_oligo(a), C.byref(out))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_host_oligo_hairpin error {rc}: {L.ribbit_hip_last_error().decode()}")
-    return out.value
+def _record_best(call, intervals):
+    iv, bases = _pairs(intervals), C.c_int64()
+    rows = _array(call, _ptr(iv), len(iv), dt=_I4, free="ribbit_intervals_free", tail=(C.byref(bases),))
+    return rows, int(bases.value)
 
 
 def host_record_best(length: int, intervals):
     """ribbit_host_record_best: the rows of a record of `length` bases of which no two overlap and which cover the most bases ->
     (their indices by ascending start, int32; the bases they cover).  The contract is in include/ribbit_hip.h.  No GPU needed."""
-    L = load_library()
-    iv = _pairs(intervals)
-    rows, n, bases = C.c_void_p(), C.c_size_t(), C.c_int64()
-    rc = L.ribbit_host_record_best(int(length), iv.ctypes.data if len(iv) else None, len(iv), C.byref(rows), C.byref(n), C.byref(bases))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_host_record_best error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return _copy(rows.value, n.value, np.dtype("<i4")), int(bases.value)
-    finally:
-        L.ribbit_intervals_free(rows)
-
-
-def bed_rows_text(bed, rows) -> bytes:
-    """ribbit_bed_rows_text: lines rows[0], rows[1], ... of `bed` (one record's BED text, row i on line i), byte for byte."""
-    L = load_library()
-    text_in = bed.encode() if isinstance(bed, str) else bytes(bed)
-    idx = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
-    text, n = C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_bed_rows_text(text_in, len(text_in), idx.ctypes.data if len(idx) else None, len(idx), C.byref(text), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_bed_rows_text error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return C.string_at(text.value, n.value)
-    finally:
-        L.ribbit_text_free(text)
-
-
-def bed_motifs(text):
-    """ribbit_bed_motifs: column 4 of every row of BED text as refine_bed writes it -> (the motifs concatenated, bytes; their
-    n + 1 offsets, int32)."""
-    L = load_library()
-    raw = text.encode() if isinstance(text, str) else bytes(text)
-    pool, offsets, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_bed_motifs(raw, len(raw), C.byref(pool), C.byref(offsets), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_bed_motifs error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        off = _copy(offsets.value, n.value + 1, np.dtype("<i4"))
-        return C.string_at(pool.value, int(off[-1])), off
-    finally:
-        L.ribbit_text_free(pool)
-        L.ribbit_intervals_free(offsets)
+    return _record_best(_host("ribbit_host_record_best", int(length)), intervals)
 
 
 def _class_args(intervals, motifs, offsets):
     """the rows, the motif pool and its offsets as the C ABI takes them; `motifs` may also be a list of strings (offsets None)"""
     iv = _pairs(intervals)
-    if offsets is None:
-        parts = [m.encode() if isinstance(m, str) else bytes(m) for m in motifs]
-        offsets = np.concatenate([[0], np.cumsum([len(m) for m in parts], dtype=np.int64)])
-        motifs = b"".join(parts)
-    pool = motifs.encode() if isinstance(motifs, str) else bytes(motifs)
-    off = np.asarray(offsets)
+    pool, off = _pool(motifs, offsets)
     if off.ndim != 1 or len(off) != len(iv) + 1:
         raise ValueError(f"{len(iv)} rows want {len(iv) + 1} offsets")
-    if len(off) and (off.min() < -(1 << 31) or off.max() >= (1 << 31)):
-        raise ValueError("an offset is not an int32")
+    _all_int32(off, "an offset is not an int32")
     return iv, pool, np.ascontiguousarray(off, dtype=np.int32)
+
+
+def _record_classes(call, intervals, motifs, offsets):
+    iv, pool, off = _class_args(intervals, motifs, offsets)
+    classes, strands, groups, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t()
+    owned = _call(call, _ptr(iv), len(iv), pool, off.ctypes.data, C.byref(classes), C.byref(strands), C.byref(groups), C.byref(n))
+    try:
+        return C.string_at(classes.value, int(off[-1])), C.string_at(strands.value, len(iv)), _copy(groups.value, n.value, MOTIF_CLASS_DT)
+    finally:
+        _free(owned, "ribbit_text_free", classes, strands)
+        _free(owned, "ribbit_motif_classes_free", groups)
 
 
 def host_record_classes(length: int, intervals, motifs, offsets=None):
@@ -1288,72 +929,23 @@ def host_record_classes(length: int, intervals, motifs, offsets=None):
     concatenated at the motifs' offsets, bytes; a strand byte per row, bytes; the groups in class order, a MOTIF_CLASS_DT array).
     motifs, offsets: as bed_motifs returns them, or a list of strings and None.  The contract is in include/ribbit_hip.h.  No
     GPU needed."""
-    L = load_library()
-    iv, pool, off = _class_args(intervals, motifs, offsets)
-    classes, strands, groups, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_host_record_classes(int(length), iv.ctypes.data if len(iv) else None, len(iv), pool, off.ctypes.data, C.byref(classes), C.byref(strands),
-                                      C.byref(groups), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_host_record_classes error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return C.string_at(classes.value, int(off[-1])), C.string_at(strands.value, len(iv)), _copy(groups.value, n.value, MOTIF_CLASS_DT)
-    finally:
-        L.ribbit_text_free(classes)
-        L.ribbit_text_free(strands)
-        L.ribbit_motif_classes_free(groups)
+    return _record_classes(_host("ribbit_host_record_classes", int(length)), intervals, motifs, offsets)
 
 
-def bed_class_text(bed, classes, offsets, strands) -> bytes:
-    """ribbit_bed_class_text: the lines of `bed` (one record's BED text, row i on line i), each with row i's class and strand
-    appended as two more columns."""
-    L = load_library()
-    text_in = bed.encode() if isinstance(bed, str) else bytes(bed)
-    cls, st = bytes(classes), bytes(strands)
-    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int32).reshape(-1))
-    if len(off) != len(st) + 1 or len(cls) < int(off[-1]):
-        raise ValueError(f"{len(st)} rows want {len(st) + 1} offsets into the classes")
-    text, n = C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_bed_class_text(text_in, len(text_in), cls, off.ctypes.data, st, len(st), C.byref(text), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_bed_class_text error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return C.string_at(text.value, n.value)
-    finally:
-        L.ribbit_text_free(text)
-
-
-def class_summary_text(name, intervals, classes, offsets, groups) -> bytes:
-    """ribbit_class_summary_text: one line per group of one record: name, class, length, rows, bases, start and end of the
-    group's longest row as `intervals` (the rows the groups were made from) has them."""
-    L = load_library()
-    raw = name.encode() if isinstance(name, str) else bytes(name)
-    if b"\0" in raw:
-        raise ValueError("a record name cannot hold a NUL byte")
-    iv, cls = _pairs(intervals), bytes(classes)
-    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int32).reshape(-1))
-    if len(off) != len(iv) + 1 or len(cls) < int(off[-1]):
-        raise ValueError(f"{len(iv)} rows want {len(iv) + 1} offsets into the classes")
-    gr = np.ascontiguousarray(np.asarray(groups, dtype=MOTIF_CLASS_DT).reshape(-1))
-    text, n = C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_class_summary_text(raw, iv.ctypes.data if len(iv) else None, len(iv), cls, off.ctypes.data, gr.ctypes.data if len(gr) else None, len(gr),
-                                     C.byref(text), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_class_summary_text error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return C.string_at(text.value, n.value)
-    finally:
-        L.ribbit_text_free(text)
-
-
-def _compound_args(intervals, labels, gap):
-    """the rows, their labels and the gap as the C ABI takes them"""
+def _record_compounds(call, intervals, labels, gap: int):
     iv, gap = _rows_arg(intervals, gap, "gap")
     lab = np.asarray(labels)
     if lab.ndim != 1 or len(lab) != len(iv):
         raise ValueError(f"{len(iv)} rows want {len(iv)} labels")
-    if len(lab) and (lab.min() < -(1 << 31) or lab.max() >= (1 << 31)):
-        raise ValueError("a label is not an int32")
-    return iv, np.ascontiguousarray(lab, dtype=np.int32), gap
+    _all_int32(lab, "a label is not an int32")
+    lab = np.ascontiguousarray(lab, dtype=np.int32)
+    chains, n, members, m = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t()
+    owned = _call(call, _ptr(iv), _ptr(lab), len(iv), gap, C.byref(chains), C.byref(n), C.byref(members), C.byref(m))
+    try:
+        return _copy(chains.value, n.value, COMPOUND_DT), _copy(members.value, m.value, _I4)
+    finally:
+        _free(owned, "ribbit_compounds_free", chains)
+        _free(owned, "ribbit_intervals_free", members)
 
 
 def host_record_compounds(length: int, intervals, labels, gap: int = 100):
@@ -1361,101 +953,32 @@ def host_record_compounds(length: int, intervals, labels, gap: int = 100):
     at most `gap` bases behind everything before it -> (the chains by ascending start, a COMPOUND_DT array; the non-empty rows'
     indices in (start, end, index) order, int32: chain c owns members[first : first + rows]).  The contract is in
     include/ribbit_hip.h.  No GPU needed."""
-    L = load_library()
-    iv, lab, gap = _compound_args(intervals, labels, gap)
-    chains, n, members, m = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_host_record_compounds(int(length), iv.ctypes.data if len(iv) else None, lab.ctypes.data if len(iv) else None, len(iv), gap,
-                                        C.byref(chains), C.byref(n), C.byref(members), C.byref(m))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_host_record_compounds error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return _copy(chains.value, n.value, COMPOUND_DT), _copy(members.value, m.value, np.dtype("<i4"))
-    finally:
-        L.ribbit_compounds_free(chains)
-        L.ribbit_intervals_free(members)
+    return _record_compounds(_host("ribbit_host_record_compounds", int(length)), intervals, labels, gap)
 
 
-def class_labels(classes, offsets, groups) -> np.ndarray:
-    """ribbit_class_labels: per row the index, in class order, of the group whose class is the row's, int32.  classes, offsets,
-    groups: what record_classes / host_record_classes return for the rows (offsets: the motifs')."""
-    L = load_library()
-    cls = bytes(classes)
-    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int32).reshape(-1))
-    if len(off) < 1 or len(cls) < int(off[-1]):
-        raise ValueError("n rows want n + 1 offsets into the classes")
-    gr = np.ascontiguousarray(np.asarray(groups, dtype=MOTIF_CLASS_DT).reshape(-1))
-    labels = C.c_void_p()
-    rc = L.ribbit_class_labels(cls, off.ctypes.data, len(off) - 1, gr.ctypes.data if len(gr) else None, len(gr), C.byref(labels))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_class_labels error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return _copy(labels.value, len(off) - 1, np.dtype("<i4"))
-    finally:
-        L.ribbit_intervals_free(labels)
-
-
-def compound_text(name, bed, length: int, intervals, compounds, members) -> bytes:
-    """ribbit_compound_text: one line per chain of one record: name, start, end, kind (p, i or c, with * when members overlap),
-    rows, classes, bases and the structure, e.g. (CA)12n5(GA)8, read from the members' lines of `bed` (row i on line i)."""
-    L = load_library()
-    raw = name.encode() if isinstance(name, str) else bytes(name)
-    if b"\0" in raw:
-        raise ValueError("a record name cannot hold a NUL byte")
-    text_in = bed.encode() if isinstance(bed, str) else bytes(bed)
+def _record_interruptions(call, intervals, motif_lengths, cigars, offsets):
     iv = _pairs(intervals)
-    ch = np.ascontiguousarray(np.asarray(compounds, dtype=COMPOUND_DT).reshape(-1))
-    mem = np.ascontiguousarray(np.asarray(members, dtype=np.int32).reshape(-1))
-    text, n = C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_compound_text(raw, text_in, len(text_in), int(length), iv.ctypes.data if len(iv) else None, len(iv), ch.ctypes.data if len(ch) else None,
-                                len(ch), mem.ctypes.data if len(mem) else None, len(mem), C.byref(text), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_compound_text error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return C.string_at(text.value, n.value)
-    finally:
-        L.ribbit_text_free(text)
-
-
-def bed_cigars(text):
-    """ribbit_bed_cigars: column 11 of every row of BED text as refine_bed writes it -> (the CIGARs concatenated, bytes; their
-    n + 1 offsets, int32)."""
-    L = load_library()
-    raw = text.encode() if isinstance(text, str) else bytes(text)
-    pool, offsets, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_bed_cigars(raw, len(raw), C.byref(pool), C.byref(offsets), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_bed_cigars error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        off = _copy(offsets.value, n.value + 1, np.dtype("<i4"))
-        return C.string_at(pool.value, int(off[-1])), off
-    finally:
-        L.ribbit_text_free(pool)
-        L.ribbit_intervals_free(offsets)
-
-
-def _interruption_args(intervals, motif_lengths, cigars, offsets):
-    """the rows, their motif lengths, the CIGAR pool and its offsets as the C ABI takes them; `cigars` may also be a list of
-    strings (offsets None)"""
-    iv = _pairs(intervals)
-    if offsets is None:
-        parts = [c.encode() if isinstance(c, str) else bytes(c) for c in cigars]
-        offsets = np.concatenate([[0], np.cumsum([len(c) for c in parts], dtype=np.int64)])
-        cigars = b"".join(parts)
-    pool = cigars.encode() if isinstance(cigars, str) else bytes(cigars)
-    off, k = np.asarray(offsets), np.asarray(motif_lengths)
+    pool, off = _pool(cigars, offsets)
+    k = np.asarray(motif_lengths)
     if off.ndim != 1 or len(off) != len(iv) + 1:
         raise ValueError(f"{len(iv)} rows want {len(iv) + 1} offsets")
     if k.ndim != 1 or len(k) != len(iv):
         raise ValueError(f"{len(iv)} rows want {len(iv)} motif lengths")
     for a in (off, k):
-        if len(a) and (a.min() < -(1 << 31) or a.max() >= (1 << 31)):
-            raise ValueError("an offset or a motif length is not an int32")
-    return iv, np.ascontiguousarray(k, dtype=np.int32), pool, np.ascontiguousarray(off, dtype=np.int32)
-
-
-def _interruption_result(rows, n, sites, m, observed, offsets):
-    off = _copy(offsets, m + 1, np.dtype("<i4")) if m else np.zeros(1, np.int32)
-    return _copy(rows, n, ROW_PURITY_DT), _copy(sites, m, INTERRUPTION_DT), C.string_at(observed, int(off[-1])) if m else b"", off
+        _all_int32(a, "an offset or a motif length is not an int32")
+    k, off = np.ascontiguousarray(k, dtype=np.int32), np.ascontiguousarray(off, dtype=np.int32)
+    rows, sites, m, observed, offsets_out = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_void_p()
+    owned = _call(call, _ptr(iv), _ptr(k), len(iv), pool, off.ctypes.data, C.byref(rows), C.byref(sites), C.byref(m), C.byref(observed),
+                  C.byref(offsets_out))
+    try:
+        seen = _copy(offsets_out.value, m.value + 1, _I4) if m.value else np.zeros(1, np.int32)
+        return (_copy(rows.value, len(iv), ROW_PURITY_DT), _copy(sites.value, m.value, INTERRUPTION_DT),
+                C.string_at(observed.value, int(seen[-1])) if m.value else b"", seen)
+    finally:
+        _free(owned, "ribbit_row_purity_free", rows)
+        _free(owned, "ribbit_interruptions_free", sites)
+        _free(owned, "ribbit_text_free", observed)
+        _free(owned, "ribbit_intervals_free", offsets_out)
 
 
 def host_record_interruptions(sequence: bytes, intervals, motif_lengths, cigars, offsets=None):
@@ -1463,89 +986,223 @@ def host_record_interruptions(sequence: bytes, intervals, motif_lengths, cigars,
     then in CIGAR order, an INTERRUPTION_DT array; their observed bases concatenated, bytes; the n_sites + 1 offsets of those,
     int32).  cigars, offsets: as bed_cigars returns them, or a list of strings and None.  The contract is in
     include/ribbit_hip.h.  No GPU needed."""
-    L = load_library()
-    iv, k, pool, off = _interruption_args(intervals, motif_lengths, cigars, offsets)
-    seq = bytes(sequence)
-    rows, sites, m, observed, offsets_out = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_void_p()
-    rc = L.ribbit_host_record_interruptions(seq, len(seq), iv.ctypes.data if len(iv) else None, k.ctypes.data if len(iv) else None, len(iv), pool, off.ctypes.data,
-                                            C.byref(rows), C.byref(sites), C.byref(m), C.byref(observed), C.byref(offsets_out))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_host_record_interruptions error {rc}: {L.ribbit_hip_last_error().decode()}")
+    return _record_interruptions(_host_bases("ribbit_host_record_interruptions", sequence), intervals, motif_lengths, cigars, offsets)
+
+
+# BED text: readers and writers ----------------------------------------------------------------
+def bed_intervals(text) -> np.ndarray:
+    """ribbit_bed_intervals: (start, end) of every row of BED text as refine_bed writes it, an (n, 2) int32 array."""
+    raw = _bytes(text)
+    pairs, n = C.c_void_p(), C.c_size_t()
+    _call("ribbit_bed_intervals", raw, len(raw), C.byref(pairs), C.byref(n))
     try:
-        return _interruption_result(rows.value, len(iv), sites.value, m.value, observed.value, offsets_out.value)
+        return _copy(pairs.value, 2 * n.value, _I4).reshape(-1, 2)
     finally:
-        L.ribbit_row_purity_free(rows)
-        L.ribbit_interruptions_free(sites)
-        L.ribbit_text_free(observed)
-        L.ribbit_intervals_free(offsets_out)
+        _free(True, "ribbit_intervals_free", pairs)
+
+
+def _bed_column(symbol: str, text):
+    """-> (a column of every row of BED text concatenated, bytes; the n + 1 offsets, int32)"""
+    raw = _bytes(text)
+    pool, offsets, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
+    _call(symbol, raw, len(raw), C.byref(pool), C.byref(offsets), C.byref(n))
+    try:
+        off = _copy(offsets.value, n.value + 1, _I4)
+        return C.string_at(pool.value, int(off[-1])), off
+    finally:
+        _free(True, "ribbit_text_free", pool)
+        _free(True, "ribbit_intervals_free", offsets)
+
+
+def bed_motifs(text):
+    """ribbit_bed_motifs: column 4 of every row of BED text as refine_bed writes it -> (the motifs concatenated, bytes; their
+    n + 1 offsets, int32)."""
+    return _bed_column("ribbit_bed_motifs", text)
+
+
+def bed_cigars(text):
+    """ribbit_bed_cigars: column 11 of every row of BED text as refine_bed writes it -> (the CIGARs concatenated, bytes; their
+    n + 1 offsets, int32)."""
+    return _bed_column("ribbit_bed_cigars", text)
+
+
+def _bed_rows_text(symbol: str, bed, rows, dt) -> bytes:
+    """a writer that takes BED text and one array with a record per row (dt None: pairs of int32)"""
+    text_in = _bytes(bed)
+    rw = _pairs(rows) if dt is None else _records(rows, dt)
+    return _text(symbol, text_in, len(text_in), _ptr(rw), len(rw))
+
+
+def bed_loci_text(name, bed, loci) -> bytes:
+    """ribbit_bed_loci_text: one line per locus of one record: name, start, end, rows, covered and the last ten columns of the
+    locus's best row of `bed` (the record's BED text, row i on line i)."""
+    raw, text_in, lo = _name(name), _bytes(bed), _records(loci, LOCUS_DT)
+    return _text("ribbit_bed_loci_text", raw, text_in, len(text_in), _ptr(lo), len(lo))
+
+
+def bed_overlap_text(bed, per_row) -> bytes:
+    """ribbit_bed_overlap_text: the lines of `bed` (one record's BED text, row i on line i), each with row i's two values of
+    `per_row` appended as two more columns."""
+    return _bed_rows_text("ribbit_bed_overlap_text", bed, per_row, None)
+
+
+def bed_nearest_text(bed, nearest, targets, labels, label_offsets=None) -> bytes:
+    """ribbit_bed_nearest_text: the lines of `bed` (one record's BED text, row i on line i), each with eight more columns: what
+    `nearest` (record_nearest with the rows as queries) names among `targets`.  labels, label_offsets: a pool and its offsets, or
+    a list of strings and None."""
+    text_in, near = _bytes(bed), _records(nearest, NEAREST_DT)
+    iv, pool, off = _class_args(targets, labels, label_offsets)
+    return _text("ribbit_bed_nearest_text", text_in, len(text_in), _ptr(near), len(near), _ptr(iv), pool, off.ctypes.data, len(iv))
+
+
+def nearest_other_text(name, targets, labels, nearest, rows, motifs, label_offsets=None, motif_offsets=None) -> bytes:
+    """ribbit_nearest_other_text: one line per interval of `targets` (a second BED's intervals on one record, with their labels): name,
+    start, end, label and the eight columns of what `nearest` (record_nearest with the intervals as queries) names among the
+    record's `rows`, a row's label being its motif.  Pools with offsets, or lists of strings and None."""
+    raw = _name(name)
+    iv, pool, off = _class_args(targets, labels, label_offsets)
+    rw, motif_pool, motif_off = _class_args(rows, motifs, motif_offsets)
+    near = _records(nearest, NEAREST_DT)
+    if len(near) != len(iv):
+        raise ValueError(f"{len(iv)} intervals want {len(iv)} nearest records, not {len(near)}")
+    return _text("ribbit_nearest_other_text", raw, _ptr(iv), pool, off.ctypes.data, len(iv), _ptr(near), _ptr(rw), motif_pool, motif_off.ctypes.data,
+                 len(rw))
+
+
+def bed_composition_text(bed, rows) -> bytes:
+    """ribbit_bed_composition_text: the lines of `bed` (one record's BED text, row i on line i), each with the 13 values of row i of
+    `rows` (record_composition) appended as 13 more columns."""
+    return _bed_rows_text("ribbit_bed_composition_text", bed, rows, COMPOSITION_DT)
+
+
+def base_windows_text(name, length: int, window: int, windows) -> bytes:
+    """ribbit_base_windows_text: one line per window of a record of `length` bases: name, start, end and the five counts of
+    `windows` (record_base_windows)."""
+    raw, window, w = _name(name), _int32(window, "window"), _records(windows, BASE_COUNTS_DT)
+    return _text("ribbit_base_windows_text", raw, int(length), window, _ptr(w), len(w))
+
+
+def bed_primers_text(bed, rows) -> bytes:
+    """ribbit_bed_primers_text: the lines of `bed` (the targets' BED rows, target i on line i), each with the primers of row i of
+    `rows` (record_primers) appended as 11 more columns."""
+    return _bed_rows_text("ribbit_bed_primers_text", bed, rows, PRIMERS_DT)
+
+
+def bed_primer_pairs_text(bed, rows) -> bytes:
+    """ribbit_bed_primer_pairs_text: the lines of `bed` (the targets' BED rows, target i on line i), each with the primer pair of
+    row i of `rows` (record_primer_pairs) appended as 21 more columns."""
+    return _bed_rows_text("ribbit_bed_primer_pairs_text", bed, rows, PRIMER_PAIRS_DT)
+
+
+def bed_primer_products_text(bed, pairs, products) -> bytes:
+    """ribbit_bed_primer_products_text: the lines of bed_primer_pairs_text(bed, pairs), each with six more columns from row i of
+    `products` (record_primer_products): the four site counts, the products other than the pair's own and the shortest of them."""
+    text_in, rw, pr = _bytes(bed), _records(pairs, PRIMER_PAIRS_DT), _records(products, PRIMER_PRODUCTS_DT)
+    if len(pr) != len(rw):
+        raise ValueError(f"{len(rw)} pairs and {len(pr)} products")
+    return _text("ribbit_bed_primer_products_text", text_in, len(text_in), _ptr(rw), _ptr(pr), len(rw))
+
+
+def oligo_duplex(a, b) -> tuple:
+    """ribbit_host_oligo_duplex: (any, end) of two oligos of 1 .. 32 letters of ACGT, each read 5' to 3': the longest run of
+    bonded pairs over all ungapped antiparallel placements, and the longest that holds a 3' base (include/ribbit_hip.h)"""
+    any_, end = C.c_int32(), C.c_int32()
+    _call("ribbit_host_oligo_duplex", _bytes(a), _bytes(b), C.byref(any_), C.byref(end))
+    return any_.value, end.value
+
+
+def oligo_hairpin(a) -> int:
+    """ribbit_host_oligo_hairpin: the longest stem an oligo closes on itself around a loop of 3 bases or more"""
+    out = C.c_int32()
+    _call("ribbit_host_oligo_hairpin", _bytes(a), C.byref(out))
+    return out.value
+
+
+def bed_rows_text(bed, rows) -> bytes:
+    """ribbit_bed_rows_text: lines rows[0], rows[1], ... of `bed` (one record's BED text, row i on line i), byte for byte."""
+    return _bed_rows_text("ribbit_bed_rows_text", bed, rows, np.int32)
+
+
+def _class_offsets(classes, offsets, rows: int | None):
+    """the rows' classes and the offsets into them, as record_classes returns them"""
+    cls, off = bytes(classes), _records(offsets, np.int32)
+    if rows is None and (len(off) < 1 or len(cls) < int(off[-1])):
+        raise ValueError("n rows want n + 1 offsets into the classes")
+    if rows is not None and (len(off) != rows + 1 or len(cls) < int(off[-1])):
+        raise ValueError(f"{rows} rows want {rows + 1} offsets into the classes")
+    return cls, off
+
+
+def bed_class_text(bed, classes, offsets, strands) -> bytes:
+    """ribbit_bed_class_text: the lines of `bed` (one record's BED text, row i on line i), each with row i's class and strand
+    appended as two more columns."""
+    text_in, st = _bytes(bed), bytes(strands)
+    cls, off = _class_offsets(classes, offsets, len(st))
+    return _text("ribbit_bed_class_text", text_in, len(text_in), cls, off.ctypes.data, st, len(st))
+
+
+def class_summary_text(name, intervals, classes, offsets, groups) -> bytes:
+    """ribbit_class_summary_text: one line per group of one record: name, class, length, rows, bases, start and end of the
+    group's longest row as `intervals` (the rows the groups were made from) has them."""
+    raw, iv = _name(name), _pairs(intervals)
+    cls, off = _class_offsets(classes, offsets, len(iv))
+    gr = _records(groups, MOTIF_CLASS_DT)
+    return _text("ribbit_class_summary_text", raw, _ptr(iv), len(iv), cls, off.ctypes.data, _ptr(gr), len(gr))
+
+
+def class_labels(classes, offsets, groups) -> np.ndarray:
+    """ribbit_class_labels: per row the index, in class order, of the group whose class is the row's, int32.  classes, offsets,
+    groups: what record_classes / host_record_classes return for the rows (offsets: the motifs')."""
+    cls, off = _class_offsets(classes, offsets, None)
+    gr = _records(groups, MOTIF_CLASS_DT)
+    return _array("ribbit_class_labels", cls, off.ctypes.data, len(off) - 1, _ptr(gr), len(gr), dt=_I4, free="ribbit_intervals_free", count=len(off) - 1)
+
+
+def compound_text(name, bed, length: int, intervals, compounds, members) -> bytes:
+    """ribbit_compound_text: one line per chain of one record: name, start, end, kind (p, i or c, with * when members overlap),
+    rows, classes, bases and the structure, e.g. (CA)12n5(GA)8, read from the members' lines of `bed` (row i on line i)."""
+    raw, text_in, iv = _name(name), _bytes(bed), _pairs(intervals)
+    ch, mem = _records(compounds, COMPOUND_DT), _records(members, np.int32)
+    return _text("ribbit_compound_text", raw, text_in, len(text_in), int(length), _ptr(iv), len(iv), _ptr(ch), len(ch), _ptr(mem), len(mem))
 
 
 def interruption_text(name, bed, intervals, rows, sites, cigars, observed, observed_offsets):
     """ribbit_interruption_text: one line per interruption of every consistent row of one record -> (the text: name, start, end,
     the interruption's ops, the observed bases or '.', the row's start and end, its motif and the 0-based repeat unit the site
     falls in; the number of inconsistent rows, whose interruptions are left out).  cigars: the pool the sites point into."""
-    L = load_library()
-    raw = name.encode() if isinstance(name, str) else bytes(name)
-    pool = cigars.encode() if isinstance(cigars, str) else bytes(cigars)
+    raw, pool = _bytes(name), _bytes(cigars)
     if b"\0" in raw or b"\0" in pool:
         raise ValueError("a record name or a CIGAR pool cannot hold a NUL byte")
-    text_in = bed.encode() if isinstance(bed, str) else bytes(bed)
-    iv = _pairs(intervals)
-    per_row = np.ascontiguousarray(np.asarray(rows, dtype=ROW_PURITY_DT).reshape(-1))
-    st = np.ascontiguousarray(np.asarray(sites, dtype=INTERRUPTION_DT).reshape(-1))
-    off = np.ascontiguousarray(np.asarray(observed_offsets, dtype=np.int32).reshape(-1))
+    text_in, iv = _bytes(bed), _pairs(intervals)
+    per_row, st, off = _records(rows, ROW_PURITY_DT), _records(sites, INTERRUPTION_DT), _records(observed_offsets, np.int32)
     if len(per_row) != len(iv) or len(off) != len(st) + 1:
         raise ValueError(f"{len(iv)} rows want {len(iv)} records, {len(st)} interruptions {len(st) + 1} offsets")
     obs = bytes(observed)
     if len(off) and len(obs) < int(off.max()):
         raise ValueError("the offsets reach behind the observed bases")
-    text, n, left = C.c_void_p(), C.c_size_t(), C.c_size_t()
-    rc = L.ribbit_interruption_text(raw, text_in, len(text_in), iv.ctypes.data if len(iv) else None, len(iv), per_row.ctypes.data if len(iv) else None,
-                                    st.ctypes.data if len(st) else None, len(st), pool, obs, off.ctypes.data, C.byref(text), C.byref(n), C.byref(left))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_interruption_text error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return C.string_at(text.value, n.value), left.value
-    finally:
-        L.ribbit_text_free(text)
+    left = C.c_size_t()
+    text = _text("ribbit_interruption_text", raw, text_in, len(text_in), _ptr(iv), len(iv), _ptr(per_row), _ptr(st), len(st), pool, obs, off.ctypes.data,
+                 tail=(C.byref(left),))
+    return text, left.value
 
 
 def bed_purity_text(bed, intervals, motif_lengths, rows) -> bytes:
     """ribbit_bed_purity_text: the lines of `bed` (one record's BED text, row i on line i), each with seven more columns: count,
     x, ins, del, pure_start, pure_end and pure_units (the last three '.' for a row whose CIGAR does not span it)."""
-    L = load_library()
-    text_in = bed.encode() if isinstance(bed, str) else bytes(bed)
-    iv = _pairs(intervals)
-    k = np.ascontiguousarray(np.asarray(motif_lengths, dtype=np.int32).reshape(-1))
-    per_row = np.ascontiguousarray(np.asarray(rows, dtype=ROW_PURITY_DT).reshape(-1))
+    text_in, iv = _bytes(bed), _pairs(intervals)
+    k, per_row = _records(motif_lengths, np.int32), _records(rows, ROW_PURITY_DT)
     if len(k) != len(iv) or len(per_row) != len(iv):
         raise ValueError(f"{len(iv)} rows want {len(iv)} motif lengths and records")
-    text, n = C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_bed_purity_text(text_in, len(text_in), iv.ctypes.data if len(iv) else None, k.ctypes.data if len(iv) else None,
-                                  per_row.ctypes.data if len(iv) else None, len(iv), C.byref(text), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_bed_purity_text error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return C.string_at(text.value, n.value)
-    finally:
-        L.ribbit_text_free(text)
+    return _text("ribbit_bed_purity_text", text_in, len(text_in), _ptr(iv), _ptr(k), _ptr(per_row), len(iv))
 
 
 def host_perfect_runs_from_events(min_motif: int, max_motif: int, event_parts, count_parts):
     """ribbit_host_perfect_runs_from_events: per-rank (events, per-motif counts) -> paired runs. No GPU needed."""
-    L = load_library()
-    params = ScanParams()
-    L.ribbit_scan_params_default(C.byref(params), min_motif, max_motif)
+    params = _scan_params(min_motif, max_motif)
     ev = np.ascontiguousarray(np.concatenate(event_parts) if len(event_parts) else np.zeros(0, "<u8"), dtype="<u8")
     cnt = np.ascontiguousarray(np.concatenate(count_parts), dtype="<u8")
-    runs, n = C.c_void_p(), C.c_size_t()
-    rc = L.ribbit_host_perfect_runs_from_events(C.byref(params), len(event_parts), ev.ctypes.data, cnt.ctypes.data, C.byref(runs), C.byref(n))
-    if rc != 0:
-        raise RibbitHipError(f"ribbit_host_perfect_runs_from_events error {rc}: {L.ribbit_hip_last_error().decode()}")
-    try:
-        return _copy(runs.value, n.value, RUN_DT)
-    finally:
-        L.ribbit_runs_free(runs)
+    return _array("ribbit_host_perfect_runs_from_events", C.byref(params), len(event_parts), ev.ctypes.data, cnt.ctypes.data, dt=RUN_DT,
+                  free="ribbit_runs_free")
 
 
 def pair_halves(halves) -> np.ndarray:
@@ -1625,9 +1282,7 @@ class PinnedBuffer:
     def __init__(self, nbytes: int):
         self._L = load_library()
         p = C.c_void_p()
-        rc = self._L.ribbit_hip_host_alloc(max(int(nbytes), 1), C.byref(p))
-        if rc != 0:
-            raise RibbitHipError(f"ribbit_hip_host_alloc error {rc}: {self._L.ribbit_hip_last_error().decode()}")
+        _ok("ribbit_hip_host_alloc", self._L.ribbit_hip_host_alloc(max(int(nbytes), 1), C.byref(p)))
         self.ptr = p.value
         self.nbytes = int(nbytes)
         self.array = np.frombuffer((C.c_char * max(self.nbytes, 1)).from_address(self.ptr), dtype=np.uint8)[:self.nbytes]
@@ -1665,8 +1320,15 @@ class Scanner:
         self.max_shift = max_motif + 2                              # ribbit.cpp:242
 
     def _check(self, rc):
-        if rc != 0:
-            raise RibbitHipError(f"ribbit_hip error {rc}: {self._L.ribbit_hip_last_error().decode()}")
+        if rc != 0:          # (tested here as well: the scan and chunk methods pay no second Python call for a status of 0)
+            _ok("ribbit_hip", rc)
+
+    def _dev(self, symbol: str) -> tuple:
+        """the device form of a row output's call (see _host): the results are the handle's and are not freed"""
+        return symbol, (self._h,), "ribbit_hip", False
+
+    def _refine_params(self, refine_params) -> RefineParams:
+        return _refine_params(refine_params, self.params.min_motif, self.params.max_motif)
 
     def close(self):
         if self._h is not None:
@@ -1799,25 +1461,17 @@ class Scanner:
 
     # parse_seed.cpp:26-44 (batched on the GPU), parse_smallmotif_seed.cpp:76-270, parse_seed.cpp:153-404 ----
     def seed_longest_runs(self):
-        p, n = C.c_void_p(), C.c_size_t()
-        self._check(self._L.ribbit_hip_seed_longest_runs(self._h, C.byref(p), C.byref(n)))
-        return _copy(p.value, n.value, np.dtype("<i4"))
+        return self._list(self._L.ribbit_hip_seed_longest_runs, _I4)
 
     def seed_best_rows(self, refine_params=None):
         """ribbit_hip_seed_best_rows: per dispatched seed the window start mostFrequentLongerMotif selects (GPU), -1 where it is not asked"""
-        rp = refine_params
-        if rp is None:
-            rp = RefineParams()
-            self._L.ribbit_refine_params_default(C.byref(rp), self.params.min_motif, self.params.max_motif)
+        rp = self._refine_params(refine_params)
         p, n = C.c_void_p(), C.c_size_t()
         self._check(self._L.ribbit_hip_seed_best_rows(self._h, C.byref(rp), C.byref(p), C.byref(n)))
-        return _copy(p.value, n.value, np.dtype("<i4"))
+        return _copy(p.value, n.value, _I4)
 
     def refine_jobs(self, refine_params=None):
-        rp = refine_params
-        if rp is None:
-            rp = RefineParams()
-            self._L.ribbit_refine_params_default(C.byref(rp), self.params.min_motif, self.params.max_motif)
+        rp = self._refine_params(refine_params)
         jobs, n, pool = C.c_void_p(), C.c_size_t(), C.c_void_p()
         self._check(self._L.ribbit_hip_refine_jobs(self._h, C.byref(rp), C.byref(jobs), C.byref(n), C.byref(pool)))
         arr = _copy(jobs.value, n.value, JOB_DT)
@@ -1827,44 +1481,34 @@ class Scanner:
     def small_motifs(self, refine_params=None):
         """ribbit_hip_small_motifs: (head [n_seeds, 4] int32, records [n_records, 4] uint32) -- possibleMotifs of the
         dispatched seeds with m <= 10 as the GPU computed it"""
-        rp = refine_params
-        if rp is None:
-            rp = RefineParams()
-            self._L.ribbit_refine_params_default(C.byref(rp), self.params.min_motif, self.params.max_motif)
+        rp = self._refine_params(refine_params)
         head, n, rec, nr = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t()
         self._check(self._L.ribbit_hip_small_motifs(self._h, C.byref(rp), C.byref(head), C.byref(n), C.byref(rec), C.byref(nr)))
-        return _copy(head.value, 4 * n.value, np.dtype("<i4")).reshape(-1, 4), _copy(rec.value, 4 * nr.value, np.dtype("<u4")).reshape(-1, 4)
+        return _copy(head.value, 4 * n.value, _I4).reshape(-1, 4), _copy(rec.value, 4 * nr.value, np.dtype("<u4")).reshape(-1, 4)
+
+    def _refine_bed(self, sequence_id: str, refine_params):
+        """-> (address, length) of the handle's BED text"""
+        rp = self._refine_params(refine_params)
+        text, n = C.c_void_p(), C.c_size_t()
+        self._check(self._L.ribbit_hip_refine_bed(self._h, C.byref(rp), sequence_id.encode(), C.byref(text), C.byref(n)))
+        return text.value, n.value
 
     def refine_bed(self, sequence_id: str = "seq", refine_params=None) -> str:
         """BED rows of the loaded record (fasta_utils.cpp:211-242 and everything below it)"""
-        rp = refine_params
-        if rp is None:
-            rp = RefineParams()
-            self._L.ribbit_refine_params_default(C.byref(rp), self.params.min_motif, self.params.max_motif)
-        text, n = C.c_void_p(), C.c_size_t()
-        self._check(self._L.ribbit_hip_refine_bed(self._h, C.byref(rp), sequence_id.encode(), C.byref(text), C.byref(n)))
-        return C.string_at(text.value, n.value).decode()
+        return C.string_at(*self._refine_bed(sequence_id, refine_params)).decode()
 
     def refine_bed_view(self, sequence_id: str = "seq", refine_params=None) -> np.ndarray:
         """The same BED text as the C ABI hands it out: a uint8 view of the library's buffer (valid until the handle's next
         refine_bed call or its close), without the copy and the decoding into a Python string that refine_bed adds -- 150 MB
         twice over for a chromosome, which a C caller (ribbit-hip writes the buffer straight to its output file) never pays."""
-        rp = refine_params
-        if rp is None:
-            rp = RefineParams()
-            self._L.ribbit_refine_params_default(C.byref(rp), self.params.min_motif, self.params.max_motif)
-        text, n = C.c_void_p(), C.c_size_t()
-        self._check(self._L.ribbit_hip_refine_bed(self._h, C.byref(rp), sequence_id.encode(), C.byref(text), C.byref(n)))
-        if not n.value:
+        text, n = self._refine_bed(sequence_id, refine_params)
+        if not n:
             return np.zeros(0, dtype=np.uint8)
-        return np.ctypeslib.as_array(C.cast(text.value, C.POINTER(C.c_uint8)), shape=(n.value,))
+        return np.ctypeslib.as_array(C.cast(text, C.POINTER(C.c_uint8)), shape=(n,))
 
     def mask_record(self, intervals, mode: str = "soft", line_width: int = 60) -> bytes:
         """The loaded record's masked, line-wrapped FASTA body on the GPU (ribbit_hip_mask_record); see host_mask_record"""
-        iv, m, w = _mask_args(intervals, mode, line_width)
-        text, n = C.c_void_p(), C.c_size_t()
-        self._check(self._L.ribbit_hip_mask_record(self._h, iv.ctypes.data if len(iv) else None, len(iv), m, w, C.byref(text), C.byref(n)))
-        return C.string_at(text.value, n.value) if n.value else b""
+        return _mask_record(self._dev("ribbit_hip_mask_record"), intervals, mode, line_width)
 
     def repeat_sequences(self, name, intervals, flank: int = 100) -> bytes:
         """The loaded record's repeat sequences with their flanks on the GPU (ribbit_hip_repeat_sequences), every batch of the
@@ -1887,113 +1531,64 @@ class Scanner:
 
     def record_loci(self, intervals, gap: int = 0) -> np.ndarray:
         """The loaded record's rows merged into loci on the GPU (ribbit_hip_record_loci); see host_record_loci"""
-        iv, gap = _rows_arg(intervals, gap, "gap")
-        loci, n = C.c_void_p(), C.c_size_t()
-        self._check(self._L.ribbit_hip_record_loci(self._h, iv.ctypes.data if len(iv) else None, len(iv), gap, C.byref(loci), C.byref(n)))
-        return _copy(loci.value, n.value, LOCUS_DT)
+        return _record_loci(self._dev("ribbit_hip_record_loci"), intervals, gap)
 
     def record_overlap(self, rows, other):
         """The loaded record's rows against the intervals `other` on the GPU (ribbit_hip_record_overlap); see host_record_overlap"""
-        iv, ot = _pairs(rows), _pairs(other)
-        per_row, totals = C.c_void_p(), OverlapTotals()
-        self._check(self._L.ribbit_hip_record_overlap(self._h, iv.ctypes.data if len(iv) else None, len(iv), ot.ctypes.data if len(ot) else None, len(ot),
-                                                      C.byref(per_row), C.byref(totals)))
-        return _copy(per_row.value, 2 * len(iv), np.dtype("<i4")).reshape(-1, 2), totals.as_dict()
+        return _record_overlap(self._dev("ribbit_hip_record_overlap"), rows, other)
 
     def record_nearest(self, queries, targets) -> np.ndarray:
         """The loaded record's queries against `targets` on the GPU (ribbit_hip_record_nearest); see host_record_nearest"""
-        q, t = _pairs(queries), _pairs(targets)
-        out = C.c_void_p()
-        self._check(self._L.ribbit_hip_record_nearest(self._h, q.ctypes.data if len(q) else None, len(q), t.ctypes.data if len(t) else None, len(t), C.byref(out)))
-        return _copy(out.value, len(q), NEAREST_DT)
+        return _record_nearest(self._dev("ribbit_hip_record_nearest"), queries, targets)
 
     def record_composition(self, intervals, flank: int = 100) -> np.ndarray:
         """The loaded record's rows' and flanks' base counts on the GPU (ribbit_hip_record_composition); see host_record_composition"""
-        iv, flank = _rows_arg(intervals, flank, "flank")
-        out = C.c_void_p()
-        self._check(self._L.ribbit_hip_record_composition(self._h, iv.ctypes.data if len(iv) else None, len(iv), flank, C.byref(out)))
-        return _copy(out.value, len(iv), COMPOSITION_DT)
+        return _record_composition(self._dev("ribbit_hip_record_composition"), intervals, flank)
 
     def record_base_windows(self, window: int) -> np.ndarray:
         """The loaded record's base counts per window on the GPU (ribbit_hip_record_base_windows); see host_record_base_windows"""
-        _, window = _rows_arg((), window, "window")
-        out, n = C.c_void_p(), C.c_size_t()
-        self._check(self._L.ribbit_hip_record_base_windows(self._h, window, C.byref(out), C.byref(n)))
-        return _copy(out.value, n.value, BASE_COUNTS_DT)
+        return _record_base_windows(self._dev("ribbit_hip_record_base_windows"), window)
 
     def record_primers(self, intervals, targets, params: PrimerParams | None = None) -> np.ndarray:
         """A forward and a reverse primer in the flanks of every target of the loaded record on the GPU, clear of the rows
         `intervals` (ribbit_hip_record_primers); see host_record_primers"""
-        iv, tg, params = _primer_args(intervals, targets, params)
-        out = C.c_void_p()
-        self._check(self._L.ribbit_hip_record_primers(self._h, iv.ctypes.data if len(iv) else None, len(iv), tg.ctypes.data if len(tg) else None, len(tg),
-                                                      C.byref(params), C.byref(out)))
-        return _copy(out.value, len(tg), PRIMERS_DT)
+        return _record_primers(self._dev("ribbit_hip_record_primers"), intervals, targets, params)
 
     def record_primer_pairs(self, intervals, targets, params: PrimerParams | None = None, pair_params: PrimerPairParams | None = None) -> np.ndarray:
         """The two primers of every target of the loaded record chosen as a pair on the GPU, checked for dimers and hairpins
         (ribbit_hip_record_primer_pairs); see host_record_primer_pairs"""
-        iv, tg, params, pair_params = _primer_pair_args(intervals, targets, params, pair_params)
-        out = C.c_void_p()
-        self._check(self._L.ribbit_hip_record_primer_pairs(self._h, iv.ctypes.data if len(iv) else None, len(iv), tg.ctypes.data if len(tg) else None, len(tg),
-                                                           C.byref(params), C.byref(pair_params), C.byref(out)))
-        return _copy(out.value, len(tg), PRIMER_PAIRS_DT)
+        return _record_primer_pairs(self._dev("ribbit_hip_record_primer_pairs"), intervals, targets, params, pair_params)
 
     def record_oligo_sites(self, oligos, params: ProductParams | None = None):
         """Where every oligo (text, 5' to 3') primes on either strand of the loaded record, on the GPU: equal oligos are searched
         once, the record's bit planes are read once (ribbit_hip_record_oligo_sites); see host_record_oligo_sites.  Counts add up
         over records: for a genome, load each record in turn and sum."""
-        og, params = _oligos(oligos), _product_params(params)
-        sites, positions, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
-        self._check(self._L.ribbit_hip_record_oligo_sites(self._h, og.ctypes.data if len(og) else None, len(og), C.byref(params), C.byref(sites), C.byref(positions),
-                                                          C.byref(n)))
-        return _sites(sites.value, len(og), positions.value, n.value)
+        return _record_oligo_sites(self._dev("ribbit_hip_record_oligo_sites"), oligos, params)
 
     def record_primer_products(self, pairs, params: ProductParams | None = None) -> np.ndarray:
         """An in-silico PCR of every primer pair on the loaded record, on the GPU (ribbit_hip_record_primer_products); see
         host_record_primer_products"""
-        rw, params = _pair_rows(pairs), _product_params(params)
-        out = C.c_void_p()
-        self._check(self._L.ribbit_hip_record_primer_products(self._h, rw.ctypes.data if len(rw) else None, len(rw), C.byref(params), C.byref(out)))
-        return _copy(out.value, len(rw), PRIMER_PRODUCTS_DT)
+        return _record_primer_products(self._dev("ribbit_hip_record_primer_products"), pairs, params)
 
     def record_best(self, intervals):
         """The loaded record's best non-overlapping rows on the GPU (ribbit_hip_record_best); see host_record_best"""
-        iv = _pairs(intervals)
-        rows, n, bases = C.c_void_p(), C.c_size_t(), C.c_int64()
-        self._check(self._L.ribbit_hip_record_best(self._h, iv.ctypes.data if len(iv) else None, len(iv), C.byref(rows), C.byref(n), C.byref(bases)))
-        return _copy(rows.value, n.value, np.dtype("<i4")), int(bases.value)
+        return _record_best(self._dev("ribbit_hip_record_best"), intervals)
 
     def record_classes(self, intervals, motifs, offsets=None):
         """The loaded record's rows by canonical motif class on the GPU (ribbit_hip_record_classes); see host_record_classes"""
-        iv, pool, off = _class_args(intervals, motifs, offsets)
-        classes, strands, groups, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t()
-        self._check(self._L.ribbit_hip_record_classes(self._h, iv.ctypes.data if len(iv) else None, len(iv), pool, off.ctypes.data, C.byref(classes),
-                                                      C.byref(strands), C.byref(groups), C.byref(n)))
-        return C.string_at(classes.value, int(off[-1])), C.string_at(strands.value, len(iv)), _copy(groups.value, n.value, MOTIF_CLASS_DT)
+        return _record_classes(self._dev("ribbit_hip_record_classes"), intervals, motifs, offsets)
 
     def record_compounds(self, intervals, labels, gap: int = 100):
         """The loaded record's rows chained into compound loci on the GPU (ribbit_hip_record_compounds); see host_record_compounds"""
-        iv, lab, gap = _compound_args(intervals, labels, gap)
-        chains, n, members, m = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t()
-        self._check(self._L.ribbit_hip_record_compounds(self._h, iv.ctypes.data if len(iv) else None, lab.ctypes.data if len(iv) else None, len(iv), gap,
-                                                        C.byref(chains), C.byref(n), C.byref(members), C.byref(m)))
-        return _copy(chains.value, n.value, COMPOUND_DT), _copy(members.value, m.value, np.dtype("<i4"))
+        return _record_compounds(self._dev("ribbit_hip_record_compounds"), intervals, labels, gap)
 
     def record_interruptions(self, intervals, motif_lengths, cigars, offsets=None):
         """The loaded record's rows' CIGARs decoded on the GPU (ribbit_hip_record_interruptions); see host_record_interruptions"""
-        iv, k, pool, off = _interruption_args(intervals, motif_lengths, cigars, offsets)
-        rows, sites, m, observed, offsets_out = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_void_p()
-        self._check(self._L.ribbit_hip_record_interruptions(self._h, iv.ctypes.data if len(iv) else None, k.ctypes.data if len(iv) else None, len(iv), pool,
-                                                            off.ctypes.data, C.byref(rows), C.byref(sites), C.byref(m), C.byref(observed), C.byref(offsets_out)))
-        return _interruption_result(rows.value, len(iv), sites.value, m.value, observed.value, offsets_out.value)
+        return _record_interruptions(self._dev("ribbit_hip_record_interruptions"), intervals, motif_lengths, cigars, offsets)
 
     def record_density(self, intervals, window: int) -> np.ndarray:
         """The loaded record's covered bases per window on the GPU (ribbit_hip_record_density); see host_record_density"""
-        iv, window = _rows_arg(intervals, window, "window")
-        cov, n = C.c_void_p(), C.c_size_t()
-        self._check(self._L.ribbit_hip_record_density(self._h, iv.ctypes.data if len(iv) else None, len(iv), window, C.byref(cov), C.byref(n)))
-        return _copy(cov.value, n.value, np.dtype("<i4"))
+        return _record_density(self._dev("ribbit_hip_record_density"), intervals, window)
 
     def debug_set_repeat_text_budget(self, nbytes: int) -> None:
         """the text budget of one ribbit_hip_repeat_sequences call in bytes (0: the default, 64 MiB)"""
@@ -2114,7 +1709,7 @@ class Scanner:
         piece, in record coordinates -> dict(calls, pend (or None), tail_pend, flush, inexact, streaks) (copies)"""
         cc = ChunkCalls()
         self._check(self._L.ribbit_hip_stage_calls_chunk(self._h, stage, own_lo, min(own_hi, (1 << 62)), pos_offset, record_length, C.byref(cc)))
-        return {"calls": _copy(cc.calls, cc.n, CALL_DT), "pend": _copy(cc.pend, cc.n, np.dtype("<i4")) if cc.pend else None,
+        return {"calls": _copy(cc.calls, cc.n, CALL_DT), "pend": _copy(cc.pend, cc.n, _I4) if cc.pend else None,
                 "tail_pend": int(cc.tail_pend), "flush": _copy(cc.flush, cc.n_flush, CALL_DT), "inexact": bool(cc.inexact),
                 "streaks": int(cc.streaks)}
 
