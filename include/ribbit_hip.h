@@ -1010,6 +1010,70 @@ int ribbit_bed_primer_products_text(const char *bed_text, size_t bed_len, const 
                                     size_t n, char **text, size_t *len);
 
 /*
+ * ---- the best primer pair of every target that amplifies nothing else in the record ----------------------------------------
+ * The two contracts above put together: where ribbit_hip_record_primer_pairs takes the best admissible pair of the two
+ * shortlists and ribbit_hip_record_primer_products says what that one pair amplifies, this takes the best admissible pair that
+ * is specific.  Everything is integer arithmetic on letters; nothing is added to either contract.
+ *   Shortlists: candidates, shortlists and the admissible pairs of a target are exactly steps (1) to (3) of the selection.
+ *   Order:      the admissible pairs in the order of step (4)'s key, (penalty_l + penalty_r + |Tm_l - Tm_r|, product, rank_l,
+ *               rank_r); no two pairs share a key.  A pair's PLACE is its 0-based position in that order.
+ *   Products:   the pair (l, r) is judged by the in-silico PCR contract with a = the left candidate's oligo, b = the right
+ *               candidate's oligo as ordered (the reverse complement of its forward-strand bases), and own = (a forward at the
+ *               left candidate's start, b reverse at the right candidate's start).
+ *   Outcomes:   every admissible pair is exactly one of OVER (products == -1: one of its four site lists is longer than
+ *               max_sites), SPECIFIC (not over and products - own == 0, as defined above) and OTHER (neither).
+ *   Choice:     the chosen pair is the first specific pair in that order.  There is no fallback: without a specific pair the
+ *               target has no pair.
+ *   Records:    per target a RibbitRowPrimerPair of the chosen pair, every field as ribbit_hip_record_primer_pairs would fill
+ *               it had it chosen that pair (ranks, the five dimer values, the six counts; pairs_admissible counts all admissible
+ *               pairs); without a pair both starts are -1 and every field is 0 except the six counts.  Its RibbitRowProducts
+ *               (eight zeros without a pair).  And a RibbitRowSpecific, below.
+ *   Values:     4,000 random bases with (CA)20 at 1500, the target (1500, 1540), no rows, the defaults
+ *               (tests/primer_specific_contract.py builds the records and computes the values from a plain statement of the
+ *               above), as (place, pairs_admissible, pairs_specific, pairs_over, pairs_other, first_products) and the chosen
+ *               pair's (left start, left length, right start, right length):
+ *                 undisturbed                                               (0, 44, 44, 0, 0, 0)     (1304, 22, 1624, 21)
+ *                 that pair's two windows copied to 3000 and 60 bases behind (2, 44, 26, 0, 18, 2)    (1304, 22, 1613, 22)
+ *                 both flanks of 200 bases copied to 2600 .. 3000           (-1, 44, 0, 0, 44, 2)    no pair
+ *                 the left flank alone copied to 2600                       (0, 44, 44, 0, 0, 0)     (1304, 22, 1624, 21)
+ *                 the same at max_sites 1                                   (-1, 44, 0, 44, 0, -1)   no pair
+ */
+typedef struct {
+    int32_t place;                            /* of the chosen pair among the admissible pairs; -1: no pair is specific */
+    int32_t pairs_admissible;                 /* = pairs_specific + pairs_over + pairs_other */
+    int32_t pairs_specific, pairs_over, pairs_other;
+    int32_t first_products;                   /* products - own of the pair in place 0 (what ribbit_bed_primer_products_text prints */
+    int32_t reserved[2];                      /* beside it): -1 when that pair is over, 0 without an admissible pair.  reserved 0 */
+} RibbitRowSpecific;                          /* 32 bytes */
+/* The loaded record's n_targets targets (at most INT32_MAX) against the coverage of its n rows, on the GPU (primer_specific.hip):
+ * *pairs, *products and *specific are one record per target each, in the order given, of handle-owned page-locked memory, valid
+ * until the handle's next call of this function, load or close.  The shortlisted oligos of a batch of targets are searched
+ * together, one pass over the record per batch; the result does not depend on the batches.  States and refusals are those of
+ * ribbit_hip_record_primer_pairs and ribbit_hip_record_primer_products: a field of any of the three parameter sets outside its
+ * range is RIBBIT_E_ARG and the error text names the field, and so is params->min_length below product_params->seed (a
+ * shortlisted primer would be shorter than the seed); before a load: RIBBIT_E_STATE.  n_targets = 0 and L = 0 are no errors. */
+int ribbit_hip_record_specific_primer_pairs(RibbitHandle *h, const int32_t *intervals, size_t n, const int32_t *targets, size_t n_targets,
+                                            const RibbitPrimerParams *params, const RibbitPrimerPairParams *pair_params,
+                                            const RibbitProductParams *product_params, const RibbitRowPrimerPair **pairs,
+                                            const RibbitRowProducts **products, const RibbitRowSpecific **specific);
+/* Host-only twin (no GPU), from the bytes of `sequence` (0 <= length < 2^31), letter by letter: the three arrays malloc'ed, release
+ * each with ribbit_primer_specific_free(). */
+int ribbit_host_record_specific_primer_pairs(const char *sequence, int64_t length, const int32_t *intervals, size_t n, const int32_t *targets,
+                                             size_t n_targets, const RibbitPrimerParams *params, const RibbitPrimerPairParams *pair_params,
+                                             const RibbitProductParams *product_params, RibbitRowPrimerPair **pairs,
+                                             RibbitRowProducts **products, RibbitRowSpecific **specific);
+void ribbit_primer_specific_free(void *from_the_host_twin);
+/* For tests: the targets of one batch of ribbit_hip_record_specific_primer_pairs on this handle; 0 restores the rule (as many as
+ * 256 MiB of site lists hold with 16 distinct oligos per target: 32,768 at max_sites 64). */
+int ribbit_hip_debug_set_specific_batch(RibbitHandle *h, size_t targets);
+/* The targets' BED rows with their specific pairs (host only): the 38 columns of ribbit_bed_primer_products_text for the chosen
+ * pair, then four more, 42 in all: place, pairs_specific, pairs_over, pairs_other.  Without a pair the first 18 pair columns, the
+ * six product columns and place are "."; the counts stay.  bed_text and the refusals as for ribbit_bed_primer_pairs_text.  *text
+ * malloc'ed, release with ribbit_text_free(). */
+int ribbit_bed_primer_specific_text(const char *bed_text, size_t bed_len, const RibbitRowPrimerPair *pairs, const RibbitRowProducts *products,
+                                    const RibbitRowSpecific *specific, size_t n, char **text, size_t *len);
+
+/*
  * ---- streaming FASTA ingest ---------------------------------------------------------------------------------------
  * Replaces the reader loop of ribbit.cpp:269-280 (getline + `sequence += line` into one pageable std::string per
  * record).  The file is read in 16-MB blocks; line bodies are copied once, straight into a page-locked buffer

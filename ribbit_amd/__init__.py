@@ -33,7 +33,8 @@ __all__ = ["RibbitHipError", "ScanParams", "Scanner", "library_path", "load_libr
            "PRIMERS_DT", "PrimerParams", "primer_params", "host_record_primers", "bed_primers_text",
            "PRIMER_PAIRS_DT", "PrimerPairParams", "primer_pair_params", "host_record_primer_pairs", "bed_primer_pairs_text", "oligo_duplex", "oligo_hairpin",
            "PRIMER_PRODUCTS_DT", "OLIGO_SITES_DT", "ProductParams", "product_params", "host_record_oligo_sites", "host_record_primer_products",
-           "bed_primer_products_text"]
+           "bed_primer_products_text",
+           "PRIMER_SPECIFIC_DT", "host_record_specific_primer_pairs", "bed_primer_specific_text"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -65,6 +66,8 @@ PRIMER_PAIRS_DT = np.dtype([(f"{side}_{n}", "<i4") for side in ("left", "right")
                                                    "left_passed", "right_passed", "pairs_tried", "pairs_admissible", "reserved")])      # RibbitRowPrimerPair
 PRIMER_PRODUCTS_DT = np.dtype([(n, "<i4") for n in ("left_forward", "left_reverse", "right_forward", "right_reverse", "products", "own", "shortest_other",
                                                      "reserved")])      # RibbitRowProducts
+PRIMER_SPECIFIC_DT = np.dtype([(n, "<i4") for n in ("place", "pairs_admissible", "pairs_specific", "pairs_over", "pairs_other", "first_products", "reserved0",
+                                                     "reserved1")])      # RibbitRowSpecific
 OLIGO_SITES_DT = np.dtype([(n, "<i4") for n in ("forward", "reverse", "forward_at", "reverse_at")])      # RibbitOligoSites
 _OLIGO_DT = np.dtype([(n, "<i4") for n in ("length", "bases_lo", "bases_hi")])      # RibbitOligo
 _I4 = np.dtype("<i4")
@@ -268,18 +271,20 @@ def _signatures() -> dict:
         "ribbit_nearest_other_text": (st, [cp, vp, cp, vp, sz, vp, vp, cp, vp, sz, pvp, psz]),
         "ribbit_base_windows_text": (st, [cp, i64, i32, vp, sz, pvp, psz]),
         "ribbit_bed_primer_products_text": (st, [cp, sz, vp, vp, sz, pvp, psz]),
+        "ribbit_bed_primer_specific_text": (st, [cp, sz, vp, vp, vp, sz, pvp, psz]),
     }
     for name in ("ribbit_hip_scan_perfect_runs", "ribbit_hip_perfect_calls", "ribbit_hip_seeds_perfect", "ribbit_hip_subst_calls",
                  "ribbit_hip_anchored_calls", "ribbit_hip_dispatch_seeds", "ribbit_hip_seed_longest_runs"):
         t[name] = (st, [vp, pvp, psz])                       # a list of the handle's and its length
-    for name in ("ribbit_hip_debug_set_event_capacity", "ribbit_hip_debug_set_repeat_text_budget", "ribbit_hip_debug_set_small_record_capacity"):
+    for name in ("ribbit_hip_debug_set_event_capacity", "ribbit_hip_debug_set_repeat_text_budget", "ribbit_hip_debug_set_small_record_capacity",
+                 "ribbit_hip_debug_set_specific_batch"):
         t[name] = (st, [vp, sz])
     for name in ("ribbit_bed_overlap_text", "ribbit_bed_rows_text", "ribbit_bed_composition_text", "ribbit_bed_primers_text",
                  "ribbit_bed_primer_pairs_text"):
         t[name] = (st, [cp, sz, vp, sz, pvp, psz])           # BED text, an array with a record per row
     for name in ("ribbit_text_free", "ribbit_runs_free", "ribbit_intervals_free", "ribbit_loci_free", "ribbit_motif_classes_free",
                  "ribbit_compounds_free", "ribbit_row_purity_free", "ribbit_interruptions_free", "ribbit_nearest_free", "ribbit_composition_free",
-                 "ribbit_primers_free", "ribbit_primer_pairs_free", "ribbit_products_free"):
+                 "ribbit_primers_free", "ribbit_primer_pairs_free", "ribbit_products_free", "ribbit_primer_specific_free"):
         t[name] = (None, [vp])
     # the row outputs: the device form takes the handle, the host form the record's length, or its bases and their number
     length, bases = [i64], [cp, i64]
@@ -294,6 +299,7 @@ def _signatures() -> dict:
                              ("record_primer_pairs", bases, [vp, sz, vp, sz, P(PrimerParams), P(PrimerPairParams), pvp]),
                              ("record_oligo_sites", bases, [vp, sz, P(ProductParams), pvp, pvp, psz]),
                              ("record_primer_products", bases, [vp, sz, P(ProductParams), pvp]),
+                             ("record_specific_primer_pairs", bases, [vp, sz, vp, sz, P(PrimerParams), P(PrimerPairParams), P(ProductParams), pvp, pvp, pvp]),
                              ("record_best", length, [vp, sz, pvp, psz, P(i64)]),
                              ("record_classes", length, [vp, sz, vp, vp, pvp, pvp, pvp, psz]),
                              ("record_compounds", length, [vp, vp, sz, i32, pvp, psz, pvp, psz]),
@@ -891,6 +897,32 @@ def host_record_primer_products(sequence: bytes, pairs, params: ProductParams | 
     return _record_primer_products(_host_bases("ribbit_host_record_primer_products", sequence), pairs, params)
 
 
+def _record_specific_primer_pairs(call, intervals, targets, params, pair_params, product_params):
+    """-> a PRIMER_PAIRS_DT, a PRIMER_PRODUCTS_DT and a PRIMER_SPECIFIC_DT array, one record per target each"""
+    iv, tg = _pairs(intervals), _pairs(targets)
+    params = _params_arg(params, primer_params, PrimerParams)
+    pair_params = _params_arg(pair_params, primer_pair_params, PrimerPairParams, "pair_params")
+    product_params = _params_arg(product_params, globals()["product_params"], ProductParams, "product_params")
+    pairs, products, specific = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    owned = _call(call, _ptr(iv), len(iv), _ptr(tg), len(tg), C.byref(params), C.byref(pair_params), C.byref(product_params), C.byref(pairs), C.byref(products),
+                  C.byref(specific))
+    try:
+        return _copy(pairs.value, len(tg), PRIMER_PAIRS_DT), _copy(products.value, len(tg), PRIMER_PRODUCTS_DT), _copy(specific.value, len(tg), PRIMER_SPECIFIC_DT)
+    finally:
+        _free(owned, "ribbit_primer_specific_free", pairs, products, specific)
+
+
+def host_record_specific_primer_pairs(sequence: bytes, intervals, targets, params: PrimerParams | None = None, pair_params: PrimerPairParams | None = None,
+                                      product_params: ProductParams | None = None):
+    """ribbit_host_record_specific_primer_pairs: for every (start, end) target the best admissible pair of host_record_primer_pairs'
+    two shortlists that amplifies nothing else in the record: the admissible pairs in the order of that choice, each judged by
+    host_record_primer_products' in-silico PCR, the first one with products - own == 0 taken; no fallback -> (a PRIMER_PAIRS_DT array
+    of the chosen pairs, a PRIMER_PRODUCTS_DT array of their products, a PRIMER_SPECIFIC_DT array: the chosen pair's place in that
+    order, the admissible pairs by outcome and what the pair in place 0 amplifies besides its own product).  The contract is in
+    include/ribbit_hip.h.  No GPU needed."""
+    return _record_specific_primer_pairs(_host_bases("ribbit_host_record_specific_primer_pairs", sequence), intervals, targets, params, pair_params, product_params)
+
+
 def _record_best(call, intervals):
     iv, bases = _pairs(intervals), C.c_int64()
     rows = _array(call, _ptr(iv), len(iv), dt=_I4, free="ribbit_intervals_free", tail=(C.byref(bases),))
@@ -1101,6 +1133,16 @@ def bed_primer_products_text(bed, pairs, products) -> bytes:
     if len(pr) != len(rw):
         raise ValueError(f"{len(rw)} pairs and {len(pr)} products")
     return _text("ribbit_bed_primer_products_text", text_in, len(text_in), _ptr(rw), _ptr(pr), len(rw))
+
+
+def bed_primer_specific_text(bed, pairs, products, specific) -> bytes:
+    """ribbit_bed_primer_specific_text: the lines of bed_primer_products_text(bed, pairs, products) for the chosen pairs, each with four
+    more columns from row i of `specific` (record_specific_primer_pairs): the pair's place among the admissible pairs ('.' without a
+    pair) and the specific, over and other pairs."""
+    text_in, rw, pr, sp = _bytes(bed), _records(pairs, PRIMER_PAIRS_DT), _records(products, PRIMER_PRODUCTS_DT), _records(specific, PRIMER_SPECIFIC_DT)
+    if not len(pr) == len(rw) == len(sp):
+        raise ValueError(f"{len(rw)} pairs, {len(pr)} products and {len(sp)} summaries")
+    return _text("ribbit_bed_primer_specific_text", text_in, len(text_in), _ptr(rw), _ptr(pr), _ptr(sp), len(rw))
 
 
 def oligo_duplex(a, b) -> tuple:
@@ -1570,6 +1612,13 @@ class Scanner:
         host_record_primer_products"""
         return _record_primer_products(self._dev("ribbit_hip_record_primer_products"), pairs, params)
 
+    def record_specific_primer_pairs(self, intervals, targets, params: PrimerParams | None = None, pair_params: PrimerPairParams | None = None,
+                                     product_params: ProductParams | None = None):
+        """The best primer pair of every target of the loaded record that amplifies nothing else in it, on the GPU: all pairs of the
+        two shortlists judged by an in-silico PCR, a wavefront per target (ribbit_hip_record_specific_primer_pairs); see
+        host_record_specific_primer_pairs"""
+        return _record_specific_primer_pairs(self._dev("ribbit_hip_record_specific_primer_pairs"), intervals, targets, params, pair_params, product_params)
+
     def record_best(self, intervals):
         """The loaded record's best non-overlapping rows on the GPU (ribbit_hip_record_best); see host_record_best"""
         return _record_best(self._dev("ribbit_hip_record_best"), intervals)
@@ -1593,6 +1642,10 @@ class Scanner:
     def debug_set_repeat_text_budget(self, nbytes: int) -> None:
         """the text budget of one ribbit_hip_repeat_sequences call in bytes (0: the default, 64 MiB)"""
         self._check(self._L.ribbit_hip_debug_set_repeat_text_budget(self._h, int(nbytes)))
+
+    def debug_set_specific_batch(self, targets: int) -> None:
+        """the targets of one batch of record_specific_primer_pairs (0: as many as 256 MiB of site lists hold)"""
+        self._check(self._L.ribbit_hip_debug_set_specific_batch(self._h, int(targets)))
 
     def debug_set_small_record_capacity(self, records: int) -> None:
         """records the arena of small_motifs holds (0 = automatic); seeds that find it full get flags 2 and go to the host twin"""

@@ -22,7 +22,8 @@
 //   api_primers.cpp     a forward and a reverse primer in the flanks of every target, from the bit planes and the rows' coverage (primers.hip), its host twin, the text
 //   api_primer_pairs.cpp  the two primers of every target chosen as a pair and checked for dimers and hairpins (primer_pairs.hip), its host twin, the oligo checks, the text
 //   api_primer_products.cpp  the sites of oligos on either strand of the record and the products of primer pairs among them (primer_products.hip), their host twins, the text
-// The last thirteen are the row outputs: their buffers are the handle's RowBufs `rows`, where all device work of a call is carved from
+//   api_primer_specific.cpp  the best primer pair of every target that amplifies nothing else in the record (primer_specific.hip, with primer_products.hip's site scan), its host twin, the text
+// The last fourteen are the row outputs: their buffers are the handle's RowBufs `rows`, where all device work of a call is carved from
 // one buffer by the layout its .hip file states (kernels.h); best, classes, compound, interruptions, nearest, primers and primer pairs stage their inputs through stage_down, what their host
 // sides share is below (hand_out, clipped_sorted_rows), what their kernels share is row_kernels.h, and the BED text they read and
 // write (the row format, the reader in pieces, the writer in pieces) is
@@ -488,6 +489,11 @@ struct RibbitHandle {
         PinnedBuf<uint32_t> h_product_header;
         PinnedBuf<uint8_t> h_products;
         PinnedBuf<int32_t> h_site_positions;
+        // the specific primer pairs (api_primer_specific.cpp): the three records of every target on their way up, one array behind the
+        // other; a batch's number of oligos on its way up; the targets of a batch (0: as many as SPECIFIC_LIST_BYTES of site lists hold)
+        PinnedBuf<uint8_t> h_specific;
+        PinnedBuf<uint32_t> h_specific_header;
+        size_t specific_batch = 0;
         // the blocks' base counts | their prefix, which belongs to the record (rec.base_prefix_valid, api_composition.cpp)
         DevBuf<rb::BaseSums> d_comp_sums;
         size_t rep_budget = 0;           // text budget of one batch of repeat sequences in bytes (0: REPEAT_TEXT_BUDGET)

@@ -186,13 +186,16 @@ RibbitPrimer primer_of(const unsigned char *seq, const Listed &it) {
     return RibbitPrimer{(int32_t)it.p, it.k, it.tm, it.penalty, (int32_t)(uint32_t)bases, (int32_t)(uint32_t)(bases >> 32)};
 }
 
-RibbitRowPrimerPair pair_of(const unsigned char *seq, const std::vector<uint8_t> &covered, const Flanks &f, const RibbitPrimerParams &prm, const RibbitPrimerPairParams &pair) {
+// every admissible pair of the target's two shortlists, each as the record the choice would fill for it, in the order of step (4);
+// none: the record of a target without a pair (the six counts; pairs_admissible is the others' too)
+void ordered_pairs_of(const unsigned char *seq, const std::vector<uint8_t> &covered, const Flanks &f, const RibbitPrimerParams &prm, const RibbitPrimerPairParams &pair,
+                      std::vector<RibbitRowPrimerPair> &ordered, RibbitRowPrimerPair &none) {
     std::vector<Listed> left, right;
     int32_t n_left, n_right, p_left, p_right;
     side(seq, covered, f.lo, f.s, false, prm, pair, left, n_left, p_left);
     side(seq, covered, f.e, f.hi, true, prm, pair, right, n_right, p_right);
-    RibbitRowPrimerPair out = no_pair(n_left, n_right, p_left, p_right, (int32_t)(left.size() * right.size()));
-    std::tuple<int32_t, int64_t, int32_t, int32_t> best{};
+    none = no_pair(n_left, n_right, p_left, p_right, (int32_t)(left.size() * right.size()));
+    ordered.clear();
     for (int32_t l = 0; l < (int32_t)left.size(); ++l)
         for (int32_t r = 0; r < (int32_t)right.size(); ++r) {
             const Listed &a = left[(size_t)l], &b = right[(size_t)r];
@@ -200,16 +203,12 @@ RibbitRowPrimerPair pair_of(const unsigned char *seq, const std::vector<uint8_t>
             if (difference > pair.max_tm_difference) continue;
             const Duplex d = duplex(a.oligo, b.oligo);
             if (d.any > pair.max_pair_any || d.end > pair.max_pair_end) continue;
-            ++out.pairs_admissible;
-            const int64_t product = b.p + b.k - a.p;
-            const auto key = std::make_tuple(a.penalty + b.penalty + difference, product, l, r);
-            if (out.left.start >= 0 && best <= key) continue;
-            best = key;
+            RibbitRowPrimerPair out = none;
             out.left = primer_of(seq, a);
             out.right = primer_of(seq, b);
-            out.pair_penalty = std::get<0>(key);
+            out.pair_penalty = a.penalty + b.penalty + difference;
             out.tm_difference = difference;
-            out.product = (int32_t)product;
+            out.product = (int32_t)(b.p + b.k - a.p);
             out.left_rank = l;
             out.right_rank = r;
             out.left_self_any = a.self.any;
@@ -220,8 +219,20 @@ RibbitRowPrimerPair pair_of(const unsigned char *seq, const std::vector<uint8_t>
             out.right_hairpin = b.hairpin;
             out.pair_any = d.any;
             out.pair_end = d.end;
+            ordered.push_back(out);
         }
-    return out;
+    const auto key = [](const RibbitRowPrimerPair &r) { return std::make_tuple(r.pair_penalty, r.product, r.left_rank, r.right_rank); };
+    std::sort(ordered.begin(), ordered.end(), [&](const RibbitRowPrimerPair &x, const RibbitRowPrimerPair &y) { return key(x) < key(y); });
+    none.pairs_admissible = (int32_t)ordered.size();
+    for (RibbitRowPrimerPair &r : ordered) r.pairs_admissible = none.pairs_admissible;
+}
+
+RibbitRowPrimerPair pair_of(const unsigned char *seq, const std::vector<uint8_t> &covered, const Flanks &f, const RibbitPrimerParams &prm, const RibbitPrimerPairParams &pair) {
+    std::vector<RibbitRowPrimerPair> ordered;
+    RibbitRowPrimerPair none;
+    ordered_pairs_of(seq, covered, f, prm, pair, ordered, none);
+    if (ordered.empty()) return none;
+    return ordered.front();
 }
 
 int host_record_primer_pairs_impl(const char *sequence, int64_t length, const int32_t *intervals, size_t n, const int32_t *targets, size_t n_targets,
@@ -231,9 +242,7 @@ int host_record_primer_pairs_impl(const char *sequence, int64_t length, const in
     if (length < 0 || length > (int64_t)INT32_MAX) return fail(RIBBIT_E_ARG, "a record of %lld bases", (long long)length);
     if (!sequence && length > 0) return fail(RIBBIT_E_ARG, "bad sequence");
     const unsigned char *seq = reinterpret_cast<const unsigned char *>(sequence);
-    std::vector<uint8_t> covered((size_t)length, 0);
-    const CoveredRuns runs(clipped_sorted_rows(length, intervals, n));
-    for (size_t k = 0; k < runs.start.size(); ++k) std::fill(covered.begin() + runs.start[k], covered.begin() + runs.end[k], 1);
+    const std::vector<uint8_t> covered = host_covered(length, intervals, n);
     Handed<RibbitRowPrimerPair> out;
     if ((rc = hand_out<RibbitRowPrimerPair>(nullptr, n_targets, false, out))) return rc;
     const RibbitPrimerParams prm = *params;
@@ -274,6 +283,25 @@ int bed_primer_pairs_text_impl(const char *bed, size_t bed_len, const RibbitRowP
 }
 
 }  // namespace
+
+// ---- what api_primer_specific.cpp takes from here (primers_host.h)
+namespace rbapi {
+
+int check_primer_pair_params(const RibbitPrimerPairParams *p) { return check_pair_params(p); }
+
+std::vector<uint8_t> host_covered(int64_t length, const int32_t *intervals, size_t n) {
+    std::vector<uint8_t> covered((size_t)length, 0);
+    const CoveredRuns runs(clipped_sorted_rows(length, intervals, n));
+    for (size_t k = 0; k < runs.start.size(); ++k) std::fill(covered.begin() + runs.start[k], covered.begin() + runs.end[k], 1);
+    return covered;
+}
+
+void host_ordered_pairs(const unsigned char *seq, const std::vector<uint8_t> &covered, const Flanks &f, const RibbitPrimerParams &prm, const RibbitPrimerPairParams &pair,
+                        std::vector<RibbitRowPrimerPair> &ordered, RibbitRowPrimerPair &none) {
+    ordered_pairs_of(seq, covered, f, prm, pair, ordered, none);
+}
+
+}  // namespace rbapi
 
 extern "C" {
 

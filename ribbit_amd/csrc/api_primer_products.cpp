@@ -215,7 +215,7 @@ char letter_at(const unsigned char *seq, int64_t p) {      // the base there in 
     return c < 0 ? 0 : "ACGT"[c];
 }
 
-struct Sites { std::vector<int32_t> forward, reverse; };
+using Sites = HostSites;
 
 // pattern at the window [x, x + k): its exact part [from, to) and at most d mismatches elsewhere, no byte of kind `other`
 bool window_holds(const unsigned char *seq, int64_t x, const std::string &pattern, size_t from, size_t to, int32_t d) {
@@ -286,12 +286,10 @@ int host_record_oligo_sites_impl(const char *sequence, int64_t length, const Rib
 
 struct Site { int64_t x, k; bool of_a; };
 
-RibbitRowProducts products_of(const unsigned char *seq, int64_t length, const RibbitRowPrimerPair &pair, const RibbitProductParams &prm) {
+// the products among the sites a and b of a pair's two oligos of ka and kb bases, whose own product is (a forward at left_start, b
+// reverse at right_start)
+RibbitRowProducts products_among(const Sites &a, const Sites &b, int32_t ka, int32_t kb, int32_t left_start, int32_t right_start, const RibbitProductParams &prm) {
     RibbitRowProducts r{};
-    if (!has_pair(pair)) return r;
-    RibbitOligo oa, ob;
-    oligos_of(pair, oa, ob);
-    const Sites a = sites_of(seq, length, letters_of(oa), prm), b = sites_of(seq, length, letters_of(ob), prm);
     r.left_forward = (int32_t)a.forward.size();
     r.left_reverse = (int32_t)a.reverse.size();
     r.right_forward = (int32_t)b.forward.size();
@@ -301,21 +299,28 @@ RibbitRowProducts products_of(const unsigned char *seq, int64_t length, const Ri
         return r;
     }
     std::vector<Site> forward, reverse;
-    for (const int32_t x : a.forward) forward.push_back(Site{x, oa.length, true});
-    for (const int32_t x : b.forward) forward.push_back(Site{x, ob.length, false});
-    for (const int32_t x : a.reverse) reverse.push_back(Site{x, oa.length, true});
-    for (const int32_t x : b.reverse) reverse.push_back(Site{x, ob.length, false});
+    for (const int32_t x : a.forward) forward.push_back(Site{x, ka, true});
+    for (const int32_t x : b.forward) forward.push_back(Site{x, kb, false});
+    for (const int32_t x : a.reverse) reverse.push_back(Site{x, ka, true});
+    for (const int32_t x : b.reverse) reverse.push_back(Site{x, kb, false});
     int64_t shortest = 0;
     for (const Site &f : forward)
         for (const Site &v : reverse) {
             const int64_t size = v.x + v.k - f.x;
             if (f.x + f.k > v.x || size > prm.max_product) continue;
             ++r.products;
-            if (f.of_a && !v.of_a && f.x == pair.left.start && v.x == pair.right.start) r.own = 1;
+            if (f.of_a && !v.of_a && f.x == left_start && v.x == right_start) r.own = 1;
             else if (shortest == 0 || size < shortest) shortest = size;
         }
     r.shortest_other = (int32_t)shortest;
     return r;
+}
+
+RibbitRowProducts products_of(const unsigned char *seq, int64_t length, const RibbitRowPrimerPair &pair, const RibbitProductParams &prm) {
+    if (!has_pair(pair)) return RibbitRowProducts{};
+    RibbitOligo oa, ob;
+    oligos_of(pair, oa, ob);
+    return products_among(sites_of(seq, length, letters_of(oa), prm), sites_of(seq, length, letters_of(ob), prm), oa.length, ob.length, pair.left.start, pair.right.start, prm);
 }
 
 int host_record_primer_products_impl(const char *sequence, int64_t length, const RibbitRowPrimerPair *pairs, size_t n, const RibbitProductParams *params,
@@ -357,22 +362,7 @@ int bed_primer_products_text_impl(const char *bed, size_t bed_len, const RibbitR
                 if (const RibbitPrimer *bad = bad_primer(r)) return PieceRefusal{BAD_LENGTH, i, (size_t)(uint32_t)bad->length};
                 put_field(out, lines[i]);
                 put_pair_columns(out, r);
-                if (has_pair(r)) {
-                    for (const int32_t v : {p.left_forward, p.left_reverse, p.right_forward, p.right_reverse}) {
-                        out += '\t';
-                        put_number(out, v);
-                    }
-                    if (p.products < 0) {
-                        out += "\t.\t.";
-                    } else {
-                        out += '\t';
-                        put_number(out, p.products - p.own);
-                        out += '\t';
-                        put_number(out, p.shortest_other);
-                    }
-                } else {
-                    for (int c = 0; c < 6; ++c) out += "\t.";
-                }
+                put_product_columns(out, r, p);
                 out += '\n';
             }
             return PieceRefusal{};
@@ -381,6 +371,26 @@ int bed_primer_products_text_impl(const char *bed, size_t bed_len, const RibbitR
 }
 
 }  // namespace
+
+// ---- what api_primer_specific.cpp takes from here (primers_host.h)
+namespace rbapi {
+
+int check_primer_product_params(const RibbitProductParams *p) { return check_product_params(p); }
+
+void host_pair_oligos(const RibbitRowPrimerPair &pair, std::string &a, std::string &b) {
+    RibbitOligo oa, ob;
+    oligos_of(pair, oa, ob);
+    a = letters_of(oa);
+    b = letters_of(ob);
+}
+
+HostSites host_oligo_sites(const unsigned char *seq, int64_t length, const std::string &oligo, const RibbitProductParams &prm) { return sites_of(seq, length, oligo, prm); }
+
+RibbitRowProducts host_products_among(const HostSites &a, const HostSites &b, int32_t ka, int32_t kb, int32_t left_start, int32_t right_start, const RibbitProductParams &prm) {
+    return products_among(a, b, ka, kb, left_start, right_start, prm);
+}
+
+}  // namespace rbapi
 
 extern "C" {
 

@@ -536,6 +536,33 @@ hipError_t launch_pair_products(const int32_t *pairs, int64_t n_pairs, const Rib
 hipError_t launch_oligo_sites(int64_t n_oligos, const RibbitProductParams &prm, uint8_t *work, size_t work_bytes, const ProductLayout &at, hipStream_t stream);
 void launch_site_gather(int64_t n_oligos, const RibbitProductParams &prm, uint8_t *work, const ProductLayout &at, const int32_t *lists, int32_t *flat, hipStream_t stream);
 
+// primer_specific.hip: the best primer pair of every one of n_targets >= 1 targets of the loaded record (length > 0) that
+// amplifies nothing else in it (api_primer_specific.cpp; include/ribbit_hip.h has the contract).  bits, targets, prm, pair: as for
+// primer_pairs.hip; product: checked by the caller.  The api file serves the targets in batches and sizes the layout by the
+// largest.  A batch takes the launches in this order, and the host reads `header` and primer_products.hip's header between them:
+//   launch_primer_shortlists   the two shortlists of every target (16 RibbitPrimer, four counts), and their primers as oligos one
+//                              behind the other, the right ones as ordered; header.oligos = N
+//   launch_product_uniques, launch_product_scan   (primer_products.hip) on those N oligos, with work + product_work as their work
+//                              buffer and `product` as their layout; none of them when N == 0
+//   launch_specific_pairs      one RibbitRowPrimerPair, RibbitRowProducts and RibbitRowSpecific per target
+struct SpecificHeader { uint32_t oligos, spare[3]; };
+struct SpecificLayout : WorkLayout {
+    size_t lists;         // the shortlists, 16 RibbitPrimer per target: the left side's 8 places, then the right side's (start -1: empty)
+    size_t side_counts;   // left_candidates, right_candidates, left_passed, right_passed of every target
+    size_t n_oligos;      // the shortlisted primers of every target | their inclusive sum, n_targets words each
+    size_t oligos;        // those primers as RibbitOligo, a target's one behind the other, 16 n_targets at most
+    size_t header;        // SpecificHeader
+    size_t pairs, products, specific;   // the result, n_targets records each
+    size_t product_work;  // the work buffer of primer_products.hip's launches for 16 n_targets oligos ...
+    ProductLayout product;              // ... and its layout (offsets from product_work)
+};
+SpecificLayout specific_layout(int64_t n_targets);
+hipError_t launch_primer_shortlists(const DevicePlanes &pl, const uint32_t *bits, const int32_t *targets, int64_t n_targets, const RibbitPrimerParams &prm,
+                                    const RibbitPrimerPairParams &pair, uint8_t *work, size_t work_bytes, const SpecificLayout &at, hipStream_t stream);
+// site_lists: what launch_product_scan filled (not read when no target of the batch has an admissible pair)
+hipError_t launch_specific_pairs(int64_t n_targets, const RibbitPrimerPairParams &pair, const RibbitProductParams &product, uint8_t *work, size_t work_bytes,
+                                 const SpecificLayout &at, const int32_t *site_lists, hipStream_t stream);
+
 // profiling aid: reads nwords dwords of src with one coalesced dword per lane (known byte count)
 void launch_calib_stream_read(const uint32_t *src, int64_t nwords, uint32_t *sink, hipStream_t stream);
 

@@ -24,15 +24,16 @@
 //              64) send one add, and each takes base + its rank.  Slots are taken in no fixed order, so a list that is complete
 //              (count <= max_sites) is sorted afterwards, one wavefront per list, bitonic in LDS: the result is the same from run
 //              to run.  A list that is not complete is never read.
-//   products   One lane per pair over its four sorted lists: for every forward site two bisections per reverse list give the
-//              sites in [x + k1, x + max_product - k2]; the same walk gives `own` and `shortest_other`.
+//   products   One lane per pair over its four sorted lists (product_walk.h, shared with primer_specific.hip): for every forward
+//              site two bisections per reverse list give the sites in [x + k1, x + max_product - k2]; the same walk gives `own`
+//              and `shortest_other`.
 // Integer vector atomics only; no inline assembly.
 #include <cstring>
 
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
-#include "row_kernels.h"
+#include "product_walk.h"
 
 namespace rb {
 
@@ -53,11 +54,6 @@ struct OligoLess {
         return a.index < b.index;
     }
 };
-struct UniqueOligo {
-    unsigned long long bases;
-    uint32_t length, spare;
-};
-
 __host__ __device__ inline uint32_t low_bits(int k) { return k >= 32 ? 0xffffffffu : (1u << k) - 1u; }
 // the even bits of v, packed
 __device__ inline uint32_t even_bits(unsigned long long v) {
@@ -246,63 +242,13 @@ __global__ void __launch_bounds__(64) sort_lists_kernel(const uint32_t *__restri
     }
 }
 
-// ---- the products of a pair
-// the entries of the ascending list[0, n) below v
-__device__ inline int below(const int32_t *__restrict__ list, int n, int64_t v) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if ((int64_t)list[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
+// ---- the products of a pair (product_walk.h)
 __global__ void __launch_bounds__(ROW_THREADS) pair_products_kernel(const int32_t *__restrict__ pairs, int64_t n_pairs, const uint32_t *__restrict__ unique_of,
                                                                       const UniqueOligo *__restrict__ uniques, const uint32_t *__restrict__ counts,
                                                                       const int32_t *__restrict__ lists, int max_product, int max_sites, RibbitRowProducts *__restrict__ out) {
     for (int64_t i = (int64_t)blockIdx.x * ROW_THREADS + threadIdx.x; i < n_pairs; i += (int64_t)gridDim.x * ROW_THREADS) {
-        RibbitRowProducts r = {};
         const int32_t ia = pairs[4 * i], ib = pairs[4 * i + 1], left_start = pairs[4 * i + 2], right_start = pairs[4 * i + 3];
-        if (ia >= 0) {
-            const uint32_t u[2] = {unique_of[ia], unique_of[ib]};
-            const int k[2] = {(int)uniques[u[0]].length, (int)uniques[u[1]].length};
-            // the lists: forward of a, forward of b; reverse of a, reverse of b
-            const uint32_t nf[2] = {counts[2 * u[0]], counts[2 * u[1]]}, nv[2] = {counts[2 * u[0] + 1], counts[2 * u[1] + 1]};
-            r.left_forward = (int32_t)nf[0];
-            r.left_reverse = (int32_t)nv[0];
-            r.right_forward = (int32_t)nf[1];
-            r.right_reverse = (int32_t)nv[1];
-            if (max(max(nf[0], nf[1]), max(nv[0], nv[1])) > (uint32_t)max_sites) {
-                r.products = -1;
-            } else {
-                int64_t shortest = INT64_MAX;
-                for (int f = 0; f < 2; ++f) {
-                    const int32_t *F = lists + (int64_t)(2 * u[f]) * max_sites;
-                    for (uint32_t j = 0; j < nf[f]; ++j) {
-                        const int64_t x = F[j];
-                        for (int v = 0; v < 2; ++v) {
-                            const int32_t *V = lists + (int64_t)(2 * u[v] + 1) * max_sites;
-                            const int n = (int)nv[v];
-                            // the reverse sites y with x + k_f <= y and y + k_v - x <= max_product
-                            const int from = below(V, n, x + k[f]), to = below(V, n, x + (int64_t)max_product - k[v] + 1);
-                            if (to <= from) continue;
-                            r.products += to - from;
-                            int first = from;
-                            if (f == 0 && v == 1 && x == left_start) {
-                                const int at = below(V, n, right_start);
-                                if (at >= from && at < to && V[at] == right_start) {
-                                    r.own = 1;
-                                    if (at == from) ++first;
-                                }
-                            }
-                            if (first < to) shortest = min(shortest, (int64_t)V[first] + k[v] - x);
-                        }
-                    }
-                }
-                r.shortest_other = shortest == INT64_MAX ? 0 : (int32_t)shortest;
-            }
-        }
-        out[i] = r;
+        out[i] = ia >= 0 ? pair_products(unique_of[ia], unique_of[ib], left_start, right_start, uniques, counts, lists, max_product, max_sites) : RibbitRowProducts{};
     }
 }
 

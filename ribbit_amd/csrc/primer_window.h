@@ -1,4 +1,4 @@
-// primer_window.h -- the front end that primers.hip and primer_pairs.hip share: one wavefront brings a window of up to `cap`
+// primer_window.h -- the front end that primers.hip, primer_pairs.hip and primer_specific.hip share: one wavefront brings a window of up to `cap`
 // bases of the loaded record into its own slice of LDS and makes the prefixes every candidate of the window is judged from
 // (include/ribbit_hip.h has the contract).  Nothing here reads the ASCII: a base's 2-bit code is 2 hi + lo of the scan's own bit
 // planes (device_planes.h: A 0, C 1, G 2, T 3), `other` is brk, and the rows' coverage is the mask's bitmap (build_coverage); bit
@@ -15,7 +15,7 @@
 // A run flag at position i looks back at most 31 positions: a candidate has at most RIBBIT_PRIMER_MAX_LENGTH = 32 bases, so
 // with max_run >= 32 no run of max_run + 1 fits into one and no flag is set.  The flags of a candidate [p, p + k) are those at
 // p + max_run .. p + k - 1, whose look-back stays inside it.
-// The wavefronts of a workgroup never wait for each other (no __syncthreads).  Included by those two .hip files only.
+// The wavefronts of a workgroup never wait for each other (no __syncthreads).  Included by those .hip files only (the latter two through primer_shortlist.h).
 #pragma once
 #include <hip/hip_runtime.h>
 

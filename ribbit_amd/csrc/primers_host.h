@@ -1,9 +1,11 @@
-// primers_host.h -- what the host sides of the primer outputs share (api_primers.cpp, api_primer_pairs.cpp, api_primer_products.cpp): the checks of
+// primers_host.h -- what the host sides of the primer outputs share (api_primers.cpp, api_primer_pairs.cpp, api_primer_products.cpp, api_primer_specific.cpp): the checks of
 // RibbitPrimerParams and of a call's arguments with their wording, a target's two windows, one candidate judged from the bytes of
 // the sequence letter by letter (the five rules and the Tm table as include/ribbit_hip.h states them), and the columns of a primer
 // and of a pair as text.  No GPU, and nothing of the kernels' packed forms.
 // Not part of the ABI; nothing outside ribbit_amd/csrc includes it.
 #pragma once
+#include <string>
+
 #include "bed_text.h"
 
 namespace rbapi {
@@ -145,5 +147,43 @@ inline void put_pair_columns(std::string &out, const RibbitRowPrimerPair &r) {
         put_number(out, v);
     }
 }
+
+// the six columns of a pair's products, each behind a tab (ribbit_bed_primer_products_text, and ribbit_bed_primer_specific_text
+// before its own four): the four counts, products - own and the shortest other product; dots in the last two when a list is
+// longer than max_sites, in all six without a pair
+inline void put_product_columns(std::string &out, const RibbitRowPrimerPair &r, const RibbitRowProducts &p) {
+    if (r.left.start < 0) {
+        for (int c = 0; c < 6; ++c) out += "\t.";
+        return;
+    }
+    for (const int32_t v : {p.left_forward, p.left_reverse, p.right_forward, p.right_reverse}) {
+        out += '\t';
+        put_number(out, v);
+    }
+    if (p.products < 0) {
+        out += "\t.\t.";
+    } else {
+        out += '\t';
+        put_number(out, p.products - p.own);
+        out += '\t';
+        put_number(out, p.shortest_other);
+    }
+}
+
+// ---- the host code behind the twins of the primer pairs and of the primer products that the twin of the specific pairs calls
+// (api_primer_specific.cpp); each is defined in the file named
+// api_primer_pairs.cpp: the check of RibbitPrimerPairParams; the rows' coverage, a byte per position; every admissible pair of a
+// target's two shortlists as the record the choice would fill for it, in the order of the choice, and the record of a target without a pair
+int check_primer_pair_params(const RibbitPrimerPairParams *p);
+std::vector<uint8_t> host_covered(int64_t length, const int32_t *intervals, size_t n);
+void host_ordered_pairs(const unsigned char *seq, const std::vector<uint8_t> &covered, const Flanks &f, const RibbitPrimerParams &prm, const RibbitPrimerPairParams &pair,
+                        std::vector<RibbitRowPrimerPair> &ordered, RibbitRowPrimerPair &none);
+// api_primer_products.cpp: the check of RibbitProductParams; a pair's two oligos as letters, 5' to 3'; the sites of an oligo on either
+// strand, ascending; the products of a pair among the sites of its two oligos
+struct HostSites { std::vector<int32_t> forward, reverse; };
+int check_primer_product_params(const RibbitProductParams *p);
+void host_pair_oligos(const RibbitRowPrimerPair &pair, std::string &a, std::string &b);
+HostSites host_oligo_sites(const unsigned char *seq, int64_t length, const std::string &oligo, const RibbitProductParams &prm);
+RibbitRowProducts host_products_among(const HostSites &a, const HostSites &b, int32_t ka, int32_t kb, int32_t left_start, int32_t right_start, const RibbitProductParams &prm);
 
 }  // namespace rbapi

@@ -13,6 +13,7 @@
 //              [--primer-bed FILE [--primer-flank F]]
 //              [--primer-pair-bed FILE [--primer-pair-flank F]]
 //              [--primer-product-bed FILE [--primer-product-flank F]]
+//              [--primer-specific-bed FILE [--primer-specific-flank F]]
 //
 // Records are independent (ribbit.cpp:269-280 handles them one after the other); here up to --jobs of them are in
 // flight at once PER GPU, each on its own handle / HIP streams, so that the upload and GPU scans of one record overlap
@@ -54,12 +55,15 @@
 // --primer-product-bed writes those rows and pairs, chosen in --primer-product-flank bases, with what each pair amplifies in its own
 // record: the places on either strand where a primer's 3' end matches exactly and the rest nearly, and the products between two of
 // them (ribbit_hip_record_primer_products, ribbit_bed_primer_products_text).
-// The BED rows are read back once per record, however many of the nineteen are asked for.
+// --primer-specific-bed writes those rows, each with the best pair of --primer-specific-flank bases on either side that amplifies
+// nothing else in its own record: all pairs of the two shortlists go through that in-silico PCR, the first specific one in the order
+// of the choice is taken (ribbit_hip_record_specific_primer_pairs, ribbit_bed_primer_specific_text).
+// The BED rows are read back once per record, however many of the twenty are asked for.
 //
-// These nineteen are the ROW OUTPUTS, and each is described once, by its entry of kOutputs below: its file option, its stage (enum
+// These twenty are the ROW OUTPUTS, and each is described once, by its entry of kOutputs below: its file option, its stage (enum
 // Stage, with the stage's names beside it), its qualifier options with their ranges and wording (defaults: Settings), and the function that
 // makes one record's text from the record's rows.  Parsing, the "needs" checks, opening the files, the sinks of the pipelined
-// records and of the last one, --timing and the RIBBIT_PROFILE line are loops over that table.  A twentieth row output is: a stage in
+// records and of the last one, --timing and the RIBBIT_PROFILE line are loops over that table.  A twenty-first row output is: a stage in
 // the enum and its names, the qualifiers' fields in Settings, a produce function, an entry of kOutputs, and its lines of kHelp.
 //
 // Reproduced quirks: -p is accepted and ignored (Q1); without -o the BED rows go to
@@ -106,14 +110,14 @@ void check(int rc) {
 }
 
 // The stages of a record: the six every record goes through, then one per row output, in the order of kOutputs.
-enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, OVERLAP, BEST, CLASSES, COMPOUND, INTERRUPTIONS, NEAREST, COMPOSITION, PRIMERS, PRIMER_PAIRS, PRIMER_PRODUCTS, N_STAGES };
+enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, OVERLAP, BEST, CLASSES, COMPOUND, INTERRUPTIONS, NEAREST, COMPOSITION, PRIMERS, PRIMER_PAIRS, PRIMER_PRODUCTS, PRIMER_SPECIFIC, N_STAGES };
 constexpr int N_FIXED_STAGES = MASK;
 // a stage's key in --timing's stage_ms_summed_over_records and its label in the RIBBIT_PROFILE line
 const struct { const char *key, *label; } kStageNames[N_STAGES] = {
     {"load", "load"}, {"perfect", "perfect"}, {"substitutions", "substitutions"}, {"anchored", "anchored"}, {"dispatch", "dispatch"},
     {"refine_and_bed", "refine+BED"}, {"mask", "mask"}, {"repeats", "repeats"}, {"loci", "loci"}, {"density", "density"}, {"overlap", "overlap"},
     {"best", "best"}, {"classes", "classes"}, {"compound", "compound"}, {"interruptions", "interruptions"}, {"nearest", "nearest"}, {"composition", "composition"}, {"primers", "primers"},
-    {"primer_pairs", "primer_pairs"}, {"primer_products", "primer_products"}};
+    {"primer_pairs", "primer_pairs"}, {"primer_products", "primer_products"}, {"primer_specific", "primer_specific"}};
 
 // wall time per stage, summed over the records (--timing, RIBBIT_PROFILE=1)
 double g_stage_ms[N_STAGES] = {};
@@ -224,6 +228,7 @@ struct Settings {
     int primer_flank = 200;              // --primer-flank F: bases on either side of a row that a primer may lie in
     int primer_pair_flank = 200;         // --primer-pair-flank F: the same for --primer-pair-bed
     int primer_product_flank = 200;      // --primer-product-flank F: the same for --primer-product-bed
+    int primer_specific_flank = 200;     // --primer-specific-flank F: the same for --primer-specific-bed
     const OtherBed *other = nullptr;         // --overlap-with FILE, read and grouped by name
 };
 
@@ -323,7 +328,7 @@ void produce_overlap_summary(RibbitHandle *h, const RecordRows &r, const Setting
     write(line.data(), line.size());
 }
 
-// the selection of a record, for --best-bed, --compound-bed, --primer-bed, --primer-pair-bed and --primer-product-bed: a later call finds what the first left in the record's rows
+// the selection of a record, for --best-bed, --compound-bed, --primer-bed, --primer-pair-bed, --primer-product-bed and --primer-specific-bed: a later call finds what the first left in the record's rows
 const RecordRows::Best &best_of(RibbitHandle *h, const RecordRows &r) {
     RecordRows::Best &b = r.best;
     if (b.have) return b;
@@ -593,6 +598,32 @@ void produce_primer_products(RibbitHandle *h, const RecordRows &r, const Setting
     ribbit_text_free(text);
 }
 
+// the selected rows again, each with the best pair of its two shortlists that amplifies nothing else in the record
+void produce_primer_specific(RibbitHandle *h, const RecordRows &r, const Settings &s, const Sink &write) {
+    StageClock c(PRIMER_SPECIFIC);
+    const RecordRows::Best &b = best_of(h, r);
+    const std::vector<int32_t> targets = targets_of(r, b);
+    RibbitPrimerParams prm;
+    ribbit_primer_params_default(&prm);
+    prm.flank = s.primer_specific_flank;
+    RibbitPrimerPairParams pair;
+    ribbit_primer_pair_params_default(&pair);
+    RibbitProductParams product;
+    ribbit_product_params_default(&product);
+    char *lines = nullptr, *text = nullptr;
+    size_t lines_len = 0, len = 0;
+    const RibbitRowPrimerPair *pairs = nullptr;
+    const RibbitRowProducts *products = nullptr;
+    const RibbitRowSpecific *specific = nullptr;
+    check(ribbit_bed_rows_text(r.bed_text, r.bed_len, b.chosen, b.n, &lines, &lines_len));
+    int rc = ribbit_hip_record_specific_primer_pairs(h, r.iv.data(), r.n(), targets.data(), b.n, &prm, &pair, &product, &pairs, &products, &specific);
+    if (rc == RIBBIT_OK) rc = ribbit_bed_primer_specific_text(lines, lines_len, pairs, products, specific, b.n, &text, &len);
+    ribbit_text_free(lines);
+    check(rc);
+    write(text, len);
+    ribbit_text_free(text);
+}
+
 // One entry per row output.  The order is the order of everything that is done for all of them: the "needs" checks, opening the
 // files (binary), producing a record's texts, the keys of --timing.
 struct Output {
@@ -603,7 +634,7 @@ struct Output {
     Qualifier qualifiers[MAX_QUALIFIERS];    // (name null: none)
     bool needs_other;                        // it compares the rows with the intervals of --overlap-with
 };
-constexpr size_t N_OUTPUTS = 19;
+constexpr size_t N_OUTPUTS = 20;
 const Output kOutputs[N_OUTPUTS] = {
     {"masked-fasta", MASK, false, produce_masked,
      {{"mask", Qualifier::SOFT_HARD, 0, 0, 0, nullptr, &Settings::mask_mode},
@@ -634,8 +665,10 @@ const Output kOutputs[N_OUTPUTS] = {
     {"primer-pair-bed", PRIMER_PAIRS, true, produce_primer_pairs,
      {{"primer-pair-flank", Qualifier::BASES, 0, RIBBIT_PRIMER_MAX_FLANK, 4, "0 .. 1000", &Settings::primer_pair_flank}, {}}, false},
     {"primer-product-bed", PRIMER_PRODUCTS, true, produce_primer_products,
-     {{"primer-product-flank", Qualifier::BASES, 0, RIBBIT_PRIMER_MAX_FLANK, 4, "0 .. 1000", &Settings::primer_product_flank}, {}}, false}};
-static_assert(RIBBIT_PRIMER_MAX_FLANK == 1000, "the range as --primer-flank's, --primer-pair-flank's and --primer-product-flank's messages and help put it");
+     {{"primer-product-flank", Qualifier::BASES, 0, RIBBIT_PRIMER_MAX_FLANK, 4, "0 .. 1000", &Settings::primer_product_flank}, {}}, false},
+    {"primer-specific-bed", PRIMER_SPECIFIC, true, produce_primer_specific,
+     {{"primer-specific-flank", Qualifier::BASES, 0, RIBBIT_PRIMER_MAX_FLANK, 4, "0 .. 1000", &Settings::primer_specific_flank}, {}}, false}};
+static_assert(RIBBIT_PRIMER_MAX_FLANK == 1000, "the range as --primer-flank's, --primer-pair-flank's, --primer-product-flank's and --primer-specific-flank's messages and help put it");
 
 // the row outputs that are on, by stage: an output whose stage an earlier one has already named is left out (--timing, RIBBIT_PROFILE)
 std::vector<Stage> stages_on(const std::array<bool, N_OUTPUTS> &on) {
@@ -810,6 +843,17 @@ const char *kHelp =
     "                                searched, not the other records of the input: for a genome, ask Scanner.record_oligo_sites\n"
     "                                of the Python package record by record and add up\n"
     "  --primer-product-flank arg    (ribbit-hip) bases of the record on either side of a row that --primer-product-bed may\n"
+    "                                place a primer in, 0 .. 1000. Default: 200\n"
+    "  --primer-specific-bed arg     (ribbit-hip) also write the rows of --best-bed's selection to this file with 31 columns\n"
+    "                                appended: the 27 of --primer-product-bed, but for the best pair that amplifies nothing\n"
+    "                                else. All pairs of the 8 best candidates of either flank that --primer-pair-bed would\n"
+    "                                admit go through that in-silico PCR, in the order of its choice, and the first one without\n"
+    "                                another product is taken; there is no fallback. Then: the place of that pair in the order\n"
+    "                                (0: --primer-pair-bed's own pair), the specific pairs, the pairs with a primer of more\n"
+    "                                than 64 sites on a strand, the pairs with another product ('.' in the first 18, in the six\n"
+    "                                of the PCR and in the place where no pair is specific). Only the record itself is\n"
+    "                                searched, not the other records of the input\n"
+    "  --primer-specific-flank arg   (ribbit-hip) bases of the record on either side of a row that --primer-specific-bed may\n"
     "                                place a primer in, 0 .. 1000. Default: 200\n";
 
 bool parse_device_list(const std::string &value, std::vector<int> &out) {

@@ -1,5 +1,5 @@
 // row_kernels.h -- what the kernels of the row outputs (overlap.hip, best.hip, classes.hip, compound.hip, interruptions.hip,
-// nearest.hip, composition.hip, primers.hip, primer_pairs.hip) write the same way: the shape of a launch, a row clipped to the record, a sum over a wavefront, the
+// nearest.hip, composition.hip, primers.hip, primer_pairs.hip, primer_products.hip, primer_specific.hip) write the same way: the shape of a launch, a row clipped to the record, a sum over a wavefront, the
 // bits a sort key of positions needs.  Included by .hip files only.
 #pragma once
 #include <hip/hip_runtime.h>
