@@ -847,8 +847,8 @@ int ribbit_bed_primers_text(const char *bed_text, size_t bed_len, const RibbitRo
  * The same windows, blocked positions, five admissibility rules, Tm and penalty as above, with the same RibbitPrimerParams;
  * on top of them an ungapped model of an oligo that binds to itself or to its partner, and the choice of the two primers of a
  * target as one pair.  Everything is integer arithmetic on the oligos' letters.  Gapped or thermodynamic (dG) dimer models,
- * bounds on the product's size and priming in other records are not part of it; priming elsewhere in the record is the in-silico PCR
- * below.
+ * bounds on the product's size are not part of it; priming elsewhere in the record is the in-silico PCR below, priming in the other
+ * records of the input the genome-wide choice behind it.
  *   Oligos:     an oligo is read 5' to 3'.  The left primer is its candidate's forward-strand bases, the right primer the reverse
  *               complement of its candidate's forward-strand bases (the text ribbit_bed_primers_text prints).  Bases x and y are
  *               bonded when y is the complement of x: with the codes A 0, C 1, G 2, T 3, when x ^ y == 3.
@@ -927,8 +927,9 @@ int ribbit_bed_primer_pairs_text(const char *bed_text, size_t bed_len, const Rib
  * ---- in-silico PCR: where else in the record an oligo primes, and what a primer pair amplifies there ----------------------
  * The check Primer-BLAST, UCSC isPCR, e-PCR and MFEprimer make before a pair is ordered, for the loaded record: every place
  * on either strand where an oligo's 3' end matches exactly and the rest of it nearly, and every two such places of a pair's
- * primers that face each other within a product size.  Everything is integer arithmetic on letters.  Other records of the
- * input, gapped alignments and thermodynamic binding are not part of it.
+ * primers that face each other within a product size.  Everything is integer arithmetic on letters.  Gapped
+ * alignments and thermodynamic binding are not part of it; the other records of the input are judged by
+ * ribbit_hip_record_shortlist_verdicts, below, with this contract on each.
  *   Letters:    codes A 0, C 1, G 2, T 3, case ignored; any other byte is `other`, as the record is packed (the brk plane).
  *   Oligo:      o has k bases, is read 5' to 3', 1 <= k <= 32; q = revcomp(o), q[j] = 3 - o[k - 1 - j].
  *   Sites:      with s = seed and d = max_mismatches, on the record R[0, L): o has a FORWARD SITE at x when 0 <= x and
@@ -1013,7 +1014,8 @@ int ribbit_bed_primer_products_text(const char *bed_text, size_t bed_len, const 
  * ---- the best primer pair of every target that amplifies nothing else in the record ----------------------------------------
  * The two contracts above put together: where ribbit_hip_record_primer_pairs takes the best admissible pair of the two
  * shortlists and ribbit_hip_record_primer_products says what that one pair amplifies, this takes the best admissible pair that
- * is specific.  Everything is integer arithmetic on letters; nothing is added to either contract.
+ * is specific.  Everything is integer arithmetic on letters; nothing is added to either contract.  Only the loaded record is
+ * searched; the same choice over all records of an input is the section behind this one.
  *   Shortlists: candidates, shortlists and the admissible pairs of a target are exactly steps (1) to (3) of the selection.
  *   Order:      the admissible pairs in the order of step (4)'s key, (penalty_l + penalty_r + |Tm_l - Tm_r|, product, rank_l,
  *               rank_r); no two pairs share a key.  A pair's PLACE is its 0-based position in that order.
@@ -1072,6 +1074,90 @@ int ribbit_hip_debug_set_specific_batch(RibbitHandle *h, size_t targets);
  * malloc'ed, release with ribbit_text_free(). */
 int ribbit_bed_primer_specific_text(const char *bed_text, size_t bed_len, const RibbitRowPrimerPair *pairs, const RibbitRowProducts *products,
                                     const RibbitRowSpecific *specific, size_t n, char **text, size_t *len);
+
+/*
+ * ---- the best primer pair of every target that amplifies nothing in any record of a genome ---------------------------------
+ * The specific primer pairs above search the record a target lies on.  Here a target's two shortlists leave that record, are
+ * judged on every record of the input, and the judgements are summed.  Everything is integer arithmetic on letters; nothing is
+ * added to the three contracts above.
+ *   Genome:     the records R_0 .. R_{n-1} of the input.  A target belongs to its HOME record R_h.  Home is a matter of position
+ *               in the input, not of name: two records with one name are two records.
+ *   Shortlists: a target's shortlists, its admissible pairs and their order are exactly steps (1) to (3) of the selection and
+ *               the order of the specific contract, made on the home record against the home record's rows.
+ *   Judgement:  on one record R_k an admissible pair (l, r) is judged by the in-silico PCR contract on R_k with the same a and b.
+ *               Only when k = h does the own product exist (a forward at the left candidate's start, b reverse at the right
+ *               candidate's start); on any other record no product is the pair's own.  The pair is OVER on R_k when one of
+ *               its four site lists on R_k is longer than max_sites; otherwise its others on R_k are products - own.
+ *   Sum:        over all records the pair is OVER when it is over on any record; otherwise OTHER when its others, summed over
+ *               the records, are above 0; otherwise SPECIFIC.
+ *   Choice:     the chosen pair is the first specific pair in the order.  There is no fallback.
+ *   One record: with n = 1 this is the specific primer pair contract, field by field.
+ *   max_sites:  holds per record: it is the longest list that is kept on one record, not a limit on a genome's total.  A site
+ *               count summed over the records may therefore exceed max_sites without the pair being over.
+ *   Values:     R_0 = the undisturbed record of the specific contract's values, the target (1500, 1540), no rows, the defaults;
+ *               R_1 = B, 4,000 other random bases (tests/primer_genome_contract.py builds the genomes and computes the values
+ *               from a plain statement of the above).  As (place, pairs_admissible, pairs_specific, pairs_over, pairs_other,
+ *               first_products) and the chosen pair's (left start, left length, right start, right length):
+ *                 R_1 = B                                                      (0, 44, 44, 0, 0, 0)     (1304, 22, 1624, 21)
+ *                 B with R_0's best pair's two windows at 3000 and 60 behind   (2, 44, 30, 0, 14, 1)    (1304, 22, 1613, 22)
+ *                 B with R_0[1300:1500] at 2600 and R_0[1540:1740] at 2800     (-1, 44, 0, 0, 44, 1)    no pair
+ *               Within one record the same two constructions give 18 other and first_products 2: a copy in another record
+ *               cannot form a product with the original.
+ */
+typedef struct {
+    RibbitPrimer left[8], right[8];           /* by rank; an empty place has start -1 and zeros; the held places are the first ones */
+    int32_t left_candidates, right_candidates, left_passed, right_passed;
+} RibbitTargetShortlists;                     /* 100 ints, 400 bytes */
+typedef struct {
+    uint64_t admissible, over, other, own;    /* bit 8 l + r for the pair (l, r) of the two shortlists */
+    int32_t forward[16], reverse[16];         /* the sites of left[0..7], then of right[0..7] as ordered; 0 for an empty place; exact */
+    int32_t first_others;                     /* of the pair in place 0: -1 over, else products - own; 0 without an admissible pair */
+    int32_t records, home_records;            /* records judged; how many of them as home */
+    int32_t reserved;                         /* 0 */
+} RibbitTargetVerdicts;                       /* 176 bytes */
+/* The two shortlists of the loaded record's n_targets targets against the coverage of its n rows, on the GPU (the lists
+ * ribbit_hip_record_specific_primer_pairs makes internally, handed out): *lists is one record per target, in the order given, of
+ * handle-owned page-locked memory, valid until the handle's next call of this function, load or close.  States and refusals are
+ * those of ribbit_hip_record_primer_pairs.  n_targets = 0 and L = 0 are no errors. */
+int ribbit_hip_record_primer_shortlists(RibbitHandle *h, const int32_t *intervals, size_t n, const int32_t *targets, size_t n_targets,
+                                        const RibbitPrimerParams *params, const RibbitPrimerPairParams *pair_params,
+                                        const RibbitTargetShortlists **lists);
+/* Every target's admissible pairs judged on the loaded record, which may be any record, on the GPU (primer_specific.hip):
+ * home is 1 when the loaded record is the one the lists were made on, else 0.  `admissible` comes from the lists alone, by
+ * step (3); over, other and own are subsets of it; records is 1 and home_records is home.  Targets go in batches by the rule of
+ * ribbit_hip_record_specific_primer_pairs (ribbit_hip_debug_set_specific_batch is obeyed); the result does not depend on the
+ * batches.  *verdicts is handle-owned page-locked memory, valid until the handle's next call of this function, load or close.
+ * Malformed lists (a held place behind an empty one, a length below `seed` or above 32, more held places than
+ * pair_params->shortlist) are RIBBIT_E_ARG, and the error text names the target's index; a parameter field outside its range
+ * is RIBBIT_E_ARG and the text names the field; before a load: RIBBIT_E_STATE.  n_targets = 0 and L = 0 are no errors: with
+ * L = 0 there are no sites, and `admissible` is still filled. */
+int ribbit_hip_record_shortlist_verdicts(RibbitHandle *h, const RibbitTargetShortlists *lists, size_t n_targets, int32_t home,
+                                         const RibbitPrimerPairParams *pair_params, const RibbitProductParams *product_params,
+                                         const RibbitTargetVerdicts **verdicts);
+/* Host-only twins (no GPU), from the bytes of `sequence` (0 <= length < 2^31), letter by letter: *lists and *verdicts malloc'ed,
+ * release with ribbit_primer_genome_free(). */
+int ribbit_host_record_primer_shortlists(const char *sequence, int64_t length, const int32_t *intervals, size_t n, const int32_t *targets,
+                                         size_t n_targets, const RibbitPrimerParams *params, const RibbitPrimerPairParams *pair_params,
+                                         RibbitTargetShortlists **lists);
+int ribbit_host_record_shortlist_verdicts(const char *sequence, int64_t length, const RibbitTargetShortlists *lists, size_t n_targets,
+                                          int32_t home, const RibbitPrimerPairParams *pair_params,
+                                          const RibbitProductParams *product_params, RibbitTargetVerdicts **verdicts);
+/* The sum over records (host only): into[i] becomes the verdicts of into[i]'s and from[i]'s records together.  `admissible` must
+ * be equal, else RIBBIT_E_ARG and the text names the index (nothing is changed then); over, other and own are OR-ed; the site
+ * counts, records and home_records are added and saturate at INT32_MAX; first_others is -1 if either side's is -1, else the
+ * saturating sum. */
+int ribbit_primer_verdicts_merge(RibbitTargetVerdicts *into, const RibbitTargetVerdicts *from, size_t n);
+/* The choice (host only): per target the admissible pairs of its lists in the order, the first one outside over | other.  *pairs
+ * is that pair's record exactly as ribbit_hip_record_specific_primer_pairs would fill it (ranks, the five dimer values, the six
+ * counts); *products its four site counts from forward and reverse, own its bit, products equal to own, shortest_other 0 (eight
+ * zeros without a pair); *specific the popcounts of the three classes (a pair that is over on one record and other on another is
+ * over), place, and first_products = first_others.  Verdicts whose home_records is not 1, whose `admissible` is not that of the
+ * lists, and malformed lists are RIBBIT_E_ARG with the target's index.  The three arrays are malloc'ed, release each with
+ * ribbit_primer_genome_free(); ribbit_bed_primer_specific_text prints them as they are. */
+int ribbit_primer_shortlists_choose(const RibbitTargetShortlists *lists, const RibbitTargetVerdicts *verdicts, size_t n,
+                                    const RibbitPrimerPairParams *pair_params, RibbitRowPrimerPair **pairs,
+                                    RibbitRowProducts **products, RibbitRowSpecific **specific);
+void ribbit_primer_genome_free(void *from_a_host_function);
 
 /*
  * ---- streaming FASTA ingest ---------------------------------------------------------------------------------------

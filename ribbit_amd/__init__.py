@@ -34,7 +34,9 @@ __all__ = ["RibbitHipError", "ScanParams", "Scanner", "library_path", "load_libr
            "PRIMER_PAIRS_DT", "PrimerPairParams", "primer_pair_params", "host_record_primer_pairs", "bed_primer_pairs_text", "oligo_duplex", "oligo_hairpin",
            "PRIMER_PRODUCTS_DT", "OLIGO_SITES_DT", "ProductParams", "product_params", "host_record_oligo_sites", "host_record_primer_products",
            "bed_primer_products_text",
-           "PRIMER_SPECIFIC_DT", "host_record_specific_primer_pairs", "bed_primer_specific_text"]
+           "PRIMER_SPECIFIC_DT", "host_record_specific_primer_pairs", "bed_primer_specific_text",
+           "PRIMER_SHORTLISTS_DT", "PRIMER_VERDICTS_DT", "host_record_primer_shortlists", "host_record_shortlist_verdicts", "primer_verdicts_merge",
+           "primer_shortlists_choose"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -68,6 +70,11 @@ PRIMER_PRODUCTS_DT = np.dtype([(n, "<i4") for n in ("left_forward", "left_revers
                                                      "reserved")])      # RibbitRowProducts
 PRIMER_SPECIFIC_DT = np.dtype([(n, "<i4") for n in ("place", "pairs_admissible", "pairs_specific", "pairs_over", "pairs_other", "first_products", "reserved0",
                                                      "reserved1")])      # RibbitRowSpecific
+_PRIMER_DT = np.dtype([(n, "<i4") for n in ("start", "length", "tm", "penalty", "bases_lo", "bases_hi")])      # RibbitPrimer
+PRIMER_SHORTLISTS_DT = np.dtype([("left", _PRIMER_DT, (8,)), ("right", _PRIMER_DT, (8,))]
+                                + [(n, "<i4") for n in ("left_candidates", "right_candidates", "left_passed", "right_passed")])      # RibbitTargetShortlists
+PRIMER_VERDICTS_DT = np.dtype([(n, "<u8") for n in ("admissible", "over", "other", "own")] + [("forward", "<i4", (16,)), ("reverse", "<i4", (16,))]
+                              + [(n, "<i4") for n in ("first_others", "records", "home_records", "reserved")])      # RibbitTargetVerdicts
 OLIGO_SITES_DT = np.dtype([(n, "<i4") for n in ("forward", "reverse", "forward_at", "reverse_at")])      # RibbitOligoSites
 _OLIGO_DT = np.dtype([(n, "<i4") for n in ("length", "bases_lo", "bases_hi")])      # RibbitOligo
 _I4 = np.dtype("<i4")
@@ -272,6 +279,8 @@ def _signatures() -> dict:
         "ribbit_base_windows_text": (st, [cp, i64, i32, vp, sz, pvp, psz]),
         "ribbit_bed_primer_products_text": (st, [cp, sz, vp, vp, sz, pvp, psz]),
         "ribbit_bed_primer_specific_text": (st, [cp, sz, vp, vp, vp, sz, pvp, psz]),
+        "ribbit_primer_verdicts_merge": (st, [vp, vp, sz]),
+        "ribbit_primer_shortlists_choose": (st, [vp, vp, sz, P(PrimerPairParams), pvp, pvp, pvp]),
     }
     for name in ("ribbit_hip_scan_perfect_runs", "ribbit_hip_perfect_calls", "ribbit_hip_seeds_perfect", "ribbit_hip_subst_calls",
                  "ribbit_hip_anchored_calls", "ribbit_hip_dispatch_seeds", "ribbit_hip_seed_longest_runs"):
@@ -284,7 +293,8 @@ def _signatures() -> dict:
         t[name] = (st, [cp, sz, vp, sz, pvp, psz])           # BED text, an array with a record per row
     for name in ("ribbit_text_free", "ribbit_runs_free", "ribbit_intervals_free", "ribbit_loci_free", "ribbit_motif_classes_free",
                  "ribbit_compounds_free", "ribbit_row_purity_free", "ribbit_interruptions_free", "ribbit_nearest_free", "ribbit_composition_free",
-                 "ribbit_primers_free", "ribbit_primer_pairs_free", "ribbit_products_free", "ribbit_primer_specific_free"):
+                 "ribbit_primers_free", "ribbit_primer_pairs_free", "ribbit_products_free", "ribbit_primer_specific_free",
+                 "ribbit_primer_genome_free"):
         t[name] = (None, [vp])
     # the row outputs: the device form takes the handle, the host form the record's length, or its bases and their number
     length, bases = [i64], [cp, i64]
@@ -300,6 +310,8 @@ def _signatures() -> dict:
                              ("record_oligo_sites", bases, [vp, sz, P(ProductParams), pvp, pvp, psz]),
                              ("record_primer_products", bases, [vp, sz, P(ProductParams), pvp]),
                              ("record_specific_primer_pairs", bases, [vp, sz, vp, sz, P(PrimerParams), P(PrimerPairParams), P(ProductParams), pvp, pvp, pvp]),
+                             ("record_primer_shortlists", bases, [vp, sz, vp, sz, P(PrimerParams), P(PrimerPairParams), pvp]),
+                             ("record_shortlist_verdicts", bases, [vp, sz, i32, P(PrimerPairParams), P(ProductParams), pvp]),
                              ("record_best", length, [vp, sz, pvp, psz, P(i64)]),
                              ("record_classes", length, [vp, sz, vp, vp, pvp, pvp, pvp, psz]),
                              ("record_compounds", length, [vp, vp, sz, i32, pvp, psz, pvp, psz]),
@@ -921,6 +933,64 @@ def host_record_specific_primer_pairs(sequence: bytes, intervals, targets, param
     order, the admissible pairs by outcome and what the pair in place 0 amplifies besides its own product).  The contract is in
     include/ribbit_hip.h.  No GPU needed."""
     return _record_specific_primer_pairs(_host_bases("ribbit_host_record_specific_primer_pairs", sequence), intervals, targets, params, pair_params, product_params)
+
+
+def _record_primer_shortlists(call, intervals, targets, params, pair_params) -> np.ndarray:
+    iv, tg = _pairs(intervals), _pairs(targets)
+    params = _params_arg(params, primer_params, PrimerParams)
+    pair_params = _params_arg(pair_params, primer_pair_params, PrimerPairParams, "pair_params")
+    return _array(call, _ptr(iv), len(iv), _ptr(tg), len(tg), C.byref(params), C.byref(pair_params), dt=PRIMER_SHORTLISTS_DT, free="ribbit_primer_genome_free",
+                  count=len(tg))
+
+
+def host_record_primer_shortlists(sequence: bytes, intervals, targets, params: PrimerParams | None = None, pair_params: PrimerPairParams | None = None) -> np.ndarray:
+    """ribbit_host_record_primer_shortlists: for every (start, end) target the two shortlists that host_record_specific_primer_pairs
+    makes internally, in a form that leaves the record: up to 8 primers a side by rank (an empty place has start -1) and the side
+    counts -> a PRIMER_SHORTLISTS_DT array, one record per target.  The contract is in include/ribbit_hip.h.  No GPU needed."""
+    return _record_primer_shortlists(_host_bases("ribbit_host_record_primer_shortlists", sequence), intervals, targets, params, pair_params)
+
+
+def _record_shortlist_verdicts(call, lists, home, pair_params, product_params) -> np.ndarray:
+    ls = _records(lists, PRIMER_SHORTLISTS_DT)
+    pair_params = _params_arg(pair_params, primer_pair_params, PrimerPairParams, "pair_params")
+    product_params = _params_arg(product_params, globals()["product_params"], ProductParams, "product_params")
+    return _array(call, _ptr(ls), len(ls), _int32(home, "home"), C.byref(pair_params), C.byref(product_params), dt=PRIMER_VERDICTS_DT,
+                  free="ribbit_primer_genome_free", count=len(ls))
+
+
+def host_record_shortlist_verdicts(sequence: bytes, lists, home, pair_params: PrimerPairParams | None = None, product_params: ProductParams | None = None) -> np.ndarray:
+    """ribbit_host_record_shortlist_verdicts: every admissible pair of every target's shortlists (a PRIMER_SHORTLISTS_DT array) judged
+    by the in-silico PCR on `sequence`, which may be any record; home (0 or 1): whether it is the record the lists were made on, where
+    alone a pair's own product exists -> a PRIMER_VERDICTS_DT array: the admissible, over, other and own pairs as masks (bit 8 l + r),
+    the sites of the 16 places, what the pair in place 0 amplifies besides its own product.  Sum them over the records of a genome with
+    primer_verdicts_merge and choose with primer_shortlists_choose.  The contract is in include/ribbit_hip.h.  No GPU needed."""
+    return _record_shortlist_verdicts(_host_bases("ribbit_host_record_shortlist_verdicts", sequence), lists, home, pair_params, product_params)
+
+
+def primer_verdicts_merge(into, other) -> np.ndarray:
+    """ribbit_primer_verdicts_merge: the verdicts of two sets of records together -> a new PRIMER_VERDICTS_DT array (neither argument
+    is changed): the masks OR-ed, the counts added; `admissible` must be equal target by target"""
+    a, b = _records(into, PRIMER_VERDICTS_DT).copy(), _records(other, PRIMER_VERDICTS_DT)
+    if len(a) != len(b):
+        raise ValueError(f"{len(a)} and {len(b)} verdicts")
+    _call("ribbit_primer_verdicts_merge", _ptr(a), _ptr(b), len(a))
+    return a
+
+
+def primer_shortlists_choose(lists, verdicts, pair_params: PrimerPairParams | None = None):
+    """ribbit_primer_shortlists_choose: per target the first admissible pair of its lists, in the order of the choice, that is neither
+    over nor other in the summed verdicts -> (a PRIMER_PAIRS_DT, a PRIMER_PRODUCTS_DT and a PRIMER_SPECIFIC_DT array) as
+    host_record_specific_primer_pairs gives them, every count and verdict over all judged records; bed_primer_specific_text prints them"""
+    ls, vd = _records(lists, PRIMER_SHORTLISTS_DT), _records(verdicts, PRIMER_VERDICTS_DT)
+    if len(ls) != len(vd):
+        raise ValueError(f"{len(ls)} lists and {len(vd)} verdicts")
+    pair_params = _params_arg(pair_params, primer_pair_params, PrimerPairParams, "pair_params")
+    pairs, products, specific = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    owned = _call("ribbit_primer_shortlists_choose", _ptr(ls), _ptr(vd), len(ls), C.byref(pair_params), C.byref(pairs), C.byref(products), C.byref(specific))
+    try:
+        return _copy(pairs.value, len(ls), PRIMER_PAIRS_DT), _copy(products.value, len(ls), PRIMER_PRODUCTS_DT), _copy(specific.value, len(ls), PRIMER_SPECIFIC_DT)
+    finally:
+        _free(owned, "ribbit_primer_genome_free", pairs, products, specific)
 
 
 def _record_best(call, intervals):
@@ -1618,6 +1688,17 @@ class Scanner:
         two shortlists judged by an in-silico PCR, a wavefront per target (ribbit_hip_record_specific_primer_pairs); see
         host_record_specific_primer_pairs"""
         return _record_specific_primer_pairs(self._dev("ribbit_hip_record_specific_primer_pairs"), intervals, targets, params, pair_params, product_params)
+
+    def record_primer_shortlists(self, intervals, targets, params: PrimerParams | None = None, pair_params: PrimerPairParams | None = None) -> np.ndarray:
+        """The two shortlists of every target of the loaded record, on the GPU, in a form that leaves the record
+        (ribbit_hip_record_primer_shortlists); see host_record_primer_shortlists"""
+        return _record_primer_shortlists(self._dev("ribbit_hip_record_primer_shortlists"), intervals, targets, params, pair_params)
+
+    def record_shortlist_verdicts(self, lists, home, pair_params: PrimerPairParams | None = None, product_params: ProductParams | None = None) -> np.ndarray:
+        """Every admissible pair of every target's shortlists judged on the loaded record, which may be any record, on the GPU: one
+        site scan per batch of targets, a wavefront per target (ribbit_hip_record_shortlist_verdicts); see
+        host_record_shortlist_verdicts"""
+        return _record_shortlist_verdicts(self._dev("ribbit_hip_record_shortlist_verdicts"), lists, home, pair_params, product_params)
 
     def record_best(self, intervals):
         """The loaded record's best non-overlapping rows on the GPU (ribbit_hip_record_best); see host_record_best"""

@@ -186,15 +186,10 @@ RibbitPrimer primer_of(const unsigned char *seq, const Listed &it) {
     return RibbitPrimer{(int32_t)it.p, it.k, it.tm, it.penalty, (int32_t)(uint32_t)bases, (int32_t)(uint32_t)(bases >> 32)};
 }
 
-// every admissible pair of the target's two shortlists, each as the record the choice would fill for it, in the order of step (4);
-// none: the record of a target without a pair (the six counts; pairs_admissible is the others' too)
-void ordered_pairs_of(const unsigned char *seq, const std::vector<uint8_t> &covered, const Flanks &f, const RibbitPrimerParams &prm, const RibbitPrimerPairParams &pair,
-                      std::vector<RibbitRowPrimerPair> &ordered, RibbitRowPrimerPair &none) {
-    std::vector<Listed> left, right;
-    int32_t n_left, n_right, p_left, p_right;
-    side(seq, covered, f.lo, f.s, false, prm, pair, left, n_left, p_left);
-    side(seq, covered, f.e, f.hi, true, prm, pair, right, n_right, p_right);
-    none = no_pair(n_left, n_right, p_left, p_right, (int32_t)(left.size() * right.size()));
+// every admissible pair of two shortlists, whose primers as records are lp and rp, each as the record the choice would fill for it,
+// in the order of step (4); none: the record of a target without a pair (the six counts; pairs_admissible is the others' too)
+void pairs_among(const std::vector<Listed> &left, const std::vector<Listed> &right, const std::vector<RibbitPrimer> &lp, const std::vector<RibbitPrimer> &rp,
+                 const RibbitPrimerPairParams &pair, std::vector<RibbitRowPrimerPair> &ordered, RibbitRowPrimerPair &none) {
     ordered.clear();
     for (int32_t l = 0; l < (int32_t)left.size(); ++l)
         for (int32_t r = 0; r < (int32_t)right.size(); ++r) {
@@ -204,8 +199,8 @@ void ordered_pairs_of(const unsigned char *seq, const std::vector<uint8_t> &cove
             const Duplex d = duplex(a.oligo, b.oligo);
             if (d.any > pair.max_pair_any || d.end > pair.max_pair_end) continue;
             RibbitRowPrimerPair out = none;
-            out.left = primer_of(seq, a);
-            out.right = primer_of(seq, b);
+            out.left = lp[(size_t)l];
+            out.right = rp[(size_t)r];
             out.pair_penalty = a.penalty + b.penalty + difference;
             out.tm_difference = difference;
             out.product = (int32_t)(b.p + b.k - a.p);
@@ -225,6 +220,44 @@ void ordered_pairs_of(const unsigned char *seq, const std::vector<uint8_t> &cove
     std::sort(ordered.begin(), ordered.end(), [&](const RibbitRowPrimerPair &x, const RibbitRowPrimerPair &y) { return key(x) < key(y); });
     none.pairs_admissible = (int32_t)ordered.size();
     for (RibbitRowPrimerPair &r : ordered) r.pairs_admissible = none.pairs_admissible;
+}
+
+struct Shortlists {
+    std::vector<Listed> left, right;
+    std::vector<RibbitPrimer> lp, rp;
+    RibbitRowPrimerPair none;
+};
+
+// a target's two shortlists from the bytes of the sequence
+void shortlists_of(const unsigned char *seq, const std::vector<uint8_t> &covered, const Flanks &f, const RibbitPrimerParams &prm, const RibbitPrimerPairParams &pair,
+                   Shortlists &s) {
+    int32_t n_left, n_right, p_left, p_right;
+    side(seq, covered, f.lo, f.s, false, prm, pair, s.left, n_left, p_left);
+    side(seq, covered, f.e, f.hi, true, prm, pair, s.right, n_right, p_right);
+    s.none = no_pair(n_left, n_right, p_left, p_right, (int32_t)(s.left.size() * s.right.size()));
+    s.lp.clear();
+    s.rp.clear();
+    for (const Listed &it : s.left) s.lp.push_back(primer_of(seq, it));
+    for (const Listed &it : s.right) s.rp.push_back(primer_of(seq, it));
+}
+
+void ordered_pairs_of(const unsigned char *seq, const std::vector<uint8_t> &covered, const Flanks &f, const RibbitPrimerParams &prm, const RibbitPrimerPairParams &pair,
+                      std::vector<RibbitRowPrimerPair> &ordered, RibbitRowPrimerPair &none) {
+    Shortlists s;
+    shortlists_of(seq, covered, f, prm, pair, s);
+    none = s.none;
+    pairs_among(s.left, s.right, s.lp, s.rp, pair, ordered, none);
+}
+
+// a stored primer as the twin lists it: its oligo from its packed bases, the self values from the oligo's letters
+Listed listed_of(const RibbitPrimer &p, bool right) {
+    const uint64_t bases = (uint64_t)(uint32_t)p.bases_hi << 32 | (uint32_t)p.bases_lo;
+    std::string o;
+    for (int32_t j = 0; j < p.length; ++j) o += right ? "TGCA"[(bases >> (2 * (p.length - 1 - j))) & 3] : "ACGT"[(bases >> (2 * j)) & 3];
+    Listed it{p.penalty, p.length, p.tm, 0, p.start, o, {0, 0}, 0};
+    it.self = duplex(it.oligo, it.oligo);
+    it.hairpin = hairpin(it.oligo);
+    return it;
 }
 
 RibbitRowPrimerPair pair_of(const unsigned char *seq, const std::vector<uint8_t> &covered, const Flanks &f, const RibbitPrimerParams &prm, const RibbitPrimerPairParams &pair) {
@@ -299,6 +332,43 @@ std::vector<uint8_t> host_covered(int64_t length, const int32_t *intervals, size
 void host_ordered_pairs(const unsigned char *seq, const std::vector<uint8_t> &covered, const Flanks &f, const RibbitPrimerParams &prm, const RibbitPrimerPairParams &pair,
                         std::vector<RibbitRowPrimerPair> &ordered, RibbitRowPrimerPair &none) {
     ordered_pairs_of(seq, covered, f, prm, pair, ordered, none);
+}
+
+void host_target_shortlists(const unsigned char *seq, const std::vector<uint8_t> &covered, const Flanks &f, const RibbitPrimerParams &prm, const RibbitPrimerPairParams &pair,
+                            RibbitTargetShortlists &out) {
+    Shortlists s;
+    shortlists_of(seq, covered, f, prm, pair, s);
+    for (size_t k = 0; k < (size_t)RIBBIT_PRIMER_PAIR_SHORTLIST; ++k) {
+        out.left[k] = k < s.lp.size() ? s.lp[k] : NO_PRIMER;
+        out.right[k] = k < s.rp.size() ? s.rp[k] : NO_PRIMER;
+    }
+    out.left_candidates = s.none.left_candidates;
+    out.right_candidates = s.none.right_candidates;
+    out.left_passed = s.none.left_passed;
+    out.right_passed = s.none.right_passed;
+}
+
+int host_held_places(const RibbitPrimer *side) {
+    int held = 0;
+    while (held < RIBBIT_PRIMER_PAIR_SHORTLIST && side[held].start >= 0) ++held;
+    return held;
+}
+
+std::string host_listed_oligo(const RibbitPrimer &p, bool right) { return listed_of(p, right).oligo; }
+
+void host_listed_pairs(const RibbitTargetShortlists &lists, const RibbitPrimerPairParams &pair, std::vector<RibbitRowPrimerPair> &ordered, RibbitRowPrimerPair &none) {
+    Shortlists s;
+    const int n_left = host_held_places(lists.left), n_right = host_held_places(lists.right);
+    for (int k = 0; k < n_left; ++k) {
+        s.lp.push_back(lists.left[k]);
+        s.left.push_back(listed_of(lists.left[k], false));
+    }
+    for (int k = 0; k < n_right; ++k) {
+        s.rp.push_back(lists.right[k]);
+        s.right.push_back(listed_of(lists.right[k], true));
+    }
+    none = no_pair(lists.left_candidates, lists.right_candidates, lists.left_passed, lists.right_passed, n_left * n_right);
+    pairs_among(s.left, s.right, s.lp, s.rp, pair, ordered, none);
 }
 
 }  // namespace rbapi

@@ -264,6 +264,9 @@ int bed_primer_specific_text_impl(const char *bed, size_t bed_len, const RibbitR
 
 }  // namespace
 
+// ---- what api_primer_genome.cpp takes from here (primers_host.h)
+size_t rbapi::specific_batch_targets(const RibbitHandle *h, const RibbitProductParams &product) { return batch_targets(h, product); }
+
 extern "C" {
 
 int ribbit_hip_record_specific_primer_pairs(RibbitHandle *h, const int32_t *intervals, size_t n, const int32_t *targets, size_t n_targets, const RibbitPrimerParams *params,

@@ -563,6 +563,29 @@ hipError_t launch_primer_shortlists(const DevicePlanes &pl, const uint32_t *bits
 hipError_t launch_specific_pairs(int64_t n_targets, const RibbitPrimerPairParams &pair, const RibbitProductParams &product, uint8_t *work, size_t work_bytes,
                                  const SpecificLayout &at, const int32_t *site_lists, hipStream_t stream);
 
+// ... and the admissible pairs of n_targets >= 1 targets' uploaded shortlists judged on the loaded record (length > 0), which need
+// not be the record they were made on (api_primer_genome.cpp: ribbit_hip_record_shortlist_verdicts).  lists: 16 RibbitPrimer per
+// target on the device, as SpecificLayout::lists holds them, checked by the caller (the held places first, 1 .. 32 bases each).  A
+// batch takes the launches in this order, and the host reads `header` and primer_products.hip's header between them:
+//   launch_listed_oligos       the held places of every target counted, and their primers as oligos one behind the other, the right
+//                              ones as ordered, without primer_shortlists_kernel; header.oligos = N
+//   launch_product_uniques, launch_product_scan   as above; none of them when N == 0
+//   launch_shortlist_verdicts  one RibbitTargetVerdicts per target; home: the own product exists on this record
+struct VerdictLayout : WorkLayout {
+    size_t n_oligos;      // the held places of every target | their inclusive sum, n_targets words each
+    size_t n_left;        // the held places of every target's left shortlist
+    size_t oligos;        // the held primers as RibbitOligo, a target's one behind the other, 16 n_targets at most
+    size_t header;        // SpecificHeader
+    size_t verdicts;      // the result, n_targets records
+    size_t product_work;  // the work buffer of primer_products.hip's launches for 16 n_targets oligos ...
+    ProductLayout product;              // ... and its layout (offsets from product_work)
+};
+VerdictLayout verdict_layout(int64_t n_targets);
+hipError_t launch_listed_oligos(const RibbitPrimer *lists, int64_t n_targets, uint8_t *work, size_t work_bytes, const VerdictLayout &at, hipStream_t stream);
+// site_lists: what launch_product_scan filled (not read when no target of the batch has an admissible pair)
+hipError_t launch_shortlist_verdicts(const RibbitPrimer *lists, int64_t n_targets, bool home, const RibbitPrimerPairParams &pair, const RibbitProductParams &product,
+                                     uint8_t *work, size_t work_bytes, const VerdictLayout &at, const int32_t *site_lists, hipStream_t stream);
+
 // profiling aid: reads nwords dwords of src with one coalesced dword per lane (known byte count)
 void launch_calib_stream_read(const uint32_t *src, int64_t nwords, uint32_t *sink, hipStream_t stream);
 

@@ -17,6 +17,10 @@
 //                over the admissible lanes.  The winner's two primers go to every lane and its five dimer values are wave
 //                maxima with a lane per placement (fill_chosen_pair), its products come by __shfl, and lane 0 writes the three
 //                records.  No LDS.
+// For a genome (api_primer_genome.cpp: ribbit_hip_record_shortlist_verdicts) the shortlists come up from the host and the loaded
+// record may be another one than they were made on: held_places_kernel counts each target's held places, the same sum and
+// shortlisted_oligos_kernel make the batch's oligos without primer_shortlists_kernel, the site scan is the same, and
+// shortlist_verdicts_kernel judges the 64 pairs as above but hands out the outcome of every pair as four masks, not a choice.
 // The kernels stride beyond ROW_MAX_BLOCKS blocks.  No atomics of their own (the site scan's integer vector atomics are
 // primer_products.hip's), no inline assembly.
 #include <cstring>
@@ -33,6 +37,7 @@ namespace {
 
 constexpr int SLOTS = 2 * SHORTLIST;      // the places of a target's two shortlists
 static_assert(sizeof(RibbitRowSpecific) == 32 && sizeof(RibbitRowProducts) == 32 && sizeof(RibbitOligo) == 12, "8, 8 and 3 ints");
+static_assert(sizeof(RibbitTargetVerdicts) == 176 && sizeof(RibbitPrimer) == 24, "four masks and 36 ints; 6 ints");
 
 __global__ void __launch_bounds__(64 * PAIR_WAVES) primer_shortlists_kernel(const int32_t *__restrict__ targets, int64_t n_targets, DevicePlanes pl,
                                                                            const uint32_t *__restrict__ bits, RibbitPrimerParams prm, RibbitPrimerPairParams pair, int cap,
@@ -146,6 +151,76 @@ __global__ void __launch_bounds__(64 * PAIR_WAVES) specific_pairs_kernel(const R
     }
 }
 
+// ---- shortlists that were made elsewhere, judged on the loaded record (ribbit_hip_record_shortlist_verdicts)
+// a lane per target: the held places of its two uploaded shortlists (the caller has checked that they are the first ones)
+__global__ void __launch_bounds__(ROW_THREADS) held_places_kernel(const RibbitPrimer *__restrict__ lists, int64_t n_targets, uint32_t *__restrict__ n_left,
+                                                                    uint32_t *__restrict__ n_oligos) {
+    for (int64_t t = (int64_t)blockIdx.x * ROW_THREADS + threadIdx.x; t < n_targets; t += (int64_t)gridDim.x * ROW_THREADS) {
+        uint32_t left = 0, right = 0;
+        for (int k = 0; k < SHORTLIST; ++k) {
+            left += lists[t * SLOTS + k].start >= 0;
+            right += lists[t * SLOTS + SHORTLIST + k].start >= 0;
+        }
+        n_left[t] = left;
+        n_oligos[t] = left + right;
+    }
+}
+
+// One wavefront per target, lane 8 l + r for the pair (l, r), as specific_pairs_kernel: the lane judges the pair's admissibility
+// from the stored primers and counts its products on this record, with the own positions only when this is the home record.  The
+// four masks are ballots, first_others comes from the lane of the wave-minimum key, and lanes 0 to 15 write the site counts of the
+// target's 16 places.  No LDS.
+__global__ void __launch_bounds__(64 * PAIR_WAVES) shortlist_verdicts_kernel(const RibbitPrimer *__restrict__ lists, const uint32_t *__restrict__ n_left_of,
+                                                                            const uint32_t *__restrict__ n_oligos, const uint32_t *__restrict__ upto, int64_t n_targets,
+                                                                            RibbitPrimerPairParams pair, int home, const uint32_t *__restrict__ unique_of,
+                                                                            const UniqueOligo *__restrict__ uniques, const uint32_t *__restrict__ counts,
+                                                                            const int32_t *__restrict__ site_lists, int max_product, int max_sites,
+                                                                            RibbitTargetVerdicts *__restrict__ out) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+    for (int64_t t = (int64_t)blockIdx.x * waves + wave; t < n_targets; t += (int64_t)gridDim.x * waves) {
+        const int n_left = (int)n_left_of[t], n_right = (int)n_oligos[t] - n_left;
+        const int64_t first_oligo = (int64_t)(upto[t] - n_oligos[t]);
+        const int l = lane >> 3, r = lane & 7;
+        unsigned long long key = NO_KEY;
+        RibbitRowProducts found = {};
+        if (l < n_left && r < n_right) {
+            const RibbitPrimer a = lists[t * SLOTS + l], b = lists[t * SLOTS + SHORTLIST + r];
+            key = judge_pair(a, b, pair, l, r);
+            if (key != NO_KEY)
+                found = pair_products(unique_of[first_oligo + l], unique_of[first_oligo + n_left + r], home ? a.start : -1, home ? b.start : -1, uniques, counts, site_lists,
+                                      max_product, max_sites);
+        }
+        const bool admissible = key != NO_KEY, over = admissible && found.products < 0;
+        const int32_t others = over ? -1 : found.products - found.own;
+        const unsigned long long m_admissible = __ballot(admissible), m_over = __ballot(over), m_other = __ballot(admissible && others > 0),
+                                 m_own = __ballot(admissible && found.own != 0);
+        const unsigned long long first = wave_min(key);
+        const int32_t first_others = first != NO_KEY ? __shfl(others, (int)(first & 63u)) : 0;
+        if (lane < SLOTS) {
+            const int rank = lane < SHORTLIST ? lane : lane - SHORTLIST;
+            const bool held = lane < SHORTLIST ? rank < n_left : rank < n_right;
+            uint32_t forward = 0, reverse = 0;
+            if (held) {
+                const uint32_t u = unique_of[first_oligo + (lane < SHORTLIST ? rank : n_left + rank)];
+                forward = counts[2 * u];
+                reverse = counts[2 * u + 1];
+            }
+            out[t].forward[lane] = (int32_t)forward;
+            out[t].reverse[lane] = (int32_t)reverse;
+        }
+        if (lane == 0) {
+            out[t].admissible = m_admissible;
+            out[t].over = m_over;
+            out[t].other = m_other;
+            out[t].own = m_own;
+            out[t].first_others = first_others;
+            out[t].records = 1;
+            out[t].home_records = home;
+            out[t].reserved = 0;
+        }
+    }
+}
+
 hipError_t sum_counts(void *scratch, size_t &bytes, const uint32_t *in, uint32_t *out, int64_t n, hipStream_t stream) {
     return rocprim::inclusive_scan(scratch, bytes, in, out, (size_t)n, rocprim::plus<uint32_t>(), stream);
 }
@@ -208,6 +283,51 @@ hipError_t launch_specific_pairs(int64_t n_targets, const RibbitPrimerPairParams
                        region<int32_t>(work, at.side_counts), n_oligos, n_oligos + n_targets, n_targets, pair, region<uint32_t>(pw, at.product.unique_of),
                        region<UniqueOligo>(pw, at.product.uniques), region<uint32_t>(pw, at.product.counts), site_lists, (int)product.max_product, (int)product.max_sites,
                        region<RibbitRowPrimerPair>(work, at.pairs), region<RibbitRowProducts>(work, at.products), region<RibbitRowSpecific>(work, at.specific));
+    return hipGetLastError();
+}
+
+VerdictLayout verdict_layout(int64_t n_targets) {
+    const size_t n = (size_t)n_targets;
+    size_t a = 0;
+    (void)sum_counts(nullptr, a, nullptr, nullptr, n_targets, 0);
+    VerdictLayout at{};
+    at.product = products_layout(n_targets * SLOTS, 0);
+    WorkCarver w;
+    at.n_oligos = w.take(2 * n * sizeof(uint32_t));
+    at.n_left = w.take(n * sizeof(uint32_t));
+    at.oligos = w.take(n * SLOTS * sizeof(RibbitOligo));
+    at.header = w.take(sizeof(SpecificHeader));
+    at.verdicts = w.take(n * sizeof(RibbitTargetVerdicts));
+    at.product_work = w.take(at.product.bytes);
+    w.close(at, a);
+    return at;
+}
+
+hipError_t launch_listed_oligos(const RibbitPrimer *lists, int64_t n_targets, uint8_t *work, size_t work_bytes, const VerdictLayout &at, hipStream_t stream) {
+    if (work_bytes < at.bytes || n_targets < 1) return hipErrorInvalidValue;
+    uint32_t *n_oligos = region<uint32_t>(work, at.n_oligos), *upto = n_oligos + n_targets;
+    hipLaunchKernelGGL(held_places_kernel, dim3(grid_for(n_targets, ROW_THREADS, ROW_MAX_BLOCKS)), dim3(ROW_THREADS), 0, stream, lists, n_targets,
+                       region<uint32_t>(work, at.n_left), n_oligos);
+    // (the layout may be a larger batch's: what the sum asks for these targets must fit its region)
+    size_t bytes = 0;
+    hipError_t e = sum_counts(nullptr, bytes, n_oligos, upto, n_targets, stream);
+    if (e != hipSuccess) return e;
+    if (bytes > at.scratch_bytes) return hipErrorInvalidValue;
+    if ((e = sum_counts(work + at.scratch, bytes, n_oligos, upto, n_targets, stream)) != hipSuccess) return e;
+    hipLaunchKernelGGL(shortlisted_oligos_kernel, dim3(grid_for(n_targets * SLOTS, ROW_THREADS, ROW_MAX_BLOCKS)), dim3(ROW_THREADS), 0, stream, lists, n_oligos, upto, n_targets,
+                       region<RibbitOligo>(work, at.oligos), region<SpecificHeader>(work, at.header));
+    return hipGetLastError();
+}
+
+hipError_t launch_shortlist_verdicts(const RibbitPrimer *lists, int64_t n_targets, bool home, const RibbitPrimerPairParams &pair, const RibbitProductParams &product,
+                                     uint8_t *work, size_t work_bytes, const VerdictLayout &at, const int32_t *site_lists, hipStream_t stream) {
+    if (work_bytes < at.bytes || n_targets < 1 || product.max_product < 1 || product.max_sites < 1) return hipErrorInvalidValue;
+    const uint32_t *n_oligos = region<uint32_t>(work, at.n_oligos);
+    uint8_t *pw = work + at.product_work;
+    hipLaunchKernelGGL(shortlist_verdicts_kernel, dim3(grid_for(n_targets, PAIR_WAVES, ROW_MAX_BLOCKS)), dim3(64 * PAIR_WAVES), 0, stream, lists,
+                       region<uint32_t>(work, at.n_left), n_oligos, n_oligos + n_targets, n_targets, pair, home ? 1 : 0, region<uint32_t>(pw, at.product.unique_of),
+                       region<UniqueOligo>(pw, at.product.uniques), region<uint32_t>(pw, at.product.counts), site_lists, (int)product.max_product, (int)product.max_sites,
+                       region<RibbitTargetVerdicts>(work, at.verdicts));
     return hipGetLastError();
 }
 

@@ -1,4 +1,5 @@
-// primers_host.h -- what the host sides of the primer outputs share (api_primers.cpp, api_primer_pairs.cpp, api_primer_products.cpp, api_primer_specific.cpp): the checks of
+// primers_host.h -- what the host sides of the primer outputs share (api_primers.cpp, api_primer_pairs.cpp, api_primer_products.cpp, api_primer_specific.cpp,
+// api_primer_genome.cpp): the checks of
 // RibbitPrimerParams and of a call's arguments with their wording, a target's two windows, one candidate judged from the bytes of
 // the sequence letter by letter (the five rules and the Tm table as include/ribbit_hip.h states them), and the columns of a primer
 // and of a pair as text.  No GPU, and nothing of the kernels' packed forms.
@@ -178,6 +179,16 @@ int check_primer_pair_params(const RibbitPrimerPairParams *p);
 std::vector<uint8_t> host_covered(int64_t length, const int32_t *intervals, size_t n);
 void host_ordered_pairs(const unsigned char *seq, const std::vector<uint8_t> &covered, const Flanks &f, const RibbitPrimerParams &prm, const RibbitPrimerPairParams &pair,
                         std::vector<RibbitRowPrimerPair> &ordered, RibbitRowPrimerPair &none);
+// ... and what api_primer_genome.cpp takes: a target's two shortlists as they leave the record; the held places of one side of stored
+// shortlists (those before the first empty one); a stored primer's oligo as letters, 5' to 3' (the right one as ordered); the
+// admissible pairs of stored shortlists from the lists alone, as host_ordered_pairs gives them from the sequence
+void host_target_shortlists(const unsigned char *seq, const std::vector<uint8_t> &covered, const Flanks &f, const RibbitPrimerParams &prm, const RibbitPrimerPairParams &pair,
+                            RibbitTargetShortlists &out);
+int host_held_places(const RibbitPrimer *side);
+std::string host_listed_oligo(const RibbitPrimer &p, bool right);
+void host_listed_pairs(const RibbitTargetShortlists &lists, const RibbitPrimerPairParams &pair, std::vector<RibbitRowPrimerPair> &ordered, RibbitRowPrimerPair &none);
+// api_primer_specific.cpp: the targets of one batch of the specific primer pairs on this handle, which the shortlists' verdicts share
+size_t specific_batch_targets(const RibbitHandle *h, const RibbitProductParams &product);
 // api_primer_products.cpp: the check of RibbitProductParams; a pair's two oligos as letters, 5' to 3'; the sites of an oligo on either
 // strand, ascending; the products of a pair among the sites of its two oligos
 struct HostSites { std::vector<int32_t> forward, reverse; };

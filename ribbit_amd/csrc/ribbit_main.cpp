@@ -58,12 +58,19 @@
 // --primer-specific-bed writes those rows, each with the best pair of --primer-specific-flank bases on either side that amplifies
 // nothing else in its own record: all pairs of the two shortlists go through that in-silico PCR, the first specific one in the order
 // of the choice is taken (ribbit_hip_record_specific_primer_pairs, ribbit_bed_primer_specific_text).
-// The BED rows are read back once per record, however many of the twenty are asked for.
+// --primer-genome-bed writes the same columns with every count and verdict taken over all records of the input.  It is the one
+// output that needs the whole input twice: per record only the selected rows' lines and the targets' two shortlists are made, in
+// --primer-genome-flank bases on either side (ribbit_hip_record_primer_shortlists), and kept in host memory in input order; after
+// the last record the FASTA is read again, every record is loaded without a scan, all targets' pairs are judged on it
+// (ribbit_hip_record_shortlist_verdicts, as home for the record's own targets), the judgements are summed
+// (ribbit_primer_verdicts_merge), and then the pairs are chosen and written (ribbit_primer_shortlists_choose,
+// ribbit_bed_primer_specific_text): write_primer_genome.
+// The BED rows are read back once per record, however many of the twenty-one are asked for.
 //
-// These twenty are the ROW OUTPUTS, and each is described once, by its entry of kOutputs below: its file option, its stage (enum
+// These twenty-one are the ROW OUTPUTS, and each is described once, by its entry of kOutputs below: its file option, its stage (enum
 // Stage, with the stage's names beside it), its qualifier options with their ranges and wording (defaults: Settings), and the function that
 // makes one record's text from the record's rows.  Parsing, the "needs" checks, opening the files, the sinks of the pipelined
-// records and of the last one, --timing and the RIBBIT_PROFILE line are loops over that table.  A twenty-first row output is: a stage in
+// records and of the last one, --timing and the RIBBIT_PROFILE line are loops over that table.  A twenty-second row output is: a stage in
 // the enum and its names, the qualifiers' fields in Settings, a produce function, an entry of kOutputs, and its lines of kHelp.
 //
 // Reproduced quirks: -p is accepted and ignored (Q1); without -o the BED rows go to
@@ -110,14 +117,14 @@ void check(int rc) {
 }
 
 // The stages of a record: the six every record goes through, then one per row output, in the order of kOutputs.
-enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, OVERLAP, BEST, CLASSES, COMPOUND, INTERRUPTIONS, NEAREST, COMPOSITION, PRIMERS, PRIMER_PAIRS, PRIMER_PRODUCTS, PRIMER_SPECIFIC, N_STAGES };
+enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, OVERLAP, BEST, CLASSES, COMPOUND, INTERRUPTIONS, NEAREST, COMPOSITION, PRIMERS, PRIMER_PAIRS, PRIMER_PRODUCTS, PRIMER_SPECIFIC, PRIMER_GENOME, N_STAGES };
 constexpr int N_FIXED_STAGES = MASK;
 // a stage's key in --timing's stage_ms_summed_over_records and its label in the RIBBIT_PROFILE line
 const struct { const char *key, *label; } kStageNames[N_STAGES] = {
     {"load", "load"}, {"perfect", "perfect"}, {"substitutions", "substitutions"}, {"anchored", "anchored"}, {"dispatch", "dispatch"},
     {"refine_and_bed", "refine+BED"}, {"mask", "mask"}, {"repeats", "repeats"}, {"loci", "loci"}, {"density", "density"}, {"overlap", "overlap"},
     {"best", "best"}, {"classes", "classes"}, {"compound", "compound"}, {"interruptions", "interruptions"}, {"nearest", "nearest"}, {"composition", "composition"}, {"primers", "primers"},
-    {"primer_pairs", "primer_pairs"}, {"primer_products", "primer_products"}, {"primer_specific", "primer_specific"}};
+    {"primer_pairs", "primer_pairs"}, {"primer_products", "primer_products"}, {"primer_specific", "primer_specific"}, {"primer_genome", "primer_genome"}};
 
 // wall time per stage, summed over the records (--timing, RIBBIT_PROFILE=1)
 double g_stage_ms[N_STAGES] = {};
@@ -229,6 +236,7 @@ struct Settings {
     int primer_pair_flank = 200;         // --primer-pair-flank F: the same for --primer-pair-bed
     int primer_product_flank = 200;      // --primer-product-flank F: the same for --primer-product-bed
     int primer_specific_flank = 200;     // --primer-specific-flank F: the same for --primer-specific-bed
+    int primer_genome_flank = 200;       // --primer-genome-flank F: the same for --primer-genome-bed
     const OtherBed *other = nullptr;         // --overlap-with FILE, read and grouped by name
 };
 
@@ -624,6 +632,33 @@ void produce_primer_specific(RibbitHandle *h, const RecordRows &r, const Setting
     ribbit_text_free(text);
 }
 
+// The first pass of --primer-genome-bed over one record: nothing for the file yet.  What goes to the sink is the record's state for the
+// second pass (write_primer_genome), which travels in input order as the other outputs' texts do: the number of targets and the
+// length of their BED lines (two 64-bit words), the targets' RibbitTargetShortlists, the lines.
+void produce_primer_genome(RibbitHandle *h, const RecordRows &r, const Settings &s, const Sink &write) {
+    StageClock c(PRIMER_GENOME);
+    const RecordRows::Best &b = best_of(h, r);
+    const std::vector<int32_t> targets = targets_of(r, b);
+    RibbitPrimerParams prm;
+    ribbit_primer_params_default(&prm);
+    prm.flank = s.primer_genome_flank;
+    RibbitPrimerPairParams pair;
+    ribbit_primer_pair_params_default(&pair);
+    char *lines = nullptr;
+    size_t lines_len = 0;
+    const RibbitTargetShortlists *lists = nullptr;
+    check(ribbit_bed_rows_text(r.bed_text, r.bed_len, b.chosen, b.n, &lines, &lines_len));
+    const int rc = ribbit_hip_record_primer_shortlists(h, r.iv.data(), r.n(), targets.data(), b.n, &prm, &pair, &lists);
+    if (rc == RIBBIT_OK) {
+        const uint64_t head[2] = {(uint64_t)b.n, (uint64_t)lines_len};
+        write(reinterpret_cast<const char *>(head), sizeof head);
+        write(reinterpret_cast<const char *>(lists), b.n * sizeof(RibbitTargetShortlists));
+        write(lines, lines_len);
+    }
+    ribbit_text_free(lines);
+    check(rc);
+}
+
 // One entry per row output.  The order is the order of everything that is done for all of them: the "needs" checks, opening the
 // files (binary), producing a record's texts, the keys of --timing.
 struct Output {
@@ -634,7 +669,7 @@ struct Output {
     Qualifier qualifiers[MAX_QUALIFIERS];    // (name null: none)
     bool needs_other;                        // it compares the rows with the intervals of --overlap-with
 };
-constexpr size_t N_OUTPUTS = 20;
+constexpr size_t N_OUTPUTS = 21;
 const Output kOutputs[N_OUTPUTS] = {
     {"masked-fasta", MASK, false, produce_masked,
      {{"mask", Qualifier::SOFT_HARD, 0, 0, 0, nullptr, &Settings::mask_mode},
@@ -667,8 +702,12 @@ const Output kOutputs[N_OUTPUTS] = {
     {"primer-product-bed", PRIMER_PRODUCTS, true, produce_primer_products,
      {{"primer-product-flank", Qualifier::BASES, 0, RIBBIT_PRIMER_MAX_FLANK, 4, "0 .. 1000", &Settings::primer_product_flank}, {}}, false},
     {"primer-specific-bed", PRIMER_SPECIFIC, true, produce_primer_specific,
-     {{"primer-specific-flank", Qualifier::BASES, 0, RIBBIT_PRIMER_MAX_FLANK, 4, "0 .. 1000", &Settings::primer_specific_flank}, {}}, false}};
-static_assert(RIBBIT_PRIMER_MAX_FLANK == 1000, "the range as --primer-flank's, --primer-pair-flank's, --primer-product-flank's and --primer-specific-flank's messages and help put it");
+     {{"primer-specific-flank", Qualifier::BASES, 0, RIBBIT_PRIMER_MAX_FLANK, 4, "0 .. 1000", &Settings::primer_specific_flank}, {}}, false},
+    {"primer-genome-bed", PRIMER_GENOME, true, produce_primer_genome,
+     {{"primer-genome-flank", Qualifier::BASES, 0, RIBBIT_PRIMER_MAX_FLANK, 4, "0 .. 1000", &Settings::primer_genome_flank}, {}}, false}};
+static_assert(RIBBIT_PRIMER_MAX_FLANK == 1000, "the range as --primer-flank's, --primer-pair-flank's, --primer-product-flank's, --primer-specific-flank's and --primer-genome-flank's messages and help put it");
+// --primer-genome-bed: what its produce function hands to the sink is not text for the file but the record's state for the second pass
+constexpr size_t GENOME_OUTPUT = N_OUTPUTS - 1;
 
 // the row outputs that are on, by stage: an output whose stage an earlier one has already named is left out (--timing, RIBBIT_PROFILE)
 std::vector<Stage> stages_on(const std::array<bool, N_OUTPUTS> &on) {
@@ -854,7 +893,17 @@ const char *kHelp =
     "                                of the PCR and in the place where no pair is specific). Only the record itself is\n"
     "                                searched, not the other records of the input\n"
     "  --primer-specific-flank arg   (ribbit-hip) bases of the record on either side of a row that --primer-specific-bed may\n"
-    "                                place a primer in, 0 .. 1000. Default: 200\n";
+    "                                place a primer in, 0 .. 1000. Default: 200\n"
+    "  --primer-genome-bed arg       (ribbit-hip) also write the rows of --best-bed's selection to this file with the 31 columns\n"
+    "                                of --primer-specific-bed, every count and verdict taken over ALL records of the input: the\n"
+    "                                pairs of a row are those of its own record, and each goes through the in-silico PCR on\n"
+    "                                every record. A pair is passed over when a primer has more than 64 sites on a strand of\n"
+    "                                any one record, or when it has a product other than its own in any record; the first pair\n"
+    "                                left is taken, and there is no fallback. The site counts are sums over the records. The\n"
+    "                                input is read a second time after the last record, on the first GPU; the rows' lines and\n"
+    "                                about 600 bytes per row stay in memory until then\n"
+    "  --primer-genome-flank arg     (ribbit-hip) bases of the record on either side of a row that --primer-genome-bed may place\n"
+    "                                a primer in, 0 .. 1000. Default: 200\n";
 
 bool parse_device_list(const std::string &value, std::vector<int> &out) {
     out.clear();
@@ -1144,6 +1193,78 @@ void process_sequence(RibbitHandle *h, const RibbitRefineParams &prm, const std:
     log << "Total number of seeds that are processed for alignment: " << nd << "\t Time elapsed: " << secs() << "secs\n";
 }
 
+// The second pass of --primer-genome-bed, after the last record, on the handle h: `states` holds what produce_primer_genome made of
+// every record, in input order.  The FASTA is read again; every record is loaded and nothing is scanned; all records' lists are
+// judged on it, the record's own as home; the verdicts are summed; then every record's pairs are chosen and its text is written.
+void write_primer_genome(RibbitHandle *h, const std::string &fasta, const std::vector<std::string> &states, std::ostream &file) {
+    StageClock c(PRIMER_GENOME);
+    std::vector<size_t> first(states.size() + 1, 0);      // record k's targets are [first[k], first[k + 1])
+    for (size_t k = 0; k < states.size(); ++k) {
+        uint64_t head[2];
+        std::memcpy(head, states[k].data(), sizeof head);
+        first[k + 1] = first[k] + (size_t)head[0];
+    }
+    const size_t total = first.back();
+    if (total == 0) return;      // (no target anywhere: every record's text is empty)
+    std::vector<RibbitTargetShortlists> lists(total);
+    for (size_t k = 0; k < states.size(); ++k)
+        if (first[k + 1] > first[k]) std::memcpy(&lists[first[k]], states[k].data() + 2 * sizeof(uint64_t), (first[k + 1] - first[k]) * sizeof(RibbitTargetShortlists));
+    std::vector<RibbitTargetVerdicts> sum(total);
+    RibbitPrimerPairParams pair;
+    ribbit_primer_pair_params_default(&pair);
+    RibbitProductParams product;
+    ribbit_product_params_default(&product);
+    RibbitFastaReader *reader = nullptr;
+    if (ribbit_fasta_open(fasta.c_str(), 1, &reader) != RIBBIT_OK) throw PathError{std::string("--primer-genome-bed: ") + ribbit_fasta_last_error()};
+    struct Close { RibbitFastaReader *r; ~Close() { ribbit_fasta_close(r); } } close{reader};
+    size_t k = 0;
+    for (;; ++k) {
+        const char *name = "", *bases = nullptr;
+        int64_t length = 0;
+        int is_last = 1;
+        const int got = ribbit_fasta_next(reader, &name, &bases, &length, &is_last);
+        if (got < 0) throw PathError{std::string("--primer-genome-bed: ") + ribbit_fasta_last_error()};
+        if (got == 0) break;
+        if (k >= states.size()) throw PathError{"--primer-genome-bed: the input has more records than when it was read first"};
+        int rc = ribbit_hip_load_record_pinned(h, bases, length);
+        // the targets before this record's, its own, those behind them
+        const size_t cut[4] = {0, first[k], first[k + 1], total};
+        for (int part = 0; part < 3 && rc == RIBBIT_OK; ++part) {
+            const size_t from = cut[part], n = cut[part + 1] - from;
+            if (n == 0) continue;
+            const RibbitTargetVerdicts *verdicts = nullptr;
+            rc = ribbit_hip_record_shortlist_verdicts(h, &lists[from], n, part == 1, &pair, &product, &verdicts);
+            if (rc != RIBBIT_OK) break;
+            if (k == 0) std::memcpy(&sum[from], verdicts, n * sizeof(RibbitTargetVerdicts));
+            else rc = ribbit_primer_verdicts_merge(&sum[from], verdicts, n);
+        }
+        ribbit_fasta_release(reader, bases);
+        check(rc);
+        if (is_last) { ++k; break; }
+    }
+    if (k != states.size()) throw PathError{"--primer-genome-bed: the input has fewer records than when it was read first"};
+    for (k = 0; k < states.size(); ++k) {
+        const size_t n = first[k + 1] - first[k];
+        if (n == 0) continue;
+        uint64_t head[2];
+        std::memcpy(head, states[k].data(), sizeof head);
+        const char *lines = states[k].data() + 2 * sizeof(uint64_t) + n * sizeof(RibbitTargetShortlists);
+        RibbitRowPrimerPair *pairs = nullptr;
+        RibbitRowProducts *products = nullptr;
+        RibbitRowSpecific *specific = nullptr;
+        char *text = nullptr;
+        size_t len = 0;
+        int rc = ribbit_primer_shortlists_choose(&lists[first[k]], &sum[first[k]], n, &pair, &pairs, &products, &specific);
+        if (rc == RIBBIT_OK) rc = ribbit_bed_primer_specific_text(lines, (size_t)head[1], pairs, products, specific, n, &text, &len);
+        ribbit_primer_genome_free(pairs);
+        ribbit_primer_genome_free(products);
+        ribbit_primer_genome_free(specific);
+        check(rc);
+        file.write(text, (std::streamsize)len);
+        ribbit_text_free(text);
+    }
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -1208,6 +1329,7 @@ int main(int argc, char **argv) {
     std::deque<Record> queue;
     std::map<size_t, Result> done;
     size_t next_out = 0;
+    std::vector<std::string> genome_states;      // --primer-genome-bed: every record's state for the second pass, in input order
     bool reader_done = false;
     bool failed = false;            // some record's GPU path failed: everybody drains
     std::string failure;
@@ -1225,7 +1347,10 @@ int main(int argc, char **argv) {
         for (auto it = done.find(next_out); it != done.end(); it = done.find(next_out)) {
             std::cerr << it->second.log;
             out.write(it->second.bed.data(), (std::streamsize)it->second.bed.size());
-            for (size_t k = 0; k < N_OUTPUTS; ++k) row_file[k].write(it->second.rows[k].data(), (std::streamsize)it->second.rows[k].size());
+            for (size_t k = 0; k < N_OUTPUTS; ++k) {
+                if (k == GENOME_OUTPUT && row_on[k]) genome_states.push_back(std::move(it->second.rows[k]));
+                else row_file[k].write(it->second.rows[k].data(), (std::streamsize)it->second.rows[k].size());
+            }
             done.erase(it);
             ++next_out;
         }
@@ -1345,9 +1470,19 @@ int main(int argc, char **argv) {
             static const char kNoBases[1] = {0};
             // (every record the reader hands out has its row outputs but the nameless empty one of a file without records, Q4)
             const bool real_last = !(last_name.empty() && last_length == 0);
-            const RowJobs row_jobs(real_last ? row_on : std::array<bool, N_OUTPUTS>{},
-                                   [&row_file](size_t k) { return [&row_file, k](const char *p, size_t n) { row_file[k].write(p, (std::streamsize)n); }; });
+            std::string last_state;
+            const RowJobs row_jobs(real_last ? row_on : std::array<bool, N_OUTPUTS>{}, [&row_file, &last_state](size_t k) {
+                return [&row_file, &last_state, k](const char *p, size_t n) {
+                    if (k == GENOME_OUTPUT) last_state.append(p, n);
+                    else row_file[k].write(p, (std::streamsize)n);
+                };
+            });
             process_sequence(h, prm, last_name, last_bases ? last_bases : kNoBases, last_length, out, std::cerr, opt.settings, row_jobs, &helpers);
+            if (row_on[GENOME_OUTPUT]) {
+                if (real_last) genome_states.push_back(std::move(last_state));
+                if (reader) { ribbit_fasta_close(reader); reader = nullptr; }      // (the last record's bases are no longer needed)
+                write_primer_genome(h, opt.fasta, genome_states, row_file[GENOME_OUTPUT]);
+            }
         } catch (const PathError &e) { failed = true; failure = e.what; }
     }
     if (failed) { std::cerr << "ribbit-hip: " << failure << "\n"; status = 1; }
