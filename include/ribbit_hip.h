@@ -1160,6 +1160,87 @@ int ribbit_primer_shortlists_choose(const RibbitTargetShortlists *lists, const R
 void ribbit_primer_genome_free(void *from_a_host_function);
 
 /*
+ * ---- every chosen primer pair typed on another assembly: where its product lies there and how long its repeat is -----------
+ * What GMATA calls e-mapping: the chosen pairs of one assembly run against the records of a second one (another individual,
+ * strain or haplotype, the previous release), to read off whether the marker transfers and how long its allele is there.
+ * Everything is integer arithmetic on letters; nothing is added to the site and product definitions of the in-silico PCR
+ * contract above.  Gapped or thermodynamic binding, more than the first product, chunks and several GPUs are not part of it.
+ *   Inputs:     all of them refer to the loaded record R[0, L), which may be any record.  n pairs as RibbitRowPrimerPair, of
+ *               which only the two primers' length and bases are read (and left.start < 0: a target without a pair); a is the
+ *               left primer, b the right primer as ordered; no product is "own".  Per pair a motif w of m letters,
+ *               1 <= m <= 1023, letters ACGT, as a pool and int32 offsets exactly as ribbit_bed_motifs hands them out; the
+ *               refusals are those of ribbit_hip_record_classes.  A RibbitProductParams.  An int32 `record` label >= 0.
+ *   Counts:     the four site counts are exact.  products is as in the product contract, -1 when one of the four lists is
+ *               longer than max_sites.
+ *   First product:  when products > 0.  Among the products (f, v) the one with the least key (f.x, v.x + v.k, forward_of,
+ *               reverse_of), forward_of and reverse_of being 0 for a site of a and 1 for a site of b.  start = f.x,
+ *               end = v.x + v.k, inner_start = f.x + f.k, inner_end = v.x.  The inner part may be empty.
+ *   Tract:      the longest stretch [s, e) inside [inner_start, inner_end) with e - s >= 2 m (a single unit is no repeat), no
+ *               byte of it `other`, and, case ignored, R[s + j] == w[(p + j) mod m] for some phase p and all j (strand 0), or
+ *               otherwise the same with revcomp(w) (strand 1).  Of equal lengths the leftmost; when both strands fit one stretch
+ *               (a motif whose reverse complement is a rotation of itself) the strand is 0.  Without a tract
+ *               tract_start = tract_end = -1 and the strand is 0.
+ *               An equivalent form: with ok[x] = (R[x] == R[x - m], both bases, both inside the inner part), the tracts are
+ *               the maximal ok stretches [u, v) with v - u >= m, taken as [u - m, v), whose first m letters are a rotation of w
+ *               or of revcomp(w).  The kernel works in this form, the host twin in the first.
+ *   Record:     with products <= 0, `record` and the six positions are -1 and forward_of, reverse_of, tract_strand are 0; with
+ *               products > 0, `record` is the label given.  A pair whose left.start < 0 is sixteen zeros except that `record`
+ *               and the positions are -1.
+ *   Sum:        over records (ribbit_pair_amplicons_merge): the four counts add and saturate at INT32_MAX; products is -1 if
+ *               either is -1, else the saturating sum; when the result is -1 the amplicon fields are the "none" values above,
+ *               otherwise they are those of `into` if into.products > 0, else those of `from`: a caller that merges in record
+ *               order keeps the first record's product.
+ *   Values:     with Lp = GATTACAGATTACAGGCT, Rp = CCTGAAGTCTCGGATCAA, a = Lp, b = revcomp(Rp), X = ACGTTGCATG, Y = CCATGACTGA,
+ *               rec = Lp X (CA)10 Y Rp (76 bases) and the defaults (tests/amplicons_contract.py computes them from a plain
+ *               statement of the above), as counts, products, (start, end, forward_of, reverse_of, inner_start, inner_end,
+ *               tract_start, tract_end, tract_strand):
+ *                 rec, CA (and AC)                    (1,0,0,1)  1  (0,76,0,1,18,58,28,49,0)   the tract takes Y's first C
+ *                 rec, TG                             (1,0,0,1)  1  the same with strand 1
+ *                 revcomp(rec), CA                    (0,1,1,0)  1  (0,76,1,0,18,58,27,48,1)
+ *                 Lp X (CA)17 Y Rp, CA                (1,0,0,1)  1  (0,90,0,1,18,72,28,63,0)
+ *                 Lp X (CA)4 N (CA)5 Y Rp, CA         (1,0,0,1)  1  (0,75,0,1,18,57,37,48,0)
+ *                 Lp X CA Y Rp, CA                    (1,0,0,1)  1  (0,58,0,1,18,40,-1,-1,0)
+ *                 rec in lower case, CA               as the first line
+ *                 rec ACGTAGCTAGCTAGGATCGA rec, CA    (2,0,0,2)  3  (0,76,0,1,18,58,28,49,0)
+ *                 Lp (GATA)6 Rp, ATAG                 (1,0,0,1)  1  (0,60,0,1,18,42,18,42,0)
+ *                 Lp X, CA                            (1,0,0,0)  0  none
+ */
+typedef struct {
+    int32_t left_forward, left_reverse, right_forward, right_reverse;   /* the sites of a and of b, exact */
+    int32_t products, record;
+    int32_t start, end, forward_of, reverse_of, inner_start, inner_end;
+    int32_t tract_start, tract_end, tract_strand, reserved;             /* reserved 0 */
+} RibbitRowAmplicon;                          /* 16 ints, 64 bytes */
+/* The n pairs (at most 2^24) on the loaded record, on the GPU (amplicons.hip): the site scan of ribbit_hip_record_primer_products,
+ * one lane per pair for the counts and the first product, one wavefront per pair with a product for the tract.  *rows is one
+ * record per pair in the order given, of handle-owned page-locked memory, valid until the handle's next call of this function,
+ * load or close.  Only pairs with left.start >= 0 send oligos; pairs go in batches, as many as 256 MiB of site lists hold with
+ * 2 oligos per pair (ribbit_hip_debug_set_specific_batch is obeyed, counting pairs); the result does not depend on the batches.
+ * n = 0 and L = 0 are no errors.  A field of params outside its range, a primer of fewer than `seed` or more than 32 bases, a
+ * bad motif pool, a negative record: RIBBIT_E_ARG with the field or index in the text; before a load: RIBBIT_E_STATE.  A record
+ * loaded as one chunk of a longer one is not served as that record: the piece is judged as the record it is. */
+int ribbit_hip_record_pair_amplicons(RibbitHandle *h, const RibbitRowPrimerPair *pairs, size_t n, const char *motifs, const int32_t *offsets,
+                                     int32_t record, const RibbitProductParams *params, const RibbitRowAmplicon **rows);
+/* Host-only twin (no GPU), from the bytes of `sequence` (0 <= length < 2^31), letter by letter in loops, the tract in its first
+ * form: *rows malloc'ed, release with ribbit_pair_amplicons_free(). */
+int ribbit_host_record_pair_amplicons(const char *sequence, int64_t length, const RibbitRowPrimerPair *pairs, size_t n, const char *motifs,
+                                      const int32_t *offsets, int32_t record, const RibbitProductParams *params, RibbitRowAmplicon **rows);
+/* The sum over records (host only), as above: into[i] becomes the amplicon of into[i]'s and from[i]'s records together. */
+int ribbit_pair_amplicons_merge(RibbitRowAmplicon *into, const RibbitRowAmplicon *from, size_t n);
+void ribbit_pair_amplicons_free(void *from_the_host_twin);
+/* The targets' BED rows as markers (host only): line i of bed_text, byte for byte, then 20 columns, each behind a tab, and a
+ * newline.  1 to 9 are the eight primer columns and the designed product as ribbit_bed_primer_pairs_text writes them; 10 is
+ * `products` on the other assembly, "." when it is -1; 11 to 20 are filled only when products == 1, otherwise ".": the record's
+ * name (names[name_offsets[record] .. name_offsets[record + 1]), n_records names), start, end, the orientation ("+" for
+ * (forward_of, reverse_of) = (0, 1), "-" for (1, 0), "l" for (0, 0), "r" for (1, 1)), the size end - start, the size minus the
+ * designed product, tract start, tract end, the tract's bases and its whole units, bases / m with m the length of the row's
+ * motif (column 4 of the row); without a tract the last four are ".".  A row without a pair has "." in all 20.  A bed_text that
+ * does not have n lines or holds a line that is no row, a primer of fewer than 1 or more than 32 bases, a `record` outside
+ * the names where products > 0: RIBBIT_E_ARG.  *text malloc'ed, release with ribbit_text_free(). */
+int ribbit_bed_marker_text(const char *bed_text, size_t bed_len, const RibbitRowPrimerPair *pairs, const RibbitRowAmplicon *amplicons,
+                           const char *names, const int32_t *name_offsets, size_t n_records, size_t n, char **text, size_t *len);
+
+/*
  * ---- streaming FASTA ingest ---------------------------------------------------------------------------------------
  * Replaces the reader loop of ribbit.cpp:269-280 (getline + `sequence += line` into one pageable std::string per
  * record).  The file is read in 16-MB blocks; line bodies are copied once, straight into a page-locked buffer

@@ -36,7 +36,8 @@ __all__ = ["RibbitHipError", "ScanParams", "Scanner", "library_path", "load_libr
            "bed_primer_products_text",
            "PRIMER_SPECIFIC_DT", "host_record_specific_primer_pairs", "bed_primer_specific_text",
            "PRIMER_SHORTLISTS_DT", "PRIMER_VERDICTS_DT", "host_record_primer_shortlists", "host_record_shortlist_verdicts", "primer_verdicts_merge",
-           "primer_shortlists_choose"]
+           "primer_shortlists_choose",
+           "PAIR_AMPLICONS_DT", "host_record_pair_amplicons", "pair_amplicons_merge", "bed_marker_text"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -75,6 +76,9 @@ PRIMER_SHORTLISTS_DT = np.dtype([("left", _PRIMER_DT, (8,)), ("right", _PRIMER_D
                                 + [(n, "<i4") for n in ("left_candidates", "right_candidates", "left_passed", "right_passed")])      # RibbitTargetShortlists
 PRIMER_VERDICTS_DT = np.dtype([(n, "<u8") for n in ("admissible", "over", "other", "own")] + [("forward", "<i4", (16,)), ("reverse", "<i4", (16,))]
                               + [(n, "<i4") for n in ("first_others", "records", "home_records", "reserved")])      # RibbitTargetVerdicts
+PAIR_AMPLICONS_DT = np.dtype([(n, "<i4") for n in ("left_forward", "left_reverse", "right_forward", "right_reverse", "products", "record", "start", "end",
+                                                    "forward_of", "reverse_of", "inner_start", "inner_end", "tract_start", "tract_end", "tract_strand",
+                                                    "reserved")])      # RibbitRowAmplicon
 OLIGO_SITES_DT = np.dtype([(n, "<i4") for n in ("forward", "reverse", "forward_at", "reverse_at")])      # RibbitOligoSites
 _OLIGO_DT = np.dtype([(n, "<i4") for n in ("length", "bases_lo", "bases_hi")])      # RibbitOligo
 _I4 = np.dtype("<i4")
@@ -281,6 +285,8 @@ def _signatures() -> dict:
         "ribbit_bed_primer_specific_text": (st, [cp, sz, vp, vp, vp, sz, pvp, psz]),
         "ribbit_primer_verdicts_merge": (st, [vp, vp, sz]),
         "ribbit_primer_shortlists_choose": (st, [vp, vp, sz, P(PrimerPairParams), pvp, pvp, pvp]),
+        "ribbit_pair_amplicons_merge": (st, [vp, vp, sz]),
+        "ribbit_bed_marker_text": (st, [cp, sz, vp, vp, cp, vp, sz, sz, pvp, psz]),
     }
     for name in ("ribbit_hip_scan_perfect_runs", "ribbit_hip_perfect_calls", "ribbit_hip_seeds_perfect", "ribbit_hip_subst_calls",
                  "ribbit_hip_anchored_calls", "ribbit_hip_dispatch_seeds", "ribbit_hip_seed_longest_runs"):
@@ -294,7 +300,7 @@ def _signatures() -> dict:
     for name in ("ribbit_text_free", "ribbit_runs_free", "ribbit_intervals_free", "ribbit_loci_free", "ribbit_motif_classes_free",
                  "ribbit_compounds_free", "ribbit_row_purity_free", "ribbit_interruptions_free", "ribbit_nearest_free", "ribbit_composition_free",
                  "ribbit_primers_free", "ribbit_primer_pairs_free", "ribbit_products_free", "ribbit_primer_specific_free",
-                 "ribbit_primer_genome_free"):
+                 "ribbit_primer_genome_free", "ribbit_pair_amplicons_free"):
         t[name] = (None, [vp])
     # the row outputs: the device form takes the handle, the host form the record's length, or its bases and their number
     length, bases = [i64], [cp, i64]
@@ -312,6 +318,7 @@ def _signatures() -> dict:
                              ("record_specific_primer_pairs", bases, [vp, sz, vp, sz, P(PrimerParams), P(PrimerPairParams), P(ProductParams), pvp, pvp, pvp]),
                              ("record_primer_shortlists", bases, [vp, sz, vp, sz, P(PrimerParams), P(PrimerPairParams), pvp]),
                              ("record_shortlist_verdicts", bases, [vp, sz, i32, P(PrimerPairParams), P(ProductParams), pvp]),
+                             ("record_pair_amplicons", bases, [vp, sz, cp, vp, i32, P(ProductParams), pvp]),
                              ("record_best", length, [vp, sz, pvp, psz, P(i64)]),
                              ("record_classes", length, [vp, sz, vp, vp, pvp, pvp, pvp, psz]),
                              ("record_compounds", length, [vp, vp, sz, i32, pvp, psz, pvp, psz]),
@@ -991,6 +998,53 @@ def primer_shortlists_choose(lists, verdicts, pair_params: PrimerPairParams | No
         return _copy(pairs.value, len(ls), PRIMER_PAIRS_DT), _copy(products.value, len(ls), PRIMER_PRODUCTS_DT), _copy(specific.value, len(ls), PRIMER_SPECIFIC_DT)
     finally:
         _free(owned, "ribbit_primer_genome_free", pairs, products, specific)
+
+
+def _record_pair_amplicons(call, pairs, motifs, record, params) -> np.ndarray:
+    rw, params = _records(pairs, PRIMER_PAIRS_DT), _params_arg(params, product_params, ProductParams)
+    offsets = None
+    if isinstance(motifs, tuple):
+        motifs, offsets = motifs
+    pool, off = _pool(motifs, offsets)
+    if off.ndim != 1 or len(off) != len(rw) + 1:
+        raise ValueError(f"{len(rw)} pairs want {len(rw) + 1} offsets")
+    _all_int32(off, "an offset is not an int32")
+    off = np.ascontiguousarray(off, dtype=np.int32)
+    return _array(call, _ptr(rw), len(rw), pool, off.ctypes.data, _int32(record, "record"), C.byref(params), dt=PAIR_AMPLICONS_DT,
+                  free="ribbit_pair_amplicons_free", count=len(rw))
+
+
+def host_record_pair_amplicons(sequence: bytes, pairs, motifs, record: int = 0, params: ProductParams | None = None) -> np.ndarray:
+    """ribbit_host_record_pair_amplicons: every pair of `pairs` (a PRIMER_PAIRS_DT array) typed on the record, which may be any
+    record: the sites of both primers, the products, where the first product lies and the longest tract of the pair's motif inside
+    it -> a PAIR_AMPLICONS_DT array with `record` as the label of every pair that has a product.  motifs: a list of strings, one per
+    pair, or (pool, offsets) as bed_motifs returns them.  Sum over the records of an assembly with pair_amplicons_merge.  The
+    contract is in include/ribbit_hip.h.  No GPU needed."""
+    return _record_pair_amplicons(_host_bases("ribbit_host_record_pair_amplicons", sequence), pairs, motifs, record, params)
+
+
+def pair_amplicons_merge(into, other) -> np.ndarray:
+    """ribbit_pair_amplicons_merge: the amplicons of two sets of records together -> a new PAIR_AMPLICONS_DT array (neither argument
+    is changed): the counts added, products -1 if either is, the product of `into` kept where it has one"""
+    a, b = _records(into, PAIR_AMPLICONS_DT).copy(), _records(other, PAIR_AMPLICONS_DT)
+    if len(a) != len(b):
+        raise ValueError(f"{len(a)} and {len(b)} amplicons")
+    _call("ribbit_pair_amplicons_merge", _ptr(a), _ptr(b), len(a))
+    return a
+
+
+def bed_marker_text(bed, pairs, amplicons, names) -> bytes:
+    """ribbit_bed_marker_text: the lines of `bed` (the targets' BED rows, target i on line i), each with 20 more columns: the eight
+    primer columns and the designed product of row i of `pairs`, the products of row i of `amplicons` (record_pair_amplicons, summed
+    over the other assembly's records) and, where that is exactly one, the record's name out of `names` (a list, by the amplicon's
+    `record`), where the product lies, its orientation, its size, the size's difference from the designed product and the tract."""
+    text_in, rw, am = _bytes(bed), _records(pairs, PRIMER_PAIRS_DT), _records(amplicons, PAIR_AMPLICONS_DT)
+    if len(am) != len(rw):
+        raise ValueError(f"{len(rw)} pairs and {len(am)} amplicons")
+    names = [_name(n) for n in names]
+    pool, off = _pool(names, None)
+    off = np.ascontiguousarray(off, dtype=np.int32)
+    return _text("ribbit_bed_marker_text", text_in, len(text_in), _ptr(rw), _ptr(am), pool, off.ctypes.data, len(names), len(rw))
 
 
 def _record_best(call, intervals):
@@ -1681,6 +1735,11 @@ class Scanner:
         """An in-silico PCR of every primer pair on the loaded record, on the GPU (ribbit_hip_record_primer_products); see
         host_record_primer_products"""
         return _record_primer_products(self._dev("ribbit_hip_record_primer_products"), pairs, params)
+
+    def record_pair_amplicons(self, pairs, motifs, record: int = 0, params: ProductParams | None = None) -> np.ndarray:
+        """Every primer pair typed on the loaded record, which may be any record, on the GPU (ribbit_hip_record_pair_amplicons); see
+        host_record_pair_amplicons"""
+        return _record_pair_amplicons(self._dev("ribbit_hip_record_pair_amplicons"), pairs, motifs, record, params)
 
     def record_specific_primer_pairs(self, intervals, targets, params: PrimerParams | None = None, pair_params: PrimerPairParams | None = None,
                                      product_params: ProductParams | None = None):

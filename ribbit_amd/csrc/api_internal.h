@@ -24,7 +24,8 @@
 //   api_primer_products.cpp  the sites of oligos on either strand of the record and the products of primer pairs among them (primer_products.hip), their host twins, the text
 //   api_primer_specific.cpp  the best primer pair of every target that amplifies nothing else in the record (primer_specific.hip, with primer_products.hip's site scan), its host twin, the text
 //   api_primer_genome.cpp    a target's two shortlists as they leave their record, their pairs judged on any loaded record (primer_specific.hip), the host twins, the sum over records, the choice
-// The last fifteen are the row outputs: their buffers are the handle's RowBufs `rows`, where all device work of a call is carved from
+//   api_amplicons.cpp        every chosen pair typed on any loaded record: its first product and the repeat tract inside it (amplicons.hip, with primer_products.hip's site scan), its host twin, the sum over records, the text
+// The last sixteen are the row outputs: their buffers are the handle's RowBufs `rows`, where all device work of a call is carved from
 // one buffer by the layout its .hip file states (kernels.h); best, classes, compound, interruptions, nearest, primers and primer pairs stage their inputs through stage_down, what their host
 // sides share is below (hand_out, clipped_sorted_rows), what their kernels share is row_kernels.h, and the BED text they read and
 // write (the row format, the reader in pieces, the writer in pieces) is
@@ -498,6 +499,8 @@ struct RibbitHandle {
         // the shortlists that leave the record and their verdicts on a record (api_primer_genome.cpp): the targets' records on their
         // way up, a batch's lists and side counts (or verdicts) as the device holds them behind them
         PinnedBuf<uint8_t> h_shortlists, h_verdicts;
+        // the pairs typed on a record (api_amplicons.cpp): one RibbitRowAmplicon per pair on its way up
+        PinnedBuf<uint8_t> h_amplicons;
         // the blocks' base counts | their prefix, which belongs to the record (rec.base_prefix_valid, api_composition.cpp)
         DevBuf<rb::BaseSums> d_comp_sums;
         size_t rep_budget = 0;           // text budget of one batch of repeat sequences in bytes (0: REPEAT_TEXT_BUDGET)

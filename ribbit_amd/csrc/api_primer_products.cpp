@@ -377,6 +377,10 @@ namespace rbapi {
 
 int check_primer_product_params(const RibbitProductParams *p) { return check_product_params(p); }
 
+int check_product_pairs(const RibbitRowPrimerPair *pairs, size_t n, const RibbitProductParams *params) { return check_pairs(pairs, n, params); }
+
+void pair_oligos(const RibbitRowPrimerPair &pair, RibbitOligo &a, RibbitOligo &b) { oligos_of(pair, a, b); }
+
 void host_pair_oligos(const RibbitRowPrimerPair &pair, std::string &a, std::string &b) {
     RibbitOligo oa, ob;
     oligos_of(pair, oa, ob);

@@ -586,6 +586,28 @@ hipError_t launch_listed_oligos(const RibbitPrimer *lists, int64_t n_targets, ui
 hipError_t launch_shortlist_verdicts(const RibbitPrimer *lists, int64_t n_targets, bool home, const RibbitPrimerPairParams &pair, const RibbitProductParams &product,
                                      uint8_t *work, size_t work_bytes, const VerdictLayout &at, const int32_t *site_lists, hipStream_t stream);
 
+// amplicons.hip: n_pairs >= 1 primer pairs typed on the loaded record (length > 0), which may be any record
+// (api_amplicons.cpp: ribbit_hip_record_pair_amplicons; include/ribbit_hip.h has the contract).  The api file serves the pairs in
+// batches and sizes the layout by the largest.  A batch takes the launches in this order, and the host reads
+// primer_products.hip's header between the first two:
+//   launch_product_uniques, launch_product_scan   (primer_products.hip) on the batch's oligos, two per pair that has any, with
+//                              work + product_work as their work buffer and `product` as their layout
+//   launch_pair_amplicons      pair_amplicons_kernel, one lane per pair: the four counts, products and the first product
+//                              (product_walk.h); then amplicon_tracts_kernel, one wavefront per pair with a product: the repeat
+//                              tract inside it, from the bit planes
+struct AmpliconLayout : WorkLayout {
+    size_t rows;          // the result, n_pairs RibbitRowAmplicon
+    size_t product_work;  // the work buffer of primer_products.hip's launches for 2 n_pairs oligos ...
+    ProductLayout product;              // ... and its layout (offsets from product_work)
+};
+AmpliconLayout amplicon_layout(int64_t n_pairs);
+// pairs: four ints per pair on the device, {a's oligo, b's oligo, -1, -1}; a's oligo -1: no pair.  pool, offsets: the motifs of
+// these pairs on the device, motif i at pool[offsets[i] - offsets[0] ..), 1 .. 1023 letters of ACGT each (checked by the caller).
+// site_lists: what launch_product_scan filled.
+hipError_t launch_pair_amplicons(const DevicePlanes &pl, const int32_t *pairs, int64_t n_pairs, const uint8_t *pool, const int32_t *offsets, int32_t record,
+                                 const RibbitProductParams &prm, uint8_t *work, size_t work_bytes, const AmpliconLayout &at, const int32_t *site_lists,
+                                 hipStream_t stream);
+
 // profiling aid: reads nwords dwords of src with one coalesced dword per lane (known byte count)
 void launch_calib_stream_read(const uint32_t *src, int64_t nwords, uint32_t *sink, hipStream_t stream);
 

@@ -196,5 +196,9 @@ int check_primer_product_params(const RibbitProductParams *p);
 void host_pair_oligos(const RibbitRowPrimerPair &pair, std::string &a, std::string &b);
 HostSites host_oligo_sites(const unsigned char *seq, int64_t length, const std::string &oligo, const RibbitProductParams &prm);
 RibbitRowProducts host_products_among(const HostSites &a, const HostSites &b, int32_t ka, int32_t kb, int32_t left_start, int32_t right_start, const RibbitProductParams &prm);
+// ... and what api_amplicons.cpp takes besides: the check of a call's pairs and parameters with its wording; a pair's two oligos as
+// the device takes them
+int check_product_pairs(const RibbitRowPrimerPair *pairs, size_t n, const RibbitProductParams *params);
+void pair_oligos(const RibbitRowPrimerPair &pair, RibbitOligo &a, RibbitOligo &b);
 
 }  // namespace rbapi

@@ -65,6 +65,11 @@
 // (ribbit_hip_record_shortlist_verdicts, as home for the record's own targets), the judgements are summed
 // (ribbit_primer_verdicts_merge), and then the pairs are chosen and written (ribbit_primer_shortlists_choose,
 // ribbit_bed_primer_specific_text): write_primer_genome.
+// --marker-fasta with --marker-bed types --primer-genome-bed's chosen pairs on a second assembly: the second pass keeps every
+// record's chosen pairs and lines; a third pass reads the other FASTA, loads every record of it without a scan, places every pair's
+// first product and measures the repeat tract inside it (ribbit_hip_record_pair_amplicons, the record's index as label), sums in
+// record order (ribbit_pair_amplicons_merge) and writes the home records' rows in input order (ribbit_bed_marker_text):
+// write_markers.  It is no row output of the table: it has two files and no text per record.
 // The BED rows are read back once per record, however many of the twenty-one are asked for.
 //
 // These twenty-one are the ROW OUTPUTS, and each is described once, by its entry of kOutputs below: its file option, its stage (enum
@@ -117,14 +122,14 @@ void check(int rc) {
 }
 
 // The stages of a record: the six every record goes through, then one per row output, in the order of kOutputs.
-enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, OVERLAP, BEST, CLASSES, COMPOUND, INTERRUPTIONS, NEAREST, COMPOSITION, PRIMERS, PRIMER_PAIRS, PRIMER_PRODUCTS, PRIMER_SPECIFIC, PRIMER_GENOME, N_STAGES };
+enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, OVERLAP, BEST, CLASSES, COMPOUND, INTERRUPTIONS, NEAREST, COMPOSITION, PRIMERS, PRIMER_PAIRS, PRIMER_PRODUCTS, PRIMER_SPECIFIC, PRIMER_GENOME, MARKERS, N_STAGES };
 constexpr int N_FIXED_STAGES = MASK;
 // a stage's key in --timing's stage_ms_summed_over_records and its label in the RIBBIT_PROFILE line
 const struct { const char *key, *label; } kStageNames[N_STAGES] = {
     {"load", "load"}, {"perfect", "perfect"}, {"substitutions", "substitutions"}, {"anchored", "anchored"}, {"dispatch", "dispatch"},
     {"refine_and_bed", "refine+BED"}, {"mask", "mask"}, {"repeats", "repeats"}, {"loci", "loci"}, {"density", "density"}, {"overlap", "overlap"},
     {"best", "best"}, {"classes", "classes"}, {"compound", "compound"}, {"interruptions", "interruptions"}, {"nearest", "nearest"}, {"composition", "composition"}, {"primers", "primers"},
-    {"primer_pairs", "primer_pairs"}, {"primer_products", "primer_products"}, {"primer_specific", "primer_specific"}, {"primer_genome", "primer_genome"}};
+    {"primer_pairs", "primer_pairs"}, {"primer_products", "primer_products"}, {"primer_specific", "primer_specific"}, {"primer_genome", "primer_genome"}, {"markers", "markers"}};
 
 // wall time per stage, summed over the records (--timing, RIBBIT_PROFILE=1)
 double g_stage_ms[N_STAGES] = {};
@@ -744,6 +749,7 @@ struct Options {
     int jobs = 0;                                 // records in flight PER DEVICE; 0 = automatic
     std::string timing;                           // --timing FILE: a JSON record of the run (the reference has cerr progress lines only)
     std::string other_path;                       // --overlap-with FILE: the intervals the overlap and nearest outputs compare the rows with
+    std::string marker_fasta, marker_bed;         // --marker-fasta FILE --marker-bed FILE: the second assembly, and the chosen pairs typed on it
     std::array<std::string, N_OUTPUTS> row_path;                  // the row outputs' files, as kOutputs orders them (empty: off)
     std::array<std::array<bool, MAX_QUALIFIERS>, N_OUTPUTS> qualifier_given{};
     Settings settings;
@@ -769,6 +775,17 @@ const char *kHelp =
     "                                keep the input order\n"
     "  --timing arg                  (ribbit-hip) write a JSON record of the run to this file: records, bases, wall time and\n"
     "                                the wall time per stage summed over the records\n"
+    "  --marker-fasta arg            (ribbit-hip) a second assembly (another individual, strain or haplotype, the previous\n"
+    "                                release) that --marker-bed types --primer-genome-bed's chosen pairs on\n"
+    "  --marker-bed arg              (ribbit-hip) also write the rows of --primer-genome-bed (chosen with --primer-genome-flank,\n"
+    "                                whether or not that file is asked for) to this file with 20 columns: the eight primer\n"
+    "                                columns and the designed product; the products the pair has on all records of\n"
+    "                                --marker-fasta ('.' where a primer has more than 64 sites on a strand of one record);\n"
+    "                                and, only where that is exactly one product: the record's name, start, end, orientation\n"
+    "                                (+, -; l, r: one primer with itself), size, size minus the designed product, then start,\n"
+    "                                end, bases and whole units of the longest tract of the row's motif inside the product\n"
+    "                                ('.' without one). A marker is worth ordering when that difference is not 0. The other\n"
+    "                                FASTA is read after the input has been read twice, on the first GPU\n"
     "  --masked-fasta arg            (ribbit-hip) also write the records to this FASTA file with the bases of their BED rows\n"
     "                                masked; a header keeps the record name only (the description after the first space\n"
     "                                is not kept)\n"
@@ -925,7 +942,7 @@ int parse_arguments(int argc, char **argv, Options &o) {
     static const std::map<std::string, std::string> longs = {
         {"help", "h"}, {"input-file", "i"}, {"output-file", "o"}, {"min-motif-length", "m"}, {"max-motif-length", "M"},
         {"purity", "p"}, {"min-length", "l"}, {"min-units", "U"}, {"perfect-units", "P"}, {"device", "D"}, {"jobs", "J"}, {"devices", "G"}, {"timing", "T"},
-        {"overlap-with", "W"}};
+        {"overlap-with", "W"}, {"marker-fasta", "F"}, {"marker-bed", "K"}};
     bool help = false;
     for (int a = 1; a < argc; ++a) {
         std::string arg = argv[a], key, value;
@@ -982,6 +999,8 @@ int parse_arguments(int argc, char **argv, Options &o) {
         else if (key == "J") o.jobs = std::atoi(value.c_str());
         else if (key == "T") o.timing = value;
         else if (key == "W") { if (value.empty()) die("--overlap-with wants a file name"); o.other_path = value; }
+        else if (key == "F") { if (value.empty()) die("--marker-fasta wants a file name"); o.marker_fasta = value; }
+        else if (key == "K") { if (value.empty()) die("--marker-bed wants a file name"); o.marker_bed = value; }
         else if (key == "G") { if (!parse_device_list(value, o.devices)) die("--devices wants a comma separated list of GPU ordinals, got '" + value + "'"); }
     }
     if (help) { std::cerr << kHelp << "\n"; return 0; }                       // ribbit.cpp:114-117
@@ -993,6 +1012,8 @@ int parse_arguments(int argc, char **argv, Options &o) {
     if (!o.other_path.empty() && !needs_other) die("--overlap-with needs --overlap-bed or --overlap-summary");
     for (size_t k = 0; k < N_OUTPUTS; ++k)
         if (kOutputs[k].needs_other && !o.row_path[k].empty() && o.other_path.empty()) die(std::string("--") + kOutputs[k].option + " needs --overlap-with");
+    if (!o.marker_fasta.empty() && o.marker_bed.empty()) die("--marker-fasta needs --marker-bed");
+    if (!o.marker_bed.empty() && o.marker_fasta.empty()) die("--marker-bed needs --marker-fasta");
     if (o.fasta.empty()) { std::cerr << "ERROR: Please specify an input fasta file!\n"; return 0; }   // :122-126
     return 1;
 }
@@ -1196,7 +1217,15 @@ void process_sequence(RibbitHandle *h, const RibbitRefineParams &prm, const std:
 // The second pass of --primer-genome-bed, after the last record, on the handle h: `states` holds what produce_primer_genome made of
 // every record, in input order.  The FASTA is read again; every record is loaded and nothing is scanned; all records' lists are
 // judged on it, the record's own as home; the verdicts are summed; then every record's pairs are chosen and its text is written.
-void write_primer_genome(RibbitHandle *h, const std::string &fasta, const std::vector<std::string> &states, std::ostream &file) {
+// file: --primer-genome-bed's, or null when only --marker-bed asked for the selection; keep: where --marker-bed's pass finds every
+// record's chosen pairs and lines (null: not kept).
+struct KeptMarkers {
+    std::vector<RibbitRowPrimerPair> pairs;      // of all records, in input order ...
+    std::vector<size_t> first{0};                // ... record k's are [first[k], first[k + 1])
+    std::string lines;                           // their BED lines, one behind the other
+    std::vector<size_t> line_at{0};              // record k's lines are lines[line_at[k], line_at[k + 1])
+};
+void write_primer_genome(RibbitHandle *h, const std::string &fasta, const std::vector<std::string> &states, std::ostream *file, KeptMarkers *keep) {
     StageClock c(PRIMER_GENOME);
     std::vector<size_t> first(states.size() + 1, 0);      // record k's targets are [first[k], first[k + 1])
     for (size_t k = 0; k < states.size(); ++k) {
@@ -1255,11 +1284,73 @@ void write_primer_genome(RibbitHandle *h, const std::string &fasta, const std::v
         char *text = nullptr;
         size_t len = 0;
         int rc = ribbit_primer_shortlists_choose(&lists[first[k]], &sum[first[k]], n, &pair, &pairs, &products, &specific);
-        if (rc == RIBBIT_OK) rc = ribbit_bed_primer_specific_text(lines, (size_t)head[1], pairs, products, specific, n, &text, &len);
+        if (rc == RIBBIT_OK && file) rc = ribbit_bed_primer_specific_text(lines, (size_t)head[1], pairs, products, specific, n, &text, &len);
+        if (rc == RIBBIT_OK && keep) {
+            keep->pairs.insert(keep->pairs.end(), pairs, pairs + n);
+            keep->first.push_back(keep->pairs.size());
+            keep->lines.append(lines, (size_t)head[1]);
+            keep->line_at.push_back(keep->lines.size());
+        }
         ribbit_primer_genome_free(pairs);
         ribbit_primer_genome_free(products);
         ribbit_primer_genome_free(specific);
         check(rc);
+        if (file) file->write(text, (std::streamsize)len);
+        ribbit_text_free(text);
+    }
+}
+
+// The third pass, --marker-bed's, after write_primer_genome, on the handle h: `kept` holds the chosen pairs and the lines of every
+// home record that has any, in input order.  The other FASTA is read; every record of it is loaded and nothing is scanned; all
+// kept pairs are typed on it in one call, with the record's index as label; the amplicons are summed in record order, so a pair
+// keeps its first record's product; then every home record's text is written.
+void write_markers(RibbitHandle *h, const std::string &fasta, const KeptMarkers &kept, std::ostream &file) {
+    StageClock c(MARKERS);
+    const size_t total = kept.pairs.size();
+    if (total == 0) return;      // (no row anywhere: the file stays empty)
+    struct Motifs {
+        char *pool = nullptr;
+        int32_t *offsets = nullptr;
+        ~Motifs() { ribbit_text_free(pool); ribbit_intervals_free(offsets); }
+    } motifs;
+    size_t n_motifs = 0;
+    check(ribbit_bed_motifs(kept.lines.data(), kept.lines.size(), &motifs.pool, &motifs.offsets, &n_motifs));
+    if (n_motifs != total) throw PathError{"--marker-bed: the kept lines are not one per chosen pair"};
+    RibbitProductParams product;
+    ribbit_product_params_default(&product);
+    std::vector<RibbitRowAmplicon> sum(total);
+    std::string names;
+    std::vector<int32_t> name_at{0};
+    RibbitFastaReader *reader = nullptr;
+    if (ribbit_fasta_open(fasta.c_str(), 1, &reader) != RIBBIT_OK) throw PathError{std::string("--marker-fasta: ") + ribbit_fasta_last_error()};
+    struct Close { RibbitFastaReader *r; ~Close() { ribbit_fasta_close(r); } } close{reader};
+    for (size_t k = 0;; ++k) {
+        const char *name = "", *bases = nullptr;
+        int64_t length = 0;
+        int is_last = 1;
+        const int got = ribbit_fasta_next(reader, &name, &bases, &length, &is_last);
+        if (got < 0) throw PathError{std::string("--marker-fasta: ") + ribbit_fasta_last_error()};
+        if (got == 0) break;
+        names += name;
+        if (names.size() > (size_t)INT32_MAX || k >= (size_t)INT32_MAX) throw PathError{"--marker-fasta: the records' names are 2^31 bytes or more"};
+        name_at.push_back((int32_t)names.size());
+        const RibbitRowAmplicon *rows = nullptr;
+        int rc = ribbit_hip_load_record_pinned(h, bases, length);
+        if (rc == RIBBIT_OK) rc = ribbit_hip_record_pair_amplicons(h, kept.pairs.data(), total, motifs.pool, motifs.offsets, (int32_t)k, &product, &rows);
+        if (rc == RIBBIT_OK) {
+            if (k == 0) std::memcpy(sum.data(), rows, total * sizeof(RibbitRowAmplicon));
+            else rc = ribbit_pair_amplicons_merge(sum.data(), rows, total);
+        }
+        ribbit_fasta_release(reader, bases);
+        check(rc);
+        if (is_last) break;
+    }
+    for (size_t k = 0; k + 1 < kept.first.size(); ++k) {
+        const size_t from = kept.first[k], n = kept.first[k + 1] - from;
+        char *text = nullptr;
+        size_t len = 0;
+        check(ribbit_bed_marker_text(kept.lines.data() + kept.line_at[k], kept.line_at[k + 1] - kept.line_at[k], &kept.pairs[from], &sum[from], names.data(), name_at.data(),
+                                     name_at.size() - 1, n, &text, &len));
         file.write(text, (std::streamsize)len);
         ribbit_text_free(text);
     }
@@ -1286,6 +1377,17 @@ int main(int argc, char **argv) {
         if (!row_on[k]) continue;
         row_file[k].open(opt.row_path[k], std::ios::binary);
         if (!row_file[k]) die(std::string("--") + kOutputs[k].option + ": cannot open '" + opt.row_path[k] + "' for writing");
+    }
+
+    // --marker-bed needs --primer-genome-bed's selection, whether or not that file is written: pipe_on says what the records produce
+    const bool markers_on = !opt.marker_bed.empty();
+    std::array<bool, N_OUTPUTS> pipe_on = row_on;
+    pipe_on[GENOME_OUTPUT] = row_on[GENOME_OUTPUT] || markers_on;
+    std::ofstream marker_file;
+    if (markers_on) {
+        if (!std::ifstream(opt.marker_fasta, std::ios::binary)) die("--marker-fasta: cannot open '" + opt.marker_fasta + "' for reading");
+        marker_file.open(opt.marker_bed, std::ios::binary);
+        if (!marker_file) die("--marker-bed: cannot open '" + opt.marker_bed + "' for writing");
     }
 
     const auto t_run0 = std::chrono::steady_clock::now();
@@ -1348,7 +1450,7 @@ int main(int argc, char **argv) {
             std::cerr << it->second.log;
             out.write(it->second.bed.data(), (std::streamsize)it->second.bed.size());
             for (size_t k = 0; k < N_OUTPUTS; ++k) {
-                if (k == GENOME_OUTPUT && row_on[k]) genome_states.push_back(std::move(it->second.rows[k]));
+                if (k == GENOME_OUTPUT && pipe_on[k]) genome_states.push_back(std::move(it->second.rows[k]));
                 else row_file[k].write(it->second.rows[k].data(), (std::streamsize)it->second.rows[k].size());
             }
             done.erase(it);
@@ -1388,7 +1490,7 @@ int main(int argc, char **argv) {
             cv.notify_all();
             std::ostringstream bed, log;
             std::array<std::string, N_OUTPUTS> texts;      // (kept in memory until the record's turn to be written)
-            const RowJobs row_jobs(row_on, [&texts](size_t k) { return [&texts, k](const char *p, size_t n) { texts[k].append(p, n); }; });
+            const RowJobs row_jobs(pipe_on, [&texts](size_t k) { return [&texts, k](const char *p, size_t n) { texts[k].append(p, n); }; });
             bool ok = true;
             std::string why;
             {
@@ -1471,17 +1573,19 @@ int main(int argc, char **argv) {
             // (every record the reader hands out has its row outputs but the nameless empty one of a file without records, Q4)
             const bool real_last = !(last_name.empty() && last_length == 0);
             std::string last_state;
-            const RowJobs row_jobs(real_last ? row_on : std::array<bool, N_OUTPUTS>{}, [&row_file, &last_state](size_t k) {
+            const RowJobs row_jobs(real_last ? pipe_on : std::array<bool, N_OUTPUTS>{}, [&row_file, &last_state](size_t k) {
                 return [&row_file, &last_state, k](const char *p, size_t n) {
                     if (k == GENOME_OUTPUT) last_state.append(p, n);
                     else row_file[k].write(p, (std::streamsize)n);
                 };
             });
             process_sequence(h, prm, last_name, last_bases ? last_bases : kNoBases, last_length, out, std::cerr, opt.settings, row_jobs, &helpers);
-            if (row_on[GENOME_OUTPUT]) {
+            if (pipe_on[GENOME_OUTPUT]) {
                 if (real_last) genome_states.push_back(std::move(last_state));
                 if (reader) { ribbit_fasta_close(reader); reader = nullptr; }      // (the last record's bases are no longer needed)
-                write_primer_genome(h, opt.fasta, genome_states, row_file[GENOME_OUTPUT]);
+                KeptMarkers kept;
+                write_primer_genome(h, opt.fasta, genome_states, row_on[GENOME_OUTPUT] ? &row_file[GENOME_OUTPUT] : nullptr, markers_on ? &kept : nullptr);
+                if (markers_on) write_markers(h, opt.marker_fasta, kept, marker_file);
             }
         } catch (const PathError &e) { failed = true; failure = e.what; }
     }
@@ -1508,13 +1612,15 @@ int main(int argc, char **argv) {
            << ", \"min_motif\": " << opt.min_motif << ", \"max_motif\": " << opt.max_motif << ", \"devices\": " << ndev << ", \"jobs_per_device\": " << jobs
            << ", \"stage_ms_summed_over_records\": {";
         for (int s = 0; s < N_FIXED_STAGES; ++s) tf << (s ? ", \"" : "\"") << kStageNames[s].key << "\": " << g_stage_ms[s];
-        for (const Stage s : stages_on(row_on)) tf << ", \"" << kStageNames[s].key << "\": " << g_stage_ms[s];
+        for (const Stage s : stages_on(pipe_on)) tf << ", \"" << kStageNames[s].key << "\": " << g_stage_ms[s];
+        if (markers_on) tf << ", \"" << kStageNames[MARKERS].key << "\": " << g_stage_ms[MARKERS];
         tf << "}}\n";
     }
     if (std::getenv("RIBBIT_PROFILE")) {
         std::cerr << "[stages, ms over all records]";
         for (int s = 0; s < N_FIXED_STAGES; ++s) std::cerr << (s ? "  " : " ") << kStageNames[s].label << " " << g_stage_ms[s];
-        for (const Stage s : stages_on(row_on)) std::cerr << "  " << kStageNames[s].label << " " << std::to_string(g_stage_ms[s]);
+        for (const Stage s : stages_on(pipe_on)) std::cerr << "  " << kStageNames[s].label << " " << std::to_string(g_stage_ms[s]);
+        if (markers_on) std::cerr << "  " << kStageNames[MARKERS].label << " " << std::to_string(g_stage_ms[MARKERS]);
         std::cerr << "\n";
     }
     size_t ignored = 0, ignored_names = 0;
