@@ -1488,12 +1488,64 @@ void ribbit_debug_set_merge_min_range(size_t calls);
  * list-head writes that changed an entry, first range empty (0/1) | parallel passes of the stage << 8}. */
 void ribbit_debug_last_merge(int stage, int32_t out[5]);
 /* Test hook: the anchored stage's merge runs its first parallel pass on the GPU for stages of 2^20 kept calls and more
- * (anchored_merge.hip: one lane per range of some 64 calls, the host threads taking the ranges of more than 192 calls meanwhile;
- * environment RIBBIT_DEVICE_MERGE_MIN / RIBBIT_DEVICE_MERGE_RANGE / RIBBIT_DEVICE_MERGE_MAX_CALLS change the three numbers).
- * out = {ranges the device merged, ranges it was given but left to the host threads (candidate lists beyond its LDS, budget of
+ * (anchored_merge.hip: one lane per range of some 64 calls; environment RIBBIT_DEVICE_MERGE_MIN / RIBBIT_DEVICE_MERGE_RANGE change
+ * the two numbers).  The ranges are put in the order of the work they are expected to be: the lanes take them from the light end,
+ * and only those expected to need at most 6000 passes of a lane's loop; the host threads take ranges from the heavy end while the
+ * kernel runs, until the two meet (api_merge.cpp, parallel_merge.h: AnchoredDevicePass).
+ * out = {ranges the device merged, ranges it was given but left to the host threads (candidate lists beyond its scratch, budget of
  * passes), ranges the host threads merged meanwhile, ranges of the stage, ranges merged again by the validation walk} of the
  * calling thread's last anchored merge; the first three are zero when the device pass did not run. */
 void ribbit_debug_last_device_merge(int32_t out[5]);
+
+/* Test hook: the first parallel pass of the anchored stage's merge, alone, on lists, planes and calls the caller made.
+ * perfect / subst: the two seed lists as they stand before the stage (types P and N in the perfect list, S, Q and N in the
+ * substitution list: RIBBIT_E_ARG otherwise -- the reference retires a candidate in the list its TYPE names, so a seed typed for
+ * the other list is never retired and its call starts again without end); calls: the full anchored call list in the
+ * scanner's order, as ribbit_host_replay_calls takes it (the stage's length filter and cursor bounds apply); xa: the composed
+ * planes of min_motif..max_motif, xa_stride words each (at least length / 32 + 1).  Every interval must lie in [0, length] and
+ * every motif size in the handle-independent range of `params`: RIBBIT_E_ARG otherwise.
+ * The ranges are cut and their start cursors computed as the production device pass prepares them, with knobs.calls_per_range
+ * calls to a range.  knobs.where: RIBBIT_MERGE_ON_LANES -- the kernel, with no host thread taking ranges beside it (h: an open
+ * handle; a loaded record stays usable, the call uploads into buffers of its own and the handle's merge buffers);
+ * RIBBIT_MERGE_ON_HOST -- the host workers (h may be null: no GPU is touched).  Both start from the lists as given.
+ * knobs: resident_waves, max_passes, head_cap (0: the production values), log_cap (0: the production formula), device_limit
+ * (how many ranges, from the light end of the work order, the lanes may take; < 0: all), only_range (>= 0: only that range
+ * runs; -1: all).
+ * knobs.full == 0 (raw): stops after the pass.  out->ran: the pass ran at all (0: a log overflowed or the device declined; nothing
+ * else but cuts, first and cursors0 is then filled); per range k < n_ranges: cuts[k], first[k] (.. first[n_ranges] = kept
+ * calls), cursors0[2k..], and range[12 k ..] = {status (AM_* bits, all ones: not run), offset into own, entries in own (without
+ * the sentinel), guard hits low / high, final cursor perfect / subst, head_reads[0] low / high, head_reads[1] low / high, 0};
+ * undo / reads: 4 words {range, list (0 perfect, 1 substitution), index, old type / was live}; heads: 8 words {range, list,
+ * index, start, end, motif size, type, changed_then}.  The lists are left as given.
+ * knobs.full != 0: the stage goes on through the unchanged validation walk, the ranges done again, the join and the flush;
+ * out->lists holds the three lists (dispatch empty) and the guard count, out->device_merge what ribbit_debug_last_device_merge
+ * reports.
+ * out->caps: the kernel's constants {AM_PS_CAP, AM_CAND_CAP, AM_PS_SPILL, AM_CAND_SPILL, AM_CHILD_CAP, AM_COV_CAP,
+ * AM_RESIDENT_WAVES, AM_MAX_PASSES, AM_SCRATCH_FULL, AM_LOG_FULL, AM_BAD_PLANE, AM_RUNAWAY, AM_TOO_SLOW, 0, 0, 0}.
+ * Release with ribbit_debug_merge_ranges_free. */
+enum { RIBBIT_MERGE_ON_LANES = 0, RIBBIT_MERGE_ON_HOST = 1 };
+typedef struct RibbitDebugMergeKnobs {
+    int32_t where, full;
+    int32_t calls_per_range, resident_waves, max_passes, head_cap;
+    int64_t log_cap, device_limit, only_range;
+} RibbitDebugMergeKnobs;
+typedef struct RibbitDebugMergeRanges {
+    int32_t ran, reserved;
+    int32_t caps[16];
+    size_t n_ranges;
+    int32_t *cuts, *first, *cursors0, *range;
+    RibbitSeed *own; size_t n_own;
+    int32_t *undo; size_t n_undo;
+    int32_t *reads; size_t n_reads;
+    int32_t *heads; size_t n_heads;
+    RibbitSeedLists lists;
+    int32_t device_merge[5];
+} RibbitDebugMergeRanges;
+int ribbit_hip_debug_merge_ranges(RibbitHandle *h, const RibbitScanParams *params, int64_t length,
+                                  const RibbitSeed *perfect, size_t n_perfect, const RibbitSeed *subst, size_t n_subst,
+                                  const RibbitCall *calls, size_t n_calls, const uint32_t *xa, size_t xa_stride,
+                                  const RibbitDebugMergeKnobs *knobs, RibbitDebugMergeRanges *out);
+void ribbit_debug_merge_ranges_free(RibbitDebugMergeRanges *out);
 /* Test hook: in how many independent ranges the calling thread's last dispatch merge (fasta_utils.cpp:187-224) ran; 1 = the
  * sequential merge (no cuts, or a list did not split cleanly at them). */
 int32_t ribbit_debug_last_dispatch_ranges(void);

@@ -142,6 +142,28 @@ class DebugPairing(C.Structure):
                 ("summary", C.c_uint32), ("overflow", C.c_uint32), ("table_status", C.c_uint32)]
 
 
+class SeedLists(C.Structure):
+    """RibbitSeedLists (malloc'ed arrays returned by ribbit_host_replay_calls)."""
+    _fields_ = [("perfect", C.c_void_p), ("n_perfect", C.c_size_t), ("subst", C.c_void_p), ("n_subst", C.c_size_t),
+                ("anchored", C.c_void_p), ("n_anchored", C.c_size_t), ("dispatch", C.c_void_p), ("n_dispatch", C.c_size_t),
+                ("guard_hits", C.c_int64)]
+
+
+class DebugMergeKnobs(C.Structure):
+    """RibbitDebugMergeKnobs: where and how ribbit_hip_debug_merge_ranges runs the first pass (include/ribbit_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("where", "full", "calls_per_range", "resident_waves", "max_passes", "head_cap")] + \
+               [(n, C.c_int64) for n in ("log_cap", "device_limit", "only_range")]
+
+
+class DebugMergeRanges(C.Structure):
+    """RibbitDebugMergeRanges: what ribbit_hip_debug_merge_ranges fills (include/ribbit_hip.h)."""
+    _fields_ = [("ran", C.c_int32), ("reserved", C.c_int32), ("caps", C.c_int32 * 16), ("n_ranges", C.c_size_t),
+                ("cuts", C.c_void_p), ("first", C.c_void_p), ("cursors0", C.c_void_p), ("range", C.c_void_p),
+                ("own", C.c_void_p), ("n_own", C.c_size_t), ("undo", C.c_void_p), ("n_undo", C.c_size_t),
+                ("reads", C.c_void_p), ("n_reads", C.c_size_t), ("heads", C.c_void_p), ("n_heads", C.c_size_t),
+                ("lists", SeedLists), ("device_merge", C.c_int32 * 5)]
+
+
 class RefineParams(C.Structure):
     """RibbitRefineParams (MINIMUM_LENGTH / PERFECT_UNITS tables, purity, cones threshold)."""
     _fields_ = [("min_length", C.c_int32 * 1024), ("perfect_units", C.c_int32 * 1024),
@@ -152,13 +174,6 @@ class Alignment(C.Structure):
     """RibbitAlignment (StripedSmithWaterman::Alignment without the strings)."""
     _fields_ = [(n, C.c_int32) for n in ("sw_score", "sw_score_next_best", "ref_begin", "ref_end", "query_begin",
                                          "query_end", "ref_end_next_best", "mismatches", "flag", "cigar_len")]
-
-
-class SeedLists(C.Structure):
-    """RibbitSeedLists (malloc'ed arrays returned by ribbit_host_replay_calls)."""
-    _fields_ = [("perfect", C.c_void_p), ("n_perfect", C.c_size_t), ("subst", C.c_void_p), ("n_subst", C.c_size_t),
-                ("anchored", C.c_void_p), ("n_anchored", C.c_size_t), ("dispatch", C.c_void_p), ("n_dispatch", C.c_size_t),
-                ("guard_hits", C.c_int64)]
 
 
 class ChunkCalls(C.Structure):
@@ -255,6 +270,8 @@ def _signatures() -> dict:
         "ribbit_hip_debug_pair_events": (st, [vp, vp, sz, i64, vp, sz, psz, P(C.c_uint32)]),
         "ribbit_hip_debug_pair_events_sharded": (st, [vp, vp, vp, sz, i64, i64, i64, i64, P(DebugPairing)]),
         "ribbit_hip_debug_stream_read": (st, [vp, i64, P(i64)]),
+        "ribbit_hip_debug_merge_ranges": (st, [vp, scan, i64, vp, sz, vp, sz, vp, sz, vp, sz, P(DebugMergeKnobs), P(DebugMergeRanges)]),
+        "ribbit_debug_merge_ranges_free": (None, [P(DebugMergeRanges)]),
         "ribbit_hip_ssw_passes": (st, [vp, vp, sz, cp, sz, i32, vp]),
         "ribbit_hip_ssw_align_jobs": (st, [vp, vp, sz, cp, sz, i32, vp, vp, sz, vp, vp]),
         "ribbit_ssw_align": (st, [cp, i32, cp, i32, i32, P(Alignment), cp, sz]),
@@ -678,6 +695,62 @@ def last_device_merge():
     ran, ranges of the stage, ranges merged again by the validation walk) of the calling thread's last anchored-stage merge; the
     first three are zero when the merge ran on the host threads alone"""
     return _counters("ribbit_debug_last_device_merge", C.c_int32, 5)
+
+
+MERGE_ON_LANES, MERGE_ON_HOST = 0, 1      # RIBBIT_MERGE_ON_LANES / RIBBIT_MERGE_ON_HOST
+MERGE_CAPS = ("ps_cap", "cand_cap", "ps_spill", "cand_spill", "child_cap", "cov_cap", "resident_waves", "max_passes",
+              "scratch_full", "log_full", "bad_plane", "runaway", "too_slow")
+
+
+def debug_merge_ranges(scanner, min_motif: int, max_motif: int, length: int, perfect, subst, calls, xa, xa_stride: int, *, where: int,
+                       full: bool = False, calls_per_range: int = 1, resident_waves: int = 0, max_passes: int = 0, head_cap: int = 0,
+                       log_cap: int = 0, device_limit: int = -1, only_range: int = -1) -> dict:
+    """ribbit_hip_debug_merge_ranges (test hook): the first parallel pass of the anchored stage's merge on lists, planes (the
+    words and stride of pack_bit_planes) and calls made by the caller, on the lanes of `scanner` (MERGE_ON_LANES) or on the host
+    workers (MERGE_ON_HOST; scanner may be None).  -> dict: ran, caps (by the names of MERGE_CAPS), cuts, first, cursors0, and
+    raw (full False): ranges = one dict per range (status, own, guard_hits, cursor, head_reads, undo, reads, heads: the logs as
+    sorted lists of tuples without the range); full: lists (as host_replay_calls returns them) and device_merge."""
+    params = _scan_params(min_motif, max_motif)
+    p, s = _records(perfect, SEED_DT), _records(subst, SEED_DT)
+    c, words = _records(calls, CALL_DT), np.ascontiguousarray(xa, dtype="<u4")
+    knobs = DebugMergeKnobs(int(where), int(bool(full)), int(calls_per_range), int(resident_waves), int(max_passes), int(head_cap),
+                            int(log_cap), int(device_limit), int(only_range))
+    out = DebugMergeRanges()
+    if words.size < (max_motif - min_motif + 1) * xa_stride:
+        raise ValueError("xa holds fewer words than a plane per motif size")
+    _ok("ribbit_hip_debug_merge_ranges", load_library().ribbit_hip_debug_merge_ranges(
+        scanner._h if scanner is not None else None, C.byref(params), int(length), _ptr(p), len(p), _ptr(s), len(s), _ptr(c), len(c),
+        words.ctypes.data, int(xa_stride), C.byref(knobs), C.byref(out)))
+    try:
+        nr = int(out.n_ranges)
+        res = {"ran": bool(out.ran), "caps": dict(zip(MERGE_CAPS, (int(v) for v in out.caps))),
+               "cuts": _copy(out.cuts, nr, _I4), "first": _copy(out.first, nr + 1, _I4), "cursors0": _copy(out.cursors0, 2 * nr, _I4).reshape(-1, 2)}
+        if full:
+            lists = out.lists
+            res["lists"] = {"perfect": _copy(lists.perfect, lists.n_perfect, SEED_DT), "subst": _copy(lists.subst, lists.n_subst, SEED_DT),
+                            "anchored": _copy(lists.anchored, lists.n_anchored, SEED_DT), "guard_hits": int(lists.guard_hits)}
+            res["device_merge"] = tuple(int(v) for v in out.device_merge)
+            return res
+        res["ranges"] = []
+        if not out.ran or not out.own:
+            return res
+        rng = _copy(out.range, 12 * nr, _I4).reshape(-1, 12)
+        own = _copy(out.own, out.n_own, SEED_DT)
+        logs = {}
+        for name, ptr, n, width in (("undo", out.undo, out.n_undo, 4), ("reads", out.reads, out.n_reads, 4), ("heads", out.heads, out.n_heads, 8)):
+            rows = _copy(ptr, width * n, _I4).reshape(-1, width)
+            logs[name] = [sorted(tuple(int(v) for v in r[1:]) for r in rows[rows[:, 0] == k]) for k in range(nr)]
+        u64 = lambda lo, hi: (int(lo) & 0xFFFFFFFF) | ((int(hi) & 0xFFFFFFFF) << 32)
+        for k in range(nr):
+            r = rng[k]
+            guards = u64(r[3], r[4])
+            res["ranges"].append({"status": int(r[0]) & 0xFFFFFFFF, "own": own[int(r[1]):int(r[1]) + int(r[2])],
+                                  "guard_hits": guards - (1 << 64) if guards >> 63 else guards, "cursor": (int(r[5]), int(r[6])),
+                                  "head_reads": (u64(r[7], r[8]), u64(r[9], r[10])),
+                                  "undo": logs["undo"][k], "reads": logs["reads"][k], "heads": logs["heads"][k]})
+        return res
+    finally:
+        load_library().ribbit_debug_merge_ranges_free(C.byref(out))
 
 
 def small_motif_counters():

@@ -311,10 +311,11 @@ void merge_subst_stage_full(SeedLists &lists, const RibbitCall *calls, size_t n,
     merge_subst_stage(lists, c.view, threads, stats);
 }
 
-void merge_anchored_stage_full(SeedLists &lists, const RibbitCall *calls, size_t n, unsigned threads, MergeStats *stats, const AnchoredDevicePass *device) {
+void merge_anchored_stage_full(SeedLists &lists, const RibbitCall *calls, size_t n, unsigned threads, MergeStats *stats, const AnchoredDevicePass *device,
+                               AnchoredPassProbe *probe) {
     Compacted c;
     compact_full(calls, n, lists.length, anchored_seedlen_cutoff, c);
-    merge_anchored_stage(lists, c.view, threads, stats, device);
+    merge_anchored_stage(lists, c.view, threads, stats, device, probe);
 }
 
 void replay_anchored_calls(SeedLists &lists, const RibbitCall *calls, size_t n, int64_t length) {
@@ -453,7 +454,8 @@ void merge_subst_stage(SeedLists &lists, const KeptCalls &kc, unsigned threads, 
     if (stats) *stats = st;
 }
 
-void merge_anchored_stage(SeedLists &lists, const KeptCalls &kc, unsigned threads, MergeStats *stats, const AnchoredDevicePass *device) {
+void merge_anchored_stage(SeedLists &lists, const KeptCalls &kc, unsigned threads, MergeStats *stats, const AnchoredDevicePass *device,
+                          AnchoredPassProbe *probe) {
     MergeStats st;
     threads = resolve_threads(threads);
     st.threads = threads;
@@ -521,6 +523,7 @@ void merge_anchored_stage(SeedLists &lists, const KeptCalls &kc, unsigned thread
         });
     }
     st.prep_parts[1] = now_ms() - t0;
+    if (probe) { probe->prepared = true; probe->first = first; probe->cut_pos = cut_pos; probe->start_cursor = start_cursor; }
     const std::vector<int32_t> perfect_types = types_of(lists.perfect), subst_types = types_of(lists.subst);
     st.prep_parts[2] = now_ms() - t0;
     const int64_t guard_before = lists.guard_hits;
@@ -597,6 +600,13 @@ void merge_anchored_stage(SeedLists &lists, const KeptCalls &kc, unsigned thread
     });
     JoinOnExit presize_guard({}, presize);
     st.before_passes_ms = now_ms() - t1;
+    // (test hook, AnchoredPassProbe::stop_after_first_pass: the stage ends here, nothing joined)
+    auto leave_after_first_pass = [&]() {
+        if (presize.joinable()) presize.join();
+        lists.anchored.clear();
+        tl_last_stats[1] = st;
+        if (stats) *stats = st;
+    };
     while (done < nr && !fallback) {
         if (++passes > 16) { fallback = true; break; }
         const size_t from = done;
@@ -665,8 +675,40 @@ void merge_anchored_stage(SeedLists &lists, const KeptCalls &kc, unsigned thread
                 });
                 meanwhile_ms = now_ms() - tm;
             };
+            // (test hook, parallel_merge.h: the lanes alone, on the ranges the probe names)
+            const std::function<void(uint32_t *, const uint32_t *)> nobody = [](uint32_t *, const uint32_t *) {};
+            if (probe) {
+                device_limit = std::min(probe->device_limit, nr);
+                if (probe->only_range >= 0) {
+                    order.clear();
+                    if ((uint64_t)probe->only_range < nr) order.push_back((uint32_t)probe->only_range);
+                    device_limit = std::min(device_limit, order.size());
+                }
+            }
             const double td = now_ms();
-            const bool ran = device->run(lists, kc, first, cut_pos, start_cursor, order, device_limit, meanwhile, res, undo, reads, heads) && res.size() == nr;
+            const bool ran = device->run(lists, kc, first, cut_pos, start_cursor, order, device_limit, probe ? nobody : meanwhile, res, undo, reads, heads) && res.size() == nr;
+            if (probe) probe->device_ran = ran;
+            if (probe && probe->stop_after_first_pass && !ran && !probe->host_workers) {      // the lanes' pass did not run: nothing to report
+                leave_after_first_pass();
+                return;
+            }
+            if (probe && probe->stop_after_first_pass && ran) {
+                probe->ranges.assign(nr, AnchoredPassProbe::Range{});
+                for (size_t k = 0; k < nr; ++k) {
+                    AnchoredPassProbe::Range &r = probe->ranges[k];
+                    r.status = res[k].status;
+                    if (r.status) continue;
+                    const size_t skip = k > 0 && res[k].own_n > 0 ? 1 : 0;
+                    r.own.assign(res[k].own + skip, res[k].own + res[k].own_n);
+                    r.guard_hits = res[k].guard_hits; r.cursor = res[k].cursor;
+                    r.head_reads[0] = res[k].head_reads[0]; r.head_reads[1] = res[k].head_reads[1];
+                }
+                for (const AnchoredDevicePass::LogEntry &e : undo) if (!res[e.range].status) probe->ranges[e.range].undo.push_back(e);
+                for (const AnchoredDevicePass::LogEntry &e : reads) if (!res[e.range].status) probe->ranges[e.range].reads.push_back(e);
+                for (const AnchoredDevicePass::HeadEntry &e : heads) if (!res[e.range].status) probe->ranges[e.range].heads.push_back(e);
+                leave_after_first_pass();
+                return;
+            }
             st.device_ms = now_ms() - td;
             st.device_meanwhile_ms = meanwhile_ms;
             st.device_host_share = (unsigned)host_took.load();
@@ -708,6 +750,11 @@ void merge_anchored_stage(SeedLists &lists, const KeptCalls &kc, unsigned thread
             for (size_t k2 = 0; k2 < nr; ++k2) if (host_done[k2]) { st.range_ms_sum += range_ms[k2]; st.range_ms_max = std::max(st.range_ms_max, range_ms[k2]); }
             todo.swap(host_todo);
         }
+        const bool probe_stops = probe && probe->stop_after_first_pass && passes == 1;
+        if (probe_stops && probe->only_range >= 0) {
+            todo.clear();
+            if ((uint64_t)probe->only_range < nr) todo.push_back((size_t)probe->only_range);
+        }
         run_ranges(todo.size(), threads, [&](size_t q) {
             const size_t k = todo[q];
             const double tr = now_ms();
@@ -715,6 +762,30 @@ void merge_anchored_stage(SeedLists &lists, const KeptCalls &kc, unsigned thread
             body(k, state[k], false, nullptr, nullptr);
             range_ms[k] = now_ms() - tr;
         });
+        if (probe_stops) {
+            // what the host workers left, seeds named by list and index as the device's logs name them
+            auto named = [&](const RibbitSeed *sd, uint32_t &list, uint32_t &index) {
+                const bool in_s = !lists.subst.empty() && sd >= lists.subst.data() && sd < lists.subst.data() + lists.subst.size();
+                list = in_s ? 1u : 0u;
+                index = (uint32_t)(sd - (in_s ? lists.subst.data() : lists.perfect.data()));
+            };
+            probe->ranges.assign(nr, AnchoredPassProbe::Range{});
+            for (size_t k : todo) {
+                AnchoredPassProbe::Range &r = probe->ranges[k];
+                const RangeState &me = state[k];
+                r.status = 0;
+                r.own.assign(me.own.begin() + (k > 0 && !me.own.empty() ? 1 : 0), me.own.end());
+                r.guard_hits = me.guard_hits; r.cursor = me.cursor;
+                r.head_reads[0] = me.head_reads[0]; r.head_reads[1] = me.head_reads[1];
+                uint32_t list, index;
+                for (const ListRefs::TypeWrite &w : me.undo) { named(w.seed, list, index); r.undo.push_back({(uint32_t)k, list, index, w.old_type}); }
+                for (const ListRefs::TypeRead &x : me.foreign_reads) { named(x.seed, list, index); r.reads.push_back({(uint32_t)k, list, index, x.live ? 1 : 0}); }
+                for (const ListRefs::HeadWrite &w : me.head_writes) { named(w.target, list, index); r.heads.push_back({(uint32_t)k, list, index, w.value, w.changed_then}); }
+            }
+            for (size_t k = nr; k-- > 0;) state[k].reset(false, 0);      // takes back the ranges' retirements
+            leave_after_first_pass();
+            return;
+        }
         const double tw = now_ms();
         st.pass_ms += tw - tp;
         for (size_t k2 : todo) { st.range_ms_sum += range_ms[k2]; st.range_ms_max = std::max(st.range_ms_max, range_ms[k2]); }

@@ -109,10 +109,45 @@ struct AnchoredDevicePass {
                        std::vector<RangeResult> &ranges, std::vector<LogEntry> &undo, std::vector<LogEntry> &reads, std::vector<HeadEntry> &heads)> run;
 };
 
+// Test hook (ribbit_hip_debug_merge_ranges): the anchored stage's first parallel pass observed, and run the way a test asks.
+// With a probe, the stage prepares its ranges as for the device pass (cut_ranges with the pass's calls per range, the bisection
+// cursors) and then
+//   * gives the lanes no competitor: `meanwhile` takes no range, the lanes may take the first `device_limit` entries of `order`
+//     (SIZE_MAX: all of them) -- or, with only_range >= 0, `order` is that one range;
+//   * or, when device->run declines (returns false without calling meanwhile), runs the ranges -- all, or only_range -- on the
+//     host workers, as the production pass does for every range the device leaves;
+//   * with stop_after_first_pass, copies what every range left (a RangeResult's fields and the three logs, seeds by list and
+//     index) into `ranges`, takes the host workers' retirements back and returns before the validation walk: the lists are then
+//     as they were given, lists.anchored is empty.
+// Without stop_after_first_pass the stage goes on unchanged (validation walk, ranges done again, join, flush).
+struct AnchoredPassProbe {
+    size_t device_limit = SIZE_MAX;
+    int64_t only_range = -1;
+    bool stop_after_first_pass = false;
+    bool host_workers = false;            // device->run declines on purpose: the ranges are the host workers' (else a pass that did not run ends the stage)
+    // filled by the stage
+    bool prepared = false;                // false: the stage did not cut (fewer than two ranges) and ran in call order
+    bool device_ran = false;              // device->run returned true
+    std::vector<size_t> first;            // first kept call of every range, and the number of kept calls
+    std::vector<int> cut_pos;
+    std::vector<Cursor2> start_cursor;
+    struct Range {
+        uint32_t status = 0xffffffffu;    // all ones: nobody merged it
+        SeedVec own;                      // without the sentinel
+        int64_t guard_hits = 0;
+        Cursor2 cursor;
+        uint64_t head_reads[2] = {0, 0};
+        std::vector<AnchoredDevicePass::LogEntry> undo, reads;
+        std::vector<AnchoredDevicePass::HeadEntry> heads;
+    };
+    std::vector<Range> ranges;            // (stop_after_first_pass)
+};
+
 // lists.subst is rebuilt from kc (lists.perfect as the perfect stage left it)
 void merge_subst_stage(SeedLists &lists, const KeptCalls &kc, unsigned threads, MergeStats *stats = nullptr);
 // lists.anchored is rebuilt from kc (lists.perfect / lists.subst as the substitution stage left them)
-void merge_anchored_stage(SeedLists &lists, const KeptCalls &kc, unsigned threads, MergeStats *stats = nullptr, const AnchoredDevicePass *device = nullptr);
+void merge_anchored_stage(SeedLists &lists, const KeptCalls &kc, unsigned threads, MergeStats *stats = nullptr, const AnchoredDevicePass *device = nullptr,
+                          AnchoredPassProbe *probe = nullptr);
 
 // Replay of a full anchored call list (ribbit_hip_anchored_calls order: in-loop calls, then the end-of-sequence flush)
 void replay_anchored_calls(SeedLists &lists, const RibbitCall *calls, size_t n, int64_t length);
@@ -122,7 +157,8 @@ void replay_subst_calls(SeedLists &lists, const RibbitCall *calls, size_t n);
 // The same two stages from a FULL call list in the scanner's call order (in-loop calls, then the end-of-sequence
 // flush with pos == length): filtered and bounded here, then merged as above.
 void merge_subst_stage_full(SeedLists &lists, const RibbitCall *calls, size_t n, unsigned threads, MergeStats *stats = nullptr);
-void merge_anchored_stage_full(SeedLists &lists, const RibbitCall *calls, size_t n, unsigned threads, MergeStats *stats = nullptr, const AnchoredDevicePass *device = nullptr);
+void merge_anchored_stage_full(SeedLists &lists, const RibbitCall *calls, size_t n, unsigned threads, MergeStats *stats = nullptr, const AnchoredDevicePass *device = nullptr,
+                               AnchoredPassProbe *probe = nullptr);
 
 // test hook: smallest number of calls per range (default 4096); small values cut wherever a cut is valid
 void set_merge_min_range(size_t calls);

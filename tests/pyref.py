@@ -193,6 +193,13 @@ class AnchoredMerge:
         self.L = int(length)
         self.guards = 0
         self.met = collections.Counter()      # how often the paths the tests want to have seen were taken
+        # Besides the named paths: one tag per rule of the reference, keyed by the line of parse_anchored_shiftxor.cpp that the
+        # merge kernel's comments cite (":203", ":246 again, by the motif", ...; tests/merge_contract.py lists them), and tags
+        # of the candidate walks ("own walk of 8", "phase 1 perfect alone 4", ...).
+        # peaks: per top-level call (run / add at depth 0), the largest sizes any of its rounds reached -- perfect-plus-
+        # substitution candidates, all candidates, factor children, non-factor children, keys of the factor coverage table.
+        self.peaks = []
+        self.head_write_log = None            # a list: the writes to list heads (:511-522) are appended to it instead of made
 
     # ---- merge_types.cpp:11-189
     def candidates(self, from_p, from_s, seed_start):
@@ -205,26 +212,47 @@ class AnchoredMerge:
             self.guards += 1
         pi, si = from_p, from_s
 
-        def walk_down(lst, idx, rank, out):
+        def walk_down(lst, idx, rank, out, what):
             """the single-list loops (:30-45, :47-62, :108-121, :143-158): entries ending at or after seed_start,
             retired ones left out, until the list's beginning or the first entry that ends before seed_start"""
+            met, retired = 0, 0
             while True:
                 end, typ = lst[idx][1], lst[idx][3]
+                met += 1
                 if end >= seed_start:
                     if typ != RANK_N:
                         out.append((rank, idx))
+                    else:
+                        retired += 1
                     idx -= 1
                 if idx < 0 or end < seed_start:
+                    self.met[f"{what} {met}"] += 1
+                    if retired:
+                        self.met[f"{what} {met}, retired among them"] += 1
+                    if end < seed_start:
+                        self.met[f"{what} ends by an entry before the seed" + (" (the sentinel)" if lst[idx][0] == -1 and lst[idx][3] == RANK_N and lst is A else "")] += 1
+                    else:
+                        self.met[f"{what} ends at index -1"] += 1
                     return idx
 
+        if len(P) == 0:
+            self.met["no perfect seed"] += 1
+        if len(P) == 1:
+            self.met["one perfect seed"] += 1
+        both = 0
         while not (p_done and s_done):            # :28
             if s_done:
-                pi = walk_down(P, pi, RANK_P, sp)
+                if both:
+                    self.met[f"phase 1 both open for {both} steps, then perfect alone"] += 1
+                pi = walk_down(P, pi, RANK_P, sp, "phase 1 perfect alone")
                 p_done = True
             elif p_done:
-                si = walk_down(S, si, RANK_S, sp)
+                if both:
+                    self.met[f"phase 1 both open for {both} steps, then substitution alone"] += 1
+                si = walk_down(S, si, RANK_S, sp, "phase 1 substitution alone")
                 s_done = True
             else:                                 # :64-94: both lists open -- the larger end first, perfect on a tie
+                both += 1
                 p_end, s_end = P[pi][1], S[si][1]
                 if s_end > p_end:
                     if S[si][3] != RANK_N:
@@ -239,11 +267,13 @@ class AnchoredMerge:
                 if si < 0 or s_end < seed_start:
                     s_done = True
 
+        self._n_sp = len(sp)
         out = []
         if len(A) == 0:                           # :103
+            self._n_sp = len(sp)
             return list(sp)
         if not sp:                                # :107
-            walk_down(A, len(A) - 1, RANK_A, out)
+            walk_down(A, len(A) - 1, RANK_A, out, "own walk")
             return out
 
         def sp_end(k):
@@ -263,7 +293,7 @@ class AnchoredMerge:
                         k_done = True
                         break
             elif k_done:
-                walk_down(A, ai, RANK_A, out)
+                walk_down(A, ai, RANK_A, out, "own walk")
                 a_done = True
             else:                                 # :160-186: note that retired anchored seeds ARE listed here
                 e, a_end = sp_end(k), A[ai][1]
@@ -281,6 +311,13 @@ class AnchoredMerge:
 
     # ---- parse_anchored_shiftxor.cpp:59-71
     def retain_nested(self, start, end, nested_m, parent_m):
+        if end > start:
+            for m in (nested_m, parent_m):
+                self.met[f"plane read on motif {m}"] += 1
+            for tag, yes in (("starts on a word boundary", start % 32 == 0), ("ends on a word boundary (bit 31)", end % 32 == 0),
+                             ("inside one word", start // 32 == (end - 1) // 32), ("over three words or more", (end - 1) // 32 - start // 32 >= 2)):
+                if yes:
+                    self.met[f"plane read {tag}"] += 1
         nested = int(self.planes[nested_m][start:end].sum())
         parent = int(self.planes[parent_m][start:end].sum())
         return nested >= parent
@@ -295,9 +332,16 @@ class AnchoredMerge:
     # ---- parse_anchored_shiftxor.cpp:113-534
     def add(self, seed_start, seed_end, m, frm, seed_type, depth=0):
         P, S, A = self.P, self.S, self.A
+        met = self.met
         fp, fs = frm
         if depth:
-            self.met["added again by a nested call"] += 1
+            met["added again by a nested call"] += 1
+        else:
+            self.peaks.append({"ps": 0, "cands": 0, "factor": 0, "nonfactor": 0, "sizes": 0})
+        peak = self.peaks[-1]
+
+        def top(key, n):
+            peak[key] = max(peak[key], n)
         # :132-152 the cursors: forward while the entry starts at or before seed_end, never beyond the last entry
         for lst, which in ((P, 0), (S, 1)):
             f = fp if which == 0 else fs
@@ -314,6 +358,8 @@ class AnchoredMerge:
             return advanced
 
         cand = self.candidates(fp, fs, seed_start)            # :156
+        top("ps", self._n_sp)
+        top("cands", len(cand))
         seed_rend = seed_end + m
         seed_len = seed_end - seed_start
         seed_rlen = seed_len + m
@@ -325,96 +371,164 @@ class AnchoredMerge:
             last_start, last_end, last_mlen, last_type = src[i]
             last_rend = last_end + last_mlen
             if last_end < seed_start:                         # :203
+                met[":203"] += 1
                 break
             if last_type == RANK_N:
+                met[":205"] += 1
                 continue
             if seed_end < last_start:
+                met[":208"] += 1
                 continue
             last_len = last_end - last_start
             last_rlen = last_rend - last_start
 
             if seed_start == last_start and seed_end == last_end:                       # :215 same interval
                 if seed_type == RANK_A and last_type > RANK_A:
+                    met[":215 returns"] += 1
                     return advanced
                 if seed_type == RANK_C and last_type == RANK_A:
+                    met[":215 retires"] += 1
                     A[i][3] = RANK_N
+                else:
+                    met[":215 goes on"] += 1
                 continue
 
             if last_start <= seed_start and seed_end <= last_end:                       # :231 inside an older seed
                 if last_type > seed_type:
+                    met[":231 higher type returns"] += 1
                     return advanced
                 if seed_type == RANK_C and last_type == RANK_A:
+                    met[":231 C inside A"] += 1
                     continue
                 if (seed_type, last_type) in ((RANK_A, RANK_A), (RANK_C, RANK_C)):
+                    if m % last_mlen == 0:
+                        met[":241 returns" if m != 4 else ":241 not for a motif of 4"] += 1
                     if m % last_mlen == 0 and m != 4:
                         return advanced
+                    if last_mlen % m == 0:
+                        met[":246" if last_mlen != 4 else ":246 not for an old motif of 4"] += 1
                     if last_mlen % m == 0 and last_mlen != 4:
                         if seed_rlen >= last_mlen - 1 or seed_rlen >= last_len:
+                            if seed_rlen >= last_mlen - 1:
+                                met[":246 again, by the motif"] += 1
+                            if seed_rlen >= last_len:
+                                met[":246 again, by the length"] += 1
+                            if m >= 900 or last_mlen >= 900:
+                                met[":246 with a motif near the top"] += 1
                             A[i][3] = RANK_N
                             return self.add(last_start, last_end, m, frm, seed_type, depth + 1)
+                        met[":246 neither"] += 1
                         continue
                     if not self.retain_nested(seed_start, seed_end, m, last_mlen):
+                        met[":257 drop"] += 1
                         return advanced
+                    met[":257 keep"] += 1
+                    if m >= 900 or last_mlen >= 900:
+                        met[":257 with a motif near the top"] += 1
                 continue
 
             if seed_start <= last_start and last_end <= seed_end:                       # :266 around an older seed
                 if last_type > seed_type:
                     if m % last_mlen == 0:
+                        if m >= 900:
+                            met[":268 with a motif near the top"] += 1
                         if last_rlen >= m - 2 or last_rlen >= seed_len - 2:
+                            if last_rlen >= m - 2:
+                                met[":268 again, by the motif"] += 1
+                            if last_rlen >= seed_len - 2:
+                                met[":268 again, by the length"] += 1
                             self._retire_by_type(last_type, i)
                             return self.add(seed_start, seed_end, last_mlen, frm, RANK_C, depth + 1)
+                        met[":268 factor child"] += 1
                         factor_types.append(last_type)
                         factor_sizes.append(last_mlen)
+                        top("factor", len(factor_types))
                     elif last_mlen % m == 0:
+                        if last_mlen >= 900:
+                            met[":285 with a motif near the top"] += 1
                         if last_mlen >= 4 * m or last_len >= 4 * m:
+                            met[":285 again"] += 1
                             self._retire_by_type(last_type, i)
                             return self.add(seed_start, seed_end, m, frm, RANK_C, depth + 1)
+                        met[":285 no action"] += 1
                         # (parentof_subperf_multiple: collected, never read)
                     elif last_mlen > m:
                         if last_mlen >= 4 * m or last_len >= 4 * m:
+                            met[":301 again"] += 1
                             self._retire_by_type(last_type, i)
                             return self.add(seed_start, seed_end, m, frm, RANK_C, depth + 1)
+                        met[":301 no action"] += 1
+                        if last_mlen >= 900:
+                            met[":301 with a motif near the top"] += 1
                     else:
+                        met[":312 non-factor child"] += 1
                         nonfactor_types.append(last_type)
+                        top("nonfactor", len(nonfactor_types))
                 elif seed_type == RANK_C and last_type == RANK_A:
+                    met[":319"] += 1
                     A[i][3] = RANK_N
                 elif (seed_type, last_type) in ((RANK_A, RANK_A), (RANK_C, RANK_C)):
                     if last_mlen == m:
+                        met[":323 equal sizes"] += 1
                         A[i][3] = RANK_N
                     elif not self.retain_nested(last_start, last_end, last_mlen, m):
+                        met[":323 nested test lost"] += 1
                         A[i][3] = RANK_N
                     elif m % last_mlen == 0:
+                        if m >= 900:
+                            met[":332 with a motif near the top"] += 1
                         if last_rlen >= m - 2 or last_rlen >= seed_len - 2:
+                            met[":332 again"] += 1
                             A[i][3] = RANK_N
                             return self.add(seed_start, seed_end, last_mlen, frm, seed_type, depth + 1)
+                        met[":332 not again"] += 1
+                    else:
+                        met[":323 kept, no factor"] += 1
                 continue
 
             # :354 partial overlap
             if last_start < seed_start:
                 reach = last_rend if last_mlen <= m else last_end
+                met[":351 old seed first, reach with its motif" if last_mlen <= m else ":351 old seed first, reach its end"] += 1
                 overlap = (seed_end if seed_end <= reach else reach) - seed_start
+                met[":351 old seed first, overlap to the new end" if seed_end <= reach else ":351 old seed first, overlap to the reach"] += 1
                 merge_start, merge_end = last_start, seed_end
             else:
                 reach = seed_rend if m <= last_mlen else seed_end
+                met[":351 new seed first, reach with its motif" if m <= last_mlen else ":351 new seed first, reach its end"] += 1
                 overlap = (last_end if last_end <= reach else reach) - last_start
+                met[":351 new seed first, overlap to the old end" if last_end <= reach else ":351 new seed first, overlap to the reach"] += 1
                 merge_start, merge_end = seed_start, last_end
 
             if seed_type == RANK_A and last_type > RANK_C:                              # :379
                 if m == last_mlen and overlap >= 4 * m:
+                    met[":376 merge"] += 1
                     self._retire_by_type(last_type, i)
                     return self.add(merge_start, merge_end, m, frm, RANK_C, depth + 1)
                 if not (m % last_mlen == 0 or last_mlen % m == 0):
+                    if m >= 900 or last_mlen >= 900:
+                        met[":376 with a motif near the top"] += 1
                     if overlap >= m - 1 or overlap >= seed_len - 1:
+                        met[":376 return"] += 1
                         return advanced
+                    met[":376 unrelated sizes, small overlap"] += 1
+                else:
+                    met[":376 related sizes, no action"] += 1
             elif seed_type in (RANK_A, RANK_C) and last_type in (RANK_A, RANK_C):       # :401
                 if m == last_mlen:
                     # (`seed_type == ... ? RANK_C : RANK_A;` at :406 ff. compares and discards: the type is unchanged)
                     if last_len >= seed_len:
                         joins = ((seed_len >= 3 * m and (overlap >= 3 * m - 1 or overlap >= seed_len - 1)) or
                                  (seed_len < 3 * m and (overlap >= m - 1 or overlap >= seed_len - 1)))
+                        met[f":398 old as long, {'long' if seed_len >= 3 * m else 'short'} new seed: {bool(joins)}"] += 1
                     else:
+                        long_old = last_len >= 3 * last_mlen and (overlap >= 3 * last_mlen - 1 or overlap >= last_len - 1)
                         joins = ((last_len >= 3 * last_mlen and (overlap >= 3 * last_mlen - 1 or overlap >= last_len - 1)) or
                                  (seed_len < 3 * last_mlen and (overlap >= last_mlen - 1 or overlap >= last_len - 1)))
+                        if last_len >= 3 * last_mlen:
+                            met[f":398 old shorter but long: {bool(long_old)}"] += 1
+                        if not long_old and seed_len < 3 * last_mlen:
+                            met[f":398 old shorter, short new seed: {bool(joins)}"] += 1
                     if joins:
                         A[i][3] = RANK_N
                         return self.add(merge_start, merge_end, last_mlen, frm, seed_type, depth + 1)
@@ -430,26 +544,33 @@ class AnchoredMerge:
                 return
             if j >= len(lst):                     # D2
                 self.guards += 1
+                met["by-counter index beyond the list"] += 1
                 return
+            if j >= 63:
+                met["by-counter index 63 or above"] += 1
             last_start, last_end, last_mlen = lst[j][0], lst[j][1], lst[j][2]
             last_rend = last_end + last_mlen
 
-        def covered(total, prev_start):
+        def covered(total, prev_start, what):
             if (last_rend & _U32) >= prev_start:
+                met[f"{what} coverage: up to the start before"] += 1
                 return _i32(total + ((prev_start - last_start) & _U32))
             if last_rend < seed_end:
+                met[f"{what} coverage: the child with its motif"] += 1
                 return total + last_rend - last_start
+            met[f"{what} coverage: up to the seed's end"] += 1
             return total + seed_end - last_start
 
         if nonfactor_types:
             cov, prev_start = 0, _U32
             for j, ktype in enumerate(nonfactor_types):
                 head(j, ktype)
-                cov = covered(cov, prev_start)
+                cov = covered(cov, prev_start, "non-factor")
                 prev_start = last_start & _U32
             if cov > 0.5 * seed_len:              # :467
                 self.met["rejected: covered by other motif sizes"] += 1
                 return advanced
+            met["non-factor coverage at or below half"] += 1
 
         if factor_types:                          # :471-526, per motif size (the maps default-insert 0)
             prev_starts = {f: -1 for f in factor_sizes}
@@ -457,12 +578,18 @@ class AnchoredMerge:
             for j, ktype in enumerate(factor_types):
                 head(j, ktype)
                 prev_start = prev_starts.setdefault(last_mlen, 0) & _U32
-                coverage[last_mlen] = covered(coverage.setdefault(last_mlen, 0), prev_start)
+                coverage[last_mlen] = covered(coverage.setdefault(last_mlen, 0), prev_start, "factor")
                 prev_starts[last_mlen] = last_start
+                top("sizes", len(coverage))
+            top("sizes", len(coverage))
+            if not any(coverage[f] >= 0.8 * seed_len for f in coverage):
+                met["no factor size covers enough"] += 1
             for f in sorted(coverage):
                 if coverage[f] >= 0.8 * seed_len:
                     m, seed_type = f, RANK_C
                     self.met["takes a factor's motif size"] += 1
+                    if any(coverage[g] >= 0.8 * seed_len for g in coverage if g > f):
+                        met["takes the smallest of several factor sizes"] += 1
                     for j, ktype in enumerate(factor_types):      # :511-522: entry j of the list, start and end as left above
                         lst = P if ktype == RANK_P else S if ktype == RANK_S else None
                         if lst is None:
@@ -474,10 +601,14 @@ class AnchoredMerge:
                             if lst[j][:2] != [last_start, last_end]:
                                 self.met["list-head write that moves an entry"] += 1
                             self.met["list-head write"] += 1
+                            if self.head_write_log is not None:      # a parallel worker: logged, not made
+                                self.head_write_log.append((0 if ktype == RANK_P else 1, j, last_start, last_end, lst[j][2], RANK_N))
+                                continue
                             lst[j] = [last_start, last_end, lst[j][2], RANK_N]
                     break
 
         if seed_end > self.L - m:                 # :529
+            met["clamped to the record's end"] += 1
             seed_end = self.L - m
         A.append([seed_start, seed_end, m, seed_type])
         return advanced

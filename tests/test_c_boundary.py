@@ -54,6 +54,26 @@ assert L.ribbit_hip_last_error().decode() == "out of host memory in the merge of
 check(rc)
 assert not out.perfect and not out.dispatch
 """,
+    # ribbit_hip_debug_merge_ranges: null arguments and knobs out of range are RIBBIT_E_ARG before anything is read; the copy of the
+    # planes (2^40 words a plane) is refused as out of memory, not thrown through the C boundary
+    "debug_merge_ranges": r"""
+knobs, out = ribbit_amd.DebugMergeKnobs(1, 0, 1, 0, 0, 0, 0, -1, -1), ribbit_amd.DebugMergeRanges()
+word = (C.c_uint32 * 4)()
+E_ARG = -1
+call = L.ribbit_hip_debug_merge_ranges
+assert call(None, None, 100, None, 0, None, 0, None, 0, C.addressof(word), 4, C.byref(knobs), C.byref(out)) == E_ARG
+assert call(None, C.byref(params), 100, None, 0, None, 0, None, 0, None, 4, C.byref(knobs), C.byref(out)) == E_ARG
+assert call(None, C.byref(params), 100, None, 0, None, 0, None, 0, C.addressof(word), 4, None, C.byref(out)) == E_ARG
+assert call(None, C.byref(params), 100, None, 0, None, 0, None, 0, C.addressof(word), 4, C.byref(knobs), None) == E_ARG
+assert call(None, C.byref(params), 100, None, 1, None, 0, None, 0, C.addressof(word), 4, C.byref(knobs), C.byref(out)) == E_ARG
+for field, value in (("where", 2), ("calls_per_range", 0), ("resident_waves", -1), ("max_passes", -1), ("head_cap", -1), ("log_cap", -1), ("only_range", -2)):
+    bad = ribbit_amd.DebugMergeKnobs(1, 0, 1, 0, 0, 0, 0, -1, -1)
+    setattr(bad, field, value)
+    assert call(None, C.byref(params), 100, None, 0, None, 0, None, 0, C.addressof(word), 4, C.byref(bad), C.byref(out)) == E_ARG, field
+L.ribbit_debug_merge_ranges_free(None)
+check(call(None, C.byref(params), 100, None, 0, None, 0, None, 0, C.addressof(word), 1 << 40, C.byref(knobs), C.byref(out)))
+assert not out.cuts and not out.own
+""",
 }
 
 
