@@ -1462,6 +1462,39 @@ typedef struct RibbitDebugPairing {
 int ribbit_hip_debug_pair_events_sharded(RibbitHandle *h, const uint64_t *events, const uint32_t *counters, size_t region_cap,
                                          int64_t length, int64_t own_lo, int64_t own_hi, int64_t pos_offset, RibbitDebugPairing *out);
 
+/* Test hook: the window stage behind the scan and the pairing (window_stage.hip: group starts, the calls kernel, the edge list
+ * and its retry, the dropmap merge, the sorts, the cursor bounds, the read-back -- the same function the product runs after its
+ * scan) on caller-made pass-streaks.  A record must be loaded: it supplies the length and the break plane (where the N are).
+ *   stage          RIBBIT_STAGE_SUBST | RIBBIT_STAGE_ANCHORED: whose result buffers the call uses;
+ *   streaks        n_streaks records (start = first passing window, end = first window behind it that does not pass, mlen,
+ *                  term = RIBBIT_TERM_*), ordered by (mlen, start);
+ *   full           1: every call, no length filter, no cursor bounds (min_span may be NULL); 0: the compact form;
+ *   min_span       max_motif - min_motif + 1 values: the smallest end - start a call of that motif needs to be kept;
+ *   own_lo, own_hi, z_lo, keep_flush, pos_offset   chunk mode as ribbit_hip_stage_calls_chunk derives it from its geometry: the
+ *                  owned scan positions (piece coordinates), the first exact position (0: none), whether the end-of-sequence
+ *                  calls are this chunk's, what is added to every coordinate of the result;
+ *   dropped_ends   n_dropped ascending positions e: a group of pass-streaks that is NOT among the streaks ends at e (the `end`
+ *                  of its last streak) and its call, made at e + 15, fails the length filter -- what the anchored scan's group
+ *                  filter leaves in its dropmap.  n_dropped = 0: no dropmap.  Ignored with full;
+ *   first_edge_cap first capacity of the edge-call list (0 = automatic); a list that overflows is sized by the count and the
+ *                  calls kernel runs again.
+ * Everything a kernel indexes with is checked first, RIBBIT_E_ARG otherwise and nothing is enqueued: 0 <= start < end <= length,
+ * mlen within the handle's motif range, term in 0..2, the order, streaks of one motif that do not overlap, 0 <= e < length,
+ * 0 <= own_lo <= own_hi, pos_offset + length <= INT32_MAX, at most 2^24 streaks and edge-list entries.  Streaks that no scan of
+ * the loaded record could have produced are answered by the stage's own flags (RIBBIT_E_INTERNAL, e.g. "flags 0x1" for two
+ * end-of-sequence calls of one motif), never by a read outside a buffer.
+ * out as for ribbit_hip_stage_calls_chunk (inexact: z_lo != 0 and an owned call starts below z_lo + 8; streaks = n_streaks);
+ * *n_edge: the edge calls the stage counted. */
+typedef struct RibbitDebugWindowStage {
+    const RibbitRun *streaks; size_t n_streaks;
+    const int32_t *min_span;
+    const int32_t *dropped_ends; size_t n_dropped;
+    int64_t own_lo, own_hi, z_lo, pos_offset;
+    size_t first_edge_cap;
+    int32_t full, keep_flush;
+} RibbitDebugWindowStage;
+int ribbit_hip_debug_window_calls(RibbitHandle *h, int stage, const RibbitDebugWindowStage *in, RibbitChunkCalls *out, uint32_t *n_edge);
+
 /* Test hook: the first guess of the event-buffer capacity of the scans (0 = automatic).  A guess that is too small
  * makes a scan overflow its regions, after which it is sized for the fullest region and run again. */
 int ribbit_hip_debug_set_event_capacity(RibbitHandle *h, size_t events);

@@ -182,6 +182,13 @@ class ChunkCalls(C.Structure):
                 ("flush", C.c_void_p), ("n_flush", C.c_size_t), ("dev_calls", C.c_void_p), ("dev_pend", C.c_void_p), ("streaks", C.c_int64)]
 
 
+class DebugWindowStage(C.Structure):
+    """RibbitDebugWindowStage: the caller-made streaks and the chunk window of ribbit_hip_debug_window_calls (include/ribbit_hip.h)."""
+    _fields_ = [("streaks", C.c_void_p), ("n_streaks", C.c_size_t), ("min_span", C.c_void_p), ("dropped_ends", C.c_void_p),
+                ("n_dropped", C.c_size_t), ("own_lo", C.c_int64), ("own_hi", C.c_int64), ("z_lo", C.c_int64), ("pos_offset", C.c_int64),
+                ("first_edge_cap", C.c_size_t), ("full", C.c_int32), ("keep_flush", C.c_int32)]
+
+
 class ChunkPart(C.Structure):
     """RibbitChunkPart: one chunk's contribution to ribbit_host_merge_chunks."""
     _fields_ = [("runs", C.c_void_p), ("n_runs", C.c_size_t), ("halves", C.c_void_p), ("n_halves", C.c_size_t),
@@ -269,6 +276,7 @@ def _signatures() -> dict:
         "ribbit_hip_debug_last_scan_split": (st, [vp, i32, pi32, pi32]),
         "ribbit_hip_debug_pair_events": (st, [vp, vp, sz, i64, vp, sz, psz, P(C.c_uint32)]),
         "ribbit_hip_debug_pair_events_sharded": (st, [vp, vp, vp, sz, i64, i64, i64, i64, P(DebugPairing)]),
+        "ribbit_hip_debug_window_calls": (st, [vp, ci, P(DebugWindowStage), P(ChunkCalls), P(C.c_uint32)]),
         "ribbit_hip_debug_stream_read": (st, [vp, i64, P(i64)]),
         "ribbit_hip_debug_merge_ranges": (st, [vp, scan, i64, vp, sz, vp, sz, vp, sz, vp, sz, P(DebugMergeKnobs), P(DebugMergeRanges)]),
         "ribbit_debug_merge_ranges_free": (None, [P(DebugMergeRanges)]),
@@ -1615,6 +1623,24 @@ class Scanner:
                 "summary": int(out.summary), "overflow": int(out.overflow),
                 "table": np.stack((table & np.uint64(0xFFFFFFFF), table >> np.uint64(32)), axis=-1).astype("<u4").reshape(nm, ntile, 2),
                 "table_status": int(out.table_status)}
+
+    def debug_window_calls(self, stage: int, streaks: np.ndarray, full: bool = False, min_span=None, own_lo: int = 0, own_hi: int = 2 ** 32 - 1,
+                           z_lo: int = 0, keep_flush: bool = True, pos_offset: int = 0, dropped_ends=(), first_edge_cap: int = 0) -> dict:
+        """ribbit_hip_debug_window_calls: the window stage behind the scan and the pairing on caller-made streaks (RUN_DT, ordered by
+        (mlen, start)) of the loaded record; min_span: one int per motif size (not needed with full); dropped_ends: ascending ends
+        of groups that are not among the streaks -> dict(calls, pend (or None), tail_pend, flush, inexact, n_edge) (copies)"""
+        sk = np.ascontiguousarray(streaks, dtype=RUN_DT)
+        sp = None if min_span is None else np.ascontiguousarray(min_span, dtype="<i4")
+        assert sp is None or len(sp) == self.params.max_motif - self.params.min_motif + 1
+        de = np.ascontiguousarray(dropped_ends, dtype="<i4").reshape(-1)
+        arg = DebugWindowStage(sk.ctypes.data if len(sk) else None, len(sk), None if sp is None else sp.ctypes.data,
+                               de.ctypes.data if len(de) else None, len(de), own_lo, own_hi, z_lo, pos_offset, first_edge_cap, int(bool(full)),
+                               int(bool(keep_flush)))
+        cc, n_edge = ChunkCalls(), C.c_uint32()
+        self._check(self._L.ribbit_hip_debug_window_calls(self._h, stage, C.byref(arg), C.byref(cc), C.byref(n_edge)))
+        return {"calls": _copy(cc.calls, cc.n, CALL_DT), "pend": _copy(cc.pend, cc.n, _I4) if cc.pend else None,
+                "tail_pend": int(cc.tail_pend), "flush": _copy(cc.flush, cc.n_flush, CALL_DT), "inexact": bool(cc.inexact),
+                "n_edge": int(n_edge.value)}
 
     def debug_set_event_capacity(self, events: int) -> None:
         self._check(self._L.ribbit_hip_debug_set_event_capacity(self._h, events))

@@ -567,6 +567,9 @@ int build_perfect_calls(RibbitHandle *h);
 int advance_to_perfect(RibbitHandle *h);
 int scan_and_pair_streaks(RibbitHandle *h, int stage /* RIBBIT_STAGE_SUBST | RIBBIT_STAGE_ANCHORED */, uint32_t *n_streaks, int (*filter_min_span)(int) = nullptr);
 int window_stage_device(RibbitHandle *h, int stage, bool full, int (*min_span)(int), DeviceCalls *out, ChunkWindow *cw = nullptr);
+// ... its second step, everything behind scan_and_pair_streaks (ribbit_hip_debug_window_calls runs it on caller-made streaks)
+int window_calls_device(RibbitHandle *h, int stage, uint32_t n_streaks, bool full, const int32_t *min_span /* per motif */, ChunkWindow *cw,
+                        bool dropmap_valid, size_t first_edge_cap /* 0: automatic */, double scan_ms, DeviceCalls *out);
 void full_calls_from_device(const DeviceCalls &dc, rb::CallVec &calls);
 int build_subst_calls(RibbitHandle *h);
 void subst_merge(RibbitHandle *h, const DeviceCalls *dc);

@@ -86,17 +86,19 @@ int scan_and_pair_streaks(RibbitHandle *h, int stage, uint32_t *n_streaks, int (
     return RIBBIT_OK;
 }
 
-// The whole window stage on the device (window_stage.hip).  full: every call, unfiltered (the call-list entry points
-// and the parity tests); otherwise only the calls that pass min_span, with their cursor bounds.  cw: chunk mode.
-int window_stage_device(RibbitHandle *h, int stage, bool full, int (*min_span)(int), DeviceCalls *out, ChunkWindow *cw) {
+// The window stage behind the scan and the pairing (window_stage.hip): from the n streak records in d_dense (motif-major by
+// start; d_events and d_dense sized by the event pass for them) to the calls on the host.  full: every call, unfiltered;
+// otherwise only the calls that pass min_span[motif - min_motif], with their cursor bounds.  cw: chunk mode.  dropmap_valid:
+// d_dropmap holds the ends of the groups a filtered scan dropped.  first_edge_cap: first capacity of the edge-call list
+// (0: what the list has, 65 536 or a sixteenth of the streaks, whichever is largest); a list that overflows is sized by the
+// count and the calls kernel runs again.  scan_ms: what the scan and the pairing took, for the RIBBIT_PROFILE line.
+int window_calls_device(RibbitHandle *h, int stage, uint32_t n, bool full, const int32_t *min_span, ChunkWindow *cw, bool dropmap_valid,
+                        size_t first_edge_cap, double scan_ms, DeviceCalls *out) {
     int rc;
-    uint32_t n = 0;
     PinnedBuf<RibbitCall> &h_calls = h->win[stage].h_calls, &h_flush = h->win[stage].h_flush;
     PinnedBuf<int32_t> &h_pend = h->win[stage].h_pend;
     PinnedBuf<uint32_t> &h_ws = h->win[stage].h_ws;
     const bool profile = rb::profile_on();
-    const double t_scan = now_ms();
-    if ((rc = scan_and_pair_streaks(h, stage, &n, full ? nullptr : min_span))) return rc;
     const double t0 = now_ms();
     const uint32_t nm = (uint32_t)(h->params.max_motif - h->params.min_motif + 1);
     const uint32_t n_words = (uint32_t)(h->length / 32 + 1);
@@ -118,7 +120,7 @@ int window_stage_device(RibbitHandle *h, int stage, bool full, int (*min_span)(i
     HIP_TRY(hipGetLastError());
     // length filter of the stage (seedlen_cutoffs), per motif
     std::vector<int32_t> spans(nm, 0);
-    if (!full) for (uint32_t mi = 0; mi < nm; ++mi) spans[mi] = min_span(h->params.min_motif + (int)mi);
+    if (!full) spans.assign(min_span, min_span + nm);
     if ((rc = h->d_min_span.ensure(nm))) return rc;
     HIP_TRY(hipMemcpyAsync(h->d_min_span.p, spans.data(), nm * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     if ((rc = h->d_flush.ensure(nm))) return rc;
@@ -126,7 +128,7 @@ int window_stage_device(RibbitHandle *h, int stage, bool full, int (*min_span)(i
     if ((rc = h->d_bitmap.ensure(n_words + 1))) return rc;
     if ((rc = h_ws.ensure(rb::WS_WORDS))) return rc;
     if ((rc = h_flush.ensure(nm))) return rc;
-    size_t edge_cap = std::max<size_t>(h->d_edge_keys.cap, std::max<size_t>((size_t)1 << 16, n / 16));
+    size_t edge_cap = first_edge_cap ? first_edge_cap : std::max<size_t>(h->d_edge_keys.cap, std::max<size_t>((size_t)1 << 16, n / 16));
     // the events are spent: their buffer (2 x 8 bytes per streak at least) receives the unsorted calls
     uint64_t *keys = h->d_events.p, *vals = h->d_events.p + h->d_events.cap / 2;
     uint32_t n_main = 0, n_edge = 0;
@@ -147,7 +149,7 @@ int window_stage_device(RibbitHandle *h, int stage, bool full, int (*min_span)(i
         if (cw) { w.own_lo = cw->own_lo; w.own_hi = cw->own_hi; w.z_lo = cw->z_lo; w.keep_flush = cw->keep_flush ? 1 : 0; }
         rb::launch_window_calls(w, h->stream);
         HIP_TRY(hipGetLastError());
-        if (h->dropmap_valid && !full) {
+        if (dropmap_valid && !full) {
             rb::launch_merge_dropmap(h->d_dropmap.p, (uint32_t)dropmap_words(h->length), n_words, w.own_lo, w.own_hi, h->d_bitmap.p,
                                      h->d_ws_counters.p, h->stream);
             HIP_TRY(hipGetLastError());
@@ -220,8 +222,20 @@ int window_stage_device(RibbitHandle *h, int stage, bool full, int (*min_span)(i
     h->host_ms = now_ms() - t0;
     if (profile)
         std::fprintf(stderr, "[window stage %d%s] scan + pairing %.1f ms (%u streaks), group scan + calls kernel %.1f ms, sort + bounds + read-back %.1f ms: "
-                     "%u calls, %u edge calls, %zu flush calls\n", stage, full ? " full" : "", t0 - t_scan, n, t_calls - t0, now_ms() - t_calls, n_main, n_edge, nf);
+                     "%u calls, %u edge calls, %zu flush calls\n", stage, full ? " full" : "", scan_ms, n, t_calls - t0, now_ms() - t_calls, n_main, n_edge, nf);
     return RIBBIT_OK;
+}
+
+// The whole window stage on the device.  full: every call, unfiltered (the call-list entry points and the parity tests);
+// otherwise only the calls that pass min_span, with their cursor bounds.  cw: chunk mode.
+int window_stage_device(RibbitHandle *h, int stage, bool full, int (*min_span)(int), DeviceCalls *out, ChunkWindow *cw) {
+    int rc;
+    uint32_t n = 0;
+    const double t_scan = now_ms();
+    if ((rc = scan_and_pair_streaks(h, stage, &n, full ? nullptr : min_span))) return rc;
+    std::vector<int32_t> spans((size_t)(h->params.max_motif - h->params.min_motif + 1), 0);
+    if (!full) for (size_t mi = 0; mi < spans.size(); ++mi) spans[mi] = min_span(h->params.min_motif + (int)mi);
+    return window_calls_device(h, stage, n, full, spans.data(), cw, h->dropmap_valid, 0, now_ms() - t_scan, out);
 }
 
 void full_calls_from_device(const DeviceCalls &dc, rb::CallVec &calls) {
@@ -472,6 +486,78 @@ int ribbit_hip_anchored_calls(RibbitHandle *h, const RibbitCall **out, size_t *n
     if (rc) return rc;
     *out = h->anchored_calls.data();
     *n = h->anchored_calls.size();
+    return RIBBIT_OK;
+}); }
+
+int ribbit_hip_debug_window_calls(RibbitHandle *h, int stage, const RibbitDebugWindowStage *in, RibbitChunkCalls *out, uint32_t *n_edge) {
+    return guarded("the window stage on caller-made streaks", [&]() -> int {
+    if (!h || !in || !out || !n_edge) return fail(RIBBIT_E_ARG, "null argument");
+    if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
+    if (h->pair_pending) return fail(RIBBIT_E_STATE, "a perfect scan is in flight on this handle: call ribbit_hip_scan_perfect_end first");
+    if (stage != RIBBIT_STAGE_SUBST && stage != RIBBIT_STAGE_ANCHORED) return fail(RIBBIT_E_ARG, "stage must be RIBBIT_STAGE_SUBST or RIBBIT_STAGE_ANCHORED");
+    const bool full = in->full != 0;
+    if ((in->n_streaks && !in->streaks) || (!full && !in->min_span) || (in->n_dropped && !in->dropped_ends)) return fail(RIBBIT_E_ARG, "null argument");
+    const size_t n = in->n_streaks, most = (size_t)1 << 24;
+    if (n > most || in->n_dropped > most || in->first_edge_cap > most) return fail(RIBBIT_E_ARG, "bad size");
+    const int64_t L = h->length;
+    if (in->own_lo < 0 || in->own_hi < in->own_lo || in->z_lo < 0 || in->z_lo > INT32_MAX || in->pos_offset < 0 || in->pos_offset + L > INT32_MAX)
+        return fail(RIBBIT_E_ARG, "bad chunk geometry: own [%lld, %lld), first exact position %lld, piece of %lld bases at %lld", (long long)in->own_lo,
+                    (long long)in->own_hi, (long long)in->z_lo, (long long)L, (long long)in->pos_offset);
+    // everything a kernel indexes with: positions, motifs, the terminator; the order the group scan and the joins rely on
+    for (size_t i = 0; i < n; ++i) {
+        const RibbitRun &r = in->streaks[i];
+        if (r.start < 0 || r.start >= r.end || r.end > L) return fail(RIBBIT_E_ARG, "streak %zu: [%d, %d) is no stretch of a record of %lld bases", i, r.start, r.end, (long long)L);
+        if (r.mlen < h->params.min_motif || r.mlen > h->params.max_motif) return fail(RIBBIT_E_ARG, "streak %zu: motif %d outside %d..%d", i, r.mlen, h->params.min_motif, h->params.max_motif);
+        if (r.term < RIBBIT_TERM_ZERO || r.term > RIBBIT_TERM_EOS) return fail(RIBBIT_E_ARG, "streak %zu: term %d", i, r.term);
+        if (i == 0) continue;
+        const RibbitRun &p = in->streaks[i - 1];
+        if (r.mlen < p.mlen || (r.mlen == p.mlen && r.start <= p.start)) return fail(RIBBIT_E_ARG, "streak %zu: not in (mlen, start) order", i);
+        if (r.mlen == p.mlen && r.start < p.end) return fail(RIBBIT_E_ARG, "streak %zu: overlaps the streak before it", i);
+    }
+    for (size_t i = 0; i < in->n_dropped; ++i) {
+        const int32_t e = in->dropped_ends[i];
+        if (e < 0 || e >= L) return fail(RIBBIT_E_ARG, "dropped end %zu: %d outside the record", i, e);
+        if (i > 0 && e <= in->dropped_ends[i - 1]) return fail(RIBBIT_E_ARG, "dropped end %zu: not ascending", i);
+    }
+    int rc;
+    if ((rc = bind_device(h))) return rc;
+    if (h->copy_pending && (rc = perfect_wait(h))) return rc;          // d_dense / d_events are shared with the perfect stage
+    // the buffers the stage inherits from the event pass, sized as that pass sizes them for 2 n events
+    size_t cap = std::max<size_t>(2 * n, rb::EV_SHARDS);
+    if ((rc = event_room(h, &cap, nullptr))) return rc;
+    if (n) HIP_TRY(hipMemcpyAsync(h->d_dense.p, in->streaks, n * sizeof(RibbitRun), hipMemcpyHostToDevice, h->stream));
+    const bool dropmap = !full && in->n_dropped > 0;
+    std::vector<uint32_t> words;
+    if (dropmap) {
+        words.assign(dropmap_words(L), 0u);
+        for (size_t i = 0; i < in->n_dropped; ++i) words[(size_t)in->dropped_ends[i] >> 5] |= 1u << (in->dropped_ends[i] & 31);
+        if ((rc = h->d_dropmap.ensure(words.size()))) return rc;
+        HIP_TRY(hipMemcpyAsync(h->d_dropmap.p, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));      // (the sources are the caller's and a local)
+    h->dropmap_valid = false;                      // what a scan left in d_dropmap is gone
+    ChunkWindow cw;
+    cw.own_lo = (uint32_t)std::min<int64_t>(in->own_lo, 0xffffffffll);
+    cw.own_hi = (uint32_t)std::min<int64_t>(in->own_hi, 0xffffffffll);
+    cw.z_lo = (uint32_t)in->z_lo;
+    cw.keep_flush = in->keep_flush != 0;
+    cw.pos_offset = (int32_t)in->pos_offset;
+    std::memset(out, 0, sizeof *out);
+    out->tail_pend = -1;
+    *n_edge = 0;
+    DeviceCalls dc;
+    rc = window_calls_device(h, stage, (uint32_t)n, full, in->min_span, &cw, dropmap, in->first_edge_cap, 0.0, &dc);
+    h->timers.have[RIBBIT_TIME_GPU] = false;       // no scan began that interval
+    if (rc) return rc;
+    out->calls = dc.calls; out->n = dc.n;
+    out->pend = dc.pend;
+    out->tail_pend = dc.tail_pend;
+    out->flush = dc.flush; out->n_flush = dc.n_flush;
+    out->inexact = cw.inexact ? 1 : 0;
+    out->dev_calls = h->d_dense.p;
+    out->dev_pend = dc.pend ? h->d_pend.p : nullptr;
+    out->streaks = (int64_t)n;
+    *n_edge = (uint32_t)h->last_edge_calls;
     return RIBBIT_OK;
 }); }
 

@@ -1,7 +1,8 @@
 """GPU tests of the chunk contract at the cuts where a chunk's logic can go wrong: one oracle run per record, then many plans
 checked against it.  A chunk is loaded with the tightest halos ribbit_hip_stage_calls_chunk accepts (2s+56 bases on the left,
 4s+16 on the right, s = max_motif + 2), so a kernel whose true reach exceeded the claimed one would show here; its kept
-calls, cursor bounds, tail_pend, flush calls, runs and run halves must be what tests/chunk_contract.py cuts out of the
+calls, cursor bounds (each -1 or the largest end before it, and together moving a merge's cursors as the full call list would:
+window_stage_contract.bounds_hold), tail_pend, flush calls, runs and run halves must be what tests/chunk_contract.py cuts out of the
 oracle's lists of the whole record.  Cuts sit on calls' scan positions and group ends, on the edges of N blocks, inside long
 N blocks and homopolymers, at the end of the record, and leave own ranges empty or one word long; the whole path (scan_part,
 merge_parts, the BED) runs over the same cuts rounded to words, over a sharded fuzz, and pieces run at offsets near INT32_MAX."""
@@ -16,6 +17,7 @@ from chunk_contract import ANCHORED_SPAN, SUBST_SPAN, _chunk_calls, _chunk_runs,
 from fuzz import fuzz_case
 from oracle_lib import LIST_ANCHORED, LIST_PERFECT, LIST_SUBST, Oracle
 from ribbit_amd import STAGE_ANCHORED, STAGE_SUBST, sharded
+from window_stage_contract import bounds_hold
 
 pytestmark = pytest.mark.gpu
 INT32_MAX = 2**31 - 1
@@ -148,6 +150,7 @@ def _check_chunk(o, got, own_lo, own_hi, where):
         assert _eq(g["calls"], calls), f"{where}: {key} calls"
         if g["pend"] is not None:
             assert np.all((g["pend"] == -1) | (g["pend"] == seen)), f"{where}: {key} pend"
+        assert bounds_hold(g["calls"], g["pend"], seen), f"{where}: {key} cursor bounds"
         assert g["tail_pend"] == tail, f"{where}: {key} tail_pend"
         assert _eq(g["flush"], flush), f"{where}: {key} flush"
 
@@ -162,6 +165,7 @@ def _whole(sc, o):
         assert not w["inexact"] and _eq(w["calls"], calls) and w["tail_pend"] == tail and _eq(w["flush"], flush), key
         if w["pend"] is not None:
             assert np.all((w["pend"] == -1) | (w["pend"] == seen)), key
+        assert bounds_hold(w["calls"], w["pend"], seen), f"{key} cursor bounds"
     return out
 
 
