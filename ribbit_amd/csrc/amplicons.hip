@@ -1,6 +1,6 @@
 // amplicons.hip -- every primer pair typed on the loaded record: where its first product lies and how long the repeat tract
 // inside it is (api_amplicons.cpp: ribbit_hip_record_pair_amplicons; include/ribbit_hip.h has the contract, kernels.h the order of
-// the launches).  The sites come from primer_products.hip's scan; two kernels follow it.
+// the launches).  The sites come from primer_products.hip's site search (kernels.h, at ProductLayout); two kernels follow it.
 //   first product   One lane per pair over its four sorted lists: product_walk.h's pair_products for the counts (no product is the
 //                   pair's own), and first_product for the least (f.x, v.x + v.k, forward_of, reverse_of).
 //   tract           One wavefront per pair with a product, four to a block, no LDS and no barrier.  The motif's two strands are
@@ -196,10 +196,9 @@ __global__ void __launch_bounds__(64 * TRACT_WAVES) amplicon_tracts_kernel(Devic
 
 AmpliconLayout amplicon_layout(int64_t n_pairs) {
     AmpliconLayout at{};
-    at.product = products_layout(2 * n_pairs, 0);
     WorkCarver w;
     at.rows = w.take((size_t)n_pairs * sizeof(RibbitRowAmplicon));
-    at.product_work = w.take(at.product.bytes);
+    at.sites = site_room(w, 2 * n_pairs);
     w.close(at, 0);
     return at;
 }
@@ -208,10 +207,10 @@ hipError_t launch_pair_amplicons(const DevicePlanes &pl, const int32_t *pairs, i
                                  const RibbitProductParams &prm, uint8_t *work, size_t work_bytes, const AmpliconLayout &at, const int32_t *site_lists,
                                  hipStream_t stream) {
     if (work_bytes < at.bytes || n_pairs < 1 || prm.max_product < 1 || prm.max_sites < 1 || record < 0 || pl.tail_words < 2) return hipErrorInvalidValue;
-    uint8_t *pw = work + at.product_work;
+    uint8_t *pw = work + at.sites.offset;
     RibbitRowAmplicon *rows = region<RibbitRowAmplicon>(work, at.rows);
     hipLaunchKernelGGL(pair_amplicons_kernel, dim3(grid_for(n_pairs, ROW_THREADS, ROW_MAX_BLOCKS)), dim3(ROW_THREADS), 0, stream, pairs, n_pairs,
-                       region<uint32_t>(pw, at.product.unique_of), region<UniqueOligo>(pw, at.product.uniques), region<uint32_t>(pw, at.product.counts), site_lists,
+                       region<uint32_t>(pw, at.sites.layout.unique_of), region<UniqueOligo>(pw, at.sites.layout.uniques), region<uint32_t>(pw, at.sites.layout.counts), site_lists,
                        (int)prm.max_product, (int)prm.max_sites, record, rows);
     hipLaunchKernelGGL(amplicon_tracts_kernel, dim3(grid_for(n_pairs, TRACT_WAVES, 4 * ROW_MAX_BLOCKS)), dim3(64 * TRACT_WAVES), 0, stream, pl, pool, offsets, n_pairs, rows);
     return hipGetLastError();

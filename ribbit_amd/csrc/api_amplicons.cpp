@@ -1,10 +1,9 @@
 // api_amplicons.cpp -- every chosen primer pair typed on any loaded record: the sites of its two oligos, its products, where the
 // first of them lies and the repeat tract inside it (amplicons.hip); see api_internal.h for the map of the files behind
-// include/ribbit_hip.h.  The GPU form serves the pairs in batches by the rule of ribbit_hip_record_specific_primer_pairs, with two
-// oligos per pair: a batch's oligos, its pairs and its motifs go down through stage_down, the oligos go through
-// ribbit_hip_record_primer_products' uniques, patterns and site scan (their work buffer is a region of this call's,
-// rb::AmpliconLayout; the unique oligos are read in the middle of a batch and size the site lists), and two kernels fill the
-// records.  After the copy back everything the device returned is checked.
+// include/ribbit_hip.h.  The GPU form serves the pairs in batches by the rule of ribbit_hip_record_specific_primer_pairs (site_batch,
+// api_internal.h), with two oligos per pair: a batch's oligos, its pairs and its motifs go down through stage_down, the oligos go
+// through the site search of ribbit_hip_record_primer_products (search_sites; its work buffer is a region of this call's,
+// rb::AmpliconLayout::sites), and two kernels fill the records.  After the copy back everything the device returned is checked.
 // The host twin works from the bytes of the sequence with the host code behind the products' twin (primers_host.h): every pair of
 // sites walked for the least key, the tract found as the contract first states it, every phase of both strands tried letter by
 // letter.  It shares nothing with the kernels.  The sum and the text need no GPU.
@@ -16,9 +15,6 @@ namespace {
 
 static_assert(sizeof(RibbitRowAmplicon) == 64 && sizeof(RibbitRowPrimerPair) == 128, "16 and 32 ints");
 constexpr int32_t MAX_MOTIF = 1023;
-constexpr size_t AMPLICON_LIST_BYTES = (size_t)256 << 20, MAX_BATCH_SITES = (size_t)1 << 29;
-
-bool has_pair(const RibbitRowPrimerPair &r) { return r.left.start >= 0; }
 
 RibbitRowAmplicon no_amplicon() {
     RibbitRowAmplicon a{};
@@ -53,14 +49,6 @@ int check_args(const RibbitRowPrimerPair *pairs, size_t n, const char *motifs, c
     return check_motifs(motifs, offsets, n);
 }
 
-// the pairs of one batch: as many as the site lists' room holds with two oligos a pair, or what the test asked for, within what
-// one site scan takes
-size_t batch_pairs(const RibbitHandle *h, const RibbitProductParams &product) {
-    const size_t per_pair = 2 * (size_t)product.max_sites;      // the list slots of a pair's patterns of one strand
-    const size_t by_rule = std::max<size_t>(1, AMPLICON_LIST_BYTES / (2 * per_pair * sizeof(int32_t)));
-    return std::min(h->rows.specific_batch ? h->rows.specific_batch : by_rule, std::max<size_t>(1, MAX_BATCH_SITES / per_pair));
-}
-
 int record_amplicons_impl(RibbitHandle *h, const RibbitRowPrimerPair *pairs, size_t n, const char *motifs, const int32_t *offsets, int32_t record,
                           const RibbitProductParams *params, const RibbitRowAmplicon **rows) {
     if (!h) return fail(RIBBIT_E_ARG, "null handle");
@@ -76,11 +64,11 @@ int record_amplicons_impl(RibbitHandle *h, const RibbitRowPrimerPair *pairs, siz
     const int64_t length = h->length;
     if (length == 0) return RIBBIT_OK;      // (no window fits: no sites, no products)
     if ((rc = bind_device(h))) return rc;
-    const size_t batch = std::min(batch_pairs(h, *params), n);
+    const size_t batch = std::min(site_batch(h, 2, *params), n);
     const rb::AmpliconLayout at = rb::amplicon_layout((int64_t)batch);
     if ((rc = buf.d_work.ensure(at.bytes, true))) return rc;
     if ((rc = buf.h_product_header.ensure(sizeof(rb::ProductHeader) / sizeof(uint32_t)))) return rc;
-    uint8_t *work = buf.d_work.p, *product_work = work + at.product_work;
+    uint8_t *work = buf.d_work.p;
     std::vector<RibbitOligo> oligos;
     std::vector<int32_t> quads;
     for (size_t from = 0; from < n; from += batch) {
@@ -104,19 +92,10 @@ int record_amplicons_impl(RibbitHandle *h, const RibbitRowPrimerPair *pairs, siz
                                       {motifs + offsets[from], (size_t)(offsets[from + m] - offsets[from])}};
         const uint8_t *d_at[4] = {nullptr, nullptr, nullptr, nullptr};
         if ((rc = stage_down(h, down, 4, d_at))) return rc;
-        // the site search's own layout for exactly these oligos, inside the room that was set aside for two a pair
+        SiteSearch found;
+        if ((rc = search_sites(h, reinterpret_cast<const RibbitOligo *>(d_at[0]), oligos.size(), 0, *params, work + at.sites.offset, at.sites.layout.bytes, true, found))) return rc;
         rb::AmpliconLayout use = at;
-        use.product = rb::products_layout((int64_t)oligos.size(), 0);
-        if (use.product.bytes > at.product.bytes) return fail(RIBBIT_E_INTERNAL, "%zu oligos need %zu bytes, not the %zu set aside", oligos.size(), use.product.bytes, at.product.bytes);
-        HIP_TRY(rb::launch_product_uniques(reinterpret_cast<const RibbitOligo *>(d_at[0]), (int64_t)oligos.size(), *params, product_work, at.product.bytes, use.product, h->stream));
-        HIP_TRY(hipMemcpyAsync(buf.h_product_header.p, product_work + use.product.header, sizeof(rb::ProductHeader), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        const size_t uniques = reinterpret_cast<const rb::ProductHeader *>(buf.h_product_header.p)->uniques;
-        if (uniques < 1 || uniques > oligos.size()) return fail(RIBBIT_E_INTERNAL, "%zu unique oligos of %zu", uniques, oligos.size());
-        // the lists' room is fixed here, by the patterns, and does not grow with the sites the scan finds
-        if ((rc = buf.d_site_lists.ensure(2 * uniques * (size_t)params->max_sites, true))) return rc;
-        HIP_TRY(rb::launch_product_scan(h->planes(), (int64_t)oligos.size(), (int64_t)uniques, *params, product_work, at.product.bytes, use.product, buf.d_site_lists.p, true,
-                                        h->stream));
+        use.sites.layout = found.at;
         HIP_TRY(rb::launch_pair_amplicons(h->planes(), reinterpret_cast<const int32_t *>(d_at[1]), (int64_t)m, d_at[3], reinterpret_cast<const int32_t *>(d_at[2]), record,
                                           *params, work, buf.d_work.cap, use, buf.d_site_lists.p, h->stream));
         HIP_TRY(hipMemcpyAsync(out + from, work + at.rows, m * sizeof(RibbitRowAmplicon), hipMemcpyDeviceToHost, h->stream));
@@ -146,17 +125,6 @@ int record_amplicons_impl(RibbitHandle *h, const RibbitRowPrimerPair *pairs, siz
 }
 
 // ---- the host twin, in letters
-char letter_at(const unsigned char *seq, int64_t p) {      // the base there in upper case, or 0 for a byte of kind `other`
-    const int c = code_of(seq[p]);
-    return c < 0 ? 0 : "ACGT"[c];
-}
-
-std::string reverse_complement(const std::string &o) {
-    std::string q;
-    for (size_t j = o.size(); j-- > 0;) q += o[j] == 'A' ? 'T' : o[j] == 'C' ? 'G' : o[j] == 'G' ? 'C' : 'A';
-    return q;
-}
-
 struct Site { int64_t x, k; int32_t of; };
 
 // the longest stretch of [is, ie) that reads as the motif repeated, at any phase, on either strand: every phase walked on its own
@@ -239,8 +207,7 @@ int host_record_amplicons_impl(const char *sequence, int64_t length, const Ribbi
                                const RibbitProductParams *params, RibbitRowAmplicon **rows) {
     int rc;
     if ((rc = check_args(pairs, n, motifs, offsets, record, params, rows))) return rc;
-    if (length < 0 || length > (int64_t)INT32_MAX) return fail(RIBBIT_E_ARG, "a record of %lld bases", (long long)length);
-    if (!sequence && length > 0) return fail(RIBBIT_E_ARG, "bad sequence");
+    if ((rc = check_sequence(sequence, length))) return rc;
     const unsigned char *seq = reinterpret_cast<const unsigned char *>(sequence);
     const RibbitProductParams prm = *params;
     Handed<RibbitRowAmplicon> out;
@@ -255,8 +222,6 @@ int host_record_amplicons_impl(const char *sequence, int64_t length, const Ribbi
 }
 
 // ---- the sum over records
-int32_t saturating_sum(int32_t a, int32_t b) { return (int32_t)std::min<int64_t>((int64_t)a + b, INT32_MAX); }
-
 int amplicons_merge_impl(RibbitRowAmplicon *into, const RibbitRowAmplicon *from, size_t n) {
     if ((!into || !from) && n > 0) return fail(RIBBIT_E_ARG, "null argument");
     for (size_t i = 0; i < n; ++i) {

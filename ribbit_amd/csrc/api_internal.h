@@ -21,16 +21,18 @@
 //   api_composition.cpp the base counts of every row, its flanks and every window from the bit planes (composition.hip), their host twins, both texts
 //   api_primers.cpp     a forward and a reverse primer in the flanks of every target, from the bit planes and the rows' coverage (primers.hip), its host twin, the text
 //   api_primer_pairs.cpp  the two primers of every target chosen as a pair and checked for dimers and hairpins (primer_pairs.hip), its host twin, the oligo checks, the text
-//   api_primer_products.cpp  the sites of oligos on either strand of the record and the products of primer pairs among them (primer_products.hip), their host twins, the text
-//   api_primer_specific.cpp  the best primer pair of every target that amplifies nothing else in the record (primer_specific.hip, with primer_products.hip's site scan), its host twin, the text
-//   api_primer_genome.cpp    a target's two shortlists as they leave their record, their pairs judged on any loaded record (primer_specific.hip), the host twins, the sum over records, the choice
-//   api_amplicons.cpp        every chosen pair typed on any loaded record: its first product and the repeat tract inside it (amplicons.hip, with primer_products.hip's site scan), its host twin, the sum over records, the text
+//   api_primer_products.cpp  the sites of oligos on either strand of the record and the products of primer pairs among them (primer_products.hip), their host twins, the text;
+//                            the site search of every in-silico PCR (search_sites) and the rule of its callers' batches (site_batch)
+//   api_primer_specific.cpp  the best primer pair of every target that amplifies nothing else in the record (primer_specific.hip, through search_sites), its host twin, the text
+//   api_primer_genome.cpp    a target's two shortlists as they leave their record, their pairs judged on any loaded record (primer_specific.hip, through search_sites), the host twins, the sum over records, the choice
+//   api_amplicons.cpp        every chosen pair typed on any loaded record: its first product and the repeat tract inside it (amplicons.hip, through search_sites), its host twin, the sum over records, the text
 // The last sixteen are the row outputs: their buffers are the handle's RowBufs `rows`, where all device work of a call is carved from
 // one buffer by the layout its .hip file states (kernels.h); best, classes, compound, interruptions, nearest, primers and primer pairs stage their inputs through stage_down, what their host
 // sides share is below (hand_out, clipped_sorted_rows), what their kernels share is row_kernels.h, and the BED text they read and
 // write (the row format, the reader in pieces, the writer in pieces) is
 //   bed_text.h          a row's named fields, bed_read / bed_gather, BedLines, write_pieces / join_text, put_number
-//   primers_host.h      what the primer outputs' host sides share: the parameter checks, a target's windows, one candidate from the bytes, a primer's and a pair's columns
+//   primers_host.h      what the primer outputs' host sides share: the parameter checks, a target's windows, one candidate from the bytes, a primer's and a pair's columns,
+//                       the writer of the pairs' texts, the twins' index of distinct oligos
 // Host threads: every team of them, here and in refine.cpp, parallel_merge.cpp and host_planes.cpp, is started by rb::on_threads /
 // rb::over_pieces of host_threads.h (part 0 on the caller, a thread that cannot start leaves its part to the caller, all joined, the
 // first exception of any part rethrown on the caller: it then meets guarded() below); the thread count rule (the handle's, else
@@ -492,7 +494,8 @@ struct RibbitHandle {
         PinnedBuf<uint8_t> h_products;
         PinnedBuf<int32_t> h_site_positions;
         // the specific primer pairs (api_primer_specific.cpp): the three records of every target on their way up, one array behind the
-        // other; a batch's number of oligos on its way up; the targets of a batch (0: as many as SPECIFIC_LIST_BYTES of site lists hold)
+        // other; a batch's number of oligos on its way up; the targets or pairs of a batch of every caller of search_sites (0: by the
+        // rule of site_batch)
         PinnedBuf<uint8_t> h_specific;
         PinnedBuf<uint32_t> h_specific_header;
         size_t specific_batch = 0;
@@ -611,5 +614,20 @@ int build_coverage(RibbitHandle *h, const int32_t *intervals, size_t n);
 inline size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
 struct StageSegment { const void *p; size_t bytes; };
 int stage_down(RibbitHandle *h, const StageSegment *segs, size_t n_segs, const uint8_t **at);
+// api_primer_products.cpp: the site search of an in-silico PCR (kernels.h, at rb::ProductLayout) for n_oligos >= 1 oligos on the
+// device, enqueued on the handle's stream with one synchronise in the middle.  product_work: the search's work buffer of room_bytes,
+// the whole of rows.d_work or a region of it, which the caller has sized before its first launch: nothing here grows d_work.  The
+// layout is carved for exactly these oligos (and n_pairs records in `out`) and must fit the room; the unique oligos are read back
+// into rows.h_product_header (the caller's to size) and size rows.d_site_lists, which the scan fills.
+struct SiteSearch {
+    rb::ProductLayout at;      // offsets from product_work
+    size_t uniques = 0;
+};
+int search_sites(RibbitHandle *h, const RibbitOligo *d_oligos, size_t n_oligos, size_t n_pairs, const RibbitProductParams &prm, uint8_t *product_work, size_t room_bytes,
+                 bool use_filter, SiteSearch &out);
+// ... and the items (targets, pairs) of one batch of a call that searches oligos_per_item oligos for each: as many as SITE_LIST_BYTES
+// of site lists hold at the worst case of distinct oligos, or what ribbit_hip_debug_set_specific_batch asked for, within what one
+// search takes
+size_t site_batch(const RibbitHandle *h, size_t oligos_per_item, const RibbitProductParams &prm);
 
 }  // namespace rbapi

@@ -3,20 +3,20 @@
 // the records and the choice made from the sum; see api_internal.h for the map of the files behind include/ribbit_hip.h.
 // ribbit_hip_record_primer_shortlists runs the first launch of ribbit_hip_record_specific_primer_pairs and copies the lists and the
 // side counts back.  ribbit_hip_record_shortlist_verdicts takes such lists down again, a batch of targets at a time by the rule of
-// that call: their held primers become the batch's oligos on the device, the site scan of primer_products.hip searches them on the
-// loaded record, and one wavefront per target judges its 64 pairs (rb::VerdictLayout).  Everything that comes from the caller is
+// that call: their held primers become the batch's oligos on the device, the site search (search_sites, api_internal.h) finds them
+// on the loaded record, and one wavefront per target judges its 64 pairs (rb::VerdictLayout).  Everything that comes from the caller is
 // checked before it goes down, because the kernels index by it.
 // The host twins work from the bytes of the sequence with the host code behind the twins they combine (primers_host.h) and share
 // nothing with the kernels.  The sum and the choice need no GPU and no sequence.
 #include "primers_host.h"
 
-#include <map>
 #include <string>
 
 namespace {
 
 static_assert(sizeof(RibbitTargetShortlists) == 400 && sizeof(RibbitTargetVerdicts) == 176 && sizeof(RibbitPrimer) == 24, "100 ints; four masks and 36 ints; 6 ints");
-constexpr size_t SLOTS = 2 * RIBBIT_PRIMER_PAIR_SHORTLIST, LIST_BYTES = SLOTS * sizeof(RibbitPrimer), SHORTLIST_BATCH = 32768;
+using rb::SLOTS;
+constexpr size_t LIST_BYTES = SLOTS * sizeof(RibbitPrimer), SHORTLIST_BATCH = 32768;
 
 // the lists as the kernels index them: the held places first, no more of them than `shortlist`, every held primer of least .. 32 bases
 int check_lists(const RibbitTargetShortlists *lists, size_t n, int32_t shortlist, int32_t least) {
@@ -43,8 +43,6 @@ int check_verdict_args(const RibbitTargetShortlists *lists, size_t n_targets, in
     if ((rc = check_primer_product_params(product))) return rc;
     return check_lists(lists, n_targets, pair->shortlist, product->seed);
 }
-
-int32_t saturating_sum(int32_t a, int32_t b) { return (int32_t)std::min<int64_t>((int64_t)a + b, INT32_MAX); }
 
 // a target's pairs in the order of the choice and the mask of their bits
 struct ListedPairs {
@@ -157,12 +155,12 @@ int record_verdicts_impl(RibbitHandle *h, const RibbitTargetShortlists *lists, s
         return RIBBIT_OK;
     }
     if ((rc = bind_device(h))) return rc;
-    const size_t batch = std::min(specific_batch_targets(h, *product), n_targets);
+    const size_t batch = std::min(site_batch(h, SLOTS, *product), n_targets);
     const rb::VerdictLayout at = rb::verdict_layout((int64_t)batch);
     if ((rc = buf.d_work.ensure(at.bytes, true))) return rc;
     if ((rc = buf.h_specific_header.ensure(sizeof(rb::SpecificHeader) / sizeof(uint32_t)))) return rc;
     if ((rc = buf.h_product_header.ensure(sizeof(rb::ProductHeader) / sizeof(uint32_t)))) return rc;
-    uint8_t *work = buf.d_work.p, *product_work = work + at.product_work;
+    uint8_t *work = buf.d_work.p;
     std::vector<RibbitPrimer> packed(batch * SLOTS);
     for (size_t from = 0; from < n_targets; from += batch) {
         const size_t m = std::min(batch, n_targets - from);
@@ -178,21 +176,12 @@ int record_verdicts_impl(RibbitHandle *h, const RibbitTargetShortlists *lists, s
         HIP_TRY(hipStreamSynchronize(h->stream));
         const size_t oligos = reinterpret_cast<const rb::SpecificHeader *>(buf.h_specific_header.p)->oligos;
         if (oligos > SLOTS * m) return fail(RIBBIT_E_INTERNAL, "%zu listed primers of %zu targets", oligos, m);
-        // the site search's own layout for exactly these oligos, inside the room that was set aside for 16 a target
         rb::VerdictLayout use = at;
         if (oligos > 0) {
-            use.product = rb::products_layout((int64_t)oligos, 0);
-            if (use.product.bytes > at.product.bytes) return fail(RIBBIT_E_INTERNAL, "%zu oligos need %zu bytes, not the %zu set aside", oligos, use.product.bytes, at.product.bytes);
-            HIP_TRY(rb::launch_product_uniques(reinterpret_cast<const RibbitOligo *>(work + at.oligos), (int64_t)oligos, *product, product_work, at.product.bytes, use.product,
-                                               h->stream));
-            HIP_TRY(hipMemcpyAsync(buf.h_product_header.p, product_work + use.product.header, sizeof(rb::ProductHeader), hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            const size_t uniques = reinterpret_cast<const rb::ProductHeader *>(buf.h_product_header.p)->uniques;
-            if (uniques < 1 || uniques > oligos) return fail(RIBBIT_E_INTERNAL, "%zu unique oligos of %zu", uniques, oligos);
-            // the lists' room is fixed here, by the patterns, and does not grow with the sites the scan finds
-            if ((rc = buf.d_site_lists.ensure(2 * uniques * (size_t)product->max_sites, true))) return rc;
-            HIP_TRY(rb::launch_product_scan(h->planes(), (int64_t)oligos, (int64_t)uniques, *product, product_work, at.product.bytes, use.product, buf.d_site_lists.p, true,
-                                            h->stream));
+            SiteSearch found;
+            if ((rc = search_sites(h, reinterpret_cast<const RibbitOligo *>(work + at.oligos), oligos, 0, *product, work + at.sites.offset, at.sites.layout.bytes, true, found)))
+                return rc;
+            use.sites.layout = found.at;
         }
         HIP_TRY(rb::launch_shortlist_verdicts(d_lists, (int64_t)m, home != 0, *pair, *product, work, buf.d_work.cap, use, buf.d_site_lists.p, h->stream));
         HIP_TRY(hipMemcpyAsync(out + from, work + at.verdicts, m * sizeof(RibbitTargetVerdicts), hipMemcpyDeviceToHost, h->stream));
@@ -216,12 +205,6 @@ int record_verdicts_impl(RibbitHandle *h, const RibbitTargetShortlists *lists, s
 }
 
 // ---- the host twins
-int check_sequence(const char *sequence, int64_t length) {
-    if (length < 0 || length > (int64_t)INT32_MAX) return fail(RIBBIT_E_ARG, "a record of %lld bases", (long long)length);
-    if (!sequence && length > 0) return fail(RIBBIT_E_ARG, "bad sequence");
-    return RIBBIT_OK;
-}
-
 int host_record_shortlists_impl(const char *sequence, int64_t length, const int32_t *intervals, size_t n, const int32_t *targets, size_t n_targets,
                                 const RibbitPrimerParams *params, const RibbitPrimerPairParams *pair, RibbitTargetShortlists **lists) {
     int rc;
@@ -259,23 +242,16 @@ int host_record_verdicts_impl(const char *sequence, int64_t length, const Ribbit
         for (size_t i = lo; i < hi; ++i) listed_pairs(lists[i], prs, found[i]);
     });
     // the sites of every distinct oligo among the held places, each searched once
-    std::map<std::string, size_t> index;
-    std::vector<const std::string *> distinct;
+    HostOligoIndex index;
     std::vector<size_t> oligo_of(n_targets * SLOTS, SIZE_MAX);
     for (size_t i = 0; i < n_targets; ++i)
         for (size_t k = 0; k < SLOTS; ++k) {
             const bool right = k >= SLOTS / 2;
             const RibbitPrimer &p = right ? lists[i].right[k - SLOTS / 2] : lists[i].left[k];
             if ((int)(right ? k - SLOTS / 2 : k) >= host_held_places(right ? lists[i].right : lists[i].left)) continue;
-            const auto at = index.emplace(host_listed_oligo(p, right), distinct.size());
-            if (at.second) distinct.push_back(&at.first->first);
-            oligo_of[i * SLOTS + k] = at.first->second;
+            oligo_of[i * SLOTS + k] = index.add(host_listed_oligo(p, right));
         }
-    std::vector<HostSites> sites(distinct.size());
-    const unsigned site_threads = (unsigned)std::max<size_t>(1, std::min<size_t>(rb::host_thread_count(0), distinct.size()));
-    rb::over_pieces(distinct.size(), site_threads, [&](size_t lo, size_t hi, unsigned) {
-        for (size_t k = lo; k < hi; ++k) sites[k] = host_oligo_sites(seq, length, *distinct[k], prd);
-    });
+    index.search(seq, length, prd);
     // the judgement
     for (size_t i = 0; i < n_targets; ++i) {
         RibbitTargetVerdicts v{};
@@ -284,12 +260,12 @@ int host_record_verdicts_impl(const char *sequence, int64_t length, const Ribbit
         v.home_records = home;
         for (size_t k = 0; k < SLOTS; ++k)
             if (oligo_of[i * SLOTS + k] != SIZE_MAX) {
-                v.forward[k] = (int32_t)sites[oligo_of[i * SLOTS + k]].forward.size();
-                v.reverse[k] = (int32_t)sites[oligo_of[i * SLOTS + k]].reverse.size();
+                v.forward[k] = (int32_t)index.sites(oligo_of[i * SLOTS + k]).forward.size();
+                v.reverse[k] = (int32_t)index.sites(oligo_of[i * SLOTS + k]).reverse.size();
             }
         for (size_t at = 0; at < found[i].ordered.size(); ++at) {
             const RibbitRowPrimerPair &r = found[i].ordered[at];
-            const RibbitRowProducts p = host_products_among(sites[oligo_of[i * SLOTS + (size_t)r.left_rank]], sites[oligo_of[i * SLOTS + SLOTS / 2 + (size_t)r.right_rank]],
+            const RibbitRowProducts p = host_products_among(index.sites(oligo_of[i * SLOTS + (size_t)r.left_rank]), index.sites(oligo_of[i * SLOTS + SLOTS / 2 + (size_t)r.right_rank]),
                                                             r.left.length, r.right.length, home ? r.left.start : -1, home ? r.right.start : -1, prd);
             const bool over = p.products < 0;
             const int32_t others = over ? -1 : p.products - p.own;

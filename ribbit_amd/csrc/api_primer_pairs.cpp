@@ -16,7 +16,9 @@ namespace {
 static_assert(sizeof(RibbitRowPrimerPair) == 128 && sizeof(RibbitPrimerPairParams) == 28, "32 and 7 ints");
 constexpr int32_t MAX_LIMIT = 32, MAX_TM_DIFFERENCE = 2000;
 
-int check_pair_params(const RibbitPrimerPairParams *p) {
+}  // namespace
+
+int rbapi::check_primer_pair_params(const RibbitPrimerPairParams *p) {
     if (!p) return fail(RIBBIT_E_ARG, "null argument");
     if (p->shortlist < 1 || p->shortlist > RIBBIT_PRIMER_PAIR_SHORTLIST) return fail(RIBBIT_E_ARG, "shortlist %d is outside 1 .. %d", (int)p->shortlist, RIBBIT_PRIMER_PAIR_SHORTLIST);
     const struct { const char *name; int32_t value; } limits[] = {{"max_self_any", p->max_self_any}, {"max_self_end", p->max_self_end}, {"max_hairpin", p->max_hairpin},
@@ -28,10 +30,12 @@ int check_pair_params(const RibbitPrimerPairParams *p) {
     return RIBBIT_OK;
 }
 
+namespace {
+
 int check_args(const int32_t *intervals, size_t n, const int32_t *targets, size_t n_targets, const RibbitPrimerParams *params, const RibbitPrimerPairParams *pair,
                const void *rows) {
     if (const int rc = check_primer_args(intervals, n, targets, n_targets, params, rows)) return rc;
-    return check_pair_params(pair);
+    return check_primer_pair_params(pair);
 }
 
 // a target without a pair: the six counts stay
@@ -241,14 +245,6 @@ void shortlists_of(const unsigned char *seq, const std::vector<uint8_t> &covered
     for (const Listed &it : s.right) s.rp.push_back(primer_of(seq, it));
 }
 
-void ordered_pairs_of(const unsigned char *seq, const std::vector<uint8_t> &covered, const Flanks &f, const RibbitPrimerParams &prm, const RibbitPrimerPairParams &pair,
-                      std::vector<RibbitRowPrimerPair> &ordered, RibbitRowPrimerPair &none) {
-    Shortlists s;
-    shortlists_of(seq, covered, f, prm, pair, s);
-    none = s.none;
-    pairs_among(s.left, s.right, s.lp, s.rp, pair, ordered, none);
-}
-
 // a stored primer as the twin lists it: its oligo from its packed bases, the self values from the oligo's letters
 Listed listed_of(const RibbitPrimer &p, bool right) {
     const uint64_t bases = (uint64_t)(uint32_t)p.bases_hi << 32 | (uint32_t)p.bases_lo;
@@ -263,7 +259,7 @@ Listed listed_of(const RibbitPrimer &p, bool right) {
 RibbitRowPrimerPair pair_of(const unsigned char *seq, const std::vector<uint8_t> &covered, const Flanks &f, const RibbitPrimerParams &prm, const RibbitPrimerPairParams &pair) {
     std::vector<RibbitRowPrimerPair> ordered;
     RibbitRowPrimerPair none;
-    ordered_pairs_of(seq, covered, f, prm, pair, ordered, none);
+    host_ordered_pairs(seq, covered, f, prm, pair, ordered, none);
     if (ordered.empty()) return none;
     return ordered.front();
 }
@@ -272,8 +268,7 @@ int host_record_primer_pairs_impl(const char *sequence, int64_t length, const in
                                   const RibbitPrimerParams *params, const RibbitPrimerPairParams *pair, RibbitRowPrimerPair **rows) {
     int rc;
     if ((rc = check_args(intervals, n, targets, n_targets, params, pair, rows))) return rc;
-    if (length < 0 || length > (int64_t)INT32_MAX) return fail(RIBBIT_E_ARG, "a record of %lld bases", (long long)length);
-    if (!sequence && length > 0) return fail(RIBBIT_E_ARG, "bad sequence");
+    if ((rc = check_sequence(sequence, length))) return rc;
     const unsigned char *seq = reinterpret_cast<const unsigned char *>(sequence);
     const std::vector<uint8_t> covered = host_covered(length, intervals, n);
     Handed<RibbitRowPrimerPair> out;
@@ -289,38 +284,15 @@ int host_record_primer_pairs_impl(const char *sequence, int64_t length, const in
 }
 
 // ---- the text
-enum : int { BAD_LENGTH = 1 };
-
 int bed_primer_pairs_text_impl(const char *bed, size_t bed_len, const RibbitRowPrimerPair *rows, size_t n, char **text, size_t *len) {
     if (!text || !len || (!bed && bed_len > 0) || (!rows && n > 0)) return fail(RIBBIT_E_ARG, "null argument");
-    const size_t parts = bed_text_parts(bed_len);
-    BedLines lines;
-    int rc;
-    if ((rc = lines.find(bed, bed_len, parts))) return rc;
-    if (lines.count() != n) return fail(RIBBIT_E_ARG, "the BED text has %zu lines, not the %zu of the rows", lines.count(), n);
-    return write_pieces(
-        parts, "the rows' primer pairs", text, len,
-        [&](size_t k, std::string &out) {
-            const size_t from = n * k / parts, to = n * (k + 1) / parts;
-            out.reserve(lines.start[to] - lines.start[from] + 192 * (to - from));
-            for (size_t i = from; i < to; ++i) {
-                const RibbitRowPrimerPair &r = rows[i];
-                if (const RibbitPrimer *p = bad_primer(r)) return PieceRefusal{BAD_LENGTH, i, (size_t)(uint32_t)p->length};
-                put_field(out, lines[i]);
-                put_pair_columns(out, r);
-                out += '\n';
-            }
-            return PieceRefusal{};
-        },
-        [](const PieceRefusal &bad) { return fail(RIBBIT_E_ARG, "row %zu: a primer of %d bases, not 1 .. %d", bad.a, (int)(int32_t)(uint32_t)bad.b, RIBBIT_PRIMER_MAX_LENGTH); });
+    return bed_pair_rows_text(bed, bed_len, rows, n, "the rows' primer pairs", 192, text, len, [](std::string &, size_t) {});
 }
 
 }  // namespace
 
-// ---- what api_primer_specific.cpp takes from here (primers_host.h)
+// ---- what the twins of the specific pairs and of a genome's pairs take from here (primers_host.h)
 namespace rbapi {
-
-int check_primer_pair_params(const RibbitPrimerPairParams *p) { return check_pair_params(p); }
 
 std::vector<uint8_t> host_covered(int64_t length, const int32_t *intervals, size_t n) {
     std::vector<uint8_t> covered((size_t)length, 0);
@@ -331,7 +303,10 @@ std::vector<uint8_t> host_covered(int64_t length, const int32_t *intervals, size
 
 void host_ordered_pairs(const unsigned char *seq, const std::vector<uint8_t> &covered, const Flanks &f, const RibbitPrimerParams &prm, const RibbitPrimerPairParams &pair,
                         std::vector<RibbitRowPrimerPair> &ordered, RibbitRowPrimerPair &none) {
-    ordered_pairs_of(seq, covered, f, prm, pair, ordered, none);
+    Shortlists s;
+    shortlists_of(seq, covered, f, prm, pair, s);
+    none = s.none;
+    pairs_among(s.left, s.right, s.lp, s.rp, pair, ordered, none);
 }
 
 void host_target_shortlists(const unsigned char *seq, const std::vector<uint8_t> &covered, const Flanks &f, const RibbitPrimerParams &prm, const RibbitPrimerPairParams &pair,

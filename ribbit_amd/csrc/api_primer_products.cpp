@@ -3,9 +3,12 @@
 // the bit planes the load packed and nothing else of the record: the oligos go down through stage_down, the work buffer is carved
 // by rb::ProductLayout, and two counts the device finds are read in the middle of a call (the unique oligos, which size the
 // patterns' lists before the scan; the kept positions, which size what comes back), so those two buffers are the handle's own.
-// After the copy back everything the device returned is checked.  The host twins work from the bytes of the sequence: every
-// window of every oligo judged letter by letter, every pair of sites walked.  They have no packed words, do not make the oligos
-// unique and share nothing with the kernels.  The text needs no GPU.
+// After the copy back everything the device returned is checked.  search_sites is the site search itself, the one place that
+// launches it: the two calls here take it with all of d_work as its room, the specific pairs, the shortlists' verdicts and the
+// amplicons with a region of theirs, and site_batch is the rule by which those three cut their work into batches.
+// The host twins work from the bytes of the sequence: every window of every oligo judged letter by letter, every pair of sites
+// walked.  They have no packed words, do not make the oligos unique and share nothing with the kernels; HostOligoIndex is for the
+// twins whose pairs share oligos.  The text needs no GPU.
 #include "primers_host.h"
 
 #include <string>
@@ -15,8 +18,15 @@ namespace {
 static_assert(sizeof(RibbitRowProducts) == 32 && sizeof(RibbitProductParams) == 16 && sizeof(RibbitOligo) == 12 && sizeof(RibbitOligoSites) == 16, "8, 4, 3 and 4 ints");
 constexpr int32_t MIN_SEED = 6, MAX_SEED = 16, MAX_MISMATCHES = 32, MAX_SITES = 1024;
 constexpr size_t MAX_PAIRS = (size_t)1 << 24, MAX_OLIGO_SITES = (size_t)1 << 29;
+constexpr size_t SITE_LIST_BYTES = (size_t)256 << 20, MAX_BATCH_SITES = (size_t)1 << 29;
 
-int check_product_params(const RibbitProductParams *p) {
+uint64_t bases_of(int32_t lo, int32_t hi) { return (uint64_t)(uint32_t)hi << 32 | (uint32_t)lo; }
+
+}  // namespace
+
+namespace rbapi {
+
+int check_primer_product_params(const RibbitProductParams *p) {
     if (!p) return fail(RIBBIT_E_ARG, "null argument");
     if (p->seed < MIN_SEED || p->seed > MAX_SEED) return fail(RIBBIT_E_ARG, "seed %d is outside %d .. %d", (int)p->seed, (int)MIN_SEED, (int)MAX_SEED);
     if (p->max_mismatches < 0 || p->max_mismatches > MAX_MISMATCHES) return fail(RIBBIT_E_ARG, "max_mismatches %d is outside 0 .. %d", (int)p->max_mismatches, (int)MAX_MISMATCHES);
@@ -25,21 +35,9 @@ int check_product_params(const RibbitProductParams *p) {
     return RIBBIT_OK;
 }
 
-int check_oligos(const RibbitOligo *oligos, size_t n, const RibbitProductParams *params) {
-    if (!oligos && n > 0) return fail(RIBBIT_E_ARG, "null argument");
-    if (const int rc = check_product_params(params)) return rc;
-    if (n > MAX_OLIGO_SITES / (size_t)params->max_sites) return fail(RIBBIT_E_ARG, "%zu oligos at max_sites %d", n, (int)params->max_sites);
-    for (size_t i = 0; i < n; ++i)
-        if (oligos[i].length < params->seed || oligos[i].length > RIBBIT_PRIMER_MAX_LENGTH)
-            return fail(RIBBIT_E_ARG, "oligo %zu: %d bases, not seed %d .. %d", i, (int)oligos[i].length, (int)params->seed, RIBBIT_PRIMER_MAX_LENGTH);
-    return RIBBIT_OK;
-}
-
-bool has_pair(const RibbitRowPrimerPair &r) { return r.left.start >= 0; }
-
-int check_pairs(const RibbitRowPrimerPair *pairs, size_t n, const RibbitProductParams *params) {
+int check_product_pairs(const RibbitRowPrimerPair *pairs, size_t n, const RibbitProductParams *params) {
     if (!pairs && n > 0) return fail(RIBBIT_E_ARG, "null argument");
-    if (const int rc = check_product_params(params)) return rc;
+    if (const int rc = check_primer_product_params(params)) return rc;
     if (n > MAX_PAIRS) return fail(RIBBIT_E_ARG, "%zu pairs", n);
     for (size_t i = 0; i < n; ++i)
         if (has_pair(pairs[i]))
@@ -49,10 +47,8 @@ int check_pairs(const RibbitRowPrimerPair *pairs, size_t n, const RibbitProductP
     return RIBBIT_OK;
 }
 
-uint64_t bases_of(int32_t lo, int32_t hi) { return (uint64_t)(uint32_t)hi << 32 | (uint32_t)lo; }
-
 // the two oligos of a pair, 5' to 3': the left primer's bases, the reverse complement of the right primer's
-void oligos_of(const RibbitRowPrimerPair &r, RibbitOligo &a, RibbitOligo &b) {
+void pair_oligos(const RibbitRowPrimerPair &r, RibbitOligo &a, RibbitOligo &b) {
     a = RibbitOligo{r.left.length, r.left.bases_lo, r.left.bases_hi};
     const uint64_t forward = bases_of(r.right.bases_lo, r.right.bases_hi);
     uint64_t q = 0;
@@ -60,31 +56,53 @@ void oligos_of(const RibbitRowPrimerPair &r, RibbitOligo &a, RibbitOligo &b) {
     b = RibbitOligo{r.right.length, (int32_t)(uint32_t)q, (int32_t)(uint32_t)(q >> 32)};
 }
 
-// ---- the GPU side: the oligos down, made unique, the scan; -> the layout and the lists, ready for either result
-struct Scanned {
-    rb::ProductLayout at;
-    size_t uniques = 0;
-};
+int search_sites(RibbitHandle *h, const RibbitOligo *d_oligos, size_t n_oligos, size_t n_pairs, const RibbitProductParams &prm, uint8_t *product_work, size_t room_bytes,
+                 bool use_filter, SiteSearch &out) {
+    RibbitHandle::RowBufs &buf = h->rows;
+    out.at = rb::products_layout((int64_t)n_oligos, (int64_t)n_pairs);
+    if (out.at.bytes > room_bytes) return fail(RIBBIT_E_INTERNAL, "%zu oligos need %zu bytes, not the %zu set aside", n_oligos, out.at.bytes, room_bytes);
+    HIP_TRY(rb::launch_product_uniques(d_oligos, (int64_t)n_oligos, prm, product_work, room_bytes, out.at, h->stream));
+    HIP_TRY(hipMemcpyAsync(buf.h_product_header.p, product_work + out.at.header, sizeof(rb::ProductHeader), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    out.uniques = reinterpret_cast<const rb::ProductHeader *>(buf.h_product_header.p)->uniques;
+    if (out.uniques < 1 || out.uniques > n_oligos) return fail(RIBBIT_E_INTERNAL, "%zu unique oligos of %zu", out.uniques, n_oligos);
+    // the lists' room is fixed here, by the patterns, and does not grow with the sites the scan finds
+    if (const int rc = buf.d_site_lists.ensure(2 * out.uniques * (size_t)prm.max_sites, true)) return rc;
+    HIP_TRY(rb::launch_product_scan(h->planes(), (int64_t)n_oligos, (int64_t)out.uniques, prm, product_work, room_bytes, out.at, buf.d_site_lists.p, use_filter, h->stream));
+    return RIBBIT_OK;
+}
 
-int scan_oligos(RibbitHandle *h, const StageSegment *segs, size_t n_segs, const uint8_t **d_at, size_t n_oligos, size_t n_pairs, const RibbitProductParams &prm, Scanned &sc) {
+size_t site_batch(const RibbitHandle *h, size_t oligos_per_item, const RibbitProductParams &prm) {
+    const size_t per_item = oligos_per_item * (size_t)prm.max_sites;      // the list slots of an item's patterns of one strand
+    const size_t by_rule = std::max<size_t>(1, SITE_LIST_BYTES / (2 * per_item * sizeof(int32_t)));
+    return std::min(h->rows.specific_batch ? h->rows.specific_batch : by_rule, std::max<size_t>(1, MAX_BATCH_SITES / per_item));
+}
+
+}  // namespace rbapi
+
+namespace {
+
+int check_oligos(const RibbitOligo *oligos, size_t n, const RibbitProductParams *params) {
+    if (!oligos && n > 0) return fail(RIBBIT_E_ARG, "null argument");
+    if (const int rc = check_primer_product_params(params)) return rc;
+    if (n > MAX_OLIGO_SITES / (size_t)params->max_sites) return fail(RIBBIT_E_ARG, "%zu oligos at max_sites %d", n, (int)params->max_sites);
+    for (size_t i = 0; i < n; ++i)
+        if (oligos[i].length < params->seed || oligos[i].length > RIBBIT_PRIMER_MAX_LENGTH)
+            return fail(RIBBIT_E_ARG, "oligo %zu: %d bases, not seed %d .. %d", i, (int)oligos[i].length, (int)params->seed, RIBBIT_PRIMER_MAX_LENGTH);
+    return RIBBIT_OK;
+}
+
+// ---- the GPU side: the oligos down and searched; -> the layout and the lists, ready for either result
+int scan_oligos(RibbitHandle *h, const StageSegment *segs, size_t n_segs, const uint8_t **d_at, size_t n_oligos, size_t n_pairs, const RibbitProductParams &prm, SiteSearch &sc) {
     RibbitHandle::RowBufs &buf = h->rows;
     int rc;
     if ((rc = bind_device(h))) return rc;
-    sc.at = rb::products_layout((int64_t)n_oligos, (int64_t)n_pairs);
-    if ((rc = buf.d_work.ensure(sc.at.bytes, true))) return rc;
+    if ((rc = buf.d_work.ensure(rb::products_layout((int64_t)n_oligos, (int64_t)n_pairs).bytes, true))) return rc;
     if ((rc = buf.h_product_header.ensure(sizeof(rb::ProductHeader) / sizeof(uint32_t)))) return rc;
     if ((rc = stage_down(h, segs, n_segs, d_at))) return rc;
-    HIP_TRY(rb::launch_product_uniques(reinterpret_cast<const RibbitOligo *>(d_at[0]), (int64_t)n_oligos, prm, buf.d_work.p, buf.d_work.cap, sc.at, h->stream));
-    HIP_TRY(hipMemcpyAsync(buf.h_product_header.p, buf.d_work.p + sc.at.header, sizeof(rb::ProductHeader), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    sc.uniques = reinterpret_cast<const rb::ProductHeader *>(buf.h_product_header.p)->uniques;
-    if (sc.uniques < 1 || sc.uniques > n_oligos) return fail(RIBBIT_E_INTERNAL, "%zu unique oligos of %zu", sc.uniques, n_oligos);
-    // the lists' room is fixed here, by the patterns, and does not grow with the sites the scan finds
-    if ((rc = buf.d_site_lists.ensure(2 * sc.uniques * (size_t)prm.max_sites, true))) return rc;
     // RIBBIT_PRODUCTS_NO_FILTER=1: the scan without the hashed bitmap in front of the bisection (tools/primer_products_timing.py measures both)
     static const bool no_filter = std::getenv("RIBBIT_PRODUCTS_NO_FILTER") && std::atoi(std::getenv("RIBBIT_PRODUCTS_NO_FILTER")) != 0;
-    HIP_TRY(rb::launch_product_scan(h->planes(), (int64_t)n_oligos, (int64_t)sc.uniques, prm, buf.d_work.p, buf.d_work.cap, sc.at, buf.d_site_lists.p, !no_filter, h->stream));
-    return RIBBIT_OK;
+    return search_sites(h, reinterpret_cast<const RibbitOligo *>(d_at[0]), n_oligos, n_pairs, prm, buf.d_work.p, buf.d_work.cap, !no_filter, sc);
 }
 
 int record_oligo_sites_impl(RibbitHandle *h, const RibbitOligo *oligos, size_t n, const RibbitProductParams *params, const RibbitOligoSites **sites,
@@ -109,7 +127,7 @@ int record_oligo_sites_impl(RibbitHandle *h, const RibbitOligo *oligos, size_t n
     }
     const StageSegment down{oligos, n * sizeof(RibbitOligo)};
     const uint8_t *d_oligos = nullptr;
-    Scanned sc;
+    SiteSearch sc;
     if ((rc = scan_oligos(h, &down, 1, &d_oligos, n, 0, *params, sc))) return rc;
     HIP_TRY(rb::launch_oligo_sites((int64_t)n, *params, buf.d_work.p, buf.d_work.cap, sc.at, h->stream));
     HIP_TRY(hipMemcpyAsync(buf.h_product_header.p, buf.d_work.p + sc.at.header, sizeof(rb::ProductHeader), hipMemcpyDeviceToHost, h->stream));
@@ -152,7 +170,7 @@ int record_primer_products_impl(RibbitHandle *h, const RibbitRowPrimerPair *pair
     if (!h) return fail(RIBBIT_E_ARG, "null handle");
     if (!rows) return fail(RIBBIT_E_ARG, "null argument");
     int rc;
-    if ((rc = check_pairs(pairs, n, params))) return rc;
+    if ((rc = check_product_pairs(pairs, n, params))) return rc;
     if (!h->loaded) return fail(RIBBIT_E_STATE, "no record loaded");
     RibbitHandle::RowBufs &buf = h->rows;
     if ((rc = buf.h_products.ensure(std::max<size_t>(n, 1) * sizeof(RibbitRowProducts), true))) return rc;
@@ -166,7 +184,7 @@ int record_primer_products_impl(RibbitHandle *h, const RibbitRowPrimerPair *pair
     for (size_t i = 0; i < n; ++i) {
         if (!has_pair(pairs[i])) continue;
         RibbitOligo a, b;
-        oligos_of(pairs[i], a, b);
+        pair_oligos(pairs[i], a, b);
         quads[4 * i] = (int32_t)oligos.size();
         quads[4 * i + 1] = (int32_t)oligos.size() + 1;
         quads[4 * i + 2] = pairs[i].left.start;
@@ -180,7 +198,7 @@ int record_primer_products_impl(RibbitHandle *h, const RibbitRowPrimerPair *pair
     }
     const StageSegment down[2] = {{oligos.data(), oligos.size() * sizeof(RibbitOligo)}, {quads.data(), quads.size() * sizeof(int32_t)}};
     const uint8_t *d_at[2] = {nullptr, nullptr};
-    Scanned sc;
+    SiteSearch sc;
     if ((rc = scan_oligos(h, down, 2, d_at, oligos.size(), n, *params, sc))) return rc;
     HIP_TRY(rb::launch_pair_products(reinterpret_cast<const int32_t *>(d_at[1]), (int64_t)n, *params, buf.d_work.p, buf.d_work.cap, sc.at, buf.d_site_lists.p, h->stream));
     HIP_TRY(hipMemcpyAsync(out, buf.d_work.p + sc.at.out, n * sizeof(RibbitRowProducts), hipMemcpyDeviceToHost, h->stream));
@@ -205,17 +223,6 @@ std::string letters_of(const RibbitOligo &o) {
     for (int32_t j = 0; j < o.length; ++j) out += "ACGT"[(bases >> (2 * j)) & 3];
     return out;
 }
-std::string reverse_complement(const std::string &o) {
-    std::string q;
-    for (size_t j = o.size(); j-- > 0;) q += o[j] == 'A' ? 'T' : o[j] == 'C' ? 'G' : o[j] == 'G' ? 'C' : 'A';
-    return q;
-}
-char letter_at(const unsigned char *seq, int64_t p) {      // the base there in upper case, or 0 for a byte of kind `other`
-    const int c = code_of(seq[p]);
-    return c < 0 ? 0 : "ACGT"[c];
-}
-
-using Sites = HostSites;
 
 // pattern at the window [x, x + k): its exact part [from, to) and at most d mismatches elsewhere, no byte of kind `other`
 bool window_holds(const unsigned char *seq, int64_t x, const std::string &pattern, size_t from, size_t to, int32_t d) {
@@ -231,8 +238,21 @@ bool window_holds(const unsigned char *seq, int64_t x, const std::string &patter
     return mismatches <= d;
 }
 
-Sites sites_of(const unsigned char *seq, int64_t length, const std::string &o, const RibbitProductParams &prm) {
-    Sites out;
+struct Site { int64_t x, k; bool of_a; };
+
+}  // namespace
+
+namespace rbapi {
+
+void host_pair_oligos(const RibbitRowPrimerPair &pair, std::string &a, std::string &b) {
+    RibbitOligo oa, ob;
+    pair_oligos(pair, oa, ob);
+    a = letters_of(oa);
+    b = letters_of(ob);
+}
+
+HostSites host_oligo_sites(const unsigned char *seq, int64_t length, const std::string &o, const RibbitProductParams &prm) {
+    HostSites out;
     const std::string q = reverse_complement(o);
     const size_t k = o.size(), s = (size_t)prm.seed;
     for (int64_t x = 0; x + (int64_t)k <= length; ++x) {
@@ -242,53 +262,23 @@ Sites sites_of(const unsigned char *seq, int64_t length, const std::string &o, c
     return out;
 }
 
-int check_sequence(const char *sequence, int64_t length) {
-    if (length < 0 || length > (int64_t)INT32_MAX) return fail(RIBBIT_E_ARG, "a record of %lld bases", (long long)length);
-    if (!sequence && length > 0) return fail(RIBBIT_E_ARG, "bad sequence");
-    return RIBBIT_OK;
+size_t HostOligoIndex::add(const std::string &oligo) {
+    const auto at = ids.emplace(oligo, distinct.size());
+    if (at.second) distinct.push_back(&at.first->first);
+    return at.first->second;
 }
 
-int host_record_oligo_sites_impl(const char *sequence, int64_t length, const RibbitOligo *oligos, size_t n, const RibbitProductParams *params, RibbitOligoSites **sites,
-                                 int32_t **positions, size_t *n_positions) {
-    if (!sites || !positions || !n_positions) return fail(RIBBIT_E_ARG, "null argument");
-    int rc;
-    if ((rc = check_oligos(oligos, n, params))) return rc;
-    if ((rc = check_sequence(sequence, length))) return rc;
-    const unsigned char *seq = reinterpret_cast<const unsigned char *>(sequence);
-    const RibbitProductParams prm = *params;
-    std::vector<Sites> found(n);
-    const unsigned threads = (unsigned)std::max<size_t>(1, std::min<size_t>(rb::host_thread_count(0), n));
-    rb::over_pieces(n, threads, [&](size_t lo, size_t hi, unsigned) {
-        for (size_t i = lo; i < hi; ++i) found[i] = sites_of(seq, length, letters_of(oligos[i]), prm);
+void HostOligoIndex::search(const unsigned char *seq, int64_t length, const RibbitProductParams &prm) {
+    found.assign(distinct.size(), HostSites{});
+    const unsigned threads = (unsigned)std::max<size_t>(1, std::min<size_t>(rb::host_thread_count(0), distinct.size()));
+    rb::over_pieces(distinct.size(), threads, [&](size_t lo, size_t hi, unsigned) {
+        for (size_t k = lo; k < hi; ++k) found[k] = host_oligo_sites(seq, length, *distinct[k], prm);
     });
-    Handed<RibbitOligoSites> out;
-    if ((rc = hand_out<RibbitOligoSites>(nullptr, n, false, out))) return rc;
-    std::vector<int32_t> flat;
-    for (size_t i = 0; i < n; ++i) {
-        RibbitOligoSites &s = out[i];
-        s = RibbitOligoSites{(int32_t)found[i].forward.size(), (int32_t)found[i].reverse.size(), -1, -1};
-        if (s.forward <= prm.max_sites) {
-            s.forward_at = (int32_t)flat.size();
-            flat.insert(flat.end(), found[i].forward.begin(), found[i].forward.end());
-        }
-        if (s.reverse <= prm.max_sites) {
-            s.reverse_at = (int32_t)flat.size();
-            flat.insert(flat.end(), found[i].reverse.begin(), found[i].reverse.end());
-        }
-    }
-    Handed<int32_t> pos;
-    if ((rc = hand_out<int32_t>(flat.data(), flat.size(), false, pos))) return rc;
-    *sites = out.release();
-    *positions = pos.release();
-    *n_positions = flat.size();
-    return RIBBIT_OK;
 }
-
-struct Site { int64_t x, k; bool of_a; };
 
 // the products among the sites a and b of a pair's two oligos of ka and kb bases, whose own product is (a forward at left_start, b
 // reverse at right_start)
-RibbitRowProducts products_among(const Sites &a, const Sites &b, int32_t ka, int32_t kb, int32_t left_start, int32_t right_start, const RibbitProductParams &prm) {
+RibbitRowProducts host_products_among(const HostSites &a, const HostSites &b, int32_t ka, int32_t kb, int32_t left_start, int32_t right_start, const RibbitProductParams &prm) {
     RibbitRowProducts r{};
     r.left_forward = (int32_t)a.forward.size();
     r.left_reverse = (int32_t)a.reverse.size();
@@ -316,18 +306,59 @@ RibbitRowProducts products_among(const Sites &a, const Sites &b, int32_t ka, int
     return r;
 }
 
+}  // namespace rbapi
+
+namespace {
+
+int host_record_oligo_sites_impl(const char *sequence, int64_t length, const RibbitOligo *oligos, size_t n, const RibbitProductParams *params, RibbitOligoSites **sites,
+                                 int32_t **positions, size_t *n_positions) {
+    if (!sites || !positions || !n_positions) return fail(RIBBIT_E_ARG, "null argument");
+    int rc;
+    if ((rc = check_oligos(oligos, n, params))) return rc;
+    if ((rc = check_sequence(sequence, length))) return rc;
+    const unsigned char *seq = reinterpret_cast<const unsigned char *>(sequence);
+    const RibbitProductParams prm = *params;
+    std::vector<HostSites> found(n);
+    const unsigned threads = (unsigned)std::max<size_t>(1, std::min<size_t>(rb::host_thread_count(0), n));
+    rb::over_pieces(n, threads, [&](size_t lo, size_t hi, unsigned) {
+        for (size_t i = lo; i < hi; ++i) found[i] = host_oligo_sites(seq, length, letters_of(oligos[i]), prm);
+    });
+    Handed<RibbitOligoSites> out;
+    if ((rc = hand_out<RibbitOligoSites>(nullptr, n, false, out))) return rc;
+    std::vector<int32_t> flat;
+    for (size_t i = 0; i < n; ++i) {
+        RibbitOligoSites &s = out[i];
+        s = RibbitOligoSites{(int32_t)found[i].forward.size(), (int32_t)found[i].reverse.size(), -1, -1};
+        if (s.forward <= prm.max_sites) {
+            s.forward_at = (int32_t)flat.size();
+            flat.insert(flat.end(), found[i].forward.begin(), found[i].forward.end());
+        }
+        if (s.reverse <= prm.max_sites) {
+            s.reverse_at = (int32_t)flat.size();
+            flat.insert(flat.end(), found[i].reverse.begin(), found[i].reverse.end());
+        }
+    }
+    Handed<int32_t> pos;
+    if ((rc = hand_out<int32_t>(flat.data(), flat.size(), false, pos))) return rc;
+    *sites = out.release();
+    *positions = pos.release();
+    *n_positions = flat.size();
+    return RIBBIT_OK;
+}
+
 RibbitRowProducts products_of(const unsigned char *seq, int64_t length, const RibbitRowPrimerPair &pair, const RibbitProductParams &prm) {
     if (!has_pair(pair)) return RibbitRowProducts{};
-    RibbitOligo oa, ob;
-    oligos_of(pair, oa, ob);
-    return products_among(sites_of(seq, length, letters_of(oa), prm), sites_of(seq, length, letters_of(ob), prm), oa.length, ob.length, pair.left.start, pair.right.start, prm);
+    std::string oa, ob;
+    host_pair_oligos(pair, oa, ob);
+    return host_products_among(host_oligo_sites(seq, length, oa, prm), host_oligo_sites(seq, length, ob, prm), pair.left.length, pair.right.length, pair.left.start,
+                               pair.right.start, prm);
 }
 
 int host_record_primer_products_impl(const char *sequence, int64_t length, const RibbitRowPrimerPair *pairs, size_t n, const RibbitProductParams *params,
                                      RibbitRowProducts **rows) {
     if (!rows) return fail(RIBBIT_E_ARG, "null argument");
     int rc;
-    if ((rc = check_pairs(pairs, n, params))) return rc;
+    if ((rc = check_product_pairs(pairs, n, params))) return rc;
     if ((rc = check_sequence(sequence, length))) return rc;
     const unsigned char *seq = reinterpret_cast<const unsigned char *>(sequence);
     const RibbitProductParams prm = *params;
@@ -342,59 +373,12 @@ int host_record_primer_products_impl(const char *sequence, int64_t length, const
 }
 
 // ---- the text
-enum : int { BAD_LENGTH = 1 };
-
 int bed_primer_products_text_impl(const char *bed, size_t bed_len, const RibbitRowPrimerPair *pairs, const RibbitRowProducts *products, size_t n, char **text, size_t *len) {
     if (!text || !len || (!bed && bed_len > 0) || ((!pairs || !products) && n > 0)) return fail(RIBBIT_E_ARG, "null argument");
-    const size_t parts = bed_text_parts(bed_len);
-    BedLines lines;
-    int rc;
-    if ((rc = lines.find(bed, bed_len, parts))) return rc;
-    if (lines.count() != n) return fail(RIBBIT_E_ARG, "the BED text has %zu lines, not the %zu of the rows", lines.count(), n);
-    return write_pieces(
-        parts, "the rows' primer products", text, len,
-        [&](size_t k, std::string &out) {
-            const size_t from = n * k / parts, to = n * (k + 1) / parts;
-            out.reserve(lines.start[to] - lines.start[from] + 256 * (to - from));
-            for (size_t i = from; i < to; ++i) {
-                const RibbitRowPrimerPair &r = pairs[i];
-                const RibbitRowProducts &p = products[i];
-                if (const RibbitPrimer *bad = bad_primer(r)) return PieceRefusal{BAD_LENGTH, i, (size_t)(uint32_t)bad->length};
-                put_field(out, lines[i]);
-                put_pair_columns(out, r);
-                put_product_columns(out, r, p);
-                out += '\n';
-            }
-            return PieceRefusal{};
-        },
-        [](const PieceRefusal &bad) { return fail(RIBBIT_E_ARG, "row %zu: a primer of %d bases, not 1 .. %d", bad.a, (int)(int32_t)(uint32_t)bad.b, RIBBIT_PRIMER_MAX_LENGTH); });
+    return bed_pair_rows_text(bed, bed_len, pairs, n, "the rows' primer products", 256, text, len, [&](std::string &out, size_t i) { put_product_columns(out, pairs[i], products[i]); });
 }
 
 }  // namespace
-
-// ---- what api_primer_specific.cpp takes from here (primers_host.h)
-namespace rbapi {
-
-int check_primer_product_params(const RibbitProductParams *p) { return check_product_params(p); }
-
-int check_product_pairs(const RibbitRowPrimerPair *pairs, size_t n, const RibbitProductParams *params) { return check_pairs(pairs, n, params); }
-
-void pair_oligos(const RibbitRowPrimerPair &pair, RibbitOligo &a, RibbitOligo &b) { oligos_of(pair, a, b); }
-
-void host_pair_oligos(const RibbitRowPrimerPair &pair, std::string &a, std::string &b) {
-    RibbitOligo oa, ob;
-    oligos_of(pair, oa, ob);
-    a = letters_of(oa);
-    b = letters_of(ob);
-}
-
-HostSites host_oligo_sites(const unsigned char *seq, int64_t length, const std::string &oligo, const RibbitProductParams &prm) { return sites_of(seq, length, oligo, prm); }
-
-RibbitRowProducts host_products_among(const HostSites &a, const HostSites &b, int32_t ka, int32_t kb, int32_t left_start, int32_t right_start, const RibbitProductParams &prm) {
-    return products_among(a, b, ka, kb, left_start, right_start, prm);
-}
-
-}  // namespace rbapi
 
 extern "C" {
 

@@ -78,8 +78,7 @@ int host_record_primers_impl(const char *sequence, int64_t length, const int32_t
                              const RibbitPrimerParams *params, RibbitRowPrimers **rows) {
     int rc;
     if ((rc = check_primer_args(intervals, n, targets, n_targets, params, rows))) return rc;
-    if (length < 0 || length > (int64_t)INT32_MAX) return fail(RIBBIT_E_ARG, "a record of %lld bases", (long long)length);
-    if (!sequence && length > 0) return fail(RIBBIT_E_ARG, "bad sequence");
+    if ((rc = check_sequence(sequence, length))) return rc;
     const unsigned char *seq = reinterpret_cast<const unsigned char *>(sequence);
     std::vector<uint8_t> covered((size_t)length, 0);
     const CoveredRuns runs(clipped_sorted_rows(length, intervals, n));

@@ -494,13 +494,15 @@ hipError_t launch_primer_pairs(const DevicePlanes &pl, const uint32_t *bits, con
                                const RibbitPrimerPairParams &pair, uint8_t *work, size_t work_bytes, const PrimerPairLayout &at, hipStream_t stream);
 
 // primer_products.hip: the sites of n_oligos >= 1 oligos on either strand of the loaded record (length > 0), from its bit planes, and
-// the products of n_pairs primer pairs among them (api_primer_products.cpp; include/ribbit_hip.h has the contract).  A call takes
-// the launches in this order, and the host reads `header` between them, because two sizes are counts the device finds:
-//   launch_product_uniques   the oligos sorted and made unique; header.uniques = U
+// the products of n_pairs primer pairs among them (api_primer_products.cpp; include/ribbit_hip.h has the contract).  The first two
+// launches are the site search, which every in-silico PCR caller takes through rbapi::search_sites (api_internal.h) and through
+// nothing else; the host reads `header` between them, because the size of the lists is a count the device finds:
+//   launch_product_uniques   the oligos sorted and made unique; header.uniques = U, copied up, the stream synchronised, 1 <= U <= n_oligos
 //   launch_product_scan      the 2 U patterns (an oligo's bases with the seed at the window's end, its reverse complement with the
 //                            seed at the window's start) sorted by seed key, one pass over the planes, every kept list sorted.
 //                            lists: 2 U max_sites ints, sized by the host from U before the pass and not by what the pass finds;
 //                            use_filter: look a position's key up in the hashed bitmap first (false: for measuring what it saves)
+// What a caller does with the lists comes behind them: its own kernels (primer_specific.hip, amplicons.hip), or here
 //   launch_pair_products     one RibbitRowProducts per pair into `out`, or
 //   launch_oligo_sites       one RibbitOligoSites per oligo into `out`; header.positions = P, then
 //   launch_site_gather       the kept lists one behind the other into flat (P ints)
@@ -535,16 +537,28 @@ hipError_t launch_pair_products(const int32_t *pairs, int64_t n_pairs, const Rib
                                 const int32_t *lists, hipStream_t stream);
 hipError_t launch_oligo_sites(int64_t n_oligos, const RibbitProductParams &prm, uint8_t *work, size_t work_bytes, const ProductLayout &at, hipStream_t stream);
 void launch_site_gather(int64_t n_oligos, const RibbitProductParams &prm, uint8_t *work, const ProductLayout &at, const int32_t *lists, int32_t *flat, hipStream_t stream);
+// The room of a site search inside another call's work buffer: where the search's own work buffer starts, and its layout (offsets
+// from there).  A layout function carves it for the most oligos a batch can have; the api file puts the layout of the batch's own
+// oligos, which search_sites hands back, in its place before it launches what reads the search's regions.
+struct SiteRoom {
+    size_t offset;
+    ProductLayout layout;
+};
+inline SiteRoom site_room(WorkCarver &w, int64_t n_oligos) {
+    SiteRoom room{0, products_layout(n_oligos, 0)};
+    room.offset = w.take(room.layout.bytes);
+    return room;
+}
 
 // primer_specific.hip: the best primer pair of every one of n_targets >= 1 targets of the loaded record (length > 0) that
 // amplifies nothing else in it (api_primer_specific.cpp; include/ribbit_hip.h has the contract).  bits, targets, prm, pair: as for
 // primer_pairs.hip; product: checked by the caller.  The api file serves the targets in batches and sizes the layout by the
-// largest.  A batch takes the launches in this order, and the host reads `header` and primer_products.hip's header between them:
+// largest.  A batch takes the launches in this order, and the host reads `header` between them:
 //   launch_primer_shortlists   the two shortlists of every target (16 RibbitPrimer, four counts), and their primers as oligos one
 //                              behind the other, the right ones as ordered; header.oligos = N
-//   launch_product_uniques, launch_product_scan   (primer_products.hip) on those N oligos, with work + product_work as their work
-//                              buffer and `product` as their layout; none of them when N == 0
+//   the site search            of those N oligos in `sites` (ProductLayout above); none when N == 0
 //   launch_specific_pairs      one RibbitRowPrimerPair, RibbitRowProducts and RibbitRowSpecific per target
+constexpr int SLOTS = 2 * RIBBIT_PRIMER_PAIR_SHORTLIST;      // the places of a target's two shortlists
 struct SpecificHeader { uint32_t oligos, spare[3]; };
 struct SpecificLayout : WorkLayout {
     size_t lists;         // the shortlists, 16 RibbitPrimer per target: the left side's 8 places, then the right side's (start -1: empty)
@@ -553,8 +567,7 @@ struct SpecificLayout : WorkLayout {
     size_t oligos;        // those primers as RibbitOligo, a target's one behind the other, 16 n_targets at most
     size_t header;        // SpecificHeader
     size_t pairs, products, specific;   // the result, n_targets records each
-    size_t product_work;  // the work buffer of primer_products.hip's launches for 16 n_targets oligos ...
-    ProductLayout product;              // ... and its layout (offsets from product_work)
+    SiteRoom sites;       // for 16 n_targets oligos
 };
 SpecificLayout specific_layout(int64_t n_targets);
 hipError_t launch_primer_shortlists(const DevicePlanes &pl, const uint32_t *bits, const int32_t *targets, int64_t n_targets, const RibbitPrimerParams &prm,
@@ -566,10 +579,10 @@ hipError_t launch_specific_pairs(int64_t n_targets, const RibbitPrimerPairParams
 // ... and the admissible pairs of n_targets >= 1 targets' uploaded shortlists judged on the loaded record (length > 0), which need
 // not be the record they were made on (api_primer_genome.cpp: ribbit_hip_record_shortlist_verdicts).  lists: 16 RibbitPrimer per
 // target on the device, as SpecificLayout::lists holds them, checked by the caller (the held places first, 1 .. 32 bases each).  A
-// batch takes the launches in this order, and the host reads `header` and primer_products.hip's header between them:
+// batch takes the launches in this order, and the host reads `header` between them:
 //   launch_listed_oligos       the held places of every target counted, and their primers as oligos one behind the other, the right
 //                              ones as ordered, without primer_shortlists_kernel; header.oligos = N
-//   launch_product_uniques, launch_product_scan   as above; none of them when N == 0
+//   the site search            as above; none when N == 0
 //   launch_shortlist_verdicts  one RibbitTargetVerdicts per target; home: the own product exists on this record
 struct VerdictLayout : WorkLayout {
     size_t n_oligos;      // the held places of every target | their inclusive sum, n_targets words each
@@ -577,8 +590,7 @@ struct VerdictLayout : WorkLayout {
     size_t oligos;        // the held primers as RibbitOligo, a target's one behind the other, 16 n_targets at most
     size_t header;        // SpecificHeader
     size_t verdicts;      // the result, n_targets records
-    size_t product_work;  // the work buffer of primer_products.hip's launches for 16 n_targets oligos ...
-    ProductLayout product;              // ... and its layout (offsets from product_work)
+    SiteRoom sites;       // for 16 n_targets oligos
 };
 VerdictLayout verdict_layout(int64_t n_targets);
 hipError_t launch_listed_oligos(const RibbitPrimer *lists, int64_t n_targets, uint8_t *work, size_t work_bytes, const VerdictLayout &at, hipStream_t stream);
@@ -588,17 +600,14 @@ hipError_t launch_shortlist_verdicts(const RibbitPrimer *lists, int64_t n_target
 
 // amplicons.hip: n_pairs >= 1 primer pairs typed on the loaded record (length > 0), which may be any record
 // (api_amplicons.cpp: ribbit_hip_record_pair_amplicons; include/ribbit_hip.h has the contract).  The api file serves the pairs in
-// batches and sizes the layout by the largest.  A batch takes the launches in this order, and the host reads
-// primer_products.hip's header between the first two:
-//   launch_product_uniques, launch_product_scan   (primer_products.hip) on the batch's oligos, two per pair that has any, with
-//                              work + product_work as their work buffer and `product` as their layout
+// batches and sizes the layout by the largest.  A batch takes the launches in this order:
+//   the site search            of the batch's oligos, two per pair that has any, in `sites` (ProductLayout above)
 //   launch_pair_amplicons      pair_amplicons_kernel, one lane per pair: the four counts, products and the first product
 //                              (product_walk.h); then amplicon_tracts_kernel, one wavefront per pair with a product: the repeat
 //                              tract inside it, from the bit planes
 struct AmpliconLayout : WorkLayout {
     size_t rows;          // the result, n_pairs RibbitRowAmplicon
-    size_t product_work;  // the work buffer of primer_products.hip's launches for 2 n_pairs oligos ...
-    ProductLayout product;              // ... and its layout (offsets from product_work)
+    SiteRoom sites;       // for 2 n_pairs oligos
 };
 AmpliconLayout amplicon_layout(int64_t n_pairs);
 // pairs: four ints per pair on the device, {a's oligo, b's oligo, -1, -1}; a's oligo -1: no pair.  pool, offsets: the motifs of

@@ -8,7 +8,8 @@
 //   oligos       One inclusive sum (rocPRIM) over those numbers says where a target's oligos start; shortlisted_oligos_kernel
 //                writes them one behind the other, the left ones as they stand, the right ones reverse-complemented (as
 //                ordered), so no empty place reaches the search.  The last target's sum is the batch's number of oligos.
-//   sites        primer_products.hip, unchanged: uniques, patterns, one pass over the planes, every kept list sorted.
+//   sites        primer_products.hip's site search (kernels.h, at ProductLayout): uniques, patterns, one pass over the planes, every
+//                kept list sorted.
 //   the walk     specific_pairs_kernel: one wavefront per target, lane 8 l + r for the pair (l, r).  The lane judges the pair's
 //                admissibility from the stored shortlists (judge_pair, as primer_pairs_kernel), counts its products over its
 //                four sorted lists (product_walk.h, as pair_products_kernel) and calls it over, specific or other.  The four
@@ -35,7 +36,7 @@ namespace rb {
 
 namespace {
 
-constexpr int SLOTS = 2 * SHORTLIST;      // the places of a target's two shortlists
+static_assert(SLOTS == 2 * SHORTLIST, "two shortlists a target");
 static_assert(sizeof(RibbitRowSpecific) == 32 && sizeof(RibbitRowProducts) == 32 && sizeof(RibbitOligo) == 12, "8, 8 and 3 ints");
 static_assert(sizeof(RibbitTargetVerdicts) == 176 && sizeof(RibbitPrimer) == 24, "four masks and 36 ints; 6 ints");
 
@@ -230,6 +231,22 @@ bool specific_params_fit(const RibbitPrimerParams &prm, const RibbitPrimerPairPa
            pair.shortlist <= SHORTLIST;
 }
 
+// the inclusive sum of the targets' counts behind them, then the counted primers of `lists` as oligos one behind the other and
+// their number in the header
+hipError_t oligos_of_lists(const RibbitPrimer *lists, uint32_t *n_oligos, int64_t n_targets, uint8_t *work, const WorkLayout &at, size_t oligos, size_t header,
+                           hipStream_t stream) {
+    uint32_t *upto = n_oligos + n_targets;
+    // (the layout may be a larger batch's: what the sum asks for these targets must fit its region)
+    size_t bytes = 0;
+    hipError_t e = sum_counts(nullptr, bytes, n_oligos, upto, n_targets, stream);
+    if (e != hipSuccess) return e;
+    if (bytes > at.scratch_bytes) return hipErrorInvalidValue;
+    if ((e = sum_counts(work + at.scratch, bytes, n_oligos, upto, n_targets, stream)) != hipSuccess) return e;
+    hipLaunchKernelGGL(shortlisted_oligos_kernel, dim3(grid_for(n_targets * SLOTS, ROW_THREADS, ROW_MAX_BLOCKS)), dim3(ROW_THREADS), 0, stream, lists, n_oligos, upto, n_targets,
+                       region<RibbitOligo>(work, oligos), region<SpecificHeader>(work, header));
+    return hipGetLastError();
+}
+
 }  // namespace
 
 SpecificLayout specific_layout(int64_t n_targets) {
@@ -237,7 +254,6 @@ SpecificLayout specific_layout(int64_t n_targets) {
     size_t a = 0;
     (void)sum_counts(nullptr, a, nullptr, nullptr, n_targets, 0);
     SpecificLayout at{};
-    at.product = products_layout(n_targets * SLOTS, 0);
     WorkCarver w;
     at.lists = w.take(n * SLOTS * sizeof(RibbitPrimer));
     at.side_counts = w.take(4 * n * sizeof(int32_t));
@@ -247,7 +263,7 @@ SpecificLayout specific_layout(int64_t n_targets) {
     at.pairs = w.take(n * sizeof(RibbitRowPrimerPair));
     at.products = w.take(n * sizeof(RibbitRowProducts));
     at.specific = w.take(n * sizeof(RibbitRowSpecific));
-    at.product_work = w.take(at.product.bytes);
+    at.sites = site_room(w, n_targets * SLOTS);
     w.close(at, a);
     return at;
 }
@@ -259,18 +275,10 @@ hipError_t launch_primer_shortlists(const DevicePlanes &pl, const uint32_t *bits
     const size_t wave_bytes = (size_t)pair_wave_words(cap) * sizeof(uint32_t);
     const int waves = pair_waves(cap);
     RibbitPrimer *lists = region<RibbitPrimer>(work, at.lists);
-    uint32_t *n_oligos = region<uint32_t>(work, at.n_oligos), *upto = n_oligos + n_targets;
+    uint32_t *n_oligos = region<uint32_t>(work, at.n_oligos);
     hipLaunchKernelGGL(primer_shortlists_kernel, dim3(grid_for(n_targets, waves, ROW_MAX_BLOCKS)), dim3(64 * waves), waves * wave_bytes, stream, targets, n_targets, pl, bits,
                        prm, pair, cap, lists, region<int32_t>(work, at.side_counts), n_oligos);
-    // (the layout may be a larger batch's: what the sum asks for these targets must fit its region)
-    size_t bytes = 0;
-    hipError_t e = sum_counts(nullptr, bytes, n_oligos, upto, n_targets, stream);
-    if (e != hipSuccess) return e;
-    if (bytes > at.scratch_bytes) return hipErrorInvalidValue;
-    if ((e = sum_counts(work + at.scratch, bytes, n_oligos, upto, n_targets, stream)) != hipSuccess) return e;
-    hipLaunchKernelGGL(shortlisted_oligos_kernel, dim3(grid_for(n_targets * SLOTS, ROW_THREADS, ROW_MAX_BLOCKS)), dim3(ROW_THREADS), 0, stream, lists, n_oligos, upto, n_targets,
-                       region<RibbitOligo>(work, at.oligos), region<SpecificHeader>(work, at.header));
-    return hipGetLastError();
+    return oligos_of_lists(lists, n_oligos, n_targets, work, at, at.oligos, at.header, stream);
 }
 
 hipError_t launch_specific_pairs(int64_t n_targets, const RibbitPrimerPairParams &pair, const RibbitProductParams &product, uint8_t *work, size_t work_bytes,
@@ -278,10 +286,10 @@ hipError_t launch_specific_pairs(int64_t n_targets, const RibbitPrimerPairParams
     if (work_bytes < at.bytes || n_targets < 1 || pair.shortlist < 1 || pair.shortlist > SHORTLIST || product.max_product < 1 || product.max_sites < 1)
         return hipErrorInvalidValue;
     const uint32_t *n_oligos = region<uint32_t>(work, at.n_oligos);
-    uint8_t *pw = work + at.product_work;
+    uint8_t *pw = work + at.sites.offset;
     hipLaunchKernelGGL(specific_pairs_kernel, dim3(grid_for(n_targets, PAIR_WAVES, ROW_MAX_BLOCKS)), dim3(64 * PAIR_WAVES), 0, stream, region<RibbitPrimer>(work, at.lists),
-                       region<int32_t>(work, at.side_counts), n_oligos, n_oligos + n_targets, n_targets, pair, region<uint32_t>(pw, at.product.unique_of),
-                       region<UniqueOligo>(pw, at.product.uniques), region<uint32_t>(pw, at.product.counts), site_lists, (int)product.max_product, (int)product.max_sites,
+                       region<int32_t>(work, at.side_counts), n_oligos, n_oligos + n_targets, n_targets, pair, region<uint32_t>(pw, at.sites.layout.unique_of),
+                       region<UniqueOligo>(pw, at.sites.layout.uniques), region<uint32_t>(pw, at.sites.layout.counts), site_lists, (int)product.max_product, (int)product.max_sites,
                        region<RibbitRowPrimerPair>(work, at.pairs), region<RibbitRowProducts>(work, at.products), region<RibbitRowSpecific>(work, at.specific));
     return hipGetLastError();
 }
@@ -291,42 +299,33 @@ VerdictLayout verdict_layout(int64_t n_targets) {
     size_t a = 0;
     (void)sum_counts(nullptr, a, nullptr, nullptr, n_targets, 0);
     VerdictLayout at{};
-    at.product = products_layout(n_targets * SLOTS, 0);
     WorkCarver w;
     at.n_oligos = w.take(2 * n * sizeof(uint32_t));
     at.n_left = w.take(n * sizeof(uint32_t));
     at.oligos = w.take(n * SLOTS * sizeof(RibbitOligo));
     at.header = w.take(sizeof(SpecificHeader));
     at.verdicts = w.take(n * sizeof(RibbitTargetVerdicts));
-    at.product_work = w.take(at.product.bytes);
+    at.sites = site_room(w, n_targets * SLOTS);
     w.close(at, a);
     return at;
 }
 
 hipError_t launch_listed_oligos(const RibbitPrimer *lists, int64_t n_targets, uint8_t *work, size_t work_bytes, const VerdictLayout &at, hipStream_t stream) {
     if (work_bytes < at.bytes || n_targets < 1) return hipErrorInvalidValue;
-    uint32_t *n_oligos = region<uint32_t>(work, at.n_oligos), *upto = n_oligos + n_targets;
+    uint32_t *n_oligos = region<uint32_t>(work, at.n_oligos);
     hipLaunchKernelGGL(held_places_kernel, dim3(grid_for(n_targets, ROW_THREADS, ROW_MAX_BLOCKS)), dim3(ROW_THREADS), 0, stream, lists, n_targets,
                        region<uint32_t>(work, at.n_left), n_oligos);
-    // (the layout may be a larger batch's: what the sum asks for these targets must fit its region)
-    size_t bytes = 0;
-    hipError_t e = sum_counts(nullptr, bytes, n_oligos, upto, n_targets, stream);
-    if (e != hipSuccess) return e;
-    if (bytes > at.scratch_bytes) return hipErrorInvalidValue;
-    if ((e = sum_counts(work + at.scratch, bytes, n_oligos, upto, n_targets, stream)) != hipSuccess) return e;
-    hipLaunchKernelGGL(shortlisted_oligos_kernel, dim3(grid_for(n_targets * SLOTS, ROW_THREADS, ROW_MAX_BLOCKS)), dim3(ROW_THREADS), 0, stream, lists, n_oligos, upto, n_targets,
-                       region<RibbitOligo>(work, at.oligos), region<SpecificHeader>(work, at.header));
-    return hipGetLastError();
+    return oligos_of_lists(lists, n_oligos, n_targets, work, at, at.oligos, at.header, stream);
 }
 
 hipError_t launch_shortlist_verdicts(const RibbitPrimer *lists, int64_t n_targets, bool home, const RibbitPrimerPairParams &pair, const RibbitProductParams &product,
                                      uint8_t *work, size_t work_bytes, const VerdictLayout &at, const int32_t *site_lists, hipStream_t stream) {
     if (work_bytes < at.bytes || n_targets < 1 || product.max_product < 1 || product.max_sites < 1) return hipErrorInvalidValue;
     const uint32_t *n_oligos = region<uint32_t>(work, at.n_oligos);
-    uint8_t *pw = work + at.product_work;
+    uint8_t *pw = work + at.sites.offset;
     hipLaunchKernelGGL(shortlist_verdicts_kernel, dim3(grid_for(n_targets, PAIR_WAVES, ROW_MAX_BLOCKS)), dim3(64 * PAIR_WAVES), 0, stream, lists,
-                       region<uint32_t>(work, at.n_left), n_oligos, n_oligos + n_targets, n_targets, pair, home ? 1 : 0, region<uint32_t>(pw, at.product.unique_of),
-                       region<UniqueOligo>(pw, at.product.uniques), region<uint32_t>(pw, at.product.counts), site_lists, (int)product.max_product, (int)product.max_sites,
+                       region<uint32_t>(work, at.n_left), n_oligos, n_oligos + n_targets, n_targets, pair, home ? 1 : 0, region<uint32_t>(pw, at.sites.layout.unique_of),
+                       region<UniqueOligo>(pw, at.sites.layout.uniques), region<uint32_t>(pw, at.sites.layout.counts), site_lists, (int)product.max_product, (int)product.max_sites,
                        region<RibbitTargetVerdicts>(work, at.verdicts));
     return hipGetLastError();
 }

@@ -1,10 +1,12 @@
-// primers_host.h -- what the host sides of the primer outputs share (api_primers.cpp, api_primer_pairs.cpp, api_primer_products.cpp, api_primer_specific.cpp,
-// api_primer_genome.cpp): the checks of
-// RibbitPrimerParams and of a call's arguments with their wording, a target's two windows, one candidate judged from the bytes of
-// the sequence letter by letter (the five rules and the Tm table as include/ribbit_hip.h states them), and the columns of a primer
-// and of a pair as text.  No GPU, and nothing of the kernels' packed forms.
+// primers_host.h -- what the host sides of the primer outputs share (api_primers.cpp, api_primer_pairs.cpp, api_primer_products.cpp,
+// api_primer_specific.cpp, api_primer_genome.cpp, api_amplicons.cpp): the checks of RibbitPrimerParams, of a call's arguments and of a
+// twin's sequence with their wording, a target's two windows, one candidate judged from the bytes of the sequence letter by letter
+// (the five rules and the Tm table as include/ribbit_hip.h states them), the columns of a primer and of a pair as text and the
+// writer of the texts that are made of them, and the host code of one twin that another twin calls.  No GPU, and nothing of the
+// kernels' packed forms.
 // Not part of the ABI; nothing outside ribbit_amd/csrc includes it.
 #pragma once
+#include <map>
 #include <string>
 
 #include "bed_text.h"
@@ -40,6 +42,18 @@ inline int check_primer_args(const int32_t *intervals, size_t n, const int32_t *
     return check_primer_params(params);
 }
 
+// a host twin's record
+inline int check_sequence(const char *sequence, int64_t length) {
+    if (length < 0 || length > (int64_t)INT32_MAX) return fail(RIBBIT_E_ARG, "a record of %lld bases", (long long)length);
+    if (!sequence && length > 0) return fail(RIBBIT_E_ARG, "bad sequence");
+    return RIBBIT_OK;
+}
+
+// the sum of two counts of different records, which stays at the largest int
+inline int32_t saturating_sum(int32_t a, int32_t b) { return (int32_t)std::min<int64_t>((int64_t)a + b, INT32_MAX); }
+
+inline bool has_pair(const RibbitRowPrimerPair &r) { return r.left.start >= 0; }
+
 // a target's two windows: the left candidates lie in [lo, s), the right ones in [e, hi)
 struct Flanks { int64_t lo, s, e, hi; };
 inline Flanks flanks_of(const int32_t *targets, size_t i, int32_t flank, int64_t length) {
@@ -56,6 +70,16 @@ inline int code_of(unsigned char b) {      // A 0, C 1, G 2, T 3 in either case,
         case 't': return 3;
         default: return -1;
     }
+}
+
+inline char letter_at(const unsigned char *seq, int64_t p) {      // the base there in upper case, or 0 for a byte of kind `other`
+    const int c = code_of(seq[p]);
+    return c < 0 ? 0 : "ACGT"[c];
+}
+inline std::string reverse_complement(const std::string &o) {      // of letters over ACGT
+    std::string q;
+    for (size_t j = o.size(); j-- > 0;) q += o[j] == 'A' ? 'T' : o[j] == 'C' ? 'G' : o[j] == 'G' ? 'C' : 'A';
+    return q;
 }
 
 // SantaLucia 1998 as the contract tabulates it: dH in 100 cal/mol, dS in 0.1 cal/(K mol), by the step's two letters
@@ -171,34 +195,70 @@ inline void put_product_columns(std::string &out, const RibbitRowPrimerPair &r, 
     }
 }
 
-// ---- the host code behind the twins of the primer pairs and of the primer products that the twin of the specific pairs calls
-// (api_primer_specific.cpp); each is defined in the file named
+// The text of n rows' primer pairs (ribbit_bed_primer_pairs_text, ribbit_bed_primer_products_text, ribbit_bed_primer_specific_text):
+// every line of the BED text, the 21 columns of its pair, and what columns(out, i) puts behind them.  reserve: what a row's columns
+// take at most; what: the text's name in the message of a piece that runs out of memory.  The callers have checked for null.
+template <typename Columns>
+int bed_pair_rows_text(const char *bed, size_t bed_len, const RibbitRowPrimerPair *pairs, size_t n, const char *what, size_t reserve, char **text, size_t *len,
+                       Columns columns) {
+    const size_t parts = bed_text_parts(bed_len);
+    BedLines lines;
+    if (const int rc = lines.find(bed, bed_len, parts)) return rc;
+    if (lines.count() != n) return fail(RIBBIT_E_ARG, "the BED text has %zu lines, not the %zu of the rows", lines.count(), n);
+    return write_pieces(
+        parts, what, text, len,
+        [&](size_t k, std::string &out) {
+            const size_t from = n * k / parts, to = n * (k + 1) / parts;
+            out.reserve(lines.start[to] - lines.start[from] + reserve * (to - from));
+            for (size_t i = from; i < to; ++i) {
+                if (const RibbitPrimer *bad = bad_primer(pairs[i])) return PieceRefusal{1, i, (size_t)(uint32_t)bad->length};      // (the only refusal)
+                put_field(out, lines[i]);
+                put_pair_columns(out, pairs[i]);
+                columns(out, i);
+                out += '\n';
+            }
+            return PieceRefusal{};
+        },
+        [](const PieceRefusal &bad) { return fail(RIBBIT_E_ARG, "row %zu: a primer of %d bases, not 1 .. %d", bad.a, (int)(int32_t)(uint32_t)bad.b, RIBBIT_PRIMER_MAX_LENGTH); });
+}
+
+// ---- the host code of one twin that another twin calls; each is defined in the file named
 // api_primer_pairs.cpp: the check of RibbitPrimerPairParams; the rows' coverage, a byte per position; every admissible pair of a
-// target's two shortlists as the record the choice would fill for it, in the order of the choice, and the record of a target without a pair
+// target's two shortlists as the record the choice would fill for it, in the order of the choice, and the record of a target without a
+// pair; a target's two shortlists as they leave the record; the held places of one side of stored shortlists (those before the first
+// empty one); a stored primer's oligo as letters, 5' to 3' (the right one as ordered); the admissible pairs of stored shortlists from
+// the lists alone, as host_ordered_pairs gives them from the sequence
 int check_primer_pair_params(const RibbitPrimerPairParams *p);
 std::vector<uint8_t> host_covered(int64_t length, const int32_t *intervals, size_t n);
 void host_ordered_pairs(const unsigned char *seq, const std::vector<uint8_t> &covered, const Flanks &f, const RibbitPrimerParams &prm, const RibbitPrimerPairParams &pair,
                         std::vector<RibbitRowPrimerPair> &ordered, RibbitRowPrimerPair &none);
-// ... and what api_primer_genome.cpp takes: a target's two shortlists as they leave the record; the held places of one side of stored
-// shortlists (those before the first empty one); a stored primer's oligo as letters, 5' to 3' (the right one as ordered); the
-// admissible pairs of stored shortlists from the lists alone, as host_ordered_pairs gives them from the sequence
 void host_target_shortlists(const unsigned char *seq, const std::vector<uint8_t> &covered, const Flanks &f, const RibbitPrimerParams &prm, const RibbitPrimerPairParams &pair,
                             RibbitTargetShortlists &out);
 int host_held_places(const RibbitPrimer *side);
 std::string host_listed_oligo(const RibbitPrimer &p, bool right);
 void host_listed_pairs(const RibbitTargetShortlists &lists, const RibbitPrimerPairParams &pair, std::vector<RibbitRowPrimerPair> &ordered, RibbitRowPrimerPair &none);
-// api_primer_specific.cpp: the targets of one batch of the specific primer pairs on this handle, which the shortlists' verdicts share
-size_t specific_batch_targets(const RibbitHandle *h, const RibbitProductParams &product);
-// api_primer_products.cpp: the check of RibbitProductParams; a pair's two oligos as letters, 5' to 3'; the sites of an oligo on either
-// strand, ascending; the products of a pair among the sites of its two oligos
+// api_primer_products.cpp: the check of RibbitProductParams, and of a call's pairs and parameters, with their wording; a pair's two
+// oligos as the device takes them, and as letters, 5' to 3'; the sites of an oligo on either strand, ascending; the products of a
+// pair among the sites of its two oligos
 struct HostSites { std::vector<int32_t> forward, reverse; };
 int check_primer_product_params(const RibbitProductParams *p);
+int check_product_pairs(const RibbitRowPrimerPair *pairs, size_t n, const RibbitProductParams *params);
+void pair_oligos(const RibbitRowPrimerPair &pair, RibbitOligo &a, RibbitOligo &b);
 void host_pair_oligos(const RibbitRowPrimerPair &pair, std::string &a, std::string &b);
 HostSites host_oligo_sites(const unsigned char *seq, int64_t length, const std::string &oligo, const RibbitProductParams &prm);
 RibbitRowProducts host_products_among(const HostSites &a, const HostSites &b, int32_t ka, int32_t kb, int32_t left_start, int32_t right_start, const RibbitProductParams &prm);
-// ... and what api_amplicons.cpp takes besides: the check of a call's pairs and parameters with its wording; a pair's two oligos as
-// the device takes them
-int check_product_pairs(const RibbitRowPrimerPair *pairs, size_t n, const RibbitProductParams *params);
-void pair_oligos(const RibbitRowPrimerPair &pair, RibbitOligo &a, RibbitOligo &b);
+// ... and the oligos of a twin whose pairs share them, every distinct one searched once: add() gives an oligo's id, search() finds
+// the sites of all that were added on the host thread team, sites() are those of an id
+class HostOligoIndex {
+public:
+    size_t add(const std::string &oligo);
+    void search(const unsigned char *seq, int64_t length, const RibbitProductParams &prm);
+    const HostSites &sites(size_t id) const { return found[id]; }
+
+private:
+    std::map<std::string, size_t> ids;
+    std::vector<const std::string *> distinct;      // (a map's keys stay where they are)
+    std::vector<HostSites> found;
+};
 
 }  // namespace rbapi

@@ -2,13 +2,17 @@
 pair of buffers, and every row output carves its intermediate arrays, its result on the device and its scans' and sorts'
 temporary storage from one device work buffer (RowBufs in ribbit_amd/csrc/api_internal.h, the layouts in kernels.h), so that
 buffer grows inside another feature than the one that sized it last; the results come up into pinned buffers of their own, "valid
-until the handle's next same call, load or close" (include/ribbit_hip.h).  Every answer here is compared with the host twin's."""
+until the handle's next same call, load or close" (include/ribbit_hip.h).  The four callers of the in-silico PCR's site search
+share the site lists and the batch size besides.  Every answer here is compared with the host twin's."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import interruptions_contract as ic
+import primer_genome_contract as pg
+import primer_specific_contract as ps
+import primers_contract as pc
 import ribbit_amd
 from classes_contract import random_motif
 
@@ -152,3 +156,62 @@ def test_a_result_outlives_the_other_row_outputs():
         assert C.string_at(best.value, 4 * n_best.value) == ribbit_amd.host_record_best(len(seq), fewer)[0].tobytes()
     finally:
         L.ribbit_hip_close(h)
+
+
+# ---- the four callers of the site search (api_primer_products.cpp: search_sites) on one handle: they share the work buffer, the
+# site lists, the header's pinned words, the debug batch size and the code that sizes them
+def _bytes(result):
+    return tuple(np.ascontiguousarray(a).tobytes() for a in (result if isinstance(result, tuple) else (result,)))
+
+
+def _search_call(sc, seq, name, k):
+    """one call on the handle, which has `seq` loaded, at the batch size it names; -> its answer, which is its host twin's"""
+    what, batch = name
+    sc.debug_set_specific_batch(batch)
+    if what == "specific":
+        got, want = sc.record_specific_primer_pairs([], k["targets"]), ribbit_amd.host_record_specific_primer_pairs(seq, [], k["targets"])
+        k.setdefault("pairs", got[0].copy())
+    elif what == "products":
+        got, want = sc.record_primer_products(k["pairs"]), ribbit_amd.host_record_primer_products(seq, k["pairs"])
+    elif what == "shortlists":
+        got, want = sc.record_primer_shortlists([], k["targets"]), ribbit_amd.host_record_primer_shortlists(seq, [], k["targets"])
+        k.setdefault("lists", got.copy())
+    elif what == "verdicts":
+        got, want = sc.record_shortlist_verdicts(k["lists"], k["home"]), ribbit_amd.host_record_shortlist_verdicts(seq, k["lists"], k["home"])
+    elif what == "amplicons":
+        motifs = ["CA"] * len(k["pairs"])
+        got, want = sc.record_pair_amplicons(k["pairs"], motifs, k["home"]), ribbit_amd.host_record_pair_amplicons(seq, k["pairs"], motifs, k["home"])
+    else:
+        got, want = sc.record_oligo_sites(k["oligos"]), ribbit_amd.host_record_oligo_sites(seq, k["oligos"])
+    assert _bytes(got) == _bytes(want), (name, k["home"])
+    return got
+
+
+def test_the_site_search_callers_interleaved_on_one_handle():
+    """the specific pairs at batch 1 size the site lists by one target; the products of the chosen pairs, with more oligos than a
+    target has, grow them inside another caller; the verdicts with all targets in one batch grow them again; the amplicons at batch
+    5 and two oligos' sites follow, and the first call again answers as before.  Then a foreign record, the home record again and
+    the round in reverse.  Target 0 is primer_specific_contract's pinned one, so no answer is an empty one"""
+    home = ps.constructed()["best pair copied"][0]
+    foreign = pg.pinned_genomes()["best pair copied to the other record"][1]
+    targets = [ps.TARGET] + pc.random_targets(len(home), np.random.RandomState(3), 12, longest=60).tolist()
+    k = dict(targets=targets, home=1, oligos=[home[1304:1326].decode(), home[1613:1635].decode()])
+    steps = [("specific", 1), ("products", 1), ("shortlists", 0), ("verdicts", 0), ("amplicons", 5), ("sites", 5), ("specific", 5)]
+    with ribbit_amd.Scanner(2, 30) as sc:
+        sc.load_record(home)
+        answers = [_search_call(sc, home, name, k) for name in steps]
+        first = [_bytes(a) for a in answers]
+        assert first[6] == first[0]
+        sc.load_record(foreign)
+        k["home"] = 0
+        abroad = [_search_call(sc, foreign, name, k) for name in (("verdicts", 0), ("amplicons", 5), ("products", 5))]
+        sc.load_record(home)
+        k["home"] = 1
+        assert [_bytes(_search_call(sc, home, name, k)) for name in reversed(steps)] == first[::-1]
+    (pairs, products, specific), verdicts = answers[0], abroad[0]
+    assert len(np.unique(k["pairs"][["left_start", "right_start"]][k["pairs"]["left_start"] >= 0])) > 8      # more than 16 oligos in the products' call
+    assert ps.as_tuples(specific[:1])[0][:6] == ps.PINNED["best pair copied"][0] == (2, 44, 26, 0, 18, 2)
+    assert (int(pairs["left_start"][0]), int(pairs["right_start"][0])) == (1304, 1613)
+    assert bin(int(verdicts["other"][0])).count("1") == pg.PINNED["best pair copied to the other record"][0][4] == 14
+    for p in (products[0], answers[1][0]):      # the chosen pair's products, from the specific pairs and from the products' own call
+        assert p["own"] == 1 and p["products"] - p["own"] == 0
