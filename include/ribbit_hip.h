@@ -1241,6 +1241,93 @@ int ribbit_bed_marker_text(const char *bed_text, size_t bed_len, const RibbitRow
                            const char *names, const int32_t *name_offsets, size_t n_records, size_t n, char **text, size_t *len);
 
 /*
+ * ---- multiplex PCR panels: the markers pooled so that no two members of a pool disturb each other --------------------------
+ * What Multiplex Manager, MPprimer and PrimerPooler do behind e-mapping: the markers worth ordering go into pools (tubes, lanes);
+ * within a pool no primer may bind a primer of another marker, the products must be tellable apart by size, and two markers
+ * that lie close together on one record must not make a product between them.  Everything is integer arithmetic on letters
+ * and positions.  dG, gapped dimers, dye colours and an optimal colouring are not part of it: first fit along the degree order
+ * is a heuristic, and the rule below is what is pinned.
+ *   Inputs:     n pairs as RibbitRowPrimerPair, 0 <= n <= RIBBIT_PANEL_MAX_PAIRS, of which only left and right (start, length,
+ *               bases) and product are read; left.start < 0: no pair.  Optionally 3 n int32 `extra`, (group, size_lo, size_hi) per
+ *               pair; NULL stands for (-1, product, product) everywhere.  group >= 0 names the record the pair lies on, -1: unknown;
+ *               size_lo <= size_hi are the product sizes the marker is expected to show.  A RibbitPanelParams.
+ *   Oligos:     those of the pair contract: L is the left primer's forward-strand bases, R the reverse complement of the right
+ *               primer's forward-strand bases; any(x, y) and end(x, y) are exactly the pair contract's.
+ *   Conflict:   of two different pairs i and j that both have a pair, the OR of three rules.
+ *               dimer: for some x in {L_i, R_i} and some y in {L_j, R_j}, any(x, y) > max_cross_any or end(x, y) > max_cross_end.
+ *               size:  size_gap > 0, size_lo_i - size_hi_j < size_gap and size_lo_j - size_hi_i < size_gap (the ranges lie less
+ *                      than size_gap apart).
+ *               near:  max_cross_product > 0, group_i == group_j >= 0, and max(end_i, end_j) - min(start_i, start_j) <=
+ *                      max_cross_product, the span of a pair being [left.start, right.start + right.length): the product that L
+ *                      of one pair and R of the other can make, which the in-silico PCR contract would count.
+ *               The relation is symmetric and has no diagonal; a row without a pair conflicts with nobody.
+ *   Degree:     conflicts_i is the number of j in conflict with i; dimer_i, size_i and near_i count each rule on its own (one j
+ *               may count in several).  The rows that have a pair are ordered by (conflicts descending, index ascending): the
+ *               Welsh-Powell order.
+ *   Pools:      first fit along that order: a pair goes into the lowest-numbered pool that has fewer than pool_size members and
+ *               no member in conflict with it; if there is none it opens the next pool.  A row without a pair has pool -1 and
+ *               counts of 0.  The low-numbered pools fill first, so the first k pools are the natural smaller panel.
+ *   Defaults:   the cross limits are 6 and 4, not the pair's own 4 and 3: among random oligos of 18 .. 25 bases at the pair's
+ *               own limits three of four pair-to-pair combinations conflict and a pool of eight cannot exist.
+ *   Values:     from tests/panel_contract.py, a plain statement of the above.  Q0 .. Q3 are four pairs of eight oligos of which no
+ *               two exceed (6, 4) (TTCAGGACCTAACCTGAG / TAGCCAAGTTCAACGGCAG, TGCAACCTAGGGAGAATGTG / ACATACGCTCTTACTGCGGTC,
+ *               CGGAGCATAAATCCCACC / GAACTAAGTTTGTCGAACC, GGTAAACGAACCGTTGCG / AATTTGAAGCAGTGGCCGGG), Qk(s, p) with left.start
+ *               s and product p; the defaults unless stated; as the pairs' pools, then (conflicts, dimer, size, near) of each:
+ *                 Q0(0, 100), Q1(1000, 150)                                  0 0      all (0,0,0,0)
+ *                 GATTACAGATTACAGGC / Q0's left, Q1's left / TTTGCCTGTAATC     0 1      both (1,1,0,0): the duplex is (10, 10)
+ *                   the same with max_cross_any = max_cross_end = 32         0 0      the dimer rule refuses nothing
+ *                 Q0(0, 100), Q1(0, 129)                                     0 1      both (1,0,1,0)    products 130: 0 0
+ *                   the same with size_gap 0                                 0 0
+ *                 Q0(0, 100), Q1(3850, 150), both in group 5                 0 1      both (1,0,0,1): the hull is 4000
+ *                   Q1(3851, 150): hull 4001; or groups 5 and 6; or -1, -1   0 0
+ *                 Q0, Q1, Q2 with pool_size 1                                0 1 2
+ *                 Q0(0, 100), Q1(0, 200), Q2(0, 300), Q3(0, 200) with sizes 90 .. 310     1 1 1 0
+ *                                                                            (1,0,1,0) three times, (3,0,3,0): the degree order
+ *                                                                            takes Q3 first; index order would give 0 0 0 1
+ *                 Q0, a row without a pair, Q1                               0 -1 0
+ */
+#define RIBBIT_PANEL_MAX_PAIRS 65536
+#define RIBBIT_PANEL_MAX_DEBUG_PAIRS 8192
+typedef struct {
+    int32_t max_cross_any, max_cross_end;     /* 6, 4;  0 .. 32 each: at 32 the dimer rule never refuses */
+    int32_t size_gap;                         /* 30;  0 .. 100000, 0: no size rule */
+    int32_t max_cross_product;                /* 4000;  0 .. 2^30, 0: no near rule */
+    int32_t pool_size;                        /* 8;  1 .. 65536 */
+} RibbitPanelParams;
+void ribbit_panel_params_default(RibbitPanelParams *params);
+typedef struct {
+    int32_t pool;                             /* -1: no pair */
+    int32_t conflicts, dimer, size, near;
+    int32_t reserved[3];                      /* 0 */
+} RibbitPanelRow;                             /* 8 ints, 32 bytes */
+/* The n pairs pooled on the GPU (panel.hip): the conflict matrix, one lane per row against tiles of columns in LDS; the degrees;
+ * one radix sort for the order; the first fit by a single workgroup, so that the matrix (512 MiB at the cap) never leaves the
+ * device.  The call needs a handle and no loaded record: it reads none, and may come before any load.  *rows is one record per
+ * pair in the order given, of handle-owned page-locked memory, valid until the handle's next panel call or close; *n_pools the
+ * pools in use; on an error *rows is NULL and *n_pools 0.  n = 0 is no error.  A field of params outside its range:
+ * RIBBIT_E_ARG, and the text names the field; n above the cap, a primer of fewer than 1 or more than 32 bases, size_lo > size_hi,
+ * group < -1: RIBBIT_E_ARG with the index in the text. */
+int ribbit_hip_panel_pools(RibbitHandle *h, const RibbitRowPrimerPair *pairs, const int32_t *extra, size_t n,
+                           const RibbitPanelParams *params, const RibbitPanelRow **rows, int32_t *n_pools);
+/* Host-only twin (no GPU), letter by letter in loops over pairs and placements: *rows malloc'ed, release with ribbit_panel_free().
+ * It is the reference for panels of thousands of pairs, not a way to pool at the cap: with m rows that have a pair it holds m^2
+ * bytes (4 GiB at 65536; RIBBIT_E_NOMEM when that is not to be had) and makes 2 m^2 duplexes in letters, seconds at m = 4096. */
+int ribbit_host_panel_pools(const RibbitRowPrimerPair *pairs, const int32_t *extra, size_t n, const RibbitPanelParams *params,
+                            RibbitPanelRow **rows, int32_t *n_pools);
+void ribbit_panel_free(void *from_the_host_twin);
+/* The conflict matrix itself, as the kernel leaves it (for tests of the kernel apart from the pooling): n rows of (n + 63) / 64
+ * words of 64 bits, row-major; bit j % 64 of word j / 64 of row i holds the conflict of i and j.  n above
+ * RIBBIT_PANEL_MAX_DEBUG_PAIRS: RIBBIT_E_ARG; everything else as ribbit_hip_panel_pools. */
+int ribbit_hip_debug_panel_conflicts(RibbitHandle *h, const RibbitRowPrimerPair *pairs, const int32_t *extra, size_t n,
+                                     const RibbitPanelParams *params, uint64_t *words);
+/* The panel as text (host only): marker_text holds the n lines that ribbit_bed_marker_text wrote for the same n pairs (a last line
+ * without its newline counts).  Only the members (pool >= 0) are written: each its marker line byte for byte, then five columns,
+ * each behind a tab: pool, conflicts, dimer, size, near.  The lines are sorted by (pool, designed product size, input order), the
+ * designed product being the ninth of a marker line's last 20 columns, so a pool reads like a lane.  A text that does not have n
+ * lines, or a member's line that has no number there: RIBBIT_E_ARG.  *text malloc'ed, release with ribbit_text_free(). */
+int ribbit_bed_panel_text(const char *marker_text, size_t len, const RibbitPanelRow *rows, size_t n, char **text, size_t *out_len);
+
+/*
  * ---- streaming FASTA ingest ---------------------------------------------------------------------------------------
  * Replaces the reader loop of ribbit.cpp:269-280 (getline + `sequence += line` into one pageable std::string per
  * record).  The file is read in 16-MB blocks; line bodies are copied once, straight into a page-locked buffer

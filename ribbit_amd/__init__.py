@@ -37,7 +37,8 @@ __all__ = ["RibbitHipError", "ScanParams", "Scanner", "library_path", "load_libr
            "PRIMER_SPECIFIC_DT", "host_record_specific_primer_pairs", "bed_primer_specific_text",
            "PRIMER_SHORTLISTS_DT", "PRIMER_VERDICTS_DT", "host_record_primer_shortlists", "host_record_shortlist_verdicts", "primer_verdicts_merge",
            "primer_shortlists_choose",
-           "PAIR_AMPLICONS_DT", "host_record_pair_amplicons", "pair_amplicons_merge", "bed_marker_text"]
+           "PAIR_AMPLICONS_DT", "host_record_pair_amplicons", "pair_amplicons_merge", "bed_marker_text",
+           "PANEL_DT", "PanelParams", "panel_params", "host_panel_pools", "bed_panel_text"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -79,6 +80,7 @@ PRIMER_VERDICTS_DT = np.dtype([(n, "<u8") for n in ("admissible", "over", "other
 PAIR_AMPLICONS_DT = np.dtype([(n, "<i4") for n in ("left_forward", "left_reverse", "right_forward", "right_reverse", "products", "record", "start", "end",
                                                     "forward_of", "reverse_of", "inner_start", "inner_end", "tract_start", "tract_end", "tract_strand",
                                                     "reserved")])      # RibbitRowAmplicon
+PANEL_DT = np.dtype([(n, "<i4") for n in ("pool", "conflicts", "dimer", "size", "near", "reserved0", "reserved1", "reserved2")])      # RibbitPanelRow
 OLIGO_SITES_DT = np.dtype([(n, "<i4") for n in ("forward", "reverse", "forward_at", "reverse_at")])      # RibbitOligoSites
 _OLIGO_DT = np.dtype([(n, "<i4") for n in ("length", "bases_lo", "bases_hi")])      # RibbitOligo
 _I4 = np.dtype("<i4")
@@ -132,6 +134,13 @@ class ProductParams(C.Structure):
     """RibbitProductParams: the exact 3' seed, the mismatches outside it, the longest product and the longest list of sites
     that record_oligo_sites and record_primer_products work with (include/ribbit_hip.h); product_params() fills one."""
     _fields_ = [(n, C.c_int32) for n in ("seed", "max_mismatches", "max_product", "max_sites")]
+
+
+class PanelParams(C.Structure):
+    """RibbitPanelParams: the cross-dimer limits, the least distance of two product sizes, the longest product two pairs of one
+    record may make between them and the members of a pool that panel_pools works with (include/ribbit_hip.h); panel_params()
+    fills one."""
+    _fields_ = [(n, C.c_int32) for n in ("max_cross_any", "max_cross_end", "size_gap", "max_cross_product", "pool_size")]
 
 
 class DebugPairing(C.Structure):
@@ -312,6 +321,11 @@ def _signatures() -> dict:
         "ribbit_primer_shortlists_choose": (st, [vp, vp, sz, P(PrimerPairParams), pvp, pvp, pvp]),
         "ribbit_pair_amplicons_merge": (st, [vp, vp, sz]),
         "ribbit_bed_marker_text": (st, [cp, sz, vp, vp, cp, vp, sz, sz, pvp, psz]),
+        "ribbit_panel_params_default": (None, [P(PanelParams)]),
+        "ribbit_hip_panel_pools": (st, [vp, vp, vp, sz, P(PanelParams), pvp, pi32]),
+        "ribbit_host_panel_pools": (st, [vp, vp, sz, P(PanelParams), pvp, pi32]),
+        "ribbit_hip_debug_panel_conflicts": (st, [vp, vp, vp, sz, P(PanelParams), vp]),
+        "ribbit_bed_panel_text": (st, [cp, sz, vp, sz, pvp, psz]),
     }
     for name in ("ribbit_hip_scan_perfect_runs", "ribbit_hip_perfect_calls", "ribbit_hip_seeds_perfect", "ribbit_hip_subst_calls",
                  "ribbit_hip_anchored_calls", "ribbit_hip_dispatch_seeds", "ribbit_hip_seed_longest_runs"):
@@ -325,7 +339,7 @@ def _signatures() -> dict:
     for name in ("ribbit_text_free", "ribbit_runs_free", "ribbit_intervals_free", "ribbit_loci_free", "ribbit_motif_classes_free",
                  "ribbit_compounds_free", "ribbit_row_purity_free", "ribbit_interruptions_free", "ribbit_nearest_free", "ribbit_composition_free",
                  "ribbit_primers_free", "ribbit_primer_pairs_free", "ribbit_products_free", "ribbit_primer_specific_free",
-                 "ribbit_primer_genome_free", "ribbit_pair_amplicons_free"):
+                 "ribbit_primer_genome_free", "ribbit_pair_amplicons_free", "ribbit_panel_free"):
         t[name] = (None, [vp])
     # the row outputs: the device form takes the handle, the host form the record's length, or its bases and their number
     length, bases = [i64], [cp, i64]
@@ -1128,6 +1142,51 @@ def bed_marker_text(bed, pairs, amplicons, names) -> bytes:
     return _text("ribbit_bed_marker_text", text_in, len(text_in), _ptr(rw), _ptr(am), pool, off.ctypes.data, len(names), len(rw))
 
 
+def panel_params(**fields) -> PanelParams:
+    """ribbit_panel_params_default with the given fields replaced, e.g. panel_params(pool_size=12, size_gap=20); the ranges are
+    checked by the calls that take it (include/ribbit_hip.h)"""
+    return _params(PanelParams, "ribbit_panel_params_default", "RibbitPanelParams", fields)
+
+
+def _panel_args(pairs, extra, params):
+    """the pairs, the extra ints (or an empty array and a null pointer) and the parameters as the C ABI takes them"""
+    rw, params = _records(pairs, PRIMER_PAIRS_DT), _params_arg(params, panel_params, PanelParams)
+    ex = np.zeros((0, 3), np.int32)
+    if extra is not None:
+        ex = np.asarray(extra)
+        if ex.size != 3 * len(rw):
+            raise ValueError(f"{len(rw)} pairs want {3 * len(rw)} extra values")
+        _all_int32(ex.reshape(-1), "an extra value is not an int32")
+        ex = np.ascontiguousarray(ex, dtype=np.int32).reshape(-1, 3)
+    return rw, ex, (ex.ctypes.data if extra is not None else None), params
+
+
+def _panel_pools(call, pairs, extra, params):
+    """-> a PANEL_DT array, one record per pair, and the number of pools"""
+    rw, ex, ex_ptr, params = _panel_args(pairs, extra, params)
+    pools = C.c_int32()
+    rows = _array(call, _ptr(rw), ex_ptr, len(rw), C.byref(params), dt=PANEL_DT, free="ribbit_panel_free", count=len(rw), tail=(C.byref(pools),))
+    return rows, int(pools.value)
+
+
+def host_panel_pools(pairs, extra=None, params: PanelParams | None = None):
+    """ribbit_host_panel_pools: the pairs of `pairs` (a PRIMER_PAIRS_DT array; only the two primers and the product are read) pooled
+    into multiplex panels: two pairs conflict when a primer of one binds a primer of the other, when their product sizes lie less
+    than size_gap apart, or when they lie on one record within max_cross_product; the pairs are taken by descending number of
+    conflicts and each goes into the first pool that has room and no member in conflict with it -> (a PANEL_DT array: the pool and
+    the conflicts of every pair, in all and by rule; the number of pools).  extra: (group, size_lo, size_hi) per pair, or None for
+    (-1, product, product).  The low-numbered pools fill first.  The contract is in include/ribbit_hip.h.  No GPU needed."""
+    return _panel_pools(_host("ribbit_host_panel_pools"), pairs, extra, params)
+
+
+def bed_panel_text(marker_text, rows) -> bytes:
+    """ribbit_bed_panel_text: the lines of `marker_text` (bed_marker_text's, pair i on line i) of the pairs that have a pool in
+    `rows` (a PANEL_DT array), each with five more columns: pool, conflicts, dimer, size, near; sorted by (pool, designed product,
+    input order)."""
+    text_in, rw = _bytes(marker_text), _records(rows, PANEL_DT)
+    return _text("ribbit_bed_panel_text", text_in, len(text_in), _ptr(rw), len(rw))
+
+
 def _record_best(call, intervals):
     iv, bases = _pairs(intervals), C.c_int64()
     rows = _array(call, _ptr(iv), len(iv), dt=_I4, free="ribbit_intervals_free", tail=(C.byref(bases),))
@@ -1839,6 +1898,19 @@ class Scanner:
         """Every primer pair typed on the loaded record, which may be any record, on the GPU (ribbit_hip_record_pair_amplicons); see
         host_record_pair_amplicons"""
         return _record_pair_amplicons(self._dev("ribbit_hip_record_pair_amplicons"), pairs, motifs, record, params)
+
+    def panel_pools(self, pairs, extra=None, params: PanelParams | None = None):
+        """The pairs pooled into multiplex panels on the GPU (ribbit_hip_panel_pools): the conflict matrix, the order and the first
+        fit; no record need be loaded; see host_panel_pools"""
+        return _panel_pools(self._dev("ribbit_hip_panel_pools"), pairs, extra, params)
+
+    def debug_panel_conflicts(self, pairs, extra=None, params: PanelParams | None = None) -> np.ndarray:
+        """The conflict matrix of the pairs as the kernel leaves it (ribbit_hip_debug_panel_conflicts; at most 8192 pairs) -> an
+        (n, (n + 63) // 64) uint64 array: bit j % 64 of word j // 64 of row i is the conflict of i and j"""
+        rw, ex, ex_ptr, params = _panel_args(pairs, extra, params)
+        words = np.zeros((len(rw), (len(rw) + 63) // 64), dtype=np.uint64)
+        _call(self._dev("ribbit_hip_debug_panel_conflicts"), _ptr(rw), ex_ptr, len(rw), C.byref(params), words.ctypes.data if words.size else None)
+        return words
 
     def record_specific_primer_pairs(self, intervals, targets, params: PrimerParams | None = None, pair_params: PrimerPairParams | None = None,
                                      product_params: ProductParams | None = None):

@@ -115,6 +115,16 @@ Duplex duplex(const std::string &a, const std::string &b) {
     return out;
 }
 
+}  // namespace
+
+void rbapi::host_duplex(const std::string &a, const std::string &b, int32_t &any, int32_t &end) {
+    const Duplex d = duplex(a, b);
+    any = d.any;
+    end = d.end;
+}
+
+namespace {
+
 int32_t hairpin(const std::string &a) {
     const int k = (int)a.size();
     int32_t best = 0;

@@ -617,6 +617,48 @@ hipError_t launch_pair_amplicons(const DevicePlanes &pl, const int32_t *pairs, i
                                  const RibbitProductParams &prm, uint8_t *work, size_t work_bytes, const AmpliconLayout &at, const int32_t *site_lists,
                                  hipStream_t stream);
 
+// panel.hip: n >= 1 primer pairs pooled into multiplex panels (api_panel.cpp: ribbit_hip_panel_pools; include/ribbit_hip.h has the
+// contract).  No record is read.  The launches, in this order, all on one stream:
+//   launch_panel_conflicts     panel_items_kernel packs every pair once (both oligos, and both reversed for the placement; the span,
+//                              the group, the size range); panel_conflicts_kernel, one wavefront per 64 rows and per chunk of column
+//                              words (grid.y): the matrix words by plain stores, the four degrees by vector atomic adds
+//   launch_panel_order         the keys ~conflicts << 32 | index (all ones without a pair) and one rocPRIM radix sort of them
+//   launch_panel_first_fit     panel_first_fit_kernel, ONE workgroup, n dependent steps; then the records and the number of pools
+// PANEL_TILE columns are one LDS tile and one matrix word; panel_chunks(n) column chunks of whole words split the words evenly:
+// chunk y holds the words [y words / chunks, (y + 1) words / chunks).
+constexpr int PANEL_TILE = 64;
+constexpr int64_t PANEL_TARGET_BLOCKS = 2048, PANEL_MIN_CHUNKS = 8;
+inline int64_t panel_words(int64_t n) { return (n + PANEL_TILE - 1) / PANEL_TILE; }
+inline int64_t panel_chunks(int64_t n) {
+    const int64_t words = panel_words(n);
+    return std::max<int64_t>(1, std::min(words, std::max(PANEL_MIN_CHUNKS, (PANEL_TARGET_BLOCKS + words - 1) / std::max<int64_t>(words, 1))));
+}
+struct PanelItem {
+    unsigned long long l, r;          // the two oligos 5' to 3', two bits a base (R: the right primer as ordered) ...
+    unsigned long long rl, rr;        // ... and their bases in reverse order, as a placement takes its partner
+    int32_t kl, kr;                   // their lengths; kl == 0: no pair
+    int32_t start, group;             // the span [start, end) = [left.start, right.start + right.length), the end in 64 bits; the record
+    int64_t end;
+    int32_t size_lo, size_hi;
+};
+static_assert(sizeof(PanelItem) == 64, "four words of 64 bits and eight ints");
+struct PanelHeader { int32_t pools, members; };      // the pools in use; the rows that have a pair
+struct PanelLayout : WorkLayout {
+    size_t items;         // n PanelItem
+    size_t matrix;        // n rows of panel_words(n) words of 64 bits
+    size_t counts;        // conflicts, dimer, size, near of every row: 4 n ints, zeroed by the launch
+    size_t keys;          // the order's keys | the keys sorted, n words of 64 bits each
+    size_t pool_of;       // the pool of every row, -1 until it has one, n ints | the pools' member counts, n ints
+    size_t header;        // the result: PanelHeader ...
+    size_t rows;          // ... and n RibbitPanelRow
+};
+PanelLayout panel_layout(int64_t n);
+// pairs: the n RibbitRowPrimerPair on the device; extra: 3 n ints on the device, or null
+hipError_t launch_panel_conflicts(const RibbitRowPrimerPair *pairs, const int32_t *extra, int64_t n, const RibbitPanelParams &prm, uint8_t *work, size_t work_bytes,
+                                  const PanelLayout &at, hipStream_t stream);
+hipError_t launch_panel_order(int64_t n, uint8_t *work, size_t work_bytes, const PanelLayout &at, hipStream_t stream);
+hipError_t launch_panel_first_fit(int64_t n, const RibbitPanelParams &prm, uint8_t *work, size_t work_bytes, const PanelLayout &at, hipStream_t stream);
+
 // profiling aid: reads nwords dwords of src with one coalesced dword per lane (known byte count)
 void launch_calib_stream_read(const uint32_t *src, int64_t nwords, uint32_t *sink, hipStream_t stream);
 

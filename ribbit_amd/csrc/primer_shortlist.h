@@ -21,7 +21,7 @@
 // 35 .. 49 of 64 lanes busy for every candidate and needs no balancing.
 // LDS per wavefront: the window's 3 words and a byte per position, a word per start, 96 words of shortlists: 3.9 KB at the
 // default flank of 200, 17.9 KB at 1000.  A workgroup has 4 wavefronts, or 2 where 4 would take more than 64 KB.
-// Included by those two .hip files only.
+// Included by those two .hip files, and by panel.hip for the oligo and the duplex alone.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -114,12 +114,15 @@ __device__ inline bool placement_fails(unsigned long long a, int ka, unsigned lo
     if (d <= 0 && run_up_from(pl.m, pl.lo) > max_end) return true;
     return hairpin_n > 0 && has_run(hairpin_part(pl, ka, d), hairpin_n);
 }
-// any(a, b) <= any_n - 1 and end(a, b) <= max_end, by one lane
-__device__ inline bool duplex_within(unsigned long long a, int ka, unsigned long long b, int kb, int any_n, int max_end) {
-    const unsigned long long rb = reversed(b, kb);
+// any(a, b) <= any_n - 1 and end(a, b) <= max_end, by one lane; rb: b's bases reversed (a caller that meets one b many times, as
+// panel.hip's lanes meet a column, reverses it once)
+__device__ inline bool duplex_within_reversed(unsigned long long a, int ka, unsigned long long rb, int kb, int any_n, int max_end) {
     for (int d = -(ka - 1); d <= kb - 1; ++d)
         if (placement_fails(a, ka, rb, kb, d, any_n, max_end, 0)) return false;
     return true;
+}
+__device__ inline bool duplex_within(unsigned long long a, int ka, unsigned long long b, int kb, int any_n, int max_end) {
+    return duplex_within_reversed(a, ka, reversed(b, kb), kb, any_n, max_end);
 }
 // the values themselves of one placement; `stem` only where a == b
 struct Runs { int32_t any, end, stem; };

@@ -229,6 +229,7 @@ int bed_pair_rows_text(const char *bed, size_t bed_len, const RibbitRowPrimerPai
 // empty one); a stored primer's oligo as letters, 5' to 3' (the right one as ordered); the admissible pairs of stored shortlists from
 // the lists alone, as host_ordered_pairs gives them from the sequence
 int check_primer_pair_params(const RibbitPrimerPairParams *p);
+void host_duplex(const std::string &a, const std::string &b, int32_t &any, int32_t &end);      // (the duplex behind ribbit_host_oligo_duplex, of letters over ACGT)
 std::vector<uint8_t> host_covered(int64_t length, const int32_t *intervals, size_t n);
 void host_ordered_pairs(const unsigned char *seq, const std::vector<uint8_t> &covered, const Flanks &f, const RibbitPrimerParams &prm, const RibbitPrimerPairParams &pair,
                         std::vector<RibbitRowPrimerPair> &ordered, RibbitRowPrimerPair &none);

@@ -70,6 +70,9 @@
 // first product and measures the repeat tract inside it (ribbit_hip_record_pair_amplicons, the record's index as label), sums in
 // record order (ribbit_pair_amplicons_merge) and writes the home records' rows in input order (ribbit_bed_marker_text):
 // write_markers.  It is no row output of the table: it has two files and no text per record.
+// --panel-bed, with both of them, pools the markers worth ordering (one product on the other assembly, of another size than
+// designed) into multiplex PCR panels: a fourth pass on the same handle takes write_markers' amplicons and lines, makes the pools on
+// the GPU with no record loaded (ribbit_hip_panel_pools) and writes the members' marker lines (ribbit_bed_panel_text): write_panel.
 // The BED rows are read back once per record, however many of the twenty-one are asked for.
 //
 // These twenty-one are the ROW OUTPUTS, and each is described once, by its entry of kOutputs below: its file option, its stage (enum
@@ -122,14 +125,14 @@ void check(int rc) {
 }
 
 // The stages of a record: the six every record goes through, then one per row output, in the order of kOutputs.
-enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, OVERLAP, BEST, CLASSES, COMPOUND, INTERRUPTIONS, NEAREST, COMPOSITION, PRIMERS, PRIMER_PAIRS, PRIMER_PRODUCTS, PRIMER_SPECIFIC, PRIMER_GENOME, MARKERS, N_STAGES };
+enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, OVERLAP, BEST, CLASSES, COMPOUND, INTERRUPTIONS, NEAREST, COMPOSITION, PRIMERS, PRIMER_PAIRS, PRIMER_PRODUCTS, PRIMER_SPECIFIC, PRIMER_GENOME, MARKERS, PANEL, N_STAGES };
 constexpr int N_FIXED_STAGES = MASK;
 // a stage's key in --timing's stage_ms_summed_over_records and its label in the RIBBIT_PROFILE line
 const struct { const char *key, *label; } kStageNames[N_STAGES] = {
     {"load", "load"}, {"perfect", "perfect"}, {"substitutions", "substitutions"}, {"anchored", "anchored"}, {"dispatch", "dispatch"},
     {"refine_and_bed", "refine+BED"}, {"mask", "mask"}, {"repeats", "repeats"}, {"loci", "loci"}, {"density", "density"}, {"overlap", "overlap"},
     {"best", "best"}, {"classes", "classes"}, {"compound", "compound"}, {"interruptions", "interruptions"}, {"nearest", "nearest"}, {"composition", "composition"}, {"primers", "primers"},
-    {"primer_pairs", "primer_pairs"}, {"primer_products", "primer_products"}, {"primer_specific", "primer_specific"}, {"primer_genome", "primer_genome"}, {"markers", "markers"}};
+    {"primer_pairs", "primer_pairs"}, {"primer_products", "primer_products"}, {"primer_specific", "primer_specific"}, {"primer_genome", "primer_genome"}, {"markers", "markers"}, {"panel", "panel"}};
 
 // wall time per stage, summed over the records (--timing, RIBBIT_PROFILE=1)
 double g_stage_ms[N_STAGES] = {};
@@ -750,6 +753,9 @@ struct Options {
     std::string timing;                           // --timing FILE: a JSON record of the run (the reference has cerr progress lines only)
     std::string other_path;                       // --overlap-with FILE: the intervals the overlap and nearest outputs compare the rows with
     std::string marker_fasta, marker_bed;         // --marker-fasta FILE --marker-bed FILE: the second assembly, and the chosen pairs typed on it
+    std::string panel_bed;                        // --panel-bed FILE: the markers worth ordering pooled into multiplex panels
+    int panel_pool_size = 8, panel_max = 16384;   // --panel-pool-size, --panel-max
+    bool panel_pool_size_given = false, panel_max_given = false;
     std::array<std::string, N_OUTPUTS> row_path;                  // the row outputs' files, as kOutputs orders them (empty: off)
     std::array<std::array<bool, MAX_QUALIFIERS>, N_OUTPUTS> qualifier_given{};
     Settings settings;
@@ -786,6 +792,17 @@ const char *kHelp =
     "                                end, bases and whole units of the longest tract of the row's motif inside the product\n"
     "                                ('.' without one). A marker is worth ordering when that difference is not 0. The other\n"
     "                                FASTA is read after the input has been read twice, on the first GPU\n"
+    "  --panel-bed arg               (ribbit-hip) with --marker-fasta and --marker-bed: also write the markers worth ordering\n"
+    "                                (exactly one product on the other assembly, of another size than designed) to this file,\n"
+    "                                pooled into multiplex PCR panels on the GPU: each marker line of --marker-bed with five more\n"
+    "                                columns: pool, conflicts, dimer, size, near. Two markers conflict when a primer of one binds\n"
+    "                                a primer of the other (ungapped run above 6, or above 4 through a 3' end), when their\n"
+    "                                expected product sizes lie less than 30 apart, or when they lie on one record within 4000\n"
+    "                                bases; markers are taken by descending conflicts and go into the first pool with room and\n"
+    "                                no conflict, so the low-numbered pools fill first. Sorted by pool, then designed product\n"
+    "  --panel-pool-size arg         (ribbit-hip) for --panel-bed: the most markers of one pool, 1 .. 65536. Default: 8\n"
+    "  --panel-max arg               (ribbit-hip) for --panel-bed: the most markers pooled, 1 .. 65536; of more, those whose size\n"
+    "                                differs most from the designed product are taken. Default: 16384\n"
     "  --masked-fasta arg            (ribbit-hip) also write the records to this FASTA file with the bases of their BED rows\n"
     "                                masked; a header keeps the record name only (the description after the first space\n"
     "                                is not kept)\n"
@@ -942,7 +959,7 @@ int parse_arguments(int argc, char **argv, Options &o) {
     static const std::map<std::string, std::string> longs = {
         {"help", "h"}, {"input-file", "i"}, {"output-file", "o"}, {"min-motif-length", "m"}, {"max-motif-length", "M"},
         {"purity", "p"}, {"min-length", "l"}, {"min-units", "U"}, {"perfect-units", "P"}, {"device", "D"}, {"jobs", "J"}, {"devices", "G"}, {"timing", "T"},
-        {"overlap-with", "W"}, {"marker-fasta", "F"}, {"marker-bed", "K"}};
+        {"overlap-with", "W"}, {"marker-fasta", "F"}, {"marker-bed", "K"}, {"panel-bed", "B"}, {"panel-pool-size", "S"}, {"panel-max", "X"}};
     bool help = false;
     for (int a = 1; a < argc; ++a) {
         std::string arg = argv[a], key, value;
@@ -1001,6 +1018,14 @@ int parse_arguments(int argc, char **argv, Options &o) {
         else if (key == "W") { if (value.empty()) die("--overlap-with wants a file name"); o.other_path = value; }
         else if (key == "F") { if (value.empty()) die("--marker-fasta wants a file name"); o.marker_fasta = value; }
         else if (key == "K") { if (value.empty()) die("--marker-bed wants a file name"); o.marker_bed = value; }
+        else if (key == "B") { if (value.empty()) die("--panel-bed wants a file name"); o.panel_bed = value; }
+        else if (key == "S" || key == "X") {
+            const char *name = key == "S" ? "--panel-pool-size" : "--panel-max";
+            if (!is_number(value) || value.size() > 5 || std::atoi(value.c_str()) < 1 || std::atoi(value.c_str()) > 65536)
+                die(std::string(name) + " wants a whole number (1 .. 65536), got '" + value + "'");
+            (key == "S" ? o.panel_pool_size : o.panel_max) = std::atoi(value.c_str());
+            (key == "S" ? o.panel_pool_size_given : o.panel_max_given) = true;
+        }
         else if (key == "G") { if (!parse_device_list(value, o.devices)) die("--devices wants a comma separated list of GPU ordinals, got '" + value + "'"); }
     }
     if (help) { std::cerr << kHelp << "\n"; return 0; }                       // ribbit.cpp:114-117
@@ -1012,6 +1037,9 @@ int parse_arguments(int argc, char **argv, Options &o) {
     if (!o.other_path.empty() && !needs_other) die("--overlap-with needs --overlap-bed or --overlap-summary");
     for (size_t k = 0; k < N_OUTPUTS; ++k)
         if (kOutputs[k].needs_other && !o.row_path[k].empty() && o.other_path.empty()) die(std::string("--") + kOutputs[k].option + " needs --overlap-with");
+    if (o.panel_bed.empty() && o.panel_pool_size_given) die("--panel-pool-size needs --panel-bed");
+    if (o.panel_bed.empty() && o.panel_max_given) die("--panel-max needs --panel-bed");
+    if (!o.panel_bed.empty() && (o.marker_fasta.empty() || o.marker_bed.empty())) die("--panel-bed needs --marker-fasta and --marker-bed");
     if (!o.marker_fasta.empty() && o.marker_bed.empty()) die("--marker-fasta needs --marker-bed");
     if (!o.marker_bed.empty() && o.marker_fasta.empty()) die("--marker-bed needs --marker-fasta");
     if (o.fasta.empty()) { std::cerr << "ERROR: Please specify an input fasta file!\n"; return 0; }   // :122-126
@@ -1224,6 +1252,7 @@ struct KeptMarkers {
     std::vector<size_t> first{0};                // ... record k's are [first[k], first[k + 1])
     std::string lines;                           // their BED lines, one behind the other
     std::vector<size_t> line_at{0};              // record k's lines are lines[line_at[k], line_at[k + 1])
+    std::vector<int32_t> record;                 // which record of the input record k is
 };
 void write_primer_genome(RibbitHandle *h, const std::string &fasta, const std::vector<std::string> &states, std::ostream *file, KeptMarkers *keep) {
     StageClock c(PRIMER_GENOME);
@@ -1290,6 +1319,7 @@ void write_primer_genome(RibbitHandle *h, const std::string &fasta, const std::v
             keep->first.push_back(keep->pairs.size());
             keep->lines.append(lines, (size_t)head[1]);
             keep->line_at.push_back(keep->lines.size());
+            keep->record.push_back((int32_t)std::min<size_t>(k, (size_t)INT32_MAX));
         }
         ribbit_primer_genome_free(pairs);
         ribbit_primer_genome_free(products);
@@ -1304,7 +1334,12 @@ void write_primer_genome(RibbitHandle *h, const std::string &fasta, const std::v
 // home record that has any, in input order.  The other FASTA is read; every record of it is loaded and nothing is scanned; all
 // kept pairs are typed on it in one call, with the record's index as label; the amplicons are summed in record order, so a pair
 // keeps its first record's product; then every home record's text is written.
-void write_markers(RibbitHandle *h, const std::string &fasta, const KeptMarkers &kept, std::ostream &file) {
+// typed: what --panel-bed's pass takes over (null: not kept): every kept pair's summed amplicon and the marker text, a line per pair
+struct TypedMarkers {
+    std::vector<RibbitRowAmplicon> amplicons;
+    std::string text;
+};
+void write_markers(RibbitHandle *h, const std::string &fasta, const KeptMarkers &kept, std::ostream &file, TypedMarkers *typed) {
     StageClock c(MARKERS);
     const size_t total = kept.pairs.size();
     if (total == 0) return;      // (no row anywhere: the file stays empty)
@@ -1352,8 +1387,65 @@ void write_markers(RibbitHandle *h, const std::string &fasta, const KeptMarkers 
         check(ribbit_bed_marker_text(kept.lines.data() + kept.line_at[k], kept.line_at[k + 1] - kept.line_at[k], &kept.pairs[from], &sum[from], names.data(), name_at.data(),
                                      name_at.size() - 1, n, &text, &len));
         file.write(text, (std::streamsize)len);
+        if (typed) typed->text.append(text, len);
         ribbit_text_free(text);
     }
+    if (typed) typed->amplicons = std::move(sum);
+}
+
+// The fourth pass, --panel-bed's, after write_markers, on the handle h.  The candidates are the kept pairs worth ordering: exactly one
+// product over the other assembly, of another size than designed.  Of more than `most`, those with the largest difference are
+// taken, among equals the lower pair penalty, then the earlier one; the taken keep the input order.  A candidate's group is its home
+// record, its size range the designed and the observed size.  The pools are made on the GPU (ribbit_hip_panel_pools, which needs
+// no record loaded) and written by ribbit_bed_panel_text over the candidates' marker lines.
+void write_panel(RibbitHandle *h, const KeptMarkers &kept, const TypedMarkers &typed, int pool_size, size_t most, std::ostream &file) {
+    StageClock c(PANEL);
+    const size_t total = kept.pairs.size();
+    if (total == 0) return;
+    std::vector<size_t> line_at{0};      // pair i's marker line is typed.text[line_at[i], line_at[i + 1]), its newline included
+    for (size_t at = 0; at < typed.text.size(); ++at)
+        if (typed.text[at] == '\n') line_at.push_back(at + 1);
+    if (line_at.size() != total + 1 || typed.amplicons.size() != total) throw PathError{"--panel-bed: the marker lines are not one per chosen pair"};
+    struct Candidate { size_t i; int64_t difference; int32_t group; };
+    std::vector<Candidate> taken;
+    for (size_t k = 0; k + 1 < kept.first.size(); ++k)
+        for (size_t i = kept.first[k]; i < kept.first[k + 1]; ++i) {
+            const RibbitRowAmplicon &a = typed.amplicons[i];
+            if (kept.pairs[i].left.start < 0 || a.products != 1) continue;
+            const int64_t difference = (int64_t)a.end - a.start - kept.pairs[i].product;
+            if (difference != 0) taken.push_back(Candidate{i, difference < 0 ? -difference : difference, kept.record[k]});
+        }
+    if (taken.size() > most) {
+        std::sort(taken.begin(), taken.end(), [&](const Candidate &a, const Candidate &b) {
+            if (a.difference != b.difference) return a.difference > b.difference;
+            if (kept.pairs[a.i].pair_penalty != kept.pairs[b.i].pair_penalty) return kept.pairs[a.i].pair_penalty < kept.pairs[b.i].pair_penalty;
+            return a.i < b.i;
+        });
+        taken.resize(most);
+        std::sort(taken.begin(), taken.end(), [](const Candidate &a, const Candidate &b) { return a.i < b.i; });
+    }
+    if (taken.empty()) return;      // (no marker worth ordering: the file stays empty)
+    std::vector<RibbitRowPrimerPair> pairs;
+    std::vector<int32_t> extra;
+    std::string lines;
+    for (const Candidate &t : taken) {
+        const RibbitRowAmplicon &a = typed.amplicons[t.i];
+        const int32_t designed = kept.pairs[t.i].product, observed = a.end - a.start;
+        pairs.push_back(kept.pairs[t.i]);
+        extra.insert(extra.end(), {t.group, std::min(designed, observed), std::max(designed, observed)});
+        lines.append(typed.text, line_at[t.i], line_at[t.i + 1] - line_at[t.i]);
+    }
+    RibbitPanelParams params;
+    ribbit_panel_params_default(&params);
+    params.pool_size = pool_size;
+    const RibbitPanelRow *rows = nullptr;
+    int32_t pools = 0;
+    check(ribbit_hip_panel_pools(h, pairs.data(), extra.data(), pairs.size(), &params, &rows, &pools));
+    char *text = nullptr;
+    size_t len = 0;
+    check(ribbit_bed_panel_text(lines.data(), lines.size(), rows, pairs.size(), &text, &len));
+    file.write(text, (std::streamsize)len);
+    ribbit_text_free(text);
 }
 
 }  // namespace
@@ -1388,6 +1480,12 @@ int main(int argc, char **argv) {
         if (!std::ifstream(opt.marker_fasta, std::ios::binary)) die("--marker-fasta: cannot open '" + opt.marker_fasta + "' for reading");
         marker_file.open(opt.marker_bed, std::ios::binary);
         if (!marker_file) die("--marker-bed: cannot open '" + opt.marker_bed + "' for writing");
+    }
+    const bool panel_on = !opt.panel_bed.empty();
+    std::ofstream panel_file;
+    if (panel_on) {
+        panel_file.open(opt.panel_bed, std::ios::binary);
+        if (!panel_file) die("--panel-bed: cannot open '" + opt.panel_bed + "' for writing");
     }
 
     const auto t_run0 = std::chrono::steady_clock::now();
@@ -1585,7 +1683,9 @@ int main(int argc, char **argv) {
                 if (reader) { ribbit_fasta_close(reader); reader = nullptr; }      // (the last record's bases are no longer needed)
                 KeptMarkers kept;
                 write_primer_genome(h, opt.fasta, genome_states, row_on[GENOME_OUTPUT] ? &row_file[GENOME_OUTPUT] : nullptr, markers_on ? &kept : nullptr);
-                if (markers_on) write_markers(h, opt.marker_fasta, kept, marker_file);
+                TypedMarkers typed;
+                if (markers_on) write_markers(h, opt.marker_fasta, kept, marker_file, panel_on ? &typed : nullptr);
+                if (panel_on) write_panel(h, kept, typed, opt.panel_pool_size, (size_t)opt.panel_max, panel_file);
             }
         } catch (const PathError &e) { failed = true; failure = e.what; }
     }
@@ -1614,6 +1714,7 @@ int main(int argc, char **argv) {
         for (int s = 0; s < N_FIXED_STAGES; ++s) tf << (s ? ", \"" : "\"") << kStageNames[s].key << "\": " << g_stage_ms[s];
         for (const Stage s : stages_on(pipe_on)) tf << ", \"" << kStageNames[s].key << "\": " << g_stage_ms[s];
         if (markers_on) tf << ", \"" << kStageNames[MARKERS].key << "\": " << g_stage_ms[MARKERS];
+        if (panel_on) tf << ", \"" << kStageNames[PANEL].key << "\": " << g_stage_ms[PANEL];
         tf << "}}\n";
     }
     if (std::getenv("RIBBIT_PROFILE")) {
@@ -1621,6 +1722,7 @@ int main(int argc, char **argv) {
         for (int s = 0; s < N_FIXED_STAGES; ++s) std::cerr << (s ? "  " : " ") << kStageNames[s].label << " " << g_stage_ms[s];
         for (const Stage s : stages_on(pipe_on)) std::cerr << "  " << kStageNames[s].label << " " << std::to_string(g_stage_ms[s]);
         if (markers_on) std::cerr << "  " << kStageNames[MARKERS].label << " " << std::to_string(g_stage_ms[MARKERS]);
+        if (panel_on) std::cerr << "  " << kStageNames[PANEL].label << " " << std::to_string(g_stage_ms[PANEL]);
         std::cerr << "\n";
     }
     size_t ignored = 0, ignored_names = 0;
