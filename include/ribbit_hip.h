@@ -1328,6 +1328,89 @@ int ribbit_hip_debug_panel_conflicts(RibbitHandle *h, const RibbitRowPrimerPair 
 int ribbit_bed_panel_text(const char *marker_text, size_t len, const RibbitPanelRow *rows, size_t n, char **text, size_t *out_len);
 
 /*
+ * ---- the chosen pairs typed on many assemblies: the genotype matrix and every marker's alleles, He and PIC -----------------
+ * What people who pick SSR markers (GMATA, Krait, QDD, MISA users) rank them by: the polymorphism over a set of individuals.
+ * A sample is one assembly; a marker's allele in a sample is the size of its one product there.  Everything is integer
+ * arithmetic.  Diploid genotype calls, null-allele estimation and alleles told apart by sequence are not part of it.
+ *   Cells:      for pair i and sample s one int32, from the RibbitRowAmplicon of the pair summed over all records of the sample
+ *               (what ribbit_pair_amplicons_merge leaves when the records are merged in file order):
+ *                 products == 1      end - start    typed; the size is > 0
+ *                 products == 0      0              absent
+ *                 products >  1      -1             several
+ *                 products == -1     -2             over (a primer with more than max_sites sites)
+ *               and 0 for a pair without a pair (left.start < 0).  ribbit_pair_amplicon_sizes writes one sample's row.
+ *   Matrix:     sample-major, cells[s n + i], 1 <= S <= RIBBIT_ALLELES_MAX_SAMPLES samples, n <= 2^24 markers.  A cell below
+ *               -2: RIBBIT_E_ARG, and the text names its index s n + i.
+ *   Per marker: designed[i], the designed product (designed[i] <= 0: the row has no pair, its record is sixteen zero ints), and
+ *               motif_length[i] >= 1, else RIBBIT_E_ARG with the index.  Over the marker's t typed cells, with every distinct
+ *               size counted c_k times, Q = sum c_k^2 and F = sum c_k^4:
+ *                 typed, absent, several, over    the cells by kind; they add up to S
+ *                 alleles                         the distinct sizes
+ *                 min_size, max_size              0 when typed == 0
+ *                 major_size, major_count         the most frequent size, of equals the least; 0, 0 when typed == 0
+ *                 same                            typed cells equal to designed
+ *                 off_step                        typed cells whose size - designed is not divisible by motif_length
+ *                 het_num = t^2 - Q               He  = het_num / t^2  (Nei's gene diversity, no t / (t - 1) correction)
+ *                 pic_num = t^4 - t^2 Q - Q^2 + F PIC = pic_num / t^4  (Botstein 1980: 1 - sum p^2 - sum_{i<j} 2 p_i^2 p_j^2)
+ *               t <= 1024, so t^4 <= 2^40: the device is compared byte for byte.
+ *   Values:     with designed = 100 and motif_length = 2 (tests/alleles_contract.py computes them from a plain statement of the
+ *               above, in fractions), as typed/absent/several/over, alleles, min, max, major size x count, same, off_step,
+ *               het_num, pic_num and the text's He and PIC:
+ *                 (100,100,100,100)           4/0/0/0  1  100  100  100x4  4  0   0    0   0.0000  0.0000
+ *                 (100,104)                   2/0/0/0  2  100  104  100x1  1  0   2    6   0.5000  0.3750
+ *                 (100,102,102,105,0,-1,-2)   4/1/1/1  3  100  105  102x2  1  1  10  142   0.6250  0.5547
+ *                 (100,102,104,106)           4/0/0/0  4  100  106  100x1  1  0  12  180   0.7500  0.7031
+ *                 (0,0,0)                     0/3/0/0  everything else 0                   .       .
+ *                 designed = -1, any cells    sixteen zeros
+ */
+#define RIBBIT_ALLELES_MAX_SAMPLES 1024
+#define RIBBIT_ALLELES_MAX_MARKERS (1 << 24)
+typedef struct {
+    int32_t typed, absent, several, over;     /* they add up to S */
+    int32_t alleles;                          /* distinct sizes among the typed */
+    int32_t min_size, max_size;               /* 0 when typed == 0 */
+    int32_t major_size, major_count;          /* the most frequent size, the least size among equals; 0, 0 when typed == 0 */
+    int32_t same;                             /* typed cells equal to designed */
+    int32_t off_step;                         /* typed cells whose size - designed is not divisible by motif_length */
+    int32_t reserved;                         /* 0 */
+    int64_t het_num;                          /* t^2 - Q */
+    int64_t pic_num;                          /* t^4 - t^2 Q - Q^2 + F */
+} RibbitRowAlleles;                           /* 64 bytes */
+/* One sample's row of cells from its n summed amplicons, as the table above (host only).  products below -1, or one product
+ * whose end is not behind its start: RIBBIT_E_ARG with the index.  A row whose pair has no pair sums to products == 0 and so to the cell 0. */
+int ribbit_pair_amplicon_sizes(const RibbitRowAmplicon *sum, size_t n, int32_t *cells);
+/* The n markers' records on the GPU (alleles.hip): a workgroup takes 16 consecutive markers, reads the samples' rows 64 bytes at a
+ * time and transposes them into LDS; one wavefront per marker counts the kinds, sorts the typed sizes (bitonic, in LDS) and
+ * reduces the runs of equal sizes.  The call needs a handle and no loaded record.  *rows is one record per marker in the order
+ * given, of handle-owned page-locked memory, valid until the handle's next call of this function or close; on an error it is
+ * NULL.  Markers go down in batches of a fixed cell budget (ribbit_hip_debug_set_specific_batch is obeyed, counting markers); the
+ * result does not depend on the batches.  n = 0 is no error.  n_samples outside 1 .. 1024, n above 2^24, a motif_length below
+ * 1, a cell below -2: RIBBIT_E_ARG with the index in the text, checked in this order before anything is launched. */
+int ribbit_hip_marker_alleles(RibbitHandle *h, const int32_t *cells, size_t n_samples, size_t n, const int32_t *designed,
+                              const int32_t *motif_lengths, const RibbitRowAlleles **rows);
+/* Host-only twin (no GPU), plain loops and std::sort: *rows malloc'ed, release with ribbit_alleles_free(). */
+int ribbit_host_marker_alleles(const int32_t *cells, size_t n_samples, size_t n, const int32_t *designed, const int32_t *motif_lengths,
+                               RibbitRowAlleles **rows);
+void ribbit_alleles_free(void *from_the_host_twin);
+/* The targets' BED rows with their alleles (host only): line i of bed_text, byte for byte, then 23 columns, each behind a tab,
+ * and a newline.  1 to 9 are the eight primer columns and the designed product as ribbit_bed_marker_text writes them; then S,
+ * typed, absent, several, over, alleles, min_size, max_size, major_size, major_count, same, off_step, He and PIC.  He and PIC
+ * have four decimals, rounded half up in integers: (num 10000 + den / 2) / den with den = typed^2 and typed^4.  With
+ * typed == 0 the columns min_size, max_size, major_size, He and PIC are ".".  A row without a pair (left.start < 0 or
+ * right.start < 0) has "." in all 23.  A bed_text that does not have n lines, a primer of fewer than 1 or more than 32 bases,
+ * n_samples outside 1 .. 1024, a record whose typed is outside 0 .. n_samples: RIBBIT_E_ARG.  *text malloc'ed, release with
+ * ribbit_text_free(). */
+int ribbit_bed_alleles_text(const char *bed_text, size_t bed_len, const RibbitRowPrimerPair *pairs, const RibbitRowAlleles *rows,
+                            size_t n_samples, size_t n, char **text, size_t *len);
+/* The genotype matrix as text (host only).  A header line: "#name", "start", "end", "motif", "designed", then the n_samples names
+ * (names[name_offsets[s] .. name_offsets[s + 1])), tab-separated.  Then one line per row in the order of bed_text: columns 1 to 4
+ * of the row, the designed product ("." when designed[i] <= 0) and one field per sample: the size of a typed cell, "." absent,
+ * "+" several, "*" over.  A bed_text that does not have n lines or holds a line that is no row, a cell below -2, n_samples
+ * outside 1 .. 1024: RIBBIT_E_ARG.  *text malloc'ed, release with ribbit_text_free(). */
+int ribbit_allele_matrix_text(const char *bed_text, size_t bed_len, const int32_t *cells, size_t n_samples, size_t n,
+                              const int32_t *designed, const char *names, const int32_t *name_offsets, char **text, size_t *len);
+
+/*
  * ---- streaming FASTA ingest ---------------------------------------------------------------------------------------
  * Replaces the reader loop of ribbit.cpp:269-280 (getline + `sequence += line` into one pageable std::string per
  * record).  The file is read in 16-MB blocks; line bodies are copied once, straight into a page-locked buffer

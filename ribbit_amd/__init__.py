@@ -38,7 +38,8 @@ __all__ = ["RibbitHipError", "ScanParams", "Scanner", "library_path", "load_libr
            "PRIMER_SHORTLISTS_DT", "PRIMER_VERDICTS_DT", "host_record_primer_shortlists", "host_record_shortlist_verdicts", "primer_verdicts_merge",
            "primer_shortlists_choose",
            "PAIR_AMPLICONS_DT", "host_record_pair_amplicons", "pair_amplicons_merge", "bed_marker_text",
-           "PANEL_DT", "PanelParams", "panel_params", "host_panel_pools", "bed_panel_text"]
+           "PANEL_DT", "PanelParams", "panel_params", "host_panel_pools", "bed_panel_text",
+           "ALLELES_DT", "pair_amplicon_sizes", "host_marker_alleles", "bed_alleles_text", "allele_matrix_text"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -80,6 +81,8 @@ PRIMER_VERDICTS_DT = np.dtype([(n, "<u8") for n in ("admissible", "over", "other
 PAIR_AMPLICONS_DT = np.dtype([(n, "<i4") for n in ("left_forward", "left_reverse", "right_forward", "right_reverse", "products", "record", "start", "end",
                                                     "forward_of", "reverse_of", "inner_start", "inner_end", "tract_start", "tract_end", "tract_strand",
                                                     "reserved")])      # RibbitRowAmplicon
+ALLELES_DT = np.dtype([(n, "<i4") for n in ("typed", "absent", "several", "over", "alleles", "min_size", "max_size", "major_size", "major_count", "same", "off_step",
+                                             "reserved")] + [("het_num", "<i8"), ("pic_num", "<i8")])      # RibbitRowAlleles
 PANEL_DT = np.dtype([(n, "<i4") for n in ("pool", "conflicts", "dimer", "size", "near", "reserved0", "reserved1", "reserved2")])      # RibbitPanelRow
 OLIGO_SITES_DT = np.dtype([(n, "<i4") for n in ("forward", "reverse", "forward_at", "reverse_at")])      # RibbitOligoSites
 _OLIGO_DT = np.dtype([(n, "<i4") for n in ("length", "bases_lo", "bases_hi")])      # RibbitOligo
@@ -326,6 +329,11 @@ def _signatures() -> dict:
         "ribbit_host_panel_pools": (st, [vp, vp, sz, P(PanelParams), pvp, pi32]),
         "ribbit_hip_debug_panel_conflicts": (st, [vp, vp, vp, sz, P(PanelParams), vp]),
         "ribbit_bed_panel_text": (st, [cp, sz, vp, sz, pvp, psz]),
+        "ribbit_pair_amplicon_sizes": (st, [vp, sz, vp]),
+        "ribbit_hip_marker_alleles": (st, [vp, vp, sz, sz, vp, vp, pvp]),
+        "ribbit_host_marker_alleles": (st, [vp, sz, sz, vp, vp, pvp]),
+        "ribbit_bed_alleles_text": (st, [cp, sz, vp, vp, sz, sz, pvp, psz]),
+        "ribbit_allele_matrix_text": (st, [cp, sz, vp, sz, sz, vp, cp, vp, pvp, psz]),
     }
     for name in ("ribbit_hip_scan_perfect_runs", "ribbit_hip_perfect_calls", "ribbit_hip_seeds_perfect", "ribbit_hip_subst_calls",
                  "ribbit_hip_anchored_calls", "ribbit_hip_dispatch_seeds", "ribbit_hip_seed_longest_runs"):
@@ -339,7 +347,7 @@ def _signatures() -> dict:
     for name in ("ribbit_text_free", "ribbit_runs_free", "ribbit_intervals_free", "ribbit_loci_free", "ribbit_motif_classes_free",
                  "ribbit_compounds_free", "ribbit_row_purity_free", "ribbit_interruptions_free", "ribbit_nearest_free", "ribbit_composition_free",
                  "ribbit_primers_free", "ribbit_primer_pairs_free", "ribbit_products_free", "ribbit_primer_specific_free",
-                 "ribbit_primer_genome_free", "ribbit_pair_amplicons_free", "ribbit_panel_free"):
+                 "ribbit_primer_genome_free", "ribbit_pair_amplicons_free", "ribbit_panel_free", "ribbit_alleles_free"):
         t[name] = (None, [vp])
     # the row outputs: the device form takes the handle, the host form the record's length, or its bases and their number
     length, bases = [i64], [cp, i64]
@@ -1187,6 +1195,69 @@ def bed_panel_text(marker_text, rows) -> bytes:
     return _text("ribbit_bed_panel_text", text_in, len(text_in), _ptr(rw), len(rw))
 
 
+def pair_amplicon_sizes(amplicons) -> np.ndarray:
+    """ribbit_pair_amplicon_sizes: one sample's row of the genotype matrix from its summed amplicons (a PAIR_AMPLICONS_DT array,
+    record_pair_amplicons merged over the sample's records) -> int32 cells: the size of the one product, 0 absent, -1 several
+    products, -2 a primer with too many sites."""
+    am = _records(amplicons, PAIR_AMPLICONS_DT)
+    cells = np.zeros(len(am), np.int32)
+    _call("ribbit_pair_amplicon_sizes", _ptr(am), len(am), _ptr(cells))
+    return cells
+
+
+def _alleles_args(cells, designed, motif_lengths):
+    """the sample-major matrix (S rows of n cells), the designed products and the motif lengths as the C ABI takes them"""
+    cl = np.asarray(cells)
+    if cl.ndim != 2:
+        raise ValueError("the cells are a matrix, one row per sample")
+    ds, ml = np.asarray(designed).reshape(-1), np.asarray(motif_lengths).reshape(-1)
+    if len(ds) != cl.shape[1] or len(ml) != cl.shape[1]:
+        raise ValueError(f"{cl.shape[1]} markers, {len(ds)} designed products and {len(ml)} motif lengths")
+    for a, what in ((cl.reshape(-1), "a cell"), (ds, "a designed product"), (ml, "a motif length")):
+        if a.dtype != np.int32:      # (a matrix of a billion cells is not walked to learn what its type says)
+            _all_int32(a, f"{what} is not an int32")
+    return np.ascontiguousarray(cl, dtype=np.int32), np.ascontiguousarray(ds, dtype=np.int32), np.ascontiguousarray(ml, dtype=np.int32)
+
+
+def _marker_alleles(call, cells, designed, motif_lengths) -> np.ndarray:
+    cl, ds, ml = _alleles_args(cells, designed, motif_lengths)
+    n = cl.shape[1]
+    return _array(call, cl.ctypes.data if cl.size else None, cl.shape[0], n, _ptr(ds), _ptr(ml), dt=ALLELES_DT, free="ribbit_alleles_free", count=n)
+
+
+def host_marker_alleles(cells, designed, motif_lengths) -> np.ndarray:
+    """ribbit_host_marker_alleles: every marker's alleles over the samples.  cells: the genotype matrix, one row per sample (1 ..
+    1024) and one column per marker (pair_amplicon_sizes makes a row); designed: the designed product of every marker, <= 0 for a
+    row without a pair; motif_lengths: the length of its motif -> an ALLELES_DT array: the cells by kind, the distinct sizes, the
+    least, the largest and the most frequent one, the cells equal to the designed size, those off the motif's step, and the
+    numerators of He (over typed^2) and PIC (over typed^4).  The contract is in include/ribbit_hip.h.  No GPU needed."""
+    return _marker_alleles(_host("ribbit_host_marker_alleles"), cells, designed, motif_lengths)
+
+
+def bed_alleles_text(bed, pairs, rows, n_samples: int) -> bytes:
+    """ribbit_bed_alleles_text: the lines of `bed` (the targets' BED rows, target i on line i), each with 23 more columns: the eight
+    primer columns and the designed product of row i of `pairs`, the number of samples and row i of `rows` (an ALLELES_DT array)
+    with He and PIC to four decimals."""
+    text_in, rw, al = _bytes(bed), _records(pairs, PRIMER_PAIRS_DT), _records(rows, ALLELES_DT)
+    if len(al) != len(rw):
+        raise ValueError(f"{len(rw)} pairs and {len(al)} records of alleles")
+    return _text("ribbit_bed_alleles_text", text_in, len(text_in), _ptr(rw), _ptr(al), int(n_samples), len(rw))
+
+
+def allele_matrix_text(bed, cells, designed, names) -> bytes:
+    """ribbit_allele_matrix_text: a header line, then for every line of `bed` its first four columns, the designed product and one
+    field per sample of `cells` (as host_marker_alleles takes them): the size, "." absent, "+" several, "*" over.  names: the
+    samples' names, one per row of `cells`."""
+    text_in = _bytes(bed)
+    cl, ds, _ = _alleles_args(cells, designed, designed)
+    names = [_name(n) for n in names]
+    if len(names) != cl.shape[0]:
+        raise ValueError(f"{cl.shape[0]} samples and {len(names)} names")
+    pool, off = _pool(names, None)
+    off = np.ascontiguousarray(off, dtype=np.int32)
+    return _text("ribbit_allele_matrix_text", text_in, len(text_in), cl.ctypes.data if cl.size else None, cl.shape[0], cl.shape[1], _ptr(ds), pool, off.ctypes.data)
+
+
 def _record_best(call, intervals):
     iv, bases = _pairs(intervals), C.c_int64()
     rows = _array(call, _ptr(iv), len(iv), dt=_I4, free="ribbit_intervals_free", tail=(C.byref(bases),))
@@ -1903,6 +1974,11 @@ class Scanner:
         """The pairs pooled into multiplex panels on the GPU (ribbit_hip_panel_pools): the conflict matrix, the order and the first
         fit; no record need be loaded; see host_panel_pools"""
         return _panel_pools(self._dev("ribbit_hip_panel_pools"), pairs, extra, params)
+
+    def marker_alleles(self, cells, designed, motif_lengths) -> np.ndarray:
+        """Every marker's alleles over the samples on the GPU (ribbit_hip_marker_alleles): one wavefront per marker, the typed sizes
+        sorted in LDS; no record need be loaded; see host_marker_alleles"""
+        return _marker_alleles(self._dev("ribbit_hip_marker_alleles"), cells, designed, motif_lengths)
 
     def debug_panel_conflicts(self, pairs, extra=None, params: PanelParams | None = None) -> np.ndarray:
         """The conflict matrix of the pairs as the kernel leaves it (ribbit_hip_debug_panel_conflicts; at most 8192 pairs) -> an

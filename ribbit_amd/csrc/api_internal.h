@@ -27,7 +27,8 @@
 //   api_primer_genome.cpp    a target's two shortlists as they leave their record, their pairs judged on any loaded record (primer_specific.hip, through search_sites), the host twins, the sum over records, the choice
 //   api_amplicons.cpp        every chosen pair typed on any loaded record: its first product and the repeat tract inside it (amplicons.hip, through search_sites), its host twin, the sum over records, the text
 //   api_panel.cpp            primer pairs pooled into multiplex panels: the conflict matrix, the order and the first fit (panel.hip), which read no record; its host twin, the text
-// The last seventeen are the row outputs: their buffers are the handle's RowBufs `rows`, where all device work of a call is carved from
+//   api_alleles.cpp          the chosen pairs typed on many assemblies: a sample's cells, every marker's alleles, He and PIC over the sample-major matrix (alleles.hip), which reads no record; its host twin, both texts
+// The last eighteen are the row outputs: their buffers are the handle's RowBufs `rows`, where all device work of a call is carved from
 // one buffer by the layout its .hip file states (kernels.h); best, classes, compound, interruptions, nearest, primers and primer pairs stage their inputs through stage_down, what their host
 // sides share is below (hand_out, clipped_sorted_rows), what their kernels share is row_kernels.h, and the BED text they read and
 // write (the row format, the reader in pieces, the writer in pieces) is
@@ -507,6 +508,8 @@ struct RibbitHandle {
         PinnedBuf<uint8_t> h_amplicons;
         // the pairs pooled into panels (api_panel.cpp): the header, then one RibbitPanelRow per pair on its way up
         PinnedBuf<uint8_t> h_panel;
+        // the markers' alleles over many samples (api_alleles.cpp): one RibbitRowAlleles per marker on its way up
+        PinnedBuf<uint8_t> h_alleles;
         // the blocks' base counts | their prefix, which belongs to the record (rec.base_prefix_valid, api_composition.cpp)
         DevBuf<rb::BaseSums> d_comp_sums;
         size_t rep_budget = 0;           // text budget of one batch of repeat sequences in bytes (0: REPEAT_TEXT_BUDGET)

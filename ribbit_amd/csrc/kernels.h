@@ -659,6 +659,25 @@ hipError_t launch_panel_conflicts(const RibbitRowPrimerPair *pairs, const int32_
 hipError_t launch_panel_order(int64_t n, uint8_t *work, size_t work_bytes, const PanelLayout &at, hipStream_t stream);
 hipError_t launch_panel_first_fit(int64_t n, const RibbitPanelParams &prm, uint8_t *work, size_t work_bytes, const PanelLayout &at, hipStream_t stream);
 
+// alleles.hip: the records of m >= 1 markers over n_samples samples (api_alleles.cpp: ribbit_hip_marker_alleles; include/ribbit_hip.h
+// has the contract).  No record is read, and the work buffer holds only the result: the inputs are read where stage_down put them.
+//   launch_marker_alleles      marker_alleles_kernel: a workgroup of four wavefronts per ALLELE_RUN consecutive markers, their cells
+//                              transposed into LDS, one wavefront per marker
+// cells: n_samples rows of `pitch` ints on the device, pitch >= m, row s holding the m markers' cells of sample s; designed and
+// motif_lengths: m ints each.  alleles_keys(S): the sort's keys per marker, a power of two >= 64.
+constexpr int ALLELE_RUN = 16;
+inline int alleles_keys(int64_t n_samples) {
+    int keys = 64;
+    while (keys < n_samples) keys <<= 1;
+    return keys;
+}
+struct AllelesLayout : WorkLayout {
+    size_t rows;          // the result, m RibbitRowAlleles
+};
+AllelesLayout alleles_layout(int64_t m);
+hipError_t launch_marker_alleles(const int32_t *cells, int64_t pitch, int64_t n_samples, int64_t m, const int32_t *designed, const int32_t *motif_lengths, uint8_t *work,
+                                 size_t work_bytes, const AllelesLayout &at, hipStream_t stream);
+
 // profiling aid: reads nwords dwords of src with one coalesced dword per lane (known byte count)
 void launch_calib_stream_read(const uint32_t *src, int64_t nwords, uint32_t *sink, hipStream_t stream);
 

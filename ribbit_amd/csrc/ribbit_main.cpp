@@ -73,6 +73,10 @@
 // --panel-bed, with both of them, pools the markers worth ordering (one product on the other assembly, of another size than
 // designed) into multiplex PCR panels: a fourth pass on the same handle takes write_markers' amplicons and lines, makes the pools on
 // the GPU with no record loaded (ribbit_hip_panel_pools) and writes the members' marker lines (ribbit_bed_panel_text): write_panel.
+// --population-list with --allele-bed or --allele-matrix types the same chosen pairs on every sample of the list, one assembly after
+// the other by the loop that --marker-bed's pass runs on its one (type_on_fasta), keeps one int32 per sample and pair
+// (ribbit_pair_amplicon_sizes), counts every marker's alleles on the GPU in one call (ribbit_hip_marker_alleles) and writes the two
+// texts (ribbit_bed_alleles_text, ribbit_allele_matrix_text): write_population, the last pass.
 // The BED rows are read back once per record, however many of the twenty-one are asked for.
 //
 // These twenty-one are the ROW OUTPUTS, and each is described once, by its entry of kOutputs below: its file option, its stage (enum
@@ -125,14 +129,14 @@ void check(int rc) {
 }
 
 // The stages of a record: the six every record goes through, then one per row output, in the order of kOutputs.
-enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, OVERLAP, BEST, CLASSES, COMPOUND, INTERRUPTIONS, NEAREST, COMPOSITION, PRIMERS, PRIMER_PAIRS, PRIMER_PRODUCTS, PRIMER_SPECIFIC, PRIMER_GENOME, MARKERS, PANEL, N_STAGES };
+enum Stage { LOAD, PERFECT, SUBSTITUTIONS, ANCHORED, DISPATCH, REFINE_BED, MASK, REPEATS, LOCI, DENSITY, OVERLAP, BEST, CLASSES, COMPOUND, INTERRUPTIONS, NEAREST, COMPOSITION, PRIMERS, PRIMER_PAIRS, PRIMER_PRODUCTS, PRIMER_SPECIFIC, PRIMER_GENOME, MARKERS, PANEL, POPULATION, N_STAGES };
 constexpr int N_FIXED_STAGES = MASK;
 // a stage's key in --timing's stage_ms_summed_over_records and its label in the RIBBIT_PROFILE line
 const struct { const char *key, *label; } kStageNames[N_STAGES] = {
     {"load", "load"}, {"perfect", "perfect"}, {"substitutions", "substitutions"}, {"anchored", "anchored"}, {"dispatch", "dispatch"},
     {"refine_and_bed", "refine+BED"}, {"mask", "mask"}, {"repeats", "repeats"}, {"loci", "loci"}, {"density", "density"}, {"overlap", "overlap"},
     {"best", "best"}, {"classes", "classes"}, {"compound", "compound"}, {"interruptions", "interruptions"}, {"nearest", "nearest"}, {"composition", "composition"}, {"primers", "primers"},
-    {"primer_pairs", "primer_pairs"}, {"primer_products", "primer_products"}, {"primer_specific", "primer_specific"}, {"primer_genome", "primer_genome"}, {"markers", "markers"}, {"panel", "panel"}};
+    {"primer_pairs", "primer_pairs"}, {"primer_products", "primer_products"}, {"primer_specific", "primer_specific"}, {"primer_genome", "primer_genome"}, {"markers", "markers"}, {"panel", "panel"}, {"population", "population"}};
 
 // wall time per stage, summed over the records (--timing, RIBBIT_PROFILE=1)
 double g_stage_ms[N_STAGES] = {};
@@ -756,6 +760,8 @@ struct Options {
     std::string panel_bed;                        // --panel-bed FILE: the markers worth ordering pooled into multiplex panels
     int panel_pool_size = 8, panel_max = 16384;   // --panel-pool-size, --panel-max
     bool panel_pool_size_given = false, panel_max_given = false;
+    std::string population_list;                  // --population-list FILE: the samples (name<TAB>path of a FASTA) the chosen pairs are typed on
+    std::string allele_bed, allele_matrix;        // --allele-bed FILE, --allele-matrix FILE: every marker's alleles over the samples, and the genotype matrix
     std::array<std::string, N_OUTPUTS> row_path;                  // the row outputs' files, as kOutputs orders them (empty: off)
     std::array<std::array<bool, MAX_QUALIFIERS>, N_OUTPUTS> qualifier_given{};
     Settings settings;
@@ -803,6 +809,23 @@ const char *kHelp =
     "  --panel-pool-size arg         (ribbit-hip) for --panel-bed: the most markers of one pool, 1 .. 65536. Default: 8\n"
     "  --panel-max arg               (ribbit-hip) for --panel-bed: the most markers pooled, 1 .. 65536; of more, those whose size\n"
     "                                differs most from the designed product are taken. Default: 16384\n"
+    "  --population-list arg         (ribbit-hip) the samples that --allele-bed and --allele-matrix type --primer-genome-bed's chosen\n"
+    "                                pairs on: a file with one sample per line, name<TAB>path of its FASTA (1 .. 1024 samples,\n"
+    "                                the names unique; empty lines and lines starting with # are skipped). The input itself is a\n"
+    "                                sample only if the list names it. The samples are read one after the other, in list order,\n"
+    "                                after every other pass, on the first GPU; one int32 is kept per sample and row\n"
+    "  --allele-bed arg              (ribbit-hip) with --population-list: also write the rows of --primer-genome-bed (chosen with\n"
+    "                                --primer-genome-flank, whether or not that file is asked for) to this file with 23 columns:\n"
+    "                                the eight primer columns and the designed product; then, over the samples, counted on the\n"
+    "                                GPU: samples, typed (exactly one product), absent, several, over (a primer with more than 64\n"
+    "                                sites), alleles (distinct product sizes), the least, the largest and the most frequent size\n"
+    "                                with its count, the samples of the designed size, those whose size is off the motif's step,\n"
+    "                                the expected heterozygosity He = 1 - sum p^2 and the polymorphism information content PIC\n"
+    "                                (Botstein 1980), four decimals ('.' where no sample is typed)\n"
+    "  --allele-matrix arg           (ribbit-hip) with --population-list: also write the genotype matrix to this file: a header\n"
+    "                                line (#name, start, end, motif, designed, the samples' names), then per row its first four\n"
+    "                                columns, the designed product and per sample the product's size, '.' absent, '+' several,\n"
+    "                                '*' over\n"
     "  --masked-fasta arg            (ribbit-hip) also write the records to this FASTA file with the bases of their BED rows\n"
     "                                masked; a header keeps the record name only (the description after the first space\n"
     "                                is not kept)\n"
@@ -959,7 +982,8 @@ int parse_arguments(int argc, char **argv, Options &o) {
     static const std::map<std::string, std::string> longs = {
         {"help", "h"}, {"input-file", "i"}, {"output-file", "o"}, {"min-motif-length", "m"}, {"max-motif-length", "M"},
         {"purity", "p"}, {"min-length", "l"}, {"min-units", "U"}, {"perfect-units", "P"}, {"device", "D"}, {"jobs", "J"}, {"devices", "G"}, {"timing", "T"},
-        {"overlap-with", "W"}, {"marker-fasta", "F"}, {"marker-bed", "K"}, {"panel-bed", "B"}, {"panel-pool-size", "S"}, {"panel-max", "X"}};
+        {"overlap-with", "W"}, {"marker-fasta", "F"}, {"marker-bed", "K"}, {"panel-bed", "B"}, {"panel-pool-size", "S"}, {"panel-max", "X"},
+        {"population-list", "L"}, {"allele-bed", "A"}, {"allele-matrix", "Y"}};
     bool help = false;
     for (int a = 1; a < argc; ++a) {
         std::string arg = argv[a], key, value;
@@ -1019,6 +1043,9 @@ int parse_arguments(int argc, char **argv, Options &o) {
         else if (key == "F") { if (value.empty()) die("--marker-fasta wants a file name"); o.marker_fasta = value; }
         else if (key == "K") { if (value.empty()) die("--marker-bed wants a file name"); o.marker_bed = value; }
         else if (key == "B") { if (value.empty()) die("--panel-bed wants a file name"); o.panel_bed = value; }
+        else if (key == "L") { if (value.empty()) die("--population-list wants a file name"); o.population_list = value; }
+        else if (key == "A") { if (value.empty()) die("--allele-bed wants a file name"); o.allele_bed = value; }
+        else if (key == "Y") { if (value.empty()) die("--allele-matrix wants a file name"); o.allele_matrix = value; }
         else if (key == "S" || key == "X") {
             const char *name = key == "S" ? "--panel-pool-size" : "--panel-max";
             if (!is_number(value) || value.size() > 5 || std::atoi(value.c_str()) < 1 || std::atoi(value.c_str()) > 65536)
@@ -1042,6 +1069,9 @@ int parse_arguments(int argc, char **argv, Options &o) {
     if (!o.panel_bed.empty() && (o.marker_fasta.empty() || o.marker_bed.empty())) die("--panel-bed needs --marker-fasta and --marker-bed");
     if (!o.marker_fasta.empty() && o.marker_bed.empty()) die("--marker-fasta needs --marker-bed");
     if (!o.marker_bed.empty() && o.marker_fasta.empty()) die("--marker-bed needs --marker-fasta");
+    if (!o.population_list.empty() && o.allele_bed.empty() && o.allele_matrix.empty()) die("--population-list needs --allele-bed or --allele-matrix");
+    if (!o.allele_bed.empty() && o.population_list.empty()) die("--allele-bed needs --population-list");
+    if (!o.allele_matrix.empty() && o.population_list.empty()) die("--allele-matrix needs --population-list");
     if (o.fasta.empty()) { std::cerr << "ERROR: Please specify an input fasta file!\n"; return 0; }   // :122-126
     return 1;
 }
@@ -1330,45 +1360,49 @@ void write_primer_genome(RibbitHandle *h, const std::string &fasta, const std::v
     }
 }
 
-// The third pass, --marker-bed's, after write_primer_genome, on the handle h: `kept` holds the chosen pairs and the lines of every
-// home record that has any, in input order.  The other FASTA is read; every record of it is loaded and nothing is scanned; all
-// kept pairs are typed on it in one call, with the record's index as label; the amplicons are summed in record order, so a pair
-// keeps its first record's product; then every home record's text is written.
-// typed: what --panel-bed's pass takes over (null: not kept): every kept pair's summed amplicon and the marker text, a line per pair
-struct TypedMarkers {
-    std::vector<RibbitRowAmplicon> amplicons;
-    std::string text;
+// the column-4 motifs of the kept lines, one per chosen pair (`option` words the refusal)
+struct KeptMotifs {
+    char *pool = nullptr;
+    int32_t *offsets = nullptr;
+    KeptMotifs(const KeptMarkers &kept, const char *option) {
+        size_t n_motifs = 0;
+        check(ribbit_bed_motifs(kept.lines.data(), kept.lines.size(), &pool, &offsets, &n_motifs));
+        if (n_motifs != kept.pairs.size()) {
+            release();
+            throw PathError{std::string(option) + ": the kept lines are not one per chosen pair"};
+        }
+    }
+    KeptMotifs(const KeptMotifs &) = delete;
+    KeptMotifs &operator=(const KeptMotifs &) = delete;
+    ~KeptMotifs() { release(); }
+    void release() { ribbit_text_free(pool); ribbit_intervals_free(offsets); pool = nullptr; offsets = nullptr; }
 };
-void write_markers(RibbitHandle *h, const std::string &fasta, const KeptMarkers &kept, std::ostream &file, TypedMarkers *typed) {
-    StageClock c(MARKERS);
+
+// All kept pairs typed on one assembly, on the handle h: the FASTA is read; every record of it is loaded and nothing is scanned; the
+// pairs are typed on it in one call, with the record's index as label; the amplicons are summed in record order into `sum` (one per
+// pair), so a pair keeps its first record's product.  names, name_at: the records' names one behind the other (null: not kept).
+// What --marker-bed's pass does with the other assembly and --population-list's with every sample; `option` words the refusals.
+void type_on_fasta(RibbitHandle *h, const std::string &fasta, const char *option, const KeptMarkers &kept, const KeptMotifs &motifs, std::vector<RibbitRowAmplicon> &sum,
+                   std::string *names, std::vector<int32_t> *name_at) {
     const size_t total = kept.pairs.size();
-    if (total == 0) return;      // (no row anywhere: the file stays empty)
-    struct Motifs {
-        char *pool = nullptr;
-        int32_t *offsets = nullptr;
-        ~Motifs() { ribbit_text_free(pool); ribbit_intervals_free(offsets); }
-    } motifs;
-    size_t n_motifs = 0;
-    check(ribbit_bed_motifs(kept.lines.data(), kept.lines.size(), &motifs.pool, &motifs.offsets, &n_motifs));
-    if (n_motifs != total) throw PathError{"--marker-bed: the kept lines are not one per chosen pair"};
     RibbitProductParams product;
     ribbit_product_params_default(&product);
-    std::vector<RibbitRowAmplicon> sum(total);
-    std::string names;
-    std::vector<int32_t> name_at{0};
     RibbitFastaReader *reader = nullptr;
-    if (ribbit_fasta_open(fasta.c_str(), 1, &reader) != RIBBIT_OK) throw PathError{std::string("--marker-fasta: ") + ribbit_fasta_last_error()};
+    if (ribbit_fasta_open(fasta.c_str(), 1, &reader) != RIBBIT_OK) throw PathError{std::string(option) + ": " + ribbit_fasta_last_error()};
     struct Close { RibbitFastaReader *r; ~Close() { ribbit_fasta_close(r); } } close{reader};
     for (size_t k = 0;; ++k) {
         const char *name = "", *bases = nullptr;
         int64_t length = 0;
         int is_last = 1;
         const int got = ribbit_fasta_next(reader, &name, &bases, &length, &is_last);
-        if (got < 0) throw PathError{std::string("--marker-fasta: ") + ribbit_fasta_last_error()};
+        if (got < 0) throw PathError{std::string(option) + ": " + ribbit_fasta_last_error()};
         if (got == 0) break;
-        names += name;
-        if (names.size() > (size_t)INT32_MAX || k >= (size_t)INT32_MAX) throw PathError{"--marker-fasta: the records' names are 2^31 bytes or more"};
-        name_at.push_back((int32_t)names.size());
+        if (names) {
+            *names += name;
+            if (names->size() > (size_t)INT32_MAX) throw PathError{std::string(option) + ": the records' names are 2^31 bytes or more"};
+            name_at->push_back((int32_t)names->size());
+        }
+        if (k >= (size_t)INT32_MAX) throw PathError{std::string(option) + ": the records' names are 2^31 bytes or more"};
         const RibbitRowAmplicon *rows = nullptr;
         int rc = ribbit_hip_load_record_pinned(h, bases, length);
         if (rc == RIBBIT_OK) rc = ribbit_hip_record_pair_amplicons(h, kept.pairs.data(), total, motifs.pool, motifs.offsets, (int32_t)k, &product, &rows);
@@ -1380,6 +1414,25 @@ void write_markers(RibbitHandle *h, const std::string &fasta, const KeptMarkers 
         check(rc);
         if (is_last) break;
     }
+}
+
+// The third pass, --marker-bed's, after write_primer_genome, on the handle h: `kept` holds the chosen pairs and the lines of every
+// home record that has any, in input order.  All kept pairs are typed on the other FASTA (type_on_fasta); then every home record's
+// text is written.
+// typed: what --panel-bed's pass takes over (null: not kept): every kept pair's summed amplicon and the marker text, a line per pair
+struct TypedMarkers {
+    std::vector<RibbitRowAmplicon> amplicons;
+    std::string text;
+};
+void write_markers(RibbitHandle *h, const std::string &fasta, const KeptMarkers &kept, std::ostream &file, TypedMarkers *typed) {
+    StageClock c(MARKERS);
+    const size_t total = kept.pairs.size();
+    if (total == 0) return;      // (no row anywhere: the file stays empty)
+    const KeptMotifs motifs(kept, "--marker-bed");
+    std::vector<RibbitRowAmplicon> sum(total);
+    std::string names;
+    std::vector<int32_t> name_at{0};
+    type_on_fasta(h, fasta, "--marker-fasta", kept, motifs, sum, &names, &name_at);
     for (size_t k = 0; k + 1 < kept.first.size(); ++k) {
         const size_t from = kept.first[k], n = kept.first[k + 1] - from;
         char *text = nullptr;
@@ -1448,6 +1501,79 @@ void write_panel(RibbitHandle *h, const KeptMarkers &kept, const TypedMarkers &t
     ribbit_text_free(text);
 }
 
+// --population-list: one sample per line, name<TAB>path of its FASTA; empty lines and lines that start with # are skipped.  Read, and
+// every path opened, before any file is made and any GPU is touched; a line that will not do ends the run and names itself.
+struct Sample { std::string name, path; };
+std::vector<Sample> read_population_list(const std::string &path) {
+    std::ifstream in(path, std::ios::binary);
+    if (!in) die("--population-list: cannot open '" + path + "' for reading");
+    std::vector<Sample> samples;
+    std::map<std::string, size_t> line_of;
+    std::string line;
+    for (size_t k = 1; std::getline(in, line); ++k) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty() || line[0] == '#') continue;
+        const std::string where = "--population-list: line " + std::to_string(k) + " of '" + path + "' ";
+        const size_t tab = line.find('\t');
+        if (tab == std::string::npos) die(where + "is not name<TAB>path");
+        if (line.find('\t', tab + 1) != std::string::npos) die(where + "has more than one tab (no name and no path may hold one)");
+        Sample sample{line.substr(0, tab), line.substr(tab + 1)};
+        if (sample.name.empty()) die(where + "has an empty name");
+        if (sample.path.empty()) die(where + "has an empty path");
+        if (samples.size() == RIBBIT_ALLELES_MAX_SAMPLES) die(where + "is sample " + std::to_string(RIBBIT_ALLELES_MAX_SAMPLES + 1) + " (at most " + std::to_string(RIBBIT_ALLELES_MAX_SAMPLES) + ")");
+        const auto seen = line_of.emplace(sample.name, k);
+        if (!seen.second) die(where + "names '" + sample.name + "' again (line " + std::to_string(seen.first->second) + " has it)");
+        if (!std::ifstream(sample.path, std::ios::binary)) die(where + "names '" + sample.path + "', which cannot be opened for reading");
+        samples.push_back(std::move(sample));
+    }
+    if (samples.empty()) die("--population-list: '" + path + "' names no sample");
+    return samples;
+}
+
+// The last pass, --population-list's, after write_primer_genome (and write_markers and write_panel, where they run), on the handle
+// h.  Every sample is typed in list order (type_on_fasta) and leaves one int32 per kept pair (ribbit_pair_amplicon_sizes): the
+// genotype matrix, sample-major, in host memory.  One call counts every marker's alleles on the GPU (ribbit_hip_marker_alleles,
+// which needs no record loaded); then the files are written.
+void write_population(RibbitHandle *h, const std::vector<Sample> &samples, const KeptMarkers &kept, std::ostream *allele_file, std::ostream *matrix_file) {
+    StageClock c(POPULATION);
+    const size_t total = kept.pairs.size(), S = samples.size();
+    std::string names;
+    std::vector<int32_t> name_at{0};
+    for (const Sample &sample : samples) {
+        names += sample.name;
+        if (names.size() > (size_t)INT32_MAX) throw PathError{"--population-list: the samples' names are 2^31 bytes or more"};
+        name_at.push_back((int32_t)names.size());
+    }
+    std::vector<int32_t> cells(S * total), designed(total), motif_lengths(total);
+    const RibbitRowAlleles *rows = nullptr;
+    if (total > 0) {
+        const KeptMotifs motifs(kept, "--population-list");
+        for (size_t i = 0; i < total; ++i) {
+            designed[i] = kept.pairs[i].left.start < 0 || kept.pairs[i].right.start < 0 ? 0 : kept.pairs[i].product;
+            motif_lengths[i] = motifs.offsets[i + 1] - motifs.offsets[i];
+        }
+        std::vector<RibbitRowAmplicon> sum(total);
+        for (size_t s = 0; s < S; ++s) {
+            std::fill(sum.begin(), sum.end(), RibbitRowAmplicon{});
+            type_on_fasta(h, samples[s].path, "--population-list", kept, motifs, sum, nullptr, nullptr);
+            check(ribbit_pair_amplicon_sizes(sum.data(), total, &cells[s * total]));
+        }
+        check(ribbit_hip_marker_alleles(h, cells.data(), S, total, designed.data(), motif_lengths.data(), &rows));
+    }
+    char *text = nullptr;
+    size_t len = 0;
+    if (allele_file && total > 0) {      // (no row anywhere: the file stays empty)
+        check(ribbit_bed_alleles_text(kept.lines.data(), kept.lines.size(), kept.pairs.data(), rows, S, total, &text, &len));
+        allele_file->write(text, (std::streamsize)len);
+        ribbit_text_free(text);
+    }
+    if (matrix_file) {      // (the header at least)
+        check(ribbit_allele_matrix_text(kept.lines.data(), kept.lines.size(), cells.data(), S, total, designed.data(), names.data(), name_at.data(), &text, &len));
+        matrix_file->write(text, (std::streamsize)len);
+        ribbit_text_free(text);
+    }
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -1459,6 +1585,9 @@ int main(int argc, char **argv) {
         read_other_bed(opt.other_path, other);
         opt.settings.other = &other;
     }
+    const bool population_on = !opt.population_list.empty();
+    std::vector<Sample> samples;      // (read, and every path tried, before any file is made and any GPU is touched)
+    if (population_on) samples = read_population_list(opt.population_list);
     std::ofstream file;
     if (!opt.out.empty()) file.open(opt.out);
     std::ostream &out = opt.out.empty() ? std::cerr : file;                   // ribbit.cpp:199-205
@@ -1471,10 +1600,11 @@ int main(int argc, char **argv) {
         if (!row_file[k]) die(std::string("--") + kOutputs[k].option + ": cannot open '" + opt.row_path[k] + "' for writing");
     }
 
-    // --marker-bed needs --primer-genome-bed's selection, whether or not that file is written: pipe_on says what the records produce
+    // --marker-bed and --population-list need --primer-genome-bed's selection, whether or not that file is written: pipe_on says what
+    // the records produce
     const bool markers_on = !opt.marker_bed.empty();
     std::array<bool, N_OUTPUTS> pipe_on = row_on;
-    pipe_on[GENOME_OUTPUT] = row_on[GENOME_OUTPUT] || markers_on;
+    pipe_on[GENOME_OUTPUT] = row_on[GENOME_OUTPUT] || markers_on || population_on;
     std::ofstream marker_file;
     if (markers_on) {
         if (!std::ifstream(opt.marker_fasta, std::ios::binary)) die("--marker-fasta: cannot open '" + opt.marker_fasta + "' for reading");
@@ -1486,6 +1616,15 @@ int main(int argc, char **argv) {
     if (panel_on) {
         panel_file.open(opt.panel_bed, std::ios::binary);
         if (!panel_file) die("--panel-bed: cannot open '" + opt.panel_bed + "' for writing");
+    }
+    std::ofstream allele_file, matrix_file;
+    if (!opt.allele_bed.empty()) {
+        allele_file.open(opt.allele_bed, std::ios::binary);
+        if (!allele_file) die("--allele-bed: cannot open '" + opt.allele_bed + "' for writing");
+    }
+    if (!opt.allele_matrix.empty()) {
+        matrix_file.open(opt.allele_matrix, std::ios::binary);
+        if (!matrix_file) die("--allele-matrix: cannot open '" + opt.allele_matrix + "' for writing");
     }
 
     const auto t_run0 = std::chrono::steady_clock::now();
@@ -1682,10 +1821,11 @@ int main(int argc, char **argv) {
                 if (real_last) genome_states.push_back(std::move(last_state));
                 if (reader) { ribbit_fasta_close(reader); reader = nullptr; }      // (the last record's bases are no longer needed)
                 KeptMarkers kept;
-                write_primer_genome(h, opt.fasta, genome_states, row_on[GENOME_OUTPUT] ? &row_file[GENOME_OUTPUT] : nullptr, markers_on ? &kept : nullptr);
+                write_primer_genome(h, opt.fasta, genome_states, row_on[GENOME_OUTPUT] ? &row_file[GENOME_OUTPUT] : nullptr, markers_on || population_on ? &kept : nullptr);
                 TypedMarkers typed;
                 if (markers_on) write_markers(h, opt.marker_fasta, kept, marker_file, panel_on ? &typed : nullptr);
                 if (panel_on) write_panel(h, kept, typed, opt.panel_pool_size, (size_t)opt.panel_max, panel_file);
+                if (population_on) write_population(h, samples, kept, opt.allele_bed.empty() ? nullptr : &allele_file, opt.allele_matrix.empty() ? nullptr : &matrix_file);
             }
         } catch (const PathError &e) { failed = true; failure = e.what; }
     }
@@ -1715,6 +1855,7 @@ int main(int argc, char **argv) {
         for (const Stage s : stages_on(pipe_on)) tf << ", \"" << kStageNames[s].key << "\": " << g_stage_ms[s];
         if (markers_on) tf << ", \"" << kStageNames[MARKERS].key << "\": " << g_stage_ms[MARKERS];
         if (panel_on) tf << ", \"" << kStageNames[PANEL].key << "\": " << g_stage_ms[PANEL];
+        if (population_on) tf << ", \"" << kStageNames[POPULATION].key << "\": " << g_stage_ms[POPULATION];
         tf << "}}\n";
     }
     if (std::getenv("RIBBIT_PROFILE")) {
@@ -1723,6 +1864,7 @@ int main(int argc, char **argv) {
         for (const Stage s : stages_on(pipe_on)) std::cerr << "  " << kStageNames[s].label << " " << std::to_string(g_stage_ms[s]);
         if (markers_on) std::cerr << "  " << kStageNames[MARKERS].label << " " << std::to_string(g_stage_ms[MARKERS]);
         if (panel_on) std::cerr << "  " << kStageNames[PANEL].label << " " << std::to_string(g_stage_ms[PANEL]);
+        if (population_on) std::cerr << "  " << kStageNames[POPULATION].label << " " << std::to_string(g_stage_ms[POPULATION]);
         std::cerr << "\n";
     }
     size_t ignored = 0, ignored_names = 0;
